@@ -25,10 +25,19 @@ value = ratings processed by all ranks / max-over-ranks time.  Ratings, schedule
 and factors are resident in HBM before the timed region; the timed region
 contains the training passes only (no RMSE pass, no host<->device copies).
 
-Rank 0 prints ONE JSON line.  Extra objects: "roofline" (algorithmic bytes of
-the dominant kernel / its average launch duration vs the 8 TB/s HBM peak) and
-"cpu_baseline" (the oracle's multithreaded CPU path on the host cores, N = 1
-only -- a reported baseline, not the target).
+Rank 0 prints ONE JSON line.  Extra object: "roofline" (algorithmic bytes of
+the dominant kernel / its average launch duration vs the 8 TB/s HBM peak).
+
+A plain run sets up, warms up, times the steps and prints the line.  Everything
+else it can measure runs with --full only (N = 1): "end_to_end" (train() from
+host arrays on a fresh handle) and "cpu_baseline" (the oracle's multithreaded
+CPU path on the host cores -- a reported baseline, not the target; skipped
+with --no-cpu-baseline).
+
+--dump-outputs DIR (N = 1) writes what the last timed step left behind -- the
+factors a caller of train() receives -- as DIR/P.npy and DIR/Q.npy (float32;
+a fixed, seeded sample of their rows where all of them would exceed 64 MB).
+The inputs are seeded, so two builds can be compared file for file.
 """
 import argparse
 import json
@@ -44,6 +53,7 @@ import numpy as np  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
 LR, LAM, SEED = 0.01, 0.05, 3
+DUMP_LIMIT_BYTES = 60_000_000  # --dump-outputs: the data of all files together (under 64 MB with the .npy headers)
 # generator revision of the named workloads (synth.py WORKLOADS): bumped whenever a calibration changes, so that
 # two bench lines of the same workload name are comparable only if this matches (r1: cfg2 head 40 K; r2: 67.9 K)
 WORKLOAD_REV = 2
@@ -174,6 +184,23 @@ def read_traffic(workload, k, nnz):
     return None, None
 
 
+def dump_outputs(out_dir, arrays):
+    """Writes each 2-d array as out_dir/<name>.npy in float32.  If they do not fit DUMP_LIMIT_BYTES together, every
+    array keeps the same share of its rows -- a fixed, seeded sample, so runs stay comparable -- and the indices of the
+    rows kept go to <name>_rows.npy (float64: exact for any row index)."""
+    os.makedirs(out_dir, exist_ok=True)
+    full = sum(a.shape[0] * a.shape[1] * 4 for a in arrays.values())
+    share = 1.0 if full <= DUMP_LIMIT_BYTES else DUMP_LIMIT_BYTES / sum(a.shape[0] * (a.shape[1] * 4 + 8) for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.asarray(a, np.float32)
+        if share < 1.0:
+            rows = np.sort(np.random.default_rng(SEED).choice(a.shape[0], int(a.shape[0] * share), replace=False))
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    log(f"wrote {', '.join(arrays)} to {out_dir}" + ("" if share == 1.0 else f" (a seeded sample of {share:.1%} of the rows)"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -190,7 +217,11 @@ def main():
                     "above 100 M ratings, host otherwise")
     ap.add_argument("--blocks", type=int, default=0)
     ap.add_argument("--waves", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="N = 1: also time train() end to end on a fresh handle and the CPU "
+                    "baselines (a plain run only times the steps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="N = 1: write the factors the last timed step left (P, Q) to "
+                    "DIR/<name>.npy, float32, at most 64 MB in all (a seeded sample of the rows beyond that)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--parts-per-rank", type=int, default=0, help="DSGD: item partitions a rank holds at a time (0 = 1)")
     ap.add_argument("--plan-crit", type=float, default=0.0, help="DSGD item plan: 0 = longest-processing-time-first (default), "
@@ -207,6 +238,10 @@ def main():
                     "driver's shared-memory rehearsal transport (RCCL refuses two ranks on one GPU), round launches (the "
                     "ranks' persistent kernels would not be co-resident).  Not a measurement.")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus > 1 or args.emulate_world > 1 or args.selftest_native_ring > 1):
+        ap.error("--dump-outputs: the single-GPU run only (--gpus 1, no --emulate-world or --selftest-native-ring)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` as the driver calls it: this process is the launcher
@@ -346,6 +381,9 @@ def main():
         wall_s = time.perf_counter() - t_wall0
         elapsed_s = max(wall_s, dev_ms / 1e3)
         rmse1 = m.rmse()
+        if args.dump_outputs:
+            P, Q = m.get_factors()
+            dump_outputs(args.dump_outputs, {"P": P, "Q": Q})
     elif native:
         # the ring under the C-ABI (csrc/dsgd.cpp): RCCL send / recv on its own stream.  It comes up on every rank or the
         # bench fails -- a line produced by another transport would not measure the product
@@ -495,7 +533,7 @@ def main():
         out["ring"] = ring_stats
     if emulation is not None:
         out["emulation"] = emulation
-    if world == 1 and not emu and not selftest:
+    if args.full and world == 1 and not emu and not selftest:
         # What a caller of train(u, i, r, 10) with HOST arrays sees end to end on a fresh handle: hashing and
         # uploading the triples, building the schedule (device ingest + device packer), seeding the factors,
         # 10 epochs AND the RMSE pass after each (the Java train() returns per-epoch RMSE).  Never `value`.
@@ -511,7 +549,7 @@ def main():
             "value": nnz * 10 / e2e[1], "unit": "updates/s", "epochs": 10, "seconds": e2e[1], "first_call_seconds": e2e[0],
             "includes": "host arrays -> set_ratings (hash, upload, device ingest + packer) -> init_factors -> 10 x (epoch + RMSE pass)",
         }
-    if world == 1 and not emu and not selftest and not args.no_cpu_baseline:
+    if args.full and world == 1 and not emu and not selftest and not args.no_cpu_baseline:
         log("timing the CPU baselines (oracle, multithreaded: the checker's arithmetic, then the textbook loop) ...")
         out["cpu_baseline"] = cpu_baseline(w, m)
     m.close()

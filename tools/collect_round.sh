@@ -15,16 +15,16 @@ prof)
     timeout -k 10 400 tools/prof.sh k256 --workload cfg4_powerlaw --scale 0.02 > $OUT/prof_k256.log 2>&1
     ;;
 bench)
-    timeout -k 10 200 python3 bench.py > $OUT/bench_default_with_cpu_baseline.json 2> $OUT/bench_default.err
+    timeout -k 10 200 python3 bench.py --full > $OUT/bench_default_with_cpu_baseline.json 2> $OUT/bench_default.err
     for w in cfg2_uniform cfg2_zipf cfg2_r1; do
-        timeout -k 10 200 python3 bench.py --no-cpu-baseline --workload $w > $OUT/bench_$w.json 2>> $OUT/bench.err
+        timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --workload $w > $OUT/bench_$w.json 2>> $OUT/bench.err
     done
-    timeout -k 10 200 python3 bench.py --no-cpu-baseline --workload cfg3_netflix --scale 0.2 > $OUT/bench_cfg3_netflix_0.2.json 2>> $OUT/bench.err
-    timeout -k 10 200 python3 bench.py --no-cpu-baseline --workload cfg4_powerlaw --scale 0.02 > $OUT/bench_cfg4_powerlaw_0.02.json 2>> $OUT/bench.err
+    timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --workload cfg3_netflix --scale 0.2 > $OUT/bench_cfg3_netflix_0.2.json 2>> $OUT/bench.err
+    timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --workload cfg4_powerlaw --scale 0.02 > $OUT/bench_cfg4_powerlaw_0.02.json 2>> $OUT/bench.err
     for n in 2 4 8; do
         timeout -k 10 200 python3 bench.py --no-cpu-baseline --emulate-world $n > $OUT/bench_emu$n.json 2>> $OUT/bench.err
     done
-    timeout -k 10 300 python3 bench.py --no-cpu-baseline --workload cfg3_netflix > $OUT/bench_cfg3_netflix_1.0.json 2>> $OUT/bench.err
+    timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --workload cfg3_netflix > $OUT/bench_cfg3_netflix_1.0.json 2>> $OUT/bench.err
     timeout -k 10 120 python3 tools/phase_profile.py cfg2_ml20m 1.0 > $OUT/phase_profile_solo.log 2>&1
     timeout -k 10 120 python3 tools/phase_profile.py cfg2_ml20m 1.0 0 0 16 > $OUT/phase_profile_nosolo.log 2>&1
     MFSGD_EMU=8 timeout -k 10 120 python3 tools/phase_profile.py cfg2_ml20m 1.0 > $OUT/phase_profile_emu8_partition.log 2>&1
