@@ -349,7 +349,7 @@ void block_ranks(const int32_t* bin, int32_t n, int B, std::vector<int32_t>& ran
     for (int b = 0; b < B; ++b) max_rank = std::max(max_rank, next[(size_t)b]);
 }
 
-int pack_count_cb(void* vctx, const PackRequest& q, std::vector<PackCellInfo>& info, std::vector<SubDesc>& subs) {
+int pack_count_cb(void* vctx, const PackRequest& q, std::vector<PackCellInfo>& info) {
     Ctx* c = static_cast<Ctx*>(vctx);
     if (!c->d_sorted || !c->d_bptr || c->host_u != q.u || c->host_i != q.i || c->n != q.n) return -1;
     const int64_t n_cells = (int64_t)q.B * q.B, WW = (int64_t)q.W * q.W;
@@ -436,12 +436,6 @@ int pack_count_cb(void* vctx, const PackRequest& q, std::vector<PackCellInfo>& i
     }
     reserve_huge(info, (size_t)n_cells);
     info.resize((size_t)n_cells);
-    if (q.want_subs) {
-        reserve_huge(subs, (size_t)(n_cells * WW));
-        subs.resize((size_t)(n_cells * WW));
-    } else {
-        subs.clear();
-    }
     for (;;) {
         ING_CHK(launch_pack(a, n_cells, (hipStream_t)0));
         ING_CHK(hipMemcpy(info.data(), c->d_info, sizeof(PackCellInfo) * (size_t)n_cells, hipMemcpyDeviceToHost));
@@ -450,7 +444,6 @@ int pack_count_cb(void* vctx, const PackRequest& q, std::vector<PackCellInfo>& i
         if (!more_rows || a.max_rows >= rows_full) break;
         a.max_rows = rows_full;
     }
-    if (q.want_subs) ING_CHK(hipMemcpy(subs.data(), c->d_subs, sizeof(SubDesc) * (size_t)(n_cells * WW), hipMemcpyDeviceToHost));
     c->args = a;
     c->n_cells = n_cells;
     c->rows_full = rows_full;
@@ -505,18 +498,16 @@ bool upload_parts(Ctx* c, int64_t n_parts, const uint32_t* sorted, int64_t n_sor
 }
 
 int pack_count_parts_cb(void* vctx, int64_t n_parts, const uint32_t* sorted, int64_t n_sorted, const int64_t* cptr,
-                        PackCellInfo* info, SubDesc* subs) {
+                        PackCellInfo* info) {
     Ctx* c = static_cast<Ctx*>(vctx);
     if (!c->d_info || n_parts < 0) return -1;
     if (n_parts == 0) return 0;
-    const int64_t WW = (int64_t)c->args.W * c->args.W;
     PartList pl;
     PackArgs a{};
     if (!upload_parts(c, n_parts, sorted, n_sorted, cptr, pl, a)) return -1;
     int rc = -1;
     ING_CHK(launch_pack(a, n_parts, (hipStream_t)0));
     ING_CHK(hipMemcpy(info, pl.d_info, sizeof(PackCellInfo) * (size_t)n_parts, hipMemcpyDeviceToHost));
-    if (subs) ING_CHK(hipMemcpy(subs, pl.d_subs, sizeof(SubDesc) * (size_t)(n_parts * WW), hipMemcpyDeviceToHost));
     rc = 0;
 fail:
     pl.release();
@@ -541,23 +532,19 @@ __global__ void __launch_bounds__(256) table_scatter_kernel(SubDesc* __restrict_
 }
 
 int emit_common(Ctx* c, const uint32_t* row_off, const uint32_t* ent_off, const int64_t* ord_off, int64_t n_rows,
-                int64_t n_steps, const MixedPieces* host, DevicePacked* out, const PartsToEmit* parts = nullptr,
-                int64_t n_descs = 0) {
+                int64_t n_steps, int64_t n_descs, DevicePacked* out, const PartsToEmit* parts = nullptr) {
     if (!c->d_info || !out) return -1;
     PackArgs a = c->args;
-    SubDesc* d_fin = nullptr;  // the final sub-cell table (n_descs > 0)
+    SubDesc* d_fin = nullptr;  // the final sub-cell table
     long long* d_pdesc = nullptr;
     uint32_t *d_ro = nullptr, *d_eo = nullptr, *d_rows = nullptr;
     long long *d_oo = nullptr, *d_order = nullptr;
     Entry* d_ent = nullptr;
-    void* staged[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     const size_t nc = (size_t)c->n_cells;
     const bool one_pass = c->d_sent != nullptr;  // the COUNT pass wrote what it packed: move it, do not pack again
+    const size_t WWs = (size_t)a.W * a.W;
     std::vector<long long> oo(ord_off, ord_off + nc);
-    auto stage = [&](int slot, const void* p, size_t bytes) -> bool {
-        if (bytes == 0) return true;
-        return hipMalloc(&staged[slot], bytes) == hipSuccess && hipMemcpy(staged[slot], p, bytes, hipMemcpyHostToDevice) == hipSuccess;
-    };
+    if (n_descs < c->n_cells) return -1;
     ING_CHK(hipMalloc(&d_ro, 4 * nc));
     ING_CHK(hipMalloc(&d_eo, 4 * nc));
     ING_CHK(hipMalloc(&d_oo, 8 * nc));
@@ -579,15 +566,11 @@ int emit_common(Ctx* c, const uint32_t* row_off, const uint32_t* ent_off, const 
     a.rows = d_rows;
     a.entries = d_ent;
     a.order = d_order;
-    if (n_descs > 0) {
-        // the final sub-cell table: the cells' tables as the COUNT pass left them (a cell that is cut gets its first
-        // chunk's below), zeros for the descriptors nothing is written to and for the two padding records
-        const size_t WWs = (size_t)a.W * a.W;
-        if (n_descs < c->n_cells) goto fail;
-        ING_CHK(hipMalloc(&d_fin, sizeof(SubDesc) * ((size_t)n_descs * WWs + 2)));
-        ING_CHK(hipMemsetAsync(d_fin + (size_t)c->n_cells * WWs, 0, sizeof(SubDesc) * ((size_t)(n_descs - c->n_cells) * WWs + 2), (hipStream_t)0));
-        ING_CHK(hipMemcpyAsync(d_fin, c->d_subs, sizeof(SubDesc) * (size_t)c->n_cells * WWs, hipMemcpyDeviceToDevice, (hipStream_t)0));
-    }
+    // the final sub-cell table: the cells' tables as the COUNT pass left them (a cell that is cut gets its first chunk's
+    // below), zeros for the descriptors nothing is written to and for the two padding records
+    ING_CHK(hipMalloc(&d_fin, sizeof(SubDesc) * ((size_t)n_descs * WWs + 2)));
+    ING_CHK(hipMemsetAsync(d_fin + (size_t)c->n_cells * WWs, 0, sizeof(SubDesc) * ((size_t)(n_descs - c->n_cells) * WWs + 2), (hipStream_t)0));
+    ING_CHK(hipMemcpyAsync(d_fin, c->d_subs, sizeof(SubDesc) * (size_t)c->n_cells * WWs, hipMemcpyDeviceToDevice, (hipStream_t)0));
     if (one_pass) {
         a.emit = 2;
         ING_CHK(launch_compact(a, c->n_cells, c->d_srows, c->d_sent, (hipStream_t)0));
@@ -618,7 +601,7 @@ int emit_common(Ctx* c, const uint32_t* row_off, const uint32_t* ent_off, const 
             pa.entries = d_ent;
             pa.order = d_order;
             ok = launch_pack(pa, parts->n_parts, (hipStream_t)0) == hipSuccess;
-            if (ok && d_fin) {
+            if (ok) {
                 // (the EMIT pass does not touch the table the COUNT pass of the same list left in pl.d_subs)
                 ok = parts->desc != nullptr && hipMalloc(&d_pdesc, 8 * np) == hipSuccess &&
                      hipMemcpy(d_pdesc, parts->desc, 8 * np, hipMemcpyHostToDevice) == hipSuccess;
@@ -640,30 +623,14 @@ int emit_common(Ctx* c, const uint32_t* row_off, const uint32_t* ent_off, const 
             goto fail;
         }
     }
-    if (host) {
-        // what the host packed: three staging arrays and their segment lists, then one copy kernel each
-        if (!stage(0, host->rows.data(), host->rows.size() * 4) || !stage(1, host->seg_rows.data(), host->seg_rows.size() * sizeof(MixedSegment)) ||
-            !stage(2, host->entries.data(), host->entries.size() * sizeof(Entry)) ||
-            !stage(3, host->seg_entries.data(), host->seg_entries.size() * sizeof(MixedSegment)) ||
-            !stage(4, host->order.data(), host->order.size() * 8) ||
-            !stage(5, host->seg_order.data(), host->seg_order.size() * sizeof(MixedSegment))) {
-            (void)hipGetLastError();
-            goto fail;
-        }
-        ING_CHK(launch_scatter(d_rows, staged[0], static_cast<const MixedSegment*>(staged[1]), (long long)host->seg_rows.size(), 4, (hipStream_t)0));
-        ING_CHK(launch_scatter(d_ent, staged[2], static_cast<const MixedSegment*>(staged[3]), (long long)host->seg_entries.size(), 16, (hipStream_t)0));
-        ING_CHK(launch_scatter(d_order, staged[4], static_cast<const MixedSegment*>(staged[5]), (long long)host->seg_order.size(), 8, (hipStream_t)0));
-    }
     ING_CHK(hipDeviceSynchronize());
     (void)hipFree(d_ro); (void)hipFree(d_eo); (void)hipFree(d_oo);
-    for (void* p : staged)
-        if (p) (void)hipFree(p);
     if (d_pdesc) (void)hipFree(d_pdesc);
     out->rows = d_rows;
     out->entries = d_ent;
     out->order = d_order;
     out->subs = d_fin;
-    out->n_subs = d_fin ? n_descs * (int64_t)a.W * a.W + 2 : 0;
+    out->n_subs = n_descs * (int64_t)WWs + 2;
     out->release = release_cb;
     drop_pack_state(c);
     return 0;
@@ -676,19 +643,13 @@ fail:
     if (d_order) (void)hipFree(d_order);
     if (d_fin) (void)hipFree(d_fin);
     if (d_pdesc) (void)hipFree(d_pdesc);
-    for (void* p : staged)
-        if (p) (void)hipFree(p);
     return -1;
 }
 
 int pack_emit_cb(void* vctx, const uint32_t* row_off, const uint32_t* ent_off, const int64_t* ord_off, int64_t n_rows,
-                 int64_t n_steps, int64_t n_descs, DevicePacked* out) {
-    return emit_common(static_cast<Ctx*>(vctx), row_off, ent_off, ord_off, n_rows, n_steps, nullptr, out, nullptr, n_descs);
-}
-
-int pack_emit_mixed_cb(void* vctx, const uint32_t* row_off, const uint32_t* ent_off, const int64_t* ord_off, int64_t n_rows,
-                       int64_t n_steps, const MixedPieces& host, DevicePacked* out) {
-    return emit_common(static_cast<Ctx*>(vctx), row_off, ent_off, ord_off, n_rows, n_steps, &host, out);
+                 int64_t n_steps, DevicePacked* out) {
+    Ctx* c = static_cast<Ctx*>(vctx);
+    return emit_common(c, row_off, ent_off, ord_off, n_rows, n_steps, c->n_cells, out);
 }
 
 int pack_emit_parts_cb(void* vctx, const uint32_t* row_off, const uint32_t* ent_off, const int64_t* ord_off, int64_t n_rows,
@@ -704,7 +665,7 @@ int pack_emit_parts_cb(void* vctx, const uint32_t* row_off, const uint32_t* ent_
     pe.row_off = p_row_off;
     pe.ent_off = p_ent_off;
     pe.ord_off = p_ord_off;
-    return emit_common(static_cast<Ctx*>(vctx), row_off, ent_off, ord_off, n_rows, n_steps, nullptr, out, &pe, n_descs);
+    return emit_common(static_cast<Ctx*>(vctx), row_off, ent_off, ord_off, n_rows, n_steps, n_descs, out, &pe);
 }
 
 int download_cb(const DevicePacked& d, uint32_t* rows, int64_t n_rows, Entry* entries, int64_t n_entries, int64_t* order,
@@ -726,7 +687,7 @@ int download_raw_cb(const void* dev, void* host, size_t bytes) {
     return 0;
 }
 
-const DeviceIngestExt kExt = {bucket_dev_cb, fetch_sorted_cb, fetch_sorted32_cb, fetch_sorted_ranges_cb, pack_count_cb, pack_emit_cb, pack_emit_mixed_cb,
+const DeviceIngestExt kExt = {bucket_dev_cb, fetch_sorted32_cb, fetch_sorted_ranges_cb, pack_count_cb, pack_emit_cb,
                               pack_count_parts_cb, pack_emit_parts_cb, download_cb, download_raw_cb};
 
 }  // namespace

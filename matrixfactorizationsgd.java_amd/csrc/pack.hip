@@ -17,8 +17,9 @@
 // turns them into offsets and checks that every cell fits the LDS image as a single chunk), then
 // EMIT (rows, entries, order written at their final places).  Anything this kernel cannot hold
 // (a cell with more ratings or rows than its LDS arrays, 16-bit counters that would overflow)
-// is reported, and the caller falls back to the host packer -- which also does the chunking of
-// cells too large for the training kernel's LDS image.
+// is reported.  The caller then cuts the cells too large for the training kernel's LDS image and
+// has this kernel pack the chunks as lists (schedule.cpp, route 3), or, when no cell's size is
+// known yet, falls back to the host packer.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -679,24 +680,6 @@ hipError_t launch_compact(const PackArgs& a, long long n_cells, const uint32_t* 
 
 // steps / rows of the scratch arrays of the one-pass mode for n ratings in n_cells cells of W*W sub-cells
 size_t pack_scratch_steps(long long n, long long n_cells, int W) { return 2 * (size_t)n + (size_t)n_cells * (size_t)(W * W * kPackSlack + 2); }
-
-// dst[seg.dst + x] = src[seg.src + x] for x < seg.n, elements of `elem` bytes (a multiple of 4): one workgroup
-// per segment.  Places the pieces the host packed in a mixed build.
-__global__ void __launch_bounds__(256) scatter_kernel(unsigned* __restrict__ dst, const unsigned* __restrict__ src,
-                                                      const MixedSegment* __restrict__ segs, const int words_per_elem) {
-    const MixedSegment s = segs[blockIdx.x];
-    unsigned* d = dst + s.dst * words_per_elem;
-    const unsigned* q = src + s.src * words_per_elem;
-    const unsigned long long nw = s.n * (unsigned long long)words_per_elem;
-    for (unsigned long long x = threadIdx.x; x < nw; x += 256) d[x] = q[x];
-}
-
-hipError_t launch_scatter(void* dst, const void* src, const MixedSegment* segs, long long n_segs, int elem_bytes, hipStream_t st) {
-    if (n_segs <= 0) return hipSuccess;
-    hipLaunchKernelGGL(scatter_kernel, dim3((unsigned)n_segs), dim3(256), 0, st, static_cast<unsigned*>(dst),
-                       static_cast<const unsigned*>(src), segs, elem_bytes / 4);
-    return hipGetLastError();
-}
 
 size_t pack_lds_bytes(const PackArgs& a) {
     const size_t M = (size_t)a.max_m, R = (size_t)a.max_rows;

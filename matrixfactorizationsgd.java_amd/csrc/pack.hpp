@@ -37,9 +37,6 @@ struct PackArgs {
     long long* order;        // EMIT out
 };
 
-struct MixedSegment;
-// one workgroup per segment: dst[seg.dst + x] = src[seg.src + x], x < seg.n, elements of elem_bytes (multiple of 4)
-hipError_t launch_scatter(void* dst, const void* src, const MixedSegment* segs, long long n_segs, int elem_bytes, hipStream_t st);
 size_t pack_lds_bytes(const PackArgs& a);
 hipError_t launch_pack(const PackArgs& a, long long n_cells, hipStream_t st);
 // one-pass mode: a.rows / a.entries / a.row_off / a.ent_off FINAL, a.info / a.subs from the pass, scratch arrays as written by it

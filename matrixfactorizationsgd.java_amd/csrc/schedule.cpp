@@ -1,4 +1,10 @@
 // schedule.cpp -- see schedule.hpp.  Host only; no HIP calls.
+//
+// build_schedule takes one of three routes (the comment above it says when):
+//  1. host: the host packs every cell, cuts those too large for the LDS image and assembles the schedule;
+//  2. device, whole cells: every cell fits as one chunk and the device packs them all;
+//  3. device with cuts: the cells that fit stay on the device, the host decides how the others are cut, and the device
+//     packs the chunks and assembles the schedule.
 #include "schedule.hpp"
 #include "hugepages.hpp"
 
@@ -220,11 +226,10 @@ struct CellOut {
     int64_t n_order = 0;
     bool dev = false;       // packed by the device packer: rows / entries / order are not here
     // [r3] a CHUNK the device packs (a part of a cell that was cut): its ratings are the range [part_lo, part_lo +
-    // n_order) of build_schedule's `part_ratings` (indices into the caller's arrays, in the cell's bucket order, the
-    // sub-cell of each beside it) -- the packing kernel takes the range as a cell of its own; its sub-cell table is
-    // entry part_tab of `part_subs`
+    // n_order) of Builder::part_ratings (indices into the caller's arrays, in the cell's bucket order, the sub-cell of
+    // each beside it) -- the packing kernel takes the range as a cell of its own
     bool dev_part = false;
-    int64_t part_lo = -1, part_tab = -1;
+    int64_t part_lo = -1;
     mutable int64_t desc = -1;  // its chunk descriptor, once placed
 };
 
@@ -238,6 +243,10 @@ struct Scratch {
     std::vector<int32_t> cand;
     std::vector<uint64_t> keys;
     std::vector<std::pair<int32_t, uint16_t>> top;
+    std::vector<int32_t> ordv;         // pack_subcell: candidates by priority
+    std::vector<RawRat> sel;           // the ratings of the cell being packed or cut on the host
+    std::vector<uint32_t> hold_idx;    // the device cut: the right half of a part, while the left closes up
+    std::vector<uint16_t> hold_sb;
 };
 
 
@@ -311,7 +320,7 @@ void pack_subcell(const Rat* rs, int n, int G, int Lg, int nrows, const Hyper& h
         if (remaining <= G) {
             for (int c = 0; c < remaining && ntake < G; ++c) try_take(c);
         } else {
-            static thread_local std::vector<int32_t> ordv;
+            std::vector<int32_t>& ordv = sc.ordv;
             ordv.resize((size_t)remaining);
             std::iota(ordv.begin(), ordv.end(), 0);
             const int want = std::min(remaining, 4 * G + 8);
@@ -482,37 +491,244 @@ void pack_solo(const Rat* rs, int n, int G, int Lg, int nrows, const Hyper& hy, 
     for (int x = n + 2; x < (int)n_units * G; ++x) entries.push_back(words(zero_slots, 0xFFFFFFFFu, 0u, 0u));
 }
 
-}  // namespace
+// Runs body(scratch, lo, hi) over [0, n_items) in pieces of `grain`, claimed in order by up to `nthreads` threads (the
+// caller's among them).  Every worker has a Scratch of its own, freed before the call returns.  An exception thrown by
+// the body stops the claiming and is rethrown here once every worker is back: none leaves its thread.
+template <class Body>
+void parallel_for(size_t n_items, size_t grain, int nthreads, const Body& body) {
+    if (n_items == 0) return;
+    std::atomic<size_t> next{0};
+    std::atomic<bool> stop{false};
+    std::exception_ptr failed;
+    std::mutex mu;
+    auto work = [&]() {
+        try {
+            Scratch sc;
+            while (!stop.load()) {
+                const size_t lo = next.fetch_add(grain);
+                if (lo >= n_items) break;
+                body(sc, lo, std::min(n_items, lo + grain));
+            }
+        } catch (...) {
+            std::lock_guard<std::mutex> lk(mu);
+            if (!failed) failed = std::current_exception();
+            stop = true;
+        }
+    };
+    const size_t pieces = (n_items + grain - 1) / grain;
+    const int nt = (int)std::min<size_t>((size_t)std::max(1, nthreads), pieces);
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; ++t) {
+        try {
+            th.emplace_back(work);
+        } catch (...) {
+            break;  // (fewer threads: the ones there are share the work)
+        }
+    }
+    work();
+    for (auto& t : th) t.join();
+    if (failed) std::rethrow_exception(failed);
+}
 
-int build_schedule(const SchedParams& prm, const int32_t* u, const int32_t* i, const float* r,
-                   const int64_t* orig, int64_t n, Schedule& out, std::string& err) {
-    const auto t_begin = std::chrono::steady_clock::now();
-    auto t_last = t_begin;
+// The ids of a part, sorted with their repeats (`v` holds them): the number of distinct ones.
+int sort_ids(std::vector<uint32_t>& v) {
+    std::sort(v.begin(), v.end());
+    int n = 0;
+    for (size_t y = 0; y < v.size(); ++y) n += y == 0 || v[y] != v[y - 1];
+    return n;
+}
+
+// How a part that does not fit is cut in two: by users or by items, whichever it has more distinct of, at the first id
+// after the first where the ratings of the ids before it reach half of the part (ids >= pivot go right).  A part that
+// is one (user, item) pair many times over is cut at the middle of its sequence instead: any cut of it will do.
+// `us`, `is`: the part's user and item ids, sorted with their repeats; nu, ni: how many distinct ones (sort_ids).
+struct CutRule {
+    bool midpoint = false;
+    bool by_user = false;
+    uint32_t pivot = 0;
+};
+
+CutRule cut_rule(const std::vector<uint32_t>& us, const std::vector<uint32_t>& is, int nu, int ni) {
+    CutRule c;
+    if (nu <= 1 && ni <= 1) {
+        c.midpoint = true;
+        return c;
+    }
+    c.by_user = (nu >= ni && nu > 1) || ni <= 1;  // (the side cut has two ids at least)
+    const std::vector<uint32_t>& v = c.by_user ? us : is;
+    const int nid = c.by_user ? nu : ni;
+    const size_t half = v.size() / 2;
+    int seen = 0;  // distinct ids passed
+    for (size_t y = 1; y < v.size(); ++y) {
+        if (v[y] == v[y - 1]) continue;
+        // y ratings belong to the `seen + 1` ids before v[y]
+        ++seen;
+        c.pivot = v[y];
+        if (y >= half || seen >= nid - 1) break;
+    }
+    return c;
+}
+
+// A part of a cell that is cut on the device (route 3): a range of Builder::part_ratings.
+struct Part {
+    int64_t lo, hi;
+    int depth;
+    int nu = 0, ni = 0;
+    bool candidate = false;  // its rows fit: the device's COUNT pass says how many steps it packs into
+    CutRule cut;             // the cut it gets if it is not a leaf
+};
+
+// A part that is a chunk.
+struct Leaf {
+    int64_t lo, hi;
+    PackCellInfo ci;
+};
+
+// MFSGD_SCHED_TRACE: where the levels of the device cut spend their time
+struct LevelClock {
+    double rows = 0, lists = 0, count = 0, cut = 0;
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    void tick(double& acc) {
+        const auto now = std::chrono::steady_clock::now();
+        acc += std::chrono::duration<double>(now - t).count();
+        t = now;
+    }
+};
+
+// build_schedule's state, shared by its phases (one member function each).
+struct Builder {
+    const SchedParams& prm;
+    const int32_t* u;
+    const int32_t* i;
+    const float* r;
+    const int64_t* orig;
+    const int64_t n;
+    Schedule& out;
+    std::string& err;
+
     const bool trace = std::getenv("MFSGD_SCHED_TRACE") != nullptr;
-    auto lap = [&](const char* what) {
+    const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+    std::chrono::steady_clock::time_point t_last = t_begin;
+
+    Geometry geo{};
+    int B = 0, W = 0, G = 0, WW = 0;
+    int32_t U = 0, I = 0;
+    int64_t ncell = 0;
+    int nthreads = 1;
+    Hyper hy{};
+    bool solo_ok = false;
+    int64_t avail = 0, min_sched = 0, min_rows = 0;
+
+    // degrees, LPT bins, bucket order
+    bool on_device = false;  // degrees and bucket order came from the device
+    std::vector<int64_t> degu, degi;
+    std::vector<int32_t> ubin, ibin;
+    int giants = 0;                    // items with a tile of their own: fine bins 0 .. giants - 1
+    std::vector<int32_t> tile_items;   // rated items per tile (mark_lone_tiles)
+    std::vector<int64_t> bptr;         // B*B*W*W + 1 bucket starts
+    std::vector<int64_t> sorted;       // the bucket order, when the host has it ...
+    std::vector<uint32_t> sorted32;    // ... or as it was fetched from the device (route 1 after a device refusal)
+    const DeviceIngestExt* ext = nullptr;  // the device holds the bucket order and packs (routes 2 and 3)
+    std::vector<PackCellInfo> info;        // the device's COUNT pass, per cell
+    bool have_info = false;                // ... and it ran: a refusal from here on means route 3
+
+    // cells and chunks: co[c] is cell c's first chunk, extra[c] the rest in chain order
+    std::vector<CellOut> co;
+    std::vector<std::vector<CellOut>> extra;
+    std::vector<uint8_t> oversize;  // cells that cannot be one chunk
+    int64_t lim_s = 0, lim_r = 0;   // the limits of one chunk (schedule bytes, row bytes)
+    std::vector<int64_t> todo;      // the cells to be cut
+    // [r3] route 3: the ratings of the cells that are cut (indices into the caller's arrays), cell after cell in bucket
+    // order, and the sub-cell of each.  The cut tree partitions a cell's range IN PLACE (stably), so every part -- and in
+    // the end every chunk -- is a range of these two arrays, a cell's chunks lie in chain order one behind the other, and
+    // the arrays as they stand are the rating lists the device's EMIT pass takes: no per-part vectors, nothing concatenated.
+    std::vector<uint32_t> part_ratings;
+    std::vector<uint16_t> part_sbs;
+    std::atomic<int> failed{0};
+    std::string fail_msg;
+    LevelClock clock;
+
+    // assembly
+    int64_t n_descs = 0;
+    std::vector<const CellOut*> by_desc;
+    int64_t tot_rows = 0, tot_steps = 0;
+    // the cells that are not one device-packed chunk, whose pieces have to be walked one by one
+    std::vector<int64_t> walk_cells;
+
+    Builder(const SchedParams& p, const int32_t* u_, const int32_t* i_, const float* r_, const int64_t* orig_, int64_t n_,
+            Schedule& out_, std::string& err_)
+        : prm(p), u(u_), i(i_), r(r_), orig(orig_), n(n_), out(out_), err(err_) {}
+
+    void lap(const char* what) {
         if (!trace) return;
         const auto now = std::chrono::steady_clock::now();
         std::fprintf(stderr, "[schedule] %-28s %.3f s\n", what, std::chrono::duration<double>(now - t_last).count());
         t_last = now;
-    };
-    const Geometry geo = geometry_for_k(prm.k);
-    const int B = prm.B, W = prm.W, G = geo.G;
-    if (B < 1 || W < 1 || W > 8 || prm.k < 1 || geo.L > 64) {
-        err = "build_schedule: bad geometry (B, W or k)";
-        return -1;
     }
-    if ((int64_t)B * B * W * W > (int64_t)1 << 28) {
-        err = "build_schedule: B*W too large";
-        return -1;
+    bool fail(const std::string& msg) {
+        err = msg;
+        return false;
     }
-    const int32_t U = prm.U, I = prm.I;
-    int nthreads = prm.threads > 0 ? prm.threads : (int)std::thread::hardware_concurrency();
-    if (nthreads < 1) nthreads = 1;
-    if (nthreads > 64) nthreads = 64;
+    int done() {
+        out.build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+        return 0;
+    }
+    int64_t cell_nnz(int64_t c) const { return bptr[(size_t)((c + 1) * WW)] - bptr[(size_t)(c * WW)]; }
+    bool addressable(int nrows) const { return (int64_t)(nrows + 2 * G) * geo.L <= 32767; }
+    // rows that fit the training kernel's LDS image beside the smallest schedule
+    bool rows_fit(int nrows) const { return addressable(nrows) && rows_bytes_for(geo, nrows) + 2 * min_sched <= avail; }
 
-    // ---- degrees and LPT partition into B*W fine bins -----------------------
-    std::vector<int64_t> degu, degi;
-    bool on_device = prm.ingest && prm.ingest->degrees && prm.ingest->bucket;
+    bool setup();
+    bool degrees();
+    void lpt_partition();
+    void bucket();
+    int device_whole_cells();
+    bool fetch_bucket_order();
+    void keep_device_cells();
+    void load_cell(int64_t c, std::vector<RawRat>& sel) const;
+    void distinct_rows(const std::vector<RawRat>& sel, Scratch& sc, int& nu, int& ni) const;
+    bool pack_chunk(const std::vector<RawRat>& sel, CellOut& o, Scratch& sc) const;
+    void pack_cells_on_host();
+    void chunk_limits();
+    void cut_part(std::vector<RawRat>& part, std::vector<CellOut>& pieces, Scratch& sc);
+    bool cut_on_host();
+    bool fetch_cut_cells(std::vector<int64_t>& r_at);
+    void rows_and_cuts(std::vector<Part>& level, bool root);
+    bool count_candidates(const std::vector<Part>& level, std::vector<size_t>& cand, std::vector<PackCellInfo>& pinfo);
+    std::vector<Part> cut_parts(const std::vector<Part>& level, const std::vector<uint8_t>& is_leaf);
+    bool chunks_from_leaves(std::vector<Leaf>& leaves, const std::vector<int64_t>& r_at);
+    bool cut_on_device();
+    bool place_chunks(bool host_tables);
+    bool assemble_on_host();
+    bool assemble_on_device();
+};
+
+bool Builder::setup() {
+    geo = geometry_for_k(prm.k);
+    B = prm.B;
+    W = prm.W;
+    G = geo.G;
+    if (B < 1 || W < 1 || W > 8 || prm.k < 1 || geo.L > 64) return fail("build_schedule: bad geometry (B, W or k)");
+    if ((int64_t)B * B * W * W > (int64_t)1 << 28) return fail("build_schedule: B*W too large");
+    WW = W * W;
+    U = prm.U;
+    I = prm.I;
+    ncell = (int64_t)B * B;
+    nthreads = prm.threads > 0 ? prm.threads : (int)std::thread::hardware_concurrency();
+    nthreads = std::min(std::max(nthreads, 1), 64);
+    hy = Hyper{prm.lr, 1.0f - prm.lr * prm.lambda};
+    // solo runs pay where the kernel has the two-wave loops for them: 16+ lanes per rating (k > 32) and
+    // a workgroup with copy waves (W <= 4); elsewhere a solo run would only be a slower run
+    solo_ok = prm.solo && geo.L >= 16 && W <= 4;
+    avail = (int64_t)prm.lds_budget - 16;
+    min_sched = sched_bytes_for(geo, W, 2, 3);
+    min_rows = rows_bytes_for(geo, 2);
+    return true;
+}
+
+// ---- degrees -------------------------------------------------------------------------------------------------------
+bool Builder::degrees() {
+    on_device = prm.ingest && prm.ingest->degrees && prm.ingest->bucket;
     if (on_device && !prm.validated) {
         for (int64_t j = 0; j < n && on_device; ++j)
             if (u[j] < 0 || u[j] >= U || i[j] < 0 || i[j] >= I) on_device = false;  // let the host loop report it
@@ -530,80 +746,55 @@ int build_schedule(const SchedParams& prm, const int32_t* u, const int32_t* i, c
         }
         if (!on_device) {
             for (int64_t j = 0; j < n; ++j) {
-                if (u[j] < 0 || u[j] >= U || i[j] < 0 || i[j] >= I) {
-                    err = "set_ratings: index out of range at rating " + std::to_string(j);
-                    return -1;
-                }
+                if (u[j] < 0 || u[j] >= U || i[j] < 0 || i[j] >= I)
+                    return fail("set_ratings: index out of range at rating " + std::to_string(j));
                 degu[(size_t)u[j]]++;
                 degi[(size_t)i[j]]++;
             }
         }
     }
     lap(on_device ? "degrees (device)" : "degrees");
-    std::vector<int32_t> ubin, ibin;
+    return true;
+}
+
+// ---- LPT partition into B*W fine bins -------------------------------------------------------------------------------
+void Builder::lpt_partition() {
     // An item whose chain alone (count x cycles per dependent step) comes to 0.8 of the work-bound estimate
     // of the epoch (the model choose_geometry() picks W with) is on or near the critical path: lpt_assign
     // gives it a tile of its own.
     int64_t giant_min = 0;
-    int giants = 0;  // items with a tile of their own: fine bins 0 .. giants - 1
     {
         const double np = (double)std::min<int64_t>(B, std::max(1, prm.n_cu));
         const double passes = std::ceil((double)B / (double)std::max(1, prm.n_cu));
         const double t_rest = 48.0 * (4.0 / geo.G) * (double)n / np + 12000.0 * (double)B * passes;
         giant_min = (int64_t)(0.8 * t_rest / (170.0 + 2.0 * geo.L));
     }
-    {
-        // users and items are independent: one thread each (the LPT itself is a sequential heap walk)
-        std::exception_ptr failed_u;
-        std::thread tu([&]() {
-            try {
-                lpt_assign(degu, B * W, ubin);
-            } catch (...) {
-                failed_u = std::current_exception();  // no exception may leave a thread
-            }
-        });
-        try {
+    // users and items are independent: one thread each (the LPT itself is a sequential walk)
+    parallel_for(2, 1, 2, [&](Scratch&, size_t side, size_t) {
+        if (side == 0)
+            lpt_assign(degu, B * W, ubin);
+        else
             giants = lpt_assign(degi, B * W, ibin, prm.lone_giants && !std::getenv("MFSGD_NO_LONE_GIANTS") ? B : 0,
                                 giant_min);  // (the variable: A/B measurements)
-        } catch (...) {
-            tu.join();
-            throw;
-        }
-        tu.join();
-        if (failed_u) std::rethrow_exception(failed_u);
-    }
+    });
     lap("LPT partition");
     // fine bin f -> block f % B, sub-group f / B
-    std::vector<int32_t> tile_items((size_t)B, 0);  // rated items per tile (mark_lone_tiles)
+    tile_items.assign((size_t)B, 0);
     for (int32_t x = 0; x < I; ++x)
         if (degi[(size_t)x] > 0) tile_items[(size_t)(ibin[(size_t)x] % B)]++;
+}
 
-    // ---- counting sort by (cell, sub-round, wave) ---------------------------
+// ---- counting sort by (cell, sub-round, wave) -----------------------------------------------------------------------
+void Builder::bucket() {
     const int64_t nb = (int64_t)B * B * W * W;
-    std::vector<int64_t> bptr;
     reserve_huge(bptr, (size_t)nb + 1);
     bptr.assign((size_t)nb + 1, 0);
-    auto bucket_of = [&](int64_t j) -> int64_t {
-        const int32_t fu = ubin[(size_t)u[j]], fi = ibin[(size_t)i[j]];
-        // (an item with a tile of its own: all its ratings in the cell's first sub-cell -- the tile holds nothing
-        // else, so nothing of the same users runs beside it, and its chain is one run instead of W)
-        const int ub = fu % B, us = fi < giants ? 0 : fu / B, it = fi % B, is = fi / B;
-        const int s = (is - us + W) % W;
-        return (((int64_t)ub * B + it) * W + s) * W + us;
-    };
-    std::vector<int64_t> sorted;
-    std::vector<uint32_t> sorted32;  // the same thing when it was fetched from the device packer's context
-    bool want_dev_chunks = false;    // mixed mode with the chunks packed on the device: the bucket order stays there
-    const DeviceIngestExt* ext = (on_device && prm.device_pack && prm.ingest->ext && prm.ingest->ext->bucket_dev &&
-                                  prm.ingest->ext->pack_count && prm.ingest->ext->pack_emit && n > 0)
-                                     ? prm.ingest->ext
-                                     : nullptr;
-    bool sorted_on_device = false;
-    if (ext && ext->bucket_dev(prm.ingest->ctx, u, i, n, ubin.data(), ibin.data(), U, I, B, W, giants, bptr.data()) == 0)
-        sorted_on_device = true;
-    else
-        ext = nullptr;
-    if (!sorted_on_device) {
+    const DeviceIngestExt* e = on_device && prm.device_pack && n > 0 ? prm.ingest->ext : nullptr;
+    if (e && e->bucket_dev && e->fetch_sorted32 && e->fetch_sorted_ranges && e->pack_count && e->pack_emit &&
+        e->pack_count_parts && e->pack_emit_parts && e->download_raw &&
+        e->bucket_dev(prm.ingest->ctx, u, i, n, ubin.data(), ibin.data(), U, I, B, W, giants, bptr.data()) == 0) {
+        ext = e;  // the bucket order stays on the device
+    } else {
         sorted.resize((size_t)n);
         if (on_device && prm.ingest->bucket(prm.ingest->ctx, u, i, n, ubin.data(), ibin.data(), U, I, B, W, giants,
                                             bptr.data(), sorted.data()) != 0) {
@@ -612,6 +803,14 @@ int build_schedule(const SchedParams& prm, const int32_t* u, const int32_t* i, c
         }
     }
     if (!on_device) {
+        auto bucket_of = [&](int64_t j) -> int64_t {
+            const int32_t fu = ubin[(size_t)u[j]], fi = ibin[(size_t)i[j]];
+            // (an item with a tile of its own: all its ratings in the cell's first sub-cell -- the tile holds nothing
+            // else, so nothing of the same users runs beside it, and its chain is one run instead of W)
+            const int ub = fu % B, us = fi < giants ? 0 : fu / B, it = fi % B, is = fi / B;
+            const int s = (is - us + W) % W;
+            return (((int64_t)ub * B + it) * W + s) * W + us;
+        };
         std::vector<int64_t> bkt((size_t)n);
         for (int64_t j = 0; j < n; ++j) {
             const int64_t b = bucket_of(j);
@@ -623,522 +822,444 @@ int build_schedule(const SchedParams& prm, const int32_t* u, const int32_t* i, c
         for (int64_t j = 0; j < n; ++j) sorted[(size_t)cur[(size_t)bkt[(size_t)j]]++] = j;
     }
     lap(on_device ? "bucket (device radix sort)" : "bucket (counting sort)");
+}
 
-    // ---- per-cell packing (parallel over cells) ------------------------------
-    const int64_t ncell = (int64_t)B * B;
-    const int WW = W * W;
-    const Hyper hy{prm.lr, 1.0f - prm.lr * prm.lambda};
-    // solo runs pay where the kernel has the two-wave loops for them: 16+ lanes per rating (k > 32) and
-    // a workgroup with copy waves (W <= 4); elsewhere a solo run would only be a slower run
-    const bool solo_ok = prm.solo && geo.L >= 16 && W <= 4;
-    const int64_t avail = (int64_t)prm.lds_budget - 16;
-    const int64_t min_sched = sched_bytes_for(geo, W, 2, 3), min_rows = rows_bytes_for(geo, 2);
-    auto addressable = [&](int nrows) { return (int64_t)(nrows + 2 * G) * geo.L <= 32767; };
-    if (avail < 2 * min_sched + min_rows) {
-        err = "lds: the LDS budget cannot hold a single rating at this k";
-        return -1;
-    }
-    // ---- the device packer: every cell as a single chunk, same bytes as the host packer below -----
-    std::vector<PackCellInfo> info;  // per cell, from the device's COUNT pass (kept for the mixed mode)
-    std::vector<SubDesc> dsubs;
-    bool have_info = false;
-    // [r3] The sub-cell tables (W*W records per chunk descriptor) are written by the device's packer and read by the
-    // training kernel: when the device packs the chunks of cut cells as well, every table is its, and the final array
-    // is assembled THERE (emit: the cells' tables, the chunks' scattered to their descriptors) instead of coming down
-    // with the COUNT results, through place() and up again with the schedule -- 75 MB three times at the Netflix
-    // shape, 1.76 GB three times at 1 B ratings.  Schedule::subs stays empty; the debug getter fetches a copy.
-    const bool dev_tables = ext && ext->download_raw && ext->pack_count_parts && ext->pack_emit_parts && ext->fetch_sorted_ranges &&
-                            !std::getenv("MFSGD_HOST_CHUNKS") && !std::getenv("MFSGD_HOST_TABLES");
-    if (sorted_on_device) {
-        const char* why = "";
-        const int rc = [&]() -> int {
-            PackRequest q;
-            q.u = u;
-            q.i = i;
-            q.r = r;
-            q.orig = orig;
-            q.n = n;
-            q.U = U;
-            q.I = I;
-            q.ubin = ubin.data();
-            q.ibin = ibin.data();
-            q.B = B;
-            q.W = W;
-            q.G = G;
-            q.L = geo.L;
-            q.lr = hy.lr;
-            q.c = hy.c;
-            q.solo_ok = solo_ok;
-            q.want_subs = !dev_tables;  // (the sub-cell tables stay on the device then: emit leaves the final one there)
-            {
-                // rows of the largest chunk the training kernel can hold beside the smallest schedule
-                int64_t fit = (avail - 2 * min_sched) / geo.rowbytes - 2 * G;
-                while (fit > 0 && !(addressable((int)fit) && rows_bytes_for(geo, (int)fit) + 2 * min_sched <= avail)) --fit;
-                q.fit_rows = (int)std::max<int64_t>(fit, 0);
+// ---- route 2: the device packer, every cell as a single chunk, same bytes as the host packer -----------------------
+// Returns 0 (done: `out` holds the schedule), 1 (declined: have_info says whether the COUNT pass ran) or -1.
+int Builder::device_whole_cells() {
+    const char* why = "";
+    const int rc = [&]() -> int {
+        PackRequest q;
+        q.u = u;
+        q.i = i;
+        q.r = r;
+        q.orig = orig;
+        q.n = n;
+        q.U = U;
+        q.I = I;
+        q.ubin = ubin.data();
+        q.ibin = ibin.data();
+        q.B = B;
+        q.W = W;
+        q.G = G;
+        q.L = geo.L;
+        q.lr = hy.lr;
+        q.c = hy.c;
+        q.solo_ok = solo_ok;
+        {
+            // rows of the largest chunk the training kernel can hold beside the smallest schedule
+            int64_t fit = (avail - 2 * min_sched) / geo.rowbytes - 2 * G;
+            while (fit > 0 && !rows_fit((int)fit)) --fit;
+            q.fit_rows = (int)std::max<int64_t>(fit, 0);
+        }
+        for (int64_t cc = 0; cc < ncell; ++cc) q.max_cell_nnz = std::max(q.max_cell_nnz, cell_nnz(cc));
+        // canonical order: rounds, then blocks; a cell's ratings are contiguous.  Known from the bucket starts alone,
+        // so the device's pass can write the order array -- and, into scratch, everything else -- while it counts
+        std::vector<int64_t> ord_off((size_t)ncell);
+        std::vector<int64_t> cell_ptr((size_t)ncell + 1, 0);
+        int64_t pos = 0;
+        for (int rd = 0; rd < B; ++rd)
+            for (int b = 0; b < B; ++b) {
+                const int64_t cc = (int64_t)b * B + (b + rd) % B;
+                cell_ptr[(size_t)((int64_t)rd * B + b)] = pos;
+                ord_off[(size_t)cc] = pos;
+                pos += cell_nnz(cc);
             }
-            for (int64_t cc = 0; cc < ncell; ++cc)
-                q.max_cell_nnz = std::max(q.max_cell_nnz, bptr[(size_t)((cc + 1) * WW)] - bptr[(size_t)(cc * WW)]);
-            // canonical order: rounds, then blocks; a cell's ratings are contiguous.  Known from the bucket starts alone,
-            // so the device's pass can write the order array -- and, into scratch, everything else -- while it counts
-            std::vector<int64_t> ord_off((size_t)ncell);
-            std::vector<int64_t> cell_ptr((size_t)ncell + 1, 0);
-            int64_t pos = 0;
-            for (int rd = 0; rd < B; ++rd)
-                for (int b = 0; b < B; ++b) {
-                    const int64_t cc = (int64_t)b * B + (b + rd) % B;
-                    cell_ptr[(size_t)((int64_t)rd * B + b)] = pos;
-                    ord_off[(size_t)cc] = pos;
-                    pos += bptr[(size_t)((cc + 1) * WW)] - bptr[(size_t)(cc * WW)];
-                }
-            cell_ptr[(size_t)ncell] = pos;
-            if (pos != n) return -1;
-            q.ord_off = ord_off.data();
-            int prc = ext->pack_count(prm.ingest->ctx, q, info, dsubs);
-            if (prc != 0) {
-                why = "the rating set is outside the kernel's limits (cell size, ranks, LDS)";
-                return prc;
-            }
-            have_info = ext->pack_emit_mixed != nullptr;  // from here on a refusal means "mixed mode", not "host"
-            lap("  device pack: count");
-            // every cell must fit the training kernel's LDS image as ONE chunk (chunking is the host's job)
-            int64_t max_s = min_sched, max_r = min_rows, tot_rows = 0, tot_steps = 0;
-            std::vector<uint32_t> row_off((size_t)ncell), ent_off((size_t)ncell);
-            for (int64_t cc = 0; cc < ncell; ++cc) {
-                const PackCellInfo& ci = info[(size_t)cc];
-                if (ci.status != 0) {
-                    why = "a cell overflowed the kernel's arrays or counters";
-                    return 1;
-                }
-                const int nrows = (int)(ci.nu + ci.ni);
-                if (ci.n_steps != 0) {
-                    if (!addressable(nrows) || rows_bytes_for(geo, nrows) + 2 * min_sched > avail) {
-                        why = "a cell's rows exceed the training kernel's LDS image";
-                        return 1;
-                    }
-                    max_s = std::max(max_s, sched_bytes_for(geo, W, nrows, (int64_t)ci.n_steps));
-                    max_r = std::max(max_r, rows_bytes_for(geo, nrows));
-                }
-                if (tot_rows > 0xFFFFFFFFll - nrows || tot_steps > 0xFFFFFFFFll - (int64_t)ci.n_steps) return 1;
-                row_off[(size_t)cc] = (uint32_t)tot_rows;
-                ent_off[(size_t)cc] = (uint32_t)tot_steps;
-                tot_rows += nrows;
-                tot_steps += ci.n_steps;
-            }
-            if (2 * max_s + max_r > avail) {
-                why = "cells have to be chunked";
+        cell_ptr[(size_t)ncell] = pos;
+        if (pos != n) return -1;
+        q.ord_off = ord_off.data();
+        int prc = ext->pack_count(prm.ingest->ctx, q, info);
+        if (prc != 0) {
+            why = "the rating set is outside the kernel's limits (cell size, ranks, LDS)";
+            return prc;
+        }
+        have_info = true;  // from here on a refusal means route 3, not the host
+        lap("  device pack: count");
+        // every cell must fit the training kernel's LDS image as ONE chunk
+        int64_t max_s = min_sched, max_r = min_rows, rows = 0, steps = 0;
+        std::vector<uint32_t> row_off((size_t)ncell), ent_off((size_t)ncell);
+        for (int64_t cc = 0; cc < ncell; ++cc) {
+            const PackCellInfo& ci = info[(size_t)cc];
+            if (ci.status != 0) {
+                why = "a cell overflowed the kernel's arrays or counters";
                 return 1;
             }
-            if (ncell > 0x7FFFFFFFll / WW) return 1;
-            Schedule sch;
-            sch.geo = geo;
-            sch.B = B;
-            sch.W = W;
-            sch.nnz = n;
-            sch.cells.resize((size_t)ncell);
-            sch.n_sub_recs = ncell * WW + 2;
-            if (!dev_tables) {
-                sch.subs.assign((size_t)(ncell * WW) + 2, SubDesc{0, 0});
-                std::memcpy(sch.subs.data(), dsubs.data(), sizeof(SubDesc) * (size_t)(ncell * WW));
+            const int nrows = (int)(ci.nu + ci.ni);
+            if (ci.n_steps != 0) {
+                if (!rows_fit(nrows)) {
+                    why = "a cell's rows exceed the training kernel's LDS image";
+                    return 1;
+                }
+                max_s = std::max(max_s, sched_bytes_for(geo, W, nrows, (int64_t)ci.n_steps));
+                max_r = std::max(max_r, rows_bytes_for(geo, nrows));
             }
-            for (int64_t cc = 0; cc < ncell; ++cc) {
-                const PackCellInfo& ci = info[(size_t)cc];
-                CellDesc d{};
-                d.row_off = row_off[(size_t)cc];
-                d.ent_off = ent_off[(size_t)cc];
-                d.n_steps = ci.n_steps | (ci.has_run ? kCellCritical : 0u);
-                d.nu = (uint16_t)ci.nu;
-                d.ni = (uint16_t)ci.ni;
-                sch.cells[(size_t)cc] = d;
-                const int64_t m_c = bptr[(size_t)((cc + 1) * WW)] - bptr[(size_t)(cc * WW)];
-                sch.max_cell_nnz = std::max(sch.max_cell_nnz, m_c);
-                sch.max_cell_rows = std::max<int64_t>(sch.max_cell_rows, ci.nu + ci.ni);
-                sch.max_cell_steps = std::max<int64_t>(sch.max_cell_steps, ci.crit);
-            }
-            mark_lone_tiles(sch.cells, B, geo, tile_items);
-            sch.sched_cap = (int)max_s;
-            sch.lds_bytes = (int)((16 + 2 * max_s + max_r + 15) & ~(int64_t)15);
-            sch.total_rows = tot_rows;
-            sch.total_steps = tot_steps;
-            sch.n_rows_words = tot_rows + 4;
-            sch.n_entry_recs = tot_steps * G;
-            sch.cell_ptr = std::move(cell_ptr);
-            for (int rd = 0; rd < B; ++rd) {
-                int64_t worst = 0;
-                for (int b = 0; b < B; ++b) worst = std::max<int64_t>(worst, info[(size_t)((int64_t)b * B + (b + rd) % B)].crit);
-                sch.sum_round_steps += worst;
-            }
-            lap("  device pack: offsets");
-            prc = ext->pack_emit(prm.ingest->ctx, row_off.data(), ent_off.data(), ord_off.data(), tot_rows, tot_steps,
-                                 dev_tables ? ncell : 0, &sch.dev.buf);
-            if (prc != 0) return -1;
-            lap("  device pack: emit");
-            sch.device_packed = true;
-            sch.dev_ops = ext;
-            sch.device_ingest = true;
-            out = std::move(sch);
-            return 0;
-        }();
-        if (rc == 0) {
-            out.build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-            return 0;
+            if (rows > 0xFFFFFFFFll - nrows || steps > 0xFFFFFFFFll - (int64_t)ci.n_steps) return 1;
+            row_off[(size_t)cc] = (uint32_t)rows;
+            ent_off[(size_t)cc] = (uint32_t)steps;
+            rows += nrows;
+            steps += ci.n_steps;
         }
-        if (rc != 1) have_info = false;
-        // the host packer needs the bucket order on this side (32-bit, as the device holds it) -- unless the device packs
-        // the chunks too ([r3]): then only the cells that are cut come here, once it is known which
-        want_dev_chunks = have_info && ext->pack_count_parts && ext->pack_emit_parts && ext->fetch_sorted_ranges &&
-                          !std::getenv("MFSGD_HOST_CHUNKS");
-        if (!want_dev_chunks) {
-            sorted32.resize((size_t)n);
-            if (!ext->fetch_sorted32 || ext->fetch_sorted32(prm.ingest->ctx, sorted32.data()) != 0) {
-                err = "build_schedule: could not fetch the bucket order from the device";
-                return -1;
-            }
+        if (2 * max_s + max_r > avail) {
+            why = "cells have to be chunked";
+            return 1;
         }
-        if (trace)
-            std::fprintf(stderr, "[schedule]   device pack %s: %s%s\n", rc == 1 ? "declined" : "FAILED", why,
-                         have_info ? " -> mixed mode: the device keeps the cells that fit, the host packs the rest" : "");
-        lap("  bucket order to the host");
-    }
-    std::atomic<int> failed{0};
-    std::string fail_msg;
+        if (ncell > 0x7FFFFFFFll / WW) return 1;
+        Schedule sch;
+        sch.geo = geo;
+        sch.B = B;
+        sch.W = W;
+        sch.nnz = n;
+        sch.cells.resize((size_t)ncell);
+        sch.n_sub_recs = ncell * WW + 2;
+        for (int64_t cc = 0; cc < ncell; ++cc) {
+            const PackCellInfo& ci = info[(size_t)cc];
+            CellDesc d{};
+            d.row_off = row_off[(size_t)cc];
+            d.ent_off = ent_off[(size_t)cc];
+            d.n_steps = ci.n_steps | (ci.has_run ? kCellCritical : 0u);
+            d.nu = (uint16_t)ci.nu;
+            d.ni = (uint16_t)ci.ni;
+            sch.cells[(size_t)cc] = d;
+            sch.max_cell_nnz = std::max(sch.max_cell_nnz, cell_nnz(cc));
+            sch.max_cell_rows = std::max<int64_t>(sch.max_cell_rows, ci.nu + ci.ni);
+            sch.max_cell_steps = std::max<int64_t>(sch.max_cell_steps, ci.crit);
+        }
+        mark_lone_tiles(sch.cells, B, geo, tile_items);
+        sch.sched_cap = (int)max_s;
+        sch.lds_bytes = (int)((16 + 2 * max_s + max_r + 15) & ~(int64_t)15);
+        sch.total_rows = rows;
+        sch.total_steps = steps;
+        sch.n_rows_words = rows + 4;
+        sch.n_entry_recs = steps * G;
+        sch.cell_ptr = std::move(cell_ptr);
+        for (int rd = 0; rd < B; ++rd) {
+            int64_t worst = 0;
+            for (int b = 0; b < B; ++b) worst = std::max<int64_t>(worst, info[(size_t)((int64_t)b * B + (b + rd) % B)].crit);
+            sch.sum_round_steps += worst;
+        }
+        lap("  device pack: offsets");
+        // (the sub-cell tables stay on the device: the emit call leaves the final one there, Schedule::subs stays empty)
+        prc = ext->pack_emit(prm.ingest->ctx, row_off.data(), ent_off.data(), ord_off.data(), rows, steps, &sch.dev.buf);
+        if (prc != 0) return -1;
+        lap("  device pack: emit");
+        sch.device_packed = true;
+        sch.dev_ops = ext;
+        sch.device_ingest = true;
+        out = std::move(sch);
+        return 0;
+    }();
+    if (rc != 1) have_info = false;  // (a failed call: route 1)
+    if (rc != 0 && trace)
+        std::fprintf(stderr, "[schedule]   device pack %s: %s%s\n", rc == 1 ? "declined" : "FAILED", why,
+                     have_info ? " -> the device keeps the cells that fit and packs the chunks of the cells that are cut" : "");
+    return rc;
+}
 
-    // One chunk: the ratings `sel` (bucket order, so sub-cells are contiguous) packed as a complete
-    // little cell.  Returns false when a sub-cell overflows the 16-bit step counts (caller splits).
-    auto pack_chunk = [&](const std::vector<RawRat>& sel, CellOut& o, Scratch& sc) -> bool {
-        const int64_t m = (int64_t)sel.size();
-        o = CellOut{};
-        o.a().subs.assign((size_t)WW, SubDesc{0, 0});
-        std::vector<uint32_t>& uu = sc.us;
-        std::vector<uint32_t>& ii = sc.is;
-        uu.resize((size_t)m);
-        ii.resize((size_t)m);
-        for (int64_t x = 0; x < m; ++x) {
-            uu[(size_t)x] = sel[(size_t)x].u;
-            ii[(size_t)x] = sel[(size_t)x].i;
-        }
-        std::sort(uu.begin(), uu.end());
-        uu.erase(std::unique(uu.begin(), uu.end()), uu.end());
-        std::sort(ii.begin(), ii.end());
-        ii.erase(std::unique(ii.begin(), ii.end()), ii.end());
-        const int nu = (int)uu.size(), ni = (int)ii.size(), nrows = nu + ni;
-        o.nu = (uint32_t)nu;
-        o.ni = (uint32_t)ni;
-        o.a().rows.reserve((size_t)nrows);
-        o.a().rows.insert(o.a().rows.end(), uu.begin(), uu.end());
-        o.a().rows.insert(o.a().rows.end(), ii.begin(), ii.end());
-        sc.rats.resize((size_t)m);
-        int64_t sub_lo[65];  // first rating of sub-cell x (x = s * W + w), sub_lo[WW] = m
-        {
-            int nxt = 0;
-            for (int64_t x = 0; x < m; ++x) {
-                const RawRat& a = sel[(size_t)x];
-                while (nxt <= (int)a.sb) sub_lo[nxt++] = x;
-                Rat t;
-                t.p = (uint16_t)(std::lower_bound(uu.begin(), uu.end(), a.u) - uu.begin());
-                t.q = (uint16_t)(nu + (std::lower_bound(ii.begin(), ii.end(), a.i) - ii.begin()));
-                t.r = a.r;
-                t.idx = a.idx;
-                sc.rats[(size_t)x] = t;
-            }
-            while (nxt <= WW) sub_lo[nxt++] = m;
-        }
-        sc.remdeg.assign((size_t)nrows, 0);
-        sc.laststep.assign((size_t)nrows, 0);
-        sc.lastslot.assign((size_t)nrows, (int8_t)-1);
-        sc.prevstep.assign((size_t)nrows, 0);
-        int32_t tstamp = 1;  // step stamps start at 2 so that t-1 never matches 0
-        o.a().entries.reserve((size_t)(m + m / 2 + G));
-        o.a().order.reserve((size_t)m);
-        uint32_t stepcur = 0;
-        int64_t crit = 0;
-        for (int s = 0; s < W; ++s) {
-            uint32_t smax = 0;
-            for (int w = 0; w < W; ++w) {
-                const int64_t slo = sub_lo[s * W + w], shi = sub_lo[s * W + w + 1];
-                uint32_t ns = 0, nr = 0;
-                const int nsub = (int)(shi - slo);
-                Rat* sub = sc.rats.data() + slo;
-                // run items: the (at most G) items whose ratings would dominate the step
-                // count of this sub-cell; their ratings go last, in run mode
-                uint16_t run_q[64];
-                int nrun = 0;
-                if (nsub >= kRunMin) {
-                    for (int j = 0; j < nsub; ++j) sc.remdeg[sub[j].q]++;
-                    std::vector<std::pair<int32_t, uint16_t>>& top = sc.top;
-                    top.clear();
-                    for (int j = 0; j < nsub; ++j) {
-                        const int32_t d = sc.remdeg[sub[j].q];
-                        if (d >= kRunMin && d * G >= nsub) top.push_back({-d, sub[j].q});
-                    }
-                    for (int j = 0; j < nsub; ++j) sc.remdeg[sub[j].q] = 0;
-                    std::sort(top.begin(), top.end());
-                    top.erase(std::unique(top.begin(), top.end()), top.end());
-                    for (size_t x = 0; x < top.size() && nrun < G; ++x) run_q[nrun++] = top[x].second;
-                }
-                // A solo run for the heaviest run item when it dwarfs the others (their run would be
-                // over in a quarter of its steps: taking it out costs less than it saves) and its
-                // users are all distinct (a repeated (user, item) pair has to see its own update).
-                bool solo = false;
-                uint16_t solo_q = 0;
-                if (solo_ok && nrun > 0) {
-                    const int n1 = -sc.top[0].first, n2 = sc.top.size() > 1 ? -sc.top[1].first : 0;
-                    if (n1 >= kSoloMin && 4 * n2 <= n1) {
-                        solo = true;
-                        solo_q = sc.top[0].second;
-                        const int32_t stamp = ++tstamp;
-                        for (int j = 0; j < nsub && solo; ++j)
-                            if (sub[j].q == solo_q) {
-                                if (sc.laststep[sub[j].p] == stamp) solo = false;
-                                sc.laststep[sub[j].p] = stamp;
-                            }
-                    }
-                    if (solo) {
-                        for (int g = 1; g < nrun; ++g) run_q[g - 1] = run_q[g];
-                        --nrun;
-                    }
-                }
-                int ngen = nsub, nsolo = 0;
-                if (solo) {  // solo ratings last
-                    nsolo = nsub - (int)(std::stable_partition(sub, sub + nsub, [&](const Rat& x) { return x.q != solo_q; }) - sub);
-                    ngen = nsub - nsolo;
-                }
-                const int nnon = ngen;  // general + run ratings
-                if (nrun > 0) {
-                    // stable partition: general ratings first, run ratings after
-                    auto is_run = [&](const Rat& x) {
-                        for (int g = 0; g < nrun; ++g)
-                            if (run_q[g] == x.q) return true;
-                        return false;
-                    };
-                    ngen = (int)(std::stable_partition(sub, sub + nnon, [&](const Rat& x) { return !is_run(x); }) - sub);
-                }
-                ++tstamp;  // break stickiness across sub-cells
-                pack_subcell(sub, ngen, G, geo.L, nrows, hy, sc, tstamp, o.a().entries, o.a().order, ns);
-                if (nrun > 0) {
-                    ++tstamp;  // the run starts with fresh loads: no hazard against the last general step
-                    pack_run(sub + ngen, nnon - ngen, run_q, nrun, G, geo.L, nrows, hy, sc, tstamp, o.a().entries, o.a().order,
-                             nr);
-                }
-                uint32_t nsu = 0;  // step units the solo records occupy
-                if (nsolo > 0) {
-                    ++tstamp;
-                    // the general and run loops read one and two steps ahead: two idle steps keep that
-                    // look-ahead on step-format entries, whatever follows
-                    for (int pad = 0; pad < kSoloPad; ++pad)
-                        for (int g = 0; g < G; ++g)
-                            o.a().entries.push_back(make_entry(encode_slots(nrows + 2 * g, nrows + 2 * g + 1, false, geo.L), 0.0f, hy.c, hy));
-                    pack_solo(sub + nnon, nsolo, G, geo.L, nrows, hy, o.a().entries, o.a().order, nsu);
-                    nsu += kSoloPad;
-                }
-                if (ns > 0xFFFF || nr > 0xFFFF || nsolo > 0xFFFF || stepcur > 0xFFFF) return false;
-                if (nr > 0 || nsolo > 0) o.has_run = true;
-                o.a().subs[(size_t)(s * W + w)] = SubDesc{stepcur | ((uint32_t)nsolo << 16), ns | (nr << 16)};
-                stepcur += ns + nr + nsu;
-                // a solo step costs about three quarters of a run step (137 against 184 cycles at L = 16)
-                smax = std::max(smax, ns + nr + (uint32_t)(nsolo * 3 / 4));
-            }
-            crit += smax;
-        }
-        // two trailing idle steps: the kernel reads entries t+1 and t+2 ahead
-        for (int pad = 0; pad < 2; ++pad)
-            for (int g = 0; g < G; ++g)
-                o.a().entries.push_back(make_entry(encode_slots(nrows + 2 * g, nrows + 2 * g + 1, false, geo.L), 0.0f, hy.c, hy));
-        o.n_steps = stepcur + 2;
-        o.crit = crit;
-        o.n_rows = (uint32_t)nrows;
-        o.n_order = m;
-        return true;
-    };
-    auto load_cell = [&](int64_t c, std::vector<RawRat>& sel) {
-        const int64_t lo = bptr[(size_t)(c * WW)], hi = bptr[(size_t)((c + 1) * WW)];
-        sel.resize((size_t)(hi - lo));
-        int sb = 0;
-        for (int64_t x = lo; x < hi; ++x) {
-            while (bptr[(size_t)(c * WW + sb + 1)] <= x) ++sb;
-            const int64_t j = sorted32.empty() ? sorted[(size_t)x] : (int64_t)sorted32[(size_t)x];
-            sel[(size_t)(x - lo)] = RawRat{(uint32_t)u[j], (uint32_t)i[j], r[j], orig ? orig[j] : j, (uint16_t)sb};
-        }
-    };
-    auto distinct_rows = [&](const std::vector<RawRat>& sel, Scratch& sc, int& nu, int& ni) {
-        sc.us.resize(sel.size());
-        sc.is.resize(sel.size());
-        for (size_t x = 0; x < sel.size(); ++x) {
-            sc.us[x] = sel[x].u;
-            sc.is[x] = sel[x].i;
-        }
-        std::sort(sc.us.begin(), sc.us.end());
-        std::sort(sc.is.begin(), sc.is.end());
-        nu = (int)(std::unique(sc.us.begin(), sc.us.end()) - sc.us.begin());
-        ni = (int)(std::unique(sc.is.begin(), sc.is.end()) - sc.is.begin());
-    };
-    auto run_parallel = [&](const std::function<void(Scratch&, std::vector<RawRat>&)>& body) {
-        std::vector<std::thread> th;
-        auto w = [&]() {
-            Scratch sc;
-            std::vector<RawRat> sel;
-            body(sc, sel);
-        };
-        const int nt = (int)std::min<int64_t>(nthreads, ncell);
-        for (int t = 1; t < nt; ++t) th.emplace_back(w);
-        w();
-        for (auto& t : th) t.join();
-    };
+// Route 1 after a device refusal: the host packer needs the bucket order on this side (32-bit, as the device holds it).
+bool Builder::fetch_bucket_order() {
+    sorted32.resize((size_t)n);
+    if (ext->fetch_sorted32(prm.ingest->ctx, sorted32.data()) != 0)
+        return fail("build_schedule: could not fetch the bucket order from the device");
+    return true;
+}
 
-    // [r3] Mixed mode with the chunks packed on the device as well (pack_count_parts / pack_emit_parts): the host only
-    // DECIDES the cuts -- from the cells' ids -- and asks the device for the size of every candidate chunk.
-    // MFSGD_HOST_CHUNKS=1: round 2's mixed mode (the host packs and chunks what the device declines; A/B measurements).
-    const bool dev_chunks = have_info && ext && want_dev_chunks;
-    // Phase 1: every cell as a single chunk, unless it cannot possibly fit.
-    std::vector<CellOut> co;
+// ---- per-cell packing -----------------------------------------------------------------------------------------------
+// Route 3: a cell the device packed as one chunk stays there (only its sizes come here); a cell it declined as one chunk
+// (its rows exceed the LDS image, or its counters overflowed) is exactly a cell the host packer would call oversize.
+void Builder::keep_device_cells() {
     reserve_huge(co, (size_t)ncell);
     co.resize((size_t)ncell);
-    std::vector<uint8_t> oversize((size_t)ncell, 0);
+    oversize.assign((size_t)ncell, 0);
+    // cells are claimed in batches: most of them only copy five numbers, and one atomic per cell (590 K of them at the
+    // Netflix shape, contended by 16 threads) cost more than the work
+    parallel_for((size_t)ncell, 256, nthreads, [&](Scratch&, size_t c0, size_t c1) {
+        for (size_t c = c0; c < c1; ++c) {
+            const int64_t m = cell_nnz((int64_t)c);
+            if (m == 0) continue;  // (an empty cell: place_chunks() writes zeros)
+            const PackCellInfo& ci = info[c];
+            CellOut& o = co[c];
+            o.nu = ci.nu;
+            o.ni = ci.ni;
+            o.n_order = m;
+            if (ci.status == 0 && rows_fit((int)(ci.nu + ci.ni))) {
+                // (its sub-cell table stays on the device: the emit call puts it into the final one)
+                o.n_steps = ci.n_steps;
+                o.crit = ci.crit;
+                o.has_run = ci.has_run != 0;
+                o.n_rows = ci.nu + ci.ni;
+                o.dev = true;
+            } else {
+                oversize[c] = 1;
+            }
+        }
+    });
+    lap("per-cell packing");
+}
+
+void Builder::load_cell(int64_t c, std::vector<RawRat>& sel) const {
+    const int64_t lo = bptr[(size_t)(c * WW)], hi = bptr[(size_t)((c + 1) * WW)];
+    sel.resize((size_t)(hi - lo));
+    int sb = 0;
+    for (int64_t x = lo; x < hi; ++x) {
+        while (bptr[(size_t)(c * WW + sb + 1)] <= x) ++sb;
+        const int64_t j = sorted32.empty() ? sorted[(size_t)x] : (int64_t)sorted32[(size_t)x];
+        sel[(size_t)(x - lo)] = RawRat{(uint32_t)u[j], (uint32_t)i[j], r[j], orig ? orig[j] : j, (uint16_t)sb};
+    }
+}
+
+// The distinct rows of `sel`; leaves its user and item ids in sc.us / sc.is, sorted with their repeats.
+void Builder::distinct_rows(const std::vector<RawRat>& sel, Scratch& sc, int& nu, int& ni) const {
+    sc.us.resize(sel.size());
+    sc.is.resize(sel.size());
+    for (size_t x = 0; x < sel.size(); ++x) {
+        sc.us[x] = sel[x].u;
+        sc.is[x] = sel[x].i;
+    }
+    nu = sort_ids(sc.us);
+    ni = sort_ids(sc.is);
+}
+
+// One chunk: the ratings `sel` (bucket order, so sub-cells are contiguous) packed as a complete little cell.
+// Returns false when a sub-cell overflows the 16-bit step counts (the caller cuts).
+bool Builder::pack_chunk(const std::vector<RawRat>& sel, CellOut& o, Scratch& sc) const {
+    const int64_t m = (int64_t)sel.size();
+    o = CellOut{};
+    o.a().subs.assign((size_t)WW, SubDesc{0, 0});
+    std::vector<uint32_t>& uu = sc.us;
+    std::vector<uint32_t>& ii = sc.is;
+    uu.resize((size_t)m);
+    ii.resize((size_t)m);
+    for (int64_t x = 0; x < m; ++x) {
+        uu[(size_t)x] = sel[(size_t)x].u;
+        ii[(size_t)x] = sel[(size_t)x].i;
+    }
+    std::sort(uu.begin(), uu.end());
+    uu.erase(std::unique(uu.begin(), uu.end()), uu.end());
+    std::sort(ii.begin(), ii.end());
+    ii.erase(std::unique(ii.begin(), ii.end()), ii.end());
+    const int nu = (int)uu.size(), ni = (int)ii.size(), nrows = nu + ni;
+    o.nu = (uint32_t)nu;
+    o.ni = (uint32_t)ni;
+    o.a().rows.reserve((size_t)nrows);
+    o.a().rows.insert(o.a().rows.end(), uu.begin(), uu.end());
+    o.a().rows.insert(o.a().rows.end(), ii.begin(), ii.end());
+    sc.rats.resize((size_t)m);
+    int64_t sub_lo[65];  // first rating of sub-cell x (x = s * W + w), sub_lo[WW] = m
     {
-        std::atomic<int64_t> next_cell{0};
-        // cells are claimed in batches: in mixed mode most of them only copy five numbers, and one atomic per cell
-        // (590 K of them at the Netflix shape, contended by 16 threads) cost more than the work
-        const int64_t batch = have_info ? 256 : 1;
-        run_parallel([&](Scratch& sc, std::vector<RawRat>& sel) {
-            for (;;) {
-                const int64_t c0 = next_cell.fetch_add(batch);
-                if (c0 >= ncell) break;
-                for (int64_t c = c0; c < std::min(ncell, c0 + batch); ++c) {
-                CellOut& o = co[(size_t)c];
-                if (bptr[(size_t)(c * WW)] == bptr[(size_t)((c + 1) * WW)]) continue;  // (an empty cell: place() writes zeros)
-                if (have_info) {
-                    // mixed mode: a cell the device packed as one chunk stays there (only its sizes come here)
-                    const PackCellInfo& ci = info[(size_t)c];
-                    const int nrows = (int)(ci.nu + ci.ni);
-                    if (ci.status == 0 && addressable(nrows) && rows_bytes_for(geo, nrows) + 2 * min_sched <= avail) {
-                        // (its sub-cell table stays in dsubs: place() takes it from there -- 590 K small vectors less at
-                        // the Netflix shape)
-                        o.nu = ci.nu;
-                        o.ni = ci.ni;
-                        o.n_steps = ci.n_steps;
-                        o.crit = ci.crit;
-                        o.has_run = ci.has_run != 0;
-                        o.n_rows = (uint32_t)nrows;
-                        o.n_order = bptr[(size_t)((c + 1) * WW)] - bptr[(size_t)(c * WW)];
-                        o.dev = true;
-                        continue;
-                    }
+        int nxt = 0;
+        for (int64_t x = 0; x < m; ++x) {
+            const RawRat& a = sel[(size_t)x];
+            while (nxt <= (int)a.sb) sub_lo[nxt++] = x;
+            Rat t;
+            t.p = (uint16_t)(std::lower_bound(uu.begin(), uu.end(), a.u) - uu.begin());
+            t.q = (uint16_t)(nu + (std::lower_bound(ii.begin(), ii.end(), a.i) - ii.begin()));
+            t.r = a.r;
+            t.idx = a.idx;
+            sc.rats[(size_t)x] = t;
+        }
+        while (nxt <= WW) sub_lo[nxt++] = m;
+    }
+    sc.remdeg.assign((size_t)nrows, 0);
+    sc.laststep.assign((size_t)nrows, 0);
+    sc.lastslot.assign((size_t)nrows, (int8_t)-1);
+    sc.prevstep.assign((size_t)nrows, 0);
+    int32_t tstamp = 1;  // step stamps start at 2 so that t-1 never matches 0
+    o.a().entries.reserve((size_t)(m + m / 2 + G));
+    o.a().order.reserve((size_t)m);
+    uint32_t stepcur = 0;
+    int64_t crit = 0;
+    for (int s = 0; s < W; ++s) {
+        uint32_t smax = 0;
+        for (int w = 0; w < W; ++w) {
+            const int64_t slo = sub_lo[s * W + w], shi = sub_lo[s * W + w + 1];
+            uint32_t ns = 0, nr = 0;
+            const int nsub = (int)(shi - slo);
+            Rat* sub = sc.rats.data() + slo;
+            // run items: the (at most G) items whose ratings would dominate the step
+            // count of this sub-cell; their ratings go last, in run mode
+            uint16_t run_q[64];
+            int nrun = 0;
+            if (nsub >= kRunMin) {
+                for (int j = 0; j < nsub; ++j) sc.remdeg[sub[j].q]++;
+                std::vector<std::pair<int32_t, uint16_t>>& top = sc.top;
+                top.clear();
+                for (int j = 0; j < nsub; ++j) {
+                    const int32_t d = sc.remdeg[sub[j].q];
+                    if (d >= kRunMin && d * G >= nsub) top.push_back({-d, sub[j].q});
                 }
-                if (dev_chunks) {
-                    // [r3] the device packs the chunks too: a cell it declined as ONE chunk (its rows exceed the LDS
-                    // image, or its counters overflowed) is exactly a cell the host packer would call oversize
-                    const PackCellInfo& ci = info[(size_t)c];
-                    o = CellOut{};
-                    o.nu = ci.nu;
-                    o.ni = ci.ni;
-                    o.n_order = bptr[(size_t)((c + 1) * WW)] - bptr[(size_t)(c * WW)];
-                    oversize[(size_t)c] = 1;
-                    continue;
+                for (int j = 0; j < nsub; ++j) sc.remdeg[sub[j].q] = 0;
+                std::sort(top.begin(), top.end());
+                top.erase(std::unique(top.begin(), top.end()), top.end());
+                for (size_t x = 0; x < top.size() && nrun < G; ++x) run_q[nrun++] = top[x].second;
+            }
+            // A solo run for the heaviest run item when it dwarfs the others (their run would be
+            // over in a quarter of its steps: taking it out costs less than it saves) and its
+            // users are all distinct (a repeated (user, item) pair has to see its own update).
+            bool solo = false;
+            uint16_t solo_q = 0;
+            if (solo_ok && nrun > 0) {
+                const int n1 = -sc.top[0].first, n2 = sc.top.size() > 1 ? -sc.top[1].first : 0;
+                if (n1 >= kSoloMin && 4 * n2 <= n1) {
+                    solo = true;
+                    solo_q = sc.top[0].second;
+                    const int32_t stamp = ++tstamp;
+                    for (int j = 0; j < nsub && solo; ++j)
+                        if (sub[j].q == solo_q) {
+                            if (sc.laststep[sub[j].p] == stamp) solo = false;
+                            sc.laststep[sub[j].p] = stamp;
+                        }
                 }
-                load_cell(c, sel);
-                int nu, ni;
-                distinct_rows(sel, sc, nu, ni);
-                if (!addressable(nu + ni) || rows_bytes_for(geo, nu + ni) + 2 * min_sched > avail ||
-                    !pack_chunk(sel, o, sc)) {
-                    o = CellOut{};
-                    o.nu = (uint32_t)nu;  // kept for the limit search below
-                    o.ni = (uint32_t)ni;
-                    o.n_order = (int64_t)sel.size();
-                    oversize[(size_t)c] = 1;
-                }
+                if (solo) {
+                    for (int g = 1; g < nrun; ++g) run_q[g - 1] = run_q[g];
+                    --nrun;
                 }
             }
-        });
+            int ngen = nsub, nsolo = 0;
+            if (solo) {  // solo ratings last
+                nsolo = nsub - (int)(std::stable_partition(sub, sub + nsub, [&](const Rat& x) { return x.q != solo_q; }) - sub);
+                ngen = nsub - nsolo;
+            }
+            const int nnon = ngen;  // general + run ratings
+            if (nrun > 0) {
+                // stable partition: general ratings first, run ratings after
+                auto is_run = [&](const Rat& x) {
+                    for (int g = 0; g < nrun; ++g)
+                        if (run_q[g] == x.q) return true;
+                    return false;
+                };
+                ngen = (int)(std::stable_partition(sub, sub + nnon, [&](const Rat& x) { return !is_run(x); }) - sub);
+            }
+            ++tstamp;  // break stickiness across sub-cells
+            pack_subcell(sub, ngen, G, geo.L, nrows, hy, sc, tstamp, o.a().entries, o.a().order, ns);
+            if (nrun > 0) {
+                ++tstamp;  // the run starts with fresh loads: no hazard against the last general step
+                pack_run(sub + ngen, nnon - ngen, run_q, nrun, G, geo.L, nrows, hy, sc, tstamp, o.a().entries, o.a().order,
+                         nr);
+            }
+            uint32_t nsu = 0;  // step units the solo records occupy
+            if (nsolo > 0) {
+                ++tstamp;
+                // the general and run loops read one and two steps ahead: two idle steps keep that
+                // look-ahead on step-format entries, whatever follows
+                for (int pad = 0; pad < kSoloPad; ++pad)
+                    for (int g = 0; g < G; ++g)
+                        o.a().entries.push_back(make_entry(encode_slots(nrows + 2 * g, nrows + 2 * g + 1, false, geo.L), 0.0f, hy.c, hy));
+                pack_solo(sub + nnon, nsolo, G, geo.L, nrows, hy, o.a().entries, o.a().order, nsu);
+                nsu += kSoloPad;
+            }
+            if (ns > 0xFFFF || nr > 0xFFFF || nsolo > 0xFFFF || stepcur > 0xFFFF) return false;
+            if (nr > 0 || nsolo > 0) o.has_run = true;
+            o.a().subs[(size_t)(s * W + w)] = SubDesc{stepcur | ((uint32_t)nsolo << 16), ns | (nr << 16)};
+            stepcur += ns + nr + nsu;
+            // a solo step costs about three quarters of a run step (137 against 184 cycles at L = 16)
+            smax = std::max(smax, ns + nr + (uint32_t)(nsolo * 3 / 4));
+        }
+        crit += smax;
     }
-    lap("per-cell packing");
+    // two trailing idle steps: the kernel reads entries t+1 and t+2 ahead
+    for (int pad = 0; pad < 2; ++pad)
+        for (int g = 0; g < G; ++g)
+            o.a().entries.push_back(make_entry(encode_slots(nrows + 2 * g, nrows + 2 * g + 1, false, geo.L), 0.0f, hy.c, hy));
+    o.n_steps = stepcur + 2;
+    o.crit = crit;
+    o.n_rows = (uint32_t)nrows;
+    o.n_order = m;
+    return true;
+}
 
-    // Limits of one chunk: S bytes of schedule, R bytes of rows, 16 + 2 S + R <= budget.  Chosen to
-    // cut as few cells as possible; when every cell fits as it is nothing is cut (and the caps below
-    // are the actual maxima, not these limits).
-    int64_t lim_s = 0, lim_r = 0;
-    {
-        int64_t max_s = min_sched, max_r = min_rows;
-        bool any_over = false;
+// Route 1: every cell packed on the host as a single chunk, unless it cannot possibly fit.
+void Builder::pack_cells_on_host() {
+    reserve_huge(co, (size_t)ncell);
+    co.resize((size_t)ncell);
+    oversize.assign((size_t)ncell, 0);
+    parallel_for((size_t)ncell, 1, nthreads, [&](Scratch& sc, size_t c0, size_t c1) {
+        for (size_t c = c0; c < c1; ++c) {
+            if (cell_nnz((int64_t)c) == 0) continue;  // (an empty cell: place_chunks() writes zeros)
+            CellOut& o = co[c];
+            load_cell((int64_t)c, sc.sel);
+            int nu, ni;
+            distinct_rows(sc.sel, sc, nu, ni);
+            if (!rows_fit(nu + ni) || !pack_chunk(sc.sel, o, sc)) {
+                o = CellOut{};
+                o.nu = (uint32_t)nu;  // kept for the limit search below
+                o.ni = (uint32_t)ni;
+                o.n_order = (int64_t)sc.sel.size();
+                oversize[c] = 1;
+            }
+        }
+    });
+    lap("per-cell packing");
+}
+
+// ---- chunk limits ---------------------------------------------------------------------------------------------------
+// Limits of one chunk: S bytes of schedule, R bytes of rows, 16 + 2 S + R <= budget.  Chosen to cut as few cells as
+// possible; when every cell fits as it is nothing is cut (and the caps are the actual maxima, not these limits).
+// Then `todo`: the cells over the limits.
+void Builder::chunk_limits() {
+    int64_t max_s = min_sched, max_r = min_rows;
+    bool any_over = false;
+    for (int64_t c = 0; c < ncell; ++c) {
+        const CellOut& o = co[(size_t)c];
+        if (oversize[(size_t)c]) {
+            any_over = true;
+            continue;
+        }
+        if (o.n_steps == 0) continue;
+        max_s = std::max(max_s, sched_bytes_for(geo, W, (int)(o.nu + o.ni), (int64_t)o.n_steps));
+        max_r = std::max(max_r, rows_bytes_for(geo, (int)(o.nu + o.ni)));
+    }
+    if (!any_over && 2 * max_s + max_r <= avail) {
+        lim_s = max_s;
+        lim_r = max_r;
+    } else {
+        constexpr int kCand = 48;
+        // per cell, once: the bytes it needs (an unpacked -- oversize -- cell: steps guessed from its rating count)
+        std::vector<int64_t> need_s((size_t)ncell, 0), need_r((size_t)ncell, 0);
+        int64_t max_need_s = max_s;  // the cells that will be cut count too: when ONLY they are large (an item with
+                                     // a tile of its own), the candidates must not stop at the small cells' sizes
         for (int64_t c = 0; c < ncell; ++c) {
             const CellOut& o = co[(size_t)c];
-            if (oversize[(size_t)c]) {
-                any_over = true;
-                continue;
-            }
-            if (o.n_steps == 0) continue;
-            max_s = std::max(max_s, sched_bytes_for(geo, W, (int)(o.nu + o.ni), (int64_t)o.n_steps));
-            max_r = std::max(max_r, rows_bytes_for(geo, (int)(o.nu + o.ni)));
+            if (o.nu + o.ni == 0) continue;
+            need_r[(size_t)c] = rows_bytes_for(geo, (int)(o.nu + o.ni));
+            need_s[(size_t)c] = oversize[(size_t)c] ? sched_bytes_for(geo, W, (int)(o.nu + o.ni), o.n_order * 2 / G + 2)
+                                                    : sched_bytes_for(geo, W, (int)(o.nu + o.ni), (int64_t)o.n_steps);
+            max_need_s = std::max(max_need_s, need_s[(size_t)c]);
         }
-        if (!any_over && 2 * max_s + max_r <= avail) {
-            lim_s = max_s;
-            lim_r = max_r;
-        } else {
-            constexpr int kCand = 48;
-            // per cell, once: the bytes it needs (an unpacked -- oversize -- cell: steps guessed from its rating count)
-            std::vector<int64_t> need_s((size_t)ncell, 0), need_r((size_t)ncell, 0);
-            int64_t max_need_s = max_s;  // the cells that will be cut count too: when ONLY they are large (an item with
-                                         // a tile of its own), the candidates must not stop at the small cells' sizes
+        // two grids: up to the largest cell that fits as it is (where the optimum usually sits), and from there
+        // up to the largest cell there is
+        const int64_t s_mid = std::min(max_s, (avail - min_rows) / 2);
+        const int64_t s_hi = std::min(max_need_s, (avail - min_rows) / 2);
+        const int n_cand = s_hi > s_mid ? 2 * kCand : kCand;
+        // the candidates are independent: one thread each, the winner (lowest cost, then lowest index) as before
+        std::vector<double> cand_cost((size_t)n_cand + 1, 0.0);
+        std::vector<int64_t> cand_s((size_t)n_cand + 1, 0), cand_r((size_t)n_cand + 1, 0);
+        parallel_for((size_t)n_cand + 1, 1, nthreads, [&](Scratch&, size_t x, size_t) {
+            int64_t S = (int)x <= kCand ? min_sched + (s_mid - min_sched) * (int64_t)x / kCand
+                                        : s_mid + (s_hi - s_mid) * ((int64_t)x - kCand) / kCand;
+            S = (S + 15) & ~(int64_t)15;
+            if (S > (avail - min_rows) / 2) S = ((avail - min_rows) / 2) & ~(int64_t)15;
+            const int64_t R = (avail - 2 * S) & ~(int64_t)15;
+            double cost = 0;
             for (int64_t c = 0; c < ncell; ++c) {
-                const CellOut& o = co[(size_t)c];
-                if (o.nu + o.ni == 0) continue;
-                need_r[(size_t)c] = rows_bytes_for(geo, (int)(o.nu + o.ni));
-                need_s[(size_t)c] = oversize[(size_t)c] ? sched_bytes_for(geo, W, (int)(o.nu + o.ni), o.n_order * 2 / G + 2)
-                                                        : sched_bytes_for(geo, W, (int)(o.nu + o.ni), (int64_t)o.n_steps);
-                max_need_s = std::max(max_need_s, need_s[(size_t)c]);
+                const int64_t rb = need_r[(size_t)c];
+                if (rb == 0) continue;
+                const int64_t sb = need_s[(size_t)c];
+                if (sb <= S && rb <= R && !oversize[(size_t)c]) continue;
+                cost += std::max(1.0, std::max((double)sb / (double)S, (double)rb / (double)R));
             }
-            // two grids: up to the largest cell that fits as it is (where the optimum usually sits), and from there
-            // up to the largest cell there is
-            const int64_t s_mid = std::min(max_s, (avail - min_rows) / 2);
-            const int64_t s_hi = std::min(max_need_s, (avail - min_rows) / 2);
-            const int n_cand = s_hi > s_mid ? 2 * kCand : kCand;
-            // the candidates are independent: one thread each, the winner (lowest cost, then lowest index) as before
-            std::vector<double> cand_cost((size_t)n_cand + 1, 0.0);
-            std::vector<int64_t> cand_s((size_t)n_cand + 1, 0), cand_r((size_t)n_cand + 1, 0);
-            std::atomic<int> next_cand{0};
-            auto eval = [&]() {
-                for (;;) {
-                    const int x = next_cand.fetch_add(1);
-                    if (x > n_cand) break;
-                    int64_t S = x <= kCand ? min_sched + (s_mid - min_sched) * x / kCand
-                                           : s_mid + (s_hi - s_mid) * (x - kCand) / kCand;
-                    S = (S + 15) & ~(int64_t)15;
-                    if (S > (avail - min_rows) / 2) S = ((avail - min_rows) / 2) & ~(int64_t)15;
-                    const int64_t R = (avail - 2 * S) & ~(int64_t)15;
-                    double cost = 0;
-                    for (int64_t c = 0; c < ncell; ++c) {
-                        const int64_t rb = need_r[(size_t)c];
-                        if (rb == 0) continue;
-                        const int64_t sb = need_s[(size_t)c];
-                        if (sb <= S && rb <= R && !oversize[(size_t)c]) continue;
-                        cost += std::max(1.0, std::max((double)sb / (double)S, (double)rb / (double)R));
-                    }
-                    cand_cost[(size_t)x] = cost;
-                    cand_s[(size_t)x] = S;
-                    cand_r[(size_t)x] = R;
-                }
-            };
-            {
-                std::vector<std::thread> th;
-                for (int t = 1; t < std::min(nthreads, n_cand + 1); ++t) th.emplace_back(eval);
-                eval();
-                for (auto& t : th) t.join();
+            cand_cost[x] = cost;
+            cand_s[x] = S;
+            cand_r[x] = R;
+        });
+        double best_cost = -1;
+        for (int x = 0; x <= n_cand; ++x)
+            if (best_cost < 0 || cand_cost[(size_t)x] < best_cost) {
+                best_cost = cand_cost[(size_t)x];
+                lim_s = cand_s[(size_t)x];
+                lim_r = cand_r[(size_t)x];
             }
-            double best_cost = -1;
-            for (int x = 0; x <= n_cand; ++x)
-                if (best_cost < 0 || cand_cost[(size_t)x] < best_cost) {
-                    best_cost = cand_cost[(size_t)x];
-                    lim_s = cand_s[(size_t)x];
-                    lim_r = cand_r[(size_t)x];
-                }
-        }
     }
     lap("  chunk limits");
-
-    // Phase 2: cells over the limits are cut in two (by users or by items, whichever there are more
-    // of; halves balanced by rating count) until every piece fits.
-    std::vector<std::vector<CellOut>> extra;
-    reserve_huge(extra, (size_t)ncell);
-    extra.resize((size_t)ncell);
-    std::vector<int64_t> todo;
     for (int64_t c = 0; c < ncell; ++c) {
         const CellOut& o = co[(size_t)c];
         if (oversize[(size_t)c] ||
@@ -1146,78 +1267,252 @@ int build_schedule(const SchedParams& prm, const int32_t* u, const int32_t* i, c
                                 rows_bytes_for(geo, (int)(o.nu + o.ni)) > lim_r)))
             todo.push_back(c);
     }
-    // [r3] The ratings of the cells that are cut (indices into the caller's arrays), cell after cell in bucket order, and
-    // the sub-cell of each.  The cut tree partitions a cell's range IN PLACE (stably), so every part -- and in the end
-    // every chunk -- is a range of these two arrays, a cell's chunks lie in chain order one behind the other, and the
-    // arrays as they stand are the rating lists the device's EMIT pass takes: no per-part vectors, nothing concatenated.
-    std::vector<uint32_t> part_ratings;
-    std::vector<uint16_t> part_sbs;
-    std::vector<SubDesc> part_subs;  // W*W per chunk, in the order the chunks were accepted
-    if (dev_chunks && !todo.empty()) {
-        // The same cut tree as the host recursion below, grown level by level: a part whose rows fit is a candidate
-        // and the device's COUNT pass says how many steps it packs into; a candidate within the limits is a leaf (a
-        // chunk), everything else is cut at the same pivot the recursion would take.  A leaf's place among its cell's
-        // chunks is its path in the tree (left before right) -- which is its place in the arrays.
-        struct Part {
-            int64_t lo, hi;  // its range of part_ratings
-            int depth;
-            int nu = 0, ni = 0;
-            bool candidate = false;
-            bool by_user = false;   // the cut this part gets if it is not a leaf ...
-            uint32_t pivot = 0;     // ... ids >= pivot go right
-        };
-        struct Leaf {
-            int64_t lo, hi;
-            PackCellInfo ci;
-            int64_t tab;  // its sub-cell table in part_subs
-        };
-        std::vector<Leaf> leaves;
+    reserve_huge(extra, (size_t)ncell);
+    extra.resize((size_t)ncell);
+}
+
+// ---- cut on the host (route 1) --------------------------------------------------------------------------------------
+// Cells over the limits are cut in two (cut_rule) until every piece fits; the pieces come out in chain order.
+void Builder::cut_part(std::vector<RawRat>& part, std::vector<CellOut>& pieces, Scratch& sc) {
+    if (failed.load()) return;
+    int nu, ni;
+    distinct_rows(part, sc, nu, ni);
+    const int nrows = nu + ni;
+    if (addressable(nrows) && rows_bytes_for(geo, nrows) <= lim_r) {
+        CellOut o;
+        if (pack_chunk(part, o, sc) && sched_bytes_for(geo, W, nrows, (int64_t)o.n_steps) <= lim_s) {
+            pieces.push_back(std::move(o));
+            return;
+        }
+    }
+    if (part.size() <= 1) {
+        if (!failed.exchange(1)) fail_msg = "lds: a single rating does not fit the chunk limits";
+        return;
+    }
+    distinct_rows(part, sc, nu, ni);  // (pack_chunk may have overwritten sc.us / sc.is)
+    const CutRule cr = cut_rule(sc.us, sc.is, nu, ni);
+    std::vector<RawRat> left, right;
+    if (cr.midpoint) {
+        left.assign(part.begin(), part.begin() + (long)(part.size() / 2));
+        right.assign(part.begin() + (long)(part.size() / 2), part.end());
+    } else {
+        for (const RawRat& a : part) ((cr.by_user ? a.u : a.i) < cr.pivot ? left : right).push_back(a);
+    }
+    std::vector<RawRat>().swap(part);
+    cut_part(left, pieces, sc);
+    cut_part(right, pieces, sc);
+}
+
+bool Builder::cut_on_host() {
+    parallel_for(todo.size(), 1, nthreads, [&](Scratch& sc, size_t x0, size_t x1) {
+        for (size_t x = x0; x < x1 && !failed.load(); ++x) {
+            const int64_t c = todo[x];
+            std::vector<CellOut> pieces;
+            load_cell(c, sc.sel);
+            cut_part(sc.sel, pieces, sc);
+            if (failed.load() || pieces.empty()) return;
+            co[(size_t)c] = std::move(pieces[0]);
+            extra[(size_t)c].assign(std::make_move_iterator(pieces.begin() + 1), std::make_move_iterator(pieces.end()));
+        }
+    });
+    if (failed.load()) return fail(fail_msg);
+    lap("  chunking");
+    return true;
+}
+
+// ---- cut on the device (route 3) ------------------------------------------------------------------------------------
+// The host only DECIDES the cuts -- from the ids -- and asks the device for the size of every candidate chunk.  The
+// same cut tree as the host recursion, grown level by level: a part whose rows fit is a candidate and the device's COUNT
+// pass says how many steps it packs into; a candidate within the limits is a leaf (a chunk), everything else is cut by
+// cut_rule.  A leaf's place among its cell's chunks is its path in the tree (left before right) -- which is its place in
+// the arrays.
+
+// The bucket order of the cells to be cut, and of those only, with the sub-cell of each rating.  r_at: where each
+// cell's ratings start in part_ratings (todo.size() + 1 entries).
+bool Builder::fetch_cut_cells(std::vector<int64_t>& r_at) {
+    std::vector<int64_t> r_lo(todo.size()), r_len(todo.size());
+    r_at.assign(todo.size() + 1, 0);
+    for (size_t x = 0; x < todo.size(); ++x) {
+        const int64_t c = todo[x];
+        r_lo[x] = bptr[(size_t)(c * WW)];
+        r_len[x] = cell_nnz(c);
+        r_at[x + 1] = r_at[x] + r_len[x];
+    }
+    const int64_t n_cut = r_at[todo.size()];
+    reserve_huge(part_ratings, (size_t)n_cut);
+    part_ratings.resize((size_t)n_cut);
+    if (ext->fetch_sorted_ranges(prm.ingest->ctx, (int64_t)todo.size(), r_lo.data(), r_len.data(), part_ratings.data()) != 0)
+        return fail("build_schedule: could not fetch the bucket order of the cells to be cut from the device");
+    lap("  bucket order of the cut cells to the host");
+    reserve_huge(part_sbs, (size_t)n_cut);
+    part_sbs.resize((size_t)n_cut);
+    parallel_for(todo.size(), 16, nthreads, [&](Scratch&, size_t x0, size_t x1) {
+        for (size_t x = x0; x < x1; ++x) {
+            const int64_t c = todo[x];
+            const int64_t lo = r_lo[x], hi = lo + r_len[x];
+            int sbi = 0;
+            for (int64_t y = lo; y < hi; ++y) {
+                while (bptr[(size_t)(c * WW + sbi + 1)] <= y) ++sbi;
+                part_sbs[(size_t)(r_at[x] + (y - lo))] = (uint16_t)sbi;
+            }
+        }
+    });
+    return true;
+}
+
+// Step 1 of a level: the distinct rows of every part and its cut; whole cells (the roots) are known not to fit: they
+// are cut unseen.
+void Builder::rows_and_cuts(std::vector<Part>& level, bool root) {
+    parallel_for(level.size(), 1, nthreads, [&](Scratch& sc, size_t x0, size_t x1) {
+        for (size_t x = x0; x < x1; ++x) {
+            Part& p = level[x];
+            const size_t m = (size_t)(p.hi - p.lo);
+            sc.us.resize(m);
+            sc.is.resize(m);
+            for (size_t y = 0; y < m; ++y) {
+                const uint32_t j = part_ratings[(size_t)p.lo + y];
+                sc.us[y] = (uint32_t)u[j];
+                sc.is[y] = (uint32_t)i[j];
+            }
+            p.nu = sort_ids(sc.us);
+            p.ni = sort_ids(sc.is);
+            const int nrows = p.nu + p.ni;
+            p.candidate = !root && addressable(nrows) && rows_bytes_for(geo, nrows) <= lim_r;
+            p.cut = cut_rule(sc.us, sc.is, p.nu, p.ni);
+        }
+    });
+}
+
+// Step 2: the candidates' sizes, from the device.
+bool Builder::count_candidates(const std::vector<Part>& level, std::vector<size_t>& cand, std::vector<PackCellInfo>& pinfo) {
+    for (size_t x = 0; x < level.size(); ++x)
+        if (level[x].candidate) cand.push_back(x);
+    pinfo.resize(cand.size());
+    if (cand.empty()) return true;
+    std::vector<int64_t> c_at(cand.size() + 1, 0);
+    for (size_t y = 0; y < cand.size(); ++y) c_at[y + 1] = c_at[y] + (level[cand[y]].hi - level[cand[y]].lo);
+    std::vector<uint32_t> lst;
+    reserve_huge(lst, (size_t)c_at[cand.size()]);
+    lst.resize((size_t)c_at[cand.size()]);
+    std::vector<int64_t> cptr(cand.size() * (size_t)WW + 1, 0);
+    parallel_for(cand.size(), 64, nthreads, [&](Scratch&, size_t y0, size_t y1) {
+        for (size_t y = y0; y < y1; ++y) {
+            const Part& p = level[cand[y]];
+            const size_t m = (size_t)(p.hi - p.lo);
+            std::memcpy(&lst[(size_t)c_at[y]], &part_ratings[(size_t)p.lo], m * sizeof(uint32_t));
+            const uint16_t* sb = &part_sbs[(size_t)p.lo];
+            size_t at = 0;
+            for (int sbi = 0; sbi < WW; ++sbi) {
+                cptr[y * (size_t)WW + (size_t)sbi] = c_at[y] + (int64_t)at;
+                while (at < m && sb[at] == (uint16_t)sbi) ++at;
+            }
+        }
+    });
+    cptr[cand.size() * (size_t)WW] = c_at[cand.size()];
+    clock.tick(clock.lists);
+    if (ext->pack_count_parts(prm.ingest->ctx, (int64_t)cand.size(), lst.data(), (int64_t)lst.size(), cptr.data(),
+                              pinfo.data()) != 0)
+        return fail("build_schedule: the device packer's COUNT pass over the chunks failed");
+    return true;
+}
+
+// Step 3: every part that is not a leaf cut in two, in place -- the next level.
+std::vector<Part> Builder::cut_parts(const std::vector<Part>& level, const std::vector<uint8_t>& is_leaf) {
+    std::vector<Part> next;
+    std::mutex mu;
+    parallel_for(level.size(), 4, nthreads, [&](Scratch& sc, size_t x0, size_t x1) {
+        std::vector<Part> mine;
+        for (size_t x = x0; x < x1 && !failed.load(); ++x) {
+            if (is_leaf[x]) continue;
+            const Part& p = level[x];
+            const int64_t m = p.hi - p.lo;
+            if (m <= 1) {
+                if (!failed.exchange(1)) fail_msg = "lds: a single rating does not fit the chunk limits";
+                break;
+            }
+            if (p.depth >= 62) {
+                if (!failed.exchange(1)) fail_msg = "build_schedule: a cell was cut more than 62 times";
+                break;
+            }
+            int64_t nl;
+            if (p.cut.midpoint) {
+                nl = m / 2;
+            } else {
+                // stable partition of the range in place: the lefts close up (a write never passes the read
+                // position), the rights wait in a buffer and follow
+                const int32_t* key_of = p.cut.by_user ? u : i;
+                const uint32_t pivot = p.cut.pivot;
+                uint32_t* idx = &part_ratings[(size_t)p.lo];
+                uint16_t* sb = &part_sbs[(size_t)p.lo];
+                sc.hold_idx.clear();
+                sc.hold_sb.clear();
+                nl = 0;
+                for (int64_t y = 0; y < m; ++y) {
+                    if ((uint32_t)key_of[idx[y]] < pivot) {
+                        idx[nl] = idx[y];
+                        sb[nl] = sb[y];
+                        ++nl;
+                    } else {
+                        sc.hold_idx.push_back(idx[y]);
+                        sc.hold_sb.push_back(sb[y]);
+                    }
+                }
+                std::memcpy(idx + nl, sc.hold_idx.data(), sc.hold_idx.size() * sizeof(uint32_t));
+                std::memcpy(sb + nl, sc.hold_sb.data(), sc.hold_sb.size() * sizeof(uint16_t));
+            }
+            Part l, r2;
+            l.depth = r2.depth = p.depth + 1;
+            l.lo = p.lo;
+            l.hi = r2.lo = p.lo + nl;
+            r2.hi = p.hi;
+            mine.push_back(l);
+            mine.push_back(r2);
+        }
+        std::lock_guard<std::mutex> lk(mu);
+        next.insert(next.end(), mine.begin(), mine.end());
+    });
+    return next;
+}
+
+// A cell's chunks in chain order = its leaves by position: co[c] and extra[c] of every cut cell.
+bool Builder::chunks_from_leaves(std::vector<Leaf>& leaves, const std::vector<int64_t>& r_at) {
+    std::sort(leaves.begin(), leaves.end(), [](const Leaf& a, const Leaf& b) { return a.lo < b.lo; });
+    auto chunk_of = [&](const Leaf& lf) {
+        CellOut o;
+        o.nu = lf.ci.nu;
+        o.ni = lf.ci.ni;
+        o.n_steps = lf.ci.n_steps;
+        o.crit = lf.ci.crit;
+        o.has_run = lf.ci.has_run != 0;
+        o.n_rows = lf.ci.nu + lf.ci.ni;
+        o.n_order = lf.hi - lf.lo;
+        o.dev_part = true;
+        o.part_lo = lf.lo;
+        return o;
+    };
+    size_t at = 0;
+    for (size_t x = 0; x < todo.size(); ++x) {
+        size_t end = at;
+        while (end < leaves.size() && leaves[end].lo < r_at[x + 1]) ++end;
+        // (the leaves of a cell tile its range: first at its start, each at the end of the one before, last at its end)
+        bool tiles = end > at && leaves[at].lo == r_at[x] && leaves[end - 1].hi == r_at[x + 1];
+        for (size_t y = at + 1; tiles && y < end; ++y) tiles = leaves[y].lo == leaves[y - 1].hi;
+        if (!tiles) return fail("build_schedule: internal error, a cut cell's chunks do not tile its ratings");
+        const int64_t c = todo[x];
+        co[(size_t)c] = chunk_of(leaves[at]);
+        extra[(size_t)c].reserve(end - at - 1);
+        for (size_t y = at + 1; y < end; ++y) extra[(size_t)c].push_back(chunk_of(leaves[y]));
+        at = end;
+    }
+    return true;
+}
+
+bool Builder::cut_on_device() {
+    if (!todo.empty()) {
+        std::vector<int64_t> r_at;
+        if (!fetch_cut_cells(r_at)) return false;
         std::vector<Part> level;
         level.reserve(todo.size());
-        // the bucket order of the cells to be cut, and of those only
-        std::vector<int64_t> r_lo(todo.size()), r_len(todo.size()), r_at(todo.size() + 1, 0);
-        for (size_t x = 0; x < todo.size(); ++x) {
-            const int64_t c = todo[x];
-            r_lo[x] = bptr[(size_t)(c * WW)];
-            r_len[x] = bptr[(size_t)((c + 1) * WW)] - r_lo[x];
-            r_at[x + 1] = r_at[x] + r_len[x];
-        }
-        const int64_t n_cut = r_at[todo.size()];
-        reserve_huge(part_ratings, (size_t)n_cut);
-        part_ratings.resize((size_t)n_cut);
-        if (ext->fetch_sorted_ranges(prm.ingest->ctx, (int64_t)todo.size(), r_lo.data(), r_len.data(), part_ratings.data()) != 0) {
-            err = "build_schedule: could not fetch the bucket order of the cells to be cut from the device";
-            return -1;
-        }
-        lap("  bucket order of the cut cells to the host");
-        reserve_huge(part_sbs, (size_t)n_cut);
-        part_sbs.resize((size_t)n_cut);
-        auto on_all_threads = [&](size_t n_items, size_t grain, const std::function<void(size_t, size_t)>& body) {
-            std::atomic<size_t> nx{0};
-            auto work = [&]() {
-                for (;;) {
-                    const size_t x0 = nx.fetch_add(grain);
-                    if (x0 >= n_items) break;
-                    body(x0, std::min(n_items, x0 + grain));
-                }
-            };
-            std::vector<std::thread> th;
-            const size_t want = (n_items + grain - 1) / grain;
-            for (int t = 1; t < (int)std::min<size_t>((size_t)nthreads, want); ++t) th.emplace_back(work);
-            work();
-            for (auto& t : th) t.join();
-        };
-        on_all_threads(todo.size(), 16, [&](size_t x0, size_t x1) {
-            for (size_t x = x0; x < x1; ++x) {
-                const int64_t c = todo[x];
-                const int64_t lo = r_lo[x], hi = lo + r_len[x];
-                int sbi = 0;
-                for (int64_t y = lo; y < hi; ++y) {
-                    while (bptr[(size_t)(c * WW + sbi + 1)] <= y) ++sbi;
-                    part_sbs[(size_t)(r_at[x] + (y - lo))] = (uint16_t)sbi;
-                }
-            }
-        });
         for (size_t x = 0; x < todo.size(); ++x) {
             Part p;
             p.lo = r_at[x];
@@ -1225,414 +1520,134 @@ int build_schedule(const SchedParams& prm, const int32_t* u, const int32_t* i, c
             p.depth = 0;
             level.push_back(p);
         }
+        std::vector<Leaf> leaves;
         bool root = true;
-        double t_rows = 0, t_lists = 0, t_count = 0, t_cut = 0;  // MFSGD_SCHED_TRACE: where the levels' time goes
         int n_levels = 0;
-        auto since = [](std::chrono::steady_clock::time_point& t) {
-            const auto now = std::chrono::steady_clock::now();
-            const double d = std::chrono::duration<double>(now - t).count();
-            t = now;
-            return d;
-        };
-        auto t_lvl = std::chrono::steady_clock::now();
+        double idle = 0;
         while (!level.empty() && !failed.load()) {
             ++n_levels;
-            (void)since(t_lvl);
-            // 1. distinct rows of every part; whole cells (the roots) are known not to fit: they are cut unseen
-            on_all_threads(level.size(), 1, [&](size_t x0, size_t x1) {
-                thread_local std::vector<uint32_t> us, is;
-                for (size_t x = x0; x < x1; ++x) {
-                    Part& p = level[x];
-                    const size_t m = (size_t)(p.hi - p.lo);
-                    us.resize(m);
-                    is.resize(m);
-                    for (size_t y = 0; y < m; ++y) {
-                        const uint32_t j = part_ratings[(size_t)p.lo + y];
-                        us[y] = (uint32_t)u[j];
-                        is[y] = (uint32_t)i[j];
-                    }
-                    std::sort(us.begin(), us.end());
-                    std::sort(is.begin(), is.end());
-                    auto distinct = [](const std::vector<uint32_t>& v) {
-                        int n = 0;
-                        for (size_t y = 0; y < v.size(); ++y) n += y == 0 || v[y] != v[y - 1];
-                        return n;
-                    };
-                    p.nu = distinct(us);
-                    p.ni = distinct(is);
-                    const int nrows = p.nu + p.ni;
-                    p.candidate = !root && addressable(nrows) && rows_bytes_for(geo, nrows) <= lim_r;
-                    // the pivot of the cut, should there be one: the first distinct id (position >= 1) at which the
-                    // ratings of the ids before it reach half of the part (the host recursion's rule)
-                    p.by_user = (p.nu >= p.ni && p.nu > 1) || p.ni <= 1;
-                    const std::vector<uint32_t>& v = p.by_user ? us : is;
-                    const int nid = p.by_user ? p.nu : p.ni;
-                    const int64_t half = (int64_t)v.size() / 2;
-                    int seen = 0;  // distinct ids passed
-                    p.pivot = v.empty() ? 0u : v[0];
-                    for (size_t y = 0; y < v.size(); ++y) {
-                        if (y > 0 && v[y] != v[y - 1]) {
-                            // y ratings belong to the `seen + 1` ids before v[y]
-                            ++seen;
-                            p.pivot = v[y];
-                            if ((int64_t)y >= half || seen >= nid - 1) break;
-                        }
-                    }
-                }
-            });
-            t_rows += since(t_lvl);
-            // 2. the candidates' sizes, from the device
+            clock.tick(idle);
+            rows_and_cuts(level, root);
+            clock.tick(clock.rows);
             std::vector<size_t> cand;
-            for (size_t x = 0; x < level.size(); ++x)
-                if (level[x].candidate) cand.push_back(x);
-            std::vector<PackCellInfo> pinfo(cand.size());
-            std::vector<SubDesc> psubs(dev_tables ? 0 : cand.size() * (size_t)WW);  // (device tables: not fetched)
-            if (!cand.empty()) {
-                std::vector<int64_t> c_at(cand.size() + 1, 0);
-                for (size_t y = 0; y < cand.size(); ++y) c_at[y + 1] = c_at[y] + (level[cand[y]].hi - level[cand[y]].lo);
-                std::vector<uint32_t> lst;
-                reserve_huge(lst, (size_t)c_at[cand.size()]);
-                lst.resize((size_t)c_at[cand.size()]);
-                std::vector<int64_t> cptr(cand.size() * (size_t)WW + 1, 0);
-                on_all_threads(cand.size(), 64, [&](size_t y0, size_t y1) {
-                    for (size_t y = y0; y < y1; ++y) {
-                        const Part& p = level[cand[y]];
-                        const size_t m = (size_t)(p.hi - p.lo);
-                        std::memcpy(&lst[(size_t)c_at[y]], &part_ratings[(size_t)p.lo], m * sizeof(uint32_t));
-                        const uint16_t* sb = &part_sbs[(size_t)p.lo];
-                        size_t at = 0;
-                        for (int sbi = 0; sbi < WW; ++sbi) {
-                            cptr[y * (size_t)WW + (size_t)sbi] = c_at[y] + (int64_t)at;
-                            while (at < m && sb[at] == (uint16_t)sbi) ++at;
-                        }
-                    }
-                });
-                cptr[cand.size() * (size_t)WW] = c_at[cand.size()];
-                t_lists += since(t_lvl);
-                if (ext->pack_count_parts(prm.ingest->ctx, (int64_t)cand.size(), lst.data(), (int64_t)lst.size(), cptr.data(),
-                                          pinfo.data(), dev_tables ? nullptr : psubs.data()) != 0) {
-                    err = "build_schedule: the device packer's COUNT pass over the chunks failed";
-                    return -1;
-                }
-            }
-            t_count += since(t_lvl);
-            // 3. leaves and cuts
-            std::vector<Part> next;
+            std::vector<PackCellInfo> pinfo;
+            if (!count_candidates(level, cand, pinfo)) return false;
+            clock.tick(clock.count);
+            // leaves: the candidates within the limits
             std::vector<uint8_t> is_leaf(level.size(), 0);
             for (size_t y = 0; y < cand.size(); ++y) {
                 const Part& p = level[cand[y]];
                 const PackCellInfo& ci = pinfo[y];
                 if (ci.status == 0 && sched_bytes_for(geo, W, p.nu + p.ni, (int64_t)ci.n_steps) <= lim_s) {
-                    Leaf lf;
-                    lf.lo = p.lo;
-                    lf.hi = p.hi;
-                    lf.ci = ci;
-                    lf.tab = (int64_t)(part_subs.size() / (size_t)WW);
-                    if (!dev_tables)
-                        part_subs.insert(part_subs.end(), psubs.begin() + (long)(y * (size_t)WW), psubs.begin() + (long)((y + 1) * (size_t)WW));
-                    leaves.push_back(lf);
+                    leaves.push_back(Leaf{p.lo, p.hi, ci});
                     is_leaf[cand[y]] = 1;
                 }
             }
-            {
-                std::mutex mu;
-                on_all_threads(level.size(), 4, [&](size_t x0, size_t x1) {
-                    thread_local std::vector<uint32_t> hold_idx;
-                    thread_local std::vector<uint16_t> hold_sb;
-                    std::vector<Part> mine;
-                    for (size_t x = x0; x < x1 && !failed.load(); ++x) {
-                        if (is_leaf[x]) continue;
-                        const Part& p = level[x];
-                        const int64_t m = p.hi - p.lo;
-                        if (m <= 1) {
-                            if (!failed.exchange(1)) fail_msg = "lds: a single rating does not fit the chunk limits";
-                            break;
-                        }
-                        if (p.depth >= 62) {
-                            if (!failed.exchange(1)) fail_msg = "build_schedule: a cell was cut more than 62 times";
-                            break;
-                        }
-                        int64_t nl;
-                        if (p.nu <= 1 && p.ni <= 1) {
-                            nl = m / 2;  // the same (user, item) pair many times over: any cut of the sequence will do
-                        } else {
-                            // stable partition of the range in place: the lefts close up (a write never passes the
-                            // read position), the rights wait in a buffer and follow
-                            const int32_t* key_of = p.by_user ? u : i;
-                            const uint32_t pivot = p.pivot;
-                            uint32_t* idx = &part_ratings[(size_t)p.lo];
-                            uint16_t* sb = &part_sbs[(size_t)p.lo];
-                            hold_idx.clear();
-                            hold_sb.clear();
-                            nl = 0;
-                            for (int64_t y = 0; y < m; ++y) {
-                                if ((uint32_t)key_of[idx[y]] < pivot) {
-                                    idx[nl] = idx[y];
-                                    sb[nl] = sb[y];
-                                    ++nl;
-                                } else {
-                                    hold_idx.push_back(idx[y]);
-                                    hold_sb.push_back(sb[y]);
-                                }
-                            }
-                            std::memcpy(idx + nl, hold_idx.data(), hold_idx.size() * sizeof(uint32_t));
-                            std::memcpy(sb + nl, hold_sb.data(), hold_sb.size() * sizeof(uint16_t));
-                        }
-                        Part l, r2;
-                        l.depth = r2.depth = p.depth + 1;
-                        l.lo = p.lo;
-                        l.hi = r2.lo = p.lo + nl;
-                        r2.hi = p.hi;
-                        mine.push_back(l);
-                        mine.push_back(r2);
-                    }
-                    std::lock_guard<std::mutex> lk(mu);
-                    next.insert(next.end(), mine.begin(), mine.end());
-                });
-            }
-            level = std::move(next);
+            level = cut_parts(level, is_leaf);
             root = false;
-            t_cut += since(t_lvl);
+            clock.tick(clock.cut);
         }
         if (trace)
             std::fprintf(stderr, "[schedule]     %d levels: rows + pivots %.3f s, candidate lists %.3f s, device COUNT %.3f s, leaves + cuts %.3f s\n",
-                         n_levels, t_rows, t_lists, t_count, t_cut);
-        if (!failed.load()) {
-            // a cell's chunks in chain order = its leaves by position
-            std::sort(leaves.begin(), leaves.end(), [](const Leaf& a, const Leaf& b) { return a.lo < b.lo; });
-            size_t at = 0;
-            for (size_t x = 0; x < todo.size() && !failed.load(); ++x) {
-                size_t end = at;
-                while (end < leaves.size() && leaves[end].lo < r_at[x + 1]) ++end;
-                // (the leaves of a cell tile its range: first at its start, each at the end of the one before, last at its end)
-                bool tiles = end > at && leaves[at].lo == r_at[x] && leaves[end - 1].hi == r_at[x + 1];
-                for (size_t y = at + 1; tiles && y < end; ++y) tiles = leaves[y].lo == leaves[y - 1].hi;
-                if (!tiles) {
-                    if (!failed.exchange(1)) fail_msg = "build_schedule: internal error, a cut cell's chunks do not tile its ratings";
-                    break;
-                }
-                const int64_t c = todo[x];
-                auto chunk_of = [&](const Leaf& lf) {
-                    CellOut o;
-                    o.nu = lf.ci.nu;
-                    o.ni = lf.ci.ni;
-                    o.n_steps = lf.ci.n_steps;
-                    o.crit = lf.ci.crit;
-                    o.has_run = lf.ci.has_run != 0;
-                    o.n_rows = lf.ci.nu + lf.ci.ni;
-                    o.n_order = lf.hi - lf.lo;
-                    o.dev_part = true;
-                    o.part_lo = lf.lo;
-                    o.part_tab = lf.tab;
-                    return o;
-                };
-                co[(size_t)c] = chunk_of(leaves[at]);
-                extra[(size_t)c].reserve(end - at - 1);
-                for (size_t y = at + 1; y < end; ++y) extra[(size_t)c].push_back(chunk_of(leaves[y]));
-                at = end;
-            }
-        }
-    } else {
-        std::atomic<int64_t> next_todo{0};
-        run_parallel([&](Scratch& sc, std::vector<RawRat>& sel) {
-            std::vector<CellOut> pieces;
-            std::function<void(std::vector<RawRat>&)> cut = [&](std::vector<RawRat>& part) {
-                if (failed.load()) return;
-                int nu, ni;
-                distinct_rows(part, sc, nu, ni);
-                const int nrows = nu + ni;
-                if (addressable(nrows) && rows_bytes_for(geo, nrows) <= lim_r) {
-                    CellOut o;
-                    if (pack_chunk(part, o, sc) &&
-                        sched_bytes_for(geo, W, nrows, (int64_t)o.n_steps) <= lim_s) {
-                        pieces.push_back(std::move(o));
-                        return;
-                    }
-                }
-                if (part.size() <= 1) {
-                    if (!failed.exchange(1)) fail_msg = "lds: a single rating does not fit the chunk limits";
-                    return;
-                }
-                // (distinct_rows left the sorted distinct ids in sc.us / sc.is; pack_chunk may have
-                // overwritten them, so recompute)
-                distinct_rows(part, sc, nu, ni);
-                if (nu <= 1 && ni <= 1) {
-                    // the same (user, item) pair many times over: any cut of the sequence will do
-                    std::vector<RawRat> left(part.begin(), part.begin() + (long)(part.size() / 2));
-                    std::vector<RawRat> right(part.begin() + (long)(part.size() / 2), part.end());
-                    std::vector<RawRat>().swap(part);
-                    cut(left);
-                    cut(right);
-                    return;
-                }
-                const bool by_user = (nu >= ni && nu > 1) || ni <= 1;
-                const std::vector<uint32_t>& ids = by_user ? sc.us : sc.is;
-                const int nid = by_user ? nu : ni;
-                std::vector<int64_t> cnt((size_t)nid, 0);
-                for (const RawRat& a : part) {
-                    const uint32_t key = by_user ? a.u : a.i;
-                    cnt[(size_t)(std::lower_bound(ids.begin(), ids.begin() + nid, key) - ids.begin())]++;
-                }
-                int64_t half = (int64_t)part.size() / 2, acc = 0;
-                int cutpos = 1;
-                for (int x = 0; x < nid - 1; ++x) {
-                    acc += cnt[(size_t)x];
-                    cutpos = x + 1;
-                    if (acc >= half) break;
-                }
-                const uint32_t pivot = ids[(size_t)cutpos];  // ids >= pivot go right
-                std::vector<RawRat> left, right;
-                for (const RawRat& a : part) ((by_user ? a.u : a.i) < pivot ? left : right).push_back(a);
-                std::vector<RawRat>().swap(part);
-                cut(left);
-                cut(right);
-            };
-            for (;;) {
-                const int64_t x = next_todo.fetch_add(1);
-                if (x >= (int64_t)todo.size() || failed.load()) break;
-                const int64_t c = todo[(size_t)x];
-                load_cell(c, sel);
-                pieces.clear();
-                cut(sel);
-                if (failed.load() || pieces.empty()) break;
-                co[(size_t)c] = std::move(pieces[0]);
-                extra[(size_t)c].assign(std::make_move_iterator(pieces.begin() + 1),
-                                        std::make_move_iterator(pieces.end()));
-            }
-        });
+                         n_levels, clock.rows, clock.lists, clock.count, clock.cut);
+        if (!failed.load() && !chunks_from_leaves(leaves, r_at)) return false;
     }
-    if (failed.load()) {
-        err = fail_msg;
-        return -1;
-    }
+    if (failed.load()) return fail(fail_msg);
     lap("  chunking");
+    return true;
+}
 
-    // ---- concatenate: first chunks at their cell index, the rest behind B*B ---
+// ---- assembly: first chunks at their cell index, the rest behind B*B ------------------------------------------------
+// Descriptors, offsets, LDS capacities and the canonical order's cell starts; the sub-cell tables too when the host
+// holds them (route 1).
+bool Builder::place_chunks(bool host_tables) {
     out = Schedule{};
     out.geo = geo;
     out.B = B;
     out.W = W;
     out.nnz = n;
-    int64_t n_descs = ncell;
+    n_descs = ncell;
     for (int64_t c = 0; c < ncell; ++c) n_descs += (int64_t)extra[(size_t)c].size();
-    if (n_descs > 0x7FFFFFFFll / WW) {
-        err = "build_schedule: too many chunks";
-        return -1;
-    }
+    if (n_descs > 0x7FFFFFFFll / WW) return fail("build_schedule: too many chunks");
     reserve_huge(out.cells, (size_t)n_descs);
     out.cells.resize((size_t)n_descs);
-    // (with the chunks packed on the device the sub-cell tables are assembled there: dev_tables above)
-    const bool host_tables = !(dev_tables && dev_chunks);
     out.n_sub_recs = n_descs * WW + 2;
     if (host_tables) {
         reserve_huge(out.subs, (size_t)(n_descs * WW) + 2);
         out.subs.resize((size_t)(n_descs * WW) + 2);  // +16 B: the staging DMA reads whole 16-byte units
         out.subs[(size_t)(n_descs * WW)] = out.subs[(size_t)(n_descs * WW) + 1] = SubDesc{0, 0};
     }
-    std::vector<const CellOut*> by_desc((size_t)n_descs, nullptr);
-    int64_t tot_rows = 0, tot_steps = 0;
-    int64_t sched_cap = 0, rows_cap = 0;
-    int64_t n_dev_cells = 0, n_dev_parts = 0;
-    // per cell, compact (the loops over rounds below walk the cells with a stride of B + 1: these stay in cache,
-    // the CellOut records do not): ratings and critical steps of all its chunks; the cells that are more than one
-    // device-packed chunk, whose pieces have to be walked one by one
-    std::vector<int64_t> cell_nnz((size_t)ncell), cell_crit((size_t)ncell);
-    std::vector<int64_t> walk_cells;
-    {
-        // pass 1, sequential and light: descriptor numbers, the chain of a cell's chunks, running offsets
-        int64_t next_desc = ncell;
-        auto place = [&](int64_t d, const CellOut& o, uint32_t next) -> bool {
-            if (tot_rows > 0xFFFFFFFFll - (int64_t)o.n_rows || tot_steps > 0xFFFFFFFFll - o.n_steps) return false;
-            CellDesc& cdsc = out.cells[(size_t)d];
-            cdsc = CellDesc{};
-            cdsc.row_off = (uint32_t)tot_rows;
-            cdsc.ent_off = (uint32_t)tot_steps;
-            cdsc.next = next;
-            by_desc[(size_t)d] = &o;
-            tot_rows += (int64_t)o.n_rows;
-            tot_steps += o.n_steps;
-            n_dev_cells += o.dev ? 1 : 0;
-            n_dev_parts += o.dev_part ? 1 : 0;
-            return true;
-        };
-        for (int64_t c = 0; c < ncell; ++c) {
-            const std::vector<CellOut>& ex = extra[(size_t)c];
-            bool ok = place(c, co[(size_t)c], ex.empty() ? 0u : (uint32_t)next_desc);
-            int64_t nnz_c = co[(size_t)c].n_order, rows_c = (int64_t)co[(size_t)c].n_rows;
-            int64_t crit_c = co[(size_t)c].crit;
-            for (size_t x = 0; ok && x < ex.size(); ++x) {
-                ok = place(next_desc, ex[x], x + 1 < ex.size() ? (uint32_t)(next_desc + 1) : 0u);
-                ++next_desc;
-                nnz_c += ex[x].n_order;
-                rows_c = std::max(rows_c, (int64_t)ex[x].n_rows);
-                crit_c += ex[x].crit;
-            }
-            if (!ok) {
-                err = "build_schedule: schedule exceeds 32-bit offsets";
-                return -1;
-            }
-            if (!ex.empty()) out.split_cells++;
-            if (!ex.empty() || !co[(size_t)c].dev) walk_cells.push_back(c);
-            cell_nnz[(size_t)c] = nnz_c;
-            cell_crit[(size_t)c] = crit_c;
-            out.max_cell_nnz = std::max(out.max_cell_nnz, nnz_c);
-            out.max_cell_rows = std::max(out.max_cell_rows, rows_c);
-            out.max_cell_steps = std::max(out.max_cell_steps, crit_c);
+    by_desc.assign((size_t)n_descs, nullptr);
+    // per cell, compact (the loops over rounds below walk the cells with a stride of B + 1: these stay in cache, the
+    // CellOut records do not): ratings and critical steps of all its chunks
+    std::vector<int64_t> cell_nnz_all((size_t)ncell), cell_crit((size_t)ncell);
+    // pass 1, sequential and light: descriptor numbers, the chain of a cell's chunks, running offsets
+    int64_t next_desc = ncell;
+    auto place = [&](int64_t d, const CellOut& o, uint32_t next) -> bool {
+        if (tot_rows > 0xFFFFFFFFll - (int64_t)o.n_rows || tot_steps > 0xFFFFFFFFll - o.n_steps) return false;
+        CellDesc& cdsc = out.cells[(size_t)d];
+        cdsc = CellDesc{};
+        cdsc.row_off = (uint32_t)tot_rows;
+        cdsc.ent_off = (uint32_t)tot_steps;
+        cdsc.next = next;
+        by_desc[(size_t)d] = &o;
+        tot_rows += (int64_t)o.n_rows;
+        tot_steps += o.n_steps;
+        return true;
+    };
+    for (int64_t c = 0; c < ncell; ++c) {
+        const std::vector<CellOut>& ex = extra[(size_t)c];
+        bool ok = place(c, co[(size_t)c], ex.empty() ? 0u : (uint32_t)next_desc);
+        int64_t nnz_c = co[(size_t)c].n_order, rows_c = (int64_t)co[(size_t)c].n_rows;
+        int64_t crit_c = co[(size_t)c].crit;
+        for (size_t x = 0; ok && x < ex.size(); ++x) {
+            ok = place(next_desc, ex[x], x + 1 < ex.size() ? (uint32_t)(next_desc + 1) : 0u);
+            ++next_desc;
+            nnz_c += ex[x].n_order;
+            rows_c = std::max(rows_c, (int64_t)ex[x].n_rows);
+            crit_c += ex[x].crit;
         }
-        // pass 2, parallel over the descriptors: the rest of each descriptor, its sub-cell table, the LDS capacities
-        std::atomic<int64_t> nx{0};
-        std::mutex mx;
-        auto fill = [&]() {
-            int64_t my_sched = 0, my_rows = 0;
-            for (;;) {
-                const int64_t d0 = nx.fetch_add(4096);
-                if (d0 >= n_descs) break;
-                for (int64_t d = d0; d < std::min(n_descs, d0 + 4096); ++d) {
-                    const CellOut& o = *by_desc[(size_t)d];
-                    CellDesc& cdsc = out.cells[(size_t)d];
-                    cdsc.n_steps = o.n_steps | (o.has_run ? kCellCritical : 0u);
-                    cdsc.nu = (uint16_t)o.nu;
-                    cdsc.ni = (uint16_t)o.ni;
-                    o.desc = d;
-                    if (!host_tables) {
-                        // (the device assembles the table)
-                    } else if (o.dev && o.a().subs.empty() && d < ncell)
-                        std::memcpy(&out.subs[(size_t)(d * WW)], &dsubs[(size_t)(d * WW)], sizeof(SubDesc) * (size_t)WW);
-                    else if (o.dev_part)
-                        std::memcpy(&out.subs[(size_t)(d * WW)], &part_subs[(size_t)(o.part_tab * WW)], sizeof(SubDesc) * (size_t)WW);
-                    else
-                        for (int x = 0; x < WW; ++x)
-                            out.subs[(size_t)(d * WW + x)] = o.a().subs.empty() ? SubDesc{0, 0} : o.a().subs[(size_t)x];
-                    if (o.n_steps != 0) {
-                        my_sched = std::max(my_sched, sched_bytes_for(geo, W, (int)(o.nu + o.ni), (int64_t)o.n_steps));
-                        my_rows = std::max(my_rows, rows_bytes_for(geo, (int)(o.nu + o.ni)));
-                    }
-                }
-            }
-            std::lock_guard<std::mutex> lk(mx);
-            sched_cap = std::max(sched_cap, my_sched);
-            rows_cap = std::max(rows_cap, my_rows);
-        };
-        std::vector<std::thread> th;
-        const int nt = n_descs >= 65536 ? nthreads : 1;
-        for (int t = 1; t < nt; ++t) th.emplace_back(fill);
-        fill();
-        for (auto& t : th) t.join();
+        if (!ok) return fail("build_schedule: schedule exceeds 32-bit offsets");
+        if (!ex.empty()) out.split_cells++;
+        if (!ex.empty() || !co[(size_t)c].dev) walk_cells.push_back(c);
+        cell_nnz_all[(size_t)c] = nnz_c;
+        cell_crit[(size_t)c] = crit_c;
+        out.max_cell_nnz = std::max(out.max_cell_nnz, nnz_c);
+        out.max_cell_rows = std::max(out.max_cell_rows, rows_c);
+        out.max_cell_steps = std::max(out.max_cell_steps, crit_c);
     }
+    // pass 2, parallel over the descriptors: the rest of each descriptor, its sub-cell table, the LDS capacities
+    int64_t sched_cap = min_sched, rows_cap = min_rows;
+    std::mutex mx;
+    parallel_for((size_t)n_descs, 4096, n_descs >= 65536 ? nthreads : 1, [&](Scratch&, size_t d0, size_t d1) {
+        int64_t my_sched = 0, my_rows = 0;
+        for (size_t d = d0; d < d1; ++d) {
+            const CellOut& o = *by_desc[d];
+            CellDesc& cdsc = out.cells[d];
+            cdsc.n_steps = o.n_steps | (o.has_run ? kCellCritical : 0u);
+            cdsc.nu = (uint16_t)o.nu;
+            cdsc.ni = (uint16_t)o.ni;
+            o.desc = (int64_t)d;
+            if (host_tables)
+                for (int x = 0; x < WW; ++x)
+                    out.subs[d * (size_t)WW + (size_t)x] = o.a().subs.empty() ? SubDesc{0, 0} : o.a().subs[(size_t)x];
+            if (o.n_steps != 0) {
+                my_sched = std::max(my_sched, sched_bytes_for(geo, W, (int)(o.nu + o.ni), (int64_t)o.n_steps));
+                my_rows = std::max(my_rows, rows_bytes_for(geo, (int)(o.nu + o.ni)));
+            }
+        }
+        std::lock_guard<std::mutex> lk(mx);
+        sched_cap = std::max(sched_cap, my_sched);
+        rows_cap = std::max(rows_cap, my_rows);
+    });
     mark_lone_tiles(out.cells, B, geo, tile_items);
     lap("  offsets");
-    {
-        sched_cap = std::max(sched_cap, min_sched);
-        rows_cap = std::max(rows_cap, min_rows);
-        const int64_t need = 16 + 2 * sched_cap + rows_cap;
-        if (need > prm.lds_budget) {
-            err = "build_schedule: internal error, chunks need " + std::to_string(need) + " bytes of LDS (budget " +
-                  std::to_string(prm.lds_budget) + ")";
-            return -1;
-        }
-        out.lds_bytes = (int)((need + 15) & ~(int64_t)15);
-        out.sched_cap = (int)sched_cap;
-    }
+    const int64_t need = 16 + 2 * sched_cap + rows_cap;
+    if (need > prm.lds_budget)
+        return fail("build_schedule: internal error, chunks need " + std::to_string(need) + " bytes of LDS (budget " +
+                    std::to_string(prm.lds_budget) + ")");
+    out.lds_bytes = (int)((need + 15) & ~(int64_t)15);
+    out.sched_cap = (int)sched_cap;
     out.total_rows = tot_rows;
     out.total_steps = tot_steps;
     // canonical order: rounds, then blocks; a cell's ratings (all its chunks) are contiguous
@@ -1643,219 +1658,48 @@ int build_schedule(const SchedParams& prm, const int32_t* u, const int32_t* i, c
         for (int b = 0; b < B; ++b) {
             const int64_t c = (int64_t)b * B + (b + rd) % B;
             out.cell_ptr[(size_t)((int64_t)rd * B + b)] = pos;
-            pos += cell_nnz[(size_t)c];
+            pos += cell_nnz_all[(size_t)c];
             worst = std::max(worst, cell_crit[(size_t)c]);
         }
         out.sum_round_steps += worst;
     }
     out.cell_ptr[(size_t)ncell] = pos;
-    if (pos != n) {
-        err = "build_schedule: internal error, packed " + std::to_string(pos) + " of " + std::to_string(n);
-        return -1;
-    }
-    if (n_dev_cells > 0 || n_dev_parts > 0) {
-        // ---- mixed finish: the device writes its cells at their final places (EMIT pass); the chunks of the cells that
-        // were cut are packed there too ([r3], from their rating lists), or -- round 2's form, MFSGD_HOST_CHUNKS -- what
-        // the host packed is scattered behind it
-        MixedPieces mp;
-        std::vector<uint32_t> row_off((size_t)ncell, 0xFFFFFFFFu), ent_off((size_t)ncell, 0u);
-        std::vector<int64_t> ord_off((size_t)ncell, 0);
-        std::vector<uint32_t> p_ro, p_eo;
-        std::vector<int64_t> p_cptr, p_oo, p_desc;  // (p_desc: the chunk descriptor of every part, for the device's final sub-cell table)
-        // (device cells are first chunks, x < ncell, and most of all descriptors: they are skipped through the compact
-        // list of the cells that are anything else)
-        for (int64_t x = 0; x < ncell; ++x) {
-            row_off[(size_t)x] = out.cells[(size_t)x].row_off;
-            ent_off[(size_t)x] = out.cells[(size_t)x].ent_off;
-        }
-        for (int64_t x = 0; x < ncell; ++x) {
-            const int64_t rd = x / B, b = x % B;
-            ord_off[(size_t)(b * B + (b + rd) % B)] = out.cell_ptr[(size_t)x];
-        }
-        std::vector<int64_t> other_descs;
-        for (const int64_t c : walk_cells) {
-            if (!co[(size_t)c].dev) {
-                row_off[(size_t)c] = 0xFFFFFFFFu;
-                ent_off[(size_t)c] = 0u;
-                other_descs.push_back(c);
-            }
-            for (const CellOut& o : extra[(size_t)c]) other_descs.push_back(o.desc);
-        }
-        std::sort(other_descs.begin(), other_descs.end());
-        for (const int64_t x : other_descs) {
-            const CellOut& o = *by_desc[(size_t)x];
-            const CellDesc& d = out.cells[(size_t)x];
-            if (o.dev || o.dev_part) continue;  // (the device's chunks: below, in the order of their rating lists)
-            if (!o.a().rows.empty()) {
-                mp.seg_rows.push_back({(uint64_t)d.row_off, (uint64_t)mp.rows.size(), (uint64_t)o.a().rows.size()});
-                mp.rows.insert(mp.rows.end(), o.a().rows.begin(), o.a().rows.end());
-            }
-            if (!o.a().entries.empty()) {
-                mp.seg_entries.push_back({(uint64_t)d.ent_off * G, (uint64_t)mp.entries.size(), (uint64_t)o.a().entries.size()});
-                mp.entries.insert(mp.entries.end(), o.a().entries.begin(), o.a().entries.end());
-            }
-        }
-        if (n_dev_parts > 0) {
-            // The chunks the device packs, in the order of their ranges of part_ratings (cut cell after cut cell, a
-            // cell's chunks in chain order): where each goes, and its W*W sub-cell starts -- independent per chunk.
-            // A chunk's place in the canonical order is its cell's plus the ratings of the chunks before it, which is
-            // its distance from the first chunk in part_ratings.
-            std::vector<const CellOut*> parts;
-            parts.reserve((size_t)n_dev_parts);
-            std::vector<int64_t> part_cell;
-            part_cell.reserve((size_t)n_dev_parts);
-            for (const int64_t c : walk_cells) {
-                if (co[(size_t)c].dev_part) {
-                    parts.push_back(&co[(size_t)c]);
-                    part_cell.push_back(c);
-                }
-                for (const CellOut& o : extra[(size_t)c])
-                    if (o.dev_part) {
-                        parts.push_back(&o);
-                        part_cell.push_back(c);
-                    }
-            }
-            bool in_order = (int64_t)parts.size() == n_dev_parts && !parts.empty() && parts[0]->part_lo == 0;
-            for (size_t y = 1; in_order && y < parts.size(); ++y) in_order = parts[y]->part_lo == parts[y - 1]->part_lo + parts[y - 1]->n_order;
-            if (!in_order || parts.back()->part_lo + parts.back()->n_order != (int64_t)part_ratings.size()) {
-                err = "build_schedule: internal error, the device-packed chunks do not tile their rating list";
-                return -1;
-            }
-            p_ro.resize(parts.size());
-            p_eo.resize(parts.size());
-            p_oo.resize(parts.size());
-            p_desc.resize(parts.size());
-            p_cptr.assign(parts.size() * (size_t)WW + 1, 0);
-            std::atomic<size_t> nx{0};
-            auto fill = [&]() {
-                for (;;) {
-                    const size_t y0 = nx.fetch_add(256);
-                    if (y0 >= parts.size()) break;
-                    for (size_t y = y0; y < std::min(parts.size(), y0 + 256); ++y) {
-                        const CellOut& o = *parts[y];
-                        const CellDesc& d = out.cells[(size_t)o.desc];
-                        const int64_t c = part_cell[y];
-                        p_ro[y] = d.row_off;
-                        p_eo[y] = d.ent_off;
-                        p_desc[y] = o.desc;
-                        p_oo[y] = ord_off[(size_t)c] + (o.part_lo - co[(size_t)c].part_lo);
-                        const uint16_t* sb = &part_sbs[(size_t)o.part_lo];
-                        const size_t m = (size_t)o.n_order;
-                        size_t at = 0;
-                        for (int sbi = 0; sbi < WW; ++sbi) {
-                            p_cptr[y * (size_t)WW + (size_t)sbi] = o.part_lo + (int64_t)at;
-                            while (at < m && sb[at] == (uint16_t)sbi) ++at;
-                        }
-                    }
-                }
-            };
-            std::vector<std::thread> th;
-            for (int t = 1; t < (parts.size() >= 4096 ? nthreads : 1); ++t) th.emplace_back(fill);
-            fill();
-            for (auto& t : th) t.join();
-            p_cptr[parts.size() * (size_t)WW] = (int64_t)part_ratings.size();
-        }
-        for (const int64_t c : walk_cells) {
-            int64_t at = ord_off[(size_t)c];
-            auto piece = [&](const CellOut& o) {
-                if (!o.dev && !o.dev_part && !o.a().order.empty()) {
-                    mp.seg_order.push_back({(uint64_t)at, (uint64_t)mp.order.size(), (uint64_t)o.a().order.size()});
-                    mp.order.insert(mp.order.end(), o.a().order.begin(), o.a().order.end());
-                }
-                at += o.n_order;
-            };
-            piece(co[(size_t)c]);
-            for (const CellOut& o : extra[(size_t)c]) piece(o);
-        }
-        if (n_dev_parts > 0 || !host_tables) {
-            if (!mp.rows.empty() || !mp.entries.empty() || !mp.order.empty()) {
-                err = "build_schedule: internal error, host-packed pieces beside device-packed chunks";
-                return -1;
-            }
-            lap("  mixed: lists of the chunks");
-            if (ext->pack_emit_parts(prm.ingest->ctx, row_off.data(), ent_off.data(), ord_off.data(), tot_rows, tot_steps,
-                                     (int64_t)p_ro.size(), part_ratings.data(), (int64_t)part_ratings.size(), p_cptr.data(), p_ro.data(),
-                                     p_eo.data(), p_oo.data(), host_tables ? 0 : n_descs, p_desc.data(), &out.dev.buf) != 0) {
-                err = "build_schedule: the device packer's EMIT pass (cells and chunks) failed";
-                return -1;
-            }
-            lap("  mixed: emit (cells + chunks)");
-            out.device_packed = true;
-            out.dev_ops = ext;
-            out.device_ingest = true;
-            out.n_rows_words = tot_rows + 4;
-            out.n_entry_recs = tot_steps * G;
-            out.build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-            return 0;
-        }
-        lap("  mixed: staging of the host-packed pieces");
-        if (ext->pack_emit_mixed(prm.ingest->ctx, row_off.data(), ent_off.data(), ord_off.data(), tot_rows, tot_steps, mp,
-                                 &out.dev.buf) != 0) {
-            err = "build_schedule: the device packer's EMIT pass failed";
-            return -1;
-        }
-        lap("  mixed: emit + scatter");
-        out.device_packed = true;
-        out.dev_ops = ext;
-        out.device_ingest = true;
-        out.n_rows_words = tot_rows + 4;
-        out.n_entry_recs = tot_steps * G;
-        out.build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-        return 0;
-    }
+    if (pos != n)
+        return fail("build_schedule: internal error, packed " + std::to_string(pos) + " of " + std::to_string(n));
+    return true;
+}
+
+// Route 1: the host-packed chunks copied into the schedule's arrays.
+bool Builder::assemble_on_host() {
     out.rows.resize_uninit((size_t)tot_rows + 4);  // +16 B: the staging DMA reads whole 16-byte units
     for (int x = 0; x < 4; ++x) out.rows[(size_t)tot_rows + (size_t)x] = 0u;
     out.entries.resize_uninit((size_t)(tot_steps * G));
-    {
-        std::atomic<int64_t> nc{0};
-        auto copier = [&]() {
-            for (;;) {
-                const int64_t c = nc.fetch_add(64);
-                if (c >= n_descs) break;
-                for (int64_t x = c; x < std::min<int64_t>(c + 64, n_descs); ++x) {
-                    const CellOut& o = *by_desc[(size_t)x];
-                    const CellDesc& d = out.cells[(size_t)x];
-                    if (!o.a().rows.empty())
-                        std::memcpy(&out.rows[d.row_off], o.a().rows.data(), o.a().rows.size() * sizeof(uint32_t));
-                    if (!o.a().entries.empty())
-                        std::memcpy(&out.entries[(size_t)d.ent_off * G], o.a().entries.data(),
-                                    o.a().entries.size() * sizeof(Entry));
-                }
-            }
-        };
-        std::vector<std::thread> th;
-        for (int t = 1; t < nthreads; ++t) th.emplace_back(copier);
-        copier();
-        for (auto& t : th) t.join();
-    }
+    parallel_for((size_t)n_descs, 64, nthreads, [&](Scratch&, size_t x0, size_t x1) {
+        for (size_t x = x0; x < x1; ++x) {
+            const CellOut& o = *by_desc[x];
+            const CellDesc& d = out.cells[x];
+            if (!o.a().rows.empty()) std::memcpy(&out.rows[d.row_off], o.a().rows.data(), o.a().rows.size() * sizeof(uint32_t));
+            if (!o.a().entries.empty())
+                std::memcpy(&out.entries[(size_t)d.ent_off * G], o.a().entries.data(), o.a().entries.size() * sizeof(Entry));
+        }
+    });
     lap("  copy rows/entries");
     out.order.resize_uninit((size_t)n);
-    {
-        // the copies, in parallel over (round, block) slots
-        std::atomic<int64_t> nslot{0};
-        auto copier = [&]() {
-            for (;;) {
-                const int64_t s0 = nslot.fetch_add(64);
-                if (s0 >= ncell) break;
-                for (int64_t x = s0; x < std::min<int64_t>(s0 + 64, ncell); ++x) {
-                    const int64_t rd = x / B, b = x % B;
-                    const int64_t c = b * B + (b + rd) % B;
-                    int64_t at = out.cell_ptr[(size_t)x];
-                    auto append = [&](const CellOut& o) {
-                        if (!o.a().order.empty())
-                            std::memcpy(&out.order[(size_t)at], o.a().order.data(), o.a().order.size() * sizeof(int64_t));
-                        at += o.n_order;
-                    };
-                    append(co[(size_t)c]);
-                    for (const CellOut& o : extra[(size_t)c]) append(o);
-                }
-            }
-        };
-        std::vector<std::thread> th;
-        for (int t = 1; t < nthreads; ++t) th.emplace_back(copier);
-        copier();
-        for (auto& t : th) t.join();
-    }
+    // the order, in parallel over (round, block) slots
+    parallel_for((size_t)ncell, 64, nthreads, [&](Scratch&, size_t x0, size_t x1) {
+        for (size_t x = x0; x < x1; ++x) {
+            const int64_t rd = (int64_t)x / B, b = (int64_t)x % B;
+            const int64_t c = b * B + (b + rd) % B;
+            int64_t at = out.cell_ptr[x];
+            auto append = [&](const CellOut& o) {
+                if (!o.a().order.empty())
+                    std::memcpy(&out.order[(size_t)at], o.a().order.data(), o.a().order.size() * sizeof(int64_t));
+                at += o.n_order;
+            };
+            append(co[(size_t)c]);
+            for (const CellOut& o : extra[(size_t)c]) append(o);
+        }
+    });
     lap("concatenate + order");
     if (n >= (int64_t)1 << 20) {
         // Giving the per-cell buffers back (about 1 GB in a few hundred thousand pieces at 20 M
@@ -1871,8 +1715,121 @@ int build_schedule(const SchedParams& prm, const int32_t* u, const int32_t* i, c
     out.device_ingest = on_device;
     out.n_rows_words = (int64_t)out.rows.size();
     out.n_entry_recs = (int64_t)out.entries.size();
-    out.build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-    return 0;
+    return true;
+}
+
+// Route 3: the device writes the cells it packed at their final places and packs the chunks of the cut cells from their
+// rating lists (EMIT pass), into one set of arrays; it assembles the final sub-cell table as well.
+bool Builder::assemble_on_device() {
+    std::vector<uint32_t> row_off((size_t)ncell), ent_off((size_t)ncell);
+    std::vector<int64_t> ord_off((size_t)ncell);
+    for (int64_t x = 0; x < ncell; ++x) {
+        row_off[(size_t)x] = out.cells[(size_t)x].row_off;
+        ent_off[(size_t)x] = out.cells[(size_t)x].ent_off;
+        const int64_t rd = x / B, b = x % B;
+        ord_off[(size_t)(b * B + (b + rd) % B)] = out.cell_ptr[(size_t)x];
+    }
+    // The chunks the device packs, in the order of their ranges of part_ratings (cut cell after cut cell, a cell's
+    // chunks in chain order): where each goes, and its W*W sub-cell starts -- independent per chunk.  A chunk's place in
+    // the canonical order is its cell's plus the ratings of the chunks before it, which is its distance from the first
+    // chunk in part_ratings.  (Device cells are first chunks, c < ncell, and most of all descriptors: they are skipped
+    // through the compact list of the cells that are anything else.)
+    std::vector<const CellOut*> parts;
+    std::vector<int64_t> part_cell;
+    for (const int64_t c : walk_cells) {
+        if (!co[(size_t)c].dev) {
+            row_off[(size_t)c] = 0xFFFFFFFFu;  // (not the device's to write as a cell)
+            ent_off[(size_t)c] = 0u;
+        }
+        if (co[(size_t)c].dev_part) {
+            parts.push_back(&co[(size_t)c]);
+            part_cell.push_back(c);
+        }
+        for (const CellOut& o : extra[(size_t)c]) {
+            parts.push_back(&o);
+            part_cell.push_back(c);
+        }
+    }
+    bool in_order = parts.empty() || parts[0]->part_lo == 0;
+    for (size_t y = 1; in_order && y < parts.size(); ++y) in_order = parts[y]->part_lo == parts[y - 1]->part_lo + parts[y - 1]->n_order;
+    if (!in_order || (parts.empty() ? 0 : parts.back()->part_lo + parts.back()->n_order) != (int64_t)part_ratings.size())
+        return fail("build_schedule: internal error, the device-packed chunks do not tile their rating list");
+    std::vector<uint32_t> p_ro(parts.size()), p_eo(parts.size());
+    std::vector<int64_t> p_oo(parts.size()), p_desc(parts.size());  // (p_desc: for the device's final sub-cell table)
+    std::vector<int64_t> p_cptr(parts.size() * (size_t)WW + 1, 0);
+    parallel_for(parts.size(), 256, parts.size() >= 4096 ? nthreads : 1, [&](Scratch&, size_t y0, size_t y1) {
+        for (size_t y = y0; y < y1; ++y) {
+            const CellOut& o = *parts[y];
+            const CellDesc& d = out.cells[(size_t)o.desc];
+            const int64_t c = part_cell[y];
+            p_ro[y] = d.row_off;
+            p_eo[y] = d.ent_off;
+            p_desc[y] = o.desc;
+            p_oo[y] = ord_off[(size_t)c] + (o.part_lo - co[(size_t)c].part_lo);
+            const uint16_t* sb = &part_sbs[(size_t)o.part_lo];
+            const size_t m = (size_t)o.n_order;
+            size_t at = 0;
+            for (int sbi = 0; sbi < WW; ++sbi) {
+                p_cptr[y * (size_t)WW + (size_t)sbi] = o.part_lo + (int64_t)at;
+                while (at < m && sb[at] == (uint16_t)sbi) ++at;
+            }
+        }
+    });
+    p_cptr[parts.size() * (size_t)WW] = (int64_t)part_ratings.size();
+    lap("  mixed: lists of the chunks");
+    if (ext->pack_emit_parts(prm.ingest->ctx, row_off.data(), ent_off.data(), ord_off.data(), tot_rows, tot_steps,
+                             (int64_t)parts.size(), part_ratings.data(), (int64_t)part_ratings.size(), p_cptr.data(),
+                             p_ro.data(), p_eo.data(), p_oo.data(), n_descs, p_desc.data(), &out.dev.buf) != 0)
+        return fail("build_schedule: the device packer's EMIT pass (cells and chunks) failed");
+    lap("  mixed: emit (cells + chunks)");
+    out.device_packed = true;
+    out.dev_ops = ext;
+    out.device_ingest = true;
+    out.n_rows_words = tot_rows + 4;
+    out.n_entry_recs = tot_steps * G;
+    return true;
+}
+
+}  // namespace
+
+// Three routes, each reachable without an environment variable:
+//  1. host: degrees and bucket order on the host or the device, every cell packed and cut on the host and the schedule
+//     assembled here -- when there is no device ingest, when the device packer declines the rating set before it has
+//     counted any cell, or when a device call fails (the bucket order then comes down with fetch_sorted32);
+//  2. device, whole cells: every cell fits the training kernel's LDS image as one chunk and the device packs them all;
+//  3. device with cuts: the device counted the cells and some do not fit; the ones that do stay on the device, the host
+//     decides the cuts of the others from their ids (the device COUNTs the candidate chunks), and the device packs the
+//     chunks and assembles the schedule and its sub-cell table (Schedule::subs stays empty, dev.buf.subs holds it).
+// Every route produces the same bytes.
+int build_schedule(const SchedParams& prm, const int32_t* u, const int32_t* i, const float* r,
+                   const int64_t* orig, int64_t n, Schedule& out, std::string& err) {
+    Builder b(prm, u, i, r, orig, n, out, err);
+    if (!b.setup() || !b.degrees()) return -1;
+    b.lpt_partition();
+    b.bucket();
+    if (b.avail < 2 * b.min_sched + b.min_rows) {
+        err = "lds: the LDS budget cannot hold a single rating at this k";
+        return -1;
+    }
+    bool device_cuts = false;
+    if (b.ext) {
+        const int rc = b.device_whole_cells();
+        if (rc == 0) return b.done();  // route 2
+        device_cuts = rc == 1 && b.have_info;
+        if (!device_cuts && !b.fetch_bucket_order()) return -1;
+        b.lap("  bucket order to the host");
+    }
+    if (device_cuts) {  // route 3
+        b.keep_device_cells();
+        b.chunk_limits();
+        if (!b.cut_on_device() || !b.place_chunks(false) || !b.assemble_on_device()) return -1;
+        return b.done();
+    }
+    // route 1
+    b.pack_cells_on_host();
+    b.chunk_limits();
+    if (!b.cut_on_host() || !b.place_chunks(true) || !b.assemble_on_host()) return -1;
+    return b.done();
 }
 
 int build_schedule_auto(SchedParams prm, const int32_t* u, const int32_t* i, const float* r,

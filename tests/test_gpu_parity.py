@@ -424,8 +424,8 @@ def test_device_packer_runs_and_solo(mf, k, W):
 
 def test_device_packer_mixed_mode_chunked_cells(mf, oracle):
     """Rating sets in which SOME cells have to be chunked (too large for the training kernel's LDS image as
-    one chunk): the device keeps the cells that fit, the host packs and chunks the rest, its pieces are
-    scattered into the device arrays -- and the result is still the host packer's bytes."""
+    one chunk): the device keeps the cells that fit, the host decides how the rest are cut, the device packs
+    those chunks into the same arrays -- and the result is still the host packer's bytes."""
     from mfsgd_amd import _lib
     from tests.dsgd_common import fuzz_chunked_cases
 
@@ -460,19 +460,14 @@ def test_device_packer_one_pass_and_two_pass_write_the_same_bytes(mf, monkeypatc
             _same_schedule(mf, w["U"], w["I"], w["k"], w["u"], w["i"], w["r"])
 
 
-def test_device_packer_tables_on_the_device_or_through_the_host(mf, monkeypatch):
+def test_device_packer_tables_on_the_device_or_through_the_host(mf):
     """[r3] The sub-cell tables of a device-packed schedule are assembled on the device (the cells' tables as counted,
-    the chunks' scattered to their descriptors); MFSGD_HOST_TABLES=1 takes them through the host as before.  The debug
-    getter fetches the device's copy: both against the host packer's bytes, with and without cut cells."""
+    the chunks' scattered to their descriptors); the route through the host is retired.  The debug getter fetches the
+    device's copy: against the host packer's bytes, with and without cut cells."""
     cases = (("cfg2_ml20m", 0.02), ("cfg3_netflix", 0.02), ("cfg4_powerlaw", 0.0003))
-    for through_host in (False, True):
-        if through_host:
-            monkeypatch.setenv("MFSGD_HOST_TABLES", "1")
-        else:
-            monkeypatch.delenv("MFSGD_HOST_TABLES", raising=False)
-        for name, scale in cases:
-            w = mf.synth.workload(name, scale)
-            _same_schedule(mf, w["U"], w["I"], w["k"], w["u"], w["i"], w["r"])
+    for name, scale in cases:
+        w = mf.synth.workload(name, scale)
+        _same_schedule(mf, w["U"], w["I"], w["k"], w["u"], w["i"], w["r"])
 
 
 def test_device_packer_partitioned_handles(mf):
