@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays */
+#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding (an addition: no existing call changed) */
 
 typedef enum mfsgd_status {
     MFSGD_OK = 0,
@@ -148,6 +148,18 @@ int mfsgd_predict(mfsgd_handle* h, const int32_t* u, const int32_t* i, float* ou
  * smaller item index.  out_items / out_scores: n_users x topn, row-major.          */
 int mfsgd_recommend(mfsgd_handle* h, const int32_t* users, int32_t n_users, int32_t topn, int32_t* out_items,
                     float* out_scores);
+/* Top-N as mfsgd_recommend, except that item j is never returned in row b when (users[b], j) is
+ * one of the n_excl pairs (excl_u[x], excl_i[x]).  Typical use: pass the u / i arrays the model
+ * was trained on, so users are recommended only items they have not rated.
+ * Pairs whose user is not requested are ignored.  Duplicate pairs are allowed.
+ * A row with fewer than topn eligible items is padded with item -1 and score NaN.
+ * n_excl == 0 (pointers may then be NULL) gives exactly mfsgd_recommend's output.
+ * Every pair must lie in range (0 <= excl_u < n_users, 0 <= excl_i < n_items); a bad argument
+ * is reported before any device work.  topn > n_items stays an error, a topn above the
+ * number of eligible items is not.  The pairs are read in chunks of bounded size; the
+ * per-user lists are built on the device for this call and freed before it returns.     */
+int mfsgd_recommend_excluding(mfsgd_handle* h, const int32_t* users, int32_t n_users, int32_t topn, const int32_t* excl_u,
+                              const int32_t* excl_i, int64_t n_excl, int32_t* out_items, float* out_scores);
 
 /* Timed variant used by bench.py: runs `epochs` training passes bracketed by
  * HIP events on the handle's stream and returns the elapsed device time and

@@ -70,6 +70,18 @@ class MatrixFactorizationSGD {
         check(mfsgd_recommend(h_, users.data(), (int32_t)users.size(), topn, items.data(), scores.data()));
         return {std::move(items), std::move(scores)};
     }
+    // int[][] recommend(int[] users, int topN, int[] exclU, int[] exclI): as above, never an item (exclU[x], exclI[x]) names
+    // for that user; rows short of eligible items end in item -1, score NaN
+    std::pair<std::vector<int32_t>, std::vector<float>> recommend(const std::vector<int32_t>& users, int topn,
+                                                                  const std::vector<int32_t>& excl_u,
+                                                                  const std::vector<int32_t>& excl_i) {
+        if (excl_u.size() != excl_i.size()) throw std::invalid_argument("length mismatch");
+        std::vector<int32_t> items(users.size() * (size_t)topn);
+        std::vector<float> scores(users.size() * (size_t)topn);
+        check(mfsgd_recommend_excluding(h_, users.data(), (int32_t)users.size(), topn, excl_u.data(), excl_i.data(),
+                                        (int64_t)excl_u.size(), items.data(), scores.data()));
+        return {std::move(items), std::move(scores)};
+    }
 
     double rmse() {
         double out = 0.0;

@@ -1043,15 +1043,95 @@ int mfsgd_predict(mfsgd_handle* h, const int32_t* u, const int32_t* i, float* ou
     return MFSGD_OK;
 }
 
+namespace {
+
+// Exclusion lists of one recommend call on the device: the pairs go up in chunks of bounded size, those of requested
+// users are kept (slot << 32 | item), then sorted and made distinct into one list per slot (recommend.hip).
+// Scratch is freed here; `ex` points into `slot`, `off` and `items`, which the caller frees.
+constexpr int64_t kExclChunk = (int64_t)1 << 22;  // pairs per upload: 32 MB of staging
+
+int exclusions_to_device(mfsgd_handle* h, const std::vector<int32_t>& slot_of_user, int32_t n_slots, const int32_t* excl_u,
+                         const int32_t* excl_i, int64_t n_excl, int64_t kept, DevBuf& slot, DevBuf& off, DevBuf& items,
+                         void*& temp, size_t& temp_bytes, RecommendExcl& ex) {
+    DevBuf cu, ci, keys, keys_tmp, count;
+    auto cleanup = [&]() {
+        cu.release(); ci.release(); keys.release(); keys_tmp.release(); count.release();
+    };
+    const int64_t chunk = std::min(n_excl, kExclChunk);
+    int rc = upload(h, slot, slot_of_user);
+    if (!rc) rc = dev_alloc(h, cu, sizeof(int32_t) * (size_t)chunk);
+    if (!rc) rc = dev_alloc(h, ci, sizeof(int32_t) * (size_t)chunk);
+    if (!rc) rc = dev_alloc(h, keys, 8 * (size_t)kept);
+    if (!rc) rc = dev_alloc(h, keys_tmp, 8 * (size_t)kept);
+    if (!rc) rc = dev_alloc(h, count, 16);  // [0] appended pairs (u64), [2] distinct ones (u32)
+    if (!rc) rc = dev_alloc(h, off, sizeof(long long) * ((size_t)n_slots + 1));
+    if (!rc) rc = dev_alloc(h, items, sizeof(int32_t) * (size_t)kept);
+    if (rc) {
+        cleanup();
+        return rc;
+    }
+    auto* cnt = static_cast<unsigned long long*>(count.p);
+    hipError_t e = hipMemsetAsync(count.p, 0, 16, h->stream);
+    for (int64_t x0 = 0; x0 < n_excl && e == hipSuccess; x0 += chunk) {
+        const int64_t c = std::min(chunk, n_excl - x0);
+        e = hipMemcpyAsync(cu.p, excl_u + x0, sizeof(int32_t) * (size_t)c, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(ci.p, excl_i + x0, sizeof(int32_t) * (size_t)c, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess)
+            e = recommend_excl_filter(static_cast<const int32_t*>(slot.p), static_cast<const int32_t*>(cu.p),
+                                      static_cast<const int32_t*>(ci.p), c, static_cast<unsigned long long*>(keys.p), cnt,
+                                      kept, h->stream);
+    }
+    if (e == hipSuccess)
+        e = recommend_excl_lists(static_cast<unsigned long long*>(keys.p), static_cast<unsigned long long*>(keys_tmp.p), kept,
+                                 n_slots, reinterpret_cast<unsigned*>(cnt + 1), static_cast<long long*>(off.p),
+                                 static_cast<int32_t*>(items.p), temp, temp_bytes, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    cleanup();
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, e == hipErrorOutOfMemory ? MFSGD_ERR_OOM : MFSGD_ERR_HIP,
+                    std::string("recommend: exclusion lists: ") + hipGetErrorString(e));
+    }
+    ex.slot = static_cast<const int32_t*>(slot.p);
+    ex.off = static_cast<const long long*>(off.p);
+    ex.items = static_cast<const int32_t*>(items.p);
+    return MFSGD_OK;
+}
+
+}  // namespace
+
 int mfsgd_recommend(mfsgd_handle* h, const int32_t* users, int32_t n_users, int32_t topn, int32_t* out_items,
                     float* out_scores) {
-    if (!h || n_users < 0 || topn < 1 || (n_users > 0 && (!users || !out_items || !out_scores)))
+    return mfsgd_recommend_excluding(h, users, n_users, topn, nullptr, nullptr, 0, out_items, out_scores);
+}
+
+int mfsgd_recommend_excluding(mfsgd_handle* h, const int32_t* users, int32_t n_users, int32_t topn, const int32_t* excl_u,
+                              const int32_t* excl_i, int64_t n_excl, int32_t* out_items, float* out_scores) {
+    if (!h || n_users < 0 || topn < 1 || (n_users > 0 && (!users || !out_items || !out_scores)) || n_excl < 0 ||
+        (n_excl > 0 && (!excl_u || !excl_i)))
         return fail(h, MFSGD_ERR_INVALID_ARG, "recommend: bad argument");
     if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "recommend: single-partition handles only");
     if (topn > h->cfg.n_items) return fail(h, MFSGD_ERR_INVALID_ARG, "recommend: topn exceeds the number of items");
     for (int32_t j = 0; j < n_users; ++j)
         if (users[j] < 0 || users[j] >= h->cfg.n_users)
             return fail(h, MFSGD_ERR_INVALID_ARG, "recommend: user " + std::to_string(j) + " out of range");
+    // a slot per distinct requested user (one user asked for twice shares it), and how many pairs are theirs
+    std::vector<int32_t> slot_of_user;
+    int32_t n_slots = 0;
+    int64_t kept = 0;
+    if (n_excl > 0) {
+        slot_of_user.assign((size_t)h->cfg.n_users, -1);
+        for (int32_t j = 0; j < n_users; ++j)
+            if (slot_of_user[(size_t)users[j]] < 0) slot_of_user[(size_t)users[j]] = n_slots++;
+        for (int64_t x = 0; x < n_excl; ++x) {
+            if (excl_u[x] < 0 || excl_u[x] >= h->cfg.n_users || excl_i[x] < 0 || excl_i[x] >= h->cfg.n_items)
+                return fail(h, MFSGD_ERR_INVALID_ARG, "recommend: excluded pair " + std::to_string(x) + " out of range");
+            kept += slot_of_user[(size_t)excl_u[x]] >= 0 ? 1 : 0;
+        }
+        if (kept > (int64_t)UINT32_MAX)
+            return fail(h, MFSGD_ERR_INVALID_ARG, "recommend: more than 2^32 - 1 excluded pairs of the requested users");
+    }
     if (n_users == 0) return MFSGD_OK;
     int rc = factors_to_device(h);
     if (rc) return rc;
@@ -1061,14 +1141,20 @@ int mfsgd_recommend(mfsgd_handle* h, const int32_t* users, int32_t n_users, int3
     int batch = (int)std::max<int64_t>(1, std::min<int64_t>(n_users, ((int64_t)64 << 20) / std::max(1, I)));
     if (fused) batch = n_users;
     batch = std::min(batch, 65535);
-    DevBuf d_users, s_in, s_out, id_in, id_out, d_off, o_s, o_i;
+    DevBuf d_users, s_in, s_out, id_in, id_out, d_off, o_s, o_i, ex_slot, ex_off, ex_items;
     void* temp = nullptr;
     size_t temp_bytes = 0;
     auto cleanup = [&]() {
         d_users.release(); s_in.release(); s_out.release(); id_in.release(); id_out.release(); d_off.release();
-        o_s.release(); o_i.release();
+        o_s.release(); o_i.release(); ex_slot.release(); ex_off.release(); ex_items.release();
         if (temp) (void)hipFree(temp);
     };
+    RecommendExcl ex;  // built once for all batches; none when no pair belongs to a requested user
+    if (kept > 0 && (rc = exclusions_to_device(h, slot_of_user, n_slots, excl_u, excl_i, n_excl, kept, ex_slot, ex_off,
+                                               ex_items, temp, temp_bytes, ex))) {
+        cleanup();
+        return rc;
+    }
     const size_t cells = (size_t)batch * (size_t)I;
     rc = dev_alloc(h, d_users, sizeof(int32_t) * (size_t)batch);
     if (!fused) {
@@ -1090,11 +1176,11 @@ int mfsgd_recommend(mfsgd_handle* h, const int32_t* users, int32_t n_users, int3
         e = hipMemcpyAsync(d_users.p, users + done, sizeof(int32_t) * (size_t)nb, hipMemcpyHostToDevice, h->stream);
         if (e == hipSuccess && fused)
             e = recommend_fused(h->geo.L, static_cast<const float*>(h->dP.p), static_cast<const float*>(h->dQ.p),
-                                static_cast<const int32_t*>(d_users.p), nb, I, topn, static_cast<float*>(o_s.p),
+                                static_cast<const int32_t*>(d_users.p), nb, I, topn, ex, static_cast<float*>(o_s.p),
                                 static_cast<int32_t*>(o_i.p), h->stream);
         else if (e == hipSuccess)
             e = recommend_batch(h->geo.L, static_cast<const float*>(h->dP.p), static_cast<const float*>(h->dQ.p),
-                                static_cast<const int32_t*>(d_users.p), nb, I, topn, static_cast<float*>(s_in.p),
+                                static_cast<const int32_t*>(d_users.p), nb, I, topn, ex, static_cast<float*>(s_in.p),
                                 static_cast<float*>(s_out.p), static_cast<int32_t*>(id_in.p), static_cast<int32_t*>(id_out.p),
                                 static_cast<long long*>(d_off.p), temp, temp_bytes, static_cast<float*>(o_s.p),
                                 static_cast<int32_t*>(o_i.p), h->stream);

@@ -50,14 +50,30 @@ hipError_t launch_init_rows(float* dst, long long rows, int k, int kp, long long
 // `started` (device-accessible host memory, or null): every workgroup adds one to it as it starts
 hipError_t launch_occupy(int workgroups, int lds_bytes, unsigned long long ticks, unsigned* started, hipStream_t st);
 
-// recommend.hip: fused score + select (one workgroup per user, nothing but the winners goes to memory) for
+// recommend.hip.  Exclusions of one recommend call: the slot of each requested user (slot_of_user[n_users], -1 for the
+// rest) and, per slot s, the sorted distinct excluded items items[off[s] .. off[s + 1]).  slot == nullptr: none.
+struct RecommendExcl {
+    const int32_t* slot = nullptr;
+    const long long* off = nullptr;
+    const int32_t* items = nullptr;
+};
+// Fused score + select (one workgroup per user, nothing but the winners goes to memory) for
 // the (n_items, topn) recommend_is_fused() accepts ...
 bool recommend_is_fused(int32_t n_items, int32_t topn);
 hipError_t recommend_fused(int L, const float* P, const float* Q, const int32_t* d_users, int nb, int32_t n_items,
-                           int32_t topn, float* out_s, int32_t* out_i, hipStream_t st);
+                           int32_t topn, const RecommendExcl& ex, float* out_s, int32_t* out_i, hipStream_t st);
 // ... and for the rest: scores of nb users against every item, top `topn` of each into out_s / out_i.
 hipError_t recommend_batch(int L, const float* P, const float* Q, const int32_t* d_users, int nb, int32_t n_items,
-                           int32_t topn, float* s_in, float* s_out, int32_t* id_in, int32_t* id_out, long long* d_off,
-                           void*& temp, size_t& temp_bytes, float* out_s, int32_t* out_i, hipStream_t st);
+                           int32_t topn, const RecommendExcl& ex, float* s_in, float* s_out, int32_t* id_in, int32_t* id_out,
+                           long long* d_off, void*& temp, size_t& temp_bytes, float* out_s, int32_t* out_i, hipStream_t st);
+// Building the lists: each chunk of pairs appends slot << 32 | item to keys[*count ...] for the pairs of requested users
+// (count starts at 0; at most cap are written) ...
+hipError_t recommend_excl_filter(const int32_t* slot_of_user, const int32_t* u, const int32_t* i, int64_t n,
+                                 unsigned long long* keys, unsigned long long* count, int64_t cap, hipStream_t st);
+// ... then the n keys are sorted (through keys_tmp) and made distinct, back into keys: *n_distinct of them,
+// off[n_slots + 1] and items[n] as RecommendExcl reads them.
+hipError_t recommend_excl_lists(unsigned long long* keys, unsigned long long* keys_tmp, int64_t n, int32_t n_slots,
+                                unsigned* n_distinct, long long* off, int32_t* items, void*& temp, size_t& temp_bytes,
+                                hipStream_t st);
 
 }  // namespace mfsgd

@@ -7,9 +7,15 @@
 // largest by a 4 x 8-bit radix select on LDS histograms, collects what lies above it (ties in
 // ascending item order) and sorts only those; no score ever goes to memory.  Larger topn: scores to
 // memory and one stable, descending segmented radix sort per batch of users (rocPRIM).
+// Exclusions (mfsgd_recommend_excluding): one sorted, distinct item list per requested user, built here from
+// the caller's (user, item) pairs; both paths have a variant that gives excluded items a key below every
+// eligible one (0: eligible keys are clamped to >= 1) and pads a row that runs out of eligible items.
 #include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
+#include <rocprim/device/device_select.hpp>
 
+#include <algorithm>
 #include <cstdint>
 
 #include "canon.hpp"
@@ -21,8 +27,19 @@ namespace mfsgd {
 
 namespace {
 
-// scores[b * n_items + i] = dot(P[users[b]], Q[i]); ids[...] = i.  grid = (item blocks, users)
-template <int L>
+// float -> unsigned whose order is the float order (-0 counts as +0, as a comparison would)
+__device__ __forceinline__ unsigned order_key(float f) {
+    unsigned u = __builtin_bit_cast(unsigned, f);
+    if (u == 0x80000000u) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// with exclusions: 0 is the key of an excluded item, so eligible keys start at 1 (only the all-ones NaN moves)
+__device__ __forceinline__ unsigned eligible_key(float f) { return max(order_key(f), 1u); }
+
+// scores[b * n_items + i] = dot(P[users[b]], Q[i]) (KEYS: eligible_key of it, as unsigned); ids[...] = i.
+// grid = (item blocks, users)
+template <int L, bool KEYS>
 __global__ void __launch_bounds__(256) score_kernel(const float* __restrict__ P, const float* __restrict__ Q,
                                                     const int32_t* __restrict__ users, const int32_t n_items,
                                                     float* __restrict__ scores, int32_t* __restrict__ ids) {
@@ -40,7 +57,8 @@ __global__ void __launch_bounds__(256) score_kernel(const float* __restrict__ P,
         const float4 q = *reinterpret_cast<const float4*>(Q + (size_t)(ok ? i : 0) * KP + lig * 4);
         const float d = group_allreduce<L>(chunk_dot(p, q));
         if (ok && lig == 0) {
-            scores[(size_t)b * n_items + i] = d;
+            if constexpr (KEYS) reinterpret_cast<unsigned*>(scores)[(size_t)b * n_items + i] = eligible_key(d);
+            else scores[(size_t)b * n_items + i] = d;
             ids[(size_t)b * n_items + i] = i;
         }
     }
@@ -51,34 +69,39 @@ constexpr int kTopnFused = 128;    // largest topn the fused kernel takes
 constexpr int kTopnTile = 14336;   // items scored per tile (56 KiB of keys in LDS: two workgroups per CU)
 constexpr int kTopnCand = 2048;    // candidates kept across tiles (tiles x topn must fit)
 
-// float -> unsigned whose order is the float order (-0 counts as +0, as a comparison would)
-__device__ __forceinline__ unsigned order_key(float f) {
-    unsigned u = __builtin_bit_cast(unsigned, f);
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 constexpr int kTopnThreads = 1024;  // 16 waves: the scores are a latency-bound row gather, so many loads in flight
 
-template <int L>
+// EXCL: the items of the user's exclusion list get key 0 in each tile and are never candidates; a tile selects
+// min(topn, its eligible items), and a row with fewer than topn candidates in all is padded (-1, NaN).
+template <int L, bool EXCL>
 __global__ void __launch_bounds__(kTopnThreads) topn_kernel(const float* __restrict__ P, const float* __restrict__ Q,
                                                             const int32_t* __restrict__ users, const int32_t n_items,
-                                                            const int32_t topn, float* __restrict__ out_s,
-                                                            int32_t* __restrict__ out_i) {
+                                                            const int32_t topn, const RecommendExcl ex,
+                                                            float* __restrict__ out_s, int32_t* __restrict__ out_i) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NT = kTopnThreads, NW = NT / 64;
     unsigned* keys = reinterpret_cast<unsigned*>(smem);                                   // kTopnTile
     unsigned long long* cand = reinterpret_cast<unsigned long long*>(keys + kTopnTile);   // kTopnCand
     unsigned* hist = reinterpret_cast<unsigned*>(cand + kTopnCand);                        // 256
     unsigned* wtot = hist + 256;                                                           // NW wave totals
-    int* ctl = reinterpret_cast<int*>(wtot + NW);  // [0] candidates so far, [1] bin, [2] need
+    int* ctl = reinterpret_cast<int*>(wtot + NW);  // [0] candidates so far, [1] bin, [2] need, [3] excluded items so far
     constexpr int KP = 4 * L;
     constexpr int GPB = NT / L;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lig = tid % L, grp = tid / L;
     const int b = blockIdx.x;
     const float4 p = *reinterpret_cast<const float4*>(P + (size_t)users[b] * KP + lig * 4);
-    if (tid == 0) ctl[0] = 0;
+    long long ex_at = 0, ex_end = 0;  // the user's exclusion list, consumed tile by tile
+    int ex_seen = 0;                  // its items met so far: ctl[3] counts them and is never reset, so no read races a reset
+    if constexpr (EXCL) {
+        const int s = ex.slot[users[b]];
+        ex_at = ex.off[s];
+        ex_end = ex.off[s + 1];
+    }
+    if (tid == 0) {
+        ctl[0] = 0;
+        if (EXCL) ctl[3] = 0;
+    }
     __syncthreads();
     for (int tile0 = 0; tile0 < n_items; tile0 += kTopnTile) {
         const int nt = min(kTopnTile, n_items - tile0);
@@ -93,8 +116,8 @@ __global__ void __launch_bounds__(kTopnThreads) topn_kernel(const float* __restr
             const float d0 = group_allreduce<L>(chunk_dot(p, q0));
             const float d1 = group_allreduce<L>(chunk_dot(p, q1));
             if (lig == 0) {
-                keys[x0] = order_key(d0);
-                if (ok1) keys[x1] = order_key(d1);
+                keys[x0] = EXCL ? eligible_key(d0) : order_key(d0);
+                if (ok1) keys[x1] = EXCL ? eligible_key(d1) : order_key(d1);
             }
         }
         for (; it < iters; ++it) {
@@ -102,11 +125,30 @@ __global__ void __launch_bounds__(kTopnThreads) topn_kernel(const float* __restr
             const bool ok = x < nt;
             const float4 q = *reinterpret_cast<const float4*>(Q + (size_t)(ok ? tile0 + x : 0) * KP + lig * 4);
             const float d = group_allreduce<L>(chunk_dot(p, q));
-            if (ok && lig == 0) keys[x] = order_key(d);
+            if (ok && lig == 0) keys[x] = EXCL ? eligible_key(d) : order_key(d);
         }
         __syncthreads();
         // radix select: the key of the need-th largest score of the tile
         int need = min(topn, nt);
+        if constexpr (EXCL) {
+            // the list is sorted and distinct, so its items in this tile are the next run of it, read from memory.
+            // Each thread walks its own stride of the list up to the tile's end (one load per thread and tile rather
+            // than a search: a chain of dependent loads cost 1.47x the plain kernel), keys to 0, counted in ctl[3].
+            int mine = 0;
+            for (long long x = ex_at + tid; x < ex_end; x += NT) {
+                const int item = ex.items[x];
+                if (item >= tile0 + nt) break;
+                keys[item - tile0] = 0u;
+                ++mine;
+            }
+            if (mine) atomicAdd(&ctl[3], mine);
+            __syncthreads();
+            const int in_tile = ctl[3] - ex_seen;
+            ex_seen += in_tile;
+            ex_at += in_tile;
+            need = min(topn, nt - in_tile);
+            if (need == 0) continue;  // nothing eligible (need is uniform across the workgroup)
+        }
         unsigned prefix = 0u, mask = 0u;
         for (int pass = 0; pass < 4; ++pass) {
             const int shift = 24 - 8 * pass;
@@ -200,28 +242,32 @@ __global__ void __launch_bounds__(kTopnThreads) topn_kernel(const float* __restr
             }
             __syncthreads();
         }
-    // the winners; their scores recomputed with the canonical dot (the bits predict() returns)
+    // the winners; their scores recomputed with the canonical dot (the bits predict() returns).  Without
+    // exclusions there are always at least topn candidates; with them, the places past the last are padded.
     const int iters = (topn + GPB - 1) / GPB;
     for (int it = 0; it < iters; ++it) {
         const int x = grp + it * GPB;
         const bool ok = x < topn;
-        const int item = ok ? (int)(cand[x] & 0xFFFFFFFFull) : 0;
+        const bool won = !EXCL || x < nc;
+        const int item = ok && won ? (int)(cand[x] & 0xFFFFFFFFull) : 0;
         const float4 q = *reinterpret_cast<const float4*>(Q + (size_t)item * KP + lig * 4);
         const float d = group_allreduce<L>(chunk_dot(p, q));
         if (ok && lig == 0) {
-            out_s[(size_t)b * topn + x] = d;
-            out_i[(size_t)b * topn + x] = item;
+            out_s[(size_t)b * topn + x] = won ? d : __builtin_nanf("");
+            out_i[(size_t)b * topn + x] = won ? item : -1;
         }
     }
 }
 
-template <int L>
-hipError_t topn_L(const float* P, const float* Q, const int32_t* users, int nb, int32_t n_items, int32_t topn, float* out_s,
-                  int32_t* out_i, hipStream_t st) {
+template <int L, bool EXCL>
+hipError_t topn_L(const float* P, const float* Q, const int32_t* users, int nb, int32_t n_items, int32_t topn,
+                  const RecommendExcl& ex, float* out_s, int32_t* out_i, hipStream_t st) {
     const size_t lds = (size_t)kTopnTile * 4 + (size_t)kTopnCand * 8 + 256 * 4 + (kTopnThreads / 64) * 4 + 16;
-    hipError_t e = hipFuncSetAttribute((const void*)topn_kernel<L>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e =
+        hipFuncSetAttribute((const void*)topn_kernel<L, EXCL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((topn_kernel<L>), dim3((unsigned)nb), dim3(kTopnThreads), lds, st, P, Q, users, n_items, topn, out_s, out_i);
+    hipLaunchKernelGGL((topn_kernel<L, EXCL>), dim3((unsigned)nb), dim3(kTopnThreads), lds, st, P, Q, users, n_items, topn,
+                       ex, out_s, out_i);
     return hipGetLastError();
 }
 
@@ -235,18 +281,148 @@ __global__ void __launch_bounds__(256) take_top_kernel(const float* __restrict__
     }
 }
 
+// With exclusions the sorted keys are eligible_key()s, not scores: the first topn ids of each row are rescored with
+// the canonical dot, and an excluded one (key 0, sorted after every eligible item) ends the row's winners.
+template <int L>
+__global__ void __launch_bounds__(256) take_top_excl_kernel(const float* __restrict__ P, const float* __restrict__ Q,
+                                                            const int32_t* __restrict__ users,
+                                                            const unsigned* __restrict__ key, const int32_t* __restrict__ id,
+                                                            const int32_t n_items, const int32_t topn,
+                                                            float* __restrict__ out_s, int32_t* __restrict__ out_i) {
+    constexpr int KP = 4 * L;
+    constexpr int GPB = 256 / L;
+    const int lig = threadIdx.x % L, grp = threadIdx.x / L;
+    const int b = blockIdx.x;
+    const float4 p = *reinterpret_cast<const float4*>(P + (size_t)users[b] * KP + lig * 4);
+    const int iters = (topn + GPB - 1) / GPB;  // uniform trip count: DPP needs every lane live
+    for (int it = 0; it < iters; ++it) {
+        const int x = grp + it * GPB;
+        const bool ok = x < topn;
+        const bool won = ok && key[(size_t)b * n_items + x] != 0u;
+        const int item = won ? id[(size_t)b * n_items + x] : 0;
+        const float4 q = *reinterpret_cast<const float4*>(Q + (size_t)item * KP + lig * 4);
+        const float d = group_allreduce<L>(chunk_dot(p, q));
+        if (ok && lig == 0) {
+            out_s[(size_t)b * topn + x] = won ? d : __builtin_nanf("");
+            out_i[(size_t)b * topn + x] = won ? item : -1;
+        }
+    }
+}
+
+// key[b * n_items + i] = 0 for every item i of the exclusion list of users[b]
+__global__ void __launch_bounds__(256) exclude_kernel(const int32_t* __restrict__ users, const RecommendExcl ex,
+                                                      const int32_t n_items, unsigned* __restrict__ key) {
+    const int b = blockIdx.x;
+    const int s = ex.slot[users[b]];
+    const long long end = ex.off[s + 1];
+    for (long long x = ex.off[s] + threadIdx.x; x < end; x += 256) key[(size_t)b * n_items + ex.items[x]] = 0u;
+}
+
 __global__ void __launch_bounds__(256) offsets_kernel(long long* __restrict__ off, const int n, const int32_t n_items) {
     for (int x = threadIdx.x; x <= n; x += 256) off[x] = (long long)x * n_items;
 }
 
+hipError_t grow_temp(void*& temp, size_t& temp_bytes, size_t need) {
+    if (need <= temp_bytes) return hipSuccess;
+    if (temp) (void)hipFree(temp);
+    temp = nullptr;
+    temp_bytes = 0;
+    const hipError_t e = hipMalloc(&temp, need);
+    if (e == hipSuccess) temp_bytes = need;
+    return e;
+}
+
+// stable descending segmented sort of nb rows of n_items (key, id) pairs; K = float (scores) or unsigned (keys)
+template <class K>
+hipError_t sort_rows(K* k_in, K* k_out, int32_t* id_in, int32_t* id_out, long long* d_off, int nb, int32_t n_items,
+                     void*& temp, size_t& temp_bytes, hipStream_t st) {
+    size_t need = 0;
+    hipError_t e = rocprim::segmented_radix_sort_pairs_desc(nullptr, need, k_in, k_out, id_in, id_out,
+                                                            (unsigned)((size_t)nb * n_items), (unsigned)nb, d_off, d_off + 1,
+                                                            0u, 32u, st);
+    if (e == hipSuccess) e = grow_temp(temp, temp_bytes, need);
+    if (e == hipSuccess)
+        e = rocprim::segmented_radix_sort_pairs_desc(temp, need, k_in, k_out, id_in, id_out, (unsigned)((size_t)nb * n_items),
+                                                     (unsigned)nb, d_off, d_off + 1, 0u, 32u, st);
+    return e;
+}
+
 template <int L>
-hipError_t score_L(const float* P, const float* Q, const int32_t* users, int nb, int32_t n_items, float* scores,
-                   int32_t* ids, hipStream_t st) {
+hipError_t batch_L(const float* P, const float* Q, const int32_t* users, int nb, int32_t n_items, int32_t topn,
+                   const RecommendExcl& ex, float* s_in, float* s_out, int32_t* id_in, int32_t* id_out, long long* d_off,
+                   void*& temp, size_t& temp_bytes, float* out_s, int32_t* out_i, hipStream_t st) {
     const int gpb = 256 / L;
     int bx = (n_items + gpb - 1) / gpb;
     if (bx > 64) bx = 64;
-    hipLaunchKernelGGL((score_kernel<L>), dim3((unsigned)bx, (unsigned)nb), dim3(256), 0, st, P, Q, users, n_items, scores, ids);
+    const dim3 sgrid((unsigned)bx, (unsigned)nb);
+    if (ex.slot)
+        hipLaunchKernelGGL((score_kernel<L, true>), sgrid, dim3(256), 0, st, P, Q, users, n_items, s_in, id_in);
+    else
+        hipLaunchKernelGGL((score_kernel<L, false>), sgrid, dim3(256), 0, st, P, Q, users, n_items, s_in, id_in);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (ex.slot) {
+        hipLaunchKernelGGL(exclude_kernel, dim3((unsigned)nb), dim3(256), 0, st, users, ex, n_items,
+                           reinterpret_cast<unsigned*>(s_in));
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(offsets_kernel, dim3(1), dim3(256), 0, st, d_off, nb, n_items);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (!ex.slot) {
+        e = sort_rows(s_in, s_out, id_in, id_out, d_off, nb, n_items, temp, temp_bytes, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(take_top_kernel, dim3((unsigned)nb), dim3(256), 0, st, s_out, id_out, n_items, topn, out_s, out_i);
+        return hipGetLastError();
+    }
+    unsigned* k_in = reinterpret_cast<unsigned*>(s_in);
+    unsigned* k_out = reinterpret_cast<unsigned*>(s_out);
+    e = sort_rows(k_in, k_out, id_in, id_out, d_off, nb, n_items, temp, temp_bytes, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((take_top_excl_kernel<L>), dim3((unsigned)nb), dim3(256), 0, st, P, Q, users, k_out, id_out, n_items,
+                       topn, out_s, out_i);
     return hipGetLastError();
+}
+
+// ---- exclusion lists -------------------------------------------------------------------------------------------
+// keys[...] = slot << 32 | item for each pair (u[x], i[x]) whose user has a slot; one atomic per wave
+__global__ void __launch_bounds__(256) excl_filter_kernel(const int32_t* __restrict__ slot_of_user,
+                                                          const int32_t* __restrict__ u, const int32_t* __restrict__ i,
+                                                          const long long n, unsigned long long* __restrict__ keys,
+                                                          unsigned long long* __restrict__ count,
+                                                          const unsigned long long cap) {
+    const int lane = threadIdx.x & 63;
+    for (long long x0 = (long long)blockIdx.x * 256; x0 < n; x0 += (long long)gridDim.x * 256) {
+        const long long x = x0 + threadIdx.x;
+        const int s = x < n ? slot_of_user[u[x]] : -1;
+        const unsigned long long m = __ballot(s >= 0);
+        if (m == 0ull) continue;  // wave-uniform
+        unsigned long long base = 0;
+        if (lane == 0) base = atomicAdd(count, (unsigned long long)__popcll(m));
+        base = __shfl(base, 0, 64);
+        const unsigned long long at = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+        if (s >= 0 && at < cap) keys[at] = ((unsigned long long)s << 32) | (unsigned)i[x];
+    }
+}
+
+// the sorted distinct keys -> items[x] and off[s] = first key of slot s (off[n_slots] = their count)
+__global__ void __launch_bounds__(256) excl_lists_kernel(const unsigned long long* __restrict__ keys,
+                                                         const unsigned* __restrict__ n_keys, const int n_slots,
+                                                         long long* __restrict__ off, int32_t* __restrict__ items) {
+    const long long n = *n_keys;
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long x = (long long)blockIdx.x * 256 + threadIdx.x; x < n || x <= n_slots; x += stride) {
+        if (x < n) items[x] = (int32_t)(keys[x] & 0xFFFFFFFFull);
+        if (x <= n_slots) {
+            const unsigned long long v = (unsigned long long)x << 32;
+            long long lo = 0, hi = n;
+            while (lo < hi) {
+                const long long mid = (lo + hi) >> 1;
+                if (keys[mid] < v) lo = mid + 1;
+                else hi = mid;
+            }
+            off[x] = lo;
+        }
+    }
 }
 
 }  // namespace
@@ -258,52 +434,73 @@ bool recommend_is_fused(int32_t n_items, int32_t topn) {
 
 // Fused score + select: no score buffers at all.
 hipError_t recommend_fused(int L, const float* P, const float* Q, const int32_t* d_users, int nb, int32_t n_items,
-                           int32_t topn, float* out_s, int32_t* out_i, hipStream_t st) {
+                           int32_t topn, const RecommendExcl& ex, float* out_s, int32_t* out_i, hipStream_t st) {
     switch (L) {
-        case 1: return topn_L<1>(P, Q, d_users, nb, n_items, topn, out_s, out_i, st);
-        case 2: return topn_L<2>(P, Q, d_users, nb, n_items, topn, out_s, out_i, st);
-        case 4: return topn_L<4>(P, Q, d_users, nb, n_items, topn, out_s, out_i, st);
-        case 8: return topn_L<8>(P, Q, d_users, nb, n_items, topn, out_s, out_i, st);
-        case 16: return topn_L<16>(P, Q, d_users, nb, n_items, topn, out_s, out_i, st);
-        case 32: return topn_L<32>(P, Q, d_users, nb, n_items, topn, out_s, out_i, st);
-        case 64: return topn_L<64>(P, Q, d_users, nb, n_items, topn, out_s, out_i, st);
+#define MFSGD_TOPN(LL)                                                                          \
+    case LL:                                                                                    \
+        return ex.slot ? topn_L<LL, true>(P, Q, d_users, nb, n_items, topn, ex, out_s, out_i, st) \
+                       : topn_L<LL, false>(P, Q, d_users, nb, n_items, topn, ex, out_s, out_i, st);
+        MFSGD_TOPN(1)
+        MFSGD_TOPN(2)
+        MFSGD_TOPN(4)
+        MFSGD_TOPN(8)
+        MFSGD_TOPN(16)
+        MFSGD_TOPN(32)
+        MFSGD_TOPN(64)
+#undef MFSGD_TOPN
         default: return hipErrorInvalidValue;
     }
 }
 
 // Device buffers are the caller's (capi.cpp): scores/ids in and out (nb * n_items each), offsets nb+1.
 hipError_t recommend_batch(int L, const float* P, const float* Q, const int32_t* d_users, int nb, int32_t n_items,
-                           int32_t topn, float* s_in, float* s_out, int32_t* id_in, int32_t* id_out, long long* d_off,
-                           void*& temp, size_t& temp_bytes, float* out_s, int32_t* out_i, hipStream_t st) {
-    hipError_t e;
+                           int32_t topn, const RecommendExcl& ex, float* s_in, float* s_out, int32_t* id_in, int32_t* id_out,
+                           long long* d_off, void*& temp, size_t& temp_bytes, float* out_s, int32_t* out_i, hipStream_t st) {
     switch (L) {
-        case 1: e = score_L<1>(P, Q, d_users, nb, n_items, s_in, id_in, st); break;
-        case 2: e = score_L<2>(P, Q, d_users, nb, n_items, s_in, id_in, st); break;
-        case 4: e = score_L<4>(P, Q, d_users, nb, n_items, s_in, id_in, st); break;
-        case 8: e = score_L<8>(P, Q, d_users, nb, n_items, s_in, id_in, st); break;
-        case 16: e = score_L<16>(P, Q, d_users, nb, n_items, s_in, id_in, st); break;
-        case 32: e = score_L<32>(P, Q, d_users, nb, n_items, s_in, id_in, st); break;
-        case 64: e = score_L<64>(P, Q, d_users, nb, n_items, s_in, id_in, st); break;
+#define MFSGD_BATCH(LL)                                                                                              \
+    case LL:                                                                                                         \
+        return batch_L<LL>(P, Q, d_users, nb, n_items, topn, ex, s_in, s_out, id_in, id_out, d_off, temp, temp_bytes, \
+                           out_s, out_i, st);
+        MFSGD_BATCH(1)
+        MFSGD_BATCH(2)
+        MFSGD_BATCH(4)
+        MFSGD_BATCH(8)
+        MFSGD_BATCH(16)
+        MFSGD_BATCH(32)
+        MFSGD_BATCH(64)
+#undef MFSGD_BATCH
         default: return hipErrorInvalidValue;
     }
+}
+
+hipError_t recommend_excl_filter(const int32_t* slot_of_user, const int32_t* u, const int32_t* i, int64_t n,
+                                 unsigned long long* keys, unsigned long long* count, int64_t cap, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    const long long blocks = std::min<long long>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(excl_filter_kernel, dim3((unsigned)blocks), dim3(256), 0, st, slot_of_user, u, i, (long long)n, keys,
+                       count, (unsigned long long)cap);
+    return hipGetLastError();
+}
+
+hipError_t recommend_excl_lists(unsigned long long* keys, unsigned long long* keys_tmp, int64_t n, int32_t n_slots,
+                                unsigned* n_distinct, long long* off, int32_t* items, void*& temp, size_t& temp_bytes,
+                                hipStream_t st) {
+    unsigned end_bit = 33;  // slot bits above the 32 of the item
+    while (end_bit < 64 && ((unsigned long long)(n_slots - 1) >> (end_bit - 32)) != 0) ++end_bit;
+    size_t need_sort = 0, need_uniq = 0;
+    hipError_t e = rocprim::radix_sort_keys(nullptr, need_sort, keys, keys_tmp, (size_t)n, 0u, end_bit, st);
+    if (e == hipSuccess)
+        e = rocprim::unique(nullptr, need_uniq, keys_tmp, keys, n_distinct, (size_t)n,
+                            rocprim::equal_to<unsigned long long>(), st);
+    if (e == hipSuccess) e = grow_temp(temp, temp_bytes, std::max(need_sort, need_uniq));
+    if (e == hipSuccess) e = rocprim::radix_sort_keys(temp, need_sort, keys, keys_tmp, (size_t)n, 0u, end_bit, st);
+    if (e == hipSuccess)
+        e = rocprim::unique(temp, need_uniq, keys_tmp, keys, n_distinct, (size_t)n,
+                            rocprim::equal_to<unsigned long long>(), st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(offsets_kernel, dim3(1), dim3(256), 0, st, d_off, nb, n_items);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    size_t need = 0;
-    e = rocprim::segmented_radix_sort_pairs_desc(nullptr, need, s_in, s_out, id_in, id_out, (unsigned)((size_t)nb * n_items),
-                                                 (unsigned)nb, d_off, d_off + 1, 0u, 32u, st);
-    if (e != hipSuccess) return e;
-    if (need > temp_bytes) {
-        if (temp) (void)hipFree(temp);
-        temp = nullptr;
-        temp_bytes = 0;
-        if ((e = hipMalloc(&temp, need)) != hipSuccess) return e;
-        temp_bytes = need;
-    }
-    e = rocprim::segmented_radix_sort_pairs_desc(temp, need, s_in, s_out, id_in, id_out, (unsigned)((size_t)nb * n_items),
-                                                 (unsigned)nb, d_off, d_off + 1, 0u, 32u, st);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(take_top_kernel, dim3((unsigned)nb), dim3(256), 0, st, s_out, id_out, n_items, topn, out_s, out_i);
+    const long long work = std::max<long long>(n, (long long)n_slots + 1);
+    const long long blocks = std::min<long long>((work + 255) / 256, 4096);
+    hipLaunchKernelGGL(excl_lists_kernel, dim3((unsigned)blocks), dim3(256), 0, st, keys, n_distinct, n_slots, off, items);
     return hipGetLastError();
 }
 

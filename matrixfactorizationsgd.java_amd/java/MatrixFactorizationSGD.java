@@ -81,6 +81,20 @@ public final class MatrixFactorizationSGD implements AutoCloseable {
         return out;
     }
 
+    /**
+     * As recommend(users, topN), but never item exclI[x] for user exclU[x] (typically the arrays the model was trained
+     * on, so that only unrated items come back).  A user with fewer than topN eligible items gets -1 in the places left.
+     */
+    public int[][] recommend(int[] users, int topN, int[] exclU, int[] exclI) {
+        if (exclU.length != exclI.length) throw new IllegalArgumentException("length mismatch");
+        int[] items = new int[users.length * topN];
+        float[] scores = new float[users.length * topN];
+        nativeRecommendExcluding(handle, users, topN, exclU, exclI, items, scores);
+        int[][] out = new int[users.length][];
+        for (int a = 0; a < users.length; a++) out[a] = java.util.Arrays.copyOfRange(items, a * topN, (a + 1) * topN);
+        return out;
+    }
+
     public double rmse() {
         return nativeRmse(handle);
     }
@@ -194,6 +208,8 @@ public final class MatrixFactorizationSGD implements AutoCloseable {
     private static native double nativeRmse(long h);
     private static native void nativePredict(long h, int[] u, int[] i, float[] out);
     private static native void nativeRecommend(long h, int[] users, int topN, int[] items, float[] scores);
+    private static native void nativeRecommendExcluding(long h, int[] users, int topN, int[] exclU, int[] exclI, int[] items,
+                                                        float[] scores);
     // DSGD (mfsgd_dsgd_*, mfsgd_set_item_partition, mfsgd_init_p_offset)
     private static native byte[] nativeDsgdUniqueId();
     private static native void nativeDsgdPlan(long[] degUser, long[] degItem, int nParts, int[] userBegin, int[] itemPart);

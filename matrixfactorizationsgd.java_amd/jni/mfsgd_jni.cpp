@@ -193,6 +193,35 @@ JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeRecommend(JNIEnv* env, 
     throw_status(env, H(h), rc);
 }
 
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeRecommendExcluding(JNIEnv* env, jclass, jlong h, jintArray users,
+                                                                            jint topn, jintArray excl_u, jintArray excl_i,
+                                                                            jintArray items, jfloatArray scores) {
+    if (!users || !excl_u || !excl_i || !items || !scores)
+        return throw_new(env, "java/lang/NullPointerException", "recommend");
+    const jsize n = env->GetArrayLength(users);
+    const jsize ne = env->GetArrayLength(excl_u);
+    if (env->GetArrayLength(excl_i) != ne)
+        return throw_new(env, "java/lang/IllegalArgumentException", "exclU and exclI must have the same length");
+    if (topn < 1 || (jlong)env->GetArrayLength(items) < (jlong)n * topn || (jlong)env->GetArrayLength(scores) < (jlong)n * topn)
+        return throw_new(env, "java/lang/IllegalArgumentException", "items / scores shorter than users x topN");
+    auto cu = alloc<int32_t>(env, (size_t)n);
+    auto ceu = alloc<int32_t>(env, (size_t)ne);
+    auto cei = alloc<int32_t>(env, (size_t)ne);
+    auto ci = alloc<int32_t>(env, (size_t)n * (size_t)topn);
+    auto cs = alloc<float>(env, (size_t)n * (size_t)topn);
+    if (!cu || !ceu || !cei || !ci || !cs) return;
+    env->GetIntArrayRegion(users, 0, n, reinterpret_cast<jint*>(cu.get()));
+    env->GetIntArrayRegion(excl_u, 0, ne, reinterpret_cast<jint*>(ceu.get()));
+    env->GetIntArrayRegion(excl_i, 0, ne, reinterpret_cast<jint*>(cei.get()));
+    if (env->ExceptionCheck()) return;
+    const int rc = mfsgd_recommend_excluding(H(h), cu.get(), n, topn, ceu.get(), cei.get(), (int64_t)ne, ci.get(), cs.get());
+    if (rc == MFSGD_OK && n > 0) {
+        env->SetIntArrayRegion(items, 0, n * topn, reinterpret_cast<const jint*>(ci.get()));
+        env->SetFloatArrayRegion(scores, 0, n * topn, cs.get());
+    }
+    throw_status(env, H(h), rc);
+}
+
 // ---- DSGD: the ring under the C-ABI (mfsgd_dsgd_*) for MatrixFactorizationSGD.trainDistributed ------------------
 
 JNIEXPORT jbyteArray JNICALL Java_MatrixFactorizationSGD_nativeDsgdUniqueId(JNIEnv* env, jclass) {

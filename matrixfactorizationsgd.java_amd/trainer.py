@@ -193,13 +193,19 @@ class MatrixFactorizationSGD:
                                             _p(out, C.c_float), uu.size))
         return float(out[0]) if scalar else out
 
-    def recommend(self, users, topn):
-        """(items, scores), each [len(users), topn]: best items per user, best first."""
+    def recommend(self, users, topn, exclude=None):
+        """(items, scores), each [len(users), topn]: best items per user, best first.  exclude = (u, i):
+        pairs never returned (for instance the training ratings, so that only unrated items come back);
+        a row with fewer than topn eligible items is padded with item -1 and score NaN."""
         uu = _i32(np.atleast_1d(users))
+        eu, ei = (np.empty(0, np.int32),) * 2 if exclude is None else (_i32(exclude[0]), _i32(exclude[1]))
+        if eu.shape != ei.shape or eu.ndim != 1:
+            raise ValueError("exclude must be two 1-d arrays of the same length")
         items = np.empty((uu.size, int(topn)), np.int32)
         scores = np.empty((uu.size, int(topn)), np.float32)
-        self._check(self._lib.mfsgd_recommend(self._handle(), _p(uu, C.c_int32), uu.size, int(topn),
-                                              _p(items, C.c_int32), _p(scores, C.c_float)))
+        self._check(self._lib.mfsgd_recommend_excluding(self._handle(), _p(uu, C.c_int32), uu.size, int(topn),
+                                                        _p(eu, C.c_int32), _p(ei, C.c_int32), eu.size,
+                                                        _p(items, C.c_int32), _p(scores, C.c_float)))
         return items, scores
 
     # -- schedule introspection (tests, bench) -----------------------------------

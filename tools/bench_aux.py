@@ -1,5 +1,5 @@
-"""Timings of the paths around training: predict (batched), recommend (top-N), RMSE pass,
-set_ratings (schedule build).  Wall-clock, through the C-ABI (host arrays in and out, so PCIe
+"""Timings of the paths around training: predict (batched), recommend (top-N, and top-N that leaves out
+the whole rating set), RMSE pass, set_ratings (schedule build).  Wall-clock, through the C-ABI (host arrays in and out, so PCIe
 copies are included); run it under `rocprofv3 --kernel-trace --stats` for the kernel times.
 
     python tools/bench_aux.py [WORKLOAD] [SCALE]
@@ -37,9 +37,16 @@ with mf.MatrixFactorizationSGD(w["U"], w["I"], k, 0.01, 0.05, 3, host_threads=16
     t0 = time.perf_counter()
     items, scores = m.recommend(users, 10)
     t_rec = time.perf_counter() - t0
+    m.recommend(users[:16], 10, exclude=(w["u"][:1000], w["i"][:1000]))
+    t0 = time.perf_counter()
+    items_x, scores_x = m.recommend(users, 10, exclude=(w["u"], w["i"]))
+    t_rec_x = time.perf_counter() - t0
+kept = int(np.isin(w["u"], users).sum())
 print(f"{name} x{scale}: {n} ratings, {w['U']} x {w['I']}, k = {k}")
 print(f"  set_ratings (schedule build + ingest)  {t_set * 1e3:9.1f} ms")
 print(f"  rmse pass                              {t_rmse * 1e3:9.3f} ms  = {n / t_rmse / 1e9:.2f} G ratings/s")
 print(f"  predict, {n} pairs (host in/out)   {t_pred * 1e3:9.1f} ms  = {n / t_pred / 1e9:.3f} G pairs/s")
 print(f"  recommend top-10, {users.size} users x {w['I']} items {t_rec * 1e3:9.1f} ms  = "
       f"{users.size * w['I'] / t_rec / 1e9:.2f} G scores/s")
+print(f"  recommend top-10 excluding all {n} ratings ({kept} are the requested users'), same users "
+      f"{t_rec_x * 1e3:9.1f} ms")
