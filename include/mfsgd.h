@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding (an addition: no existing call changed) */
+#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows (additions: no existing call changed) */
 
 typedef enum mfsgd_status {
     MFSGD_OK = 0,
@@ -160,6 +160,28 @@ int mfsgd_recommend(mfsgd_handle* h, const int32_t* users, int32_t n_users, int3
  * per-user lists are built on the device for this call and freed before it returns.     */
 int mfsgd_recommend_excluding(mfsgd_handle* h, const int32_t* users, int32_t n_users, int32_t topn, const int32_t* excl_u,
                               const int32_t* excl_i, int64_t n_excl, int32_t* out_items, float* out_scores);
+
+/* Fold-in: rows for n_new users that are not in the model, against the model's item factors Q, which stay fixed.
+ * New user x owns the ratings row_ptr[x] .. row_ptr[x + 1] (CSR, row_ptr[0] == 0) of items / ratings.  Its row starts
+ * as init_rows[x] (n_new x k, dense) or, with init_rows == NULL, as row x of the P that mfsgd_init_factors(seed) gives
+ * a model of n_new users (element f: draw x * k + f of java.util.Random(seed), nextFloat() / sqrt(k)).  Then, `epochs`
+ * times over the user's ratings in the order given, the P half of the canonical update:
+ *     q = Q[items[j]];  d = dot(row, q);  s = fma(-lr, d, lr * ratings[j]);  row[f] = fma(s, q[f], (1 - lr * lambda) * row[f])
+ * with the handle's lr and lambda.  out_rows (n_new x k, dense) receives the rows: bit for bit what the CPU oracle's
+ * update gives for p.  A user without ratings and epochs == 0 are valid (the start row comes back), and so is an item
+ * twice in one list (two steps).  The model is not modified.  A user's chain is sequential: one very long user costs
+ * length x epochs dependent steps however many other users there are.
+ * Arguments are checked before any device work (MFSGD_ERR_INVALID_ARG, message "fold_in: ..."): negative n_new or
+ * epochs, a null array that is needed, row_ptr[0] != 0, a decreasing row_ptr, an item outside [0, n_items).
+ * MFSGD_ERR_STATE: n_parts != 1 (the handle does not hold Q), or factors never initialised, set or loaded.
+ * n_new == 0 is MFSGD_OK.  Ratings go to the device in batches of whole users of bounded size.                      */
+int mfsgd_fold_in_users(mfsgd_handle* h, int32_t n_new, const int64_t* row_ptr, const int32_t* items, const float* ratings,
+                        int32_t epochs, const float* init_rows, int64_t seed, float* out_rows);
+/* Top-N as mfsgd_recommend_excluding, where "user j" is rows[j] (n_rows x k, dense: for instance what
+ * mfsgd_fold_in_users returned) instead of a row of P: every row is answered, in order, and excl_row[x] indexes rows.
+ * Same ordering, padding, scores and argument checks, with n_rows in the place of n_users.                           */
+int mfsgd_recommend_rows(mfsgd_handle* h, const float* rows, int32_t n_rows, int32_t topn, const int32_t* excl_row,
+                         const int32_t* excl_item, int64_t n_excl, int32_t* out_items, float* out_scores);
 
 /* Timed variant used by bench.py: runs `epochs` training passes bracketed by
  * HIP events on the handle's stream and returns the elapsed device time and

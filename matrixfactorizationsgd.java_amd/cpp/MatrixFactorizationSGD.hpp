@@ -83,6 +83,31 @@ class MatrixFactorizationSGD {
         return {std::move(items), std::move(scores)};
     }
 
+    // float[] foldIn(long[] rowPtr, int[] items, float[] ratings, int epochs[, float[] init]): rows (n_new x k, row-major)
+    // of users that are not in the model, against the fixed item factors; without init the rows start seeded
+    std::vector<float> foldIn(const std::vector<int64_t>& row_ptr, const std::vector<int32_t>& items,
+                              const std::vector<float>& ratings, int epochs, int64_t seed) {
+        return foldIn(row_ptr, items, ratings, epochs, nullptr, seed);
+    }
+    std::vector<float> foldIn(const std::vector<int64_t>& row_ptr, const std::vector<int32_t>& items,
+                              const std::vector<float>& ratings, int epochs, const std::vector<float>& init) {
+        if (row_ptr.empty() || init.size() != (row_ptr.size() - 1) * (size_t)k_) throw std::invalid_argument("length mismatch");
+        return foldIn(row_ptr, items, ratings, epochs, init.data(), 0);
+    }
+    // int[][] recommendRows(float[] rows, int topN, int[] exclRow, int[] exclItem): recommend for rows (n x k) that are
+    // not in the model, such as foldIn's; exclRow indexes rows
+    std::pair<std::vector<int32_t>, std::vector<float>> recommendRows(const std::vector<float>& rows, int topn,
+                                                                      const std::vector<int32_t>& excl_row = {},
+                                                                      const std::vector<int32_t>& excl_item = {}) {
+        if (excl_row.size() != excl_item.size() || rows.size() % (size_t)k_ != 0) throw std::invalid_argument("length mismatch");
+        const size_t n = rows.size() / (size_t)k_;
+        std::vector<int32_t> items(n * (size_t)topn);
+        std::vector<float> scores(n * (size_t)topn);
+        check(mfsgd_recommend_rows(h_, rows.data(), (int32_t)n, topn, excl_row.data(), excl_item.data(),
+                                   (int64_t)excl_row.size(), items.data(), scores.data()));
+        return {std::move(items), std::move(scores)};
+    }
+
     double rmse() {
         double out = 0.0;
         check(mfsgd_rmse(h_, &out));
@@ -171,6 +196,15 @@ class MatrixFactorizationSGD {
     }
 
    private:
+    std::vector<float> foldIn(const std::vector<int64_t>& row_ptr, const std::vector<int32_t>& items,
+                              const std::vector<float>& ratings, int epochs, const float* init, int64_t seed) {
+        if (row_ptr.empty() || items.size() != ratings.size() || (int64_t)items.size() != row_ptr.back())
+            throw std::invalid_argument("length mismatch");
+        std::vector<float> rows((row_ptr.size() - 1) * (size_t)k_);
+        check(mfsgd_fold_in_users(h_, (int32_t)(row_ptr.size() - 1), row_ptr.data(), items.data(), ratings.data(), epochs, init,
+                                  seed, rows.data()));
+        return rows;
+    }
     void check(int rc) {
         if (rc != MFSGD_OK) throw std::runtime_error(mfsgd_last_error(h_));
     }

@@ -1101,31 +1101,32 @@ int exclusions_to_device(mfsgd_handle* h, const std::vector<int32_t>& slot_of_us
 
 }  // namespace
 
-int mfsgd_recommend(mfsgd_handle* h, const int32_t* users, int32_t n_users, int32_t topn, int32_t* out_items,
-                    float* out_scores) {
-    return mfsgd_recommend_excluding(h, users, n_users, topn, nullptr, nullptr, 0, out_items, out_scores);
-}
+namespace {
 
-int mfsgd_recommend_excluding(mfsgd_handle* h, const int32_t* users, int32_t n_users, int32_t topn, const int32_t* excl_u,
-                              const int32_t* excl_i, int64_t n_excl, int32_t* out_items, float* out_scores) {
+// Body of the recommend calls: "user j" is row j of a matrix of n_rows rows, and `users` names the rows asked for.
+// host_rows == nullptr: the matrix is the model's P.  Otherwise it is host_rows (n_rows x k, dense), which goes up
+// into a kp-padded temporary for the length of the call.
+int recommend_core(mfsgd_handle* h, const float* host_rows, int32_t n_rows, const int32_t* users, int32_t n_users,
+                   int32_t topn, const int32_t* excl_u, const int32_t* excl_i, int64_t n_excl, int32_t* out_items,
+                   float* out_scores) {
     if (!h || n_users < 0 || topn < 1 || (n_users > 0 && (!users || !out_items || !out_scores)) || n_excl < 0 ||
         (n_excl > 0 && (!excl_u || !excl_i)))
         return fail(h, MFSGD_ERR_INVALID_ARG, "recommend: bad argument");
     if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "recommend: single-partition handles only");
     if (topn > h->cfg.n_items) return fail(h, MFSGD_ERR_INVALID_ARG, "recommend: topn exceeds the number of items");
     for (int32_t j = 0; j < n_users; ++j)
-        if (users[j] < 0 || users[j] >= h->cfg.n_users)
+        if (users[j] < 0 || users[j] >= n_rows)
             return fail(h, MFSGD_ERR_INVALID_ARG, "recommend: user " + std::to_string(j) + " out of range");
     // a slot per distinct requested user (one user asked for twice shares it), and how many pairs are theirs
     std::vector<int32_t> slot_of_user;
     int32_t n_slots = 0;
     int64_t kept = 0;
     if (n_excl > 0) {
-        slot_of_user.assign((size_t)h->cfg.n_users, -1);
+        slot_of_user.assign((size_t)n_rows, -1);
         for (int32_t j = 0; j < n_users; ++j)
             if (slot_of_user[(size_t)users[j]] < 0) slot_of_user[(size_t)users[j]] = n_slots++;
         for (int64_t x = 0; x < n_excl; ++x) {
-            if (excl_u[x] < 0 || excl_u[x] >= h->cfg.n_users || excl_i[x] < 0 || excl_i[x] >= h->cfg.n_items)
+            if (excl_u[x] < 0 || excl_u[x] >= n_rows || excl_i[x] < 0 || excl_i[x] >= h->cfg.n_items)
                 return fail(h, MFSGD_ERR_INVALID_ARG, "recommend: excluded pair " + std::to_string(x) + " out of range");
             kept += slot_of_user[(size_t)excl_u[x]] >= 0 ? 1 : 0;
         }
@@ -1133,6 +1134,8 @@ int mfsgd_recommend_excluding(mfsgd_handle* h, const int32_t* users, int32_t n_u
             return fail(h, MFSGD_ERR_INVALID_ARG, "recommend: more than 2^32 - 1 excluded pairs of the requested users");
     }
     if (n_users == 0) return MFSGD_OK;
+    if (host_rows && h->where == mfsgd_handle::Where::None)  // (asked here: factors_to_device wants a device first)
+        return fail(h, MFSGD_ERR_STATE, "recommend_rows: factors not initialised");
     int rc = factors_to_device(h);
     if (rc) return rc;
     const int32_t I = h->cfg.n_items;
@@ -1141,14 +1144,24 @@ int mfsgd_recommend_excluding(mfsgd_handle* h, const int32_t* users, int32_t n_u
     int batch = (int)std::max<int64_t>(1, std::min<int64_t>(n_users, ((int64_t)64 << 20) / std::max(1, I)));
     if (fused) batch = n_users;
     batch = std::min(batch, 65535);
-    DevBuf d_users, s_in, s_out, id_in, id_out, d_off, o_s, o_i, ex_slot, ex_off, ex_items;
+    DevBuf d_rows, d_users, s_in, s_out, id_in, id_out, d_off, o_s, o_i, ex_slot, ex_off, ex_items;
     void* temp = nullptr;
     size_t temp_bytes = 0;
     auto cleanup = [&]() {
-        d_users.release(); s_in.release(); s_out.release(); id_in.release(); id_out.release(); d_off.release();
+        d_rows.release(); d_users.release(); s_in.release(); s_out.release(); id_in.release(); id_out.release(); d_off.release();
         o_s.release(); o_i.release(); ex_slot.release(); ex_off.release(); ex_items.release();
         if (temp) (void)hipFree(temp);
     };
+    if (host_rows) {
+        const int k = h->cfg.k, kp = h->geo.kp;
+        std::vector<float> padded((size_t)n_rows * kp, 0.0f);
+        for (int64_t x = 0; x < n_rows; ++x) std::memcpy(&padded[(size_t)x * kp], host_rows + x * k, sizeof(float) * (size_t)k);
+        if ((rc = upload(h, d_rows, padded))) {
+            cleanup();
+            return rc;
+        }
+    }
+    const float* P = host_rows ? static_cast<const float*>(d_rows.p) : static_cast<const float*>(h->dP.p);
     RecommendExcl ex;  // built once for all batches; none when no pair belongs to a requested user
     if (kept > 0 && (rc = exclusions_to_device(h, slot_of_user, n_slots, excl_u, excl_i, n_excl, kept, ex_slot, ex_off,
                                                ex_items, temp, temp_bytes, ex))) {
@@ -1175,11 +1188,11 @@ int mfsgd_recommend_excluding(mfsgd_handle* h, const int32_t* users, int32_t n_u
         const int nb = std::min<int32_t>(batch, n_users - done);
         e = hipMemcpyAsync(d_users.p, users + done, sizeof(int32_t) * (size_t)nb, hipMemcpyHostToDevice, h->stream);
         if (e == hipSuccess && fused)
-            e = recommend_fused(h->geo.L, static_cast<const float*>(h->dP.p), static_cast<const float*>(h->dQ.p),
+            e = recommend_fused(h->geo.L, P, static_cast<const float*>(h->dQ.p),
                                 static_cast<const int32_t*>(d_users.p), nb, I, topn, ex, static_cast<float*>(o_s.p),
                                 static_cast<int32_t*>(o_i.p), h->stream);
         else if (e == hipSuccess)
-            e = recommend_batch(h->geo.L, static_cast<const float*>(h->dP.p), static_cast<const float*>(h->dQ.p),
+            e = recommend_batch(h->geo.L, P, static_cast<const float*>(h->dQ.p),
                                 static_cast<const int32_t*>(d_users.p), nb, I, topn, ex, static_cast<float*>(s_in.p),
                                 static_cast<float*>(s_out.p), static_cast<int32_t*>(id_in.p), static_cast<int32_t*>(id_out.p),
                                 static_cast<long long*>(d_off.p), temp, temp_bytes, static_cast<float*>(o_s.p),
@@ -1194,6 +1207,120 @@ int mfsgd_recommend_excluding(mfsgd_handle* h, const int32_t* users, int32_t n_u
     if (e != hipSuccess) {
         (void)hipGetLastError();
         return fail(h, e == hipErrorOutOfMemory ? MFSGD_ERR_OOM : MFSGD_ERR_HIP, std::string("recommend: ") + hipGetErrorString(e));
+    }
+    return MFSGD_OK;
+}
+
+}  // namespace
+
+int mfsgd_recommend(mfsgd_handle* h, const int32_t* users, int32_t n_users, int32_t topn, int32_t* out_items,
+                    float* out_scores) {
+    return mfsgd_recommend_excluding(h, users, n_users, topn, nullptr, nullptr, 0, out_items, out_scores);
+}
+
+int mfsgd_recommend_excluding(mfsgd_handle* h, const int32_t* users, int32_t n_users, int32_t topn, const int32_t* excl_u,
+                              const int32_t* excl_i, int64_t n_excl, int32_t* out_items, float* out_scores) {
+    if (!h) return MFSGD_ERR_INVALID_ARG;
+    return recommend_core(h, nullptr, h->cfg.n_users, users, n_users, topn, excl_u, excl_i, n_excl, out_items, out_scores);
+}
+
+int mfsgd_recommend_rows(mfsgd_handle* h, const float* rows, int32_t n_rows, int32_t topn, const int32_t* excl_row,
+                         const int32_t* excl_item, int64_t n_excl, int32_t* out_items, float* out_scores) {
+    if (!h || n_rows < 0 || (n_rows > 0 && !rows)) return fail(h, MFSGD_ERR_INVALID_ARG, "recommend_rows: bad argument");
+    std::vector<int32_t> all((size_t)n_rows);
+    for (int32_t j = 0; j < n_rows; ++j) all[(size_t)j] = j;
+    return recommend_core(h, rows, n_rows, all.data(), n_rows, topn, excl_row, excl_item, n_excl, out_items,
+                          out_scores);
+}
+
+namespace {
+// Ratings of one fold-in batch (whole users; a single user longer than this is a batch of its own): 32 MB of staging
+constexpr int64_t kFoldChunk = (int64_t)1 << 22;
+constexpr int64_t kFoldUsers = (int64_t)1 << 20;  // ... and its users, so that a run of empty users is bounded too
+}  // namespace
+
+int mfsgd_fold_in_users(mfsgd_handle* h, int32_t n_new, const int64_t* row_ptr, const int32_t* items, const float* ratings,
+                        int32_t epochs, const float* init_rows, int64_t seed, float* out_rows) {
+    if (!h) return MFSGD_ERR_INVALID_ARG;
+    if (n_new < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "fold_in: n_new is negative");
+    if (epochs < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "fold_in: epochs is negative");
+    if (n_new > 0 && (!row_ptr || !out_rows)) return fail(h, MFSGD_ERR_INVALID_ARG, "fold_in: row_ptr or out_rows is null");
+    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "fold_in: single-partition handles only");
+    if (h->where == mfsgd_handle::Where::None)  // (asked here: factors_to_device wants a device first)
+        return fail(h, MFSGD_ERR_STATE, "fold_in: factors not initialised");
+    if (n_new == 0) return MFSGD_OK;
+    if (row_ptr[0] != 0) return fail(h, MFSGD_ERR_INVALID_ARG, "fold_in: row_ptr[0] is not 0");
+    for (int32_t x = 0; x < n_new; ++x)
+        if (row_ptr[x + 1] < row_ptr[x])
+            return fail(h, MFSGD_ERR_INVALID_ARG, "fold_in: row_ptr decreases at user " + std::to_string(x));
+    const int64_t total = row_ptr[n_new];
+    if (total > 0 && (!items || !ratings)) return fail(h, MFSGD_ERR_INVALID_ARG, "fold_in: items or ratings is null");
+    for (int64_t j = 0; j < total; ++j)
+        if (items[j] < 0 || items[j] >= h->cfg.n_items)
+            return fail(h, MFSGD_ERR_INVALID_ARG, "fold_in: item of rating " + std::to_string(j) + " out of range");
+    int rc = factors_to_device(h);
+    if (rc) return rc;
+    const int k = h->cfg.k;
+    // batches of whole users, in the caller's order, so that each batch is one contiguous piece of items / ratings
+    std::vector<int32_t> cut{0};
+    int64_t max_ratings = 0, max_users = 0;
+    for (int32_t u0 = 0; u0 < n_new;) {
+        int32_t u1 = u0 + 1;
+        while (u1 < n_new && u1 - u0 < kFoldUsers && row_ptr[u1 + 1] - row_ptr[u0] <= kFoldChunk) ++u1;
+        max_ratings = std::max<int64_t>(max_ratings, row_ptr[u1] - row_ptr[u0]);
+        max_users = std::max<int64_t>(max_users, u1 - u0);
+        cut.push_back(u1);
+        u0 = u1;
+    }
+    DevBuf d_rows, d_ptr, d_perm, d_items, d_r;
+    auto cleanup = [&]() {
+        d_rows.release(); d_ptr.release(); d_perm.release(); d_items.release(); d_r.release();
+    };
+    const size_t row_bytes = sizeof(float) * (size_t)n_new * (size_t)k;
+    rc = dev_alloc(h, d_rows, row_bytes);
+    if (epochs > 0 && total > 0) {
+        if (!rc) rc = dev_alloc(h, d_ptr, sizeof(int64_t) * ((size_t)max_users + 1));
+        if (!rc) rc = dev_alloc(h, d_perm, sizeof(int32_t) * (size_t)max_users);
+        if (!rc) rc = dev_alloc(h, d_items, sizeof(int32_t) * (size_t)max_ratings);
+        if (!rc) rc = dev_alloc(h, d_r, sizeof(float) * (size_t)max_ratings);
+    }
+    if (rc) {
+        cleanup();
+        return rc;
+    }
+    // the start rows, dense: the kernel pads them to kp in its registers
+    hipError_t e;
+    if (init_rows)
+        e = hipMemcpyAsync(d_rows.p, init_rows, row_bytes, hipMemcpyHostToDevice, h->stream);
+    else
+        e = launch_init_rows(static_cast<float*>(d_rows.p), n_new, k, k, seed, 0, (float)(1.0 / std::sqrt((double)k)), h->stream);
+    std::vector<int32_t> perm;
+    for (size_t b = 0; b + 1 < cut.size() && e == hipSuccess && epochs > 0; ++b) {
+        const int32_t u0 = cut[b], nb = cut[b + 1] - cut[b];
+        const int64_t base = row_ptr[u0], nr = row_ptr[u0 + nb] - base;
+        if (nr == 0) continue;
+        // longest first: a wave runs as long as its longest user
+        perm.resize((size_t)nb);
+        for (int32_t x = 0; x < nb; ++x) perm[(size_t)x] = x;
+        const int64_t* rp = row_ptr + u0;
+        std::stable_sort(perm.begin(), perm.end(), [rp](int32_t a, int32_t b2) { return rp[a + 1] - rp[a] > rp[b2 + 1] - rp[b2]; });
+        e = hipMemcpyAsync(d_ptr.p, rp, sizeof(int64_t) * ((size_t)nb + 1), hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_perm.p, perm.data(), sizeof(int32_t) * (size_t)nb, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_items.p, items + base, sizeof(int32_t) * (size_t)nr, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_r.p, ratings + base, sizeof(float) * (size_t)nr, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess)
+            e = launch_fold_in(h->geo.L, static_cast<const float*>(h->dQ.p), static_cast<float*>(d_rows.p) + (size_t)u0 * k, k,
+                               static_cast<const long long*>(d_ptr.p), base, static_cast<const int32_t*>(d_perm.p), nb,
+                               static_cast<const int32_t*>(d_items.p), static_cast<const float*>(d_r.p), epochs, h->cfg.lr,
+                               1.0f - h->cfg.lr * h->cfg.lambda, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // perm and the staging buffers are reused
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out_rows, d_rows.p, row_bytes, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    cleanup();
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, e == hipErrorOutOfMemory ? MFSGD_ERR_OOM : MFSGD_ERR_HIP, std::string("fold_in: ") + hipGetErrorString(e));
     }
     return MFSGD_OK;
 }

@@ -42,6 +42,16 @@ hipError_t launch_reduce_sse(const double* partial, int64_t n, double* out, hipS
 hipError_t launch_predict(int L, const float* P, const float* Q, const int32_t* u, const int32_t* i,
                           float* out, int64_t n, hipStream_t st);
 
+// foldin.hip.  Fold-in of the nb users of one batch against fixed item factors Q (kp-padded rows): group g takes user
+// x = perm[g], whose ratings are entries row_ptr[x] - base .. row_ptr[x + 1] - base of items / ratings (row_ptr: nb + 1
+// words), and runs `epochs` passes of the P half of the canonical update over them, in the order given.
+// rows: nb x k dense, the start rows on entry and the folded rows on return.  perm is best sorted by length, longest
+// first (a wave runs as long as its longest user); the result does not depend on it.  The batch holds at least one
+// rating, and every item is a row of Q: the caller checks.
+hipError_t launch_fold_in(int L, const float* Q, float* rows, int k, const long long* row_ptr, long long base,
+                          const int32_t* perm, int nb, const int32_t* items, const float* ratings, int epochs, float lr,
+                          float c, hipStream_t st);
+
 // rows x kp floats: java.util.Random(seed) draws first_pos + row * k ... scaled, zero padded (device-side seeding).
 hipError_t launch_init_rows(float* dst, long long rows, int k, int kp, long long seed, unsigned long long first_pos, float scale,
                             hipStream_t st);

@@ -95,6 +95,37 @@ public final class MatrixFactorizationSGD implements AutoCloseable {
         return out;
     }
 
+    /**
+     * Rows (nNew x k, row-major) for users that are not in the model: new user x owns ratings rowPtr[x] .. rowPtr[x + 1]
+     * of items / ratings, and epochs passes of the per-rating SGD step run over them against the item factors, which
+     * stay fixed.  init (nNew x k) gives the start rows; null: seeded rows, as a model of nNew users would start.
+     * The model is not modified.
+     */
+    public float[] foldIn(long[] rowPtr, int[] items, float[] ratings, int epochs, float[] init, long seed) {
+        if (rowPtr.length < 1 || items.length != ratings.length || items.length != rowPtr[rowPtr.length - 1])
+            throw new IllegalArgumentException("length mismatch");
+        int nNew = rowPtr.length - 1;
+        if (init != null && init.length != nNew * k) throw new IllegalArgumentException("init must be nNew x k");
+        float[] rows = new float[nNew * k];
+        nativeFoldIn(handle, rowPtr, items, ratings, epochs, init, seed, rows);
+        return rows;
+    }
+
+    /**
+     * recommend(users, topN, exclU, exclI) for rows (n x k) that are not in the model, such as foldIn's: row j plays
+     * user j, and exclRow indexes rows.
+     */
+    public int[][] recommendRows(float[] rows, int topN, int[] exclRow, int[] exclItem) {
+        if (exclRow.length != exclItem.length || rows.length % k != 0) throw new IllegalArgumentException("length mismatch");
+        int n = rows.length / k;
+        int[] items = new int[n * topN];
+        float[] scores = new float[n * topN];
+        nativeRecommendRows(handle, rows, topN, exclRow, exclItem, items, scores);
+        int[][] out = new int[n][];
+        for (int a = 0; a < n; a++) out[a] = java.util.Arrays.copyOfRange(items, a * topN, (a + 1) * topN);
+        return out;
+    }
+
     public double rmse() {
         return nativeRmse(handle);
     }
@@ -210,6 +241,10 @@ public final class MatrixFactorizationSGD implements AutoCloseable {
     private static native void nativeRecommend(long h, int[] users, int topN, int[] items, float[] scores);
     private static native void nativeRecommendExcluding(long h, int[] users, int topN, int[] exclU, int[] exclI, int[] items,
                                                         float[] scores);
+    private static native void nativeFoldIn(long h, long[] rowPtr, int[] items, float[] ratings, int epochs, float[] init,
+                                            long seed, float[] rows);
+    private static native void nativeRecommendRows(long h, float[] rows, int topN, int[] exclRow, int[] exclItem, int[] items,
+                                                   float[] scores);
     // DSGD (mfsgd_dsgd_*, mfsgd_set_item_partition, mfsgd_init_p_offset)
     private static native byte[] nativeDsgdUniqueId();
     private static native void nativeDsgdPlan(long[] degUser, long[] degItem, int nParts, int[] userBegin, int[] itemPart);

@@ -222,6 +222,73 @@ JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeRecommendExcluding(JNIE
     throw_status(env, H(h), rc);
 }
 
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeFoldIn(JNIEnv* env, jclass, jlong h, jlongArray row_ptr, jintArray items,
+                                                                jfloatArray ratings, jint epochs, jfloatArray init, jlong seed,
+                                                                jfloatArray rows) {
+    if (!row_ptr || !items || !ratings || !rows) return throw_new(env, "java/lang/NullPointerException", "foldIn");
+    const jsize np = env->GetArrayLength(row_ptr);
+    const jsize nr = env->GetArrayLength(items);
+    const jsize nw = env->GetArrayLength(rows);
+    if (np < 1 || env->GetArrayLength(ratings) != nr || (init && env->GetArrayLength(init) != nw))
+        return throw_new(env, "java/lang/IllegalArgumentException", "foldIn: length mismatch");
+    auto cp = alloc<int64_t>(env, (size_t)np);
+    auto ci = alloc<int32_t>(env, (size_t)nr);
+    auto cr = alloc<float>(env, (size_t)nr);
+    auto c0 = alloc<float>(env, (size_t)nw);
+    auto cw = alloc<float>(env, (size_t)nw);
+    if (!cp || !ci || !cr || !c0 || !cw) return;
+    env->GetLongArrayRegion(row_ptr, 0, np, reinterpret_cast<jlong*>(cp.get()));
+    env->GetIntArrayRegion(items, 0, nr, reinterpret_cast<jint*>(ci.get()));
+    env->GetFloatArrayRegion(ratings, 0, nr, cr.get());
+    if (init) env->GetFloatArrayRegion(init, 0, nw, c0.get());
+    if (env->ExceptionCheck()) return;
+    int32_t n_users = 0, n_items = 0, k = 0;
+    int rc = mfsgd_get_dims(H(h), &n_users, &n_items, &k);
+    if (rc == MFSGD_OK && (jlong)nw != (jlong)(np - 1) * k)
+        return throw_new(env, "java/lang/IllegalArgumentException", "foldIn: rows must be nNew x k");
+    // (the last offset is checked against the arrays here: the C call cannot know their lengths)
+    if (rc == MFSGD_OK && cp.get()[np - 1] != (int64_t)nr)
+        return throw_new(env, "java/lang/IllegalArgumentException", "foldIn: rowPtr must end at items.length");
+    if (rc == MFSGD_OK)
+        rc = mfsgd_fold_in_users(H(h), (int32_t)(np - 1), cp.get(), ci.get(), cr.get(), epochs, init ? c0.get() : nullptr,
+                                 (int64_t)seed, cw.get());
+    if (rc == MFSGD_OK && nw > 0) env->SetFloatArrayRegion(rows, 0, nw, cw.get());
+    throw_status(env, H(h), rc);
+}
+
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeRecommendRows(JNIEnv* env, jclass, jlong h, jfloatArray rows, jint topn,
+                                                                       jintArray excl_row, jintArray excl_item, jintArray items,
+                                                                       jfloatArray scores) {
+    if (!rows || !excl_row || !excl_item || !items || !scores)
+        return throw_new(env, "java/lang/NullPointerException", "recommendRows");
+    int32_t n_users = 0, n_items = 0, k = 0;
+    int rc = mfsgd_get_dims(H(h), &n_users, &n_items, &k);
+    if (rc != MFSGD_OK) return throw_status(env, H(h), rc);
+    const jsize nf = env->GetArrayLength(rows);
+    const jsize ne = env->GetArrayLength(excl_row);
+    if (k < 1 || nf % k != 0 || env->GetArrayLength(excl_item) != ne)
+        return throw_new(env, "java/lang/IllegalArgumentException", "recommendRows: length mismatch");
+    const jsize n = nf / k;
+    if (topn < 1 || (jlong)env->GetArrayLength(items) < (jlong)n * topn || (jlong)env->GetArrayLength(scores) < (jlong)n * topn)
+        return throw_new(env, "java/lang/IllegalArgumentException", "items / scores shorter than rows x topN");
+    auto cr = alloc<float>(env, (size_t)nf);
+    auto cer = alloc<int32_t>(env, (size_t)ne);
+    auto cei = alloc<int32_t>(env, (size_t)ne);
+    auto ci = alloc<int32_t>(env, (size_t)n * (size_t)topn);
+    auto cs = alloc<float>(env, (size_t)n * (size_t)topn);
+    if (!cr || !cer || !cei || !ci || !cs) return;
+    env->GetFloatArrayRegion(rows, 0, nf, cr.get());
+    env->GetIntArrayRegion(excl_row, 0, ne, reinterpret_cast<jint*>(cer.get()));
+    env->GetIntArrayRegion(excl_item, 0, ne, reinterpret_cast<jint*>(cei.get()));
+    if (env->ExceptionCheck()) return;
+    rc = mfsgd_recommend_rows(H(h), cr.get(), n, topn, cer.get(), cei.get(), (int64_t)ne, ci.get(), cs.get());
+    if (rc == MFSGD_OK && n > 0) {
+        env->SetIntArrayRegion(items, 0, n * topn, reinterpret_cast<const jint*>(ci.get()));
+        env->SetFloatArrayRegion(scores, 0, n * topn, cs.get());
+    }
+    throw_status(env, H(h), rc);
+}
+
 // ---- DSGD: the ring under the C-ABI (mfsgd_dsgd_*) for MatrixFactorizationSGD.trainDistributed ------------------
 
 JNIEXPORT jbyteArray JNICALL Java_MatrixFactorizationSGD_nativeDsgdUniqueId(JNIEnv* env, jclass) {

@@ -208,6 +208,47 @@ class MatrixFactorizationSGD:
                                                         _p(items, C.c_int32), _p(scores, C.c_float)))
         return items, scores
 
+    def fold_in(self, row_ptr, items, ratings, epochs, init=None, seed=None):
+        """Rows [n_new, k] for users that are not in the model: new user x owns ratings row_ptr[x] .. row_ptr[x + 1]
+        of items / ratings (CSR), and `epochs` passes of the per-rating SGD step run over them against the model's
+        item factors, which stay fixed.  init: start rows [n_new, k]; None: seeded rows (seed None: the model's),
+        those init_factors(seed) would give a model of n_new users.  The model is not modified."""
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        ii, rr = _i32(items), _f32(ratings)
+        if rp.ndim != 1 or rp.size < 1:
+            raise ValueError("row_ptr must be a 1-d array of n_new + 1 offsets")
+        n_new = rp.size - 1
+        if ii.ndim != 1 or ii.shape != rr.shape or ii.size != rp[-1]:
+            raise ValueError("items and ratings must be 1-d arrays of row_ptr[-1] entries")
+        ip = None
+        if init is not None:
+            init = _f32(init)
+            if init.shape != (n_new, self.k):
+                raise ValueError("init must be n_new x k")
+            ip = _p(init, C.c_float)
+        rows = np.empty((n_new, self.k), np.float32)
+        self._check(self._lib.mfsgd_fold_in_users(self._handle(), n_new, _p(rp, C.c_int64), _p(ii, C.c_int32),
+                                                  _p(rr, C.c_float), int(epochs), ip,
+                                                  self.seed if seed is None else int(seed), _p(rows, C.c_float)))
+        return rows
+
+    def recommend_rows(self, rows, topn, exclude=None):
+        """recommend() for rows that are not in the model (for instance what fold_in returned): (items, scores), each
+        [len(rows), topn].  exclude = (row, item): pairs never returned, row indexing `rows`."""
+        rows = _f32(rows)
+        if rows.ndim != 2 or rows.shape[1] != self.k:
+            raise ValueError("rows must be n_rows x k")
+        er, ei = (np.empty(0, np.int32),) * 2 if exclude is None else (_i32(exclude[0]), _i32(exclude[1]))
+        if er.shape != ei.shape or er.ndim != 1:
+            raise ValueError("exclude must be two 1-d arrays of the same length")
+        n = rows.shape[0]
+        items = np.empty((n, int(topn)), np.int32)
+        scores = np.empty((n, int(topn)), np.float32)
+        self._check(self._lib.mfsgd_recommend_rows(self._handle(), _p(rows, C.c_float), n, int(topn), _p(er, C.c_int32),
+                                                   _p(ei, C.c_int32), er.size, _p(items, C.c_int32),
+                                                   _p(scores, C.c_float)))
+        return items, scores
+
     # -- schedule introspection (tests, bench) -----------------------------------
     def schedule_info(self, part=0):
         info = _lib.ScheduleInfo()

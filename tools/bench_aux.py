@@ -1,5 +1,6 @@
 """Timings of the paths around training: predict (batched), recommend (top-N, and top-N that leaves out
-the whole rating set), RMSE pass, set_ratings (schedule build).  Wall-clock, through the C-ABI (host arrays in and out, so PCIe
+the whole rating set), fold-in of users against the trained item factors and top-N for the folded rows, RMSE pass,
+set_ratings (schedule build).  Wall-clock, through the C-ABI (host arrays in and out, so PCIe
 copies are included); run it under `rocprofv3 --kernel-trace --stats` for the kernel times.
 
     python tools/bench_aux.py [WORKLOAD] [SCALE]
@@ -41,6 +42,22 @@ with mf.MatrixFactorizationSGD(w["U"], w["I"], k, 0.01, 0.05, 3, host_threads=16
     t0 = time.perf_counter()
     items_x, scores_x = m.recommend(users, 10, exclude=(w["u"], w["i"]))
     t_rec_x = time.perf_counter() - t0
+    # fold-in: the same users' own lists (in the workload's order) as if they were new, 10 epochs from seeded rows
+    mine = np.flatnonzero(np.isin(w["u"], users))
+    mine = mine[np.argsort(w["u"][mine], kind="stable")]
+    lens = np.bincount(w["u"][mine], minlength=w["U"])[users]
+    row_ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    f_items, f_ratings = w["i"][mine].astype(np.int32), w["r"][mine].astype(np.float32)
+    fold_epochs = 10
+    m.fold_in(row_ptr[:17], f_items[:row_ptr[16]], f_ratings[:row_ptr[16]], 1)
+    t0 = time.perf_counter()
+    rows = m.fold_in(row_ptr, f_items, f_ratings, fold_epochs)
+    t_fold = time.perf_counter() - t0
+    f_rows = np.repeat(np.arange(users.size, dtype=np.int32), lens).astype(np.int32)
+    m.recommend_rows(rows[:16], 10)
+    t0 = time.perf_counter()
+    items_r, scores_r = m.recommend_rows(rows, 10, exclude=(f_rows, f_items))
+    t_rec_r = time.perf_counter() - t0
 kept = int(np.isin(w["u"], users).sum())
 print(f"{name} x{scale}: {n} ratings, {w['U']} x {w['I']}, k = {k}")
 print(f"  set_ratings (schedule build + ingest)  {t_set * 1e3:9.1f} ms")
@@ -50,3 +67,9 @@ print(f"  recommend top-10, {users.size} users x {w['I']} items {t_rec * 1e3:9.1
       f"{users.size * w['I'] / t_rec / 1e9:.2f} G scores/s")
 print(f"  recommend top-10 excluding all {n} ratings ({kept} are the requested users'), same users "
       f"{t_rec_x * 1e3:9.1f} ms")
+n_fold = int(row_ptr[-1])
+print(f"  fold-in, {users.size} users, {n_fold} ratings (longest {int(lens.max())}), {fold_epochs} epochs {t_fold * 1e3:9.1f} ms  = "
+      f"{n_fold * fold_epochs / t_fold / 1e9:.3f} G updates/s (rmse pass: {n / t_rmse / 1e9:.2f} G ratings/s)")
+print(f"    chain bound: {int(lens.max())} x {fold_epochs} steps x 85 cycles at 2.07 GHz = "
+      f"{int(lens.max()) * fold_epochs * 85 / 2.07e9 * 1e3:.3f} ms for the slowest wave")
+print(f"  recommend_rows top-10 of the folded rows, excluding their {n_fold} ratings {t_rec_r * 1e3:9.1f} ms")
