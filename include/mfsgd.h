@@ -250,6 +250,12 @@ int mfsgd_debug_epoch_profile(mfsgd_handle* h, uint64_t* out, int32_t* n_workgro
  * already in place}.                                                                              */
 int mfsgd_debug_counters(const mfsgd_handle* h, int64_t* out4);
 
+/* Diagnostic (not part of the Java surface): *live = bytes of device memory the library holds in this process
+ * right now, over all handles (it takes none: the count is process-wide).  Memory a caller owns (the Q blocks
+ * handed to mfsgd_part_train) is not in it.  Tests compare it before and after a call, or a handle's whole
+ * life, to see that nothing was kept: free-memory readings of a shared GPU cannot tell.                     */
+int mfsgd_debug_device_bytes(int64_t* live);
+
 /* Diagnostic (not part of the Java surface): occupies the LDS of all but four CUs for `milliseconds` (<= 5000)
  * with a spinning kernel on a side stream, asynchronously -- what a foreign kernel sharing the GPU
  * looks like to the persistent epoch kernel.  Tests use it to force the "workgroups not co-resident"

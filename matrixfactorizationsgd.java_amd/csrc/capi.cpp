@@ -9,7 +9,6 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
-#include <cstdio>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -22,6 +21,7 @@
 #include <vector>
 
 #include "../../include/mfsgd.h"
+#include "devmem.hpp"
 #include "ingest.hpp"
 #include "jrandom.hpp"
 #include "kernels.hpp"
@@ -32,16 +32,6 @@ using namespace mfsgd;
 namespace {
 
 thread_local std::string g_create_error;
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-};
 
 struct Part {
     Schedule sched;
@@ -57,6 +47,15 @@ struct Part {
     // training graphs keyed by the (P, Q) pointers they were captured with (both are baked into the
     // kernel node; P changes when the factors are re-seeded, Q with every caller-owned block)
     std::map<std::pair<const void*, const void*>, hipGraphExec_t> graphs;
+
+    Part() = default;
+    Part(Part&&) = default;  // (the moved-from map is empty: nothing is destroyed twice)
+    ~Part() { drop_graphs(); }
+    void drop_graphs() {
+        for (auto& kv : graphs)
+            if (kv.second) (void)hipGraphExecDestroy(kv.second);
+        graphs.clear();
+    }
 };
 
 }  // namespace
@@ -99,13 +98,28 @@ int fail(const mfsgd_handle* h, int code, const std::string& msg) {
     return code;
 }
 
+int hip_fail(const mfsgd_handle* h, const std::string& what, hipError_t e) {
+    return fail(h, e == hipErrorOutOfMemory ? MFSGD_ERR_OOM : MFSGD_ERR_HIP, what + hipGetErrorString(e));
+}
+
 #define HIPCHK(h, call)                                                                         \
     do {                                                                                        \
         hipError_t e_ = (call);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return fail((h), e_ == hipErrorOutOfMemory ? MFSGD_ERR_OOM : MFSGD_ERR_HIP,         \
-                        std::string(#call) + ": " + hipGetErrorString(e_));                     \
+        if (e_ != hipSuccess) return hip_fail((h), std::string(#call) + ": ", e_);              \
     } while (0)
+
+// The serving calls name themselves instead of the HIP call that failed: `bad` makes the return code of an error ...
+#define HIPCHK_OR(bad, call)                   \
+    do {                                       \
+        hipError_t e_ = (call);                \
+        if (e_ != hipSuccess) return bad(e_);  \
+    } while (0)
+
+// ... and most of them leave no error behind in the runtime
+int serve_fail(const mfsgd_handle* h, const char* prefix, hipError_t e) {
+    (void)hipGetLastError();
+    return hip_fail(h, prefix, e);
+}
 
 int usable_devices(int* count, std::string* why) {
     int n = 0;
@@ -147,11 +161,8 @@ int ensure_device(mfsgd_handle* h) {
 }
 
 int dev_alloc(mfsgd_handle* h, DevBuf& b, size_t bytes) {
-    if (b.p && b.bytes >= bytes) return MFSGD_OK;
-    b.release();
-    if (bytes == 0) bytes = 16;
-    HIPCHK(h, hipMalloc(&b.p, bytes));
-    b.bytes = bytes;
+    const hipError_t e = b.alloc(bytes);
+    if (e != hipSuccess) return hip_fail(h, "hipMalloc(&b.p, bytes): ", e);  // (the text this failure has always had)
     return MFSGD_OK;
 }
 
@@ -160,14 +171,8 @@ int upload(mfsgd_handle* h, DevBuf& b, const T& v) {
     using E = std::remove_reference_t<decltype(*v.data())>;
     int rc = dev_alloc(h, b, v.size() * sizeof(E));
     if (rc) return rc;
-    if (!v.empty()) HIPCHK(h, hipMemcpy(b.p, v.data(), v.size() * sizeof(E), hipMemcpyHostToDevice));
+    if (!v.empty()) HIPCHK(h, hipMemcpy(b.get(), v.data(), v.size() * sizeof(E), hipMemcpyHostToDevice));
     return MFSGD_OK;
-}
-
-void drop_graphs(Part& p) {
-    for (auto& kv : p.graphs)
-        if (kv.second) (void)hipGraphExecDestroy(kv.second);
-    p.graphs.clear();
 }
 
 // The device copies of the factors go away (re-seed, set_factors, load): nothing captured with the
@@ -178,9 +183,9 @@ void release_device_factors(mfsgd_handle* h) {
         (void)hipSetDevice(h->cfg.device);
         (void)hipDeviceSynchronize();
     }
-    for (Part& p : h->parts) drop_graphs(p);
-    h->dP.release();
-    h->dQ.release();
+    for (Part& p : h->parts) p.drop_graphs();
+    h->dP.reset();
+    h->dQ.reset();
 }
 
 void default_item_map(mfsgd_handle* h) {
@@ -205,31 +210,23 @@ void default_item_map(mfsgd_handle* h) {
 size_t sync_bytes(const Part& p) {
     return ((size_t)p.sched.B * kDoneStride + 8) * sizeof(unsigned) + (size_t)p.sched.B * (size_t)p.sched.geo.L * 4 * 8;
 }
-unsigned* abort_word(const Part& p) { return static_cast<unsigned*>(p.d_sync.p) + (size_t)p.sched.B * kDoneStride + 4; }
+unsigned* abort_word(const Part& p) { return p.d_sync.as<unsigned>() + (size_t)p.sched.B * kDoneStride + 4; }
 
 int ensure_part_on_device(mfsgd_handle* h, Part& p) {
     if (p.on_device) return MFSGD_OK;
     int rc;
     if ((rc = upload(h, p.d_cells, p.sched.cells))) return rc;
-    if (p.sched.device_packed && p.sched.dev.buf.subs) {
+    DevicePacked& dev = p.sched.dev.buf;
+    if (p.sched.device_packed && dev.subs) {
         // (the device assembled the sub-cell tables too)
-        p.d_subs.release();
-        p.d_subs.p = p.sched.dev.buf.subs;
-        p.d_subs.bytes = (size_t)p.sched.dev.buf.n_subs * sizeof(SubDesc);
-        p.sched.dev.buf.subs = nullptr;
+        p.d_subs.adopt(std::exchange(dev.subs, nullptr), (size_t)dev.n_subs * sizeof(SubDesc));
     } else if ((rc = upload(h, p.d_subs, p.sched.subs))) {
         return rc;
     }
     if (p.sched.device_packed) {
-        // the device packer left rows and entries where they are needed
-        p.d_rows.release();
-        p.d_entries.release();
-        p.d_rows.p = p.sched.dev.buf.rows;
-        p.d_rows.bytes = (size_t)p.sched.n_rows_words * sizeof(uint32_t);
-        p.d_entries.p = p.sched.dev.buf.entries;
-        p.d_entries.bytes = (size_t)p.sched.n_entry_recs * sizeof(Entry);
-        p.sched.dev.buf.rows = nullptr;  // owned by the DevBufs from here on (same allocator: hipFree)
-        p.sched.dev.buf.entries = nullptr;
+        // the device packer left rows and entries where they are needed: the DevBufs own them from here on
+        p.d_rows.adopt(std::exchange(dev.rows, nullptr), (size_t)p.sched.n_rows_words * sizeof(uint32_t));
+        p.d_entries.adopt(std::exchange(dev.entries, nullptr), (size_t)p.sched.n_entry_recs * sizeof(Entry));
     } else {
         if ((rc = upload(h, p.d_rows, p.sched.rows))) return rc;
         if ((rc = upload(h, p.d_entries, p.sched.entries))) return rc;
@@ -237,7 +234,7 @@ int ensure_part_on_device(mfsgd_handle* h, Part& p) {
     if ((rc = dev_alloc(h, p.d_sse_partial, sizeof(double) * p.sched.cells.size()))) return rc;
     if ((rc = dev_alloc(h, p.d_sse_out, sizeof(double)))) return rc;
     if ((rc = dev_alloc(h, p.d_sync, sync_bytes(p)))) return rc;
-    HIPCHK(h, hipMemset(p.d_sync.p, 0, sync_bytes(p)));
+    HIPCHK(h, hipMemset(p.d_sync.get(), 0, sync_bytes(p)));
     HIPCHK(h, hipDeviceSynchronize());  // (memset is asynchronous; the first launch may be on another stream)
     p.on_device = true;
     return MFSGD_OK;
@@ -260,12 +257,12 @@ int factors_to_device(mfsgd_handle* h) {
 
 CellLaunch make_launch(const mfsgd_handle* h, const Part& p, float* Q) {
     CellLaunch a{};
-    a.P = p.swapped ? Q : static_cast<float*>(h->dP.p);
-    a.Q = p.swapped ? static_cast<float*>(h->dP.p) : Q;
-    a.cells = static_cast<const CellDesc*>(p.d_cells.p);
-    a.rows = static_cast<const uint32_t*>(p.d_rows.p);
-    a.subs = static_cast<const SubDesc*>(p.d_subs.p);
-    a.entries = static_cast<const Entry*>(p.d_entries.p);
+    a.P = p.swapped ? Q : h->dP.as<float>();
+    a.Q = p.swapped ? h->dP.as<float>() : Q;
+    a.cells = p.d_cells.as<const CellDesc>();
+    a.rows = p.d_rows.as<const uint32_t>();
+    a.subs = p.d_subs.as<const SubDesc>();
+    a.entries = p.d_entries.as<const Entry>();
     a.B = p.sched.B;
     a.rd = 0;
     a.grid = p.sched.B;
@@ -273,7 +270,7 @@ CellLaunch make_launch(const mfsgd_handle* h, const Part& p, float* Q) {
     a.sched_cap = p.sched.sched_cap;
     a.lr = h->cfg.lr;
     a.c = 1.0f - h->cfg.lr * h->cfg.lambda;
-    a.sse_partial = static_cast<double*>(p.d_sse_partial.p);
+    a.sse_partial = p.d_sse_partial.as<double>();
     return a;
 }
 
@@ -316,8 +313,7 @@ int launch_epoch_body(mfsgd_handle* h, Part& p, float* Q, hipStream_t st) {
         // flags are counted within the launch: zero them (and the abort word) every time
         // no memset: the kernel resets its own hand-off flags behind a device-side barrier (kernels.hip,
         // run_ring) -- a memset node in a replayed graph is not reliably ordered before the kernel node
-        HIPCHK(h, launch_epoch_persistent(h->geo.L, p.sched.W, a, p.sched.B, static_cast<unsigned*>(p.d_sync.p),
-                                          abort_word(p), st));
+        HIPCHK(h, launch_epoch_persistent(h->geo.L, p.sched.W, a, p.sched.B, p.d_sync.as<unsigned>(), abort_word(p), st));
         return MFSGD_OK;
     }
     return launch_epoch_eager(h, p, Q, st);
@@ -329,7 +325,7 @@ int launch_epoch(mfsgd_handle* h, Part& p, float* Q, hipStream_t st) {
     int rc = probe_persistent(h, p);
     if (rc) return rc;
     if (h->cfg.flags & MFSGD_FLAG_NO_GRAPH) return launch_epoch_body(h, p, Q, st);
-    const auto key = std::make_pair((const void*)h->dP.p, (const void*)Q);
+    const auto key = std::make_pair((const void*)h->dP.get(), (const void*)Q);
     auto it = p.graphs.find(key);
     if (it == p.graphs.end()) {
         // capture the launch(es) of one epoch once; replayed every epoch
@@ -349,7 +345,7 @@ int launch_epoch(mfsgd_handle* h, Part& p, float* Q, hipStream_t st) {
         if (p.graphs.size() >= 32) {
             // replays of the old graphs may still be in flight on a caller's stream
             HIPCHK(h, hipDeviceSynchronize());
-            drop_graphs(p);
+            p.drop_graphs();
         }
         it = p.graphs.emplace(key, exec).first;
     }
@@ -364,7 +360,7 @@ int launch_epoch(mfsgd_handle* h, Part& p, float* Q, hipStream_t st) {
 constexpr int kNotResident = 1;
 int check_abort(mfsgd_handle* h, Part& p, unsigned* started = nullptr) {
     if (started) *started = 0;
-    if (p.persistent_np <= 0 || !p.d_sync.p) return MFSGD_OK;
+    if (p.persistent_np <= 0 || !p.d_sync) return MFSGD_OK;
     unsigned w[2] = {0, 0};
     HIPCHK(h, hipMemcpy(w, abort_word(p), sizeof w, hipMemcpyDeviceToHost));
     if (started) *started = w[1];
@@ -390,7 +386,7 @@ int check_abort(mfsgd_handle* h, Part& p, unsigned* started = nullptr) {
 // with a slower peer on its communication stream) is not needed.
 void give_up_persistence(mfsgd_handle* h, Part& p, const hipStream_t* idle = nullptr) {
     if (!idle) (void)hipDeviceSynchronize();
-    drop_graphs(p);
+    p.drop_graphs();
     p.persistent_np = 0;
     h->n_not_resident++;
 }
@@ -417,7 +413,7 @@ int launch_sse(mfsgd_handle* h, Part& p, const float* Q, hipStream_t st) {
         a.grid = std::min(n_cells, per_cu * std::max(1, h->n_cu));
         HIPCHK(h, launch_sse_persistent(h->geo.L, p.sched.W, a, n_cells, st));
     }
-    HIPCHK(h, launch_reduce_sse(a.sse_partial, (int64_t)a.grid, static_cast<double*>(p.d_sse_out.p), st));
+    HIPCHK(h, launch_reduce_sse(a.sse_partial, (int64_t)a.grid, p.d_sse_out.as<double>(), st));
     return MFSGD_OK;
 }
 
@@ -428,12 +424,10 @@ int part_sse_sync(mfsgd_handle* h, Part& p, const float* Q, hipStream_t st, doub
     }
     int rc = launch_sse(h, p, Q, st);
     if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(sse, p.d_sse_out.p, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(sse, p.d_sse_out.get(), sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
     return check_abort_strict(h, p);
 }
-
-int launch_epoch(mfsgd_handle* h, Part& p, float* Q, hipStream_t st);
 
 // `launched` epochs of a single-partition handle are in flight on st: wait, and if the persistent
 // kernel found itself not resident (it then did nothing, nor did the launches behind it), run what
@@ -464,8 +458,8 @@ int host_copies(const mfsgd_handle* h, const Part& cp, bool want_order, bool wan
     try {
         DevicePacked d = s.dev.buf;
         if (p.on_device) {  // rows / entries have moved into the DevBufs
-            d.rows = p.d_rows.p;
-            d.entries = p.d_entries.p;
+            d.rows = p.d_rows.get();
+            d.entries = p.d_entries.get();
         }
         if (want_order && s.order.empty() && s.nnz > 0) {
             s.order.resize_uninit((size_t)s.nnz);
@@ -473,7 +467,7 @@ int host_copies(const mfsgd_handle* h, const Part& cp, bool want_order, bool wan
                 return fail(h, MFSGD_ERR_HIP, "could not copy the canonical order from the device");
         }
         if (want_arrays && s.subs.empty() && s.n_sub_recs > 0 && s.dev_ops->download_raw) {
-            const void* dsubs = p.on_device ? p.d_subs.p : s.dev.buf.subs;
+            const void* dsubs = p.on_device ? p.d_subs.get() : s.dev.buf.subs;
             if (dsubs) {
                 s.subs.resize((size_t)s.n_sub_recs);
                 if (s.dev_ops->download_raw(dsubs, s.subs.data(), s.subs.size() * sizeof(SubDesc)) != 0)
@@ -635,18 +629,9 @@ void mfsgd_destroy(mfsgd_handle* h) {
         (void)hipSetDevice(h->cfg.device);
         (void)hipStreamSynchronize(h->stream);
     }
-    for (Part& p : h->parts) {
-        drop_graphs(p);
-        p.d_cells.release();
-        p.d_rows.release();
-        p.d_subs.release();
-        p.d_entries.release();
-        p.d_sse_partial.release();
-        p.d_sse_out.release();
-        p.d_sync.release();
-    }
-    h->dP.release();
-    h->dQ.release();
+    h->parts.clear();
+    h->dP.reset();
+    h->dQ.reset();
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->side_stream) {
@@ -686,16 +671,6 @@ int mfsgd_set_ratings(mfsgd_handle* h, const int32_t* u, const int32_t* i, const
         if (h->device_ready) {
             (void)hipSetDevice(h->cfg.device);
             (void)hipStreamSynchronize(h->stream);
-        }
-        for (Part& p : h->parts) {
-            drop_graphs(p);
-            p.d_cells.release();
-            p.d_rows.release();
-            p.d_subs.release();
-            p.d_entries.release();
-            p.d_sse_partial.release();
-            p.d_sse_out.release();
-            p.d_sync.release();
         }
         h->parts.clear();
         h->have_ratings = false;
@@ -857,11 +832,11 @@ static int seed_factors(mfsgd_handle* h, int64_t seed, int64_t u_offset, bool wi
     if (ensure_device(h) == MFSGD_OK) {
         int rc;
         if ((rc = dev_alloc(h, h->dP, sizeof(float) * (size_t)h->cfg.n_users * kp))) return rc;
-        HIPCHK(h, launch_init_rows(static_cast<float*>(h->dP.p), h->cfg.n_users, k, kp, seed, (unsigned long long)u_offset * (unsigned long long)k,
+        HIPCHK(h, launch_init_rows(h->dP.as<float>(), h->cfg.n_users, k, kp, seed, (unsigned long long)u_offset * (unsigned long long)k,
                                    scale, h->stream));
         if (with_q) {
             if ((rc = dev_alloc(h, h->dQ, sizeof(float) * (size_t)h->cfg.n_items * kp))) return rc;
-            HIPCHK(h, launch_init_rows(static_cast<float*>(h->dQ.p), h->cfg.n_items, k, kp, seed,
+            HIPCHK(h, launch_init_rows(h->dQ.as<float>(), h->cfg.n_items, k, kp, seed,
                                        (unsigned long long)h->cfg.n_users * (unsigned long long)k, scale, h->stream));
         }
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -936,11 +911,11 @@ int mfsgd_get_factors(mfsgd_handle* h, float* P, float* Q) {
             HIPCHK(h, hipStreamSynchronize(h->stream));
             if (P) {
                 tp.resize((size_t)h->cfg.n_users * kp);
-                HIPCHK(h, hipMemcpy(tp.data(), h->dP.p, tp.size() * sizeof(float), hipMemcpyDeviceToHost));
+                HIPCHK(h, hipMemcpy(tp.data(), h->dP.get(), tp.size() * sizeof(float), hipMemcpyDeviceToHost));
             }
             if (Q && h->n_parts == 1) {
                 tq.resize((size_t)h->cfg.n_items * kp);
-                HIPCHK(h, hipMemcpy(tq.data(), h->dQ.p, tq.size() * sizeof(float), hipMemcpyDeviceToHost));
+                HIPCHK(h, hipMemcpy(tq.data(), h->dQ.get(), tq.size() * sizeof(float), hipMemcpyDeviceToHost));
             }
             sp = &tp;
             sq = &tq;
@@ -963,7 +938,7 @@ int mfsgd_train(mfsgd_handle* h, int32_t epochs, double* rmse_per_epoch) {
     int rc = prepare_compute(h);
     if (rc) return rc;
     Part& p = h->parts[0];
-    float* Q = static_cast<float*>(h->dQ.p);
+    float* Q = h->dQ.as<float>();
     for (int e = 0; e < epochs; ++e) {
         if ((rc = launch_epoch(h, p, Q, h->stream))) return rc;
         if (rmse_per_epoch) {
@@ -982,7 +957,7 @@ int mfsgd_train_timed(mfsgd_handle* h, int32_t epochs, double* elapsed_ms, int64
     int rc = prepare_compute(h);
     if (rc) return rc;
     Part& p = h->parts[0];
-    float* Q = static_cast<float*>(h->dQ.p);
+    float* Q = h->dQ.as<float>();
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));
     for (int e = 0; e < epochs; ++e)
@@ -1003,7 +978,7 @@ int mfsgd_rmse(mfsgd_handle* h, double* out) {
     if (rc) return rc;
     Part& p = h->parts[0];
     double sse = 0.0;
-    if ((rc = part_sse_sync(h, p, static_cast<const float*>(h->dQ.p), h->stream, &sse))) return rc;
+    if ((rc = part_sse_sync(h, p, h->dQ.as<const float>(), h->stream, &sse))) return rc;
     *out = p.sched.nnz > 0 ? std::sqrt(sse / (double)p.sched.nnz) : 0.0;
     return MFSGD_OK;
 }
@@ -1018,28 +993,17 @@ int mfsgd_predict(mfsgd_handle* h, const int32_t* u, const int32_t* i, float* ou
     int rc = factors_to_device(h);
     if (rc) return rc;
     DevBuf du, di, dout;
-    auto cleanup = [&]() {
-        du.release();
-        di.release();
-        dout.release();
-    };
-    rc = dev_alloc(h, du, sizeof(int32_t) * (size_t)n);
-    if (!rc) rc = dev_alloc(h, di, sizeof(int32_t) * (size_t)n);
-    if (!rc) rc = dev_alloc(h, dout, sizeof(float) * (size_t)n);
-    if (rc) {
-        cleanup();
-        return rc;
-    }
-    hipError_t e = hipMemcpyAsync(du.p, u, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(di.p, i, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess)
-        e = launch_predict(h->geo.L, static_cast<const float*>(h->dP.p), static_cast<const float*>(h->dQ.p),
-                           static_cast<const int32_t*>(du.p), static_cast<const int32_t*>(di.p),
-                           static_cast<float*>(dout.p), n, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dout.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    cleanup();
-    if (e != hipSuccess) return fail(h, MFSGD_ERR_HIP, std::string("predict: ") + hipGetErrorString(e));
+    if ((rc = dev_alloc(h, du, sizeof(int32_t) * (size_t)n))) return rc;
+    if ((rc = dev_alloc(h, di, sizeof(int32_t) * (size_t)n))) return rc;
+    if ((rc = dev_alloc(h, dout, sizeof(float) * (size_t)n))) return rc;
+    // (this call has always reported every HIP failure as MFSGD_ERR_HIP and left the runtime's error word alone)
+    auto bad = [h](hipError_t e) { return fail(h, MFSGD_ERR_HIP, std::string("predict: ") + hipGetErrorString(e)); };
+    HIPCHK_OR(bad, hipMemcpyAsync(du.get(), u, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    HIPCHK_OR(bad, hipMemcpyAsync(di.get(), i, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    HIPCHK_OR(bad, launch_predict(h->geo.L, h->dP.as<const float>(), h->dQ.as<const float>(), du.as<const int32_t>(),
+                                  di.as<const int32_t>(), dout.as<float>(), n, h->stream));
+    HIPCHK_OR(bad, hipMemcpyAsync(out, dout.get(), sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
     return MFSGD_OK;
 }
 
@@ -1047,55 +1011,40 @@ namespace {
 
 // Exclusion lists of one recommend call on the device: the pairs go up in chunks of bounded size, those of requested
 // users are kept (slot << 32 | item), then sorted and made distinct into one list per slot (recommend.hip).
-// Scratch is freed here; `ex` points into `slot`, `off` and `items`, which the caller frees.
+// Scratch lives as long as this function; `ex` points into `slot`, `off` and `items`, which are the caller's.
 constexpr int64_t kExclChunk = (int64_t)1 << 22;  // pairs per upload: 32 MB of staging
 
 int exclusions_to_device(mfsgd_handle* h, const std::vector<int32_t>& slot_of_user, int32_t n_slots, const int32_t* excl_u,
                          const int32_t* excl_i, int64_t n_excl, int64_t kept, DevBuf& slot, DevBuf& off, DevBuf& items,
-                         void*& temp, size_t& temp_bytes, RecommendExcl& ex) {
+                         DevBuf& temp, RecommendExcl& ex) {
+    auto bad = [h](hipError_t e) { return serve_fail(h, "recommend: exclusion lists: ", e); };
     DevBuf cu, ci, keys, keys_tmp, count;
-    auto cleanup = [&]() {
-        cu.release(); ci.release(); keys.release(); keys_tmp.release(); count.release();
-    };
     const int64_t chunk = std::min(n_excl, kExclChunk);
-    int rc = upload(h, slot, slot_of_user);
-    if (!rc) rc = dev_alloc(h, cu, sizeof(int32_t) * (size_t)chunk);
-    if (!rc) rc = dev_alloc(h, ci, sizeof(int32_t) * (size_t)chunk);
-    if (!rc) rc = dev_alloc(h, keys, 8 * (size_t)kept);
-    if (!rc) rc = dev_alloc(h, keys_tmp, 8 * (size_t)kept);
-    if (!rc) rc = dev_alloc(h, count, 16);  // [0] appended pairs (u64), [2] distinct ones (u32)
-    if (!rc) rc = dev_alloc(h, off, sizeof(long long) * ((size_t)n_slots + 1));
-    if (!rc) rc = dev_alloc(h, items, sizeof(int32_t) * (size_t)kept);
-    if (rc) {
-        cleanup();
-        return rc;
-    }
-    auto* cnt = static_cast<unsigned long long*>(count.p);
-    hipError_t e = hipMemsetAsync(count.p, 0, 16, h->stream);
-    for (int64_t x0 = 0; x0 < n_excl && e == hipSuccess; x0 += chunk) {
+    int rc;
+    if ((rc = upload(h, slot, slot_of_user))) return rc;
+    if ((rc = dev_alloc(h, cu, sizeof(int32_t) * (size_t)chunk))) return rc;
+    if ((rc = dev_alloc(h, ci, sizeof(int32_t) * (size_t)chunk))) return rc;
+    if ((rc = dev_alloc(h, keys, 8 * (size_t)kept))) return rc;
+    if ((rc = dev_alloc(h, keys_tmp, 8 * (size_t)kept))) return rc;
+    if ((rc = dev_alloc(h, count, 16))) return rc;  // [0] appended pairs (u64), [2] distinct ones (u32)
+    if ((rc = dev_alloc(h, off, sizeof(long long) * ((size_t)n_slots + 1)))) return rc;
+    if ((rc = dev_alloc(h, items, sizeof(int32_t) * (size_t)kept))) return rc;
+    auto* cnt = count.as<unsigned long long>();
+    HIPCHK_OR(bad, hipMemsetAsync(cnt, 0, 16, h->stream));
+    for (int64_t x0 = 0; x0 < n_excl; x0 += chunk) {
         const int64_t c = std::min(chunk, n_excl - x0);
-        e = hipMemcpyAsync(cu.p, excl_u + x0, sizeof(int32_t) * (size_t)c, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(ci.p, excl_i + x0, sizeof(int32_t) * (size_t)c, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess)
-            e = recommend_excl_filter(static_cast<const int32_t*>(slot.p), static_cast<const int32_t*>(cu.p),
-                                      static_cast<const int32_t*>(ci.p), c, static_cast<unsigned long long*>(keys.p), cnt,
-                                      kept, h->stream);
+        HIPCHK_OR(bad, hipMemcpyAsync(cu.get(), excl_u + x0, sizeof(int32_t) * (size_t)c, hipMemcpyHostToDevice, h->stream));
+        HIPCHK_OR(bad, hipMemcpyAsync(ci.get(), excl_i + x0, sizeof(int32_t) * (size_t)c, hipMemcpyHostToDevice, h->stream));
+        HIPCHK_OR(bad, recommend_excl_filter(slot.as<const int32_t>(), cu.as<const int32_t>(), ci.as<const int32_t>(), c,
+                                             keys.as<unsigned long long>(), cnt, kept, h->stream));
     }
-    if (e == hipSuccess)
-        e = recommend_excl_lists(static_cast<unsigned long long*>(keys.p), static_cast<unsigned long long*>(keys_tmp.p), kept,
-                                 n_slots, reinterpret_cast<unsigned*>(cnt + 1), static_cast<long long*>(off.p),
-                                 static_cast<int32_t*>(items.p), temp, temp_bytes, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    cleanup();
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(h, e == hipErrorOutOfMemory ? MFSGD_ERR_OOM : MFSGD_ERR_HIP,
-                    std::string("recommend: exclusion lists: ") + hipGetErrorString(e));
-    }
-    ex.slot = static_cast<const int32_t*>(slot.p);
-    ex.off = static_cast<const long long*>(off.p);
-    ex.items = static_cast<const int32_t*>(items.p);
+    HIPCHK_OR(bad, recommend_excl_lists(keys.as<unsigned long long>(), keys_tmp.as<unsigned long long>(), kept, n_slots,
+                                        reinterpret_cast<unsigned*>(cnt + 1), off.as<long long>(), items.as<int32_t>(),
+                                        temp, h->stream));
+    HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
+    ex.slot = slot.as<const int32_t>();
+    ex.off = off.as<const long long>();
+    ex.items = items.as<const int32_t>();
     return MFSGD_OK;
 }
 
@@ -1144,69 +1093,45 @@ int recommend_core(mfsgd_handle* h, const float* host_rows, int32_t n_rows, cons
     int batch = (int)std::max<int64_t>(1, std::min<int64_t>(n_users, ((int64_t)64 << 20) / std::max(1, I)));
     if (fused) batch = n_users;
     batch = std::min(batch, 65535);
+    auto bad = [h](hipError_t e) { return serve_fail(h, "recommend: ", e); };
     DevBuf d_rows, d_users, s_in, s_out, id_in, id_out, d_off, o_s, o_i, ex_slot, ex_off, ex_items;
-    void* temp = nullptr;
-    size_t temp_bytes = 0;
-    auto cleanup = [&]() {
-        d_rows.release(); d_users.release(); s_in.release(); s_out.release(); id_in.release(); id_out.release(); d_off.release();
-        o_s.release(); o_i.release(); ex_slot.release(); ex_off.release(); ex_items.release();
-        if (temp) (void)hipFree(temp);
-    };
+    DevBuf temp;  // of the sorts: one for the exclusion lists and every batch, grown when one needs more
     if (host_rows) {
         const int k = h->cfg.k, kp = h->geo.kp;
         std::vector<float> padded((size_t)n_rows * kp, 0.0f);
         for (int64_t x = 0; x < n_rows; ++x) std::memcpy(&padded[(size_t)x * kp], host_rows + x * k, sizeof(float) * (size_t)k);
-        if ((rc = upload(h, d_rows, padded))) {
-            cleanup();
-            return rc;
-        }
+        if ((rc = upload(h, d_rows, padded))) return rc;
     }
-    const float* P = host_rows ? static_cast<const float*>(d_rows.p) : static_cast<const float*>(h->dP.p);
+    const float* P = host_rows ? d_rows.as<const float>() : h->dP.as<const float>();
+    const float* Q = h->dQ.as<const float>();
     RecommendExcl ex;  // built once for all batches; none when no pair belongs to a requested user
     if (kept > 0 && (rc = exclusions_to_device(h, slot_of_user, n_slots, excl_u, excl_i, n_excl, kept, ex_slot, ex_off,
-                                               ex_items, temp, temp_bytes, ex))) {
-        cleanup();
+                                               ex_items, temp, ex)))
         return rc;
-    }
     const size_t cells = (size_t)batch * (size_t)I;
-    rc = dev_alloc(h, d_users, sizeof(int32_t) * (size_t)batch);
+    if ((rc = dev_alloc(h, d_users, sizeof(int32_t) * (size_t)batch))) return rc;
     if (!fused) {
-        if (!rc) rc = dev_alloc(h, s_in, 4 * cells);
-        if (!rc) rc = dev_alloc(h, s_out, 4 * cells);
-        if (!rc) rc = dev_alloc(h, id_in, 4 * cells);
-        if (!rc) rc = dev_alloc(h, id_out, 4 * cells);
-        if (!rc) rc = dev_alloc(h, d_off, sizeof(long long) * ((size_t)batch + 1));
+        if ((rc = dev_alloc(h, s_in, 4 * cells))) return rc;
+        if ((rc = dev_alloc(h, s_out, 4 * cells))) return rc;
+        if ((rc = dev_alloc(h, id_in, 4 * cells))) return rc;
+        if ((rc = dev_alloc(h, id_out, 4 * cells))) return rc;
+        if ((rc = dev_alloc(h, d_off, sizeof(long long) * ((size_t)batch + 1)))) return rc;
     }
-    if (!rc) rc = dev_alloc(h, o_s, 4 * (size_t)batch * topn);
-    if (!rc) rc = dev_alloc(h, o_i, 4 * (size_t)batch * topn);
-    if (rc) {
-        cleanup();
-        return rc;
-    }
-    hipError_t e = hipSuccess;
-    for (int32_t done = 0; done < n_users && e == hipSuccess; done += batch) {
+    if ((rc = dev_alloc(h, o_s, 4 * (size_t)batch * topn))) return rc;
+    if ((rc = dev_alloc(h, o_i, 4 * (size_t)batch * topn))) return rc;
+    for (int32_t done = 0; done < n_users; done += batch) {
         const int nb = std::min<int32_t>(batch, n_users - done);
-        e = hipMemcpyAsync(d_users.p, users + done, sizeof(int32_t) * (size_t)nb, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess && fused)
-            e = recommend_fused(h->geo.L, P, static_cast<const float*>(h->dQ.p),
-                                static_cast<const int32_t*>(d_users.p), nb, I, topn, ex, static_cast<float*>(o_s.p),
-                                static_cast<int32_t*>(o_i.p), h->stream);
-        else if (e == hipSuccess)
-            e = recommend_batch(h->geo.L, P, static_cast<const float*>(h->dQ.p),
-                                static_cast<const int32_t*>(d_users.p), nb, I, topn, ex, static_cast<float*>(s_in.p),
-                                static_cast<float*>(s_out.p), static_cast<int32_t*>(id_in.p), static_cast<int32_t*>(id_out.p),
-                                static_cast<long long*>(d_off.p), temp, temp_bytes, static_cast<float*>(o_s.p),
-                                static_cast<int32_t*>(o_i.p), h->stream);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(out_scores + (size_t)done * topn, o_s.p, 4 * (size_t)nb * topn, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(out_items + (size_t)done * topn, o_i.p, 4 * (size_t)nb * topn, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    }
-    cleanup();
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(h, e == hipErrorOutOfMemory ? MFSGD_ERR_OOM : MFSGD_ERR_HIP, std::string("recommend: ") + hipGetErrorString(e));
+        const int32_t* du = d_users.as<const int32_t>();
+        HIPCHK_OR(bad, hipMemcpyAsync(d_users.get(), users + done, sizeof(int32_t) * (size_t)nb, hipMemcpyHostToDevice, h->stream));
+        if (fused)
+            HIPCHK_OR(bad, recommend_fused(h->geo.L, P, Q, du, nb, I, topn, ex, o_s.as<float>(), o_i.as<int32_t>(), h->stream));
+        else
+            HIPCHK_OR(bad, recommend_batch(h->geo.L, P, Q, du, nb, I, topn, ex, s_in.as<float>(), s_out.as<float>(),
+                                           id_in.as<int32_t>(), id_out.as<int32_t>(), d_off.as<long long>(), temp,
+                                           o_s.as<float>(), o_i.as<int32_t>(), h->stream));
+        HIPCHK_OR(bad, hipMemcpyAsync(out_scores + (size_t)done * topn, o_s.get(), 4 * (size_t)nb * topn, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK_OR(bad, hipMemcpyAsync(out_items + (size_t)done * topn, o_i.get(), 4 * (size_t)nb * topn, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
     }
     return MFSGD_OK;
 }
@@ -1272,30 +1197,23 @@ int mfsgd_fold_in_users(mfsgd_handle* h, int32_t n_new, const int64_t* row_ptr, 
         cut.push_back(u1);
         u0 = u1;
     }
+    auto bad = [h](hipError_t e) { return serve_fail(h, "fold_in: ", e); };
     DevBuf d_rows, d_ptr, d_perm, d_items, d_r;
-    auto cleanup = [&]() {
-        d_rows.release(); d_ptr.release(); d_perm.release(); d_items.release(); d_r.release();
-    };
     const size_t row_bytes = sizeof(float) * (size_t)n_new * (size_t)k;
-    rc = dev_alloc(h, d_rows, row_bytes);
+    if ((rc = dev_alloc(h, d_rows, row_bytes))) return rc;
     if (epochs > 0 && total > 0) {
-        if (!rc) rc = dev_alloc(h, d_ptr, sizeof(int64_t) * ((size_t)max_users + 1));
-        if (!rc) rc = dev_alloc(h, d_perm, sizeof(int32_t) * (size_t)max_users);
-        if (!rc) rc = dev_alloc(h, d_items, sizeof(int32_t) * (size_t)max_ratings);
-        if (!rc) rc = dev_alloc(h, d_r, sizeof(float) * (size_t)max_ratings);
-    }
-    if (rc) {
-        cleanup();
-        return rc;
+        if ((rc = dev_alloc(h, d_ptr, sizeof(int64_t) * ((size_t)max_users + 1)))) return rc;
+        if ((rc = dev_alloc(h, d_perm, sizeof(int32_t) * (size_t)max_users))) return rc;
+        if ((rc = dev_alloc(h, d_items, sizeof(int32_t) * (size_t)max_ratings))) return rc;
+        if ((rc = dev_alloc(h, d_r, sizeof(float) * (size_t)max_ratings))) return rc;
     }
     // the start rows, dense: the kernel pads them to kp in its registers
-    hipError_t e;
     if (init_rows)
-        e = hipMemcpyAsync(d_rows.p, init_rows, row_bytes, hipMemcpyHostToDevice, h->stream);
+        HIPCHK_OR(bad, hipMemcpyAsync(d_rows.get(), init_rows, row_bytes, hipMemcpyHostToDevice, h->stream));
     else
-        e = launch_init_rows(static_cast<float*>(d_rows.p), n_new, k, k, seed, 0, (float)(1.0 / std::sqrt((double)k)), h->stream);
+        HIPCHK_OR(bad, launch_init_rows(d_rows.as<float>(), n_new, k, k, seed, 0, (float)(1.0 / std::sqrt((double)k)), h->stream));
     std::vector<int32_t> perm;
-    for (size_t b = 0; b + 1 < cut.size() && e == hipSuccess && epochs > 0; ++b) {
+    for (size_t b = 0; b + 1 < cut.size() && epochs > 0; ++b) {
         const int32_t u0 = cut[b], nb = cut[b + 1] - cut[b];
         const int64_t base = row_ptr[u0], nr = row_ptr[u0 + nb] - base;
         if (nr == 0) continue;
@@ -1304,24 +1222,18 @@ int mfsgd_fold_in_users(mfsgd_handle* h, int32_t n_new, const int64_t* row_ptr, 
         for (int32_t x = 0; x < nb; ++x) perm[(size_t)x] = x;
         const int64_t* rp = row_ptr + u0;
         std::stable_sort(perm.begin(), perm.end(), [rp](int32_t a, int32_t b2) { return rp[a + 1] - rp[a] > rp[b2 + 1] - rp[b2]; });
-        e = hipMemcpyAsync(d_ptr.p, rp, sizeof(int64_t) * ((size_t)nb + 1), hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_perm.p, perm.data(), sizeof(int32_t) * (size_t)nb, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_items.p, items + base, sizeof(int32_t) * (size_t)nr, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_r.p, ratings + base, sizeof(float) * (size_t)nr, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess)
-            e = launch_fold_in(h->geo.L, static_cast<const float*>(h->dQ.p), static_cast<float*>(d_rows.p) + (size_t)u0 * k, k,
-                               static_cast<const long long*>(d_ptr.p), base, static_cast<const int32_t*>(d_perm.p), nb,
-                               static_cast<const int32_t*>(d_items.p), static_cast<const float*>(d_r.p), epochs, h->cfg.lr,
-                               1.0f - h->cfg.lr * h->cfg.lambda, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // perm and the staging buffers are reused
+        HIPCHK_OR(bad, hipMemcpyAsync(d_ptr.get(), rp, sizeof(int64_t) * ((size_t)nb + 1), hipMemcpyHostToDevice, h->stream));
+        HIPCHK_OR(bad, hipMemcpyAsync(d_perm.get(), perm.data(), sizeof(int32_t) * (size_t)nb, hipMemcpyHostToDevice, h->stream));
+        HIPCHK_OR(bad, hipMemcpyAsync(d_items.get(), items + base, sizeof(int32_t) * (size_t)nr, hipMemcpyHostToDevice, h->stream));
+        HIPCHK_OR(bad, hipMemcpyAsync(d_r.get(), ratings + base, sizeof(float) * (size_t)nr, hipMemcpyHostToDevice, h->stream));
+        HIPCHK_OR(bad, launch_fold_in(h->geo.L, h->dQ.as<const float>(), d_rows.as<float>() + (size_t)u0 * k, k,
+                                      d_ptr.as<const long long>(), base, d_perm.as<const int32_t>(), nb,
+                                      d_items.as<const int32_t>(), d_r.as<const float>(), epochs, h->cfg.lr,
+                                      1.0f - h->cfg.lr * h->cfg.lambda, h->stream));
+        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // perm and the staging buffers are reused
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(out_rows, d_rows.p, row_bytes, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    cleanup();
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(h, e == hipErrorOutOfMemory ? MFSGD_ERR_OOM : MFSGD_ERR_HIP, std::string("fold_in: ") + hipGetErrorString(e));
-    }
+    HIPCHK_OR(bad, hipMemcpyAsync(out_rows, d_rows.get(), row_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
     return MFSGD_OK;
 }
 
@@ -1416,13 +1328,13 @@ int mfsgd_debug_epoch_profile(mfsgd_handle* h, uint64_t* out, int32_t* n_workgro
     if (p.persistent_np <= 0) return fail(h, MFSGD_ERR_STATE, "debug_epoch_profile: persistent kernel not in use");
     const size_t words = (size_t)p.persistent_np * 16;
     if ((rc = dev_alloc(h, p.d_sse_partial, std::max(words * sizeof(uint64_t), sizeof(double) * p.sched.cells.size())))) return rc;
-    CellLaunch a = make_launch(h, p, static_cast<float*>(h->dQ.p));
+    CellLaunch a = make_launch(h, p, h->dQ.as<float>());
     a.grid = p.persistent_np;
     a.diag = true;
-    a.sse_partial = static_cast<double*>(p.d_sse_partial.p);
-    HIPCHK(h, hipMemsetAsync(p.d_sse_partial.p, 0, words * sizeof(uint64_t), h->stream));
-    HIPCHK(h, launch_epoch_persistent(h->geo.L, p.sched.W, a, p.sched.B, static_cast<unsigned*>(p.d_sync.p), abort_word(p), h->stream));
-    HIPCHK(h, hipMemcpyAsync(out, p.d_sse_partial.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    a.sse_partial = p.d_sse_partial.as<double>();
+    HIPCHK(h, hipMemsetAsync(p.d_sse_partial.get(), 0, words * sizeof(uint64_t), h->stream));
+    HIPCHK(h, launch_epoch_persistent(h->geo.L, p.sched.W, a, p.sched.B, p.d_sync.as<unsigned>(), abort_word(p), h->stream));
+    HIPCHK(h, hipMemcpyAsync(out, p.d_sse_partial.get(), words * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     *n_workgroups = p.persistent_np;
     return check_abort_strict(h, p);
@@ -1437,6 +1349,12 @@ int mfsgd_debug_counters(const mfsgd_handle* h, int64_t* out4) {
         out4[1] += p.persistent_np > 0 ? 1 : 0;  // partitions trained by the persistent kernel
         out4[2] += (int64_t)p.graphs.size();
     }
+    return MFSGD_OK;
+}
+
+int mfsgd_debug_device_bytes(int64_t* live) {
+    if (!live) return MFSGD_ERR_INVALID_ARG;
+    *live = g_dev_live_bytes.load();
     return MFSGD_OK;
 }
 
@@ -1471,18 +1389,17 @@ int mfsgd_debug_round_stamps(mfsgd_handle* h, int32_t part, int32_t round, uint6
     Part& p = h->parts[0];
     if (round < 0 || round >= p.sched.B) return fail(h, MFSGD_ERR_INVALID_ARG, "debug_round_stamps: bad round");
     const size_t words = (size_t)p.sched.B * (6 + (size_t)p.sched.W * p.sched.W * 4);
-    if (words * sizeof(uint64_t) > p.d_sse_partial.bytes) {
+    if (words * sizeof(uint64_t) > p.d_sse_partial.bytes()) {
         int rc2 = dev_alloc(h, p.d_sse_partial, words * sizeof(uint64_t));
         if (rc2) return rc2;
     }
-    CellLaunch a = make_launch(h, p, static_cast<float*>(h->dQ.p));
+    CellLaunch a = make_launch(h, p, h->dQ.as<float>());
     a.rd = round;
     a.diag = true;
-    
-    HIPCHK(h, hipMemsetAsync(p.d_sse_partial.p, 0, words * sizeof(uint64_t), h->stream));
-    a.sse_partial = static_cast<double*>(p.d_sse_partial.p);
+    HIPCHK(h, hipMemsetAsync(p.d_sse_partial.get(), 0, words * sizeof(uint64_t), h->stream));
+    a.sse_partial = p.d_sse_partial.as<double>();
     HIPCHK(h, launch_cell(true, h->geo.L, p.sched.W, a, h->stream));
-    HIPCHK(h, hipMemcpyAsync(out, p.d_sse_partial.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(out, p.d_sse_partial.get(), words * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MFSGD_OK;
 }

@@ -1,0 +1,81 @@
+// devmem.hpp -- the owner of device memory: every hipMalloc of the library lives in a DevBuf, which frees it.
+// Host-compilable (capi.cpp, dsgd.cpp): the runtime API only.
+#pragma once
+
+#include <hip/hip_runtime_api.h>
+
+#include <atomic>
+#include <cstddef>
+#include <cstdint>
+
+namespace mfsgd {
+
+// Bytes held by the DevBufs of this process (mfsgd_debug_device_bytes): what a test compares before and after a
+// call to see that nothing was kept -- free-memory readings of a shared GPU cannot tell.
+inline std::atomic<int64_t> g_dev_live_bytes{0};
+
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_), bytes_(o.bytes_) { o.forget(); }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p_ = o.p_;
+            bytes_ = o.bytes_;
+            o.forget();
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+
+    void* get() const { return p_; }
+    size_t bytes() const { return bytes_; }
+    explicit operator bool() const { return p_ != nullptr; }
+    template <class T>
+    T* as() const {
+        return static_cast<T*>(p_);
+    }
+
+    // At least `bytes` bytes (16 for 0): a buffer that is already that large is kept, contents and all; a smaller one
+    // is freed first.
+    hipError_t alloc(size_t bytes) {
+        if (p_ && bytes_ >= bytes) return hipSuccess;
+        reset();
+        if (bytes == 0) bytes = 16;
+        void* p = nullptr;
+        const hipError_t e = hipMalloc(&p, bytes);
+        if (e == hipSuccess) adopt(p, bytes);
+        return e;
+    }
+    // Takes over a pointer that came from hipMalloc (null: ends up empty).
+    void adopt(void* p, size_t bytes) {
+        reset();
+        if (!p) return;
+        p_ = p;
+        bytes_ = bytes;
+        g_dev_live_bytes.fetch_add((int64_t)bytes, std::memory_order_relaxed);
+    }
+    // Gives the pointer up: the caller frees it (hipFree).
+    void* detach() {
+        void* p = p_;
+        g_dev_live_bytes.fetch_sub((int64_t)bytes_, std::memory_order_relaxed);
+        forget();
+        return p;
+    }
+    void reset() {
+        if (p_) (void)hipFree(detach());
+    }
+
+private:
+    void forget() {
+        p_ = nullptr;
+        bytes_ = 0;
+    }
+    void* p_ = nullptr;
+    size_t bytes_ = 0;
+};
+
+}  // namespace mfsgd

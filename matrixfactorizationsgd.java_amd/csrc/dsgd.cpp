@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "../../include/mfsgd.h"
+#include "devmem.hpp"
 
 namespace {
 
@@ -148,11 +149,11 @@ struct mfsgd_dsgd {
     ncclComm_t comm = nullptr;
     ShmRing* shm = nullptr;  // the rehearsal transport instead of RCCL (MFSGD_DSGD_TRANSPORT=shm)
     hipStream_t compute = nullptr, wire = nullptr;
-    float* buf[2] = {nullptr, nullptr};  // [cur, nxt]: m blocks of max_rows x kp floats each
+    mfsgd::DevBuf buf[2];  // [cur, nxt]: m blocks of max_rows x kp floats each
     int cur = 0;
     int group = 0;  // group currently held: partitions group * m .. group * m + m - 1
     std::vector<hipEvent_t> trained, arrived;  // per slot j
-    double* d_red = nullptr;                   // 2 doubles for the RMSE all-reduce
+    mfsgd::DevBuf d_red;                       // 2 doubles for the RMSE all-reduce
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // counters (mfsgd_dsgd_stats): sub-epoch trainings enqueued, of those with the recovery point, of those re-run
     // as round launches, bytes sent
@@ -160,7 +161,7 @@ struct mfsgd_dsgd {
     bool always_check = false;  // MFSGD_DSGD_CHECK=1: the recovery point in every sub-epoch
     std::string err;
 
-    float* block(int which, int j) const { return buf[which] + (size_t)j * max_rows * kp; }
+    float* block(int which, int j) const { return buf[which].as<float>() + (size_t)j * max_rows * kp; }
     int part(int j) const { return group * m + j; }
 };
 
@@ -329,9 +330,10 @@ int allreduce2(mfsgd_dsgd* d, double* v, ncclRedOp_t op) {
         return MFSGD_OK;
     }
 #endif  // MFSGD_DSGD_REHEARSAL
-    DHIP(d, hipMemcpyAsync(d->d_red, v, 2 * sizeof(double), hipMemcpyHostToDevice, d->wire));
-    DNCCL(d, rccl().AllReduce(d->d_red, d->d_red, 2, ncclDouble, op, d->comm, d->wire));
-    DHIP(d, hipMemcpyAsync(v, d->d_red, 2 * sizeof(double), hipMemcpyDeviceToHost, d->wire));
+    double* red = d->d_red.as<double>();
+    DHIP(d, hipMemcpyAsync(red, v, 2 * sizeof(double), hipMemcpyHostToDevice, d->wire));
+    DNCCL(d, rccl().AllReduce(red, red, 2, ncclDouble, op, d->comm, d->wire));
+    DHIP(d, hipMemcpyAsync(v, red, 2 * sizeof(double), hipMemcpyDeviceToHost, d->wire));
     DHIP(d, hipStreamSynchronize(d->wire));
     return MFSGD_OK;
 }
@@ -432,10 +434,10 @@ int mfsgd_dsgd_create(mfsgd_handle* h, int32_t rank, int32_t world, const void* 
         return bail(MFSGD_ERR_HIP);
     const size_t bytes = (size_t)d->m * d->max_rows * kp * sizeof(float);
     for (int b = 0; b < 2; ++b) {
-        if (hip(hipMalloc(reinterpret_cast<void**>(&d->buf[b]), bytes), "hipMalloc(Q blocks)")) return bail(MFSGD_ERR_OOM);
-        if (hip(hipMemset(d->buf[b], 0, bytes), "hipMemset")) return bail(MFSGD_ERR_HIP);
+        if (hip(d->buf[b].alloc(bytes), "hipMalloc(Q blocks)")) return bail(MFSGD_ERR_OOM);
+        if (hip(hipMemset(d->buf[b].get(), 0, bytes), "hipMemset")) return bail(MFSGD_ERR_HIP);
     }
-    if (hip(hipMalloc(reinterpret_cast<void**>(&d->d_red), 2 * sizeof(double)), "hipMalloc")) return bail(MFSGD_ERR_OOM);
+    if (hip(d->d_red.alloc(2 * sizeof(double)), "hipMalloc")) return bail(MFSGD_ERR_OOM);
     d->trained.assign((size_t)d->m, nullptr);
     d->arrived.assign((size_t)d->m, nullptr);
     for (int j = 0; j < d->m; ++j)
@@ -514,12 +516,9 @@ void mfsgd_dsgd_destroy(mfsgd_dsgd* d) {
         if (e) (void)hipEventDestroy(e);
     if (d->ev0) (void)hipEventDestroy(d->ev0);
     if (d->ev1) (void)hipEventDestroy(d->ev1);
-    for (int b = 0; b < 2; ++b)
-        if (d->buf[b]) (void)hipFree(d->buf[b]);
-    if (d->d_red) (void)hipFree(d->d_red);
     if (d->compute) (void)hipStreamDestroy(d->compute);
     if (d->wire) (void)hipStreamDestroy(d->wire);
-    delete d;
+    delete d;  // (the Q blocks and the reduction words go with it)
 }
 
 int mfsgd_dsgd_init_q(mfsgd_dsgd* d, int64_t seed, int64_t u_total) {

@@ -5,8 +5,10 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <utility>
 #include <vector>
 
+#include "devmem.hpp"
 #include "ingest.hpp"
 #include "hugepages.hpp"
 #include "pack.hpp"
@@ -14,6 +16,29 @@
 namespace mfsgd {
 
 namespace {
+
+// What bucket_dev() and the COUNT pass leave on the device for the packer's later calls.  Dropping it is assigning an
+// empty one: every buffer is freed by its owner.
+struct PackState {
+    DevBuf sorted;                   // unsigned x n: rating indices in bucket order
+    DevBuf bptr;                     // long long x (nb + 1)
+    int64_t nb = 0;
+    DevBuf r;                        // float x n
+    DevBuf orig;                     // long long x n, or empty
+    DevBuf urank, irank;             // int32 per row
+    DevBuf info;                     // PackCellInfo per cell
+    DevBuf subs;                     // SubDesc x W*W per cell
+    PackArgs args{};                 // as launched for COUNT; EMIT reuses it
+    int64_t n_cells = 0;
+    int rows_full = 0;               // the row capacity no cell (or part of one) can exceed
+    // one-pass mode: what the COUNT pass already wrote
+    struct OnePass {
+        DevBuf srows;                // uint32: scratch rows (2 per rating)
+        DevBuf sent;                 // Entry: scratch entries (worst-case strides)
+        DevBuf order;                // long long x n: the canonical order, final
+        DevBuf ord_off;              // long long per cell
+    } one;
+};
 
 struct Ctx {
     int device = 0;
@@ -24,57 +49,25 @@ struct Ctx {
     const int32_t* host_u = nullptr;
     const int32_t* host_i = nullptr;
     int64_t n = 0;
-    int32_t *du = nullptr, *di = nullptr;
-    // kept after bucket_dev() for the device packer
-    unsigned* d_sorted = nullptr;    // rating indices in bucket order
-    long long* d_bptr = nullptr;     // nb + 1
-    int64_t nb = 0;
-    float* d_r = nullptr;
-    long long* d_orig = nullptr;
-    int32_t *d_urank = nullptr, *d_irank = nullptr;
-    PackCellInfo* d_info = nullptr;
-    SubDesc* d_subs = nullptr;
-    PackArgs args{};                 // as launched for COUNT; EMIT reuses it
-    int64_t n_cells = 0;
-    int rows_full = 0;               // the row capacity no cell (or part of one) can exceed
-    // one-pass mode: what the COUNT pass already wrote
-    uint32_t* d_srows = nullptr;     // scratch rows (2 per rating)
-    Entry* d_sent = nullptr;         // scratch entries (worst-case strides)
-    long long* d_order = nullptr;    // the canonical order, final
-    long long* d_ord_off = nullptr;
+    DevBuf du, di;                   // int32 x n each
+    PackState pk;
 };
 
-#define ING_CHK(call)                      \
-    do {                                   \
-        if ((call) != hipSuccess) {        \
-            (void)hipGetLastError();       \
-            goto fail;                     \
-        }                                  \
+// A HIP call failed: the callback answers -1 (the host loops take over); what it allocated goes with its owners.
+#define ING_CHK(call)                 \
+    do {                              \
+        if ((call) != hipSuccess) {   \
+            (void)hipGetLastError();  \
+            return -1;                \
+        }                             \
     } while (0)
 
-void drop_pack_state(Ctx* c) {
-    void* ptrs[] = {c->d_sorted, c->d_bptr, c->d_r, c->d_orig, c->d_urank, c->d_irank, c->d_info, c->d_subs,
-                    c->d_srows, c->d_sent, c->d_order, c->d_ord_off};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    c->d_srows = nullptr;
-    c->d_sent = nullptr;
-    c->d_order = nullptr;
-    c->d_ord_off = nullptr;
-    c->d_sorted = nullptr;
-    c->d_bptr = nullptr;
-    c->d_r = nullptr;
-    c->d_orig = nullptr;
-    c->d_urank = c->d_irank = nullptr;
-    c->d_info = nullptr;
-    c->d_subs = nullptr;
-}
+void drop_pack_state(Ctx* c) { c->pk = PackState{}; }
 
 void drop_triples(Ctx* c) {
     drop_pack_state(c);
-    if (c->du) (void)hipFree(c->du);
-    if (c->di) (void)hipFree(c->di);
-    c->du = c->di = nullptr;
+    c->du.reset();
+    c->di.reset();
     c->host_u = c->host_i = nullptr;
     c->n = 0;
 }
@@ -84,9 +77,9 @@ bool ensure_triples(Ctx* c, const int32_t* u, const int32_t* i, int64_t n) {
     drop_triples(c);
     if (hipSetDevice(c->device) != hipSuccess) return false;
     const size_t bytes = (size_t)(n > 0 ? n : 1) * sizeof(int32_t);
-    if (hipMalloc(&c->du, bytes) != hipSuccess || hipMalloc(&c->di, bytes) != hipSuccess ||
-        hipMemcpy(c->du, u, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(c->di, i, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+    if (c->du.alloc(bytes) != hipSuccess || c->di.alloc(bytes) != hipSuccess ||
+        hipMemcpy(c->du.get(), u, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(c->di.get(), i, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipGetLastError();
         drop_triples(c);
         return false;
@@ -164,90 +157,76 @@ int degrees_cb(void* vctx, const int32_t* u, const int32_t* i, int64_t n, int32_
     Ctx* c = static_cast<Ctx*>(vctx);
     if (n >= (int64_t)1 << 32) return -1;
     if (!ensure_triples(c, u, i, n)) return -1;
-    unsigned *d_u = nullptr, *d_i = nullptr;
     std::vector<unsigned> hu((size_t)U), hi((size_t)I);
-    ING_CHK(hipMalloc(&d_u, sizeof(unsigned) * (size_t)U));
-    ING_CHK(hipMalloc(&d_i, sizeof(unsigned) * (size_t)I));
-    ING_CHK(hipMemset(d_u, 0, sizeof(unsigned) * (size_t)U));
-    ING_CHK(hipMemset(d_i, 0, sizeof(unsigned) * (size_t)I));
-    if (std::min(U, I) <= kDegLdsRows && n >= (1 << 20)) {
-        const bool items_small = I <= U;
-        const int n_small = items_small ? I : U;
-        const size_t lds = 4 * (size_t)n_small;
-        ING_CHK(hipFuncSetAttribute((const void*)degree_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(degree_lds_kernel, dim3(256), dim3(1024), lds, 0, items_small ? c->du : c->di, items_small ? c->di : c->du, n,
-                           items_small ? d_u : d_i, items_small ? d_i : d_u, n_small);
-    } else {
-        hipLaunchKernelGGL(degree_kernel, dim3(grid_for(n)), dim3(256), 0, 0, c->du, c->di, n, d_u, d_i);
+    {
+        DevBuf bu, bi;
+        ING_CHK(bu.alloc(sizeof(unsigned) * (size_t)U));
+        ING_CHK(bi.alloc(sizeof(unsigned) * (size_t)I));
+        unsigned *d_u = bu.as<unsigned>(), *d_i = bi.as<unsigned>();
+        const int32_t *du = c->du.as<int32_t>(), *di = c->di.as<int32_t>();
+        ING_CHK(hipMemset(d_u, 0, sizeof(unsigned) * (size_t)U));
+        ING_CHK(hipMemset(d_i, 0, sizeof(unsigned) * (size_t)I));
+        if (std::min(U, I) <= kDegLdsRows && n >= (1 << 20)) {
+            const bool items_small = I <= U;
+            const int n_small = items_small ? I : U;
+            const size_t lds = 4 * (size_t)n_small;
+            ING_CHK(hipFuncSetAttribute((const void*)degree_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(degree_lds_kernel, dim3(256), dim3(1024), lds, 0, items_small ? du : di, items_small ? di : du, n,
+                               items_small ? d_u : d_i, items_small ? d_i : d_u, n_small);
+        } else {
+            hipLaunchKernelGGL(degree_kernel, dim3(grid_for(n)), dim3(256), 0, 0, du, di, n, d_u, d_i);
+        }
+        ING_CHK(hipGetLastError());
+        ING_CHK(hipMemcpy(hu.data(), d_u, sizeof(unsigned) * (size_t)U, hipMemcpyDeviceToHost));
+        ING_CHK(hipMemcpy(hi.data(), d_i, sizeof(unsigned) * (size_t)I, hipMemcpyDeviceToHost));
     }
-    ING_CHK(hipGetLastError());
-    ING_CHK(hipMemcpy(hu.data(), d_u, sizeof(unsigned) * (size_t)U, hipMemcpyDeviceToHost));
-    ING_CHK(hipMemcpy(hi.data(), d_i, sizeof(unsigned) * (size_t)I, hipMemcpyDeviceToHost));
-    (void)hipFree(d_u);
-    (void)hipFree(d_i);
     for (int32_t x = 0; x < U; ++x) degu[x] = hu[(size_t)x];
     for (int32_t x = 0; x < I; ++x) degi[x] = hi[(size_t)x];
     return 0;
-fail:
-    if (d_u) (void)hipFree(d_u);
-    if (d_i) (void)hipFree(d_i);
-    return -1;
 }
 
 // Keys, one stable LSD radix sort of (key, index) pairs, bucket starts.  Leaves the sorted indices and
-// the bucket starts on the device (c->d_sorted, c->d_bptr).
+// the bucket starts on the device (c->pk.sorted, c->pk.bptr).
 int bucket_on_device(Ctx* c, const int32_t* u, const int32_t* i, int64_t n, const int32_t* ubin, const int32_t* ibin,
                      int32_t U, int32_t I, int B, int W, int giants) {
     const int64_t nb = (int64_t)B * B * W * W;
     if (n >= (int64_t)1 << 32 || nb >= (int64_t)1 << 32) return -1;
     if (!ensure_triples(c, u, i, n)) return -1;
     drop_pack_state(c);
-    int32_t *d_ubin = nullptr, *d_ibin = nullptr;
-    unsigned *k0 = nullptr, *k1 = nullptr, *v0 = nullptr, *v1 = nullptr;
-    long long* d_bptr = nullptr;
-    void* temp = nullptr;
+    DevBuf d_ubin, d_ibin, k0, k1, v0, v1, d_bptr, temp;  // all but v1 and d_bptr go when this returns
     size_t temp_bytes = 0;
     const size_t nn = (size_t)(n > 0 ? n : 1);
     unsigned bits = 1;
     while (((int64_t)1 << bits) < nb) ++bits;
-    ING_CHK(hipMalloc(&d_ubin, sizeof(int32_t) * (size_t)U));
-    ING_CHK(hipMalloc(&d_ibin, sizeof(int32_t) * (size_t)I));
-    ING_CHK(hipMemcpy(d_ubin, ubin, sizeof(int32_t) * (size_t)U, hipMemcpyHostToDevice));
-    ING_CHK(hipMemcpy(d_ibin, ibin, sizeof(int32_t) * (size_t)I, hipMemcpyHostToDevice));
-    ING_CHK(hipMalloc(&k0, 4 * nn));
-    ING_CHK(hipMalloc(&k1, 4 * nn));
-    ING_CHK(hipMalloc(&v0, 4 * nn));
-    ING_CHK(hipMalloc(&v1, 4 * nn));
-    ING_CHK(hipMalloc(&d_bptr, sizeof(long long) * (size_t)(nb + 1)));
-    hipLaunchKernelGGL(key_kernel, dim3(grid_for(n)), dim3(256), 0, 0, c->du, c->di, n, d_ubin, d_ibin, B, W, giants, k0, v0);
+    ING_CHK(d_ubin.alloc(sizeof(int32_t) * (size_t)U));
+    ING_CHK(d_ibin.alloc(sizeof(int32_t) * (size_t)I));
+    ING_CHK(hipMemcpy(d_ubin.get(), ubin, sizeof(int32_t) * (size_t)U, hipMemcpyHostToDevice));
+    ING_CHK(hipMemcpy(d_ibin.get(), ibin, sizeof(int32_t) * (size_t)I, hipMemcpyHostToDevice));
+    ING_CHK(k0.alloc(4 * nn));
+    ING_CHK(k1.alloc(4 * nn));
+    ING_CHK(v0.alloc(4 * nn));
+    ING_CHK(v1.alloc(4 * nn));
+    ING_CHK(d_bptr.alloc(sizeof(long long) * (size_t)(nb + 1)));
+    unsigned *key_in = k0.as<unsigned>(), *key_out = k1.as<unsigned>(), *val_in = v0.as<unsigned>(), *val_out = v1.as<unsigned>();
+    hipLaunchKernelGGL(key_kernel, dim3(grid_for(n)), dim3(256), 0, 0, c->du.as<int32_t>(), c->di.as<int32_t>(), n,
+                       d_ubin.as<int32_t>(), d_ibin.as<int32_t>(), B, W, giants, key_in, val_in);
     ING_CHK(hipGetLastError());
     // LSD radix sort: stable, so equal keys keep their input order -- the host counting sort's order
-    ING_CHK(rocprim::radix_sort_pairs(nullptr, temp_bytes, k0, k1, v0, v1, (size_t)n, 0u, bits, (hipStream_t)0));
-    ING_CHK(hipMalloc(&temp, temp_bytes ? temp_bytes : 16));
-    ING_CHK(rocprim::radix_sort_pairs(temp, temp_bytes, k0, k1, v0, v1, (size_t)n, 0u, bits, (hipStream_t)0));
-    hipLaunchKernelGGL(bound_kernel, dim3(grid_for(nb + 1)), dim3(256), 0, 0, k1, n, nb, d_bptr);
+    ING_CHK(rocprim::radix_sort_pairs(nullptr, temp_bytes, key_in, key_out, val_in, val_out, (size_t)n, 0u, bits, (hipStream_t)0));
+    ING_CHK(temp.alloc(temp_bytes));
+    ING_CHK(rocprim::radix_sort_pairs(temp.get(), temp_bytes, key_in, key_out, val_in, val_out, (size_t)n, 0u, bits, (hipStream_t)0));
+    hipLaunchKernelGGL(bound_kernel, dim3(grid_for(nb + 1)), dim3(256), 0, 0, key_out, n, nb, d_bptr.as<long long>());
     ING_CHK(hipGetLastError());
     ING_CHK(hipDeviceSynchronize());
-    (void)hipFree(d_ubin); (void)hipFree(d_ibin); (void)hipFree(k0); (void)hipFree(k1); (void)hipFree(v0); (void)hipFree(temp);
-    c->d_sorted = v1;
-    c->d_bptr = d_bptr;
-    c->nb = nb;
+    c->pk.sorted = std::move(v1);
+    c->pk.bptr = std::move(d_bptr);
+    c->pk.nb = nb;
     return 0;
-fail:
-    if (d_ubin) (void)hipFree(d_ubin);
-    if (d_ibin) (void)hipFree(d_ibin);
-    if (k0) (void)hipFree(k0);
-    if (k1) (void)hipFree(k1);
-    if (v0) (void)hipFree(v0);
-    if (v1) (void)hipFree(v1);
-    if (d_bptr) (void)hipFree(d_bptr);
-    if (temp) (void)hipFree(temp);
-    return -1;
 }
 
 int fetch_bptr(Ctx* c, int64_t* bptr) {
     static_assert(sizeof(long long) == sizeof(int64_t), "the bucket starts come down as they are");
-    if (hipMemcpy(bptr, c->d_bptr, sizeof(long long) * (size_t)(c->nb + 1), hipMemcpyDeviceToHost) != hipSuccess) {
+    if (hipMemcpy(bptr, c->pk.bptr.get(), sizeof(long long) * (size_t)(c->pk.nb + 1), hipMemcpyDeviceToHost) != hipSuccess) {
         (void)hipGetLastError();
         return -1;
     }
@@ -256,9 +235,9 @@ int fetch_bptr(Ctx* c, int64_t* bptr) {
 
 int fetch_sorted_cb(void* vctx, int64_t* sorted) {
     Ctx* c = static_cast<Ctx*>(vctx);
-    if (!c->d_sorted) return -1;
+    if (!c->pk.sorted) return -1;
     std::vector<unsigned> hv((size_t)(c->n > 0 ? c->n : 1));
-    if (hipMemcpy(hv.data(), c->d_sorted, 4 * (size_t)c->n, hipMemcpyDeviceToHost) != hipSuccess) {
+    if (hipMemcpy(hv.data(), c->pk.sorted.get(), 4 * (size_t)c->n, hipMemcpyDeviceToHost) != hipSuccess) {
         (void)hipGetLastError();
         return -1;
     }
@@ -268,8 +247,8 @@ int fetch_sorted_cb(void* vctx, int64_t* sorted) {
 
 int fetch_sorted32_cb(void* vctx, uint32_t* sorted) {
     Ctx* c = static_cast<Ctx*>(vctx);
-    if (!c->d_sorted) return -1;
-    if (c->n > 0 && hipMemcpy(sorted, c->d_sorted, 4 * (size_t)c->n, hipMemcpyDeviceToHost) != hipSuccess) {
+    if (!c->pk.sorted) return -1;
+    if (c->n > 0 && hipMemcpy(sorted, c->pk.sorted.get(), 4 * (size_t)c->n, hipMemcpyDeviceToHost) != hipSuccess) {
         (void)hipGetLastError();
         return -1;
     }
@@ -286,7 +265,7 @@ __global__ void __launch_bounds__(256) gather_ranges_kernel(const unsigned* __re
 
 int fetch_sorted_ranges_cb(void* vctx, int64_t n_ranges, const int64_t* lo, const int64_t* len, uint32_t* out) {
     Ctx* c = static_cast<Ctx*>(vctx);
-    if (!c->d_sorted || n_ranges < 0) return -1;
+    if (!c->pk.sorted || n_ranges < 0) return -1;
     if (n_ranges == 0) return 0;
     std::vector<long long> dst((size_t)n_ranges);
     long long total = 0;
@@ -296,27 +275,20 @@ int fetch_sorted_ranges_cb(void* vctx, int64_t n_ranges, const int64_t* lo, cons
         total += len[x];
     }
     if (total == 0) return 0;
-    long long *d_lo = nullptr, *d_len = nullptr, *d_dst = nullptr;
-    unsigned* d_out = nullptr;
-    int rc = -1;
+    DevBuf d_lo, d_len, d_dst, d_out;
     static_assert(sizeof(long long) == sizeof(int64_t), "ranges are uploaded as they are");
-    ING_CHK(hipMalloc(&d_lo, 8 * (size_t)n_ranges));
-    ING_CHK(hipMalloc(&d_len, 8 * (size_t)n_ranges));
-    ING_CHK(hipMalloc(&d_dst, 8 * (size_t)n_ranges));
-    ING_CHK(hipMalloc(&d_out, 4 * (size_t)total));
-    ING_CHK(hipMemcpy(d_lo, lo, 8 * (size_t)n_ranges, hipMemcpyHostToDevice));
-    ING_CHK(hipMemcpy(d_len, len, 8 * (size_t)n_ranges, hipMemcpyHostToDevice));
-    ING_CHK(hipMemcpy(d_dst, dst.data(), 8 * (size_t)n_ranges, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(gather_ranges_kernel, dim3((unsigned)n_ranges), dim3(256), 0, 0, c->d_sorted, d_lo, d_len, d_dst, d_out);
+    ING_CHK(d_lo.alloc(8 * (size_t)n_ranges));
+    ING_CHK(d_len.alloc(8 * (size_t)n_ranges));
+    ING_CHK(d_dst.alloc(8 * (size_t)n_ranges));
+    ING_CHK(d_out.alloc(4 * (size_t)total));
+    ING_CHK(hipMemcpy(d_lo.get(), lo, 8 * (size_t)n_ranges, hipMemcpyHostToDevice));
+    ING_CHK(hipMemcpy(d_len.get(), len, 8 * (size_t)n_ranges, hipMemcpyHostToDevice));
+    ING_CHK(hipMemcpy(d_dst.get(), dst.data(), 8 * (size_t)n_ranges, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(gather_ranges_kernel, dim3((unsigned)n_ranges), dim3(256), 0, 0, c->pk.sorted.as<unsigned>(),
+                       d_lo.as<long long>(), d_len.as<long long>(), d_dst.as<long long>(), d_out.as<unsigned>());
     ING_CHK(hipGetLastError());
-    ING_CHK(hipMemcpy(out, d_out, 4 * (size_t)total, hipMemcpyDeviceToHost));
-    rc = 0;
-fail:
-    if (d_lo) (void)hipFree(d_lo);
-    if (d_len) (void)hipFree(d_len);
-    if (d_dst) (void)hipFree(d_dst);
-    if (d_out) (void)hipFree(d_out);
-    return rc;
+    ING_CHK(hipMemcpy(out, d_out.get(), 4 * (size_t)total, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int bucket_dev_cb(void* vctx, const int32_t* u, const int32_t* i, int64_t n, const int32_t* ubin, const int32_t* ibin,
@@ -351,7 +323,7 @@ void block_ranks(const int32_t* bin, int32_t n, int B, std::vector<int32_t>& ran
 
 int pack_count_cb(void* vctx, const PackRequest& q, std::vector<PackCellInfo>& info) {
     Ctx* c = static_cast<Ctx*>(vctx);
-    if (!c->d_sorted || !c->d_bptr || c->host_u != q.u || c->host_i != q.i || c->n != q.n) return -1;
+    if (!c->pk.sorted || !c->pk.bptr || c->host_u != q.u || c->host_i != q.i || c->n != q.n) return -1;
     const int64_t n_cells = (int64_t)q.B * q.B, WW = (int64_t)q.W * q.W;
     if (n_cells >= (int64_t)1 << 31 || q.G > 64) return 1;
     std::vector<int32_t> ur, ir;
@@ -382,29 +354,30 @@ int pack_count_cb(void* vctx, const PackRequest& q, std::vector<PackCellInfo>& i
         worst.max_rows = rows_full;
         if (pack_lds_bytes(worst) > 160 * 1024 - 256) return 1;
     }
-    int rc = -1;
-    ING_CHK(hipMalloc(&c->d_r, sizeof(float) * (size_t)std::max<int64_t>(q.n, 1)));
-    ING_CHK(hipMemcpy(c->d_r, q.r, sizeof(float) * (size_t)q.n, hipMemcpyHostToDevice));
+    PackState& pk = c->pk;
+    const size_t nn = (size_t)std::max<int64_t>(q.n, 1);
+    ING_CHK(pk.r.alloc(sizeof(float) * nn));
+    ING_CHK(hipMemcpy(pk.r.get(), q.r, sizeof(float) * (size_t)q.n, hipMemcpyHostToDevice));
     if (q.orig) {
-        ING_CHK(hipMalloc(&c->d_orig, sizeof(long long) * (size_t)std::max<int64_t>(q.n, 1)));
-        ING_CHK(hipMemcpy(c->d_orig, q.orig, sizeof(long long) * (size_t)q.n, hipMemcpyHostToDevice));
+        ING_CHK(pk.orig.alloc(sizeof(long long) * nn));
+        ING_CHK(hipMemcpy(pk.orig.get(), q.orig, sizeof(long long) * (size_t)q.n, hipMemcpyHostToDevice));
     }
-    ING_CHK(hipMalloc(&c->d_urank, sizeof(int32_t) * (size_t)q.U));
-    ING_CHK(hipMalloc(&c->d_irank, sizeof(int32_t) * (size_t)q.I));
-    ING_CHK(hipMemcpy(c->d_urank, ur.data(), sizeof(int32_t) * (size_t)q.U, hipMemcpyHostToDevice));
-    ING_CHK(hipMemcpy(c->d_irank, ir.data(), sizeof(int32_t) * (size_t)q.I, hipMemcpyHostToDevice));
-    ING_CHK(hipMalloc(&c->d_info, sizeof(PackCellInfo) * (size_t)n_cells));
-    ING_CHK(hipMalloc(&c->d_subs, sizeof(SubDesc) * (size_t)(n_cells * WW)));
-    a.u = c->du;
-    a.i = c->di;
-    a.r = c->d_r;
-    a.orig = c->d_orig;
-    a.sorted = c->d_sorted;
-    a.bptr = c->d_bptr;
-    a.urank = c->d_urank;
-    a.irank = c->d_irank;
-    a.info = c->d_info;
-    a.subs = c->d_subs;
+    ING_CHK(pk.urank.alloc(sizeof(int32_t) * (size_t)q.U));
+    ING_CHK(pk.irank.alloc(sizeof(int32_t) * (size_t)q.I));
+    ING_CHK(hipMemcpy(pk.urank.get(), ur.data(), sizeof(int32_t) * (size_t)q.U, hipMemcpyHostToDevice));
+    ING_CHK(hipMemcpy(pk.irank.get(), ir.data(), sizeof(int32_t) * (size_t)q.I, hipMemcpyHostToDevice));
+    ING_CHK(pk.info.alloc(sizeof(PackCellInfo) * (size_t)n_cells));
+    ING_CHK(pk.subs.alloc(sizeof(SubDesc) * (size_t)(n_cells * WW)));
+    a.u = c->du.as<int32_t>();
+    a.i = c->di.as<int32_t>();
+    a.r = pk.r.as<float>();
+    a.orig = pk.orig.as<long long>();
+    a.sorted = pk.sorted.as<unsigned>();
+    a.bptr = pk.bptr.as<long long>();
+    a.urank = pk.urank.as<int32_t>();
+    a.irank = pk.irank.as<int32_t>();
+    a.info = pk.info.as<PackCellInfo>();
+    a.subs = pk.subs.as<SubDesc>();
     a.emit = 0;
     if (q.ord_off && !std::getenv("MFSGD_PACK_TWICE")) {  // (the variable: A/B measurements)
         // one-pass mode: scratch for rows and entries, the order array itself; if any of it does not fit, count only
@@ -412,87 +385,65 @@ int pack_count_cb(void* vctx, const PackRequest& q, std::vector<PackCellInfo>& i
         const size_t steps = pack_scratch_steps(q.n, n_cells, q.W);
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-        const size_t need = sizeof(Entry) * steps * (size_t)q.G + 16 * (size_t)std::max<int64_t>(q.n, 1);
-        if (need <= free_b / 3 && hipMalloc(&c->d_srows, 4 * (2 * (size_t)std::max<int64_t>(q.n, 1))) == hipSuccess &&
-            hipMalloc(&c->d_sent, sizeof(Entry) * steps * (size_t)q.G) == hipSuccess &&
-            hipMalloc(&c->d_order, 8 * (size_t)std::max<int64_t>(q.n, 1)) == hipSuccess &&
-            hipMalloc(&c->d_ord_off, 8 * (size_t)n_cells) == hipSuccess &&
-            hipMemcpy(c->d_ord_off, q.ord_off, 8 * (size_t)n_cells, hipMemcpyHostToDevice) == hipSuccess) {
+        const size_t need = sizeof(Entry) * steps * (size_t)q.G + 16 * nn;
+        if (need <= free_b / 3 && pk.one.srows.alloc(4 * (2 * nn)) == hipSuccess &&
+            pk.one.sent.alloc(sizeof(Entry) * steps * (size_t)q.G) == hipSuccess && pk.one.order.alloc(8 * nn) == hipSuccess &&
+            pk.one.ord_off.alloc(8 * (size_t)n_cells) == hipSuccess &&
+            hipMemcpy(pk.one.ord_off.get(), q.ord_off, 8 * (size_t)n_cells, hipMemcpyHostToDevice) == hipSuccess) {
             a.emit = 2;
-            a.rows = c->d_srows;
-            a.entries = c->d_sent;
-            a.order = c->d_order;
-            a.ord_off = c->d_ord_off;
+            a.rows = pk.one.srows.as<uint32_t>();
+            a.entries = pk.one.sent.as<Entry>();
+            a.order = pk.one.order.as<long long>();
+            a.ord_off = pk.one.ord_off.as<long long>();
         } else {
             (void)hipGetLastError();
-            void* ptrs[] = {c->d_srows, c->d_sent, c->d_order, c->d_ord_off};
-            for (void* p : ptrs)
-                if (p) (void)hipFree(p);
-            c->d_srows = nullptr;
-            c->d_sent = nullptr;
-            c->d_order = nullptr;
-            c->d_ord_off = nullptr;
+            pk.one = PackState::OnePass{};
         }
     }
     reserve_huge(info, (size_t)n_cells);
     info.resize((size_t)n_cells);
     for (;;) {
         ING_CHK(launch_pack(a, n_cells, (hipStream_t)0));
-        ING_CHK(hipMemcpy(info.data(), c->d_info, sizeof(PackCellInfo) * (size_t)n_cells, hipMemcpyDeviceToHost));
+        ING_CHK(hipMemcpy(info.data(), pk.info.get(), sizeof(PackCellInfo) * (size_t)n_cells, hipMemcpyDeviceToHost));
         bool more_rows = false;
         for (const PackCellInfo& ci : info) more_rows = more_rows || ci.status == 2;
         if (!more_rows || a.max_rows >= rows_full) break;
         a.max_rows = rows_full;
     }
-    c->args = a;
-    c->n_cells = n_cells;
-    c->rows_full = rows_full;
+    pk.args = a;
+    pk.n_cells = n_cells;
+    pk.rows_full = rows_full;
     return 0;
-fail:
-    return rc;
 }
 
 // A list of parts (chunks) as the packing kernel's cells: uploads it and returns the arguments of a launch over it
-// (COUNT outputs allocated); the caller frees what `owned` holds.
+// (COUNT outputs allocated), which live as long as `pl`.
 struct PartList {
-    unsigned* d_sorted = nullptr;
-    long long* d_cptr = nullptr;
-    PackCellInfo* d_info = nullptr;
-    SubDesc* d_subs = nullptr;
-    void release() {
-        void* ptrs[] = {d_sorted, d_cptr, d_info, d_subs};
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-        d_sorted = nullptr;
-        d_cptr = nullptr;
-        d_info = nullptr;
-        d_subs = nullptr;
-    }
+    DevBuf sorted, cptr, info, subs;
 };
 
 bool upload_parts(Ctx* c, int64_t n_parts, const uint32_t* sorted, int64_t n_sorted, const int64_t* cptr, PartList& pl, PackArgs& a) {
-    const int64_t WW = (int64_t)c->args.W * c->args.W;
+    const int64_t WW = (int64_t)c->pk.args.W * c->pk.args.W;
     static_assert(sizeof(long long) == sizeof(int64_t), "cptr is uploaded as it is");
-    if (hipMalloc(&pl.d_sorted, 4 * (size_t)std::max<int64_t>(n_sorted, 1)) != hipSuccess ||
-        hipMalloc(&pl.d_cptr, 8 * (size_t)(n_parts * WW + 1)) != hipSuccess ||
-        hipMalloc(&pl.d_info, sizeof(PackCellInfo) * (size_t)n_parts) != hipSuccess ||
-        hipMalloc(&pl.d_subs, sizeof(SubDesc) * (size_t)(n_parts * WW)) != hipSuccess ||
-        hipMemcpy(pl.d_sorted, sorted, 4 * (size_t)n_sorted, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(pl.d_cptr, cptr, 8 * (size_t)(n_parts * WW + 1), hipMemcpyHostToDevice) != hipSuccess) {
+    if (pl.sorted.alloc(4 * (size_t)std::max<int64_t>(n_sorted, 1)) != hipSuccess ||
+        pl.cptr.alloc(8 * (size_t)(n_parts * WW + 1)) != hipSuccess ||
+        pl.info.alloc(sizeof(PackCellInfo) * (size_t)n_parts) != hipSuccess ||
+        pl.subs.alloc(sizeof(SubDesc) * (size_t)(n_parts * WW)) != hipSuccess ||
+        hipMemcpy(pl.sorted.get(), sorted, 4 * (size_t)n_sorted, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(pl.cptr.get(), cptr, 8 * (size_t)(n_parts * WW + 1), hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipGetLastError();
-        pl.release();
         return false;
     }
-    a = c->args;
+    a = c->pk.args;
     a.rows = nullptr;  // (a COUNT pass proper: the cells' one-pass scratch is not the parts')
     a.entries = nullptr;
     a.order = nullptr;
     a.ord_off = nullptr;
-    a.max_rows = c->rows_full;  // a part can hold any number of rows a cell can
-    a.sorted = pl.d_sorted;
-    a.bptr = pl.d_cptr;
-    a.info = pl.d_info;
-    a.subs = pl.d_subs;
+    a.max_rows = c->pk.rows_full;  // a part can hold any number of rows a cell can
+    a.sorted = pl.sorted.as<unsigned>();
+    a.bptr = pl.cptr.as<long long>();
+    a.info = pl.info.as<PackCellInfo>();
+    a.subs = pl.subs.as<SubDesc>();
     a.emit = 0;
     return true;
 }
@@ -500,18 +451,14 @@ bool upload_parts(Ctx* c, int64_t n_parts, const uint32_t* sorted, int64_t n_sor
 int pack_count_parts_cb(void* vctx, int64_t n_parts, const uint32_t* sorted, int64_t n_sorted, const int64_t* cptr,
                         PackCellInfo* info) {
     Ctx* c = static_cast<Ctx*>(vctx);
-    if (!c->d_info || n_parts < 0) return -1;
+    if (!c->pk.info || n_parts < 0) return -1;
     if (n_parts == 0) return 0;
     PartList pl;
     PackArgs a{};
     if (!upload_parts(c, n_parts, sorted, n_sorted, cptr, pl, a)) return -1;
-    int rc = -1;
     ING_CHK(launch_pack(a, n_parts, (hipStream_t)0));
-    ING_CHK(hipMemcpy(info, pl.d_info, sizeof(PackCellInfo) * (size_t)n_parts, hipMemcpyDeviceToHost));
-    rc = 0;
-fail:
-    pl.release();
-    return rc;
+    ING_CHK(hipMemcpy(info, pl.info.get(), sizeof(PackCellInfo) * (size_t)n_parts, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 struct PartsToEmit {
@@ -533,123 +480,97 @@ __global__ void __launch_bounds__(256) table_scatter_kernel(SubDesc* __restrict_
 
 int emit_common(Ctx* c, const uint32_t* row_off, const uint32_t* ent_off, const int64_t* ord_off, int64_t n_rows,
                 int64_t n_steps, int64_t n_descs, DevicePacked* out, const PartsToEmit* parts = nullptr) {
-    if (!c->d_info || !out) return -1;
-    PackArgs a = c->args;
-    SubDesc* d_fin = nullptr;  // the final sub-cell table
-    long long* d_pdesc = nullptr;
-    uint32_t *d_ro = nullptr, *d_eo = nullptr, *d_rows = nullptr;
-    long long *d_oo = nullptr, *d_order = nullptr;
-    Entry* d_ent = nullptr;
-    const size_t nc = (size_t)c->n_cells;
-    const bool one_pass = c->d_sent != nullptr;  // the COUNT pass wrote what it packed: move it, do not pack again
+    PackState& pk = c->pk;
+    if (!pk.info || !out) return -1;
+    PackArgs a = pk.args;
+    DevBuf ro, eo, oo, pdesc;         // the offsets, for the length of this call
+    DevBuf rows, ent, order, fin;     // what `out` gets: fin = the final sub-cell table
+    const size_t nc = (size_t)pk.n_cells;
+    const bool one_pass = (bool)pk.one.sent;  // the COUNT pass wrote what it packed: move it, do not pack again
     const size_t WWs = (size_t)a.W * a.W;
-    std::vector<long long> oo(ord_off, ord_off + nc);
-    if (n_descs < c->n_cells) return -1;
-    ING_CHK(hipMalloc(&d_ro, 4 * nc));
-    ING_CHK(hipMalloc(&d_eo, 4 * nc));
-    ING_CHK(hipMalloc(&d_oo, 8 * nc));
-    ING_CHK(hipMemcpy(d_ro, row_off, 4 * nc, hipMemcpyHostToDevice));
-    ING_CHK(hipMemcpy(d_eo, ent_off, 4 * nc, hipMemcpyHostToDevice));
-    ING_CHK(hipMemcpy(d_oo, oo.data(), 8 * nc, hipMemcpyHostToDevice));
-    ING_CHK(hipMalloc(&d_rows, 4 * (size_t)(n_rows + 4)));
-    ING_CHK(hipMemset(d_rows + n_rows, 0, 16));  // the staging DMA reads whole 16-byte units
-    ING_CHK(hipMalloc(&d_ent, sizeof(Entry) * (size_t)std::max<int64_t>(n_steps * a.G, 1)));
-    if (one_pass) {
-        d_order = c->d_order;  // written by the COUNT pass, at its final place
-        c->d_order = nullptr;
-    } else {
-        ING_CHK(hipMalloc(&d_order, 8 * (size_t)std::max<int64_t>(c->n, 1)));
-    }
-    a.row_off = d_ro;
-    a.ent_off = d_eo;
-    a.ord_off = d_oo;
-    a.rows = d_rows;
-    a.entries = d_ent;
-    a.order = d_order;
+    std::vector<long long> oo_host(ord_off, ord_off + nc);
+    if (n_descs < pk.n_cells) return -1;
+    ING_CHK(ro.alloc(4 * nc));
+    ING_CHK(eo.alloc(4 * nc));
+    ING_CHK(oo.alloc(8 * nc));
+    ING_CHK(hipMemcpy(ro.get(), row_off, 4 * nc, hipMemcpyHostToDevice));
+    ING_CHK(hipMemcpy(eo.get(), ent_off, 4 * nc, hipMemcpyHostToDevice));
+    ING_CHK(hipMemcpy(oo.get(), oo_host.data(), 8 * nc, hipMemcpyHostToDevice));
+    ING_CHK(rows.alloc(4 * (size_t)(n_rows + 4)));
+    ING_CHK(hipMemset(rows.as<uint32_t>() + n_rows, 0, 16));  // the staging DMA reads whole 16-byte units
+    ING_CHK(ent.alloc(sizeof(Entry) * (size_t)std::max<int64_t>(n_steps * a.G, 1)));
+    if (one_pass)
+        order = std::move(pk.one.order);  // written by the COUNT pass, at its final place
+    else
+        ING_CHK(order.alloc(8 * (size_t)std::max<int64_t>(c->n, 1)));
+    a.row_off = ro.as<uint32_t>();
+    a.ent_off = eo.as<uint32_t>();
+    a.ord_off = oo.as<long long>();
+    a.rows = rows.as<uint32_t>();
+    a.entries = ent.as<Entry>();
+    a.order = order.as<long long>();
     // the final sub-cell table: the cells' tables as the COUNT pass left them (a cell that is cut gets its first chunk's
     // below), zeros for the descriptors nothing is written to and for the two padding records
-    ING_CHK(hipMalloc(&d_fin, sizeof(SubDesc) * ((size_t)n_descs * WWs + 2)));
-    ING_CHK(hipMemsetAsync(d_fin + (size_t)c->n_cells * WWs, 0, sizeof(SubDesc) * ((size_t)(n_descs - c->n_cells) * WWs + 2), (hipStream_t)0));
-    ING_CHK(hipMemcpyAsync(d_fin, c->d_subs, sizeof(SubDesc) * (size_t)c->n_cells * WWs, hipMemcpyDeviceToDevice, (hipStream_t)0));
+    ING_CHK(fin.alloc(sizeof(SubDesc) * ((size_t)n_descs * WWs + 2)));
+    SubDesc* d_fin = fin.as<SubDesc>();
+    ING_CHK(hipMemsetAsync(d_fin + nc * WWs, 0, sizeof(SubDesc) * ((size_t)(n_descs - pk.n_cells) * WWs + 2), (hipStream_t)0));
+    ING_CHK(hipMemcpyAsync(d_fin, pk.subs.get(), sizeof(SubDesc) * nc * WWs, hipMemcpyDeviceToDevice, (hipStream_t)0));
     if (one_pass) {
         a.emit = 2;
-        ING_CHK(launch_compact(a, c->n_cells, c->d_srows, c->d_sent, (hipStream_t)0));
+        ING_CHK(launch_compact(a, pk.n_cells, pk.one.srows.as<uint32_t>(), pk.one.sent.as<Entry>(), (hipStream_t)0));
     } else {
         a.emit = 1;
-        ING_CHK(launch_pack(a, c->n_cells, (hipStream_t)0));
+        ING_CHK(launch_pack(a, pk.n_cells, (hipStream_t)0));
     }
     if (parts && parts->n_parts > 0) {
         // the chunks of the cells that were cut: COUNT over the final list (the EMIT pass reads the sub-cell table the
-        // COUNT pass of the SAME list left on the device), then EMIT at the caller's offsets into the same arrays
+        // COUNT pass of the SAME list left on the device), then EMIT at the caller's offsets into the same arrays.
+        // The list and its offsets go at the end of this block, before the arrays are handed on.
         PartList pl;
         PackArgs pa{};
-        uint32_t *p_ro = nullptr, *p_eo = nullptr;
-        long long* p_oo = nullptr;
+        DevBuf p_ro, p_eo, p_oo;
         const size_t np = (size_t)parts->n_parts;
-        bool ok = upload_parts(c, parts->n_parts, parts->sorted, parts->n_sorted, parts->cptr, pl, pa);
-        ok = ok && launch_pack(pa, parts->n_parts, (hipStream_t)0) == hipSuccess;
-        ok = ok && hipMalloc(&p_ro, 4 * np) == hipSuccess && hipMalloc(&p_eo, 4 * np) == hipSuccess && hipMalloc(&p_oo, 8 * np) == hipSuccess;
-        ok = ok && hipMemcpy(p_ro, parts->row_off, 4 * np, hipMemcpyHostToDevice) == hipSuccess &&
-             hipMemcpy(p_eo, parts->ent_off, 4 * np, hipMemcpyHostToDevice) == hipSuccess &&
-             hipMemcpy(p_oo, parts->ord_off, 8 * np, hipMemcpyHostToDevice) == hipSuccess;
-        if (ok) {
-            pa.emit = 1;
-            pa.row_off = p_ro;
-            pa.ent_off = p_eo;
-            pa.ord_off = p_oo;
-            pa.rows = d_rows;
-            pa.entries = d_ent;
-            pa.order = d_order;
-            ok = launch_pack(pa, parts->n_parts, (hipStream_t)0) == hipSuccess;
-            if (ok) {
-                // (the EMIT pass does not touch the table the COUNT pass of the same list left in pl.d_subs)
-                ok = parts->desc != nullptr && hipMalloc(&d_pdesc, 8 * np) == hipSuccess &&
-                     hipMemcpy(d_pdesc, parts->desc, 8 * np, hipMemcpyHostToDevice) == hipSuccess;
-                if (ok) {
-                    const long long tot = (long long)np * a.W * a.W;
-                    hipLaunchKernelGGL(table_scatter_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)0, d_fin, pl.d_subs,
-                                       d_pdesc, (long long)np, a.W * a.W);
-                    ok = hipGetLastError() == hipSuccess;
-                }
-            }
-            ok = ok && hipDeviceSynchronize() == hipSuccess;
-        }
-        if (p_ro) (void)hipFree(p_ro);
-        if (p_eo) (void)hipFree(p_eo);
-        if (p_oo) (void)hipFree(p_oo);
-        pl.release();
-        if (!ok) {
-            (void)hipGetLastError();
-            goto fail;
-        }
+        if (!upload_parts(c, parts->n_parts, parts->sorted, parts->n_sorted, parts->cptr, pl, pa)) return -1;
+        ING_CHK(launch_pack(pa, parts->n_parts, (hipStream_t)0));
+        ING_CHK(p_ro.alloc(4 * np));
+        ING_CHK(p_eo.alloc(4 * np));
+        ING_CHK(p_oo.alloc(8 * np));
+        ING_CHK(hipMemcpy(p_ro.get(), parts->row_off, 4 * np, hipMemcpyHostToDevice));
+        ING_CHK(hipMemcpy(p_eo.get(), parts->ent_off, 4 * np, hipMemcpyHostToDevice));
+        ING_CHK(hipMemcpy(p_oo.get(), parts->ord_off, 8 * np, hipMemcpyHostToDevice));
+        pa.emit = 1;
+        pa.row_off = p_ro.as<uint32_t>();
+        pa.ent_off = p_eo.as<uint32_t>();
+        pa.ord_off = p_oo.as<long long>();
+        pa.rows = a.rows;
+        pa.entries = a.entries;
+        pa.order = a.order;
+        ING_CHK(launch_pack(pa, parts->n_parts, (hipStream_t)0));
+        // (the EMIT pass does not touch the table the COUNT pass of the same list left in pl.subs)
+        if (!parts->desc) return -1;
+        ING_CHK(pdesc.alloc(8 * np));
+        ING_CHK(hipMemcpy(pdesc.get(), parts->desc, 8 * np, hipMemcpyHostToDevice));
+        const long long tot = (long long)np * a.W * a.W;
+        hipLaunchKernelGGL(table_scatter_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)0, d_fin,
+                           pl.subs.as<SubDesc>(), pdesc.as<long long>(), (long long)np, a.W * a.W);
+        ING_CHK(hipGetLastError());
+        ING_CHK(hipDeviceSynchronize());
     }
     ING_CHK(hipDeviceSynchronize());
-    (void)hipFree(d_ro); (void)hipFree(d_eo); (void)hipFree(d_oo);
-    if (d_pdesc) (void)hipFree(d_pdesc);
-    out->rows = d_rows;
-    out->entries = d_ent;
-    out->order = d_order;
-    out->subs = d_fin;
+    out->rows = rows.detach();
+    out->entries = ent.detach();
+    out->order = order.detach();
+    out->subs = fin.detach();
     out->n_subs = n_descs * (int64_t)WWs + 2;
     out->release = release_cb;
     drop_pack_state(c);
     return 0;
-fail:
-    if (d_ro) (void)hipFree(d_ro);
-    if (d_eo) (void)hipFree(d_eo);
-    if (d_oo) (void)hipFree(d_oo);
-    if (d_rows) (void)hipFree(d_rows);
-    if (d_ent) (void)hipFree(d_ent);
-    if (d_order) (void)hipFree(d_order);
-    if (d_fin) (void)hipFree(d_fin);
-    if (d_pdesc) (void)hipFree(d_pdesc);
-    return -1;
 }
 
 int pack_emit_cb(void* vctx, const uint32_t* row_off, const uint32_t* ent_off, const int64_t* ord_off, int64_t n_rows,
                  int64_t n_steps, DevicePacked* out) {
     Ctx* c = static_cast<Ctx*>(vctx);
-    return emit_common(c, row_off, ent_off, ord_off, n_rows, n_steps, c->n_cells, out);
+    return emit_common(c, row_off, ent_off, ord_off, n_rows, n_steps, c->pk.n_cells, out);
 }
 
 int pack_emit_parts_cb(void* vctx, const uint32_t* row_off, const uint32_t* ent_off, const int64_t* ord_off, int64_t n_rows,

@@ -5,6 +5,7 @@
 
 #include <cstdint>
 
+#include "devmem.hpp"
 #include "schedule.hpp"
 
 namespace mfsgd {
@@ -72,10 +73,11 @@ struct RecommendExcl {
 bool recommend_is_fused(int32_t n_items, int32_t topn);
 hipError_t recommend_fused(int L, const float* P, const float* Q, const int32_t* d_users, int nb, int32_t n_items,
                            int32_t topn, const RecommendExcl& ex, float* out_s, int32_t* out_i, hipStream_t st);
-// ... and for the rest: scores of nb users against every item, top `topn` of each into out_s / out_i.
+// ... and for the rest: scores of nb users against every item, top `topn` of each into out_s / out_i.  `temp` is the
+// sorts' scratch: the caller's, so that one serves all batches; grown here when it is too small.
 hipError_t recommend_batch(int L, const float* P, const float* Q, const int32_t* d_users, int nb, int32_t n_items,
                            int32_t topn, const RecommendExcl& ex, float* s_in, float* s_out, int32_t* id_in, int32_t* id_out,
-                           long long* d_off, void*& temp, size_t& temp_bytes, float* out_s, int32_t* out_i, hipStream_t st);
+                           long long* d_off, DevBuf& temp, float* out_s, int32_t* out_i, hipStream_t st);
 // Building the lists: each chunk of pairs appends slot << 32 | item to keys[*count ...] for the pairs of requested users
 // (count starts at 0; at most cap are written) ...
 hipError_t recommend_excl_filter(const int32_t* slot_of_user, const int32_t* u, const int32_t* i, int64_t n,
@@ -83,7 +85,6 @@ hipError_t recommend_excl_filter(const int32_t* slot_of_user, const int32_t* u, 
 // ... then the n keys are sorted (through keys_tmp) and made distinct, back into keys: *n_distinct of them,
 // off[n_slots + 1] and items[n] as RecommendExcl reads them.
 hipError_t recommend_excl_lists(unsigned long long* keys, unsigned long long* keys_tmp, int64_t n, int32_t n_slots,
-                                unsigned* n_distinct, long long* off, int32_t* items, void*& temp, size_t& temp_bytes,
-                                hipStream_t st);
+                                unsigned* n_distinct, long long* off, int32_t* items, DevBuf& temp, hipStream_t st);
 
 }  // namespace mfsgd

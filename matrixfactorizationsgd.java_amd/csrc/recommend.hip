@@ -322,27 +322,17 @@ __global__ void __launch_bounds__(256) offsets_kernel(long long* __restrict__ of
     for (int x = threadIdx.x; x <= n; x += 256) off[x] = (long long)x * n_items;
 }
 
-hipError_t grow_temp(void*& temp, size_t& temp_bytes, size_t need) {
-    if (need <= temp_bytes) return hipSuccess;
-    if (temp) (void)hipFree(temp);
-    temp = nullptr;
-    temp_bytes = 0;
-    const hipError_t e = hipMalloc(&temp, need);
-    if (e == hipSuccess) temp_bytes = need;
-    return e;
-}
-
 // stable descending segmented sort of nb rows of n_items (key, id) pairs; K = float (scores) or unsigned (keys)
 template <class K>
 hipError_t sort_rows(K* k_in, K* k_out, int32_t* id_in, int32_t* id_out, long long* d_off, int nb, int32_t n_items,
-                     void*& temp, size_t& temp_bytes, hipStream_t st) {
+                     DevBuf& temp, hipStream_t st) {
     size_t need = 0;
     hipError_t e = rocprim::segmented_radix_sort_pairs_desc(nullptr, need, k_in, k_out, id_in, id_out,
                                                             (unsigned)((size_t)nb * n_items), (unsigned)nb, d_off, d_off + 1,
                                                             0u, 32u, st);
-    if (e == hipSuccess) e = grow_temp(temp, temp_bytes, need);
+    if (e == hipSuccess) e = temp.alloc(need);
     if (e == hipSuccess)
-        e = rocprim::segmented_radix_sort_pairs_desc(temp, need, k_in, k_out, id_in, id_out, (unsigned)((size_t)nb * n_items),
+        e = rocprim::segmented_radix_sort_pairs_desc(temp.get(), need, k_in, k_out, id_in, id_out, (unsigned)((size_t)nb * n_items),
                                                      (unsigned)nb, d_off, d_off + 1, 0u, 32u, st);
     return e;
 }
@@ -350,7 +340,7 @@ hipError_t sort_rows(K* k_in, K* k_out, int32_t* id_in, int32_t* id_out, long lo
 template <int L>
 hipError_t batch_L(const float* P, const float* Q, const int32_t* users, int nb, int32_t n_items, int32_t topn,
                    const RecommendExcl& ex, float* s_in, float* s_out, int32_t* id_in, int32_t* id_out, long long* d_off,
-                   void*& temp, size_t& temp_bytes, float* out_s, int32_t* out_i, hipStream_t st) {
+                   DevBuf& temp, float* out_s, int32_t* out_i, hipStream_t st) {
     const int gpb = 256 / L;
     int bx = (n_items + gpb - 1) / gpb;
     if (bx > 64) bx = 64;
@@ -369,14 +359,14 @@ hipError_t batch_L(const float* P, const float* Q, const int32_t* users, int nb,
     hipLaunchKernelGGL(offsets_kernel, dim3(1), dim3(256), 0, st, d_off, nb, n_items);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (!ex.slot) {
-        e = sort_rows(s_in, s_out, id_in, id_out, d_off, nb, n_items, temp, temp_bytes, st);
+        e = sort_rows(s_in, s_out, id_in, id_out, d_off, nb, n_items, temp, st);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(take_top_kernel, dim3((unsigned)nb), dim3(256), 0, st, s_out, id_out, n_items, topn, out_s, out_i);
         return hipGetLastError();
     }
     unsigned* k_in = reinterpret_cast<unsigned*>(s_in);
     unsigned* k_out = reinterpret_cast<unsigned*>(s_out);
-    e = sort_rows(k_in, k_out, id_in, id_out, d_off, nb, n_items, temp, temp_bytes, st);
+    e = sort_rows(k_in, k_out, id_in, id_out, d_off, nb, n_items, temp, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((take_top_excl_kernel<L>), dim3((unsigned)nb), dim3(256), 0, st, P, Q, users, k_out, id_out, n_items,
                        topn, out_s, out_i);
@@ -455,12 +445,12 @@ hipError_t recommend_fused(int L, const float* P, const float* Q, const int32_t*
 // Device buffers are the caller's (capi.cpp): scores/ids in and out (nb * n_items each), offsets nb+1.
 hipError_t recommend_batch(int L, const float* P, const float* Q, const int32_t* d_users, int nb, int32_t n_items,
                            int32_t topn, const RecommendExcl& ex, float* s_in, float* s_out, int32_t* id_in, int32_t* id_out,
-                           long long* d_off, void*& temp, size_t& temp_bytes, float* out_s, int32_t* out_i, hipStream_t st) {
+                           long long* d_off, DevBuf& temp, float* out_s, int32_t* out_i, hipStream_t st) {
     switch (L) {
 #define MFSGD_BATCH(LL)                                                                                              \
     case LL:                                                                                                         \
-        return batch_L<LL>(P, Q, d_users, nb, n_items, topn, ex, s_in, s_out, id_in, id_out, d_off, temp, temp_bytes, \
-                           out_s, out_i, st);
+        return batch_L<LL>(P, Q, d_users, nb, n_items, topn, ex, s_in, s_out, id_in, id_out, d_off, temp, out_s, \
+                           out_i, st);
         MFSGD_BATCH(1)
         MFSGD_BATCH(2)
         MFSGD_BATCH(4)
@@ -483,8 +473,7 @@ hipError_t recommend_excl_filter(const int32_t* slot_of_user, const int32_t* u, 
 }
 
 hipError_t recommend_excl_lists(unsigned long long* keys, unsigned long long* keys_tmp, int64_t n, int32_t n_slots,
-                                unsigned* n_distinct, long long* off, int32_t* items, void*& temp, size_t& temp_bytes,
-                                hipStream_t st) {
+                                unsigned* n_distinct, long long* off, int32_t* items, DevBuf& temp, hipStream_t st) {
     unsigned end_bit = 33;  // slot bits above the 32 of the item
     while (end_bit < 64 && ((unsigned long long)(n_slots - 1) >> (end_bit - 32)) != 0) ++end_bit;
     size_t need_sort = 0, need_uniq = 0;
@@ -492,10 +481,10 @@ hipError_t recommend_excl_lists(unsigned long long* keys, unsigned long long* ke
     if (e == hipSuccess)
         e = rocprim::unique(nullptr, need_uniq, keys_tmp, keys, n_distinct, (size_t)n,
                             rocprim::equal_to<unsigned long long>(), st);
-    if (e == hipSuccess) e = grow_temp(temp, temp_bytes, std::max(need_sort, need_uniq));
-    if (e == hipSuccess) e = rocprim::radix_sort_keys(temp, need_sort, keys, keys_tmp, (size_t)n, 0u, end_bit, st);
+    if (e == hipSuccess) e = temp.alloc(std::max(need_sort, need_uniq));
+    if (e == hipSuccess) e = rocprim::radix_sort_keys(temp.get(), need_sort, keys, keys_tmp, (size_t)n, 0u, end_bit, st);
     if (e == hipSuccess)
-        e = rocprim::unique(temp, need_uniq, keys_tmp, keys, n_distinct, (size_t)n,
+        e = rocprim::unique(temp.get(), need_uniq, keys_tmp, keys, n_distinct, (size_t)n,
                             rocprim::equal_to<unsigned long long>(), st);
     if (e != hipSuccess) return e;
     const long long work = std::max<long long>(n, (long long)n_slots + 1);

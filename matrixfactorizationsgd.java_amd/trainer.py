@@ -35,6 +35,15 @@ def _p(a, ctype):
     return a.ctypes.data_as(C.POINTER(ctype))
 
 
+def debug_device_bytes():
+    """mfsgd_debug_device_bytes: bytes of device memory the library holds in this process right now, over all handles."""
+    live = C.c_int64(-1)
+    rc = _lib.load_library().mfsgd_debug_device_bytes(C.byref(live))
+    if rc != 0:
+        raise MfsgdError(rc, "mfsgd_debug_device_bytes: bad argument")
+    return live.value
+
+
 def dsgd_plan(deg_user, deg_item, n_parts):
     """The global DSGD partitioner (mfsgd_dsgd_plan): (user_begin[n_parts + 1], item_part[n_items])."""
     du = np.ascontiguousarray(deg_user, np.int64)
@@ -349,6 +358,10 @@ class MatrixFactorizationSGD:
         self._check(self._lib.mfsgd_part_sse(self._handle(), int(part), C.c_void_p(q_block_ptr),
                                              C.c_void_p(stream_ptr), C.byref(out)))
         return out.value
+
+    def part_sync(self, part, stream_ptr=0):
+        """Waits for what part_train put on the stream and checks that the launches ran (mfsgd_part_sync)."""
+        self._check(self._lib.mfsgd_part_sync(self._handle(), int(part), C.c_void_p(stream_ptr)))
 
     def _group_lanes(self):
         need, L = (self.k + 3) // 4, 1

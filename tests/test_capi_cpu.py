@@ -76,6 +76,25 @@ def test_set_get_factors_roundtrip(mf):
     np.testing.assert_array_equal(Q, Q2)
 
 
+def test_a_host_only_life_cycle_holds_no_device_memory(mf):
+    """Ratings ingested on the host, factors seeded, set and read back: nothing of it is device memory, and after
+    the handle is closed the library's count of the device bytes it holds (mfsgd_debug_device_bytes) is zero."""
+    from mfsgd_amd import _lib
+
+    rng = np.random.default_rng(1)
+    U, I, k = 9, 7, 5
+    u, i = rng.integers(0, U, 60), rng.integers(0, I, 60)
+    with mf.MatrixFactorizationSGD(U, I, k, 0.01, 0.05, 1, flags=_lib.FLAG_HOST_INGEST) as m:
+        m.set_ratings(u, i, rng.random(60, dtype=np.float32))
+        m.init_factors()
+        P, Q = m.get_factors()
+        m.set_factors(P, Q)
+        P2, Q2 = m.get_factors()
+    np.testing.assert_array_equal(P, P2)
+    np.testing.assert_array_equal(Q, Q2)
+    assert mf.debug_device_bytes() == 0
+
+
 def test_part_init_q_is_a_slice_of_the_full_init(mf, oracle):
     U_total, I, k, G, seed = 11, 13, 6, 3, 77
     _, Qo = oracle.init_factors(U_total, I, k, seed)
