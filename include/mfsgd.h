@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows (additions: no existing call changed) */
+#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking (additions: no existing call changed) */
 
 typedef enum mfsgd_status {
     MFSGD_OK = 0,
@@ -108,7 +108,8 @@ int mfsgd_create(const mfsgd_config* cfg, mfsgd_handle** out);
 /* Java: close(). NULL is allowed. */
 void mfsgd_destroy(mfsgd_handle* h);
 /* Message of the last failure on this handle (h == NULL: of the last failed
- * mfsgd_create on this thread).  Never NULL; valid until the next call. */
+ * mfsgd_create or mfsgd_ranking_metrics_from_ranks on this thread).  Never NULL;
+ * valid until the next call. */
 const char* mfsgd_last_error(const mfsgd_handle* h);
 
 /* ---- ratings -> schedule (host) -------------------------------------------
@@ -182,6 +183,52 @@ int mfsgd_fold_in_users(mfsgd_handle* h, int32_t n_new, const int64_t* row_ptr, 
  * Same ordering, padding, scores and argument checks, with n_rows in the place of n_users.                           */
 int mfsgd_recommend_rows(mfsgd_handle* h, const float* rows, int32_t n_rows, int32_t topn, const int32_t* excl_row,
                          const int32_t* excl_item, int64_t n_excl, int32_t* out_items, float* out_scores);
+
+/* ---- ranking quality: where held-out items land, and the top-N metrics of that ------------------------------------
+ * out_rank[x] = how many items come before items[x] in users[x]'s recommendation order, among the items that are
+ * eligible for that user: the position (0 = best) items[x] takes in the list mfsgd_recommend_excluding(users[x],
+ * topn = n_items, the same pairs) returns, with items[x] itself counted as eligible even if a pair excludes it.
+ * Order: item j comes before item t when score(j) > score(t), or when the two scores compare equal as floats (-0.0
+ * equals +0.0) and j < t; scores are the bits mfsgd_predict() returns.  Ranks are exact integers.  The rank of a pair
+ * whose score is NaN is unspecified, and so are the ranks of a user any of whose items scores NaN.
+ * Eligibility: item j competes for user u unless (u, j) is one of the n_excl pairs; a user's other held-out items
+ * compete like any other item.  Duplicate pairs are allowed in both lists (a duplicate held-out pair gets the same
+ * rank twice); exclusion pairs of users without a held-out pair are ignored.
+ * Nothing of size users x n_items exists anywhere: the device counts, per pair, the items that beat it (csrc/rank.hip).
+ * Arguments are checked before any device work (MFSGD_ERR_INVALID_ARG, message "rank_items: ..."): negative n or
+ * n_excl, a null array that is needed, a user or item out of range in either list (also in exclusion pairs of users
+ * nobody asked about); for mfsgd_rank_items_rows also a negative n_rows and a null rows with n_rows > 0, and "in range"
+ * means below n_rows.  MFSGD_ERR_STATE: n_parts != 1, or (with n > 0) factors never initialised, set or loaded.
+ * MFSGD_ERR_NO_DEVICE: a valid call with n > 0 and no usable GPU; there is never a CPU result.  n == 0 is MFSGD_OK and
+ * touches nothing.  The model is not modified; the pairs go to the device in pieces of bounded size and
+ * everything allocated there is freed before the call returns.                                                      */
+int mfsgd_rank_items(mfsgd_handle* h, const int32_t* users, const int32_t* items, int64_t n,
+                     const int32_t* excl_u, const int32_t* excl_i, int64_t n_excl, int32_t* out_rank);
+/* The same where "user j" is rows[j] (n_rows x k, dense; e.g. what mfsgd_fold_in_users returned); row_of_pair and
+ * excl_row index rows. */
+int mfsgd_rank_items_rows(mfsgd_handle* h, const float* rows, int32_t n_rows, const int32_t* row_of_pair,
+                          const int32_t* items, int64_t n, const int32_t* excl_row, const int32_t* excl_item,
+                          int64_t n_excl, int32_t* out_rank);
+
+typedef struct mfsgd_ranking_metrics {
+    int64_t n_pairs, n_users;                                /* pairs given; distinct users among them */
+    double hit_rate, precision, recall, ndcg, mrr;           /* means over those users */
+} mfsgd_ranking_metrics;
+/* Host only, no handle, works without a GPU: the metrics of (users[x], ranks[x]) pairs at cut-off topn.  For user u
+ * with pairs T_u and their ranks r_t: hits = #{t : r_t < topn}; hit = (hits > 0); precision = hits / topn;
+ * recall = hits / |T_u|; ndcg = DCG / IDCG with DCG = sum over r_t < topn of 1 / log2(r_t + 2) and IDCG = sum over
+ * p < min(|T_u|, topn) of 1 / log2(p + 2); mrr = 1 / (min r_t + 1), which is not cut at topn.  Each field is the mean
+ * of its per-user value over the users that have a pair, summed in fp64 in ascending user order; n == 0 gives zeros.
+ * Duplicate pairs are NOT detected: the caller passes distinct (user, item) pairs for the metrics to mean anything.
+ * MFSGD_ERR_INVALID_ARG (message "ranking_metrics: ...", from mfsgd_last_error(NULL)): negative n, topn < 1, a null
+ * pointer that is needed, a negative rank.                                                                         */
+int mfsgd_ranking_metrics_from_ranks(const int32_t* users, const int32_t* ranks, int64_t n, int32_t topn,
+                                     mfsgd_ranking_metrics* out);
+/* mfsgd_rank_items followed by mfsgd_ranking_metrics_from_ranks.  out_rank may be NULL.  topn < 1 and a null `out`
+ * are MFSGD_ERR_INVALID_ARG as well, before any device work. */
+int mfsgd_evaluate_ranking(mfsgd_handle* h, const int32_t* users, const int32_t* items, int64_t n, int32_t topn,
+                           const int32_t* excl_u, const int32_t* excl_i, int64_t n_excl,
+                           mfsgd_ranking_metrics* out, int32_t* out_rank);
 
 /* Timed variant used by bench.py: runs `epochs` training passes bracketed by
  * HIP events on the handle's stream and returns the elapsed device time and

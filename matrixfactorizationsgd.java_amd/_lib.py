@@ -62,6 +62,21 @@ class ScheduleInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RankingMetrics(C.Structure):
+    _fields_ = [
+        ("n_pairs", C.c_int64),
+        ("n_users", C.c_int64),
+        ("hit_rate", C.c_double),
+        ("precision", C.c_double),
+        ("recall", C.c_double),
+        ("ndcg", C.c_double),
+        ("mrr", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 FLAG_NO_GRAPH = 1
 FLAG_ROUND_LAUNCH = 2
 FLAG_HOST_INGEST = 4
@@ -93,6 +108,11 @@ SIGNATURES = {
     "mfsgd_recommend_excluding": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i32p, _i32p, C.c_int64, _i32p, _f32p]),
     "mfsgd_fold_in_users": (C.c_int, [_H, C.c_int32, _i64p, _i32p, _f32p, C.c_int32, _f32p, C.c_int64, _f32p]),
     "mfsgd_recommend_rows": (C.c_int, [_H, _f32p, C.c_int32, C.c_int32, _i32p, _i32p, C.c_int64, _i32p, _f32p]),
+    "mfsgd_rank_items": (C.c_int, [_H, _i32p, _i32p, C.c_int64, _i32p, _i32p, C.c_int64, _i32p]),
+    "mfsgd_rank_items_rows": (C.c_int, [_H, _f32p, C.c_int32, _i32p, _i32p, C.c_int64, _i32p, _i32p, C.c_int64, _i32p]),
+    "mfsgd_ranking_metrics_from_ranks": (C.c_int, [_i32p, _i32p, C.c_int64, C.c_int32, C.POINTER(RankingMetrics)]),
+    "mfsgd_evaluate_ranking": (C.c_int, [_H, _i32p, _i32p, C.c_int64, C.c_int32, _i32p, _i32p, C.c_int64,
+                                         C.POINTER(RankingMetrics), _i32p]),
     "mfsgd_train_timed": (C.c_int, [_H, C.c_int32, _f64p, _i64p]),
     "mfsgd_ratings_file_open": (C.c_int, [C.c_char_p, C.c_int32, C.POINTER(_H)]),
     "mfsgd_ratings_file_info": (C.c_int, [_H, _i64p, _i32p, _i32p]),

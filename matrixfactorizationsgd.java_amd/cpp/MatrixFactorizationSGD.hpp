@@ -108,6 +108,43 @@ class MatrixFactorizationSGD {
         return {std::move(items), std::move(scores)};
     }
 
+    // int[] rankItems(int[] u, int[] i, int[] exclU, int[] exclI): per held-out pair the number of items that come before
+    // it in its user's recommendation order (its index in recommend(u, items, exclU, exclI)'s row)
+    std::vector<int32_t> rankItems(const std::vector<int32_t>& u, const std::vector<int32_t>& i,
+                                   const std::vector<int32_t>& excl_u = {}, const std::vector<int32_t>& excl_i = {}) {
+        if (u.size() != i.size() || excl_u.size() != excl_i.size()) throw std::invalid_argument("length mismatch");
+        std::vector<int32_t> ranks(u.size());
+        check(mfsgd_rank_items(h_, u.data(), i.data(), (int64_t)u.size(), excl_u.data(), excl_i.data(),
+                               (int64_t)excl_u.size(), ranks.data()));
+        return ranks;
+    }
+    // int[] rankItemsRows(float[] rows, int[] row, int[] i, int[] exclRow, int[] exclItem): the same for rows (n x k) that
+    // are not in the model, such as foldIn's
+    std::vector<int32_t> rankItemsRows(const std::vector<float>& rows, const std::vector<int32_t>& row,
+                                       const std::vector<int32_t>& i, const std::vector<int32_t>& excl_row = {},
+                                       const std::vector<int32_t>& excl_item = {}) {
+        if (row.size() != i.size() || excl_row.size() != excl_item.size() || rows.size() % (size_t)k_ != 0)
+            throw std::invalid_argument("length mismatch");
+        std::vector<int32_t> ranks(row.size());
+        check(mfsgd_rank_items_rows(h_, rows.data(), (int32_t)(rows.size() / (size_t)k_), row.data(), i.data(),
+                                    (int64_t)row.size(), excl_row.data(), excl_item.data(), (int64_t)excl_row.size(),
+                                    ranks.data()));
+        return ranks;
+    }
+    // RankingMetrics evaluateRanking(int[] u, int[] i, int topN, int[] exclU, int[] exclI): the ranks and their hit rate,
+    // precision, recall, NDCG at topN and MRR (means over the users that have a pair)
+    std::pair<mfsgd_ranking_metrics, std::vector<int32_t>> evaluateRanking(const std::vector<int32_t>& u,
+                                                                           const std::vector<int32_t>& i, int topn,
+                                                                           const std::vector<int32_t>& excl_u = {},
+                                                                           const std::vector<int32_t>& excl_i = {}) {
+        if (u.size() != i.size() || excl_u.size() != excl_i.size()) throw std::invalid_argument("length mismatch");
+        mfsgd_ranking_metrics m{};
+        std::vector<int32_t> ranks(u.size());
+        check(mfsgd_evaluate_ranking(h_, u.data(), i.data(), (int64_t)u.size(), topn, excl_u.data(), excl_i.data(),
+                                     (int64_t)excl_u.size(), &m, ranks.data()));
+        return {m, std::move(ranks)};
+    }
+
     double rmse() {
         double out = 0.0;
         check(mfsgd_rmse(h_, &out));

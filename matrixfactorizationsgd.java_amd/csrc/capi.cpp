@@ -1012,12 +1012,14 @@ namespace {
 // Exclusion lists of one recommend call on the device: the pairs go up in chunks of bounded size, those of requested
 // users are kept (slot << 32 | item), then sorted and made distinct into one list per slot (recommend.hip).
 // Scratch lives as long as this function; `ex` points into `slot`, `off` and `items`, which are the caller's.
+// `what` starts the message of a HIP failure: the call the lists are built for.
 constexpr int64_t kExclChunk = (int64_t)1 << 22;  // pairs per upload: 32 MB of staging
 
 int exclusions_to_device(mfsgd_handle* h, const std::vector<int32_t>& slot_of_user, int32_t n_slots, const int32_t* excl_u,
                          const int32_t* excl_i, int64_t n_excl, int64_t kept, DevBuf& slot, DevBuf& off, DevBuf& items,
-                         DevBuf& temp, RecommendExcl& ex) {
-    auto bad = [h](hipError_t e) { return serve_fail(h, "recommend: exclusion lists: ", e); };
+                         DevBuf& temp, RecommendExcl& ex, const char* what = "recommend") {
+    const std::string prefix = std::string(what) + ": exclusion lists: ";
+    auto bad = [h, &prefix](hipError_t e) { return serve_fail(h, prefix.c_str(), e); };
     DevBuf cu, ci, keys, keys_tmp, count;
     const int64_t chunk = std::min(n_excl, kExclChunk);
     int rc;
@@ -1156,6 +1158,228 @@ int mfsgd_recommend_rows(mfsgd_handle* h, const float* rows, int32_t n_rows, int
     for (int32_t j = 0; j < n_rows; ++j) all[(size_t)j] = j;
     return recommend_core(h, rows, n_rows, all.data(), n_rows, topn, excl_row, excl_item, n_excl, out_items,
                           out_scores);
+}
+
+
+namespace {
+
+// Pairs of one rank launch (whole users; a single user with more is a launch of its own): 16 MB of items up, as much
+// of ranks down
+constexpr int64_t kRankChunk = (int64_t)1 << 22;
+
+// Body of the rank calls, generic over the row matrix as recommend_core is: "user j" is row j of a matrix of n_rows
+// rows, the model's P (host_rows == nullptr) or host_rows (n_rows x k, dense).  The pairs are grouped by distinct
+// user on the host (counting sort; one slot per user, the slot numbering the exclusion lists use too), go up in
+// bounded pieces of whole users, and the ranks come back to the places of the pairs as given.
+int rank_core(mfsgd_handle* h, const float* host_rows, int32_t n_rows, const int32_t* users, const int32_t* items,
+              int64_t n, const int32_t* excl_u, const int32_t* excl_i, int64_t n_excl, int32_t* out_rank) {
+    if (n < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: n is negative");
+    if (n_excl < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: n_excl is negative");
+    if (n > 0 && (!users || !items || !out_rank))
+        return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: users, items or out_rank is null");
+    if (n_excl > 0 && (!excl_u || !excl_i)) return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: an exclusion array is null");
+    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "rank_items: single-partition handles only");
+    const int32_t I = h->cfg.n_items;
+    for (int64_t x = 0; x < n; ++x)
+        if (users[x] < 0 || users[x] >= n_rows || items[x] < 0 || items[x] >= I)
+            return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: pair " + std::to_string(x) + " out of range");
+    // a slot per distinct user, and how many exclusion pairs are theirs
+    std::vector<int32_t> slot_of_user((size_t)n_rows, -1), row_of_slot;
+    std::vector<long long> off{0};
+    for (int64_t x = 0; x < n; ++x) {
+        int32_t& s = slot_of_user[(size_t)users[x]];
+        if (s < 0) {
+            s = (int32_t)row_of_slot.size();
+            row_of_slot.push_back(users[x]);
+            off.push_back(0);
+        }
+        ++off[(size_t)s + 1];
+    }
+    const int32_t n_slots = (int32_t)row_of_slot.size();
+    // The slots in the order of their pair counts, most first: a workgroup takes neighbouring slots and passes over Q
+    // once per round of its user with the most pairs, so users with many pairs belong together.
+    {
+        std::vector<int32_t> order((size_t)n_slots);
+        for (int32_t s = 0; s < n_slots; ++s) order[(size_t)s] = s;
+        std::stable_sort(order.begin(), order.end(),
+                         [&off](int32_t a, int32_t b) { return off[(size_t)a + 1] > off[(size_t)b + 1]; });
+        std::vector<int32_t> rows_sorted((size_t)n_slots);
+        std::vector<long long> off_sorted((size_t)n_slots + 1, 0);
+        for (int32_t s = 0; s < n_slots; ++s) {
+            rows_sorted[(size_t)s] = row_of_slot[(size_t)order[(size_t)s]];
+            off_sorted[(size_t)s + 1] = off[(size_t)order[(size_t)s] + 1];
+            slot_of_user[(size_t)rows_sorted[(size_t)s]] = s;
+        }
+        row_of_slot.swap(rows_sorted);
+        off.swap(off_sorted);
+    }
+    int64_t kept = 0;
+    for (int64_t x = 0; x < n_excl; ++x) {
+        if (excl_u[x] < 0 || excl_u[x] >= n_rows || excl_i[x] < 0 || excl_i[x] >= I)
+            return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: excluded pair " + std::to_string(x) + " out of range");
+        kept += slot_of_user[(size_t)excl_u[x]] >= 0 ? 1 : 0;
+    }
+    if (kept > (int64_t)UINT32_MAX)
+        return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: more than 2^32 - 1 excluded pairs of the users asked about");
+    if (n == 0) return MFSGD_OK;
+    if (h->where == mfsgd_handle::Where::None)  // (asked here: factors_to_device wants a device first)
+        return fail(h, MFSGD_ERR_STATE, "rank_items: factors not initialised");
+    int rc = factors_to_device(h);
+    if (rc) return rc;
+    // counting sort: the pairs of slot s at off[s] .. off[s + 1], in the order given; place[x] = where pair x went
+    for (int32_t s = 0; s < n_slots; ++s) off[(size_t)s + 1] += off[(size_t)s];
+    std::vector<int32_t> grouped((size_t)n), ranks((size_t)n);
+    std::vector<int64_t> place((size_t)n);
+    {
+        std::vector<long long> next(off.begin(), off.end() - 1);
+        for (int64_t x = 0; x < n; ++x) {
+            place[(size_t)x] = next[(size_t)slot_of_user[(size_t)users[x]]]++;
+            grouped[(size_t)place[(size_t)x]] = items[x];
+        }
+    }
+    std::vector<int32_t> cut{0};
+    int64_t max_pairs = 0;
+    for (int32_t s = 0; s < n_slots;) {
+        int32_t s1 = s + 1;
+        while (s1 < n_slots && off[(size_t)s1 + 1] - off[(size_t)s] <= kRankChunk) ++s1;
+        max_pairs = std::max<int64_t>(max_pairs, off[(size_t)s1] - off[(size_t)s]);
+        cut.push_back(s1);
+        s = s1;
+    }
+    auto bad = [h](hipError_t e) { return serve_fail(h, "rank_items: ", e); };
+    DevBuf d_rows, d_slot_rows, d_off, d_items, d_out, ex_slot, ex_off, ex_items, temp;
+    if (host_rows) {
+        const int k = h->cfg.k, kp = h->geo.kp;
+        std::vector<float> padded((size_t)n_rows * kp, 0.0f);
+        for (int64_t x = 0; x < n_rows; ++x) std::memcpy(&padded[(size_t)x * kp], host_rows + x * k, sizeof(float) * (size_t)k);
+        if ((rc = upload(h, d_rows, padded))) return rc;
+    }
+    const float* P = host_rows ? d_rows.as<const float>() : h->dP.as<const float>();
+    RecommendExcl ex;  // built once for all launches; none when no pair belongs to a user asked about
+    if (kept > 0 && (rc = exclusions_to_device(h, slot_of_user, n_slots, excl_u, excl_i, n_excl, kept, ex_slot, ex_off,
+                                               ex_items, temp, ex, "rank_items")))
+        return rc;
+    if ((rc = upload(h, d_slot_rows, row_of_slot))) return rc;
+    if ((rc = upload(h, d_off, off))) return rc;
+    if ((rc = dev_alloc(h, d_items, sizeof(int32_t) * (size_t)max_pairs))) return rc;
+    if ((rc = dev_alloc(h, d_out, sizeof(int32_t) * (size_t)max_pairs))) return rc;
+    for (size_t b = 0; b + 1 < cut.size(); ++b) {
+        const int32_t b0 = cut[b], nb = cut[b + 1] - b0;
+        const long long base = off[(size_t)b0];
+        const size_t bytes = sizeof(int32_t) * (size_t)(off[(size_t)(b0 + nb)] - base);
+        RecommendExcl exb = ex;
+        if (exb.off) exb.off += b0;
+        HIPCHK_OR(bad, hipMemcpyAsync(d_items.get(), grouped.data() + base, bytes, hipMemcpyHostToDevice, h->stream));
+        HIPCHK_OR(bad, launch_rank_items(h->geo.L, P, h->dQ.as<const float>(), d_slot_rows.as<const int32_t>() + b0, nb,
+                                         d_off.as<const long long>() + b0, base, d_items.as<const int32_t>(), I, exb,
+                                         d_out.as<int32_t>(), h->stream));
+        HIPCHK_OR(bad, hipMemcpyAsync(ranks.data() + base, d_out.get(), bytes, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // the staging buffers are reused
+    }
+    for (int64_t x = 0; x < n; ++x) out_rank[x] = ranks[(size_t)place[(size_t)x]];
+    return MFSGD_OK;
+}
+
+int metrics_fail(int code, const std::string& msg) {
+    g_create_error = "ranking_metrics: " + msg;
+    return code;
+}
+
+}  // namespace
+
+int mfsgd_rank_items(mfsgd_handle* h, const int32_t* users, const int32_t* items, int64_t n, const int32_t* excl_u,
+                     const int32_t* excl_i, int64_t n_excl, int32_t* out_rank) {
+    if (!h) return MFSGD_ERR_INVALID_ARG;
+    try {
+        return rank_core(h, nullptr, h->cfg.n_users, users, items, n, excl_u, excl_i, n_excl, out_rank);
+    } catch (const std::bad_alloc&) {
+        return fail(h, MFSGD_ERR_OOM, "rank_items: out of host memory");
+    }
+}
+
+int mfsgd_rank_items_rows(mfsgd_handle* h, const float* rows, int32_t n_rows, const int32_t* row_of_pair,
+                          const int32_t* items, int64_t n, const int32_t* excl_row, const int32_t* excl_item,
+                          int64_t n_excl, int32_t* out_rank) {
+    if (!h) return MFSGD_ERR_INVALID_ARG;
+    if (n_rows < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: n_rows is negative");
+    if (n_rows > 0 && !rows) return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: rows is null");
+    try {
+        return rank_core(h, rows, n_rows, row_of_pair, items, n, excl_row, excl_item, n_excl, out_rank);
+    } catch (const std::bad_alloc&) {
+        return fail(h, MFSGD_ERR_OOM, "rank_items: out of host memory");
+    }
+}
+
+int mfsgd_ranking_metrics_from_ranks(const int32_t* users, const int32_t* ranks, int64_t n, int32_t topn,
+                                     mfsgd_ranking_metrics* out) {
+    if (!out) return metrics_fail(MFSGD_ERR_INVALID_ARG, "out is null");
+    if (n < 0) return metrics_fail(MFSGD_ERR_INVALID_ARG, "n is negative");
+    if (topn < 1) return metrics_fail(MFSGD_ERR_INVALID_ARG, "topn is below 1");
+    if (n > 0 && (!users || !ranks)) return metrics_fail(MFSGD_ERR_INVALID_ARG, "users or ranks is null");
+    for (int64_t x = 0; x < n; ++x)
+        if (ranks[x] < 0) return metrics_fail(MFSGD_ERR_INVALID_ARG, "rank " + std::to_string(x) + " is negative");
+    *out = mfsgd_ranking_metrics{};
+    out->n_pairs = n;
+    if (n == 0) return MFSGD_OK;
+    try {
+        // ascending user, and inside a user ascending rank: every sum below has one order whatever the caller's was
+        std::vector<std::pair<int32_t, int32_t>> ur((size_t)n);
+        for (int64_t x = 0; x < n; ++x) ur[(size_t)x] = {users[x], ranks[x]};
+        std::sort(ur.begin(), ur.end());
+        std::vector<double> idcg{0.0};  // [m]: the DCG of m hits in the first m places
+        double hit = 0, prec = 0, rec = 0, ndcg = 0, mrr = 0;
+        int64_t n_users = 0;
+        for (size_t a = 0; a < ur.size();) {
+            size_t b = a;
+            int64_t hits = 0;
+            double dcg = 0.0;
+            for (; b < ur.size() && ur[b].first == ur[a].first; ++b)
+                if (ur[b].second < topn) {
+                    ++hits;
+                    dcg += 1.0 / std::log2((double)ur[b].second + 2.0);
+                }
+            const size_t m = std::min<size_t>(b - a, (size_t)topn);
+            while (idcg.size() <= m) idcg.push_back(idcg.back() + 1.0 / std::log2((double)idcg.size() + 1.0));
+            hit += hits > 0 ? 1.0 : 0.0;
+            prec += (double)hits / (double)topn;
+            rec += (double)hits / (double)(b - a);
+            ndcg += dcg / idcg[m];
+            mrr += 1.0 / ((double)ur[a].second + 1.0);  // (the user's lowest rank comes first)
+            ++n_users;
+            a = b;
+        }
+        out->n_users = n_users;
+        out->hit_rate = hit / (double)n_users;
+        out->precision = prec / (double)n_users;
+        out->recall = rec / (double)n_users;
+        out->ndcg = ndcg / (double)n_users;
+        out->mrr = mrr / (double)n_users;
+    } catch (const std::bad_alloc&) {
+        return metrics_fail(MFSGD_ERR_OOM, "out of host memory");
+    }
+    return MFSGD_OK;
+}
+
+int mfsgd_evaluate_ranking(mfsgd_handle* h, const int32_t* users, const int32_t* items, int64_t n, int32_t topn,
+                           const int32_t* excl_u, const int32_t* excl_i, int64_t n_excl, mfsgd_ranking_metrics* out,
+                           int32_t* out_rank) {
+    if (!h) return MFSGD_ERR_INVALID_ARG;
+    if (topn < 1) return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: topn is below 1");
+    if (!out) return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: the metrics struct is null");
+    try {
+        std::vector<int32_t> own;
+        if (!out_rank && n > 0) {
+            own.resize((size_t)n);
+            out_rank = own.data();
+        }
+        int rc = rank_core(h, nullptr, h->cfg.n_users, users, items, n, excl_u, excl_i, n_excl, out_rank);
+        if (rc) return rc;
+        rc = mfsgd_ranking_metrics_from_ranks(users, out_rank, n, topn, out);
+        if (rc) return fail(h, rc, g_create_error);
+        return MFSGD_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(h, MFSGD_ERR_OOM, "rank_items: out of host memory");
+    }
 }
 
 namespace {

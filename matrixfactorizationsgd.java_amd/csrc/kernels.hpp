@@ -87,4 +87,13 @@ hipError_t recommend_excl_filter(const int32_t* slot_of_user, const int32_t* u, 
 hipError_t recommend_excl_lists(unsigned long long* keys, unsigned long long* keys_tmp, int64_t n, int32_t n_slots,
                                 unsigned* n_distinct, long long* off, int32_t* items, DevBuf& temp, hipStream_t st);
 
+// rank.hip.  Ranks of held-out items: slot s (of n_slots) is row rows[s] of P (kp-padded rows), its pairs are
+// items[off[s] - base .. off[s + 1] - base), and out[...] at the same places receives, per pair, the number of items
+// that come before it in that row's recommendation order (recommend.hip's), the items of the slot's exclusion list
+// left out (ex.off / ex.items indexed by the same slots; ex.off == nullptr: none; ex.slot is not read).  Every item is
+// a row of Q and every off[s] - base .. off[s + 1] - base lies inside items and out: the caller checks.
+hipError_t launch_rank_items(int L, const float* P, const float* Q, const int32_t* rows, int n_slots, const long long* off,
+                             long long base, const int32_t* items, int32_t n_items, const RecommendExcl& ex,
+                             int32_t* out, hipStream_t st);
+
 }  // namespace mfsgd

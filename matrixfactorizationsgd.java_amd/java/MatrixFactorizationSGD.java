@@ -126,6 +126,54 @@ public final class MatrixFactorizationSGD implements AutoCloseable {
         return out;
     }
 
+    /**
+     * For each held-out pair (u[x], i[x]) the number of items that come before i[x] in u[x]'s recommendation order
+     * (0: it would be recommended first), the pairs (exclU[x], exclI[x]) not competing -- the index of i[x] in the row
+     * recommend(u[x], items, exclU, exclI) returns.  The held-out item itself is ranked even when a pair excludes it.
+     */
+    public int[] rankItems(int[] u, int[] i, int[] exclU, int[] exclI) {
+        if (u.length != i.length || exclU.length != exclI.length) throw new IllegalArgumentException("length mismatch");
+        int[] ranks = new int[u.length];
+        nativeRankItems(handle, u, i, exclU, exclI, ranks);
+        return ranks;
+    }
+
+    /** rankItems for rows (n x k) that are not in the model, such as foldIn's: row and exclRow index rows. */
+    public int[] rankItemsRows(float[] rows, int[] row, int[] i, int[] exclRow, int[] exclItem) {
+        if (row.length != i.length || exclRow.length != exclItem.length || rows.length % k != 0)
+            throw new IllegalArgumentException("length mismatch");
+        int[] ranks = new int[row.length];
+        nativeRankItemsRows(handle, rows, row, i, exclRow, exclItem, ranks);
+        return ranks;
+    }
+
+    /** What evaluateRanking returns: means over the users that have a held-out pair, and the rank of every pair. */
+    public static final class RankingMetrics {
+        public long nPairs, nUsers;
+        public double hitRate, precision, recall, ndcg, mrr;
+        public int[] ranks;
+    }
+
+    /**
+     * rankItems(u, i, exclU, exclI) and the top-N metrics of those ranks at cut-off topN: hit rate, precision, recall
+     * and NDCG at topN, and MRR.  The held-out pairs must be distinct for the figures to mean anything.
+     */
+    public RankingMetrics evaluateRanking(int[] u, int[] i, int topN, int[] exclU, int[] exclI) {
+        if (u.length != i.length || exclU.length != exclI.length) throw new IllegalArgumentException("length mismatch");
+        RankingMetrics m = new RankingMetrics();
+        m.ranks = new int[u.length];
+        double[] v = new double[7];
+        nativeEvaluateRanking(handle, u, i, topN, exclU, exclI, v, m.ranks);
+        m.nPairs = (long) v[0];
+        m.nUsers = (long) v[1];
+        m.hitRate = v[2];
+        m.precision = v[3];
+        m.recall = v[4];
+        m.ndcg = v[5];
+        m.mrr = v[6];
+        return m;
+    }
+
     public double rmse() {
         return nativeRmse(handle);
     }
@@ -243,6 +291,11 @@ public final class MatrixFactorizationSGD implements AutoCloseable {
                                                         float[] scores);
     private static native void nativeFoldIn(long h, long[] rowPtr, int[] items, float[] ratings, int epochs, float[] init,
                                             long seed, float[] rows);
+    private static native void nativeRankItems(long h, int[] u, int[] i, int[] exclU, int[] exclI, int[] ranks);
+    private static native void nativeRankItemsRows(long h, float[] rows, int[] row, int[] i, int[] exclRow, int[] exclItem,
+                                                   int[] ranks);
+    private static native void nativeEvaluateRanking(long h, int[] u, int[] i, int topN, int[] exclU, int[] exclI,
+                                                     double[] metrics7, int[] ranks);
     private static native void nativeRecommendRows(long h, float[] rows, int topN, int[] exclRow, int[] exclItem, int[] items,
                                                    float[] scores);
     // DSGD (mfsgd_dsgd_*, mfsgd_set_item_partition, mfsgd_init_p_offset)

@@ -256,6 +256,72 @@ JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeFoldIn(JNIEnv* env, jcl
     throw_status(env, H(h), rc);
 }
 
+namespace {
+
+// Body of the three rank natives: rows == nullptr ranks against P, metrics7 != nullptr adds the metrics at topn.
+void rank_native(JNIEnv* env, jlong h, jfloatArray rows, jintArray u, jintArray i, jint topn, jintArray excl_u,
+                 jintArray excl_i, jdoubleArray metrics7, jintArray ranks, const char* what) {
+    if (!u || !i || !excl_u || !excl_i || !ranks) return throw_new(env, "java/lang/NullPointerException", what);
+    int32_t n_users = 0, n_items = 0, k = 0;
+    int rc = mfsgd_get_dims(H(h), &n_users, &n_items, &k);
+    if (rc != MFSGD_OK) return throw_status(env, H(h), rc);
+    const jsize n = env->GetArrayLength(u);
+    const jsize ne = env->GetArrayLength(excl_u);
+    const jsize nf = rows ? env->GetArrayLength(rows) : 0;
+    if (env->GetArrayLength(i) != n || env->GetArrayLength(excl_i) != ne || env->GetArrayLength(ranks) < n ||
+        (rows && (k < 1 || nf % k != 0)) || (metrics7 && env->GetArrayLength(metrics7) < 7))
+        return throw_new(env, "java/lang/IllegalArgumentException", "rankItems: length mismatch");
+    // copies, not pins: the call launches kernels and waits for them
+    auto cf = alloc<float>(env, (size_t)nf);
+    auto cu = alloc<int32_t>(env, (size_t)n);
+    auto ci = alloc<int32_t>(env, (size_t)n);
+    auto ceu = alloc<int32_t>(env, (size_t)ne);
+    auto cei = alloc<int32_t>(env, (size_t)ne);
+    auto cr = alloc<int32_t>(env, (size_t)n);
+    if (!cf || !cu || !ci || !ceu || !cei || !cr) return;
+    if (rows) env->GetFloatArrayRegion(rows, 0, nf, cf.get());
+    env->GetIntArrayRegion(u, 0, n, reinterpret_cast<jint*>(cu.get()));
+    env->GetIntArrayRegion(i, 0, n, reinterpret_cast<jint*>(ci.get()));
+    env->GetIntArrayRegion(excl_u, 0, ne, reinterpret_cast<jint*>(ceu.get()));
+    env->GetIntArrayRegion(excl_i, 0, ne, reinterpret_cast<jint*>(cei.get()));
+    if (env->ExceptionCheck()) return;
+    mfsgd_ranking_metrics m = {};
+    if (rows)
+        rc = mfsgd_rank_items_rows(H(h), cf.get(), nf / k, cu.get(), ci.get(), (int64_t)n, ceu.get(), cei.get(), (int64_t)ne,
+                                   cr.get());
+    else if (metrics7)
+        rc = mfsgd_evaluate_ranking(H(h), cu.get(), ci.get(), (int64_t)n, topn, ceu.get(), cei.get(), (int64_t)ne, &m, cr.get());
+    else
+        rc = mfsgd_rank_items(H(h), cu.get(), ci.get(), (int64_t)n, ceu.get(), cei.get(), (int64_t)ne, cr.get());
+    if (rc == MFSGD_OK && n > 0) env->SetIntArrayRegion(ranks, 0, n, reinterpret_cast<const jint*>(cr.get()));
+    if (rc == MFSGD_OK && metrics7) {
+        const jdouble v[7] = {(jdouble)m.n_pairs, (jdouble)m.n_users, m.hit_rate, m.precision, m.recall, m.ndcg, m.mrr};
+        env->SetDoubleArrayRegion(metrics7, 0, 7, v);
+    }
+    throw_status(env, H(h), rc);
+}
+
+}  // namespace
+
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeRankItems(JNIEnv* env, jclass, jlong h, jintArray u, jintArray i,
+                                                                   jintArray excl_u, jintArray excl_i, jintArray ranks) {
+    rank_native(env, h, nullptr, u, i, 0, excl_u, excl_i, nullptr, ranks, "rankItems");
+}
+
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeRankItemsRows(JNIEnv* env, jclass, jlong h, jfloatArray rows,
+                                                                       jintArray row, jintArray i, jintArray excl_row,
+                                                                       jintArray excl_item, jintArray ranks) {
+    if (!rows) return throw_new(env, "java/lang/NullPointerException", "rankItemsRows");
+    rank_native(env, h, rows, row, i, 0, excl_row, excl_item, nullptr, ranks, "rankItemsRows");
+}
+
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeEvaluateRanking(JNIEnv* env, jclass, jlong h, jintArray u, jintArray i,
+                                                                         jint topn, jintArray excl_u, jintArray excl_i,
+                                                                         jdoubleArray metrics7, jintArray ranks) {
+    if (!metrics7) return throw_new(env, "java/lang/NullPointerException", "evaluateRanking");
+    rank_native(env, h, nullptr, u, i, topn, excl_u, excl_i, metrics7, ranks, "evaluateRanking");
+}
+
 JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeRecommendRows(JNIEnv* env, jclass, jlong h, jfloatArray rows, jint topn,
                                                                        jintArray excl_row, jintArray excl_item, jintArray items,
                                                                        jfloatArray scores) {

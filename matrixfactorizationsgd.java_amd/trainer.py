@@ -75,6 +75,29 @@ def dsgd_plan_ex(deg_user, deg_item, world, parts_per_rank=1, k=64, chain_crit=0
                         threshold=int(info[3]))
 
 
+def ranking_metrics(users, ranks, topn):
+    """mfsgd_ranking_metrics_from_ranks (host only, needs no model and no GPU): dict(n_pairs, n_users, hit_rate,
+    precision, recall, ndcg, mrr) of held-out pairs given as (user, rank of the item) at cut-off topn -- means over the
+    users that have a pair.  The pairs must be distinct for the figures to mean anything."""
+    uu, rr = _i32(users), _i32(ranks)
+    if uu.shape != rr.shape or uu.ndim != 1:
+        raise ValueError("users and ranks must have the same 1-d shape")
+    lib = _lib.load_library()
+    out = _lib.RankingMetrics()
+    rc = lib.mfsgd_ranking_metrics_from_ranks(_p(uu, C.c_int32), _p(rr, C.c_int32), uu.size, int(topn), C.byref(out))
+    if rc != 0:
+        raise MfsgdError(rc, lib.mfsgd_last_error(None).decode())
+    return out.as_dict()
+
+
+def _pairs(a, b, what):
+    """Two int32 1-d arrays of one length (None: no pairs)."""
+    aa, bb = (np.empty(0, np.int32),) * 2 if a is None else (_i32(a), _i32(b))
+    if aa.shape != bb.shape or aa.ndim != 1:
+        raise ValueError(f"{what} must be two 1-d arrays of the same length")
+    return aa, bb
+
+
 class MatrixFactorizationSGD:
     def __init__(self, users, items, k, lr, lam, seed, *, device=0, blocks=0, waves=0,
                  n_parts=0, host_threads=0, flags=0):
@@ -257,6 +280,46 @@ class MatrixFactorizationSGD:
                                                    _p(ei, C.c_int32), er.size, _p(items, C.c_int32),
                                                    _p(scores, C.c_float)))
         return items, scores
+
+    def rank_items(self, u, i, exclude=None):
+        """int32[n]: for each held-out pair (u[x], i[x]) the number of items that come before i[x] in u[x]'s
+        recommendation order (0 = it would be recommended first) -- its index in recommend(u[x], items, exclude)'s row.
+        exclude = (u, i): pairs that do not compete (for instance the training ratings); the held-out item itself is
+        ranked even when a pair excludes it.  Nothing is sorted: the device counts the items that beat each pair."""
+        uu, ii = _pairs(np.atleast_1d(u), np.atleast_1d(i), "u and i")
+        eu, ei = _pairs(*((None, None) if exclude is None else exclude), "exclude")
+        ranks = np.empty(uu.size, np.int32)
+        self._check(self._lib.mfsgd_rank_items(self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32), uu.size,
+                                               _p(eu, C.c_int32), _p(ei, C.c_int32), eu.size, _p(ranks, C.c_int32)))
+        return ranks
+
+    def rank_items_rows(self, rows, row, i, exclude=None):
+        """rank_items() for rows that are not in the model (for instance what fold_in returned): pair x is
+        (rows[row[x]], i[x]); exclude = (row, item), row indexing `rows`."""
+        rows = _f32(rows)
+        if rows.ndim != 2 or rows.shape[1] != self.k:
+            raise ValueError("rows must be n_rows x k")
+        rr, ii = _pairs(np.atleast_1d(row), np.atleast_1d(i), "row and i")
+        er, ei = _pairs(*((None, None) if exclude is None else exclude), "exclude")
+        ranks = np.empty(rr.size, np.int32)
+        self._check(self._lib.mfsgd_rank_items_rows(self._handle(), _p(rows, C.c_float), rows.shape[0], _p(rr, C.c_int32),
+                                                    _p(ii, C.c_int32), rr.size, _p(er, C.c_int32), _p(ei, C.c_int32),
+                                                    er.size, _p(ranks, C.c_int32)))
+        return ranks
+
+    def evaluate_ranking(self, u, i, topn, exclude=None):
+        """rank_items(u, i, exclude) and ranking_metrics(u, ranks, topn) in one call: the metrics dict, which also
+        carries "ranks" (int32[n])."""
+        uu, ii = _pairs(np.atleast_1d(u), np.atleast_1d(i), "u and i")
+        eu, ei = _pairs(*((None, None) if exclude is None else exclude), "exclude")
+        ranks = np.empty(uu.size, np.int32)
+        out = _lib.RankingMetrics()
+        self._check(self._lib.mfsgd_evaluate_ranking(self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32), uu.size,
+                                                     int(topn), _p(eu, C.c_int32), _p(ei, C.c_int32), eu.size,
+                                                     C.byref(out), _p(ranks, C.c_int32)))
+        res = out.as_dict()
+        res["ranks"] = ranks
+        return res
 
     # -- schedule introspection (tests, bench) -----------------------------------
     def schedule_info(self, part=0):
