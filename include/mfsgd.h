@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking (additions: no existing call changed) */
+#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver (additions: no existing call changed) */
 
 typedef enum mfsgd_status {
     MFSGD_OK = 0,
@@ -229,6 +229,39 @@ int mfsgd_ranking_metrics_from_ranks(const int32_t* users, const int32_t* ranks,
 int mfsgd_evaluate_ranking(mfsgd_handle* h, const int32_t* users, const int32_t* items, int64_t n, int32_t topn,
                            const int32_t* excl_u, const int32_t* excl_i, int64_t n_excl,
                            mfsgd_ranking_metrics* out, int32_t* out_rank);
+
+/* ---- lr and lambda on a live model; learning-rate schedules --------------------------------------------------------
+ * mfsgd_set_hyper gives the handle another lr and lambda without rebuilding anything: the two numbers sit in the
+ * schedules' step entries (lr * r and the decay factor 1 - lr * lambda) and nowhere else in them, so the entries are
+ * re-baked in place, on the device where they live there (csrc/rehyper.hip) and on the host where they live there.
+ * Afterwards every schedule is byte for byte what mfsgd_set_ratings would have built on a handle created with the new
+ * values, and everything that reads the handle's lr / lambda (training, mfsgd_fold_in_users, a later rebuild) uses
+ * them.  The factors are not touched; the identity of the rating set is kept (the same triples again are still
+ * recognised).  The call waits for the handle's stream first, and allocates no device memory that it does not free.
+ * Before any ratings it only changes the configuration.  n_parts > 1: all partitions are rewritten; no
+ * mfsgd_part_train on a caller's stream may be in flight, and every rank of a ring must make the same call (the
+ * update of a rating must not depend on the rank that applies it).
+ * MFSGD_ERR_INVALID_ARG ("set_hyper: ..."): a NaN.  Should the rewrite itself fail (a HIP error), the schedules are
+ * dropped and mfsgd_set_ratings has to be called again.                                                              */
+int mfsgd_set_hyper(mfsgd_handle* h, float lr, float lambda);
+int mfsgd_get_hyper(const mfsgd_handle* h, float* lr, float* lambda);   /* either may be NULL */
+/* epochs passes, epoch e at lr[e] and lambda[e] (lambda == NULL: the handle's current one throughout).
+ * rmse_per_epoch nullable as in mfsgd_train.  Afterwards the handle holds the last epoch's values.  Nothing is re-baked
+ * between two epochs whose pair of values is bit-identical.  Checked before any device work (MFSGD_ERR_INVALID_ARG,
+ * "train_schedule: ..."): negative epochs, a null lr with epochs > 0, a NaN anywhere in the arrays.  epochs == 0 is
+ * MFSGD_OK; otherwise MFSGD_ERR_STATE / MFSGD_ERR_NO_DEVICE as mfsgd_train.  A change of values inside the call is
+ * mfsgd_set_hyper: should its rewrite fail, the call returns that error, the epochs before it stay applied, and the
+ * handle holds the new values but no schedules (mfsgd_set_ratings again). */
+int mfsgd_train_schedule(mfsgd_handle* h, int32_t epochs, const float* lr, const float* lambda, double* rmse_per_epoch);
+/* Bold driver.  prev = RMSE before the first epoch (one read-only pass).  Epoch e runs at the handle's current lr,
+ * reported in lr_used[e]; rmse[e] is the RMSE after it.  Then, in fp32: lr = lr * up if rmse[e] < prev (strictly),
+ * else lr = lr * down (a NaN RMSE therefore shrinks).  prev = rmse[e].  Nothing is rolled back.
+ * The handle keeps the lr the next epoch would use.  lr_used and rmse_per_epoch: `epochs` entries, both required.
+ * MFSGD_ERR_INVALID_ARG ("bold_driver: ..."): negative epochs, up or down NaN or not above zero, a null array with
+ * epochs > 0.  epochs == 0 is MFSGD_OK; otherwise MFSGD_ERR_STATE / MFSGD_ERR_NO_DEVICE as mfsgd_train.  A failed
+ * rewrite between two epochs ends the call as it ends mfsgd_train_schedule: the epochs so far stay applied (lr_used
+ * and rmse_per_epoch are valid up to there), the handle holds the next rate but no schedules. */
+int mfsgd_train_bold_driver(mfsgd_handle* h, int32_t epochs, float up, float down, float* lr_used, double* rmse_per_epoch);
 
 /* Timed variant used by bench.py: runs `epochs` training passes bracketed by
  * HIP events on the handle's stream and returns the elapsed device time and

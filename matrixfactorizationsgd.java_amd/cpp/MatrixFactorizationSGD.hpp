@@ -151,6 +151,33 @@ class MatrixFactorizationSGD {
         return out;
     }
 
+    // void setHyper(float lr, float lambda): another lr and lambda for the live model; the schedules are re-baked in
+    // place, nothing is rebuilt, the factors stay
+    void setHyper(float lr, float lambda) { check(mfsgd_set_hyper(h_, lr, lambda)); }
+    // {lr, lambda} the model holds now
+    std::pair<float, float> hyper() {
+        float lr = 0.f, lambda = 0.f;
+        check(mfsgd_get_hyper(h_, &lr, &lambda));
+        return {lr, lambda};
+    }
+    // double[] trainSchedule(float[] lr, float[] lambda /*nullable*/): one epoch per entry over the ratings of the last
+    // train() call, epoch e at lr[e] and lambda[e]; the RMSE after each epoch.  The model keeps the last epoch's values
+    std::vector<double> trainSchedule(const std::vector<float>& lr, const std::vector<float>* lambda = nullptr) {
+        if (lambda && lambda->size() != lr.size()) throw std::invalid_argument("length mismatch");
+        std::vector<double> rmse(lr.size());
+        check(mfsgd_train_schedule(h_, (int32_t)lr.size(), lr.data(), lambda ? lambda->data() : nullptr, rmse.data()));
+        return rmse;
+    }
+    // double[] trainBoldDriver(int epochs, float up, float down, float[] lrUsed): the rate grows by `up` after an epoch
+    // that lowered the RMSE and shrinks by `down` otherwise; {lrUsed, rmse}, one entry per epoch each
+    std::pair<std::vector<float>, std::vector<double>> trainBoldDriver(int epochs, float up = 1.05f, float down = 0.5f) {
+        if (epochs < 0) throw std::invalid_argument("negative epochs");
+        std::vector<float> used((size_t)epochs);
+        std::vector<double> rmse((size_t)epochs);
+        check(mfsgd_train_bold_driver(h_, epochs, up, down, used.data(), rmse.data()));
+        return {std::move(used), std::move(rmse)};
+    }
+
     std::pair<std::vector<float>, std::vector<float>> factors() {
         std::vector<float> p((size_t)users_ * k_), q((size_t)items_ * k_);
         check(mfsgd_get_factors(h_, p.data(), q.data()));

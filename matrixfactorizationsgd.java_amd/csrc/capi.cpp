@@ -971,6 +971,168 @@ int mfsgd_train_timed(mfsgd_handle* h, int32_t epochs, double* elapsed_ms, int64
     return check_abort_strict(h, p);  // a timing of launches that did nothing would be meaningless
 }
 
+// lr and lambda on a live handle ---------------------------------------------------
+// The schedules keep their structure; the entries are re-baked wherever they live ("Changing lr and
+// lambda"): the device copy by rehyper.hip on the handle's stream, the host copy by rehyper_schedule, both at once.
+// The cached training graphs carry lr and c as kernel arguments: they are dropped and captured again on demand.
+static bool same_bits(float a, float b) { return std::memcmp(&a, &b, sizeof a) == 0; }
+
+static int apply_hyper(mfsgd_handle* h, float lr, float lambda) {
+    if (same_bits(lr, h->cfg.lr) && same_bits(lambda, h->cfg.lambda)) return MFSGD_OK;
+    if (!h->have_ratings) {
+        h->cfg.lr = lr;
+        h->cfg.lambda = lambda;
+        return MFSGD_OK;
+    }
+    // whatever goes wrong from here on leaves entries half rewritten: the schedules are dropped then, and the next
+    // mfsgd_set_ratings builds them again, with the new values
+    auto broken = [&](int code, const std::string& msg) {
+        if (h->device_ready) (void)hipDeviceSynchronize();
+        h->parts.clear();
+        h->have_ratings = false;
+        h->cfg.lr = lr;
+        h->cfg.lambda = lambda;
+        return fail(h, code, "set_hyper: " + msg + " (the schedules were dropped: call mfsgd_set_ratings again)");
+    };
+    try {
+        if (h->device_ready) {
+            HIPCHK(h, hipSetDevice(h->cfg.device));
+            // DSGD partitions are trained on the callers' streams: the header rules out launches in flight, this
+            // makes sure of it before their graphs go
+            HIPCHK(h, h->n_parts > 1 ? hipDeviceSynchronize() : hipStreamSynchronize(h->stream));
+        }
+        const float c = 1.0f - lr * lambda;
+        std::vector<DevBuf> temps;  // descriptors of a part that is not on the device yet; freed before this returns
+        bool launched = false;
+        for (Part& p : h->parts) {
+            Schedule& s = p.sched;
+            Entry* d_entries = p.on_device ? p.d_entries.as<Entry>() : static_cast<Entry*>(s.dev.buf.entries);
+            if (!d_entries || s.n_entry_recs == 0 || s.cells.empty()) continue;
+            const CellDesc* d_cells = p.d_cells.as<const CellDesc>();
+            const SubDesc* d_subs = p.on_device ? p.d_subs.as<const SubDesc>() : static_cast<const SubDesc*>(s.dev.buf.subs);
+            if (!p.on_device) {  // the device packer's buffers, not adopted yet: the descriptors are still on the host only
+                temps.emplace_back();
+                if (const int rc = upload(h, temps.back(), s.cells)) return broken(rc, "the chunk descriptors did not reach the device: " + h->err);
+                d_cells = temps.back().as<const CellDesc>();
+                if (!d_subs) {
+                    temps.emplace_back();
+                    if (const int rc = upload(h, temps.back(), s.subs)) return broken(rc, "the sub-cell tables did not reach the device: " + h->err);
+                    d_subs = temps.back().as<const SubDesc>();
+                }
+            }
+            const hipError_t e = launch_rehyper(d_cells, d_subs, d_entries, (int64_t)s.cells.size(), s.n_entry_recs, s.W,
+                                                s.geo.G, lr, c, h->stream);
+            if (e != hipSuccess) return broken(MFSGD_ERR_HIP, std::string("the re-bake kernel could not be launched: ") + hipGetErrorString(e));
+            launched = true;
+        }
+        for (Part& p : h->parts) {
+            Schedule& s = p.sched;
+            if (s.entries.empty()) continue;
+            if (!s.subs.empty()) {
+                rehyper_schedule(s, lr, lambda, h->cfg.host_threads);
+            } else {
+                // (a host copy of a device-packed schedule whose sub-cell tables never came down: it is a copy made
+                // on demand, and the next demand makes it again, from the re-baked device arrays)
+                s.entries = PodVec<Entry>();
+            }
+        }
+        if (launched) {
+            const hipError_t e = hipStreamSynchronize(h->stream);
+            if (e != hipSuccess) return broken(MFSGD_ERR_HIP, std::string("the re-bake kernel failed: ") + hipGetErrorString(e));
+        }
+        for (Part& p : h->parts) p.drop_graphs();
+        h->cfg.lr = lr;
+        h->cfg.lambda = lambda;
+        return MFSGD_OK;
+    } catch (const std::bad_alloc&) {
+        return broken(MFSGD_ERR_OOM, "out of host memory");
+    }
+}
+
+static bool is_nan(float x) { return !(x == x); }
+
+int mfsgd_set_hyper(mfsgd_handle* h, float lr, float lambda) {
+    if (!h) return MFSGD_ERR_INVALID_ARG;
+    if (is_nan(lr) || is_nan(lambda)) return fail(h, MFSGD_ERR_INVALID_ARG, "set_hyper: lr / lambda is NaN");
+    return apply_hyper(h, lr, lambda);
+}
+
+int mfsgd_get_hyper(const mfsgd_handle* h, float* lr, float* lambda) {
+    if (!h) return MFSGD_ERR_INVALID_ARG;
+    if (lr) *lr = h->cfg.lr;
+    if (lambda) *lambda = h->cfg.lambda;
+    return MFSGD_OK;
+}
+
+int mfsgd_train_schedule(mfsgd_handle* h, int32_t epochs, const float* lr, const float* lambda, double* rmse_per_epoch) {
+    if (!h) return MFSGD_ERR_INVALID_ARG;
+    if (epochs < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "train_schedule: negative epochs");
+    if (epochs > 0 && !lr) return fail(h, MFSGD_ERR_INVALID_ARG, "train_schedule: lr is null");
+    for (int e = 0; e < epochs; ++e)
+        if (is_nan(lr[e]) || (lambda && is_nan(lambda[e])))
+            return fail(h, MFSGD_ERR_INVALID_ARG, "train_schedule: lr / lambda of epoch " + std::to_string(e) + " is NaN");
+    if (epochs == 0) return MFSGD_OK;
+    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "train_schedule: handle has n_parts > 1, drive it with mfsgd_part_train");
+    int rc = prepare_compute(h);
+    if (rc) return rc;
+    float* Q = h->dQ.as<float>();
+    int pending = 0;  // epochs launched and not settled yet: all at the handle's current values
+    for (int e = 0; e < epochs; ++e) {
+        const float lam = lambda ? lambda[e] : h->cfg.lambda;
+        if (!same_bits(lr[e], h->cfg.lr) || !same_bits(lam, h->cfg.lambda)) {
+            // (a persistent launch that found itself not resident is made up for at the values it was launched with)
+            if ((rc = settle_epochs_ok(h, h->parts[0], Q, h->stream, pending))) return rc;
+            pending = 0;
+            if ((rc = apply_hyper(h, lr[e], lam))) return rc;
+        }
+        Part& p = h->parts[0];
+        if ((rc = launch_epoch(h, p, Q, h->stream))) return rc;
+        ++pending;
+        if (rmse_per_epoch) {
+            double sse = 0.0;
+            if ((rc = settle_epochs_ok(h, p, Q, h->stream, pending))) return rc;
+            pending = 0;
+            if ((rc = part_sse_sync(h, p, Q, h->stream, &sse))) return rc;
+            rmse_per_epoch[e] = p.sched.nnz > 0 ? std::sqrt(sse / (double)p.sched.nnz) : 0.0;
+        }
+    }
+    return settle_epochs_ok(h, h->parts[0], Q, h->stream, pending);
+}
+
+int mfsgd_train_bold_driver(mfsgd_handle* h, int32_t epochs, float up, float down, float* lr_used, double* rmse_per_epoch) {
+    if (!h) return MFSGD_ERR_INVALID_ARG;
+    if (epochs < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "bold_driver: negative epochs");
+    if (!(up > 0.0f) || !(down > 0.0f)) return fail(h, MFSGD_ERR_INVALID_ARG, "bold_driver: up and down must be above zero");
+    if (epochs > 0 && (!lr_used || !rmse_per_epoch))
+        return fail(h, MFSGD_ERR_INVALID_ARG, "bold_driver: lr_used and rmse_per_epoch are both required");
+    if (epochs == 0) return MFSGD_OK;
+    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "bold_driver: handle has n_parts > 1, drive it with mfsgd_part_train");
+    int rc = prepare_compute(h);
+    if (rc) return rc;
+    float* Q = h->dQ.as<float>();
+    auto rmse_now = [&](double* out) {
+        Part& p = h->parts[0];
+        double sse = 0.0;
+        const int r = part_sse_sync(h, p, Q, h->stream, &sse);
+        *out = p.sched.nnz > 0 ? std::sqrt(sse / (double)p.sched.nnz) : 0.0;
+        return r;
+    };
+    double prev = 0.0;
+    if ((rc = rmse_now(&prev))) return rc;
+    for (int e = 0; e < epochs; ++e) {
+        lr_used[e] = h->cfg.lr;
+        if ((rc = launch_epoch(h, h->parts[0], Q, h->stream))) return rc;
+        if ((rc = settle_epochs_ok(h, h->parts[0], Q, h->stream, 1))) return rc;
+        if ((rc = rmse_now(&rmse_per_epoch[e]))) return rc;
+        // (a NaN RMSE compares false: the rate shrinks)
+        const float next = rmse_per_epoch[e] < prev ? h->cfg.lr * up : h->cfg.lr * down;
+        prev = rmse_per_epoch[e];
+        if (is_nan(next)) return fail(h, MFSGD_ERR_STATE, "bold_driver: the learning rate became NaN after epoch " + std::to_string(e));
+        if ((rc = apply_hyper(h, next, h->cfg.lambda))) return rc;
+    }
+    return MFSGD_OK;
+}
+
 int mfsgd_rmse(mfsgd_handle* h, double* out) {
     if (!h || !out) return fail(h, MFSGD_ERR_INVALID_ARG, "rmse: null argument");
     if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "rmse: handle has n_parts > 1, use mfsgd_part_sse");

@@ -53,6 +53,13 @@ hipError_t launch_fold_in(int L, const float* Q, float* rows, int k, const long 
                           const int32_t* perm, int nb, const int32_t* items, const float* ratings, int epochs, float lr,
                           float c, hipStream_t st);
 
+// rehyper.hip.  Re-bakes lr and c = 1 - lr*lambda into the entries of a schedule on the device, in place: afterwards
+// they are byte for byte what the packers write for those values (schedule.cpp, rehyper_schedule, is the host's form).
+// cells / subs: the n_descs chunk descriptors and their W*W sub-cell records each; entries: n_entries records.
+// Asynchronous on st; allocates nothing.
+hipError_t launch_rehyper(const CellDesc* cells, const SubDesc* subs, Entry* entries, int64_t n_descs, int64_t n_entries,
+                          int W, int G, float lr, float c, hipStream_t st);
+
 // rows x kp floats: java.util.Random(seed) draws first_pos + row * k ... scaled, zero padded (device-side seeding).
 hipError_t launch_init_rows(float* dst, long long rows, int k, int kp, long long seed, unsigned long long first_pos, float scale,
                             hipStream_t st);

@@ -1897,6 +1897,54 @@ int build_schedule_auto(SchedParams prm, const int32_t* u, const int32_t* i, con
     }
 }
 
+// lr and lambda reach a schedule through make_entry / put_entry and the solo records only (geometry, cuts, order, rows,
+// sub-cell tables and slot words never see them), so new values are one pass over the entries.  Which word holds what is
+// read off the STRUCTURE -- a chunk's sub-cells in table order, each [general steps][run steps][kSoloPad idle steps]
+// [solo header, records, terminator + padding], then the chunk's two trailing idle steps -- never off the old values:
+// with lambda == 0 (or lr*lambda below half an ulp of 1) the old c IS 1.0f and cannot be told from an idle run slot's.
+// rehyper.hip is the same pass over a schedule that lives on the device.
+void rehyper_schedule(Schedule& s, float lr, float lambda, int threads) {
+    if (s.entries.empty() || s.subs.empty() || s.cells.empty()) return;
+    const Hyper hy{lr, 1.0f - lr * lambda};
+    const size_t G = (size_t)s.geo.G, WW = (size_t)s.W * (size_t)s.W;
+    int nt = threads > 0 ? threads : (int)std::thread::hardware_concurrency();
+    nt = std::min(std::max(nt, 1), 64);
+    // step-format entries: lr * r as make_entry rounds it; c, or 1 where a run step's slot is idle (bit 31)
+    auto steps = [&](Entry* e, size_t n, bool run) {
+        for (size_t x = 0; x < n; ++x) {
+            e[x].lrr = hy.lr * e[x].r;
+            e[x].ce = run && (e[x].slots >> 31) ? 1.0f : hy.c;
+        }
+    };
+    // small schedules stay on the caller's thread; the others are dealt out in pieces of about 32 K entries, so that
+    // a few large chunks spread over the threads as well as many small ones
+    const size_t per_desc = std::max<size_t>(1, (size_t)s.n_entry_recs / s.cells.size());
+    const size_t grain = std::max<size_t>(1, ((size_t)1 << 15) / per_desc);
+    parallel_for(s.cells.size(), grain, s.n_entry_recs >= (int64_t)1 << 16 ? nt : 1, [&](Scratch&, size_t d0, size_t d1) {
+        for (size_t d = d0; d < d1; ++d) {
+            const CellDesc& cd = s.cells[d];
+            const size_t n_steps = cd.n_steps & ~kCellCritical;
+            if (n_steps == 0) continue;  // (an empty cell)
+            Entry* base = &s.entries[(size_t)cd.ent_off * G];
+            for (size_t x = 0; x < WW; ++x) {
+                const SubDesc sd = s.subs[d * WW + x];
+                const size_t nsolo = sd.off >> 16, ns = sd.n & 0xFFFFu, nr = sd.n >> 16;
+                Entry* e = base + (size_t)(sd.off & 0xFFFFu) * G;
+                steps(e, ns * G, false);
+                steps(e + ns * G, nr * G, true);
+                if (nsolo == 0) continue;
+                e += (ns + nr) * G;
+                steps(e, (size_t)kSoloPad * G, false);
+                e += (size_t)kSoloPad * G;
+                // record t = e[1 + t] = {next slots, mailbox, lr * r, r}: `ce` is where r sits; the header (e[0]) and
+                // what follows the last record hold no rating and stay as they are
+                for (size_t t = 1; t <= nsolo; ++t) e[t].lrr = hy.lr * e[t].ce;
+            }
+            steps(base + (n_steps - 2) * G, 2 * G, false);
+        }
+    });
+}
+
 void dsgd_plan_users(const int64_t* degu, int32_t U, int32_t G, int32_t* user_begin) {
     // users: boundary g is the first user at which the running rating count reaches g/G of the
     // total, pushed right where needed so that no range is empty while users remain

@@ -176,6 +176,11 @@ int build_schedule(const SchedParams& prm, const int32_t* u, const int32_t* i, c
 int build_schedule_auto(SchedParams prm, const int32_t* u, const int32_t* i, const float* r,
                         const int64_t* orig, int64_t n, Schedule& out, std::string& err);
 
+// Re-bakes other hyper-parameters into the host arrays of a built schedule, in place (s.entries through s.cells and
+// s.subs; nothing happens when either big array is not on the host): afterwards the entries are byte for byte what
+// build_schedule would have written with prm.lr = lr, prm.lambda = lambda.  Up to `threads` threads (0 = all).
+void rehyper_schedule(Schedule& s, float lr, float lambda, int threads);
+
 // DSGD over G devices of ONE global rating set: users are cut into G contiguous
 // ranges balanced by rating count -- device g keeps the P rows of users [user_begin[g],
 // user_begin[g+1]) -- and items into G partitions balanced by rating count (LPT; items nobody

@@ -178,6 +178,45 @@ public final class MatrixFactorizationSGD implements AutoCloseable {
         return nativeRmse(handle);
     }
 
+    /**
+     * Another learning rate and lambda for the live model (mfsgd_set_hyper): the schedules are re-baked in place,
+     * nothing is rebuilt and the factors stay where they are.
+     */
+    public void setHyper(float lr, float lambda) {
+        nativeSetHyper(handle, lr, lambda);
+    }
+
+    /** {lr, lambda} the model holds now. */
+    public float[] hyper() {
+        float[] out = new float[2];
+        nativeGetHyper(handle, out);
+        return out;
+    }
+
+    /**
+     * One epoch per entry of {@code lr} over the ratings of the last train() call, epoch e at lr[e] and lambda[e]
+     * ({@code lambda} null: the current one throughout); returns the RMSE after each epoch.  The model keeps the last
+     * epoch's values.
+     */
+    public double[] trainSchedule(float[] lr, float[] lambda) {
+        if (lambda != null && lambda.length != lr.length) throw new IllegalArgumentException("length mismatch");
+        double[] rmse = new double[lr.length];
+        nativeTrainSchedule(handle, lr, lambda, rmse);
+        return rmse;
+    }
+
+    /**
+     * {@code epochs} passes under the bold driver: after an epoch that lowered the RMSE the rate grows by {@code up},
+     * otherwise it shrinks by {@code down}.  {@code lrUsed[e]} receives the rate of epoch e; returns the RMSE after
+     * each epoch.  The model keeps the rate the next epoch would use.
+     */
+    public double[] trainBoldDriver(int epochs, float up, float down, float[] lrUsed) {
+        if (lrUsed.length < epochs) throw new IllegalArgumentException("lrUsed shorter than epochs");
+        double[] rmse = new double[epochs];
+        nativeTrainBoldDriver(handle, epochs, up, down, lrUsed, rmse);
+        return rmse;
+    }
+
     /** P (users x k) and Q (items x k), row-major. */
     public float[][] factors() {
         float[] p = new float[users * k], q = new float[items * k];
@@ -285,6 +324,11 @@ public final class MatrixFactorizationSGD implements AutoCloseable {
     private static native void nativeGetFactors(long h, float[] p, float[] q);
     private static native void nativeTrain(long h, int epochs, double[] rmsePerEpoch);
     private static native double nativeRmse(long h);
+    private static native void nativeSetHyper(long h, float lr, float lambda);
+    private static native void nativeGetHyper(long h, float[] lrLambda);
+    private static native void nativeTrainSchedule(long h, float[] lr, float[] lambda, double[] rmsePerEpoch);
+    private static native void nativeTrainBoldDriver(long h, int epochs, float up, float down, float[] lrUsed,
+                                                     double[] rmsePerEpoch);
     private static native void nativePredict(long h, int[] u, int[] i, float[] out);
     private static native void nativeRecommend(long h, int[] users, int topN, int[] items, float[] scores);
     private static native void nativeRecommendExcluding(long h, int[] users, int topN, int[] exclU, int[] exclI, int[] items,

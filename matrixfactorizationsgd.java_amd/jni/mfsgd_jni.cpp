@@ -154,6 +154,52 @@ JNIEXPORT jdouble JNICALL Java_MatrixFactorizationSGD_nativeRmse(JNIEnv* env, jc
     return out;
 }
 
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeSetHyper(JNIEnv* env, jclass, jlong h, jfloat lr, jfloat lambda) {
+    throw_status(env, H(h), mfsgd_set_hyper(H(h), lr, lambda));
+}
+
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeGetHyper(JNIEnv* env, jclass, jlong h, jfloatArray out) {
+    if (!out || env->GetArrayLength(out) < 2) return throw_new(env, "java/lang/IllegalArgumentException", "hyper: out needs two entries");
+    float v[2] = {0.f, 0.f};
+    const int rc = mfsgd_get_hyper(H(h), &v[0], &v[1]);
+    if (rc == MFSGD_OK) env->SetFloatArrayRegion(out, 0, 2, v);
+    throw_status(env, H(h), rc);
+}
+
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeTrainSchedule(JNIEnv* env, jclass, jlong h, jfloatArray lr,
+                                                                       jfloatArray lambda, jdoubleArray rmse) {
+    if (!lr || !rmse) return throw_new(env, "java/lang/NullPointerException", "trainSchedule");
+    const jsize epochs = env->GetArrayLength(lr);
+    if ((lambda && env->GetArrayLength(lambda) != epochs) || env->GetArrayLength(rmse) < epochs)
+        return throw_new(env, "java/lang/IllegalArgumentException", "lr, lambda and rmse must have one entry per epoch");
+    // native copies, nothing pinned: the call trains and re-bakes the schedule between epochs
+    auto clr = alloc<float>(env, (size_t)epochs);
+    auto clam = alloc<float>(env, (size_t)epochs);
+    auto tmp = alloc<double>(env, (size_t)epochs);
+    if (!clr || !clam || !tmp) return;
+    env->GetFloatArrayRegion(lr, 0, epochs, clr.get());
+    if (lambda) env->GetFloatArrayRegion(lambda, 0, epochs, clam.get());
+    if (env->ExceptionCheck()) return;
+    const int rc = mfsgd_train_schedule(H(h), epochs, clr.get(), lambda ? clam.get() : nullptr, tmp.get());
+    if (rc == MFSGD_OK && epochs > 0) env->SetDoubleArrayRegion(rmse, 0, epochs, tmp.get());
+    throw_status(env, H(h), rc);
+}
+
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeTrainBoldDriver(JNIEnv* env, jclass, jlong h, jint epochs, jfloat up,
+                                                                         jfloat down, jfloatArray lr_used, jdoubleArray rmse) {
+    if (epochs < 0 || !lr_used || !rmse || env->GetArrayLength(lr_used) < epochs || env->GetArrayLength(rmse) < epochs)
+        return throw_new(env, "java/lang/IllegalArgumentException", "lrUsed / rmse array shorter than epochs");
+    auto used = alloc<float>(env, (size_t)epochs);
+    auto tmp = alloc<double>(env, (size_t)epochs);
+    if (!used || !tmp) return;
+    const int rc = mfsgd_train_bold_driver(H(h), epochs, up, down, used.get(), tmp.get());
+    if (rc == MFSGD_OK && epochs > 0) {
+        env->SetFloatArrayRegion(lr_used, 0, epochs, used.get());
+        env->SetDoubleArrayRegion(rmse, 0, epochs, tmp.get());
+    }
+    throw_status(env, H(h), rc);
+}
+
 JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativePredict(JNIEnv* env, jclass, jlong h, jintArray u, jintArray i,
                                                                  jfloatArray out) {
     if (!u || !i || !out) return throw_new(env, "java/lang/NullPointerException", "predict");

@@ -203,6 +203,49 @@ class MatrixFactorizationSGD:
                                           _p(out, C.c_double) if rmse else None))
         return out if rmse else None
 
+    def set_hyper(self, lr, lam):
+        """Another lr and lambda for the live model (mfsgd_set_hyper): the schedules are re-baked in place -- nothing
+        is rebuilt, the factors stay where they are."""
+        self._check(self._lib.mfsgd_set_hyper(self._handle(), float(lr), float(lam)))
+        self.lr, self.lam = self.hyper()
+
+    def hyper(self):
+        """(lr, lambda) the handle holds now, as Python floats of the fp32 values."""
+        lr, lam = C.c_float(), C.c_float()
+        self._check(self._lib.mfsgd_get_hyper(self._handle(), C.byref(lr), C.byref(lam)))
+        return lr.value, lam.value
+
+    def fit_schedule(self, lr, lam=None, *, rmse=True):
+        """One epoch per entry of lr, epoch e at lr[e] and lam[e] (lam None: the current lambda throughout); returns
+        the RMSE after each epoch like fit().  The model keeps the last epoch's values."""
+        lrs = _f32(np.atleast_1d(lr))
+        lams = None if lam is None else _f32(np.atleast_1d(lam))
+        if lrs.ndim != 1 or (lams is not None and lams.shape != lrs.shape):
+            raise ValueError("lr and lam must be 1-d arrays of the same length")
+        out = np.zeros(lrs.size, np.float64)
+        try:
+            self._check(self._lib.mfsgd_train_schedule(self._handle(), lrs.size, _p(lrs, C.c_float),
+                                                       None if lams is None else _p(lams, C.c_float),
+                                                       _p(out, C.c_double) if rmse else None))
+        finally:
+            if self._h:
+                self.lr, self.lam = self.hyper()
+        return out if rmse else None
+
+    def fit_bold_driver(self, epochs, up=1.05, down=0.5):
+        """`epochs` passes under the bold driver: after an epoch that lowered the RMSE the rate grows by `up`,
+        otherwise it shrinks by `down`.  Returns (lr_used float32[epochs], rmse float64[epochs]); the model keeps
+        the rate the next epoch would use."""
+        used = np.zeros(int(epochs), np.float32)
+        out = np.zeros(int(epochs), np.float64)
+        try:
+            self._check(self._lib.mfsgd_train_bold_driver(self._handle(), int(epochs), float(up), float(down),
+                                                          _p(used, C.c_float), _p(out, C.c_double)))
+        finally:
+            if self._h:
+                self.lr, self.lam = self.hyper()
+        return used, out
+
     def train_timed(self, epochs):
         """(elapsed device milliseconds, kernel launches) for `epochs` passes."""
         ms = C.c_double()
