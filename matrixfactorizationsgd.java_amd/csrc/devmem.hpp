@@ -1,5 +1,5 @@
 // devmem.hpp -- the owner of device memory: every hipMalloc of the library lives in a DevBuf, which frees it.
-// Host-compilable (capi.cpp, dsgd.cpp): the runtime API only.
+// Host-compilable (the C-ABI units, dsgd.cpp): the runtime API only.
 #pragma once
 
 #include <hip/hip_runtime_api.h>

@@ -1,0 +1,317 @@
+// handle.cpp -- the handle of the C-ABI (include/mfsgd.h): its life cycle, the error channel, device bring-up, and
+// the factors (seed, set, get, upload).
+//
+// No reference counterpart exists; the surface follows SURVEY.md section 8b.  There is no CPU
+// compute path in this library: every compute entry point needs a gfx950
+// device and fails with MFSGD_ERR_NO_DEVICE otherwise.
+#include <cmath>
+#include <cstring>
+#include <memory>
+
+#include "handle.hpp"
+#include "jrandom.hpp"
+
+namespace mfsgd {
+
+thread_local std::string g_create_error;
+
+int fail(const mfsgd_handle* h, int code, const std::string& msg) {
+    if (h) h->err = msg;
+    return code;
+}
+
+int hip_fail(const mfsgd_handle* h, const std::string& what, hipError_t e) {
+    return fail(h, e == hipErrorOutOfMemory ? MFSGD_ERR_OOM : MFSGD_ERR_HIP, what + hipGetErrorString(e));
+}
+
+int serve_fail(const mfsgd_handle* h, const char* prefix, hipError_t e) {
+    (void)hipGetLastError();
+    return hip_fail(h, prefix, e);
+}
+
+int check_part(const mfsgd_handle* h, int32_t part, const char* name) {
+    if (part < 0 || part >= h->n_parts) return fail(h, MFSGD_ERR_INVALID_ARG, std::string(name) + ": bad partition");
+    return MFSGD_OK;
+}
+
+static int usable_devices(int* count, std::string* why) {
+    int n = 0;
+    hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess || n <= 0) {
+        (void)hipGetLastError();
+        *count = 0;
+        if (why) *why = std::string("no HIP device visible (") + hipGetErrorString(e) + ")";
+        return 0;
+    }
+    *count = n;
+    return 0;
+}
+
+int ensure_device(mfsgd_handle* h) {
+    if (h->device_ready) {
+        HIPCHK(h, hipSetDevice(h->cfg.device));
+        return MFSGD_OK;
+    }
+    int n = 0;
+    std::string why;
+    usable_devices(&n, &why);
+    if (n <= 0) return fail(h, MFSGD_ERR_NO_DEVICE, "libmfsgd has no CPU fallback: " + why);
+    if (h->cfg.device < 0 || h->cfg.device >= n)
+        return fail(h, MFSGD_ERR_NO_DEVICE, "device ordinal " + std::to_string(h->cfg.device) +
+                                                " out of range (" + std::to_string(n) + " visible)");
+    hipDeviceProp_t prop;
+    HIPCHK(h, hipGetDeviceProperties(&prop, h->cfg.device));
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return fail(h, MFSGD_ERR_NO_DEVICE,
+                    std::string("device is ") + prop.gcnArchName + "; libmfsgd is built for gfx950 only");
+    h->n_cu = prop.multiProcessorCount;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    HIPCHK(h, hipEventCreate(&h->ev0));
+    HIPCHK(h, hipEventCreate(&h->ev1));
+    h->device_ready = true;
+    return MFSGD_OK;
+}
+
+int dev_alloc(mfsgd_handle* h, DevBuf& b, size_t bytes) {
+    const hipError_t e = b.alloc(bytes);
+    if (e != hipSuccess) return hip_fail(h, "hipMalloc(&b.p, bytes): ", e);  // (the text this failure has always had)
+    return MFSGD_OK;
+}
+
+// The device copies of the factors go away (re-seed, set_factors, load): nothing captured with the
+// old pointers may be replayed, and nothing may still be running on them.
+static void release_device_factors(mfsgd_handle* h) {
+    if (h->where != mfsgd_handle::Where::Device) return;
+    if (h->device_ready) {
+        (void)hipSetDevice(h->cfg.device);
+        (void)hipDeviceSynchronize();
+    }
+    for (Part& p : h->parts) p.drop_graphs();
+    h->dP.reset();
+    h->dQ.reset();
+}
+
+// factors host <-> device -------------------------------------------------------
+int factors_to_device(mfsgd_handle* h) {
+    int rc = ensure_device(h);
+    if (rc) return rc;
+    if (h->where == mfsgd_handle::Where::Device) return MFSGD_OK;
+    if (h->where == mfsgd_handle::Where::None)
+        return fail(h, MFSGD_ERR_STATE, "factors not initialised: call mfsgd_init_factors or mfsgd_set_factors");
+    if ((rc = upload(h, h->dP, h->hP))) return rc;
+    if (h->n_parts == 1 && (rc = upload(h, h->dQ, h->hQ))) return rc;
+    h->where = mfsgd_handle::Where::Device;
+    std::vector<float>().swap(h->hP);
+    std::vector<float>().swap(h->hQ);
+    return MFSGD_OK;
+}
+
+static void fill_rows(JRandom& g, float* dst, int64_t rows, int k, int kp, float scale) {
+    for (int64_t x = 0; x < rows; ++x) {
+        float* row = dst + x * kp;
+        for (int f = 0; f < k; ++f) row[f] = g.nextFloat() * scale;
+        for (int f = k; f < kp; ++f) row[f] = 0.0f;
+    }
+}
+
+// Seeds P (stream position of row u: (u_offset + u) * k) and, for single-partition handles with with_q, Q
+// (row i: (n_users + i) * k).  On the device when there is one (a kernel per matrix; nothing crosses PCIe);
+// on the host otherwise (host-only callers: the factors are uploaded when the first compute call comes).
+static int seed_factors(mfsgd_handle* h, int64_t seed, int64_t u_offset, bool with_q) {
+    const int k = h->cfg.k, kp = h->geo.kp;
+    const float scale = (float)(1.0 / std::sqrt((double)k));
+    release_device_factors(h);
+    h->where = mfsgd_handle::Where::None;
+    if (ensure_device(h) == MFSGD_OK) {
+        int rc;
+        if ((rc = dev_alloc(h, h->dP, sizeof(float) * (size_t)h->cfg.n_users * kp))) return rc;
+        HIPCHK(h, launch_init_rows(h->dP.as<float>(), h->cfg.n_users, k, kp, seed, (unsigned long long)u_offset * (unsigned long long)k,
+                                   scale, h->stream));
+        if (with_q) {
+            if ((rc = dev_alloc(h, h->dQ, sizeof(float) * (size_t)h->cfg.n_items * kp))) return rc;
+            HIPCHK(h, launch_init_rows(h->dQ.as<float>(), h->cfg.n_items, k, kp, seed,
+                                       (unsigned long long)h->cfg.n_users * (unsigned long long)k, scale, h->stream));
+        }
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        std::vector<float>().swap(h->hP);
+        std::vector<float>().swap(h->hQ);
+        h->where = mfsgd_handle::Where::Device;
+        return MFSGD_OK;
+    }
+    h->err.clear();  // no device: not an error for this call
+    h->hP.assign((size_t)h->cfg.n_users * kp, 0.0f);
+    JRandom g(seed);
+    g.skip((uint64_t)u_offset * (uint64_t)k);
+    fill_rows(g, h->hP.data(), h->cfg.n_users, k, kp, scale);
+    h->hQ.clear();
+    if (with_q) {
+        h->hQ.assign((size_t)h->cfg.n_items * kp, 0.0f);
+        JRandom gq(seed);
+        gq.skip((uint64_t)h->cfg.n_users * (uint64_t)k);
+        fill_rows(gq, h->hQ.data(), h->cfg.n_items, k, kp, scale);
+    }
+    h->where = mfsgd_handle::Where::Host;
+    return MFSGD_OK;
+}
+
+}  // namespace mfsgd
+
+using namespace mfsgd;
+
+// =============================================================================
+extern "C" {
+
+int mfsgd_abi_version(void) { return MFSGD_ABI_VERSION; }
+
+int mfsgd_device_count(int32_t* out) {
+    if (!out) return MFSGD_ERR_INVALID_ARG;
+    return guarded_free(nullptr, [&]() -> int {
+        int n = 0;
+        usable_devices(&n, nullptr);
+        int ok = 0;
+        for (int d = 0; d < n; ++d) {
+            hipDeviceProp_t prop;
+            if (hipGetDeviceProperties(&prop, d) == hipSuccess && std::strncmp(prop.gcnArchName, "gfx950", 6) == 0) ++ok;
+        }
+        *out = ok;
+        return MFSGD_OK;
+    });
+}
+
+int mfsgd_create(const mfsgd_config* cfg, mfsgd_handle** out) {
+    if (out) *out = nullptr;
+    return guarded_free("mfsgd_create", [&]() -> int {
+        auto bad = [&](const char* m, int code = MFSGD_ERR_INVALID_ARG) {
+            g_create_error = std::string("mfsgd_create: ") + m;
+            return code;
+        };
+        if (!cfg || !out) return bad("null argument");
+        if (cfg->n_users < 1 || cfg->n_items < 1) return bad("n_users and n_items must be >= 1");
+        if (cfg->k < 1) return bad("k must be >= 1");
+        if (cfg->k > MFSGD_MAX_K) return bad("k exceeds MFSGD_MAX_K (256)", MFSGD_ERR_UNSUPPORTED);
+        if (!(cfg->lr == cfg->lr) || !(cfg->lambda == cfg->lambda)) return bad("lr / lambda is NaN");
+        if (cfg->blocks < 0 || cfg->waves < 0 || cfg->n_parts < 0 || cfg->device < 0 || cfg->host_threads < 0)
+            return bad("negative geometry field");
+        if (cfg->waves != 0 && cfg->waves != 1 && cfg->waves != 2 && cfg->waves != 4 && cfg->waves != 8)
+            return bad("waves must be 0 (auto), 1, 2, 4 or 8");
+        for (int x = 0; x < 5; ++x)
+            if (cfg->reserved[x] != 0) return bad("reserved fields must be zero");
+        auto h = std::make_unique<mfsgd_handle>();
+        h->cfg = *cfg;
+        h->geo = geometry_for_k(cfg->k);
+        h->n_parts = cfg->n_parts > 1 ? cfg->n_parts : 1;
+        if (h->n_parts > cfg->n_items) return bad("n_parts exceeds n_items");
+        if (h->n_parts > 1) default_item_map(h.get());
+        *out = h.release();
+        return MFSGD_OK;
+    });
+}
+
+void mfsgd_destroy(mfsgd_handle* h) {
+    if (!h) return;
+    if (h->device_ready) {
+        (void)hipSetDevice(h->cfg.device);
+        (void)hipStreamSynchronize(h->stream);
+    }
+    h->parts.clear();
+    h->dP.reset();
+    h->dQ.reset();
+    if (h->ev0) (void)hipEventDestroy(h->ev0);
+    if (h->ev1) (void)hipEventDestroy(h->ev1);
+    if (h->side_stream) {
+        (void)hipStreamSynchronize(h->side_stream);
+        if (h->occupy_started) (void)hipHostFree(h->occupy_started);
+        h->occupy_started = nullptr;
+        (void)hipStreamDestroy(h->side_stream);
+    }
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h;
+}
+
+const char* mfsgd_last_error(const mfsgd_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+
+int mfsgd_get_dims(const mfsgd_handle* h, int32_t* n_users, int32_t* n_items, int32_t* k) {
+    if (!h) return MFSGD_ERR_INVALID_ARG;
+    if (n_users) *n_users = h->cfg.n_users;
+    if (n_items) *n_items = h->cfg.n_items;
+    if (k) *k = h->cfg.k;
+    return MFSGD_OK;
+}
+
+int mfsgd_get_parts(const mfsgd_handle* h, int32_t* n_parts, int32_t* kp, int32_t* device) {
+    if (!h) return MFSGD_ERR_INVALID_ARG;
+    if (n_parts) *n_parts = h->n_parts;
+    if (kp) *kp = h->geo.kp;
+    if (device) *device = h->cfg.device;
+    return MFSGD_OK;
+}
+
+int mfsgd_init_p_offset(mfsgd_handle* h, int64_t seed, int64_t u_offset) {
+    return guarded(h, "init_p_offset", [&]() -> int {
+        if (u_offset < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "init_p_offset: bad argument");
+        return seed_factors(h, seed, u_offset, false);
+    });
+}
+
+int mfsgd_init_factors(mfsgd_handle* h, int64_t seed) {
+    return guarded(h, "init_factors", [&]() -> int {
+        return seed_factors(h, seed, 0, h->n_parts == 1);  // n_parts > 1: Q lives in caller-owned blocks
+    });
+}
+
+int mfsgd_set_factors(mfsgd_handle* h, const float* P, const float* Q) {
+    return guarded(h, "set_factors", [&]() -> int {
+        if (!P) return fail(h, MFSGD_ERR_INVALID_ARG, "set_factors: P is null");
+        if (h->n_parts == 1 && !Q) return fail(h, MFSGD_ERR_INVALID_ARG, "set_factors: Q is null");
+        const int k = h->cfg.k, kp = h->geo.kp;
+        release_device_factors(h);
+        h->hP.assign((size_t)h->cfg.n_users * kp, 0.0f);
+        for (int64_t x = 0; x < h->cfg.n_users; ++x) std::memcpy(&h->hP[(size_t)x * kp], P + x * k, sizeof(float) * (size_t)k);
+        h->hQ.clear();
+        if (h->n_parts == 1) {
+            h->hQ.assign((size_t)h->cfg.n_items * kp, 0.0f);
+            for (int64_t x = 0; x < h->cfg.n_items; ++x) std::memcpy(&h->hQ[(size_t)x * kp], Q + x * k, sizeof(float) * (size_t)k);
+        }
+        h->where = mfsgd_handle::Where::Host;
+        return MFSGD_OK;
+    });
+}
+
+int mfsgd_get_factors(mfsgd_handle* h, float* P, float* Q) {
+    return guarded(h, "get_factors", [&]() -> int {
+        if (h->where == mfsgd_handle::Where::None) return fail(h, MFSGD_ERR_STATE, "get_factors: factors not initialised");
+        const int k = h->cfg.k, kp = h->geo.kp;
+        const std::vector<float>*sp = &h->hP, *sq = &h->hQ;
+        std::vector<float> tp, tq;
+        if (h->where == mfsgd_handle::Where::Device) {
+            HIPCHK(h, hipSetDevice(h->cfg.device));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            if (P) {
+                tp.resize((size_t)h->cfg.n_users * kp);
+                HIPCHK(h, hipMemcpy(tp.data(), h->dP.get(), tp.size() * sizeof(float), hipMemcpyDeviceToHost));
+            }
+            if (Q && h->n_parts == 1) {
+                tq.resize((size_t)h->cfg.n_items * kp);
+                HIPCHK(h, hipMemcpy(tq.data(), h->dQ.get(), tq.size() * sizeof(float), hipMemcpyDeviceToHost));
+            }
+            sp = &tp;
+            sq = &tq;
+        }
+        if (P)
+            for (int64_t x = 0; x < h->cfg.n_users; ++x) std::memcpy(P + x * k, &(*sp)[(size_t)x * kp], sizeof(float) * (size_t)k);
+        if (Q) {
+            if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "get_factors: Q lives in caller-owned blocks when n_parts > 1");
+            for (int64_t x = 0; x < h->cfg.n_items; ++x) std::memcpy(Q + x * k, &(*sq)[(size_t)x * kp], sizeof(float) * (size_t)k);
+        }
+        return MFSGD_OK;
+    });
+}
+
+int mfsgd_debug_device_bytes(int64_t* live) {
+    if (!live) return MFSGD_ERR_INVALID_ARG;
+    *live = g_dev_live_bytes.load();
+    return MFSGD_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,181 @@
+// handle.hpp -- what the units of the C-ABI share (handle.cpp, ratings.cpp, train.cpp, serve.cpp): the handle, its
+// partitions, the error channel, the guard every `int` entry point runs in, and the helpers that cross units.
+// Internal: installed nowhere.  dsgd.cpp and io.cpp see the handle through include/mfsgd.h only.
+#pragma once
+
+#include <hip/hip_runtime_api.h>
+
+#include <cstdint>
+#include <map>
+#include <new>
+#include <string>
+#include <type_traits>
+#include <utility>
+#include <vector>
+
+#include "../../include/mfsgd.h"
+#include "devmem.hpp"
+#include "kernels.hpp"
+#include "schedule.hpp"
+
+namespace mfsgd {
+
+struct Part {
+    Schedule sched;
+    int32_t q_rows = 0;  // rows of this partition's Q block
+    // Forwarding and register-resident runs exist on the kernel's q side only.  The update is
+    // symmetric in p and q, so when the heaviest USER outweighs the heaviest item the schedule
+    // is built with the roles exchanged and the kernels get (Q, P) instead of (P, Q).
+    bool swapped = false;
+    bool on_device = false;
+    DevBuf d_cells, d_rows, d_subs, d_entries, d_sse_partial, d_sse_out;
+    DevBuf d_sync;        // persistent kernel: done[B] words (kDoneStride apart) + the abort word
+    int persistent_np = -1;  // co-resident workgroups of the epoch kernel; 0 = use round launches; -1 = not probed
+    // training graphs keyed by the (P, Q) pointers they were captured with (both are baked into the
+    // kernel node; P changes when the factors are re-seeded, Q with every caller-owned block)
+    std::map<std::pair<const void*, const void*>, hipGraphExec_t> graphs;
+
+    Part() = default;
+    Part(Part&&) = default;  // (the moved-from map is empty: nothing is destroyed twice)
+    ~Part() { drop_graphs(); }
+    void drop_graphs() {
+        for (auto& kv : graphs)
+            if (kv.second) (void)hipGraphExecDestroy(kv.second);
+        graphs.clear();
+    }
+};
+
+// d_sync: done[B] words (kDoneStride apart), then {arrivals, generation, -, -} of the kernel's start-of-launch
+// barrier, then {abort code, launches that started, -, -}.  Zeroed once, when allocated; the kernel keeps it
+// consistent from launch to launch by itself.
+// Behind them the tile mailboxes of the persistent kernel: B x kp granules of 8 bytes ({value, tag}; only tiles the
+// scheduler marked kCellLoneTile use theirs).
+inline size_t sync_bytes(const Part& p) {
+    return ((size_t)p.sched.B * kDoneStride + 8) * sizeof(unsigned) + (size_t)p.sched.B * (size_t)p.sched.geo.L * 4 * 8;
+}
+inline unsigned* abort_word(const Part& p) { return p.d_sync.as<unsigned>() + (size_t)p.sched.B * kDoneStride + 4; }
+
+}  // namespace mfsgd
+
+struct mfsgd_handle {
+    mfsgd_config cfg{};
+    mfsgd::Geometry geo{};
+    int n_parts = 1;
+    std::vector<mfsgd::Part> parts;
+    bool have_ratings = false;
+    int64_t nnz_total = 0;
+    // DSGD item map (n_parts > 1): item i lives in partition item_part[i], row item_row[i] of that
+    // partition's Q block.  Default: i % n_parts, i / n_parts; mfsgd_set_item_partition replaces it.
+    std::vector<int32_t> item_part, item_row, part_q_rows;
+    bool custom_item_map = false;
+
+    // factors: host staging (kp-padded rows) until the device copy is created
+    enum class Where { None, Host, Device } where = Where::None;
+    std::vector<float> hP, hQ;
+    mfsgd::DevBuf dP, dQ;
+
+    bool device_ready = false;
+    int n_cu = 0;
+    hipStream_t stream = nullptr;
+    hipStream_t side_stream = nullptr;  // diagnostics only (mfsgd_debug_occupy)
+    unsigned* occupy_started = nullptr; // ... pinned host word its workgroups count themselves in
+    int64_t n_not_resident = 0;         // persistent launches that gave up at the residency check
+    // identity of the rating set the schedules were built from: its length and a 128-bit hash of every
+    // byte of u, i and r -- a repeated mfsgd_set_ratings with the same triples keeps the schedules
+    uint64_t ratings_hash[2] = {0, 0};
+    int64_t n_schedule_builds = 0, n_schedule_reuses = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    mutable std::string err;
+};
+
+namespace mfsgd {
+
+// The message channel of the calls that have no handle (mfsgd_create, mfsgd_ranking_metrics_from_ranks): read with
+// mfsgd_last_error(NULL), per thread.
+extern thread_local std::string g_create_error;
+
+int fail(const mfsgd_handle* h, int code, const std::string& msg);
+int hip_fail(const mfsgd_handle* h, const std::string& what, hipError_t e);
+
+#define HIPCHK(h, call)                                                                         \
+    do {                                                                                        \
+        hipError_t e_ = (call);                                                                 \
+        if (e_ != hipSuccess) return hip_fail((h), std::string(#call) + ": ", e_);              \
+    } while (0)
+
+// The serving calls name themselves instead of the HIP call that failed: `bad` makes the return code of an error ...
+#define HIPCHK_OR(bad, call)                   \
+    do {                                       \
+        hipError_t e_ = (call);                \
+        if (e_ != hipSuccess) return bad(e_);  \
+    } while (0)
+
+// ... and most of them leave no error behind in the runtime
+int serve_fail(const mfsgd_handle* h, const char* prefix, hipError_t e);
+
+// The guard: no C++ exception crosses the boundary (include/mfsgd.h).  Every `int` entry point runs its body in
+// guarded() or, without a handle, in guarded_free().  `report` turns (code, what) into the return value; should even
+// the message not fit into memory, the code goes back alone.
+template <class F, class R>
+int guard_run(F&& body, int other, R&& report) noexcept {
+    int code = other;
+    const char* what = "out of host memory";
+    std::string kept;
+    try {
+        return body();
+    } catch (const std::bad_alloc&) {
+        code = MFSGD_ERR_OOM;
+    } catch (const std::exception& e) {
+        try {
+            kept = e.what();
+            what = kept.c_str();
+        } catch (const std::exception&) {
+            what = "";
+        }
+    }
+    try {
+        return report(code, what);
+    } catch (const std::exception&) {
+        return code;
+    }
+}
+
+// A null handle is MFSGD_ERR_INVALID_ARG.  std::bad_alloc becomes MFSGD_ERR_OOM, "<name>: out of host memory"; any other
+// std::exception becomes `other`, "<name>: <what()>".
+template <class F>
+int guarded(const mfsgd_handle* h, const char* name, F&& body, int other = MFSGD_ERR_HIP) {
+    if (!h) return MFSGD_ERR_INVALID_ARG;
+    return guard_run(body, other, [&](int code, const char* what) { return fail(h, code, std::string(name) + ": " + what); });
+}
+
+// The same for a call without a handle: the message goes where mfsgd_create's go, or (name == nullptr) nowhere.
+template <class F>
+int guarded_free(const char* name, F&& body) {
+    return guard_run(body, MFSGD_ERR_HIP, [&](int code, const char* what) {
+        if (name) g_create_error = std::string(name) + ": " + what;
+        return code;
+    });
+}
+
+// MFSGD_OK, or MFSGD_ERR_INVALID_ARG with "<name>: bad partition".  (Not a Part*: h->parts is empty until
+// mfsgd_set_ratings, and some callers ask before.)
+int check_part(const mfsgd_handle* h, int32_t part, const char* name);
+
+// handle.cpp
+int ensure_device(mfsgd_handle* h);
+int dev_alloc(mfsgd_handle* h, DevBuf& b, size_t bytes);
+int factors_to_device(mfsgd_handle* h);
+// ratings.cpp
+void default_item_map(mfsgd_handle* h);
+int prepare_compute(mfsgd_handle* h);  // ratings present; factors and every partition's schedule on the device
+
+template <class T>
+int upload(mfsgd_handle* h, DevBuf& b, const T& v) {
+    using E = std::remove_reference_t<decltype(*v.data())>;
+    int rc = dev_alloc(h, b, v.size() * sizeof(E));
+    if (rc) return rc;
+    if (!v.empty()) HIPCHK(h, hipMemcpy(b.get(), v.data(), v.size() * sizeof(E), hipMemcpyHostToDevice));
+    return MFSGD_OK;
+}
+
+}  // namespace mfsgd

@@ -104,7 +104,7 @@ struct DeviceIngestExt {
     int (*download_raw)(const void* dev, void* host, size_t bytes) = nullptr;  // (the sub-cell tables, for the debug getter)
 };
 
-// Implemented in ingest.hip.  `device` must already be usable (capi checks).
+// Implemented in ingest.hip.  `device` must already be usable (ratings.cpp checks).
 DeviceIngest make_device_ingest(int device);
 void destroy_device_ingest(DeviceIngest& d);
 

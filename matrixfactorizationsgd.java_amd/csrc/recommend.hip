@@ -442,7 +442,7 @@ hipError_t recommend_fused(int L, const float* P, const float* Q, const int32_t*
     }
 }
 
-// Device buffers are the caller's (capi.cpp): scores/ids in and out (nb * n_items each), offsets nb+1.
+// Device buffers are the caller's (serve.cpp): scores/ids in and out (nb * n_items each), offsets nb+1.
 hipError_t recommend_batch(int L, const float* P, const float* Q, const int32_t* d_users, int nb, int32_t n_items,
                            int32_t topn, const RecommendExcl& ex, float* s_in, float* s_out, int32_t* id_in, int32_t* id_out,
                            long long* d_off, DevBuf& temp, float* out_s, int32_t* out_i, hipStream_t st) {

@@ -1,0 +1,488 @@
+// serve.cpp -- what a trained model answers: predictions, top-N recommendations, ranks of held-out items and their
+// metrics, and the fold-in of new users.  Every call batches its work through bounded staging buffers.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "handle.hpp"
+
+namespace mfsgd {
+
+// How a serving call speaks of itself and of the users it was given, in the messages the two cores share.
+struct ServeName {
+    const char* call;
+    const char* whose;
+};
+constexpr ServeName kRecommend{"recommend", "the requested users"}, kRank{"rank_items", "the users asked about"};
+
+// The row matrix of a serving call on the device: the model's P, or host_rows (n_rows x k, dense), which goes up into
+// a kp-padded temporary (`buf`) for the length of the call.
+static int upload_rows(mfsgd_handle* h, const float* host_rows, int32_t n_rows, DevBuf& buf, const float** rows) {
+    *rows = h->dP.as<const float>();
+    if (!host_rows) return MFSGD_OK;
+    const int k = h->cfg.k, kp = h->geo.kp;
+    std::vector<float> padded((size_t)n_rows * kp, 0.0f);
+    for (int64_t x = 0; x < n_rows; ++x) std::memcpy(&padded[(size_t)x * kp], host_rows + x * k, sizeof(float) * (size_t)k);
+    const int rc = upload(h, buf, padded);
+    *rows = buf.as<const float>();
+    return rc;
+}
+
+// Range check of the exclusion pairs, and *kept = how many of them belong to a user that has a slot.
+static int count_exclusions(const mfsgd_handle* h, const ServeName& what, const std::vector<int32_t>& slot_of_user, int32_t n_rows,
+                            const int32_t* excl_u, const int32_t* excl_i, int64_t n_excl, int64_t* kept) {
+    *kept = 0;
+    for (int64_t x = 0; x < n_excl; ++x) {
+        if (excl_u[x] < 0 || excl_u[x] >= n_rows || excl_i[x] < 0 || excl_i[x] >= h->cfg.n_items)
+            return fail(h, MFSGD_ERR_INVALID_ARG, std::string(what.call) + ": excluded pair " + std::to_string(x) + " out of range");
+        *kept += slot_of_user[(size_t)excl_u[x]] >= 0 ? 1 : 0;
+    }
+    if (*kept > (int64_t)UINT32_MAX)
+        return fail(h, MFSGD_ERR_INVALID_ARG, std::string(what.call) + ": more than 2^32 - 1 excluded pairs of " + what.whose);
+    return MFSGD_OK;
+}
+
+// Exclusion lists of one recommend call on the device: the pairs go up in chunks of bounded size, those of requested
+// users are kept (slot << 32 | item), then sorted and made distinct into one list per slot (recommend.hip).
+// Scratch lives as long as this function; `ex` points into `slot`, `off` and `items`, which are the caller's.
+// `what` starts the message of a HIP failure: the call the lists are built for.
+constexpr int64_t kExclChunk = (int64_t)1 << 22;  // pairs per upload: 32 MB of staging
+
+static int exclusions_to_device(mfsgd_handle* h, const ServeName& what, const std::vector<int32_t>& slot_of_user, int32_t n_slots,
+                                const int32_t* excl_u, const int32_t* excl_i, int64_t n_excl, int64_t kept, DevBuf& slot,
+                                DevBuf& off, DevBuf& items, DevBuf& temp, RecommendExcl& ex) {
+    const std::string prefix = std::string(what.call) + ": exclusion lists: ";
+    auto bad = [h, &prefix](hipError_t e) { return serve_fail(h, prefix.c_str(), e); };
+    DevBuf cu, ci, keys, keys_tmp, count;
+    const int64_t chunk = std::min(n_excl, kExclChunk);
+    int rc;
+    if ((rc = upload(h, slot, slot_of_user))) return rc;
+    if ((rc = dev_alloc(h, cu, sizeof(int32_t) * (size_t)chunk))) return rc;
+    if ((rc = dev_alloc(h, ci, sizeof(int32_t) * (size_t)chunk))) return rc;
+    if ((rc = dev_alloc(h, keys, 8 * (size_t)kept))) return rc;
+    if ((rc = dev_alloc(h, keys_tmp, 8 * (size_t)kept))) return rc;
+    if ((rc = dev_alloc(h, count, 16))) return rc;  // [0] appended pairs (u64), [2] distinct ones (u32)
+    if ((rc = dev_alloc(h, off, sizeof(long long) * ((size_t)n_slots + 1)))) return rc;
+    if ((rc = dev_alloc(h, items, sizeof(int32_t) * (size_t)kept))) return rc;
+    auto* cnt = count.as<unsigned long long>();
+    HIPCHK_OR(bad, hipMemsetAsync(cnt, 0, 16, h->stream));
+    for (int64_t x0 = 0; x0 < n_excl; x0 += chunk) {
+        const int64_t c = std::min(chunk, n_excl - x0);
+        HIPCHK_OR(bad, hipMemcpyAsync(cu.get(), excl_u + x0, sizeof(int32_t) * (size_t)c, hipMemcpyHostToDevice, h->stream));
+        HIPCHK_OR(bad, hipMemcpyAsync(ci.get(), excl_i + x0, sizeof(int32_t) * (size_t)c, hipMemcpyHostToDevice, h->stream));
+        HIPCHK_OR(bad, recommend_excl_filter(slot.as<const int32_t>(), cu.as<const int32_t>(), ci.as<const int32_t>(), c,
+                                             keys.as<unsigned long long>(), cnt, kept, h->stream));
+    }
+    HIPCHK_OR(bad, recommend_excl_lists(keys.as<unsigned long long>(), keys_tmp.as<unsigned long long>(), kept, n_slots,
+                                        reinterpret_cast<unsigned*>(cnt + 1), off.as<long long>(), items.as<int32_t>(),
+                                        temp, h->stream));
+    HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
+    ex.slot = slot.as<const int32_t>();
+    ex.off = off.as<const long long>();
+    ex.items = items.as<const int32_t>();
+    return MFSGD_OK;
+}
+
+// Body of the recommend calls: "user j" is row j of a matrix of n_rows rows, and `users` names the rows asked for.
+// host_rows == nullptr: the matrix is the model's P.  Otherwise it is host_rows (n_rows x k, dense).
+static int recommend_core(mfsgd_handle* h, const float* host_rows, int32_t n_rows, const int32_t* users, int32_t n_users,
+                          int32_t topn, const int32_t* excl_u, const int32_t* excl_i, int64_t n_excl, int32_t* out_items,
+                          float* out_scores) {
+    if (n_users < 0 || topn < 1 || (n_users > 0 && (!users || !out_items || !out_scores)) || n_excl < 0 ||
+        (n_excl > 0 && (!excl_u || !excl_i)))
+        return fail(h, MFSGD_ERR_INVALID_ARG, "recommend: bad argument");
+    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "recommend: single-partition handles only");
+    if (topn > h->cfg.n_items) return fail(h, MFSGD_ERR_INVALID_ARG, "recommend: topn exceeds the number of items");
+    for (int32_t j = 0; j < n_users; ++j)
+        if (users[j] < 0 || users[j] >= n_rows)
+            return fail(h, MFSGD_ERR_INVALID_ARG, "recommend: user " + std::to_string(j) + " out of range");
+    // a slot per distinct requested user (one user asked for twice shares it), and how many pairs are theirs
+    std::vector<int32_t> slot_of_user;
+    int32_t n_slots = 0;
+    int64_t kept = 0;
+    int rc;
+    if (n_excl > 0) {
+        slot_of_user.assign((size_t)n_rows, -1);
+        for (int32_t j = 0; j < n_users; ++j)
+            if (slot_of_user[(size_t)users[j]] < 0) slot_of_user[(size_t)users[j]] = n_slots++;
+        if ((rc = count_exclusions(h, kRecommend, slot_of_user, n_rows, excl_u, excl_i, n_excl, &kept))) return rc;
+    }
+    if (n_users == 0) return MFSGD_OK;
+    if (host_rows && h->where == mfsgd_handle::Where::None)  // (asked here: factors_to_device wants a device first)
+        return fail(h, MFSGD_ERR_STATE, "recommend_rows: factors not initialised");
+    if ((rc = factors_to_device(h))) return rc;
+    const int32_t I = h->cfg.n_items;
+    const bool fused = recommend_is_fused(I, topn);  // score + select in one kernel, no score buffers
+    // users per batch: about 64 M scores at a time (the sort path materialises them)
+    int batch = (int)std::max<int64_t>(1, std::min<int64_t>(n_users, ((int64_t)64 << 20) / std::max(1, I)));
+    if (fused) batch = n_users;
+    batch = std::min(batch, 65535);
+    auto bad = [h](hipError_t e) { return serve_fail(h, "recommend: ", e); };
+    DevBuf d_rows, d_users, s_in, s_out, id_in, id_out, d_off, o_s, o_i, ex_slot, ex_off, ex_items;
+    DevBuf temp;  // of the sorts: one for the exclusion lists and every batch, grown when one needs more
+    const float* P;
+    if ((rc = upload_rows(h, host_rows, n_rows, d_rows, &P))) return rc;
+    const float* Q = h->dQ.as<const float>();
+    RecommendExcl ex;  // built once for all batches; none when no pair belongs to a requested user
+    if (kept > 0 && (rc = exclusions_to_device(h, kRecommend, slot_of_user, n_slots, excl_u, excl_i, n_excl, kept, ex_slot,
+                                               ex_off, ex_items, temp, ex)))
+        return rc;
+    const size_t cells = (size_t)batch * (size_t)I;
+    if ((rc = dev_alloc(h, d_users, sizeof(int32_t) * (size_t)batch))) return rc;
+    if (!fused) {
+        if ((rc = dev_alloc(h, s_in, 4 * cells))) return rc;
+        if ((rc = dev_alloc(h, s_out, 4 * cells))) return rc;
+        if ((rc = dev_alloc(h, id_in, 4 * cells))) return rc;
+        if ((rc = dev_alloc(h, id_out, 4 * cells))) return rc;
+        if ((rc = dev_alloc(h, d_off, sizeof(long long) * ((size_t)batch + 1)))) return rc;
+    }
+    if ((rc = dev_alloc(h, o_s, 4 * (size_t)batch * topn))) return rc;
+    if ((rc = dev_alloc(h, o_i, 4 * (size_t)batch * topn))) return rc;
+    for (int32_t done = 0; done < n_users; done += batch) {
+        const int nb = std::min<int32_t>(batch, n_users - done);
+        const int32_t* du = d_users.as<const int32_t>();
+        HIPCHK_OR(bad, hipMemcpyAsync(d_users.get(), users + done, sizeof(int32_t) * (size_t)nb, hipMemcpyHostToDevice, h->stream));
+        if (fused)
+            HIPCHK_OR(bad, recommend_fused(h->geo.L, P, Q, du, nb, I, topn, ex, o_s.as<float>(), o_i.as<int32_t>(), h->stream));
+        else
+            HIPCHK_OR(bad, recommend_batch(h->geo.L, P, Q, du, nb, I, topn, ex, s_in.as<float>(), s_out.as<float>(),
+                                           id_in.as<int32_t>(), id_out.as<int32_t>(), d_off.as<long long>(), temp,
+                                           o_s.as<float>(), o_i.as<int32_t>(), h->stream));
+        HIPCHK_OR(bad, hipMemcpyAsync(out_scores + (size_t)done * topn, o_s.get(), 4 * (size_t)nb * topn, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK_OR(bad, hipMemcpyAsync(out_items + (size_t)done * topn, o_i.get(), 4 * (size_t)nb * topn, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
+    }
+    return MFSGD_OK;
+}
+
+// Pairs of one rank launch (whole users; a single user with more is a launch of its own): 16 MB of items up, as much
+// of ranks down
+constexpr int64_t kRankChunk = (int64_t)1 << 22;
+
+// Body of the rank calls, generic over the row matrix as recommend_core is: "user j" is row j of a matrix of n_rows
+// rows, the model's P (host_rows == nullptr) or host_rows (n_rows x k, dense).  The pairs are grouped by distinct
+// user on the host (counting sort; one slot per user, the slot numbering the exclusion lists use too), go up in
+// bounded pieces of whole users, and the ranks come back to the places of the pairs as given.
+static int rank_core(mfsgd_handle* h, const float* host_rows, int32_t n_rows, const int32_t* users, const int32_t* items,
+                     int64_t n, const int32_t* excl_u, const int32_t* excl_i, int64_t n_excl, int32_t* out_rank) {
+    if (n < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: n is negative");
+    if (n_excl < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: n_excl is negative");
+    if (n > 0 && (!users || !items || !out_rank))
+        return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: users, items or out_rank is null");
+    if (n_excl > 0 && (!excl_u || !excl_i)) return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: an exclusion array is null");
+    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "rank_items: single-partition handles only");
+    const int32_t I = h->cfg.n_items;
+    for (int64_t x = 0; x < n; ++x)
+        if (users[x] < 0 || users[x] >= n_rows || items[x] < 0 || items[x] >= I)
+            return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: pair " + std::to_string(x) + " out of range");
+    // a slot per distinct user, and how many exclusion pairs are theirs
+    std::vector<int32_t> slot_of_user((size_t)n_rows, -1), row_of_slot;
+    std::vector<long long> off{0};
+    for (int64_t x = 0; x < n; ++x) {
+        int32_t& s = slot_of_user[(size_t)users[x]];
+        if (s < 0) {
+            s = (int32_t)row_of_slot.size();
+            row_of_slot.push_back(users[x]);
+            off.push_back(0);
+        }
+        ++off[(size_t)s + 1];
+    }
+    const int32_t n_slots = (int32_t)row_of_slot.size();
+    // The slots in the order of their pair counts, most first: a workgroup takes neighbouring slots and passes over Q
+    // once per round of its user with the most pairs, so users with many pairs belong together.
+    {
+        std::vector<int32_t> order((size_t)n_slots);
+        for (int32_t s = 0; s < n_slots; ++s) order[(size_t)s] = s;
+        std::stable_sort(order.begin(), order.end(),
+                         [&off](int32_t a, int32_t b) { return off[(size_t)a + 1] > off[(size_t)b + 1]; });
+        std::vector<int32_t> rows_sorted((size_t)n_slots);
+        std::vector<long long> off_sorted((size_t)n_slots + 1, 0);
+        for (int32_t s = 0; s < n_slots; ++s) {
+            rows_sorted[(size_t)s] = row_of_slot[(size_t)order[(size_t)s]];
+            off_sorted[(size_t)s + 1] = off[(size_t)order[(size_t)s] + 1];
+            slot_of_user[(size_t)rows_sorted[(size_t)s]] = s;
+        }
+        row_of_slot.swap(rows_sorted);
+        off.swap(off_sorted);
+    }
+    int64_t kept = 0;
+    int rc = count_exclusions(h, kRank, slot_of_user, n_rows, excl_u, excl_i, n_excl, &kept);
+    if (rc) return rc;
+    if (n == 0) return MFSGD_OK;
+    if (h->where == mfsgd_handle::Where::None)  // (asked here: factors_to_device wants a device first)
+        return fail(h, MFSGD_ERR_STATE, "rank_items: factors not initialised");
+    if ((rc = factors_to_device(h))) return rc;
+    // counting sort: the pairs of slot s at off[s] .. off[s + 1], in the order given; place[x] = where pair x went
+    for (int32_t s = 0; s < n_slots; ++s) off[(size_t)s + 1] += off[(size_t)s];
+    std::vector<int32_t> grouped((size_t)n), ranks((size_t)n);
+    std::vector<int64_t> place((size_t)n);
+    {
+        std::vector<long long> next(off.begin(), off.end() - 1);
+        for (int64_t x = 0; x < n; ++x) {
+            place[(size_t)x] = next[(size_t)slot_of_user[(size_t)users[x]]]++;
+            grouped[(size_t)place[(size_t)x]] = items[x];
+        }
+    }
+    std::vector<int32_t> cut{0};
+    int64_t max_pairs = 0;
+    for (int32_t s = 0; s < n_slots;) {
+        int32_t s1 = s + 1;
+        while (s1 < n_slots && off[(size_t)s1 + 1] - off[(size_t)s] <= kRankChunk) ++s1;
+        max_pairs = std::max<int64_t>(max_pairs, off[(size_t)s1] - off[(size_t)s]);
+        cut.push_back(s1);
+        s = s1;
+    }
+    auto bad = [h](hipError_t e) { return serve_fail(h, "rank_items: ", e); };
+    DevBuf d_rows, d_slot_rows, d_off, d_items, d_out, ex_slot, ex_off, ex_items, temp;
+    const float* P;
+    if ((rc = upload_rows(h, host_rows, n_rows, d_rows, &P))) return rc;
+    RecommendExcl ex;  // built once for all launches; none when no pair belongs to a user asked about
+    if (kept > 0 && (rc = exclusions_to_device(h, kRank, slot_of_user, n_slots, excl_u, excl_i, n_excl, kept, ex_slot, ex_off,
+                                               ex_items, temp, ex)))
+        return rc;
+    if ((rc = upload(h, d_slot_rows, row_of_slot))) return rc;
+    if ((rc = upload(h, d_off, off))) return rc;
+    if ((rc = dev_alloc(h, d_items, sizeof(int32_t) * (size_t)max_pairs))) return rc;
+    if ((rc = dev_alloc(h, d_out, sizeof(int32_t) * (size_t)max_pairs))) return rc;
+    for (size_t b = 0; b + 1 < cut.size(); ++b) {
+        const int32_t b0 = cut[b], nb = cut[b + 1] - b0;
+        const long long base = off[(size_t)b0];
+        const size_t bytes = sizeof(int32_t) * (size_t)(off[(size_t)(b0 + nb)] - base);
+        RecommendExcl exb = ex;
+        if (exb.off) exb.off += b0;
+        HIPCHK_OR(bad, hipMemcpyAsync(d_items.get(), grouped.data() + base, bytes, hipMemcpyHostToDevice, h->stream));
+        HIPCHK_OR(bad, launch_rank_items(h->geo.L, P, h->dQ.as<const float>(), d_slot_rows.as<const int32_t>() + b0, nb,
+                                         d_off.as<const long long>() + b0, base, d_items.as<const int32_t>(), I, exb,
+                                         d_out.as<int32_t>(), h->stream));
+        HIPCHK_OR(bad, hipMemcpyAsync(ranks.data() + base, d_out.get(), bytes, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // the staging buffers are reused
+    }
+    for (int64_t x = 0; x < n; ++x) out_rank[x] = ranks[(size_t)place[(size_t)x]];
+    return MFSGD_OK;
+}
+
+static int metrics_fail(int code, const std::string& msg) {
+    g_create_error = "ranking_metrics: " + msg;
+    return code;
+}
+
+// Ratings of one fold-in batch (whole users; a single user longer than this is a batch of its own): 32 MB of staging
+constexpr int64_t kFoldChunk = (int64_t)1 << 22;
+constexpr int64_t kFoldUsers = (int64_t)1 << 20;  // ... and its users, so that a run of empty users is bounded too
+
+}  // namespace mfsgd
+
+using namespace mfsgd;
+
+extern "C" {
+
+int mfsgd_predict(mfsgd_handle* h, const int32_t* u, const int32_t* i, float* out, int64_t n) {
+    return guarded(h, "predict", [&]() -> int {
+        if (n < 0 || (n > 0 && (!u || !i || !out))) return fail(h, MFSGD_ERR_INVALID_ARG, "predict: bad argument");
+        if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "predict: single-partition handles only");
+        for (int64_t j = 0; j < n; ++j)
+            if (u[j] < 0 || u[j] >= h->cfg.n_users || i[j] < 0 || i[j] >= h->cfg.n_items)
+                return fail(h, MFSGD_ERR_INVALID_ARG, "predict: pair " + std::to_string(j) + " out of range");
+        if (n == 0) return MFSGD_OK;
+        int rc = factors_to_device(h);
+        if (rc) return rc;
+        DevBuf du, di, dout;
+        if ((rc = dev_alloc(h, du, sizeof(int32_t) * (size_t)n))) return rc;
+        if ((rc = dev_alloc(h, di, sizeof(int32_t) * (size_t)n))) return rc;
+        if ((rc = dev_alloc(h, dout, sizeof(float) * (size_t)n))) return rc;
+        // (this call has always reported every HIP failure as MFSGD_ERR_HIP and left the runtime's error word alone)
+        auto bad = [h](hipError_t e) { return fail(h, MFSGD_ERR_HIP, std::string("predict: ") + hipGetErrorString(e)); };
+        HIPCHK_OR(bad, hipMemcpyAsync(du.get(), u, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+        HIPCHK_OR(bad, hipMemcpyAsync(di.get(), i, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+        HIPCHK_OR(bad, launch_predict(h->geo.L, h->dP.as<const float>(), h->dQ.as<const float>(), du.as<const int32_t>(),
+                                      di.as<const int32_t>(), dout.as<float>(), n, h->stream));
+        HIPCHK_OR(bad, hipMemcpyAsync(out, dout.get(), sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
+        return MFSGD_OK;
+    });
+}
+
+int mfsgd_recommend(mfsgd_handle* h, const int32_t* users, int32_t n_users, int32_t topn, int32_t* out_items,
+                    float* out_scores) {
+    return guarded(h, "recommend", [&]() -> int {
+        return recommend_core(h, nullptr, h->cfg.n_users, users, n_users, topn, nullptr, nullptr, 0, out_items, out_scores);
+    });
+}
+
+int mfsgd_recommend_excluding(mfsgd_handle* h, const int32_t* users, int32_t n_users, int32_t topn, const int32_t* excl_u,
+                              const int32_t* excl_i, int64_t n_excl, int32_t* out_items, float* out_scores) {
+    return guarded(h, "recommend", [&]() -> int {
+        return recommend_core(h, nullptr, h->cfg.n_users, users, n_users, topn, excl_u, excl_i, n_excl, out_items, out_scores);
+    });
+}
+
+int mfsgd_recommend_rows(mfsgd_handle* h, const float* rows, int32_t n_rows, int32_t topn, const int32_t* excl_row,
+                         const int32_t* excl_item, int64_t n_excl, int32_t* out_items, float* out_scores) {
+    return guarded(h, "recommend_rows", [&]() -> int {
+        if (n_rows < 0 || (n_rows > 0 && !rows)) return fail(h, MFSGD_ERR_INVALID_ARG, "recommend_rows: bad argument");
+        std::vector<int32_t> all((size_t)n_rows);
+        for (int32_t j = 0; j < n_rows; ++j) all[(size_t)j] = j;
+        return recommend_core(h, rows, n_rows, all.data(), n_rows, topn, excl_row, excl_item, n_excl, out_items,
+                              out_scores);
+    });
+}
+
+int mfsgd_rank_items(mfsgd_handle* h, const int32_t* users, const int32_t* items, int64_t n, const int32_t* excl_u,
+                     const int32_t* excl_i, int64_t n_excl, int32_t* out_rank) {
+    return guarded(h, "rank_items", [&]() -> int {
+        return rank_core(h, nullptr, h->cfg.n_users, users, items, n, excl_u, excl_i, n_excl, out_rank);
+    });
+}
+
+int mfsgd_rank_items_rows(mfsgd_handle* h, const float* rows, int32_t n_rows, const int32_t* row_of_pair,
+                          const int32_t* items, int64_t n, const int32_t* excl_row, const int32_t* excl_item,
+                          int64_t n_excl, int32_t* out_rank) {
+    return guarded(h, "rank_items", [&]() -> int {
+        if (n_rows < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: n_rows is negative");
+        if (n_rows > 0 && !rows) return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: rows is null");
+        return rank_core(h, rows, n_rows, row_of_pair, items, n, excl_row, excl_item, n_excl, out_rank);
+    });
+}
+
+int mfsgd_ranking_metrics_from_ranks(const int32_t* users, const int32_t* ranks, int64_t n, int32_t topn,
+                                     mfsgd_ranking_metrics* out) {
+    return guarded_free("ranking_metrics", [&]() -> int {
+        if (!out) return metrics_fail(MFSGD_ERR_INVALID_ARG, "out is null");
+        if (n < 0) return metrics_fail(MFSGD_ERR_INVALID_ARG, "n is negative");
+        if (topn < 1) return metrics_fail(MFSGD_ERR_INVALID_ARG, "topn is below 1");
+        if (n > 0 && (!users || !ranks)) return metrics_fail(MFSGD_ERR_INVALID_ARG, "users or ranks is null");
+        for (int64_t x = 0; x < n; ++x)
+            if (ranks[x] < 0) return metrics_fail(MFSGD_ERR_INVALID_ARG, "rank " + std::to_string(x) + " is negative");
+        *out = mfsgd_ranking_metrics{};
+        out->n_pairs = n;
+        if (n == 0) return MFSGD_OK;
+        // ascending user, and inside a user ascending rank: every sum below has one order whatever the caller's was
+        std::vector<std::pair<int32_t, int32_t>> ur((size_t)n);
+        for (int64_t x = 0; x < n; ++x) ur[(size_t)x] = {users[x], ranks[x]};
+        std::sort(ur.begin(), ur.end());
+        std::vector<double> idcg{0.0};  // [m]: the DCG of m hits in the first m places
+        double hit = 0, prec = 0, rec = 0, ndcg = 0, mrr = 0;
+        int64_t n_users = 0;
+        for (size_t a = 0; a < ur.size();) {
+            size_t b = a;
+            int64_t hits = 0;
+            double dcg = 0.0;
+            for (; b < ur.size() && ur[b].first == ur[a].first; ++b)
+                if (ur[b].second < topn) {
+                    ++hits;
+                    dcg += 1.0 / std::log2((double)ur[b].second + 2.0);
+                }
+            const size_t m = std::min<size_t>(b - a, (size_t)topn);
+            while (idcg.size() <= m) idcg.push_back(idcg.back() + 1.0 / std::log2((double)idcg.size() + 1.0));
+            hit += hits > 0 ? 1.0 : 0.0;
+            prec += (double)hits / (double)topn;
+            rec += (double)hits / (double)(b - a);
+            ndcg += dcg / idcg[m];
+            mrr += 1.0 / ((double)ur[a].second + 1.0);  // (the user's lowest rank comes first)
+            ++n_users;
+            a = b;
+        }
+        out->n_users = n_users;
+        out->hit_rate = hit / (double)n_users;
+        out->precision = prec / (double)n_users;
+        out->recall = rec / (double)n_users;
+        out->ndcg = ndcg / (double)n_users;
+        out->mrr = mrr / (double)n_users;
+        return MFSGD_OK;
+    });
+}
+
+int mfsgd_evaluate_ranking(mfsgd_handle* h, const int32_t* users, const int32_t* items, int64_t n, int32_t topn,
+                           const int32_t* excl_u, const int32_t* excl_i, int64_t n_excl, mfsgd_ranking_metrics* out,
+                           int32_t* out_rank) {
+    return guarded(h, "rank_items", [&]() -> int {
+        if (topn < 1) return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: topn is below 1");
+        if (!out) return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: the metrics struct is null");
+        std::vector<int32_t> own;
+        if (!out_rank && n > 0) {
+            own.resize((size_t)n);
+            out_rank = own.data();
+        }
+        int rc = rank_core(h, nullptr, h->cfg.n_users, users, items, n, excl_u, excl_i, n_excl, out_rank);
+        if (rc) return rc;
+        rc = mfsgd_ranking_metrics_from_ranks(users, out_rank, n, topn, out);
+        if (rc) return fail(h, rc, g_create_error);
+        return MFSGD_OK;
+    });
+}
+
+int mfsgd_fold_in_users(mfsgd_handle* h, int32_t n_new, const int64_t* row_ptr, const int32_t* items, const float* ratings,
+                        int32_t epochs, const float* init_rows, int64_t seed, float* out_rows) {
+    return guarded(h, "fold_in", [&]() -> int {
+        if (n_new < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "fold_in: n_new is negative");
+        if (epochs < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "fold_in: epochs is negative");
+        if (n_new > 0 && (!row_ptr || !out_rows)) return fail(h, MFSGD_ERR_INVALID_ARG, "fold_in: row_ptr or out_rows is null");
+        if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "fold_in: single-partition handles only");
+        if (h->where == mfsgd_handle::Where::None)  // (asked here: factors_to_device wants a device first)
+            return fail(h, MFSGD_ERR_STATE, "fold_in: factors not initialised");
+        if (n_new == 0) return MFSGD_OK;
+        if (row_ptr[0] != 0) return fail(h, MFSGD_ERR_INVALID_ARG, "fold_in: row_ptr[0] is not 0");
+        for (int32_t x = 0; x < n_new; ++x)
+            if (row_ptr[x + 1] < row_ptr[x])
+                return fail(h, MFSGD_ERR_INVALID_ARG, "fold_in: row_ptr decreases at user " + std::to_string(x));
+        const int64_t total = row_ptr[n_new];
+        if (total > 0 && (!items || !ratings)) return fail(h, MFSGD_ERR_INVALID_ARG, "fold_in: items or ratings is null");
+        for (int64_t j = 0; j < total; ++j)
+            if (items[j] < 0 || items[j] >= h->cfg.n_items)
+                return fail(h, MFSGD_ERR_INVALID_ARG, "fold_in: item of rating " + std::to_string(j) + " out of range");
+        int rc = factors_to_device(h);
+        if (rc) return rc;
+        const int k = h->cfg.k;
+        // batches of whole users, in the caller's order, so that each batch is one contiguous piece of items / ratings
+        std::vector<int32_t> cut{0};
+        int64_t max_ratings = 0, max_users = 0;
+        for (int32_t u0 = 0; u0 < n_new;) {
+            int32_t u1 = u0 + 1;
+            while (u1 < n_new && u1 - u0 < kFoldUsers && row_ptr[u1 + 1] - row_ptr[u0] <= kFoldChunk) ++u1;
+            max_ratings = std::max<int64_t>(max_ratings, row_ptr[u1] - row_ptr[u0]);
+            max_users = std::max<int64_t>(max_users, u1 - u0);
+            cut.push_back(u1);
+            u0 = u1;
+        }
+        auto bad = [h](hipError_t e) { return serve_fail(h, "fold_in: ", e); };
+        DevBuf d_rows, d_ptr, d_perm, d_items, d_r;
+        const size_t row_bytes = sizeof(float) * (size_t)n_new * (size_t)k;
+        if ((rc = dev_alloc(h, d_rows, row_bytes))) return rc;
+        if (epochs > 0 && total > 0) {
+            if ((rc = dev_alloc(h, d_ptr, sizeof(int64_t) * ((size_t)max_users + 1)))) return rc;
+            if ((rc = dev_alloc(h, d_perm, sizeof(int32_t) * (size_t)max_users))) return rc;
+            if ((rc = dev_alloc(h, d_items, sizeof(int32_t) * (size_t)max_ratings))) return rc;
+            if ((rc = dev_alloc(h, d_r, sizeof(float) * (size_t)max_ratings))) return rc;
+        }
+        // the start rows, dense: the kernel pads them to kp in its registers
+        if (init_rows)
+            HIPCHK_OR(bad, hipMemcpyAsync(d_rows.get(), init_rows, row_bytes, hipMemcpyHostToDevice, h->stream));
+        else
+            HIPCHK_OR(bad, launch_init_rows(d_rows.as<float>(), n_new, k, k, seed, 0, (float)(1.0 / std::sqrt((double)k)), h->stream));
+        std::vector<int32_t> perm;
+        for (size_t b = 0; b + 1 < cut.size() && epochs > 0; ++b) {
+            const int32_t u0 = cut[b], nb = cut[b + 1] - cut[b];
+            const int64_t base = row_ptr[u0], nr = row_ptr[u0 + nb] - base;
+            if (nr == 0) continue;
+            // longest first: a wave runs as long as its longest user
+            perm.resize((size_t)nb);
+            for (int32_t x = 0; x < nb; ++x) perm[(size_t)x] = x;
+            const int64_t* rp = row_ptr + u0;
+            std::stable_sort(perm.begin(), perm.end(), [rp](int32_t a, int32_t b2) { return rp[a + 1] - rp[a] > rp[b2 + 1] - rp[b2]; });
+            HIPCHK_OR(bad, hipMemcpyAsync(d_ptr.get(), rp, sizeof(int64_t) * ((size_t)nb + 1), hipMemcpyHostToDevice, h->stream));
+            HIPCHK_OR(bad, hipMemcpyAsync(d_perm.get(), perm.data(), sizeof(int32_t) * (size_t)nb, hipMemcpyHostToDevice, h->stream));
+            HIPCHK_OR(bad, hipMemcpyAsync(d_items.get(), items + base, sizeof(int32_t) * (size_t)nr, hipMemcpyHostToDevice, h->stream));
+            HIPCHK_OR(bad, hipMemcpyAsync(d_r.get(), ratings + base, sizeof(float) * (size_t)nr, hipMemcpyHostToDevice, h->stream));
+            HIPCHK_OR(bad, launch_fold_in(h->geo.L, h->dQ.as<const float>(), d_rows.as<float>() + (size_t)u0 * k, k,
+                                          d_ptr.as<const long long>(), base, d_perm.as<const int32_t>(), nb,
+                                          d_items.as<const int32_t>(), d_r.as<const float>(), epochs, h->cfg.lr,
+                                          1.0f - h->cfg.lr * h->cfg.lambda, h->stream));
+            HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // perm and the staging buffers are reused
+        }
+        HIPCHK_OR(bad, hipMemcpyAsync(out_rows, d_rows.get(), row_bytes, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
+        return MFSGD_OK;
+    });
+}
+
+}  // extern "C"

@@ -109,6 +109,26 @@ def test_fit_schedule_equals_the_manual_loop(mf):
         assert m.debug_counters()["graphs"] <= 32
 
 
+@pytest.mark.parametrize("rmse", [True, False])
+def test_fit_equals_a_constant_schedule(mf, rmse):
+    """mfsgd_train and mfsgd_train_schedule with the handle's own lr throughout run one loop: the same factors and the
+    same RMSE values, bit for bit, with and without RMSE output."""
+    name, epochs = "solo_k64_w2", 3
+    with fresh(mf, name, 0.01, 0.05) as m, fresh(mf, name, 0.01, 0.05) as s:
+        for x in (m, s):
+            x.init_factors()
+        a = m.fit(epochs, rmse=rmse)
+        b = s.fit_schedule([s.hyper()[0]] * epochs, rmse=rmse)
+        if rmse:
+            assert len(a) == len(b) == epochs
+            np.testing.assert_array_equal(np.asarray(a), np.asarray(b))
+        else:
+            assert a is None and b is None
+        for x, y in zip(m.get_factors(), s.get_factors()):
+            np.testing.assert_array_equal(x, y)
+        assert m.hyper() == s.hyper()
+
+
 def test_bold_driver_follows_its_rule(mf, oracle):
     name, lr0, lam, up, down, epochs = "solo_k64_w2", 0.01, 0.05, 2.0, 0.5, 7
     k, kw, U, I, u, i, r = _problem(name)
