@@ -1,4 +1,5 @@
-// devmem.hpp -- the owner of device memory: every hipMalloc of the library lives in a DevBuf, which frees it.
+// devmem.hpp -- the owners of what the device lends: every hipMalloc of the library lives in a DevBuf, which frees it;
+// the DSGD ring's streams and events live in a Stream / an Event.
 // Host-compilable (the C-ABI units, dsgd.cpp): the runtime API only.
 #pragma once
 
@@ -77,5 +78,40 @@ private:
     void* p_ = nullptr;
     size_t bytes_ = 0;
 };
+
+// The owner of a stream or an event: empty until create(flags), destroyed with its owner, handed to the runtime as
+// the plain handle it converts to.
+template <class H, hipError_t (*Create)(H*, unsigned), hipError_t (*Destroy)(H)>
+class DevHandle {
+public:
+    DevHandle() = default;
+    DevHandle(const DevHandle&) = delete;
+    DevHandle& operator=(const DevHandle&) = delete;
+    DevHandle(DevHandle&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    DevHandle& operator=(DevHandle&& o) noexcept {
+        if (this != &o) {
+            reset();
+            h_ = o.h_;
+            o.h_ = nullptr;
+        }
+        return *this;
+    }
+    ~DevHandle() { reset(); }
+
+    hipError_t create(unsigned flags) {
+        reset();
+        return Create(&h_, flags);
+    }
+    operator H() const { return h_; }
+    void reset() {
+        if (h_) (void)Destroy(h_);
+        h_ = nullptr;
+    }
+
+private:
+    H h_ = nullptr;
+};
+using Stream = DevHandle<hipStream_t, hipStreamCreateWithFlags, hipStreamDestroy>;
+using Event = DevHandle<hipEvent_t, hipEventCreateWithFlags, hipEventDestroy>;
 
 }  // namespace mfsgd

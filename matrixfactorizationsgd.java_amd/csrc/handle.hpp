@@ -1,6 +1,7 @@
-// handle.hpp -- what the units of the C-ABI share (handle.cpp, ratings.cpp, train.cpp, serve.cpp): the handle, its
-// partitions, the error channel, the guard every `int` entry point runs in, and the helpers that cross units.
-// Internal: installed nowhere.  dsgd.cpp and io.cpp see the handle through include/mfsgd.h only.
+// handle.hpp -- what the units of the C-ABI that see inside the handle share (handle.cpp, ratings.cpp, train.cpp,
+// serve.cpp): the handle, its partitions, the error channel, the guard with that channel, and the helpers that cross
+// units.  Internal: installed nowhere.  dsgd.cpp and io.cpp see the handle through include/mfsgd.h only, and take the
+// guard from guard.hpp.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -15,6 +16,7 @@
 
 #include "../../include/mfsgd.h"
 #include "devmem.hpp"
+#include "guard.hpp"
 #include "kernels.hpp"
 #include "schedule.hpp"
 
@@ -113,33 +115,8 @@ int hip_fail(const mfsgd_handle* h, const std::string& what, hipError_t e);
 // ... and most of them leave no error behind in the runtime
 int serve_fail(const mfsgd_handle* h, const char* prefix, hipError_t e);
 
-// The guard: no C++ exception crosses the boundary (include/mfsgd.h).  Every `int` entry point runs its body in
-// guarded() or, without a handle, in guarded_free().  `report` turns (code, what) into the return value; should even
-// the message not fit into memory, the code goes back alone.
-template <class F, class R>
-int guard_run(F&& body, int other, R&& report) noexcept {
-    int code = other;
-    const char* what = "out of host memory";
-    std::string kept;
-    try {
-        return body();
-    } catch (const std::bad_alloc&) {
-        code = MFSGD_ERR_OOM;
-    } catch (const std::exception& e) {
-        try {
-            kept = e.what();
-            what = kept.c_str();
-        } catch (const std::exception&) {
-            what = "";
-        }
-    }
-    try {
-        return report(code, what);
-    } catch (const std::exception&) {
-        return code;
-    }
-}
-
+// The guard (guard.hpp) with this error channel: every `int` entry point of the four units runs its body in guarded()
+// or, without a handle, in guarded_free().
 // A null handle is MFSGD_ERR_INVALID_ARG.  std::bad_alloc becomes MFSGD_ERR_OOM, "<name>: out of host memory"; any other
 // std::exception becomes `other`, "<name>: <what()>".
 template <class F>

@@ -14,11 +14,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <new>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/mfsgd.h"
+#include "guard.hpp"
 
 struct mfsgd_ratings_file {
     std::vector<int32_t> u, i;
@@ -34,6 +35,18 @@ int io_fail(int code, const std::string& msg) {
     g_io_error = msg;
     return code;
 }
+
+// The guard (guard.hpp) with this unit's error channel.  Host code only: what is not std::bad_alloc is a size the
+// containers refuse.
+template <class F>
+int io_guarded(const char* name, F&& body) {
+    return mfsgd::guard_run(body, MFSGD_ERR_UNSUPPORTED, [&](int code, const char* what) { return io_fail(code, std::string(name) + ": " + what); });
+}
+
+struct FileClose {
+    void operator()(FILE* f) const { (void)std::fclose(f); }
+};
+using File = std::unique_ptr<FILE, FileClose>;
 
 bool read_whole(const char* path, std::vector<char>& buf, std::string& err) {
     FILE* f = std::fopen(path, "rb");
@@ -209,8 +222,8 @@ const char* mfsgd_io_last_error(void) { return g_io_error.c_str(); }
 
 int mfsgd_ratings_file_open(const char* path, int32_t format, mfsgd_ratings_file** out) {
     if (out) *out = nullptr;
-    if (!path || !out) return io_fail(MFSGD_ERR_INVALID_ARG, "ratings_file_open: null argument");
-    try {
+    return io_guarded("ratings_file_open", [&]() -> int {
+        if (!path || !out) return io_fail(MFSGD_ERR_INVALID_ARG, "ratings_file_open: null argument");
         std::vector<char> buf;
         std::string err;
         if (!read_whole(path, buf, err)) return io_fail(MFSGD_ERR_INVALID_ARG, err);
@@ -227,15 +240,13 @@ int mfsgd_ratings_file_open(const char* path, int32_t format, mfsgd_ratings_file
         }
         if (!ok) return io_fail(MFSGD_ERR_INVALID_ARG, std::string(path) + ": " + err);
         if (uid.size() > 0x7FFFFFF0ull * 64) return io_fail(MFSGD_ERR_UNSUPPORTED, "too many ratings");
-        mfsgd_ratings_file* f = new mfsgd_ratings_file();
+        auto f = std::make_unique<mfsgd_ratings_file>();
         compact(uid, f->user_ids, f->u);
         compact(iid, f->item_ids, f->i);
         f->r.swap(r);
-        *out = f;
+        *out = f.release();
         return MFSGD_OK;
-    } catch (const std::bad_alloc&) {
-        return io_fail(MFSGD_ERR_OOM, "ratings_file_open: out of host memory");
-    }
+    });
 }
 
 int mfsgd_ratings_file_info(const mfsgd_ratings_file* f, int64_t* nnz, int32_t* n_users, int32_t* n_items) {
@@ -262,57 +273,48 @@ void mfsgd_ratings_file_close(mfsgd_ratings_file* f) { delete f; }
 
 // ---- factor files: "MFSGDF01", int32 U, I, k, reserved, then P (U x k) and Q (I x k), fp32 LE ----
 int mfsgd_save_factors(mfsgd_handle* h, const char* path) {
-    if (!h || !path) return io_fail(MFSGD_ERR_INVALID_ARG, "save_factors: null argument");
-    int32_t dims[3];
-    int rc = mfsgd_get_dims(h, &dims[0], &dims[1], &dims[2]);
-    if (rc) return rc;
-    try {
+    return io_guarded("save_factors", [&]() -> int {
+        if (!h || !path) return io_fail(MFSGD_ERR_INVALID_ARG, "save_factors: null argument");
+        int32_t dims[3];
+        int rc = mfsgd_get_dims(h, &dims[0], &dims[1], &dims[2]);
+        if (rc) return rc;
         std::vector<float> P((size_t)dims[0] * dims[2]), Q((size_t)dims[1] * dims[2]);
         rc = mfsgd_get_factors(h, P.data(), Q.data());
         if (rc) return rc;
-        FILE* f = std::fopen(path, "wb");
+        File f(std::fopen(path, "wb"));
         if (!f) return io_fail(MFSGD_ERR_INVALID_ARG, std::string("cannot create ") + path + ": " + std::strerror(errno));
         const int32_t hdr[4] = {dims[0], dims[1], dims[2], 0};
-        bool ok = std::fwrite("MFSGDF01", 1, 8, f) == 8 && std::fwrite(hdr, sizeof hdr, 1, f) == 1 &&
-                  std::fwrite(P.data(), sizeof(float), P.size(), f) == P.size() &&
-                  std::fwrite(Q.data(), sizeof(float), Q.size(), f) == Q.size();
-        ok = (std::fclose(f) == 0) && ok;
+        bool ok = std::fwrite("MFSGDF01", 1, 8, f.get()) == 8 && std::fwrite(hdr, sizeof hdr, 1, f.get()) == 1 &&
+                  std::fwrite(P.data(), sizeof(float), P.size(), f.get()) == P.size() &&
+                  std::fwrite(Q.data(), sizeof(float), Q.size(), f.get()) == Q.size();
+        ok = (std::fclose(f.release()) == 0) && ok;  // what the close flushes is part of the write
         if (!ok) return io_fail(MFSGD_ERR_INVALID_ARG, std::string("write failed: ") + path);
         return MFSGD_OK;
-    } catch (const std::bad_alloc&) {
-        return io_fail(MFSGD_ERR_OOM, "save_factors: out of host memory");
-    }
+    });
 }
 
 int mfsgd_load_factors(mfsgd_handle* h, const char* path) {
-    if (!h || !path) return io_fail(MFSGD_ERR_INVALID_ARG, "load_factors: null argument");
-    int32_t dims[3];
-    int rc = mfsgd_get_dims(h, &dims[0], &dims[1], &dims[2]);
-    if (rc) return rc;
-    FILE* f = std::fopen(path, "rb");
-    if (!f) return io_fail(MFSGD_ERR_INVALID_ARG, std::string("cannot open ") + path + ": " + std::strerror(errno));
-    char magic[8];
-    int32_t hdr[4];
-    if (std::fread(magic, 1, 8, f) != 8 || std::memcmp(magic, "MFSGDF01", 8) != 0 || std::fread(hdr, sizeof hdr, 1, f) != 1) {
-        std::fclose(f);
-        return io_fail(MFSGD_ERR_INVALID_ARG, std::string(path) + ": not a factor file");
-    }
-    if (hdr[0] != dims[0] || hdr[1] != dims[1] || hdr[2] != dims[2]) {
-        std::fclose(f);
-        return io_fail(MFSGD_ERR_INVALID_ARG, std::string(path) + ": shape " + std::to_string(hdr[0]) + "x" + std::to_string(hdr[1]) +
-                                                  " k=" + std::to_string(hdr[2]) + " does not match the handle");
-    }
-    try {
+    return io_guarded("load_factors", [&]() -> int {
+        if (!h || !path) return io_fail(MFSGD_ERR_INVALID_ARG, "load_factors: null argument");
+        int32_t dims[3];
+        int rc = mfsgd_get_dims(h, &dims[0], &dims[1], &dims[2]);
+        if (rc) return rc;
+        File f(std::fopen(path, "rb"));
+        if (!f) return io_fail(MFSGD_ERR_INVALID_ARG, std::string("cannot open ") + path + ": " + std::strerror(errno));
+        char magic[8];
+        int32_t hdr[4];
+        if (std::fread(magic, 1, 8, f.get()) != 8 || std::memcmp(magic, "MFSGDF01", 8) != 0 || std::fread(hdr, sizeof hdr, 1, f.get()) != 1)
+            return io_fail(MFSGD_ERR_INVALID_ARG, std::string(path) + ": not a factor file");
+        if (hdr[0] != dims[0] || hdr[1] != dims[1] || hdr[2] != dims[2])
+            return io_fail(MFSGD_ERR_INVALID_ARG, std::string(path) + ": shape " + std::to_string(hdr[0]) + "x" + std::to_string(hdr[1]) +
+                                                      " k=" + std::to_string(hdr[2]) + " does not match the handle");
         std::vector<float> P((size_t)dims[0] * dims[2]), Q((size_t)dims[1] * dims[2]);
-        const bool ok = std::fread(P.data(), sizeof(float), P.size(), f) == P.size() &&
-                        std::fread(Q.data(), sizeof(float), Q.size(), f) == Q.size();
-        std::fclose(f);
+        const bool ok = std::fread(P.data(), sizeof(float), P.size(), f.get()) == P.size() &&
+                        std::fread(Q.data(), sizeof(float), Q.size(), f.get()) == Q.size();
+        f.reset();
         if (!ok) return io_fail(MFSGD_ERR_INVALID_ARG, std::string(path) + ": truncated");
         return mfsgd_set_factors(h, P.data(), Q.data());
-    } catch (const std::bad_alloc&) {
-        std::fclose(f);
-        return io_fail(MFSGD_ERR_OOM, "load_factors: out of host memory");
-    }
+    });
 }
 
 }  // extern "C"

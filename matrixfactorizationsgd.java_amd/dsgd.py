@@ -160,6 +160,16 @@ class NativeDSGD:
             out[part.value] = blk
         return out
 
+    def set_block(self, j, array):
+        """Replaces the Q block in slot j of the group held with a rows x k host array (as home_blocks() gives them)."""
+        C = self._C
+        part, rows = C.c_int32(), C.c_int32()
+        self._check(self._lib.mfsgd_dsgd_get_q(self._d, int(j), C.byref(part), C.byref(rows), None))
+        blk = np.ascontiguousarray(array, np.float32)
+        if blk.shape != (rows.value, self.t.k):
+            raise ValueError(f"block of partition {part.value}: expected {(rows.value, self.t.k)}, got {blk.shape}")
+        self._check(self._lib.mfsgd_dsgd_set_q(self._d, int(j), blk.ctypes.data_as(C.POINTER(C.c_float))))
+
 
 class TorchDistRing:
     """Ring shift over torch.distributed (backend "nccl" = RCCL on ROCm, or gloo on CPU)."""

@@ -833,6 +833,54 @@ def test_native_dsgd_world1_self_ring(mf, oracle, m, k):
     assert np.array_equal(P1, Po)
 
 
+@pytest.mark.parametrize("k", [100, 5])
+def test_native_dsgd_blocks_round_trip_and_rings_come_and_go(mf, oracle, k):
+    """Rows narrower than their padding (k = 100 in kp = 128, k = 5 in kp = 8) through mfsgd_dsgd_get_q / set_q, and
+    ring after ring on one live trainer: three rings of one epoch each, every one seeded with the blocks its predecessor
+    brought home, equal the sequential definition of three epochs bit for bit; a block of ones comes back as it went
+    in, and no ring's first RMSE sees anything in the pad columns."""
+    from mfsgd_amd.dsgd import NativeDSGD, assemble_q
+
+    rng = np.random.default_rng(300 + k)
+    U, I, n, n_parts = 700, 500, 40000, 3
+    key = rng.choice(U * I, n, replace=False)
+    u, i, r = (key // I).astype(np.int32), (key % I).astype(np.int32), (rng.random(n) * 4 + 1).astype(np.float32)
+    rm0, rm, blocks = [], [], None
+    with mf.MatrixFactorizationSGD(U, I, k, LR, LAM, 5, n_parts=n_parts) as t:
+        t.set_ratings(u, i, r)
+        t.init_p_offset(5, 0)
+        for ring in range(3):
+            with NativeDSGD(t, 0, 1, NativeDSGD.unique_id()) as d:
+                assert d.m == n_parts
+                for j in range(n_parts):
+                    d.set_block(j, np.ones((t.part_rows(j), k), np.float32))
+                ones = d.home_blocks()
+                assert sorted(ones) == list(range(n_parts))
+                for j in range(n_parts):
+                    assert ones[j].shape == (t.part_rows(j), k) and np.array_equal(ones[j], np.ones_like(ones[j])), j
+                if blocks is None:
+                    d.init_q(5, U)
+                else:
+                    for j in range(n_parts):
+                        d.set_block(j, blocks[j])
+                rm0.append(d.rmse())
+                rm.extend(d.train(1))
+                blocks = d.home_blocks()
+        P1, _ = t.get_factors()
+        orders = [t.order(p)[0] for p in range(n_parts)]
+    Po, Qo = oracle.init_factors(U, I, k, 5)
+    ref0, ref = [], []
+    for _ in range(3):
+        ref0.append(oracle.rmse(Po, Qo, u, i, r))
+        for p in range(n_parts):
+            oracle.sgd_pass_ordered(Po, Qo, u, i, r, orders[p], LR, LAM)
+        ref.append(oracle.rmse(Po, Qo, u, i, r))
+    assert np.array_equal(P1, Po), "P after three rings differs from the sequential definition"
+    assert np.array_equal(assemble_q(blocks, I, k, n_parts), Qo), "Q blocks after three rings differ from the sequential definition"
+    np.testing.assert_allclose(rm, ref, rtol=1e-9)
+    np.testing.assert_allclose(rm0, ref0, rtol=0, atol=1e-9)
+
+
 def test_native_dsgd_recovers_when_a_persistent_launch_is_not_resident(mf, oracle):
     """The ring's recovery point (csrc/dsgd.cpp enqueue_epoch, mfsgd_part_settle): a foreign kernel holds the LDS of
     all but four CUs while the ring trains, so the persistent launches of its partitions find their workgroups not
