@@ -1,4 +1,5 @@
-// devmem.hpp -- the owners of what the device lends: every hipMalloc of the library lives in a DevBuf, which frees it;
+// devmem.hpp -- the owners of what the device lends: every hipMalloc of the library lives in a DevBuf, which frees it (a
+// pointer never leaves its DevBuf: ownership moves from one DevBuf to another);
 // the DSGD ring's streams and events live in a Stream / an Event.
 // Host-compilable (the C-ABI units, dsgd.cpp): the runtime API only.
 #pragma once
@@ -48,26 +49,18 @@ public:
         if (bytes == 0) bytes = 16;
         void* p = nullptr;
         const hipError_t e = hipMalloc(&p, bytes);
-        if (e == hipSuccess) adopt(p, bytes);
+        if (e == hipSuccess) {
+            p_ = p;
+            bytes_ = bytes;
+            g_dev_live_bytes.fetch_add((int64_t)bytes, std::memory_order_relaxed);
+        }
         return e;
     }
-    // Takes over a pointer that came from hipMalloc (null: ends up empty).
-    void adopt(void* p, size_t bytes) {
-        reset();
-        if (!p) return;
-        p_ = p;
-        bytes_ = bytes;
-        g_dev_live_bytes.fetch_add((int64_t)bytes, std::memory_order_relaxed);
-    }
-    // Gives the pointer up: the caller frees it (hipFree).
-    void* detach() {
-        void* p = p_;
+    void reset() {
+        if (!p_) return;
+        (void)hipFree(p_);
         g_dev_live_bytes.fetch_sub((int64_t)bytes_, std::memory_order_relaxed);
         forget();
-        return p;
-    }
-    void reset() {
-        if (p_) (void)hipFree(detach());
     }
 
 private:

@@ -1,10 +1,12 @@
-// ingest.hip -- see ingest.hpp.  Streaming passes over the COO triples: HBM-bound integer work
-// (coalesced reads of u/i, random 4-byte gathers of the bin maps, one LSD radix sort).
+// ingest.hip -- the implementation of DeviceIngest (ingest.hpp), the only one.  Streaming passes over the COO triples:
+// HBM-bound integer work (coalesced reads of u/i, random 4-byte gathers of the bin maps, one LSD radix sort), and the
+// host side of the device packer (pack.hip).  Every allocation is a DevBuf; what emit() produces leaves in DevBufs.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include <algorithm>
 #include <cstdint>
+#include <memory>
 #include <utility>
 #include <vector>
 
@@ -40,20 +42,54 @@ struct PackState {
     } one;
 };
 
-struct Ctx {
-    int device = 0;
-    // the triples stay on the device between degrees() and bucket() of the same arrays.  "The same arrays" is
-    // recognised by (pointer, pointer, length), which holds only WITHIN one build: a caller that builds several
-    // schedules from buffers it frees and allocates again (the partitions of a DSGD handle) gets the same addresses
-    // back from the allocator for different contents and must call DeviceIngest::forget between the builds
-    const int32_t* host_u = nullptr;
-    const int32_t* host_i = nullptr;
-    int64_t n = 0;
-    DevBuf du, di;                   // int32 x n each
-    PackState pk;
+// A list of parts (chunks) on the device, as the packing kernel's cells (upload_parts)
+struct PartList {
+    DevBuf sorted, cptr, info, subs;
 };
 
-// A HIP call failed: the callback answers -1 (the host loops take over); what it allocated goes with its owners.
+// The device ingest there is (ingest.hpp).  The loaded triples go to the device with the first call that needs them
+// and stay there, with what was derived from them, until drop() or the next load().
+struct Ingest final : DeviceIngest {
+    const int device;
+    const int32_t* u = nullptr;      // host: the loaded set
+    const int32_t* i = nullptr;
+    int64_t n = -1;
+    DevBuf du, di;                   // int32 x n each: its copy, once a call needed it
+    PackState pk;
+
+    explicit Ingest(int dev) : device(dev) {}
+    void load(const int32_t* u_, const int32_t* i_, int64_t n_) override {
+        drop();
+        u = u_;
+        i = i_;
+        n = n_;
+    }
+    void drop() override {
+        unload();
+        u = i = nullptr;
+        n = -1;
+    }
+    int64_t loaded() const override { return n; }
+    int degrees(int32_t U, int32_t I, int64_t* degu, int64_t* degi) override;
+    int bucket(const int32_t* ubin, const int32_t* ibin, int32_t U, int32_t I, int B, int W, int giants, int64_t* bptr,
+               int64_t* sorted) override;
+    int bucket_dev(const int32_t* ubin, const int32_t* ibin, int32_t U, int32_t I, int B, int W, int giants,
+                   int64_t* bptr) override;
+    int fetch_sorted32(uint32_t* sorted) override;
+    int fetch_sorted_ranges(int64_t n_ranges, const int64_t* lo, const int64_t* len, uint32_t* out) override;
+    int pack_count(const PackRequest& q, std::vector<PackCellInfo>& info) override;
+    int pack_count_parts(const PartsToEmit& parts, PackCellInfo* info) override;
+    int emit(const CellOffsets& cells, const PartsToEmit* parts, DevicePacked& out) override;
+
+    void unload();  // frees the device copy and what was derived from it
+    bool ensure_triples();
+    int bucket_on_device(const int32_t* ubin, const int32_t* ibin, int32_t U, int32_t I, int B, int W, int giants);
+    int fetch_bptr(int64_t* bptr);
+    int fetch_sorted(int64_t* sorted);
+    bool upload_parts(const PartsToEmit& parts, PartList& pl, PackArgs& a);
+};
+
+// A HIP call failed: the call answers -1 (the host loops take over); what it allocated goes with its owners.
 #define ING_CHK(call)                 \
     do {                              \
         if ((call) != hipSuccess) {   \
@@ -62,31 +98,24 @@ struct Ctx {
         }                             \
     } while (0)
 
-void drop_pack_state(Ctx* c) { c->pk = PackState{}; }
-
-void drop_triples(Ctx* c) {
-    drop_pack_state(c);
-    c->du.reset();
-    c->di.reset();
-    c->host_u = c->host_i = nullptr;
-    c->n = 0;
+void Ingest::unload() {
+    pk = PackState{};
+    du.reset();
+    di.reset();
 }
 
-bool ensure_triples(Ctx* c, const int32_t* u, const int32_t* i, int64_t n) {
-    if (c->host_u == u && c->host_i == i && c->n == n && c->du) return true;
-    drop_triples(c);
-    if (hipSetDevice(c->device) != hipSuccess) return false;
+bool Ingest::ensure_triples() {
+    if (du) return true;
+    if (n < 0) return false;
+    if (hipSetDevice(device) != hipSuccess) return false;
     const size_t bytes = (size_t)(n > 0 ? n : 1) * sizeof(int32_t);
-    if (c->du.alloc(bytes) != hipSuccess || c->di.alloc(bytes) != hipSuccess ||
-        hipMemcpy(c->du.get(), u, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(c->di.get(), i, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+    if (du.alloc(bytes) != hipSuccess || di.alloc(bytes) != hipSuccess ||
+        hipMemcpy(du.get(), u, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(di.get(), i, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipGetLastError();
-        drop_triples(c);
+        unload();
         return false;
     }
-    c->host_u = u;
-    c->host_i = i;
-    c->n = n;
     return true;
 }
 
@@ -152,18 +181,16 @@ int grid_for(int64_t n) {
     return (int)(g < 1 ? 1 : g);
 }
 
-int degrees_cb(void* vctx, const int32_t* u, const int32_t* i, int64_t n, int32_t U, int32_t I, int64_t* degu,
-               int64_t* degi) {
-    Ctx* c = static_cast<Ctx*>(vctx);
+int Ingest::degrees(int32_t U, int32_t I, int64_t* degu, int64_t* degi) {
     if (n >= (int64_t)1 << 32) return -1;
-    if (!ensure_triples(c, u, i, n)) return -1;
+    if (!ensure_triples()) return -1;
     std::vector<unsigned> hu((size_t)U), hi((size_t)I);
     {
         DevBuf bu, bi;
         ING_CHK(bu.alloc(sizeof(unsigned) * (size_t)U));
         ING_CHK(bi.alloc(sizeof(unsigned) * (size_t)I));
         unsigned *d_u = bu.as<unsigned>(), *d_i = bi.as<unsigned>();
-        const int32_t *du = c->du.as<int32_t>(), *di = c->di.as<int32_t>();
+        const int32_t *d_uu = du.as<int32_t>(), *d_ii = di.as<int32_t>();
         ING_CHK(hipMemset(d_u, 0, sizeof(unsigned) * (size_t)U));
         ING_CHK(hipMemset(d_i, 0, sizeof(unsigned) * (size_t)I));
         if (std::min(U, I) <= kDegLdsRows && n >= (1 << 20)) {
@@ -171,10 +198,10 @@ int degrees_cb(void* vctx, const int32_t* u, const int32_t* i, int64_t n, int32_
             const int n_small = items_small ? I : U;
             const size_t lds = 4 * (size_t)n_small;
             ING_CHK(hipFuncSetAttribute((const void*)degree_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(degree_lds_kernel, dim3(256), dim3(1024), lds, 0, items_small ? du : di, items_small ? di : du, n,
+            hipLaunchKernelGGL(degree_lds_kernel, dim3(256), dim3(1024), lds, 0, items_small ? d_uu : d_ii, items_small ? d_ii : d_uu, n,
                                items_small ? d_u : d_i, items_small ? d_i : d_u, n_small);
         } else {
-            hipLaunchKernelGGL(degree_kernel, dim3(grid_for(n)), dim3(256), 0, 0, du, di, n, d_u, d_i);
+            hipLaunchKernelGGL(degree_kernel, dim3(grid_for(n)), dim3(256), 0, 0, d_uu, d_ii, n, d_u, d_i);
         }
         ING_CHK(hipGetLastError());
         ING_CHK(hipMemcpy(hu.data(), d_u, sizeof(unsigned) * (size_t)U, hipMemcpyDeviceToHost));
@@ -186,13 +213,12 @@ int degrees_cb(void* vctx, const int32_t* u, const int32_t* i, int64_t n, int32_
 }
 
 // Keys, one stable LSD radix sort of (key, index) pairs, bucket starts.  Leaves the sorted indices and
-// the bucket starts on the device (c->pk.sorted, c->pk.bptr).
-int bucket_on_device(Ctx* c, const int32_t* u, const int32_t* i, int64_t n, const int32_t* ubin, const int32_t* ibin,
-                     int32_t U, int32_t I, int B, int W, int giants) {
+// the bucket starts on the device (pk.sorted, pk.bptr).
+int Ingest::bucket_on_device(const int32_t* ubin, const int32_t* ibin, int32_t U, int32_t I, int B, int W, int giants) {
     const int64_t nb = (int64_t)B * B * W * W;
     if (n >= (int64_t)1 << 32 || nb >= (int64_t)1 << 32) return -1;
-    if (!ensure_triples(c, u, i, n)) return -1;
-    drop_pack_state(c);
+    if (!ensure_triples()) return -1;
+    pk = PackState{};
     DevBuf d_ubin, d_ibin, k0, k1, v0, v1, d_bptr, temp;  // all but v1 and d_bptr go when this returns
     size_t temp_bytes = 0;
     const size_t nn = (size_t)(n > 0 ? n : 1);
@@ -208,7 +234,7 @@ int bucket_on_device(Ctx* c, const int32_t* u, const int32_t* i, int64_t n, cons
     ING_CHK(v1.alloc(4 * nn));
     ING_CHK(d_bptr.alloc(sizeof(long long) * (size_t)(nb + 1)));
     unsigned *key_in = k0.as<unsigned>(), *key_out = k1.as<unsigned>(), *val_in = v0.as<unsigned>(), *val_out = v1.as<unsigned>();
-    hipLaunchKernelGGL(key_kernel, dim3(grid_for(n)), dim3(256), 0, 0, c->du.as<int32_t>(), c->di.as<int32_t>(), n,
+    hipLaunchKernelGGL(key_kernel, dim3(grid_for(n)), dim3(256), 0, 0, du.as<int32_t>(), di.as<int32_t>(), n,
                        d_ubin.as<int32_t>(), d_ibin.as<int32_t>(), B, W, giants, key_in, val_in);
     ING_CHK(hipGetLastError());
     // LSD radix sort: stable, so equal keys keep their input order -- the host counting sort's order
@@ -218,37 +244,35 @@ int bucket_on_device(Ctx* c, const int32_t* u, const int32_t* i, int64_t n, cons
     hipLaunchKernelGGL(bound_kernel, dim3(grid_for(nb + 1)), dim3(256), 0, 0, key_out, n, nb, d_bptr.as<long long>());
     ING_CHK(hipGetLastError());
     ING_CHK(hipDeviceSynchronize());
-    c->pk.sorted = std::move(v1);
-    c->pk.bptr = std::move(d_bptr);
-    c->pk.nb = nb;
+    pk.sorted = std::move(v1);
+    pk.bptr = std::move(d_bptr);
+    pk.nb = nb;
     return 0;
 }
 
-int fetch_bptr(Ctx* c, int64_t* bptr) {
+int Ingest::fetch_bptr(int64_t* bptr) {
     static_assert(sizeof(long long) == sizeof(int64_t), "the bucket starts come down as they are");
-    if (hipMemcpy(bptr, c->pk.bptr.get(), sizeof(long long) * (size_t)(c->pk.nb + 1), hipMemcpyDeviceToHost) != hipSuccess) {
+    if (hipMemcpy(bptr, pk.bptr.get(), sizeof(long long) * (size_t)(pk.nb + 1), hipMemcpyDeviceToHost) != hipSuccess) {
         (void)hipGetLastError();
         return -1;
     }
     return 0;
 }
 
-int fetch_sorted_cb(void* vctx, int64_t* sorted) {
-    Ctx* c = static_cast<Ctx*>(vctx);
-    if (!c->pk.sorted) return -1;
-    std::vector<unsigned> hv((size_t)(c->n > 0 ? c->n : 1));
-    if (hipMemcpy(hv.data(), c->pk.sorted.get(), 4 * (size_t)c->n, hipMemcpyDeviceToHost) != hipSuccess) {
+int Ingest::fetch_sorted(int64_t* sorted) {
+    if (!pk.sorted) return -1;
+    std::vector<unsigned> hv((size_t)(n > 0 ? n : 1));
+    if (hipMemcpy(hv.data(), pk.sorted.get(), 4 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) {
         (void)hipGetLastError();
         return -1;
     }
-    for (int64_t j = 0; j < c->n; ++j) sorted[j] = (int64_t)hv[(size_t)j];
+    for (int64_t j = 0; j < n; ++j) sorted[j] = (int64_t)hv[(size_t)j];
     return 0;
 }
 
-int fetch_sorted32_cb(void* vctx, uint32_t* sorted) {
-    Ctx* c = static_cast<Ctx*>(vctx);
-    if (!c->pk.sorted) return -1;
-    if (c->n > 0 && hipMemcpy(sorted, c->pk.sorted.get(), 4 * (size_t)c->n, hipMemcpyDeviceToHost) != hipSuccess) {
+int Ingest::fetch_sorted32(uint32_t* sorted) {
+    if (!pk.sorted) return -1;
+    if (n > 0 && hipMemcpy(sorted, pk.sorted.get(), 4 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) {
         (void)hipGetLastError();
         return -1;
     }
@@ -263,14 +287,13 @@ __global__ void __launch_bounds__(256) gather_ranges_kernel(const unsigned* __re
     for (long long y = threadIdx.x; y < n; y += 256) out[d + y] = sorted[a + y];
 }
 
-int fetch_sorted_ranges_cb(void* vctx, int64_t n_ranges, const int64_t* lo, const int64_t* len, uint32_t* out) {
-    Ctx* c = static_cast<Ctx*>(vctx);
-    if (!c->pk.sorted || n_ranges < 0) return -1;
+int Ingest::fetch_sorted_ranges(int64_t n_ranges, const int64_t* lo, const int64_t* len, uint32_t* out) {
+    if (!pk.sorted || n_ranges < 0) return -1;
     if (n_ranges == 0) return 0;
     std::vector<long long> dst((size_t)n_ranges);
     long long total = 0;
     for (int64_t x = 0; x < n_ranges; ++x) {
-        if (lo[x] < 0 || len[x] < 0 || lo[x] + len[x] > c->n) return -1;
+        if (lo[x] < 0 || len[x] < 0 || lo[x] + len[x] > n) return -1;
         dst[(size_t)x] = total;
         total += len[x];
     }
@@ -284,34 +307,28 @@ int fetch_sorted_ranges_cb(void* vctx, int64_t n_ranges, const int64_t* lo, cons
     ING_CHK(hipMemcpy(d_lo.get(), lo, 8 * (size_t)n_ranges, hipMemcpyHostToDevice));
     ING_CHK(hipMemcpy(d_len.get(), len, 8 * (size_t)n_ranges, hipMemcpyHostToDevice));
     ING_CHK(hipMemcpy(d_dst.get(), dst.data(), 8 * (size_t)n_ranges, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(gather_ranges_kernel, dim3((unsigned)n_ranges), dim3(256), 0, 0, c->pk.sorted.as<unsigned>(),
+    hipLaunchKernelGGL(gather_ranges_kernel, dim3((unsigned)n_ranges), dim3(256), 0, 0, pk.sorted.as<unsigned>(),
                        d_lo.as<long long>(), d_len.as<long long>(), d_dst.as<long long>(), d_out.as<unsigned>());
     ING_CHK(hipGetLastError());
     ING_CHK(hipMemcpy(out, d_out.get(), 4 * (size_t)total, hipMemcpyDeviceToHost));
     return 0;
 }
 
-int bucket_dev_cb(void* vctx, const int32_t* u, const int32_t* i, int64_t n, const int32_t* ubin, const int32_t* ibin,
-                  int32_t U, int32_t I, int B, int W, int giants, int64_t* bptr) {
-    Ctx* c = static_cast<Ctx*>(vctx);
-    if (bucket_on_device(c, u, i, n, ubin, ibin, U, I, B, W, giants) != 0) return -1;
-    return fetch_bptr(c, bptr);
+int Ingest::bucket_dev(const int32_t* ubin, const int32_t* ibin, int32_t U, int32_t I, int B, int W, int giants,
+                       int64_t* bptr) {
+    if (bucket_on_device(ubin, ibin, U, I, B, W, giants) != 0) return -1;
+    return fetch_bptr(bptr);
 }
 
-int bucket_cb(void* vctx, const int32_t* u, const int32_t* i, int64_t n, const int32_t* ubin, const int32_t* ibin,
-              int32_t U, int32_t I, int B, int W, int giants, int64_t* bptr, int64_t* sorted) {
-    Ctx* c = static_cast<Ctx*>(vctx);
-    if (bucket_on_device(c, u, i, n, ubin, ibin, U, I, B, W, giants) != 0) return -1;
-    const int rc = fetch_bptr(c, bptr) == 0 && fetch_sorted_cb(c, sorted) == 0 ? 0 : -1;
-    drop_pack_state(c);
+int Ingest::bucket(const int32_t* ubin, const int32_t* ibin, int32_t U, int32_t I, int B, int W, int giants, int64_t* bptr,
+                   int64_t* sorted) {
+    if (bucket_on_device(ubin, ibin, U, I, B, W, giants) != 0) return -1;
+    const int rc = fetch_bptr(bptr) == 0 && fetch_sorted(sorted) == 0 ? 0 : -1;
+    pk = PackState{};
     return rc;
 }
 
-// ---- the device packer (pack.hip) behind the DeviceIngestExt callbacks ----------------------------
-void release_cb(void* p) {
-    if (p) (void)hipFree(p);
-}
-
+// ---- the device packer (pack.hip) -------------------------------------------------------------------
 // rank of every row among the rows of its block (block = bin % B), ascending row index
 void block_ranks(const int32_t* bin, int32_t n, int B, std::vector<int32_t>& rank, int32_t& max_rank) {
     std::vector<int32_t> next((size_t)B, 0);
@@ -321,9 +338,8 @@ void block_ranks(const int32_t* bin, int32_t n, int B, std::vector<int32_t>& ran
     for (int b = 0; b < B; ++b) max_rank = std::max(max_rank, next[(size_t)b]);
 }
 
-int pack_count_cb(void* vctx, const PackRequest& q, std::vector<PackCellInfo>& info) {
-    Ctx* c = static_cast<Ctx*>(vctx);
-    if (!c->pk.sorted || !c->pk.bptr || c->host_u != q.u || c->host_i != q.i || c->n != q.n) return -1;
+int Ingest::pack_count(const PackRequest& q, std::vector<PackCellInfo>& info) {
+    if (!pk.sorted || !pk.bptr) return -1;
     const int64_t n_cells = (int64_t)q.B * q.B, WW = (int64_t)q.W * q.W;
     if (n_cells >= (int64_t)1 << 31 || q.G > 64) return 1;
     std::vector<int32_t> ur, ir;
@@ -354,13 +370,12 @@ int pack_count_cb(void* vctx, const PackRequest& q, std::vector<PackCellInfo>& i
         worst.max_rows = rows_full;
         if (pack_lds_bytes(worst) > 160 * 1024 - 256) return 1;
     }
-    PackState& pk = c->pk;
-    const size_t nn = (size_t)std::max<int64_t>(q.n, 1);
+    const size_t nn = (size_t)std::max<int64_t>(n, 1);
     ING_CHK(pk.r.alloc(sizeof(float) * nn));
-    ING_CHK(hipMemcpy(pk.r.get(), q.r, sizeof(float) * (size_t)q.n, hipMemcpyHostToDevice));
+    ING_CHK(hipMemcpy(pk.r.get(), q.r, sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
     if (q.orig) {
         ING_CHK(pk.orig.alloc(sizeof(long long) * nn));
-        ING_CHK(hipMemcpy(pk.orig.get(), q.orig, sizeof(long long) * (size_t)q.n, hipMemcpyHostToDevice));
+        ING_CHK(hipMemcpy(pk.orig.get(), q.orig, sizeof(long long) * (size_t)n, hipMemcpyHostToDevice));
     }
     ING_CHK(pk.urank.alloc(sizeof(int32_t) * (size_t)q.U));
     ING_CHK(pk.irank.alloc(sizeof(int32_t) * (size_t)q.I));
@@ -368,8 +383,8 @@ int pack_count_cb(void* vctx, const PackRequest& q, std::vector<PackCellInfo>& i
     ING_CHK(hipMemcpy(pk.irank.get(), ir.data(), sizeof(int32_t) * (size_t)q.I, hipMemcpyHostToDevice));
     ING_CHK(pk.info.alloc(sizeof(PackCellInfo) * (size_t)n_cells));
     ING_CHK(pk.subs.alloc(sizeof(SubDesc) * (size_t)(n_cells * WW)));
-    a.u = c->du.as<int32_t>();
-    a.i = c->di.as<int32_t>();
+    a.u = du.as<int32_t>();
+    a.i = di.as<int32_t>();
     a.r = pk.r.as<float>();
     a.orig = pk.orig.as<long long>();
     a.sorted = pk.sorted.as<unsigned>();
@@ -382,7 +397,7 @@ int pack_count_cb(void* vctx, const PackRequest& q, std::vector<PackCellInfo>& i
     if (q.ord_off && !std::getenv("MFSGD_PACK_TWICE")) {  // (the variable: A/B measurements)
         // one-pass mode: scratch for rows and entries, the order array itself; if any of it does not fit, count only
         // (nor when the scratch would take more than a third of what is free: the final arrays come after it)
-        const size_t steps = pack_scratch_steps(q.n, n_cells, q.W);
+        const size_t steps = pack_scratch_steps(n, n_cells, q.W);
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
         const size_t need = sizeof(Entry) * steps * (size_t)q.G + 16 * nn;
@@ -418,28 +433,25 @@ int pack_count_cb(void* vctx, const PackRequest& q, std::vector<PackCellInfo>& i
 
 // A list of parts (chunks) as the packing kernel's cells: uploads it and returns the arguments of a launch over it
 // (COUNT outputs allocated), which live as long as `pl`.
-struct PartList {
-    DevBuf sorted, cptr, info, subs;
-};
-
-bool upload_parts(Ctx* c, int64_t n_parts, const uint32_t* sorted, int64_t n_sorted, const int64_t* cptr, PartList& pl, PackArgs& a) {
-    const int64_t WW = (int64_t)c->pk.args.W * c->pk.args.W;
+bool Ingest::upload_parts(const PartsToEmit& parts, PartList& pl, PackArgs& a) {
+    const int64_t n_parts = parts.n_parts, n_sorted = parts.n_sorted;
+    const int64_t WW = (int64_t)pk.args.W * pk.args.W;
     static_assert(sizeof(long long) == sizeof(int64_t), "cptr is uploaded as it is");
     if (pl.sorted.alloc(4 * (size_t)std::max<int64_t>(n_sorted, 1)) != hipSuccess ||
         pl.cptr.alloc(8 * (size_t)(n_parts * WW + 1)) != hipSuccess ||
         pl.info.alloc(sizeof(PackCellInfo) * (size_t)n_parts) != hipSuccess ||
         pl.subs.alloc(sizeof(SubDesc) * (size_t)(n_parts * WW)) != hipSuccess ||
-        hipMemcpy(pl.sorted.get(), sorted, 4 * (size_t)n_sorted, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(pl.cptr.get(), cptr, 8 * (size_t)(n_parts * WW + 1), hipMemcpyHostToDevice) != hipSuccess) {
+        hipMemcpy(pl.sorted.get(), parts.sorted, 4 * (size_t)n_sorted, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(pl.cptr.get(), parts.cptr, 8 * (size_t)(n_parts * WW + 1), hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipGetLastError();
         return false;
     }
-    a = c->pk.args;
+    a = pk.args;
     a.rows = nullptr;  // (a COUNT pass proper: the cells' one-pass scratch is not the parts')
     a.entries = nullptr;
     a.order = nullptr;
     a.ord_off = nullptr;
-    a.max_rows = c->pk.rows_full;  // a part can hold any number of rows a cell can
+    a.max_rows = pk.rows_full;  // a part can hold any number of rows a cell can
     a.sorted = pl.sorted.as<unsigned>();
     a.bptr = pl.cptr.as<long long>();
     a.info = pl.info.as<PackCellInfo>();
@@ -448,27 +460,16 @@ bool upload_parts(Ctx* c, int64_t n_parts, const uint32_t* sorted, int64_t n_sor
     return true;
 }
 
-int pack_count_parts_cb(void* vctx, int64_t n_parts, const uint32_t* sorted, int64_t n_sorted, const int64_t* cptr,
-                        PackCellInfo* info) {
-    Ctx* c = static_cast<Ctx*>(vctx);
-    if (!c->pk.info || n_parts < 0) return -1;
-    if (n_parts == 0) return 0;
+int Ingest::pack_count_parts(const PartsToEmit& parts, PackCellInfo* info) {
+    if (!pk.info || parts.n_parts < 0) return -1;
+    if (parts.n_parts == 0) return 0;
     PartList pl;
     PackArgs a{};
-    if (!upload_parts(c, n_parts, sorted, n_sorted, cptr, pl, a)) return -1;
-    ING_CHK(launch_pack(a, n_parts, (hipStream_t)0));
-    ING_CHK(hipMemcpy(info, pl.info.get(), sizeof(PackCellInfo) * (size_t)n_parts, hipMemcpyDeviceToHost));
+    if (!upload_parts(parts, pl, a)) return -1;
+    ING_CHK(launch_pack(a, parts.n_parts, (hipStream_t)0));
+    ING_CHK(hipMemcpy(info, pl.info.get(), sizeof(PackCellInfo) * (size_t)parts.n_parts, hipMemcpyDeviceToHost));
     return 0;
 }
-
-struct PartsToEmit {
-    int64_t n_parts = 0, n_sorted = 0;
-    const uint32_t* sorted = nullptr;
-    const int64_t* cptr = nullptr;
-    const uint32_t *row_off = nullptr, *ent_off = nullptr;
-    const int64_t* ord_off = nullptr;
-    const int64_t* desc = nullptr;  // the chunk descriptor of every part (final sub-cell table)
-};
 
 // fin[desc[y] * WW + x] = src[y * WW + x]: the parts' sub-cell tables to their chunk descriptors
 __global__ void __launch_bounds__(256) table_scatter_kernel(SubDesc* __restrict__ fin, const SubDesc* __restrict__ src,
@@ -478,23 +479,22 @@ __global__ void __launch_bounds__(256) table_scatter_kernel(SubDesc* __restrict_
     fin[desc[x / WW] * WW + x % WW] = src[x];
 }
 
-int emit_common(Ctx* c, const uint32_t* row_off, const uint32_t* ent_off, const int64_t* ord_off, int64_t n_rows,
-                int64_t n_steps, int64_t n_descs, DevicePacked* out, const PartsToEmit* parts = nullptr) {
-    PackState& pk = c->pk;
-    if (!pk.info || !out) return -1;
+int Ingest::emit(const CellOffsets& cells, const PartsToEmit* parts, DevicePacked& out) {
+    if (!pk.info) return -1;
+    const int64_t n_rows = cells.n_rows, n_steps = cells.n_steps, n_descs = cells.n_descs;
     PackArgs a = pk.args;
     DevBuf ro, eo, oo, pdesc;         // the offsets, for the length of this call
     DevBuf rows, ent, order, fin;     // what `out` gets: fin = the final sub-cell table
     const size_t nc = (size_t)pk.n_cells;
     const bool one_pass = (bool)pk.one.sent;  // the COUNT pass wrote what it packed: move it, do not pack again
     const size_t WWs = (size_t)a.W * a.W;
-    std::vector<long long> oo_host(ord_off, ord_off + nc);
+    std::vector<long long> oo_host(cells.ord_off, cells.ord_off + nc);
     if (n_descs < pk.n_cells) return -1;
     ING_CHK(ro.alloc(4 * nc));
     ING_CHK(eo.alloc(4 * nc));
     ING_CHK(oo.alloc(8 * nc));
-    ING_CHK(hipMemcpy(ro.get(), row_off, 4 * nc, hipMemcpyHostToDevice));
-    ING_CHK(hipMemcpy(eo.get(), ent_off, 4 * nc, hipMemcpyHostToDevice));
+    ING_CHK(hipMemcpy(ro.get(), cells.row_off, 4 * nc, hipMemcpyHostToDevice));
+    ING_CHK(hipMemcpy(eo.get(), cells.ent_off, 4 * nc, hipMemcpyHostToDevice));
     ING_CHK(hipMemcpy(oo.get(), oo_host.data(), 8 * nc, hipMemcpyHostToDevice));
     ING_CHK(rows.alloc(4 * (size_t)(n_rows + 4)));
     ING_CHK(hipMemset(rows.as<uint32_t>() + n_rows, 0, 16));  // the staging DMA reads whole 16-byte units
@@ -502,7 +502,7 @@ int emit_common(Ctx* c, const uint32_t* row_off, const uint32_t* ent_off, const 
     if (one_pass)
         order = std::move(pk.one.order);  // written by the COUNT pass, at its final place
     else
-        ING_CHK(order.alloc(8 * (size_t)std::max<int64_t>(c->n, 1)));
+        ING_CHK(order.alloc(8 * (size_t)std::max<int64_t>(n, 1)));
     a.row_off = ro.as<uint32_t>();
     a.ent_off = eo.as<uint32_t>();
     a.ord_off = oo.as<long long>();
@@ -530,7 +530,7 @@ int emit_common(Ctx* c, const uint32_t* row_off, const uint32_t* ent_off, const 
         PackArgs pa{};
         DevBuf p_ro, p_eo, p_oo;
         const size_t np = (size_t)parts->n_parts;
-        if (!upload_parts(c, parts->n_parts, parts->sorted, parts->n_sorted, parts->cptr, pl, pa)) return -1;
+        if (!upload_parts(*parts, pl, pa)) return -1;
         ING_CHK(launch_pack(pa, parts->n_parts, (hipStream_t)0));
         ING_CHK(p_ro.alloc(4 * np));
         ING_CHK(p_eo.alloc(4 * np));
@@ -557,81 +557,17 @@ int emit_common(Ctx* c, const uint32_t* row_off, const uint32_t* ent_off, const 
         ING_CHK(hipDeviceSynchronize());
     }
     ING_CHK(hipDeviceSynchronize());
-    out->rows = rows.detach();
-    out->entries = ent.detach();
-    out->order = order.detach();
-    out->subs = fin.detach();
-    out->n_subs = n_descs * (int64_t)WWs + 2;
-    out->release = release_cb;
-    drop_pack_state(c);
+    out.rows = std::move(rows);
+    out.entries = std::move(ent);
+    out.order = std::move(order);
+    out.subs = std::move(fin);
+    out.n_subs = n_descs * (int64_t)WWs + 2;
+    pk = PackState{};
     return 0;
 }
-
-int pack_emit_cb(void* vctx, const uint32_t* row_off, const uint32_t* ent_off, const int64_t* ord_off, int64_t n_rows,
-                 int64_t n_steps, DevicePacked* out) {
-    Ctx* c = static_cast<Ctx*>(vctx);
-    return emit_common(c, row_off, ent_off, ord_off, n_rows, n_steps, c->pk.n_cells, out);
-}
-
-int pack_emit_parts_cb(void* vctx, const uint32_t* row_off, const uint32_t* ent_off, const int64_t* ord_off, int64_t n_rows,
-                       int64_t n_steps, int64_t n_parts, const uint32_t* sorted, int64_t n_sorted, const int64_t* cptr,
-                       const uint32_t* p_row_off, const uint32_t* p_ent_off, const int64_t* p_ord_off, int64_t n_descs,
-                       const int64_t* p_desc, DevicePacked* out) {
-    PartsToEmit pe;
-    pe.desc = p_desc;
-    pe.n_parts = n_parts;
-    pe.n_sorted = n_sorted;
-    pe.sorted = sorted;
-    pe.cptr = cptr;
-    pe.row_off = p_row_off;
-    pe.ent_off = p_ent_off;
-    pe.ord_off = p_ord_off;
-    return emit_common(static_cast<Ctx*>(vctx), row_off, ent_off, ord_off, n_rows, n_steps, n_descs, out, &pe);
-}
-
-int download_cb(const DevicePacked& d, uint32_t* rows, int64_t n_rows, Entry* entries, int64_t n_entries, int64_t* order,
-                int64_t n) {
-    if (rows && n_rows > 0 && hipMemcpy(rows, d.rows, 4 * (size_t)n_rows, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    if (entries && n_entries > 0 &&
-        hipMemcpy(entries, d.entries, sizeof(Entry) * (size_t)n_entries, hipMemcpyDeviceToHost) != hipSuccess)
-        return -1;
-    if (order && n > 0 && hipMemcpy(order, d.order, 8 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    return 0;
-}
-
-int download_raw_cb(const void* dev, void* host, size_t bytes) {
-    if (bytes == 0) return 0;
-    if (!dev || !host || hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost) != hipSuccess) {
-        (void)hipGetLastError();
-        return -1;
-    }
-    return 0;
-}
-
-const DeviceIngestExt kExt = {bucket_dev_cb, fetch_sorted32_cb, fetch_sorted_ranges_cb, pack_count_cb, pack_emit_cb,
-                              pack_count_parts_cb, pack_emit_parts_cb, download_cb, download_raw_cb};
 
 }  // namespace
 
-DeviceIngest make_device_ingest(int device) {
-    DeviceIngest d;
-    Ctx* c = new Ctx();
-    c->device = device;
-    d.ctx = c;
-    d.degrees = degrees_cb;
-    d.bucket = bucket_cb;
-    d.forget = [](void* vctx) { drop_triples(static_cast<Ctx*>(vctx)); };
-    d.ext = &kExt;
-    return d;
-}
-
-void destroy_device_ingest(DeviceIngest& d) {
-    if (d.ctx) {
-        Ctx* c = static_cast<Ctx*>(d.ctx);
-        drop_triples(c);
-        delete c;
-    }
-    d = DeviceIngest{};
-}
+std::unique_ptr<DeviceIngest> make_device_ingest(int device) { return std::make_unique<Ingest>(device); }
 
 }  // namespace mfsgd

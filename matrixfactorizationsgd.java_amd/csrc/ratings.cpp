@@ -33,17 +33,16 @@ static int ensure_part_on_device(mfsgd_handle* h, Part& p) {
     if (p.on_device) return MFSGD_OK;
     int rc;
     if ((rc = upload(h, p.d_cells, p.sched.cells))) return rc;
-    DevicePacked& dev = p.sched.dev.buf;
+    DevicePacked& dev = p.sched.dev;
     if (p.sched.device_packed && dev.subs) {
-        // (the device assembled the sub-cell tables too)
-        p.d_subs.adopt(std::exchange(dev.subs, nullptr), (size_t)dev.n_subs * sizeof(SubDesc));
+        p.d_subs = std::move(dev.subs);  // (the device assembled the sub-cell tables too)
     } else if ((rc = upload(h, p.d_subs, p.sched.subs))) {
         return rc;
     }
     if (p.sched.device_packed) {
-        // the device packer left rows and entries where they are needed: the DevBufs own them from here on
-        p.d_rows.adopt(std::exchange(dev.rows, nullptr), (size_t)p.sched.n_rows_words * sizeof(uint32_t));
-        p.d_entries.adopt(std::exchange(dev.entries, nullptr), (size_t)p.sched.n_entry_recs * sizeof(Entry));
+        // the device packer left rows and entries where they are needed: the partition's DevBufs own them from here on
+        p.d_rows = std::move(dev.rows);
+        p.d_entries = std::move(dev.entries);
     } else {
         if ((rc = upload(h, p.d_rows, p.sched.rows))) return rc;
         if ((rc = upload(h, p.d_entries, p.sched.entries))) return rc;
@@ -71,30 +70,33 @@ int prepare_compute(mfsgd_handle* h) {
 static int host_copies(const mfsgd_handle* h, const Part& cp, bool want_order, bool want_arrays) {
     Part& p = const_cast<Part&>(cp);
     Schedule& s = p.sched;
-    if (!s.device_packed || !s.dev_ops || !s.dev_ops->download) return MFSGD_OK;
+    if (!s.device_packed) return MFSGD_OK;
+    // rows, entries and subs are the schedule's until the first compute call, the partition's after it
+    const DevBuf& d_rows = p.on_device ? p.d_rows : s.dev.rows;
+    const DevBuf& d_entries = p.on_device ? p.d_entries : s.dev.entries;
+    const DevBuf& d_subs = p.on_device ? p.d_subs : s.dev.subs;
+    auto download = [](void* host, const DevBuf& dev, size_t bytes) {
+        if (bytes == 0) return true;
+        if (bytes <= dev.bytes() && hipMemcpy(host, dev.get(), bytes, hipMemcpyDeviceToHost) == hipSuccess) return true;
+        (void)hipGetLastError();
+        return false;
+    };
     try {
-        DevicePacked d = s.dev.buf;
-        if (p.on_device) {  // rows / entries have moved into the DevBufs
-            d.rows = p.d_rows.get();
-            d.entries = p.d_entries.get();
-        }
         if (want_order && s.order.empty() && s.nnz > 0) {
             s.order.resize_uninit((size_t)s.nnz);
-            if (s.dev_ops->download(d, nullptr, 0, nullptr, 0, s.order.data(), s.nnz) != 0)
+            if (!download(s.order.data(), s.dev.order, s.order.size() * sizeof(int64_t)))
                 return fail(h, MFSGD_ERR_HIP, "could not copy the canonical order from the device");
         }
-        if (want_arrays && s.subs.empty() && s.n_sub_recs > 0 && s.dev_ops->download_raw) {
-            const void* dsubs = p.on_device ? p.d_subs.get() : s.dev.buf.subs;
-            if (dsubs) {
-                s.subs.resize((size_t)s.n_sub_recs);
-                if (s.dev_ops->download_raw(dsubs, s.subs.data(), s.subs.size() * sizeof(SubDesc)) != 0)
-                    return fail(h, MFSGD_ERR_HIP, "could not copy the sub-cell tables from the device");
-            }
+        if (want_arrays && s.subs.empty() && s.n_sub_recs > 0 && d_subs) {
+            s.subs.resize((size_t)s.n_sub_recs);
+            if (!download(s.subs.data(), d_subs, s.subs.size() * sizeof(SubDesc)))
+                return fail(h, MFSGD_ERR_HIP, "could not copy the sub-cell tables from the device");
         }
         if (want_arrays && s.entries.empty() && s.n_entry_recs > 0) {
             s.rows.resize_uninit((size_t)s.n_rows_words);
             s.entries.resize_uninit((size_t)s.n_entry_recs);
-            if (s.dev_ops->download(d, s.rows.data(), s.n_rows_words, s.entries.data(), s.n_entry_recs, nullptr, 0) != 0)
+            if (!download(s.rows.data(), d_rows, s.rows.size() * sizeof(uint32_t)) ||
+                !download(s.entries.data(), d_entries, s.entries.size() * sizeof(Entry)))
                 return fail(h, MFSGD_ERR_HIP, "could not copy the schedule from the device");
         }
         return MFSGD_OK;
@@ -239,7 +241,7 @@ static int check_range(const mfsgd_handle* h, const Triples& t) {
 // Ingestion (degree histograms, bucket order) runs on the GPU when there is one and the
 // rating set is large enough to pay for the upload; the host loops are the fallback.
 struct IngestContext {
-    DeviceIngest ingest;
+    std::unique_ptr<DeviceIngest> ingest;  // null: host loops
     IngestContext(mfsgd_handle* h, int64_t nnz) {
         const bool want_dev = !(h->cfg.flags & MFSGD_FLAG_HOST_INGEST) &&
                               ((h->cfg.flags & MFSGD_FLAG_DEVICE_INGEST) || nnz >= (int64_t)1 << 20);
@@ -247,13 +249,11 @@ struct IngestContext {
         if (ensure_device(h) == MFSGD_OK) ingest = make_device_ingest(h->cfg.device);
         else h->err.clear();  // no device: not an error for a host-side call
     }
-    IngestContext(const IngestContext&) = delete;
-    ~IngestContext() { destroy_device_ingest(ingest); }
 };
 
-static SchedParams sched_params(const mfsgd_handle* h, DeviceIngest& ingest) {
+static SchedParams sched_params(const mfsgd_handle* h, DeviceIngest* ingest) {
     SchedParams prm;
-    prm.ingest = ingest.ctx ? &ingest : nullptr;
+    prm.ingest = ingest;
     prm.U = h->cfg.n_users;
     prm.k = h->cfg.k;
     prm.lr = h->cfg.lr;
@@ -270,7 +270,7 @@ static SchedParams sched_params(const mfsgd_handle* h, DeviceIngest& ingest) {
     return prm;
 }
 
-static int build_single(mfsgd_handle* h, SchedParams prm, DeviceIngest& ingest, const Triples& t, Lap& lap) {
+static int build_single(mfsgd_handle* h, SchedParams prm, const Triples& t, Lap& lap) {
     const int32_t *u = t.u, *i = t.i;
     const int64_t nnz = t.nnz;
     Part& p = h->parts[0];
@@ -278,8 +278,9 @@ static int build_single(mfsgd_handle* h, SchedParams prm, DeviceIngest& ingest, 
     // rating counts per user and per item: on the device when it ingests, else here; they
     // decide which side carries the longest chain and are handed on to the scheduler
     std::vector<int64_t> du((size_t)h->cfg.n_users, 0), di((size_t)h->cfg.n_items, 0);
-    if (!(ingest.ctx && ingest.degrees &&
-          ingest.degrees(ingest.ctx, u, i, nnz, h->cfg.n_users, h->cfg.n_items, du.data(), di.data()) == 0)) {
+    DeviceIngest* const ingest = prm.ingest;
+    if (ingest) ingest->load(u, i, nnz);
+    if (!(ingest && ingest->degrees(h->cfg.n_users, h->cfg.n_items, du.data(), di.data()) == 0)) {
         std::fill(du.begin(), du.end(), 0);
         std::fill(di.begin(), di.end(), 0);
         for (int64_t j = 0; j < nnz; ++j) {
@@ -299,16 +300,18 @@ static int build_single(mfsgd_handle* h, SchedParams prm, DeviceIngest& ingest, 
     if (p.swapped) {
         prm.U = h->cfg.n_items;
         prm.I = h->cfg.n_users;
+        if (ingest) ingest->load(i, u, nnz);  // (the roles exchanged: another rating set to the device)
         rc = build_schedule_auto(prm, i, u, t.r, nullptr, nnz, p.sched, err);
     } else {
         prm.I = p.q_rows;
         rc = build_schedule_auto(prm, u, i, t.r, nullptr, nnz, p.sched, err);
     }
+    if (ingest) ingest->drop();
     if (rc != 0) return fail(h, MFSGD_ERR_SCHEDULE, err);
     return MFSGD_OK;
 }
 
-static int build_partitioned(mfsgd_handle* h, SchedParams prm, DeviceIngest& ingest, const Triples& t, Lap& lap) {
+static int build_partitioned(mfsgd_handle* h, SchedParams prm, const Triples& t, Lap& lap) {
     const int32_t *u = t.u, *i = t.i;
     const float* r = t.r;
     const int64_t nnz = t.nnz;
@@ -336,9 +339,9 @@ static int build_partitioned(mfsgd_handle* h, SchedParams prm, DeviceIngest& ing
         }
         Part& p = h->parts[(size_t)g];
         p.q_rows = h->part_q_rows[(size_t)g];
-        // uu / ii of two partitions of equal size sit at the same addresses (the allocator hands the block
-        // back): the ingest context must not take them for the arrays it already holds on the device
-        if (ingest.ctx && ingest.forget) ingest.forget(ingest.ctx);
+        // every partition is a rating set of its own to the device ingest (uu / ii of two partitions of equal size sit
+        // at the same addresses: the allocator hands the block back)
+        if (prm.ingest) prm.ingest->load(uu.data(), ii.data(), m);
         prm.I = std::max<int32_t>(1, p.q_rows);
         prm.validated = true;  // check_range checked; local rows are in range by construction
         // the partition's own rating counts per row: build_schedule_auto compares the longest chain with the
@@ -352,7 +355,9 @@ static int build_partitioned(mfsgd_handle* h, SchedParams prm, DeviceIngest& ing
         prm.degu = du.data();
         prm.degi = di.data();
         std::string err;
-        if (build_schedule_auto(prm, uu.data(), ii.data(), rr.data(), orig.data() + lo, m, p.sched, err) != 0)
+        const int rc = build_schedule_auto(prm, uu.data(), ii.data(), rr.data(), orig.data() + lo, m, p.sched, err);
+        if (prm.ingest) prm.ingest->drop();  // (uu / ii go with this iteration)
+        if (rc != 0)
             return fail(h, MFSGD_ERR_SCHEDULE, "partition " + std::to_string(g) + ": " + err);
     }
     return MFSGD_OK;
@@ -391,8 +396,8 @@ int mfsgd_set_ratings(mfsgd_handle* h, const int32_t* u, const int32_t* i, const
         h->parts.resize((size_t)h->n_parts);
         IngestContext ic(h, nnz);
         lap("device ingest context");
-        const SchedParams prm = sched_params(h, ic.ingest);
-        rc = h->n_parts == 1 ? build_single(h, prm, ic.ingest, t, lap) : build_partitioned(h, prm, ic.ingest, t, lap);
+        const SchedParams prm = sched_params(h, ic.ingest.get());
+        rc = h->n_parts == 1 ? build_single(h, prm, t, lap) : build_partitioned(h, prm, t, lap);
         if (rc) return rc;
         lap("schedules");
         commit_ratings(h, nnz, hash);

@@ -1,4 +1,5 @@
-// schedule.cpp -- see schedule.hpp.  Host only; no HIP calls.
+// schedule.cpp -- see schedule.hpp.  Host code that writes no HIP call of its own: the device is reached through
+// DeviceIngest (ingest.hpp) alone, and the device memory a schedule holds is owned by its DevBufs (devmem.hpp).
 //
 // build_schedule takes one of three routes (the comment above it says when):
 //  1. host: the host packs every cell, cuts those too large for the LDS image and assembles the schedule;
@@ -628,7 +629,7 @@ struct Builder {
     std::vector<int64_t> bptr;         // B*B*W*W + 1 bucket starts
     std::vector<int64_t> sorted;       // the bucket order, when the host has it ...
     std::vector<uint32_t> sorted32;    // ... or as it was fetched from the device (route 1 after a device refusal)
-    const DeviceIngestExt* ext = nullptr;  // the device holds the bucket order and packs (routes 2 and 3)
+    DeviceIngest* ext = nullptr;           // the device holds the bucket order and packs (routes 2 and 3)
     std::vector<PackCellInfo> info;        // the device's COUNT pass, per cell
     bool have_info = false;                // ... and it ran: a refusal from here on means route 3
 
@@ -728,7 +729,7 @@ bool Builder::setup() {
 
 // ---- degrees -------------------------------------------------------------------------------------------------------
 bool Builder::degrees() {
-    on_device = prm.ingest && prm.ingest->degrees && prm.ingest->bucket;
+    on_device = prm.ingest && prm.ingest->loaded() == n;
     if (on_device && !prm.validated) {
         for (int64_t j = 0; j < n && on_device; ++j)
             if (u[j] < 0 || u[j] >= U || i[j] < 0 || i[j] >= I) on_device = false;  // let the host loop report it
@@ -739,7 +740,7 @@ bool Builder::degrees() {
     } else {
         degu.assign((size_t)U, 0);
         degi.assign((size_t)I, 0);
-        if (on_device && prm.ingest->degrees(prm.ingest->ctx, u, i, n, U, I, degu.data(), degi.data()) != 0) {
+        if (on_device && prm.ingest->degrees(U, I, degu.data(), degi.data()) != 0) {
             on_device = false;
             std::fill(degu.begin(), degu.end(), 0);
             std::fill(degi.begin(), degi.end(), 0);
@@ -789,15 +790,12 @@ void Builder::bucket() {
     const int64_t nb = (int64_t)B * B * W * W;
     reserve_huge(bptr, (size_t)nb + 1);
     bptr.assign((size_t)nb + 1, 0);
-    const DeviceIngestExt* e = on_device && prm.device_pack && n > 0 ? prm.ingest->ext : nullptr;
-    if (e && e->bucket_dev && e->fetch_sorted32 && e->fetch_sorted_ranges && e->pack_count && e->pack_emit &&
-        e->pack_count_parts && e->pack_emit_parts && e->download_raw &&
-        e->bucket_dev(prm.ingest->ctx, u, i, n, ubin.data(), ibin.data(), U, I, B, W, giants, bptr.data()) == 0) {
-        ext = e;  // the bucket order stays on the device
+    if (on_device && prm.device_pack && n > 0 &&
+        prm.ingest->bucket_dev(ubin.data(), ibin.data(), U, I, B, W, giants, bptr.data()) == 0) {
+        ext = prm.ingest;  // the bucket order stays on the device
     } else {
         sorted.resize((size_t)n);
-        if (on_device && prm.ingest->bucket(prm.ingest->ctx, u, i, n, ubin.data(), ibin.data(), U, I, B, W, giants,
-                                            bptr.data(), sorted.data()) != 0) {
+        if (on_device && prm.ingest->bucket(ubin.data(), ibin.data(), U, I, B, W, giants, bptr.data(), sorted.data()) != 0) {
             on_device = false;
             std::fill(bptr.begin(), bptr.end(), 0);
         }
@@ -830,11 +828,8 @@ int Builder::device_whole_cells() {
     const char* why = "";
     const int rc = [&]() -> int {
         PackRequest q;
-        q.u = u;
-        q.i = i;
         q.r = r;
         q.orig = orig;
-        q.n = n;
         q.U = U;
         q.I = I;
         q.ubin = ubin.data();
@@ -868,7 +863,7 @@ int Builder::device_whole_cells() {
         cell_ptr[(size_t)ncell] = pos;
         if (pos != n) return -1;
         q.ord_off = ord_off.data();
-        int prc = ext->pack_count(prm.ingest->ctx, q, info);
+        const int prc = ext->pack_count(q, info);
         if (prc != 0) {
             why = "the rating set is outside the kernel's limits (cell size, ranks, LDS)";
             return prc;
@@ -939,11 +934,10 @@ int Builder::device_whole_cells() {
         }
         lap("  device pack: offsets");
         // (the sub-cell tables stay on the device: the emit call leaves the final one there, Schedule::subs stays empty)
-        prc = ext->pack_emit(prm.ingest->ctx, row_off.data(), ent_off.data(), ord_off.data(), rows, steps, &sch.dev.buf);
-        if (prc != 0) return -1;
+        const CellOffsets at{row_off.data(), ent_off.data(), ord_off.data(), rows, steps, ncell};
+        if (ext->emit(at, nullptr, sch.dev) != 0) return -1;
         lap("  device pack: emit");
         sch.device_packed = true;
-        sch.dev_ops = ext;
         sch.device_ingest = true;
         out = std::move(sch);
         return 0;
@@ -958,7 +952,7 @@ int Builder::device_whole_cells() {
 // Route 1 after a device refusal: the host packer needs the bucket order on this side (32-bit, as the device holds it).
 bool Builder::fetch_bucket_order() {
     sorted32.resize((size_t)n);
-    if (ext->fetch_sorted32(prm.ingest->ctx, sorted32.data()) != 0)
+    if (ext->fetch_sorted32(sorted32.data()) != 0)
         return fail("build_schedule: could not fetch the bucket order from the device");
     return true;
 }
@@ -1341,7 +1335,7 @@ bool Builder::fetch_cut_cells(std::vector<int64_t>& r_at) {
     const int64_t n_cut = r_at[todo.size()];
     reserve_huge(part_ratings, (size_t)n_cut);
     part_ratings.resize((size_t)n_cut);
-    if (ext->fetch_sorted_ranges(prm.ingest->ctx, (int64_t)todo.size(), r_lo.data(), r_len.data(), part_ratings.data()) != 0)
+    if (ext->fetch_sorted_ranges((int64_t)todo.size(), r_lo.data(), r_len.data(), part_ratings.data()) != 0)
         return fail("build_schedule: could not fetch the bucket order of the cells to be cut from the device");
     lap("  bucket order of the cut cells to the host");
     reserve_huge(part_sbs, (size_t)n_cut);
@@ -1410,8 +1404,12 @@ bool Builder::count_candidates(const std::vector<Part>& level, std::vector<size_
     });
     cptr[cand.size() * (size_t)WW] = c_at[cand.size()];
     clock.tick(clock.lists);
-    if (ext->pack_count_parts(prm.ingest->ctx, (int64_t)cand.size(), lst.data(), (int64_t)lst.size(), cptr.data(),
-                              pinfo.data()) != 0)
+    PartsToEmit parts;
+    parts.n_parts = (int64_t)cand.size();
+    parts.n_sorted = (int64_t)lst.size();
+    parts.sorted = lst.data();
+    parts.cptr = cptr.data();
+    if (ext->pack_count_parts(parts, pinfo.data()) != 0)
         return fail("build_schedule: the device packer's COUNT pass over the chunks failed");
     return true;
 }
@@ -1777,13 +1775,20 @@ bool Builder::assemble_on_device() {
     });
     p_cptr[parts.size() * (size_t)WW] = (int64_t)part_ratings.size();
     lap("  mixed: lists of the chunks");
-    if (ext->pack_emit_parts(prm.ingest->ctx, row_off.data(), ent_off.data(), ord_off.data(), tot_rows, tot_steps,
-                             (int64_t)parts.size(), part_ratings.data(), (int64_t)part_ratings.size(), p_cptr.data(),
-                             p_ro.data(), p_eo.data(), p_oo.data(), n_descs, p_desc.data(), &out.dev.buf) != 0)
+    const CellOffsets at{row_off.data(), ent_off.data(), ord_off.data(), tot_rows, tot_steps, n_descs};
+    PartsToEmit pe;
+    pe.n_parts = (int64_t)parts.size();
+    pe.n_sorted = (int64_t)part_ratings.size();
+    pe.sorted = part_ratings.data();
+    pe.cptr = p_cptr.data();
+    pe.row_off = p_ro.data();
+    pe.ent_off = p_eo.data();
+    pe.ord_off = p_oo.data();
+    pe.desc = p_desc.data();
+    if (ext->emit(at, &pe, out.dev) != 0)
         return fail("build_schedule: the device packer's EMIT pass (cells and chunks) failed");
     lap("  mixed: emit (cells + chunks)");
     out.device_packed = true;
-    out.dev_ops = ext;
     out.device_ingest = true;
     out.n_rows_words = tot_rows + 4;
     out.n_entry_recs = tot_steps * G;
@@ -1799,7 +1804,7 @@ bool Builder::assemble_on_device() {
 //  2. device, whole cells: every cell fits the training kernel's LDS image as one chunk and the device packs them all;
 //  3. device with cuts: the device counted the cells and some do not fit; the ones that do stay on the device, the host
 //     decides the cuts of the others from their ids (the device COUNTs the candidate chunks), and the device packs the
-//     chunks and assembles the schedule and its sub-cell table (Schedule::subs stays empty, dev.buf.subs holds it).
+//     chunks and assembles the schedule and its sub-cell table (Schedule::subs stays empty, dev.subs holds it).
 // Every route produces the same bytes.
 int build_schedule(const SchedParams& prm, const int32_t* u, const int32_t* i, const float* r,
                    const int64_t* orig, int64_t n, Schedule& out, std::string& err) {

@@ -18,6 +18,10 @@
 // Executing rounds, cells, sub-rounds, waves, steps and slots in index order
 // is the canonical sequential order; any conflict-free parallel execution
 // gives bit-identical factors.
+//
+// The scheduler is host code with no HIP call of its own.  The device does part of the work through
+// SchedParams::ingest (ingest.hpp), and a schedule it packed holds its big arrays as DevBufs (devmem.hpp, which needs
+// the runtime API's header only).
 #pragma once
 
 #include <cstdint>
@@ -26,6 +30,7 @@
 #include <string>
 #include <vector>
 
+#include "devmem.hpp"
 #include "ingest.hpp"
 #include "records.hpp"
 
@@ -88,35 +93,6 @@ private:
     size_t n_ = 0;
 };
 
-// Device buffers of a schedule the device packer built (rows, entries, order never existed on the
-// host); whoever ends up holding them frees them through `release`.
-struct DeviceSchedule {
-    DevicePacked buf{};
-    DeviceSchedule() = default;
-    DeviceSchedule(const DeviceSchedule&) = delete;
-    DeviceSchedule& operator=(const DeviceSchedule&) = delete;
-    DeviceSchedule(DeviceSchedule&& o) noexcept : buf(o.buf) { o.buf = DevicePacked{}; }
-    DeviceSchedule& operator=(DeviceSchedule&& o) noexcept {
-        if (this != &o) {
-            reset();
-            buf = o.buf;
-            o.buf = DevicePacked{};
-        }
-        return *this;
-    }
-    ~DeviceSchedule() { reset(); }
-    void reset() {
-        if (buf.release) {
-            buf.release(buf.rows);
-            buf.release(buf.entries);
-            buf.release(buf.order);
-            buf.release(buf.subs);
-        }
-        buf = DevicePacked{};
-    }
-    bool present() const { return buf.entries != nullptr; }
-};
-
 struct SchedParams {
     int32_t U = 0, I = 0;   // row counts of P and of this partition's Q block
     int k = 0;
@@ -126,14 +102,16 @@ struct SchedParams {
     int lds_budget = 160 * 1024 - 512;
     int n_cu = 256;
     int threads = 0;        // 0 = hardware_concurrency
-    const DeviceIngest* ingest = nullptr;  // optional: degrees and bucket order computed on the GPU
+    // optional, not owned: the device ingest with the caller's rating set loaded -- degrees, bucket order and (with
+    // device_pack) the cells computed on the GPU.  Null, or another length loaded than the `n` handed in: host loops
+    DeviceIngest* ingest = nullptr;
     // optional: rating counts per P row / Q row the caller already has (skips that pass), and a
     // promise that every (u, i) has been range-checked
     const int64_t* degu = nullptr;
     const int64_t* degi = nullptr;
     bool validated = false;
     bool solo = true;  // allow solo runs (MFSGD_FLAG_NO_SOLO clears it: A/B measurements, tests)
-    bool device_pack = true;  // let the device pack the cells when it can (needs `ingest` with the packer)
+    bool device_pack = true;  // let the device pack the cells when it can (needs `ingest`)
     bool lone_giants = true;  // an item that fills a fine bin by itself gets its tile to itself (schedule.cpp, lpt_assign)
 };
 
@@ -156,13 +134,13 @@ struct Schedule {
     double build_seconds = 0;
     bool device_ingest = false;  // degrees + bucket order came from the GPU
     // Device-packed schedules: rows / entries / order live in `dev` only (the PodVecs above stay empty
-    // until somebody asks for a host copy); the counts are always valid.
+    // until somebody asks for a host copy); the counts are always valid.  The DevBufs of `dev` own them until the
+    // first compute call moves rows, entries and subs on to the partition's (ratings.cpp); the order stays.
     bool device_packed = false;
-    DeviceSchedule dev;
-    const DeviceIngestExt* dev_ops = nullptr;  // for the host copies on demand
+    DevicePacked dev;
     int64_t n_rows_words = 0;  // rows[] length incl. the 4 padding words
     int64_t n_entry_recs = 0;  // entries[] length
-    int64_t n_sub_recs = 0;    // subs[] length incl. the 2 padding records (the array itself may live in dev.buf.subs only)
+    int64_t n_sub_recs = 0;    // subs[] length incl. the 2 padding records (the array itself may live in dev.subs only)
 };
 
 // u/i are row indices into P and into this partition's Q block; orig[j] is the

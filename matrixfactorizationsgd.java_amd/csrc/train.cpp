@@ -250,10 +250,10 @@ static int apply_hyper(mfsgd_handle* h, float lr, float lambda) {
         bool launched = false;
         for (Part& p : h->parts) {
             Schedule& s = p.sched;
-            Entry* d_entries = p.on_device ? p.d_entries.as<Entry>() : static_cast<Entry*>(s.dev.buf.entries);
+            Entry* d_entries = p.on_device ? p.d_entries.as<Entry>() : s.dev.entries.as<Entry>();
             if (!d_entries || s.n_entry_recs == 0 || s.cells.empty()) continue;
             const CellDesc* d_cells = p.d_cells.as<const CellDesc>();
-            const SubDesc* d_subs = p.on_device ? p.d_subs.as<const SubDesc>() : static_cast<const SubDesc*>(s.dev.buf.subs);
+            const SubDesc* d_subs = p.on_device ? p.d_subs.as<const SubDesc>() : s.dev.subs.as<const SubDesc>();
             if (!p.on_device) {  // the device packer's buffers, not adopted yet: the descriptors are still on the host only
                 temps.emplace_back();
                 if (const int rc = upload(h, temps.back(), s.cells)) return broken(rc, "the chunk descriptors did not reach the device: " + h->err);

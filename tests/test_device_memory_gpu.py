@@ -1,7 +1,9 @@
 """Device memory has one owner type (csrc/devmem.hpp), which counts the bytes it holds: mfsgd_debug_device_bytes.
 Whatever a handle allocates is back when it is closed, and a serving call keeps nothing -- on every route through
 set_ratings (whole cells on the device, cut cells, the two-pass packer, the host packer behind the device sort,
-partitioned handles).  No call here fails on the device: the counter is compared before and after calls that work."""
+partitioned handles).  The arrays of a device-packed schedule are counted from set_ratings on, while they wait for the
+first compute call, the canonical order among them.  No call here fails on the device: the counter is compared before
+and after calls that work."""
 import numpy as np
 import pytest
 
@@ -37,6 +39,35 @@ def test_a_life_cycle_returns_everything(mf):
         m.init_factors(8)             # releases the device factors and the training graphs
         m.fit(1)
         assert mf.debug_device_bytes() > live0
+    assert mf.debug_device_bytes() == live0
+
+
+def test_packed_arrays_are_counted_while_they_wait(mf):
+    """A device-packed schedule holds rows, entries, order and sub-cell tables in DevBufs of its own until the first
+    compute call moves three of them on; the order (an int64 per rating) stays where it is."""
+    F = _flags(mf)
+    w = mf.synth.workload("cfg1_ml100k", 1.0)
+    nnz = w["nnz"]
+    keep = np.arange(nnz) % 3 != 0
+    live0 = mf.debug_device_bytes()
+    with mf.MatrixFactorizationSGD(w["U"], w["I"], w["k"], LR, LAM, 7, flags=F.FLAG_DEVICE_INGEST) as m:
+        m.set_ratings(w["u"], w["i"], w["r"])
+        assert m.schedule_info()["device_ingest"] == 2
+        held = mf.debug_device_bytes()
+        assert held >= live0 + 8 * nnz
+        order0, _ = m.order()         # downloads from the schedule's own buffer
+        assert np.array_equal(np.sort(order0), np.arange(nnz))
+        assert mf.debug_device_bytes() == held
+        # other ratings, then the first set again, still before any compute call: each schedule's arrays go with it
+        m.set_ratings(w["u"][keep], w["i"][keep], w["r"][keep])
+        assert mf.debug_device_bytes() <= held
+        m.set_ratings(w["u"], w["i"], w["r"])
+        assert m.debug_counters()["schedule_builds"] == 3
+        assert mf.debug_device_bytes() <= held
+        m.init_factors()
+        m.fit(1)                      # rows, entries and tables move to the partition; the order does not
+        order1, _ = m.order()
+        assert np.array_equal(order1, order0)
     assert mf.debug_device_bytes() == live0
 
 
@@ -103,6 +134,8 @@ def test_cut_cells_two_pass_packer_and_host_packer_return_everything(mf, monkeyp
         with mf.MatrixFactorizationSGD(c["U"], c["I"], c["k"], LR, LAM, 5, blocks=c["blocks"], waves=c["waves"], flags=flags) as m:
             m.set_ratings(c["u"], c["i"], c["r"])
             info = m.schedule_info()
+            if info["device_ingest"] == 2:  # packed on the device: the arrays wait in the schedule, counted
+                assert mf.debug_device_bytes() >= live0 + 8 * len(c["u"])
         assert mf.debug_device_bytes() == live0
         return info
 
