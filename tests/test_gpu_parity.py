@@ -304,7 +304,8 @@ def test_recommend_topn_equals_sorted_predictions(mf, oracle, k):
 def test_recommend_fused_select_and_sort_paths(mf, oracle, I, topn, k):
     """The fused score + radix-select kernel (topn <= 128: one tile, three tiles) and the segmented-sort
     path (topn = 129) against sorting the oracle's predictions; many exact ties, including ties that
-    straddle the selection threshold, and -0.0 / +0.0."""
+    straddle the selection threshold, and zero scores.  (The -0.0 entry below does not make a -0.0 SCORE: the zeros
+    of mixed sign in the row, and the +0.0 pad columns, sum to +0.0.  Real -0.0 scores: tests/test_serving_edges_gpu.py.)"""
     rng = np.random.default_rng(I + topn)
     U = 40
     P = rng.standard_normal((U, k)).astype(np.float32)
@@ -312,7 +313,7 @@ def test_recommend_fused_select_and_sort_paths(mf, oracle, I, topn, k):
     Q[rng.integers(0, I, I // 3)] = Q[3 % I]  # a third of the catalogue scores exactly alike
     if I > 100:
         Q[50:60] = 0.0  # zero scores ...
-        Q[55, 0] = -0.0  # (a -0.0 that must tie with them)
+        Q[55, 0] = -0.0  # (a -0.0 entry; the row's score is still +0.0)
         P[7] = np.abs(P[7])
         Q[60:5000:7] = -np.abs(Q[60:5000:7])  # ... in the middle of user 7's ranking
     users = np.array([0, 7, 7, U - 1, 13, 21], np.int32)

@@ -50,8 +50,9 @@ def _ranks_ref(oracle, P, Q, u, i, eu, ei):
 
 
 def _factors(I, topn, k):
-    """The factors of test_recommend_excluding_matches_sorted_predictions: a third of Q alike, zero and -0.0 scores,
-    a user (7) with all-positive scores."""
+    """The factors of test_recommend_excluding_matches_sorted_predictions: a third of Q alike, zero scores (all +0.0:
+    the one -0.0 entry sums with +0.0 products; real -0.0 scores are in tests/test_serving_edges_gpu.py), a user (7)
+    with an all-positive row."""
     rng = np.random.default_rng(I + topn)
     U = 40
     P = rng.standard_normal((U, k)).astype(np.float32)
@@ -110,7 +111,7 @@ def _case(oracle, I, k):
     assert tied.size >= 2 or I < 100
     held.add(3, tied[:6])
     excl.add(3, tied[1::2])
-    if I > 100:  # the zero and -0.0 scores tie as well
+    if I > 100:  # the zero scores tie as well
         zeros = allitems[50:60]
         held.add(3, zeros[[0, 5, 9]])
         excl.add(3, zeros[[5, 6]])

@@ -26,7 +26,8 @@ def _expected(oracle, P, Q, users, topn, eu, ei):
 
 
 def _factors(I, topn, k):
-    """The factors of test_recommend_fused_select_and_sort_paths: a third of Q alike, zero and -0.0 scores."""
+    """The factors of test_recommend_fused_select_and_sort_paths: a third of Q alike, zero scores (all +0.0: the one
+    -0.0 entry sums with +0.0 products; real -0.0 scores are in tests/test_serving_edges_gpu.py)."""
     rng = np.random.default_rng(I + topn)
     U = 40
     P = rng.standard_normal((U, k)).astype(np.float32)
