@@ -1,5 +1,5 @@
 // canon.hpp -- the canonical arithmetic of DESIGN.md section 3 on the device: ONE definition, shared by
-// the training / RMSE / predict kernels (kernels.hip) and the top-N scorer (recommend.hip), so that
+// the training / RMSE / predict kernels (epoch.hip, cells.hip, kernels.hip) and the top-N scorer (recommend.hip), so that
 // predict(), recommend() and the oracle agree bit for bit by construction.
 // Build every translation unit that includes this with -ffp-contract=off.
 #pragma once

@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "canon.hpp"
+#include "dispatch.hpp"
 #include "kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -122,23 +123,11 @@ hipError_t launch_fold_in(int L, const float* Q, float* rows, int k, const long 
     if (nb <= 0) return hipSuccess;
     const int gpb = 256 / L;
     const dim3 grid((unsigned)((nb + gpb - 1) / gpb)), block(256);
-    switch (L) {
-#define MFSGD_FOLD(LL)                                                                                                 \
-    case LL:                                                                                                           \
-        hipLaunchKernelGGL((fold_in_kernel<LL, kFoldDepth>), grid, block, 0, st, Q, rows, k, row_ptr, base, perm, nb, \
-                           items, ratings, epochs, lr, c);                                                             \
-        break;
-        MFSGD_FOLD(1)
-        MFSGD_FOLD(2)
-        MFSGD_FOLD(4)
-        MFSGD_FOLD(8)
-        MFSGD_FOLD(16)
-        MFSGD_FOLD(32)
-        MFSGD_FOLD(64)
-#undef MFSGD_FOLD
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return with_L(L, [&](auto l) {
+        hipLaunchKernelGGL((fold_in_kernel<l(), kFoldDepth>), grid, block, 0, st, Q, rows, k, row_ptr, base, perm, nb, items,
+                           ratings, epochs, lr, c);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace mfsgd

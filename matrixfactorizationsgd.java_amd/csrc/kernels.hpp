@@ -1,4 +1,5 @@
-// kernels.hpp -- host-callable launchers of kernels.hip.
+// kernels.hpp -- host-callable launchers of every kernel unit: epoch.hip, cells.hip, kernels.hip, foldin.hip,
+// rehyper.hip, recommend.hip and rank.hip.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -28,11 +29,12 @@ struct CellLaunch {
     bool diag = false;  // diagnostic launch: in-kernel cycle stamps are written to sse_partial (as u64 words)
 };
 
-// One training round (train = true) or the SSE pass over every cell.
+// cells.hip.  One training round (train = true) or the SSE pass over every cell.
 hipError_t launch_cell(bool train, int L, int W, const CellLaunch& a, hipStream_t st);
-// Persistent epoch kernel: a.grid workgroups (all must be co-resident: at most
+// epoch.hip.  Persistent epoch kernel: a.grid workgroups (all must be co-resident: at most
 // blocks_per_cu x CUs) run n_rounds rounds; `done` holds B words spaced kDoneStride
-// apart (zeroed by the caller before every launch), `abort_word` one word.
+// apart (the kernel resets its own flags at the start of every launch: the caller zeroes
+// nothing between launches), `abort_word` one word.
 constexpr int kDoneStride = 32;
 hipError_t epoch_blocks_per_cu(int L, int W, const CellLaunch& a, int* blocks_per_cu);
 hipError_t launch_epoch_persistent(int L, int W, const CellLaunch& a, int n_rounds, unsigned* done,

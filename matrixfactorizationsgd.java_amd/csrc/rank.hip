@@ -12,6 +12,7 @@
 #include <cstdint>
 
 #include "canon.hpp"
+#include "dispatch.hpp"
 #include "kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -262,23 +263,11 @@ hipError_t launch_rank_items(int L, const float* P, const float* Q, const int32_
                              int32_t* out, hipStream_t st) {
     if (n_slots <= 0) return hipSuccess;
     const dim3 grid((unsigned)((n_slots + kRankUsers - 1) / kRankUsers));
-    switch (L) {
-#define MFSGD_RANK(LL)                                                                                                 \
-    case LL:                                                                                                           \
-        hipLaunchKernelGGL((rank_kernel<LL>), grid, dim3(kRankThreads), 0, st, P, Q, rows, n_slots, off, base, items, \
-                           n_items, ex.off, ex.items, out);                                                            \
-        break;
-        MFSGD_RANK(1)
-        MFSGD_RANK(2)
-        MFSGD_RANK(4)
-        MFSGD_RANK(8)
-        MFSGD_RANK(16)
-        MFSGD_RANK(32)
-        MFSGD_RANK(64)
-#undef MFSGD_RANK
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return with_L(L, [&](auto l) {
+        hipLaunchKernelGGL((rank_kernel<l()>), grid, dim3(kRankThreads), 0, st, P, Q, rows, n_slots, off, base, items, n_items,
+                           ex.off, ex.items, out);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace mfsgd

@@ -19,6 +19,7 @@
 #include <cstdint>
 
 #include "canon.hpp"
+#include "dispatch.hpp"
 #include "kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -425,42 +426,19 @@ bool recommend_is_fused(int32_t n_items, int32_t topn) {
 // Fused score + select: no score buffers at all.
 hipError_t recommend_fused(int L, const float* P, const float* Q, const int32_t* d_users, int nb, int32_t n_items,
                            int32_t topn, const RecommendExcl& ex, float* out_s, int32_t* out_i, hipStream_t st) {
-    switch (L) {
-#define MFSGD_TOPN(LL)                                                                          \
-    case LL:                                                                                    \
-        return ex.slot ? topn_L<LL, true>(P, Q, d_users, nb, n_items, topn, ex, out_s, out_i, st) \
-                       : topn_L<LL, false>(P, Q, d_users, nb, n_items, topn, ex, out_s, out_i, st);
-        MFSGD_TOPN(1)
-        MFSGD_TOPN(2)
-        MFSGD_TOPN(4)
-        MFSGD_TOPN(8)
-        MFSGD_TOPN(16)
-        MFSGD_TOPN(32)
-        MFSGD_TOPN(64)
-#undef MFSGD_TOPN
-        default: return hipErrorInvalidValue;
-    }
+    return with_L(L, [&](auto l) {
+        return ex.slot ? topn_L<l(), true>(P, Q, d_users, nb, n_items, topn, ex, out_s, out_i, st)
+                       : topn_L<l(), false>(P, Q, d_users, nb, n_items, topn, ex, out_s, out_i, st);
+    });
 }
 
 // Device buffers are the caller's (serve.cpp): scores/ids in and out (nb * n_items each), offsets nb+1.
 hipError_t recommend_batch(int L, const float* P, const float* Q, const int32_t* d_users, int nb, int32_t n_items,
                            int32_t topn, const RecommendExcl& ex, float* s_in, float* s_out, int32_t* id_in, int32_t* id_out,
                            long long* d_off, DevBuf& temp, float* out_s, int32_t* out_i, hipStream_t st) {
-    switch (L) {
-#define MFSGD_BATCH(LL)                                                                                              \
-    case LL:                                                                                                         \
-        return batch_L<LL>(P, Q, d_users, nb, n_items, topn, ex, s_in, s_out, id_in, id_out, d_off, temp, out_s, \
-                           out_i, st);
-        MFSGD_BATCH(1)
-        MFSGD_BATCH(2)
-        MFSGD_BATCH(4)
-        MFSGD_BATCH(8)
-        MFSGD_BATCH(16)
-        MFSGD_BATCH(32)
-        MFSGD_BATCH(64)
-#undef MFSGD_BATCH
-        default: return hipErrorInvalidValue;
-    }
+    return with_L(L, [&](auto l) {
+        return batch_L<l()>(P, Q, d_users, nb, n_items, topn, ex, s_in, s_out, id_in, id_out, d_off, temp, out_s, out_i, st);
+    });
 }
 
 hipError_t recommend_excl_filter(const int32_t* slot_of_user, const int32_t* u, const int32_t* i, int64_t n,

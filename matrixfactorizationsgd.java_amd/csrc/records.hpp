@@ -6,7 +6,7 @@
 
 namespace mfsgd {
 
-// Device-facing records (layout shared with kernels.hip).
+// Device-facing records (layout shared with cell.hpp).
 //
 // A cell whose LDS image would not fit is cut into CHUNKS: disjoint subsets of its users
 // (or items), each a complete little cell with its own row list, sub-cell table and steps.
@@ -21,7 +21,7 @@ struct CellDesc {
     uint16_t ni;       // distinct items  -> LDS slots [nu, nu + ni)
     uint32_t next;     // index of the cell's next chunk, 0 = this is the last one
     uint32_t rsv[3];   // [0] bit 0 (kCellLoneTile): every cell of this cell's tile is ONE chunk holding ONE item row
-                       // -- the persistent kernel hands that row on through the tile's mailbox (kernels.hip)
+                       // -- the persistent kernel hands that row on through the tile's mailbox (epoch.hip)
 };
 static_assert(sizeof(CellDesc) == 32, "CellDesc layout");
 constexpr uint32_t kCellCritical = 0x80000000u;

@@ -15,7 +15,7 @@
 //                 which is how the helper learns that step t has happened and what s_t was.
 // The decay factor is the same for every step (there are no idle slots in a solo run), so it is
 // an operand (SGPR pair {c, c}), not part of the entry.  Arithmetic is, instruction for
-// instruction, DESIGN.md section 3: the pair of waves produces the bits Cell::solo_generic does.
+// instruction, DESIGN.md section 3: the pair of waves produces the bits the one-wave C++ form of the run (cell.hpp, Cell::apply) does.
 //
 // [r2, late] s of an even and the following odd step are posted TOGETHER (one ds_write2_b32 behind the odd
 // step; a last odd-numbered step is posted alone): the chain wave issues half an LDS write per step less.
@@ -24,7 +24,9 @@
 // and not used by the product: the helper is the slower of the pair at 16 lanes per rating, but a third wave on the
 // LDS slows the chain wave by what the second helper gains.)
 //
-// Shared with tools/ubench3.hip, which times the loops against each other in isolation.
+// Every loop here has ONE form: what is in this file is what the product runs (the pads below are the only build-time
+// knob, for tools/ubench3.hip).  Included by cell.hpp, whose wrappers bind the operands, and by tools/ubench3.hip, which
+// times the loops against each other in isolation.
 #pragma once
 
 // The loops below are a few 64-byte instruction-cache lines long and their cycle count per pass depends on
@@ -190,7 +192,7 @@ constexpr int mfsgd_pad_helper(int lanes) {
 
 
 // ---- hand-scheduled GENERAL step loop (gfx950) [r3] -------------------------------------------
-// `n` general steps of one wave (kernels.hip Cell::apply, `step`): every lane group applies one rating per step --
+// `n` general steps of one wave (cell.hpp Cell::apply, `step`): every lane group applies one rating per step --
 // both rows come from LDS, both go back -- and consecutive steps are independent except where the packer flagged a
 // q row as forwarded (bit 31 of the next entry's slots word: the same item in the same lane slot; its new row is taken
 // from registers, the LDS copy read ahead of the write being stale).  The compiler's schedule of the C++ step waits
@@ -374,87 +376,6 @@ constexpr int mfsgd_pad_helper(int lanes) {
 // Once s_0 is there they are final -- only the helper writes them.  (A first version of this loop fetched p_0 in its
 // prologue, in front of the poll: bit-exact in tools/ubench3 -- which has no general steps -- and wrong in the product
 // whenever a user of step 0 also had a general step in the sub-cell.  tools/ubench3 now dirties p_0 first.)
-#ifdef MFSGD_HELPER_PER_STEP  // round 2's per-step helper on the new record layout (A/B, bisecting)
-#define MFSGD_SOLO_HELPER_HALF(TAG, P0, P1, P2, P3, N0, N3, MBOX, MSLOT, MPAIR, NEXTM, PADDR, NADDR, OFF0, OFF1) \
-        "s_waitcnt lgkmcnt(1)\n\t" \
-        "v_cmp_eq_u32 vcc, -1, v" MBOX "\n\t" \
-        "v_mad_u32_u16 v" NADDR ", v" MSLOT ", 16, v139\n\t" \
-        "v_pk_mul_f32 v[126:127], v[" P0 ":" P1 "], %[c2]\n\t" \
-        "s_cbranch_vccnz 2" TAG "f\n\t" \
-        "1" TAG ":\n\t" \
-        "ds_read_b128 v[" N0 ":" N3 "], v" NADDR "\n\t" \
-        "v_pk_mul_f32 v[128:129], v[" P2 ":" P3 "], %[c2]\n\t" \
-        "ds_read2_b32 v[" NEXTM "], v138 " OFF0 "\n\t" \
-        "v_pk_mul_f32 v[122:123], v[100:101], %[c2]\n\t" \
-        "v_pk_mul_f32 v[124:125], v[102:103], %[c2]\n\t" \
-        "v_pk_fma_f32 v[134:135], v[" MPAIR "], v[100:101], v[126:127] op_sel_hi:[0,1,1]\n\t" \
-        "v_pk_fma_f32 v[136:137], v[" MPAIR "], v[102:103], v[128:129] op_sel_hi:[0,1,1]\n\t" \
-        "v_pk_fma_f32 v[100:101], v[" MPAIR "], v[" P0 ":" P1 "], v[122:123] op_sel_hi:[0,1,1]\n\t" \
-        "v_pk_fma_f32 v[102:103], v[" MPAIR "], v[" P2 ":" P3 "], v[124:125] op_sel_hi:[0,1,1]\n\t" \
-        "s_sub_u32 %[n], %[n], 1\n\t" \
-        "ds_write_b128 v" PADDR ", v[134:137]\n\t" \
-        "s_cmp_eq_u32 %[n], 0\n\t"
-
-#define MFSGD_SOLO_HELPER_SLOW(TAG, MBOX, OFF1) \
-        "2" TAG ":\n\t" \
-        "s_sleep 1\n\t" \
-        "ds_read_b32 v" MBOX ", v138 offset:" OFF1 "\n\t" \
-        "s_sub_u32 %[spins], %[spins], 1\n\t" \
-        "s_cmp_eq_u32 %[spins], 0\n\t" \
-        "s_cbranch_scc1 9f\n\t" \
-        "s_waitcnt lgkmcnt(0)\n\t" \
-        "v_cmp_eq_u32 vcc, -1, v" MBOX "\n\t" \
-        "s_cbranch_vccnz 2" TAG "b\n\t" \
-        "s_branch 1" TAG "b\n\t"
-
-#define MFSGD_SOLO_HELPER_ASM_TEXT \
-        "v_mov_b32 v138, %[ea]\n\t" \
-        "v_mov_b32 v139, %[rb]\n\t" \
-        "ds_read_b32 v133, v138\n\t" \
-        "ds_read2_b32 v[116:117], v138 offset0:5 offset1:4\n\t" \
-        "s_waitcnt lgkmcnt(1)\n\t" \
-        "v_mad_u32_u16 v112, v133, 16, v139\n\t" \
-        "v_bfe_u32 v140, v133, 16, 15\n\t" \
-        "v_lshl_add_u32 v140, v140, 4, v139\n\t" \
-        "s_waitcnt lgkmcnt(0)\n\t" \
-        "v_cmp_eq_u32 vcc, -1, v116\n\t" \
-        "s_cbranch_vccz 4f\n\t" \
-        "3:\n\t" \
-        "s_sleep 1\n\t" \
-        "ds_read_b32 v116, v138 offset:20\n\t" \
-        "s_sub_u32 %[spins], %[spins], 1\n\t" \
-        "s_cmp_eq_u32 %[spins], 0\n\t" \
-        "s_cbranch_scc1 9f\n\t" \
-        "s_waitcnt lgkmcnt(0)\n\t" \
-        "v_cmp_eq_u32 vcc, -1, v116\n\t" \
-        "s_cbranch_vccnz 3b\n\t" \
-        "4:\n\t" \
-        "ds_read_b128 v[100:103], v140\n\t" \
-        "ds_read_b128 v[104:107], v112\n\t" \
-        "ds_write_b32 v138, v133\n\t" \
-        "s_nop 1\n\t" \
-        "v_add_u32 v138, 16, v138\n\t" \
-        MFSGD_LOOP_ALIGN \
-        "5:\n\t" \
-        MFSGD_SOLO_HELPER_HALF("0", "104", "105", "106", "107", "108", "111", "116", "117", "116:117", "118:119", "112", "113", "offset0:5 offset1:4", "4") \
-        "s_cbranch_scc1 8f\n\t" \
-        MFSGD_SOLO_HELPER_HALF("1", "108", "109", "110", "111", "104", "107", "118", "119", "118:119", "116:117", "113", "112", "offset0:9 offset1:8", "20") \
-        "v_add_u32 v138, 32, v138\n\t" \
-        "s_cbranch_scc0 5b\n\t" \
-        "8:\n\t" \
-        "s_cmp_eq_u32 %[fin], 0\n\t" \
-        "s_cbranch_scc1 9f\n\t" \
-        "ds_write_b128 v140, v[100:103]\n\t" \
-        "s_branch 9f\n\t" \
-        MFSGD_SOLO_HELPER_SLOW("0", "116", "4") \
-        MFSGD_SOLO_HELPER_SLOW("1", "118", "20") \
-        "9:\n\t" \
-        "s_waitcnt lgkmcnt(0)\n\t"
-
-#else
-#ifndef MFSGD_HV
-#define MFSGD_HV 3
-#endif
 #define MFSGD_SOLO_HELPER_PAIR(TAG, M0, M1, M2, M3, N0, N3) \
         "s_waitcnt lgkmcnt(1)\n\t" \
         "v_max_u32 v133, v" M1 ", v" M3 "\n\t" \
@@ -574,7 +495,6 @@ constexpr int mfsgd_pad_helper(int lanes) {
         "9:\n\t" \
         "s_waitcnt lgkmcnt(0)\n\t"
 
-#endif
 #define MFSGD_SOLO_HELPER_OPERANDS                                                                                     \
     : [n] "+s"(n), [spins] "+s"(spins)                                                                                 \
     : [ea] "v"(ea), [rb] "v"(rowbase), [c2] "s"(c2), [fin] "s"(fin), [pad] "n"(PADV)                                                                 \

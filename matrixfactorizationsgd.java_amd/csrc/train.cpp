@@ -68,7 +68,7 @@ static int launch_epoch_body(mfsgd_handle* h, Part& p, float* Q, hipStream_t st)
         CellLaunch a = make_launch(h, p, Q);
         a.grid = p.persistent_np;
         // flags are counted within the launch: zero them (and the abort word) every time
-        // no memset: the kernel resets its own hand-off flags behind a device-side barrier (kernels.hip,
+        // no memset: the kernel resets its own hand-off flags behind a device-side barrier (epoch.hip,
         // run_ring) -- a memset node in a replayed graph is not reliably ordered before the kernel node
         HIPCHK(h, launch_epoch_persistent(h->geo.L, p.sched.W, a, p.sched.B, p.d_sync.as<unsigned>(), abort_word(p), st));
         return MFSGD_OK;

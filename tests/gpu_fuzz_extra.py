@@ -48,7 +48,7 @@ for n, c in enumerate(fuzz_cases(400, seed=31337)):
 for n, c in enumerate(fuzz_chunked_cases(80, seed=777, max_ratings=20000)):
     check(c, "chunked", n)
 # third family (round 2): a few dominant items, so that tiles of one item form and travel through the mailbox
-# (kernels.hip run_ring) -- three epochs, i.e. three launches: the tags carry the launch generation
+# (epoch.hip run_ring) -- three epochs, i.e. three launches: the tags carry the launch generation
 def lone_cases(count, seed):
     rng = np.random.default_rng(seed)
     for _ in range(count):

@@ -1,5 +1,5 @@
 """CPU replay of the device schedule with the kernel's exact memory semantics
-(kernels.hip cell_kernel): rows gathered into an LDS image, the rows of step
+(cells.hip cell_kernel, cell.hpp Cell): rows gathered into an LDS image, the rows of step
 t+1 read BEFORE the rows of step t are written back, flagged q rows forwarded in
 registers, run-mode q rows resident for the whole run.  Arithmetic is the
 oracle's mfo_sgd_update.  If the scheduler ever breaks a hazard rule the replay

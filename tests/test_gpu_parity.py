@@ -926,7 +926,7 @@ def test_native_dsgd_recovers_when_a_persistent_launch_is_not_resident(mf, oracl
 @pytest.mark.parametrize("k,B", [(64, 16), (64, 40), (128, 16), (256, 24), (100, 12)])
 def test_lone_tile_mailbox_hand_off(mf, oracle, monkeypatch, k, B):
     """An item with a tile of its own travels from workgroup to workgroup through the tile's mailbox ({value, tag}
-    granules, kernels.hip run_ring) instead of store + flag + gather: factors and RMSE bit-exact against the
+    granules, epoch.hip run_ring) instead of store + flag + gather: factors and RMSE bit-exact against the
     oracle over several epochs (every epoch is a launch of its own: the tags carry the launch generation), for
     one, two and four granules per lane, in a graph replay and in eager launches; and the same schedule with the
     mailbox switched off (MFSGD_NO_MAILBOX) gives the same bits."""

@@ -67,7 +67,7 @@ __global__ void __launch_bounds__(192) k(const float* rows_in, const uint32_t* e
     int n = n_steps;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t0)::"memory");
     if (wave == 0 && mode == 3) {
-        // the one-wave run loop (kernels.hip run_loop_asm): slot 0 carries the chain, the others idle
+        // the one-wave run loop (cell.hpp run_loop_asm): slot 0 carries the chain, the others idle
         typedef float f4 __attribute__((ext_vector_type(4)));
         const int g = lane / LG;
         const unsigned qaddr = (g == 0 ? NSTEP : NSTEP + 1) * ROWB + (lane % LG) * 16;
@@ -79,7 +79,7 @@ __global__ void __launch_bounds__(192) k(const float* rows_in, const uint32_t* e
         asm volatile(MFSGD_RUN_LOOP_ASM_TEXT(EXTRA, SFMA) MFSGD_RUN_LOOP_ASM_OPERANDS);
         if (g == 0) *(f4*)(smem + qaddr) = q;
     } else if (wave == 0 && mode == 4) {
-        // cut run: the chain wave stores q into its row between the halves (kernels.hip, solo_split)
+        // cut run: the chain wave stores q into its row between the halves (measured and not used by the product: run_asm.hpp)
         typedef float f4 __attribute__((ext_vector_type(4)));
         f4 q = *(const f4*)(smem + NSTEP * ROWB + (lane % LG) * 16);
         constexpr int PADV = mfsgd_pad_chain(LG);
