@@ -73,14 +73,15 @@ __device__ __forceinline__ void gen_loop_asm(const unsigned ea, const unsigned r
 }
 
 // ---- solo run: chain wave / helper wave (run_asm.hpp) -------------------------------------
-// `ea`: LDS byte address of the run's header record, `rowbase`: LDS byte address of row slot 0 plus
-// this lane's 16-byte offset inside a row, n >= 1 steps, c2 = {c, c} as one 64-bit scalar.
+// `ea`: LDS byte address of the run's header record, `s0`: that record's slots word (p row of step 0 | q row << 16),
+// `rowbase`: LDS byte address of row slot 0 plus this lane's 16-byte offset inside a row, n >= 1 steps, c2 = {c, c}
+// as one 64-bit scalar.  The loop loads the q row itself (next to its first p row and entry words).
 template <int L>
-__device__ __forceinline__ void solo_chain_asm(float4& rq, const unsigned ea, const unsigned rowbase, int n,
+__device__ __forceinline__ void solo_chain_asm(float4& rq, const unsigned ea, const unsigned s0, const unsigned rowbase, int n,
                                                const float lr, const uint64_t c2) {
     static_assert(L == 16 || L == 32 || L == 64, "solo loops: 16, 32 or 64 lanes per rating");
     using f4 = __attribute__((ext_vector_type(4))) float;
-    f4 q = {rq.x, rq.y, rq.z, rq.w};
+    f4 q;
     n = __builtin_amdgcn_readfirstlane(n);
     constexpr int PADV = mfsgd_pad_chain(L);
     if constexpr (L == 16)
@@ -495,11 +496,10 @@ struct Cell {
                 // Solo run: header record, then one 16-byte record per step {next slots, mailbox, lr*r, r}.
                 const uint4* hdr = lent + (size_t)(sc.first() + n + nr + kSoloPad) * G;
                 const unsigned s0 = hdr->x;
-                const unsigned rqa = (__builtin_amdgcn_ubfe(s0, 16, 15) << 4) + lo;
                 if constexpr (TRAIN && NH > 0 && L >= 16) {
                     // chain wave: dot -> s -> q' only; its helper (a copy wave) stores the p rows and q
-                    float4 q = lds_ld(lr_, rqa);
-                    solo_chain_asm<L>(q, (unsigned)(uintptr_t)(lptr_t)hdr, row_base(lr_, lo), nsolo, lr, pack_c2(c));
+                    float4 q;
+                    solo_chain_asm<L>(q, (unsigned)(uintptr_t)(lptr_t)hdr, s0, row_base(lr_, lo), nsolo, lr, pack_c2(c));
                     // the run was the cell's last work (its records end where the cell's steps end): hand the row on now
                     const int units = (nsolo + 2 + G - 1) / G + kSoloPad;
                     if (post_at != nullptr && sc.first() + n + nr + units + 2 == n_steps) {
@@ -517,6 +517,7 @@ struct Cell {
                 } else if constexpr (TRAIN) {
                     // one wave does everything (kernels without copy waves); every lane group computes the
                     // same step -- the chain is sequential -- and they all store the same bits
+                    const unsigned rqa = (__builtin_amdgcn_ubfe(s0, 16, 15) << 4) + lo;
                     float4 q = lds_ld(lr_, rqa);
                     unsigned pa = ((s0 & 0xFFFFu) << 4) + lo;
                     for (int t = 0; t < nsolo; ++t) {

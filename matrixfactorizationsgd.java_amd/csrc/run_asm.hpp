@@ -24,9 +24,9 @@
 // and not used by the product: the helper is the slower of the pair at 16 lanes per rating, but a third wave on the
 // LDS slows the chain wave by what the second helper gains.)
 //
-// Every loop here has ONE form: what is in this file is what the product runs (the pads below are the only build-time
-// knob, for tools/ubench3.hip).  Included by cell.hpp, whose wrappers bind the operands, and by tools/ubench3.hip, which
-// times the loops against each other in isolation.
+// Every loop here has ONE form: what is in this file is what the product runs (the pads and the chain loop's pairs per
+// pass below are the only build-time knobs, for tools/ubench3.hip).  Included by cell.hpp, whose wrappers bind the
+// operands, and by tools/ubench3.hip, which times the loops against each other in isolation.
 #pragma once
 
 // The loops below are a few 64-byte instruction-cache lines long and their cycle count per pass depends on
@@ -34,6 +34,10 @@
 // period 8 instructions).  Cycles per step at 0 / 2 / 4 / 6 s_nops past a 64-byte boundary:
 //     solo pair   L = 16: 136.1 137.5 133.7 138.8    L = 32: 165.4 168.6 174.3 178.0    L = 64: 173.4 175.4 170.3 176.4
 //     run loop    L = 16: 145.6 143.6 149.6 151.6    L = 32: 174.5 174.5 182.4 180.4    L = 64: 177.8 177.7 181.7 183.7
+// The solo pair as it is now (s posted in pairs, the chain wave's body four A/B pairs long; at the longest n the
+// microbenchmark holds -- 300 / 200 / 120 steps; profiles/chain_unroll_ubench3.log, the pair +- 1.5 from run to run):
+//     solo pair   L = 16: 124.7 125.6 125.1 125.4    L = 32: 144.8 147.7 147.2 147.0    L = 64: 162.3 157.7 165.7 160.7
+//     chain alone L = 16: 118.3 120.3 120.3 120.3    L = 32: 138.2 140.2 140.2 140.2    L = 64: 152.8 148.9 154.9 150.8
 // Every loop head is therefore placed explicitly (operand [pad], an assembly-time constant): the product
 // runs the layout that was timed, whatever code the compiler puts in front of the loop.
 constexpr int mfsgd_pad_run(int lanes) {
@@ -54,7 +58,7 @@ constexpr int mfsgd_pad_chain(int lanes) {
 #ifdef MFSGD_PAD_CHAIN
     return MFSGD_PAD_CHAIN;
 #else
-    return lanes == 32 ? 2 : 0;  // (the loop that posts s in pairs; the table above is the earlier one-post-per-step loop)
+    return lanes == 64 ? 2 : 0;  // the four-pair body, second table above (profiles/chain_unroll_ubench3.log)
 #endif
 }
 constexpr int mfsgd_pad_helper(int lanes) {
@@ -62,6 +66,16 @@ constexpr int mfsgd_pad_helper(int lanes) {
     return MFSGD_PAD_HELPER;
 #else
     return lanes == 16 ? 6 : 2;  // [r3] the loop that takes the steps in pairs (tools/ubench3, profiles/r03_ubench3.log)
+#endif
+}
+// A/B pairs of solo chain steps per pass of the chain wave's loop, an assembly-time constant like the pads (1, 2 or 4:
+// tools/ubench3.hip times them against each other; a taken backward branch costs this loop about 9 cycles, which is
+// 4.7 cycles per step at one pair per pass and 1.2 at four).
+constexpr int mfsgd_chain_pairs() {
+#ifdef MFSGD_CHAIN_PAIRS
+    return MFSGD_CHAIN_PAIRS;
+#else
+    return 4;
 #endif
 }
 #define MFSGD_LOOP_ALIGN ".p2align 6\n\t.rept %c[pad]\n\ts_nop 0\n\t.endr\n\t"
@@ -314,34 +328,51 @@ constexpr int mfsgd_pad_helper(int lanes) {
         "v_pk_fma_f32 v[100:101], v[" S ":" S1 "], v[" P0 ":" P1 "], v[122:123] op_sel_hi:[0,1,1]\n\t" \
         "v_pk_fma_f32 v[102:103], v[" S ":" S1 "], v[" P2 ":" P3 "], v[124:125] op_sel_hi:[0,1,1]\n\t"
 
-// `ea` = LDS byte address of the header entry; n >= 1 steps.
+// `ea` = LDS byte address of the header entry, `s0` = its slots word (the caller has read it to find the q row; the
+// helper wave needs the header in LDS, so the record stays); n >= 1 steps.  The q row is loaded HERE, not by the
+// caller: {lr*r_0, slots_1}, p row 0 and q are three LDS reads in flight together, one round trip in front of step 0.
+// (The harmless rewrite of the header word keeps "one LDS operation behind the reads", as in the run loop.)
+// One pass of the loop is %c[pairs] A/B pairs in a straight line (.irp: an assembly-time constant, see
+// mfsgd_chain_pairs): the entry offsets grow along the body, v138 is bumped and the backward branch taken once per
+// pass.  Every step keeps its own forward exit test -- after an A step to that step's "post s alone" tail (2<j>),
+// after a B step to the end -- so what the helper sees is what the one-pair loop posts.
 #define MFSGD_SOLO_CHAIN_ASM_TEXT(EXTRA, SFMA) \
         "v_mov_b32 v138, %[ea]\n\t" \
         "v_mov_b32 v131, %[lr]\n\t" \
         "v_mov_b32 v139, %[rb]\n\t" \
-        "ds_read_b32 v133, v138\n\t" \
         "ds_read2_b32 v[116:117], v138 offset0:6 offset1:4\n\t" \
-        "v_mov_b32 v100, %[q0]\n\t" \
-        "v_mov_b32 v101, %[q1]\n\t" \
-        "v_mov_b32 v102, %[q2]\n\t" \
-        "v_mov_b32 v103, %[q3]\n\t" \
-        "s_waitcnt lgkmcnt(1)\n\t" \
-        "v_mad_u32_u16 v113, v133, 16, v139\n\t" \
+        "v_mad_u32_u16 v113, %[s0], 16, v139\n\t" \
+        "v_bfe_u32 v133, %[s0], 16, 15\n\t" \
         "ds_read_b128 v[104:107], v113\n\t" \
-        "ds_write_b32 v138, v133\n\t" \
-        "s_nop 1\n\t" \
+        "v_lshl_add_u32 v133, v133, 4, v139\n\t" \
+        "ds_read_b128 v[100:103], v133\n\t" \
+        "ds_write_b32 v138, %[s0]\n\t" \
         "v_add_u32 v138, 16, v138\n\t" \
         MFSGD_LOOP_ALIGN \
         "1:\n\t" \
-        MFSGD_SOLO_CHAIN_HALF("104", "105", "106", "107", "108", "109", "110", "111", "116", "117", "118:119", "offset0:6 offset1:4", "1", "130", "131", EXTRA, SFMA) \
-        "s_cbranch_scc1 2f\n\t" \
-        MFSGD_SOLO_CHAIN_HALF("108", "109", "110", "111", "104", "105", "106", "107", "118", "119", "116:117", "offset0:10 offset1:8", "0", "128", "129", EXTRA, SFMA) \
-        "ds_write2_b32 v138, v130, v128 offset0:1 offset1:5\n\t" \
-        "v_add_u32 v138, 32, v138\n\t" \
+        ".irp j,0,1,2,3\n\t" \
+        ".if \\j < %c[pairs]\n\t" \
+        MFSGD_SOLO_CHAIN_HALF("104", "105", "106", "107", "108", "109", "110", "111", "116", "117", "118:119", "offset0:6+8*\\j offset1:4+8*\\j", "1", "130", "131", EXTRA, SFMA) \
+        "s_cbranch_scc1 2\\j\\()f\n\t" \
+        MFSGD_SOLO_CHAIN_HALF("108", "109", "110", "111", "104", "105", "106", "107", "118", "119", "116:117", "offset0:10+8*\\j offset1:8+8*\\j", "0", "128", "129", EXTRA, SFMA) \
+        "ds_write2_b32 v138, v130, v128 offset0:1+8*\\j offset1:5+8*\\j\n\t" \
+        ".if \\j + 1 < %c[pairs]\n\t" \
+        "s_cbranch_scc1 3f\n\t" \
+        ".endif\n\t" \
+        ".endif\n\t" \
+        ".endr\n\t" \
+        "v_add_u32 v138, %c[bump], v138\n\t" \
         "s_cbranch_scc0 1b\n\t" \
         "s_branch 3f\n\t" \
-        "2:\n\t" \
-        "ds_write_b32 v138, v130 offset:4\n\t" \
+        ".irp j,3,2,1,0\n\t" \
+        ".if \\j < %c[pairs]\n\t" \
+        "2\\j:\n\t" \
+        "ds_write_b32 v138, v130 offset:4+32*\\j\n\t" \
+        ".if \\j > 0\n\t" \
+        "s_branch 3f\n\t" \
+        ".endif\n\t" \
+        ".endif\n\t" \
+        ".endr\n\t" \
         "3:\n\t" \
         "s_waitcnt lgkmcnt(0)\n\t" \
         "v_mov_b32 %[q0], v100\n\t" \
@@ -350,8 +381,9 @@ constexpr int mfsgd_pad_helper(int lanes) {
         "v_mov_b32 %[q3], v103\n\t"
 
 #define MFSGD_SOLO_CHAIN_OPERANDS                                                                                      \
-    : [n] "+s"(n), [q0] "+v"(q[0]), [q1] "+v"(q[1]), [q2] "+v"(q[2]), [q3] "+v"(q[3])                                  \
-    : [ea] "v"(ea), [rb] "v"(rowbase), [lr] "s"(lr), [c2] "s"(c2), [pad] "n"(PADV)                                     \
+    : [n] "+s"(n), [q0] "=v"(q[0]), [q1] "=v"(q[1]), [q2] "=v"(q[2]), [q3] "=v"(q[3])                                  \
+    : [ea] "v"(ea), [rb] "v"(rowbase), [s0] "v"(s0), [lr] "s"(lr), [c2] "s"(c2), [pad] "n"(PADV),                      \
+      [pairs] "n"(mfsgd_chain_pairs()), [bump] "n"(32 * mfsgd_chain_pairs())                                           \
     : "memory", "scc", "vcc", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", \
       "v113", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v128", "v129", "v130",  \
       "v131", "v132", "v133", "v138", "v139"

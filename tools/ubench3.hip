@@ -81,15 +81,19 @@ __global__ void __launch_bounds__(192) k(const float* rows_in, const uint32_t* e
     } else if (wave == 0 && mode == 4) {
         // cut run: the chain wave stores q into its row between the halves (measured and not used by the product: run_asm.hpp)
         typedef float f4 __attribute__((ext_vector_type(4)));
-        f4 q = *(const f4*)(smem + NSTEP * ROWB + (lane % LG) * 16);
+        f4 q;  // (the chain loop loads the q row itself)
         constexpr int PADV = mfsgd_pad_chain(LG);
         const int m = (n_steps / 2) & ~1;
         const unsigned ea0 = ea;
         n = m;
-        asm volatile(MFSGD_SOLO_CHAIN_ASM_TEXT(EXTRA_SOLO, SFMA2) MFSGD_SOLO_CHAIN_OPERANDS);
+        {
+            const unsigned s0 = *(const uint32_t*)(smem + ENT_OFF);
+            asm volatile(MFSGD_SOLO_CHAIN_ASM_TEXT(EXTRA_SOLO, SFMA2) MFSGD_SOLO_CHAIN_OPERANDS);
+        }
         *(f4*)(smem + NSTEP * ROWB + (lane % LG) * 16) = q;
         {
             const unsigned ea = ea0 + m * 16;
+            const unsigned s0 = *(const uint32_t*)(smem + ENT_OFF + m * 16);  // entry m - 1 serves as the second half's header
             n = n_steps - m;
             asm volatile(MFSGD_SOLO_CHAIN_ASM_TEXT(EXTRA_SOLO, SFMA2) MFSGD_SOLO_CHAIN_OPERANDS);
         }
@@ -106,7 +110,8 @@ __global__ void __launch_bounds__(192) k(const float* rows_in, const uint32_t* e
             v += 1.0f;
             *p0 = v;
         }
-        f4 q = *(const f4*)(smem + NSTEP * ROWB + (lane % LG) * 16);
+        f4 q;  // (the chain loop loads the q row itself)
+        const unsigned s0 = *(const uint32_t*)(smem + ENT_OFF);  // the header's slots word, as Cell::apply reads it
         constexpr int PADV = mfsgd_pad_chain(LG);
         asm volatile(MFSGD_SOLO_CHAIN_ASM_TEXT(EXTRA_SOLO, SFMA2) MFSGD_SOLO_CHAIN_OPERANDS);
     } else if (wave == 1 && (mode == 0 || mode == 2 || mode == 5)) {
@@ -153,7 +158,15 @@ static float ref_dot(const float* p, const float* q) {
     return s[0];
 }
 
-int main() {
+// ubench3          : every mode at n = NSTEP, NSTEP - 1, 1, 2, 50, 51
+// ubench3 chain    : the chain wave's loop only (modes 0 and 1) at those n and at every n = 1..33 -- every exit of a
+//                    straight-line body of up to eight steps, twice over (built with -DMFSGD_CHAIN_PAIRS=1|2|4 and
+//                    -DMFSGD_PAD_CHAIN=0|2|4|6: tools/build_ubench.sh); one line per n, the short runs as one line
+int main(int argc, char** argv) {
+    const bool chain_only = argc > 1 && strcmp(argv[1], "chain") == 0;
+    std::vector<int> lengths = {NSTEP, NSTEP - 1, 1, 2, 50, 51};
+    if (chain_only)
+        for (int n = 3; n <= 33; ++n) lengths.push_back(n);
     const int KP = 4 * LG;
     std::vector<float> rows((size_t)NROWS * KP), ref;
     uint32_t seed = 12345;
@@ -240,8 +253,10 @@ int main() {
     uint32_t* d_run;
     (void)hipMalloc(&d_run, run.size() * 4);
     (void)hipMemcpy(d_run, run.data(), run.size() * 4, hipMemcpyHostToDevice);
-    for (int mode = 0; mode < 6; ++mode)
-        for (int n : {NSTEP, NSTEP - 1, 1, 2, 50, 51}) {
+    struct Res { double chain, helper; int bad; };
+    std::vector<Res> res[2] = {std::vector<Res>(NSTEP + 1), std::vector<Res>(NSTEP + 1)};
+    for (int mode = 0; mode < (chain_only ? 2 : 6); ++mode)
+        for (int n : lengths) {
             if ((mode == 3 && (n & 1)) || (mode == 4 && n < 8)) continue;
             (void)hipMemcpy(d_ent, (mode == 2 ? ent2 : ent).data(), ent.size() * 4, hipMemcpyHostToDevice);
             unsigned long long best[2] = {~0ull, ~0ull}, h[4];
@@ -272,9 +287,27 @@ int main() {
                 }
                 bad = memcmp(out.data(), r2.data(), out.size() * 4) != 0;
             }
+            if (chain_only) {  // one line per n below
+                res[mode][n] = {(double)best[0], (double)best[1], bad};
+                continue;
+            }
             printf("L=%d mode=%d (%s) n=%d: chain %.1f cycles/step, helper %.1f cycles/step%s\n", LG, mode,
                    mode == 1 ? "chain alone" : mode == 4 ? "cut run: chain + two helpers" : mode == 2 ? "helper alone" : mode == 3 ? "one-wave run loop" : mode == 5 ? "chain + helper, p row of step 0 updated in front of the run" : "chain + helper", n, (double)best[0] / n, (double)best[1] / n,
                    mode == 1 ? "" : (bad ? "  MISMATCH" : "  bit-exact"));
         }
+    if (chain_only) {
+        // pair = the later of the two waves of mode 0; alone = mode 1; the short runs as one line (cycles per RUN, alone)
+        int exact = 0, wrong = 0;
+        for (int n = 1; n <= 33; ++n) (res[0][n].bad ? wrong : exact)++;
+        for (int n : {NSTEP, NSTEP - 1, 50, 51, 2, 1}) {
+            const Res &p = res[0][n], &a = res[1][n];
+            printf("L=%d pairs=%d pad=%d n=%d: pair %.1f, chain in the pair %.1f, chain alone %.1f cycles/step%s\n", LG, mfsgd_chain_pairs(),
+                   mfsgd_pad_chain(LG), n, (p.helper > p.chain ? p.helper : p.chain) / n, p.chain / n, a.chain / n, p.bad ? "  MISMATCH" : "  bit-exact");
+        }
+        printf("L=%d pairs=%d pad=%d n=1..33: %d bit-exact, %d MISMATCH; chain alone, cycles per run at n = 7 8 9 15 16 17 31 32 33:", LG,
+               mfsgd_chain_pairs(), mfsgd_pad_chain(LG), exact, wrong);
+        for (int n : {7, 8, 9, 15, 16, 17, 31, 32, 33}) printf(" %.0f", res[1][n].chain);
+        printf("\n");
+    }
     return 0;
 }
