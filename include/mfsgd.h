@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver (additions: no existing call changed) */
+#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver; + mfsgd_set_validation, mfsgd_validation_size, mfsgd_validation_rmse, mfsgd_rmse_pairs, mfsgd_train_early_stop (additions: no existing call changed) */
 
 typedef enum mfsgd_status {
     MFSGD_OK = 0,
@@ -262,6 +262,57 @@ int mfsgd_train_schedule(mfsgd_handle* h, int32_t epochs, const float* lr, const
  * rewrite between two epochs ends the call as it ends mfsgd_train_schedule: the epochs so far stay applied (lr_used
  * and rmse_per_epoch are valid up to there), the handle holds the next rate but no schedules. */
 int mfsgd_train_bold_driver(mfsgd_handle* h, int32_t epochs, float up, float down, float* lr_used, double* rmse_per_epoch);
+
+/* ---- a held-out set on the device; early stopping on its RMSE -------------------------------------------------------
+ * Every RMSE above is over the ratings the model is trained on.  These calls measure pairs it is NOT trained on: the
+ * error of a pair is e = r - dot(P[u], Q[i]) in fp32, the dot being the bits mfsgd_predict() returns, and the SSE is
+ * the sum of (double)e * (double)e (csrc/validate.hip).  The result is a pure function of the factor bits, the pair
+ * list in the order given and k: pair j is added to partial j mod 16384, each partial in ascending j, and the partials
+ * are folded in one fixed order -- nothing depends on the device's size, on blocks / waves / flags or on the launch
+ * path, and the same call twice gives the same 64 bits.  A NaN or Inf in a rating or a factor propagates.  Duplicate
+ * pairs are allowed.  The model is not modified by the three measuring calls.
+ * MFSGD_ERR_INVALID_ARG (messages "set_validation: ...", "validation_rmse: ...", "rmse_pairs: ...", "early_stop: ..."),
+ * checked before any device work: negative n or max_epochs, a null array that is needed, a user or item out of range,
+ * patience < 1, min_delta NaN or negative, a NaN in lr / lambda, null epochs_run / best_epoch.  MFSGD_ERR_STATE:
+ * n_parts != 1; factors never initialised, set or loaded (for the calls that read them); no ratings, or an empty
+ * validation set, for mfsgd_train_early_stop with max_epochs > 0.  MFSGD_ERR_NO_DEVICE: a valid compute call without a
+ * usable GPU; there is never a CPU result.  max_epochs == 0 and mfsgd_rmse_pairs with n == 0 are MFSGD_OK and touch
+ * nothing.
+ *
+ * The held-out set of a handle: n pairs, copied; replaces an earlier one; n == 0 (pointers may be NULL) clears it and
+ * frees its device memory.  Host-only: works without a GPU, touches no schedule and no factor, survives
+ * mfsgd_set_ratings / mfsgd_set_hyper / mfsgd_load_factors.  The pairs go to the device at the first call that needs
+ * them there and the host copy is dropped then. */
+int mfsgd_set_validation(mfsgd_handle* h, const int32_t* u, const int32_t* i, const float* r, int64_t n);
+int mfsgd_validation_size(const mfsgd_handle* h, int64_t* n);
+/* RMSE (and, nullable, the SSE) of the held-out set under the current factors; an empty set gives 0.0 like mfsgd_rmse. */
+int mfsgd_validation_rmse(mfsgd_handle* h, double* rmse, double* sse);
+/* The same for pairs of the caller's, nothing kept: uploaded in pieces of bounded size (2^20 pairs), freed before
+ * return.  The SSE is the fp64 sum of the pieces' SSEs in order.  For a list that fits in one piece this is bit for bit
+ * what mfsgd_validation_rmse gives after mfsgd_set_validation of the same arrays. */
+int mfsgd_rmse_pairs(mfsgd_handle* h, const int32_t* u, const int32_t* i, const float* r, int64_t n, double* rmse, double* sse);
+/* Train until the held-out RMSE stops improving.  The rule, in full:
+ *     best = +inf, best_epoch = -1, bad = 0
+ *     for e = 0 .. max_epochs - 1:
+ *         train one epoch, at lr[e] / lambda[e] where given (re-baked as by mfsgd_set_hyper only when the pair of values
+ *             changes, as in mfsgd_train_schedule; a null array: the handle's current value throughout)
+ *         train_rmse[e] = RMSE over the training ratings, if asked for
+ *         v = val_rmse[e] = RMSE of the held-out set
+ *         if v < best - min_delta:   (a NaN compares false; the first finite v always improves on +inf)
+ *             best = v, best_epoch = e, bad = 0; with restore_best, P and Q are copied to a snapshot on the device
+ *         else: bad = bad + 1; stop when bad >= patience
+ * *epochs_run = epochs trained; entries of val_rmse / train_rmse beyond that are untouched.  Afterwards, if
+ * restore_best, best_epoch >= 0 and best_epoch != epochs_run - 1, the snapshot is copied back: the factors are exactly
+ * those after epoch best_epoch.  With best_epoch == -1 (no finite improvement) they stay as trained.  The handle keeps
+ * the lr / lambda of the last epoch run.  The snapshot (device to device, on the handle's stream; allocated only with
+ * restore_best) is freed before the call returns, on every path.  A failed re-bake ends the call as it ends
+ * mfsgd_train_schedule: the epochs so far stay applied (*epochs_run, val_rmse and train_rmse are valid up to there),
+ * nothing is restored, the handle holds the new values but no schedules. */
+int mfsgd_train_early_stop(mfsgd_handle* h, int32_t max_epochs, int32_t patience, double min_delta, int32_t restore_best,
+                           const float* lr, const float* lambda,          /* nullable, max_epochs entries: as mfsgd_train_schedule */
+                           double* val_rmse,                              /* required when max_epochs > 0 */
+                           double* train_rmse,                            /* nullable: one extra training-set pass per epoch */
+                           int32_t* epochs_run, int32_t* best_epoch);     /* both required */
 
 /* Timed variant used by bench.py: runs `epochs` training passes bracketed by
  * HIP events on the handle's stream and returns the elapsed device time and

@@ -118,6 +118,12 @@ SIGNATURES = {
     "mfsgd_get_hyper": (C.c_int, [_H, _f32p, _f32p]),
     "mfsgd_train_schedule": (C.c_int, [_H, C.c_int32, _f32p, _f32p, _f64p]),
     "mfsgd_train_bold_driver": (C.c_int, [_H, C.c_int32, C.c_float, C.c_float, _f32p, _f64p]),
+    "mfsgd_set_validation": (C.c_int, [_H, _i32p, _i32p, _f32p, C.c_int64]),
+    "mfsgd_validation_size": (C.c_int, [_H, _i64p]),
+    "mfsgd_validation_rmse": (C.c_int, [_H, _f64p, _f64p]),
+    "mfsgd_rmse_pairs": (C.c_int, [_H, _i32p, _i32p, _f32p, C.c_int64, _f64p, _f64p]),
+    "mfsgd_train_early_stop": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_double, C.c_int32, _f32p, _f32p, _f64p, _f64p,
+                                         _i32p, _i32p]),
     "mfsgd_ratings_file_open": (C.c_int, [C.c_char_p, C.c_int32, C.POINTER(_H)]),
     "mfsgd_ratings_file_info": (C.c_int, [_H, _i64p, _i32p, _i32p]),
     "mfsgd_ratings_file_read": (C.c_int, [_H, _i32p, _i32p, _f32p, _i64p, _i64p]),

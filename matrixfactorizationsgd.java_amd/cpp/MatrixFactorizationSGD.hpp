@@ -178,6 +178,57 @@ class MatrixFactorizationSGD {
         return {std::move(used), std::move(rmse)};
     }
 
+    // ---- held-out validation and early stopping on it ------------------------------------------------------------------
+    // void setValidation(int[] u, int[] i, float[] r): the held-out set of the model, copied and kept on the device from
+    // the first call that measures it; empty arrays clear it
+    void setValidation(const std::vector<int32_t>& u, const std::vector<int32_t>& i, const std::vector<float>& r) {
+        if (u.size() != i.size() || u.size() != r.size()) throw std::invalid_argument("length mismatch");
+        check(mfsgd_set_validation(h_, u.data(), i.data(), r.data(), (int64_t)u.size()));
+    }
+    int64_t validationSize() {
+        int64_t n = 0;
+        check(mfsgd_validation_size(h_, &n));
+        return n;
+    }
+    // double validationRmse(): RMSE of the held-out set under the current factors (sse, nullable: the sum of squares)
+    double validationRmse(double* sse = nullptr) {
+        double out = 0.0;
+        check(mfsgd_validation_rmse(h_, &out, sse));
+        return out;
+    }
+    // double rmseOn(int[] u, int[] i, float[] r): the same for pairs of the caller's; nothing is kept
+    double rmseOn(const std::vector<int32_t>& u, const std::vector<int32_t>& i, const std::vector<float>& r, double* sse = nullptr) {
+        if (u.size() != i.size() || u.size() != r.size()) throw std::invalid_argument("length mismatch");
+        double out = 0.0;
+        check(mfsgd_rmse_pairs(h_, u.data(), i.data(), r.data(), (int64_t)u.size(), &out, sse));
+        return out;
+    }
+    // EarlyStopping trainEarlyStopping(int maxEpochs, int patience, double minDelta, boolean restoreBest, float[] lr,
+    // float[] lambda, boolean trainRmse): trains until the held-out RMSE has not improved by more than minDelta for
+    // `patience` epochs in a row (include/mfsgd.h states the rule); with restoreBest the model ends with the factors of
+    // the best epoch.  lr / lambda: nullable, maxEpochs entries.  valRmse / trainRmse hold epochsRun entries
+    struct EarlyStopping {
+        std::vector<double> valRmse, trainRmse;
+        int32_t epochsRun = 0, bestEpoch = -1;
+    };
+    EarlyStopping trainEarlyStopping(int maxEpochs, int patience = 3, double minDelta = 0.0, bool restoreBest = true,
+                                     const std::vector<float>* lr = nullptr, const std::vector<float>* lambda = nullptr,
+                                     bool trainRmse = false) {
+        if (maxEpochs < 0) throw std::invalid_argument("negative maxEpochs");
+        if ((lr && lr->size() != (size_t)maxEpochs) || (lambda && lambda->size() != (size_t)maxEpochs))
+            throw std::invalid_argument("length mismatch");
+        EarlyStopping out;
+        out.valRmse.resize((size_t)maxEpochs);
+        if (trainRmse) out.trainRmse.resize((size_t)maxEpochs);
+        const int rc = mfsgd_train_early_stop(h_, maxEpochs, patience, minDelta, restoreBest ? 1 : 0, lr ? lr->data() : nullptr,
+                                              lambda ? lambda->data() : nullptr, out.valRmse.data(),
+                                              trainRmse ? out.trainRmse.data() : nullptr, &out.epochsRun, &out.bestEpoch);
+        check(rc);
+        out.valRmse.resize((size_t)out.epochsRun);
+        if (trainRmse) out.trainRmse.resize((size_t)out.epochsRun);
+        return out;
+    }
+
     std::pair<std::vector<float>, std::vector<float>> factors() {
         std::vector<float> p((size_t)users_ * k_), q((size_t)items_ * k_);
         check(mfsgd_get_factors(h_, p.data(), q.data()));

@@ -217,6 +217,7 @@ void mfsgd_destroy(mfsgd_handle* h) {
     h->parts.clear();
     h->dP.reset();
     h->dQ.reset();
+    h->val = Validation{};
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->side_stream) {

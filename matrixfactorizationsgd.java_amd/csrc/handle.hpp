@@ -47,6 +47,16 @@ struct Part {
     }
 };
 
+// The held-out set of a handle (mfsgd_set_validation): the pairs on the host as given until the first call that needs
+// them on the device, there from then on, with the scratch of the SSE pass over them (kPairsSlots partials, then the sum).
+struct Validation {
+    int64_t n = 0;
+    std::vector<int32_t> hu, hi;
+    std::vector<float> hr;
+    bool on_device = false;
+    DevBuf du, di, dr, d_sse;
+};
+
 // d_sync: done[B] words (kDoneStride apart), then {arrivals, generation, -, -} of the kernel's start-of-launch
 // barrier, then {abort code, launches that started, -, -}.  Zeroed once, when allocated; the kernel keeps it
 // consistent from launch to launch by itself.
@@ -75,6 +85,8 @@ struct mfsgd_handle {
     enum class Where { None, Host, Device } where = Where::None;
     std::vector<float> hP, hQ;
     mfsgd::DevBuf dP, dQ;
+
+    mfsgd::Validation val;
 
     bool device_ready = false;
     int n_cu = 0;

@@ -1,5 +1,5 @@
 // kernels.hpp -- host-callable launchers of every kernel unit: epoch.hip, cells.hip, kernels.hip, foldin.hip,
-// rehyper.hip, recommend.hip and rank.hip.
+// rehyper.hip, recommend.hip, rank.hip and validate.hip.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -104,5 +104,15 @@ hipError_t recommend_excl_lists(unsigned long long* keys, unsigned long long* ke
 hipError_t launch_rank_items(int L, const float* P, const float* Q, const int32_t* rows, int n_slots, const long long* off,
                              long long base, const int32_t* items, int32_t n_items, const RecommendExcl& ex,
                              int32_t* out, hipStream_t st);
+
+// validate.hip.  Sum over the n >= 1 pairs of (double)e * (double)e with e = r[j] - dot(P[u[j]], Q[i[j]]) in fp32 (the
+// bits launch_predict returns), into *out.  Pair j is added to partial j mod kPairsSlots, each partial in ascending j,
+// and launch_reduce_sse folds the pairs_sse_partials(n) partials that have a pair: the 64 bits of *out are a function of
+// the factors, the pair list in its order and k, of nothing else.  partial: room for kPairsSlots doubles.  Every user
+// is a row of P and every item a row of Q (kp-padded rows): the caller checks.  Asynchronous on st.
+constexpr int kPairsSlots = 16384;
+int64_t pairs_sse_partials(int64_t n);
+hipError_t launch_pairs_sse(int L, const float* P, const float* Q, const int32_t* u, const int32_t* i, const float* r,
+                            int64_t n, double* partial, double* out, hipStream_t st);
 
 }  // namespace mfsgd

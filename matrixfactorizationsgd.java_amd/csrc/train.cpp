@@ -1,6 +1,6 @@
 // train.cpp -- epochs: the launch paths (one launch per round, the persistent kernel, the captured graph), the
-// persistent kernel's recovery protocol, the training calls, lr / lambda on a live handle, the DSGD partition calls
-// and the diagnostics of the epoch kernel.
+// persistent kernel's recovery protocol, the training calls, lr / lambda on a live handle, the held-out set with its
+// RMSE and early stopping on it, the DSGD partition calls and the diagnostics of the epoch kernel.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -322,6 +322,71 @@ static int run_epochs(mfsgd_handle* h, int epochs, const float* lr, const float*
     return settle_epochs_ok(h, h->parts[0], Q, h->stream, pending);
 }
 
+// Held-out pairs ("Held-out validation and early stopping") ---------------------
+// Pairs of one upload of mfsgd_rmse_pairs: 12 MB of staging.  A list of at most this many pairs is one launch, the
+// launch mfsgd_validation_rmse makes for the handle's own set.  (include/mfsgd.h states the size, and PIECE of
+// tests/test_validation_gpu.py cuts its slices by it: change the three together.)
+constexpr int64_t kPairsPiece = (int64_t)1 << 20;
+
+// The argument checks of a pair list, before any device work: `call` starts the message.
+static int check_pairs(const mfsgd_handle* h, const char* call, const int32_t* u, const int32_t* i, const float* r, int64_t n) {
+    if (n < 0) return fail(h, MFSGD_ERR_INVALID_ARG, std::string(call) + ": n is negative");
+    if (n > 0 && (!u || !i || !r)) return fail(h, MFSGD_ERR_INVALID_ARG, std::string(call) + ": u, i or r is null");
+    for (int64_t j = 0; j < n; ++j)
+        if (u[j] < 0 || u[j] >= h->cfg.n_users || i[j] < 0 || i[j] >= h->cfg.n_items)
+            return fail(h, MFSGD_ERR_INVALID_ARG, std::string(call) + ": pair " + std::to_string(j) + " out of range");
+    return MFSGD_OK;
+}
+
+// What every call that reads the factors asks before it asks for a device.
+static int check_reads_factors(const mfsgd_handle* h, const char* call) {
+    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, std::string(call) + ": single-partition handles only");
+    if (h->where == mfsgd_handle::Where::None) return fail(h, MFSGD_ERR_STATE, std::string(call) + ": factors not initialised");
+    return MFSGD_OK;
+}
+
+// The scratch of launch_pairs_sse: its partials, then the sum.
+static int alloc_pairs_scratch(mfsgd_handle* h, DevBuf& b) { return dev_alloc(h, b, sizeof(double) * ((size_t)kPairsSlots + 1)); }
+
+// SSE of n >= 1 pairs that are on the device, under the handle's factors (P is always the users' matrix, whichever
+// side of the kernels the schedule gave it: as mfsgd_predict reads it), on the handle's stream; waits for it.
+static int pairs_sse_sync(mfsgd_handle* h, const char* call, const DevBuf& du, const DevBuf& di, const DevBuf& dr, int64_t n,
+                          const DevBuf& scratch, double* sse) {
+    const std::string prefix = std::string(call) + ": ";
+    auto bad = [h, &prefix](hipError_t e) { return serve_fail(h, prefix.c_str(), e); };
+    double* partial = scratch.as<double>();
+    HIPCHK_OR(bad, launch_pairs_sse(h->geo.L, h->dP.as<const float>(), h->dQ.as<const float>(), du.as<const int32_t>(),
+                                    di.as<const int32_t>(), dr.as<const float>(), n, partial, partial + kPairsSlots, h->stream));
+    HIPCHK_OR(bad, hipMemcpyAsync(sse, partial + kPairsSlots, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
+    return MFSGD_OK;
+}
+
+// The handle's held-out set on the device (the device is there: the caller has asked for it); the host copy goes.
+static int validation_to_device(mfsgd_handle* h) {
+    Validation& v = h->val;
+    if (v.on_device || v.n == 0) return MFSGD_OK;
+    int rc;
+    if ((rc = upload(h, v.du, v.hu)) || (rc = upload(h, v.di, v.hi)) || (rc = upload(h, v.dr, v.hr)) ||
+        (rc = alloc_pairs_scratch(h, v.d_sse))) {
+        v.du.reset(), v.di.reset(), v.dr.reset(), v.d_sse.reset();
+        return rc;
+    }
+    v.on_device = true;
+    std::vector<int32_t>().swap(v.hu);
+    std::vector<int32_t>().swap(v.hi);
+    std::vector<float>().swap(v.hr);
+    return MFSGD_OK;
+}
+
+// SSE of the handle's held-out set (not empty) under the current factors.
+static int validation_sse(mfsgd_handle* h, const char* call, double* sse) {
+    int rc = factors_to_device(h);
+    if (rc || (rc = validation_to_device(h))) return rc;
+    const Validation& v = h->val;
+    return pairs_sse_sync(h, call, v.du, v.di, v.dr, v.n, v.d_sse, sse);
+}
+
 }  // namespace mfsgd
 
 using namespace mfsgd;
@@ -420,6 +485,142 @@ int mfsgd_rmse(mfsgd_handle* h, double* out) {
         int rc = prepare_compute(h);
         if (rc) return rc;
         return rmse_of(h, h->parts[0], h->dQ.as<const float>(), out);
+    });
+}
+
+int mfsgd_set_validation(mfsgd_handle* h, const int32_t* u, const int32_t* i, const float* r, int64_t n) {
+    return guarded(h, "set_validation", [&]() -> int {
+        if (const int rc = check_pairs(h, "set_validation", u, i, r, n)) return rc;
+        if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "set_validation: single-partition handles only");
+        Validation fresh;
+        if (n > 0) {
+            fresh.hu.assign(u, u + n);
+            fresh.hi.assign(i, i + n);
+            fresh.hr.assign(r, r + n);
+            fresh.n = n;
+        }
+        if (h->val.on_device) {  // an SSE pass over the old set cannot be in flight (every call waits), a D2H copy neither
+            (void)hipSetDevice(h->cfg.device);
+            (void)hipStreamSynchronize(h->stream);
+        }
+        h->val = std::move(fresh);
+        return MFSGD_OK;
+    });
+}
+
+int mfsgd_validation_size(const mfsgd_handle* h, int64_t* n) {
+    return guarded(h, "validation_size", [&]() -> int {
+        if (!n) return fail(h, MFSGD_ERR_INVALID_ARG, "validation_size: null argument");
+        *n = h->val.n;
+        return MFSGD_OK;
+    });
+}
+
+int mfsgd_validation_rmse(mfsgd_handle* h, double* rmse, double* sse) {
+    return guarded(h, "validation_rmse", [&]() -> int {
+        if (!rmse) return fail(h, MFSGD_ERR_INVALID_ARG, "validation_rmse: rmse is null");
+        if (const int rc = check_reads_factors(h, "validation_rmse")) return rc;
+        double s = 0.0;
+        if (h->val.n > 0)
+            if (const int rc = validation_sse(h, "validation_rmse", &s)) return rc;
+        *rmse = h->val.n > 0 ? std::sqrt(s / (double)h->val.n) : 0.0;
+        if (sse) *sse = s;
+        return MFSGD_OK;
+    });
+}
+
+int mfsgd_rmse_pairs(mfsgd_handle* h, const int32_t* u, const int32_t* i, const float* r, int64_t n, double* rmse, double* sse) {
+    return guarded(h, "rmse_pairs", [&]() -> int {
+        if (!rmse) return fail(h, MFSGD_ERR_INVALID_ARG, "rmse_pairs: rmse is null");
+        if (const int rc = check_pairs(h, "rmse_pairs", u, i, r, n)) return rc;
+        if (n == 0) {
+            *rmse = 0.0;
+            if (sse) *sse = 0.0;
+            return MFSGD_OK;
+        }
+        int rc = check_reads_factors(h, "rmse_pairs");
+        if (rc || (rc = factors_to_device(h))) return rc;
+        auto bad = [h](hipError_t e) { return serve_fail(h, "rmse_pairs: ", e); };
+        const int64_t piece = std::min(n, kPairsPiece);
+        DevBuf du, di, dr, scratch;
+        if ((rc = dev_alloc(h, du, sizeof(int32_t) * (size_t)piece))) return rc;
+        if ((rc = dev_alloc(h, di, sizeof(int32_t) * (size_t)piece))) return rc;
+        if ((rc = dev_alloc(h, dr, sizeof(float) * (size_t)piece))) return rc;
+        if ((rc = alloc_pairs_scratch(h, scratch))) return rc;
+        double total = 0.0;
+        for (int64_t j0 = 0; j0 < n; j0 += piece) {
+            const int64_t c = std::min(piece, n - j0);
+            double s = 0.0;
+            HIPCHK_OR(bad, hipMemcpyAsync(du.get(), u + j0, sizeof(int32_t) * (size_t)c, hipMemcpyHostToDevice, h->stream));
+            HIPCHK_OR(bad, hipMemcpyAsync(di.get(), i + j0, sizeof(int32_t) * (size_t)c, hipMemcpyHostToDevice, h->stream));
+            HIPCHK_OR(bad, hipMemcpyAsync(dr.get(), r + j0, sizeof(float) * (size_t)c, hipMemcpyHostToDevice, h->stream));
+            if ((rc = pairs_sse_sync(h, "rmse_pairs", du, di, dr, c, scratch, &s))) return rc;  // (the staging buffers are reused)
+            total = j0 == 0 ? s : total + s;
+        }
+        *rmse = std::sqrt(total / (double)n);
+        if (sse) *sse = total;
+        return MFSGD_OK;
+    });
+}
+
+int mfsgd_train_early_stop(mfsgd_handle* h, int32_t max_epochs, int32_t patience, double min_delta, int32_t restore_best,
+                           const float* lr, const float* lambda, double* val_rmse, double* train_rmse, int32_t* epochs_run,
+                           int32_t* best_epoch) {
+    return guarded(h, "early_stop", [&]() -> int {
+        if (max_epochs < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "early_stop: negative max_epochs");
+        if (patience < 1) return fail(h, MFSGD_ERR_INVALID_ARG, "early_stop: patience must be at least 1");
+        if (!(min_delta >= 0.0)) return fail(h, MFSGD_ERR_INVALID_ARG, "early_stop: min_delta is NaN or negative");
+        if (!epochs_run || !best_epoch) return fail(h, MFSGD_ERR_INVALID_ARG, "early_stop: epochs_run or best_epoch is null");
+        if (max_epochs > 0 && !val_rmse) return fail(h, MFSGD_ERR_INVALID_ARG, "early_stop: val_rmse is null");
+        for (int e = 0; e < max_epochs; ++e)
+            if ((lr && is_nan(lr[e])) || (lambda && is_nan(lambda[e])))
+                return fail(h, MFSGD_ERR_INVALID_ARG, "early_stop: lr / lambda of epoch " + std::to_string(e) + " is NaN");
+        if (max_epochs == 0) {
+            *epochs_run = 0;
+            *best_epoch = -1;
+            return MFSGD_OK;
+        }
+        if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "early_stop: handle has n_parts > 1, drive it with mfsgd_part_train");
+        if (!h->have_ratings) return fail(h, MFSGD_ERR_STATE, "early_stop: no ratings: call mfsgd_set_ratings first");
+        if (h->val.n == 0) return fail(h, MFSGD_ERR_STATE, "early_stop: no validation set: call mfsgd_set_validation first");
+        int rc = check_reads_factors(h, "early_stop");
+        if (rc) return rc;
+        *epochs_run = 0;  // (a call rejected above has touched nothing; from here on the two say how far it got)
+        *best_epoch = -1;
+        if ((rc = prepare_compute(h)) || (rc = validation_to_device(h))) return rc;
+        auto bad = [h](hipError_t e) { return serve_fail(h, "early_stop: ", e); };
+        DevBuf snap_p, snap_q;  // the factors after the best epoch so far; gone when this returns, whichever way
+        if (restore_best) {
+            if ((rc = dev_alloc(h, snap_p, h->dP.bytes()))) return rc;
+            if ((rc = dev_alloc(h, snap_q, h->dQ.bytes()))) return rc;
+        }
+        double best = HUGE_VAL;
+        int bad_epochs = 0;
+        for (int e = 0; e < max_epochs; ++e) {
+            if ((rc = run_epochs(h, 1, lr ? lr + e : nullptr, lambda ? lambda + e : nullptr, train_rmse ? train_rmse + e : nullptr)))
+                return rc;
+            *epochs_run = e + 1;
+            double s = 0.0;
+            if ((rc = validation_sse(h, "early_stop", &s))) return rc;
+            const double v = val_rmse[e] = std::sqrt(s / (double)h->val.n);
+            if (v < best - min_delta) {  // (a NaN compares false)
+                best = v;
+                *best_epoch = e;
+                bad_epochs = 0;
+                if (restore_best) {
+                    HIPCHK_OR(bad, hipMemcpyAsync(snap_p.get(), h->dP.get(), h->dP.bytes(), hipMemcpyDeviceToDevice, h->stream));
+                    HIPCHK_OR(bad, hipMemcpyAsync(snap_q.get(), h->dQ.get(), h->dQ.bytes(), hipMemcpyDeviceToDevice, h->stream));
+                }
+            } else if (++bad_epochs >= patience) {
+                break;
+            }
+        }
+        if (restore_best && *best_epoch >= 0 && *best_epoch != *epochs_run - 1) {
+            HIPCHK_OR(bad, hipMemcpyAsync(h->dP.get(), snap_p.get(), h->dP.bytes(), hipMemcpyDeviceToDevice, h->stream));
+            HIPCHK_OR(bad, hipMemcpyAsync(h->dQ.get(), snap_q.get(), h->dQ.bytes(), hipMemcpyDeviceToDevice, h->stream));
+        }
+        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // the snapshot is freed behind this
+        return MFSGD_OK;
     });
 }
 

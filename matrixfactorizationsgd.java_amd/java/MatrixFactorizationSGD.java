@@ -217,6 +217,66 @@ public final class MatrixFactorizationSGD implements AutoCloseable {
         return rmse;
     }
 
+    /**
+     * The held-out set of the model (mfsgd_set_validation): copied, kept on the device from the first call that
+     * measures it; empty arrays clear it.  Needs no GPU; survives train(), setHyper() and loadFactors().
+     */
+    public void setValidation(int[] u, int[] i, float[] r) {
+        if (u.length != i.length || u.length != r.length) throw new IllegalArgumentException("length mismatch");
+        nativeSetValidation(handle, u, i, r);
+    }
+
+    public long validationSize() {
+        return nativeValidationSize(handle);
+    }
+
+    /** RMSE of the held-out set under the current factors; 0.0 for an empty set. */
+    public double validationRmse() {
+        double[] out = new double[2];
+        nativeValidationRmse(handle, out);
+        return out[0];
+    }
+
+    /** RMSE of the given pairs under the current factors (mfsgd_rmse_pairs): nothing is kept. */
+    public double rmseOn(int[] u, int[] i, float[] r) {
+        if (u.length != i.length || u.length != r.length) throw new IllegalArgumentException("length mismatch");
+        double[] out = new double[2];
+        nativeRmsePairs(handle, u, i, r, out);
+        return out[0];
+    }
+
+    /** What trainEarlyStopping() did: the curves hold epochsRun entries ({@code trainRmse} null unless asked for). */
+    public static final class EarlyStopping {
+        public final double[] valRmse, trainRmse;
+        public final int epochsRun, bestEpoch;
+
+        EarlyStopping(double[] valRmse, double[] trainRmse, int epochsRun, int bestEpoch) {
+            this.valRmse = valRmse;
+            this.trainRmse = trainRmse;
+            this.epochsRun = epochsRun;
+            this.bestEpoch = bestEpoch;
+        }
+    }
+
+    /**
+     * Trains until the held-out RMSE has not improved by more than {@code minDelta} for {@code patience} epochs in a
+     * row, at most {@code maxEpochs} epochs (mfsgd_train_early_stop states the rule); with {@code restoreBest} the model
+     * ends with the factors of the best epoch.  {@code lr} / {@code lambda}: per-epoch values as in trainSchedule(),
+     * maxEpochs entries each, or null for the current value throughout.
+     */
+    public EarlyStopping trainEarlyStopping(int maxEpochs, int patience, double minDelta, boolean restoreBest, float[] lr,
+                                            float[] lambda, boolean trainRmse) {
+        if (maxEpochs < 0) throw new IllegalArgumentException("negative maxEpochs");
+        if ((lr != null && lr.length != maxEpochs) || (lambda != null && lambda.length != maxEpochs))
+            throw new IllegalArgumentException("length mismatch");
+        double[] val = new double[maxEpochs];
+        double[] trn = trainRmse ? new double[maxEpochs] : null;
+        int[] out = new int[2];
+        nativeTrainEarlyStop(handle, maxEpochs, patience, minDelta, restoreBest ? 1 : 0, lr, lambda, val, trn, out);
+        return new EarlyStopping(java.util.Arrays.copyOf(val, out[0]), trn == null ? null : java.util.Arrays.copyOf(trn, out[0]),
+                                 out[0], out[1]);
+    }
+
     /** P (users x k) and Q (items x k), row-major. */
     public float[][] factors() {
         float[] p = new float[users * k], q = new float[items * k];
@@ -329,6 +389,13 @@ public final class MatrixFactorizationSGD implements AutoCloseable {
     private static native void nativeTrainSchedule(long h, float[] lr, float[] lambda, double[] rmsePerEpoch);
     private static native void nativeTrainBoldDriver(long h, int epochs, float up, float down, float[] lrUsed,
                                                      double[] rmsePerEpoch);
+    private static native void nativeSetValidation(long h, int[] u, int[] i, float[] r);
+    private static native long nativeValidationSize(long h);
+    private static native void nativeValidationRmse(long h, double[] rmseSse);
+    private static native void nativeRmsePairs(long h, int[] u, int[] i, float[] r, double[] rmseSse);
+    private static native void nativeTrainEarlyStop(long h, int maxEpochs, int patience, double minDelta, int restoreBest,
+                                                    float[] lr, float[] lambda, double[] valRmse, double[] trainRmse,
+                                                    int[] epochsRunBestEpoch);
     private static native void nativePredict(long h, int[] u, int[] i, float[] out);
     private static native void nativeRecommend(long h, int[] users, int topN, int[] items, float[] scores);
     private static native void nativeRecommendExcluding(long h, int[] users, int topN, int[] exclU, int[] exclI, int[] items,

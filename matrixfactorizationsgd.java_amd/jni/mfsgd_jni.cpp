@@ -200,6 +200,90 @@ JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeTrainBoldDriver(JNIEnv*
     throw_status(env, H(h), rc);
 }
 
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeSetValidation(JNIEnv* env, jclass, jlong h, jintArray u, jintArray i,
+                                                                       jfloatArray r) {
+    if (!u || !i || !r) return throw_new(env, "java/lang/NullPointerException", "setValidation");
+    const jsize n = env->GetArrayLength(u);
+    if (env->GetArrayLength(i) != n || env->GetArrayLength(r) != n)
+        return throw_new(env, "java/lang/IllegalArgumentException", "u, i and r must have the same length");
+    auto cu = alloc<int32_t>(env, (size_t)n);
+    auto ci = alloc<int32_t>(env, (size_t)n);
+    auto cr = alloc<float>(env, (size_t)n);
+    if (!cu || !ci || !cr) return;
+    env->GetIntArrayRegion(u, 0, n, reinterpret_cast<jint*>(cu.get()));
+    env->GetIntArrayRegion(i, 0, n, reinterpret_cast<jint*>(ci.get()));
+    env->GetFloatArrayRegion(r, 0, n, cr.get());
+    if (env->ExceptionCheck()) return;
+    throw_status(env, H(h), mfsgd_set_validation(H(h), cu.get(), ci.get(), cr.get(), n));
+}
+
+JNIEXPORT jlong JNICALL Java_MatrixFactorizationSGD_nativeValidationSize(JNIEnv* env, jclass, jlong h) {
+    int64_t n = 0;
+    throw_status(env, H(h), mfsgd_validation_size(H(h), &n));
+    return n;
+}
+
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeValidationRmse(JNIEnv* env, jclass, jlong h, jdoubleArray out) {
+    if (!out || env->GetArrayLength(out) < 2)
+        return throw_new(env, "java/lang/IllegalArgumentException", "validationRmse: out needs two entries");
+    double v[2] = {0.0, 0.0};
+    const int rc = mfsgd_validation_rmse(H(h), &v[0], &v[1]);
+    if (rc == MFSGD_OK) env->SetDoubleArrayRegion(out, 0, 2, v);
+    throw_status(env, H(h), rc);
+}
+
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeRmsePairs(JNIEnv* env, jclass, jlong h, jintArray u, jintArray i,
+                                                                   jfloatArray r, jdoubleArray out) {
+    if (!u || !i || !r || !out) return throw_new(env, "java/lang/NullPointerException", "rmseOn");
+    const jsize n = env->GetArrayLength(u);
+    if (env->GetArrayLength(i) != n || env->GetArrayLength(r) != n || env->GetArrayLength(out) < 2)
+        return throw_new(env, "java/lang/IllegalArgumentException", "u, i and r must have the same length, out two entries");
+    // copies, not pins: mfsgd_rmse_pairs launches a kernel per piece and waits for it
+    auto cu = alloc<int32_t>(env, (size_t)n);
+    auto ci = alloc<int32_t>(env, (size_t)n);
+    auto cr = alloc<float>(env, (size_t)n);
+    if (!cu || !ci || !cr) return;
+    env->GetIntArrayRegion(u, 0, n, reinterpret_cast<jint*>(cu.get()));
+    env->GetIntArrayRegion(i, 0, n, reinterpret_cast<jint*>(ci.get()));
+    env->GetFloatArrayRegion(r, 0, n, cr.get());
+    if (env->ExceptionCheck()) return;
+    double v[2] = {0.0, 0.0};
+    const int rc = mfsgd_rmse_pairs(H(h), cu.get(), ci.get(), cr.get(), n, &v[0], &v[1]);
+    if (rc == MFSGD_OK) env->SetDoubleArrayRegion(out, 0, 2, v);
+    throw_status(env, H(h), rc);
+}
+
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeTrainEarlyStop(JNIEnv* env, jclass, jlong h, jint max_epochs,
+                                                                        jint patience, jdouble min_delta, jint restore_best,
+                                                                        jfloatArray lr, jfloatArray lambda, jdoubleArray val_rmse,
+                                                                        jdoubleArray train_rmse, jintArray out) {
+    if (!val_rmse || !out) return throw_new(env, "java/lang/NullPointerException", "trainEarlyStopping");
+    if (max_epochs < 0 || env->GetArrayLength(val_rmse) < max_epochs || env->GetArrayLength(out) < 2 ||
+        (lr && env->GetArrayLength(lr) != max_epochs) || (lambda && env->GetArrayLength(lambda) != max_epochs) ||
+        (train_rmse && env->GetArrayLength(train_rmse) < max_epochs))
+        return throw_new(env, "java/lang/IllegalArgumentException", "lr, lambda, valRmse and trainRmse need one entry per epoch, out two");
+    // native copies, nothing pinned: the call trains, measures and re-bakes the schedule between epochs
+    auto clr = alloc<float>(env, (size_t)max_epochs);
+    auto clam = alloc<float>(env, (size_t)max_epochs);
+    auto cval = alloc<double>(env, (size_t)max_epochs);
+    auto ctrn = alloc<double>(env, (size_t)max_epochs);
+    if (!clr || !clam || !cval || !ctrn) return;
+    if (lr) env->GetFloatArrayRegion(lr, 0, max_epochs, clr.get());
+    if (lambda) env->GetFloatArrayRegion(lambda, 0, max_epochs, clam.get());
+    if (env->ExceptionCheck()) return;
+    int32_t ran[2] = {0, -1};
+    const int rc = mfsgd_train_early_stop(H(h), max_epochs, patience, min_delta, restore_best, lr ? clr.get() : nullptr,
+                                          lambda ? clam.get() : nullptr, cval.get(), train_rmse ? ctrn.get() : nullptr, &ran[0],
+                                          &ran[1]);
+    // (the epochs that ran are reported even when a later one failed: they stay applied)
+    if (ran[0] > 0) {
+        env->SetDoubleArrayRegion(val_rmse, 0, ran[0], cval.get());
+        if (train_rmse) env->SetDoubleArrayRegion(train_rmse, 0, ran[0], ctrn.get());
+    }
+    env->SetIntArrayRegion(out, 0, 2, reinterpret_cast<const jint*>(ran));
+    throw_status(env, H(h), rc);
+}
+
 JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativePredict(JNIEnv* env, jclass, jlong h, jintArray u, jintArray i,
                                                                  jfloatArray out) {
     if (!u || !i || !out) return throw_new(env, "java/lang/NullPointerException", "predict");

@@ -246,6 +246,67 @@ class MatrixFactorizationSGD:
                 self.lr, self.lam = self.hyper()
         return used, out
 
+    # -- held-out validation ------------------------------------------------------
+    @staticmethod
+    def _triples(u, i, r):
+        uu, ii = _pairs(np.atleast_1d(u), np.atleast_1d(i), "u and i")
+        rr = _f32(np.atleast_1d(r))
+        if rr.shape != uu.shape:
+            raise ValueError("u, i, r must be 1-d arrays of equal length")
+        return uu, ii, rr
+
+    def set_validation(self, u, i, r):
+        """The held-out set of the model (mfsgd_set_validation): copied, kept on the device from the first call that
+        measures it; empty arrays clear it.  Needs no GPU; survives set_ratings, set_hyper and load_factors."""
+        uu, ii, rr = self._triples(u, i, r)
+        self._check(self._lib.mfsgd_set_validation(self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32), _p(rr, C.c_float),
+                                                   uu.size))
+
+    def validation_size(self):
+        n = C.c_int64(-1)
+        self._check(self._lib.mfsgd_validation_size(self._handle(), C.byref(n)))
+        return n.value
+
+    def validation_rmse(self, *, sse=False):
+        """RMSE of the held-out set under the current factors (sse=True: (rmse, sse)); 0.0 for an empty set."""
+        rm, s = C.c_double(), C.c_double()
+        self._check(self._lib.mfsgd_validation_rmse(self._handle(), C.byref(rm), C.byref(s)))
+        return (rm.value, s.value) if sse else rm.value
+
+    def rmse_on(self, u, i, r, *, sse=False):
+        """RMSE of the given pairs under the current factors (mfsgd_rmse_pairs): nothing is kept."""
+        uu, ii, rr = self._triples(u, i, r)
+        rm, s = C.c_double(), C.c_double()
+        self._check(self._lib.mfsgd_rmse_pairs(self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32), _p(rr, C.c_float),
+                                               uu.size, C.byref(rm), C.byref(s)))
+        return (rm.value, s.value) if sse else rm.value
+
+    def fit_early_stopping(self, max_epochs, patience=3, min_delta=0.0, restore_best=True, lr=None, lam=None,
+                           train_rmse=False):
+        """Trains until the held-out RMSE has not improved by more than min_delta for `patience` epochs in a row, at
+        most max_epochs epochs (mfsgd_train_early_stop states the rule); with restore_best the model ends with the
+        factors of the best epoch.  lr / lam: per-epoch values as in fit_schedule (None: the current one throughout).
+        Returns dict(val_rmse float64[epochs_run], train_rmse the same or None, epochs_run, best_epoch)."""
+        n = int(max_epochs)
+        lrs = None if lr is None else _f32(np.atleast_1d(lr))
+        lams = None if lam is None else _f32(np.atleast_1d(lam))
+        for a in (lrs, lams):
+            if a is not None and a.shape != (max(n, 0),):
+                raise ValueError("lr and lam must be 1-d arrays of max_epochs entries")
+        val = np.zeros(max(n, 0), np.float64)
+        trn = np.zeros(max(n, 0), np.float64) if train_rmse else None
+        ran, best = C.c_int32(0), C.c_int32(-1)
+        try:
+            self._check(self._lib.mfsgd_train_early_stop(
+                self._handle(), n, int(patience), float(min_delta), 1 if restore_best else 0,
+                None if lrs is None else _p(lrs, C.c_float), None if lams is None else _p(lams, C.c_float),
+                _p(val, C.c_double), None if trn is None else _p(trn, C.c_double), C.byref(ran), C.byref(best)))
+        finally:
+            if self._h:
+                self.lr, self.lam = self.hyper()
+        return dict(val_rmse=val[:ran.value], train_rmse=None if trn is None else trn[:ran.value],
+                    epochs_run=ran.value, best_epoch=best.value)
+
     def train_timed(self, epochs):
         """(elapsed device milliseconds, kernel launches) for `epochs` passes."""
         ms = C.c_double()

@@ -1,9 +1,9 @@
 """Timings of the paths around training: predict (batched), recommend (top-N, and top-N that leaves out
 the whole rating set), fold-in of users against the trained item factors and top-N for the folded rows, RMSE pass,
-set_ratings (schedule build).  Wall-clock, through the C-ABI (host arrays in and out, so PCIe
-copies are included); run it under `rocprofv3 --kernel-trace --stats` for the kernel times.
+set_ratings (schedule build), held-out validation RMSE and early stopping on it.  Wall-clock, through the C-ABI (host
+arrays in and out, so PCIe copies are included); run it under `rocprofv3 --kernel-trace --stats` for the kernel times.
 
-    python tools/bench_aux.py [WORKLOAD] [SCALE]
+    python tools/bench_aux.py [WORKLOAD] [SCALE] [validation]      (validation: that leg alone)
 """
 import sys
 import time
@@ -13,10 +13,64 @@ import numpy as np
 sys.path.insert(0, __file__.rsplit("/", 2)[0])
 import mfsgd_amd as mf  # noqa: E402
 
+
+def _median_ms(f, reps=5):
+    f()  # warm-up
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        f()
+        t.append(time.perf_counter() - t0)
+    return float(np.median(t)) * 1e3
+
+
+def validation_leg(m, w, n_held=2_000_000, epochs=10):
+    """Held-out RMSE of n_held pairs drawn from the workload's id ranges, on a model that has trained: (a) the set kept
+    on the device against predict() of the same pairs plus numpy; (b) early stopping that never stops against fit() of
+    as many epochs.  Medians of 5 after a warm-up.  (c), the kernels alone, is the kernel trace of this run:
+    pairs_sse_kernel against predict_kernel, which gathers the same rows of the same pairs."""
+    rng = np.random.default_rng(17)
+    hu = rng.integers(0, w["U"], n_held).astype(np.int32)
+    hi = rng.integers(0, w["I"], n_held).astype(np.int32)
+    hr = (rng.integers(1, 11, n_held) * 0.5).astype(np.float32)
+    m.set_validation(hu, hi, hr)
+    got = m.validation_rmse()
+
+    def by_predict():
+        e = hr - m.predict(hu, hi)
+        return float(np.sqrt(np.mean(e.astype(np.float64) ** 2)))
+
+    want = by_predict()
+    t_val = _median_ms(m.validation_rmse)
+    t_on = _median_ms(lambda: m.rmse_on(hu, hi, hr))
+    t_pred = _median_ms(by_predict)
+    t_fit = _median_ms(lambda: m.fit(epochs, rmse=False))
+    t_es = _median_ms(lambda: m.fit_early_stopping(epochs, patience=epochs + 1))
+    t_es_plain = _median_ms(lambda: m.fit_early_stopping(epochs, patience=epochs + 1, restore_best=False))
+    print(f"  validation, {n_held} held-out pairs: rmse {got:.6f} (predict + numpy: {want:.6f})")
+    print(f"    (a) validation_rmse(), set on the device  {t_val:9.3f} ms  = {n_held / t_val / 1e6:.2f} G pairs/s")
+    print(f"        rmse_on(u, i, r), pairs from the host  {t_on:9.3f} ms")
+    print(f"        predict(u, i) + numpy RMSE             {t_pred:9.3f} ms  = {t_pred / t_val:.1f} x validation_rmse()")
+    print(f"    (b) fit({epochs})                                {t_fit:9.3f} ms  = {t_fit / epochs:.3f} ms per epoch")
+    print(f"        fit_early_stopping({epochs}), never stops     {t_es:9.3f} ms  = +{(t_es - t_fit) / epochs:.3f} ms per epoch "
+          f"(+{(t_es - t_fit) / t_fit * 100:.1f} % of the epoch)")
+    print(f"        ... with restore_best=False            {t_es_plain:9.3f} ms  = +{(t_es_plain - t_fit) / epochs:.3f} ms per epoch "
+          f"(+{(t_es_plain - t_fit) / t_fit * 100:.1f} %)")
+    m.set_validation([], [], [])
+
+
 name = sys.argv[1] if len(sys.argv) > 1 else "cfg2_ml20m"
 scale = float(sys.argv[2]) if len(sys.argv) > 2 else 1.0
 w = mf.synth.workload(name, scale)
 k = w["k"]
+if len(sys.argv) > 3 and sys.argv[3] == "validation":
+    with mf.MatrixFactorizationSGD(w["U"], w["I"], k, 0.01, 0.05, 3, host_threads=16) as m:
+        m.set_ratings(w["u"], w["i"], w["r"])
+        m.init_factors()
+        m.fit(1, rmse=False)
+        print(f"{name} x{scale}: {w['nnz']} ratings, {w['U']} x {w['I']}, k = {k}")
+        validation_leg(m, w)
+    sys.exit(0)
 with mf.MatrixFactorizationSGD(w["U"], w["I"], k, 0.01, 0.05, 3, host_threads=16) as m:
     t0 = time.perf_counter()
     m.set_ratings(w["u"], w["i"], w["r"])
@@ -58,6 +112,8 @@ with mf.MatrixFactorizationSGD(w["U"], w["I"], k, 0.01, 0.05, 3, host_threads=16
     t0 = time.perf_counter()
     items_r, scores_r = m.recommend_rows(rows, 10, exclude=(f_rows, f_items))
     t_rec_r = time.perf_counter() - t0
+    print(f"{name} x{scale}: validation leg (the model has trained one epoch)")
+    validation_leg(m, w)
 kept = int(np.isin(w["u"], users).sum())
 print(f"{name} x{scale}: {n} ratings, {w['U']} x {w['I']}, k = {k}")
 print(f"  set_ratings (schedule build + ingest)  {t_set * 1e3:9.1f} ms")
