@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver; + mfsgd_set_validation, mfsgd_validation_size, mfsgd_validation_rmse, mfsgd_rmse_pairs, mfsgd_train_early_stop (additions: no existing call changed) */
+#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver; + mfsgd_set_validation, mfsgd_validation_size, mfsgd_validation_rmse, mfsgd_rmse_pairs, mfsgd_train_early_stop; + mfsgd_row_inv_norms, mfsgd_similar_items, mfsgd_similar_users, mfsgd_similar_rows (additions: no existing call changed) */
 
 typedef enum mfsgd_status {
     MFSGD_OK = 0,
@@ -229,6 +229,45 @@ int mfsgd_ranking_metrics_from_ranks(const int32_t* users, const int32_t* ranks,
 int mfsgd_evaluate_ranking(mfsgd_handle* h, const int32_t* users, const int32_t* items, int64_t n, int32_t topn,
                            const int32_t* excl_u, const int32_t* excl_i, int64_t n_excl,
                            mfsgd_ranking_metrics* out, int32_t* out_rank);
+
+/* ---- similar items and users: cosine nearest neighbours among the rows of Q, or of P --------------------------------
+ * The arithmetic, all fp32, round to nearest even, subnormals kept, nothing contracted; dot is
+ * the canonical dot, the bits mfsgd_predict() returns:
+ *     n2(x)     = dot(x, x)
+ *     rn(x)     = n2(x) > 0 ? 1.0f / sqrtf(n2(x)) : 0.0f      (sqrt and division each correctly rounded)
+ *     cos(a, b) = (dot(a, b) * rn(a)) * rn(b)                 (a the query row, b the candidate: two roundings, in this order)
+ * What follows from it: the score is not clamped -- cos(a, a) can be 1.0000001 or 0.99999994; cos(a, b) and cos(b, a)
+ * may differ in the last bit; a row whose n2 is 0 (all +-0.0) has rn = 0, so as a query all its scores are zeros and its
+ * neighbours are the smallest indices, and as a candidate it scores zero; a row scaled by a power of two has, barring
+ * under- or overflow, bit-identical scores to the unscaled row, so the two tie exactly.  Rows whose n2 is not finite,
+ * and any NaN, give unspecified ranks, as in mfsgd_rank_items.
+ * Order: recommend's.  j comes before t when score(j) > score(t), or when the two compare equal as floats (-0.0 equals
+ * +0.0) and j < t.  Outputs are n x topn, row-major, best first; the scores are the bits of cos above.
+ * mfsgd_similar_items / _users never return the query's own index in its row: exclusion is by index, not by score, so a
+ * duplicate row elsewhere stays eligible.  mfsgd_similar_rows excludes nothing.  A row with fewer than topn eligible
+ * candidates is padded with index -1 and score NaN, as in mfsgd_recommend_excluding (that only happens when topn equals
+ * the side's size).  A query asked for twice gets the same row twice; queries may come in any order.
+ * Arguments are checked before any device work (MFSGD_ERR_INVALID_ARG, message "similar_items: ...", "similar_users:
+ * ...", "similar_rows: ..." or "row_inv_norms: ..."): negative n or n_rows, topn < 1 or above the side's size, a null
+ * array that is needed, an index out of range, a side other than MFSGD_SIDE_USERS / MFSGD_SIDE_ITEMS.
+ * MFSGD_ERR_STATE: n_parts != 1, or factors never initialised, set or loaded.  MFSGD_ERR_NO_DEVICE: a valid call with
+ * work to do and no usable GPU; there is never a CPU result.  n == 0 (n_rows == 0) is MFSGD_OK and touches nothing.
+ * The model is not modified, everything allocated on the device is freed before return, and nothing is cached in the
+ * handle between calls: the inverse norms are computed per call (one pass over the side, about what scoring one query
+ * costs).  Selection is mfsgd_recommend's, kernels and all (csrc/recommend.hip); csrc/similar.hip adds the norms.   */
+#define MFSGD_SIDE_USERS 0
+#define MFSGD_SIDE_ITEMS 1
+/* rn() of every row of P (side 0: n_users floats) or Q (side 1: n_items floats). */
+int mfsgd_row_inv_norms(mfsgd_handle* h, int32_t side, float* out);
+/* For each of the n query items the topn other items with the largest cos(Q[items[b]], Q[j]), best first. */
+int mfsgd_similar_items(mfsgd_handle* h, const int32_t* items, int32_t n, int32_t topn,
+                        int32_t* out_items, float* out_scores);
+/* The same among users: P against P. */
+int mfsgd_similar_users(mfsgd_handle* h, const int32_t* users, int32_t n, int32_t topn,
+                        int32_t* out_users, float* out_scores);
+/* Query vectors of the caller's (n_rows x k, dense: a folded-in user, a cold item's vector) against one side. */
+int mfsgd_similar_rows(mfsgd_handle* h, int32_t side, const float* rows, int32_t n_rows, int32_t topn,
+                       int32_t* out_index, float* out_scores);
 
 /* ---- lr and lambda on a live model; learning-rate schedules --------------------------------------------------------
  * mfsgd_set_hyper gives the handle another lr and lambda without rebuilding anything: the two numbers sit in the

@@ -108,6 +108,39 @@ class MatrixFactorizationSGD {
         return {std::move(items), std::move(scores)};
     }
 
+    // int[][] similarItems(int[] items, int topN) / similarUsers(int[] users, int topN): per query the topN other rows of
+    // Q / of P with the largest cosine, best first, never the query itself (row-major queries x topN, with the scores)
+    std::pair<std::vector<int32_t>, std::vector<float>> similarItems(const std::vector<int32_t>& items, int topn) {
+        std::vector<int32_t> index(items.size() * (size_t)topn);
+        std::vector<float> scores(items.size() * (size_t)topn);
+        check(mfsgd_similar_items(h_, items.data(), (int32_t)items.size(), topn, index.data(), scores.data()));
+        return {std::move(index), std::move(scores)};
+    }
+    std::pair<std::vector<int32_t>, std::vector<float>> similarUsers(const std::vector<int32_t>& users, int topn) {
+        std::vector<int32_t> index(users.size() * (size_t)topn);
+        std::vector<float> scores(users.size() * (size_t)topn);
+        check(mfsgd_similar_users(h_, users.data(), (int32_t)users.size(), topn, index.data(), scores.data()));
+        return {std::move(index), std::move(scores)};
+    }
+    // int[][] similarRows(float[] rows, int topN, int side): the same for query vectors (n x k) that are not in the model,
+    // against the rows of Q (MFSGD_SIDE_ITEMS) or P (MFSGD_SIDE_USERS); nothing is excluded
+    std::pair<std::vector<int32_t>, std::vector<float>> similarRows(const std::vector<float>& rows, int topn,
+                                                                    int side = MFSGD_SIDE_ITEMS) {
+        if (rows.size() % (size_t)k_ != 0) throw std::invalid_argument("length mismatch");
+        const size_t n = rows.size() / (size_t)k_;
+        std::vector<int32_t> index(n * (size_t)topn);
+        std::vector<float> scores(n * (size_t)topn);
+        check(mfsgd_similar_rows(h_, side, rows.data(), (int32_t)n, topn, index.data(), scores.data()));
+        return {std::move(index), std::move(scores)};
+    }
+    // float[] rowInvNorms(int side): 1 / sqrt(dot(row, row)) of every row of P or Q, 0 for a zero row
+    std::vector<float> rowInvNorms(int side) {
+        if (side != MFSGD_SIDE_USERS && side != MFSGD_SIDE_ITEMS) throw std::invalid_argument("side");
+        std::vector<float> out((size_t)(side == MFSGD_SIDE_ITEMS ? items_ : users_));
+        check(mfsgd_row_inv_norms(h_, side, out.data()));
+        return out;
+    }
+
     // int[] rankItems(int[] u, int[] i, int[] exclU, int[] exclI): per held-out pair the number of items that come before
     // it in its user's recommendation order (its index in recommend(u, items, exclU, exclI)'s row)
     std::vector<int32_t> rankItems(const std::vector<int32_t>& u, const std::vector<int32_t>& i,

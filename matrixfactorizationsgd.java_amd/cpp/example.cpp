@@ -22,6 +22,10 @@ int main() {
         const std::vector<double> rmse = mf.train(u, i, r, 5);
         for (size_t e = 0; e < rmse.size(); ++e) std::printf("epoch %zu rmse %.6f\n", e + 1, rmse[e]);
         std::printf("predict(3,4) = %.6f (rating %.1f)\n", mf.predict(3, 4), r[3 * I + 4]);
+        // the serving surface beside predict: recommend, recommendRows (after foldIn), rankItems / evaluateRanking, and the
+        // cosine neighbours similarItems / similarUsers / similarRows with rowInvNorms
+        const auto like4 = mf.similarItems({4}, 3);
+        std::printf("items like 4: %d (%.6f) %d %d\n", like4.first[0], like4.second[0], like4.first[1], like4.first[2]);
         // the distributed surface through the same host: ONE rank whose ring is an RCCL self-ring, two item partitions
         // (what rank g of an N-GPU job runs, with world = N and its own user range)
         MatrixFactorizationSGD dist(U, I, k, 0.01f, 0.05f, 42, /*device*/ 0, /*nParts*/ 2);

@@ -1,5 +1,5 @@
 // kernels.hpp -- host-callable launchers of every kernel unit: epoch.hip, cells.hip, kernels.hip, foldin.hip,
-// rehyper.hip, recommend.hip, rank.hip and validate.hip.
+// rehyper.hip, recommend.hip, rank.hip, similar.hip and validate.hip.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -77,16 +77,25 @@ struct RecommendExcl {
     const long long* off = nullptr;
     const int32_t* items = nullptr;
 };
+// What is scored: ra == nullptr, dot(P[u], Q[j]) (recommend); otherwise the cosine (dot * ra[u]) * rb[j] of DESIGN.md
+// section 3, ra / rb being the inverse norms of the rows of P / Q (similar.hip).  Selection, ties, exclusions and
+// padding are the same code for both.
+struct CosineScale {
+    const float* ra = nullptr;
+    const float* rb = nullptr;
+};
 // Fused score + select (one workgroup per user, nothing but the winners goes to memory) for
 // the (n_items, topn) recommend_is_fused() accepts ...
 bool recommend_is_fused(int32_t n_items, int32_t topn);
 hipError_t recommend_fused(int L, const float* P, const float* Q, const int32_t* d_users, int nb, int32_t n_items,
-                           int32_t topn, const RecommendExcl& ex, float* out_s, int32_t* out_i, hipStream_t st);
+                           int32_t topn, const RecommendExcl& ex, const CosineScale& cs, float* out_s, int32_t* out_i,
+                           hipStream_t st);
 // ... and for the rest: scores of nb users against every item, top `topn` of each into out_s / out_i.  `temp` is the
 // sorts' scratch: the caller's, so that one serves all batches; grown here when it is too small.
 hipError_t recommend_batch(int L, const float* P, const float* Q, const int32_t* d_users, int nb, int32_t n_items,
-                           int32_t topn, const RecommendExcl& ex, float* s_in, float* s_out, int32_t* id_in, int32_t* id_out,
-                           long long* d_off, DevBuf& temp, float* out_s, int32_t* out_i, hipStream_t st);
+                           int32_t topn, const RecommendExcl& ex, const CosineScale& cs, float* s_in, float* s_out,
+                           int32_t* id_in, int32_t* id_out, long long* d_off, DevBuf& temp, float* out_s, int32_t* out_i,
+                           hipStream_t st);
 // Building the lists: each chunk of pairs appends slot << 32 | item to keys[*count ...] for the pairs of requested users
 // (count starts at 0; at most cap are written) ...
 hipError_t recommend_excl_filter(const int32_t* slot_of_user, const int32_t* u, const int32_t* i, int64_t n,
@@ -104,6 +113,10 @@ hipError_t recommend_excl_lists(unsigned long long* keys, unsigned long long* ke
 hipError_t launch_rank_items(int L, const float* P, const float* Q, const int32_t* rows, int n_slots, const long long* off,
                              long long base, const int32_t* items, int32_t n_items, const RecommendExcl& ex,
                              int32_t* out, hipStream_t st);
+
+// similar.hip.  out[x] = rn(row x) = 1 / sqrt(dot(row, row)), or 0 where that dot is 0, for the
+// n_rows kp-padded rows of M.  Asynchronous on st.
+hipError_t launch_row_inv_norms(int L, const float* M, int64_t n_rows, float* out, hipStream_t st);
 
 // validate.hip.  Sum over the n >= 1 pairs of (double)e * (double)e with e = r[j] - dot(P[u[j]], Q[i[j]]) in fp32 (the
 // bits launch_predict returns), into *out.  Pair j is added to partial j mod kPairsSlots, each partial in ascending j,

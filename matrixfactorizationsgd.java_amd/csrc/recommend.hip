@@ -10,6 +10,8 @@
 // Exclusions (mfsgd_recommend_excluding): one sorted, distinct item list per requested user, built here from
 // the caller's (user, item) pairs; both paths have a variant that gives excluded items a key below every
 // eligible one (0: eligible keys are clamped to >= 1) and pads a row that runs out of eligible items.
+// What is scored is a compile-time policy of the kernels: the dot (recommend), or the cosine built on it with the rows'
+// inverse norms (the similar calls, similar.hip) -- selection, ties, exclusions and padding exist once for both.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
@@ -38,11 +40,28 @@ __device__ __forceinline__ unsigned order_key(float f) {
 // with exclusions: 0 is the key of an excluded item, so eligible keys start at 1 (only the all-ones NaN moves)
 __device__ __forceinline__ unsigned eligible_key(float f) { return max(order_key(f), 1u); }
 
-// scores[b * n_items + i] = dot(P[users[b]], Q[i]) (KEYS: eligible_key of it, as unsigned); ids[...] = i.
+// How a kernel below turns dot(P[u], Q[j]) into the score of (u, j) -- a compile-time policy, so that selection, ties,
+// exclusions and the final rescoring exist once for both.  Plain: the dot itself (recommend).
+struct DotScore {
+    __device__ __forceinline__ float row(int) const { return 0.0f; }
+    __device__ __forceinline__ float col(int) const { return 0.0f; }
+    __device__ __forceinline__ float operator()(float d, float, float) const { return d; }
+};
+// Cosine (similar.hip): (dot * ra[u]) * rb[j], two roundings in this order, ra / rb the inverse
+// norms of the rows of P / Q.  col(j) is loaded beside Q[j], ahead of the reduction that needs it.
+struct CosScore {
+    const float* __restrict__ ra;
+    const float* __restrict__ rb;
+    __device__ __forceinline__ float row(int u) const { return ra[u]; }
+    __device__ __forceinline__ float col(int j) const { return rb[j]; }
+    __device__ __forceinline__ float operator()(float d, float a, float b) const { return (d * a) * b; }
+};
+
+// scores[b * n_items + i] = score of (users[b], i) (KEYS: eligible_key of it, as unsigned); ids[...] = i.
 // grid = (item blocks, users)
-template <int L, bool KEYS>
+template <int L, bool KEYS, class S>
 __global__ void __launch_bounds__(256) score_kernel(const float* __restrict__ P, const float* __restrict__ Q,
-                                                    const int32_t* __restrict__ users, const int32_t n_items,
+                                                    const int32_t* __restrict__ users, const int32_t n_items, const S sc,
                                                     float* __restrict__ scores, int32_t* __restrict__ ids) {
     constexpr int KP = 4 * L;
     constexpr int GPB = 256 / L;
@@ -50,13 +69,15 @@ __global__ void __launch_bounds__(256) score_kernel(const float* __restrict__ P,
     const int grp = threadIdx.x / L;
     const int b = blockIdx.y;
     const float4 p = *reinterpret_cast<const float4*>(P + (size_t)users[b] * KP + lig * 4);
+    const float ra = sc.row(users[b]);
     const int stride = (int)gridDim.x * GPB;
     const int iters = (n_items + stride - 1) / stride;  // uniform trip count: DPP needs every lane live
     for (int it = 0; it < iters; ++it) {
         const int i = (int)blockIdx.x * GPB + grp + it * stride;
         const bool ok = i < n_items;
         const float4 q = *reinterpret_cast<const float4*>(Q + (size_t)(ok ? i : 0) * KP + lig * 4);
-        const float d = group_allreduce<L>(chunk_dot(p, q));
+        const float rb = sc.col(ok ? i : 0);
+        const float d = sc(group_allreduce<L>(chunk_dot(p, q)), ra, rb);
         if (ok && lig == 0) {
             if constexpr (KEYS) reinterpret_cast<unsigned*>(scores)[(size_t)b * n_items + i] = eligible_key(d);
             else scores[(size_t)b * n_items + i] = d;
@@ -74,10 +95,10 @@ constexpr int kTopnThreads = 1024;  // 16 waves: the scores are a latency-bound 
 
 // EXCL: the items of the user's exclusion list get key 0 in each tile and are never candidates; a tile selects
 // min(topn, its eligible items), and a row with fewer than topn candidates in all is padded (-1, NaN).
-template <int L, bool EXCL>
+template <int L, bool EXCL, class S>
 __global__ void __launch_bounds__(kTopnThreads) topn_kernel(const float* __restrict__ P, const float* __restrict__ Q,
                                                             const int32_t* __restrict__ users, const int32_t n_items,
-                                                            const int32_t topn, const RecommendExcl ex,
+                                                            const int32_t topn, const RecommendExcl ex, const S sc,
                                                             float* __restrict__ out_s, int32_t* __restrict__ out_i) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NT = kTopnThreads, NW = NT / 64;
@@ -92,6 +113,7 @@ __global__ void __launch_bounds__(kTopnThreads) topn_kernel(const float* __restr
     const int lig = tid % L, grp = tid / L;
     const int b = blockIdx.x;
     const float4 p = *reinterpret_cast<const float4*>(P + (size_t)users[b] * KP + lig * 4);
+    const float ra = sc.row(users[b]);
     long long ex_at = 0, ex_end = 0;  // the user's exclusion list, consumed tile by tile
     int ex_seen = 0;                  // its items met so far: ctl[3] counts them and is never reset, so no read races a reset
     if constexpr (EXCL) {
@@ -114,8 +136,9 @@ __global__ void __launch_bounds__(kTopnThreads) topn_kernel(const float* __restr
             const bool ok1 = x1 < nt;
             const float4 q0 = *reinterpret_cast<const float4*>(Q + (size_t)(tile0 + x0) * KP + lig * 4);
             const float4 q1 = *reinterpret_cast<const float4*>(Q + (size_t)(ok1 ? tile0 + x1 : 0) * KP + lig * 4);
-            const float d0 = group_allreduce<L>(chunk_dot(p, q0));
-            const float d1 = group_allreduce<L>(chunk_dot(p, q1));
+            const float r0 = sc.col(tile0 + x0), r1 = sc.col(ok1 ? tile0 + x1 : 0);
+            const float d0 = sc(group_allreduce<L>(chunk_dot(p, q0)), ra, r0);
+            const float d1 = sc(group_allreduce<L>(chunk_dot(p, q1)), ra, r1);
             if (lig == 0) {
                 keys[x0] = EXCL ? eligible_key(d0) : order_key(d0);
                 if (ok1) keys[x1] = EXCL ? eligible_key(d1) : order_key(d1);
@@ -125,7 +148,8 @@ __global__ void __launch_bounds__(kTopnThreads) topn_kernel(const float* __restr
             const int x = grp + it * GPB;
             const bool ok = x < nt;
             const float4 q = *reinterpret_cast<const float4*>(Q + (size_t)(ok ? tile0 + x : 0) * KP + lig * 4);
-            const float d = group_allreduce<L>(chunk_dot(p, q));
+            const float r = sc.col(ok ? tile0 + x : 0);
+            const float d = sc(group_allreduce<L>(chunk_dot(p, q)), ra, r);
             if (ok && lig == 0) keys[x] = EXCL ? eligible_key(d) : order_key(d);
         }
         __syncthreads();
@@ -243,7 +267,7 @@ __global__ void __launch_bounds__(kTopnThreads) topn_kernel(const float* __restr
             }
             __syncthreads();
         }
-    // the winners; their scores recomputed with the canonical dot (the bits predict() returns).  Without
+    // the winners; their scores recomputed (plain: the canonical dot, the bits predict() returns).  Without
     // exclusions there are always at least topn candidates; with them, the places past the last are padded.
     const int iters = (topn + GPB - 1) / GPB;
     for (int it = 0; it < iters; ++it) {
@@ -252,7 +276,7 @@ __global__ void __launch_bounds__(kTopnThreads) topn_kernel(const float* __restr
         const bool won = !EXCL || x < nc;
         const int item = ok && won ? (int)(cand[x] & 0xFFFFFFFFull) : 0;
         const float4 q = *reinterpret_cast<const float4*>(Q + (size_t)item * KP + lig * 4);
-        const float d = group_allreduce<L>(chunk_dot(p, q));
+        const float d = sc(group_allreduce<L>(chunk_dot(p, q)), ra, sc.col(item));
         if (ok && lig == 0) {
             out_s[(size_t)b * topn + x] = won ? d : __builtin_nanf("");
             out_i[(size_t)b * topn + x] = won ? item : -1;
@@ -260,15 +284,15 @@ __global__ void __launch_bounds__(kTopnThreads) topn_kernel(const float* __restr
     }
 }
 
-template <int L, bool EXCL>
+template <int L, bool EXCL, class S>
 hipError_t topn_L(const float* P, const float* Q, const int32_t* users, int nb, int32_t n_items, int32_t topn,
-                  const RecommendExcl& ex, float* out_s, int32_t* out_i, hipStream_t st) {
+                  const RecommendExcl& ex, const S& sc, float* out_s, int32_t* out_i, hipStream_t st) {
     const size_t lds = (size_t)kTopnTile * 4 + (size_t)kTopnCand * 8 + 256 * 4 + (kTopnThreads / 64) * 4 + 16;
     hipError_t e =
-        hipFuncSetAttribute((const void*)topn_kernel<L, EXCL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipFuncSetAttribute((const void*)topn_kernel<L, EXCL, S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((topn_kernel<L, EXCL>), dim3((unsigned)nb), dim3(kTopnThreads), lds, st, P, Q, users, n_items, topn,
-                       ex, out_s, out_i);
+    hipLaunchKernelGGL((topn_kernel<L, EXCL, S>), dim3((unsigned)nb), dim3(kTopnThreads), lds, st, P, Q, users, n_items, topn,
+                       ex, sc, out_s, out_i);
     return hipGetLastError();
 }
 
@@ -282,19 +306,20 @@ __global__ void __launch_bounds__(256) take_top_kernel(const float* __restrict__
     }
 }
 
-// With exclusions the sorted keys are eligible_key()s, not scores: the first topn ids of each row are rescored with
-// the canonical dot, and an excluded one (key 0, sorted after every eligible item) ends the row's winners.
-template <int L>
+// With exclusions the sorted keys are eligible_key()s, not scores: the first topn ids of each row are rescored (plain:
+// the canonical dot), and an excluded one (key 0, sorted after every eligible item) ends the row's winners.
+template <int L, class S>
 __global__ void __launch_bounds__(256) take_top_excl_kernel(const float* __restrict__ P, const float* __restrict__ Q,
                                                             const int32_t* __restrict__ users,
                                                             const unsigned* __restrict__ key, const int32_t* __restrict__ id,
-                                                            const int32_t n_items, const int32_t topn,
+                                                            const int32_t n_items, const int32_t topn, const S sc,
                                                             float* __restrict__ out_s, int32_t* __restrict__ out_i) {
     constexpr int KP = 4 * L;
     constexpr int GPB = 256 / L;
     const int lig = threadIdx.x % L, grp = threadIdx.x / L;
     const int b = blockIdx.x;
     const float4 p = *reinterpret_cast<const float4*>(P + (size_t)users[b] * KP + lig * 4);
+    const float ra = sc.row(users[b]);
     const int iters = (topn + GPB - 1) / GPB;  // uniform trip count: DPP needs every lane live
     for (int it = 0; it < iters; ++it) {
         const int x = grp + it * GPB;
@@ -302,7 +327,7 @@ __global__ void __launch_bounds__(256) take_top_excl_kernel(const float* __restr
         const bool won = ok && key[(size_t)b * n_items + x] != 0u;
         const int item = won ? id[(size_t)b * n_items + x] : 0;
         const float4 q = *reinterpret_cast<const float4*>(Q + (size_t)item * KP + lig * 4);
-        const float d = group_allreduce<L>(chunk_dot(p, q));
+        const float d = sc(group_allreduce<L>(chunk_dot(p, q)), ra, sc.col(item));
         if (ok && lig == 0) {
             out_s[(size_t)b * topn + x] = won ? d : __builtin_nanf("");
             out_i[(size_t)b * topn + x] = won ? item : -1;
@@ -338,18 +363,18 @@ hipError_t sort_rows(K* k_in, K* k_out, int32_t* id_in, int32_t* id_out, long lo
     return e;
 }
 
-template <int L>
+template <int L, class S>
 hipError_t batch_L(const float* P, const float* Q, const int32_t* users, int nb, int32_t n_items, int32_t topn,
-                   const RecommendExcl& ex, float* s_in, float* s_out, int32_t* id_in, int32_t* id_out, long long* d_off,
+                   const RecommendExcl& ex, const S& sc, float* s_in, float* s_out, int32_t* id_in, int32_t* id_out, long long* d_off,
                    DevBuf& temp, float* out_s, int32_t* out_i, hipStream_t st) {
     const int gpb = 256 / L;
     int bx = (n_items + gpb - 1) / gpb;
     if (bx > 64) bx = 64;
     const dim3 sgrid((unsigned)bx, (unsigned)nb);
     if (ex.slot)
-        hipLaunchKernelGGL((score_kernel<L, true>), sgrid, dim3(256), 0, st, P, Q, users, n_items, s_in, id_in);
+        hipLaunchKernelGGL((score_kernel<L, true, S>), sgrid, dim3(256), 0, st, P, Q, users, n_items, sc, s_in, id_in);
     else
-        hipLaunchKernelGGL((score_kernel<L, false>), sgrid, dim3(256), 0, st, P, Q, users, n_items, s_in, id_in);
+        hipLaunchKernelGGL((score_kernel<L, false, S>), sgrid, dim3(256), 0, st, P, Q, users, n_items, sc, s_in, id_in);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (ex.slot) {
@@ -369,8 +394,8 @@ hipError_t batch_L(const float* P, const float* Q, const int32_t* users, int nb,
     unsigned* k_out = reinterpret_cast<unsigned*>(s_out);
     e = sort_rows(k_in, k_out, id_in, id_out, d_off, nb, n_items, temp, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((take_top_excl_kernel<L>), dim3((unsigned)nb), dim3(256), 0, st, P, Q, users, k_out, id_out, n_items,
-                       topn, out_s, out_i);
+    hipLaunchKernelGGL((take_top_excl_kernel<L, S>), dim3((unsigned)nb), dim3(256), 0, st, P, Q, users, k_out, id_out, n_items,
+                       topn, sc, out_s, out_i);
     return hipGetLastError();
 }
 
@@ -425,19 +450,30 @@ bool recommend_is_fused(int32_t n_items, int32_t topn) {
 
 // Fused score + select: no score buffers at all.
 hipError_t recommend_fused(int L, const float* P, const float* Q, const int32_t* d_users, int nb, int32_t n_items,
-                           int32_t topn, const RecommendExcl& ex, float* out_s, int32_t* out_i, hipStream_t st) {
+                           int32_t topn, const RecommendExcl& ex, const CosineScale& cs, float* out_s, int32_t* out_i,
+                           hipStream_t st) {
     return with_L(L, [&](auto l) {
-        return ex.slot ? topn_L<l(), true>(P, Q, d_users, nb, n_items, topn, ex, out_s, out_i, st)
-                       : topn_L<l(), false>(P, Q, d_users, nb, n_items, topn, ex, out_s, out_i, st);
+        constexpr int LL = l();
+        auto go = [&](const auto& sc) {
+            return ex.slot ? topn_L<LL, true>(P, Q, d_users, nb, n_items, topn, ex, sc, out_s, out_i, st)
+                           : topn_L<LL, false>(P, Q, d_users, nb, n_items, topn, ex, sc, out_s, out_i, st);
+        };
+        return cs.ra ? go(CosScore{cs.ra, cs.rb}) : go(DotScore{});
     });
 }
 
 // Device buffers are the caller's (serve.cpp): scores/ids in and out (nb * n_items each), offsets nb+1.
 hipError_t recommend_batch(int L, const float* P, const float* Q, const int32_t* d_users, int nb, int32_t n_items,
-                           int32_t topn, const RecommendExcl& ex, float* s_in, float* s_out, int32_t* id_in, int32_t* id_out,
-                           long long* d_off, DevBuf& temp, float* out_s, int32_t* out_i, hipStream_t st) {
+                           int32_t topn, const RecommendExcl& ex, const CosineScale& cs, float* s_in, float* s_out,
+                           int32_t* id_in, int32_t* id_out, long long* d_off, DevBuf& temp, float* out_s, int32_t* out_i,
+                           hipStream_t st) {
     return with_L(L, [&](auto l) {
-        return batch_L<l()>(P, Q, d_users, nb, n_items, topn, ex, s_in, s_out, id_in, id_out, d_off, temp, out_s, out_i, st);
+        constexpr int LL = l();
+        auto go = [&](const auto& sc) {
+            return batch_L<LL>(P, Q, d_users, nb, n_items, topn, ex, sc, s_in, s_out, id_in, id_out, d_off, temp, out_s, out_i,
+                                st);
+        };
+        return cs.ra ? go(CosScore{cs.ra, cs.rb}) : go(DotScore{});
     });
 }
 

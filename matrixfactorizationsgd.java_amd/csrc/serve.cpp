@@ -1,5 +1,6 @@
-// serve.cpp -- what a trained model answers: predictions, top-N recommendations, ranks of held-out items and their
-// metrics, and the fold-in of new users.  Every call batches its work through bounded staging buffers.
+// serve.cpp -- what a trained model answers: predictions, top-N recommendations, cosine neighbours of items and users,
+// ranks of held-out items and their metrics, and the fold-in of new users.  Every call batches its work through bounded
+// staging buffers.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -83,6 +84,49 @@ static int exclusions_to_device(mfsgd_handle* h, const ServeName& what, const st
     return MFSGD_OK;
 }
 
+// The device half of a top-N call, shared by recommend_core and similar_core: for each of the n rows users[...] of P the
+// topn rows of Q (n_items of them) with the largest score (cs: the dot, or the cosine), exclusions as `ex` has them.
+// Fused where recommend_is_fused() holds; otherwise in batches of users through the sort path.  `temp` is the sorts'
+// scratch, the caller's (the exclusion lists may have grown it already).  `prefix` starts the message of a HIP failure.
+static int topn_batches(mfsgd_handle* h, const char* prefix, const float* P, const float* Q, int32_t I, const int32_t* users,
+                        int32_t n_users, int32_t topn, const RecommendExcl& ex, const CosineScale& cs, DevBuf& temp,
+                        int32_t* out_items, float* out_scores) {
+    const bool fused = recommend_is_fused(I, topn);  // score + select in one kernel, no score buffers
+    // users per batch: about 64 M scores at a time (the sort path materialises them)
+    int batch = (int)std::max<int64_t>(1, std::min<int64_t>(n_users, ((int64_t)64 << 20) / std::max(1, I)));
+    if (fused) batch = n_users;
+    batch = std::min(batch, 65535);
+    auto bad = [h, prefix](hipError_t e) { return serve_fail(h, prefix, e); };
+    DevBuf d_users, s_in, s_out, id_in, id_out, d_off, o_s, o_i;
+    int rc;
+    const size_t cells = (size_t)batch * (size_t)I;
+    if ((rc = dev_alloc(h, d_users, sizeof(int32_t) * (size_t)batch))) return rc;
+    if (!fused) {
+        if ((rc = dev_alloc(h, s_in, 4 * cells))) return rc;
+        if ((rc = dev_alloc(h, s_out, 4 * cells))) return rc;
+        if ((rc = dev_alloc(h, id_in, 4 * cells))) return rc;
+        if ((rc = dev_alloc(h, id_out, 4 * cells))) return rc;
+        if ((rc = dev_alloc(h, d_off, sizeof(long long) * ((size_t)batch + 1)))) return rc;
+    }
+    if ((rc = dev_alloc(h, o_s, 4 * (size_t)batch * topn))) return rc;
+    if ((rc = dev_alloc(h, o_i, 4 * (size_t)batch * topn))) return rc;
+    for (int32_t done = 0; done < n_users; done += batch) {
+        const int nb = std::min<int32_t>(batch, n_users - done);
+        const int32_t* du = d_users.as<const int32_t>();
+        HIPCHK_OR(bad, hipMemcpyAsync(d_users.get(), users + done, sizeof(int32_t) * (size_t)nb, hipMemcpyHostToDevice, h->stream));
+        if (fused)
+            HIPCHK_OR(bad, recommend_fused(h->geo.L, P, Q, du, nb, I, topn, ex, cs, o_s.as<float>(), o_i.as<int32_t>(), h->stream));
+        else
+            HIPCHK_OR(bad, recommend_batch(h->geo.L, P, Q, du, nb, I, topn, ex, cs, s_in.as<float>(), s_out.as<float>(),
+                                           id_in.as<int32_t>(), id_out.as<int32_t>(), d_off.as<long long>(), temp,
+                                           o_s.as<float>(), o_i.as<int32_t>(), h->stream));
+        HIPCHK_OR(bad, hipMemcpyAsync(out_scores + (size_t)done * topn, o_s.get(), 4 * (size_t)nb * topn, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK_OR(bad, hipMemcpyAsync(out_items + (size_t)done * topn, o_i.get(), 4 * (size_t)nb * topn, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
+    }
+    return MFSGD_OK;
+}
+
 // Body of the recommend calls: "user j" is row j of a matrix of n_rows rows, and `users` names the rows asked for.
 // host_rows == nullptr: the matrix is the model's P.  Otherwise it is host_rows (n_rows x k, dense).
 static int recommend_core(mfsgd_handle* h, const float* host_rows, int32_t n_rows, const int32_t* users, int32_t n_users,
@@ -111,48 +155,78 @@ static int recommend_core(mfsgd_handle* h, const float* host_rows, int32_t n_row
     if (host_rows && h->where == mfsgd_handle::Where::None)  // (asked here: factors_to_device wants a device first)
         return fail(h, MFSGD_ERR_STATE, "recommend_rows: factors not initialised");
     if ((rc = factors_to_device(h))) return rc;
-    const int32_t I = h->cfg.n_items;
-    const bool fused = recommend_is_fused(I, topn);  // score + select in one kernel, no score buffers
-    // users per batch: about 64 M scores at a time (the sort path materialises them)
-    int batch = (int)std::max<int64_t>(1, std::min<int64_t>(n_users, ((int64_t)64 << 20) / std::max(1, I)));
-    if (fused) batch = n_users;
-    batch = std::min(batch, 65535);
-    auto bad = [h](hipError_t e) { return serve_fail(h, "recommend: ", e); };
-    DevBuf d_rows, d_users, s_in, s_out, id_in, id_out, d_off, o_s, o_i, ex_slot, ex_off, ex_items;
+    DevBuf d_rows, ex_slot, ex_off, ex_items;
     DevBuf temp;  // of the sorts: one for the exclusion lists and every batch, grown when one needs more
     const float* P;
     if ((rc = upload_rows(h, host_rows, n_rows, d_rows, &P))) return rc;
-    const float* Q = h->dQ.as<const float>();
     RecommendExcl ex;  // built once for all batches; none when no pair belongs to a requested user
     if (kept > 0 && (rc = exclusions_to_device(h, kRecommend, slot_of_user, n_slots, excl_u, excl_i, n_excl, kept, ex_slot,
                                                ex_off, ex_items, temp, ex)))
         return rc;
-    const size_t cells = (size_t)batch * (size_t)I;
-    if ((rc = dev_alloc(h, d_users, sizeof(int32_t) * (size_t)batch))) return rc;
-    if (!fused) {
-        if ((rc = dev_alloc(h, s_in, 4 * cells))) return rc;
-        if ((rc = dev_alloc(h, s_out, 4 * cells))) return rc;
-        if ((rc = dev_alloc(h, id_in, 4 * cells))) return rc;
-        if ((rc = dev_alloc(h, id_out, 4 * cells))) return rc;
-        if ((rc = dev_alloc(h, d_off, sizeof(long long) * ((size_t)batch + 1)))) return rc;
+    return topn_batches(h, "recommend: ", P, h->dQ.as<const float>(), h->cfg.n_items, users, n_users, topn, ex, CosineScale{},
+                        temp, out_items, out_scores);
+}
+
+// Body of the similar calls: the neighbours of n query rows among the rows of one side's matrix M (Q for
+// MFSGD_SIDE_ITEMS, P for MFSGD_SIDE_USERS) under the cosine of DESIGN.md section 3.  host_rows == nullptr: the queries
+// are the rows queries[...] of M itself, and with self_excl each leaves out its own index: a one-item exclusion list per
+// distinct query, so the EXCL variants of recommend.hip do it.  Otherwise the queries are host_rows (n_rows x k, dense),
+// uploaded for the length of the call, queries[...] index them, and nothing is excluded.  The inverse norms are
+// computed here, per call; nothing stays in the handle.  `name` is the call's, without the colon.
+static int similar_core(mfsgd_handle* h, const char* name, int32_t side, const float* host_rows, int32_t n_rows,
+                        const int32_t* queries, int32_t n, int32_t topn, bool self_excl, int32_t* out_index,
+                        float* out_scores) {
+    const std::string call = std::string(name) + ": ";
+    if (n < 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "n is negative");
+    if (topn < 1) return fail(h, MFSGD_ERR_INVALID_ARG, call + "topn is below 1");
+    if (n > 0 && (!queries || !out_index || !out_scores))
+        return fail(h, MFSGD_ERR_INVALID_ARG, call + "the queries or an output array is null");
+    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, call + "single-partition handles only");
+    const int32_t size = side == MFSGD_SIDE_ITEMS ? h->cfg.n_items : h->cfg.n_users;
+    if (topn > size)
+        return fail(h, MFSGD_ERR_INVALID_ARG,
+                    call + "topn exceeds the number of " + (side == MFSGD_SIDE_ITEMS ? "items" : "users"));
+    for (int32_t j = 0; j < n; ++j)
+        if (queries[j] < 0 || queries[j] >= n_rows)
+            return fail(h, MFSGD_ERR_INVALID_ARG, call + "query " + std::to_string(j) + " out of range");
+    if (n == 0) return MFSGD_OK;
+    if (h->where == mfsgd_handle::Where::None)  // (asked here: factors_to_device wants a device first)
+        return fail(h, MFSGD_ERR_STATE, call + "factors not initialised");
+    int rc;
+    if ((rc = factors_to_device(h))) return rc;
+    auto bad = [h, &call](hipError_t e) { return serve_fail(h, call.c_str(), e); };
+    DevBuf d_rows, d_ra, d_rb, ex_slot, ex_off, ex_items, temp;
+    const float* M = side == MFSGD_SIDE_ITEMS ? h->dQ.as<const float>() : h->dP.as<const float>();
+    const float* A = M;
+    if (host_rows && (rc = upload_rows(h, host_rows, n_rows, d_rows, &A))) return rc;
+    CosineScale cs;
+    if ((rc = dev_alloc(h, d_rb, sizeof(float) * (size_t)size))) return rc;
+    HIPCHK_OR(bad, launch_row_inv_norms(h->geo.L, M, size, d_rb.as<float>(), h->stream));
+    cs.ra = cs.rb = d_rb.as<const float>();
+    if (host_rows) {
+        if ((rc = dev_alloc(h, d_ra, sizeof(float) * (size_t)n_rows))) return rc;
+        HIPCHK_OR(bad, launch_row_inv_norms(h->geo.L, A, n_rows, d_ra.as<float>(), h->stream));
+        cs.ra = d_ra.as<const float>();
     }
-    if ((rc = dev_alloc(h, o_s, 4 * (size_t)batch * topn))) return rc;
-    if ((rc = dev_alloc(h, o_i, 4 * (size_t)batch * topn))) return rc;
-    for (int32_t done = 0; done < n_users; done += batch) {
-        const int nb = std::min<int32_t>(batch, n_users - done);
-        const int32_t* du = d_users.as<const int32_t>();
-        HIPCHK_OR(bad, hipMemcpyAsync(d_users.get(), users + done, sizeof(int32_t) * (size_t)nb, hipMemcpyHostToDevice, h->stream));
-        if (fused)
-            HIPCHK_OR(bad, recommend_fused(h->geo.L, P, Q, du, nb, I, topn, ex, o_s.as<float>(), o_i.as<int32_t>(), h->stream));
-        else
-            HIPCHK_OR(bad, recommend_batch(h->geo.L, P, Q, du, nb, I, topn, ex, s_in.as<float>(), s_out.as<float>(),
-                                           id_in.as<int32_t>(), id_out.as<int32_t>(), d_off.as<long long>(), temp,
-                                           o_s.as<float>(), o_i.as<int32_t>(), h->stream));
-        HIPCHK_OR(bad, hipMemcpyAsync(out_scores + (size_t)done * topn, o_s.get(), 4 * (size_t)nb * topn, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK_OR(bad, hipMemcpyAsync(out_items + (size_t)done * topn, o_i.get(), 4 * (size_t)nb * topn, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
+    RecommendExcl ex;
+    if (self_excl) {
+        // a slot per distinct query (one asked for twice shares it); the list of slot s is the query itself
+        std::vector<int32_t> slot_of_row((size_t)n_rows, -1), self;
+        for (int32_t j = 0; j < n; ++j)
+            if (slot_of_row[(size_t)queries[j]] < 0) {
+                slot_of_row[(size_t)queries[j]] = (int32_t)self.size();
+                self.push_back(queries[j]);
+            }
+        std::vector<long long> off(self.size() + 1);
+        for (size_t x = 0; x < off.size(); ++x) off[x] = (long long)x;
+        if ((rc = upload(h, ex_slot, slot_of_row))) return rc;
+        if ((rc = upload(h, ex_off, off))) return rc;
+        if ((rc = upload(h, ex_items, self))) return rc;
+        ex.slot = ex_slot.as<const int32_t>();
+        ex.off = ex_off.as<const long long>();
+        ex.items = ex_items.as<const int32_t>();
     }
-    return MFSGD_OK;
+    return topn_batches(h, call.c_str(), A, M, size, queries, n, topn, ex, cs, temp, out_index, out_scores);
 }
 
 // Pairs of one rank launch (whole users; a single user with more is a launch of its own): 16 MB of items up, as much
@@ -324,6 +398,57 @@ int mfsgd_recommend_rows(mfsgd_handle* h, const float* rows, int32_t n_rows, int
         for (int32_t j = 0; j < n_rows; ++j) all[(size_t)j] = j;
         return recommend_core(h, rows, n_rows, all.data(), n_rows, topn, excl_row, excl_item, n_excl, out_items,
                               out_scores);
+    });
+}
+
+int mfsgd_row_inv_norms(mfsgd_handle* h, int32_t side, float* out) {
+    return guarded(h, "row_inv_norms", [&]() -> int {
+        if (side != MFSGD_SIDE_USERS && side != MFSGD_SIDE_ITEMS)
+            return fail(h, MFSGD_ERR_INVALID_ARG, "row_inv_norms: side is neither MFSGD_SIDE_USERS nor MFSGD_SIDE_ITEMS");
+        if (!out) return fail(h, MFSGD_ERR_INVALID_ARG, "row_inv_norms: out is null");
+        if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "row_inv_norms: single-partition handles only");
+        if (h->where == mfsgd_handle::Where::None)  // (asked here: factors_to_device wants a device first)
+            return fail(h, MFSGD_ERR_STATE, "row_inv_norms: factors not initialised");
+        int rc = factors_to_device(h);
+        if (rc) return rc;
+        const int32_t size = side == MFSGD_SIDE_ITEMS ? h->cfg.n_items : h->cfg.n_users;
+        const float* M = side == MFSGD_SIDE_ITEMS ? h->dQ.as<const float>() : h->dP.as<const float>();
+        auto bad = [h](hipError_t e) { return serve_fail(h, "row_inv_norms: ", e); };
+        DevBuf d_rn;
+        if ((rc = dev_alloc(h, d_rn, sizeof(float) * (size_t)size))) return rc;
+        HIPCHK_OR(bad, launch_row_inv_norms(h->geo.L, M, size, d_rn.as<float>(), h->stream));
+        HIPCHK_OR(bad, hipMemcpyAsync(out, d_rn.get(), sizeof(float) * (size_t)size, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
+        return MFSGD_OK;
+    });
+}
+
+int mfsgd_similar_items(mfsgd_handle* h, const int32_t* items, int32_t n, int32_t topn, int32_t* out_items,
+                        float* out_scores) {
+    return guarded(h, "similar_items", [&]() -> int {
+        return similar_core(h, "similar_items", MFSGD_SIDE_ITEMS, nullptr, h->cfg.n_items, items, n, topn, true, out_items,
+                            out_scores);
+    });
+}
+
+int mfsgd_similar_users(mfsgd_handle* h, const int32_t* users, int32_t n, int32_t topn, int32_t* out_users,
+                        float* out_scores) {
+    return guarded(h, "similar_users", [&]() -> int {
+        return similar_core(h, "similar_users", MFSGD_SIDE_USERS, nullptr, h->cfg.n_users, users, n, topn, true, out_users,
+                            out_scores);
+    });
+}
+
+int mfsgd_similar_rows(mfsgd_handle* h, int32_t side, const float* rows, int32_t n_rows, int32_t topn, int32_t* out_index,
+                       float* out_scores) {
+    return guarded(h, "similar_rows", [&]() -> int {
+        if (side != MFSGD_SIDE_USERS && side != MFSGD_SIDE_ITEMS)
+            return fail(h, MFSGD_ERR_INVALID_ARG, "similar_rows: side is neither MFSGD_SIDE_USERS nor MFSGD_SIDE_ITEMS");
+        if (n_rows < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "similar_rows: n_rows is negative");
+        if (n_rows > 0 && !rows) return fail(h, MFSGD_ERR_INVALID_ARG, "similar_rows: rows is null");
+        std::vector<int32_t> all((size_t)n_rows);
+        for (int32_t j = 0; j < n_rows; ++j) all[(size_t)j] = j;
+        return similar_core(h, "similar_rows", side, rows, n_rows, all.data(), n_rows, topn, false, out_index, out_scores);
     });
 }
 

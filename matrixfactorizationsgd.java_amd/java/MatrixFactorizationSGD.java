@@ -126,6 +126,52 @@ public final class MatrixFactorizationSGD implements AutoCloseable {
         return out;
     }
 
+    /** The two sides of the model for similarRows and rowInvNorms: rows of P, rows of Q. */
+    public static final int SIDE_USERS = 0, SIDE_ITEMS = 1;
+
+    private static int[][] rowsOf(int[] flat, int n, int topN) {
+        int[][] out = new int[n][];
+        for (int a = 0; a < n; a++) out[a] = java.util.Arrays.copyOfRange(flat, a * topN, (a + 1) * topN);
+        return out;
+    }
+
+    /**
+     * For each query item the topN other items whose rows of Q have the largest cosine with its row, best first (ties:
+     * smaller index).  The query itself is never returned; with topN == items the last place of each row is -1.
+     */
+    public int[][] similarItems(int[] items, int topN) {
+        int[] index = new int[items.length * topN];
+        nativeSimilar(handle, SIDE_ITEMS, items, topN, index, new float[items.length * topN]);
+        return rowsOf(index, items.length, topN);
+    }
+
+    /** similarItems among users: rows of P against P. */
+    public int[][] similarUsers(int[] users, int topN) {
+        int[] index = new int[users.length * topN];
+        nativeSimilar(handle, SIDE_USERS, users, topN, index, new float[users.length * topN]);
+        return rowsOf(index, users.length, topN);
+    }
+
+    /**
+     * The neighbours of query vectors of the caller's (n x k: a folded-in user, a cold item's vector) among the rows of
+     * Q (SIDE_ITEMS) or P (SIDE_USERS).  Nothing is excluded.
+     */
+    public int[][] similarRows(float[] rows, int topN, int side) {
+        if (rows.length % k != 0) throw new IllegalArgumentException("length mismatch");
+        int n = rows.length / k;
+        int[] index = new int[n * topN];
+        nativeSimilarRows(handle, side, rows, topN, index, new float[n * topN]);
+        return rowsOf(index, n, topN);
+    }
+
+    /** 1 / sqrt(dot(row, row)) of every row of P (SIDE_USERS) or Q (SIDE_ITEMS), 0 for a zero row. */
+    public float[] rowInvNorms(int side) {
+        if (side != SIDE_USERS && side != SIDE_ITEMS) throw new IllegalArgumentException("side");
+        float[] out = new float[side == SIDE_ITEMS ? items : users];
+        nativeRowInvNorms(handle, side, out);
+        return out;
+    }
+
     /**
      * For each held-out pair (u[x], i[x]) the number of items that come before i[x] in u[x]'s recommendation order
      * (0: it would be recommended first), the pairs (exclU[x], exclI[x]) not competing -- the index of i[x] in the row
@@ -402,6 +448,9 @@ public final class MatrixFactorizationSGD implements AutoCloseable {
                                                         float[] scores);
     private static native void nativeFoldIn(long h, long[] rowPtr, int[] items, float[] ratings, int epochs, float[] init,
                                             long seed, float[] rows);
+    private static native void nativeSimilar(long h, int side, int[] queries, int topN, int[] index, float[] scores);
+    private static native void nativeSimilarRows(long h, int side, float[] rows, int topN, int[] index, float[] scores);
+    private static native void nativeRowInvNorms(long h, int side, float[] out);
     private static native void nativeRankItems(long h, int[] u, int[] i, int[] exclU, int[] exclI, int[] ranks);
     private static native void nativeRankItemsRows(long h, float[] rows, int[] row, int[] i, int[] exclRow, int[] exclItem,
                                                    int[] ranks);

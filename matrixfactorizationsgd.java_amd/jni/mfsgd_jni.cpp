@@ -485,6 +485,73 @@ JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeRecommendRows(JNIEnv* e
     throw_status(env, H(h), rc);
 }
 
+// ---- cosine neighbours: similarItems / similarUsers (queries by index), similarRows (query vectors), rowInvNorms ----
+
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeSimilar(JNIEnv* env, jclass, jlong h, jint side, jintArray queries,
+                                                                 jint topn, jintArray index, jfloatArray scores) {
+    if (!queries || !index || !scores) return throw_new(env, "java/lang/NullPointerException", "similar");
+    if (side != MFSGD_SIDE_USERS && side != MFSGD_SIDE_ITEMS)
+        return throw_new(env, "java/lang/IllegalArgumentException", "similar: side");
+    const jsize n = env->GetArrayLength(queries);
+    if (topn < 1 || (jlong)env->GetArrayLength(index) < (jlong)n * topn || (jlong)env->GetArrayLength(scores) < (jlong)n * topn)
+        return throw_new(env, "java/lang/IllegalArgumentException", "index / scores shorter than queries x topN");
+    auto cq = alloc<int32_t>(env, (size_t)n);
+    auto ci = alloc<int32_t>(env, (size_t)n * (size_t)topn);
+    auto cs = alloc<float>(env, (size_t)n * (size_t)topn);
+    if (!cq || !ci || !cs) return;
+    env->GetIntArrayRegion(queries, 0, n, reinterpret_cast<jint*>(cq.get()));
+    if (env->ExceptionCheck()) return;
+    const int rc = side == MFSGD_SIDE_ITEMS ? mfsgd_similar_items(H(h), cq.get(), n, topn, ci.get(), cs.get())
+                                            : mfsgd_similar_users(H(h), cq.get(), n, topn, ci.get(), cs.get());
+    if (rc == MFSGD_OK && n > 0) {
+        env->SetIntArrayRegion(index, 0, n * topn, reinterpret_cast<const jint*>(ci.get()));
+        env->SetFloatArrayRegion(scores, 0, n * topn, cs.get());
+    }
+    throw_status(env, H(h), rc);
+}
+
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeSimilarRows(JNIEnv* env, jclass, jlong h, jint side, jfloatArray rows,
+                                                                     jint topn, jintArray index, jfloatArray scores) {
+    if (!rows || !index || !scores) return throw_new(env, "java/lang/NullPointerException", "similarRows");
+    int32_t n_users = 0, n_items = 0, k = 0;
+    int rc = mfsgd_get_dims(H(h), &n_users, &n_items, &k);
+    if (rc != MFSGD_OK) return throw_status(env, H(h), rc);
+    const jsize nf = env->GetArrayLength(rows);
+    if (k < 1 || nf % k != 0) return throw_new(env, "java/lang/IllegalArgumentException", "similarRows: length mismatch");
+    const jsize n = nf / k;
+    if (topn < 1 || (jlong)env->GetArrayLength(index) < (jlong)n * topn || (jlong)env->GetArrayLength(scores) < (jlong)n * topn)
+        return throw_new(env, "java/lang/IllegalArgumentException", "index / scores shorter than rows x topN");
+    auto cr = alloc<float>(env, (size_t)nf);
+    auto ci = alloc<int32_t>(env, (size_t)n * (size_t)topn);
+    auto cs = alloc<float>(env, (size_t)n * (size_t)topn);
+    if (!cr || !ci || !cs) return;
+    env->GetFloatArrayRegion(rows, 0, nf, cr.get());
+    if (env->ExceptionCheck()) return;
+    rc = mfsgd_similar_rows(H(h), side, cr.get(), n, topn, ci.get(), cs.get());
+    if (rc == MFSGD_OK && n > 0) {
+        env->SetIntArrayRegion(index, 0, n * topn, reinterpret_cast<const jint*>(ci.get()));
+        env->SetFloatArrayRegion(scores, 0, n * topn, cs.get());
+    }
+    throw_status(env, H(h), rc);
+}
+
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeRowInvNorms(JNIEnv* env, jclass, jlong h, jint side, jfloatArray out) {
+    if (!out) return throw_new(env, "java/lang/NullPointerException", "rowInvNorms");
+    int32_t n_users = 0, n_items = 0, k = 0;
+    int rc = mfsgd_get_dims(H(h), &n_users, &n_items, &k);
+    if (rc != MFSGD_OK) return throw_status(env, H(h), rc);
+    if (side != MFSGD_SIDE_USERS && side != MFSGD_SIDE_ITEMS)
+        return throw_new(env, "java/lang/IllegalArgumentException", "rowInvNorms: side");
+    const jsize n = side == MFSGD_SIDE_ITEMS ? n_items : n_users;
+    if (env->GetArrayLength(out) < n)
+        return throw_new(env, "java/lang/IllegalArgumentException", "rowInvNorms: out shorter than the side");
+    auto co = alloc<float>(env, (size_t)n);
+    if (!co) return;
+    rc = mfsgd_row_inv_norms(H(h), side, co.get());
+    if (rc == MFSGD_OK && n > 0) env->SetFloatArrayRegion(out, 0, n, co.get());
+    throw_status(env, H(h), rc);
+}
+
 // ---- DSGD: the ring under the C-ABI (mfsgd_dsgd_*) for MatrixFactorizationSGD.trainDistributed ------------------
 
 JNIEXPORT jbyteArray JNICALL Java_MatrixFactorizationSGD_nativeDsgdUniqueId(JNIEnv* env, jclass) {

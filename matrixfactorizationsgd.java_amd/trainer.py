@@ -425,6 +425,55 @@ class MatrixFactorizationSGD:
         res["ranks"] = ranks
         return res
 
+    # -- cosine neighbours (include/mfsgd.h, "similar items and users") -----------
+    _SIDES = {"users": 0, "items": 1}
+
+    def _side(self, side):
+        if side not in self._SIDES:
+            raise ValueError('side must be "users" or "items"')
+        return self._SIDES[side], self.users if side == "users" else self.items
+
+    def row_inv_norms(self, side):
+        """float32[n_users] (side "users") or [n_items] ("items"): 1 / sqrt(dot(row, row)) of every row of P or Q, 0 for a
+        zero row -- the factors of the cosine the similar_* calls score with."""
+        code, size = self._side(side)
+        out = np.empty(size, np.float32)
+        self._check(self._lib.mfsgd_row_inv_norms(self._handle(), code, _p(out, C.c_float)))
+        return out
+
+    def _similar(self, call, queries, topn):
+        qq = _i32(np.atleast_1d(queries))
+        if qq.ndim != 1:
+            raise ValueError("the queries must be a 1-d array")
+        index = np.empty((qq.size, int(topn)), np.int32)
+        scores = np.empty((qq.size, int(topn)), np.float32)
+        self._check(call(self._handle(), _p(qq, C.c_int32), qq.size, int(topn), _p(index, C.c_int32), _p(scores, C.c_float)))
+        return index, scores
+
+    def similar_items(self, items, topn):
+        """(index, scores), each [len(items), topn]: for each query item the other items with the largest cosine between
+        their rows of Q, best first, ties by the smaller index; the query itself is never returned, and a row that runs
+        out of candidates (topn == n_items) is padded with -1 / NaN."""
+        return self._similar(self._lib.mfsgd_similar_items, items, topn)
+
+    def similar_users(self, users, topn):
+        """similar_items() among users: rows of P against P."""
+        return self._similar(self._lib.mfsgd_similar_users, users, topn)
+
+    def similar_rows(self, rows, topn, side="items"):
+        """(index, scores), each [len(rows), topn]: the neighbours of query vectors of the caller's (n_rows x k: a folded-in
+        user, a cold item's vector) among the rows of Q (side "items") or P ("users").  Nothing is excluded."""
+        code, _ = self._side(side)
+        rows = _f32(rows)
+        if rows.ndim != 2 or rows.shape[1] != self.k:
+            raise ValueError("rows must be n_rows x k")
+        n = rows.shape[0]
+        index = np.empty((n, int(topn)), np.int32)
+        scores = np.empty((n, int(topn)), np.float32)
+        self._check(self._lib.mfsgd_similar_rows(self._handle(), code, _p(rows, C.c_float), n, int(topn),
+                                                 _p(index, C.c_int32), _p(scores, C.c_float)))
+        return index, scores
+
     # -- schedule introspection (tests, bench) -----------------------------------
     def schedule_info(self, part=0):
         info = _lib.ScheduleInfo()
