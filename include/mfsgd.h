@@ -494,7 +494,13 @@ int mfsgd_part_train(mfsgd_handle* h, int32_t part, float* q_block_dev, void* st
 int mfsgd_part_sse(mfsgd_handle* h, int32_t part, const float* q_block_dev, void* stream,
                    double* sse);
 /* Seeds P when this handle holds users [u_offset, u_offset + n_users) of a
- * larger problem: stream position of P row u is (u_offset + u) * k.           */
+ * larger problem: stream position of P row u is (u_offset + u) * k.  It seeds
+ * P alone: on a single-partition handle the handle's own Q is gone afterwards,
+ * and every call that reads it (training, RMSE, predict, recommend, rank,
+ * similar items, fold-in, the held-out measures, mfsgd_get_factors with a Q)
+ * is MFSGD_ERR_STATE until mfsgd_init_factors, mfsgd_set_factors or
+ * mfsgd_load_factors; the mfsgd_part_* calls with a caller-owned block,
+ * mfsgd_similar_users and mfsgd_get_factors(P, NULL) go on working.           */
 int mfsgd_init_p_offset(mfsgd_handle* h, int64_t seed, int64_t u_offset);
 /* The recovery point of an asynchronous sub-epoch: waits for `stream`; if the LAST mfsgd_part_train of this
  * partition found its persistent launch not co-resident (another kernel held CUs; the launch then changed

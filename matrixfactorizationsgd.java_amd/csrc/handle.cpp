@@ -34,6 +34,14 @@ int check_part(const mfsgd_handle* h, int32_t part, const char* name) {
     return MFSGD_OK;
 }
 
+int check_has_q(const mfsgd_handle* h, const char* call) {
+    if (h->n_parts == 1 && h->where != mfsgd_handle::Where::None && !h->have_q)
+        return fail(h, MFSGD_ERR_STATE,
+                    std::string(call) + ": Q is not initialised: call mfsgd_init_factors or mfsgd_set_factors, or drive the "
+                                        "handle with mfsgd_part_* and a caller-owned block");
+    return MFSGD_OK;
+}
+
 static int usable_devices(int* count, std::string* why) {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
@@ -123,6 +131,7 @@ static int seed_factors(mfsgd_handle* h, int64_t seed, int64_t u_offset, bool wi
     const float scale = (float)(1.0 / std::sqrt((double)k));
     release_device_factors(h);
     h->where = mfsgd_handle::Where::None;
+    h->have_q = with_q;
     if (ensure_device(h) == MFSGD_OK) {
         int rc;
         if ((rc = dev_alloc(h, h->dP, sizeof(float) * (size_t)h->cfg.n_users * kp))) return rc;
@@ -274,6 +283,7 @@ int mfsgd_set_factors(mfsgd_handle* h, const float* P, const float* Q) {
             h->hQ.assign((size_t)h->cfg.n_items * kp, 0.0f);
             for (int64_t x = 0; x < h->cfg.n_items; ++x) std::memcpy(&h->hQ[(size_t)x * kp], Q + x * k, sizeof(float) * (size_t)k);
         }
+        h->have_q = h->n_parts == 1;
         h->where = mfsgd_handle::Where::Host;
         return MFSGD_OK;
     });
@@ -282,6 +292,8 @@ int mfsgd_set_factors(mfsgd_handle* h, const float* P, const float* Q) {
 int mfsgd_get_factors(mfsgd_handle* h, float* P, float* Q) {
     return guarded(h, "get_factors", [&]() -> int {
         if (h->where == mfsgd_handle::Where::None) return fail(h, MFSGD_ERR_STATE, "get_factors: factors not initialised");
+        if (Q)
+            if (const int rc = check_has_q(h, "get_factors")) return rc;  // (before P is touched: an error writes nothing)
         const int k = h->cfg.k, kp = h->geo.kp;
         const std::vector<float>*sp = &h->hP, *sq = &h->hQ;
         std::vector<float> tp, tq;

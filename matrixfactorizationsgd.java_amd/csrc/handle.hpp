@@ -85,6 +85,9 @@ struct mfsgd_handle {
     enum class Where { None, Host, Device } where = Where::None;
     std::vector<float> hP, hQ;
     mfsgd::DevBuf dP, dQ;
+    // The handle holds a Q of its own: single-partition handles after mfsgd_init_factors, mfsgd_set_factors or
+    // mfsgd_load_factors.  Not after mfsgd_init_p_offset, which seeds P alone (check_has_q).
+    bool have_q = false;
 
     mfsgd::Validation val;
 
@@ -149,6 +152,11 @@ int guarded_free(const char* name, F&& body) {
 // MFSGD_OK, or MFSGD_ERR_INVALID_ARG with "<name>: bad partition".  (Not a Part*: h->parts is empty until
 // mfsgd_set_ratings, and some callers ask before.)
 int check_part(const mfsgd_handle* h, int32_t part, const char* name);
+
+// What every call that reads the handle's own Q asks before it asks for a device: MFSGD_OK, or MFSGD_ERR_STATE with
+// "<call>: Q is not initialised: ..." on a single-partition handle whose factors were seeded by mfsgd_init_p_offset
+// (P alone).  Factors that were never initialised are the caller's own check, with the message it has always had.
+int check_has_q(const mfsgd_handle* h, const char* call);
 
 // handle.cpp
 int ensure_device(mfsgd_handle* h);

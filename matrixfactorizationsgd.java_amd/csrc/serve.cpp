@@ -154,7 +154,7 @@ static int recommend_core(mfsgd_handle* h, const float* host_rows, int32_t n_row
     if (n_users == 0) return MFSGD_OK;
     if (host_rows && h->where == mfsgd_handle::Where::None)  // (asked here: factors_to_device wants a device first)
         return fail(h, MFSGD_ERR_STATE, "recommend_rows: factors not initialised");
-    if ((rc = factors_to_device(h))) return rc;
+    if ((rc = check_has_q(h, host_rows ? "recommend_rows" : "recommend")) || (rc = factors_to_device(h))) return rc;
     DevBuf d_rows, ex_slot, ex_off, ex_items;
     DevBuf temp;  // of the sorts: one for the exclusion lists and every batch, grown when one needs more
     const float* P;
@@ -193,6 +193,7 @@ static int similar_core(mfsgd_handle* h, const char* name, int32_t side, const f
     if (h->where == mfsgd_handle::Where::None)  // (asked here: factors_to_device wants a device first)
         return fail(h, MFSGD_ERR_STATE, call + "factors not initialised");
     int rc;
+    if (side == MFSGD_SIDE_ITEMS && (rc = check_has_q(h, name))) return rc;  // (the users' side reads P alone)
     if ((rc = factors_to_device(h))) return rc;
     auto bad = [h, &call](hipError_t e) { return serve_fail(h, call.c_str(), e); };
     DevBuf d_rows, d_ra, d_rb, ex_slot, ex_off, ex_items, temp;
@@ -285,7 +286,7 @@ static int rank_core(mfsgd_handle* h, const float* host_rows, int32_t n_rows, co
     if (n == 0) return MFSGD_OK;
     if (h->where == mfsgd_handle::Where::None)  // (asked here: factors_to_device wants a device first)
         return fail(h, MFSGD_ERR_STATE, "rank_items: factors not initialised");
-    if ((rc = factors_to_device(h))) return rc;
+    if ((rc = check_has_q(h, "rank_items")) || (rc = factors_to_device(h))) return rc;
     // counting sort: the pairs of slot s at off[s] .. off[s + 1], in the order given; place[x] = where pair x went
     for (int32_t s = 0; s < n_slots; ++s) off[(size_t)s + 1] += off[(size_t)s];
     std::vector<int32_t> grouped((size_t)n), ranks((size_t)n);
@@ -358,8 +359,8 @@ int mfsgd_predict(mfsgd_handle* h, const int32_t* u, const int32_t* i, float* ou
             if (u[j] < 0 || u[j] >= h->cfg.n_users || i[j] < 0 || i[j] >= h->cfg.n_items)
                 return fail(h, MFSGD_ERR_INVALID_ARG, "predict: pair " + std::to_string(j) + " out of range");
         if (n == 0) return MFSGD_OK;
-        int rc = factors_to_device(h);
-        if (rc) return rc;
+        int rc = check_has_q(h, "predict");
+        if (rc || (rc = factors_to_device(h))) return rc;
         DevBuf du, di, dout;
         if ((rc = dev_alloc(h, du, sizeof(int32_t) * (size_t)n))) return rc;
         if ((rc = dev_alloc(h, di, sizeof(int32_t) * (size_t)n))) return rc;
@@ -409,8 +410,8 @@ int mfsgd_row_inv_norms(mfsgd_handle* h, int32_t side, float* out) {
         if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "row_inv_norms: single-partition handles only");
         if (h->where == mfsgd_handle::Where::None)  // (asked here: factors_to_device wants a device first)
             return fail(h, MFSGD_ERR_STATE, "row_inv_norms: factors not initialised");
-        int rc = factors_to_device(h);
-        if (rc) return rc;
+        int rc = side == MFSGD_SIDE_ITEMS ? check_has_q(h, "row_inv_norms") : MFSGD_OK;
+        if (rc || (rc = factors_to_device(h))) return rc;
         const int32_t size = side == MFSGD_SIDE_ITEMS ? h->cfg.n_items : h->cfg.n_users;
         const float* M = side == MFSGD_SIDE_ITEMS ? h->dQ.as<const float>() : h->dP.as<const float>();
         auto bad = [h](hipError_t e) { return serve_fail(h, "row_inv_norms: ", e); };
@@ -545,6 +546,7 @@ int mfsgd_fold_in_users(mfsgd_handle* h, int32_t n_new, const int64_t* row_ptr, 
         if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "fold_in: single-partition handles only");
         if (h->where == mfsgd_handle::Where::None)  // (asked here: factors_to_device wants a device first)
             return fail(h, MFSGD_ERR_STATE, "fold_in: factors not initialised");
+        if (const int rc = check_has_q(h, "fold_in")) return rc;
         if (n_new == 0) return MFSGD_OK;
         if (row_ptr[0] != 0) return fail(h, MFSGD_ERR_INVALID_ARG, "fold_in: row_ptr[0] is not 0");
         for (int32_t x = 0; x < n_new; ++x)

@@ -342,7 +342,7 @@ static int check_pairs(const mfsgd_handle* h, const char* call, const int32_t* u
 static int check_reads_factors(const mfsgd_handle* h, const char* call) {
     if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, std::string(call) + ": single-partition handles only");
     if (h->where == mfsgd_handle::Where::None) return fail(h, MFSGD_ERR_STATE, std::string(call) + ": factors not initialised");
-    return MFSGD_OK;
+    return check_has_q(h, call);
 }
 
 // The scratch of launch_pairs_sse: its partials, then the sum.
@@ -397,6 +397,7 @@ int mfsgd_train(mfsgd_handle* h, int32_t epochs, double* rmse_per_epoch) {
     return guarded(h, "train", [&]() -> int {
         if (epochs < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "train: bad argument");
         if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "train: handle has n_parts > 1, drive it with mfsgd_part_train");
+        if (const int rc = check_has_q(h, "train")) return rc;
         return run_epochs(h, epochs, nullptr, nullptr, rmse_per_epoch);
     });
 }
@@ -405,8 +406,8 @@ int mfsgd_train_timed(mfsgd_handle* h, int32_t epochs, double* elapsed_ms, int64
     return guarded(h, "train_timed", [&]() -> int {
         if (epochs < 0 || !elapsed_ms) return fail(h, MFSGD_ERR_INVALID_ARG, "train_timed: bad argument");
         if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "train_timed: single-partition handles only");
-        int rc = prepare_compute(h);
-        if (rc) return rc;
+        int rc = check_has_q(h, "train_timed");
+        if (rc || (rc = prepare_compute(h))) return rc;
         Part& p = h->parts[0];
         float* Q = h->dQ.as<float>();
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -446,6 +447,7 @@ int mfsgd_train_schedule(mfsgd_handle* h, int32_t epochs, const float* lr, const
                 return fail(h, MFSGD_ERR_INVALID_ARG, "train_schedule: lr / lambda of epoch " + std::to_string(e) + " is NaN");
         if (epochs == 0) return MFSGD_OK;
         if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "train_schedule: handle has n_parts > 1, drive it with mfsgd_part_train");
+        if (const int rc = check_has_q(h, "train_schedule")) return rc;
         return run_epochs(h, epochs, lr, lambda, rmse_per_epoch);
     });
 }
@@ -458,8 +460,8 @@ int mfsgd_train_bold_driver(mfsgd_handle* h, int32_t epochs, float up, float dow
             return fail(h, MFSGD_ERR_INVALID_ARG, "bold_driver: lr_used and rmse_per_epoch are both required");
         if (epochs == 0) return MFSGD_OK;
         if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "bold_driver: handle has n_parts > 1, drive it with mfsgd_part_train");
-        int rc = prepare_compute(h);
-        if (rc) return rc;
+        int rc = check_has_q(h, "bold_driver");
+        if (rc || (rc = prepare_compute(h))) return rc;
         float* Q = h->dQ.as<float>();
         double prev = 0.0;
         if ((rc = rmse_of(h, h->parts[0], Q, &prev))) return rc;
@@ -482,8 +484,8 @@ int mfsgd_rmse(mfsgd_handle* h, double* out) {
     return guarded(h, "rmse", [&]() -> int {
         if (!out) return fail(h, MFSGD_ERR_INVALID_ARG, "rmse: null argument");
         if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "rmse: handle has n_parts > 1, use mfsgd_part_sse");
-        int rc = prepare_compute(h);
-        if (rc) return rc;
+        int rc = check_has_q(h, "rmse");
+        if (rc || (rc = prepare_compute(h))) return rc;
         return rmse_of(h, h->parts[0], h->dQ.as<const float>(), out);
     });
 }
@@ -678,8 +680,8 @@ int mfsgd_debug_epoch_profile(mfsgd_handle* h, uint64_t* out, int32_t* n_workgro
     return guarded(h, "debug_epoch_profile", [&]() -> int {
         if (!out || !n_workgroups) return fail(h, MFSGD_ERR_INVALID_ARG, "debug_epoch_profile: null argument");
         if (h->n_parts != 1) return fail(h, MFSGD_ERR_INVALID_ARG, "debug_epoch_profile: single-partition handles only");
-        int rc = prepare_compute(h);
-        if (rc) return rc;
+        int rc = check_has_q(h, "debug_epoch_profile");
+        if (rc || (rc = prepare_compute(h))) return rc;
         Part& p = h->parts[0];
         if ((rc = probe_persistent(h, p))) return rc;
         if (p.persistent_np <= 0) return fail(h, MFSGD_ERR_STATE, "debug_epoch_profile: persistent kernel not in use");
@@ -741,8 +743,8 @@ int mfsgd_debug_round_stamps(mfsgd_handle* h, int32_t part, int32_t round, uint6
     return guarded(h, "debug_round_stamps", [&]() -> int {
         if (!out) return fail(h, MFSGD_ERR_INVALID_ARG, "debug_round_stamps: null argument");
         if (h->n_parts != 1 || part != 0) return fail(h, MFSGD_ERR_INVALID_ARG, "debug_round_stamps: single-partition handles only");
-        int rc = prepare_compute(h);
-        if (rc) return rc;
+        int rc = check_has_q(h, "debug_round_stamps");
+        if (rc || (rc = prepare_compute(h))) return rc;
         Part& p = h->parts[0];
         if (round < 0 || round >= p.sched.B) return fail(h, MFSGD_ERR_INVALID_ARG, "debug_round_stamps: bad round");
         const size_t words = (size_t)p.sched.B * (6 + (size_t)p.sched.W * p.sched.W * 4);

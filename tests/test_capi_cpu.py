@@ -112,6 +112,62 @@ def test_part_init_q_is_a_slice_of_the_full_init(mf, oracle):
     np.testing.assert_array_equal(P, Po[4:9])
 
 
+def test_a_single_partition_handle_seeded_by_init_p_offset_has_no_q(mf, oracle, tmp_path):
+    """mfsgd_init_p_offset seeds P alone.  On a single-partition handle every call that reads the handle's own Q is
+    MFSGD_ERR_STATE from then on, with the call's prefix, before a device is asked for (so the code is the same with and
+    without a GPU, and nothing is launched); the calls that need P alone go on working; init_factors, set_factors and
+    load_factors make the handle whole again."""
+    from tests.handle_model import q_less_calls
+    from tests.test_validation_cpu import STATE, _raises
+
+    U_total, U, I, k, seed, off = 11, 5, 7, 6, 77, 4
+    Po, Qo = oracle.init_factors(U_total, I, k, seed)
+    with mf.MatrixFactorizationSGD(U, I, k, 0.01, 0.05, seed) as m:
+        m.set_ratings([0, 1, 2, 4], [0, 1, 2, 6], [1.0, 2.0, 3.0, 4.0])
+        m.set_validation([3, 4], [4, 6], [2.5, 3.5])
+        m.init_factors()
+        full = m.get_factors()
+        path = str(tmp_path / "whole.bin")
+        m.save_factors(path)
+
+        def lose_q():
+            m.init_p_offset(seed, off)
+            for prefix, call in q_less_calls(m):
+                _raises(mf, STATE, prefix, call)
+                assert "Q is not initialised" in m._lib.mfsgd_last_error(m._handle()).decode(), prefix
+            with pytest.raises(mf.MfsgdError) as ei:
+                m.save_factors(str(tmp_path / "none.bin"))
+            assert ei.value.code == STATE
+            # P alone is still there, and so is everything that needs no Q of the handle's
+            P = np.empty((U, k), np.float32)
+            m._check(m._lib.mfsgd_get_factors(m._handle(), P.ctypes.data_as(C.POINTER(C.c_float)), None))
+            np.testing.assert_array_equal(P, Po[off:off + U])
+            assert m.part_rows(0) == I and np.array_equal(m.part_init_q(0, seed, U_total)[:, :k], Qo)
+            assert m.hyper() == (float(np.float32(0.01)), float(np.float32(0.05))) and m.validation_size() == 2
+            if not have_gpu():
+                for call in (lambda: m.similar_users([0], 1), lambda: m.row_inv_norms("users")):
+                    with pytest.raises(mf.MfsgdError) as ei:
+                        call()
+                    assert ei.value.code == -2, ei.value  # MFSGD_ERR_NO_DEVICE: past the state checks
+            else:
+                assert m.similar_users([0], 1)[0].shape == (1, 1) and m.row_inv_norms("users").shape == (U,)
+
+        lose_q()
+        m.set_factors(*full)
+        for a, b in zip(m.get_factors(), full):
+            np.testing.assert_array_equal(a, b)
+        lose_q()
+        m.init_factors()
+        for a, b in zip(m.get_factors(), full):
+            np.testing.assert_array_equal(a, b)
+        lose_q()
+        m.load_factors(path)
+        for a, b in zip(m.get_factors(), full):
+            np.testing.assert_array_equal(a, b)
+        if have_gpu():
+            m.fit(1)
+
+
 @pytest.mark.skipif(have_gpu(), reason="checks the no-device error path")
 def test_compute_without_device_fails_loudly(mf):
     with mf.MatrixFactorizationSGD(4, 3, 8, 0.01, 0.05, 1) as m:
