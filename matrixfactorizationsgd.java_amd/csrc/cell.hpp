@@ -83,7 +83,7 @@ __device__ __forceinline__ void solo_chain_asm(float4& rq, const unsigned ea, co
     using f4 = __attribute__((ext_vector_type(4))) float;
     f4 q;
     n = __builtin_amdgcn_readfirstlane(n);
-    constexpr int PADV = mfsgd_pad_chain(L);
+    constexpr int PADV = mfsgd_pad_chain_tail(L), PADS = mfsgd_pad_chain_steady(L);  // the loop's two heads
     if constexpr (L == 16)
         asm volatile(MFSGD_SOLO_CHAIN_ASM_TEXT("", MFSGD_SFMA2_V) MFSGD_SOLO_CHAIN_OPERANDS);
     else if constexpr (L == 32)

@@ -24,9 +24,9 @@
 // and not used by the product: the helper is the slower of the pair at 16 lanes per rating, but a third wave on the
 // LDS slows the chain wave by what the second helper gains.)
 //
-// Every loop here has ONE form: what is in this file is what the product runs (the pads and the chain loop's pairs per
-// pass below are the only build-time knobs, for tools/ubench3.hip).  Included by cell.hpp, whose wrappers bind the
-// operands, and by tools/ubench3.hip, which times the loops against each other in isolation.
+// Every loop here has ONE form: what is in this file is what the product runs (the pads, the chain loop's steady
+// steps and its tail's pairs per pass below are the only build-time knobs, for tools/ubench3.hip).  Included by
+// cell.hpp, whose wrappers bind the operands, and by tools/ubench3.hip, which times the loops against each other in isolation.
 #pragma once
 
 // The loops below are a few 64-byte instruction-cache lines long and their cycle count per pass depends on
@@ -34,11 +34,21 @@
 // period 8 instructions).  Cycles per step at 0 / 2 / 4 / 6 s_nops past a 64-byte boundary:
 //     solo pair   L = 16: 136.1 137.5 133.7 138.8    L = 32: 165.4 168.6 174.3 178.0    L = 64: 173.4 175.4 170.3 176.4
 //     run loop    L = 16: 145.6 143.6 149.6 151.6    L = 32: 174.5 174.5 182.4 180.4    L = 64: 177.8 177.7 181.7 183.7
-// The solo pair as it is now (s posted in pairs, the chain wave's body four A/B pairs long; at the longest n the
+// The solo pair before the steady body (s posted in pairs, the chain wave's body four A/B pairs long; at the longest n the
 // microbenchmark holds -- 300 / 200 / 120 steps; profiles/chain_unroll_ubench3.log, the pair +- 1.5 from run to run):
 //     solo pair   L = 16: 124.7 125.6 125.1 125.4    L = 32: 144.8 147.7 147.2 147.0    L = 64: 162.3 157.7 165.7 160.7
 //     chain alone L = 16: 118.3 120.3 120.3 120.3    L = 32: 138.2 140.2 140.2 140.2    L = 64: 152.8 148.9 154.9 150.8
-// Every loop head is therefore placed explicitly (operand [pad], an assembly-time constant): the product
+// The chain wave's loop with a steady body of P steps without exits in front of that four-pair loop, now its tail (see
+// MFSGD_SOLO_CHAIN_ASM_TEXT; profiles/chain_steady_ubench3.log, same n, the parent's loop at 118.3 / 138.2 / 148.8 alone
+// and 125.0 / 145.7 / 158.5 as a pair in that session), at 0 / 2 / 4 / 6 s_nops in front of the STEADY head:
+//     chain alone, P = 8   L = 16: 113.1 113.1 114.1 114.6    L = 32: 127.7 127.7 128.8 129.2    L = 64: 141.3 141.4 142.4 142.9
+//     chain alone, P = 16  L = 16: 111.8 111.9 112.3 112.5    L = 32: 126.7 126.8 127.3 127.5    L = 64: 140.6 140.7 141.2 141.4
+//     solo pair,   P = 8   L = 16: 118.7 118.7 118.1 117.9    L = 32: 134.0 136.0 137.3 137.4    L = 64: 150.4 150.5 152.3 151.7
+//     solo pair,   P = 16  L = 16: 118.9 119.6 119.4 120.3    L = 32: 133.4 134.0 134.1 133.4    L = 64: 150.0 148.2 149.0 149.9
+// and in front of the TAIL head (P = 8, steady pad 0; the tail decides runs shorter than P and the last steps of the others:
+// chain alone at n = 50, cycles per step):
+//     L = 16: 123.0 123.0 123.5 123.4    L = 32: 136.8 136.5 137.0 137.0    L = 64: 148.2 148.3 148.8 148.4
+// Every loop head is therefore placed explicitly (operands [pad] / [pads], assembly-time constants): the product
 // runs the layout that was timed, whatever code the compiler puts in front of the loop.
 constexpr int mfsgd_pad_run(int lanes) {
 #ifdef MFSGD_PAD_RUN
@@ -54,11 +64,19 @@ constexpr int mfsgd_pad_gen(int lanes) {
     return 0;
 #endif
 }
-constexpr int mfsgd_pad_chain(int lanes) {
-#ifdef MFSGD_PAD_CHAIN
-    return MFSGD_PAD_CHAIN;
+// The chain wave's loop has two heads (the steady body and the tail, see MFSGD_SOLO_CHAIN_ASM_TEXT), each placed on its own.
+constexpr int mfsgd_pad_chain_steady(int lanes) {
+#ifdef MFSGD_PAD_CHAIN_STEADY
+    return MFSGD_PAD_CHAIN_STEADY;
 #else
-    return lanes == 64 ? 2 : 0;  // the four-pair body, second table above (profiles/chain_unroll_ubench3.log)
+    return 0;
+#endif
+}
+constexpr int mfsgd_pad_chain_tail(int lanes) {
+#ifdef MFSGD_PAD_CHAIN_TAIL
+    return MFSGD_PAD_CHAIN_TAIL;
+#else
+    return lanes == 64 ? 2 : 0;  // the four-pair body with its exits, second table above (profiles/chain_unroll_ubench3.log)
 #endif
 }
 constexpr int mfsgd_pad_helper(int lanes) {
@@ -68,9 +86,9 @@ constexpr int mfsgd_pad_helper(int lanes) {
     return lanes == 16 ? 6 : 2;  // [r3] the loop that takes the steps in pairs (tools/ubench3, profiles/r03_ubench3.log)
 #endif
 }
-// A/B pairs of solo chain steps per pass of the chain wave's loop, an assembly-time constant like the pads (1, 2 or 4:
-// tools/ubench3.hip times them against each other; a taken backward branch costs this loop about 9 cycles, which is
-// 4.7 cycles per step at one pair per pass and 1.2 at four).
+// A/B pairs of solo chain steps per pass of the chain wave's TAIL loop, an assembly-time constant like the pads (1, 2 or 4:
+// a taken backward branch costs this loop about 9 cycles more than a not-taken exit -- about 15 against 6, DESIGN.md
+// section 5 -- which is 4.7 cycles per step at one pair per pass and 1.2 at four).
 constexpr int mfsgd_chain_pairs() {
 #ifdef MFSGD_CHAIN_PAIRS
     return MFSGD_CHAIN_PAIRS;
@@ -78,7 +96,17 @@ constexpr int mfsgd_chain_pairs() {
     return 4;
 #endif
 }
+// Steps per pass of the chain wave's STEADY body (P: even, at most 16), which runs while at least P steps remain.
+constexpr int mfsgd_chain_steady() {
+#ifdef MFSGD_CHAIN_STEADY
+    return MFSGD_CHAIN_STEADY;
+#else
+    return 16;  // third table above
+#endif
+}
+static_assert(mfsgd_chain_steady() % 2 == 0 && mfsgd_chain_steady() >= 2 && mfsgd_chain_steady() <= 16, "steady body: A/B pairs, at most eight");
 #define MFSGD_LOOP_ALIGN ".p2align 6\n\t.rept %c[pad]\n\ts_nop 0\n\t.endr\n\t"
+#define MFSGD_LOOP_ALIGN_STEADY ".p2align 6\n\t.rept %c[pads]\n\ts_nop 0\n\t.endr\n\t"
 
 // ---- hand-scheduled run loop (gfx950) ---------------------------------------------------
 // `pairs` x 2 run steps of one wave: resident q rows in v[100:103] / v[140:143] (alternating),
@@ -306,7 +334,7 @@ constexpr int mfsgd_chain_pairs() {
 // v[100:103] q (updated in place); v[104:107] / v[108:111] p row of the even / odd step (prefetched
 // a step ahead); v[116:117] / v[118:119] {lr*r, next slots} of the even / odd step; v113 p address;
 // v[120:121] chunk products, v132 dot, v[122:125] c*q, v130 s.
-#define MFSGD_SOLO_CHAIN_HALF(P0, P1, P2, P3, N0, N1, N2, N3, ELRR, ESLOT, NEXTE, OFF_NEXT, WAIT, S, S1, EXTRA, SFMA) \
+#define MFSGD_SOLO_CHAIN_HALF(P0, P1, P2, P3, N0, N1, N2, N3, ELRR, ESLOT, NEXTE, OFF_NEXT, WAIT, S, S1, GAP, EXTRA, SFMA) \
         "s_waitcnt lgkmcnt(" WAIT ")\n\t" \
         "v_pk_mul_f32 v[120:121], v[" P0 ":" P1 "], v[100:101]\n\t" \
         "v_pk_fma_f32 v[120:121], v[" P2 ":" P3 "], v[102:103], v[120:121]\n\t" \
@@ -320,8 +348,7 @@ constexpr int mfsgd_chain_pairs() {
         "ds_read2_b32 v[" NEXTE "], v138 " OFF_NEXT "\n\t" \
         "s_nop 0\n\t" \
         "v_add_f32_dpp v132, v132, v132 row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
-        "s_sub_u32 %[n], %[n], 1\n\t" \
-        "s_cmp_eq_u32 %[n], 0\n\t" \
+        GAP \
         "v_add_f32_dpp v132, v132, v132 row_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
         EXTRA \
         SFMA(S, ELRR) \
@@ -332,10 +359,25 @@ constexpr int mfsgd_chain_pairs() {
 // helper wave needs the header in LDS, so the record stays); n >= 1 steps.  The q row is loaded HERE, not by the
 // caller: {lr*r_0, slots_1}, p row 0 and q are three LDS reads in flight together, one round trip in front of step 0.
 // (The harmless rewrite of the header word keeps "one LDS operation behind the reads", as in the run loop.)
-// One pass of the loop is %c[pairs] A/B pairs in a straight line (.irp: an assembly-time constant, see
-// mfsgd_chain_pairs): the entry offsets grow along the body, v138 is bumped and the backward branch taken once per
-// pass.  Every step keeps its own forward exit test -- after an A step to that step's "post s alone" tail (2<j>),
-// after a B step to the end -- so what the helper sees is what the one-pair loop posts.
+// The loop has TWO bodies built from the same half step.
+// STEADY (5:), while at least P = %c[steady] steps remain (mfsgd_chain_steady): P steps in a straight line with no exit
+// and no per-step counter -- an s_nop 1 fills the DPP gap where the tail counts -- and, in that gap of the pass's last
+// step, n -= P and the compare against P; v138 is bumped and the backward branch taken once per pass.
+// TAIL (1:), for the n < P steps that remain (all of a run shorter than P; skipped when none remain): %c[pairs] A/B pairs
+// per pass (mfsgd_chain_pairs), every step with its own forward exit test -- after an A step to that step's "post s
+// alone" tail (2<j>), after a B step to the end.  The state at the top of either body is that at the top of an A step:
+// v138 -> its entry, its p row, its entry words and one LDS write behind them in flight, q in v[100:103].
+// Both bodies read ahead and post s of a pair with the same instructions at the same offsets and points of a B step, so
+// what the helper sees is what the one-pair loop posts.
+#define MFSGD_SOLO_CHAIN_GAP_COUNT "s_sub_u32 %[n], %[n], 1\n\ts_cmp_eq_u32 %[n], 0\n\t"
+#define MFSGD_SOLO_CHAIN_GAP_NOP "s_nop 1\n\t"
+#define MFSGD_SOLO_CHAIN_GAP_PASS \
+        ".if 2 * \\j + 2 < %c[steady]\n\ts_nop 1\n\t.else\n\ts_sub_u32 %[n], %[n], %c[steady]\n\ts_cmp_ge_u32 %[n], %c[steady]\n\t.endif\n\t"
+#define MFSGD_SOLO_CHAIN_PAIR(GAP_A, GAP_B, EXIT_A, EXTRA, SFMA) \
+        MFSGD_SOLO_CHAIN_HALF("104", "105", "106", "107", "108", "109", "110", "111", "116", "117", "118:119", "offset0:6+8*\\j offset1:4+8*\\j", "1", "130", "131", GAP_A, EXTRA, SFMA) \
+        EXIT_A \
+        MFSGD_SOLO_CHAIN_HALF("108", "109", "110", "111", "104", "105", "106", "107", "118", "119", "116:117", "offset0:10+8*\\j offset1:8+8*\\j", "0", "128", "129", GAP_B, EXTRA, SFMA) \
+        "ds_write2_b32 v138, v130, v128 offset0:1+8*\\j offset1:5+8*\\j\n\t"
 #define MFSGD_SOLO_CHAIN_ASM_TEXT(EXTRA, SFMA) \
         "v_mov_b32 v138, %[ea]\n\t" \
         "v_mov_b32 v131, %[lr]\n\t" \
@@ -348,14 +390,25 @@ constexpr int mfsgd_chain_pairs() {
         "ds_read_b128 v[100:103], v133\n\t" \
         "ds_write_b32 v138, %[s0]\n\t" \
         "v_add_u32 v138, 16, v138\n\t" \
+        "s_cmp_lt_u32 %[n], %c[steady]\n\t" \
+        "s_cbranch_scc1 1f\n\t" \
+        MFSGD_LOOP_ALIGN_STEADY \
+        "5:\n\t" \
+        ".irp j,0,1,2,3,4,5,6,7\n\t" \
+        ".if 2 * \\j < %c[steady]\n\t" \
+        MFSGD_SOLO_CHAIN_PAIR(MFSGD_SOLO_CHAIN_GAP_NOP, MFSGD_SOLO_CHAIN_GAP_PASS, "", EXTRA, SFMA) \
+        ".endif\n\t" \
+        ".endr\n\t" \
+        "v_add_u32 v138, %c[sbump], v138\n\t" \
+        "s_cbranch_scc1 5b\n\t" \
+        "s_cmp_eq_u32 %[n], 0\n\t" \
+        "s_cbranch_scc1 3f\n\t" \
+        "s_branch 1f\n\t" \
         MFSGD_LOOP_ALIGN \
         "1:\n\t" \
         ".irp j,0,1,2,3\n\t" \
         ".if \\j < %c[pairs]\n\t" \
-        MFSGD_SOLO_CHAIN_HALF("104", "105", "106", "107", "108", "109", "110", "111", "116", "117", "118:119", "offset0:6+8*\\j offset1:4+8*\\j", "1", "130", "131", EXTRA, SFMA) \
-        "s_cbranch_scc1 2\\j\\()f\n\t" \
-        MFSGD_SOLO_CHAIN_HALF("108", "109", "110", "111", "104", "105", "106", "107", "118", "119", "116:117", "offset0:10+8*\\j offset1:8+8*\\j", "0", "128", "129", EXTRA, SFMA) \
-        "ds_write2_b32 v138, v130, v128 offset0:1+8*\\j offset1:5+8*\\j\n\t" \
+        MFSGD_SOLO_CHAIN_PAIR(MFSGD_SOLO_CHAIN_GAP_COUNT, MFSGD_SOLO_CHAIN_GAP_COUNT, "s_cbranch_scc1 2\\j\\()f\n\t", EXTRA, SFMA) \
         ".if \\j + 1 < %c[pairs]\n\t" \
         "s_cbranch_scc1 3f\n\t" \
         ".endif\n\t" \
@@ -383,7 +436,8 @@ constexpr int mfsgd_chain_pairs() {
 #define MFSGD_SOLO_CHAIN_OPERANDS                                                                                      \
     : [n] "+s"(n), [q0] "=v"(q[0]), [q1] "=v"(q[1]), [q2] "=v"(q[2]), [q3] "=v"(q[3])                                  \
     : [ea] "v"(ea), [rb] "v"(rowbase), [s0] "v"(s0), [lr] "s"(lr), [c2] "s"(c2), [pad] "n"(PADV),                      \
-      [pairs] "n"(mfsgd_chain_pairs()), [bump] "n"(32 * mfsgd_chain_pairs())                                           \
+      [pads] "n"(PADS), [pairs] "n"(mfsgd_chain_pairs()), [bump] "n"(32 * mfsgd_chain_pairs()),                         \
+      [steady] "n"(mfsgd_chain_steady()), [sbump] "n"(16 * mfsgd_chain_steady())                                       \
     : "memory", "scc", "vcc", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", \
       "v113", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v128", "v129", "v130",  \
       "v131", "v132", "v133", "v138", "v139"

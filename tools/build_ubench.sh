@@ -8,15 +8,20 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 for L in 16 32 64; do
     $HIPCC --offload-arch=gfx950 -O2 -ffp-contract=off -DLG=$L -Wno-unused-value ubench3.hip -o bin/ub3_$L
 done
-# the chain wave's loop at 1 / 2 / 4 A/B pairs per pass and every placement of its head (profiles/chain_unroll_ubench3.log):
-#   for f in tools/bin/ub3c_*; do echo $f; $f chain; done
+# the chain wave's loop: steady body of P = 8 / 16 steps at every placement of its head, and every placement of the tail's
+# head at P = 8 (profiles/chain_steady_ubench3.log); each -D defaults to the shipped value:
+#   for f in tools/bin/ub3s_*; do echo $f; $f chain; done
 for L in 16 32 64; do
-    for P in 1 2 4; do
+    for P in 8 16; do
         for PAD in 0 2 4 6; do
-            $HIPCC --offload-arch=gfx950 -O2 -ffp-contract=off -DLG=$L -DMFSGD_CHAIN_PAIRS=$P -DMFSGD_PAD_CHAIN=$PAD -Wno-unused-value ubench3.hip -o bin/ub3c_${L}_pairs${P}_pad${PAD} &
+            $HIPCC --offload-arch=gfx950 -O2 -ffp-contract=off -DLG=$L -DMFSGD_CHAIN_STEADY=$P -DMFSGD_PAD_CHAIN_STEADY=$PAD -Wno-unused-value ubench3.hip -o bin/ub3s_${L}_P${P}_s${PAD} &
         done
         wait
     done
+    for PAD in 0 2 4 6; do
+        $HIPCC --offload-arch=gfx950 -O2 -ffp-contract=off -DLG=$L -DMFSGD_CHAIN_STEADY=8 -DMFSGD_PAD_CHAIN_TAIL=$PAD -Wno-unused-value ubench3.hip -o bin/ub3s_${L}_P8_t${PAD} &
+    done
+    wait
 done
 # L = 64 with the two v_permlane*_swap levels instead of the row_bcast reduction (what round 1 ran)
 $HIPCC --offload-arch=gfx950 -O2 -ffp-contract=off -DLG=64 -DOLD64 -Wno-unused-value ubench3.hip -o bin/ub3_64old

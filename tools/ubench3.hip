@@ -82,7 +82,7 @@ __global__ void __launch_bounds__(192) k(const float* rows_in, const uint32_t* e
         // cut run: the chain wave stores q into its row between the halves (measured and not used by the product: run_asm.hpp)
         typedef float f4 __attribute__((ext_vector_type(4)));
         f4 q;  // (the chain loop loads the q row itself)
-        constexpr int PADV = mfsgd_pad_chain(LG);
+        constexpr int PADV = mfsgd_pad_chain_tail(LG), PADS = mfsgd_pad_chain_steady(LG);
         const int m = (n_steps / 2) & ~1;
         const unsigned ea0 = ea;
         n = m;
@@ -112,7 +112,7 @@ __global__ void __launch_bounds__(192) k(const float* rows_in, const uint32_t* e
         }
         f4 q;  // (the chain loop loads the q row itself)
         const unsigned s0 = *(const uint32_t*)(smem + ENT_OFF);  // the header's slots word, as Cell::apply reads it
-        constexpr int PADV = mfsgd_pad_chain(LG);
+        constexpr int PADV = mfsgd_pad_chain_tail(LG), PADS = mfsgd_pad_chain_steady(LG);
         asm volatile(MFSGD_SOLO_CHAIN_ASM_TEXT(EXTRA_SOLO, SFMA2) MFSGD_SOLO_CHAIN_OPERANDS);
     } else if (wave == 1 && (mode == 0 || mode == 2 || mode == 5)) {
         int spins = 1 << 20, fin = 1;
@@ -160,8 +160,9 @@ static float ref_dot(const float* p, const float* q) {
 
 // ubench3          : every mode at n = NSTEP, NSTEP - 1, 1, 2, 50, 51
 // ubench3 chain    : the chain wave's loop only (modes 0 and 1) at those n and at every n = 1..33 -- every exit of a
-//                    straight-line body of up to eight steps, twice over (built with -DMFSGD_CHAIN_PAIRS=1|2|4 and
-//                    -DMFSGD_PAD_CHAIN=0|2|4|6: tools/build_ubench.sh); one line per n, the short runs as one line
+//                    tail of up to eight steps and every hand-over from a steady body of 8 or 16, twice over (built with
+//                    -DMFSGD_CHAIN_STEADY=8|16, -DMFSGD_PAD_CHAIN_STEADY=0|2|4|6, -DMFSGD_PAD_CHAIN_TAIL=0|2|4|6 and
+//                    -DMFSGD_CHAIN_PAIRS=1|2|4: tools/build_ubench.sh); one line per n, the short runs as one line
 int main(int argc, char** argv) {
     const bool chain_only = argc > 1 && strcmp(argv[1], "chain") == 0;
     std::vector<int> lengths = {NSTEP, NSTEP - 1, 1, 2, 50, 51};
@@ -301,11 +302,11 @@ int main(int argc, char** argv) {
         for (int n = 1; n <= 33; ++n) (res[0][n].bad ? wrong : exact)++;
         for (int n : {NSTEP, NSTEP - 1, 50, 51, 2, 1}) {
             const Res &p = res[0][n], &a = res[1][n];
-            printf("L=%d pairs=%d pad=%d n=%d: pair %.1f, chain in the pair %.1f, chain alone %.1f cycles/step%s\n", LG, mfsgd_chain_pairs(),
-                   mfsgd_pad_chain(LG), n, (p.helper > p.chain ? p.helper : p.chain) / n, p.chain / n, a.chain / n, p.bad ? "  MISMATCH" : "  bit-exact");
+            printf("L=%d P=%d pairs=%d pad=%d/%d n=%d: pair %.1f, chain in the pair %.1f, chain alone %.1f cycles/step%s\n", LG, mfsgd_chain_steady(),
+                   mfsgd_chain_pairs(), mfsgd_pad_chain_steady(LG), mfsgd_pad_chain_tail(LG), n, (p.helper > p.chain ? p.helper : p.chain) / n, p.chain / n, a.chain / n, p.bad ? "  MISMATCH" : "  bit-exact");
         }
-        printf("L=%d pairs=%d pad=%d n=1..33: %d bit-exact, %d MISMATCH; chain alone, cycles per run at n = 7 8 9 15 16 17 31 32 33:", LG,
-               mfsgd_chain_pairs(), mfsgd_pad_chain(LG), exact, wrong);
+        printf("L=%d P=%d pairs=%d pad=%d/%d n=1..33: %d bit-exact, %d MISMATCH; chain alone, cycles per run at n = 7 8 9 15 16 17 31 32 33:", LG,
+               mfsgd_chain_steady(), mfsgd_chain_pairs(), mfsgd_pad_chain_steady(LG), mfsgd_pad_chain_tail(LG), exact, wrong);
         for (int n : {7, 8, 9, 15, 16, 17, 31, 32, 33}) printf(" %.0f", res[1][n].chain);
         printf("\n");
     }
