@@ -77,6 +77,19 @@ class RankingMetrics(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class OnlineInfo(C.Structure):
+    _fields_ = [
+        ("n", C.c_int64),
+        ("pieces", C.c_int64),
+        ("levels", C.c_int64),
+        ("max_width", C.c_int64),
+        ("launches", C.c_int64),
+    ]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 FLAG_NO_GRAPH = 1
 FLAG_ROUND_LAUNCH = 2
 FLAG_HOST_INGEST = 4
@@ -128,6 +141,8 @@ SIGNATURES = {
     "mfsgd_rmse_pairs": (C.c_int, [_H, _i32p, _i32p, _f32p, C.c_int64, _f64p, _f64p]),
     "mfsgd_train_early_stop": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_double, C.c_int32, _f32p, _f32p, _f64p, _f64p,
                                          _i32p, _i32p]),
+    "mfsgd_online_levels": (C.c_int, [_H, _i32p, _i32p, C.c_int64, _i32p, C.POINTER(OnlineInfo)]),
+    "mfsgd_apply_ratings": (C.c_int, [_H, _i32p, _i32p, _f32p, C.c_int64, _f32p, C.POINTER(OnlineInfo)]),
     "mfsgd_ratings_file_open": (C.c_int, [C.c_char_p, C.c_int32, C.POINTER(_H)]),
     "mfsgd_ratings_file_info": (C.c_int, [_H, _i64p, _i32p, _i32p]),
     "mfsgd_ratings_file_read": (C.c_int, [_H, _i32p, _i32p, _f32p, _i64p, _i64p]),

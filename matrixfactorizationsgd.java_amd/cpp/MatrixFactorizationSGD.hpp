@@ -211,6 +211,27 @@ class MatrixFactorizationSGD {
         return {std::move(used), std::move(rmse)};
     }
 
+    // ---- online updates -----------------------------------------------------------------------------------------------
+    // float[] partialFit(int[] u, int[] i, float[] r): applies the ratings to the live model in the order given, bit for
+    // bit the sequential per-rating loop at the current lr / lambda (include/mfsgd.h, "online updates"); returns each
+    // rating's error just before its own update.  The stored ratings, their schedules and the held-out set are not
+    // touched, and none is needed.  info (nullable): pieces, levels, widest level, kernel launches
+    std::vector<float> partialFit(const std::vector<int32_t>& u, const std::vector<int32_t>& i, const std::vector<float>& r,
+                                  mfsgd_online_info* info = nullptr) {
+        if (u.size() != i.size() || u.size() != r.size()) throw std::invalid_argument("length mismatch");
+        std::vector<float> err(u.size());
+        check(mfsgd_apply_ratings(h_, u.data(), i.data(), r.data(), (int64_t)u.size(), err.data(), info));
+        return err;
+    }
+    // int[] onlineLevels(int[] u, int[] i): the dependency level of every rating inside its piece, as partialFit would
+    // run the list; host only
+    std::vector<int32_t> onlineLevels(const std::vector<int32_t>& u, const std::vector<int32_t>& i, mfsgd_online_info* info = nullptr) {
+        if (u.size() != i.size()) throw std::invalid_argument("length mismatch");
+        std::vector<int32_t> level(u.size());
+        check(mfsgd_online_levels(h_, u.data(), i.data(), (int64_t)u.size(), level.data(), info));
+        return level;
+    }
+
     // ---- held-out validation and early stopping on it ------------------------------------------------------------------
     // void setValidation(int[] u, int[] i, float[] r): the held-out set of the model, copied and kept on the device from
     // the first call that measures it; empty arrays clear it

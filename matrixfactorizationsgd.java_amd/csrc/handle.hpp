@@ -90,6 +90,10 @@ struct mfsgd_handle {
     bool have_q = false;
 
     mfsgd::Validation val;
+    // Online updates (mfsgd_online_levels, mfsgd_apply_ratings): per user / per item, 1 + the level of the latest rating
+    // of the piece being levelled that has it, 0 for none.  Host memory, allocated at the first such call; all zero
+    // between calls (a piece resets the entries it touched).
+    std::vector<int32_t> online_last_u, online_last_i;
 
     bool device_ready = false;
     int n_cu = 0;

@@ -1,5 +1,5 @@
 // kernels.hpp -- host-callable launchers of every kernel unit: epoch.hip, cells.hip, kernels.hip, foldin.hip,
-// rehyper.hip, recommend.hip, rank.hip, similar.hip and validate.hip.
+// online.hip, rehyper.hip, recommend.hip, rank.hip, similar.hip and validate.hip.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -54,6 +54,16 @@ hipError_t launch_predict(int L, const float* P, const float* Q, const int32_t* 
 hipError_t launch_fold_in(int L, const float* Q, float* rows, int k, const long long* row_ptr, long long base,
                           const int32_t* perm, int nb, const int32_t* items, const float* ratings, int epochs, float lr,
                           float c, hipStream_t st);
+
+// online.hip.  Levels l0 .. l1 - 1 of one piece of an online update against the live P and Q (kp-padded rows): level l is
+// the ratings level_ptr[l] .. level_ptr[l + 1] - 1 of u / i / r, which share no user and no item; each gets the whole
+// canonical update, and err[orig[j]] (err nullable) the error before it.  One level may be given to any number of
+// workgroups; several levels (their order is the barrier between them) go to ONE workgroup, which walks them -- anything
+// else is hipErrorInvalidValue.  Every user is a row of P, every item a row of Q, and every orig an entry of err: the
+// caller checks.  Asynchronous on st.
+hipError_t launch_apply_levels(int L, float* P, float* Q, const int32_t* u, const int32_t* i, const float* r,
+                               const int32_t* orig, const int32_t* level_ptr, int l0, int l1, int workgroups, float lr,
+                               float c, float* err, hipStream_t st);
 
 // rehyper.hip.  Re-bakes lr and c = 1 - lr*lambda into the entries of a schedule on the device, in place: afterwards
 // they are byte for byte what the packers write for those values (schedule.cpp, rehyper_schedule, is the host's form).

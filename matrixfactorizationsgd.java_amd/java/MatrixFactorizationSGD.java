@@ -264,6 +264,19 @@ public final class MatrixFactorizationSGD implements AutoCloseable {
     }
 
     /**
+     * Applies fresh ratings of users and items the model already has, in the order given (mfsgd_apply_ratings): bit for
+     * bit the sequential per-rating SGD loop at the current lr / lambda.  Returns each rating's error just before its
+     * own update ("test, then train").  The ratings train() stored, their schedules and the held-out set are not
+     * touched, and none is needed: a model that was only loaded can be updated.
+     */
+    public float[] partialFit(int[] u, int[] i, float[] r) {
+        if (u.length != i.length || u.length != r.length) throw new IllegalArgumentException("length mismatch");
+        float[] err = new float[u.length];
+        nativeApplyRatings(handle, u, i, r, err);
+        return err;
+    }
+
+    /**
      * The held-out set of the model (mfsgd_set_validation): copied, kept on the device from the first call that
      * measures it; empty arrays clear it.  Needs no GPU; survives train(), setHyper() and loadFactors().
      */
@@ -442,6 +455,7 @@ public final class MatrixFactorizationSGD implements AutoCloseable {
     private static native void nativeTrainEarlyStop(long h, int maxEpochs, int patience, double minDelta, int restoreBest,
                                                     float[] lr, float[] lambda, double[] valRmse, double[] trainRmse,
                                                     int[] epochsRunBestEpoch);
+    private static native void nativeApplyRatings(long h, int[] u, int[] i, float[] r, float[] err);
     private static native void nativePredict(long h, int[] u, int[] i, float[] out);
     private static native void nativeRecommend(long h, int[] users, int topN, int[] items, float[] scores);
     private static native void nativeRecommendExcluding(long h, int[] users, int topN, int[] exclU, int[] exclI, int[] items,

@@ -253,6 +253,27 @@ JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeRmsePairs(JNIEnv* env, 
     throw_status(env, H(h), rc);
 }
 
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeApplyRatings(JNIEnv* env, jclass, jlong h, jintArray u, jintArray i,
+                                                                      jfloatArray r, jfloatArray err) {
+    if (!u || !i || !r || !err) return throw_new(env, "java/lang/NullPointerException", "partialFit");
+    const jsize n = env->GetArrayLength(u);
+    if (env->GetArrayLength(i) != n || env->GetArrayLength(r) != n || env->GetArrayLength(err) != n)
+        return throw_new(env, "java/lang/IllegalArgumentException", "u, i, r and err must have the same length");
+    // copies, not pins: mfsgd_apply_ratings launches a kernel per level or run of levels and waits for the device
+    auto cu = alloc<int32_t>(env, (size_t)n);
+    auto ci = alloc<int32_t>(env, (size_t)n);
+    auto cr = alloc<float>(env, (size_t)n);
+    auto ce = alloc<float>(env, (size_t)n);
+    if (!cu || !ci || !cr || !ce) return;
+    env->GetIntArrayRegion(u, 0, n, reinterpret_cast<jint*>(cu.get()));
+    env->GetIntArrayRegion(i, 0, n, reinterpret_cast<jint*>(ci.get()));
+    env->GetFloatArrayRegion(r, 0, n, cr.get());
+    if (env->ExceptionCheck()) return;
+    const int rc = mfsgd_apply_ratings(H(h), cu.get(), ci.get(), cr.get(), n, ce.get(), nullptr);
+    if (rc == MFSGD_OK && n > 0) env->SetFloatArrayRegion(err, 0, n, ce.get());
+    throw_status(env, H(h), rc);
+}
+
 JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeTrainEarlyStop(JNIEnv* env, jclass, jlong h, jint max_epochs,
                                                                         jint patience, jdouble min_delta, jint restore_best,
                                                                         jfloatArray lr, jfloatArray lambda, jdoubleArray val_rmse,

@@ -307,6 +307,32 @@ class MatrixFactorizationSGD:
         return dict(val_rmse=val[:ran.value], train_rmse=None if trn is None else trn[:ran.value],
                     epochs_run=ran.value, best_epoch=best.value)
 
+    # -- online updates (include/mfsgd.h, "online updates") -------------------------
+    def partial_fit(self, u, i, r, *, errors=False, info=False):
+        """Applies the ratings (u[j], i[j], r[j]) to the live model in the order given (mfsgd_apply_ratings): bit for bit
+        the sequential per-rating SGD loop, at the current lr and lambda.  The stored ratings, their schedules and the
+        held-out set are not touched, and none is needed.  errors=True returns float32[n], each rating's error just
+        before its own update ("test, then train"); info=True returns dict(n, pieces, levels, max_width, launches);
+        both: (errors, info); neither: None."""
+        uu, ii, rr = self._triples(u, i, r)
+        err = np.empty(uu.size, np.float32) if errors else None
+        out = _lib.OnlineInfo()
+        self._check(self._lib.mfsgd_apply_ratings(self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32), _p(rr, C.c_float),
+                                                  uu.size, None if err is None else _p(err, C.c_float), C.byref(out)))
+        res = tuple(x for x, on in ((err, errors), (out.as_dict(), info)) if on)
+        return None if not res else res[0] if len(res) == 1 else res
+
+    def online_levels(self, u, i):
+        """(levels int32[n], dict(n, pieces, levels, max_width, launches = 0)): the dependency level of every rating
+        inside its piece of 2^20, as partial_fit would run the list (mfsgd_online_levels).  Host only: needs no GPU, no
+        ratings and no factors."""
+        uu, ii = _pairs(np.atleast_1d(u), np.atleast_1d(i), "u and i")
+        levels = np.empty(uu.size, np.int32)
+        out = _lib.OnlineInfo()
+        self._check(self._lib.mfsgd_online_levels(self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32), uu.size,
+                                                  _p(levels, C.c_int32), C.byref(out)))
+        return levels, out.as_dict()
+
     def train_timed(self, epochs):
         """(elapsed device milliseconds, kernel launches) for `epochs` passes."""
         ms = C.c_double()

@@ -1,9 +1,10 @@
 """Timings of the paths around training: predict (batched), recommend (top-N, and top-N that leaves out
 the whole rating set), fold-in of users against the trained item factors and top-N for the folded rows, RMSE pass,
-set_ratings (schedule build), held-out validation RMSE and early stopping on it.  Wall-clock, through the C-ABI (host
+set_ratings (schedule build), held-out validation RMSE and early stopping on it, online updates of a live model.  Wall-clock, through the C-ABI (host
 arrays in and out, so PCIe copies are included); run it under `rocprofv3 --kernel-trace --stats` for the kernel times.
 
     python tools/bench_aux.py [WORKLOAD] [SCALE] [validation]      (validation: that leg alone)
+    python tools/bench_aux.py [WORKLOAD] [SCALE] online [N ...]    (the online leg alone; batch sizes, default 2^10 2^16 2^20)
 """
 import sys
 import time
@@ -59,6 +60,38 @@ def validation_leg(m, w, n_held=2_000_000, epochs=10):
     m.set_validation([], [], [])
 
 
+def online_leg(m, w, sizes=(1 << 10, 1 << 16, 1 << 20)):
+    """partial_fit of batches drawn from the workload's own ratings (so users and items come with the workload's
+    frequencies), on a model that holds the workload and has trained: host levelling alone (online_levels), the whole
+    call with the errors coming back, and what the call leaves for upload, kernels and download; against the only
+    route there was before -- set_ratings(batch), fit(1), set_ratings(workload) -- which also applies the batch in the
+    scheduler's order, not the given one.  Medians of 5 after a warm-up; the kernels alone (apply_levels_kernel) are
+    the kernel trace of this run with one batch size: total time / 6 calls."""
+    rng = np.random.default_rng(23)
+    print(f"  online updates: batch | levels | widest | launches | levelling ms | partial_fit ms | rest ms | "
+          f"old route ms (set batch + fit(1) + set workload)")
+    for n in sizes:
+        at = rng.integers(0, w["nnz"], n)
+        bu, bi, br = w["u"][at].astype(np.int32), w["i"][at].astype(np.int32), w["r"][at].astype(np.float32)
+        info = m.partial_fit(bu, bi, br, info=True)
+        t_lv = _median_ms(lambda: m.online_levels(bu, bi))
+        t_pf = _median_ms(lambda: m.partial_fit(bu, bi, br, errors=True))
+
+        def old_route():
+            t0 = time.perf_counter()
+            m.set_ratings(bu, bi, br)
+            t1 = time.perf_counter()
+            m.fit(1, rmse=False)
+            t2 = time.perf_counter()
+            m.set_ratings(w["u"], w["i"], w["r"])
+            return np.array([t1 - t0, t2 - t1, time.perf_counter() - t2]) * 1e3
+
+        old_route()
+        parts = np.median([old_route() for _ in range(3)], axis=0)
+        print(f"    {n:8d} | {info['levels']:6d} | {info['max_width']:7d} | {info['launches']:6d} | {t_lv:9.3f} | {t_pf:9.3f} | "
+              f"{t_pf - t_lv:9.3f} | {parts.sum():9.1f} ({parts[0]:.1f} + {parts[1]:.1f} + {parts[2]:.1f})")
+
+
 name = sys.argv[1] if len(sys.argv) > 1 else "cfg2_ml20m"
 scale = float(sys.argv[2]) if len(sys.argv) > 2 else 1.0
 w = mf.synth.workload(name, scale)
@@ -70,6 +103,14 @@ if len(sys.argv) > 3 and sys.argv[3] == "validation":
         m.fit(1, rmse=False)
         print(f"{name} x{scale}: {w['nnz']} ratings, {w['U']} x {w['I']}, k = {k}")
         validation_leg(m, w)
+    sys.exit(0)
+if len(sys.argv) > 3 and sys.argv[3] == "online":
+    with mf.MatrixFactorizationSGD(w["U"], w["I"], k, 0.01, 0.05, 3, host_threads=16) as m:
+        m.set_ratings(w["u"], w["i"], w["r"])
+        m.init_factors()
+        m.fit(1, rmse=False)
+        print(f"{name} x{scale}: {w['nnz']} ratings, {w['U']} x {w['I']}, k = {k}")
+        online_leg(m, w, *([tuple(int(x) for x in sys.argv[4:])] if len(sys.argv) > 4 else []))
     sys.exit(0)
 with mf.MatrixFactorizationSGD(w["U"], w["I"], k, 0.01, 0.05, 3, host_threads=16) as m:
     t0 = time.perf_counter()
@@ -114,6 +155,7 @@ with mf.MatrixFactorizationSGD(w["U"], w["I"], k, 0.01, 0.05, 3, host_threads=16
     t_rec_r = time.perf_counter() - t0
     print(f"{name} x{scale}: validation leg (the model has trained one epoch)")
     validation_leg(m, w)
+    online_leg(m, w)
 kept = int(np.isin(w["u"], users).sum())
 print(f"{name} x{scale}: {n} ratings, {w['U']} x {w['I']}, k = {k}")
 print(f"  set_ratings (schedule build + ingest)  {t_set * 1e3:9.1f} ms")
