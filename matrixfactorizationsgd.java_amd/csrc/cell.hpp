@@ -106,8 +106,39 @@ __device__ __forceinline__ bool solo_helper_asm(const unsigned ea, const unsigne
     return spins != 0;
 }
 
+// The chain wave of a lone-tile cell (run_asm.hpp, MFSGD_LONE_CHAIN_ASM_TEXT): sets the run up, takes the row from its
+// mailbox `src` (tag `want`), joins ONE workgroup barrier, runs the n steps and posts the row to `dst` (tag `ptag`, lanes
+// of the mask `pm`).  `ctl`: LDS byte address of the control block ([0] abort broadcast, [1] arrival stamp when `prof`).
+// Returns false if it gave up waiting (abort word and ctl[0] raised, barrier joined, nothing trained or posted).
+template <int L>
+__device__ __forceinline__ bool lone_chain_asm(const unsigned ea, const unsigned s0, const unsigned rowbase, int n, const float lr,
+                                               const uint64_t c2, const __attribute__((address_space(1))) unsigned long long* src,
+                                               unsigned want, const __attribute__((address_space(1))) unsigned* abw,
+                                               const unsigned ctl, __attribute__((address_space(1))) unsigned long long* dst,
+                                               unsigned ptag, uint64_t pm, unsigned prof) {
+    static_assert(L == 16 || L == 32 || L == 64, "solo loops: 16, 32 or 64 lanes per rating");
+    // (workgroup-uniform by construction; the compiler cannot always see it, and the text wants scalar registers)
+    n = __builtin_amdgcn_readfirstlane(n);
+    pm = (uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)pm) |
+         (uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(pm >> 32)) << 32;
+    want = (unsigned)__builtin_amdgcn_readfirstlane((int)want);
+    ptag = (unsigned)__builtin_amdgcn_readfirstlane((int)ptag);
+    prof = (unsigned)__builtin_amdgcn_readfirstlane((int)prof);
+    unsigned spins = 0, gave = 0, t0;
+    uint64_t tmp;
+    constexpr int PADV = mfsgd_pad_chain_tail(L), PADS = mfsgd_pad_chain_steady(L);  // the same heads at the same places
+    if constexpr (L == 16)
+        asm volatile(MFSGD_LONE_CHAIN_ASM_TEXT("", MFSGD_SFMA2_V) MFSGD_LONE_CHAIN_OPERANDS);
+    else if constexpr (L == 32)
+        asm volatile(MFSGD_LONE_CHAIN_ASM_TEXT(MFSGD_BCAST_ADD32, MFSGD_SFMA2_S) MFSGD_LONE_CHAIN_OPERANDS);
+    else
+        asm volatile(MFSGD_LONE_CHAIN_ASM_TEXT(MFSGD_BCAST_ADD64, MFSGD_SFMA2_S) MFSGD_LONE_CHAIN_OPERANDS);
+    return gave == 0;
+}
+
 // copy waves of the persistent training kernel: as many again as apply waves, up to 8 waves in all
-// (16 waves would leave each only 128 VGPRs; the assembly run loop uses v100..v143)
+// (16 waves would leave each only 128 VGPRs; the assembly loops use fixed registers up to v159 -- the lone-tile chain
+// text of run_asm.hpp -- and the persistent kernel comes to 175-178 VGPRs)
 template <int L, int W>
 constexpr int epoch_helpers() {
     return W <= 4 ? W : 0;
@@ -301,6 +332,61 @@ struct Cell {
             for (int x = 0; x < UNR; ++x) put(s + x * NWV * G, rid[x], v[x]);
         }
         for (; s < hi; s += NWV * G) put(s, lids[s], lds_ld(lrows, (unsigned)(s * ROWB) + laneoff));
+    }
+
+    // ---- the lone-tile fast lane of the persistent kernel (epoch.hip, run_ring) ----------------
+    // The cell's only work is ONE solo run in sub-cell 0 (workgroup-uniform; the schedule of the bound cell is in LDS):
+    // no general and no run steps in front of it, its records end where the cell's steps end -- the test apply() makes
+    // for the early post -- and every other sub-cell is empty.
+    __device__ __forceinline__ bool lone_solo_only() const {
+        if constexpr (NH > 0 && kAsmLoops && W * W <= 64) {
+            const uint2 sd = lsub[lane < W * W ? lane : 0];
+            const int nsolo = (int)(sd.x >> 16);
+            const bool ok = lane == 0 ? (sd.x & 0xFFFFu) == 0u && sd.y == 0u && nsolo > 0 &&
+                                            (nsolo + 2 + G - 1) / G + kSoloPad + 2 == n_steps
+                                      : lane >= W * W || (sd.y == 0u && nsolo == 0);
+            return __builtin_amdgcn_ballot_w64(!ok) == 0ull;
+        } else {
+            return false;
+        }
+    }
+    // Sub-round 0 of such a cell, all waves; called behind the workgroup barrier that has the own rows and the next
+    // schedule in LDS, and with the tile's row still on its way.  The chain wave (apply wave 0) takes the row from
+    // `src` itself (lone_chain_asm); every other wave goes straight to the ONE barrier the chain wave joins on arrival
+    // and waits THERE through the tile wait -- the helper with its run decoded, but not inside its loop, whose spin
+    // bound is sized for a chain wave one step away.  Ends with the cell's W sub-round barriers, as apply() would: the
+    // other sub-cells are empty (lone_solo_only), so sub-rounds 1 .. W - 1 are their barrier and nothing else.
+    // Returns false, in every wave, if the chain wave gave up (ctl[0] is set): nothing was trained, posted or stored.
+    __device__ __forceinline__ bool lone_round0(const float lr, const float c,
+                                                const __attribute__((address_space(1))) unsigned long long* src,
+                                                const unsigned want, const __attribute__((address_space(1))) unsigned* abw,
+                                                volatile unsigned* ctl, const bool prof) {
+        const uint4* const hdr = lent + (size_t)kSoloPad * G;  // sub-cell 0 starts at step 0 and has no other steps
+        if constexpr (NH > 0 && kAsmLoops) {
+            if (wave_all == 0) {
+                const unsigned s0 = hdr->x;
+                const int nsolo = __builtin_amdgcn_readfirstlane((int)(lsub[0].x >> 16));
+                const bool post = post_at != nullptr;  // the run ends the cell (lone_solo_only): hand the row on behind it
+                const uint64_t pm = !post ? 0ull : L == 64 ? ~0ull : (1ull << (L & 63)) - 1ull;  // lane group 0
+                auto* dst = (__attribute__((address_space(1))) unsigned long long*)post_at + lig * 4;
+                const bool ok = lone_chain_asm<L>((unsigned)(uintptr_t)(lptr_t)hdr, s0, row_base(lrows, laneoff), nsolo, lr, pack_c2(c),
+                                                  src + lig * 4, want, abw, (unsigned)(uintptr_t)(lptr_t)ctl, dst, post_tag, pm,
+                                                  prof ? 1u : 0u);
+                if (!ok) return false;
+                if (post && lane == 0) *posted_flag = 1u;
+                for (int s = 0; s < W; ++s) wg_barrier();
+                return true;
+            }
+            int ns = 0;
+            const bool mine = helper && (wave + 1) % W == 0;  // apply wave 0's helper
+            if (mine) ns = __builtin_amdgcn_readfirstlane((int)(lsub[0].x >> 16));
+            wg_barrier();  // the chain wave has the row (or has given up)
+            if (ctl[0] != 0) return false;
+            if (mine && !solo_helper_asm<L>((unsigned)(uintptr_t)(lptr_t)hdr, row_base(lrows, laneoff), ns, pack_c2(c)) && fail_flag)
+                *fail_flag = 1;
+            for (int s = 0; s < W; ++s) wg_barrier();
+        }
+        return true;
     }
 
     // ---- apply the ratings out of LDS ------------------------------------------

@@ -175,6 +175,20 @@ __device__ __forceinline__ void run_ring(unsigned char* smem, float* __restrict_
     // consumer polls the granules themselves until every tag is the one it expects -- one memory round trip per
     // hop, no drain, no flag, no gather -- and nothing of an earlier round or launch can be mistaken for it.
     // Only the holder in the launch's LAST round stores the row to Q; the first round takes it from Q.
+    // THE FAST LANE.  The hop the epoch waits for is the lone tile of the heaviest item, whose cell is ONE solo run in
+    // sub-cell 0 (Cell::lone_solo_only; R > 0).  Nothing but the row's VALUE is missing while such a cell waits, so
+    // everything else happens in front of the wait (Cell::lone_round0, run_asm.hpp MFSGD_LONE_CHAIN_ASM_TEXT):
+    //   all waves    s_waitcnt vmcnt(0) + workgroup barrier: own P rows and the next schedule are in LDS; ctl[0] is looked at;
+    //   chain wave   (apply wave 0) decodes its run, prepares the post (address, tag, lane mask), reads {lr r_0, slots_1}
+    //                and p row 0, then polls the mailbox ITSELF, four granules per lane in the layout the chain loop
+    //                keeps q in (every lane group the same addresses), bounded like the poll below;
+    //   other waves  wait at ONE s_barrier -- the helper with its run decoded, outside its loop;
+    //   arrival      tag test, one ds_write_b128 of q into the row's LDS slot (for the helper, which reads it behind
+    //                s_0), that s_barrier, step 0.  Behind the last step's q' the four granule stores of the post;
+    //   giving up    the chain wave raises the abort word and ctl[0], joins the barrier, and every wave leaves behind
+    //                it as on the other path: nothing trained, posted or stored.
+    // The barriers of a cell are as many as on the other path, in every wave.  Every other cell -- R == 0, a lone tile
+    // whose run is not one solo run in sub-cell 0, W = 8 (no helpers) -- takes the path below, unchanged.
     gu64* const mbox = (gu64*)(abort_word + 4);
     const unsigned tag_hi = ctl[2] << 16;
     constexpr int KP = Cell<L, W, NH>::KP, ROWB = Cell<L, W, NH>::ROWB;
@@ -232,6 +246,13 @@ __device__ __forceinline__ void run_ring(unsigned char* smem, float* __restrict_
             pt = now;
         }
     };
+    // ... up to a stamp another part of the wave's code took (the low word of s_memtime)
+    auto mark_at = [&](int k, const unsigned now_lo) {
+        const unsigned long long now = pt + (unsigned long long)(now_lo - (unsigned)pt);
+        pacc[k] += now - pt;
+        pcur[k] = now - pt;
+        pt = now;
+    };
     if (prof) pt = __builtin_amdgcn_s_memtime();
 
     for (; it0.R < n_rounds;) {
@@ -263,81 +284,113 @@ __device__ __forceinline__ void run_ring(unsigned char* smem, float* __restrict_
 #else
         mark(0);  // drain of the previous stores + issue of the prefetch and the P gather
 #endif
-        if (R > 0 && it0.first && lone) {
-            // the tile is one row: take it from the tile's mailbox as soon as block b + 1 has posted it
-            if (cx.wave_all == 0) {
-                const unsigned tile = (unsigned)((b + R % B) % B);
-                const unsigned want = tag_hi | (unsigned)R;  // posted in round R - 1
-                const gu64* src = mbox + (size_t)tile * KP + cx.lane;
-                unsigned long long v[NGR];
-                unsigned spins = 0;
-                for (;;) {
-                    bool ok = true;
-#pragma unroll
-                    for (int j = 0; j < NGR; ++j) {
-                        v[j] = __hip_atomic_load(src + 64 * j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        ok = ok && (unsigned)(v[j] >> 32) == want;
-                    }
-                    if (__builtin_amdgcn_ballot_w64(!ok) == 0ull) break;
-                    __builtin_amdgcn_s_sleep(1);
-                    if ((++spins & 255u) == 0u) {
-                        if (__hip_atomic_load((gu32*)abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ||
-                            spins > (1u << 22)) {
-                            if (cx.lane == 0) {
-                                __hip_atomic_store((gu32*)abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                ctl[0] = 1;
-                            }
-                            break;
-                        }
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < NGR; ++j)
-                    *reinterpret_cast<unsigned*>(cx.lrows + (size_t)cx.nu * ROWB + (size_t)(cx.lane + 64 * j) * 4) = (unsigned)v[j];
-            }
-        } else if (R > 0 && it0.first) {
-            // wait until block b + 1 has finished round R - 1 (it held our tile)
-            if (cx.tid == 0) {
-                wait_flag((gu32*)(done + (size_t)((b + 1) % B) * kFlagStride), (unsigned)R, abort_word, ctl);
-            }
-        }
-        mark(1);  // waiting for the tile (wave 0)
-        const bool from_mbox = lone && R > 0;  // the tile's row is in LDS already (wave 0 put it there)
-        // (Waiting for the own rows in front of this barrier and dropping the second one for a row that came from its
-        // mailbox -- one barrier less on the hop the epoch waits for -- was measured: 4.00 against 3.97 ms per epoch
-        // on the same box, three runs each; the second barrier stays.)
-        wg_barrier();
-        mark(2);  // the other waves' arrival
-        if (ctl[0] != 0) {  // uniform: some workgroup timed out (or a solo helper of this one gave up)
-            if (cx.tid == 0) __hip_atomic_store((gu32*)abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            return;
-        }
-        if (work && !from_mbox) cx.template gather<true>(P, Q, cx.nu, cx.nrows);  // the tile's q rows, sc1: stored by another CU
-        if (work) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // rows (and the prefetched schedule) have landed
+        // The fast lane of the hop the epoch waits for (protocol: the comment above run_ring): a lone-tile cell whose only
+        // work is ONE solo run takes everything that does not depend on the row's VALUE in front of the wait for it.
+        const bool fast = R > 0 && it0.first && lone && cx.lone_solo_only();  // uniform
+        if (fast) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // own rows (and the prefetched schedule) have landed
             wg_barrier();
-            mark(3);  // tile rows (and own rows, and the next schedule) landed
-            double acc = 0.0;
-            if (lone && R + 1 < n_rounds) {
-                cx.post_at = (unsigned long long*)(abort_word + 4) + (size_t)((b + R % B) % B) * KP;  // the tile's mailbox
+            mark(2);  // the other waves' arrival
+            if (ctl[0] != 0) {  // uniform: a solo helper of this workgroup gave up in the previous cell
+                if (cx.tid == 0) __hip_atomic_store((gu32*)abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                return;
+            }
+            const unsigned tile = (unsigned)((b + R % B) % B);
+            if (R + 1 < n_rounds) {
+                cx.post_at = (unsigned long long*)(mbox + (size_t)tile * KP);  // the tile's mailbox
                 cx.post_tag = tag_hi | (unsigned)(R + 1);
             } else {
                 cx.post_at = nullptr;
             }
-            cx.template apply<true>(lr, c, acc);  // ends with a workgroup barrier
-            mark(4);  // the ratings
-            // write-through even when more chunks of this cell follow: item rows that no later
-            // chunk touches have to be visible to the next workgroup all the same
-            if (lone && R + 1 < n_rounds) {
-                // post the row for block b - 1 (round R + 1); Q gets it from the holder in the last round
-                // (unless the chain wave has posted it from its registers already, Cell::post_at)
-                if (cx.wave_all == 0 && ctl[3] == 0u) {
+            // every wave but the chain wave waits inside for the row, at the barrier the chain wave joins on arrival; the
+            // run and the cell's sub-round barriers follow inside too
+            if (!cx.lone_round0(lr, c, mbox + (size_t)tile * KP, tag_hi | (unsigned)R, (gu32*)abort_word, ctl, prof != nullptr))
+                return;  // uniform: the row never came (abort word and ctl[0] are set); nothing has been stored
+            if (prof) {
+                const unsigned arrived = ctl[1];  // the chain wave's stamp (this thread's own wave: tid 0 books)
+                mark_at(1, arrived);  // waiting for the tile
+                mark_at(3, arrived);  // (nothing is gathered)
+            }
+            mark(4);  // the ratings, from the row's arrival
+            // posted by the chain wave; in the launch's last round the row goes to Q from its LDS slot (the helper's store)
+            if (R + 1 >= n_rounds) cx.template scatter<true>(P, Q, cx.nu, cx.nrows);
+        } else {
+            if (R > 0 && it0.first && lone) {
+                // the tile is one row: take it from the tile's mailbox as soon as block b + 1 has posted it
+                if (cx.wave_all == 0) {
                     const unsigned tile = (unsigned)((b + R % B) % B);
-                    const unsigned long long tag = (unsigned long long)(tag_hi | (unsigned)(R + 1)) << 32;
-                    post_row<NGR>(mbox + (size_t)tile * KP + cx.lane, tag, cx.lane, cx.lrows + (size_t)cx.nu * ROWB);
+                    const unsigned want = tag_hi | (unsigned)R;  // posted in round R - 1
+                    const gu64* src = mbox + (size_t)tile * KP + cx.lane;
+                    unsigned long long v[NGR];
+                    unsigned spins = 0;
+                    for (;;) {
+                        bool ok = true;
+#pragma unroll
+                        for (int j = 0; j < NGR; ++j) {
+                            v[j] = __hip_atomic_load(src + 64 * j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            ok = ok && (unsigned)(v[j] >> 32) == want;
+                        }
+                        if (__builtin_amdgcn_ballot_w64(!ok) == 0ull) break;
+                        __builtin_amdgcn_s_sleep(1);
+                        if ((++spins & 255u) == 0u) {
+                            if (__hip_atomic_load((gu32*)abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ||
+                                spins > (1u << 22)) {
+                                if (cx.lane == 0) {
+                                    __hip_atomic_store((gu32*)abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                    ctl[0] = 1;
+                                }
+                                break;
+                            }
+                        }
+                    }
+#pragma unroll
+                    for (int j = 0; j < NGR; ++j)
+                        *reinterpret_cast<unsigned*>(cx.lrows + (size_t)cx.nu * ROWB + (size_t)(cx.lane + 64 * j) * 4) = (unsigned)v[j];
                 }
-            } else {
-                cx.template scatter<true>(P, Q, cx.nu, cx.nrows);
+            } else if (R > 0 && it0.first) {
+                // wait until block b + 1 has finished round R - 1 (it held our tile)
+                if (cx.tid == 0) {
+                    wait_flag((gu32*)(done + (size_t)((b + 1) % B) * kFlagStride), (unsigned)R, abort_word, ctl);
+                }
+            }
+            mark(1);  // waiting for the tile (wave 0)
+            const bool from_mbox = lone && R > 0;  // the tile's row is in LDS already (wave 0 put it there)
+            // (Waiting for the own rows in front of this barrier and dropping the second one for a row that came from its
+            // mailbox -- one barrier less on the hop the epoch waits for -- was measured: 4.00 against 3.97 ms per epoch
+            // on the same box, three runs each; the second barrier stays.)
+            wg_barrier();
+            mark(2);  // the other waves' arrival
+            if (ctl[0] != 0) {  // uniform: some workgroup timed out (or a solo helper of this one gave up)
+                if (cx.tid == 0) __hip_atomic_store((gu32*)abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                return;
+            }
+            if (work && !from_mbox) cx.template gather<true>(P, Q, cx.nu, cx.nrows);  // the tile's q rows, sc1: stored by another CU
+            if (work) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // rows (and the prefetched schedule) have landed
+                wg_barrier();
+                mark(3);  // tile rows (and own rows, and the next schedule) landed
+                double acc = 0.0;
+                if (lone && R + 1 < n_rounds) {
+                    cx.post_at = (unsigned long long*)(abort_word + 4) + (size_t)((b + R % B) % B) * KP;  // the tile's mailbox
+                    cx.post_tag = tag_hi | (unsigned)(R + 1);
+                } else {
+                    cx.post_at = nullptr;
+                }
+                cx.template apply<true>(lr, c, acc);  // ends with a workgroup barrier
+                mark(4);  // the ratings
+                // write-through even when more chunks of this cell follow: item rows that no later
+                // chunk touches have to be visible to the next workgroup all the same
+                if (lone && R + 1 < n_rounds) {
+                    // post the row for block b - 1 (round R + 1); Q gets it from the holder in the last round
+                    // (unless the chain wave has posted it from its registers already, Cell::post_at)
+                    if (cx.wave_all == 0 && ctl[3] == 0u) {
+                        const unsigned tile = (unsigned)((b + R % B) % B);
+                        const unsigned long long tag = (unsigned long long)(tag_hi | (unsigned)(R + 1)) << 32;
+                        post_row<NGR>(mbox + (size_t)tile * KP + cx.lane, tag, cx.lane, cx.lrows + (size_t)cx.nu * ROWB);
+                    }
+                } else {
+                    cx.template scatter<true>(P, Q, cx.nu, cx.nrows);
+                }
             }
         }
         // publish the tile: every storing wave drains, then one lane signals

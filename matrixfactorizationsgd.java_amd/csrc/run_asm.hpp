@@ -378,19 +378,9 @@ static_assert(mfsgd_chain_steady() % 2 == 0 && mfsgd_chain_steady() >= 2 && mfsg
         EXIT_A \
         MFSGD_SOLO_CHAIN_HALF("108", "109", "110", "111", "104", "105", "106", "107", "118", "119", "116:117", "offset0:10+8*\\j offset1:8+8*\\j", "0", "128", "129", GAP_B, EXTRA, SFMA) \
         "ds_write2_b32 v138, v130, v128 offset0:1+8*\\j offset1:5+8*\\j\n\t"
-#define MFSGD_SOLO_CHAIN_ASM_TEXT(EXTRA, SFMA) \
-        "v_mov_b32 v138, %[ea]\n\t" \
-        "v_mov_b32 v131, %[lr]\n\t" \
-        "v_mov_b32 v139, %[rb]\n\t" \
-        "ds_read2_b32 v[116:117], v138 offset0:6 offset1:4\n\t" \
-        "v_mad_u32_u16 v113, %[s0], 16, v139\n\t" \
-        "v_bfe_u32 v133, %[s0], 16, 15\n\t" \
-        "ds_read_b128 v[104:107], v113\n\t" \
-        "v_lshl_add_u32 v133, v133, 4, v139\n\t" \
-        "ds_read_b128 v[100:103], v133\n\t" \
-        "ds_write_b32 v138, %[s0]\n\t" \
-        "v_add_u32 v138, 16, v138\n\t" \
-        "s_cmp_lt_u32 %[n], %c[steady]\n\t" \
+// (The two bodies and the tail's "post s alone" exits are a macro of their own: MFSGD_LONE_CHAIN_ASM_TEXT below enters the
+// same text from a second prologue.  Entered with scc = "n < P" tested; left at the label 3 that follows it.)
+#define MFSGD_SOLO_CHAIN_BODIES(EXTRA, SFMA) \
         "s_cbranch_scc1 1f\n\t" \
         MFSGD_LOOP_ALIGN_STEADY \
         "5:\n\t" \
@@ -425,7 +415,22 @@ static_assert(mfsgd_chain_steady() % 2 == 0 && mfsgd_chain_steady() >= 2 && mfsg
         "s_branch 3f\n\t" \
         ".endif\n\t" \
         ".endif\n\t" \
-        ".endr\n\t" \
+        ".endr\n\t"
+
+#define MFSGD_SOLO_CHAIN_ASM_TEXT(EXTRA, SFMA) \
+        "v_mov_b32 v138, %[ea]\n\t" \
+        "v_mov_b32 v131, %[lr]\n\t" \
+        "v_mov_b32 v139, %[rb]\n\t" \
+        "ds_read2_b32 v[116:117], v138 offset0:6 offset1:4\n\t" \
+        "v_mad_u32_u16 v113, %[s0], 16, v139\n\t" \
+        "v_bfe_u32 v133, %[s0], 16, 15\n\t" \
+        "ds_read_b128 v[104:107], v113\n\t" \
+        "v_lshl_add_u32 v133, v133, 4, v139\n\t" \
+        "ds_read_b128 v[100:103], v133\n\t" \
+        "ds_write_b32 v138, %[s0]\n\t" \
+        "v_add_u32 v138, 16, v138\n\t" \
+        "s_cmp_lt_u32 %[n], %c[steady]\n\t" \
+        MFSGD_SOLO_CHAIN_BODIES(EXTRA, SFMA) \
         "3:\n\t" \
         "s_waitcnt lgkmcnt(0)\n\t" \
         "v_mov_b32 %[q0], v100\n\t" \
@@ -441,6 +446,126 @@ static_assert(mfsgd_chain_steady() % 2 == 0 && mfsgd_chain_steady() >= 2 && mfsg
     : "memory", "scc", "vcc", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", \
       "v113", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v128", "v129", "v130",  \
       "v131", "v132", "v133", "v138", "v139"
+
+// ---- chain wave of a LONE-TILE cell: the row comes out of its mailbox straight into the loop ----------------------
+// The persistent kernel's fast lane (epoch.hip, run_ring): the cell is ONE solo run, and its q row
+// arrives from another workgroup as 4 L granules {value, tag} in global memory.  This is MFSGD_SOLO_CHAIN_ASM_TEXT
+// with a second prologue and a second epilogue around the same bodies, and the wait for the row between the halves of
+// the prologue:
+//   before the wait   v138 / v131 / v139 as above; {lr*r_0, slots_1} and p row 0 read and WAITED for; the q row's LDS
+//                     address in v133; the tags of the post in the odd registers of v[150:157];
+//   the wait          every lane loads granules 4 lig .. 4 lig + 3 (8 bytes each, sc1: what the compiler emits for a
+//                     relaxed agent-scope atomic load) -- every lane group the same addresses, so all hold the same q --
+//                     value of granule j into v100 / v142 / v144 / v146, its tag beside it; every lane tests its four
+//                     tags against %[want]; one vcc test for the wave.  A miss: s_sleep 1, and every 256th the abort
+//                     word (%[abw]) and the bound of 2^22 polls;
+//   arrival           three moves complete q in v[100:103]; ONE ds_write_b128 puts it into the row's LDS slot for the
+//                     helper (which reads it only behind s_0, and this wave's LDS operations complete in order: no wait)
+//                     and is the "one LDS write behind the reads" the bodies' counted waits expect; ONE s_barrier, at
+//                     which the other waves of the workgroup have been waiting; then the bodies.  No VMEM is outstanding.
+//   the post          straight behind the last step's q': four moves pair the values with the tags, four 8-byte sc1
+//                     stores under the exec mask %[pm] (lanes 0 .. L - 1, or none when the row is not handed on).
+//   giving up         (abort word set, or the bound): lane 0 raises the abort word and the LDS word at %[ctl], both are
+//                     waited for, the wave joins the barrier and leaves with %[gave] = 1: nothing trained or posted.
+// %[prof] != 0 (diagnostic launches): the low word of s_memtime at arrival goes to the LDS word at %[ctl] + 4.
+// n >= 1 steps; %[src] / %[dst]: this lane's first granule of the mailbox taken from / posted to.
+// (-DMFSGD_LONE_POLL_NO_SLEEP: the poll without its s_sleep 1, a build for the A/B of DESIGN.md section 5 only)
+#ifdef MFSGD_LONE_POLL_NO_SLEEP
+#define MFSGD_LONE_POLL_SLEEP ""
+#else
+#define MFSGD_LONE_POLL_SLEEP "s_sleep 1\n\t"
+#endif
+#define MFSGD_LONE_CHAIN_ASM_TEXT(EXTRA, SFMA) \
+        "v_mov_b32 v138, %[ea]\n\t" \
+        "v_mov_b32 v131, %[lr]\n\t" \
+        "v_mov_b32 v139, %[rb]\n\t" \
+        "ds_read2_b32 v[116:117], v138 offset0:6 offset1:4\n\t" \
+        "v_mad_u32_u16 v113, %[s0], 16, v139\n\t" \
+        "v_bfe_u32 v133, %[s0], 16, 15\n\t" \
+        "ds_read_b128 v[104:107], v113\n\t" \
+        "v_lshl_add_u32 v133, v133, 4, v139\n\t" \
+        "v_add_u32 v138, 16, v138\n\t" \
+        "v_mov_b32 v151, %[ptag]\n\t" \
+        "v_mov_b32 v153, %[ptag]\n\t" \
+        "v_mov_b32 v155, %[ptag]\n\t" \
+        "v_mov_b32 v157, %[ptag]\n\t" \
+        "v_mov_b32 v149, 0\n\t" \
+        "s_waitcnt lgkmcnt(0)\n\t" \
+        "60:\n\t" \
+        "global_load_dwordx2 v[100:101], %[src], off sc1\n\t" \
+        "global_load_dwordx2 v[142:143], %[src], off offset:8 sc1\n\t" \
+        "global_load_dwordx2 v[144:145], %[src], off offset:16 sc1\n\t" \
+        "global_load_dwordx2 v[146:147], %[src], off offset:24 sc1\n\t" \
+        "s_waitcnt vmcnt(0)\n\t" \
+        "v_xor_b32 v101, %[want], v101\n\t" \
+        "v_xor_b32 v143, %[want], v143\n\t" \
+        "v_xor_b32 v145, %[want], v145\n\t" \
+        "v_xor_b32 v147, %[want], v147\n\t" \
+        "v_or3_b32 v101, v101, v143, v145\n\t" \
+        "v_or_b32 v101, v101, v147\n\t" \
+        "v_cmp_ne_u32 vcc, 0, v101\n\t" \
+        "s_cbranch_vccz 62f\n\t" \
+        MFSGD_LONE_POLL_SLEEP \
+        "s_add_u32 %[spins], %[spins], 1\n\t" \
+        "s_and_b32 %[t0], %[spins], 0xff\n\t" \
+        "s_cbranch_scc1 60b\n\t" \
+        "global_load_dword v148, v149, %[abw] sc1\n\t" \
+        "s_waitcnt vmcnt(0)\n\t" \
+        "v_readfirstlane_b32 %[t0], v148\n\t" \
+        "s_cmp_lg_u32 %[t0], 0\n\t" \
+        "s_cbranch_scc1 61f\n\t" \
+        "s_cmp_le_u32 %[spins], 0x400000\n\t" \
+        "s_cbranch_scc1 60b\n\t" \
+        "61:\n\t" \
+        "v_mov_b32 v148, 1\n\t" \
+        "s_mov_b64 %[tmp], exec\n\t" \
+        "s_mov_b64 exec, 1\n\t" \
+        "global_store_dword v149, v148, %[abw] sc1\n\t" \
+        "ds_write_b32 %[ctl], v148\n\t" \
+        "s_mov_b64 exec, %[tmp]\n\t" \
+        "s_mov_b32 %[gave], 1\n\t" \
+        "s_waitcnt vmcnt(0) lgkmcnt(0)\n\t" \
+        "s_barrier\n\t" \
+        "s_branch 69f\n\t" \
+        "62:\n\t" \
+        "v_mov_b32 v101, v142\n\t" \
+        "v_mov_b32 v102, v144\n\t" \
+        "v_mov_b32 v103, v146\n\t" \
+        "s_cmp_eq_u32 %[prof], 0\n\t" \
+        "s_cbranch_scc1 63f\n\t" \
+        "s_memtime %[tmp]\n\t" \
+        "s_waitcnt lgkmcnt(0)\n\t" \
+        "v_mov_b64 v[158:159], %[tmp]\n\t" \
+        "ds_write_b32 %[ctl], v158 offset:4\n\t" \
+        "63:\n\t" \
+        "s_cmp_lt_u32 %[n], %c[steady]\n\t" \
+        "ds_write_b128 v133, v[100:103]\n\t" \
+        "s_barrier\n\t" \
+        MFSGD_SOLO_CHAIN_BODIES(EXTRA, SFMA) \
+        "3:\n\t" \
+        "v_mov_b32 v150, v100\n\t" \
+        "v_mov_b32 v152, v101\n\t" \
+        "v_mov_b32 v154, v102\n\t" \
+        "v_mov_b32 v156, v103\n\t" \
+        "s_and_saveexec_b64 %[tmp], %[pm]\n\t" \
+        "global_store_dwordx2 %[dst], v[150:151], off sc1\n\t" \
+        "global_store_dwordx2 %[dst], v[152:153], off offset:8 sc1\n\t" \
+        "global_store_dwordx2 %[dst], v[154:155], off offset:16 sc1\n\t" \
+        "global_store_dwordx2 %[dst], v[156:157], off offset:24 sc1\n\t" \
+        "s_mov_b64 exec, %[tmp]\n\t" \
+        "69:\n\t" \
+        "s_waitcnt lgkmcnt(0)\n\t"
+
+#define MFSGD_LONE_CHAIN_OPERANDS                                                                                      \
+    : [n] "+s"(n), [spins] "+s"(spins), [gave] "+s"(gave), [tmp] "=&s"(tmp), [t0] "=&s"(t0)                            \
+    : [ea] "v"(ea), [rb] "v"(rowbase), [s0] "v"(s0), [lr] "s"(lr), [c2] "s"(c2), [src] "v"(src), [want] "s"(want),     \
+      [abw] "s"(abw), [ctl] "v"(ctl), [dst] "v"(dst), [ptag] "s"(ptag), [pm] "s"(pm), [prof] "s"(prof),                \
+      [pad] "n"(PADV), [pads] "n"(PADS), [pairs] "n"(mfsgd_chain_pairs()), [bump] "n"(32 * mfsgd_chain_pairs()),        \
+      [steady] "n"(mfsgd_chain_steady()), [sbump] "n"(16 * mfsgd_chain_steady())                                       \
+    : "memory", "scc", "vcc", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", \
+      "v113", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v128", "v129", "v130",  \
+      "v131", "v132", "v133", "v138", "v139", "v142", "v143", "v144", "v145", "v146", "v147", "v148", "v149", "v150",  \
+      "v151", "v152", "v153", "v154", "v155", "v156", "v157", "v158", "v159"
 
 // ---- helper wave ------------------------------------------------------------------------------
 // [r3] The helper takes the steps in PAIRS, as the chain wave posts them: ONE ds_read2_b64 fetches {slots_{t+1}, s_t}

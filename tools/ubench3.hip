@@ -2,6 +2,9 @@
 // two waves on two SIMDs, wave 0 = chain wave, wave 1 = helper.  Prints cycles per step of the pair
 // (and of the chain wave alone, MODE=1: no helper, nothing stored) and compares every p row and the
 // q row with a plain host restatement of DESIGN.md section 3.
+// Modes 6 / 7 (`ubench3 lone`): the run of a lone-tile cell of the persistent kernel -- q comes out of a mailbox in global
+// memory into the chain wave's registers, p row 0 and the entry words are read in front of the wait, the helper waits at
+// the barrier the chain wave joins on arrival (MFSGD_LONE_CHAIN_ASM_TEXT); timed from the arrival stamp, beside mode 0.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -50,15 +53,24 @@ constexpr int ENT_OFF = NROWS * ROWB;          // entries behind the rows
 constexpr int GS = 64 / LG;                    // slots per step of the (old) run loop
 constexpr int RUN_OFF = ENT_OFF + (NSTEP + 2) * 16;  // mode 3: run-loop entries, NSTEP + 2 steps x GS x 16 bytes
 constexpr int EXTRA_ZERO = NROWS;              // (mode 3 idle slots use the zero row too)
+constexpr int CTL_OFF = RUN_OFF + (NSTEP + 2) * GS * 16;  // modes 6 / 7: control block ([0] abort broadcast, [1] arrival stamp)
+using gu64 = __attribute__((address_space(1))) unsigned long long;
+using gu32 = __attribute__((address_space(1))) unsigned;
 
 __global__ void __launch_bounds__(192) k(const float* rows_in, const uint32_t* ent_in, float* rows_out, uint32_t* ent_out,
                                          unsigned long long* cyc, int n_steps, float lr, float c, int mode,
-                                         const uint32_t* run_in, int first_row) {
+                                         const uint32_t* run_in, int first_row, const unsigned long long* mbox,
+                                         unsigned* abort_word, unsigned long long* post_box, unsigned want_tag) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     for (int x = threadIdx.x; x < NROWS * ROWB / 4; x += blockDim.x) ((float*)smem)[x] = rows_in[x];
     for (int x = threadIdx.x; x < (NSTEP + 2) * 4; x += blockDim.x) ((uint32_t*)(smem + ENT_OFF))[x] = ent_in[x];
     for (int x = threadIdx.x; x < (NSTEP + 2) * GS * 4; x += blockDim.x) ((uint32_t*)(smem + RUN_OFF))[x] = run_in[x];
+    if (threadIdx.x < 4) ((uint32_t*)(smem + CTL_OFF))[threadIdx.x] = 0u;
     __syncthreads();
+    if (mode >= 6) {  // the q row is NOT in LDS: it comes out of the mailbox
+        for (int x = threadIdx.x; x < ROWB / 4; x += blockDim.x) ((float*)(smem + NSTEP * ROWB))[x] = -7.0f;
+        __syncthreads();
+    }
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const unsigned rowbase = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)smem + (lane % LG) * 16;
     const unsigned ea = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(smem + ENT_OFF);
@@ -96,6 +108,37 @@ __global__ void __launch_bounds__(192) k(const float* rows_in, const uint32_t* e
             const unsigned s0 = *(const uint32_t*)(smem + ENT_OFF + m * 16);  // entry m - 1 serves as the second half's header
             n = n_steps - m;
             asm volatile(MFSGD_SOLO_CHAIN_ASM_TEXT(EXTRA_SOLO, SFMA2) MFSGD_SOLO_CHAIN_OPERANDS);
+        }
+    } else if (mode >= 6) {
+        const unsigned ctl = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(smem + CTL_OFF);
+        if (wave == 0) {
+            typedef float f4 __attribute__((ext_vector_type(4)));
+            if (mode == 7) {  // mode 5's case: the p row of step 0 updated in front of the run (here: in front of its early read)
+                f4* p0 = (f4*)(smem + first_row * ROWB + (lane % LG) * 16);
+                f4 v = *p0;
+                v += 1.0f;
+                *p0 = v;
+            }
+            const unsigned s0 = *(const uint32_t*)(smem + ENT_OFF);
+            const gu64* src = (const gu64*)mbox + (lane % LG) * 4;
+            gu64* dst = (gu64*)post_box + (lane % LG) * 4;
+            const gu32* abw = (const gu32*)abort_word;
+            const unsigned want = (unsigned)__builtin_amdgcn_readfirstlane((int)want_tag), ptag = want + 1u, prof = 1u;
+            const uint64_t pm = LG == 64 ? ~0ull : (1ull << (LG & 63)) - 1ull;
+            unsigned spins = 0, gave = 0, t0;
+            uint64_t tmp;
+            constexpr int PADV = mfsgd_pad_chain_tail(LG), PADS = mfsgd_pad_chain_steady(LG);
+            asm volatile(MFSGD_LONE_CHAIN_ASM_TEXT(EXTRA_SOLO, SFMA2) MFSGD_LONE_CHAIN_OPERANDS);
+            if (gave && lane == 0) cyc[2] = 2;
+        } else if (wave == 1) {
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            if (*(volatile uint32_t*)(smem + CTL_OFF) == 0u) {
+                int spins = 1 << 20, fin = 1;
+                asm volatile("" : "+s"(fin));
+                constexpr int PADV = mfsgd_pad_helper(LG);
+                asm volatile(MFSGD_SOLO_HELPER_ASM_TEXT MFSGD_SOLO_HELPER_OPERANDS);
+                if (spins == 0 && lane == 0) cyc[2] = 1;
+            }
         }
     } else if (wave == 0 && mode != 2) {
         typedef float f4 __attribute__((ext_vector_type(4)));
@@ -136,6 +179,7 @@ __global__ void __launch_bounds__(192) k(const float* rows_in, const uint32_t* e
         if (spins == 0 && lane == 0) cyc[2] = 1;
     }
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t1)::"memory");
+    if (mode >= 6) t0 = t1 - (unsigned long long)((unsigned)t1 - ((volatile uint32_t*)(smem + CTL_OFF))[1]);  // from the row's arrival
     if (lane == 0) cyc[wave == 2 ? 3 : wave] = t1 - t0;
     __syncthreads();
     for (int x = threadIdx.x; x < NROWS * ROWB / 4; x += blockDim.x) rows_out[x] = ((float*)smem)[x];
@@ -165,8 +209,9 @@ static float ref_dot(const float* p, const float* q) {
 //                    -DMFSGD_CHAIN_PAIRS=1|2|4: tools/build_ubench.sh); one line per n, the short runs as one line
 int main(int argc, char** argv) {
     const bool chain_only = argc > 1 && strcmp(argv[1], "chain") == 0;
+    const bool lone_only = argc > 1 && strcmp(argv[1], "lone") == 0;
     std::vector<int> lengths = {NSTEP, NSTEP - 1, 1, 2, 50, 51};
-    if (chain_only)
+    if (chain_only || lone_only)
         for (int n = 3; n <= 33; ++n) lengths.push_back(n);
     const int KP = 4 * LG;
     std::vector<float> rows((size_t)NROWS * KP), ref;
@@ -216,7 +261,22 @@ int main(int argc, char** argv) {
     (void)hipMalloc(&d_cyc, 32);
     (void)hipMemcpy(d_in, rows.data(), rows.size() * 4, hipMemcpyHostToDevice);
     (void)hipMemcpy(d_ent, ent.data(), ent.size() * 4, hipMemcpyHostToDevice);
-    const size_t lds = (size_t)NROWS * ROWB + (NSTEP + 2) * 16 + (size_t)(NSTEP + 2) * GS * 16;
+    const size_t lds = (size_t)NROWS * ROWB + (NSTEP + 2) * 16 + (size_t)(NSTEP + 2) * GS * 16 + 16;
+    // modes 6 / 7: the q row as its mailbox holds it ({value, tag} granules), the abort word, the mailbox it is posted to
+    const unsigned want_tag = (5u << 16) | 3u;
+    std::vector<unsigned long long> mb(KP), posted(KP);
+    for (int f = 0; f < KP; ++f) {
+        uint32_t bits;
+        memcpy(&bits, &rows[(size_t)NSTEP * KP + f], 4);
+        mb[f] = ((unsigned long long)want_tag << 32) | bits;
+    }
+    unsigned long long *d_mb, *d_post;
+    unsigned* d_abw;
+    (void)hipMalloc(&d_mb, KP * 8);
+    (void)hipMalloc(&d_post, KP * 8);
+    (void)hipMalloc(&d_abw, 4);
+    (void)hipMemcpy(d_mb, mb.data(), KP * 8, hipMemcpyHostToDevice);
+    (void)hipMemset(d_abw, 0, 4);
     (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     // mode 2: mailboxes pre-filled with the reference's s_t -> the helper's own pace
     std::vector<uint32_t> ent2 = ent;
@@ -255,18 +315,22 @@ int main(int argc, char** argv) {
     (void)hipMalloc(&d_run, run.size() * 4);
     (void)hipMemcpy(d_run, run.data(), run.size() * 4, hipMemcpyHostToDevice);
     struct Res { double chain, helper; int bad; };
-    std::vector<Res> res[2] = {std::vector<Res>(NSTEP + 1), std::vector<Res>(NSTEP + 1)};
-    for (int mode = 0; mode < (chain_only ? 2 : 6); ++mode)
+    std::vector<Res> res[8];
+    for (auto& v : res) v.resize(NSTEP + 1);
+    for (int mode = 0; mode < (chain_only ? 2 : 8); ++mode)
         for (int n : lengths) {
             if ((mode == 3 && (n & 1)) || (mode == 4 && n < 8)) continue;
+            if (lone_only ? (mode != 0 && mode < 6) : (!chain_only && mode >= 6 && n > 2 && n < 50)) continue;
             (void)hipMemcpy(d_ent, (mode == 2 ? ent2 : ent).data(), ent.size() * 4, hipMemcpyHostToDevice);
             unsigned long long best[2] = {~0ull, ~0ull}, h[4];
             std::vector<float> out(rows.size());
             for (int rep = 0; rep < 5; ++rep) {
                 (void)hipMemset(d_cyc, 0, 32);
-                hipLaunchKernelGGL(k, dim3(1), dim3(mode == 4 ? 192 : 128), lds, 0, d_in, d_ent, d_out, d_ent_out, d_cyc, n, lr, c, mode, d_run, prow[0]);
+                (void)hipMemset(d_post, 0, KP * 8);
+                hipLaunchKernelGGL(k, dim3(1), dim3(mode == 4 ? 192 : 128), lds, 0, d_in, d_ent, d_out, d_ent_out, d_cyc, n, lr, c, mode, d_run, prow[0],
+                                   d_mb, d_abw, d_post, want_tag);
                 (void)hipMemcpy(h, d_cyc, 32, hipMemcpyDeviceToHost);
-                if (h[2]) printf("helper gave up!\n");
+                if (h[2]) puts(h[2] == 2 ? "chain wave gave up!" : "helper gave up!");
                 if (mode == 4 && h[3] > h[1]) h[1] = h[3];  // cut run: the later of the two helpers
                 for (int w = 0; w < 2; ++w) best[w] = h[w] < best[w] ? h[w] : best[w];
             }
@@ -274,7 +338,7 @@ int main(int argc, char** argv) {
             int bad = 0;
             if (mode != 1) {  // the reference for n steps (mode 0: p row of step 0 was updated in front of the run)
                 std::vector<float> r2 = rows;
-                if (mode == 5)
+                if (mode == 5 || mode == 7)
                     for (int f = 0; f < KP; ++f) r2[(size_t)prow[0] * KP + f] += 1.0f;
                 float* qq = &r2[(size_t)NSTEP * KP];
                 for (int t = 0; t < n; ++t) {
@@ -287,13 +351,21 @@ int main(int argc, char** argv) {
                     }
                 }
                 bad = memcmp(out.data(), r2.data(), out.size() * 4) != 0;
+                if (mode >= 6) {  // ... and the row as it was posted: {q after n steps, tag + 1}
+                    (void)hipMemcpy(posted.data(), d_post, KP * 8, hipMemcpyDeviceToHost);
+                    for (int f = 0; f < KP; ++f) {
+                        uint32_t bits;
+                        memcpy(&bits, &qq[f], 4);
+                        bad |= posted[f] != (((unsigned long long)(want_tag + 1u) << 32) | bits);
+                    }
+                }
             }
-            if (chain_only) {  // one line per n below
+            if (chain_only || lone_only) {  // one line per n below
                 res[mode][n] = {(double)best[0], (double)best[1], bad};
                 continue;
             }
             printf("L=%d mode=%d (%s) n=%d: chain %.1f cycles/step, helper %.1f cycles/step%s\n", LG, mode,
-                   mode == 1 ? "chain alone" : mode == 4 ? "cut run: chain + two helpers" : mode == 2 ? "helper alone" : mode == 3 ? "one-wave run loop" : mode == 5 ? "chain + helper, p row of step 0 updated in front of the run" : "chain + helper", n, (double)best[0] / n, (double)best[1] / n,
+                   mode == 1 ? "chain alone" : mode == 6 ? "lone-tile start: q from its mailbox in registers, chain + helper, from arrival" : mode == 7 ? "lone-tile start, p row of step 0 updated in front of the run" : mode == 4 ? "cut run: chain + two helpers" : mode == 2 ? "helper alone" : mode == 3 ? "one-wave run loop" : mode == 5 ? "chain + helper, p row of step 0 updated in front of the run" : "chain + helper", n, (double)best[0] / n, (double)best[1] / n,
                    mode == 1 ? "" : (bad ? "  MISMATCH" : "  bit-exact"));
         }
     if (chain_only) {
@@ -309,6 +381,22 @@ int main(int argc, char** argv) {
                mfsgd_chain_steady(), mfsgd_chain_pairs(), mfsgd_pad_chain_steady(LG), mfsgd_pad_chain_tail(LG), exact, wrong);
         for (int n : {7, 8, 9, 15, 16, 17, 31, 32, 33}) printf(" %.0f", res[1][n].chain);
         printf("\n");
+    }
+    if (lone_only) {
+        // whole-run cycles (the later of the two waves / the chain wave), LDS start (mode 0) beside the lone-tile start (mode 6)
+        int exact = 0, wrong = 0;
+        for (int n = 1; n <= 33; ++n) {
+            (res[6][n].bad ? wrong : exact)++;
+            (res[7][n].bad ? wrong : exact)++;
+        }
+        for (int n : {1, 2, 50, 51, NSTEP - 1, NSTEP}) {
+            const Res &a = res[0][n], &b = res[6][n];
+            printf("L=%d lone n=%d: cycles per run, pair / chain wave: LDS start %.0f / %.0f, lone-tile start %.0f / %.0f (%+.0f / %+.0f)%s\n", LG, n,
+                   a.helper > a.chain ? a.helper : a.chain, a.chain, b.helper > b.chain ? b.helper : b.chain, b.chain,
+                   (b.helper > b.chain ? b.helper : b.chain) - (a.helper > a.chain ? a.helper : a.chain), b.chain - a.chain,
+                   a.bad || b.bad || res[7][n].bad ? "  MISMATCH" : "  bit-exact");
+        }
+        printf("L=%d lone n=1..33, modes 6 and 7: %d bit-exact, %d MISMATCH\n", LG, exact, wrong);
     }
     return 0;
 }
