@@ -129,7 +129,21 @@ int mfsgd_set_ratings(mfsgd_handle* h, const int32_t* u, const int32_t* i, const
  * Host layout is dense row-major: P is n_users x k, Q is n_items x k.
  * init: java.util.Random(seed).nextFloat() * (float)(1/sqrt(k)), P then Q.
  * With n_parts > 1 only P (and nothing of Q) lives in the handle: Q travels
- * in caller-owned device blocks (mfsgd_part_* below); pass Q = NULL here.    */
+ * in caller-owned device blocks (mfsgd_part_* below); pass Q = NULL here.
+ * NaN: which entries are NaN is kept, a NaN's sign and payload are not.  Every
+ * NaN that enters the library -- a factor given to mfsgd_set_factors,
+ * mfsgd_load_factors or mfsgd_dsgd_set_q, a rating given to mfsgd_set_ratings
+ * (in the schedules) or mfsgd_apply_ratings -- is replaced by the quiet NaN
+ * 0x7FC00000: the training kernels use the word 0xFFFFFFFF, itself a NaN, as
+ * "not posted yet" between two of their waves, and arithmetic hands a NaN
+ * operand's payload on.  mfsgd_get_factors before any training therefore
+ * returns 0x7FC00000 where a NaN of another payload went in.
+ * Inf: overflow propagates as the arithmetic of k columns says where k is a
+ * multiple of 4 times a power of two (k == kp: 4, 8, 16, 32, 64, 128, 256).
+ * At other k a device row carries zero pad columns, and in the TRAINING
+ * kernels an infinite step size makes them NaN (Inf * 0): such a row turns NaN
+ * one step of its own earlier than the definition's, which keeps Inf there.
+ * mfsgd_apply_ratings keeps its pad columns zero and follows the definition.  */
 int mfsgd_init_factors(mfsgd_handle* h, int64_t seed);
 int mfsgd_set_factors(mfsgd_handle* h, const float* P, const float* Q);
 int mfsgd_get_factors(mfsgd_handle* h, float* P, float* Q);
@@ -530,7 +544,14 @@ int mfsgd_part_init_q(const mfsgd_handle* h, int32_t part, int64_t seed, int64_t
                       float* q_block_host);
 /* One DSGD sub-epoch: every rating of this handle's users whose item is in
  * `part`, against q_block_dev.  Asynchronous on `stream`.  Calls for different
- * partitions of ONE handle must not overlap in time: they update the same P rows. */
+ * partitions of ONE handle must not overlap in time: they update the same P rows.
+ * The block is the caller's memory and is used as it is: a NaN in it must not
+ * have all of its low 22 mantissa bits set (0x7FFFFFFF, 0xFFFFFFFF, 0x7FBFFFFF,
+ * 0xFFBFFFFF: a buffer filled with 0xFF bytes is the usual source).  Such a row
+ * in a long chain makes the launch give up ("timed out waiting for a tile
+ * hand-off", MFSGD_ERR_HIP at the next check, factors invalid).  Blocks that
+ * came from mfsgd_part_init_q, mfsgd_dsgd_set_q or a kernel of this library
+ * never hold one: the library's own NaNs are 0x7FC00000 / 0xFFC00000.          */
 int mfsgd_part_train(mfsgd_handle* h, int32_t part, float* q_block_dev, void* stream);
 /* Sum of squared errors of the same ratings (fp64), synchronous. */
 int mfsgd_part_sse(mfsgd_handle* h, int32_t part, const float* q_block_dev, void* stream,

@@ -47,6 +47,7 @@ __device__ __forceinline__ void run_loop_asm(float4& rq, const unsigned ea, cons
     static_assert(L == 16 || L == 32 || L == 64, "hand-scheduled run loop: 16, 32 or 64 lanes per rating");
     using f4 = __attribute__((ext_vector_type(4))) float;
     f4 q = {rq.x, rq.y, rq.z, rq.w};
+    uint64_t live, sv;  // the lanes of the step's live slots / the wave's exec mask (scalar temporaries of the text)
     constexpr int PADV = mfsgd_pad_run(L);
     if constexpr (L == 16)
         asm volatile(MFSGD_RUN_LOOP_ASM_TEXT("", MFSGD_SFMA_V) MFSGD_RUN_LOOP_ASM_OPERANDS);
@@ -503,22 +504,26 @@ struct Cell {
             asm volatile("" : "+v"(nxt.en.x));   // ... nor its address arithmetic (no instruction emitted)
             const float r = __builtin_bit_cast(float, TRAIN ? cur.en.z : cur.en.y);
             const float ce = __builtin_bit_cast(float, cur.en.w);
+            const bool idle = (int)cur.en.x < 0;
             nxt.pa = ((nxt.en.x & 0xFFFFu) << 4) + lo;
             const float4 pn = lds_ld(lr_, nxt.pa);
             cur.en = eptr[e2];
             __builtin_amdgcn_sched_barrier(0);  // keep the prefetch ahead of the arithmetic
             const float dot = group_allreduce<L>(chunk_dot(cur.p, rq));
             if constexpr (TRAIN) {
-                // idle slot: p = 0 and r = 0 give s == 0, and its entry carries ce = 1, so the
-                // resident row stays bit-identical (fma(0, p, 1*q) == q) and zeros are
-                // rewritten to the all-zero p row: no flag test, no select.
+                // idle slot (p = the all-zero row, r = 0, ce = 1): the resident row stays as it is and nothing is stored.
+                // Not left to fma(0, p, 1*q): a resident row that holds an Inf or a NaN makes the dot with the zero row
+                // NaN, which would turn the whole row NaN (run_asm.hpp masks the same lanes).
                 const float sc = __builtin_fmaf(-lr, dot, r);
                 const float4 p2 = axpy_row(sc, rq, ce, cur.p);
-                rq = axpy_row(sc, cur.p, ce, rq);
-                lds_st(lr_, cur.pa, p2);
-            } else {
+                const float4 q2 = axpy_row(sc, cur.p, ce, rq);
+                if (!idle) {
+                    rq = q2;
+                    lds_st(lr_, cur.pa, p2);
+                }
+            } else if (!idle) {
                 const float err = r - dot;
-                acc += (double)err * (double)err;  // idle: p row and r are zero, err == 0
+                acc += (double)err * (double)err;
             }
             nxt.p = pn;
         };

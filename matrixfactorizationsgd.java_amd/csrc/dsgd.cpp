@@ -28,6 +28,7 @@
 #include "../../include/mfsgd.h"
 #include "devmem.hpp"
 #include "guard.hpp"
+#include "records.hpp"
 #include "transport.hpp"
 
 struct mfsgd_dsgd {
@@ -188,6 +189,7 @@ int rmse(mfsgd_dsgd* d, double* out) {
 int put_block(mfsgd_dsgd* d, int j, const float* src, int32_t rows, int stride) {
     std::vector<float> host(d->count(), 0.0f);
     for (int32_t x = 0; x < rows; ++x) std::memcpy(&host[(size_t)x * d->kp], src + (size_t)x * stride, sizeof(float) * (size_t)d->k);
+    for (float& x : host) x = mfsgd::canon_nan(x);  // (records.hpp: no NaN keeps a payload of the caller's)
     DHIP(d, hipMemcpy(d->block(d->cur, j), host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
     return MFSGD_OK;
 }

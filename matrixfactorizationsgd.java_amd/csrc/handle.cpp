@@ -283,6 +283,8 @@ int mfsgd_set_factors(mfsgd_handle* h, const float* P, const float* Q) {
             h->hQ.assign((size_t)h->cfg.n_items * kp, 0.0f);
             for (int64_t x = 0; x < h->cfg.n_items; ++x) std::memcpy(&h->hQ[(size_t)x * kp], Q + x * k, sizeof(float) * (size_t)k);
         }
+        for (float& x : h->hP) x = canon_nan(x);  // (records.hpp: no NaN keeps a payload of the caller's)
+        for (float& x : h->hQ) x = canon_nan(x);
         h->have_q = h->n_parts == 1;
         h->where = mfsgd_handle::Where::Host;
         return MFSGD_OK;

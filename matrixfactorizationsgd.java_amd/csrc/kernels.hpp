@@ -62,8 +62,8 @@ hipError_t launch_fold_in(int L, const float* Q, float* rows, int k, const long 
 // else is hipErrorInvalidValue.  Every user is a row of P, every item a row of Q, and every orig an entry of err: the
 // caller checks.  Asynchronous on st.
 hipError_t launch_apply_levels(int L, float* P, float* Q, const int32_t* u, const int32_t* i, const float* r,
-                               const int32_t* orig, const int32_t* level_ptr, int l0, int l1, int workgroups, float lr,
-                               float c, float* err, hipStream_t st);
+                               const int32_t* orig, const int32_t* level_ptr, int l0, int l1, int workgroups, int k,
+                               float lr, float c, float* err, hipStream_t st);
 
 // rehyper.hip.  Re-bakes lr and c = 1 - lr*lambda into the entries of a schedule on the device, in place: afterwards
 // they are byte for byte what the packers write for those values (schedule.cpp, rehyper_schedule, is the host's form).

@@ -29,7 +29,7 @@ __global__ void __launch_bounds__(256) apply_levels_kernel(float* P, float* Q, c
                                                            const int32_t* __restrict__ i, const float* __restrict__ r,
                                                            const int32_t* __restrict__ orig,
                                                            const int32_t* __restrict__ level_ptr, const int l0, const int l1,
-                                                           const float lr, const float c, float* __restrict__ err) {
+                                                           const int k, const float lr, const float c, float* __restrict__ err) {
     constexpr int KP = 4 * L;
     constexpr int GPB = 256 / L;  // groups per block
     const int lig = threadIdx.x % L;
@@ -48,8 +48,18 @@ __global__ void __launch_bounds__(256) apply_levels_kernel(float* P, float* Q, c
             const float dot = group_allreduce<L>(chunk_dot(p, q));
             const float e = rj - dot;
             const float s = __builtin_fmaf(-lr, dot, lr * rj);
-            const float4 np = axpy_row(s, q, c, p);
-            const float4 nq = axpy_row(s, p, c, q);
+            float4 np = axpy_row(s, q, c, p);
+            float4 nq = axpy_row(s, p, c, q);
+            // the pad columns (k .. KP - 1) stay +0.0: fma(s, 0, c * 0) is +0.0 for every finite s, but NaN for an infinite
+            // one (an overflowing rating), and a NaN pad column would make every later dot of the row NaN where the k
+            // columns of the definition are infinite at most
+            const int pad_from = k - lig * 4;  // elements of this lane's chunk that are columns of the row
+            if (pad_from < 4) {
+                if (pad_from < 1) np.x = nq.x = 0.0f;
+                if (pad_from < 2) np.y = nq.y = 0.0f;
+                if (pad_from < 3) np.z = nq.z = 0.0f;
+                np.w = nq.w = 0.0f;
+            }
             if (live) {
                 *reinterpret_cast<float4*>(prow) = np;
                 *reinterpret_cast<float4*>(qrow) = nq;
@@ -67,13 +77,13 @@ __global__ void __launch_bounds__(256) apply_levels_kernel(float* P, float* Q, c
 }  // namespace
 
 hipError_t launch_apply_levels(int L, float* P, float* Q, const int32_t* u, const int32_t* i, const float* r,
-                               const int32_t* orig, const int32_t* level_ptr, int l0, int l1, int workgroups, float lr,
-                               float c, float* err, hipStream_t st) {
+                               const int32_t* orig, const int32_t* level_ptr, int l0, int l1, int workgroups, int k,
+                               float lr, float c, float* err, hipStream_t st) {
     if (l1 <= l0) return hipSuccess;
     if (workgroups < 1 || (l1 - l0 > 1 && workgroups != 1)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)workgroups), block(256);
     return with_L(L, [&](auto l) {
-        hipLaunchKernelGGL((apply_levels_kernel<l()>), grid, block, 0, st, P, Q, u, i, r, orig, level_ptr, l0, l1, lr, c, err);
+        hipLaunchKernelGGL((apply_levels_kernel<l()>), grid, block, 0, st, P, Q, u, i, r, orig, level_ptr, l0, l1, k, lr, c, err);
         return hipGetLastError();
     });
 }

@@ -207,8 +207,8 @@ __global__ void __launch_bounds__(64 * kWaves) pack_kernel(const PackArgs a) {
     auto put_entry = [&](unsigned step, int g, unsigned slots, float r, float ce) {
         Entry e;
         e.slots = slots;
-        e.r = r;
-        e.lrr = lr * r;
+        e.r = canon_nan(r);
+        e.lrr = canon_nan(lr * e.r);
         e.ce = ce;
         a.entries[(ent_base + step) * G + g] = e;
     };
@@ -571,10 +571,10 @@ __global__ void __launch_bounds__(64 * kWaves) pack_kernel(const PackArgs a) {
                         if (x2 == 0) {
                             wd[0] = slots_of(0); wd[1] = 0u; wd[2] = 0u; wd[3] = 0u;
                         } else if (tt < nsolo) {
-                            const float rr = rat_r[list[tt]];
+                            const float rr = canon_nan(rat_r[list[tt]]);
                             wd[0] = slots_of(tt + 1);
                             wd[1] = 0xFFFFFFFFu;
-                            wd[2] = __builtin_bit_cast(unsigned, lr * rr);
+                            wd[2] = __builtin_bit_cast(unsigned, canon_nan(lr * rr));
                             wd[3] = __builtin_bit_cast(unsigned, rr);
                         } else {
                             wd[0] = zero_slots; wd[1] = 0xFFFFFFFFu; wd[2] = 0u; wd[3] = 0u;

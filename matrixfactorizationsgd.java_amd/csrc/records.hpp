@@ -57,6 +57,23 @@ struct PackCellInfo {
     long long crit;    // sum over sub-rounds of the slowest wave's step-equivalents
 };
 
+// THE quiet NaN.  Every NaN that enters the library -- a rating and its lr * r wherever a packer or a re-bake writes them,
+// a rating of apply_ratings, a factor given to set_factors / load_factors / dsgd_set_q -- becomes this one
+// (which entries are NaN is the contract, sign and payload are not).  A solo record's mailbox word
+// is 0xFFFFFFFF until the chain wave posts s there (run_asm.hpp), and 0xFFFFFFFF is a NaN: s = fma(-lr, dot, lr * r)
+// hands an operand's payload on, so a NaN with the low 22 mantissa bits set in a rating or a row would be posted as
+// "not yet" and the helper would give up after its 2^22 polls.  A NaN born in a kernel is this one, and arithmetic
+// changes at most its sign.  Host and device build the same word whatever their multiplier does with a payload.
+constexpr uint32_t kQuietNaN = 0x7FC00000u;
+#if defined(__HIP__) || defined(__HIPCC__)
+#define MFSGD_HOST_DEVICE __host__ __device__
+#else
+#define MFSGD_HOST_DEVICE
+#endif
+MFSGD_HOST_DEVICE inline float canon_nan(float x) {
+    return (__builtin_bit_cast(uint32_t, x) & 0x7FFFFFFFu) > 0x7F800000u ? __builtin_bit_cast(float, kQuietNaN) : x;
+}
+
 constexpr int kRunMin = 8;    // shortest item chain worth a register-resident run
 constexpr int kSoloMin = 12;  // shortest chain worth a solo run (a second wave does the off-chain half)
 

@@ -70,11 +70,11 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) rehyper_kernel(const Cell
                 // a step entry; in a run step bit 31 of the slot word marks an idle slot, whose row must not decay
                 const bool idle_run = y < trailing && rel >= run_lo && rel < run_hi && (e.x >> 31) != 0;
                 float2 v;
-                v.x = lr * __uint_as_float(e.y);
+                v.x = canon_nan(lr * __uint_as_float(e.y));
                 v.y = idle_run ? 1.0f : c;
                 *reinterpret_cast<float2*>(w + 2) = v;
             } else if (nsolo > 0 && rel > rec_lo && rel <= rec_lo + nsolo) {
-                w[2] = lr * __uint_as_float(e.w);  // record t = rel - rec_lo - 1; the header and the tail hold no rating
+                w[2] = canon_nan(lr * __uint_as_float(e.w));  // record t = rel - rec_lo - 1; the header and the tail hold no rating
             }
         }
     }

@@ -34,6 +34,8 @@
 // period 8 instructions).  Cycles per step at 0 / 2 / 4 / 6 s_nops past a 64-byte boundary:
 //     solo pair   L = 16: 136.1 137.5 133.7 138.8    L = 32: 165.4 168.6 174.3 178.0    L = 64: 173.4 175.4 170.3 176.4
 //     run loop    L = 16: 145.6 143.6 149.6 151.6    L = 32: 174.5 174.5 182.4 180.4    L = 64: 177.8 177.7 181.7 183.7
+// The run loop with its idle slots masked (the loop below; profiles/run_idle_mask_ubench3.log, pad 2): L = 16: 157.6, the
+// loop without the mask at 143.6 in that session.
 // The solo pair before the steady body (s posted in pairs, the chain wave's body four A/B pairs long; at the longest n the
 // microbenchmark holds -- 300 / 200 / 120 steps; profiles/chain_unroll_ubench3.log, the pair +- 1.5 from run to run):
 //     solo pair   L = 16: 124.7 125.6 125.1 125.4    L = 32: 144.8 147.7 147.2 147.0    L = 64: 162.3 157.7 165.7 160.7
@@ -129,6 +131,14 @@ static_assert(mfsgd_chain_steady() % 2 == 0 && mfsgd_chain_steady() >= 2 && mfsg
 //   32 / 64 lanes per rating -> s = fma(-lr, dot, lr*r) -> q' = fma(s, p, ce*q), p' = fma(s, q, ce*p)
 //   -> store p'.  The prologue loads step 0; a harmless rewrite of an entry word keeps "one LDS
 //   operation behind the reads" so that every pass can use the same counted wait.
+//   IDLE slots (bit 31 of the slots word: p = the all-zero row, r = 0, ce = 1) keep their resident row by construction,
+//   not by arithmetic: ce*q is computed straight into the other q set and q' = fma(s, p, .) accumulated onto it in place
+//   with the idle lanes masked out of exec (%[live] = lanes of the live slots, %[sv] = the wave's exec; from the last DPP
+//   add to the two q' operations), so an idle slot's row is 1*q whatever s is.  Left to fma(0, p, 1*q), a resident row
+//   holding Inf or NaN gave 0*Inf = NaN as its dot and turned NaN as a whole; the NaN p' went into the zero row, and from
+//   there into the resident rows of other idle slots.  p' is still computed and stored for every lane (the counted waits
+//   rely on the store): an idle slot's goes to its dummy row, which nothing that reaches P or Q reads any more.
+//   (A lane group is one or two whole DPP rows, and the partner rows of the swap levels belong to the same group.)
 #define MFSGD_RUN_LOOP_ASM_TEXT(EXTRA, SFMA) \
         "v_mov_b32 v138, %[ea]\n\t" \
         "v_mov_b32 v131, %[lr]\n\t" \
@@ -148,49 +158,55 @@ static_assert(mfsgd_chain_steady() % 2 == 0 && mfsgd_chain_steady() >= 2 && mfsg
         MFSGD_LOOP_ALIGN \
         "1:\n\t" \
         "s_waitcnt lgkmcnt(1)\n\t" \
+        "v_cmp_lt_i32_e64 %[live], -1, v114\n\t" \
         "v_pk_mul_f32 v[120:121], v[104:105], v[100:101]\n\t" \
         "v_pk_fma_f32 v[120:121], v[106:107], v[102:103], v[120:121]\n\t" \
         "v_add_f32 v132, v120, v121\n\t" \
         "v_mad_u32_u16 v113, v115, 16, v139\n\t" \
-        "v_pk_mul_f32 v[122:123], v[116:117], v[100:101] op_sel:[1,0]\n\t" \
+        "v_pk_mul_f32 v[140:141], v[116:117], v[100:101] op_sel:[1,0]\n\t" \
         "v_add_f32_dpp v132, v132, v132 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
         "ds_read_b128 v[108:111], v113\n\t" \
-        "v_pk_mul_f32 v[124:125], v[116:117], v[102:103] op_sel:[1,0]\n\t" \
+        "v_pk_mul_f32 v[142:143], v[116:117], v[102:103] op_sel:[1,0]\n\t" \
         "v_add_f32_dpp v132, v132, v132 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
         "v_pk_mul_f32 v[126:127], v[116:117], v[104:105] op_sel:[1,0]\n\t" \
         "v_pk_mul_f32 v[128:129], v[116:117], v[106:107] op_sel:[1,0]\n\t" \
         "v_add_f32_dpp v132, v132, v132 row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
         "ds_read_b32 v114, v138 offset:%c[e2]\n\t" \
         "ds_read_b64 v[118:119], v138 offset:%c[e1p8]\n\t" \
+        "s_and_saveexec_b64 %[sv], %[live]\n\t" \
         "v_add_f32_dpp v132, v132, v132 row_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
         EXTRA \
         SFMA("116") \
-        "v_pk_fma_f32 v[140:141], v[130:131], v[104:105], v[122:123] op_sel_hi:[0,1,1]\n\t" \
-        "v_pk_fma_f32 v[142:143], v[130:131], v[106:107], v[124:125] op_sel_hi:[0,1,1]\n\t" \
+        "v_pk_fma_f32 v[140:141], v[130:131], v[104:105], v[140:141] op_sel_hi:[0,1,1]\n\t" \
+        "v_pk_fma_f32 v[142:143], v[130:131], v[106:107], v[142:143] op_sel_hi:[0,1,1]\n\t" \
+        "s_mov_b64 exec, %[sv]\n\t" \
         "v_pk_fma_f32 v[134:135], v[130:131], v[100:101], v[126:127] op_sel_hi:[0,1,1]\n\t" \
         "v_pk_fma_f32 v[136:137], v[130:131], v[102:103], v[128:129] op_sel_hi:[0,1,1]\n\t" \
         "s_sub_u32 %[n], %[n], 1\n\t" \
         "ds_write_b128 v112, v[134:137]\n\t" \
         "s_waitcnt lgkmcnt(1)\n\t" \
+        "v_cmp_lt_i32_e64 %[live], -1, v115\n\t" \
         "v_pk_mul_f32 v[120:121], v[108:109], v[140:141]\n\t" \
         "v_pk_fma_f32 v[120:121], v[110:111], v[142:143], v[120:121]\n\t" \
         "v_add_f32 v132, v120, v121\n\t" \
         "v_mad_u32_u16 v112, v114, 16, v139\n\t" \
-        "v_pk_mul_f32 v[122:123], v[118:119], v[140:141] op_sel:[1,0]\n\t" \
+        "v_pk_mul_f32 v[100:101], v[118:119], v[140:141] op_sel:[1,0]\n\t" \
         "v_add_f32_dpp v132, v132, v132 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
         "ds_read_b128 v[104:107], v112\n\t" \
-        "v_pk_mul_f32 v[124:125], v[118:119], v[142:143] op_sel:[1,0]\n\t" \
+        "v_pk_mul_f32 v[102:103], v[118:119], v[142:143] op_sel:[1,0]\n\t" \
         "v_add_f32_dpp v132, v132, v132 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
         "v_pk_mul_f32 v[126:127], v[118:119], v[108:109] op_sel:[1,0]\n\t" \
         "v_pk_mul_f32 v[128:129], v[118:119], v[110:111] op_sel:[1,0]\n\t" \
         "v_add_f32_dpp v132, v132, v132 row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
         "ds_read_b32 v115, v138 offset:%c[e3]\n\t" \
         "ds_read_b64 v[116:117], v138 offset:%c[e2p8]\n\t" \
+        "s_and_saveexec_b64 %[sv], %[live]\n\t" \
         "v_add_f32_dpp v132, v132, v132 row_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
         EXTRA \
         SFMA("118") \
-        "v_pk_fma_f32 v[100:101], v[130:131], v[108:109], v[122:123] op_sel_hi:[0,1,1]\n\t" \
-        "v_pk_fma_f32 v[102:103], v[130:131], v[110:111], v[124:125] op_sel_hi:[0,1,1]\n\t" \
+        "v_pk_fma_f32 v[100:101], v[130:131], v[108:109], v[100:101] op_sel_hi:[0,1,1]\n\t" \
+        "v_pk_fma_f32 v[102:103], v[130:131], v[110:111], v[102:103] op_sel_hi:[0,1,1]\n\t" \
+        "s_mov_b64 exec, %[sv]\n\t" \
         "v_pk_fma_f32 v[134:135], v[130:131], v[140:141], v[126:127] op_sel_hi:[0,1,1]\n\t" \
         "v_pk_fma_f32 v[136:137], v[130:131], v[142:143], v[128:129] op_sel_hi:[0,1,1]\n\t" \
         "v_add_u32 v138, %c[e2], v138\n\t" \
@@ -223,7 +239,8 @@ static_assert(mfsgd_chain_steady() % 2 == 0 && mfsgd_chain_steady() >= 2 && mfsg
 #define MFSGD_SFMA2_V(S, LRR) "v_fma_f32 v" S ", -%[lr], v132, v" LRR "\n\t"
 #define MFSGD_SFMA2_S(S, LRR) "v_fma_f32 v" S ", -v131, vcc_lo, v" LRR "\n\t"
 #define MFSGD_RUN_LOOP_ASM_OPERANDS                                                                                   \
-    : [q0] "+v"(q[0]), [q1] "+v"(q[1]), [q2] "+v"(q[2]), [q3] "+v"(q[3]), [n] "+s"(pairs)                              \
+    : [q0] "+v"(q[0]), [q1] "+v"(q[1]), [q2] "+v"(q[2]), [q3] "+v"(q[3]), [n] "+s"(pairs), [live] "=&s"(live),        \
+      [sv] "=&s"(sv)                                                                                                  \
     : [ea] "v"(ea), [rb] "v"(rowbase), [lr] "s"(lr), [e1] "n"(EST), [e2] "n"(2 * EST), [e3] "n"(3 * EST),              \
       [e1p8] "n"(EST + 8), [e2p8] "n"(2 * EST + 8), [pad] "n"(PADV)                                                                    \
     : "memory", "scc", "vcc", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", \

@@ -266,8 +266,8 @@ struct Hyper {
 inline Entry make_entry(uint32_t slots, float r, float ce, const Hyper& hy) {
     Entry e;
     e.slots = slots;
-    e.r = r;
-    e.lrr = hy.lr * r;
+    e.r = canon_nan(r);
+    e.lrr = canon_nan(hy.lr * e.r);
     e.ce = ce;
     return e;
 }
@@ -484,7 +484,7 @@ void pack_solo(const Rat* rs, int n, int G, int Lg, int nrows, const Hyper& hy, 
     auto slots_of = [&](int t) { return t < n ? encode_slots(rs[t].p, (int)q, false, Lg) : zero_slots; };
     entries.push_back(words(slots_of(0), 0u, 0u, 0u));
     for (int t = 0; t < n; ++t) {
-        entries.push_back(words(slots_of(t + 1), 0xFFFFFFFFu, bits(hy.lr * rs[t].r), bits(rs[t].r)));
+        entries.push_back(words(slots_of(t + 1), 0xFFFFFFFFu, bits(canon_nan(hy.lr * canon_nan(rs[t].r))), bits(canon_nan(rs[t].r))));
         order.push_back(rs[t].idx);
     }
     entries.push_back(words(zero_slots, 0xFFFFFFFFu, 0u, 0u));
@@ -1917,7 +1917,7 @@ void rehyper_schedule(Schedule& s, float lr, float lambda, int threads) {
     // step-format entries: lr * r as make_entry rounds it; c, or 1 where a run step's slot is idle (bit 31)
     auto steps = [&](Entry* e, size_t n, bool run) {
         for (size_t x = 0; x < n; ++x) {
-            e[x].lrr = hy.lr * e[x].r;
+            e[x].lrr = canon_nan(hy.lr * e[x].r);
             e[x].ce = run && (e[x].slots >> 31) ? 1.0f : hy.c;
         }
     };
@@ -1943,7 +1943,7 @@ void rehyper_schedule(Schedule& s, float lr, float lambda, int threads) {
                 e += (size_t)kSoloPad * G;
                 // record t = e[1 + t] = {next slots, mailbox, lr * r, r}: `ce` is where r sits; the header (e[0]) and
                 // what follows the last record hold no rating and stay as they are
-                for (size_t t = 1; t <= nsolo; ++t) e[t].lrr = hy.lr * e[t].ce;
+                for (size_t t = 1; t <= nsolo; ++t) e[t].lrr = canon_nan(hy.lr * e[t].ce);
             }
             steps(base + (n_steps - 2) * G, 2 * G, false);
         }

@@ -57,9 +57,6 @@ static int probe_persistent(mfsgd_handle* h, Part& p) {
     // them some CUs, or a persistent launch that needs the whole chip would sit in its residency check until the
     // exchange in flight has finished
     long np = (long)per_cu * (h->n_parts > 1 ? std::max(1, h->n_cu - 8) : h->n_cu);
-    // test hook: pretend the chip holds this many times more workgroups than it does, so that the
-    // residency check of the epoch kernel has to fail (tests/test_gpu_parity.py)
-    if (const char* f = std::getenv("MFSGD_TEST_OVERSUBSCRIBE")) np *= std::max(1, std::atoi(f));
     p.persistent_np = (int)std::min<long>(np, p.sched.B);
     return MFSGD_OK;
 }
@@ -441,7 +438,7 @@ static void online_sort_piece(mfsgd_handle* h, const int32_t* u, const int32_t* 
         const int32_t at = next[(size_t)pc.level[(size_t)j]]++;
         pc.u[(size_t)at] = u[j];
         pc.i[(size_t)at] = i[j];
-        pc.r[(size_t)at] = r[j];
+        pc.r[(size_t)at] = canon_nan(r[j]);  // (records.hpp: a payload must not reach P and Q)
         pc.orig[(size_t)at] = (int32_t)j;
     }
 }
@@ -774,7 +771,7 @@ int mfsgd_apply_ratings(mfsgd_handle* h, const int32_t* u, const int32_t* i, con
             HIPCHK_OR(bad, online_launches(pc.level_ptr, pc.n_levels, h->geo.L, &got.launches, [&](int32_t l0, int32_t l1, int32_t wgs) {
                 return launch_apply_levels(h->geo.L, h->dP.as<float>(), h->dQ.as<float>(), du.as<const int32_t>(),
                                            di.as<const int32_t>(), dr.as<const float>(), dorig.as<const int32_t>(),
-                                           dptr.as<const int32_t>(), l0, l1, wgs, lr, c1, err ? derr.as<float>() : nullptr,
+                                           dptr.as<const int32_t>(), l0, l1, wgs, h->cfg.k, lr, c1, err ? derr.as<float>() : nullptr,
                                            h->stream);
             }));
             if (err) HIPCHK_OR(bad, hipMemcpyAsync(err + j0, derr.get(), sizeof(float) * (size_t)c, hipMemcpyDeviceToHost, h->stream));

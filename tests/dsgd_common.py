@@ -101,6 +101,17 @@ def native_problem():
     return U, I, k, u, i, r, epochs
 
 
+def native_problem_named(name):
+    """(U, I, k, u, i, r, epochs, constructor keywords) of a problem the ranks of the multi-process test rebuild by name:
+    "skewed" is native_problem(); "hot_items" the lone-tile set at k = 64, B = 8 (hot_items_problem below), whose item 9
+    is rated by every user of every rank."""
+    if name == "skewed":
+        return native_problem() + ({},)
+    assert name == "hot_items", name
+    k, B, _, U, I, u, i, r = hot_items_problem("k64")
+    return U, I, k, u, i, r, 2, dict(blocks=B, waves=2)
+
+
 class OracleBackend:
     """CPU stand-in for dsgd.HipBackend (tests only)."""
 
@@ -198,3 +209,35 @@ def fuzz_chunked_cases(n_cases, seed=4242, max_ratings=9000):
         B = int(rng.choice([1, 1, 2, 3, 4]))
         yield dict(U=U, I=I, k=k, u=u.astype(np.int32), i=i.astype(np.int32), r=r, blocks=B, waves=W,
                    lr=float(rng.choice([0.01, 0.05])), lam=float(rng.choice([0.0, 0.05])))
+
+
+# ---- hot items under partitioned handles (tests/test_dsgd_hot_items_gpu.py) ---------------------------------------------
+HOT_SHAPES = {"k64": (64, 8, 2, 1200), "k128": (128, 6, 3, 900), "k256": (256, 12, 2, 1200)}  # name -> (k, B, G, U)
+HOT_A, HOT_B = 9, 17  # rated by every user / by every other user
+
+
+def hot_items_problem(shape):
+    """The lone-tile set of test_lone_tile_mailbox_hand_off with fill 4 at a DSGD shape: (k, B, G, U, I, u, i, r)."""
+    from tests.test_lone_hop_gpu import _problem
+
+    k, B, G, U = HOT_SHAPES[shape]
+    U, I, u, i, r = _problem(U, 90, 4, k + B)
+    return k, B, G, U, I, u, i, r
+
+
+def hot_item_map(mf, how, U, I, u, i, G):
+    """Item -> partition: "apart" is mfsgd_dsgd_plan's (it deals the heaviest items one per partition), "together" the
+    default i % G with item 17 moved into item 9's partition."""
+    if how == "apart":
+        ip = np.asarray(mf.dsgd_plan(np.bincount(u, minlength=U), np.bincount(i, minlength=I), G)[1], np.int32)
+        assert ip[HOT_A] != ip[HOT_B]
+        return ip
+    ip = (np.arange(I) % G).astype(np.int32)
+    ip[HOT_B] = ip[HOT_A]
+    return ip
+
+
+def lone_and_solo(t, part):
+    """(lone-tile cells, solo runs) of a partition's schedule."""
+    cells, _, subs, _ = t.debug_schedule(part)
+    return int((cells[:, 5] & 1).sum()), int(((subs[:, 0] >> 16) > 0).sum())

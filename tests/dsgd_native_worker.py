@@ -5,7 +5,9 @@ the blocks travel through the driver's shared-memory rehearsal transport (RCCL c
 one GPU), everything else -- groups, slots, double buffers, event ordering, the RMSE reduction -- is the
 code the RCCL ring runs.
 
-    python tests/dsgd_native_worker.py RANK WORLD PARTS_PER_RANK OUT_DIR
+    python tests/dsgd_native_worker.py RANK WORLD PARTS_PER_RANK OUT_DIR [PROBLEM]
+
+PROBLEM names a rating set of tests/dsgd_common.native_problem_named ("skewed" when left out).
 
 The rehearsal transport lives in lib/libmfsgd_rehearsal.so only (MFSGD_LIBRARY points at it, MFSGD_DSGD_TRANSPORT=shm
 selects it); rank 0 makes the ring id and leaves it in OUT_DIR/ring.id for the others.
@@ -21,7 +23,7 @@ import numpy as np  # noqa: E402
 import mfsgd_amd as mf  # noqa: E402
 from mfsgd_amd import _lib  # noqa: E402
 from mfsgd_amd.dsgd import NativeDSGD  # noqa: E402
-from tests.dsgd_common import SEED, native_problem, plan_shards, plan_trainer  # noqa: E402
+from tests.dsgd_common import SEED, native_problem_named, plan_shards, plan_trainer  # noqa: E402
 
 
 def main():
@@ -44,12 +46,12 @@ def main():
             time.sleep(0.05)
         with open(id_path, "rb") as f:
             uid = f.read()
-    U, I, k, u, i, r, epochs = native_problem()
+    U, I, k, u, i, r, epochs, kw = native_problem_named(sys.argv[5] if len(sys.argv) > 5 else "skewed")
     n_parts = world * m
     ub, ip, sel = plan_shards(mf, U, I, u, i, world)  # users over the ranks ...
     _, ip = mf.dsgd_plan(np.bincount(u, minlength=U), np.bincount(i, minlength=I), n_parts)  # ... items over all partitions
     # several processes share this GPU: round launches (a persistent kernel wants its workgroups co-resident)
-    t = plan_trainer(mf, rank, ub, ip, sel, I, k, u, i, r, n_parts, flags=_lib.FLAG_ROUND_LAUNCH)
+    t = plan_trainer(mf, rank, ub, ip, sel, I, k, u, i, r, n_parts, flags=_lib.FLAG_ROUND_LAUNCH, **kw)
     with NativeDSGD(t, rank, world, uid) as d:
         assert d.m == m
         d.init_q(SEED, U)

@@ -342,3 +342,292 @@ def check_edge_scores(kind, sc):
         assert np.isinf(sc).sum() == POS_INF_ITEMS.size + NEG_INF_ITEMS.size
     if kind == "subnormal":
         assert is_subnormal(sc).all() and np.unique(sc).size >= 600
+
+
+# ---- NaN and Inf through the solo runs (tests/test_chain_specials_gpu.py, tests/test_contract_edges_cpu.py) -----------
+ALL_ONES_NAN = np.array([0xFFFFFFFF], np.uint32).view(np.float32)[0]  # the NaN whose bits are a solo record's empty mailbox
+HOT_ITEM = 7  # hot_item_set's
+
+
+def solo_runs(mf, U, I, k, u, i, **kw):
+    """The solo runs of the schedule a handle of this geometry builds (host packer; no GPU needed): one array of rating
+    indices per run, in step order, runs in schedule order.  Read off the records themselves: with the ratings 1, 2, 3 ...
+    a record {next slots, mailbox = all ones, lr * r, r} names its rating in its last word; the header in front of a
+    run's records has mailbox 0, the terminator behind them r = 0, and no step entry holds all ones in its second word."""
+    assert u.size < (1 << 24)
+    with mf.MatrixFactorizationSGD(U, I, k, LR, LAM, 1, **kw) as m:
+        m.set_ratings(u, i, np.arange(1, u.size + 1, dtype=np.float32))
+        ent = m.debug_schedule()[3]
+        order = m.order()[0]
+        n_solo = int((m.debug_schedule()[2][:, 0] >> 16).sum())
+    rec = (ent[:, 1] == 0xFFFFFFFF) & (ent[:, 3] != 0)
+    at = np.flatnonzero(rec)
+    runs = [ent[x, 3].view(np.float32).astype(np.int64) - 1 for x in np.split(at, np.flatnonzero(np.diff(at) != 1) + 1)] if at.size else []
+    assert sum(x.size for x in runs) == n_solo
+    place = np.empty(u.size, np.int64)
+    place[order] = np.arange(u.size)
+    for x in runs:  # the steps of a run follow the exported order, and are one item's
+        assert (np.diff(place[x]) == 1).all() and np.unique(i[x]).size == 1
+    runs.sort(key=lambda x: place[x[0]])
+    return runs, place
+
+
+def odd_run_set(mf, k, W):
+    """hot_item_set(k, W) if a solo run of item 7 has an odd number of steps (k = 256: 125); else the same set with ONE
+    rating of item 7 moved to an item its user has not rated -- every user keeps its degree, and with it its block -- so
+    that one run of 300 / 150 steps becomes one of 299 / 149 (asserted by whoever uses it: runs_of_the_hot_item)."""
+    U, I, u, i, kw = hot_item_set(k, W)
+    runs, _ = solo_runs(mf, U, I, k, u, i, **kw)
+    if any(x.size % 2 == 1 and i[x[0]] == HOT_ITEM for x in runs):
+        return U, I, u, i, kw
+    last = [x for x in runs if i[x[0]] == HOT_ITEM][-1]
+    j = last[last.size // 2]
+    mine = set(i[u == u[j]].tolist())
+    i = i.copy()
+    i[j] = next(t for t in range(I - 1, -1, -1) if t not in mine)
+    return U, I, u, i, kw
+
+
+def runs_of_the_hot_item(mf, U, I, k, u, i, item=HOT_ITEM, **kw):
+    runs, place = solo_runs(mf, U, I, k, u, i, **kw)
+    return [x for x in runs if i[x[0]] == item], place
+
+
+NAN_PLACES = ("rating_first_step", "rating_even_step", "rating_odd_step", "rating_last_step_of_an_odd_run", "p_row_mid_run", "q_hot_item")
+
+
+def place_nan(where, mf, k, U, I, u, i, kw, P0, Q0, r, item=HOT_ITEM):
+    """One all-ones NaN at `where` (NAN_PLACES), as late in the exported order as that place exists, so that one epoch leaves
+    NaN and finite entries side by side: the rating places in the LAST solo run of the item (of the last odd-length one);
+    the P row of that user in the middle half of a run whose FIRST rating comes latest in the order (a NaN row spreads
+    from the first rating of its user on).  Q[item] cannot be late: everybody who rated the item -- in hot_item_set every
+    user -- is NaN after one epoch.  Returns (P0, Q0, r, run length, step)."""
+    runs, place = runs_of_the_hot_item(mf, U, I, k, u, i, item, **kw)
+    assert runs and all(x.size >= 12 for x in runs)
+    P0, Q0, r = P0.copy(), Q0.copy(), r.copy()
+    run, step = runs[-1], -1
+    if where == "rating_first_step":
+        step = 0
+    elif where == "rating_even_step":
+        step = (run.size // 2) & ~1
+    elif where == "rating_odd_step":
+        step = (run.size // 2) | 1
+    elif where == "rating_last_step_of_an_odd_run":
+        run = [x for x in runs if x.size % 2 == 1][-1]
+        step = run.size - 1
+    elif where == "p_row_mid_run":
+        first = np.full(U, u.size, np.int64)
+        np.minimum.at(first, u, place)
+        mid = [(first[u[x[t]]], n, t) for n, x in enumerate(runs) for t in range(x.size // 4, x.size - x.size // 4)]
+        _, n, step = max(mid)
+        run = runs[n]
+        P0[u[run[step]], (3 * k) // 4] = ALL_ONES_NAN
+        return P0, Q0, r, run.size, step
+    elif where == "q_hot_item":
+        Q0[item, k // 3] = ALL_ONES_NAN
+        return P0, Q0, r, run.size, step
+    else:
+        raise ValueError(where)
+    r[run[step]] = ALL_ONES_NAN
+    return P0, Q0, r, run.size, step
+
+
+def ordinary_factors(U, I, k, seed=3):
+    rng = np.random.default_rng([seed, U, I, k])
+    return ((rng.standard_normal((U, k)) / np.sqrt(k)).astype(np.float32),
+            (rng.standard_normal((I, k)) / np.sqrt(k)).astype(np.float32))
+
+
+def ordinary_ratings(n, seed=4):
+    return (np.random.default_rng([seed, n]).random(n) * 4 + 1).astype(np.float32)
+
+
+def assert_same_but_for_the_nans(name, got, want):
+    """The NaN masks are equal and every other entry is equal bit for bit, infinities included."""
+    nan = np.isnan(want)
+    assert np.array_equal(np.isnan(got), nan), f"{name}: {(np.isnan(got) != nan).sum()} entries are NaN on one side only"
+    assert got[~nan].tobytes() == want[~nan].tobytes(), f"{name}: entries that are not NaN differ"
+
+
+def assert_rmse_same_but_for_the_nans(rm, rmo):
+    assert np.isfinite(rm) == np.isfinite(rmo), (rm, rmo)
+    if np.isfinite(rmo):
+        np.testing.assert_allclose(rm, rmo, rtol=1e-9, atol=0)
+
+
+def nan_share(P, Q):
+    return float(np.isnan(np.concatenate([P.ravel(), Q.ravel()])).mean())
+
+
+def classes(P, Q):
+    """(finite, infinite, NaN entries present) of a state."""
+    both = np.concatenate([P.ravel(), Q.ravel()])
+    return bool(np.isfinite(both).any()), bool(np.isinf(both).any()), bool(np.isnan(both).any())
+
+
+LONE_CELLS = {64: 0, 128: 0, 256: 24}  # lone-tile cells of hot_item_set(k, W) at SOLO_KW (k = 256: B = 24, all of item 7's)
+LONE_ITEM, LONE_PROBLEM_CELLS = 9, 24  # lone_problem: items 9 and 17 have a tile each, 12 cells per tile
+
+
+def lone_problem():
+    """test_lone_hop_gpu.test_row_widths' problem at k = 64: B = 12, item 9 rated by all 1800 users -- 150 per cell, one solo
+    run each, every cell a lone-tile cell of the fast lane.  (U, I, k, u, i, r, constructor keywords)"""
+    from tests.test_lone_hop_gpu import _problem
+
+    U, I, u, i, r = _problem(150 * 12, 90, 6, 64 + 12)
+    return U, I, 64, u, i, r, dict(blocks=12, waves=2)
+
+
+def check_nan_case(where, states):
+    """states: the oracle's [(P, Q, rmse)] after each epoch of a NaN case.  After the first epoch NaN and finite entries
+    stand side by side, between 0.05 % and 60 % NaN -- but for the NaN in Q[hot item]: every user rated that item, so all
+    of P is NaN after one epoch wherever the item's ratings come in the order, and so is most or all of Q."""
+    share = nan_share(*states[0][:2])
+    assert np.isnan(states[0][2]) and np.isnan(states[-1][2])
+    if where == "q_hot_item":
+        assert share > 0.6 and np.isnan(states[0][0]).all()
+    else:
+        assert 0.0005 <= share <= 0.6, share
+        assert not np.isinf(states[0][0]).any() and not np.isinf(states[0][1]).any()
+    assert nan_share(*states[-1][:2]) >= share
+
+
+# ---- overflow through every loop form (B) ------------------------------------------------------------------------------
+def _without_k_and_r(U, I, k, u, i, r, kw):
+    return U, I, u, i, kw
+
+
+OVERFLOW_SETS = {  # name -> (set builder, k, hot item or None)
+    "hot_item_k64_w2": (lambda: hot_item_set(64, 2), 64, HOT_ITEM),
+    "hot_item_k128_w4": (lambda: hot_item_set(128, 4), 128, HOT_ITEM),
+    "hot_item_k256_w2": (lambda: hot_item_set(256, 2), 256, HOT_ITEM),
+    "chunked_k256_b1": (lambda: chunked_set(256, 1, 2, 900), 256, None),
+    "swapped_k64": (hot_user_set, 64, None),
+    "lone_k64_b12": (lambda: _without_k_and_r(*lone_problem()), 64, LONE_ITEM),
+}
+OVERFLOW_PLACES = ("anywhere", "last_in_the_order", "on_the_hot_item")
+
+
+def overflow_cases():
+    return [(name, where) for name in sorted(OVERFLOW_SETS) for where in OVERFLOW_PLACES
+            if where != "on_the_hot_item" or OVERFLOW_SETS[name][2] is not None]
+
+
+def overflow_ratings(where, u, i, order, hot):
+    """Ratings 1 .. 5 with +-3e38 on 1 % of them, anywhere or at the end of `order`; or on the hot item's last 20 ratings
+    in `order`."""
+    rng = np.random.default_rng(5)
+    r = (rng.random(u.size) * 4 + 1).astype(np.float32)
+    n_big = 20 if where == "on_the_hot_item" else u.size // 100
+    huge = np.where(rng.random(n_big) < 0.5, np.float32(3e38), np.float32(-3e38))
+    if where == "anywhere":
+        r[rng.choice(u.size, n_big, replace=False)] = huge
+    elif where == "last_in_the_order":
+        r[order[-n_big:]] = huge
+    else:
+        r[order[i[order] == hot][-n_big:]] = huge
+    return r
+
+
+def check_overflow_set(name, info, sched):
+    """The schedule holds the loop form the set is there for."""
+    solo, lone = int(((sched[2][:, 0] >> 16) > 0).sum()), int((sched[0][:, 5] & 1).sum())
+    if name.startswith("hot_item"):
+        run_steps = int((sched[2][:, 1] >> 16).sum())  # (at k = 64 the light items' chains stay general steps)
+        assert solo >= 10 and (run_steps > 0 or OVERFLOW_SETS[name][1] == 64), (solo, run_steps)
+        assert lone == LONE_CELLS[OVERFLOW_SETS[name][1]]
+    if name.startswith("chunked"):
+        assert info["split_cells"] >= 1
+    if name.startswith("swapped"):
+        assert info["swapped"] == 1
+    if name.startswith("lone"):
+        assert lone == LONE_PROBLEM_CELLS and solo >= 12
+
+
+def check_overflow_case(where, states):
+    """The rule of test_overflow_goes_to_infinity_and_nan_where_the_oracle_does, on the oracle's states after each epoch:
+    NaN has been seen and the last RMSE is not finite; and, unless the large ratings are anywhere (then everything may be
+    NaN within the first epoch), finite, infinite and NaN entries have each been seen and one state holds at least two of
+    the classes side by side."""
+    seen = np.array([classes(P, Q) for P, Q, _ in states])
+    assert seen[:, 2].any() and not np.isfinite(states[-1][2])
+    if where != "anywhere":
+        assert seen.any(axis=0).all(), seen
+        assert (seen.sum(axis=1) >= 2).any(), seen
+
+
+# ---- NaN and overflow through apply_ratings and fold-in (B) -----------------------------------------------------------
+ONLINE_SPECIALS = [(batch, kind, k) for batch in ("one_item", "wide") for kind in ("nan", "huge") for k in (64, 5)]
+
+
+def online_special_batch(batch, kind):
+    """online_common's one_item_batch (a chain of 600 levels) or hot_item_batch (wide levels, every 40th rating of item 7)
+    with ONE special rating half-way, on the hot item: an all-ones NaN, or 3e38 (the item's row grows, overflows and
+    turns NaN over the next few of its ratings)."""
+    from tests import online_common as oc
+
+    U, I, u, i, r = oc.one_item_batch() if batch == "one_item" else oc.hot_item_batch()
+    at = (u.size // 2) // 40 * 40
+    assert i[at] == (3 if batch == "one_item" else 7)
+    r = r.copy()
+    r[at] = ALL_ONES_NAN if kind == "nan" else np.float32(3e38)
+    return U, I, u, i, r, at
+
+
+def check_online_special(kind, at, err, P, Q):
+    """On the oracle's results: the errors before the special rating are finite; a NaN rating's own error and later ones
+    are NaN, and NaN and finite rows stand side by side in P and in Q; a rating of 3e38 leaves infinite entries in P (in
+    the chain of one item every user comes once: the rows overflow and stay infinite, no NaN arises) beside finite ones."""
+    assert np.isfinite(err[:at]).all()
+    if kind == "nan":
+        assert np.isnan(err[at]) and np.isnan(err[at + 1:]).any()
+        for a in (P, Q):
+            assert np.isnan(a).any() and np.isfinite(a).any()
+    else:
+        assert err[at] > 1e38 and np.isinf(P).any() and np.isfinite(P).any() and np.isfinite(Q).any()
+
+
+FOLD_IN_SPECIAL_USERS = {1: ((25, "nan"),), 2: ((10, "huge"),), 4: ((10, "huge"), (30, "nan"))}
+
+
+def fold_in_specials(k):
+    """(Q, row_ptr, items, ratings, init): six new users of 40 ratings each against 300 items; user 1 has an all-ones NaN
+    rating, user 2 one of 3e38, user 4 both; users 0, 3 and 5 are ordinary."""
+    rng = np.random.default_rng(3000 + k)
+    n_new, I, n = 6, 300, 40
+    row_ptr = (np.arange(n_new + 1) * n).astype(np.int64)
+    items = np.concatenate([rng.choice(I, n, replace=False) for _ in range(n_new)]).astype(np.int32)
+    ratings = rng.uniform(1.0, 5.0, items.size).astype(np.float32)
+    for user, specials in FOLD_IN_SPECIAL_USERS.items():
+        for at, kind in specials:
+            ratings[user * n + at] = ALL_ONES_NAN if kind == "nan" else np.float32(3e38)
+    init, Q = ordinary_factors(n_new, I, k, seed=9)
+    return Q, row_ptr, items, ratings, init
+
+
+def check_fold_in_specials(want):
+    assert np.isfinite(want[[0, 3, 5]]).all() and np.isnan(want[1]).all() and np.isnan(want[4]).all()
+    # (3e38 alone: against fixed item rows the row stays finite, at the top of fp32's range)
+    assert np.isfinite(want[2]).all() and np.abs(want[2]).max() > 1e30
+
+
+# ---- hot rows on the user side and on both sides (D) --------------------------------------------------------------------
+def hot_user_lone_set(B):
+    """The lone-tile problem transposed: user 9 rates all 150 * B items, user 17 every other one, 4 * 150 * B random
+    ratings on top -- the roles are swapped, users 9 and 17 have a tile each (2 B lone-tile cells, 2 B solo runs)."""
+    from tests.test_lone_hop_gpu import _problem
+
+    I, U, i, u, r = _problem(150 * B, 90, 4, 500 + B)
+    return U, I, u, i, r
+
+
+def two_sided_set(U, I, seed=1):
+    """User 3 rates every item AND item 9 is rated by every user, 3 * max(U, I) random ratings on top: the longer side's
+    hot row gets the lone tile and the solo runs (U < I: roles swapped), the other side's is a chain of dependent steps
+    in every cell it meets."""
+    rng = np.random.default_rng(seed)
+    n = 3 * max(U, I)
+    u = list(range(U)) + [3] * I + list(rng.integers(0, U, n))
+    i = [9] * U + list(range(I)) + list(rng.integers(0, I, n))
+    key = rng.permutation(np.unique(np.array(u, np.int64) * I + np.array(i)))
+    return U, I, (key // I).astype(np.int32), (key % I).astype(np.int32), (rng.random(key.size) * 4 + 1).astype(np.float32)

@@ -225,6 +225,14 @@ def test_hot_user_chain_swapped_roles(mf, oracle):
     key = np.unique(np.array(u) * I + np.array(i))
     _, info = _run(mf, oracle, U, I, 64, key // I, key % I, rng.random(key.size) * 4 + 1, epochs=2)
     assert info["swapped"] == 1
+    # the hot user's chain is what the solo runs and the lone-tile hop are for: B = 8, 8 lone-tile cells, 13 solo runs
+    with mf.MatrixFactorizationSGD(U, I, 64, LR, LAM, 11) as m:
+        m.set_ratings((key // I).astype(np.int32), (key % I).astype(np.int32), np.ones(key.size, np.float32))
+        cells, _, subs, _ = m.debug_schedule()
+        B = m.schedule_info()["blocks"]
+    solo = subs[:, 0] >> 16
+    assert (cells[:, 5] & 1).sum() >= B and solo.sum() > 0, (B, int((cells[:, 5] & 1).sum()), int(solo.sum()))
+    print(f"B {B}, lone cells {(cells[:, 5] & 1).sum()}, solo runs {(solo > 0).sum()}, solo steps {solo.sum()}")
 
 
 def test_large_values_and_zero_lambda(mf, oracle):
@@ -377,6 +385,12 @@ def _same_schedule(mf, U, I, k, u, i, r, n_parts=0, expect_packed=None, **kw):
     return all(packed)
 
 
+def _lib_flag(name):
+    from mfsgd_amd import _lib
+
+    return getattr(_lib, name)
+
+
 def test_device_ingest_and_device_packer_build_the_same_schedule(mf):
     """Degree histograms + bucket order (ingest.hip) and the per-cell step packer (pack.hip) on the GPU
     against the host loops: the same bytes, whoever builds the schedule."""
@@ -384,6 +398,16 @@ def test_device_ingest_and_device_packer_build_the_same_schedule(mf):
                                 ("cfg3_netflix", 0.01, None), ("cfg0_dense100x80", 1.0, True)):
         w = mf.synth.workload(name, scale)
         _same_schedule(mf, w["U"], w["I"], w["k"], w["u"], w["i"], w["r"], expect_packed=packed)
+    # ratings that are the all-ones NaN (a solo record's empty mailbox word), in solo records and in step entries: every
+    # builder writes the quiet NaN for the rating and for lr * r (tests/test_hyper_cpu.py, check_kind "solo_nan")
+    from tests.test_hyper_cpu import PROBLEMS, check_kind
+
+    make, k, kw, kind = PROBLEMS["solo_nan_k64_w2"]
+    U, I, u, i, r = make()
+    _same_schedule(mf, U, I, k, u, i, r, expect_packed=True, **kw)
+    with mf.MatrixFactorizationSGD(U, I, k, LR, LAM, 5, flags=_lib_flag("FLAG_DEVICE_INGEST"), **kw) as m:
+        m.set_ratings(u, i, r)
+        check_kind(m, kind)
 
 
 def test_device_packer_fuzz(mf, oracle):
@@ -970,18 +994,24 @@ def test_native_dsgd_multi_process_shm(mf, oracle, tmp_path, monkeypatch, world,
     blocks moved by the driver's shared-memory rehearsal transport (RCCL refuses two ranks on one GPU; with
     RCCL only ncclSend / ncclRecv / ncclAllReduce differ).  Factors, Q blocks and the RMSE trajectory against
     the sequential DSGD definition run by the oracle over global factors: bit-exact."""
+    _multi_process_shm(mf, oracle, tmp_path, world, m, "skewed")
+
+
+def _multi_process_shm(mf, oracle, tmp_path, world, m, problem):
+    """problem: a name of tests/dsgd_common.native_problem_named, which every rank rebuilds.  Returns the trainers' (lone-tile
+    cells, solo runs) per (rank, partition)."""
     import os
     import subprocess
     import sys
 
     from mfsgd_amd import _lib
     from tests.conftest import ROOT
-    from tests.dsgd_common import LAM as DL, LR as DLR, SEED, native_problem, plan_shards, plan_trainer
+    from tests.dsgd_common import LAM as DL, LR as DLR, SEED, lone_and_solo, native_problem_named, plan_shards, plan_trainer
 
     # the rehearsal transport is in lib/libmfsgd_rehearsal.so only: the ranks load that one (this process keeps the product library)
     env = dict(os.environ, MFSGD_DSGD_TRANSPORT="shm", MFSGD_LIBRARY=_lib.rehearsal_library_path())
     procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "dsgd_native_worker.py"), str(rk), str(world), str(m),
-                               str(tmp_path)], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+                               str(tmp_path), problem], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
              for rk in range(world)]
     outs = []
     for pr in procs:
@@ -993,7 +1023,7 @@ def test_native_dsgd_multi_process_shm(mf, oracle, tmp_path, monkeypatch, world,
             raise
     for rk, (pr, o) in enumerate(zip(procs, outs)):
         assert pr.returncode == 0, f"rank {rk}:\n{o[-3000:]}"
-    U, I, k, u, i, r, epochs = native_problem()
+    U, I, k, u, i, r, epochs, kw = native_problem_named(problem)
     n_parts = world * m
     ub, _, sel = plan_shards(mf, U, I, u, i, world)
     _, ip = mf.dsgd_plan(np.bincount(u, minlength=U), np.bincount(i, minlength=I), n_parts)
@@ -1008,7 +1038,8 @@ def test_native_dsgd_multi_process_shm(mf, oracle, tmp_path, monkeypatch, world,
             seen.append(int(part))
     assert sorted(seen) == list(range(n_parts))
     # the sequential definition: sub-epoch s, rank g trains the partitions of group (g + s) % world, one after another
-    trainers = [plan_trainer(mf, g, ub, ip, sel, I, k, u, i, r, n_parts) for g in range(world)]
+    trainers = [plan_trainer(mf, g, ub, ip, sel, I, k, u, i, r, n_parts, **kw) for g in range(world)]
+    forms = [[lone_and_solo(t, part) for part in range(n_parts)] for t in trainers]
     Po, Qo = oracle.init_factors(U, I, k, SEED)
     rm0 = oracle.rmse(Po, Qo, u, i, r)
     ref = []
@@ -1027,6 +1058,7 @@ def test_native_dsgd_multi_process_shm(mf, oracle, tmp_path, monkeypatch, world,
         assert abs(float(g["rm0"]) - rm0) <= 1e-9
         np.testing.assert_allclose(g["rm"], ref, rtol=1e-9)
         assert np.abs(g["rm"] - np.array(ref)).max() <= RMSE_TOL
+    return forms
 
 
 def test_native_dsgd_rejects_bad_arguments(mf):

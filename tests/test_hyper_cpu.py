@@ -27,6 +27,17 @@ def _dominant_item():
     return U, I, (key // I).astype(np.int32), (key % I).astype(np.int32), (rng.random(key.size) * 4 + 1).astype(np.float32)
 
 
+def _dominant_item_with_nan_ratings():
+    """_dominant_item with the NaN whose bits are all ones -- a solo record's empty mailbox word (csrc/run_asm.hpp) -- on
+    every 40th rating of item 7 (solo steps) and every 97th rating of all: whoever writes a schedule writes the quiet
+    NaN 0x7FC00000 for such a rating and for its lr * r (csrc/records.hpp, canon_nan)."""
+    U, I, u, i, r = _dominant_item()
+    r = r.copy()
+    r[np.flatnonzero(i == 7)[::40]] = np.array([0xFFFFFFFF], np.uint32).view(np.float32)[0]
+    r[::97] = np.array([0xFFFFFFFF], np.uint32).view(np.float32)[0]
+    return U, I, u, i, r
+
+
 def _chunked():
     rng = np.random.default_rng(257)
     U, I, n = 900, 800, 700
@@ -48,6 +59,7 @@ PROBLEMS = {
     "solo_k64_w2": (_dominant_item, 64, dict(blocks=2, waves=2), "solo"),
     "solo_k128_w4": (_dominant_item, 128, dict(blocks=2, waves=4), "solo"),
     "solo_k64_w1": (_dominant_item, 64, dict(blocks=2, waves=1), "solo"),
+    "solo_nan_k64_w2": (_dominant_item_with_nan_ratings, 64, dict(blocks=2, waves=2), "solo_nan"),
     "run_k32_w2": (_dominant_item, 32, dict(blocks=2, waves=2), "run"),
     "chunked_k256": (_chunked, 256, dict(blocks=1, waves=2), "split"),
     "hot_user": (_hot_user, 64, dict(blocks=2, waves=2), "swapped"),
@@ -82,6 +94,13 @@ def check_kind(m, kind):
         nsolo, nrun = int((subs[:, 0] >> 16).sum()), int((subs[:, 1] >> 16).sum())
         if kind == "solo":
             assert nsolo > 0, "solo steps must exist"
+        if kind == "solo_nan":  # NaN ratings in solo records and in step entries, every one the quiet NaN in both words
+            record = (entries[:, 1] == 0xFFFFFFFF) & (entries[:, 3] != 0)
+            nan_record = record & ((entries[:, 3] & 0x7FFFFFFF) > 0x7F800000)
+            nan_step = ~record & ((entries[:, 1] & 0x7FFFFFFF) > 0x7F800000) & (entries[:, 1] != 0xFFFFFFFF)
+            assert nsolo > 0 and nan_record.sum() >= 5 and nan_step.sum() >= 5, (nan_record.sum(), nan_step.sum())
+            assert (entries[nan_record][:, 2:] == 0x7FC00000).all() and (entries[nan_step][:, 1:3] == 0x7FC00000).all()
+            assert not (entries[:, 2] == 0xFFFFFFFF).any()
         if kind == "run":
             assert nsolo == 0 and nrun > 0
             G = info["slots"]

@@ -67,10 +67,26 @@ def test_parity_through_a_change_of_values(mf, oracle, name, flag):
 @pytest.mark.parametrize("pair", range(len(PAIRS)))
 def test_device_rebake_is_the_fresh_schedule_byte_for_byte(mf, pair, trained):
     """trained False: the buffers are still the device packer's; True: the part has adopted them."""
+    _device_rebake(mf, "solo_k64_w2", pair, trained)
+
+
+@pytest.mark.parametrize("trained", [False, True])
+@pytest.mark.parametrize("pair", range(len(PAIRS)))
+def test_device_rebake_of_nan_ratings_is_the_fresh_schedule_byte_for_byte(mf, pair, trained):
+    """The same on the set whose ratings hold all-ones NaNs, in solo records and in step entries: device packer, device
+    re-bake and (the snapshot of the host copy) the host re-bake write the quiet NaN for lr * r at every lr, 0 included;
+    and training through such a schedule returns."""
+    from tests.test_hyper_cpu import check_kind
+
+    with fresh(mf, "solo_nan_k64_w2", *PAIRS[pair][0]) as m:
+        check_kind(m, "solo_nan")
+    _device_rebake(mf, "solo_nan_k64_w2", pair, trained)
+
+
+def _device_rebake(mf, name, pair, trained):
     from mfsgd_amd import _lib
 
     (lr0, lam0), (lr1, lam1) = PAIRS[pair]
-    name = "solo_k64_w2"
     with fresh(mf, name, lr1, lam1, flags=_lib.FLAG_DEVICE_INGEST) as f, \
             fresh(mf, name, lr0, lam0, flags=_lib.FLAG_DEVICE_INGEST) as m:
         assert m.schedule_info()["device_ingest"] == 2 and f.schedule_info()["device_ingest"] == 2

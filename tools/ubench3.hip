@@ -86,6 +86,7 @@ __global__ void __launch_bounds__(192) k(const float* rows_in, const uint32_t* e
         f4 q = *(const f4*)(smem + qaddr);
         const unsigned ea = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(smem + RUN_OFF) + g * 16;
         int pairs = n_steps / 2;
+        uint64_t live, sv;  // scalar temporaries of the run loop's text
         constexpr int EST = GS * 16;
         constexpr int PADV = mfsgd_pad_run(LG);
         asm volatile(MFSGD_RUN_LOOP_ASM_TEXT(EXTRA, SFMA) MFSGD_RUN_LOOP_ASM_OPERANDS);
