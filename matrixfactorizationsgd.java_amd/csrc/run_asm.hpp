@@ -50,6 +50,13 @@
 // and in front of the TAIL head (P = 8, steady pad 0; the tail decides runs shorter than P and the last steps of the others:
 // chain alone at n = 50, cycles per step):
 //     L = 16: 123.0 123.0 123.5 123.4    L = 32: 136.8 136.5 137.0 137.0    L = 64: 148.2 148.3 148.8 148.4
+// The chain wave's two LDS reads behind ONE DPP add and the helper's two reads adjacent (see MFSGD_SOLO_CHAIN_HALF and
+// MFSGD_SOLO_HELPER_PAIR; profiles/chain_scale_ubench3.log, same n, the parent's loops at 111.8 / 127.1 / 141.2 alone and
+// 118.5-121.6 / 132.4-132.8 / 148.5-148.7 as a pair in the sessions of that log), at 0 / 2 / 4 / 6 s_nops in front of the
+// STEADY head (helper as in the parent), the TAIL head (chain alone at n = 50) and the HELPER's head (the pair):
+//     chain alone, steady  L = 16: 101.9 101.9 102.4 102.6    L = 32: 119.1 119.2 119.7 119.9    L = 64: 133.3 133.4 133.9 134.1
+//     chain alone, tail    L = 16: 112.1 112.0 112.5 112.5    L = 32: 128.8 128.6 129.0 129.0    L = 64: 140.5 140.6 141.0 140.6
+//     solo pair,   helper  L = 16: 119.2 109.5 113.3 117.0    L = 32: 122.8 125.3 124.1 124.3    L = 64: 142.1 141.8 141.3 141.2
 // Every loop head is therefore placed explicitly (operands [pad] / [pads], assembly-time constants): the product
 // runs the layout that was timed, whatever code the compiler puts in front of the loop.
 constexpr int mfsgd_pad_run(int lanes) {
@@ -85,7 +92,7 @@ constexpr int mfsgd_pad_helper(int lanes) {
 #ifdef MFSGD_PAD_HELPER
     return MFSGD_PAD_HELPER;
 #else
-    return lanes == 16 ? 6 : 2;  // [r3] the loop that takes the steps in pairs (tools/ubench3, profiles/r03_ubench3.log)
+    return lanes == 16 ? 2 : lanes == 32 ? 0 : 6;  // the pair loop with its two reads adjacent (profiles/chain_scale_ubench3.log)
 #endif
 }
 // A/B pairs of solo chain steps per pass of the chain wave's TAIL loop, an assembly-time constant like the pads (1, 2 or 4:
@@ -351,6 +358,12 @@ static_assert(mfsgd_chain_steady() % 2 == 0 && mfsgd_chain_steady() >= 2 && mfsg
 // v[100:103] q (updated in place); v[104:107] / v[108:111] p row of the even / odd step (prefetched
 // a step ahead); v[116:117] / v[118:119] {lr*r, next slots} of the even / odd step; v113 p address;
 // v[120:121] chunk products, v132 dot, v[122:125] c*q, v130 s.
+// The two wait states behind each of the four DPP adds hold, in order: {p address, c*q01}, {the p-row read, the entry
+// read}, {c*q23, s_nop}, GAP.  Any VALU, SALU or s_nop filler costs such a slot nothing (tools/ubench5.hip,
+// profiles/chain_slots_ubench.log: packed or not); what costs is an LDS instruction -- 8 cycles per GAP that holds
+// one, and no more for a second one beside it -- so the step's two reads share ONE gap (one read in each of two gaps,
+// as this step had them: 111.8 instead of 101.9 cycles at L = 16; both in the next gap down: 107.8).  They are issued in
+// the order they always were, so the counted waits and what the helper sees are unchanged.
 #define MFSGD_SOLO_CHAIN_HALF(P0, P1, P2, P3, N0, N1, N2, N3, ELRR, ESLOT, NEXTE, OFF_NEXT, WAIT, S, S1, GAP, EXTRA, SFMA) \
         "s_waitcnt lgkmcnt(" WAIT ")\n\t" \
         "v_pk_mul_f32 v[120:121], v[" P0 ":" P1 "], v[100:101]\n\t" \
@@ -360,9 +373,9 @@ static_assert(mfsgd_chain_steady() % 2 == 0 && mfsgd_chain_steady() >= 2 && mfsg
         "v_pk_mul_f32 v[122:123], v[100:101], %[c2]\n\t" \
         "v_add_f32_dpp v132, v132, v132 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
         "ds_read_b128 v[" N0 ":" N3 "], v113\n\t" \
-        "v_pk_mul_f32 v[124:125], v[102:103], %[c2]\n\t" \
-        "v_add_f32_dpp v132, v132, v132 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
         "ds_read2_b32 v[" NEXTE "], v138 " OFF_NEXT "\n\t" \
+        "v_add_f32_dpp v132, v132, v132 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+        "v_pk_mul_f32 v[124:125], v[102:103], %[c2]\n\t" \
         "s_nop 0\n\t" \
         "v_add_f32_dpp v132, v132, v132 row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
         GAP \
@@ -598,7 +611,9 @@ static_assert(mfsgd_chain_steady() % 2 == 0 && mfsgd_chain_steady() >= 2 && mfsg
 // always arrives; the bound only keeps a broken schedule from hanging the GPU) -- on return %[spins] == 0 means it
 // gave up and nothing further was written.
 // LDS operations of a pair, in issue order: read p_{t+1}, read the next pair's words, write p'_t, read p_{t+2}, write
-// p'_{t+1}: "all but the last one" at the top of the next pair has its words and its first p row.
+// p'_{t+1}: "all but the last one" at the top of the next pair has its words and its first p row.  The first two reads
+// are ADJACENT instructions (c*p23 behind them, not between them): an LDS instruction that follows VALU work costs the
+// wave about 8 cycles and a second one beside it nothing (tools/ubench5.hip, profiles/chain_slots_ubench.log).
 // NOTHING of the rows is read before s_0 has been posted: the chain wave runs the general and run steps of its sub-cell
 // before the solo run, and they may update the p rows the run is about to use (the helper starts with the sub-round).
 // Once s_0 is there they are final -- only the helper writes them.  (A first version of this loop fetched p_0 in its
@@ -613,8 +628,8 @@ static_assert(mfsgd_chain_steady() % 2 == 0 && mfsgd_chain_steady() >= 2 && mfsg
         "s_cbranch_vccnz 7" TAG "f\n\t" \
         "6" TAG ":\n\t" \
         "ds_read_b128 v[108:111], v113\n\t" \
-        "v_pk_mul_f32 v[128:129], v[106:107], %[c2]\n\t" \
         "ds_read2_b64 v[" N0 ":" N3 "], v138 offset0:4 offset1:6\n\t" \
+        "v_pk_mul_f32 v[128:129], v[106:107], %[c2]\n\t" \
         "v_pk_mul_f32 v[122:123], v[100:101], %[c2]\n\t" \
         "v_pk_mul_f32 v[124:125], v[102:103], %[c2]\n\t" \
         "v_pk_fma_f32 v[134:135], v[" M0 ":" M1 "], v[100:101], v[126:127] op_sel:[1,0,0]\n\t" \

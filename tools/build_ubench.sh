@@ -27,3 +27,5 @@ done
 $HIPCC --offload-arch=gfx950 -O2 -ffp-contract=off -DLG=64 -DOLD64 -Wno-unused-value ubench3.hip -o bin/ub3_64old
 $HIPCC --offload-arch=gfx950 -O2 ubench.hip -o bin/ubench
 $HIPCC --offload-arch=gfx950 -O2 -Wno-unused-value ubench4.hip -o bin/ub4
+# what the two wait-state slots behind a DPP add cost by what fills them (profiles/chain_slots_ubench.log)
+$HIPCC --offload-arch=gfx950 -O2 -Wno-unused-value ubench5.hip -o bin/ub5
