@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver; + mfsgd_set_validation, mfsgd_validation_size, mfsgd_validation_rmse, mfsgd_rmse_pairs, mfsgd_train_early_stop; + mfsgd_row_inv_norms, mfsgd_similar_items, mfsgd_similar_users, mfsgd_similar_rows; + mfsgd_online_levels, mfsgd_apply_ratings (additions: no existing call changed) */
+#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver; + mfsgd_set_validation, mfsgd_validation_size, mfsgd_validation_rmse, mfsgd_rmse_pairs, mfsgd_train_early_stop; + mfsgd_row_inv_norms, mfsgd_similar_items, mfsgd_similar_users, mfsgd_similar_rows; + mfsgd_online_levels, mfsgd_apply_ratings; + mfsgd_fold_in_items, mfsgd_append_users, mfsgd_append_items, mfsgd_reserve_rows, mfsgd_get_capacity (additions: no existing call changed) */
 
 typedef enum mfsgd_status {
     MFSGD_OK = 0,
@@ -132,7 +132,8 @@ int mfsgd_set_ratings(mfsgd_handle* h, const int32_t* u, const int32_t* i, const
  * in caller-owned device blocks (mfsgd_part_* below); pass Q = NULL here.
  * NaN: which entries are NaN is kept, a NaN's sign and payload are not.  Every
  * NaN that enters the library -- a factor given to mfsgd_set_factors,
- * mfsgd_load_factors or mfsgd_dsgd_set_q, a rating given to mfsgd_set_ratings
+ * mfsgd_load_factors, mfsgd_append_users, mfsgd_append_items or
+ * mfsgd_dsgd_set_q, a rating given to mfsgd_set_ratings
  * (in the schedules) or mfsgd_apply_ratings -- is replaced by the quiet NaN
  * 0x7FC00000: the training kernels use the word 0xFFFFFFFF, itself a NaN, as
  * "not posted yet" between two of their waves, and arithmetic hands a NaN
@@ -191,6 +192,17 @@ int mfsgd_recommend_excluding(mfsgd_handle* h, const int32_t* users, int32_t n_u
  * MFSGD_ERR_STATE: n_parts != 1 (the handle does not hold Q), or factors never initialised, set or loaded.
  * n_new == 0 is MFSGD_OK.  Ratings go to the device in batches of whole users of bounded size.                      */
 int mfsgd_fold_in_users(mfsgd_handle* h, int32_t n_new, const int64_t* row_ptr, const int32_t* items, const float* ratings,
+                        int32_t epochs, const float* init_rows, int64_t seed, float* out_rows);
+/* The mirror of mfsgd_fold_in_users: rows for n_new ITEMS that are not in the model, against the model's user factors P,
+ * which stay fixed.  New item x owns the ratings row_ptr[x] .. row_ptr[x + 1] of users / ratings.  Its row starts as
+ * init_rows[x] or, with init_rows == NULL, as row x of the P that mfsgd_init_factors(seed) gives a model of n_new users
+ * (the same draws mfsgd_fold_in_users starts from).  Then, `epochs` times over the item's ratings in the order given:
+ *     p = P[users[j]];  d = dot(row, p);  s = fma(-lr, d, lr * ratings[j]);  row[f] = fma(s, p[f], (1 - lr * lambda) * row[f])
+ * The canonical dot and the update are bitwise symmetric in their two rows, so out_rows is bit for bit what the CPU
+ * oracle's update gives for q.  Checks, their order, the state errors (the call asks for a Q in the handle as well,
+ * for the symmetry of the contract) and the batching are those of mfsgd_fold_in_users; the messages start with
+ * "fold_in_items: " and name the user of a rating where those name its item.  The model is not modified.             */
+int mfsgd_fold_in_items(mfsgd_handle* h, int32_t n_new, const int64_t* row_ptr, const int32_t* users, const float* ratings,
                         int32_t epochs, const float* init_rows, int64_t seed, float* out_rows);
 /* Top-N as mfsgd_recommend_excluding, where "user j" is rows[j] (n_rows x k, dense: for instance what
  * mfsgd_fold_in_users returned) instead of a row of P: every row is answered, in order, and excl_row[x] indexes rows.
@@ -408,6 +420,48 @@ int mfsgd_online_levels(mfsgd_handle* h, const int32_t* u, const int32_t* i, int
                         int32_t* level /* nullable */, mfsgd_online_info* info /* nullable */);
 int mfsgd_apply_ratings(mfsgd_handle* h, const int32_t* u, const int32_t* i, const float* r, int64_t n,
                         float* err /* nullable */, mfsgd_online_info* info /* nullable */);
+
+/* ---- growing a live model: rows appended to P and Q in place -----------------------------------------------------------
+ * mfsgd_append_users / mfsgd_append_items give the model n_new more users / items: the new rows take the indices
+ * old_count .. old_count + n_new - 1, and *first (nullable) receives old_count.  rows: n_new x k, dense -- for instance
+ * what mfsgd_fold_in_users / mfsgd_fold_in_items returned; every NaN in it becomes 0x7FC00000, as in mfsgd_set_factors.
+ * rows == NULL: element f of new row x is draw x * k + f of java.util.Random(seed), nextFloat() * (float)(1/sqrt(k)):
+ * the start rows of a fold-in without init_rows.  The pad columns k .. kp - 1 of a new row are zero.
+ * Where the rows go: with the factors on host staging (no GPU needed) the staging grows; with the factors on the
+ * device everything happens there -- the caller's rows go up through a bounded staging buffer (freed before return)
+ * and a kernel pads them into place (csrc/grow.hip), seeded rows are drawn in place, and no old row crosses PCIe.
+ * What changes: the counts, for everything that reads them -- mfsgd_get_dims, mfsgd_get_factors, mfsgd_save_factors,
+ * the range checks and scan lengths of predict, recommend, rank, similar, fold-in, validation, online updates and
+ * mfsgd_set_ratings, the early-stop snapshot.  What does not: the stored ratings and their identity (the same triples
+ * again are still recognised, nothing is rebuilt), every schedule and mfsgd_get_order, the held-out set, lr and lambda,
+ * the bits of the old rows.  Training afterwards runs the same schedule in the same order -- the order
+ * mfsgd_get_order returns -- and does not touch the new rows, which have no ratings.  A fresh handle created at the
+ * grown size may cut its blocks differently: the grown handle is NOT byte-equal to such a build, it is equal to the
+ * oracle run over its own order.  A later mfsgd_set_ratings with other triples may name the new indices and builds a
+ * schedule for the grown sizes as usual.
+ * Capacity: a handle has a capacity per side, at least its count and equal to it until mfsgd_reserve_rows asks for
+ * more; the device buffers hold capacity x kp floats, and rows from the count on are never read and never observable.
+ * Without a reserve call device memory use is exactly what it is without these calls.  mfsgd_reserve_rows raises a
+ * capacity to at least the value given and never shrinks it (a value at or below the current capacity, 0 included,
+ * leaves that side alone).  It works in every factor state: before the factors are on the device it records the
+ * number, and they are allocated with it when they get there; with the factors on the device it reallocates now.
+ * Re-seeding or replacing the factors keeps the capacity.
+ * An append that fits the capacity writes the new rows in place: P and Q keep their addresses, so the cached training
+ * graphs, which hold those addresses (and nothing that derives from the counts), stay valid and the next mfsgd_train
+ * replays them.  An append beyond the capacity reallocates that side to exactly max(count + n_new, reserve): it waits
+ * for the handle's stream, allocates the new buffer, copies the old rows device to device, writes the new ones,
+ * synchronises, drops the training graphs (they hold the dead pointer; the next mfsgd_train captures again) and frees
+ * the old buffer.  The new buffer is allocated BEFORE the old one is released: peak device use during a reallocating
+ * append (or reserve) is old + new, and a failed allocation is MFSGD_ERR_OOM with the model exactly as it was.  Growth
+ * policy beyond the reserve is the caller's: the library never over-allocates on its own.
+ * Checks, in this order.  MFSGD_ERR_INVALID_ARG ("append_users: ..." / "append_items: ..." / "reserve_rows: ..."): a
+ * negative n_new or capacity, a count that would exceed INT32_MAX.  MFSGD_ERR_STATE: n_parts != 1; for the appends also
+ * factors never initialised, set or loaded, or no Q (after mfsgd_init_p_offset).  n_new == 0 is MFSGD_OK and touches
+ * nothing; *first is still set.                                                                                      */
+int mfsgd_append_users(mfsgd_handle* h, int32_t n_new, const float* rows /* nullable */, int64_t seed, int32_t* first /* nullable */);
+int mfsgd_append_items(mfsgd_handle* h, int32_t n_new, const float* rows /* nullable */, int64_t seed, int32_t* first /* nullable */);
+int mfsgd_reserve_rows(mfsgd_handle* h, int32_t user_capacity, int32_t item_capacity);
+int mfsgd_get_capacity(const mfsgd_handle* h, int32_t* users, int32_t* items);   /* either may be NULL */
 
 /* Timed variant used by bench.py: runs `epochs` training passes bracketed by
  * HIP events on the handle's stream and returns the elapsed device time and

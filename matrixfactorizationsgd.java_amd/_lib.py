@@ -120,6 +120,7 @@ SIGNATURES = {
     "mfsgd_recommend": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i32p, _f32p]),
     "mfsgd_recommend_excluding": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i32p, _i32p, C.c_int64, _i32p, _f32p]),
     "mfsgd_fold_in_users": (C.c_int, [_H, C.c_int32, _i64p, _i32p, _f32p, C.c_int32, _f32p, C.c_int64, _f32p]),
+    "mfsgd_fold_in_items": (C.c_int, [_H, C.c_int32, _i64p, _i32p, _f32p, C.c_int32, _f32p, C.c_int64, _f32p]),
     "mfsgd_recommend_rows": (C.c_int, [_H, _f32p, C.c_int32, C.c_int32, _i32p, _i32p, C.c_int64, _i32p, _f32p]),
     "mfsgd_rank_items": (C.c_int, [_H, _i32p, _i32p, C.c_int64, _i32p, _i32p, C.c_int64, _i32p]),
     "mfsgd_rank_items_rows": (C.c_int, [_H, _f32p, C.c_int32, _i32p, _i32p, C.c_int64, _i32p, _i32p, C.c_int64, _i32p]),
@@ -143,6 +144,10 @@ SIGNATURES = {
                                          _i32p, _i32p]),
     "mfsgd_online_levels": (C.c_int, [_H, _i32p, _i32p, C.c_int64, _i32p, C.POINTER(OnlineInfo)]),
     "mfsgd_apply_ratings": (C.c_int, [_H, _i32p, _i32p, _f32p, C.c_int64, _f32p, C.POINTER(OnlineInfo)]),
+    "mfsgd_append_users": (C.c_int, [_H, C.c_int32, _f32p, C.c_int64, _i32p]),
+    "mfsgd_append_items": (C.c_int, [_H, C.c_int32, _f32p, C.c_int64, _i32p]),
+    "mfsgd_reserve_rows": (C.c_int, [_H, C.c_int32, C.c_int32]),
+    "mfsgd_get_capacity": (C.c_int, [_H, _i32p, _i32p]),
     "mfsgd_ratings_file_open": (C.c_int, [C.c_char_p, C.c_int32, C.POINTER(_H)]),
     "mfsgd_ratings_file_info": (C.c_int, [_H, _i64p, _i32p, _i32p]),
     "mfsgd_ratings_file_read": (C.c_int, [_H, _i32p, _i32p, _f32p, _i64p, _i64p]),

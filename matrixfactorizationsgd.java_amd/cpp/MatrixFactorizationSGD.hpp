@@ -94,6 +94,34 @@ class MatrixFactorizationSGD {
         if (row_ptr.empty() || init.size() != (row_ptr.size() - 1) * (size_t)k_) throw std::invalid_argument("length mismatch");
         return foldIn(row_ptr, items, ratings, epochs, init.data(), 0);
     }
+    // float[] foldInItems(long[] rowPtr, int[] users, float[] ratings, int epochs[, float[] init]): the same for items that
+    // are not in the model, against the fixed user factors
+    std::vector<float> foldInItems(const std::vector<int64_t>& row_ptr, const std::vector<int32_t>& users,
+                                   const std::vector<float>& ratings, int epochs, int64_t seed) {
+        return foldIn(row_ptr, users, ratings, epochs, nullptr, seed, mfsgd_fold_in_items);
+    }
+    std::vector<float> foldInItems(const std::vector<int64_t>& row_ptr, const std::vector<int32_t>& users,
+                                   const std::vector<float>& ratings, int epochs, const std::vector<float>& init) {
+        if (row_ptr.empty() || init.size() != (row_ptr.size() - 1) * (size_t)k_) throw std::invalid_argument("length mismatch");
+        return foldIn(row_ptr, users, ratings, epochs, init.data(), 0, mfsgd_fold_in_items);
+    }
+    // int addUsers(float[] rows) / addUsers(int n, long seed), addItems likewise: rows (n x k; for instance a fold-in's)
+    // or n seeded rows appended to the live model, nothing rebuilt; returns the index of the first new row
+    int addUsers(const std::vector<float>& rows) { return append(mfsgd_append_users, users_, &rows, 0, 0); }
+    int addUsers(int n, int64_t seed) { return append(mfsgd_append_users, users_, nullptr, n, seed); }
+    int addItems(const std::vector<float>& rows) { return append(mfsgd_append_items, items_, &rows, 0, 0); }
+    int addItems(int n, int64_t seed) { return append(mfsgd_append_items, items_, nullptr, n, seed); }
+    // void reserve(int users, int items): room for that many in all (0: leave that side alone), so that appends up to
+    // there keep P and Q where they are, and with them the cached training graphs
+    void reserve(int users, int items) { check(mfsgd_reserve_rows(h_, users, items)); }
+    // int[] capacity(): {users, items}
+    std::pair<int, int> capacity() {
+        int32_t u = 0, i = 0;
+        check(mfsgd_get_capacity(h_, &u, &i));
+        return {u, i};
+    }
+    int users() const { return users_; }
+    int items() const { return items_; }
     // int[][] recommendRows(float[] rows, int topN, int[] exclRow, int[] exclItem): recommend for rows (n x k) that are
     // not in the model, such as foldIn's; exclRow indexes rows
     std::pair<std::vector<int32_t>, std::vector<float>> recommendRows(const std::vector<float>& rows, int topn,
@@ -365,14 +393,26 @@ class MatrixFactorizationSGD {
     }
 
    private:
-    std::vector<float> foldIn(const std::vector<int64_t>& row_ptr, const std::vector<int32_t>& items,
-                              const std::vector<float>& ratings, int epochs, const float* init, int64_t seed) {
-        if (row_ptr.empty() || items.size() != ratings.size() || (int64_t)items.size() != row_ptr.back())
+    using FoldInCall = int (*)(mfsgd_handle*, int32_t, const int64_t*, const int32_t*, const float*, int32_t, const float*,
+                               int64_t, float*);
+    std::vector<float> foldIn(const std::vector<int64_t>& row_ptr, const std::vector<int32_t>& ids,
+                              const std::vector<float>& ratings, int epochs, const float* init, int64_t seed,
+                              FoldInCall call = mfsgd_fold_in_users) {
+        if (row_ptr.empty() || ids.size() != ratings.size() || (int64_t)ids.size() != row_ptr.back())
             throw std::invalid_argument("length mismatch");
         std::vector<float> rows((row_ptr.size() - 1) * (size_t)k_);
-        check(mfsgd_fold_in_users(h_, (int32_t)(row_ptr.size() - 1), row_ptr.data(), items.data(), ratings.data(), epochs, init,
-                                  seed, rows.data()));
+        check(call(h_, (int32_t)(row_ptr.size() - 1), row_ptr.data(), ids.data(), ratings.data(), epochs, init, seed,
+                   rows.data()));
         return rows;
+    }
+    int append(int (*call)(mfsgd_handle*, int32_t, const float*, int64_t, int32_t*), int& count, const std::vector<float>* rows,
+               int n, int64_t seed) {
+        if (rows && rows->size() % (size_t)k_ != 0) throw std::invalid_argument("rows must be n x k");
+        if (rows) n = (int)(rows->size() / (size_t)k_);
+        int32_t first = -1;
+        check(call(h_, n, rows ? rows->data() : nullptr, seed, &first));
+        count += n;
+        return first;
     }
     void check(int rc) {
         if (rc != MFSGD_OK) throw std::runtime_error(mfsgd_last_error(h_));

@@ -1,7 +1,9 @@
-// foldin.hip -- fold-in of new users against fixed item factors ("Fold-in"): the P half of the canonical
-// update of section 3, run over each new user's ratings alone.  Q is only read, new users are independent of each
-// other, so there is no block schedule and no LDS image: one lane group of L lanes per user keeps that user's row in
-// registers for the whole chain, fed by a gather of Q rows that runs kFoldDepth steps ahead of the arithmetic.
+// foldin.hip -- fold-in of new rows against the fixed factors of the other side ("Fold-in"): one half of
+// the canonical update of section 3, run over each new row's ratings alone.  New users are folded in against Q, new
+// items against P: the update is symmetric in its two rows and both matrices have the stride kp, so the kernel reads
+// "the fixed side" F and never asks which it is.  F is only read, new rows are independent of each other, so there is
+// no block schedule and no LDS image: one lane group of L lanes per new row keeps that row in registers for the whole
+// chain, fed by a gather of F rows that runs kFoldDepth steps ahead of the arithmetic.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -15,21 +17,21 @@
 namespace mfsgd {
 namespace {
 
-// Steps the Q gather runs ahead of the chain; the (item, rating) stream runs another kFoldDepth ahead of the gather,
-// since a Q address needs its item first.
+// Steps the F gather runs ahead of the chain; the (id, rating) stream runs another kFoldDepth ahead of the gather,
+// since an F address needs its id first.
 constexpr int kFoldDepth = 8;
 
-// Group g of the launch folds in user perm[g] of the batch: ratings row_ptr[x] - base .. row_ptr[x + 1] - base of
-// items / ratings, row `rows + x * k` (dense; read once at the start, written once at the end).
+// Group g of the launch folds in new row perm[g] of the batch: ratings row_ptr[x] - base .. row_ptr[x + 1] - base of
+// ids / ratings, row `rows + x * k` (dense; read once at the start, written once at the end).
 // The chain of a group is its list repeated `epochs` times: len * epochs steps, the position in the list wrapping
 // round.  Every lane runs the trip count of the longest chain in its wave (the DPP levels of group_allreduce need
 // their partner lanes live); a group whose chain has ended keeps loading, from its own list, and keeps its row by a
 // select.
 template <int L, int D>
-__global__ void __launch_bounds__(256) fold_in_kernel(const float* __restrict__ Q, float* __restrict__ rows, const int k,
+__global__ void __launch_bounds__(256) fold_in_kernel(const float* __restrict__ F, float* __restrict__ rows, const int k,
                                                       const long long* __restrict__ row_ptr, const long long base,
                                                       const int32_t* __restrict__ perm, const int nb,
-                                                      const int32_t* __restrict__ items,
+                                                      const int32_t* __restrict__ ids,
                                                       const float* __restrict__ ratings, const int epochs,
                                                       const float lr, const float c) {
     constexpr int KP = 4 * L;
@@ -65,19 +67,19 @@ __global__ void __launch_bounds__(256) fold_in_kernel(const float* __restrict__ 
         long long ja = 0;  // position in the list of the next entry to fetch
         int it[D];         // entries of steps t + D .. t + 2D - 1
         float rr[D];
-        float4 q[D];       // Q rows and lr * rating of steps t .. t + D - 1
+        float4 q[D];       // F rows and lr * rating of steps t .. t + D - 1
         float sr[D];
         // The entry stream is read with relaxed atomic loads of wavefront scope: the same global_load instructions, but
         // the compiler leaves them where they are written.  With plain loads it moves every load of the pipeline next to
         // its use (it carries the positions round the loop instead of the loaded values), and each step then waits for
-        // an item and after that for its Q row.
+        // an id and after that for its F row.
         auto fetch_entry = [&](int d) {
-            it[d] = __hip_atomic_load(items + first + ja, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            it[d] = __hip_atomic_load(ids + first + ja, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
             rr[d] = __hip_atomic_load(ratings + first + ja, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
             ja = ja + 1 == wrap ? 0 : ja + 1;
         };
         auto fetch_row = [&](int d) {
-            q[d] = *reinterpret_cast<const float4*>(Q + (size_t)it[d] * KP + lig * 4);
+            q[d] = *reinterpret_cast<const float4*>(F + (size_t)it[d] * KP + lig * 4);
             sr[d] = lr * rr[d];
         };
 #pragma unroll
@@ -117,14 +119,14 @@ __global__ void __launch_bounds__(256) fold_in_kernel(const float* __restrict__ 
 
 }  // namespace
 
-hipError_t launch_fold_in(int L, const float* Q, float* rows, int k, const long long* row_ptr, long long base,
-                          const int32_t* perm, int nb, const int32_t* items, const float* ratings, int epochs, float lr,
+hipError_t launch_fold_in(int L, const float* F, float* rows, int k, const long long* row_ptr, long long base,
+                          const int32_t* perm, int nb, const int32_t* ids, const float* ratings, int epochs, float lr,
                           float c, hipStream_t st) {
     if (nb <= 0) return hipSuccess;
     const int gpb = 256 / L;
     const dim3 grid((unsigned)((nb + gpb - 1) / gpb)), block(256);
     return with_L(L, [&](auto l) {
-        hipLaunchKernelGGL((fold_in_kernel<l(), kFoldDepth>), grid, block, 0, st, Q, rows, k, row_ptr, base, perm, nb, items,
+        hipLaunchKernelGGL((fold_in_kernel<l(), kFoldDepth>), grid, block, 0, st, F, rows, k, row_ptr, base, perm, nb, ids,
                            ratings, epochs, lr, c);
         return hipGetLastError();
     });

@@ -1,9 +1,11 @@
 // handle.cpp -- the handle of the C-ABI (include/mfsgd.h): its life cycle, the error channel, device bring-up, and
-// the factors (seed, set, get, upload).
+// the factors (seed, set, get, upload, and growing them: rows appended in place, capacity).
 //
 // No reference counterpart exists; the surface follows SURVEY.md section 8b.  There is no CPU
 // compute path in this library: every compute entry point needs a gfx950
 // device and fails with MFSGD_ERR_NO_DEVICE otherwise.
+#include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -101,14 +103,24 @@ static void release_device_factors(mfsgd_handle* h) {
 }
 
 // factors host <-> device -------------------------------------------------------
+// The staged rows of one side into a buffer of `capacity` rows (mfsgd_reserve_rows; the count where nothing is reserved,
+// and then this is upload()).
+static int upload_with_capacity(mfsgd_handle* h, DevBuf& b, const std::vector<float>& v, int32_t capacity) {
+    const size_t bytes = std::max(v.size(), (size_t)capacity * (size_t)h->geo.kp) * sizeof(float);
+    int rc = dev_alloc(h, b, bytes);
+    if (rc) return rc;
+    if (!v.empty()) HIPCHK(h, hipMemcpy(b.get(), v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
+    return MFSGD_OK;
+}
+
 int factors_to_device(mfsgd_handle* h) {
     int rc = ensure_device(h);
     if (rc) return rc;
     if (h->where == mfsgd_handle::Where::Device) return MFSGD_OK;
     if (h->where == mfsgd_handle::Where::None)
         return fail(h, MFSGD_ERR_STATE, "factors not initialised: call mfsgd_init_factors or mfsgd_set_factors");
-    if ((rc = upload(h, h->dP, h->hP))) return rc;
-    if (h->n_parts == 1 && (rc = upload(h, h->dQ, h->hQ))) return rc;
+    if ((rc = upload_with_capacity(h, h->dP, h->hP, h->user_capacity()))) return rc;
+    if (h->n_parts == 1 && (rc = upload_with_capacity(h, h->dQ, h->hQ, h->item_capacity()))) return rc;
     h->where = mfsgd_handle::Where::Device;
     std::vector<float>().swap(h->hP);
     std::vector<float>().swap(h->hQ);
@@ -134,11 +146,11 @@ static int seed_factors(mfsgd_handle* h, int64_t seed, int64_t u_offset, bool wi
     h->have_q = with_q;
     if (ensure_device(h) == MFSGD_OK) {
         int rc;
-        if ((rc = dev_alloc(h, h->dP, sizeof(float) * (size_t)h->cfg.n_users * kp))) return rc;
+        if ((rc = dev_alloc(h, h->dP, sizeof(float) * (size_t)h->user_capacity() * kp))) return rc;
         HIPCHK(h, launch_init_rows(h->dP.as<float>(), h->cfg.n_users, k, kp, seed, (unsigned long long)u_offset * (unsigned long long)k,
                                    scale, h->stream));
         if (with_q) {
-            if ((rc = dev_alloc(h, h->dQ, sizeof(float) * (size_t)h->cfg.n_items * kp))) return rc;
+            if ((rc = dev_alloc(h, h->dQ, sizeof(float) * (size_t)h->item_capacity() * kp))) return rc;
             HIPCHK(h, launch_init_rows(h->dQ.as<float>(), h->cfg.n_items, k, kp, seed,
                                        (unsigned long long)h->cfg.n_users * (unsigned long long)k, scale, h->stream));
         }
@@ -161,6 +173,98 @@ static int seed_factors(mfsgd_handle* h, int64_t seed, int64_t u_offset, bool wi
         fill_rows(gq, h->hQ.data(), h->cfg.n_items, k, kp, scale);
     }
     h->where = mfsgd_handle::Where::Host;
+    return MFSGD_OK;
+}
+
+// Growing a live model ("Growing a live model") -----------------------------------------------------------
+// A buffer of new_rows rows that starts with the `rows` rows `old` holds: after a wait for the handle's stream, copied
+// device to device on it (asynchronous: the caller synchronises before it lets go of `old`).  Allocated before anything
+// is released, so a failure leaves the model as it was.
+static int grown_copy(mfsgd_handle* h, const char* prefix, const DevBuf& old, int64_t rows, int64_t new_rows, DevBuf& grown) {
+    auto bad = [h, prefix](hipError_t e) { return serve_fail(h, prefix, e); };
+    const size_t row_bytes = sizeof(float) * (size_t)h->geo.kp;
+    HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
+    if (const int rc = dev_alloc(h, grown, (size_t)new_rows * row_bytes)) return rc;
+    HIPCHK_OR(bad, hipMemcpyAsync(grown.get(), old.get(), (size_t)rows * row_bytes, hipMemcpyDeviceToDevice, h->stream));
+    return MFSGD_OK;
+}
+
+// The grown buffer takes the place of the old one: nothing runs on either (the caller has synchronised), and the
+// training graphs, which hold the old pointer, go first.
+static void adopt(mfsgd_handle* h, DevBuf& buf, DevBuf& grown) {
+    for (Part& p : h->parts) p.drop_graphs();
+    buf = std::move(grown);
+}
+
+// Dense rows of the caller's per staging buffer of an append: 32 MB
+constexpr int64_t kAppendStageFloats = (int64_t)1 << 23;
+
+// n_new rows (rows: n_new x k dense, or null: seeded) behind the `count` rows at dst_base, on the handle's stream; the
+// caller's rows go up in pieces through a staging buffer that is gone when this returns.
+static int write_new_rows(mfsgd_handle* h, const char* prefix, float* dst_base, int64_t count, int32_t n_new, const float* rows,
+                          int64_t seed) {
+    auto bad = [h, prefix](hipError_t e) { return serve_fail(h, prefix, e); };
+    const int k = h->cfg.k, kp = h->geo.kp;
+    float* dst = dst_base + (size_t)count * kp;
+    if (!rows) {
+        HIPCHK_OR(bad, launch_init_rows(dst, n_new, k, kp, seed, 0, (float)(1.0 / std::sqrt((double)k)), h->stream));
+        return MFSGD_OK;
+    }
+    const int64_t piece = std::min<int64_t>(n_new, std::max<int64_t>(1, kAppendStageFloats / k));
+    DevBuf stage;
+    if (const int rc = dev_alloc(h, stage, sizeof(float) * (size_t)piece * k)) return rc;
+    for (int64_t x0 = 0; x0 < n_new; x0 += piece) {
+        const int64_t nb = std::min<int64_t>(piece, n_new - x0);
+        HIPCHK_OR(bad, hipMemcpyAsync(stage.get(), rows + x0 * k, sizeof(float) * (size_t)nb * k, hipMemcpyHostToDevice, h->stream));
+        HIPCHK_OR(bad, launch_place_rows(dst + (size_t)x0 * kp, stage.as<const float>(), nb, k, kp, h->stream));
+        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // the staging buffer is reused, and freed on return
+    }
+    return MFSGD_OK;
+}
+
+// Body of mfsgd_append_users / mfsgd_append_items.
+static int append_rows(mfsgd_handle* h, bool items, const char* name, int32_t n_new, const float* rows, int64_t seed,
+                       int32_t* first) {
+    const std::string call = std::string(name) + ": ";
+    int32_t& count = items ? h->cfg.n_items : h->cfg.n_users;
+    if (n_new < 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "n_new is negative");
+    if ((int64_t)count + n_new > (int64_t)INT32_MAX)
+        return fail(h, MFSGD_ERR_INVALID_ARG, call + "the number of " + (items ? "items" : "users") + " would exceed INT32_MAX");
+    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, call + "single-partition handles only");
+    if (h->where == mfsgd_handle::Where::None) return fail(h, MFSGD_ERR_STATE, call + "factors not initialised");
+    if (const int rc = check_has_q(h, name)) return rc;
+    if (first) *first = count;
+    if (n_new == 0) return MFSGD_OK;
+    const int k = h->cfg.k, kp = h->geo.kp;
+    const int64_t need = (int64_t)count + n_new;
+    std::vector<int32_t>& last = items ? h->online_last_i : h->online_last_u;
+    if (!last.empty()) last.reserve((size_t)need);  // (what can fail comes before anything changes)
+    if (h->where == mfsgd_handle::Where::Host) {
+        std::vector<float>& v = items ? h->hQ : h->hP;
+        const size_t old = v.size();
+        v.resize(old + (size_t)n_new * kp, 0.0f);
+        if (rows) {
+            for (int64_t x = 0; x < n_new; ++x)
+                for (int f = 0; f < k; ++f) v[old + (size_t)x * kp + f] = canon_nan(rows[x * k + f]);
+        } else {
+            JRandom g(seed);
+            fill_rows(g, v.data() + old, n_new, k, kp, (float)(1.0 / std::sqrt((double)k)));
+        }
+    } else {
+        int rc = ensure_device(h);
+        if (rc) return rc;
+        auto bad = [h, &call](hipError_t e) { return serve_fail(h, call.c_str(), e); };
+        DevBuf& buf = items ? h->dQ : h->dP;
+        DevBuf grown;  // beyond the capacity: to exactly what is needed (the capacity is at least the reserve)
+        if (need > (items ? h->item_capacity() : h->user_capacity()) && (rc = grown_copy(h, call.c_str(), buf, count, need, grown)))
+            return rc;
+        if ((rc = write_new_rows(h, call.c_str(), grown ? grown.as<float>() : buf.as<float>(), count, n_new, rows, seed))) return rc;
+        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
+        if (grown) adopt(h, buf, grown);
+    }
+    count = (int32_t)need;
+    if (items && !h->parts.empty()) h->parts[0].q_rows = count;
+    if (!last.empty()) last.resize((size_t)need, 0);
     return MFSGD_OK;
 }
 
@@ -319,6 +423,51 @@ int mfsgd_get_factors(mfsgd_handle* h, float* P, float* Q) {
             if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "get_factors: Q lives in caller-owned blocks when n_parts > 1");
             for (int64_t x = 0; x < h->cfg.n_items; ++x) std::memcpy(Q + x * k, &(*sq)[(size_t)x * kp], sizeof(float) * (size_t)k);
         }
+        return MFSGD_OK;
+    });
+}
+
+int mfsgd_append_users(mfsgd_handle* h, int32_t n_new, const float* rows, int64_t seed, int32_t* first) {
+    return guarded(h, "append_users", [&]() -> int { return append_rows(h, false, "append_users", n_new, rows, seed, first); });
+}
+
+int mfsgd_append_items(mfsgd_handle* h, int32_t n_new, const float* rows, int64_t seed, int32_t* first) {
+    return guarded(h, "append_items", [&]() -> int { return append_rows(h, true, "append_items", n_new, rows, seed, first); });
+}
+
+int mfsgd_reserve_rows(mfsgd_handle* h, int32_t user_capacity, int32_t item_capacity) {
+    return guarded(h, "reserve_rows", [&]() -> int {
+        if (user_capacity < 0 || item_capacity < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "reserve_rows: a capacity is negative");
+        if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "reserve_rows: single-partition handles only");
+        // with the factors on the device a larger capacity is a larger buffer now; before that it is a number
+        // factors_to_device and seed_factors read
+        struct Side {
+            DevBuf& buf;
+            int32_t count, capacity, want;
+            int32_t& reserved;
+        } sides[2] = {{h->dP, h->cfg.n_users, h->user_capacity(), user_capacity, h->reserved_users},
+                      {h->dQ, h->cfg.n_items, h->item_capacity(), item_capacity, h->reserved_items}};
+        for (Side& s : sides) {
+            if (s.want <= s.capacity) continue;
+            if (h->where == mfsgd_handle::Where::Device && s.buf) {
+                int rc = ensure_device(h);
+                if (rc) return rc;
+                DevBuf grown;
+                if ((rc = grown_copy(h, "reserve_rows: ", s.buf, s.count, s.want, grown))) return rc;
+                const hipError_t e = hipStreamSynchronize(h->stream);
+                if (e != hipSuccess) return serve_fail(h, "reserve_rows: ", e);
+                adopt(h, s.buf, grown);
+            }
+            s.reserved = s.want;
+        }
+        return MFSGD_OK;
+    });
+}
+
+int mfsgd_get_capacity(const mfsgd_handle* h, int32_t* users, int32_t* items) {
+    return guarded(h, "get_capacity", [&]() -> int {
+        if (users) *users = h->user_capacity();
+        if (items) *items = h->item_capacity();
         return MFSGD_OK;
     });
 }

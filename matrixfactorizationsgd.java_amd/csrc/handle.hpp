@@ -88,6 +88,14 @@ struct mfsgd_handle {
     // The handle holds a Q of its own: single-partition handles after mfsgd_init_factors, mfsgd_set_factors or
     // mfsgd_load_factors.  Not after mfsgd_init_p_offset, which seeds P alone (check_has_q).
     bool have_q = false;
+    // Rows the caller reserved per side (mfsgd_reserve_rows; 0: none).  The device buffers hold user_capacity() /
+    // item_capacity() rows of kp floats: the count, or the reserve where that is larger.  Rows from the count on are
+    // written by an append before anything reads them.
+    int32_t reserved_users = 0, reserved_items = 0;
+    int32_t user_capacity() const { return cfg.n_users > reserved_users ? cfg.n_users : reserved_users; }
+    int32_t item_capacity() const { return cfg.n_items > reserved_items ? cfg.n_items : reserved_items; }
+    size_t p_bytes() const { return sizeof(float) * (size_t)cfg.n_users * (size_t)geo.kp; }  // the rows P has
+    size_t q_bytes() const { return sizeof(float) * (size_t)cfg.n_items * (size_t)geo.kp; }
 
     mfsgd::Validation val;
     // Online updates (mfsgd_online_levels, mfsgd_apply_ratings): per user / per item, 1 + the level of the latest rating

@@ -1,5 +1,5 @@
 // kernels.hpp -- host-callable launchers of every kernel unit: epoch.hip, cells.hip, kernels.hip, foldin.hip,
-// online.hip, rehyper.hip, recommend.hip, rank.hip, similar.hip and validate.hip.
+// online.hip, rehyper.hip, recommend.hip, rank.hip, similar.hip, validate.hip and grow.hip.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -45,14 +45,15 @@ hipError_t launch_reduce_sse(const double* partial, int64_t n, double* out, hipS
 hipError_t launch_predict(int L, const float* P, const float* Q, const int32_t* u, const int32_t* i,
                           float* out, int64_t n, hipStream_t st);
 
-// foldin.hip.  Fold-in of the nb users of one batch against fixed item factors Q (kp-padded rows): group g takes user
-// x = perm[g], whose ratings are entries row_ptr[x] - base .. row_ptr[x + 1] - base of items / ratings (row_ptr: nb + 1
-// words), and runs `epochs` passes of the P half of the canonical update over them, in the order given.
+// foldin.hip.  Fold-in of the nb new rows of one batch against the fixed side's factors F (kp-padded rows: Q for new
+// users, P for new items -- the update is symmetric in its two rows): group g takes new row x = perm[g], whose ratings
+// are entries row_ptr[x] - base .. row_ptr[x + 1] - base of ids / ratings (row_ptr: nb + 1 words; ids name rows of F),
+// and runs `epochs` passes of its half of the canonical update over them, in the order given.
 // rows: nb x k dense, the start rows on entry and the folded rows on return.  perm is best sorted by length, longest
-// first (a wave runs as long as its longest user); the result does not depend on it.  The batch holds at least one
-// rating, and every item is a row of Q: the caller checks.
-hipError_t launch_fold_in(int L, const float* Q, float* rows, int k, const long long* row_ptr, long long base,
-                          const int32_t* perm, int nb, const int32_t* items, const float* ratings, int epochs, float lr,
+// first (a wave runs as long as its longest list); the result does not depend on it.  The batch holds at least one
+// rating, and every id is a row of F: the caller checks.
+hipError_t launch_fold_in(int L, const float* F, float* rows, int k, const long long* row_ptr, long long base,
+                          const int32_t* perm, int nb, const int32_t* ids, const float* ratings, int epochs, float lr,
                           float c, hipStream_t st);
 
 // online.hip.  Levels l0 .. l1 - 1 of one piece of an online update against the live P and Q (kp-padded rows): level l is
@@ -75,6 +76,12 @@ hipError_t launch_rehyper(const CellDesc* cells, const SubDesc* subs, Entry* ent
 // rows x kp floats: java.util.Random(seed) draws first_pos + row * k ... scaled, zero padded (device-side seeding).
 hipError_t launch_init_rows(float* dst, long long rows, int k, int kp, long long seed, unsigned long long first_pos, float scale,
                             hipStream_t st);
+
+// grow.hip.  dst[x * kp + f] = canon_nan(src[x * k + f]) for f < k and 0.0f for k <= f < kp, x = 0 .. rows - 1: dense
+// rows of the caller's (src: device memory) into kp-padded rows of the live factors (dst: 16-byte aligned, as every row
+// of a kp-strided matrix is).  16-byte stores throughout; 16-byte loads where k is a multiple of 4 and src is aligned.
+// Asynchronous on st.
+hipError_t launch_place_rows(float* dst, const float* src, long long rows, int k, int kp, hipStream_t st);
 
 // Diagnostic (tests): `workgroups` one-wave workgroups, each holding lds_bytes of LDS, spin for `ticks` x 10 ns.
 // `started` (device-accessible host memory, or null): every workgroup adds one to it as it starts

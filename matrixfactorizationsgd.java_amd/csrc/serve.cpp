@@ -1,6 +1,6 @@
 // serve.cpp -- what a trained model answers: predictions, top-N recommendations, cosine neighbours of items and users,
-// ranks of held-out items and their metrics, and the fold-in of new users.  Every call batches its work through bounded
-// staging buffers.
+// ranks of held-out items and their metrics, and the fold-in of new users and new items.  Every call batches its work
+// through bounded staging buffers.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -341,9 +341,95 @@ static int metrics_fail(int code, const std::string& msg) {
     return code;
 }
 
-// Ratings of one fold-in batch (whole users; a single user longer than this is a batch of its own): 32 MB of staging
+// Ratings of one fold-in batch (whole lists; a single list longer than this is a batch of its own): 32 MB of staging
 constexpr int64_t kFoldChunk = (int64_t)1 << 22;
-constexpr int64_t kFoldUsers = (int64_t)1 << 20;  // ... and its users, so that a run of empty users is bounded too
+constexpr int64_t kFoldRows = (int64_t)1 << 20;  // ... and its new rows, so that a run of empty lists is bounded too
+
+// Body of the fold-in calls: n_new rows of one side against the fixed factors of the other.  `fixed` says where those
+// are once the factors are on the device (asked then, not before: the upload creates them), n_fixed is their row
+// count, and `what` how the call speaks of itself, of a new row and of an id.
+struct FoldName {
+    const char* call;   // "fold_in"
+    const char* row;    // "user": what a new row is
+    const char* id;     // "item": what a rating names on the fixed side
+    const char* ids;    // "items"
+};
+constexpr FoldName kFoldInUsers{"fold_in", "user", "item", "items"}, kFoldInItems{"fold_in_items", "item", "user", "users"};
+
+static int fold_in_core(mfsgd_handle* h, const FoldName& what, const DevBuf mfsgd_handle::*fixed, int32_t n_fixed, int32_t n_new,
+                        const int64_t* row_ptr, const int32_t* ids, const float* ratings, int32_t epochs, const float* init_rows,
+                        int64_t seed, float* out_rows) {
+    const std::string call = std::string(what.call) + ": ";
+    if (n_new < 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "n_new is negative");
+    if (epochs < 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "epochs is negative");
+    if (n_new > 0 && (!row_ptr || !out_rows)) return fail(h, MFSGD_ERR_INVALID_ARG, call + "row_ptr or out_rows is null");
+    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, call + "single-partition handles only");
+    if (h->where == mfsgd_handle::Where::None)  // (asked here: factors_to_device wants a device first)
+        return fail(h, MFSGD_ERR_STATE, call + "factors not initialised");
+    if (const int rc = check_has_q(h, what.call)) return rc;
+    if (n_new == 0) return MFSGD_OK;
+    if (row_ptr[0] != 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "row_ptr[0] is not 0");
+    for (int32_t x = 0; x < n_new; ++x)
+        if (row_ptr[x + 1] < row_ptr[x])
+            return fail(h, MFSGD_ERR_INVALID_ARG, call + "row_ptr decreases at " + what.row + " " + std::to_string(x));
+    const int64_t total = row_ptr[n_new];
+    if (total > 0 && (!ids || !ratings)) return fail(h, MFSGD_ERR_INVALID_ARG, call + what.ids + " or ratings is null");
+    for (int64_t j = 0; j < total; ++j)
+        if (ids[j] < 0 || ids[j] >= n_fixed)
+            return fail(h, MFSGD_ERR_INVALID_ARG, call + what.id + " of rating " + std::to_string(j) + " out of range");
+    int rc = factors_to_device(h);
+    if (rc) return rc;
+    const int k = h->cfg.k;
+    // batches of whole lists, in the caller's order, so that each batch is one contiguous piece of ids / ratings
+    std::vector<int32_t> cut{0};
+    int64_t max_ratings = 0, max_rows = 0;
+    for (int32_t x0 = 0; x0 < n_new;) {
+        int32_t x1 = x0 + 1;
+        while (x1 < n_new && x1 - x0 < kFoldRows && row_ptr[x1 + 1] - row_ptr[x0] <= kFoldChunk) ++x1;
+        max_ratings = std::max<int64_t>(max_ratings, row_ptr[x1] - row_ptr[x0]);
+        max_rows = std::max<int64_t>(max_rows, x1 - x0);
+        cut.push_back(x1);
+        x0 = x1;
+    }
+    auto bad = [h, &call](hipError_t e) { return serve_fail(h, call.c_str(), e); };
+    DevBuf d_rows, d_ptr, d_perm, d_ids, d_r;
+    const size_t row_bytes = sizeof(float) * (size_t)n_new * (size_t)k;
+    if ((rc = dev_alloc(h, d_rows, row_bytes))) return rc;
+    if (epochs > 0 && total > 0) {
+        if ((rc = dev_alloc(h, d_ptr, sizeof(int64_t) * ((size_t)max_rows + 1)))) return rc;
+        if ((rc = dev_alloc(h, d_perm, sizeof(int32_t) * (size_t)max_rows))) return rc;
+        if ((rc = dev_alloc(h, d_ids, sizeof(int32_t) * (size_t)max_ratings))) return rc;
+        if ((rc = dev_alloc(h, d_r, sizeof(float) * (size_t)max_ratings))) return rc;
+    }
+    // the start rows, dense: the kernel pads them to kp in its registers
+    if (init_rows)
+        HIPCHK_OR(bad, hipMemcpyAsync(d_rows.get(), init_rows, row_bytes, hipMemcpyHostToDevice, h->stream));
+    else
+        HIPCHK_OR(bad, launch_init_rows(d_rows.as<float>(), n_new, k, k, seed, 0, (float)(1.0 / std::sqrt((double)k)), h->stream));
+    std::vector<int32_t> perm;
+    for (size_t b = 0; b + 1 < cut.size() && epochs > 0; ++b) {
+        const int32_t x0 = cut[b], nb = cut[b + 1] - cut[b];
+        const int64_t base = row_ptr[x0], nr = row_ptr[x0 + nb] - base;
+        if (nr == 0) continue;
+        // longest first: a wave runs as long as its longest list
+        perm.resize((size_t)nb);
+        for (int32_t x = 0; x < nb; ++x) perm[(size_t)x] = x;
+        const int64_t* rp = row_ptr + x0;
+        std::stable_sort(perm.begin(), perm.end(), [rp](int32_t a, int32_t b2) { return rp[a + 1] - rp[a] > rp[b2 + 1] - rp[b2]; });
+        HIPCHK_OR(bad, hipMemcpyAsync(d_ptr.get(), rp, sizeof(int64_t) * ((size_t)nb + 1), hipMemcpyHostToDevice, h->stream));
+        HIPCHK_OR(bad, hipMemcpyAsync(d_perm.get(), perm.data(), sizeof(int32_t) * (size_t)nb, hipMemcpyHostToDevice, h->stream));
+        HIPCHK_OR(bad, hipMemcpyAsync(d_ids.get(), ids + base, sizeof(int32_t) * (size_t)nr, hipMemcpyHostToDevice, h->stream));
+        HIPCHK_OR(bad, hipMemcpyAsync(d_r.get(), ratings + base, sizeof(float) * (size_t)nr, hipMemcpyHostToDevice, h->stream));
+        HIPCHK_OR(bad, launch_fold_in(h->geo.L, (h->*fixed).as<const float>(), d_rows.as<float>() + (size_t)x0 * k, k,
+                                      d_ptr.as<const long long>(), base, d_perm.as<const int32_t>(), nb,
+                                      d_ids.as<const int32_t>(), d_r.as<const float>(), epochs, h->cfg.lr,
+                                      1.0f - h->cfg.lr * h->cfg.lambda, h->stream));
+        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // perm and the staging buffers are reused
+    }
+    HIPCHK_OR(bad, hipMemcpyAsync(out_rows, d_rows.get(), row_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
+    return MFSGD_OK;
+}
 
 }  // namespace mfsgd
 
@@ -540,75 +626,16 @@ int mfsgd_evaluate_ranking(mfsgd_handle* h, const int32_t* users, const int32_t*
 int mfsgd_fold_in_users(mfsgd_handle* h, int32_t n_new, const int64_t* row_ptr, const int32_t* items, const float* ratings,
                         int32_t epochs, const float* init_rows, int64_t seed, float* out_rows) {
     return guarded(h, "fold_in", [&]() -> int {
-        if (n_new < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "fold_in: n_new is negative");
-        if (epochs < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "fold_in: epochs is negative");
-        if (n_new > 0 && (!row_ptr || !out_rows)) return fail(h, MFSGD_ERR_INVALID_ARG, "fold_in: row_ptr or out_rows is null");
-        if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "fold_in: single-partition handles only");
-        if (h->where == mfsgd_handle::Where::None)  // (asked here: factors_to_device wants a device first)
-            return fail(h, MFSGD_ERR_STATE, "fold_in: factors not initialised");
-        if (const int rc = check_has_q(h, "fold_in")) return rc;
-        if (n_new == 0) return MFSGD_OK;
-        if (row_ptr[0] != 0) return fail(h, MFSGD_ERR_INVALID_ARG, "fold_in: row_ptr[0] is not 0");
-        for (int32_t x = 0; x < n_new; ++x)
-            if (row_ptr[x + 1] < row_ptr[x])
-                return fail(h, MFSGD_ERR_INVALID_ARG, "fold_in: row_ptr decreases at user " + std::to_string(x));
-        const int64_t total = row_ptr[n_new];
-        if (total > 0 && (!items || !ratings)) return fail(h, MFSGD_ERR_INVALID_ARG, "fold_in: items or ratings is null");
-        for (int64_t j = 0; j < total; ++j)
-            if (items[j] < 0 || items[j] >= h->cfg.n_items)
-                return fail(h, MFSGD_ERR_INVALID_ARG, "fold_in: item of rating " + std::to_string(j) + " out of range");
-        int rc = factors_to_device(h);
-        if (rc) return rc;
-        const int k = h->cfg.k;
-        // batches of whole users, in the caller's order, so that each batch is one contiguous piece of items / ratings
-        std::vector<int32_t> cut{0};
-        int64_t max_ratings = 0, max_users = 0;
-        for (int32_t u0 = 0; u0 < n_new;) {
-            int32_t u1 = u0 + 1;
-            while (u1 < n_new && u1 - u0 < kFoldUsers && row_ptr[u1 + 1] - row_ptr[u0] <= kFoldChunk) ++u1;
-            max_ratings = std::max<int64_t>(max_ratings, row_ptr[u1] - row_ptr[u0]);
-            max_users = std::max<int64_t>(max_users, u1 - u0);
-            cut.push_back(u1);
-            u0 = u1;
-        }
-        auto bad = [h](hipError_t e) { return serve_fail(h, "fold_in: ", e); };
-        DevBuf d_rows, d_ptr, d_perm, d_items, d_r;
-        const size_t row_bytes = sizeof(float) * (size_t)n_new * (size_t)k;
-        if ((rc = dev_alloc(h, d_rows, row_bytes))) return rc;
-        if (epochs > 0 && total > 0) {
-            if ((rc = dev_alloc(h, d_ptr, sizeof(int64_t) * ((size_t)max_users + 1)))) return rc;
-            if ((rc = dev_alloc(h, d_perm, sizeof(int32_t) * (size_t)max_users))) return rc;
-            if ((rc = dev_alloc(h, d_items, sizeof(int32_t) * (size_t)max_ratings))) return rc;
-            if ((rc = dev_alloc(h, d_r, sizeof(float) * (size_t)max_ratings))) return rc;
-        }
-        // the start rows, dense: the kernel pads them to kp in its registers
-        if (init_rows)
-            HIPCHK_OR(bad, hipMemcpyAsync(d_rows.get(), init_rows, row_bytes, hipMemcpyHostToDevice, h->stream));
-        else
-            HIPCHK_OR(bad, launch_init_rows(d_rows.as<float>(), n_new, k, k, seed, 0, (float)(1.0 / std::sqrt((double)k)), h->stream));
-        std::vector<int32_t> perm;
-        for (size_t b = 0; b + 1 < cut.size() && epochs > 0; ++b) {
-            const int32_t u0 = cut[b], nb = cut[b + 1] - cut[b];
-            const int64_t base = row_ptr[u0], nr = row_ptr[u0 + nb] - base;
-            if (nr == 0) continue;
-            // longest first: a wave runs as long as its longest user
-            perm.resize((size_t)nb);
-            for (int32_t x = 0; x < nb; ++x) perm[(size_t)x] = x;
-            const int64_t* rp = row_ptr + u0;
-            std::stable_sort(perm.begin(), perm.end(), [rp](int32_t a, int32_t b2) { return rp[a + 1] - rp[a] > rp[b2 + 1] - rp[b2]; });
-            HIPCHK_OR(bad, hipMemcpyAsync(d_ptr.get(), rp, sizeof(int64_t) * ((size_t)nb + 1), hipMemcpyHostToDevice, h->stream));
-            HIPCHK_OR(bad, hipMemcpyAsync(d_perm.get(), perm.data(), sizeof(int32_t) * (size_t)nb, hipMemcpyHostToDevice, h->stream));
-            HIPCHK_OR(bad, hipMemcpyAsync(d_items.get(), items + base, sizeof(int32_t) * (size_t)nr, hipMemcpyHostToDevice, h->stream));
-            HIPCHK_OR(bad, hipMemcpyAsync(d_r.get(), ratings + base, sizeof(float) * (size_t)nr, hipMemcpyHostToDevice, h->stream));
-            HIPCHK_OR(bad, launch_fold_in(h->geo.L, h->dQ.as<const float>(), d_rows.as<float>() + (size_t)u0 * k, k,
-                                          d_ptr.as<const long long>(), base, d_perm.as<const int32_t>(), nb,
-                                          d_items.as<const int32_t>(), d_r.as<const float>(), epochs, h->cfg.lr,
-                                          1.0f - h->cfg.lr * h->cfg.lambda, h->stream));
-            HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // perm and the staging buffers are reused
-        }
-        HIPCHK_OR(bad, hipMemcpyAsync(out_rows, d_rows.get(), row_bytes, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
-        return MFSGD_OK;
+        return fold_in_core(h, kFoldInUsers, &mfsgd_handle::dQ, h->cfg.n_items, n_new, row_ptr, items, ratings, epochs, init_rows, seed,
+                            out_rows);
+    });
+}
+
+int mfsgd_fold_in_items(mfsgd_handle* h, int32_t n_new, const int64_t* row_ptr, const int32_t* users, const float* ratings,
+                        int32_t epochs, const float* init_rows, int64_t seed, float* out_rows) {
+    return guarded(h, "fold_in_items", [&]() -> int {
+        return fold_in_core(h, kFoldInItems, &mfsgd_handle::dP, h->cfg.n_users, n_new, row_ptr, users, ratings, epochs, init_rows, seed,
+                            out_rows);
     });
 }
 

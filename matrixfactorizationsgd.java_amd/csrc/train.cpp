@@ -679,8 +679,8 @@ int mfsgd_train_early_stop(mfsgd_handle* h, int32_t max_epochs, int32_t patience
         auto bad = [h](hipError_t e) { return serve_fail(h, "early_stop: ", e); };
         DevBuf snap_p, snap_q;  // the factors after the best epoch so far; gone when this returns, whichever way
         if (restore_best) {
-            if ((rc = dev_alloc(h, snap_p, h->dP.bytes()))) return rc;
-            if ((rc = dev_alloc(h, snap_q, h->dQ.bytes()))) return rc;
+            if ((rc = dev_alloc(h, snap_p, h->p_bytes()))) return rc;
+            if ((rc = dev_alloc(h, snap_q, h->q_bytes()))) return rc;
         }
         double best = HUGE_VAL;
         int bad_epochs = 0;
@@ -696,16 +696,16 @@ int mfsgd_train_early_stop(mfsgd_handle* h, int32_t max_epochs, int32_t patience
                 *best_epoch = e;
                 bad_epochs = 0;
                 if (restore_best) {
-                    HIPCHK_OR(bad, hipMemcpyAsync(snap_p.get(), h->dP.get(), h->dP.bytes(), hipMemcpyDeviceToDevice, h->stream));
-                    HIPCHK_OR(bad, hipMemcpyAsync(snap_q.get(), h->dQ.get(), h->dQ.bytes(), hipMemcpyDeviceToDevice, h->stream));
+                    HIPCHK_OR(bad, hipMemcpyAsync(snap_p.get(), h->dP.get(), h->p_bytes(), hipMemcpyDeviceToDevice, h->stream));
+                    HIPCHK_OR(bad, hipMemcpyAsync(snap_q.get(), h->dQ.get(), h->q_bytes(), hipMemcpyDeviceToDevice, h->stream));
                 }
             } else if (++bad_epochs >= patience) {
                 break;
             }
         }
         if (restore_best && *best_epoch >= 0 && *best_epoch != *epochs_run - 1) {
-            HIPCHK_OR(bad, hipMemcpyAsync(h->dP.get(), snap_p.get(), h->dP.bytes(), hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK_OR(bad, hipMemcpyAsync(h->dQ.get(), snap_q.get(), h->dQ.bytes(), hipMemcpyDeviceToDevice, h->stream));
+            HIPCHK_OR(bad, hipMemcpyAsync(h->dP.get(), snap_p.get(), h->p_bytes(), hipMemcpyDeviceToDevice, h->stream));
+            HIPCHK_OR(bad, hipMemcpyAsync(h->dQ.get(), snap_q.get(), h->q_bytes(), hipMemcpyDeviceToDevice, h->stream));
         }
         HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // the snapshot is freed behind this
         return MFSGD_OK;

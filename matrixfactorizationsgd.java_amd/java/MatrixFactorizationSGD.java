@@ -17,7 +17,8 @@ public final class MatrixFactorizationSGD implements AutoCloseable {
     private long handle; // mfsgd_handle*
     private long ring;   // mfsgd_dsgd* (trainDistributed), 0 until the first call
     private int slots;   // item partitions this rank holds at a time (nParts / world)
-    private final int users, items, k, nParts;
+    private int users, items; // follow the handle: addUsers / addItems grow them
+    private final int k, nParts;
     private final long seed;
     private boolean initialised;
 
@@ -109,6 +110,69 @@ public final class MatrixFactorizationSGD implements AutoCloseable {
         float[] rows = new float[nNew * k];
         nativeFoldIn(handle, rowPtr, items, ratings, epochs, init, seed, rows);
         return rows;
+    }
+
+    /**
+     * foldIn for items that are not in the model: new item x owns ratings rowPtr[x] .. rowPtr[x + 1] of users / ratings,
+     * and the step runs against the user factors, which stay fixed.  The model is not modified; addItems(rows) puts the
+     * rows into it.
+     */
+    public float[] foldInItems(long[] rowPtr, int[] users, float[] ratings, int epochs, float[] init, long seed) {
+        if (rowPtr.length < 1 || users.length != ratings.length || users.length != rowPtr[rowPtr.length - 1])
+            throw new IllegalArgumentException("length mismatch");
+        int nNew = rowPtr.length - 1;
+        if (init != null && init.length != nNew * k) throw new IllegalArgumentException("init must be nNew x k");
+        float[] rows = new float[nNew * k];
+        nativeFoldInItems(handle, rowPtr, users, ratings, epochs, init, seed, rows);
+        return rows;
+    }
+
+    /**
+     * Appends users to the live model and returns the index of the first: rows (n x k, row-major; for instance what
+     * foldIn returned).  Nothing is rebuilt: the stored ratings, their schedules, the held-out set and the old rows stay
+     * as they are, and with the factors on the device no old row leaves it.
+     */
+    public int addUsers(float[] rows) {
+        if (rows.length % k != 0) throw new IllegalArgumentException("rows must be n x k");
+        int first = nativeAppend(handle, SIDE_USERS, rows, rows.length / k, 0);
+        users += rows.length / k;
+        return first;
+    }
+
+    /** n seeded rows: foldIn's default start rows for this seed. */
+    public int addUsers(int n, long seed) {
+        int first = nativeAppend(handle, SIDE_USERS, null, n, seed);
+        users += n;
+        return first;
+    }
+
+    /** addUsers for items; rows: for instance what foldInItems returned. */
+    public int addItems(float[] rows) {
+        if (rows.length % k != 0) throw new IllegalArgumentException("rows must be n x k");
+        int first = nativeAppend(handle, SIDE_ITEMS, rows, rows.length / k, 0);
+        items += rows.length / k;
+        return first;
+    }
+
+    public int addItems(int n, long seed) {
+        int first = nativeAppend(handle, SIDE_ITEMS, null, n, seed);
+        items += n;
+        return first;
+    }
+
+    /**
+     * Room for that many users / items in all (0: leave that side alone): appends up to there write in place, P and Q
+     * keep their addresses and the cached training graphs stay valid.  Never shrinks.
+     */
+    public void reserve(int users, int items) {
+        nativeReserve(handle, users, items);
+    }
+
+    /** {users, items} the model has room for without reallocating; the counts where nothing was reserved. */
+    public int[] capacity() {
+        int[] out = new int[2];
+        nativeCapacity(handle, out);
+        return out;
     }
 
     /**
@@ -462,6 +526,11 @@ public final class MatrixFactorizationSGD implements AutoCloseable {
                                                         float[] scores);
     private static native void nativeFoldIn(long h, long[] rowPtr, int[] items, float[] ratings, int epochs, float[] init,
                                             long seed, float[] rows);
+    private static native void nativeFoldInItems(long h, long[] rowPtr, int[] users, float[] ratings, int epochs, float[] init,
+                                                 long seed, float[] rows);
+    private static native int nativeAppend(long h, int side, float[] rows, int n, long seed);
+    private static native void nativeReserve(long h, int users, int items);
+    private static native void nativeCapacity(long h, int[] usersItems);
     private static native void nativeSimilar(long h, int side, int[] queries, int topN, int[] index, float[] scores);
     private static native void nativeSimilarRows(long h, int side, float[] rows, int topN, int[] index, float[] scores);
     private static native void nativeRowInvNorms(long h, int side, float[] out);

@@ -373,15 +373,18 @@ JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeRecommendExcluding(JNIE
     throw_status(env, H(h), rc);
 }
 
-JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeFoldIn(JNIEnv* env, jclass, jlong h, jlongArray row_ptr, jintArray items,
-                                                                jfloatArray ratings, jint epochs, jfloatArray init, jlong seed,
-                                                                jfloatArray rows) {
-    if (!row_ptr || !items || !ratings || !rows) return throw_new(env, "java/lang/NullPointerException", "foldIn");
+namespace {
+
+// Body of the two fold-in natives: new users against Q (items_side false; `items` are the ids of items), new items
+// against P (`items` are the ids of users).  `what` names the Java method; the length messages fit both.
+void fold_in_native(JNIEnv* env, jlong h, bool items_side, const char* what, jlongArray row_ptr, jintArray items,
+                    jfloatArray ratings, jint epochs, jfloatArray init, jlong seed, jfloatArray rows) {
+    if (!row_ptr || !items || !ratings || !rows) return throw_new(env, "java/lang/NullPointerException", what);
     const jsize np = env->GetArrayLength(row_ptr);
     const jsize nr = env->GetArrayLength(items);
     const jsize nw = env->GetArrayLength(rows);
     if (np < 1 || env->GetArrayLength(ratings) != nr || (init && env->GetArrayLength(init) != nw))
-        return throw_new(env, "java/lang/IllegalArgumentException", "foldIn: length mismatch");
+        return throw_new(env, "java/lang/IllegalArgumentException", "fold-in: length mismatch");
     auto cp = alloc<int64_t>(env, (size_t)np);
     auto ci = alloc<int32_t>(env, (size_t)nr);
     auto cr = alloc<float>(env, (size_t)nr);
@@ -396,14 +399,70 @@ JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeFoldIn(JNIEnv* env, jcl
     int32_t n_users = 0, n_items = 0, k = 0;
     int rc = mfsgd_get_dims(H(h), &n_users, &n_items, &k);
     if (rc == MFSGD_OK && (jlong)nw != (jlong)(np - 1) * k)
-        return throw_new(env, "java/lang/IllegalArgumentException", "foldIn: rows must be nNew x k");
+        return throw_new(env, "java/lang/IllegalArgumentException", "fold-in: rows must be nNew x k");
     // (the last offset is checked against the arrays here: the C call cannot know their lengths)
     if (rc == MFSGD_OK && cp.get()[np - 1] != (int64_t)nr)
-        return throw_new(env, "java/lang/IllegalArgumentException", "foldIn: rowPtr must end at items.length");
+        return throw_new(env, "java/lang/IllegalArgumentException", "fold-in: rowPtr must end at the length of the index array");
     if (rc == MFSGD_OK)
-        rc = mfsgd_fold_in_users(H(h), (int32_t)(np - 1), cp.get(), ci.get(), cr.get(), epochs, init ? c0.get() : nullptr,
-                                 (int64_t)seed, cw.get());
+        rc = (items_side ? mfsgd_fold_in_items : mfsgd_fold_in_users)(H(h), (int32_t)(np - 1), cp.get(), ci.get(), cr.get(), epochs,
+                                                                      init ? c0.get() : nullptr, (int64_t)seed, cw.get());
     if (rc == MFSGD_OK && nw > 0) env->SetFloatArrayRegion(rows, 0, nw, cw.get());
+    throw_status(env, H(h), rc);
+}
+
+}  // namespace
+
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeFoldIn(JNIEnv* env, jclass, jlong h, jlongArray row_ptr, jintArray items,
+                                                                jfloatArray ratings, jint epochs, jfloatArray init, jlong seed,
+                                                                jfloatArray rows) {
+    fold_in_native(env, h, false, "foldIn", row_ptr, items, ratings, epochs, init, seed, rows);
+}
+
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeFoldInItems(JNIEnv* env, jclass, jlong h, jlongArray row_ptr,
+                                                                     jintArray users, jfloatArray ratings, jint epochs,
+                                                                     jfloatArray init, jlong seed, jfloatArray rows) {
+    fold_in_native(env, h, true, "foldInItems", row_ptr, users, ratings, epochs, init, seed, rows);
+}
+
+// Growing a live model: side 0 appends users, side 1 items; rows (n x k) or, rows == null, n seeded rows.  Returns the
+// index of the first new row.
+JNIEXPORT jint JNICALL Java_MatrixFactorizationSGD_nativeAppend(JNIEnv* env, jclass, jlong h, jint side, jfloatArray rows, jint n,
+                                                                jlong seed) {
+    int32_t n_users = 0, n_items = 0, k = 0, first = -1;
+    int rc = mfsgd_get_dims(H(h), &n_users, &n_items, &k);
+    if (rc != MFSGD_OK) {
+        throw_new(env, "java/lang/IllegalArgumentException", "append: bad handle");
+        return -1;
+    }
+    std::unique_ptr<float[]> cr;
+    if (rows) {
+        const jsize len = env->GetArrayLength(rows);
+        if (len % k != 0) {
+            throw_new(env, "java/lang/IllegalArgumentException", "append: rows must be n x k");
+            return -1;
+        }
+        // native copy, nothing pinned: a reallocating append waits for the device
+        cr = alloc<float>(env, (size_t)len);
+        if (!cr) return -1;
+        env->GetFloatArrayRegion(rows, 0, len, cr.get());
+        if (env->ExceptionCheck()) return -1;
+        n = len / k;
+    }
+    rc = (side == 0 ? mfsgd_append_users : mfsgd_append_items)(H(h), n, rows ? cr.get() : nullptr, (int64_t)seed, &first);
+    throw_status(env, H(h), rc);
+    return first;
+}
+
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeReserve(JNIEnv* env, jclass, jlong h, jint users, jint items) {
+    throw_status(env, H(h), mfsgd_reserve_rows(H(h), users, items));
+}
+
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeCapacity(JNIEnv* env, jclass, jlong h, jintArray users_items) {
+    if (!users_items || env->GetArrayLength(users_items) != 2)
+        return throw_new(env, "java/lang/IllegalArgumentException", "capacity: an int[2] is needed");
+    int32_t cap[2] = {0, 0};
+    const int rc = mfsgd_get_capacity(H(h), &cap[0], &cap[1]);
+    if (rc == MFSGD_OK) env->SetIntArrayRegion(users_items, 0, 2, reinterpret_cast<const jint*>(cap));
     throw_status(env, H(h), rc);
 }
 

@@ -370,18 +370,14 @@ class MatrixFactorizationSGD:
                                                         _p(items, C.c_int32), _p(scores, C.c_float)))
         return items, scores
 
-    def fold_in(self, row_ptr, items, ratings, epochs, init=None, seed=None):
-        """Rows [n_new, k] for users that are not in the model: new user x owns ratings row_ptr[x] .. row_ptr[x + 1]
-        of items / ratings (CSR), and `epochs` passes of the per-rating SGD step run over them against the model's
-        item factors, which stay fixed.  init: start rows [n_new, k]; None: seeded rows (seed None: the model's),
-        those init_factors(seed) would give a model of n_new users.  The model is not modified."""
+    def _fold_in(self, call, row_ptr, ids, ratings, epochs, init, seed, what):
         rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
-        ii, rr = _i32(items), _f32(ratings)
+        ii, rr = _i32(ids), _f32(ratings)
         if rp.ndim != 1 or rp.size < 1:
             raise ValueError("row_ptr must be a 1-d array of n_new + 1 offsets")
         n_new = rp.size - 1
         if ii.ndim != 1 or ii.shape != rr.shape or ii.size != rp[-1]:
-            raise ValueError("items and ratings must be 1-d arrays of row_ptr[-1] entries")
+            raise ValueError(f"{what} and ratings must be 1-d arrays of row_ptr[-1] entries")
         ip = None
         if init is not None:
             init = _f32(init)
@@ -389,10 +385,68 @@ class MatrixFactorizationSGD:
                 raise ValueError("init must be n_new x k")
             ip = _p(init, C.c_float)
         rows = np.empty((n_new, self.k), np.float32)
-        self._check(self._lib.mfsgd_fold_in_users(self._handle(), n_new, _p(rp, C.c_int64), _p(ii, C.c_int32),
-                                                  _p(rr, C.c_float), int(epochs), ip,
-                                                  self.seed if seed is None else int(seed), _p(rows, C.c_float)))
+        self._check(call(self._handle(), n_new, _p(rp, C.c_int64), _p(ii, C.c_int32), _p(rr, C.c_float), int(epochs), ip,
+                         self.seed if seed is None else int(seed), _p(rows, C.c_float)))
         return rows
+
+    def fold_in(self, row_ptr, items, ratings, epochs, init=None, seed=None):
+        """Rows [n_new, k] for users that are not in the model: new user x owns ratings row_ptr[x] .. row_ptr[x + 1]
+        of items / ratings (CSR), and `epochs` passes of the per-rating SGD step run over them against the model's
+        item factors, which stay fixed.  init: start rows [n_new, k]; None: seeded rows (seed None: the model's),
+        those init_factors(seed) would give a model of n_new users.  The model is not modified."""
+        return self._fold_in(self._lib.mfsgd_fold_in_users, row_ptr, items, ratings, epochs, init, seed, "items")
+
+    def fold_in_items(self, row_ptr, users, ratings, epochs, init=None, seed=None):
+        """fold_in() for items that are not in the model (mfsgd_fold_in_items): new item x owns ratings row_ptr[x] ..
+        row_ptr[x + 1] of users / ratings, and the step runs against the model's user factors, which stay fixed.  The
+        seeded start rows are fold_in()'s.  The model is not modified; add_items(rows) puts the rows into it."""
+        return self._fold_in(self._lib.mfsgd_fold_in_items, row_ptr, users, ratings, epochs, init, seed, "users")
+
+    # -- growing a live model (include/mfsgd.h, "growing a live model") -------------
+    def _dims(self):
+        u, i = C.c_int32(), C.c_int32()
+        self._check(self._lib.mfsgd_get_dims(self._handle(), C.byref(u), C.byref(i), None))
+        self.users, self.items = u.value, i.value
+
+    def _append(self, call, rows, n, seed):
+        if (rows is None) == (n is None):
+            raise ValueError("give either rows or n")
+        rp = None
+        if rows is not None:
+            rows = _f32(rows)
+            if rows.ndim != 2 or rows.shape[1] != self.k:
+                raise ValueError("rows must be n_new x k")
+            n, rp = rows.shape[0], _p(rows, C.c_float)
+        first = C.c_int32(-1)
+        try:
+            self._check(call(self._handle(), int(n), rp, self.seed if seed is None else int(seed), C.byref(first)))
+        finally:
+            if self._h:
+                self._dims()
+        return first.value
+
+    def add_users(self, rows=None, *, n=None, seed=None):
+        """Appends users to the live model (mfsgd_append_users) and returns the index of the first: rows [n_new, k] (for
+        instance what fold_in returned), or n seeded rows (seed None: the model's) -- fold_in's default start rows.
+        Nothing is rebuilt: the stored ratings, their schedules and order, the held-out set and the old rows stay as
+        they are, and with the factors on the device no old row leaves it."""
+        return self._append(self._lib.mfsgd_append_users, rows, n, seed)
+
+    def add_items(self, rows=None, *, n=None, seed=None):
+        """add_users() for items (mfsgd_append_items); rows: for instance what fold_in_items returned."""
+        return self._append(self._lib.mfsgd_append_items, rows, n, seed)
+
+    def reserve(self, users=None, items=None):
+        """Room for that many users / items in all (mfsgd_reserve_rows; None: leave that side alone): appends up to
+        there write in place, P and Q keep their addresses and the cached training graphs stay valid.  Never shrinks."""
+        self._check(self._lib.mfsgd_reserve_rows(self._handle(), 0 if users is None else int(users),
+                                                 0 if items is None else int(items)))
+
+    def capacity(self):
+        """(users, items) the model has room for without reallocating; the counts where nothing was reserved."""
+        u, i = C.c_int32(), C.c_int32()
+        self._check(self._lib.mfsgd_get_capacity(self._handle(), C.byref(u), C.byref(i)))
+        return u.value, i.value
 
     def recommend_rows(self, rows, topn, exclude=None):
         """recommend() for rows that are not in the model (for instance what fold_in returned): (items, scores), each
