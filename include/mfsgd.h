@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver; + mfsgd_set_validation, mfsgd_validation_size, mfsgd_validation_rmse, mfsgd_rmse_pairs, mfsgd_train_early_stop; + mfsgd_row_inv_norms, mfsgd_similar_items, mfsgd_similar_users, mfsgd_similar_rows; + mfsgd_online_levels, mfsgd_apply_ratings; + mfsgd_fold_in_items, mfsgd_append_users, mfsgd_append_items, mfsgd_reserve_rows, mfsgd_get_capacity (additions: no existing call changed) */
+#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver; + mfsgd_set_validation, mfsgd_validation_size, mfsgd_validation_rmse, mfsgd_rmse_pairs, mfsgd_train_early_stop; + mfsgd_row_inv_norms, mfsgd_similar_items, mfsgd_similar_users, mfsgd_similar_rows; + mfsgd_online_levels, mfsgd_apply_ratings; + mfsgd_fold_in_items, mfsgd_append_users, mfsgd_append_items, mfsgd_reserve_rows, mfsgd_get_capacity; + mfsgd_recommend_among, mfsgd_recommend_rows_among, mfsgd_debug_serve_seconds (additions: no existing call changed) */
 
 typedef enum mfsgd_status {
     MFSGD_OK = 0,
@@ -209,6 +209,36 @@ int mfsgd_fold_in_items(mfsgd_handle* h, int32_t n_new, const int64_t* row_ptr, 
  * Same ordering, padding, scores and argument checks, with n_rows in the place of n_users.                           */
 int mfsgd_recommend_rows(mfsgd_handle* h, const float* rows, int32_t n_rows, int32_t topn, const int32_t* excl_row,
                          const int32_t* excl_item, int64_t n_excl, int32_t* out_items, float* out_scores);
+/* Top-N among candidates: "the best topn of these items", for a re-ranking step whose lists come from retrieval, a
+ * category, the stock.  Row b of the output holds the topn best items of row b's candidate list that no exclusion pair
+ * of users[b] removes, ordered exactly as mfsgd_recommend_excluding orders (larger score first; scores that compare
+ * equal as floats, -0.0 == +0.0, by the smaller ITEM INDEX, not by the place in the list), scores being the bits
+ * mfsgd_predict() returns, and padded with item -1 and score NaN where fewer than topn are eligible: it is
+ * mfsgd_recommend_excluding(users[b], topn = n_items, the same pairs) with every item outside the list deleted, cut or
+ * padded to topn.  A list that names every item gives that call's row bit for bit; NaN scores are handled as there.
+ * The lists: cand_ptr == NULL, one list cand_items[0 .. n_cand) shared by every requested row; otherwise CSR over the
+ * REQUEST ROWS -- row b is the position in users, not the user id, so one user asked for twice may carry two lists --
+ * row b owning cand_items[cand_ptr[b] .. cand_ptr[b + 1]), with cand_ptr[0] == 0, cand_ptr non-decreasing and
+ * cand_ptr[n_users] == n_cand.  A list may come in any order and name an item more than once (it counts once); an
+ * empty list is valid (a row of padding), and so is a topn above a list's length.
+ * Arguments are checked before any device work, in mfsgd_recommend_excluding's order with the candidates after the
+ * users and before the exclusion pairs (MFSGD_ERR_INVALID_ARG, message "recommend_among: ..."): that call's own checks
+ * (topn < 1 and topn > n_items among them), then a negative n_cand, a null cand_items with n_cand > 0, each of the three
+ * cand_ptr rules, a candidate outside [0, n_items) (the message names its position in cand_items), more than 2^32 - 1
+ * candidates.  After mfsgd_append_items the new indices are valid candidates; those between count and capacity are not.
+ * MFSGD_ERR_STATE and MFSGD_ERR_NO_DEVICE as mfsgd_recommend_excluding reports them; n_users == 0 is MFSGD_OK.
+ * Cost: work and device memory per request row follow its list and its user's exclusion list, never n_items.  The
+ * candidates are read in chunks of bounded size; the lists are sorted and made distinct on the device for this call
+ * and freed before it returns, on every path.  The model is not modified.                                            */
+int mfsgd_recommend_among(mfsgd_handle* h, const int32_t* users, int32_t n_users, int32_t topn, const int64_t* cand_ptr,
+                          const int32_t* cand_items, int64_t n_cand, const int32_t* excl_u, const int32_t* excl_i,
+                          int64_t n_excl, int32_t* out_items, float* out_scores);
+/* mfsgd_recommend_among where "user j" is rows[j] (n_rows x k, dense), as mfsgd_recommend_rows is to
+ * mfsgd_recommend_excluding: every row is answered, in order, cand_ptr (n_rows + 1 entries) and excl_row index the rows.
+ * Messages start with "recommend_rows_among: ".                                                                      */
+int mfsgd_recommend_rows_among(mfsgd_handle* h, const float* rows, int32_t n_rows, int32_t topn, const int64_t* cand_ptr,
+                               const int32_t* cand_items, int64_t n_cand, const int32_t* excl_row, const int32_t* excl_item,
+                               int64_t n_excl, int32_t* out_items, float* out_scores);
 
 /* ---- ranking quality: where held-out items land, and the top-N metrics of that ------------------------------------
  * out_rank[x] = how many items come before items[x] in users[x]'s recommendation order, among the items that are
@@ -535,6 +565,12 @@ int mfsgd_debug_counters(const mfsgd_handle* h, int64_t* out4);
  * handed to mfsgd_part_train) is not in it.  Tests compare it before and after a call, or a handle's whole
  * life, to see that nothing was kept: free-memory readings of a shared GPU cannot tell.                     */
 int mfsgd_debug_device_bytes(int64_t* live);
+
+/* Diagnostic (not part of the Java surface): out2 = host seconds the handle's latest recommend call (any of the
+ * mfsgd_recommend* calls) spent in its two device halves, each measured up to its synchronise: {building the candidate
+ * and exclusion lists (upload, sort, unique), scoring and selecting (output download included)}.  The argument checks
+ * and the upload of rows come before both and are in neither.  tools/among_bench.py reports them apart.            */
+int mfsgd_debug_serve_seconds(mfsgd_handle* h, double* out2);
 
 /* Diagnostic (not part of the Java surface): occupies the LDS of all but four CUs for `milliseconds` (<= 5000)
  * with a spinning kernel on a side stream, asynchronously -- what a foreign kernel sharing the GPU

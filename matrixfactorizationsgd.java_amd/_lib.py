@@ -122,6 +122,11 @@ SIGNATURES = {
     "mfsgd_fold_in_users": (C.c_int, [_H, C.c_int32, _i64p, _i32p, _f32p, C.c_int32, _f32p, C.c_int64, _f32p]),
     "mfsgd_fold_in_items": (C.c_int, [_H, C.c_int32, _i64p, _i32p, _f32p, C.c_int32, _f32p, C.c_int64, _f32p]),
     "mfsgd_recommend_rows": (C.c_int, [_H, _f32p, C.c_int32, C.c_int32, _i32p, _i32p, C.c_int64, _i32p, _f32p]),
+    "mfsgd_recommend_among": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i64p, _i32p, C.c_int64, _i32p, _i32p, C.c_int64,
+                                        _i32p, _f32p]),
+    "mfsgd_recommend_rows_among": (C.c_int, [_H, _f32p, C.c_int32, C.c_int32, _i64p, _i32p, C.c_int64, _i32p, _i32p,
+                                             C.c_int64, _i32p, _f32p]),
+    "mfsgd_debug_serve_seconds": (C.c_int, [_H, _f64p]),
     "mfsgd_rank_items": (C.c_int, [_H, _i32p, _i32p, C.c_int64, _i32p, _i32p, C.c_int64, _i32p]),
     "mfsgd_rank_items_rows": (C.c_int, [_H, _f32p, C.c_int32, _i32p, _i32p, C.c_int64, _i32p, _i32p, C.c_int64, _i32p]),
     "mfsgd_ranking_metrics_from_ranks": (C.c_int, [_i32p, _i32p, C.c_int64, C.c_int32, C.POINTER(RankingMetrics)]),

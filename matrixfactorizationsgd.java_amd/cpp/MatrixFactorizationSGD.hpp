@@ -135,6 +135,40 @@ class MatrixFactorizationSGD {
                                    (int64_t)excl_row.size(), items.data(), scores.data()));
         return {std::move(items), std::move(scores)};
     }
+    // int[][] recommendAmong(int[] users, int topN, long[] candPtr, int[] candItems, int[] exclU, int[] exclI): the best
+    // topN of each row's candidates only -- candPtr empty: one list, candItems, for every row; otherwise CSR over the rows
+    // of users (users.length + 1 offsets).  Lists may be unsorted and repeat items; rows short of candidates are padded
+    std::pair<std::vector<int32_t>, std::vector<float>> recommendAmong(const std::vector<int32_t>& users, int topn,
+                                                                       const std::vector<int64_t>& cand_ptr,
+                                                                       const std::vector<int32_t>& cand_items,
+                                                                       const std::vector<int32_t>& excl_u = {},
+                                                                       const std::vector<int32_t>& excl_i = {}) {
+        if (excl_u.size() != excl_i.size() || (!cand_ptr.empty() && cand_ptr.size() != users.size() + 1))
+            throw std::invalid_argument("length mismatch");
+        std::vector<int32_t> items(users.size() * (size_t)topn);
+        std::vector<float> scores(users.size() * (size_t)topn);
+        check(mfsgd_recommend_among(h_, users.data(), (int32_t)users.size(), topn, cand_ptr.empty() ? nullptr : cand_ptr.data(),
+                                    cand_items.data(), (int64_t)cand_items.size(), excl_u.data(), excl_i.data(),
+                                    (int64_t)excl_u.size(), items.data(), scores.data()));
+        return {std::move(items), std::move(scores)};
+    }
+    // int[][] recommendRowsAmong(float[] rows, int topN, long[] candPtr, int[] candItems, int[] exclRow, int[] exclItem):
+    // the same for rows (n x k) that are not in the model; candPtr and exclRow index rows
+    std::pair<std::vector<int32_t>, std::vector<float>> recommendRowsAmong(const std::vector<float>& rows, int topn,
+                                                                           const std::vector<int64_t>& cand_ptr,
+                                                                           const std::vector<int32_t>& cand_items,
+                                                                           const std::vector<int32_t>& excl_row = {},
+                                                                           const std::vector<int32_t>& excl_item = {}) {
+        if (excl_row.size() != excl_item.size() || rows.size() % (size_t)k_ != 0) throw std::invalid_argument("length mismatch");
+        const size_t n = rows.size() / (size_t)k_;
+        if (!cand_ptr.empty() && cand_ptr.size() != n + 1) throw std::invalid_argument("length mismatch");
+        std::vector<int32_t> items(n * (size_t)topn);
+        std::vector<float> scores(n * (size_t)topn);
+        check(mfsgd_recommend_rows_among(h_, rows.data(), (int32_t)n, topn, cand_ptr.empty() ? nullptr : cand_ptr.data(),
+                                         cand_items.data(), (int64_t)cand_items.size(), excl_row.data(), excl_item.data(),
+                                         (int64_t)excl_row.size(), items.data(), scores.data()));
+        return {std::move(items), std::move(scores)};
+    }
 
     // int[][] similarItems(int[] items, int topN) / similarUsers(int[] users, int topN): per query the topN other rows of
     // Q / of P with the largest cosine, best first, never the query itself (row-major queries x topN, with the scores)

@@ -113,6 +113,9 @@ struct mfsgd_handle {
     // byte of u, i and r -- a repeated mfsgd_set_ratings with the same triples keeps the schedules
     uint64_t ratings_hash[2] = {0, 0};
     int64_t n_schedule_builds = 0, n_schedule_reuses = 0;
+    // host seconds of the latest recommend call's two device halves, each up to its synchronise: building the candidate
+    // and exclusion lists, then scoring and selecting (mfsgd_debug_serve_seconds)
+    double serve_lists_s = 0.0, serve_topn_s = 0.0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     mutable std::string err;
 };

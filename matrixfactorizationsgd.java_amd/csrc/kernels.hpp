@@ -113,6 +113,30 @@ hipError_t recommend_batch(int L, const float* P, const float* Q, const int32_t*
                            int32_t topn, const RecommendExcl& ex, const CosineScale& cs, float* s_in, float* s_out,
                            int32_t* id_in, int32_t* id_out, long long* d_off, DevBuf& temp, float* out_s, int32_t* out_i,
                            hipStream_t st);
+// Top-N among candidates (mfsgd_recommend_among): request row b of a batch scores the sorted, distinct items
+// items[off[r] .. off[r + 1]) only, r = b (per_row == 1: a list per request row, off pointing at the batch's first
+// row) or 0 (per_row == 0: one list for every row).  The kernels are the ones above with the list in the place of
+// "every item"; the score is the dot.  `longest` is the longest list of the batch, `total` the sum of their lengths.
+struct RecommendAmong {
+    const long long* off = nullptr;
+    const int32_t* items = nullptr;
+    int per_row = 0;
+};
+// Fused for the (longest list, topn) this accepts: the limits of recommend_is_fused with the list in n_items' place ...
+bool recommend_among_is_fused(int64_t longest, int32_t topn);
+hipError_t recommend_among_fused(int L, const float* P, const float* Q, const int32_t* d_users, int nb,
+                                 const RecommendAmong& am, int32_t topn, const RecommendExcl& ex, float* out_s,
+                                 int32_t* out_i, hipStream_t st);
+// ... and the sort path for the rest, the segments being the lists: the buffers hold `total` scores / ids, d_off nb + 1.
+hipError_t recommend_among_batch(int L, const float* P, const float* Q, const int32_t* d_users, int nb,
+                                 const RecommendAmong& am, int64_t total, int64_t longest, int32_t topn,
+                                 const RecommendExcl& ex, float* s_in, float* s_out, int32_t* id_in, int32_t* id_out,
+                                 long long* d_off, DevBuf& temp, float* out_s, int32_t* out_i, hipStream_t st);
+// Building the candidate lists: keys[x0 + x] = row << 32 | items[x] for a chunk of n candidates that starts at position
+// x0 of the call's, row being the request row whose range of ptr (n_rows + 1 entries, CSR; nullptr: row 0) holds the
+// position.  recommend_excl_lists below then makes the lists of them, n_slots being the request rows (or 1).
+hipError_t recommend_cand_keys(const long long* ptr, int32_t n_rows, const int32_t* items, int64_t x0, int64_t n,
+                               unsigned long long* keys, hipStream_t st);
 // Building the lists: each chunk of pairs appends slot << 32 | item to keys[*count ...] for the pairs of requested users
 // (count starts at 0; at most cap are written) ...
 hipError_t recommend_excl_filter(const int32_t* slot_of_user, const int32_t* u, const int32_t* i, int64_t n,

@@ -12,6 +12,9 @@
 // eligible one (0: eligible keys are clamped to >= 1) and pads a row that runs out of eligible items.
 // What is scored is a compile-time policy of the kernels: the dot (recommend), or the cosine built on it with the rows'
 // inverse norms (the similar calls, similar.hip) -- selection, ties, exclusions and padding exist once for both.
+// Which rows of Q a request row scores is a second policy: every item, position x being item x, or the row's sorted,
+// distinct candidate list (mfsgd_recommend_among), position x being the x-th item of it -- the kernels select on
+// positions either way, and because a list ascends "ties by the smaller position" is "ties by the smaller item".
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
@@ -57,12 +60,60 @@ struct CosScore {
     __device__ __forceinline__ float operator()(float d, float a, float b) const { return (d * a) * b; }
 };
 
-// scores[b * n_items + i] = score of (users[b], i) (KEYS: eligible_key of it, as unsigned); ids[...] = i.
+// Which rows of Q request row b scores -- the other compile-time policy.  row(b) is what the row scores: n positions,
+// position x being item item(x), ascending in x.  seg(b) is where the row's scores start in the sort path's buffers.
+// Every item: position x is item x.
+struct AllItems {
+    static constexpr bool kListed = false;
+    int32_t n_items;
+    struct Row {
+        int n;
+        __device__ __forceinline__ int item(int x) const { return x; }
+    };
+    __device__ __forceinline__ Row row(int) const { return {n_items}; }
+    __device__ __forceinline__ long long seg(int b) const { return (long long)b * n_items; }
+};
+// The candidates of mfsgd_recommend_among: row b scores the sorted, distinct items[off[r] .. off[r + 1]), r = b with
+// a list per request row (per_row == 1: off starts at the batch's first row) and 0 with one list for all of them.
+struct ListedItems {
+    static constexpr bool kListed = true;
+    const long long* __restrict__ off;
+    const int32_t* __restrict__ items;
+    int per_row;
+    struct Row {
+        const int32_t* __restrict__ it;
+        int n;
+        __device__ __forceinline__ int item(int x) const { return it[x]; }
+    };
+    __device__ __forceinline__ Row row(int b) const {
+        const int r = b * per_row;
+        return {items + off[r], (int)(off[r + 1] - off[r])};
+    }
+    __device__ __forceinline__ long long seg(int b) const {
+        return per_row ? off[b] - off[0] : (long long)b * (off[1] - off[0]);
+    }
+};
+
+// Is `item` in the sorted, distinct list items[lo .. hi)?  (The listed kernels ask per candidate: a list's candidates are
+// not a run of the exclusion list, as a tile of every item is.)
+__device__ __forceinline__ bool in_sorted(const int32_t* __restrict__ items, long long lo, const long long hi, const int item) {
+    const long long end = hi;
+    long long h = hi;
+    while (lo < h) {
+        const long long mid = (lo + h) >> 1;
+        if (items[mid] < item) lo = mid + 1;
+        else h = mid;
+    }
+    return lo < end && items[lo] == item;
+}
+
+// scores[seg(b) + x] = score of (users[b], item x of the row) (KEYS: eligible_key of it, as unsigned; 0 for a listed
+// item of the user's exclusion list -- of every item, exclude_kernel below does that); ids[...] = the item.
 // grid = (item blocks, users)
-template <int L, bool KEYS, class S>
+template <int L, bool KEYS, class S, class Src>
 __global__ void __launch_bounds__(256) score_kernel(const float* __restrict__ P, const float* __restrict__ Q,
-                                                    const int32_t* __restrict__ users, const int32_t n_items, const S sc,
-                                                    float* __restrict__ scores, int32_t* __restrict__ ids) {
+                                                    const int32_t* __restrict__ users, const Src src, const RecommendExcl ex,
+                                                    const S sc, float* __restrict__ scores, int32_t* __restrict__ ids) {
     constexpr int KP = 4 * L;
     constexpr int GPB = 256 / L;
     const int lig = threadIdx.x % L;
@@ -70,18 +121,33 @@ __global__ void __launch_bounds__(256) score_kernel(const float* __restrict__ P,
     const int b = blockIdx.y;
     const float4 p = *reinterpret_cast<const float4*>(P + (size_t)users[b] * KP + lig * 4);
     const float ra = sc.row(users[b]);
+    const auto v = src.row(b);
+    const size_t base = (size_t)src.seg(b);
+    long long ex_lo = 0, ex_hi = 0;
+    if constexpr (KEYS && Src::kListed) {
+        const int s = ex.slot[users[b]];
+        ex_lo = ex.off[s];
+        ex_hi = ex.off[s + 1];
+    }
     const int stride = (int)gridDim.x * GPB;
-    const int iters = (n_items + stride - 1) / stride;  // uniform trip count: DPP needs every lane live
+    const int iters = (v.n + stride - 1) / stride;  // uniform trip count: DPP needs every lane live
     for (int it = 0; it < iters; ++it) {
-        const int i = (int)blockIdx.x * GPB + grp + it * stride;
-        const bool ok = i < n_items;
-        const float4 q = *reinterpret_cast<const float4*>(Q + (size_t)(ok ? i : 0) * KP + lig * 4);
-        const float rb = sc.col(ok ? i : 0);
+        const int x = (int)blockIdx.x * GPB + grp + it * stride;
+        const bool ok = x < v.n;
+        const int i = v.item(ok ? x : 0);
+        const float4 q = *reinterpret_cast<const float4*>(Q + (size_t)i * KP + lig * 4);
+        const float rb = sc.col(i);
         const float d = sc(group_allreduce<L>(chunk_dot(p, q)), ra, rb);
         if (ok && lig == 0) {
-            if constexpr (KEYS) reinterpret_cast<unsigned*>(scores)[(size_t)b * n_items + i] = eligible_key(d);
-            else scores[(size_t)b * n_items + i] = d;
-            ids[(size_t)b * n_items + i] = i;
+            if constexpr (KEYS) {
+                unsigned key = eligible_key(d);
+                if constexpr (Src::kListed)
+                    if (in_sorted(ex.items, ex_lo, ex_hi, i)) key = 0u;
+                reinterpret_cast<unsigned*>(scores)[base + x] = key;
+            } else {
+                scores[base + x] = d;
+            }
+            ids[base + x] = i;
         }
     }
 }
@@ -94,10 +160,13 @@ constexpr int kTopnCand = 2048;    // candidates kept across tiles (tiles x topn
 constexpr int kTopnThreads = 1024;  // 16 waves: the scores are a latency-bound row gather, so many loads in flight
 
 // EXCL: the items of the user's exclusion list get key 0 in each tile and are never candidates; a tile selects
-// min(topn, its eligible items), and a row with fewer than topn candidates in all is padded (-1, NaN).
-template <int L, bool EXCL, class S>
+// min(topn, its eligible items), and a row with fewer than topn candidates in all is padded (-1, NaN) -- which a
+// listed row (Src) can be without exclusions too: its list may be shorter than topn, or empty.
+// (The same workgroup serves a list of a few hundred items, most of it idle through the selection's barriers: one of
+// 256 threads and a 4,096-position tile was measured and gained too little to keep)
+template <int L, bool EXCL, class S, class Src>
 __global__ void __launch_bounds__(kTopnThreads) topn_kernel(const float* __restrict__ P, const float* __restrict__ Q,
-                                                            const int32_t* __restrict__ users, const int32_t n_items,
+                                                            const int32_t* __restrict__ users, const Src src,
                                                             const int32_t topn, const RecommendExcl ex, const S sc,
                                                             float* __restrict__ out_s, int32_t* __restrict__ out_i) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -114,7 +183,9 @@ __global__ void __launch_bounds__(kTopnThreads) topn_kernel(const float* __restr
     const int b = blockIdx.x;
     const float4 p = *reinterpret_cast<const float4*>(P + (size_t)users[b] * KP + lig * 4);
     const float ra = sc.row(users[b]);
-    long long ex_at = 0, ex_end = 0;  // the user's exclusion list, consumed tile by tile
+    const auto v = src.row(b);  // what this row scores: v.n positions, position x being item v.item(x)
+    const int n_items = v.n;
+    long long ex_at = 0, ex_end = 0;  // the user's exclusion list, consumed tile by tile (every item) or searched (listed)
     int ex_seen = 0;                  // its items met so far: ctl[3] counts them and is never reset, so no read races a reset
     if constexpr (EXCL) {
         const int s = ex.slot[users[b]];
@@ -134,9 +205,10 @@ __global__ void __launch_bounds__(kTopnThreads) topn_kernel(const float* __restr
         for (; it + 1 < iters; it += 2) {
             const int x0 = grp + it * GPB, x1 = x0 + GPB;
             const bool ok1 = x1 < nt;
-            const float4 q0 = *reinterpret_cast<const float4*>(Q + (size_t)(tile0 + x0) * KP + lig * 4);
-            const float4 q1 = *reinterpret_cast<const float4*>(Q + (size_t)(ok1 ? tile0 + x1 : 0) * KP + lig * 4);
-            const float r0 = sc.col(tile0 + x0), r1 = sc.col(ok1 ? tile0 + x1 : 0);
+            const int i0 = v.item(tile0 + x0), i1 = v.item(ok1 ? tile0 + x1 : 0);  // (listed: both loads leave first)
+            const float4 q0 = *reinterpret_cast<const float4*>(Q + (size_t)i0 * KP + lig * 4);
+            const float4 q1 = *reinterpret_cast<const float4*>(Q + (size_t)i1 * KP + lig * 4);
+            const float r0 = sc.col(i0), r1 = sc.col(i1);
             const float d0 = sc(group_allreduce<L>(chunk_dot(p, q0)), ra, r0);
             const float d1 = sc(group_allreduce<L>(chunk_dot(p, q1)), ra, r1);
             if (lig == 0) {
@@ -147,8 +219,9 @@ __global__ void __launch_bounds__(kTopnThreads) topn_kernel(const float* __restr
         for (; it < iters; ++it) {
             const int x = grp + it * GPB;
             const bool ok = x < nt;
-            const float4 q = *reinterpret_cast<const float4*>(Q + (size_t)(ok ? tile0 + x : 0) * KP + lig * 4);
-            const float r = sc.col(ok ? tile0 + x : 0);
+            const int i = v.item(ok ? tile0 + x : 0);
+            const float4 q = *reinterpret_cast<const float4*>(Q + (size_t)i * KP + lig * 4);
+            const float r = sc.col(i);
             const float d = sc(group_allreduce<L>(chunk_dot(p, q)), ra, r);
             if (ok && lig == 0) keys[x] = EXCL ? eligible_key(d) : order_key(d);
         }
@@ -159,18 +232,28 @@ __global__ void __launch_bounds__(kTopnThreads) topn_kernel(const float* __restr
             // the list is sorted and distinct, so its items in this tile are the next run of it, read from memory.
             // Each thread walks its own stride of the list up to the tile's end (one load per thread and tile rather
             // than a search: a chain of dependent loads cost 1.47x the plain kernel), keys to 0, counted in ctl[3].
+            // A listed tile is no run of the exclusion list: each thread looks its own positions' items up in it
+            // instead, log2(the user's exclusions) dependent loads per candidate, and the list is never consumed.
             int mine = 0;
-            for (long long x = ex_at + tid; x < ex_end; x += NT) {
-                const int item = ex.items[x];
-                if (item >= tile0 + nt) break;
-                keys[item - tile0] = 0u;
-                ++mine;
+            if constexpr (Src::kListed) {
+                for (int x = tid; x < nt; x += NT)
+                    if (in_sorted(ex.items, ex_at, ex_end, v.item(tile0 + x))) {
+                        keys[x] = 0u;
+                        ++mine;
+                    }
+            } else {
+                for (long long x = ex_at + tid; x < ex_end; x += NT) {
+                    const int item = ex.items[x];
+                    if (item >= tile0 + nt) break;
+                    keys[item - tile0] = 0u;
+                    ++mine;
+                }
             }
             if (mine) atomicAdd(&ctl[3], mine);
             __syncthreads();
             const int in_tile = ctl[3] - ex_seen;
             ex_seen += in_tile;
-            ex_at += in_tile;
+            if constexpr (!Src::kListed) ex_at += in_tile;
             need = min(topn, nt - in_tile);
             if (need == 0) continue;  // nothing eligible (need is uniform across the workgroup)
         }
@@ -268,13 +351,14 @@ __global__ void __launch_bounds__(kTopnThreads) topn_kernel(const float* __restr
             __syncthreads();
         }
     // the winners; their scores recomputed (plain: the canonical dot, the bits predict() returns).  Without
-    // exclusions there are always at least topn candidates; with them, the places past the last are padded.
+    // exclusions the whole catalogue always has at least topn candidates; with them, or with a list, the places past the
+    // last are padded.
     const int iters = (topn + GPB - 1) / GPB;
     for (int it = 0; it < iters; ++it) {
         const int x = grp + it * GPB;
         const bool ok = x < topn;
-        const bool won = !EXCL || x < nc;
-        const int item = ok && won ? (int)(cand[x] & 0xFFFFFFFFull) : 0;
+        const bool won = !(EXCL || Src::kListed) || x < nc;
+        const int item = ok && won ? v.item((int)(cand[x] & 0xFFFFFFFFull)) : 0;  // the position back to its item
         const float4 q = *reinterpret_cast<const float4*>(Q + (size_t)item * KP + lig * 4);
         const float d = sc(group_allreduce<L>(chunk_dot(p, q)), ra, sc.col(item));
         if (ok && lig == 0) {
@@ -284,25 +368,29 @@ __global__ void __launch_bounds__(kTopnThreads) topn_kernel(const float* __restr
     }
 }
 
-template <int L, bool EXCL, class S>
-hipError_t topn_L(const float* P, const float* Q, const int32_t* users, int nb, int32_t n_items, int32_t topn,
+template <int L, bool EXCL, class S, class Src>
+hipError_t topn_L(const float* P, const float* Q, const int32_t* users, int nb, const Src& src, int32_t topn,
                   const RecommendExcl& ex, const S& sc, float* out_s, int32_t* out_i, hipStream_t st) {
     const size_t lds = (size_t)kTopnTile * 4 + (size_t)kTopnCand * 8 + 256 * 4 + (kTopnThreads / 64) * 4 + 16;
-    hipError_t e =
-        hipFuncSetAttribute((const void*)topn_kernel<L, EXCL, S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute((const void*)topn_kernel<L, EXCL, S, Src>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((topn_kernel<L, EXCL, S>), dim3((unsigned)nb), dim3(kTopnThreads), lds, st, P, Q, users, n_items, topn,
+    hipLaunchKernelGGL((topn_kernel<L, EXCL, S, Src>), dim3((unsigned)nb), dim3(kTopnThreads), lds, st, P, Q, users, src, topn,
                        ex, sc, out_s, out_i);
     return hipGetLastError();
 }
 
+// The sorted rows lie at off[b] .. off[b + 1]; a row shorter than topn (a candidate list can be) is padded.
 __global__ void __launch_bounds__(256) take_top_kernel(const float* __restrict__ s, const int32_t* __restrict__ id,
-                                                       const int32_t n_items, const int32_t topn,
+                                                       const long long* __restrict__ off, const int32_t topn,
                                                        float* __restrict__ out_s, int32_t* __restrict__ out_i) {
     const int b = blockIdx.x;
+    const size_t o = (size_t)off[b];
+    const long long len = off[b + 1] - off[b];
     for (int x = threadIdx.x; x < topn; x += 256) {
-        out_s[(size_t)b * topn + x] = s[(size_t)b * n_items + x];
-        out_i[(size_t)b * topn + x] = id[(size_t)b * n_items + x];
+        const bool won = x < len;
+        out_s[(size_t)b * topn + x] = won ? s[o + x] : __builtin_nanf("");
+        out_i[(size_t)b * topn + x] = won ? id[o + x] : -1;
     }
 }
 
@@ -312,7 +400,7 @@ template <int L, class S>
 __global__ void __launch_bounds__(256) take_top_excl_kernel(const float* __restrict__ P, const float* __restrict__ Q,
                                                             const int32_t* __restrict__ users,
                                                             const unsigned* __restrict__ key, const int32_t* __restrict__ id,
-                                                            const int32_t n_items, const int32_t topn, const S sc,
+                                                            const long long* __restrict__ off, const int32_t topn, const S sc,
                                                             float* __restrict__ out_s, int32_t* __restrict__ out_i) {
     constexpr int KP = 4 * L;
     constexpr int GPB = 256 / L;
@@ -320,12 +408,14 @@ __global__ void __launch_bounds__(256) take_top_excl_kernel(const float* __restr
     const int b = blockIdx.x;
     const float4 p = *reinterpret_cast<const float4*>(P + (size_t)users[b] * KP + lig * 4);
     const float ra = sc.row(users[b]);
+    const size_t o = (size_t)off[b];
+    const long long len = off[b + 1] - off[b];
     const int iters = (topn + GPB - 1) / GPB;  // uniform trip count: DPP needs every lane live
     for (int it = 0; it < iters; ++it) {
         const int x = grp + it * GPB;
         const bool ok = x < topn;
-        const bool won = ok && key[(size_t)b * n_items + x] != 0u;
-        const int item = won ? id[(size_t)b * n_items + x] : 0;
+        const bool won = ok && x < len && key[o + x] != 0u;
+        const int item = won ? id[o + x] : 0;
         const float4 q = *reinterpret_cast<const float4*>(Q + (size_t)item * KP + lig * 4);
         const float d = sc(group_allreduce<L>(chunk_dot(p, q)), ra, sc.col(item));
         if (ok && lig == 0) {
@@ -344,59 +434,91 @@ __global__ void __launch_bounds__(256) exclude_kernel(const int32_t* __restrict_
     for (long long x = ex.off[s] + threadIdx.x; x < end; x += 256) key[(size_t)b * n_items + ex.items[x]] = 0u;
 }
 
-__global__ void __launch_bounds__(256) offsets_kernel(long long* __restrict__ off, const int n, const int32_t n_items) {
-    for (int x = threadIdx.x; x <= n; x += 256) off[x] = (long long)x * n_items;
+// off[x] = where row x starts among the rows of a batch: a fixed stride for every item, the lists' lengths otherwise
+template <class Src>
+__global__ void __launch_bounds__(256) offsets_kernel(long long* __restrict__ off, const int n, const Src src) {
+    for (int x = threadIdx.x; x <= n; x += 256) off[x] = src.seg(x);
 }
 
-// stable descending segmented sort of nb rows of n_items (key, id) pairs; K = float (scores) or unsigned (keys)
+// stable descending segmented sort of nb rows, `total` (key, id) pairs in all, row b at d_off[b] .. d_off[b + 1];
+// K = float (scores) or unsigned (keys)
 template <class K>
-hipError_t sort_rows(K* k_in, K* k_out, int32_t* id_in, int32_t* id_out, long long* d_off, int nb, int32_t n_items,
+hipError_t sort_rows(K* k_in, K* k_out, int32_t* id_in, int32_t* id_out, long long* d_off, int nb, long long total,
                      DevBuf& temp, hipStream_t st) {
     size_t need = 0;
-    hipError_t e = rocprim::segmented_radix_sort_pairs_desc(nullptr, need, k_in, k_out, id_in, id_out,
-                                                            (unsigned)((size_t)nb * n_items), (unsigned)nb, d_off, d_off + 1,
-                                                            0u, 32u, st);
+    hipError_t e = rocprim::segmented_radix_sort_pairs_desc(nullptr, need, k_in, k_out, id_in, id_out, (unsigned)total,
+                                                            (unsigned)nb, d_off, d_off + 1, 0u, 32u, st);
     if (e == hipSuccess) e = temp.alloc(need);
     if (e == hipSuccess)
-        e = rocprim::segmented_radix_sort_pairs_desc(temp.get(), need, k_in, k_out, id_in, id_out, (unsigned)((size_t)nb * n_items),
+        e = rocprim::segmented_radix_sort_pairs_desc(temp.get(), need, k_in, k_out, id_in, id_out, (unsigned)total,
                                                      (unsigned)nb, d_off, d_off + 1, 0u, 32u, st);
     return e;
 }
 
-template <int L, class S>
-hipError_t batch_L(const float* P, const float* Q, const int32_t* users, int nb, int32_t n_items, int32_t topn,
-                   const RecommendExcl& ex, const S& sc, float* s_in, float* s_out, int32_t* id_in, int32_t* id_out, long long* d_off,
-                   DevBuf& temp, float* out_s, int32_t* out_i, hipStream_t st) {
+// The sort path for nb rows that score `total` positions in all, the longest `longest` of them.
+template <int L, class S, class Src>
+hipError_t batch_L(const float* P, const float* Q, const int32_t* users, int nb, const Src& src, long long total,
+                   long long longest, int32_t topn, const RecommendExcl& ex, const S& sc, float* s_in, float* s_out,
+                   int32_t* id_in, int32_t* id_out, long long* d_off, DevBuf& temp, float* out_s, int32_t* out_i,
+                   hipStream_t st) {
+    if (total == 0) {  // nothing but empty lists: every place is padding
+        hipLaunchKernelGGL(offsets_kernel<Src>, dim3(1), dim3(256), 0, st, d_off, nb, src);
+        hipLaunchKernelGGL(take_top_kernel, dim3((unsigned)nb), dim3(256), 0, st, s_out, id_out, d_off, topn, out_s, out_i);
+        return hipGetLastError();
+    }
     const int gpb = 256 / L;
-    int bx = (n_items + gpb - 1) / gpb;
-    if (bx > 64) bx = 64;
+    const int bx = (int)std::min<long long>((longest + gpb - 1) / gpb, 64);
     const dim3 sgrid((unsigned)bx, (unsigned)nb);
     if (ex.slot)
-        hipLaunchKernelGGL((score_kernel<L, true, S>), sgrid, dim3(256), 0, st, P, Q, users, n_items, sc, s_in, id_in);
+        hipLaunchKernelGGL((score_kernel<L, true, S, Src>), sgrid, dim3(256), 0, st, P, Q, users, src, ex, sc, s_in, id_in);
     else
-        hipLaunchKernelGGL((score_kernel<L, false, S>), sgrid, dim3(256), 0, st, P, Q, users, n_items, sc, s_in, id_in);
+        hipLaunchKernelGGL((score_kernel<L, false, S, Src>), sgrid, dim3(256), 0, st, P, Q, users, src, ex, sc, s_in, id_in);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if (ex.slot) {
-        hipLaunchKernelGGL(exclude_kernel, dim3((unsigned)nb), dim3(256), 0, st, users, ex, n_items,
-                           reinterpret_cast<unsigned*>(s_in));
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+    if constexpr (!Src::kListed) {  // (a listed row's exclusions were looked up as it was scored)
+        if (ex.slot) {
+            hipLaunchKernelGGL(exclude_kernel, dim3((unsigned)nb), dim3(256), 0, st, users, ex, src.n_items,
+                               reinterpret_cast<unsigned*>(s_in));
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+        }
     }
-    hipLaunchKernelGGL(offsets_kernel, dim3(1), dim3(256), 0, st, d_off, nb, n_items);
+    hipLaunchKernelGGL(offsets_kernel<Src>, dim3(1), dim3(256), 0, st, d_off, nb, src);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (!ex.slot) {
-        e = sort_rows(s_in, s_out, id_in, id_out, d_off, nb, n_items, temp, st);
+        e = sort_rows(s_in, s_out, id_in, id_out, d_off, nb, total, temp, st);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(take_top_kernel, dim3((unsigned)nb), dim3(256), 0, st, s_out, id_out, n_items, topn, out_s, out_i);
+        hipLaunchKernelGGL(take_top_kernel, dim3((unsigned)nb), dim3(256), 0, st, s_out, id_out, d_off, topn, out_s, out_i);
         return hipGetLastError();
     }
     unsigned* k_in = reinterpret_cast<unsigned*>(s_in);
     unsigned* k_out = reinterpret_cast<unsigned*>(s_out);
-    e = sort_rows(k_in, k_out, id_in, id_out, d_off, nb, n_items, temp, st);
+    e = sort_rows(k_in, k_out, id_in, id_out, d_off, nb, total, temp, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((take_top_excl_kernel<L, S>), dim3((unsigned)nb), dim3(256), 0, st, P, Q, users, k_out, id_out, n_items,
+    hipLaunchKernelGGL((take_top_excl_kernel<L, S>), dim3((unsigned)nb), dim3(256), 0, st, P, Q, users, k_out, id_out, d_off,
                        topn, sc, out_s, out_i);
     return hipGetLastError();
+}
+
+// ---- candidate lists -------------------------------------------------------------------------------------------
+// keys[x0 + x] = row << 32 | items[x] for the candidates x0 .. x0 + n of a call: row is the request row whose CSR range
+// ptr[row] .. ptr[row + 1] holds position x0 + x (ptr == nullptr: one list, row 0).  The keys then go the way of the
+// exclusion pairs' (recommend_excl_lists): sorted and distinct, one ascending list per row.
+__global__ void __launch_bounds__(256) cand_keys_kernel(const long long* __restrict__ ptr, const int n_rows,
+                                                        const int32_t* __restrict__ items, const long long x0,
+                                                        const long long n, unsigned long long* __restrict__ keys) {
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long x = (long long)blockIdx.x * 256 + threadIdx.x; x < n; x += stride) {
+        int lo = 0;
+        if (ptr) {  // the last row whose start is <= x0 + x (empty rows before it start there too)
+            int hi = n_rows;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (ptr[mid + 1] <= x0 + x) lo = mid + 1;
+                else hi = mid;
+            }
+        }
+        keys[x0 + x] = ((unsigned long long)lo << 32) | (unsigned)items[x];
+    }
 }
 
 // ---- exclusion lists -------------------------------------------------------------------------------------------
@@ -455,8 +577,9 @@ hipError_t recommend_fused(int L, const float* P, const float* Q, const int32_t*
     return with_L(L, [&](auto l) {
         constexpr int LL = l();
         auto go = [&](const auto& sc) {
-            return ex.slot ? topn_L<LL, true>(P, Q, d_users, nb, n_items, topn, ex, sc, out_s, out_i, st)
-                           : topn_L<LL, false>(P, Q, d_users, nb, n_items, topn, ex, sc, out_s, out_i, st);
+            const AllItems src{n_items};
+            return ex.slot ? topn_L<LL, true>(P, Q, d_users, nb, src, topn, ex, sc, out_s, out_i, st)
+                           : topn_L<LL, false>(P, Q, d_users, nb, src, topn, ex, sc, out_s, out_i, st);
         };
         return cs.ra ? go(CosScore{cs.ra, cs.rb}) : go(DotScore{});
     });
@@ -470,11 +593,47 @@ hipError_t recommend_batch(int L, const float* P, const float* Q, const int32_t*
     return with_L(L, [&](auto l) {
         constexpr int LL = l();
         auto go = [&](const auto& sc) {
-            return batch_L<LL>(P, Q, d_users, nb, n_items, topn, ex, sc, s_in, s_out, id_in, id_out, d_off, temp, out_s, out_i,
-                                st);
+            return batch_L<LL>(P, Q, d_users, nb, AllItems{n_items}, (long long)nb * n_items, n_items, topn, ex, sc, s_in, s_out,
+                                id_in, id_out, d_off, temp, out_s, out_i, st);
         };
         return cs.ra ? go(CosScore{cs.ra, cs.rb}) : go(DotScore{});
     });
+}
+
+bool recommend_among_is_fused(int64_t longest, int32_t topn) {
+    const long long tiles = ((long long)longest + kTopnTile - 1) / kTopnTile;
+    return topn <= kTopnFused && tiles * topn <= kTopnCand;
+}
+
+hipError_t recommend_among_fused(int L, const float* P, const float* Q, const int32_t* d_users, int nb,
+                                 const RecommendAmong& am, int32_t topn, const RecommendExcl& ex, float* out_s,
+                                 int32_t* out_i, hipStream_t st) {
+    return with_L(L, [&](auto l) {
+        constexpr int LL = l();
+        const ListedItems src{am.off, am.items, am.per_row};
+        return ex.slot ? topn_L<LL, true>(P, Q, d_users, nb, src, topn, ex, DotScore{}, out_s, out_i, st)
+                       : topn_L<LL, false>(P, Q, d_users, nb, src, topn, ex, DotScore{}, out_s, out_i, st);
+    });
+}
+
+hipError_t recommend_among_batch(int L, const float* P, const float* Q, const int32_t* d_users, int nb,
+                                 const RecommendAmong& am, int64_t total, int64_t longest, int32_t topn,
+                                 const RecommendExcl& ex, float* s_in, float* s_out, int32_t* id_in, int32_t* id_out,
+                                 long long* d_off, DevBuf& temp, float* out_s, int32_t* out_i, hipStream_t st) {
+    return with_L(L, [&](auto l) {
+        constexpr int LL = l();
+        return batch_L<LL>(P, Q, d_users, nb, ListedItems{am.off, am.items, am.per_row}, (long long)total, (long long)longest,
+                            topn, ex, DotScore{}, s_in, s_out, id_in, id_out, d_off, temp, out_s, out_i, st);
+    });
+}
+
+hipError_t recommend_cand_keys(const long long* ptr, int32_t n_rows, const int32_t* items, int64_t x0, int64_t n,
+                               unsigned long long* keys, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    const long long blocks = std::min<long long>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(cand_keys_kernel, dim3((unsigned)blocks), dim3(256), 0, st, ptr, (int)n_rows, items, (long long)x0,
+                       (long long)n, keys);
+    return hipGetLastError();
 }
 
 hipError_t recommend_excl_filter(const int32_t* slot_of_user, const int32_t* u, const int32_t* i, int64_t n,

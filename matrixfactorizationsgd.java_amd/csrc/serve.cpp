@@ -2,6 +2,7 @@
 // ranks of held-out items and their metrics, and the fold-in of new users and new items.  Every call batches its work
 // through bounded staging buffers.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 
@@ -15,6 +16,7 @@ struct ServeName {
     const char* whose;
 };
 constexpr ServeName kRecommend{"recommend", "the requested users"}, kRank{"rank_items", "the users asked about"};
+constexpr ServeName kAmong{"recommend_among", "the requested users"}, kRowsAmong{"recommend_rows_among", "the rows"};
 
 // The row matrix of a serving call on the device: the model's P, or host_rows (n_rows x k, dense), which goes up into
 // a kp-padded temporary (`buf`) for the length of the call.
@@ -84,22 +86,101 @@ static int exclusions_to_device(mfsgd_handle* h, const ServeName& what, const st
     return MFSGD_OK;
 }
 
+// The candidates of a recommend_among call as the caller gave them (checked by recommend_core): ptr == nullptr, one
+// list for every request row; otherwise CSR over the request rows.
+struct Candidates {
+    const int64_t* ptr;
+    const int32_t* items;
+    int64_t n;
+};
+
+// ... and as the kernels read them: sorted, distinct lists on the device, with their offsets on the host as well (one
+// list: off = {0, its length}), which say how long each row's list came out, so what a batch holds and which path it takes.
+struct CandLists {
+    RecommendAmong dev;
+    std::vector<long long> off;
+    long long length(int32_t b) const { return dev.per_row ? off[(size_t)b + 1] - off[(size_t)b] : off[1]; }
+};
+
+// Candidate lists of one recommend_among call on the device, the way exclusions_to_device builds its lists: the items go
+// up in chunks of bounded size, each becomes the key row << 32 | item (the row found in cand.ptr on the device), and the
+// keys are sorted and made distinct into one ascending list per request row, or into one list.  Scratch lives as long
+// as this function; `out` points into `off` and `items`, which are the caller's.  cand.n > 0.
+static int candidates_to_device(mfsgd_handle* h, const ServeName& what, const Candidates& cand, int32_t n_rows, DevBuf& off,
+                                DevBuf& items, DevBuf& temp, CandLists& out) {
+    const std::string prefix = std::string(what.call) + ": candidate lists: ";
+    auto bad = [h, &prefix](hipError_t e) { return serve_fail(h, prefix.c_str(), e); };
+    DevBuf d_ptr, ci, keys, keys_tmp, count;
+    const int64_t chunk = std::min(cand.n, kExclChunk);
+    const int32_t n_slots = cand.ptr ? n_rows : 1;
+    int rc;
+    if (cand.ptr) {
+        if ((rc = dev_alloc(h, d_ptr, sizeof(int64_t) * ((size_t)n_rows + 1)))) return rc;
+        HIPCHK_OR(bad, hipMemcpyAsync(d_ptr.get(), cand.ptr, sizeof(int64_t) * ((size_t)n_rows + 1), hipMemcpyHostToDevice, h->stream));
+    }
+    if ((rc = dev_alloc(h, ci, sizeof(int32_t) * (size_t)chunk))) return rc;
+    if ((rc = dev_alloc(h, keys, 8 * (size_t)cand.n))) return rc;
+    if ((rc = dev_alloc(h, keys_tmp, 8 * (size_t)cand.n))) return rc;
+    if ((rc = dev_alloc(h, count, 16))) return rc;  // [0] distinct keys (u32)
+    if ((rc = dev_alloc(h, off, sizeof(long long) * ((size_t)n_slots + 1)))) return rc;
+    if ((rc = dev_alloc(h, items, sizeof(int32_t) * (size_t)cand.n))) return rc;
+    for (int64_t x0 = 0; x0 < cand.n; x0 += chunk) {
+        const int64_t c = std::min(chunk, cand.n - x0);
+        HIPCHK_OR(bad, hipMemcpyAsync(ci.get(), cand.items + x0, sizeof(int32_t) * (size_t)c, hipMemcpyHostToDevice, h->stream));
+        HIPCHK_OR(bad, recommend_cand_keys(cand.ptr ? d_ptr.as<const long long>() : nullptr, n_rows, ci.as<const int32_t>(), x0, c,
+                                           keys.as<unsigned long long>(), h->stream));
+    }
+    HIPCHK_OR(bad, recommend_excl_lists(keys.as<unsigned long long>(), keys_tmp.as<unsigned long long>(), cand.n, n_slots,
+                                        count.as<unsigned>(), off.as<long long>(), items.as<int32_t>(), temp, h->stream));
+    out.off.resize((size_t)n_slots + 1);
+    HIPCHK_OR(bad, hipMemcpyAsync(out.off.data(), off.get(), sizeof(long long) * ((size_t)n_slots + 1), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
+    out.dev.off = off.as<const long long>();
+    out.dev.items = items.as<const int32_t>();
+    out.dev.per_row = cand.ptr ? 1 : 0;
+    return MFSGD_OK;
+}
+
 // The device half of a top-N call, shared by recommend_core and similar_core: for each of the n rows users[...] of P the
-// topn rows of Q (n_items of them) with the largest score (cs: the dot, or the cosine), exclusions as `ex` has them.
-// Fused where recommend_is_fused() holds; otherwise in batches of users through the sort path.  `temp` is the sorts'
-// scratch, the caller's (the exclusion lists may have grown it already).  `prefix` starts the message of a HIP failure.
+// topn rows of Q with the largest score (cs: the dot, or the cosine), exclusions as `ex` has them -- among all n_items
+// rows of Q, or (cl, the dot only) among the candidates of request row b.  Fused where recommend_is_fused() /
+// recommend_among_is_fused() holds; otherwise in batches of rows through the sort path, about 64 M scores at a time
+// (it materialises them): cells of rows x n_items, or of the lists' lengths added up.  `temp` is the sorts' scratch, the
+// caller's (the lists may have grown it already).  `prefix` starts the message of a HIP failure.
+constexpr int64_t kSortCells = (int64_t)64 << 20;
+
 static int topn_batches(mfsgd_handle* h, const char* prefix, const float* P, const float* Q, int32_t I, const int32_t* users,
                         int32_t n_users, int32_t topn, const RecommendExcl& ex, const CosineScale& cs, DevBuf& temp,
-                        int32_t* out_items, float* out_scores) {
-    const bool fused = recommend_is_fused(I, topn);  // score + select in one kernel, no score buffers
-    // users per batch: about 64 M scores at a time (the sort path materialises them)
-    int batch = (int)std::max<int64_t>(1, std::min<int64_t>(n_users, ((int64_t)64 << 20) / std::max(1, I)));
-    if (fused) batch = n_users;
-    batch = std::min(batch, 65535);
+                        int32_t* out_items, float* out_scores, const CandLists* cl = nullptr) {
+    auto length = [cl, I](int32_t b) -> int64_t { return cl ? cl->length(b) : I; };
+    int64_t longest = cl ? 0 : I;
+    for (int32_t b = 0; cl && b < n_users; ++b) longest = std::max(longest, length(b));
+    // score + select in one kernel, no score buffers
+    const bool fused = cl ? recommend_among_is_fused(longest, topn) : recommend_is_fused(I, topn);
+    // whole rows per batch: as many as the cells allow (one at least), the launch's grid bounding them too
+    std::vector<int32_t> cut{0};
+    std::vector<int64_t> batch_cells, batch_longest;
+    int64_t max_cells = 0;
+    int32_t batch = 0;
+    for (int32_t b0 = 0; b0 < n_users;) {
+        int32_t b1 = b0;
+        int64_t cells = 0, lng = 0;
+        while (b1 < n_users && b1 - b0 < 65535 && (fused || b1 == b0 || cells + length(b1) <= kSortCells)) {
+            cells += length(b1);
+            lng = std::max(lng, length(b1));
+            ++b1;
+        }
+        cut.push_back(b1);
+        batch_cells.push_back(cells);
+        batch_longest.push_back(lng);
+        max_cells = std::max(max_cells, cells);
+        batch = std::max(batch, b1 - b0);
+        b0 = b1;
+    }
     auto bad = [h, prefix](hipError_t e) { return serve_fail(h, prefix, e); };
     DevBuf d_users, s_in, s_out, id_in, id_out, d_off, o_s, o_i;
     int rc;
-    const size_t cells = (size_t)batch * (size_t)I;
+    const size_t cells = (size_t)max_cells;
     if ((rc = dev_alloc(h, d_users, sizeof(int32_t) * (size_t)batch))) return rc;
     if (!fused) {
         if ((rc = dev_alloc(h, s_in, 4 * cells))) return rc;
@@ -110,16 +191,29 @@ static int topn_batches(mfsgd_handle* h, const char* prefix, const float* P, con
     }
     if ((rc = dev_alloc(h, o_s, 4 * (size_t)batch * topn))) return rc;
     if ((rc = dev_alloc(h, o_i, 4 * (size_t)batch * topn))) return rc;
-    for (int32_t done = 0; done < n_users; done += batch) {
-        const int nb = std::min<int32_t>(batch, n_users - done);
+    for (size_t c = 0; c + 1 < cut.size(); ++c) {
+        const int32_t done = cut[c];
+        const int nb = cut[c + 1] - done;
         const int32_t* du = d_users.as<const int32_t>();
         HIPCHK_OR(bad, hipMemcpyAsync(d_users.get(), users + done, sizeof(int32_t) * (size_t)nb, hipMemcpyHostToDevice, h->stream));
-        if (fused)
+        if (cl) {
+            RecommendAmong am = cl->dev;
+            if (am.per_row) am.off += done;
+            if (fused)
+                HIPCHK_OR(bad, recommend_among_fused(h->geo.L, P, Q, du, nb, am, topn, ex, o_s.as<float>(), o_i.as<int32_t>(),
+                                                     h->stream));
+            else
+                HIPCHK_OR(bad, recommend_among_batch(h->geo.L, P, Q, du, nb, am, batch_cells[c], batch_longest[c], topn, ex,
+                                                     s_in.as<float>(), s_out.as<float>(), id_in.as<int32_t>(),
+                                                     id_out.as<int32_t>(), d_off.as<long long>(), temp, o_s.as<float>(),
+                                                     o_i.as<int32_t>(), h->stream));
+        } else if (fused) {
             HIPCHK_OR(bad, recommend_fused(h->geo.L, P, Q, du, nb, I, topn, ex, cs, o_s.as<float>(), o_i.as<int32_t>(), h->stream));
-        else
+        } else {
             HIPCHK_OR(bad, recommend_batch(h->geo.L, P, Q, du, nb, I, topn, ex, cs, s_in.as<float>(), s_out.as<float>(),
                                            id_in.as<int32_t>(), id_out.as<int32_t>(), d_off.as<long long>(), temp,
                                            o_s.as<float>(), o_i.as<int32_t>(), h->stream));
+        }
         HIPCHK_OR(bad, hipMemcpyAsync(out_scores + (size_t)done * topn, o_s.get(), 4 * (size_t)nb * topn, hipMemcpyDeviceToHost, h->stream));
         HIPCHK_OR(bad, hipMemcpyAsync(out_items + (size_t)done * topn, o_i.get(), 4 * (size_t)nb * topn, hipMemcpyDeviceToHost, h->stream));
         HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
@@ -129,17 +223,44 @@ static int topn_batches(mfsgd_handle* h, const char* prefix, const float* P, con
 
 // Body of the recommend calls: "user j" is row j of a matrix of n_rows rows, and `users` names the rows asked for.
 // host_rows == nullptr: the matrix is the model's P.  Otherwise it is host_rows (n_rows x k, dense).
-static int recommend_core(mfsgd_handle* h, const float* host_rows, int32_t n_rows, const int32_t* users, int32_t n_users,
-                          int32_t topn, const int32_t* excl_u, const int32_t* excl_i, int64_t n_excl, int32_t* out_items,
-                          float* out_scores) {
+// `what` is how the messages of the argument checks name the call (both recommend calls say "recommend"), `own` the
+// call's own name, which its state errors carry.  cand != nullptr: among the candidates only (the among calls), which
+// are checked after the users and before the exclusion pairs.
+static int recommend_core(mfsgd_handle* h, const ServeName& what, const char* own, const float* host_rows, int32_t n_rows,
+                          const int32_t* users, int32_t n_users, int32_t topn, const Candidates* cand, const int32_t* excl_u,
+                          const int32_t* excl_i, int64_t n_excl, int32_t* out_items, float* out_scores) {
+    const std::string call = std::string(what.call) + ": ";
     if (n_users < 0 || topn < 1 || (n_users > 0 && (!users || !out_items || !out_scores)) || n_excl < 0 ||
         (n_excl > 0 && (!excl_u || !excl_i)))
-        return fail(h, MFSGD_ERR_INVALID_ARG, "recommend: bad argument");
-    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "recommend: single-partition handles only");
-    if (topn > h->cfg.n_items) return fail(h, MFSGD_ERR_INVALID_ARG, "recommend: topn exceeds the number of items");
+        return fail(h, MFSGD_ERR_INVALID_ARG, call + "bad argument");
+    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, call + "single-partition handles only");
+    if (topn > h->cfg.n_items) return fail(h, MFSGD_ERR_INVALID_ARG, call + "topn exceeds the number of items");
     for (int32_t j = 0; j < n_users; ++j)
         if (users[j] < 0 || users[j] >= n_rows)
-            return fail(h, MFSGD_ERR_INVALID_ARG, "recommend: user " + std::to_string(j) + " out of range");
+            return fail(h, MFSGD_ERR_INVALID_ARG, call + "user " + std::to_string(j) + " out of range");
+    if (cand) {
+        if (cand->n < 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "n_cand is negative");
+        if (cand->n > 0 && !cand->items) return fail(h, MFSGD_ERR_INVALID_ARG, call + "cand_items is null");
+        if (cand->ptr) {
+            if (cand->ptr[0] != 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "cand_ptr[0] is not 0");
+            for (int32_t b = 0; b < n_users; ++b)
+                if (cand->ptr[b + 1] < cand->ptr[b])
+                    return fail(h, MFSGD_ERR_INVALID_ARG, call + "cand_ptr decreases at row " + std::to_string(b));
+            if (cand->ptr[n_users] != cand->n)
+                return fail(h, MFSGD_ERR_INVALID_ARG, call + "cand_ptr ends at " + std::to_string(cand->ptr[n_users]) + ", not at n_cand");
+        }
+        // (in blocks without a branch, so that the compiler vectorises it: the candidates are the most the host reads)
+        const uint32_t I = (uint32_t)h->cfg.n_items;
+        for (int64_t x0 = 0; x0 < cand->n; x0 += 4096) {
+            const int64_t x1 = std::min(cand->n, x0 + 4096);
+            uint32_t outside = 0;
+            for (int64_t x = x0; x < x1; ++x) outside |= (uint32_t)((uint32_t)cand->items[x] >= I);
+            for (int64_t x = x0; outside && x < x1; ++x)
+                if ((uint32_t)cand->items[x] >= I)
+                    return fail(h, MFSGD_ERR_INVALID_ARG, call + "candidate " + std::to_string(x) + " out of range");
+        }
+        if (cand->n > (int64_t)UINT32_MAX) return fail(h, MFSGD_ERR_INVALID_ARG, call + "more than 2^32 - 1 candidates");
+    }
     // a slot per distinct requested user (one user asked for twice shares it), and how many pairs are theirs
     std::vector<int32_t> slot_of_user;
     int32_t n_slots = 0;
@@ -149,22 +270,35 @@ static int recommend_core(mfsgd_handle* h, const float* host_rows, int32_t n_row
         slot_of_user.assign((size_t)n_rows, -1);
         for (int32_t j = 0; j < n_users; ++j)
             if (slot_of_user[(size_t)users[j]] < 0) slot_of_user[(size_t)users[j]] = n_slots++;
-        if ((rc = count_exclusions(h, kRecommend, slot_of_user, n_rows, excl_u, excl_i, n_excl, &kept))) return rc;
+        if ((rc = count_exclusions(h, what, slot_of_user, n_rows, excl_u, excl_i, n_excl, &kept))) return rc;
     }
     if (n_users == 0) return MFSGD_OK;
     if (host_rows && h->where == mfsgd_handle::Where::None)  // (asked here: factors_to_device wants a device first)
-        return fail(h, MFSGD_ERR_STATE, "recommend_rows: factors not initialised");
-    if ((rc = check_has_q(h, host_rows ? "recommend_rows" : "recommend")) || (rc = factors_to_device(h))) return rc;
-    DevBuf d_rows, ex_slot, ex_off, ex_items;
-    DevBuf temp;  // of the sorts: one for the exclusion lists and every batch, grown when one needs more
+        return fail(h, MFSGD_ERR_STATE, std::string(own) + ": factors not initialised");
+    if ((rc = check_has_q(h, own)) || (rc = factors_to_device(h))) return rc;
+    if (cand && cand->n == 0) {  // nothing is a candidate: every place is padding
+        std::fill(out_items, out_items + (size_t)n_users * topn, -1);
+        std::fill(out_scores, out_scores + (size_t)n_users * topn, std::nanf(""));
+        return MFSGD_OK;
+    }
+    DevBuf d_rows, ex_slot, ex_off, ex_items, cand_off, cand_items;
+    DevBuf temp;  // of the sorts: one for the lists and every batch, grown when one needs more
     const float* P;
     if ((rc = upload_rows(h, host_rows, n_rows, d_rows, &P))) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    CandLists cl;  // built once for all batches
+    if (cand && (rc = candidates_to_device(h, what, *cand, n_users, cand_off, cand_items, temp, cl))) return rc;
     RecommendExcl ex;  // built once for all batches; none when no pair belongs to a requested user
-    if (kept > 0 && (rc = exclusions_to_device(h, kRecommend, slot_of_user, n_slots, excl_u, excl_i, n_excl, kept, ex_slot,
+    if (kept > 0 && (rc = exclusions_to_device(h, what, slot_of_user, n_slots, excl_u, excl_i, n_excl, kept, ex_slot,
                                                ex_off, ex_items, temp, ex)))
         return rc;
-    return topn_batches(h, "recommend: ", P, h->dQ.as<const float>(), h->cfg.n_items, users, n_users, topn, ex, CosineScale{},
-                        temp, out_items, out_scores);
+    const auto t1 = std::chrono::steady_clock::now();
+    rc = topn_batches(h, call.c_str(), P, h->dQ.as<const float>(), h->cfg.n_items, users, n_users, topn, ex, CosineScale{},
+                      temp, out_items, out_scores, cand ? &cl : nullptr);
+    // (both halves end in a synchronise: mfsgd_debug_serve_seconds)
+    h->serve_lists_s = std::chrono::duration<double>(t1 - t0).count();
+    h->serve_topn_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+    return rc;
 }
 
 // Body of the similar calls: the neighbours of n query rows among the rows of one side's matrix M (Q for
@@ -466,14 +600,16 @@ int mfsgd_predict(mfsgd_handle* h, const int32_t* u, const int32_t* i, float* ou
 int mfsgd_recommend(mfsgd_handle* h, const int32_t* users, int32_t n_users, int32_t topn, int32_t* out_items,
                     float* out_scores) {
     return guarded(h, "recommend", [&]() -> int {
-        return recommend_core(h, nullptr, h->cfg.n_users, users, n_users, topn, nullptr, nullptr, 0, out_items, out_scores);
+        return recommend_core(h, kRecommend, "recommend", nullptr, h->cfg.n_users, users, n_users, topn, nullptr, nullptr, nullptr,
+                              0, out_items, out_scores);
     });
 }
 
 int mfsgd_recommend_excluding(mfsgd_handle* h, const int32_t* users, int32_t n_users, int32_t topn, const int32_t* excl_u,
                               const int32_t* excl_i, int64_t n_excl, int32_t* out_items, float* out_scores) {
     return guarded(h, "recommend", [&]() -> int {
-        return recommend_core(h, nullptr, h->cfg.n_users, users, n_users, topn, excl_u, excl_i, n_excl, out_items, out_scores);
+        return recommend_core(h, kRecommend, "recommend", nullptr, h->cfg.n_users, users, n_users, topn, nullptr, excl_u, excl_i,
+                              n_excl, out_items, out_scores);
     });
 }
 
@@ -483,8 +619,40 @@ int mfsgd_recommend_rows(mfsgd_handle* h, const float* rows, int32_t n_rows, int
         if (n_rows < 0 || (n_rows > 0 && !rows)) return fail(h, MFSGD_ERR_INVALID_ARG, "recommend_rows: bad argument");
         std::vector<int32_t> all((size_t)n_rows);
         for (int32_t j = 0; j < n_rows; ++j) all[(size_t)j] = j;
-        return recommend_core(h, rows, n_rows, all.data(), n_rows, topn, excl_row, excl_item, n_excl, out_items,
-                              out_scores);
+        return recommend_core(h, kRecommend, "recommend_rows", rows, n_rows, all.data(), n_rows, topn, nullptr, excl_row,
+                              excl_item, n_excl, out_items, out_scores);
+    });
+}
+
+int mfsgd_recommend_among(mfsgd_handle* h, const int32_t* users, int32_t n_users, int32_t topn, const int64_t* cand_ptr,
+                          const int32_t* cand_items, int64_t n_cand, const int32_t* excl_u, const int32_t* excl_i,
+                          int64_t n_excl, int32_t* out_items, float* out_scores) {
+    return guarded(h, "recommend_among", [&]() -> int {
+        const Candidates cand{cand_ptr, cand_items, n_cand};
+        return recommend_core(h, kAmong, kAmong.call, nullptr, h->cfg.n_users, users, n_users, topn, &cand, excl_u, excl_i,
+                              n_excl, out_items, out_scores);
+    });
+}
+
+int mfsgd_recommend_rows_among(mfsgd_handle* h, const float* rows, int32_t n_rows, int32_t topn, const int64_t* cand_ptr,
+                               const int32_t* cand_items, int64_t n_cand, const int32_t* excl_row, const int32_t* excl_item,
+                               int64_t n_excl, int32_t* out_items, float* out_scores) {
+    return guarded(h, "recommend_rows_among", [&]() -> int {
+        if (n_rows < 0 || (n_rows > 0 && !rows)) return fail(h, MFSGD_ERR_INVALID_ARG, "recommend_rows_among: bad argument");
+        std::vector<int32_t> all((size_t)n_rows);
+        for (int32_t j = 0; j < n_rows; ++j) all[(size_t)j] = j;
+        const Candidates cand{cand_ptr, cand_items, n_cand};
+        return recommend_core(h, kRowsAmong, kRowsAmong.call, rows, n_rows, all.data(), n_rows, topn, &cand, excl_row, excl_item,
+                              n_excl, out_items, out_scores);
+    });
+}
+
+int mfsgd_debug_serve_seconds(mfsgd_handle* h, double* out2) {
+    return guarded(h, "debug_serve_seconds", [&]() -> int {
+        if (!out2) return fail(h, MFSGD_ERR_INVALID_ARG, "debug_serve_seconds: out2 is null");
+        out2[0] = h->serve_lists_s;
+        out2[1] = h->serve_topn_s;
+        return MFSGD_OK;
     });
 }
 

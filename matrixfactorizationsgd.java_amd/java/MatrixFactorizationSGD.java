@@ -83,6 +83,24 @@ public final class MatrixFactorizationSGD implements AutoCloseable {
     }
 
     /**
+     * The topN best of each row's candidates only ("the best 10 of these 500"), never item exclI[x] for user exclU[x].
+     * candPtr == null: candItems is one list for every row; otherwise row a of users (the place in the array, not the
+     * user: one user asked twice may carry two lists) owns candItems[candPtr[a] .. candPtr[a + 1]), candPtr having
+     * users.length + 1 entries from 0 to candItems.length.  A list may be unsorted, repeat items (they count once) and
+     * be empty.  Order and scores are recommend's; a row with fewer than topN eligible candidates gets -1 in the places left.
+     */
+    public int[][] recommendAmong(int[] users, int topN, long[] candPtr, int[] candItems, int[] exclU, int[] exclI) {
+        if (exclU.length != exclI.length || (candPtr != null && candPtr.length != users.length + 1))
+            throw new IllegalArgumentException("length mismatch");
+        int[] items = new int[users.length * topN];
+        float[] scores = new float[users.length * topN];
+        nativeRecommendAmong(handle, users, topN, candPtr, candItems, exclU, exclI, items, scores);
+        int[][] out = new int[users.length][];
+        for (int a = 0; a < users.length; a++) out[a] = java.util.Arrays.copyOfRange(items, a * topN, (a + 1) * topN);
+        return out;
+    }
+
+    /**
      * As recommend(users, topN), but never item exclI[x] for user exclU[x] (typically the arrays the model was trained
      * on, so that only unrated items come back).  A user with fewer than topN eligible items gets -1 in the places left.
      */
@@ -524,6 +542,8 @@ public final class MatrixFactorizationSGD implements AutoCloseable {
     private static native void nativeRecommend(long h, int[] users, int topN, int[] items, float[] scores);
     private static native void nativeRecommendExcluding(long h, int[] users, int topN, int[] exclU, int[] exclI, int[] items,
                                                         float[] scores);
+    private static native void nativeRecommendAmong(long h, int[] users, int topN, long[] candPtr, int[] candItems, int[] exclU,
+                                                    int[] exclI, int[] items, float[] scores);
     private static native void nativeFoldIn(long h, long[] rowPtr, int[] items, float[] ratings, int epochs, float[] init,
                                             long seed, float[] rows);
     private static native void nativeFoldInItems(long h, long[] rowPtr, int[] users, float[] ratings, int epochs, float[] init,

@@ -373,6 +373,45 @@ JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeRecommendExcluding(JNIE
     throw_status(env, H(h), rc);
 }
 
+// cand_ptr == null: one candidate list (cand_items) for every row; otherwise CSR over the rows of `users`
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeRecommendAmong(JNIEnv* env, jclass, jlong h, jintArray users,
+                                                                        jint topn, jlongArray cand_ptr, jintArray cand_items,
+                                                                        jintArray excl_u, jintArray excl_i, jintArray items,
+                                                                        jfloatArray scores) {
+    if (!users || !cand_items || !excl_u || !excl_i || !items || !scores)
+        return throw_new(env, "java/lang/NullPointerException", "recommendAmong");
+    const jsize n = env->GetArrayLength(users);
+    const jsize nc = env->GetArrayLength(cand_items);
+    const jsize ne = env->GetArrayLength(excl_u);
+    if (env->GetArrayLength(excl_i) != ne)
+        return throw_new(env, "java/lang/IllegalArgumentException", "exclU and exclI must have the same length");
+    if (cand_ptr && (jlong)env->GetArrayLength(cand_ptr) != (jlong)n + 1)
+        return throw_new(env, "java/lang/IllegalArgumentException", "candPtr must have users.length + 1 entries");
+    if (topn < 1 || (jlong)env->GetArrayLength(items) < (jlong)n * topn || (jlong)env->GetArrayLength(scores) < (jlong)n * topn)
+        return throw_new(env, "java/lang/IllegalArgumentException", "items / scores shorter than users x topN");
+    auto cu = alloc<int32_t>(env, (size_t)n);
+    auto cp = alloc<int64_t>(env, (size_t)n + 1);
+    auto cc = alloc<int32_t>(env, (size_t)nc);
+    auto ceu = alloc<int32_t>(env, (size_t)ne);
+    auto cei = alloc<int32_t>(env, (size_t)ne);
+    auto ci = alloc<int32_t>(env, (size_t)n * (size_t)topn);
+    auto cs = alloc<float>(env, (size_t)n * (size_t)topn);
+    if (!cu || !cp || !cc || !ceu || !cei || !ci || !cs) return;
+    env->GetIntArrayRegion(users, 0, n, reinterpret_cast<jint*>(cu.get()));
+    if (cand_ptr) env->GetLongArrayRegion(cand_ptr, 0, n + 1, reinterpret_cast<jlong*>(cp.get()));
+    env->GetIntArrayRegion(cand_items, 0, nc, reinterpret_cast<jint*>(cc.get()));
+    env->GetIntArrayRegion(excl_u, 0, ne, reinterpret_cast<jint*>(ceu.get()));
+    env->GetIntArrayRegion(excl_i, 0, ne, reinterpret_cast<jint*>(cei.get()));
+    if (env->ExceptionCheck()) return;
+    const int rc = mfsgd_recommend_among(H(h), cu.get(), n, topn, cand_ptr ? cp.get() : nullptr, cc.get(), (int64_t)nc, ceu.get(),
+                                         cei.get(), (int64_t)ne, ci.get(), cs.get());
+    if (rc == MFSGD_OK && n > 0) {
+        env->SetIntArrayRegion(items, 0, n * topn, reinterpret_cast<const jint*>(ci.get()));
+        env->SetFloatArrayRegion(scores, 0, n * topn, cs.get());
+    }
+    throw_status(env, H(h), rc);
+}
+
 namespace {
 
 // Body of the two fold-in natives: new users against Q (items_side false; `items` are the ids of items), new items

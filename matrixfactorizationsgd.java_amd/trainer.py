@@ -35,6 +35,32 @@ def _p(a, ctype):
     return a.ctypes.data_as(C.POINTER(ctype))
 
 
+def _candidates(cand, n_rows):
+    """The `candidates` argument of recommend / recommend_rows as the C-ABI takes it: (ptr int64[n_rows + 1] or None,
+    items int32[n]).  A 1-d integer array (or list of integers): one list shared by every row.  A tuple (ptr, items): CSR
+    over the request rows.  Any other sequence: one 1-d integer array per request row."""
+    def ints(a, what):
+        a = np.asarray(a)
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+            raise ValueError(f"{what} must be a 1-d integer array")
+        return a
+    if isinstance(cand, tuple):
+        if len(cand) != 2:
+            raise ValueError("candidates as a tuple must be (ptr, items)")
+        ptr, items = ints(cand[0], "candidates' ptr"), ints(cand[1], "candidates' items")
+        if ptr.size != n_rows + 1:
+            raise ValueError("candidates' ptr must have one entry per requested row, and one more")
+        return np.ascontiguousarray(ptr, dtype=np.int64), _i32(items)
+    if isinstance(cand, np.ndarray) or len(cand) == 0 or np.isscalar(cand[0]):
+        return None, _i32(ints(cand, "candidates"))
+    lists = [ints(c, "each row's candidates") for c in cand]
+    if len(lists) != n_rows:
+        raise ValueError("candidates must hold one list per requested row")
+    ptr = np.zeros(n_rows + 1, np.int64)
+    np.cumsum([c.size for c in lists], out=ptr[1:])
+    return ptr, _i32(np.concatenate(lists)) if lists else np.empty(0, np.int32)
+
+
 def debug_device_bytes():
     """mfsgd_debug_device_bytes: bytes of device memory the library holds in this process right now, over all handles."""
     live = C.c_int64(-1)
@@ -355,20 +381,37 @@ class MatrixFactorizationSGD:
                                             _p(out, C.c_float), uu.size))
         return float(out[0]) if scalar else out
 
-    def recommend(self, users, topn, exclude=None):
+    def recommend(self, users, topn, exclude=None, candidates=None):
         """(items, scores), each [len(users), topn]: best items per user, best first.  exclude = (u, i):
         pairs never returned (for instance the training ratings, so that only unrated items come back);
-        a row with fewer than topn eligible items is padded with item -1 and score NaN."""
+        a row with fewer than topn eligible items is padded with item -1 and score NaN.
+        candidates: the items a row may return at all (mfsgd_recommend_among) -- a 1-d integer array, one list for every
+        row; a tuple (ptr, items), CSR over the rows of `users` (row b is the position in users, not the user); or a
+        sequence of one 1-d array per row.  Lists may be unsorted, repeat items and be empty.  None: every item."""
         uu = _i32(np.atleast_1d(users))
         eu, ei = (np.empty(0, np.int32),) * 2 if exclude is None else (_i32(exclude[0]), _i32(exclude[1]))
         if eu.shape != ei.shape or eu.ndim != 1:
             raise ValueError("exclude must be two 1-d arrays of the same length")
+        cp, ci = (None, None) if candidates is None else _candidates(candidates, uu.size)
         items = np.empty((uu.size, int(topn)), np.int32)
         scores = np.empty((uu.size, int(topn)), np.float32)
-        self._check(self._lib.mfsgd_recommend_excluding(self._handle(), _p(uu, C.c_int32), uu.size, int(topn),
+        if candidates is None:
+            self._check(self._lib.mfsgd_recommend_excluding(self._handle(), _p(uu, C.c_int32), uu.size, int(topn),
+                                                            _p(eu, C.c_int32), _p(ei, C.c_int32), eu.size,
+                                                            _p(items, C.c_int32), _p(scores, C.c_float)))
+        else:
+            self._check(self._lib.mfsgd_recommend_among(self._handle(), _p(uu, C.c_int32), uu.size, int(topn),
+                                                        None if cp is None else _p(cp, C.c_int64), _p(ci, C.c_int32), ci.size,
                                                         _p(eu, C.c_int32), _p(ei, C.c_int32), eu.size,
                                                         _p(items, C.c_int32), _p(scores, C.c_float)))
         return items, scores
+
+    def serve_seconds(self):
+        """(lists, topn): host seconds the latest recommend call spent building its candidate and exclusion lists on the
+        device, and scoring and selecting (mfsgd_debug_serve_seconds)."""
+        out = np.zeros(2, np.float64)
+        self._check(self._lib.mfsgd_debug_serve_seconds(self._handle(), _p(out, C.c_double)))
+        return float(out[0]), float(out[1])
 
     def _fold_in(self, call, row_ptr, ids, ratings, epochs, init, seed, what):
         rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
@@ -448,9 +491,10 @@ class MatrixFactorizationSGD:
         self._check(self._lib.mfsgd_get_capacity(self._handle(), C.byref(u), C.byref(i)))
         return u.value, i.value
 
-    def recommend_rows(self, rows, topn, exclude=None):
+    def recommend_rows(self, rows, topn, exclude=None, candidates=None):
         """recommend() for rows that are not in the model (for instance what fold_in returned): (items, scores), each
-        [len(rows), topn].  exclude = (row, item): pairs never returned, row indexing `rows`."""
+        [len(rows), topn].  exclude = (row, item): pairs never returned, row indexing `rows`.  candidates: as in
+        recommend(), the per-row forms indexing `rows` (mfsgd_recommend_rows_among)."""
         rows = _f32(rows)
         if rows.ndim != 2 or rows.shape[1] != self.k:
             raise ValueError("rows must be n_rows x k")
@@ -458,11 +502,18 @@ class MatrixFactorizationSGD:
         if er.shape != ei.shape or er.ndim != 1:
             raise ValueError("exclude must be two 1-d arrays of the same length")
         n = rows.shape[0]
+        cp, ci = (None, None) if candidates is None else _candidates(candidates, n)
         items = np.empty((n, int(topn)), np.int32)
         scores = np.empty((n, int(topn)), np.float32)
-        self._check(self._lib.mfsgd_recommend_rows(self._handle(), _p(rows, C.c_float), n, int(topn), _p(er, C.c_int32),
-                                                   _p(ei, C.c_int32), er.size, _p(items, C.c_int32),
-                                                   _p(scores, C.c_float)))
+        if candidates is None:
+            self._check(self._lib.mfsgd_recommend_rows(self._handle(), _p(rows, C.c_float), n, int(topn), _p(er, C.c_int32),
+                                                       _p(ei, C.c_int32), er.size, _p(items, C.c_int32),
+                                                       _p(scores, C.c_float)))
+        else:
+            self._check(self._lib.mfsgd_recommend_rows_among(self._handle(), _p(rows, C.c_float), n, int(topn),
+                                                             None if cp is None else _p(cp, C.c_int64), _p(ci, C.c_int32),
+                                                             ci.size, _p(er, C.c_int32), _p(ei, C.c_int32), er.size,
+                                                             _p(items, C.c_int32), _p(scores, C.c_float)))
         return items, scores
 
     def rank_items(self, u, i, exclude=None):
