@@ -1,7 +1,8 @@
 """Seeded sequences of calls on one live handle against the model of tests/handle_model.py, as far as they go without a
 GPU: ratings (kept, rebuilt, dropped by a failed call), lr and lambda re-baked into a schedule any number of times, factors
-seeded on the host, set, saved, loaded and seeded without Q, the held-out set, and every getter, each compared with the
-model after the call; the calls that need a device are MFSGD_ERR_NO_DEVICE and change nothing.  (On a machine that has a
+seeded on the host, set, saved, loaded and seeded without Q, rows appended to the host staging, room reserved, empty
+batches of online updates, the held-out set, and every getter, each compared with the model after the call; the calls
+that need a device are MFSGD_ERR_NO_DEVICE and change nothing.  (On a machine that has a
 GPU the same sequences run with it, and the few compute calls they draw are compared with the oracle.)
 Also here: the driver's self-test (a model with one rule wrong must be reported), and the dry run of the GPU module's
 cases, which shows that the op weights meet that module's coverage conditions by the model alone."""
@@ -34,11 +35,14 @@ def test_host_sequences(mf, oracle, k, flag):
     print(f"k={k} {flag}: {sorted(counts.items())}\n{sorted(facts.items())}")
     # what the host path is there to cover has happened, successfully, in these twenty lives
     for kind in ("set_ratings", "set_hyper", "set_factors", "init_factors", "init_p_offset", "get_factors", "set_validation",
-                 "clear_validation", "save_load", "order", "debug_schedule", "schedule_info", "hyper", "debug_counters"):
+                 "clear_validation", "save_load", "order", "debug_schedule", "schedule_info", "hyper", "debug_counters",
+                 "add_users", "add_items", "reserve"):
         assert counts.get((kind, "ok"), 0) >= 5, (kind, counts)
+    assert facts.get("partial_fit_of_no_ratings", 0) >= 5, facts  # (n = 0 needs no device)
     assert counts.get(("set_ratings", "INVALID_ARG"), 0) >= 1
     for fact in ("set_ratings_reuse", "set_ratings_rebuild_of_equal_length", "set_ratings_build_of_the_set_a_failed_call_dropped",
-                 "set_hyper_before_any_ratings", "set_hyper_on_a_host_packed_schedule", "set_hyper_same_bits"):
+                 "set_hyper_before_any_ratings", "set_hyper_on_a_host_packed_schedule", "set_hyper_same_bits",
+                 "set_ratings_reuse_after_growth", "init_factors_after_growth", "stale_factor_file_refused"):
         assert facts.get(fact, 0) >= 1, (fact, facts)
     if not have_gpu():
         assert any(outcome == "NO_DEVICE" for _, outcome in counts), "no call that needs a device was drawn"
@@ -65,10 +69,12 @@ def test_schedule_after_many_changes_of_values_is_the_fresh_one(mf):
                 assert np.array_equal(x, y)
 
 
-@pytest.mark.parametrize("wrong", ["hyper_before_ratings", "failed_set_ratings_keeps"])
+@pytest.mark.parametrize("wrong", ["hyper_before_ratings", "failed_set_ratings_keeps", "reseed_forgets_growth",
+                                   "append_forgets_the_ratings"])
 def test_the_driver_reports_a_model_with_one_wrong_rule(mf, oracle, wrong):
-    """The comparison has teeth: a model that believes `set_hyper before set_ratings does not change lr`, or `a failed
-    set_ratings keeps the old schedule`, disagrees with the library on the same seeds the correct model passes."""
+    """The comparison has teeth: a model that believes `set_hyper before set_ratings does not change lr`, `a failed
+    set_ratings keeps the old schedule`, `init_factors seeds the sizes the handle was created with` or `the same triples
+    after an append are built again` disagrees with the library on the same seeds the correct model passes."""
     caught = []
     for seed in HOST_SEEDS:
         try:
@@ -91,9 +97,13 @@ def test_a_failure_lists_every_op_so_far(mf, oracle):
 def test_the_op_weights_meet_the_gpu_modules_conditions_by_the_model_alone():
     """The GPU module's cases in a dry run (no library, no oracle): the draw depends only on the seed and the model's
     abstract state, so these are the ops and outcomes of the real runs, and the coverage conditions hold for them."""
+    cases = [(flag, geo, seed) for flag in hm.GPU_FLAGS for geo in sorted(hm.GEOMETRIES) for seed in hm.GPU_SEEDS]
     results = [hm.run_sequence(None, None, hm.gpu_seed(flag, geo, seed), hm.GPU_OPS, hm.gpu_config(flag, geo), dry=True)
-               for flag in hm.GPU_FLAGS for geo in sorted(hm.GEOMETRIES) for seed in hm.GPU_SEEDS]
+               for flag, geo, seed in cases]
     total = hm.check_coverage(results)
+    for geometry in hm.GEOMETRIES:  # every geometry runs both kernels of csrc/online.hip at least once
+        for fact in ("partial_fit_with_a_wide_level", "partial_fit_with_a_narrow_level"):
+            assert sum(res["facts"][fact] for (_, geo, _), res in zip(cases, results) if geo == geometry) >= 1, (geometry, fact)
     print(f"{total['ops']} ops, {total['errors']} errors ({100 * total['errors'] / total['ops']:.1f} %)")
     print(sorted(total["counts"].items()))
     print(sorted(total["facts"].items()))
