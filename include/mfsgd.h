@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver; + mfsgd_set_validation, mfsgd_validation_size, mfsgd_validation_rmse, mfsgd_rmse_pairs, mfsgd_train_early_stop; + mfsgd_row_inv_norms, mfsgd_similar_items, mfsgd_similar_users, mfsgd_similar_rows; + mfsgd_online_levels, mfsgd_apply_ratings; + mfsgd_fold_in_items, mfsgd_append_users, mfsgd_append_items, mfsgd_reserve_rows, mfsgd_get_capacity; + mfsgd_recommend_among, mfsgd_recommend_rows_among, mfsgd_debug_serve_seconds (additions: no existing call changed) */
+#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver; + mfsgd_set_validation, mfsgd_validation_size, mfsgd_validation_rmse, mfsgd_rmse_pairs, mfsgd_train_early_stop; + mfsgd_row_inv_norms, mfsgd_similar_items, mfsgd_similar_users, mfsgd_similar_rows; + mfsgd_online_levels, mfsgd_apply_ratings; + mfsgd_fold_in_items, mfsgd_append_users, mfsgd_append_items, mfsgd_reserve_rows, mfsgd_get_capacity; + mfsgd_recommend_among, mfsgd_recommend_rows_among, mfsgd_debug_serve_seconds; + mfsgd_set_seen, mfsgd_mark_seen, mfsgd_clear_seen, mfsgd_seen_size, mfsgd_get_seen, mfsgd_recommend_unseen, mfsgd_recommend_unseen_among, mfsgd_rank_items_unseen, mfsgd_evaluate_ranking_unseen (additions: no existing call changed) */
 
 typedef enum mfsgd_status {
     MFSGD_OK = 0,
@@ -285,6 +285,77 @@ int mfsgd_ranking_metrics_from_ranks(const int32_t* users, const int32_t* ranks,
 int mfsgd_evaluate_ranking(mfsgd_handle* h, const int32_t* users, const int32_t* items, int64_t n, int32_t topn,
                            const int32_t* excl_u, const int32_t* excl_i, int64_t n_excl,
                            mfsgd_ranking_metrics* out, int32_t* out_rank);
+
+/* ---- the seen-item index: what each user has already seen, kept on the device ----------------------------------------
+ * mfsgd_recommend_excluding and its kin take the complete (user, item) pair list on every call, check it, upload it and
+ * sort it into per-user lists that are freed before they return.  The index is those lists built once and kept in the
+ * handle: one sorted, distinct item list per user in CSR form on the device, extended in place as ratings arrive and
+ * read by the _unseen calls below where it lies.  A handle has no index until mfsgd_set_seen or mfsgd_mark_seen; an
+ * empty index (no pairs) is a valid state, and the _unseen calls then exclude nothing.
+ * All of these calls are for single-partition handles (n_parts != 1: MFSGD_ERR_STATE), check their arguments before any
+ * device work, run on the handle's stream and return with the device idle.
+ * The index and the model do not touch each other: mfsgd_set_ratings, mfsgd_set_hyper, seeding, setting or loading
+ * factors, training, mfsgd_apply_ratings (it does NOT mark: pass the same u / i to mfsgd_mark_seen), the validation calls,
+ * fold-in and mfsgd_append_items leave the index as it is, and the index changes no factor bit, no schedule and no cached
+ * training graph.  Users added by mfsgd_append_users have empty lists; inside the reserved capacity that append allocates
+ * nothing for the index, and one that reallocates, like mfsgd_reserve_rows, copies the per-user tables device to device
+ * into larger ones, new before old (MFSGD_ERR_OOM leaves everything as it was; every list is kept).
+ * Memory: with D distinct pairs, 4 D + 12 user_capacity + 8 bytes of device memory (4 per pair; per user of capacity 8
+ * of offset and 4 of the table through which the kernels reach a list by user id), all of it counted by
+ * mfsgd_debug_device_bytes; an empty index and a handle without one hold nothing.
+ *
+ * mfsgd_set_seen: the index becomes the distinct pairs of (u[x], i[x]), x < n; duplicates count once.  Needs neither
+ * factors nor ratings.  Every pair must satisfy 0 <= u < n_users and 0 <= i < n_items under the handle's CURRENT counts
+ * (rows appended to the model are valid).  MFSGD_ERR_INVALID_ARG, message "set_seen: ...", in this order: a negative n; a
+ * null array with n > 0; (then MFSGD_ERR_STATE for n_parts != 1;) a pair out of range -- the message names its position;
+ * more than 2^32 - 1 pairs.  n == 0 leaves an empty index, on the host alone: it works without a GPU.  A valid call
+ * with n > 0 and no usable GPU is MFSGD_ERR_NO_DEVICE.  The pairs go up in chunks of 2^22 (32 MB of staging, whatever
+ * n is) and are sorted and made distinct on the device.  The new index is complete before the old one is released, so a
+ * failure (MFSGD_ERR_OOM, MFSGD_ERR_HIP, MFSGD_ERR_NO_DEVICE) leaves the old one as it was.  Transient peak on top of the
+ * old and the new index: 16 bytes per pair given (keys, and the sort's second buffer), the staging, and the sort's
+ * scratch; all of it is freed before the call returns.
+ * mfsgd_mark_seen: the index becomes the union of itself and the pairs; on a handle without an index, or with an empty
+ * one, it is mfsgd_set_seen.  n == 0 touches nothing, except that a handle without an index gets an empty one.  Checks
+ * and failure rule are mfsgd_set_seen's, the messages start with "mark_seen: ".  The index does not go through a sort
+ * again: the batch is sorted and made distinct, the keys the index lacks are found by a binary search each, and every
+ * element of the merged index is placed on its own -- work linear in D + n (times the logarithm of a search), nothing
+ * serial in a user's list length.  A batch that adds nothing allocates no new index.  Transient peak: the old index
+ * beside the new one (4 (D + new pairs) + 8 (user_capacity + 1)), 17 bytes per pair of the batch, staging and scratch.
+ * mfsgd_clear_seen: the handle has no index afterwards, and all of its device memory is freed.
+ * mfsgd_seen_size: *pairs = D, or -1 when the handle has no index.  Host only.
+ * mfsgd_get_seen: row_ptr (n_users + 1 entries) receives the CSR offsets of the requested users' lists, in the order
+ * requested; users may repeat.  With items != NULL and items_capacity >= row_ptr[n_users] it receives the lists too,
+ * ascending; a smaller capacity is MFSGD_ERR_INVALID_ARG with the needed size in the message and in row_ptr.  A gather
+ * kernel collects the lists: nothing of size D crosses the bus unless it was asked for.  MFSGD_ERR_INVALID_ARG
+ * ("get_seen: ..."): negative n_users, null row_ptr, null users with n_users > 0, negative items_capacity; then
+ * MFSGD_ERR_STATE for n_parts != 1 and for a handle without an index ("no seen set"); then a user out of range.
+ * n_users == 0 is MFSGD_OK.                                                                                            */
+int mfsgd_set_seen(mfsgd_handle* h, const int32_t* u, const int32_t* i, int64_t n);
+int mfsgd_mark_seen(mfsgd_handle* h, const int32_t* u, const int32_t* i, int64_t n);
+int mfsgd_clear_seen(mfsgd_handle* h);
+int mfsgd_seen_size(const mfsgd_handle* h, int64_t* pairs);
+int mfsgd_get_seen(mfsgd_handle* h, const int32_t* users, int32_t n_users, int64_t* row_ptr /* n_users + 1 */,
+                   int32_t* items /* nullable */, int64_t items_capacity);
+/* The serving calls against the index.  Each is the call it is named after -- mfsgd_recommend_excluding,
+ * mfsgd_recommend_among, mfsgd_rank_items, mfsgd_evaluate_ranking -- given the index's pairs as its exclusion pairs:
+ * order, ties, score bits, padding with -1 / NaN, the rule that a ranked pair's own item counts as eligible even if
+ * excluded, and what those calls say about NaN scores carry over.  (One corner: where NO requested user has a pair, the
+ * pair-list calls run their kernels without exclusions, these run them with empty lists; the two differ only in how a
+ * score whose bits are all ones, a NaN no arithmetic of this library produces, ties with other NaNs.)
+ * Checks are the base call's, in its order, the messages starting with the new call's name; "no seen set"
+ * (MFSGD_ERR_STATE) comes right after the n_parts check, before the remaining argument checks and the factor and device
+ * checks.  n_users == 0 / n == 0 stay MFSGD_OK.
+ * Cost: no host loop, no upload and no device pass follows D: the kernels reach a user's list through the user id, in the
+ * index where it lies, and nothing is allocated for exclusions.  mfsgd_debug_serve_seconds reports the two halves of the
+ * recommend calls; the lists half covers the candidate lists only.  The model and the index are not modified.         */
+int mfsgd_recommend_unseen(mfsgd_handle* h, const int32_t* users, int32_t n_users, int32_t topn, int32_t* out_items,
+                           float* out_scores);
+int mfsgd_recommend_unseen_among(mfsgd_handle* h, const int32_t* users, int32_t n_users, int32_t topn,
+                                 const int64_t* cand_ptr, const int32_t* cand_items, int64_t n_cand, int32_t* out_items,
+                                 float* out_scores);
+int mfsgd_rank_items_unseen(mfsgd_handle* h, const int32_t* users, const int32_t* items, int64_t n, int32_t* out_rank);
+int mfsgd_evaluate_ranking_unseen(mfsgd_handle* h, const int32_t* users, const int32_t* items, int64_t n, int32_t topn,
+                                  mfsgd_ranking_metrics* out, int32_t* out_rank /* nullable */);
 
 /* ---- similar items and users: cosine nearest neighbours among the rows of Q, or of P --------------------------------
  * The arithmetic, all fp32, round to nearest even, subnormals kept, nothing contracted; dot is

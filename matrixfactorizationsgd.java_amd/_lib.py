@@ -132,6 +132,15 @@ SIGNATURES = {
     "mfsgd_ranking_metrics_from_ranks": (C.c_int, [_i32p, _i32p, C.c_int64, C.c_int32, C.POINTER(RankingMetrics)]),
     "mfsgd_evaluate_ranking": (C.c_int, [_H, _i32p, _i32p, C.c_int64, C.c_int32, _i32p, _i32p, C.c_int64,
                                          C.POINTER(RankingMetrics), _i32p]),
+    "mfsgd_set_seen": (C.c_int, [_H, _i32p, _i32p, C.c_int64]),
+    "mfsgd_mark_seen": (C.c_int, [_H, _i32p, _i32p, C.c_int64]),
+    "mfsgd_clear_seen": (C.c_int, [_H]),
+    "mfsgd_seen_size": (C.c_int, [_H, _i64p]),
+    "mfsgd_get_seen": (C.c_int, [_H, _i32p, C.c_int32, _i64p, _i32p, C.c_int64]),
+    "mfsgd_recommend_unseen": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i32p, _f32p]),
+    "mfsgd_recommend_unseen_among": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i64p, _i32p, C.c_int64, _i32p, _f32p]),
+    "mfsgd_rank_items_unseen": (C.c_int, [_H, _i32p, _i32p, C.c_int64, _i32p]),
+    "mfsgd_evaluate_ranking_unseen": (C.c_int, [_H, _i32p, _i32p, C.c_int64, C.c_int32, C.POINTER(RankingMetrics), _i32p]),
     "mfsgd_row_inv_norms": (C.c_int, [_H, C.c_int32, _f32p]),
     "mfsgd_similar_items": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i32p, _f32p]),
     "mfsgd_similar_users": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i32p, _f32p]),

@@ -240,6 +240,70 @@ class MatrixFactorizationSGD {
         return {m, std::move(ranks)};
     }
 
+    // The seen-item index: what each user has already seen, built once on the device and kept there, so that the
+    // ...Unseen calls below serve "items this user has not seen" without the pair list.
+    // void setSeen(int[] u, int[] i): the index becomes the distinct pairs; markSeen: their union with the index (a merge
+    // on the device, the index is not sorted again); clearSeen: no index; long seenSize(): its pairs, -1 without one
+    void setSeen(const std::vector<int32_t>& u, const std::vector<int32_t>& i) {
+        if (u.size() != i.size()) throw std::invalid_argument("length mismatch");
+        check(mfsgd_set_seen(h_, u.data(), i.data(), (int64_t)u.size()));
+    }
+    void markSeen(const std::vector<int32_t>& u, const std::vector<int32_t>& i) {
+        if (u.size() != i.size()) throw std::invalid_argument("length mismatch");
+        check(mfsgd_mark_seen(h_, u.data(), i.data(), (int64_t)u.size()));
+    }
+    void clearSeen() { check(mfsgd_clear_seen(h_)); }
+    int64_t seenSize() {
+        int64_t n = -1;
+        check(mfsgd_seen_size(h_, &n));
+        return n;
+    }
+    // {long[] rowPtr, int[] items} seen(int[] users): the requested users' seen items, ascending within a user, CSR over
+    // users as given
+    std::pair<std::vector<int64_t>, std::vector<int32_t>> seen(const std::vector<int32_t>& users) {
+        std::vector<int64_t> ptr(users.size() + 1, 0);
+        check(mfsgd_get_seen(h_, users.data(), (int32_t)users.size(), ptr.data(), nullptr, 0));
+        std::vector<int32_t> items((size_t)ptr.back());
+        if (!items.empty())
+            check(mfsgd_get_seen(h_, users.data(), (int32_t)users.size(), ptr.data(), items.data(), (int64_t)items.size()));
+        return {std::move(ptr), std::move(items)};
+    }
+    // int[][] recommendUnseen(int[] users, int topN): recommend(users, topN, exclU, exclI) with the index's pairs
+    std::pair<std::vector<int32_t>, std::vector<float>> recommendUnseen(const std::vector<int32_t>& users, int topn) {
+        std::vector<int32_t> items(users.size() * (size_t)topn);
+        std::vector<float> scores(users.size() * (size_t)topn);
+        check(mfsgd_recommend_unseen(h_, users.data(), (int32_t)users.size(), topn, items.data(), scores.data()));
+        return {std::move(items), std::move(scores)};
+    }
+    // int[][] recommendUnseenAmong(int[] users, int topN, long[] candPtr, int[] candItems): recommendAmong likewise
+    std::pair<std::vector<int32_t>, std::vector<float>> recommendUnseenAmong(const std::vector<int32_t>& users, int topn,
+                                                                             const std::vector<int64_t>& cand_ptr,
+                                                                             const std::vector<int32_t>& cand_items) {
+        if (!cand_ptr.empty() && cand_ptr.size() != users.size() + 1) throw std::invalid_argument("length mismatch");
+        std::vector<int32_t> items(users.size() * (size_t)topn);
+        std::vector<float> scores(users.size() * (size_t)topn);
+        check(mfsgd_recommend_unseen_among(h_, users.data(), (int32_t)users.size(), topn,
+                                           cand_ptr.empty() ? nullptr : cand_ptr.data(), cand_items.data(),
+                                           (int64_t)cand_items.size(), items.data(), scores.data()));
+        return {std::move(items), std::move(scores)};
+    }
+    // int[] rankItemsUnseen(int[] u, int[] i) / RankingMetrics evaluateRankingUnseen(int[] u, int[] i, int topN): rankItems
+    // and evaluateRanking with the index's pairs not competing
+    std::vector<int32_t> rankItemsUnseen(const std::vector<int32_t>& u, const std::vector<int32_t>& i) {
+        if (u.size() != i.size()) throw std::invalid_argument("length mismatch");
+        std::vector<int32_t> ranks(u.size());
+        check(mfsgd_rank_items_unseen(h_, u.data(), i.data(), (int64_t)u.size(), ranks.data()));
+        return ranks;
+    }
+    std::pair<mfsgd_ranking_metrics, std::vector<int32_t>> evaluateRankingUnseen(const std::vector<int32_t>& u,
+                                                                                 const std::vector<int32_t>& i, int topn) {
+        if (u.size() != i.size()) throw std::invalid_argument("length mismatch");
+        mfsgd_ranking_metrics m{};
+        std::vector<int32_t> ranks(u.size());
+        check(mfsgd_evaluate_ranking_unseen(h_, u.data(), i.data(), (int64_t)u.size(), topn, &m, ranks.data()));
+        return {m, std::move(ranks)};
+    }
+
     double rmse() {
         double out = 0.0;
         check(mfsgd_rmse(h_, &out));

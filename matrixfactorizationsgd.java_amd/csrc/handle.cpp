@@ -239,6 +239,11 @@ static int append_rows(mfsgd_handle* h, bool items, const char* name, int32_t n_
     const int64_t need = (int64_t)count + n_new;
     std::vector<int32_t>& last = items ? h->online_last_i : h->online_last_u;
     if (!last.empty()) last.reserve((size_t)need);  // (what can fail comes before anything changes)
+    // users beyond the capacity: the per-user tables of the seen-item index grow with it, new before old as the rows do
+    DevBuf seen_off, seen_slot;
+    if (!items && need > h->user_capacity()) {
+        if (const int rc = seen_grown_tables(h, call.c_str(), (int32_t)need, seen_off, seen_slot)) return rc;
+    }
     if (h->where == mfsgd_handle::Where::Host) {
         std::vector<float>& v = items ? h->hQ : h->hP;
         const size_t old = v.size();
@@ -261,6 +266,10 @@ static int append_rows(mfsgd_handle* h, bool items, const char* name, int32_t n_
         if ((rc = write_new_rows(h, call.c_str(), grown ? grown.as<float>() : buf.as<float>(), count, n_new, rows, seed))) return rc;
         HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
         if (grown) adopt(h, buf, grown);
+    }
+    if (seen_off) {
+        (void)hipStreamSynchronize(h->stream);
+        seen_adopt_tables(h, (int32_t)need, seen_off, seen_slot);
     }
     count = (int32_t)need;
     if (items && !h->parts.empty()) h->parts[0].q_rows = count;
@@ -331,6 +340,7 @@ void mfsgd_destroy(mfsgd_handle* h) {
     h->dP.reset();
     h->dQ.reset();
     h->val = Validation{};
+    h->seen = Seen{};
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->side_stream) {
@@ -449,6 +459,14 @@ int mfsgd_reserve_rows(mfsgd_handle* h, int32_t user_capacity, int32_t item_capa
                       {h->dQ, h->cfg.n_items, h->item_capacity(), item_capacity, h->reserved_items}};
         for (Side& s : sides) {
             if (s.want <= s.capacity) continue;
+            DevBuf seen_off, seen_slot;  // the users' side: the tables of the seen-item index grow too
+            if (&s == &sides[0]) {
+                if (const int rc = seen_grown_tables(h, "reserve_rows: ", s.want, seen_off, seen_slot)) return rc;
+                if (seen_off) {
+                    const hipError_t e = hipStreamSynchronize(h->stream);
+                    if (e != hipSuccess) return serve_fail(h, "reserve_rows: ", e);
+                }
+            }
             if (h->where == mfsgd_handle::Where::Device && s.buf) {
                 int rc = ensure_device(h);
                 if (rc) return rc;
@@ -458,6 +476,7 @@ int mfsgd_reserve_rows(mfsgd_handle* h, int32_t user_capacity, int32_t item_capa
                 if (e != hipSuccess) return serve_fail(h, "reserve_rows: ", e);
                 adopt(h, s.buf, grown);
             }
+            seen_adopt_tables(h, s.want, seen_off, seen_slot);
             s.reserved = s.want;
         }
         return MFSGD_OK;
@@ -470,6 +489,41 @@ int mfsgd_get_capacity(const mfsgd_handle* h, int32_t* users, int32_t* items) {
         if (items) *items = h->item_capacity();
         return MFSGD_OK;
     });
+}
+
+// ---- the seen-item index (seen_index.cpp) ----
+int mfsgd_set_seen(mfsgd_handle* h, const int32_t* u, const int32_t* i, int64_t n) {
+    return guarded(h, "set_seen", [&]() -> int { return seen_update(h, "set_seen", false, u, i, n); });
+}
+
+int mfsgd_mark_seen(mfsgd_handle* h, const int32_t* u, const int32_t* i, int64_t n) {
+    return guarded(h, "mark_seen", [&]() -> int { return seen_update(h, "mark_seen", true, u, i, n); });
+}
+
+int mfsgd_clear_seen(mfsgd_handle* h) {
+    return guarded(h, "clear_seen", [&]() -> int {
+        if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "clear_seen: single-partition handles only");
+        if (h->device_ready) {
+            (void)hipSetDevice(h->cfg.device);
+            (void)hipStreamSynchronize(h->stream);
+        }
+        h->seen = Seen{};
+        return MFSGD_OK;
+    });
+}
+
+int mfsgd_seen_size(const mfsgd_handle* h, int64_t* pairs) {
+    return guarded(h, "seen_size", [&]() -> int {
+        if (!pairs) return fail(h, MFSGD_ERR_INVALID_ARG, "seen_size: pairs is null");
+        if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "seen_size: single-partition handles only");
+        *pairs = h->seen.present ? h->seen.n : -1;
+        return MFSGD_OK;
+    });
+}
+
+int mfsgd_get_seen(mfsgd_handle* h, const int32_t* users, int32_t n_users, int64_t* row_ptr, int32_t* items,
+                   int64_t items_capacity) {
+    return guarded(h, "get_seen", [&]() -> int { return seen_get(h, users, n_users, row_ptr, items, items_capacity); });
 }
 
 int mfsgd_debug_device_bytes(int64_t* live) {

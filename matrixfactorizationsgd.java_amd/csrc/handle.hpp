@@ -57,6 +57,34 @@ struct Validation {
     DevBuf du, di, dr, d_sse;
 };
 
+// The seen-item index of a handle (mfsgd_set_seen, mfsgd_mark_seen; seen.hip): what each user has already seen, one
+// sorted, distinct item list per user in CSR form on the device, where the _unseen serving calls read it.
+// present: the handle has an index, which may be empty (n == 0); the tables exist while n > 0.
+//   items  n x int32: the list of user u is items[off[u] .. off[u + 1]), ascending
+//   off    (capacity + 1) x int64, capacity = the handle's user_capacity() when the tables were made; every entry from
+//          the user count on holds n, so users appended inside the capacity have empty lists and need no work
+//   slot   capacity x int32, slot[u] = u: {slot, off, items} is a RecommendExcl whose slots are the user ids, so the
+//          EXCL kernels of recommend.hip read the index as they read the lists of one call
+// 4 n + 12 capacity + 8 bytes in all.
+struct Seen {
+    bool present = false;
+    int64_t n = 0;
+    int32_t capacity = 0;
+    DevBuf off, items, slot;
+    RecommendExcl excl() const {
+        RecommendExcl ex;
+        if (n > 0) {
+            ex.slot = slot.as<const int32_t>();
+            ex.off = off.as<const long long>();
+            ex.items = items.as<const int32_t>();
+        }
+        return ex;
+    }
+};
+
+// Pairs (exclusions, candidates, seen pairs) per upload of a call that reads a caller's list: 32 MB of staging
+constexpr int64_t kExclChunk = (int64_t)1 << 22;
+
 // d_sync: done[B] words (kDoneStride apart), then {arrivals, generation, -, -} of the kernel's start-of-launch
 // barrier, then {abort code, launches that started, -, -}.  Zeroed once, when allocated; the kernel keeps it
 // consistent from launch to launch by itself.
@@ -118,6 +146,8 @@ struct mfsgd_handle {
     double serve_lists_s = 0.0, serve_topn_s = 0.0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     mutable std::string err;
+    // what each user has already seen (mfsgd_set_seen, mfsgd_mark_seen): read by the _unseen serving calls
+    mfsgd::Seen seen;
 };
 
 namespace mfsgd {
@@ -177,6 +207,14 @@ int check_has_q(const mfsgd_handle* h, const char* call);
 int ensure_device(mfsgd_handle* h);
 int dev_alloc(mfsgd_handle* h, DevBuf& b, size_t bytes);
 int factors_to_device(mfsgd_handle* h);
+// seen_index.cpp.  The tables of the seen-item index for a user capacity of new_cap, when it has tables and they are
+// smaller: new ones (off2, slot2) filled on the handle's stream from the old, which stay as they are (the caller
+// synchronises, then seen_adopt_tables).  Nothing to do leaves off2 empty.  `prefix` starts the message of a failure.
+int seen_grown_tables(mfsgd_handle* h, const char* prefix, int32_t new_cap, DevBuf& off2, DevBuf& slot2);
+void seen_adopt_tables(mfsgd_handle* h, int32_t new_cap, DevBuf& off2, DevBuf& slot2);
+// ... and the bodies of mfsgd_set_seen (merge == false) / mfsgd_mark_seen, `name` being the call's, and of mfsgd_get_seen
+int seen_update(mfsgd_handle* h, const char* name, bool merge, const int32_t* u, const int32_t* i, int64_t n);
+int seen_get(mfsgd_handle* h, const int32_t* users, int32_t n_users, int64_t* row_ptr, int32_t* items, int64_t items_capacity);
 // ratings.cpp
 void default_item_map(mfsgd_handle* h);
 int prepare_compute(mfsgd_handle* h);  // ratings present; factors and every partition's schedule on the device

@@ -1,5 +1,5 @@
 // kernels.hpp -- host-callable launchers of every kernel unit: epoch.hip, cells.hip, kernels.hip, foldin.hip,
-// online.hip, rehyper.hip, recommend.hip, rank.hip, similar.hip, validate.hip and grow.hip.
+// online.hip, rehyper.hip, recommend.hip, rank.hip, seen.hip, similar.hip, validate.hip and grow.hip.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -151,9 +151,32 @@ hipError_t recommend_excl_lists(unsigned long long* keys, unsigned long long* ke
 // that come before it in that row's recommendation order (recommend.hip's), the items of the slot's exclusion list
 // left out (ex.off / ex.items indexed by the same slots; ex.off == nullptr: none; ex.slot is not read).  Every item is
 // a row of Q and every off[s] - base .. off[s + 1] - base lies inside items and out: the caller checks.
+// ex_by_user: the lists are those of the seen-item index instead, reached through the slot's user: ex.off[rows[s]].
 hipError_t launch_rank_items(int L, const float* P, const float* Q, const int32_t* rows, int n_slots, const long long* off,
                              long long base, const int32_t* items, int32_t n_items, const RecommendExcl& ex,
-                             int32_t* out, hipStream_t st);
+                             int32_t* out, hipStream_t st, bool ex_by_user = false);
+
+// seen.hip.  The seen-item index (handle.hpp, Seen): off (capacity + 1 entries, those from the user count on holding the
+// total), items, and the identity slot table that makes {slot, off, items} a RecommendExcl over user ids.
+// keys[x] = u[x] << 32 | i[x] for a chunk of pairs; recommend_excl_lists then makes a whole index of the keys.
+hipError_t seen_pair_keys(const int32_t* u, const int32_t* i, int64_t n, unsigned long long* keys, hipStream_t st);
+// The tables of a capacity: slot[x] = x for x < new_cap and, with off2 != nullptr, off2[x] = old_off[x] for x <= old_cap
+// and `total` for old_cap < x <= new_cap.
+hipError_t seen_tables(const long long* old_off, int32_t old_cap, int64_t total, int32_t new_cap, long long* off2, int32_t* slot,
+                       hipStream_t st);
+// The m keys of a batch sorted and made distinct (keys, through keys_tmp), and those the index {off, items} does not
+// hold, ascending, into keys_tmp: counts[0] distinct keys, counts[1] of them new.  flags: m bytes of scratch.
+hipError_t seen_batch_fresh(unsigned long long* keys, unsigned long long* keys_tmp, int64_t m, int32_t n_users,
+                            const long long* off, const int32_t* items, unsigned char* flags, unsigned* counts, DevBuf& temp,
+                            hipStream_t st);
+// The index {off, items} (`total` items, cap + 1 offsets) merged with n_fresh sorted distinct keys none of which it
+// holds, into off2 (cap + 1) and items2 (total + n_fresh).  Every user of a key is below cap: the caller checks.
+hipError_t seen_merge(const long long* off, const int32_t* items, int64_t total, int32_t cap, const unsigned long long* fresh,
+                      int64_t n_fresh, long long* off2, int32_t* items2, hipStream_t st);
+// len[b] = the length of the list of users[b]; out[row_ptr[b] ...] = that list (longest: the largest len).
+hipError_t seen_lengths(const long long* off, const int32_t* users, int32_t n, long long* len, hipStream_t st);
+hipError_t seen_gather(const long long* off, const int32_t* items, const int32_t* users, int32_t n, const long long* row_ptr,
+                       int64_t longest, int32_t* out, hipStream_t st);
 
 // similar.hip.  out[x] = rn(row x) = 1 / sqrt(dot(row, row)), or 0 where that dot is 0, for the
 // n_rows kp-padded rows of M.  Asynchronous on st.

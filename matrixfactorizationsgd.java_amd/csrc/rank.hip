@@ -55,8 +55,9 @@ __device__ __forceinline__ int beaten(const unsigned long long* thr, const int n
 
 // Slot s = blockIdx.x * kRankUsers + j is user rows[s]; its pairs are items[off[s] - base .. off[s + 1] - base), and
 // out[...] at the same places receives their ranks.  ex_off / ex_items: RecommendExcl's lists of the same slots
-// (ex_off == nullptr: none).
-template <int L>
+// (ex_off == nullptr: none).  BY_USER: the lists are indexed by user instead, slot s having that of rows[s] (the
+// seen-item index of the handle, read where it lies).
+template <int L, bool BY_USER>
 __global__ void __launch_bounds__(kRankThreads) rank_kernel(const float* __restrict__ P, const float* __restrict__ Q,
                                                             const int32_t* __restrict__ rows, const int n_slots,
                                                             const long long* __restrict__ off, const long long base,
@@ -201,7 +202,8 @@ __global__ void __launch_bounds__(kRankThreads) rank_kernel(const float* __restr
 #pragma unroll
         for (int j = 0; j < UPW; ++j) {
             if (n[j] == 0 || !ex_off) continue;  // (uniform)
-            const long long x_at = ex_off[s0 + j], len = ex_off[s0 + j + 1] - x_at;
+            const int xs = BY_USER ? rows[s0 + j] : s0 + j;  // (n[j] > 0: the slot exists)
+            const long long x_at = ex_off[xs], len = ex_off[xs + 1] - x_at;
             const long long xiters = (len + GPB - 1) / GPB;
             for (long long xt = 0; xt < xiters; ++xt) {
                 const long long x = grp + xt * GPB;
@@ -260,12 +262,16 @@ __global__ void __launch_bounds__(kRankThreads) rank_kernel(const float* __restr
 
 hipError_t launch_rank_items(int L, const float* P, const float* Q, const int32_t* rows, int n_slots, const long long* off,
                              long long base, const int32_t* items, int32_t n_items, const RecommendExcl& ex,
-                             int32_t* out, hipStream_t st) {
+                             int32_t* out, hipStream_t st, bool ex_by_user) {
     if (n_slots <= 0) return hipSuccess;
     const dim3 grid((unsigned)((n_slots + kRankUsers - 1) / kRankUsers));
     return with_L(L, [&](auto l) {
-        hipLaunchKernelGGL((rank_kernel<l()>), grid, dim3(kRankThreads), 0, st, P, Q, rows, n_slots, off, base, items, n_items,
-                           ex.off, ex.items, out);
+        if (ex_by_user)
+            hipLaunchKernelGGL((rank_kernel<l(), true>), grid, dim3(kRankThreads), 0, st, P, Q, rows, n_slots, off, base, items,
+                               n_items, ex.off, ex.items, out);
+        else
+            hipLaunchKernelGGL((rank_kernel<l(), false>), grid, dim3(kRankThreads), 0, st, P, Q, rows, n_slots, off, base, items,
+                               n_items, ex.off, ex.items, out);
         return hipGetLastError();
     });
 }

@@ -17,6 +17,10 @@ struct ServeName {
 };
 constexpr ServeName kRecommend{"recommend", "the requested users"}, kRank{"rank_items", "the users asked about"};
 constexpr ServeName kAmong{"recommend_among", "the requested users"}, kRowsAmong{"recommend_rows_among", "the rows"};
+// ... and the calls that exclude what the handle's seen-item index holds instead of a pair list
+constexpr ServeName kUnseen{"recommend_unseen", "the requested users"}, kUnseenAmong{"recommend_unseen_among", "the requested users"};
+constexpr ServeName kRankUnseen{"rank_items_unseen", "the users asked about"};
+constexpr ServeName kEvaluateUnseen{"evaluate_ranking_unseen", "the users asked about"};
 
 // The row matrix of a serving call on the device: the model's P, or host_rows (n_rows x k, dense), which goes up into
 // a kp-padded temporary (`buf`) for the length of the call.
@@ -49,8 +53,7 @@ static int count_exclusions(const mfsgd_handle* h, const ServeName& what, const 
 // users are kept (slot << 32 | item), then sorted and made distinct into one list per slot (recommend.hip).
 // Scratch lives as long as this function; `ex` points into `slot`, `off` and `items`, which are the caller's.
 // `what` starts the message of a HIP failure: the call the lists are built for.
-constexpr int64_t kExclChunk = (int64_t)1 << 22;  // pairs per upload: 32 MB of staging
-
+// (kExclChunk pairs per upload, handle.hpp)
 static int exclusions_to_device(mfsgd_handle* h, const ServeName& what, const std::vector<int32_t>& slot_of_user, int32_t n_slots,
                                 const int32_t* excl_u, const int32_t* excl_i, int64_t n_excl, int64_t kept, DevBuf& slot,
                                 DevBuf& off, DevBuf& items, DevBuf& temp, RecommendExcl& ex) {
@@ -225,15 +228,18 @@ static int topn_batches(mfsgd_handle* h, const char* prefix, const float* P, con
 // host_rows == nullptr: the matrix is the model's P.  Otherwise it is host_rows (n_rows x k, dense).
 // `what` is how the messages of the argument checks name the call (both recommend calls say "recommend"), `own` the
 // call's own name, which its state errors carry.  cand != nullptr: among the candidates only (the among calls), which
-// are checked after the users and before the exclusion pairs.
+// are checked after the users and before the exclusion pairs.  unseen: the exclusion lists are those of the handle's
+// seen-item index, read where they lie through its identity slot table (the _unseen calls: no pairs, the model's P) --
+// nothing is built, uploaded or looped over for them, on the host or on the device.
 static int recommend_core(mfsgd_handle* h, const ServeName& what, const char* own, const float* host_rows, int32_t n_rows,
                           const int32_t* users, int32_t n_users, int32_t topn, const Candidates* cand, const int32_t* excl_u,
-                          const int32_t* excl_i, int64_t n_excl, int32_t* out_items, float* out_scores) {
+                          const int32_t* excl_i, int64_t n_excl, int32_t* out_items, float* out_scores, bool unseen = false) {
     const std::string call = std::string(what.call) + ": ";
     if (n_users < 0 || topn < 1 || (n_users > 0 && (!users || !out_items || !out_scores)) || n_excl < 0 ||
         (n_excl > 0 && (!excl_u || !excl_i)))
         return fail(h, MFSGD_ERR_INVALID_ARG, call + "bad argument");
     if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, call + "single-partition handles only");
+    if (unseen && !h->seen.present) return fail(h, MFSGD_ERR_STATE, call + "no seen set");
     if (topn > h->cfg.n_items) return fail(h, MFSGD_ERR_INVALID_ARG, call + "topn exceeds the number of items");
     for (int32_t j = 0; j < n_users; ++j)
         if (users[j] < 0 || users[j] >= n_rows)
@@ -289,6 +295,7 @@ static int recommend_core(mfsgd_handle* h, const ServeName& what, const char* ow
     CandLists cl;  // built once for all batches
     if (cand && (rc = candidates_to_device(h, what, *cand, n_users, cand_off, cand_items, temp, cl))) return rc;
     RecommendExcl ex;  // built once for all batches; none when no pair belongs to a requested user
+    if (unseen) ex = h->seen.excl();  // (none when the index is empty)
     if (kept > 0 && (rc = exclusions_to_device(h, what, slot_of_user, n_slots, excl_u, excl_i, n_excl, kept, ex_slot,
                                                ex_off, ex_items, temp, ex)))
         return rc;
@@ -372,18 +379,24 @@ constexpr int64_t kRankChunk = (int64_t)1 << 22;
 // rows, the model's P (host_rows == nullptr) or host_rows (n_rows x k, dense).  The pairs are grouped by distinct
 // user on the host (counting sort; one slot per user, the slot numbering the exclusion lists use too), go up in
 // bounded pieces of whole users, and the ranks come back to the places of the pairs as given.
-static int rank_core(mfsgd_handle* h, const float* host_rows, int32_t n_rows, const int32_t* users, const int32_t* items,
-                     int64_t n, const int32_t* excl_u, const int32_t* excl_i, int64_t n_excl, int32_t* out_rank) {
-    if (n < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: n is negative");
-    if (n_excl < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: n_excl is negative");
+// `what` is how the call speaks of itself (kRank for every call with a pair list).  unseen: the exclusion lists are those
+// of the handle's seen-item index, which the kernel reaches through each slot's user (the _unseen calls: no pairs, the
+// model's P).
+static int rank_core(mfsgd_handle* h, const ServeName& what, const float* host_rows, int32_t n_rows, const int32_t* users,
+                     const int32_t* items, int64_t n, const int32_t* excl_u, const int32_t* excl_i, int64_t n_excl,
+                     int32_t* out_rank, bool unseen = false) {
+    const std::string call = std::string(what.call) + ": ";
+    if (n < 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "n is negative");
+    if (n_excl < 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "n_excl is negative");
     if (n > 0 && (!users || !items || !out_rank))
-        return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: users, items or out_rank is null");
-    if (n_excl > 0 && (!excl_u || !excl_i)) return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: an exclusion array is null");
-    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "rank_items: single-partition handles only");
+        return fail(h, MFSGD_ERR_INVALID_ARG, call + "users, items or out_rank is null");
+    if (n_excl > 0 && (!excl_u || !excl_i)) return fail(h, MFSGD_ERR_INVALID_ARG, call + "an exclusion array is null");
+    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, call + "single-partition handles only");
+    if (unseen && !h->seen.present) return fail(h, MFSGD_ERR_STATE, call + "no seen set");
     const int32_t I = h->cfg.n_items;
     for (int64_t x = 0; x < n; ++x)
         if (users[x] < 0 || users[x] >= n_rows || items[x] < 0 || items[x] >= I)
-            return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: pair " + std::to_string(x) + " out of range");
+            return fail(h, MFSGD_ERR_INVALID_ARG, call + "pair " + std::to_string(x) + " out of range");
     // a slot per distinct user, and how many exclusion pairs are theirs
     std::vector<int32_t> slot_of_user((size_t)n_rows, -1), row_of_slot;
     std::vector<long long> off{0};
@@ -415,12 +428,12 @@ static int rank_core(mfsgd_handle* h, const float* host_rows, int32_t n_rows, co
         off.swap(off_sorted);
     }
     int64_t kept = 0;
-    int rc = count_exclusions(h, kRank, slot_of_user, n_rows, excl_u, excl_i, n_excl, &kept);
+    int rc = count_exclusions(h, what, slot_of_user, n_rows, excl_u, excl_i, n_excl, &kept);
     if (rc) return rc;
     if (n == 0) return MFSGD_OK;
     if (h->where == mfsgd_handle::Where::None)  // (asked here: factors_to_device wants a device first)
-        return fail(h, MFSGD_ERR_STATE, "rank_items: factors not initialised");
-    if ((rc = check_has_q(h, "rank_items")) || (rc = factors_to_device(h))) return rc;
+        return fail(h, MFSGD_ERR_STATE, call + "factors not initialised");
+    if ((rc = check_has_q(h, what.call)) || (rc = factors_to_device(h))) return rc;
     // counting sort: the pairs of slot s at off[s] .. off[s + 1], in the order given; place[x] = where pair x went
     for (int32_t s = 0; s < n_slots; ++s) off[(size_t)s + 1] += off[(size_t)s];
     std::vector<int32_t> grouped((size_t)n), ranks((size_t)n);
@@ -441,12 +454,13 @@ static int rank_core(mfsgd_handle* h, const float* host_rows, int32_t n_rows, co
         cut.push_back(s1);
         s = s1;
     }
-    auto bad = [h](hipError_t e) { return serve_fail(h, "rank_items: ", e); };
+    auto bad = [h, &call](hipError_t e) { return serve_fail(h, call.c_str(), e); };
     DevBuf d_rows, d_slot_rows, d_off, d_items, d_out, ex_slot, ex_off, ex_items, temp;
     const float* P;
     if ((rc = upload_rows(h, host_rows, n_rows, d_rows, &P))) return rc;
     RecommendExcl ex;  // built once for all launches; none when no pair belongs to a user asked about
-    if (kept > 0 && (rc = exclusions_to_device(h, kRank, slot_of_user, n_slots, excl_u, excl_i, n_excl, kept, ex_slot, ex_off,
+    if (unseen) ex = h->seen.excl();  // (none when the index is empty)
+    if (kept > 0 && (rc = exclusions_to_device(h, what, slot_of_user, n_slots, excl_u, excl_i, n_excl, kept, ex_slot, ex_off,
                                                ex_items, temp, ex)))
         return rc;
     if ((rc = upload(h, d_slot_rows, row_of_slot))) return rc;
@@ -458,11 +472,11 @@ static int rank_core(mfsgd_handle* h, const float* host_rows, int32_t n_rows, co
         const long long base = off[(size_t)b0];
         const size_t bytes = sizeof(int32_t) * (size_t)(off[(size_t)(b0 + nb)] - base);
         RecommendExcl exb = ex;
-        if (exb.off) exb.off += b0;
+        if (exb.off && !unseen) exb.off += b0;  // (the index is reached by user, not by slot)
         HIPCHK_OR(bad, hipMemcpyAsync(d_items.get(), grouped.data() + base, bytes, hipMemcpyHostToDevice, h->stream));
         HIPCHK_OR(bad, launch_rank_items(h->geo.L, P, h->dQ.as<const float>(), d_slot_rows.as<const int32_t>() + b0, nb,
                                          d_off.as<const long long>() + b0, base, d_items.as<const int32_t>(), I, exb,
-                                         d_out.as<int32_t>(), h->stream));
+                                         d_out.as<int32_t>(), h->stream, unseen));
         HIPCHK_OR(bad, hipMemcpyAsync(ranks.data() + base, d_out.get(), bytes, hipMemcpyDeviceToHost, h->stream));
         HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // the staging buffers are reused
     }
@@ -710,7 +724,7 @@ int mfsgd_similar_rows(mfsgd_handle* h, int32_t side, const float* rows, int32_t
 int mfsgd_rank_items(mfsgd_handle* h, const int32_t* users, const int32_t* items, int64_t n, const int32_t* excl_u,
                      const int32_t* excl_i, int64_t n_excl, int32_t* out_rank) {
     return guarded(h, "rank_items", [&]() -> int {
-        return rank_core(h, nullptr, h->cfg.n_users, users, items, n, excl_u, excl_i, n_excl, out_rank);
+        return rank_core(h, kRank, nullptr, h->cfg.n_users, users, items, n, excl_u, excl_i, n_excl, out_rank);
     });
 }
 
@@ -720,7 +734,7 @@ int mfsgd_rank_items_rows(mfsgd_handle* h, const float* rows, int32_t n_rows, co
     return guarded(h, "rank_items", [&]() -> int {
         if (n_rows < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: n_rows is negative");
         if (n_rows > 0 && !rows) return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: rows is null");
-        return rank_core(h, rows, n_rows, row_of_pair, items, n, excl_row, excl_item, n_excl, out_rank);
+        return rank_core(h, kRank, rows, n_rows, row_of_pair, items, n, excl_row, excl_item, n_excl, out_rank);
     });
 }
 
@@ -772,22 +786,60 @@ int mfsgd_ranking_metrics_from_ranks(const int32_t* users, const int32_t* ranks,
     });
 }
 
+// Body of the evaluate calls: rank_core, then the metrics of its ranks.
+static int evaluate_core(mfsgd_handle* h, const ServeName& what, const int32_t* users, const int32_t* items, int64_t n,
+                         int32_t topn, const int32_t* excl_u, const int32_t* excl_i, int64_t n_excl, mfsgd_ranking_metrics* out,
+                         int32_t* out_rank, bool unseen) {
+    const std::string call = std::string(what.call) + ": ";
+    if (topn < 1) return fail(h, MFSGD_ERR_INVALID_ARG, call + "topn is below 1");
+    if (!out) return fail(h, MFSGD_ERR_INVALID_ARG, call + "the metrics struct is null");
+    std::vector<int32_t> own;
+    if (!out_rank && n > 0) {
+        own.resize((size_t)n);
+        out_rank = own.data();
+    }
+    int rc = rank_core(h, what, nullptr, h->cfg.n_users, users, items, n, excl_u, excl_i, n_excl, out_rank, unseen);
+    if (rc) return rc;
+    rc = mfsgd_ranking_metrics_from_ranks(users, out_rank, n, topn, out);
+    if (rc) return fail(h, rc, g_create_error);
+    return MFSGD_OK;
+}
+
 int mfsgd_evaluate_ranking(mfsgd_handle* h, const int32_t* users, const int32_t* items, int64_t n, int32_t topn,
                            const int32_t* excl_u, const int32_t* excl_i, int64_t n_excl, mfsgd_ranking_metrics* out,
                            int32_t* out_rank) {
     return guarded(h, "rank_items", [&]() -> int {
-        if (topn < 1) return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: topn is below 1");
-        if (!out) return fail(h, MFSGD_ERR_INVALID_ARG, "rank_items: the metrics struct is null");
-        std::vector<int32_t> own;
-        if (!out_rank && n > 0) {
-            own.resize((size_t)n);
-            out_rank = own.data();
-        }
-        int rc = rank_core(h, nullptr, h->cfg.n_users, users, items, n, excl_u, excl_i, n_excl, out_rank);
-        if (rc) return rc;
-        rc = mfsgd_ranking_metrics_from_ranks(users, out_rank, n, topn, out);
-        if (rc) return fail(h, rc, g_create_error);
-        return MFSGD_OK;
+        return evaluate_core(h, kRank, users, items, n, topn, excl_u, excl_i, n_excl, out, out_rank, false);
+    });
+}
+
+int mfsgd_recommend_unseen(mfsgd_handle* h, const int32_t* users, int32_t n_users, int32_t topn, int32_t* out_items,
+                           float* out_scores) {
+    return guarded(h, kUnseen.call, [&]() -> int {
+        return recommend_core(h, kUnseen, kUnseen.call, nullptr, h->cfg.n_users, users, n_users, topn, nullptr, nullptr, nullptr, 0,
+                              out_items, out_scores, true);
+    });
+}
+
+int mfsgd_recommend_unseen_among(mfsgd_handle* h, const int32_t* users, int32_t n_users, int32_t topn, const int64_t* cand_ptr,
+                                 const int32_t* cand_items, int64_t n_cand, int32_t* out_items, float* out_scores) {
+    return guarded(h, kUnseenAmong.call, [&]() -> int {
+        const Candidates cand{cand_ptr, cand_items, n_cand};
+        return recommend_core(h, kUnseenAmong, kUnseenAmong.call, nullptr, h->cfg.n_users, users, n_users, topn, &cand, nullptr,
+                              nullptr, 0, out_items, out_scores, true);
+    });
+}
+
+int mfsgd_rank_items_unseen(mfsgd_handle* h, const int32_t* users, const int32_t* items, int64_t n, int32_t* out_rank) {
+    return guarded(h, kRankUnseen.call, [&]() -> int {
+        return rank_core(h, kRankUnseen, nullptr, h->cfg.n_users, users, items, n, nullptr, nullptr, 0, out_rank, true);
+    });
+}
+
+int mfsgd_evaluate_ranking_unseen(mfsgd_handle* h, const int32_t* users, const int32_t* items, int64_t n, int32_t topn,
+                                  mfsgd_ranking_metrics* out, int32_t* out_rank) {
+    return guarded(h, kEvaluateUnseen.call, [&]() -> int {
+        return evaluate_core(h, kEvaluateUnseen, users, items, n, topn, nullptr, nullptr, 0, out, out_rank, true);
     });
 }
 

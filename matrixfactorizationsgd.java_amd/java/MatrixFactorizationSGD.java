@@ -101,6 +101,79 @@ public final class MatrixFactorizationSGD implements AutoCloseable {
     }
 
     /**
+     * The seen-item index: what each user has already seen, built once on the device and kept there, so that the
+     * ...Unseen calls serve "items this user has not seen" without the pair list.  setSeen: the index becomes the
+     * distinct pairs (u[x], i[x]).
+     */
+    public void setSeen(int[] u, int[] i) {
+        if (u.length != i.length) throw new IllegalArgumentException("length mismatch");
+        nativeSeenUpdate(handle, 0, u, i);
+    }
+
+    /** The union of the index and the pairs: a merge on the device, the index is not sorted again. */
+    public void markSeen(int[] u, int[] i) {
+        if (u.length != i.length) throw new IllegalArgumentException("length mismatch");
+        nativeSeenUpdate(handle, 1, u, i);
+    }
+
+    /** Drops the index and frees its device memory. */
+    public void clearSeen() {
+        nativeSeenUpdate(handle, 2, null, null);
+    }
+
+    /** Distinct pairs in the index; -1 when the model has none. */
+    public long seenSize() {
+        return nativeSeenSize(handle);
+    }
+
+    /** The seen items of the requested users, ascending within a user: list a belongs to users[a]. */
+    public int[][] seen(int[] users) {
+        int[] rowPtr = new int[users.length + 1];
+        nativeGetSeen(handle, users, rowPtr, null);
+        int[] items = new int[rowPtr[users.length]];
+        if (items.length > 0) nativeGetSeen(handle, users, rowPtr, items);
+        int[][] out = new int[users.length][];
+        for (int a = 0; a < users.length; a++) out[a] = java.util.Arrays.copyOfRange(items, rowPtr[a], rowPtr[a + 1]);
+        return out;
+    }
+
+    /** recommend(users, topN, exclU, exclI) with the pairs of the seen-item index, read on the device where they lie. */
+    public int[][] recommendUnseen(int[] users, int topN) {
+        return recommendUnseenAmong(users, topN, null, null);
+    }
+
+    /** recommendAmong with the pairs of the seen-item index; candItems == null: every item (recommendUnseen). */
+    public int[][] recommendUnseenAmong(int[] users, int topN, long[] candPtr, int[] candItems) {
+        if (candPtr != null && (candItems == null || candPtr.length != users.length + 1))
+            throw new IllegalArgumentException("length mismatch");
+        int[] items = new int[users.length * topN];
+        float[] scores = new float[users.length * topN];
+        nativeRecommendUnseen(handle, users, topN, candPtr, candItems, items, scores);
+        int[][] out = new int[users.length][];
+        for (int a = 0; a < users.length; a++) out[a] = java.util.Arrays.copyOfRange(items, a * topN, (a + 1) * topN);
+        return out;
+    }
+
+    /** rankItems(u, i, exclU, exclI) with the pairs of the seen-item index. */
+    public int[] rankItemsUnseen(int[] u, int[] i) {
+        if (u.length != i.length) throw new IllegalArgumentException("length mismatch");
+        int[] ranks = new int[u.length];
+        nativeRankUnseen(handle, u, i, 0, null, ranks);
+        return ranks;
+    }
+
+    /**
+     * evaluateRanking with the pairs of the seen-item index: {nPairs, nUsers, hitRate, precision, recall, ndcg, mrr},
+     * and the ranks into ranks (u.length entries; may be null).
+     */
+    public double[] evaluateRankingUnseen(int[] u, int[] i, int topN, int[] ranks) {
+        if (u.length != i.length) throw new IllegalArgumentException("length mismatch");
+        double[] metrics = new double[7];
+        nativeRankUnseen(handle, u, i, topN, metrics, ranks != null ? ranks : new int[u.length]);
+        return metrics;
+    }
+
+    /**
      * As recommend(users, topN), but never item exclI[x] for user exclU[x] (typically the arrays the model was trained
      * on, so that only unrated items come back).  A user with fewer than topN eligible items gets -1 in the places left.
      */
@@ -544,6 +617,12 @@ public final class MatrixFactorizationSGD implements AutoCloseable {
                                                         float[] scores);
     private static native void nativeRecommendAmong(long h, int[] users, int topN, long[] candPtr, int[] candItems, int[] exclU,
                                                     int[] exclI, int[] items, float[] scores);
+    private static native void nativeSeenUpdate(long h, int op, int[] u, int[] i);
+    private static native long nativeSeenSize(long h);
+    private static native void nativeGetSeen(long h, int[] users, int[] rowPtr, int[] items);
+    private static native void nativeRecommendUnseen(long h, int[] users, int topN, long[] candPtr, int[] candItems, int[] items,
+                                                     float[] scores);
+    private static native void nativeRankUnseen(long h, int[] u, int[] i, int topN, double[] metrics7, int[] ranks);
     private static native void nativeFoldIn(long h, long[] rowPtr, int[] items, float[] ratings, int epochs, float[] init,
                                             long seed, float[] rows);
     private static native void nativeFoldInItems(long h, long[] rowPtr, int[] users, float[] ratings, int epochs, float[] init,

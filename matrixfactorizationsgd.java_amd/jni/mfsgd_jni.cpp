@@ -412,6 +412,112 @@ JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeRecommendAmong(JNIEnv* 
     throw_status(env, H(h), rc);
 }
 
+// ---- the seen-item index: setSeen / markSeen / clearSeen (op 0 / 1 / 2), seenSize, seen, and the ...Unseen calls ----
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeSeenUpdate(JNIEnv* env, jclass, jlong h, jint op, jintArray u, jintArray i) {
+    if (op == 2) return throw_status(env, H(h), mfsgd_clear_seen(H(h)));
+    if (!u || !i) return throw_new(env, "java/lang/NullPointerException", op == 0 ? "setSeen" : "markSeen");
+    const jsize n = env->GetArrayLength(u);
+    if (env->GetArrayLength(i) != n) return throw_new(env, "java/lang/IllegalArgumentException", "u and i must have the same length");
+    // copies, not pins: the call uploads the pairs and waits for the device
+    auto cu = alloc<int32_t>(env, (size_t)n);
+    auto ci = alloc<int32_t>(env, (size_t)n);
+    if (!cu || !ci) return;
+    env->GetIntArrayRegion(u, 0, n, reinterpret_cast<jint*>(cu.get()));
+    env->GetIntArrayRegion(i, 0, n, reinterpret_cast<jint*>(ci.get()));
+    if (env->ExceptionCheck()) return;
+    throw_status(env, H(h), (op == 0 ? mfsgd_set_seen : mfsgd_mark_seen)(H(h), cu.get(), ci.get(), (int64_t)n));
+}
+
+JNIEXPORT jlong JNICALL Java_MatrixFactorizationSGD_nativeSeenSize(JNIEnv* env, jclass, jlong h) {
+    int64_t n = -1;
+    throw_status(env, H(h), mfsgd_seen_size(H(h), &n));
+    return (jlong)n;
+}
+
+// items == null: the offsets only.  The offsets come back as ints: the lists of one call fill a Java array, so their total
+// is below 2^31 or the call is refused.
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeGetSeen(JNIEnv* env, jclass, jlong h, jintArray users, jintArray row_ptr,
+                                                                 jintArray items) {
+    if (!users || !row_ptr) return throw_new(env, "java/lang/NullPointerException", "seen");
+    const jsize n = env->GetArrayLength(users);
+    const jsize ni = items ? env->GetArrayLength(items) : 0;
+    if ((jlong)env->GetArrayLength(row_ptr) != (jlong)n + 1)
+        return throw_new(env, "java/lang/IllegalArgumentException", "rowPtr must have users.length + 1 entries");
+    auto cu = alloc<int32_t>(env, (size_t)n);
+    auto cp = alloc<int64_t>(env, (size_t)n + 1);
+    auto cp32 = alloc<int32_t>(env, (size_t)n + 1);
+    auto ci = alloc<int32_t>(env, (size_t)ni);
+    if (!cu || !cp || !cp32 || !ci) return;
+    env->GetIntArrayRegion(users, 0, n, reinterpret_cast<jint*>(cu.get()));
+    if (env->ExceptionCheck()) return;
+    const int rc = mfsgd_get_seen(H(h), cu.get(), n, cp.get(), items ? ci.get() : nullptr, (int64_t)ni);
+    if (rc == MFSGD_OK) {
+        if (cp.get()[n] > (int64_t)INT32_MAX)
+            return throw_new(env, "java/lang/IllegalArgumentException", "seen: the lists hold more than 2^31 - 1 items; ask for fewer users");
+        for (jsize x = 0; x <= n; ++x) cp32.get()[x] = (int32_t)cp.get()[x];
+        env->SetIntArrayRegion(row_ptr, 0, n + 1, reinterpret_cast<const jint*>(cp32.get()));
+        if (items && cp.get()[n] > 0) env->SetIntArrayRegion(items, 0, (jsize)cp.get()[n], reinterpret_cast<const jint*>(ci.get()));
+    }
+    throw_status(env, H(h), rc);
+}
+
+// cand_items == null: every item (mfsgd_recommend_unseen); otherwise the candidates as nativeRecommendAmong takes them
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeRecommendUnseen(JNIEnv* env, jclass, jlong h, jintArray users, jint topn,
+                                                                         jlongArray cand_ptr, jintArray cand_items,
+                                                                         jintArray items, jfloatArray scores) {
+    if (!users || !items || !scores || (cand_ptr && !cand_items))
+        return throw_new(env, "java/lang/NullPointerException", "recommendUnseen");
+    const jsize n = env->GetArrayLength(users);
+    const jsize nc = cand_items ? env->GetArrayLength(cand_items) : 0;
+    if (cand_ptr && (jlong)env->GetArrayLength(cand_ptr) != (jlong)n + 1)
+        return throw_new(env, "java/lang/IllegalArgumentException", "candPtr must have users.length + 1 entries");
+    if (topn < 1 || (jlong)env->GetArrayLength(items) < (jlong)n * topn || (jlong)env->GetArrayLength(scores) < (jlong)n * topn)
+        return throw_new(env, "java/lang/IllegalArgumentException", "items / scores shorter than users x topN");
+    auto cu = alloc<int32_t>(env, (size_t)n);
+    auto cp = alloc<int64_t>(env, (size_t)n + 1);
+    auto cc = alloc<int32_t>(env, (size_t)nc);
+    auto ci = alloc<int32_t>(env, (size_t)n * (size_t)topn);
+    auto cs = alloc<float>(env, (size_t)n * (size_t)topn);
+    if (!cu || !cp || !cc || !ci || !cs) return;
+    env->GetIntArrayRegion(users, 0, n, reinterpret_cast<jint*>(cu.get()));
+    if (cand_ptr) env->GetLongArrayRegion(cand_ptr, 0, n + 1, reinterpret_cast<jlong*>(cp.get()));
+    if (cand_items) env->GetIntArrayRegion(cand_items, 0, nc, reinterpret_cast<jint*>(cc.get()));
+    if (env->ExceptionCheck()) return;
+    const int rc = cand_items ? mfsgd_recommend_unseen_among(H(h), cu.get(), n, topn, cand_ptr ? cp.get() : nullptr, cc.get(),
+                                                             (int64_t)nc, ci.get(), cs.get())
+                              : mfsgd_recommend_unseen(H(h), cu.get(), n, topn, ci.get(), cs.get());
+    if (rc == MFSGD_OK && n > 0) {
+        env->SetIntArrayRegion(items, 0, n * topn, reinterpret_cast<const jint*>(ci.get()));
+        env->SetFloatArrayRegion(scores, 0, n * topn, cs.get());
+    }
+    throw_status(env, H(h), rc);
+}
+
+// metrics7 == null: the ranks alone (mfsgd_rank_items_unseen); otherwise mfsgd_evaluate_ranking_unseen at topn
+JNIEXPORT void JNICALL Java_MatrixFactorizationSGD_nativeRankUnseen(JNIEnv* env, jclass, jlong h, jintArray u, jintArray i, jint topn,
+                                                                    jdoubleArray metrics7, jintArray ranks) {
+    if (!u || !i || !ranks) return throw_new(env, "java/lang/NullPointerException", "rankItemsUnseen");
+    const jsize n = env->GetArrayLength(u);
+    if (env->GetArrayLength(i) != n || env->GetArrayLength(ranks) < n || (metrics7 && env->GetArrayLength(metrics7) < 7))
+        return throw_new(env, "java/lang/IllegalArgumentException", "rankItemsUnseen: length mismatch");
+    auto cu = alloc<int32_t>(env, (size_t)n);
+    auto ci = alloc<int32_t>(env, (size_t)n);
+    auto cr = alloc<int32_t>(env, (size_t)n);
+    if (!cu || !ci || !cr) return;
+    env->GetIntArrayRegion(u, 0, n, reinterpret_cast<jint*>(cu.get()));
+    env->GetIntArrayRegion(i, 0, n, reinterpret_cast<jint*>(ci.get()));
+    if (env->ExceptionCheck()) return;
+    mfsgd_ranking_metrics m = {};
+    const int rc = metrics7 ? mfsgd_evaluate_ranking_unseen(H(h), cu.get(), ci.get(), (int64_t)n, topn, &m, cr.get())
+                            : mfsgd_rank_items_unseen(H(h), cu.get(), ci.get(), (int64_t)n, cr.get());
+    if (rc == MFSGD_OK && n > 0) env->SetIntArrayRegion(ranks, 0, n, reinterpret_cast<const jint*>(cr.get()));
+    if (rc == MFSGD_OK && metrics7) {
+        const jdouble v[7] = {(jdouble)m.n_pairs, (jdouble)m.n_users, m.hit_rate, m.precision, m.recall, m.ndcg, m.mrr};
+        env->SetDoubleArrayRegion(metrics7, 0, 7, v);
+    }
+    throw_status(env, H(h), rc);
+}
+
 namespace {
 
 // Body of the two fold-in natives: new users against Q (items_side false; `items` are the ids of items), new items

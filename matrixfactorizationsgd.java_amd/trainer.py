@@ -124,6 +124,16 @@ def _pairs(a, b, what):
     return aa, bb
 
 
+def _exclusions(exclude):
+    """The `exclude` argument of the serving calls: (seen, u, i).  None: no pairs; (u, i): those pairs; the string "seen":
+    what the handle's seen-item index holds (the _unseen calls of the C-ABI), and then u and i are empty."""
+    if isinstance(exclude, str):
+        if exclude != "seen":
+            raise ValueError('exclude must be None, (u, i) or "seen"')
+        return (True,) + _pairs(None, None, "exclude")
+    return (False,) + _pairs(*((None, None) if exclude is None else exclude), "exclude")
+
+
 class MatrixFactorizationSGD:
     def __init__(self, users, items, k, lr, lam, seed, *, device=0, blocks=0, waves=0,
                  n_parts=0, host_threads=0, flags=0):
@@ -334,17 +344,20 @@ class MatrixFactorizationSGD:
                     epochs_run=ran.value, best_epoch=best.value)
 
     # -- online updates (include/mfsgd.h, "online updates") -------------------------
-    def partial_fit(self, u, i, r, *, errors=False, info=False):
+    def partial_fit(self, u, i, r, *, errors=False, info=False, seen=False):
         """Applies the ratings (u[j], i[j], r[j]) to the live model in the order given (mfsgd_apply_ratings): bit for bit
         the sequential per-rating SGD loop, at the current lr and lambda.  The stored ratings, their schedules and the
         held-out set are not touched, and none is needed.  errors=True returns float32[n], each rating's error just
         before its own update ("test, then train"); info=True returns dict(n, pieces, levels, max_width, launches);
-        both: (errors, info); neither: None."""
+        both: (errors, info); neither: None.  seen=True: the applied pairs are then marked in the seen-item index
+        (mark_seen), which the update by itself leaves alone."""
         uu, ii, rr = self._triples(u, i, r)
         err = np.empty(uu.size, np.float32) if errors else None
         out = _lib.OnlineInfo()
         self._check(self._lib.mfsgd_apply_ratings(self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32), _p(rr, C.c_float),
                                                   uu.size, None if err is None else _p(err, C.c_float), C.byref(out)))
+        if seen:
+            self.mark_seen(uu, ii)
         res = tuple(x for x, on in ((err, errors), (out.as_dict(), info)) if on)
         return None if not res else res[0] if len(res) == 1 else res
 
@@ -384,18 +397,24 @@ class MatrixFactorizationSGD:
     def recommend(self, users, topn, exclude=None, candidates=None):
         """(items, scores), each [len(users), topn]: best items per user, best first.  exclude = (u, i):
         pairs never returned (for instance the training ratings, so that only unrated items come back);
-        a row with fewer than topn eligible items is padded with item -1 and score NaN.
+        a row with fewer than topn eligible items is padded with item -1 and score NaN.  exclude = "seen": the pairs of
+        the seen-item index (set_seen / mark_seen), read on the device where they lie -- the same rows, without the list.
         candidates: the items a row may return at all (mfsgd_recommend_among) -- a 1-d integer array, one list for every
         row; a tuple (ptr, items), CSR over the rows of `users` (row b is the position in users, not the user); or a
         sequence of one 1-d array per row.  Lists may be unsorted, repeat items and be empty.  None: every item."""
         uu = _i32(np.atleast_1d(users))
-        eu, ei = (np.empty(0, np.int32),) * 2 if exclude is None else (_i32(exclude[0]), _i32(exclude[1]))
-        if eu.shape != ei.shape or eu.ndim != 1:
-            raise ValueError("exclude must be two 1-d arrays of the same length")
+        seen, eu, ei = _exclusions(exclude)
         cp, ci = (None, None) if candidates is None else _candidates(candidates, uu.size)
         items = np.empty((uu.size, int(topn)), np.int32)
         scores = np.empty((uu.size, int(topn)), np.float32)
-        if candidates is None:
+        if seen and candidates is None:
+            self._check(self._lib.mfsgd_recommend_unseen(self._handle(), _p(uu, C.c_int32), uu.size, int(topn),
+                                                         _p(items, C.c_int32), _p(scores, C.c_float)))
+        elif seen:
+            self._check(self._lib.mfsgd_recommend_unseen_among(self._handle(), _p(uu, C.c_int32), uu.size, int(topn),
+                                                               None if cp is None else _p(cp, C.c_int64), _p(ci, C.c_int32),
+                                                               ci.size, _p(items, C.c_int32), _p(scores, C.c_float)))
+        elif candidates is None:
             self._check(self._lib.mfsgd_recommend_excluding(self._handle(), _p(uu, C.c_int32), uu.size, int(topn),
                                                             _p(eu, C.c_int32), _p(ei, C.c_int32), eu.size,
                                                             _p(items, C.c_int32), _p(scores, C.c_float)))
@@ -405,6 +424,44 @@ class MatrixFactorizationSGD:
                                                         _p(eu, C.c_int32), _p(ei, C.c_int32), eu.size,
                                                         _p(items, C.c_int32), _p(scores, C.c_float)))
         return items, scores
+
+    # -- the seen-item index (include/mfsgd.h, "the seen-item index") ---------------
+    def set_seen(self, u, i):
+        """The seen-item index becomes the distinct pairs (u[x], i[x]) (mfsgd_set_seen): built once on the device and kept
+        there, so that exclude="seen" serves "items this user has not seen" without the list.  Empty arrays leave an
+        empty index (no GPU needed)."""
+        uu, ii = _pairs(np.atleast_1d(u), np.atleast_1d(i), "u and i")
+        self._check(self._lib.mfsgd_set_seen(self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32), uu.size))
+
+    def mark_seen(self, u, i):
+        """Adds the pairs to the seen-item index (mfsgd_mark_seen): a merge on the device, the index is not sorted again.
+        Without an index it is set_seen."""
+        uu, ii = _pairs(np.atleast_1d(u), np.atleast_1d(i), "u and i")
+        self._check(self._lib.mfsgd_mark_seen(self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32), uu.size))
+
+    def clear_seen(self):
+        """Drops the seen-item index and frees its device memory: the handle has none afterwards."""
+        self._check(self._lib.mfsgd_clear_seen(self._handle()))
+
+    def seen_size(self):
+        """Distinct pairs in the seen-item index; -1 when the handle has none."""
+        n = C.c_int64(-2)
+        self._check(self._lib.mfsgd_seen_size(self._handle(), C.byref(n)))
+        return n.value
+
+    def seen(self, users):
+        """(row_ptr int64[len(users) + 1], items int32[row_ptr[-1]]): the seen items of the requested users, ascending
+        within a user, CSR over `users` as given (mfsgd_get_seen: gathered on the device)."""
+        uu = _i32(np.atleast_1d(users))
+        if uu.ndim != 1:
+            raise ValueError("users must be a 1-d array")
+        ptr = np.zeros(uu.size + 1, np.int64)
+        self._check(self._lib.mfsgd_get_seen(self._handle(), _p(uu, C.c_int32), uu.size, _p(ptr, C.c_int64), None, 0))
+        items = np.empty(int(ptr[-1]), np.int32)
+        if items.size:
+            self._check(self._lib.mfsgd_get_seen(self._handle(), _p(uu, C.c_int32), uu.size, _p(ptr, C.c_int64),
+                                                 _p(items, C.c_int32), items.size))
+        return ptr, items
 
     def serve_seconds(self):
         """(lists, topn): host seconds the latest recommend call spent building its candidate and exclusion lists on the
@@ -520,10 +577,15 @@ class MatrixFactorizationSGD:
         """int32[n]: for each held-out pair (u[x], i[x]) the number of items that come before i[x] in u[x]'s
         recommendation order (0 = it would be recommended first) -- its index in recommend(u[x], items, exclude)'s row.
         exclude = (u, i): pairs that do not compete (for instance the training ratings); the held-out item itself is
-        ranked even when a pair excludes it.  Nothing is sorted: the device counts the items that beat each pair."""
+        ranked even when a pair excludes it.  exclude = "seen": the pairs of the seen-item index.  Nothing is sorted: the
+        device counts the items that beat each pair."""
         uu, ii = _pairs(np.atleast_1d(u), np.atleast_1d(i), "u and i")
-        eu, ei = _pairs(*((None, None) if exclude is None else exclude), "exclude")
+        seen, eu, ei = _exclusions(exclude)
         ranks = np.empty(uu.size, np.int32)
+        if seen:
+            self._check(self._lib.mfsgd_rank_items_unseen(self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32), uu.size,
+                                                          _p(ranks, C.c_int32)))
+            return ranks
         self._check(self._lib.mfsgd_rank_items(self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32), uu.size,
                                                _p(eu, C.c_int32), _p(ei, C.c_int32), eu.size, _p(ranks, C.c_int32)))
         return ranks
@@ -546,12 +608,16 @@ class MatrixFactorizationSGD:
         """rank_items(u, i, exclude) and ranking_metrics(u, ranks, topn) in one call: the metrics dict, which also
         carries "ranks" (int32[n])."""
         uu, ii = _pairs(np.atleast_1d(u), np.atleast_1d(i), "u and i")
-        eu, ei = _pairs(*((None, None) if exclude is None else exclude), "exclude")
+        seen, eu, ei = _exclusions(exclude)
         ranks = np.empty(uu.size, np.int32)
         out = _lib.RankingMetrics()
-        self._check(self._lib.mfsgd_evaluate_ranking(self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32), uu.size,
-                                                     int(topn), _p(eu, C.c_int32), _p(ei, C.c_int32), eu.size,
-                                                     C.byref(out), _p(ranks, C.c_int32)))
+        if seen:
+            self._check(self._lib.mfsgd_evaluate_ranking_unseen(self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32), uu.size,
+                                                                int(topn), C.byref(out), _p(ranks, C.c_int32)))
+        else:
+            self._check(self._lib.mfsgd_evaluate_ranking(self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32), uu.size,
+                                                         int(topn), _p(eu, C.c_int32), _p(ei, C.c_int32), eu.size,
+                                                         C.byref(out), _p(ranks, C.c_int32)))
         res = out.as_dict()
         res["ranks"] = ranks
         return res
