@@ -15,6 +15,13 @@ Growth (add_users, add_items, reserve), online updates (partial_fit) and the col
 their rows appended) are ops like any other: they change the factors behind the schedule's back, the counts, the device
 addresses of P and Q and whether the cached graphs are valid, and every later op is answered for the grown model.
 
+The seen-item index (include/mfsgd.h, "the seen-item index") is part of the model: `seen` is None (the handle has no
+index) or the sorted distinct keys u << 32 | i.  set_seen, mark_seen, clear_seen, seen_size, get_seen, the three serving
+calls with exclude="seen" and partial_fit(seen=True) are ops; after EVERY op seen_size() is the model's, and after every op
+the header says leaves the index as it is, or extends its per-user tables (SEEN_READ_AFTER), the whole index is read back
+and compared.  (That read synchronises the stream when the index holds pairs, as get_factors would: the sequences keep
+their stretches without an index, before the first set_seen and behind every clear_seen, for the missing-wait check.)
+
 The draw of an op depends on the seed and on the model's abstract state only (which of ratings, factors and held-out set
 exist), never on a number the library returned, so the same seed gives the same ops against the library, against a
 deliberately wrong model, and in a dry run without any library (dry=True), which is how the op weights are checked."""
@@ -28,6 +35,8 @@ import numpy as np
 
 from tests.test_fold_in_gpu import fold_in_ref
 from tests.test_fold_in_items_gpu import fold_in_items_ref
+from tests.test_rank_items_cpu import _assert_metrics as same_metrics
+from tests.test_rank_items_cpu import _metrics_ref as metrics_ref
 from tests.test_rank_items_gpu import _ranks_ref as ranks_ref
 from tests.test_recommend_among_gpu import _ref_a as among_ref_a
 from tests.test_recommend_among_gpu import _ref_b as among_ref_b
@@ -47,18 +56,31 @@ WEIGHTS = dict(set_ratings=11, init_factors=3, set_factors=3, save_load=2.5, ini
                fit_schedule=3, fit_bold_driver=3, fit_early_stopping=4, set_hyper=8, set_validation=3, clear_validation=1.6,
                validation_rmse=3, rmse_on=3, rmse=3, predict=3, recommend=2, recommend_excl=2, rank_items=2, similar_items=2,
                similar_users=2, fold_in=2, order=3.5, debug_schedule=3.5, schedule_info=2, hyper=2, debug_counters=2,
-               get_factors=2, add_users=4, add_items=4, reserve=4, partial_fit=4.5, fold_in_items=2, recommend_among=2)
+               get_factors=2, add_users=4, add_items=4, reserve=4, partial_fit=4.5, fold_in_items=2, recommend_among=2,
+               set_seen=3, mark_seen=4, clear_seen=2, seen_size=1.5, get_seen=2.5, recommend_unseen=2.5, rank_unseen=2,
+               evaluate_unseen=2)
 COMPUTE = ("fit", "train", "fit_schedule", "fit_bold_driver", "fit_early_stopping", "validation_rmse", "rmse_on", "rmse",
            "predict", "recommend", "recommend_excl", "rank_items", "similar_items", "similar_users", "fold_in",
-           "partial_fit", "fold_in_items", "recommend_among")
+           "partial_fit", "fold_in_items", "recommend_among", "recommend_unseen", "rank_unseen", "evaluate_unseen")
+# ... of which the host profile draws these as often as the gpu profile: what they answer without a device is a rule too
+# (an empty batch of online updates; "no seen set", which precedes the factor and device checks)
+HOST_TOO = ("partial_fit", "recommend_unseen", "rank_unseen", "evaluate_unseen")
+# the ops after which the whole index is read back: the header's "leave the index as it is" list, and the growth calls
+SEEN_READ_AFTER = ("add_users", "add_items", "reserve", "set_ratings", "set_factors", "save_load", "init_factors",
+                   "init_p_offset", "fit", "train", "fit_schedule", "fit_bold_driver", "fit_early_stopping", "fold_in",
+                   "fold_in_items", "partial_fit")
 # the error codes the model can answer with when there is a device, per kind (init_factors, set_factors, init_p_offset,
-# set_hyper, set_validation, hyper, debug_counters and reserve always succeed)
+# set_hyper, set_validation, hyper, debug_counters, reserve, clear_seen and seen_size always succeed)
 POSSIBLE_ERRORS = {kind: (STATE,) for kind in
                    ("fit", "train", "fit_schedule", "fit_bold_driver", "fit_early_stopping", "validation_rmse",
                     "rmse_on", "rmse", "predict", "recommend", "recommend_excl", "rank_items", "similar_items",
                     "similar_users", "fold_in", "order", "debug_schedule", "schedule_info", "get_factors",
                     "add_users", "add_items", "partial_fit", "fold_in_items", "recommend_among")}
 POSSIBLE_ERRORS["set_ratings"] = (INVALID,)
+for _kind in ("set_seen", "mark_seen"):
+    POSSIBLE_ERRORS[_kind] = (INVALID,)
+for _kind in ("get_seen", "recommend_unseen", "rank_unseen", "evaluate_unseen"):
+    POSSIBLE_ERRORS[_kind] = (STATE,)
 POSSIBLE_ERRORS["save_load"] = (STATE, INVALID)  # (INVALID: the file was saved before an append and no longer loads)
 QUIET_NAN = 0x7FC00000
 HOT = 9  # the row of set A that every row of the other side rates
@@ -224,7 +246,9 @@ class Runner:
     V (a held-out set that is not empty), initialised (the Python wrapper's flag), builds, the live counts U and I (U0 and
     I0: what the handle was created with), res (the largest reserve per side), built_at (the counts at the latest schedule
     build), where ("none", "host", "device": csrc/handle.cpp's Where), graphs (cached training graphs), pending (what
-    happened to the factors since the latest epoch).  Numbers (not in a dry run): P, Q, lr, lam, ratings, val."""
+    happened to the factors since the latest epoch), seen (None, or the index's sorted distinct keys u << 32 | i: drawn from
+    the seed and the counts alone, so a dry run has them too), seen_moved (what happened to the index's per-user tables
+    since its latest full read).  Numbers (not in a dry run): P, Q, lr, lam, ratings, val."""
 
     def __init__(self, mf, oracle, cfg, *, device, dry, wrong, tmpdir):
         self.mf, self.oracle, self.cfg, self.device, self.dry, self.wrong, self.tmpdir = mf, oracle, cfg, device, dry, wrong, tmpdir
@@ -232,6 +256,7 @@ class Runner:
         self.U0, self.I0, self.res, self.built_at = self.U, self.I, [0, 0], (self.U, self.I)
         self.where, self.graphs, self.pending, self.appended_since_build = "none", 0, set(), False
         self.hyper_after_growth, self.no_upload = False, False
+        self.seen, self.seen_moved, self.last_msg = None, set(), ""
         self.swap = bool(cfg.get("swap_roles"))
         self.sets = rating_sets(self.U, self.I, self.swap)
         self.group_lanes = 1
@@ -255,7 +280,7 @@ class Runner:
         w = dict(WEIGHTS)
         if self.cfg.get("profile", "gpu") == "host":
             for kind in COMPUTE:
-                if kind != "partial_fit":  # (an empty batch needs no device: the host profile draws many of them)
+                if kind not in HOST_TOO:
                     w[kind] *= 0.2
         if self.F == "full" and not self.grown():
             w["add_users"] *= 2
@@ -289,6 +314,9 @@ class Runner:
         code = getattr(self, "op_" + kind)(np.random.default_rng(seed))
         if code == OK and kind in COMPUTE and not self.no_upload:
             self.uploaded()
+        self.check_seen_size()
+        if kind in SEEN_READ_AFTER:
+            self.check_seen_lists()
         self.log[-1] += f" -> {NAMES[code]}"
         self.counts[(kind, NAMES[code])] += 1
 
@@ -305,6 +333,7 @@ class Runner:
         except self.mf.MfsgdError as e:
             value, code, msg = None, e.code, str(e)
         assert code == want, f"returned {NAMES.get(code, code)} {msg!r}, the model expects {NAMES[want]}"
+        self.last_msg = msg
         return code, value
 
     def code_train(self):
@@ -538,6 +567,8 @@ class Runner:
         code, _ = self.call(OK, lambda: self.m.set_factors(P, Q))
         self.F, self.initialised, self.P, self.Q = "full", True, P, Q
         self.seeded_or_replaced(False)
+        if self.wrong == "set_factors_clears_the_index":
+            self.seen = None
         self.check_counts()
         return code
 
@@ -981,6 +1012,202 @@ class Runner:
             same_among(got, among_ref_b(predict, users, lists, topn, eu, ei), "against sorted predictions")
         return code
 
+    # .. the seen-item index ...........................................................................................
+    def seen_pairs(self):
+        """(u, i) int32 of the model's index."""
+        keys = np.empty(0, np.int64) if self.seen is None else self.seen
+        return (keys >> 32).astype(np.int32), (keys & 0xFFFFFFFF).astype(np.int32)
+
+    def seen_merge(self, u, i):
+        keys = np.unique((np.asarray(u, np.int64) << 32) | np.asarray(i, np.int64))
+        self.seen = keys if self.seen is None else np.union1d(self.seen, keys)
+
+    def seen_lists(self, users):
+        """(row_ptr int64[len(users) + 1], items int32): what seen(users) returns."""
+        users = np.asarray(users, np.int64)
+        lo, hi = np.searchsorted(self.seen, users << 32), np.searchsorted(self.seen, (users + 1) << 32)
+        ptr = np.concatenate([[0], np.cumsum(hi - lo)]).astype(np.int64)
+        items = [self.seen[a:b] & 0xFFFFFFFF for a, b in zip(lo, hi)]
+        return ptr, (np.concatenate(items) if items else np.empty(0, np.int64)).astype(np.int32)
+
+    def check_seen_size(self):
+        """After every op: seen_size() is the model's (-1: no index).  Host only."""
+        if not self.dry:
+            got, want = self.m.seen_size(), -1 if self.seen is None else int(self.seen.size)
+            assert got == want, f"seen_size() is {got}, the model's index holds {want}"
+
+    def check_seen_lists(self):
+        """The whole index, read back: seen(arange(U)) equals the model.  (An empty index is read on the host.)"""
+        if self.seen is None:
+            self.seen_moved.clear()
+            return
+        if not self.dry:
+            got = self.m.seen(np.arange(self.U, dtype=np.int32))
+            want = self.seen_lists(np.arange(self.U))
+            assert got[0].dtype == np.int64 and got[1].dtype == np.int32
+            assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), \
+                f"seen(every user) differs from the model: {got[1].size} items, the model holds {want[1].size}"
+        for what in sorted(self.seen_moved):
+            self.facts["seen_read_after_" + what] += 1
+        self.seen_moved.clear()
+
+    def seen_update(self, g, merge):
+        """set_seen (merge False) / mark_seen: a valid batch, an empty one, one wholly inside the index, one with a pair
+        out of range at a drawn position.  csrc/seen_index.cpp: the pairs are checked first (MFSGD_ERR_INVALID_ARG, "pair
+        N out of range"); n == 0 is answered on the host; n > 0 needs a device; a refused call leaves the index alone."""
+        host = self.cfg.get("profile", "gpu") == "host"
+        variants = ("some", "inside", "empty", "empty", "empty", "bad") if host else ("some", "some", "some", "empty", "inside", "bad")
+        v = variants[int(g.integers(len(variants)))]
+        n = int(g.integers(1, 400))
+        u, i, _ = self.pairs(g, n)
+        pick, j, which = g.integers(0, 1 << 30, n), int(g.integers(n)), int(g.integers(2))
+        if v == "inside":
+            if self.seen is not None and self.seen.size:
+                keys = self.seen[pick % self.seen.size]
+                u, i = (keys >> 32).astype(np.int32), (keys & 0xFFFFFFFF).astype(np.int32)
+            else:
+                v = "some"
+        if v == "empty":
+            u, i = u[:0], i[:0]
+        if v == "bad":
+            if which:
+                u[j] = self.U
+            else:
+                i[j] = self.I
+        name = "mark_seen" if merge else "set_seen"
+        self.note(f"[{v}: n={u.size}" + (f", pair {j} out of range]" if v == "bad" else "]"))
+        want = INVALID if v == "bad" else OK if self.device or u.size == 0 else NO_DEVICE
+        fn = (lambda: self.m.mark_seen(u, i)) if merge else (lambda: self.m.set_seen(u, i))
+        before = None if self.seen is None else self.seen.size
+        code, _ = self.call(want, fn)
+        if code == INVALID and not self.dry:
+            assert f"{name}: pair {j} out of range" in self.last_msg, self.last_msg
+        if code == OK:
+            if merge:
+                if u.size and (u >= self.U0).any():
+                    self.facts["mark_seen_of_an_appended_user"] += 1
+                if u.size and (i >= self.I0).any():
+                    self.facts["mark_seen_of_an_appended_item"] += 1
+                self.seen_merge(u, i)  # (of nothing, on a handle without an index: an empty index)
+                if v == "inside":
+                    assert self.seen.size == before
+                    self.facts["mark_seen_wholly_inside_the_index"] += 1
+            else:
+                if before:
+                    self.facts["set_seen_replacing_a_non_empty_index"] += 1
+                self.seen = None
+                self.seen_merge(u, i)
+            if u.size == 0:
+                self.facts[name + "_of_no_pairs"] += 1
+        else:  # refused: the index is as it was, all of it
+            if merge and before:
+                self.facts["refused_mark_seen_then_read"] += 1
+            self.check_seen_lists()
+        return code
+
+    def op_set_seen(self, g):
+        return self.seen_update(g, False)
+
+    def op_mark_seen(self, g):
+        return self.seen_update(g, True)
+
+    def op_clear_seen(self, g):
+        code, _ = self.call(OK, lambda: self.m.clear_seen())
+        self.seen = None
+        self.seen_moved.clear()
+        return code
+
+    def op_seen_size(self, g):
+        code, got = self.call(OK, lambda: self.m.seen_size())
+        if not self.dry:
+            assert got == (-1 if self.seen is None else self.seen.size), (got, self.seen)
+        return code
+
+    def op_get_seen(self, g):
+        """seen(users) for drawn users, with repeats, or for none.  A handle without an index: MFSGD_ERR_STATE; an empty
+        index and zero users are answered on the host."""
+        n = int(g.integers(0, 9))
+        users = self.appended_rows(g, 0, n)
+        if n > 2:
+            users[2] = users[0]
+        self.note(f"[{n} users]")
+        if self.seen is None:
+            want = STATE
+        else:
+            want = OK if self.device or n == 0 or self.seen.size == 0 else NO_DEVICE
+        code, got = self.call(want, lambda: self.m.seen(users))
+        if code == STATE and not self.dry:
+            assert "get_seen: no seen set" in self.last_msg, self.last_msg
+        if code == OK:
+            if self.seen.size == 0 or n == 0:
+                self.facts["get_seen_answered_on_the_host"] += 1
+            if not self.dry:
+                want_ptr, want_items = self.seen_lists(users)
+                assert np.array_equal(got[0], want_ptr) and np.array_equal(got[1], want_items), (got, want_ptr, want_items)
+        return code
+
+    def code_unseen(self, none_first):
+        """The serving calls against the index: "no seen set" comes before every factor and device check."""
+        if self.seen is None:
+            if self.F != "full":
+                self.facts["unseen_refused_for_no_seen_set_without_factors"] += 1
+            return STATE
+        return self.code_pq(none_first)
+
+    def unseen_outcome(self, code, name):
+        if code == STATE and self.seen is None and not self.dry:
+            assert f"{name}: no seen set" in self.last_msg, self.last_msg
+        if code == OK and self.seen.size == 0:
+            self.facts["unseen_call_on_an_empty_index"] += 1  # (it excludes nothing)
+
+    def op_recommend_unseen(self, g):
+        """recommend(users, n, exclude="seen"), over the whole catalogue or among drawn candidates (one shared list or one
+        per row; empty, short and repeating ones), against the references of recommend_excl / recommend_among given the
+        model's pairs."""
+        users = self.appended_rows(g, 0, 4)
+        users[3] = users[0]
+        among, shared, topn = bool(g.integers(2)), bool(g.integers(2)), int(g.integers(1, 8))
+        lists = [self.appended_rows(g, 1, int(n)) for n in g.integers(0, 30, 4)]
+        lists[1] = lists[1][:2]
+        lists[2] = lists[2][:0]
+        lists[0] = np.concatenate([lists[0], lists[0][:3]])
+        if shared:
+            lists = [lists[int(g.integers(4))]] * 4
+        self.note(f"[among={among}, shared={shared}, topn {topn}, lists of {[int(c.size) for c in lists]}]")
+        cand = None
+        if among:
+            cand = lists[0] if shared else (np.concatenate([[0], np.cumsum([c.size for c in lists])]).astype(np.int64),
+                                            np.concatenate(lists))
+        code, got = self.call(self.code_unseen(False), lambda: self.m.recommend(users, topn, exclude="seen", candidates=cand))
+        self.unseen_outcome(code, "recommend_unseen_among" if among else "recommend_unseen")
+        if code == OK and not self.dry:
+            eu, ei = self.seen_pairs()
+            if among:
+                predict = lambda u, i: self.oracle.predict(self.P, self.Q, u, i)
+                same_among(got, among_ref_b(predict, users, lists, topn, eu, ei), "against sorted predictions")
+            else:
+                same_topn(got, recommend_ref(self.oracle, self.P, self.Q, users, topn, eu, ei))
+        return code
+
+    def op_rank_unseen(self, g):
+        u, i, _ = self.pairs(g, 12)
+        code, got = self.call(self.code_unseen(True), lambda: self.m.rank_items(u, i, exclude="seen"))
+        self.unseen_outcome(code, "rank_items_unseen")
+        if code == OK and not self.dry:
+            assert np.array_equal(got, ranks_ref(self.oracle, self.P, self.Q, u, i, *self.seen_pairs())), got
+        return code
+
+    def op_evaluate_unseen(self, g):
+        u, i, _ = self.pairs(g, 12)
+        topn = int(g.integers(1, 20))
+        code, got = self.call(self.code_unseen(True), lambda: self.m.evaluate_ranking(u, i, topn, exclude="seen"))
+        self.unseen_outcome(code, "evaluate_ranking_unseen")
+        if code == OK and not self.dry:
+            ranks = ranks_ref(self.oracle, self.P, self.Q, u, i, *self.seen_pairs())
+            assert np.array_equal(got["ranks"], ranks), got
+            same_metrics(got, metrics_ref(u, ranks, topn))
+        return code
+
     # .. growth ........................................................................................................
     def append(self, side, rows, n, seed):
         """add_users (side 0) / add_items (side 1) of `rows`, or of n seeded rows, against the handle and the model; returns
@@ -1006,6 +1233,16 @@ class Runner:
                 self.appended_since_build = True
                 if self.packed() and not self.sched_computed:
                     self.facts["append_on_a_device_packed_schedule_before_compute"] += 1
+            if side == 0 and self.seen is not None and self.seen.size:
+                # the new users have empty lists; beyond the capacity the per-user tables are copied into larger ones
+                if old + n_new <= self.capacity()[0]:
+                    self.seen_moved.add("an_append_in_place")
+                else:
+                    self.seen_moved.add("a_reallocating_append_on_" + ("the_device" if self.where == "device" else "host_staging"))
+                if self.wrong == "append_users_gives_new_users_the_last_list":
+                    last = self.seen[(self.seen >> 32) == old - 1] & 0xFFFFFFFF
+                    new = (np.arange(old, old + n_new, dtype=np.int64)[:, None] << 32) | last[None, :]
+                    self.seen = np.union1d(self.seen, new.ravel())
             if side:
                 self.I += n_new
             else:
@@ -1066,6 +1303,8 @@ class Runner:
         code, _ = self.call(OK, lambda: self.m.reserve(users=want[0], items=want[1]))
         for side in sides:
             if want[side] > self.capacity()[side]:
+                if side == 0 and self.seen is not None and self.seen.size:
+                    self.seen_moved.add("reserve")  # (the index's per-user tables are as long as the capacity)
                 if self.where == "device" and (side == 0 or self.F == "full"):  # (that side has a buffer: it moves)
                     self.graphs = 0
                     self.facts["reserve_that_reallocates"] += 1
@@ -1102,17 +1341,24 @@ class Runner:
             r = np.concatenate([np.full(per_pass + 9, 3.5, np.float32), r])
             n = u.size
         check_order = bool(g.integers(2))
+        mark = int(g.integers(3)) == 0  # partial_fit(seen=True): the applied pairs are marked behind the update
         n_levels, widths = online_levels(u, i)
         width = max(widths, default=0)
         wide = width > per_pass  # (a random batch can have such a level without the rows in front)
         narrow = n > 0 and min(widths) <= per_pass
-        self.note(f"[n={n}, hot={hot}, appended rows={on_new}, {n_levels} levels, the widest of {width}]")
+        self.note(f"[n={n}, hot={hot}, appended rows={on_new}, {n_levels} levels, the widest of {width}, seen={mark}]")
         if self.F != "full":
             want = STATE
         else:
             want = OK if self.device or n == 0 else NO_DEVICE
-        code, got = self.call(want, lambda: self.m.partial_fit(u, i, r, errors=True, info=True))
+        code, got = self.call(want, lambda: self.m.partial_fit(u, i, r, errors=True, info=True, seen=mark))
         self.no_upload = n == 0
+        if mark:
+            # trainer.py: mark_seen runs behind mfsgd_apply_ratings, so a refused update (it raises) marks nothing, and
+            # an applied one marks exactly its pairs -- no pairs, on a handle without an index, leave an empty index
+            self.facts["partial_fit_seen_" + ("applied" if code == OK else "refused")] += 1
+            if code == OK:
+                self.seen_merge(u, i)
         if code == OK and n == 0:
             self.facts["partial_fit_of_no_ratings"] += 1
         if code == OK and n > 0:
@@ -1191,8 +1437,8 @@ def run_sequence(mf, oracle, seed, n_ops, config, *, device=True, dry=False, wro
     dict(counts {(kind, outcome): n}, facts {name: n}, n_ops, errors, seconds, log).
     device=False: no GPU is expected, and every call that needs one is MFSGD_ERR_NO_DEVICE.  dry=True: no library at all,
     the ops and their outcomes as the model alone gives them.  wrong: a deliberately wrong rule of the model
-    ("hyper_before_ratings", "failed_set_ratings_keeps", "reseed_forgets_growth", "append_forgets_the_ratings"), for the
-    driver's self-test."""
+    ("hyper_before_ratings", "failed_set_ratings_keeps", "reseed_forgets_growth", "append_forgets_the_ratings",
+    "set_factors_clears_the_index", "append_users_gives_new_users_the_last_list"), for the driver's self-test."""
     cfg = dict(blocks=0, waves=0, flags=0, lr=0.02, lam=0.03, seed=7, profile="gpu")
     cfg.update(config)
     rng = np.random.default_rng(seed)
@@ -1226,6 +1472,12 @@ GROWTH_FACTS = ("fit_after_append_in_place", "fit_after_reallocating_append", "f
                 "early_stopping_restored_after_growth", "validation_pair_on_an_appended_row", "stale_factor_file_refused",
                 "append_on_a_device_packed_schedule_before_compute", "trained_on_a_swapped_schedule_after_growth")
 NUMERIC_FACTS = ("early_stopping_restored_after_growth",)
+SEEN_FACTS = ("seen_read_after_an_append_in_place", "seen_read_after_a_reallocating_append_on_the_device",
+              "seen_read_after_a_reallocating_append_on_host_staging", "seen_read_after_reserve",
+              "mark_seen_of_an_appended_user", "mark_seen_of_an_appended_item",
+              "unseen_refused_for_no_seen_set_without_factors", "unseen_call_on_an_empty_index",
+              "set_seen_replacing_a_non_empty_index", "refused_mark_seen_then_read", "mark_seen_wholly_inside_the_index",
+              "partial_fit_seen_applied", "partial_fit_seen_refused")
 
 
 def check_coverage(results):
@@ -1244,7 +1496,7 @@ def check_coverage(results):
     for fact in ("set_ratings_reuse", "set_ratings_rebuild_of_equal_length", "set_hyper_on_a_device_packed_schedule_before_compute",
                  "set_hyper_on_a_device_packed_schedule_after_compute", "set_hyper_on_a_host_packed_schedule",
                  "set_hyper_before_any_ratings", "set_hyper_before_any_compute", "set_hyper_same_bits",
-                 "trained_on_a_lone_tile_schedule", "schedule_getter_before_compute", "schedule_getter_after_compute") + GROWTH_FACTS:
+                 "trained_on_a_lone_tile_schedule", "schedule_getter_before_compute", "schedule_getter_after_compute") + GROWTH_FACTS + SEEN_FACTS:
         if fact in NUMERIC_FACTS and any(res.get("dry") for res in results):
             continue  # (whether an early stop restores depends on the numbers: a dry run has none)
         assert facts[fact] >= 1, f"{fact} never happened: {dict(facts)}"
@@ -1263,7 +1515,7 @@ GEOMETRIES = {
 }
 GPU_FLAGS = ("default", "FLAG_ROUND_LAUNCH", "FLAG_NO_GRAPH", "FLAG_DEVICE_INGEST", "FLAG_HOST_INGEST")
 GPU_SEEDS = (0, 1)
-GPU_OPS = 64
+GPU_OPS = 75  # (64 before the ops of the seen-item index: as many draws of every other kind as then, 64 x 132.7 / 113.2)
 
 
 def flag_value(name):

@@ -1,9 +1,11 @@
-"""Seeded sequences of about sixty calls on one live handle, each call compared with the model of tests/handle_model.py
+"""Seeded sequences of about seventy calls on one live handle, each call compared with the model of tests/handle_model.py
 (the oracle and numpy) before the next is made: training in every flavour, lr and lambda changed on schedules the device
 packed and on schedules the host packed, before and after the first compute call, rating sets that are kept, rebuilt in
 recycled allocations and dropped by a failed call, factors seeded, set, loaded and seeded without Q, users and items
 appended in place and by reallocation, room reserved, online updates, fold-in of users and of items with the rows
-appended, top-N among candidates, the held-out set, serving and the getters -- for every launch path (flags) and four
+appended, top-N among candidates, the held-out set, the seen-item index (set, merged, cleared, read back after every
+call that must leave it alone or move its tables, served from with exclude="seen"), serving and the getters -- for every
+launch path (flags) and four
 geometries (the C++ step; solo runs with a lone-tile mailbox; the padded L = 32; exchanged roles, where the hot row is a
 user's and the kernels receive (Q, P)).  get_factors is drawn like any other op and never added after one: it
 synchronises, and would hide a missing wait (the one exception reads back an appended NaN).  One scripted life per launch
@@ -56,7 +58,10 @@ def test_a_grown_model_through_a_whole_life(mf, oracle, flag, geometry):
     and the new user; fit over the kept schedule and graph; items appended beyond the capacity (Q moves); other values
     re-baked into the kept schedule; fit; a rating set that names the appended rows, built at the grown sizes; a held-out
     set with pairs on appended rows; early stopping that restores a snapshot of the grown model.  The factors are the
-    oracle's bit for bit over the exported orders, and the cached graphs and the schedule builds are counted at every step."""
+    oracle's bit for bit over the exported orders, and the cached graphs and the schedule builds are counted at every step.
+    The seen-item index goes along: set from the ratings before the growth (no graph goes), the appended users and items
+    marked after it, read back whole at the end, and the three serving calls with exclude="seen" answered for the grown,
+    restored model by the oracle."""
     cfg = dict(dict(blocks=0, waves=0, lr=0.02, lam=0.03, seed=7), **hm.gpu_config(flag, geometry))
     _geometry_is_what_it_is_for(mf, cfg)
     U, I, k, swap = cfg["U"], cfg["I"], cfg["k"], bool(cfg.get("swap_roles"))
@@ -82,6 +87,13 @@ def test_a_grown_model_through_a_whole_life(mf, oracle, flag, geometry):
     vu[::5], vi[2::5] = rng.integers(U, U1, 60), rng.integers(I, I1, 60)
     vr = (rng.integers(1, 11, 300) * 0.5).astype(np.float32)
     lrs = np.array(LIFE_LR, np.float32)
+    # the index: the ratings before the growth; after it pairs of appended users and of appended items, one pair twice
+    mu = np.concatenate([rng.integers(U, U1, 40), rng.integers(0, U1, 40), [U, U]]).astype(np.int32)
+    mi = np.concatenate([rng.integers(0, I1, 40), rng.integers(I, I1, 40), [I1 - 1, I1 - 1]]).astype(np.int32)
+    su, si = np.concatenate([A[0], mu]), np.concatenate([A[1], mi])
+    users = np.array([0, U, U1 - 1, hm.HOT, U], np.int32)       # old and appended users, one twice
+    hu = np.concatenate([mu[:6], A[0][:6], [U1 - 1, 3]]).astype(np.int32)  # held-out pairs, some of them seen
+    hi = np.concatenate([mi[:6], A[1][:6], [I1 - 1, I]]).astype(np.int32)
     t0 = time.perf_counter()
     with mf.MatrixFactorizationSGD(U, I, k, cfg["lr"], cfg["lam"], 7, blocks=cfg["blocks"], waves=cfg["waves"], flags=cfg["flags"]) as m:
         def counters(graphs, builds, what):
@@ -92,6 +104,8 @@ def test_a_grown_model_through_a_whole_life(mf, oracle, flag, geometry):
         m.init_factors()
         m.fit(2, rmse=False)
         counters(one, 1, "fit")
+        m.set_seen(A[0], A[1])                        # the index and the model do not touch each other
+        counters(one, 1, "set_seen")
         m.reserve(users=U + 10)                       # P moves: the graph holds its old address
         counters(0, 1, "reserve")
         assert m.capacity() == (U + 10, I)
@@ -107,6 +121,8 @@ def test_a_grown_model_through_a_whole_life(mf, oracle, flag, geometry):
         assert m.add_items(new_q) == I                # beyond the capacity: Q moves
         counters(0, 1, "add_items")
         assert m.capacity() == (U + 10, I1) and (m.users, m.items) == (U1, I1)
+        m.mark_seen(mu, mi)                           # the appended rows are valid, and their lists start empty
+        counters(0, 1, "mark_seen")
         m.set_hyper(0.011, 0.02)                      # re-baked into the kept schedule
         counters(0, 1, "set_hyper")
         rm8 = m.fit(1)
@@ -118,6 +134,11 @@ def test_a_grown_model_through_a_whole_life(mf, oracle, flag, geometry):
         counters(one, 2, "early stopping")
         got = m.get_factors()
         order_kept = m.order()[0]
+        unseen = (m.recommend(users, 6, exclude="seen"), m.rank_items(hu, hi, exclude="seen"),
+                  m.evaluate_ranking(hu, hi, 5, exclude="seen"))
+        counters(one, 2, "the calls against the index")
+        index = m.seen(np.arange(U1, dtype=np.int32))
+        assert m.seen_size() == index[1].size
     seconds = time.perf_counter() - t0
     P, Q = oracle.init_factors(U, I, k, 7)
     lr, lam = cfg["lr"], cfg["lam"]
@@ -146,6 +167,16 @@ def test_a_grown_model_through_a_whole_life(mf, oracle, flag, geometry):
     hm._same_bits(got[0], best_p, "P")
     hm._same_bits(got[1], best_q, "Q")
     assert not np.array_equal(best_p[U:], moved[0]) and not np.array_equal(best_q[I:], moved[1])  # set C trained the new rows
+    # the index kept every list through reserve, both appends, two rating sets and the training, and serves the final model
+    keys = np.unique((su.astype(np.int64) << 32) | si)
+    assert np.array_equal(index[0], np.searchsorted(keys >> 32, np.arange(U1 + 1))), "the index's offsets"
+    assert np.array_equal(index[1], (keys & 0xFFFFFFFF).astype(np.int32)), "the index's items"
+    assert (np.diff(index[0])[U:] > 0).any()  # (appended users have lists of their own by now)
+    hm.same_topn(unseen[0], hm.recommend_ref(oracle, best_p, best_q, users, 6, su, si))
+    ranks = hm.ranks_ref(oracle, best_p, best_q, hu, hi, su, si)
+    assert np.array_equal(unseen[1], ranks) and np.array_equal(unseen[2]["ranks"], ranks), (unseen[1], ranks)
+    assert not np.array_equal(ranks, hm.ranks_ref(oracle, best_p, best_q, hu, hi, su[:0], si[:0]))  # (the index matters)
+    hm.same_metrics(unseen[2], hm.metrics_ref(hu, ranks, 5))
 
 
 def test_fallback_to_round_launches_in_the_middle_of_a_life(mf, oracle):
@@ -193,8 +224,8 @@ def test_the_sequences_together_covered_what_they_are_for():
     """Over all cases: every op kind succeeded at least ten times, every error the model can answer with occurred, rating
     sets were kept and rebuilt at equal length, lr and lambda changed on a device-packed schedule before and after its
     first compute call and on a host-packed one, a lone-tile schedule was trained, the schedule getters ran before and
-    after the first compute call of a schedule, every fact of growth and online updates (handle_model.GROWTH_FACTS)
-    happened, and at most 35 % of all ops ended in an error code."""
+    after the first compute call of a schedule, every fact of growth and online updates (handle_model.GROWTH_FACTS) and
+    of the seen-item index (handle_model.SEEN_FACTS) happened, and at most 35 % of all ops ended in an error code."""
     want = len(hm.GPU_FLAGS) * len(hm.GEOMETRIES) * len(hm.GPU_SEEDS)
     assert len(_results) == want, f"{len(_results)} of {want} cases ran before this one: run the whole module"
     total = hm.check_coverage(_results.values())

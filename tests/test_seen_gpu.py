@@ -1,16 +1,25 @@
 """The seen-item index on the device: set_seen / mark_seen / seen against numpy's unique of the same pairs, and the serving
 calls with exclude="seen" against the same calls given the index's pairs as a list, which build their lists per call and
-do not read the index.  Items and ranks compare exactly, scores bit for bit, padding (-1, NaN) by position."""
+do not read the index.  Items and ranks compare exactly, scores bit for bit, padding (-1, NaN) by position.
+Tests 9 to 11 do not compare the library with itself: batches of request rows with exclusions (a pair list, the index) and
+with per-row candidates against the oracle's scores and numpy (tests/test_serving_limits_gpu.py has the other staging
+limits), and lists read back past the strides of the gather kernel."""
 import gc
 
 import numpy as np
 import pytest
+
+from tests import edge_inputs as E
 
 pytestmark = pytest.mark.gpu
 
 LR, LAM = 0.01, 0.05
 TILE = 14336      # csrc/recommend.hip: kTopnTile, positions per tile of the fused kernel
 CHUNK = 1 << 22   # csrc/handle.hpp: kExclChunk, pairs per upload of set_seen / mark_seen
+LAUNCH_ROWS = 65535     # csrc/serve.cpp, topn_batches: request rows per launch (b1 - b0 < 65535)
+SORT_CELLS = 64 << 20   # csrc/serve.cpp: kSortCells, scores one batch of the sort path materialises
+GATHER_ROWS = 4096      # csrc/seen.hip, seen_gather: grid.x, the rows a pass of the gather takes
+GATHER_SPAN = 64 * 256  # ... grid.y parts of kSeenThreads positions: what a pass takes of one list
 INVALID_ARG = -1
 
 
@@ -335,3 +344,157 @@ def test_the_index_holds_what_the_bound_says_and_the_calls_keep_nothing(mf):
     finally:
         m.close()
     assert live() == before
+
+
+# ---- 9. batches of request rows: the fused path -----------------------------------------------------------------------------
+def test_fused_path_batches_with_exclusions_and_candidates(mf, oracle):
+    """The shape of test_fused_path_more_users_than_one_launch (tests/test_serving_edges_gpu.py): 70 000 request rows are a
+    launch of 65 535 and one of 4 465.  Across the cut `ex` stays as it is while the users restart at the batch, for a
+    pair list and for the index's identity slot table, and am.off += done re-bases the per-row candidate lists."""
+    U, I, k, topn = 70000, 5, 4, 5
+    assert -(-U // LAUNCH_ROWS) == 2
+    rng = np.random.default_rng(70001)
+    P = rng.standard_normal((U, k)).astype(np.float32)
+    Q = rng.standard_normal((I, k)).astype(np.float32)
+    Q[3] = Q[1]  # a tie in every row
+    users = rng.permutation(U).astype(np.int32)  # (request row b is user users[b]: the lists go by user, not by row)
+    edge = np.array([65534, 65535, 65536, 69999])
+    half = np.unique(np.concatenate([rng.choice(U, U // 2, replace=False), edge, users[edge]])).astype(np.int32)
+    eu, ei = np.repeat(half, 2), rng.integers(0, I, 2 * half.size).astype(np.int32)
+    perm = rng.permutation(eu.size)
+    eu, ei = np.ascontiguousarray(eu[perm]), np.ascontiguousarray(ei[perm])
+    cand = np.argsort(rng.random((U, I)), axis=1)[:, :3].astype(np.int32)  # three of the five items per request row
+    ptr = 3 * np.arange(U + 1, dtype=np.int64)
+    sc = oracle.predict(P, Q, np.repeat(users, I), np.tile(np.arange(I, dtype=np.int32), U)).reshape(U, I)
+    item = np.broadcast_to(np.arange(I, dtype=np.int32), (U, I))
+    row_of_user = np.empty(U, np.int64)
+    row_of_user[users] = np.arange(U)
+    X = np.zeros((U, I), bool)
+    X[row_of_user[eu], ei] = True
+    C = np.zeros((U, I), bool)
+    np.put_along_axis(C, cand.astype(np.int64), True, axis=1)
+
+    def ref(out):
+        """per row: the items that are not `out`, the larger score first, ties by the smaller item; -1 / NaN behind them"""
+        order = np.lexsort((item, -sc.astype(np.float64), out), axis=1)
+        pad = np.take_along_axis(out, order, axis=1)
+        return (np.where(pad, -1, order).astype(np.int32), np.where(pad, np.float32(np.nan), np.take_along_axis(sc, order, axis=1)))
+    want_x, want_c, want_cx = ref(X), ref(~C), ref(~C | X)
+    plain = ref(np.zeros((U, I), bool))
+    some = np.array([0, 65534, 65535, 65536, 69999])
+    E.assert_recommend((want_x[0][some], want_x[1][some]), E.recommend_ref(oracle, P, Q, users[some], topn, eu, ei))
+    second = np.arange(LAUNCH_ROWS, U)
+    for want in (want_x, want_c, want_cx):  # the second launch's lists change its rows
+        assert (want[0][second] != plain[0][second]).any(axis=1).sum() > second.size // 3
+    assert (want_cx[0][second] != want_c[0][second]).any() and X[edge].any(axis=1).all()
+    with _model(mf, P, Q) as m:
+        _same(m.recommend(users, topn, exclude=(eu, ei)), want_x, "a pair list")
+        _same(m.recommend(users, topn, candidates=(ptr, cand.ravel())), want_c, "per-row candidates")
+        m.set_seen(eu, ei)
+        got = m.recommend(users, topn, exclude="seen")
+        _same(got, want_x, "the index")
+        for b in edge:
+            assert not np.isin(ei[eu == users[b]], got[0][b]).any()
+        _same(m.recommend(users, topn, exclude="seen", candidates=(ptr, cand.ravel())), want_cx, "candidates and the index")
+
+
+# ---- 10. batches of request rows: the sort path -----------------------------------------------------------------------------
+def test_sort_path_batches_with_exclusions(mf, oracle):
+    """The shape of test_sort_path_more_users_than_one_staging_batch: a batch of 292 users and one of 8, every user's
+    three best items and 1 000 random ones excluded, as a pair list and from the index."""
+    I, k, topn, n_users = 16 * TILE + 1, 4, 129, 300
+    assert SORT_CELLS // I == 292 and topn > 128
+    rng, P, Q = E.tied_factors(n_users, I, k, 301)
+    users = rng.permutation(n_users).astype(np.int32)
+    rows = {}
+    best = {int(u): E.top_of(rows.setdefault(int(u), E.all_scores(oracle, P, Q, int(u))), 3) for u in users}
+    eu = np.repeat(users, 1003)
+    ei = np.concatenate([np.concatenate([best[int(u)], rng.integers(0, I, 1000)]) for u in users]).astype(np.int32)
+    perm = rng.permutation(eu.size)
+    eu, ei = np.ascontiguousarray(eu[perm]), np.ascontiguousarray(ei[perm])
+    want = E.recommend_ref(oracle, P, Q, users, topn, eu, ei, score_rows=rows)
+    for b in range(292, n_users):  # the second batch: the best items would have led the row
+        assert not np.isin(best[int(users[b])], want[0][b]).any()
+    with _model(mf, P, Q) as m:
+        got = m.recommend(users, topn, exclude=(eu, ei))
+        E.assert_recommend(got, want, "a pair list")
+        m.set_seen(eu, ei)
+        seen = m.recommend(users, topn, exclude="seen")
+        E.assert_recommend(seen, want, "the index")
+    for b in range(292, n_users):
+        assert not np.isin(best[int(users[b])], got[0][b]).any() and not np.isin(best[int(users[b])], seen[0][b]).any()
+
+
+# ---- 11. lists read back past the strides of the gather ---------------------------------------------------------------------
+def test_seen_reads_back_past_the_strides_of_the_gather(mf):
+    """gather_kernel strides over a list in at most 64 parts of 256 positions and over the request rows in at most 4 096
+    workgroups: a list of 17 000 and one of 20 000 items, asked for at request rows beyond 4 096, take second trips of both
+    loops.  Then a merge that adds 3 000 keys to the long user, interleaved with its old ones."""
+    U, I = 5000, 20000
+    long_user, full_user = 4321, 77
+    rng = np.random.default_rng(11)
+    assert 17000 > GATHER_SPAN and I > GATHER_SPAN and U + 200 > GATHER_ROWS
+    has = rng.permutation(I)[:17000].astype(np.int32)
+    lens = rng.integers(0, 6, U)
+    lens[[long_user, full_user]] = 0
+    su = np.concatenate([np.repeat(np.arange(U), lens), np.full(has.size, long_user), np.full(I, full_user)]).astype(np.int32)
+    si = np.concatenate([rng.integers(0, I, int(lens.sum())), has, np.arange(I)]).astype(np.int32)
+    perm = rng.permutation(su.size)
+    su, si = su[perm], si[perm]
+    users = rng.permutation(U).astype(np.int32)
+    for at, user in ((4500, long_user), (4999, full_user)):  # the long lists at request rows of the second trip
+        users[np.flatnonzero(users == user)[0]] = users[at]
+        users[at] = user
+    users = np.concatenate([users, rng.integers(0, U, 198), [long_user, 3]]).astype(np.int32)
+    assert users.size == U + 200 and np.flatnonzero(users == long_user).min() >= GATHER_ROWS
+    assert np.flatnonzero(users == full_user).min() >= GATHER_ROWS and np.array_equal(np.unique(users), np.arange(U))
+
+    def check(m, su, si, what):
+        all_ptr, all_items = _csr(su, si, U)
+        ptr, items = m.seen(users)
+        assert np.array_equal(np.diff(ptr), np.diff(all_ptr)[users]), what
+        want = np.concatenate([all_items[all_ptr[u]:all_ptr[u + 1]] for u in users])
+        assert np.array_equal(items, want), what
+        ptr, items = m.seen([long_user])  # one request row, many parts
+        assert ptr.tolist() == [0, all_ptr[long_user + 1] - all_ptr[long_user]], what
+        assert np.array_equal(items, all_items[all_ptr[long_user]:all_ptr[long_user + 1]]), what
+        return items.size
+    with mf.MatrixFactorizationSGD(U, I, 4, LR, LAM, 1) as m:
+        m.set_seen(su, si)
+        assert check(m, su, si, "set_seen") == 17000
+        _seen_is(m, su, si, "set_seen")
+        more = np.concatenate([np.setdiff1d(np.arange(I), has), has[:500]]).astype(np.int32)  # 3 000 new, 500 it has
+        rng.shuffle(more)
+        bu, bi = np.full(more.size, long_user, np.int32), more
+        m.mark_seen(bu, bi)
+        su, si = np.concatenate([su, bu]), np.concatenate([si, bi])
+        assert check(m, su, si, "mark_seen") == I
+        _seen_is(m, su, si, "mark_seen")
+
+
+# ---- 12. growth with the factors on host staging ----------------------------------------------------------------------------
+def test_the_index_follows_appends_on_host_staging(mf, oracle):
+    """set_factors leaves the factors on host staging until the first compute call (csrc/handle.cpp, Where::Host); the
+    index is on the device all the same, and an append that reallocates, a reserve and an append in place move or keep
+    its per-user tables as they do with the factors on the device."""
+    U, I, k = 40, 30, 8
+    rng, P, Q = _factors(U, I, k, 12)
+    su, si = rng.integers(0, U, 500).astype(np.int32), rng.integers(0, I, 500).astype(np.int32)
+    new = rng.standard_normal((8, k)).astype(np.float32)
+    with _model(mf, P, Q) as m:
+        m.set_seen(su, si)
+        assert m.add_users(new[:6]) == U and m.capacity()[0] == U + 6  # beyond the capacity
+        _seen_is(m, su, si, "after a reallocating append on host staging")
+        m.mark_seen([U + 5, U, 0], [3, I - 1, 0])
+        su, si = np.concatenate([su, [U + 5, U, 0]]).astype(np.int32), np.concatenate([si, [3, I - 1, 0]]).astype(np.int32)
+        _seen_is(m, su, si, "new users marked")
+        m.reserve(U + 20)
+        _seen_is(m, su, si, "after reserve")
+        assert m.add_users(new[6:]) == U + 6 and m.capacity()[0] == U + 20  # in place
+        _seen_is(m, su, si, "after an append in place on host staging")
+        users = np.arange(U + 8, dtype=np.int32)
+        got = m.recommend(users, 5, exclude="seen")  # (the first compute call: the factors go up now)
+        _seen_is(m, su, si, "after the upload")
+    want = E.recommend_ref(oracle, np.vstack([P, new]), Q, users, 5, su, si)
+    assert not np.array_equal(want[0], E.recommend_ref(oracle, np.vstack([P, new]), Q, users, 5)[0])
+    E.assert_recommend(got, want)
