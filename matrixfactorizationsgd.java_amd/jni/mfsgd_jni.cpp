@@ -1,8 +1,14 @@
 // mfsgd_jni.cpp -- JNI shim between java/MatrixFactorizationSGD.java and the C-ABI
 // of include/mfsgd.h.
 //
-// UNCOMPILED AND UNTESTED: there is no JDK (no jni.h) in this container or on the
-// GPU box.  Build, where a JDK exists:
+// NEVER RUN UNDER A REAL JVM: there is no JDK (no jni.h) in this container or on the
+// GPU box.  What the test-suite does instead: every native below is executed under a JVM
+// stand-in (tests/jni_stub/jni.h + fake_jvm.cpp) that enforces the JNI rules a shim can
+// break -- typed arrays, region bounds, no call but ExceptionCheck while an exception is
+// pending, no critical regions, known classes only -- and each result is compared byte for
+// byte with what the Python surface returns for the same call on a twin handle
+// (tests/test_jni_cpu.py, tests/test_jni_gpu.py).  java/MatrixFactorizationSGD.java itself
+// is still unchecked: there is no javac.  Build, where a JDK exists:
 //   g++ -std=c++17 -fPIC -shared -I$JAVA_HOME/include -I$JAVA_HOME/include/linux ...
 //       -I../../include mfsgd_jni.cpp -L../lib -lmfsgd -Wl,-rpath,'$ORIGIN' -o libmfsgd_jni.so
 //
@@ -13,7 +19,8 @@
 // inside a critical region); every call works on NATIVE copies made with
 // Get*ArrayRegion; array lengths are checked here, not only in Java; a failed native
 // allocation throws OutOfMemoryError; a non-zero status becomes a RuntimeException
-// carrying mfsgd_last_error(); no C++ exception crosses the boundary.
+// carrying mfsgd_last_error(), or a fixed text where the library has none (a null or
+// closed handle): no exception has an empty message; no C++ exception crosses the boundary.
 #include <jni.h>
 
 #include <cstdint>
@@ -24,24 +31,35 @@
 
 namespace {
 
-void throw_status(JNIEnv* env, mfsgd_handle* h, int rc) {
-    if (rc == MFSGD_OK) return;
-    jclass cls = env->FindClass("java/lang/RuntimeException");
-    if (cls) env->ThrowNew(cls, mfsgd_last_error(h));
+void throw_new(JNIEnv* env, const char* cls_name, const char* msg) {
+    jclass cls = env->FindClass(cls_name);
+    if (cls) env->ThrowNew(cls, msg);
 }
+
+// An exception never carries an empty message: where the library has no text the shim says what it knows.
+const char* text_or(const char* msg, const char* fallback) { return msg && *msg ? msg : fallback; }
 
 mfsgd_handle* H(jlong h) { return reinterpret_cast<mfsgd_handle*>(h); }
 mfsgd_dsgd* D(jlong d) { return reinterpret_cast<mfsgd_dsgd*>(d); }
 
-void throw_dsgd(JNIEnv* env, mfsgd_dsgd* d, int rc) {
+// h == nullptr: the Java object was closed or never created.  mfsgd_last_error(nullptr) is the message of the last
+// failed mfsgd_create on this thread (empty when there was none): it says nothing about this call.
+void throw_status(JNIEnv* env, mfsgd_handle* h, int rc) {
     if (rc == MFSGD_OK) return;
-    jclass cls = env->FindClass("java/lang/RuntimeException");
-    if (cls) env->ThrowNew(cls, mfsgd_dsgd_last_error(d));
+    throw_new(env, "java/lang/RuntimeException",
+              h ? text_or(mfsgd_last_error(h), "mfsgd: the call failed without a message") : "mfsgd: null or closed handle");
 }
 
-void throw_new(JNIEnv* env, const char* cls_name, const char* msg) {
-    jclass cls = env->FindClass(cls_name);
-    if (cls) env->ThrowNew(cls, msg);
+void throw_dsgd(JNIEnv* env, mfsgd_dsgd* d, int rc) {
+    if (rc == MFSGD_OK) return;
+    throw_new(env, "java/lang/RuntimeException",
+              d ? text_or(mfsgd_dsgd_last_error(d), "mfsgd: the ring call failed without a message") : "mfsgd: null or closed ring");
+}
+
+// the calls that have no object yet (mfsgd_create, mfsgd_dsgd_unique_id, mfsgd_dsgd_create) leave their message with
+// the thread
+void throw_text(JNIEnv* env, int rc, const char* msg, const char* fallback) {
+    if (rc != MFSGD_OK) throw_new(env, "java/lang/RuntimeException", text_or(msg, fallback));
 }
 
 // new[] that reports failure to Java instead of throwing across the boundary
@@ -67,7 +85,8 @@ JNIEXPORT jlong JNICALL Java_MatrixFactorizationSGD_nativeCreate(JNIEnv* env, jc
     cfg.device = device;
     cfg.n_parts = n_parts;
     mfsgd_handle* h = nullptr;
-    throw_status(env, nullptr, mfsgd_create(&cfg, &h));
+    const int rc = mfsgd_create(&cfg, &h);
+    throw_text(env, rc, mfsgd_last_error(nullptr), "mfsgd_create failed");
     return reinterpret_cast<jlong>(h);
 }
 
@@ -783,7 +802,7 @@ JNIEXPORT jbyteArray JNICALL Java_MatrixFactorizationSGD_nativeDsgdUniqueId(JNIE
     signed char id[MFSGD_DSGD_ID_BYTES];
     const int rc = mfsgd_dsgd_unique_id(id);
     if (rc != MFSGD_OK) {
-        throw_dsgd(env, nullptr, rc);
+        throw_text(env, rc, mfsgd_dsgd_last_error(nullptr), "mfsgd_dsgd_unique_id failed");
         return nullptr;
     }
     jbyteArray out = env->NewByteArray(MFSGD_DSGD_ID_BYTES);
@@ -848,7 +867,8 @@ JNIEXPORT jlong JNICALL Java_MatrixFactorizationSGD_nativeDsgdCreate(JNIEnv* env
     env->GetByteArrayRegion(id, 0, MFSGD_DSGD_ID_BYTES, raw);
     if (env->ExceptionCheck()) return 0;
     mfsgd_dsgd* d = nullptr;
-    throw_dsgd(env, nullptr, mfsgd_dsgd_create(H(h), rank, world, raw, &d));  // collective: ncclCommInitRank
+    const int rc = mfsgd_dsgd_create(H(h), rank, world, raw, &d);  // collective: ncclCommInitRank
+    throw_text(env, rc, mfsgd_dsgd_last_error(nullptr), "mfsgd_dsgd_create failed");
     return reinterpret_cast<jlong>(d);
 }
 

@@ -1,10 +1,12 @@
 /*
- * DECLARATION-ONLY STUB of the handful of JNI names jni/mfsgd_jni.cpp uses, transcribed from the
- * Java Native Interface specification (types, the JNIEnv member functions' signatures).  There is
- * no JDK in this image, so the real <jni.h> does not exist here; this file lets the test-suite
- * check that the shim is well-formed C++ against those signatures (hipcc -fsyntax-only).  It is
- * TEST INFRASTRUCTURE: nothing links against it, it implements nothing, and a shim that passes
- * this check has still never run under a JVM.
+ * STUB of the handful of JNI names jni/mfsgd_jni.cpp uses, transcribed from the Java Native
+ * Interface specification (types, the JNIEnv member functions' signatures).  There is no JDK in
+ * this image, so the real <jni.h> does not exist here; this is the one header the shim is compiled
+ * against in the test-suite: for syntax and types (g++ -fsyntax-only), and for real, together with
+ * fake_jvm.cpp beside it, which defines the member functions declared below over a registry of
+ * typed arrays and records every breach of the JNI rules (tests/jni_fake.py, tests/test_jni_*.py).
+ * It is TEST INFRASTRUCTURE: the header itself implements nothing, and a shim that passes these
+ * tests has run under that stand-in, still never under a JVM.
  */
 #ifndef MFSGD_TEST_JNI_STUB_H
 #define MFSGD_TEST_JNI_STUB_H
