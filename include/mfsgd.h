@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver; + mfsgd_set_validation, mfsgd_validation_size, mfsgd_validation_rmse, mfsgd_rmse_pairs, mfsgd_train_early_stop; + mfsgd_row_inv_norms, mfsgd_similar_items, mfsgd_similar_users, mfsgd_similar_rows; + mfsgd_online_levels, mfsgd_apply_ratings; + mfsgd_fold_in_items, mfsgd_append_users, mfsgd_append_items, mfsgd_reserve_rows, mfsgd_get_capacity; + mfsgd_recommend_among, mfsgd_recommend_rows_among, mfsgd_debug_serve_seconds; + mfsgd_set_seen, mfsgd_mark_seen, mfsgd_clear_seen, mfsgd_seen_size, mfsgd_get_seen, mfsgd_recommend_unseen, mfsgd_recommend_unseen_among, mfsgd_rank_items_unseen, mfsgd_evaluate_ranking_unseen (additions: no existing call changed) */
+#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver; + mfsgd_set_validation, mfsgd_validation_size, mfsgd_validation_rmse, mfsgd_rmse_pairs, mfsgd_train_early_stop; + mfsgd_row_inv_norms, mfsgd_similar_items, mfsgd_similar_users, mfsgd_similar_rows; + mfsgd_online_levels, mfsgd_apply_ratings; + mfsgd_fold_in_items, mfsgd_append_users, mfsgd_append_items, mfsgd_reserve_rows, mfsgd_get_capacity; + mfsgd_recommend_among, mfsgd_recommend_rows_among, mfsgd_debug_serve_seconds; + mfsgd_set_seen, mfsgd_mark_seen, mfsgd_clear_seen, mfsgd_seen_size, mfsgd_get_seen, mfsgd_recommend_unseen, mfsgd_recommend_unseen_among, mfsgd_rank_items_unseen, mfsgd_evaluate_ranking_unseen; + mfsgd_sample_unseen (additions: no existing call changed) */
 
 typedef enum mfsgd_status {
     MFSGD_OK = 0,
@@ -336,6 +336,38 @@ int mfsgd_clear_seen(mfsgd_handle* h);
 int mfsgd_seen_size(const mfsgd_handle* h, int64_t* pairs);
 int mfsgd_get_seen(mfsgd_handle* h, const int32_t* users, int32_t n_users, int64_t* row_ptr /* n_users + 1 */,
                    int32_t* items /* nullable */, int64_t items_capacity);
+/* mfsgd_sample_unseen: negative sampling for implicit feedback (clicks, plays: positives only).  Row x of out_items
+ * receives m items drawn uniformly, with replacement, among the items user users[x] has NOT seen according to the index;
+ * users may repeat and come in any order.  "Unseen" means unseen by the index, whatever the rating set holds: pairs that
+ * must never be drawn (held-out positives, say) belong in the index.  Items appended with mfsgd_append_items are unseen by
+ * everybody, users appended with mfsgd_append_users have empty lists.
+ * The draw.  Draw d of row x has the counter c = first + x * m + d and is a pure function of (seed, c), that user's list S
+ * (sorted, distinct, length s) and the handle's current n_items -- not of n, of the other rows, of how a caller cuts one
+ * call into several (rows [a, b) of a call are the call on users + a with first + a * m), or of the device.  All of it in
+ * unsigned 64-bit arithmetic that wraps:
+ *     z = (uint64)seed + 0x9E3779B97F4A7C15 * (c + 1)
+ *     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *     z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *     z =  z ^ (z >> 31)
+ *     r = z >> 32
+ *     cnt = n_items - s;  cnt == 0: out = -1 (the user has seen everything)
+ *     t = (r * cnt) >> 32                in [0, cnt), each value's probability within 2^-32 of 1 / cnt
+ *     p = the number of positions q in [0, s) with S[q] - q <= t
+ *     out = t + p                        the t-th unseen item, counting from 0 in ascending order
+ * S[q] - q never decreases, so p is one binary search: a draw is exact, never rejected and retried, and costs O(log s)
+ * however much the user has seen.  Two draws of a row may give the same item.  An empty index gives out = t.
+ * Checks, all before any device work, in this order.  MFSGD_ERR_INVALID_ARG ("sample_unseen: ..."): a negative n or m; a
+ * negative first, or first + n * m above 2^63 - 1; null users or out_items with n * m > 0.  Then MFSGD_ERR_STATE for
+ * n_parts != 1 and for a handle without an index ("no seen set").  Then MFSGD_ERR_INVALID_ARG for a user outside
+ * [0, n_users); the message names the row, and out_items is untouched.  n * m == 0 is MFSGD_OK past the state checks
+ * and touches nothing.  A valid call with work to do and no usable GPU is MFSGD_ERR_NO_DEVICE, an empty index included:
+ * there is never a CPU result.  Needs neither factors nor ratings, and modifies neither the model nor the index.
+ * Cost: one thread per draw reads its user's two offsets and searches the list in the index where it lies; no pass over
+ * the pairs of the index or over n_items.  The rows go up and the draws come down in pieces of whole rows of at most
+ * 2^22 draws (a row with more is a piece of its own): at most 32 MB of staging whatever n is (more only for such a row),
+ * all of it freed before the call returns, on every path -- mfsgd_debug_device_bytes is the same before and after.     */
+int mfsgd_sample_unseen(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first,
+                        int32_t* out_items /* n x m, row-major */);
 /* The serving calls against the index.  Each is the call it is named after -- mfsgd_recommend_excluding,
  * mfsgd_recommend_among, mfsgd_rank_items, mfsgd_evaluate_ranking -- given the index's pairs as its exclusion pairs:
  * order, ties, score bits, padding with -1 / NaN, the rule that a ranked pair's own item counts as eligible even if

@@ -526,6 +526,11 @@ int mfsgd_get_seen(mfsgd_handle* h, const int32_t* users, int32_t n_users, int64
     return guarded(h, "get_seen", [&]() -> int { return seen_get(h, users, n_users, row_ptr, items, items_capacity); });
 }
 
+int mfsgd_sample_unseen(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first,
+                        int32_t* out_items) {
+    return guarded(h, "sample_unseen", [&]() -> int { return seen_sample(h, users, n, m, seed, first, out_items); });
+}
+
 int mfsgd_debug_device_bytes(int64_t* live) {
     if (!live) return MFSGD_ERR_INVALID_ARG;
     *live = g_dev_live_bytes.load();

@@ -1,5 +1,5 @@
 // kernels.hpp -- host-callable launchers of every kernel unit: epoch.hip, cells.hip, kernels.hip, foldin.hip,
-// online.hip, rehyper.hip, recommend.hip, rank.hip, seen.hip, similar.hip, validate.hip and grow.hip.
+// online.hip, rehyper.hip, recommend.hip, rank.hip, seen.hip, sample.hip, similar.hip, validate.hip and grow.hip.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -177,6 +177,12 @@ hipError_t seen_merge(const long long* off, const int32_t* items, int64_t total,
 hipError_t seen_lengths(const long long* off, const int32_t* users, int32_t n, long long* len, hipStream_t st);
 hipError_t seen_gather(const long long* off, const int32_t* items, const int32_t* users, int32_t n, const long long* row_ptr,
                        int64_t longest, int32_t* out, hipStream_t st);
+
+// sample.hip.  Uniform draws among the items a user has not seen (include/mfsgd.h, mfsgd_sample_unseen): out[x], x <
+// n_draws, is draw x % m of row x / m of `users` (every one a user of the index {off, items}; off == nullptr: an index
+// without pairs) with the counter first + x, among n_items items; -1 where the user has seen them all.  n_draws < 2^31.
+hipError_t sample_unseen_draws(const long long* off, const int32_t* items, const int32_t* users, int64_t n_draws, int32_t m,
+                               int32_t n_items, int64_t seed, uint64_t first, int32_t* out, hipStream_t st);
 
 // similar.hip.  out[x] = rn(row x) = 1 / sqrt(dot(row, row)), or 0 where that dot is 0, for the
 // n_rows kp-padded rows of M.  Asynchronous on st.

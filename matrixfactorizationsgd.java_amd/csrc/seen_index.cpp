@@ -195,4 +195,48 @@ int seen_get(mfsgd_handle* h, const int32_t* users, int32_t n_users, int64_t* ro
     return MFSGD_OK;
 }
 
+// Body of mfsgd_sample_unseen (handle.cpp): row x of out_items receives m draws among the items users[x] has not seen.
+// The rows go up and the draws come down in pieces of whole rows, at most kSampleChunk draws each (a row with more is a
+// piece of its own); draw d of row x has the counter first + x * m + d wherever the pieces are cut.
+int seen_sample(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first, int32_t* out_items) {
+    if (n < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen: n is negative");
+    if (m < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen: m is negative");
+    if (first < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen: first is negative");
+    if ((m > 0 && n > INT64_MAX / m) || first > INT64_MAX - n * m)
+        return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen: first + n * m exceeds 2^63 - 1");
+    const int64_t total = n * m;
+    if (total > 0 && (!users || !out_items)) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen: users or out_items is null");
+    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "sample_unseen: single-partition handles only");
+    if (!h->seen.present) return fail(h, MFSGD_ERR_STATE, "sample_unseen: no seen set");
+    if (total == 0) return MFSGD_OK;
+    const uint32_t U = (uint32_t)h->cfg.n_users;
+    for (int64_t x0 = 0; x0 < n; x0 += 4096) {  // (in blocks without a branch, as check_pairs)
+        const int64_t x1 = std::min(n, x0 + 4096);
+        uint32_t outside = 0;
+        for (int64_t x = x0; x < x1; ++x) outside |= (uint32_t)((uint32_t)users[x] >= U);
+        for (int64_t x = x0; outside && x < x1; ++x)
+            if ((uint32_t)users[x] >= U)
+                return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen: user " + std::to_string(x) + " out of range");
+    }
+    int rc = ensure_device(h);
+    if (rc) return rc;
+    auto bad = [h](hipError_t e) { return serve_fail(h, "sample_unseen: ", e); };
+    const Seen& s = h->seen;
+    const int64_t rows = std::min(n, std::max<int64_t>(1, kSampleChunk / m));
+    DevBuf d_users, d_out;
+    if ((rc = dev_alloc(h, d_users, sizeof(int32_t) * (size_t)rows))) return rc;
+    if ((rc = dev_alloc(h, d_out, sizeof(int32_t) * (size_t)(rows * m)))) return rc;
+    for (int64_t x0 = 0; x0 < n; x0 += rows) {
+        const int64_t c = std::min(rows, n - x0), draws = c * m;
+        HIPCHK_OR(bad, hipMemcpyAsync(d_users.get(), users + x0, sizeof(int32_t) * (size_t)c, hipMemcpyHostToDevice, h->stream));
+        HIPCHK_OR(bad, sample_unseen_draws(s.n > 0 ? s.off.as<const long long>() : nullptr, s.items.as<const int32_t>(),
+                                           d_users.as<const int32_t>(), draws, m, h->cfg.n_items, seed,
+                                           (uint64_t)first + (uint64_t)(x0 * m), d_out.as<int32_t>(), h->stream));
+        HIPCHK_OR(bad, hipMemcpyAsync(out_items + x0 * m, d_out.get(), sizeof(int32_t) * (size_t)draws, hipMemcpyDeviceToHost,
+                                      h->stream));
+        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // (pageable memory: the staging is free for the next piece)
+    }
+    return MFSGD_OK;
+}
+
 }  // namespace mfsgd

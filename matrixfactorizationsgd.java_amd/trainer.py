@@ -463,6 +463,66 @@ class MatrixFactorizationSGD:
                                                  _p(items, C.c_int32), items.size))
         return ptr, items
 
+    # -- implicit feedback: negatives sampled off the seen-item index -----------------
+    def sample_unseen(self, users, m=1, seed=0, first=0):
+        """int32 [len(users), m]: for each row, m items drawn uniformly (with replacement) among those the row's user has
+        not seen according to the seen-item index (mfsgd_sample_unseen: one device thread per draw, exact, no rejection);
+        -1 throughout a row whose user has seen every item.  Draw d of row x is a pure function of seed, the counter
+        first + x * m + d, the user's list and the item count: rows [a:b] of a call are the call on users[a:b] with
+        first + a * m."""
+        uu = _i32(np.atleast_1d(users))
+        if uu.ndim != 1:
+            raise ValueError("users must be a 1-d array")
+        out = np.empty((uu.size, max(int(m), 0)), np.int32)
+        self._sample_unseen_into(uu, m, seed, first, out)
+        return out
+
+    def _sample_unseen_into(self, uu, m, seed, first, out):
+        """sample_unseen(uu, ...) into `out`, a C-contiguous int32 array of uu.size * m entries."""
+        self._check(self._lib.mfsgd_sample_unseen(self._handle(), _p(uu, C.c_int32), uu.size, int(m), int(seed), int(first),
+                                                  _p(out, C.c_int32)))
+
+    def fit_implicit(self, u, i, epochs, negatives=4, *, seed=0, pos=1.0, neg=0.0, first_epoch=0, rmse=True):
+        """Trains on one-class data (clicks, plays, purchases): (u[x], i[x]) are the positives, duplicates allowed, and
+        every epoch pairs each of them with `negatives` freshly drawn items its user has not seen, trained towards `neg`.
+        Unseen means unseen by the seen-item index, not by (u, i).  A handle without an index gets set_seen(u, i), and
+        keeps it (recommend(exclude="seen") wants it afterwards); an index the handle already has is used as it is, so a
+        caller who puts held-out positives into it first never trains them as negatives.  Factors that were never
+        initialised are seeded, as in train().
+        Epoch e, counted from first_epoch: J = sample_unseen(u, negatives, seed, first=e * n * negatives); the rating set
+        is the positives in the order given at `pos`, then (u[x], J[x, d], neg) in row-major order without the -1 of
+        users who have seen everything; set_ratings of that set, fit(1).  Seed and epoch number alone decide the draws:
+        epochs=a followed by epochs=b, first_epoch=a is epochs=a + b bit for bit.  negatives=0: one set_ratings of the
+        positives and fit(epochs).  Returns the RMSE of each epoch over that epoch's own set (None with rmse=False);
+        the last epoch's set stays the handle's rating set."""
+        uu, ii = _pairs(np.atleast_1d(u), np.atleast_1d(i), "u and i")
+        epochs, negatives, n = int(epochs), int(negatives), uu.size
+        if epochs < 0 or negatives < 0:
+            raise ValueError("epochs and negatives must not be negative")
+        if self.seen_size() < 0:
+            self.set_seen(uu, ii)
+        if not self._initialised:
+            self.init_factors()
+        rr = np.full(n, pos, np.float32)
+        if negatives == 0:
+            self.set_ratings(uu, ii, rr)
+            return self.fit(epochs, rmse=rmse)
+        # the set of an epoch is laid out once: the draws come down into the items' tail, where set_ratings reads them
+        set_u, set_i = np.concatenate([uu, np.repeat(uu, negatives)]), np.concatenate([ii, np.empty(n * negatives, np.int32)])
+        set_r = np.concatenate([rr, np.full(n * negatives, neg, np.float32)])
+        out = np.zeros(epochs, np.float64)
+        for x in range(epochs):
+            self._sample_unseen_into(uu, negatives, seed, (int(first_epoch) + x) * n * negatives, set_i[n:])
+            if n and set_i[n:].min() < 0:  # users who have seen everything have no negatives
+                keep = np.concatenate([np.ones(n, bool), set_i[n:] >= 0])
+                self.set_ratings(set_u[keep], set_i[keep], set_r[keep])
+            else:
+                self.set_ratings(set_u, set_i, set_r)
+            got = self.fit(1, rmse=rmse)
+            if rmse:
+                out[x] = got[0]
+        return out if rmse else None
+
     def serve_seconds(self):
         """(lists, topn): host seconds the latest recommend call spent building its candidate and exclusion lists on the
         device, and scoring and selecting (mfsgd_debug_serve_seconds)."""
