@@ -57,20 +57,26 @@
 //     chain alone, steady  L = 16: 101.9 101.9 102.4 102.6    L = 32: 119.1 119.2 119.7 119.9    L = 64: 133.3 133.4 133.9 134.1
 //     chain alone, tail    L = 16: 112.1 112.0 112.5 112.5    L = 32: 128.8 128.6 129.0 129.0    L = 64: 140.5 140.6 141.0 140.6
 //     solo pair,   helper  L = 16: 119.2 109.5 113.3 117.0    L = 32: 122.8 125.3 124.1 124.3    L = 64: 142.1 141.8 141.3 141.2
+// The run loop's and the general loop's LDS reads of a step as ONE group behind the first DPP add (see MFSGD_RUN_LOOP_ASM_TEXT
+// and MFSGD_GEN_HALF; profiles/loop_groups_ubench.log: tools/ubench3 modes 3 and 8, one wave, cycles per step at the longest
+// n -- 300 / 200 / 120 run steps with the idle slots masked, 64 general steps -- the parent's loops at 157.7 / 188.4 / 193.5
+// and 226.2 / 260.4 / 258.5 in that session, alternating, every figure repeating to 0.1), at 0 / 2 / 4 / 6 s_nops:
+//     run loop      L = 16: 147.7 149.6 151.7 153.6    L = 32: 178.5 180.6 182.6 184.5    L = 64: 183.6 185.6 187.9 189.7
+//     general loop  L = 16: 212.2 214.4 220.4 216.2    L = 32: 244.6 236.4 244.5 252.4    L = 64: 242.5 244.6 250.6 244.9
 // Every loop head is therefore placed explicitly (operands [pad] / [pads], assembly-time constants): the product
 // runs the layout that was timed, whatever code the compiler puts in front of the loop.
 constexpr int mfsgd_pad_run(int lanes) {
 #ifdef MFSGD_PAD_RUN
     return MFSGD_PAD_RUN;
 #else
-    return 2;
+    return 0;  // the loop with its three reads in one group, last table above (profiles/loop_groups_ubench.log)
 #endif
 }
 constexpr int mfsgd_pad_gen(int lanes) {
 #ifdef MFSGD_PAD_GEN
     return MFSGD_PAD_GEN;
 #else
-    return 0;
+    return lanes == 32 ? 2 : 0;  // the loop with its four reads in one group, last table above
 #endif
 }
 // The chain wave's loop has two heads (the steady body and the tail, see MFSGD_SOLO_CHAIN_ASM_TEXT), each placed on its own.
@@ -146,6 +152,16 @@ static_assert(mfsgd_chain_steady() % 2 == 0 && mfsgd_chain_steady() >= 2 && mfsg
 //   there into the resident rows of other idle slots.  p' is still computed and stored for every lane (the counted waits
 //   rely on the store): an idle slot's goes to its dummy row, which nothing that reaches P or Q reads any more.
 //   (A lane group is one or two whole DPP rows, and the partner rows of the swap levels belong to the same group.)
+//   LDS operations of one step, in issue order: read p(t+1), read slots(t+2), read {lr*r, ce}(t+1) -- ONE group, in the
+//   two wait states behind the FIRST DPP add, where the chain wave's reads measured best (an LDS instruction behind VALU
+//   work costs the wave about 8 cycles per group of adjacent ones, tools/ubench5.hip; the entry reads used to be a group
+//   of their own behind the third add) -- then, behind the arithmetic, write p'(t).  The order is the one the step always
+//   had, so the counted wait is too: LDS operations of a wave complete in order, and "all but the last one" at the top of
+//   step t + 1 leaves only the write of p'(t) outstanding -- p(t+1), slots(t+2) and {lr*r, ce}(t+1) are in registers.
+//   The prefetch of p(t+1) is issued in front of the store of p'(t) as before (a p row may recur at distance two, never
+//   at distance one).  What the moved reads overwrite is dead by then: v114 / v115 (slots of the step in flight) is last
+//   read by the v_cmp at the top of its step, v[116:117] / v[118:119] by the other half's SFMA.  The wait states in
+//   front of the four adds hold, in order: {p address, ce*q01}, {the three reads}, {ce*p01, ce*p23}, {ce*q23, s_and_saveexec}.
 #define MFSGD_RUN_LOOP_ASM_TEXT(EXTRA, SFMA) \
         "v_mov_b32 v138, %[ea]\n\t" \
         "v_mov_b32 v131, %[lr]\n\t" \
@@ -173,13 +189,13 @@ static_assert(mfsgd_chain_steady() % 2 == 0 && mfsgd_chain_steady() >= 2 && mfsg
         "v_pk_mul_f32 v[140:141], v[116:117], v[100:101] op_sel:[1,0]\n\t" \
         "v_add_f32_dpp v132, v132, v132 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
         "ds_read_b128 v[108:111], v113\n\t" \
-        "v_pk_mul_f32 v[142:143], v[116:117], v[102:103] op_sel:[1,0]\n\t" \
+        "ds_read_b32 v114, v138 offset:%c[e2]\n\t" \
+        "ds_read_b64 v[118:119], v138 offset:%c[e1p8]\n\t" \
         "v_add_f32_dpp v132, v132, v132 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
         "v_pk_mul_f32 v[126:127], v[116:117], v[104:105] op_sel:[1,0]\n\t" \
         "v_pk_mul_f32 v[128:129], v[116:117], v[106:107] op_sel:[1,0]\n\t" \
         "v_add_f32_dpp v132, v132, v132 row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
-        "ds_read_b32 v114, v138 offset:%c[e2]\n\t" \
-        "ds_read_b64 v[118:119], v138 offset:%c[e1p8]\n\t" \
+        "v_pk_mul_f32 v[142:143], v[116:117], v[102:103] op_sel:[1,0]\n\t" \
         "s_and_saveexec_b64 %[sv], %[live]\n\t" \
         "v_add_f32_dpp v132, v132, v132 row_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
         EXTRA \
@@ -200,13 +216,13 @@ static_assert(mfsgd_chain_steady() % 2 == 0 && mfsgd_chain_steady() >= 2 && mfsg
         "v_pk_mul_f32 v[100:101], v[118:119], v[140:141] op_sel:[1,0]\n\t" \
         "v_add_f32_dpp v132, v132, v132 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
         "ds_read_b128 v[104:107], v112\n\t" \
-        "v_pk_mul_f32 v[102:103], v[118:119], v[142:143] op_sel:[1,0]\n\t" \
+        "ds_read_b32 v115, v138 offset:%c[e3]\n\t" \
+        "ds_read_b64 v[116:117], v138 offset:%c[e2p8]\n\t" \
         "v_add_f32_dpp v132, v132, v132 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
         "v_pk_mul_f32 v[126:127], v[118:119], v[108:109] op_sel:[1,0]\n\t" \
         "v_pk_mul_f32 v[128:129], v[118:119], v[110:111] op_sel:[1,0]\n\t" \
         "v_add_f32_dpp v132, v132, v132 row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
-        "ds_read_b32 v115, v138 offset:%c[e3]\n\t" \
-        "ds_read_b64 v[116:117], v138 offset:%c[e2p8]\n\t" \
+        "v_pk_mul_f32 v[102:103], v[118:119], v[142:143] op_sel:[1,0]\n\t" \
         "s_and_saveexec_b64 %[sv], %[live]\n\t" \
         "v_add_f32_dpp v132, v132, v132 row_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
         EXTRA \
@@ -273,9 +289,17 @@ static_assert(mfsgd_chain_steady() % 2 == 0 && mfsgd_chain_steady() >= 2 && mfsg
 //   set A / B; v[104:107], v[100:103] / v[108:111], v[140:143] p and q row of set A / B; v[144:147] the q row read
 //   ahead (selected against the forwarded q'); v[120:121] chunk products, v132 dot, v[122:125] c*q, v[126:129] c*p,
 //   v130 s, v[134:137] p'; q' is computed straight into the OTHER set's q registers.
-// LDS operations of one step, in issue order: read p(t+1), read q(t+1), read slots(t+2), read lr*r(t+1), write p'(t),
-// write q'(t).  LDS operations of a wave complete in order, so "all but the last four" has q(t+1) in registers (the
-// select behind the writes) and "all but the last two" at the top of the next step has the two entry words.
+// LDS operations of one step, in issue order: read p(t+1), read q(t+1), read slots(t+2), read lr*r(t+1) -- ONE group of
+// four adjacent reads in the wait states behind the FIRST DPP add (an LDS instruction behind VALU work costs the wave
+// about 8 cycles per group of adjacent ones, tools/ubench5.hip; they used to be three groups, one behind each of the
+// first, second and fourth add), with the q address computed in front of that add beside the p address -- then, behind
+// the arithmetic, write p'(t), write q'(t).  The order is the one the step always had, so the counts are too: LDS
+// operations of a wave complete in order, six are outstanding behind the writes, "all but the last four" has p(t+1) and
+// q(t+1) in registers (the select behind the writes) and "all but the last two" at the top of the next step has the two
+// entry words as well, only the writes still in flight.  The stale-read rule holds as before: the rows of step t + 1
+// are read in front of the writes of step t, and the forwarded q' is selected behind them.  What the moved reads
+// overwrite is dead by then: the slots word of the step in flight (its addresses were computed a step ago; the flag
+// test reads the NEXT step's word), lr*r of the other set, and v[144:147], last read by the previous step's select.
 // Hazards, as the packer guarantees (schedule.cpp, "Eligibility"): a p row never appears in two consecutive steps
 // of a wave; a q row only in the same lane slot, flagged.  Arithmetic: instruction for instruction DESIGN.md section 3.
 #define MFSGD_GEN_HALF(P0, P1, P2, P3, Q0, Q1, Q2, Q3, PADDR, QADDR, NP0, NP3, NQ0, NQ1, NQ2, NQ3, NPADDR, NQADDR, SLOT_NEXT, \
@@ -286,19 +310,19 @@ static_assert(mfsgd_chain_steady() % 2 == 0 && mfsgd_chain_steady() >= 2 && mfsg
         "v_add_f32 v132, v120, v121\n\t" \
         "v_mad_u32_u16 v" NPADDR ", v" SLOT_NEXT ", 16, v139\n\t" \
         "v_bfe_u32 v133, v" SLOT_NEXT ", 16, 15\n\t" \
+        "v_lshl_add_u32 v" NQADDR ", v133, 4, v139\n\t" \
         "v_add_f32_dpp v132, v132, v132 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
         "ds_read_b128 v[" NP0 ":" NP3 "], v" NPADDR "\n\t" \
-        "v_lshl_add_u32 v" NQADDR ", v133, 4, v139\n\t" \
-        "v_add_f32_dpp v132, v132, v132 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
         "ds_read_b128 v[144:147], v" NQADDR "\n\t" \
-        "v_pk_mul_f32 v[122:123], v[" Q0 ":" Q1 "], %[c2]\n\t" \
-        "v_add_f32_dpp v132, v132, v132 row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
-        "v_pk_mul_f32 v[124:125], v[" Q2 ":" Q3 "], %[c2]\n\t" \
-        "v_pk_mul_f32 v[126:127], v[" P0 ":" P1 "], %[c2]\n\t" \
-        "v_add_f32_dpp v132, v132, v132 row_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
-        "v_pk_mul_f32 v[128:129], v[" P2 ":" P3 "], %[c2]\n\t" \
         "ds_read_b32 v" SLOT_NEXT2 ", v138 offset:" OFF_SLOT2 "\n\t" \
         "ds_read_b32 v" LRR_NEXT ", v138 offset:" OFF_LRR1 "\n\t" \
+        "v_add_f32_dpp v132, v132, v132 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+        "v_pk_mul_f32 v[122:123], v[" Q0 ":" Q1 "], %[c2]\n\t" \
+        "v_pk_mul_f32 v[124:125], v[" Q2 ":" Q3 "], %[c2]\n\t" \
+        "v_add_f32_dpp v132, v132, v132 row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+        "v_pk_mul_f32 v[126:127], v[" P0 ":" P1 "], %[c2]\n\t" \
+        "v_pk_mul_f32 v[128:129], v[" P2 ":" P3 "], %[c2]\n\t" \
+        "v_add_f32_dpp v132, v132, v132 row_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
         EXTRA \
         SFMA(LRR) \
         "v_pk_fma_f32 v[" NQ0 ":" NQ1 "], v[130:131], v[" P0 ":" P1 "], v[122:123] op_sel_hi:[0,1,1]\n\t" \

@@ -23,6 +23,14 @@ for L in 16 32 64; do
     done
     wait
 done
+# the one-wave loops (run loop, general loop) at every placement of their heads (profiles/loop_groups_ubench.log):
+#   for f in tools/bin/ub3p_*; do echo $f; $f loops; done
+for L in 16 32 64; do
+    for PAD in 0 2 4 6; do
+        $HIPCC --offload-arch=gfx950 -O2 -ffp-contract=off -DLG=$L -DMFSGD_PAD_RUN=$PAD -DMFSGD_PAD_GEN=$PAD -Wno-unused-value ubench3.hip -o bin/ub3p_${L}_$PAD &
+    done
+    wait
+done
 # L = 64 with the two v_permlane*_swap levels instead of the row_bcast reduction (what round 1 ran)
 $HIPCC --offload-arch=gfx950 -O2 -ffp-contract=off -DLG=64 -DOLD64 -Wno-unused-value ubench3.hip -o bin/ub3_64old
 $HIPCC --offload-arch=gfx950 -O2 ubench.hip -o bin/ubench

@@ -2,6 +2,9 @@
 // two waves on two SIMDs, wave 0 = chain wave, wave 1 = helper.  Prints cycles per step of the pair
 // (and of the chain wave alone, MODE=1: no helper, nothing stored) and compares every p row and the
 // q row with a plain host restatement of DESIGN.md section 3.
+// Modes 3 / 8 (`ubench3 loops`): the one-wave loops of a sub-cell, wave 0 alone -- the run loop (slot 0 carries the chain, the
+// other slots idle) and the general loop (every lane group a rating per step, forwarded q rows and p rows recurring at
+// distance two in the data) -- cycles per step and the same comparison.
 // Modes 6 / 7 (`ubench3 lone`): the run of a lone-tile cell of the persistent kernel -- q comes out of a mailbox in global
 // memory into the chain wave's registers, p row 0 and the entry words are read in front of the wait, the helper waits at
 // the barrier the chain wave joins on arrival (MFSGD_LONE_CHAIN_ASM_TEXT); timed from the arrival stamp, beside mode 0.
@@ -67,7 +70,7 @@ __global__ void __launch_bounds__(192) k(const float* rows_in, const uint32_t* e
     for (int x = threadIdx.x; x < (NSTEP + 2) * GS * 4; x += blockDim.x) ((uint32_t*)(smem + RUN_OFF))[x] = run_in[x];
     if (threadIdx.x < 4) ((uint32_t*)(smem + CTL_OFF))[threadIdx.x] = 0u;
     __syncthreads();
-    if (mode >= 6) {  // the q row is NOT in LDS: it comes out of the mailbox
+    if (mode == 6 || mode == 7) {  // the q row is NOT in LDS: it comes out of the mailbox
         for (int x = threadIdx.x; x < ROWB / 4; x += blockDim.x) ((float*)(smem + NSTEP * ROWB))[x] = -7.0f;
         __syncthreads();
     }
@@ -91,6 +94,12 @@ __global__ void __launch_bounds__(192) k(const float* rows_in, const uint32_t* e
         constexpr int PADV = mfsgd_pad_run(LG);
         asm volatile(MFSGD_RUN_LOOP_ASM_TEXT(EXTRA, SFMA) MFSGD_RUN_LOOP_ASM_OPERANDS);
         if (g == 0) *(f4*)(smem + qaddr) = q;
+    } else if (wave == 0 && mode == 8) {
+        // the one-wave general loop (cell.hpp gen_loop_asm): every lane group one rating per step, both rows from LDS
+        const unsigned ea = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(smem + RUN_OFF) + (lane / LG) * 16;
+        constexpr int EST = GS * 16;
+        constexpr int PADV = mfsgd_pad_gen(LG);
+        asm volatile(MFSGD_GEN_LOOP_ASM_TEXT(EXTRA, SFMA) MFSGD_GEN_LOOP_ASM_OPERANDS);
     } else if (wave == 0 && mode == 4) {
         // cut run: the chain wave stores q into its row between the halves (measured and not used by the product: run_asm.hpp)
         typedef float f4 __attribute__((ext_vector_type(4)));
@@ -110,7 +119,7 @@ __global__ void __launch_bounds__(192) k(const float* rows_in, const uint32_t* e
             n = n_steps - m;
             asm volatile(MFSGD_SOLO_CHAIN_ASM_TEXT(EXTRA_SOLO, SFMA2) MFSGD_SOLO_CHAIN_OPERANDS);
         }
-    } else if (mode >= 6) {
+    } else if (mode == 6 || mode == 7) {
         const unsigned ctl = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(smem + CTL_OFF);
         if (wave == 0) {
             typedef float f4 __attribute__((ext_vector_type(4)));
@@ -180,7 +189,7 @@ __global__ void __launch_bounds__(192) k(const float* rows_in, const uint32_t* e
         if (spins == 0 && lane == 0) cyc[2] = 1;
     }
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t1)::"memory");
-    if (mode >= 6) t0 = t1 - (unsigned long long)((unsigned)t1 - ((volatile uint32_t*)(smem + CTL_OFF))[1]);  // from the row's arrival
+    if (mode == 6 || mode == 7) t0 = t1 - (unsigned long long)((unsigned)t1 - ((volatile uint32_t*)(smem + CTL_OFF))[1]);  // from the row's arrival
     if (lane == 0) cyc[wave == 2 ? 3 : wave] = t1 - t0;
     __syncthreads();
     for (int x = threadIdx.x; x < NROWS * ROWB / 4; x += blockDim.x) rows_out[x] = ((float*)smem)[x];
@@ -203,17 +212,24 @@ static float ref_dot(const float* p, const float* q) {
     return s[0];
 }
 
-// ubench3          : every mode at n = NSTEP, NSTEP - 1, 1, 2, 50, 51
+// ubench3          : every mode at n = NSTEP, NSTEP - 1, 1, 2, 50, 51; then mode 8, the general loop, at n = 1..33 and 64
+//                    (forwarded-q flags and p rows recurring at distance two in its data)
 // ubench3 chain    : the chain wave's loop only (modes 0 and 1) at those n and at every n = 1..33 -- every exit of a
 //                    tail of up to eight steps and every hand-over from a steady body of 8 or 16, twice over (built with
 //                    -DMFSGD_CHAIN_STEADY=8|16, -DMFSGD_PAD_CHAIN_STEADY=0|2|4|6, -DMFSGD_PAD_CHAIN_TAIL=0|2|4|6 and
 //                    -DMFSGD_CHAIN_PAIRS=1|2|4: tools/build_ubench.sh); one line per n, the short runs as one line
+// ubench3 loops    : the one-wave loops only -- mode 3, the run loop, at every even n = 2..34 and the longest, then mode 8
 int main(int argc, char** argv) {
+    const bool loops_only = argc > 1 && strcmp(argv[1], "loops") == 0;
     const bool chain_only = argc > 1 && strcmp(argv[1], "chain") == 0;
     const bool lone_only = argc > 1 && strcmp(argv[1], "lone") == 0;
     std::vector<int> lengths = {NSTEP, NSTEP - 1, 1, 2, 50, 51};
     if (chain_only || lone_only)
         for (int n = 3; n <= 33; ++n) lengths.push_back(n);
+    if (loops_only) {
+        lengths = {NSTEP};
+        for (int n = 2; n <= 34; n += 2) lengths.push_back(n);
+    }
     const int KP = 4 * LG;
     std::vector<float> rows((size_t)NROWS * KP), ref;
     uint32_t seed = 12345;
@@ -320,7 +336,7 @@ int main(int argc, char** argv) {
     for (auto& v : res) v.resize(NSTEP + 1);
     for (int mode = 0; mode < (chain_only ? 2 : 8); ++mode)
         for (int n : lengths) {
-            if ((mode == 3 && (n & 1)) || (mode == 4 && n < 8)) continue;
+            if ((mode == 3 && (n & 1)) || (mode == 4 && n < 8) || (loops_only && mode != 3)) continue;
             if (lone_only ? (mode != 0 && mode < 6) : (!chain_only && mode >= 6 && n > 2 && n < 50)) continue;
             (void)hipMemcpy(d_ent, (mode == 2 ? ent2 : ent).data(), ent.size() * 4, hipMemcpyHostToDevice);
             unsigned long long best[2] = {~0ull, ~0ull}, h[4];
@@ -369,6 +385,69 @@ int main(int argc, char** argv) {
                    mode == 1 ? "chain alone" : mode == 6 ? "lone-tile start: q from its mailbox in registers, chain + helper, from arrival" : mode == 7 ? "lone-tile start, p row of step 0 updated in front of the run" : mode == 4 ? "cut run: chain + two helpers" : mode == 2 ? "helper alone" : mode == 3 ? "one-wave run loop" : mode == 5 ? "chain + helper, p row of step 0 updated in front of the run" : "chain + helper", n, (double)best[0] / n, (double)best[1] / n,
                    mode == 1 ? "" : (bad ? "  MISMATCH" : "  bit-exact"));
         }
+    if (!chain_only && !lone_only) {
+        // mode 8: the general loop.  Group g keeps three q rows of its own (the pool's last 3 GS rows) and visits them
+        // 0 0 1 0 2 0 0 1 ...: the second of two visits in a row is flagged as forwarded (bit 31 of its slots word), the
+        // others recur at distance two or three; its p rows are fresh ones, every third step the row of two steps before.
+        const int NG = 64;
+        static_assert((NG + 1) * GS + 3 * GS <= NSTEP, "general mode: rows");
+        auto prow_g = [&](int t, int g) { return (t % 3 == 2 ? t - 2 : t) * GS + g; };
+        auto qrow_g = [&](int t, int g) { const int pat[5] = {0, 0, 1, 0, 2}; return NSTEP - 1 - (g * 3 + pat[t % 5]); };
+        std::vector<uint32_t> gen((NSTEP + 2) * GS * 4, 0);
+        std::vector<float> rg((size_t)NG * GS);
+        int flags = 0, dist2 = 0;
+        for (int t = 0; t < NSTEP + 2; ++t)
+            for (int g = 0; g < GS; ++g) {
+                uint32_t* e = &gen[(size_t)(t * GS + g) * 4];
+                if (t < NG) {
+                    const float r = rg[(size_t)t * GS + g] = 1.0f + 4.0f * rnd(), lrr = lr * r;
+                    const bool fwd = t > 0 && qrow_g(t, g) == qrow_g(t - 1, g);
+                    e[0] = (uint32_t)(prow_g(t, g) * LG) | ((uint32_t)(qrow_g(t, g) * LG) << 16) | (fwd ? 0x80000000u : 0u);
+                    memcpy(&e[1], &r, 4);
+                    memcpy(&e[2], &lrr, 4);
+                    memcpy(&e[3], &c, 4);
+                    flags += fwd;
+                    dist2 += t >= 2 && prow_g(t, g) == prow_g(t - 2, g);
+                } else {
+                    e[0] = (uint32_t)((NSTEP + 1) * LG) | ((uint32_t)((NSTEP + 1) * LG) << 16);
+                }
+            }
+        (void)hipMemcpy(d_run, gen.data(), gen.size() * 4, hipMemcpyHostToDevice);
+        std::vector<int> glen;
+        for (int n = 1; n <= 33; ++n) glen.push_back(n);
+        glen.push_back(NG);
+        int exact = 0, wrong = 0;
+        std::vector<double> cyc_n(NG + 1, 0.0);
+        for (int n : glen) {
+            unsigned long long best = ~0ull, h[4];
+            for (int rep = 0; rep < 5; ++rep) {
+                (void)hipMemset(d_cyc, 0, 32);
+                hipLaunchKernelGGL(k, dim3(1), dim3(128), lds, 0, d_in, d_ent, d_out, d_ent_out, d_cyc, n, lr, c, 8, d_run, prow[0], d_mb, d_abw,
+                                   d_post, want_tag);
+                (void)hipMemcpy(h, d_cyc, 32, hipMemcpyDeviceToHost);
+                best = h[0] < best ? h[0] : best;
+            }
+            std::vector<float> out(rows.size()), r2 = rows;
+            (void)hipMemcpy(out.data(), d_out, out.size() * 4, hipMemcpyDeviceToHost);
+            for (int t = 0; t < n; ++t)
+                for (int g = 0; g < GS; ++g) {
+                    float *p = &r2[(size_t)prow_g(t, g) * KP], *qq = &r2[(size_t)qrow_g(t, g) * KP];
+                    const float dot = ref_dot(p, qq), s = fmaf(-lr, dot, lr * rg[(size_t)t * GS + g]);
+                    for (int f = 0; f < KP; ++f) {
+                        const float po = p[f], qo = qq[f];
+                        p[f] = fmaf(s, qo, c * po);
+                        qq[f] = fmaf(s, po, c * qo);
+                    }
+                }
+            (memcmp(out.data(), r2.data(), out.size() * 4) != 0 ? wrong : exact)++;
+            cyc_n[n] = (double)best;
+        }
+        printf("L=%d mode=8 (one-wave general loop, pad %d; %d forwarded-q flags, %d p rows at distance two in the data) n=1..33 and %d: %d bit-exact, %d MISMATCH\n",
+               LG, mfsgd_pad_gen(LG), flags, dist2, NG, exact, wrong);
+        printf("L=%d mode=8 n=%d: %.1f cycles/step; cycles per run at n = 1 2 3 4 5 8 16 33:", LG, NG, cyc_n[NG] / NG);
+        for (int n : {1, 2, 3, 4, 5, 8, 16, 33}) printf(" %.0f", cyc_n[n]);
+        printf("  (step of a long run: %.1f)\n", (cyc_n[NG] - cyc_n[32]) / (NG - 32));
+    }
     if (chain_only) {
         // pair = the later of the two waves of mode 0; alone = mode 1; the short runs as one line (cycles per RUN, alone)
         int exact = 0, wrong = 0;

@@ -23,8 +23,8 @@ constexpr int PASSES = 64;
 // highest byte touched is 1024 + 4 * 6 + 3.
 #define UB5_CLOBBERS                                                                                                    \
     "memory", "scc", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", \
-        "v113", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v128", "v130", "v131", \
-        "v132", "v138", "v139"
+        "v113", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127", "v128", \
+        "v130", "v131", "v132", "v138", "v139", "v140", "v141", "v142", "v143", "v144", "v145"
 #define UB5_KERNEL(NAME, BODY)                                                                                          \
     __global__ void __launch_bounds__(64) NAME(unsigned long long* cyc, float c) {                                      \
         __shared__ __attribute__((aligned(16))) unsigned char smem[4096];                                               \
@@ -97,6 +97,35 @@ UB5_KERNEL(k_rd2_mul, DPP RD2 MUL_A)
 UB5_KERNEL(k_mad_mul, DPP MAD_A MUL_A)
 UB5_KERNEL(k_mad_pkmul, DPP MAD_A PKMUL_A)
 
+// Groups of LDS instructions in the gaps of a whole step (four links, two slots each, as the run and general loops fill
+// them): the same instructions in one gap, in two and in three.  Every body below is four links long, so the printed
+// figure is per STEP, beyond four links of {s_nop 0, s_nop 0} with the same VALU fillers and no LDS instruction.
+#define RD32 "ds_read_b32 v118, v138 offset:32\n\t"
+#define RD32B "ds_read_b32 v119, v138 offset:24\n\t"
+#define RD64 "ds_read_b64 v[118:119], v138 offset:24\n\t"
+#define RD128B "ds_read_b128 v[140:143], v139\n\t"
+#define WR128 "ds_write_b128 v113, v[104:107]\n\t"
+#define PKMUL_C "v_pk_mul_f32 v[126:127], v[104:105], %[c2]\n\t"
+#define PKMUL_D "v_pk_mul_f32 v[144:145], v[106:107], %[c2]\n\t"
+// run loop: no LDS; three groups of reads as it was ({p}, {}, {slots, entry}); the three reads in the first gap
+UB5_KERNEL(k_step_run_none, DPP PKMUL_A NOP0 DPP PKMUL_B PKMUL_C DPP PKMUL_D NOP0 DPP NOP0 NOP0)
+UB5_KERNEL(k_step_run_old, DPP RD128 PKMUL_A DPP PKMUL_B PKMUL_C DPP RD32 RD64 DPP PKMUL_D NOP0)
+UB5_KERNEL(k_step_run_new, DPP RD128 RD32 RD64 DPP PKMUL_B PKMUL_C DPP PKMUL_A PKMUL_D DPP NOP0 NOP0)
+UB5_KERNEL(k_step_run_gap2, DPP PKMUL_A PKMUL_D DPP RD128 RD32 RD64 DPP PKMUL_B PKMUL_C DPP NOP0 NOP0)
+// general loop: reads {p}, {q}, {}, {slots, lr*r} as it was; all four in the first gap; two gaps of two
+UB5_KERNEL(k_step_gen_none, DPP MAD_A PKMUL_A DPP PKMUL_B PKMUL_C DPP PKMUL_D NOP0 DPP NOP0 NOP0)
+UB5_KERNEL(k_step_gen_old, DPP RD128 MAD_A DPP RD128B PKMUL_A DPP PKMUL_B PKMUL_C DPP PKMUL_D RD32 RD32B)
+UB5_KERNEL(k_step_gen_four, DPP RD128 RD128B RD32 RD32B DPP PKMUL_A PKMUL_B DPP PKMUL_C PKMUL_D DPP MAD_A NOP0)
+UB5_KERNEL(k_step_gen_2x2, DPP RD128 RD128B DPP RD32 RD32B DPP PKMUL_A PKMUL_B DPP PKMUL_C PKMUL_D MAD_A)
+// the chain wave's post: {read, read} in a gap and the ds_write2_b32 behind the last link; the write in that gap too
+UB5_KERNEL(k_step_post_own, DPP RD128 RD2 DPP PKMUL_A NOP0 DPP PKMUL_B NOP0 DPP NOP0 NOP0 PKMUL_C PKMUL_D WR2)
+UB5_KERNEL(k_step_post_gap, DPP RD128 RD2 WR2 DPP PKMUL_A NOP0 DPP PKMUL_B NOP0 DPP NOP0 NOP0 PKMUL_C PKMUL_D)
+UB5_KERNEL(k_step_post_none, DPP PKMUL_A NOP0 DPP PKMUL_B NOP0 DPP NOP0 NOP0 DPP NOP0 NOP0 PKMUL_C PKMUL_D)
+// the helper's write of p' and read of the next row outside any gap: apart (VALU between them), adjacent
+UB5_KERNEL(k_step_wr_rd_apart, DPP NOP0 NOP0 PKMUL_A PKMUL_B WR128 MAD_B PKMUL_C RD128B PKMUL_D)
+UB5_KERNEL(k_step_wr_rd_adj, DPP NOP0 NOP0 PKMUL_A PKMUL_B MAD_B PKMUL_C WR128 RD128B PKMUL_D)
+UB5_KERNEL(k_step_wr_rd_none, DPP NOP0 NOP0 PKMUL_A PKMUL_B MAD_B PKMUL_C PKMUL_D)
+
 // dependent latency, three operations per link
 UB5_KERNEL(k_lat_pk, "v_pk_fma_f32 v[100:101], v[104:105], v[116:117], v[100:101]\n\t"
                      "v_pk_mul_f32 v[100:101], v[100:101], v[104:105]\n\t"
@@ -156,6 +185,19 @@ int main() {
            "{v_mad_u32_u16, v_mul_f32} %+.2f  {v_mad_u32_u16, v_pk_mul_f32} %+.2f\n",
            run(k_rd128_mul, d_cyc) - base, run(k_rd128_pkmul, d_cyc) - base, run(k_rd2_mul, d_cyc) - base, run(k_mad_mul, d_cyc) - base,
            run(k_mad_pkmul, d_cyc) - base);
+    {
+        const double run0 = run(k_step_run_none, d_cyc), gen0 = run(k_step_gen_none, d_cyc), post0 = run(k_step_post_none, d_cyc),
+                     wr0 = run(k_step_wr_rd_none, d_cyc);
+        printf("groups of LDS instructions in a step of four links, cycles per step beyond the same step without them:\n");
+        printf("  run loop      {p} {} {slots, entry} (three gaps, as it was) %+.2f   {p, slots, entry} in the first gap %+.2f   in the second gap %+.2f\n",
+               run(k_step_run_old, d_cyc) - run0, run(k_step_run_new, d_cyc) - run0, run(k_step_run_gap2, d_cyc) - run0);
+        printf("  general loop  {p} {q} {} {slots, lr*r} (as it was) %+.2f   {p, q, slots, lr*r} in the first gap %+.2f   {p, q} {slots, lr*r} %+.2f\n",
+               run(k_step_gen_old, d_cyc) - gen0, run(k_step_gen_four, d_cyc) - gen0, run(k_step_gen_2x2, d_cyc) - gen0);
+        printf("  chain post    {read, read} and ds_write2_b32 behind the step %+.2f   {read, read, write2} in one gap %+.2f\n",
+               run(k_step_post_own, d_cyc) - post0, run(k_step_post_gap, d_cyc) - post0);
+        printf("  helper        ds_write_b128, VALU, ds_read_b128 outside a gap %+.2f   adjacent %+.2f\n", run(k_step_wr_rd_apart, d_cyc) - wr0,
+               run(k_step_wr_rd_adj, d_cyc) - wr0);
+    }
     printf("dependent latency, cycles per operation: pk_fma -> pk_mul -> pk_fma %.2f, fma -> mul -> fma %.2f, the two halves as two interleaved chains %.2f per pair\n",
            run(k_lat_pk, d_cyc) / 3, run(k_lat_plain, d_cyc) / 3, run(k_lat_plain2, d_cyc) / 3);
     printf("chunk dot, cycles per link: pk_mul, pk_fma, add %.2f; mul, mul, fma, fma, add %.2f\n", run(k_dot_pk, d_cyc), run(k_dot_plain, d_cyc));
