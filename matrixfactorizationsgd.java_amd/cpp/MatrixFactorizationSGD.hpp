@@ -36,6 +36,9 @@ class MatrixFactorizationSGD {
     MatrixFactorizationSGD(const MatrixFactorizationSGD&) = delete;
     MatrixFactorizationSGD& operator=(const MatrixFactorizationSGD&) = delete;
 
+    // what every top-N call returns: {index, scores}, row-major rows x topN
+    using TopN = std::pair<std::vector<int32_t>, std::vector<float>>;
+
     // double[] train(int[] u, int[] i, float[] r, int epochs): RMSE after each epoch
     std::vector<double> train(const std::vector<int32_t>& u, const std::vector<int32_t>& i, const std::vector<float>& r,
                               int epochs) {
@@ -64,23 +67,21 @@ class MatrixFactorizationSGD {
     }
 
     // int[][] recommend(int[] users, int topN): best items per user, best first (row-major users x topN)
-    std::pair<std::vector<int32_t>, std::vector<float>> recommend(const std::vector<int32_t>& users, int topn) {
-        std::vector<int32_t> items(users.size() * (size_t)topn);
-        std::vector<float> scores(users.size() * (size_t)topn);
-        check(mfsgd_recommend(h_, users.data(), (int32_t)users.size(), topn, items.data(), scores.data()));
-        return {std::move(items), std::move(scores)};
+    TopN recommend(const std::vector<int32_t>& users, int topn) {
+        TopN out = top_n(users.size(), topn);
+        check(mfsgd_recommend(h_, users.data(), (int32_t)users.size(), topn, out.first.data(), out.second.data()));
+        return out;
     }
     // int[][] recommend(int[] users, int topN, int[] exclU, int[] exclI): as above, never an item (exclU[x], exclI[x]) names
     // for that user; rows short of eligible items end in item -1, score NaN
-    std::pair<std::vector<int32_t>, std::vector<float>> recommend(const std::vector<int32_t>& users, int topn,
-                                                                  const std::vector<int32_t>& excl_u,
-                                                                  const std::vector<int32_t>& excl_i) {
+    TopN recommend(const std::vector<int32_t>& users, int topn,
+                   const std::vector<int32_t>& excl_u,
+                   const std::vector<int32_t>& excl_i) {
         if (excl_u.size() != excl_i.size()) throw std::invalid_argument("length mismatch");
-        std::vector<int32_t> items(users.size() * (size_t)topn);
-        std::vector<float> scores(users.size() * (size_t)topn);
+        TopN out = top_n(users.size(), topn);
         check(mfsgd_recommend_excluding(h_, users.data(), (int32_t)users.size(), topn, excl_u.data(), excl_i.data(),
-                                        (int64_t)excl_u.size(), items.data(), scores.data()));
-        return {std::move(items), std::move(scores)};
+                                        (int64_t)excl_u.size(), out.first.data(), out.second.data()));
+        return out;
     }
 
     // float[] foldIn(long[] rowPtr, int[] items, float[] ratings, int epochs[, float[] init]): rows (n_new x k, row-major)
@@ -124,76 +125,70 @@ class MatrixFactorizationSGD {
     int items() const { return items_; }
     // int[][] recommendRows(float[] rows, int topN, int[] exclRow, int[] exclItem): recommend for rows (n x k) that are
     // not in the model, such as foldIn's; exclRow indexes rows
-    std::pair<std::vector<int32_t>, std::vector<float>> recommendRows(const std::vector<float>& rows, int topn,
-                                                                      const std::vector<int32_t>& excl_row = {},
-                                                                      const std::vector<int32_t>& excl_item = {}) {
+    TopN recommendRows(const std::vector<float>& rows, int topn,
+                       const std::vector<int32_t>& excl_row = {},
+                       const std::vector<int32_t>& excl_item = {}) {
         if (excl_row.size() != excl_item.size() || rows.size() % (size_t)k_ != 0) throw std::invalid_argument("length mismatch");
         const size_t n = rows.size() / (size_t)k_;
-        std::vector<int32_t> items(n * (size_t)topn);
-        std::vector<float> scores(n * (size_t)topn);
+        TopN out = top_n(n, topn);
         check(mfsgd_recommend_rows(h_, rows.data(), (int32_t)n, topn, excl_row.data(), excl_item.data(),
-                                   (int64_t)excl_row.size(), items.data(), scores.data()));
-        return {std::move(items), std::move(scores)};
+                                   (int64_t)excl_row.size(), out.first.data(), out.second.data()));
+        return out;
     }
     // int[][] recommendAmong(int[] users, int topN, long[] candPtr, int[] candItems, int[] exclU, int[] exclI): the best
     // topN of each row's candidates only -- candPtr empty: one list, candItems, for every row; otherwise CSR over the rows
     // of users (users.length + 1 offsets).  Lists may be unsorted and repeat items; rows short of candidates are padded
-    std::pair<std::vector<int32_t>, std::vector<float>> recommendAmong(const std::vector<int32_t>& users, int topn,
-                                                                       const std::vector<int64_t>& cand_ptr,
-                                                                       const std::vector<int32_t>& cand_items,
-                                                                       const std::vector<int32_t>& excl_u = {},
-                                                                       const std::vector<int32_t>& excl_i = {}) {
+    TopN recommendAmong(const std::vector<int32_t>& users, int topn,
+                        const std::vector<int64_t>& cand_ptr,
+                        const std::vector<int32_t>& cand_items,
+                        const std::vector<int32_t>& excl_u = {},
+                        const std::vector<int32_t>& excl_i = {}) {
         if (excl_u.size() != excl_i.size() || (!cand_ptr.empty() && cand_ptr.size() != users.size() + 1))
             throw std::invalid_argument("length mismatch");
-        std::vector<int32_t> items(users.size() * (size_t)topn);
-        std::vector<float> scores(users.size() * (size_t)topn);
+        TopN out = top_n(users.size(), topn);
         check(mfsgd_recommend_among(h_, users.data(), (int32_t)users.size(), topn, cand_ptr.empty() ? nullptr : cand_ptr.data(),
                                     cand_items.data(), (int64_t)cand_items.size(), excl_u.data(), excl_i.data(),
-                                    (int64_t)excl_u.size(), items.data(), scores.data()));
-        return {std::move(items), std::move(scores)};
+                                    (int64_t)excl_u.size(), out.first.data(), out.second.data()));
+        return out;
     }
     // int[][] recommendRowsAmong(float[] rows, int topN, long[] candPtr, int[] candItems, int[] exclRow, int[] exclItem):
     // the same for rows (n x k) that are not in the model; candPtr and exclRow index rows
-    std::pair<std::vector<int32_t>, std::vector<float>> recommendRowsAmong(const std::vector<float>& rows, int topn,
-                                                                           const std::vector<int64_t>& cand_ptr,
-                                                                           const std::vector<int32_t>& cand_items,
-                                                                           const std::vector<int32_t>& excl_row = {},
-                                                                           const std::vector<int32_t>& excl_item = {}) {
+    TopN recommendRowsAmong(const std::vector<float>& rows, int topn,
+                            const std::vector<int64_t>& cand_ptr,
+                            const std::vector<int32_t>& cand_items,
+                            const std::vector<int32_t>& excl_row = {},
+                            const std::vector<int32_t>& excl_item = {}) {
         if (excl_row.size() != excl_item.size() || rows.size() % (size_t)k_ != 0) throw std::invalid_argument("length mismatch");
         const size_t n = rows.size() / (size_t)k_;
         if (!cand_ptr.empty() && cand_ptr.size() != n + 1) throw std::invalid_argument("length mismatch");
-        std::vector<int32_t> items(n * (size_t)topn);
-        std::vector<float> scores(n * (size_t)topn);
+        TopN out = top_n(n, topn);
         check(mfsgd_recommend_rows_among(h_, rows.data(), (int32_t)n, topn, cand_ptr.empty() ? nullptr : cand_ptr.data(),
                                          cand_items.data(), (int64_t)cand_items.size(), excl_row.data(), excl_item.data(),
-                                         (int64_t)excl_row.size(), items.data(), scores.data()));
-        return {std::move(items), std::move(scores)};
+                                         (int64_t)excl_row.size(), out.first.data(), out.second.data()));
+        return out;
     }
 
     // int[][] similarItems(int[] items, int topN) / similarUsers(int[] users, int topN): per query the topN other rows of
     // Q / of P with the largest cosine, best first, never the query itself (row-major queries x topN, with the scores)
-    std::pair<std::vector<int32_t>, std::vector<float>> similarItems(const std::vector<int32_t>& items, int topn) {
-        std::vector<int32_t> index(items.size() * (size_t)topn);
-        std::vector<float> scores(items.size() * (size_t)topn);
-        check(mfsgd_similar_items(h_, items.data(), (int32_t)items.size(), topn, index.data(), scores.data()));
-        return {std::move(index), std::move(scores)};
+    TopN similarItems(const std::vector<int32_t>& items, int topn) {
+        TopN out = top_n(items.size(), topn);
+        check(mfsgd_similar_items(h_, items.data(), (int32_t)items.size(), topn, out.first.data(), out.second.data()));
+        return out;
     }
-    std::pair<std::vector<int32_t>, std::vector<float>> similarUsers(const std::vector<int32_t>& users, int topn) {
-        std::vector<int32_t> index(users.size() * (size_t)topn);
-        std::vector<float> scores(users.size() * (size_t)topn);
-        check(mfsgd_similar_users(h_, users.data(), (int32_t)users.size(), topn, index.data(), scores.data()));
-        return {std::move(index), std::move(scores)};
+    TopN similarUsers(const std::vector<int32_t>& users, int topn) {
+        TopN out = top_n(users.size(), topn);
+        check(mfsgd_similar_users(h_, users.data(), (int32_t)users.size(), topn, out.first.data(), out.second.data()));
+        return out;
     }
     // int[][] similarRows(float[] rows, int topN, int side): the same for query vectors (n x k) that are not in the model,
     // against the rows of Q (MFSGD_SIDE_ITEMS) or P (MFSGD_SIDE_USERS); nothing is excluded
-    std::pair<std::vector<int32_t>, std::vector<float>> similarRows(const std::vector<float>& rows, int topn,
-                                                                    int side = MFSGD_SIDE_ITEMS) {
+    TopN similarRows(const std::vector<float>& rows, int topn,
+                     int side = MFSGD_SIDE_ITEMS) {
         if (rows.size() % (size_t)k_ != 0) throw std::invalid_argument("length mismatch");
         const size_t n = rows.size() / (size_t)k_;
-        std::vector<int32_t> index(n * (size_t)topn);
-        std::vector<float> scores(n * (size_t)topn);
-        check(mfsgd_similar_rows(h_, side, rows.data(), (int32_t)n, topn, index.data(), scores.data()));
-        return {std::move(index), std::move(scores)};
+        TopN out = top_n(n, topn);
+        check(mfsgd_similar_rows(h_, side, rows.data(), (int32_t)n, topn, out.first.data(), out.second.data()));
+        return out;
     }
     // float[] rowInvNorms(int side): 1 / sqrt(dot(row, row)) of every row of P or Q, 0 for a zero row
     std::vector<float> rowInvNorms(int side) {
@@ -269,23 +264,21 @@ class MatrixFactorizationSGD {
         return {std::move(ptr), std::move(items)};
     }
     // int[][] recommendUnseen(int[] users, int topN): recommend(users, topN, exclU, exclI) with the index's pairs
-    std::pair<std::vector<int32_t>, std::vector<float>> recommendUnseen(const std::vector<int32_t>& users, int topn) {
-        std::vector<int32_t> items(users.size() * (size_t)topn);
-        std::vector<float> scores(users.size() * (size_t)topn);
-        check(mfsgd_recommend_unseen(h_, users.data(), (int32_t)users.size(), topn, items.data(), scores.data()));
-        return {std::move(items), std::move(scores)};
+    TopN recommendUnseen(const std::vector<int32_t>& users, int topn) {
+        TopN out = top_n(users.size(), topn);
+        check(mfsgd_recommend_unseen(h_, users.data(), (int32_t)users.size(), topn, out.first.data(), out.second.data()));
+        return out;
     }
     // int[][] recommendUnseenAmong(int[] users, int topN, long[] candPtr, int[] candItems): recommendAmong likewise
-    std::pair<std::vector<int32_t>, std::vector<float>> recommendUnseenAmong(const std::vector<int32_t>& users, int topn,
-                                                                             const std::vector<int64_t>& cand_ptr,
-                                                                             const std::vector<int32_t>& cand_items) {
+    TopN recommendUnseenAmong(const std::vector<int32_t>& users, int topn,
+                              const std::vector<int64_t>& cand_ptr,
+                              const std::vector<int32_t>& cand_items) {
         if (!cand_ptr.empty() && cand_ptr.size() != users.size() + 1) throw std::invalid_argument("length mismatch");
-        std::vector<int32_t> items(users.size() * (size_t)topn);
-        std::vector<float> scores(users.size() * (size_t)topn);
+        TopN out = top_n(users.size(), topn);
         check(mfsgd_recommend_unseen_among(h_, users.data(), (int32_t)users.size(), topn,
                                            cand_ptr.empty() ? nullptr : cand_ptr.data(), cand_items.data(),
-                                           (int64_t)cand_items.size(), items.data(), scores.data()));
-        return {std::move(items), std::move(scores)};
+                                           (int64_t)cand_items.size(), out.first.data(), out.second.data()));
+        return out;
     }
     // int[] rankItemsUnseen(int[] u, int[] i) / RankingMetrics evaluateRankingUnseen(int[] u, int[] i, int topN): rankItems
     // and evaluateRanking with the index's pairs not competing
@@ -511,6 +504,10 @@ class MatrixFactorizationSGD {
         check(call(h_, n, rows ? rows->data() : nullptr, seed, &first));
         count += n;
         return first;
+    }
+    // the two vectors of a top-N result, n x topn entries each, for the C call to fill
+    static TopN top_n(size_t n, int topn) {
+        return {std::vector<int32_t>(n * (size_t)topn), std::vector<float>(n * (size_t)topn)};
     }
     void check(int rc) {
         if (rc != MFSGD_OK) throw std::runtime_error(mfsgd_last_error(h_));

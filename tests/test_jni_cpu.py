@@ -1,9 +1,10 @@
 """The JNI shim, executed (tests/jni_fake.py): what needs no GPU.
 
 Signature conformance of all natives with the Java class; argument screening of every native, one broken argument at a
-time; status -> exception; no exception without a message; the natives that run on the host compared bit for bit with
-the Python surface on a twin handle; array handling; and the guard that every native the shim defines is named by a
-test here or in tests/test_jni_gpu.py.  Every comparison is of bytes."""
+time, and the class and text of every such refusal against a recorded file; status -> exception; no exception without
+a message; the natives that run on the host compared bit for bit with the Python surface on a twin handle; array
+handling; and the guard that every native the shim defines is named by a test here or in tests/test_jni_gpu.py.  Every
+comparison is of bytes."""
 import contextlib
 import ctypes as C
 import os
@@ -326,6 +327,62 @@ def test_a_bad_handle_is_refused_where_the_shim_needs_the_dimensions(jvm):
         if name == "nativeAppend":
             assert c.ret == -1
         c.close()
+
+
+BAD_HANDLE = ("nativeSetFactors", "nativeGetFactors", "nativeAppend", "nativeSetItemPartition", "nativeGetUserFactors",
+              "nativeRecommendRows", "nativeSimilarRows", "nativeRowInvNorms", "nativeRankItems", "nativeRankItemsRows",
+              "nativeEvaluateRanking")
+REFUSALS = os.path.join(ROOT, "tests", "golden", "jni_refusals.json")
+
+
+def refusal_cases(jvm, h):
+    """(key, native, arguments or None) of every refusal the screening tests above and the handle-zero test below
+    provoke, from the same tables: each non-nullable array null in turn and the two extra null cases, every entry of
+    BREAKS, the bad-handle natives, and every native with handle 0 (arguments None: a native that takes no array)."""
+    v, v0 = valid(h), valid(0)
+    for name in screened():
+        for p, x in v[name].items():
+            if isinstance(x, (Out, np.ndarray)) and p not in NULLABLE.get(name, ()):
+                yield f"{name} | {p} = null", name, dict(v[name], **{p: None})
+        for what, change in BREAKS[name]:
+            yield f"{name} | {what}", name, dict(v[name], **change)
+    yield "nativeRecommendUnseen | candPtr without candItems", "nativeRecommendUnseen", dict(v["nativeRecommendUnseen"], candItems=None)
+    yield "nativeSeenUpdate | markSeen: u = null", "nativeSeenUpdate", dict(v["nativeSeenUpdate"], op=1, u=None)
+    for name in BAD_HANDLE:
+        yield f"{name} | bad handle", name, v0[name]
+    for name in sorted(set(jvm.natives) - {"nativeCreate", "nativeDsgdUniqueId", "nativeDsgdPlan"}):
+        yield f"{name} | handle 0", name, v0.get(name)
+
+
+def recorded_refusals(jvm, h):
+    """{key: [exception class, message]} (null where nothing was thrown) of refusal_cases, as the shim answers now."""
+    out = {}
+    for key, name, args in refusal_cases(jvm, h):
+        assert key not in out, key
+        if args is None:
+            getattr(jvm, name)(*[0 if t in ("int", "long") else 0.5 for t, _ in jvm.natives[name][1]])
+            pend, viol = jvm.pending(), jvm.violations()
+        else:
+            c = Call(jvm, name, args)
+            pend, viol = c.pending, c.violations
+            c.close()
+        assert viol == [], (key, viol)
+        out[key] = list(pend) if pend else None
+    return out
+
+
+def test_every_refusal_is_the_recorded_one_class_and_text(jvm, model):
+    """The screening tests accept any text and one of two classes.  Here every refusal they provoke is compared with
+    tests/golden/jni_refusals.json, recorded from the shim before its natives were rebuilt on shared helpers
+    (tests/golden/make_jni_refusals.py writes it): the same cases, the same exception class, the same message, byte for
+    byte.  A text changed on purpose is re-recorded, and the diff of that file shows it."""
+    import json
+
+    with open(REFUSALS) as f:
+        want = json.load(f)
+    got = recorded_refusals(jvm, model)
+    assert set(got) == set(want), (sorted(set(got) - set(want)), sorted(set(want) - set(got)))
+    assert got == want, {k: (got[k], want[k]) for k in got if got[k] != want[k]}
 
 
 # ---- status -> exception ----------------------------------------------------------------------------------------------
