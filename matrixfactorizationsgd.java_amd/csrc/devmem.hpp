@@ -9,6 +9,7 @@
 #include <atomic>
 #include <cstddef>
 #include <cstdint>
+#include <utility>
 
 namespace mfsgd {
 
@@ -70,6 +71,27 @@ private:
     }
     void* p_ = nullptr;
     size_t bytes_ = 0;
+};
+
+// A DevBuf of elements of one type, so that a buffer's element type and its size are written once: data() is typed, and
+// alloc(n) and size() count elements, with DevBuf::alloc's semantics (a buffer that is large enough is kept, 0 elements
+// become 16 bytes; size() is what is there, so at least the n asked for).  The memory and the live-bytes accounting
+// are the DevBuf's, and one that another owner filled (the device packer's) is adopted whole.  Move-only, as its DevBuf.
+template <class T>
+class DevArray {
+public:
+    DevArray() = default;
+    DevArray(DevBuf&& b) noexcept : buf_(std::move(b)) {}
+
+    T* data() const { return buf_.template as<T>(); }
+    size_t size() const { return buf_.bytes() / sizeof(T); }
+    const DevBuf& buf() const { return buf_; }
+    explicit operator bool() const { return (bool)buf_; }
+    hipError_t alloc(size_t n) { return buf_.alloc(n * sizeof(T)); }
+    void reset() { buf_.reset(); }
+
+private:
+    DevBuf buf_;
 };
 
 // The owner of a stream or an event: empty until create(flags), destroyed with its owner, handed to the runtime as

@@ -44,6 +44,12 @@ int check_has_q(const mfsgd_handle* h, const char* call) {
     return MFSGD_OK;
 }
 
+int check_reads_factors(const mfsgd_handle* h, const char* call, bool reads_q) {
+    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, std::string(call) + ": single-partition handles only");
+    if (h->where == mfsgd_handle::Where::None) return fail(h, MFSGD_ERR_STATE, std::string(call) + ": factors not initialised");
+    return reads_q ? check_has_q(h, call) : MFSGD_OK;
+}
+
 static int usable_devices(int* count, std::string* why) {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
@@ -105,11 +111,10 @@ static void release_device_factors(mfsgd_handle* h) {
 // factors host <-> device -------------------------------------------------------
 // The staged rows of one side into a buffer of `capacity` rows (mfsgd_reserve_rows; the count where nothing is reserved,
 // and then this is upload()).
-static int upload_with_capacity(mfsgd_handle* h, DevBuf& b, const std::vector<float>& v, int32_t capacity) {
-    const size_t bytes = std::max(v.size(), (size_t)capacity * (size_t)h->geo.kp) * sizeof(float);
-    int rc = dev_alloc(h, b, bytes);
+static int upload_with_capacity(mfsgd_handle* h, DevArray<float>& b, const std::vector<float>& v, int32_t capacity) {
+    int rc = dev_alloc(h, b, std::max(v.size(), (size_t)capacity * (size_t)h->geo.kp));
     if (rc) return rc;
-    if (!v.empty()) HIPCHK(h, hipMemcpy(b.get(), v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (!v.empty()) HIPCHK(h, hipMemcpy(b.data(), v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
     return MFSGD_OK;
 }
 
@@ -146,12 +151,12 @@ static int seed_factors(mfsgd_handle* h, int64_t seed, int64_t u_offset, bool wi
     h->have_q = with_q;
     if (ensure_device(h) == MFSGD_OK) {
         int rc;
-        if ((rc = dev_alloc(h, h->dP, sizeof(float) * (size_t)h->user_capacity() * kp))) return rc;
-        HIPCHK(h, launch_init_rows(h->dP.as<float>(), h->cfg.n_users, k, kp, seed, (unsigned long long)u_offset * (unsigned long long)k,
+        if ((rc = dev_alloc(h, h->dP, (size_t)h->user_capacity() * kp))) return rc;
+        HIPCHK(h, launch_init_rows(h->dP.data(), h->cfg.n_users, k, kp, seed, (unsigned long long)u_offset * (unsigned long long)k,
                                    scale, h->stream));
         if (with_q) {
-            if ((rc = dev_alloc(h, h->dQ, sizeof(float) * (size_t)h->item_capacity() * kp))) return rc;
-            HIPCHK(h, launch_init_rows(h->dQ.as<float>(), h->cfg.n_items, k, kp, seed,
+            if ((rc = dev_alloc(h, h->dQ, (size_t)h->item_capacity() * kp))) return rc;
+            HIPCHK(h, launch_init_rows(h->dQ.data(), h->cfg.n_items, k, kp, seed,
                                        (unsigned long long)h->cfg.n_users * (unsigned long long)k, scale, h->stream));
         }
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -180,18 +185,19 @@ static int seed_factors(mfsgd_handle* h, int64_t seed, int64_t u_offset, bool wi
 // A buffer of new_rows rows that starts with the `rows` rows `old` holds: after a wait for the handle's stream, copied
 // device to device on it (asynchronous: the caller synchronises before it lets go of `old`).  Allocated before anything
 // is released, so a failure leaves the model as it was.
-static int grown_copy(mfsgd_handle* h, const char* prefix, const DevBuf& old, int64_t rows, int64_t new_rows, DevBuf& grown) {
+static int grown_copy(mfsgd_handle* h, const char* prefix, const DevArray<float>& old, int64_t rows, int64_t new_rows,
+                      DevArray<float>& grown) {
     auto bad = [h, prefix](hipError_t e) { return serve_fail(h, prefix, e); };
-    const size_t row_bytes = sizeof(float) * (size_t)h->geo.kp;
+    const size_t kp = (size_t)h->geo.kp;
     HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
-    if (const int rc = dev_alloc(h, grown, (size_t)new_rows * row_bytes)) return rc;
-    HIPCHK_OR(bad, hipMemcpyAsync(grown.get(), old.get(), (size_t)rows * row_bytes, hipMemcpyDeviceToDevice, h->stream));
+    if (const int rc = dev_alloc(h, grown, (size_t)new_rows * kp)) return rc;
+    HIPCHK_OR(bad, hipMemcpyAsync(grown.data(), old.data(), sizeof(float) * (size_t)rows * kp, hipMemcpyDeviceToDevice, h->stream));
     return MFSGD_OK;
 }
 
 // The grown buffer takes the place of the old one: nothing runs on either (the caller has synchronised), and the
 // training graphs, which hold the old pointer, go first.
-static void adopt(mfsgd_handle* h, DevBuf& buf, DevBuf& grown) {
+static void adopt(mfsgd_handle* h, DevArray<float>& buf, DevArray<float>& grown) {
     for (Part& p : h->parts) p.drop_graphs();
     buf = std::move(grown);
 }
@@ -211,12 +217,12 @@ static int write_new_rows(mfsgd_handle* h, const char* prefix, float* dst_base, 
         return MFSGD_OK;
     }
     const int64_t piece = std::min<int64_t>(n_new, std::max<int64_t>(1, kAppendStageFloats / k));
-    DevBuf stage;
-    if (const int rc = dev_alloc(h, stage, sizeof(float) * (size_t)piece * k)) return rc;
+    DevArray<float> stage;
+    if (const int rc = dev_alloc(h, stage, (size_t)piece * k)) return rc;
     for (int64_t x0 = 0; x0 < n_new; x0 += piece) {
         const int64_t nb = std::min<int64_t>(piece, n_new - x0);
-        HIPCHK_OR(bad, hipMemcpyAsync(stage.get(), rows + x0 * k, sizeof(float) * (size_t)nb * k, hipMemcpyHostToDevice, h->stream));
-        HIPCHK_OR(bad, launch_place_rows(dst + (size_t)x0 * kp, stage.as<const float>(), nb, k, kp, h->stream));
+        HIPCHK_OR(bad, copy_up(stage, rows + x0 * k, (size_t)nb * k, h->stream));
+        HIPCHK_OR(bad, launch_place_rows(dst + (size_t)x0 * kp, stage.data(), nb, k, kp, h->stream));
         HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // the staging buffer is reused, and freed on return
     }
     return MFSGD_OK;
@@ -230,9 +236,7 @@ static int append_rows(mfsgd_handle* h, bool items, const char* name, int32_t n_
     if (n_new < 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "n_new is negative");
     if ((int64_t)count + n_new > (int64_t)INT32_MAX)
         return fail(h, MFSGD_ERR_INVALID_ARG, call + "the number of " + (items ? "items" : "users") + " would exceed INT32_MAX");
-    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, call + "single-partition handles only");
-    if (h->where == mfsgd_handle::Where::None) return fail(h, MFSGD_ERR_STATE, call + "factors not initialised");
-    if (const int rc = check_has_q(h, name)) return rc;
+    if (const int rc = check_reads_factors(h, name)) return rc;
     if (first) *first = count;
     if (n_new == 0) return MFSGD_OK;
     const int k = h->cfg.k, kp = h->geo.kp;
@@ -240,7 +244,8 @@ static int append_rows(mfsgd_handle* h, bool items, const char* name, int32_t n_
     std::vector<int32_t>& last = items ? h->online_last_i : h->online_last_u;
     if (!last.empty()) last.reserve((size_t)need);  // (what can fail comes before anything changes)
     // users beyond the capacity: the per-user tables of the seen-item index grow with it, new before old as the rows do
-    DevBuf seen_off, seen_slot;
+    DevArray<long long> seen_off;
+    DevArray<int32_t> seen_slot;
     if (!items && need > h->user_capacity()) {
         if (const int rc = seen_grown_tables(h, call.c_str(), (int32_t)need, seen_off, seen_slot)) return rc;
     }
@@ -259,11 +264,11 @@ static int append_rows(mfsgd_handle* h, bool items, const char* name, int32_t n_
         int rc = ensure_device(h);
         if (rc) return rc;
         auto bad = [h, &call](hipError_t e) { return serve_fail(h, call.c_str(), e); };
-        DevBuf& buf = items ? h->dQ : h->dP;
-        DevBuf grown;  // beyond the capacity: to exactly what is needed (the capacity is at least the reserve)
+        DevArray<float>& buf = items ? h->dQ : h->dP;
+        DevArray<float> grown;  // beyond the capacity: to exactly what is needed (the capacity is at least the reserve)
         if (need > (items ? h->item_capacity() : h->user_capacity()) && (rc = grown_copy(h, call.c_str(), buf, count, need, grown)))
             return rc;
-        if ((rc = write_new_rows(h, call.c_str(), grown ? grown.as<float>() : buf.as<float>(), count, n_new, rows, seed))) return rc;
+        if ((rc = write_new_rows(h, call.c_str(), grown ? grown.data() : buf.data(), count, n_new, rows, seed))) return rc;
         HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
         if (grown) adopt(h, buf, grown);
     }
@@ -418,11 +423,11 @@ int mfsgd_get_factors(mfsgd_handle* h, float* P, float* Q) {
             HIPCHK(h, hipStreamSynchronize(h->stream));
             if (P) {
                 tp.resize((size_t)h->cfg.n_users * kp);
-                HIPCHK(h, hipMemcpy(tp.data(), h->dP.get(), tp.size() * sizeof(float), hipMemcpyDeviceToHost));
+                HIPCHK(h, hipMemcpy(tp.data(), h->dP.data(), tp.size() * sizeof(float), hipMemcpyDeviceToHost));
             }
             if (Q && h->n_parts == 1) {
                 tq.resize((size_t)h->cfg.n_items * kp);
-                HIPCHK(h, hipMemcpy(tq.data(), h->dQ.get(), tq.size() * sizeof(float), hipMemcpyDeviceToHost));
+                HIPCHK(h, hipMemcpy(tq.data(), h->dQ.data(), tq.size() * sizeof(float), hipMemcpyDeviceToHost));
             }
             sp = &tp;
             sq = &tq;
@@ -452,14 +457,15 @@ int mfsgd_reserve_rows(mfsgd_handle* h, int32_t user_capacity, int32_t item_capa
         // with the factors on the device a larger capacity is a larger buffer now; before that it is a number
         // factors_to_device and seed_factors read
         struct Side {
-            DevBuf& buf;
+            DevArray<float>& buf;
             int32_t count, capacity, want;
             int32_t& reserved;
         } sides[2] = {{h->dP, h->cfg.n_users, h->user_capacity(), user_capacity, h->reserved_users},
                       {h->dQ, h->cfg.n_items, h->item_capacity(), item_capacity, h->reserved_items}};
         for (Side& s : sides) {
             if (s.want <= s.capacity) continue;
-            DevBuf seen_off, seen_slot;  // the users' side: the tables of the seen-item index grow too
+            DevArray<long long> seen_off;  // the users' side: the tables of the seen-item index grow too
+            DevArray<int32_t> seen_slot;
             if (&s == &sides[0]) {
                 if (const int rc = seen_grown_tables(h, "reserve_rows: ", s.want, seen_off, seen_slot)) return rc;
                 if (seen_off) {
@@ -470,7 +476,7 @@ int mfsgd_reserve_rows(mfsgd_handle* h, int32_t user_capacity, int32_t item_capa
             if (h->where == mfsgd_handle::Where::Device && s.buf) {
                 int rc = ensure_device(h);
                 if (rc) return rc;
-                DevBuf grown;
+                DevArray<float> grown;
                 if ((rc = grown_copy(h, "reserve_rows: ", s.buf, s.count, s.want, grown))) return rc;
                 const hipError_t e = hipStreamSynchronize(h->stream);
                 if (e != hipSuccess) return serve_fail(h, "reserve_rows: ", e);

@@ -1,5 +1,5 @@
-// handle.hpp -- what the units of the C-ABI that see inside the handle share (handle.cpp, ratings.cpp, train.cpp,
-// serve.cpp): the handle, its partitions, the error channel, the guard with that channel, and the helpers that cross
+// handle.hpp -- what the units of the C-ABI that see inside the handle share (handle.cpp, seen_index.cpp, ratings.cpp,
+// train.cpp, online_update.cpp, serve.cpp): the handle, its partitions, the error channel, the guard with that channel, and the helpers that cross
 // units.  Internal: installed nowhere.  dsgd.cpp and io.cpp see the handle through include/mfsgd.h only, and take the
 // guard from guard.hpp.
 #pragma once
@@ -30,8 +30,13 @@ struct Part {
     // is built with the roles exchanged and the kernels get (Q, P) instead of (P, Q).
     bool swapped = false;
     bool on_device = false;
-    DevBuf d_cells, d_rows, d_subs, d_entries, d_sse_partial, d_sse_out;
-    DevBuf d_sync;        // persistent kernel: done[B] words (kDoneStride apart) + the abort word
+    DevArray<CellDesc> d_cells;
+    DevArray<uint32_t> d_rows;
+    DevArray<SubDesc> d_subs;
+    DevArray<Entry> d_entries;
+    DevBuf d_sse_partial;  // read under two types: the doubles of an SSE pass, or the u64 stamps of a diagnostic launch
+    DevArray<double> d_sse_out;
+    DevArray<unsigned> d_sync;  // persistent kernel: done[B] words (kDoneStride apart) + the abort word
     int persistent_np = -1;  // co-resident workgroups of the epoch kernel; 0 = use round launches; -1 = not probed
     // training graphs keyed by the (P, Q) pointers they were captured with (both are baked into the
     // kernel node; P changes when the factors are re-seeded, Q with every caller-owned block)
@@ -54,7 +59,9 @@ struct Validation {
     std::vector<int32_t> hu, hi;
     std::vector<float> hr;
     bool on_device = false;
-    DevBuf du, di, dr, d_sse;
+    DevArray<int32_t> du, di;
+    DevArray<float> dr;
+    DevArray<double> d_sse;
 };
 
 // The seen-item index of a handle (mfsgd_set_seen, mfsgd_mark_seen; seen.hip): what each user has already seen, one
@@ -70,16 +77,9 @@ struct Seen {
     bool present = false;
     int64_t n = 0;
     int32_t capacity = 0;
-    DevBuf off, items, slot;
-    RecommendExcl excl() const {
-        RecommendExcl ex;
-        if (n > 0) {
-            ex.slot = slot.as<const int32_t>();
-            ex.off = off.as<const long long>();
-            ex.items = items.as<const int32_t>();
-        }
-        return ex;
-    }
+    DevArray<long long> off;
+    DevArray<int32_t> items, slot;
+    RecommendExcl excl() const { return n > 0 ? RecommendExcl{slot.data(), off.data(), items.data()} : RecommendExcl{}; }
 };
 
 // Pairs (exclusions, candidates, seen pairs) per upload of a call that reads a caller's list: 32 MB of staging
@@ -96,7 +96,7 @@ constexpr int64_t kSampleChunk = (int64_t)1 << 22;
 inline size_t sync_bytes(const Part& p) {
     return ((size_t)p.sched.B * kDoneStride + 8) * sizeof(unsigned) + (size_t)p.sched.B * (size_t)p.sched.geo.L * 4 * 8;
 }
-inline unsigned* abort_word(const Part& p) { return p.d_sync.as<unsigned>() + (size_t)p.sched.B * kDoneStride + 4; }
+inline unsigned* abort_word(const Part& p) { return p.d_sync.data() + (size_t)p.sched.B * kDoneStride + 4; }
 
 }  // namespace mfsgd
 
@@ -115,7 +115,7 @@ struct mfsgd_handle {
     // factors: host staging (kp-padded rows) until the device copy is created
     enum class Where { None, Host, Device } where = Where::None;
     std::vector<float> hP, hQ;
-    mfsgd::DevBuf dP, dQ;
+    mfsgd::DevArray<float> dP, dQ;
     // The handle holds a Q of its own: single-partition handles after mfsgd_init_factors, mfsgd_set_factors or
     // mfsgd_load_factors.  Not after mfsgd_init_p_offset, which seeds P alone (check_has_q).
     bool have_q = false;
@@ -205,6 +205,9 @@ int check_part(const mfsgd_handle* h, int32_t part, const char* name);
 // "<call>: Q is not initialised: ..." on a single-partition handle whose factors were seeded by mfsgd_init_p_offset
 // (P alone).  Factors that were never initialised are the caller's own check, with the message it has always had.
 int check_has_q(const mfsgd_handle* h, const char* call);
+// What every call that reads the factors asks before it asks for a device, in this order: single-partition handles
+// only, factors not initialised, then (unless the call reads P alone: reads_q == false) check_has_q.
+int check_reads_factors(const mfsgd_handle* h, const char* call, bool reads_q = true);
 
 // handle.cpp
 int ensure_device(mfsgd_handle* h);
@@ -213,8 +216,8 @@ int factors_to_device(mfsgd_handle* h);
 // seen_index.cpp.  The tables of the seen-item index for a user capacity of new_cap, when it has tables and they are
 // smaller: new ones (off2, slot2) filled on the handle's stream from the old, which stay as they are (the caller
 // synchronises, then seen_adopt_tables).  Nothing to do leaves off2 empty.  `prefix` starts the message of a failure.
-int seen_grown_tables(mfsgd_handle* h, const char* prefix, int32_t new_cap, DevBuf& off2, DevBuf& slot2);
-void seen_adopt_tables(mfsgd_handle* h, int32_t new_cap, DevBuf& off2, DevBuf& slot2);
+int seen_grown_tables(mfsgd_handle* h, const char* prefix, int32_t new_cap, DevArray<long long>& off2, DevArray<int32_t>& slot2);
+void seen_adopt_tables(mfsgd_handle* h, int32_t new_cap, DevArray<long long>& off2, DevArray<int32_t>& slot2);
 // ... and the bodies of mfsgd_set_seen (merge == false) / mfsgd_mark_seen, `name` being the call's, and of mfsgd_get_seen
 int seen_update(mfsgd_handle* h, const char* name, bool merge, const int32_t* u, const int32_t* i, int64_t n);
 int seen_get(mfsgd_handle* h, const int32_t* users, int32_t n_users, int64_t* row_ptr, int32_t* items, int64_t items_capacity);
@@ -224,13 +227,38 @@ int seen_sample(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int
 void default_item_map(mfsgd_handle* h);
 int prepare_compute(mfsgd_handle* h);  // ratings present; factors and every partition's schedule on the device
 
+// The typed forms: n elements, and a whole vector (std::vector or PodVec) of them.
 template <class T>
-int upload(mfsgd_handle* h, DevBuf& b, const T& v) {
-    using E = std::remove_reference_t<decltype(*v.data())>;
-    int rc = dev_alloc(h, b, v.size() * sizeof(E));
-    if (rc) return rc;
-    if (!v.empty()) HIPCHK(h, hipMemcpy(b.get(), v.data(), v.size() * sizeof(E), hipMemcpyHostToDevice));
+int dev_alloc(mfsgd_handle* h, DevArray<T>& a, size_t n) {
+    const hipError_t e = a.alloc(n);
+    if (e != hipSuccess) return hip_fail(h, "hipMalloc(&b.p, bytes): ", e);  // (the text this failure has always had)
     return MFSGD_OK;
+}
+template <class T, class V>
+int upload(mfsgd_handle* h, DevArray<T>& a, const V& v) {
+    static_assert(std::is_same_v<std::remove_cv_t<std::remove_reference_t<decltype(*v.data())>>, T>, "element type");
+    int rc = dev_alloc(h, a, v.size());
+    if (rc) return rc;
+    if (!v.empty()) HIPCHK(h, hipMemcpy(a.data(), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return MFSGD_OK;
+}
+
+// n elements of the host's into / out of a typed array, from its element `at` on, asynchronously on st.  U is T, or the
+// other name of the same integer (int64_t and long long); more than the array was allocated for is refused.
+template <class T, class U>
+constexpr bool kSameElement = std::is_same_v<T, U> || (std::is_integral_v<T> && std::is_integral_v<U> && sizeof(T) == sizeof(U) &&
+                                                       std::is_signed_v<T> == std::is_signed_v<U>);
+template <class T, class U>
+hipError_t copy_up(const DevArray<T>& a, const U* src, size_t n, hipStream_t st, size_t at = 0) {
+    static_assert(kSameElement<T, U>, "element type");
+    if (at + n > a.size()) return hipErrorInvalidValue;
+    return hipMemcpyAsync(a.data() + at, src, n * sizeof(T), hipMemcpyHostToDevice, st);
+}
+template <class T, class U>
+hipError_t copy_down(U* dst, const DevArray<T>& a, size_t n, hipStream_t st, size_t at = 0) {
+    static_assert(kSameElement<T, U>, "element type");
+    if (at + n > a.size()) return hipErrorInvalidValue;
+    return hipMemcpyAsync(dst, a.data() + at, n * sizeof(T), hipMemcpyDeviceToHost, st);
 }
 
 }  // namespace mfsgd

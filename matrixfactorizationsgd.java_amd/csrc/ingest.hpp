@@ -60,14 +60,14 @@ struct PartsToEmit {
 };
 
 // What a successful emit() leaves on the device, owned: the schedule holds it until the first compute call moves rows,
-// entries and subs into the partition's own DevBufs (the order stays: only mfsgd_get_order reads it).
+// entries and subs into the partition's own arrays (the order stays: only mfsgd_get_order reads it).
 struct DevicePacked {
-    DevBuf rows;     // uint32 x n_rows (+4 padding words)
-    DevBuf entries;  // Entry x n_entries
-    DevBuf order;    // int64 x n
+    DevArray<uint32_t> rows;  // n_rows (+4 padding words)
+    DevArray<Entry> entries;  // n_entries
+    DevArray<int64_t> order;  // n
     // [r3] the sub-cell tables of all chunk descriptors (n_subs SubDesc records, the two padding records included): the
     // device wrote them and the training kernel reads them, so they need not come to the host and go back
-    DevBuf subs;
+    DevArray<SubDesc> subs;
     int64_t n_subs = 0;
 };
 

@@ -101,37 +101,42 @@ struct CosineScale {
     const float* ra = nullptr;
     const float* rb = nullptr;
 };
-// Fused score + select (one workgroup per user, nothing but the winners goes to memory) for
-// the (n_items, topn) recommend_is_fused() accepts ...
-bool recommend_is_fused(int32_t n_items, int32_t topn);
-hipError_t recommend_fused(int L, const float* P, const float* Q, const int32_t* d_users, int nb, int32_t n_items,
-                           int32_t topn, const RecommendExcl& ex, const CosineScale& cs, float* out_s, int32_t* out_i,
-                           hipStream_t st);
-// ... and for the rest: scores of nb users against every item, top `topn` of each into out_s / out_i.  `temp` is the
-// sorts' scratch: the caller's, so that one serves all batches; grown here when it is too small.
-hipError_t recommend_batch(int L, const float* P, const float* Q, const int32_t* d_users, int nb, int32_t n_items,
-                           int32_t topn, const RecommendExcl& ex, const CosineScale& cs, float* s_in, float* s_out,
-                           int32_t* id_in, int32_t* id_out, long long* d_off, DevBuf& temp, float* out_s, int32_t* out_i,
-                           hipStream_t st);
 // Top-N among candidates (mfsgd_recommend_among): request row b of a batch scores the sorted, distinct items
 // items[off[r] .. off[r + 1]) only, r = b (per_row == 1: a list per request row, off pointing at the batch's first
-// row) or 0 (per_row == 0: one list for every row).  The kernels are the ones above with the list in the place of
-// "every item"; the score is the dot.  `longest` is the longest list of the batch, `total` the sum of their lengths.
+// row) or 0 (per_row == 0: one list for every row).  The kernels are the same with the list in the place of "every
+// item"; the score is the dot.
 struct RecommendAmong {
     const long long* off = nullptr;
     const int32_t* items = nullptr;
     int per_row = 0;
 };
-// Fused for the (longest list, topn) this accepts: the limits of recommend_is_fused with the list in n_items' place ...
-bool recommend_among_is_fused(int64_t longest, int32_t topn);
-hipError_t recommend_among_fused(int L, const float* P, const float* Q, const int32_t* d_users, int nb,
-                                 const RecommendAmong& am, int32_t topn, const RecommendExcl& ex, float* out_s,
-                                 int32_t* out_i, hipStream_t st);
-// ... and the sort path for the rest, the segments being the lists: the buffers hold `total` scores / ids, d_off nb + 1.
-hipError_t recommend_among_batch(int L, const float* P, const float* Q, const int32_t* d_users, int nb,
-                                 const RecommendAmong& am, int64_t total, int64_t longest, int32_t topn,
-                                 const RecommendExcl& ex, float* s_in, float* s_out, int32_t* id_in, int32_t* id_out,
-                                 long long* d_off, DevBuf& temp, float* out_s, int32_t* out_i, hipStream_t st);
+// One batch of a top-N call: for each of the nb rows d_users[...] of P (device memory, kp-padded rows) the topn rows of
+// Q with the largest score, into out_s / out_i (nb x topn).  among == nullptr: every one of the n_items rows of Q is
+// scored; otherwise the lists (the dot only).  `longest` is the most one row scores, `total` what all rows score.
+struct TopnJob {
+    int L = 0, nb = 0;
+    const float *P = nullptr, *Q = nullptr;
+    const int32_t* d_users = nullptr;
+    int32_t n_items = 0, topn = 0;
+    RecommendExcl ex;
+    CosineScale cs;
+    const RecommendAmong* among = nullptr;
+    int64_t total = 0, longest = 0;
+    float* out_s = nullptr;
+    int32_t* out_i = nullptr;
+};
+// The sort path's buffers, the caller's (one set serves all batches): `total` scores or keys and ids in and out, nb + 1
+// offsets, and the sorts' scratch, grown when it is too small.
+struct TopnScratch {
+    float *s_in, *s_out;
+    int32_t *id_in, *id_out;
+    long long* d_off;
+    DevBuf* temp;
+};
+// Fused score + select (one workgroup per row, nothing but the winners goes to memory) for the (longest row, topn)
+// recommend_is_fused() accepts: recommend_topn without scratch.  With scratch it is the sort path, for the rest.
+bool recommend_is_fused(int64_t longest, int32_t topn);
+hipError_t recommend_topn(const TopnJob& job, const TopnScratch* scratch, hipStream_t st);
 // Building the candidate lists: keys[x0 + x] = row << 32 | items[x] for a chunk of n candidates that starts at position
 // x0 of the call's, row being the request row whose range of ptr (n_rows + 1 entries, CSR; nullptr: row 0) holds the
 // position.  recommend_excl_lists below then makes the lists of them, n_slots being the request rows (or 1).

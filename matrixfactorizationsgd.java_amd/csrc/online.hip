@@ -1,5 +1,5 @@
 // online.hip -- fresh ratings applied to the live P and Q in the order given ("Online updates"): the whole
-// canonical update of section 3, both halves, per rating.  The host has cut the list into dependency levels (train.cpp,
+// canonical update of section 3, both halves, per rating.  The host has cut the list into dependency levels (online_update.cpp,
 // online_levels_of): the ratings of one level share no user and no item, every rating's predecessors on either row lie
 // in a lower level, so the levels in ascending order, each in any order, give the bits of the sequential loop.  No block
 // schedule and no LDS image: one lane group of L lanes per rating, rows read from and written to global memory.

@@ -40,7 +40,7 @@ static int ensure_part_on_device(mfsgd_handle* h, Part& p) {
         return rc;
     }
     if (p.sched.device_packed) {
-        // the device packer left rows and entries where they are needed: the partition's DevBufs own them from here on
+        // the device packer left rows and entries where they are needed: the partition's arrays own them from here on
         p.d_rows = std::move(dev.rows);
         p.d_entries = std::move(dev.entries);
     } else {
@@ -48,9 +48,9 @@ static int ensure_part_on_device(mfsgd_handle* h, Part& p) {
         if ((rc = upload(h, p.d_entries, p.sched.entries))) return rc;
     }
     if ((rc = dev_alloc(h, p.d_sse_partial, sizeof(double) * p.sched.cells.size()))) return rc;
-    if ((rc = dev_alloc(h, p.d_sse_out, sizeof(double)))) return rc;
-    if ((rc = dev_alloc(h, p.d_sync, sync_bytes(p)))) return rc;
-    HIPCHK(h, hipMemset(p.d_sync.get(), 0, sync_bytes(p)));
+    if ((rc = dev_alloc(h, p.d_sse_out, 1))) return rc;
+    if ((rc = dev_alloc(h, p.d_sync, sync_bytes(p) / sizeof(unsigned)))) return rc;
+    HIPCHK(h, hipMemset(p.d_sync.data(), 0, sync_bytes(p)));
     HIPCHK(h, hipDeviceSynchronize());  // (memset is asynchronous; the first launch may be on another stream)
     p.on_device = true;
     return MFSGD_OK;
@@ -72,9 +72,9 @@ static int host_copies(const mfsgd_handle* h, const Part& cp, bool want_order, b
     Schedule& s = p.sched;
     if (!s.device_packed) return MFSGD_OK;
     // rows, entries and subs are the schedule's until the first compute call, the partition's after it
-    const DevBuf& d_rows = p.on_device ? p.d_rows : s.dev.rows;
-    const DevBuf& d_entries = p.on_device ? p.d_entries : s.dev.entries;
-    const DevBuf& d_subs = p.on_device ? p.d_subs : s.dev.subs;
+    const DevBuf& d_rows = p.on_device ? p.d_rows.buf() : s.dev.rows.buf();
+    const DevBuf& d_entries = p.on_device ? p.d_entries.buf() : s.dev.entries.buf();
+    const DevBuf& d_subs = p.on_device ? p.d_subs.buf() : s.dev.subs.buf();
     auto download = [](void* host, const DevBuf& dev, size_t bytes) {
         if (bytes == 0) return true;
         if (bytes <= dev.bytes() && hipMemcpy(host, dev.get(), bytes, hipMemcpyDeviceToHost) == hipSuccess) return true;
@@ -84,7 +84,7 @@ static int host_copies(const mfsgd_handle* h, const Part& cp, bool want_order, b
     try {
         if (want_order && s.order.empty() && s.nnz > 0) {
             s.order.resize_uninit((size_t)s.nnz);
-            if (!download(s.order.data(), s.dev.order, s.order.size() * sizeof(int64_t)))
+            if (!download(s.order.data(), s.dev.order.buf(), s.order.size() * sizeof(int64_t)))
                 return fail(h, MFSGD_ERR_HIP, "could not copy the canonical order from the device");
         }
         if (want_arrays && s.subs.empty() && s.n_sub_recs > 0 && d_subs) {

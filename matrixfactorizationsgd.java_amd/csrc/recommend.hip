@@ -565,66 +565,34 @@ __global__ void __launch_bounds__(256) excl_lists_kernel(const unsigned long lon
 
 }  // namespace
 
-bool recommend_is_fused(int32_t n_items, int32_t topn) {
-    const long long tiles = ((long long)n_items + kTopnTile - 1) / kTopnTile;
-    return topn <= kTopnFused && tiles * topn <= kTopnCand;
-}
-
-// Fused score + select: no score buffers at all.
-hipError_t recommend_fused(int L, const float* P, const float* Q, const int32_t* d_users, int nb, int32_t n_items,
-                           int32_t topn, const RecommendExcl& ex, const CosineScale& cs, float* out_s, int32_t* out_i,
-                           hipStream_t st) {
-    return with_L(L, [&](auto l) {
-        constexpr int LL = l();
-        auto go = [&](const auto& sc) {
-            const AllItems src{n_items};
-            return ex.slot ? topn_L<LL, true>(P, Q, d_users, nb, src, topn, ex, sc, out_s, out_i, st)
-                           : topn_L<LL, false>(P, Q, d_users, nb, src, topn, ex, sc, out_s, out_i, st);
-        };
-        return cs.ra ? go(CosScore{cs.ra, cs.rb}) : go(DotScore{});
-    });
-}
-
-// Device buffers are the caller's (serve.cpp): scores/ids in and out (nb * n_items each), offsets nb+1.
-hipError_t recommend_batch(int L, const float* P, const float* Q, const int32_t* d_users, int nb, int32_t n_items,
-                           int32_t topn, const RecommendExcl& ex, const CosineScale& cs, float* s_in, float* s_out,
-                           int32_t* id_in, int32_t* id_out, long long* d_off, DevBuf& temp, float* out_s, int32_t* out_i,
-                           hipStream_t st) {
-    return with_L(L, [&](auto l) {
-        constexpr int LL = l();
-        auto go = [&](const auto& sc) {
-            return batch_L<LL>(P, Q, d_users, nb, AllItems{n_items}, (long long)nb * n_items, n_items, topn, ex, sc, s_in, s_out,
-                                id_in, id_out, d_off, temp, out_s, out_i, st);
-        };
-        return cs.ra ? go(CosScore{cs.ra, cs.rb}) : go(DotScore{});
-    });
-}
-
-bool recommend_among_is_fused(int64_t longest, int32_t topn) {
+bool recommend_is_fused(int64_t longest, int32_t topn) {
     const long long tiles = ((long long)longest + kTopnTile - 1) / kTopnTile;
     return topn <= kTopnFused && tiles * topn <= kTopnCand;
 }
 
-hipError_t recommend_among_fused(int L, const float* P, const float* Q, const int32_t* d_users, int nb,
-                                 const RecommendAmong& am, int32_t topn, const RecommendExcl& ex, float* out_s,
-                                 int32_t* out_i, hipStream_t st) {
-    return with_L(L, [&](auto l) {
+// The policies of a batch are chosen here, once: what is scored (every item, or the lists), the score (the dot, or the
+// cosine), whether anything is excluded, and the path (without scratch: fused score + select, no score buffers at all).
+// One dispatch over L per (path, source), fused before sorted and every item before the lists: the kernels lie in the
+// code object in the order of these instantiations, and tools/kernel_identity.py compares it address for address.
+hipError_t recommend_topn(const TopnJob& j, const TopnScratch* scratch, hipStream_t st) {
+    if (j.among && j.cs.ra) return hipErrorInvalidValue;  // (candidates are scored by the dot: there is no such kernel)
+    auto fused = [&](auto l, const auto& src, const auto& sc) {
         constexpr int LL = l();
-        const ListedItems src{am.off, am.items, am.per_row};
-        return ex.slot ? topn_L<LL, true>(P, Q, d_users, nb, src, topn, ex, DotScore{}, out_s, out_i, st)
-                       : topn_L<LL, false>(P, Q, d_users, nb, src, topn, ex, DotScore{}, out_s, out_i, st);
-    });
-}
-
-hipError_t recommend_among_batch(int L, const float* P, const float* Q, const int32_t* d_users, int nb,
-                                 const RecommendAmong& am, int64_t total, int64_t longest, int32_t topn,
-                                 const RecommendExcl& ex, float* s_in, float* s_out, int32_t* id_in, int32_t* id_out,
-                                 long long* d_off, DevBuf& temp, float* out_s, int32_t* out_i, hipStream_t st) {
-    return with_L(L, [&](auto l) {
-        constexpr int LL = l();
-        return batch_L<LL>(P, Q, d_users, nb, ListedItems{am.off, am.items, am.per_row}, (long long)total, (long long)longest,
-                            topn, ex, DotScore{}, s_in, s_out, id_in, id_out, d_off, temp, out_s, out_i, st);
-    });
+        return j.ex.slot ? topn_L<LL, true>(j.P, j.Q, j.d_users, j.nb, src, j.topn, j.ex, sc, j.out_s, j.out_i, st)
+                         : topn_L<LL, false>(j.P, j.Q, j.d_users, j.nb, src, j.topn, j.ex, sc, j.out_s, j.out_i, st);
+    };
+    auto sorted = [&](auto l, const auto& src, const auto& sc) {
+        return batch_L<l()>(j.P, j.Q, j.d_users, j.nb, src, (long long)j.total, (long long)j.longest, j.topn, j.ex, sc,
+                            scratch->s_in, scratch->s_out, scratch->id_in, scratch->id_out, scratch->d_off, *scratch->temp,
+                            j.out_s, j.out_i, st);
+    };
+    const AllItems all{j.n_items};
+    const CosScore cos{j.cs.ra, j.cs.rb};
+    if (!j.among && !scratch) return with_L(j.L, [&](auto l) { return j.cs.ra ? fused(l, all, cos) : fused(l, all, DotScore{}); });
+    if (!j.among) return with_L(j.L, [&](auto l) { return j.cs.ra ? sorted(l, all, cos) : sorted(l, all, DotScore{}); });
+    const ListedItems listed{j.among->off, j.among->items, j.among->per_row};
+    if (!scratch) return with_L(j.L, [&](auto l) { return fused(l, listed, DotScore{}); });
+    return with_L(j.L, [&](auto l) { return sorted(l, listed, DotScore{}); });
 }
 
 hipError_t recommend_cand_keys(const long long* ptr, int32_t n_rows, const int32_t* items, int64_t x0, int64_t n,

@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "handle.hpp"
+#include "serve_util.hpp"
 
 namespace mfsgd {
 
@@ -14,16 +15,8 @@ static int check_pairs(const mfsgd_handle* h, const std::string& call, const int
     if (n < 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "n is negative");
     if (n > 0 && (!u || !i)) return fail(h, MFSGD_ERR_INVALID_ARG, call + "u or i is null");
     if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, call + "single-partition handles only");
-    // (in blocks without a branch, so that the compiler vectorises it, as recommend_core checks its candidates)
-    const uint32_t U = (uint32_t)h->cfg.n_users, I = (uint32_t)h->cfg.n_items;
-    for (int64_t x0 = 0; x0 < n; x0 += 4096) {
-        const int64_t x1 = std::min(n, x0 + 4096);
-        uint32_t outside = 0;
-        for (int64_t x = x0; x < x1; ++x) outside |= (uint32_t)((uint32_t)u[x] >= U) | (uint32_t)((uint32_t)i[x] >= I);
-        for (int64_t x = x0; outside && x < x1; ++x)
-            if ((uint32_t)u[x] >= U || (uint32_t)i[x] >= I)
-                return fail(h, MFSGD_ERR_INVALID_ARG, call + "pair " + std::to_string(x) + " out of range");
-    }
+    const int64_t x = first_outside(u, h->cfg.n_users, i, h->cfg.n_items, n);
+    if (x >= 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "pair " + std::to_string(x) + " out of range");
     if (n > (int64_t)UINT32_MAX) return fail(h, MFSGD_ERR_INVALID_ARG, call + "more than 2^32 - 1 pairs");
     return MFSGD_OK;
 }
@@ -32,16 +25,15 @@ static int check_pairs(const mfsgd_handle* h, const std::string& call, const int
 // this returns.  Asynchronous but for the synchronise before a staging buffer is reused.
 template <class Bad>
 static int pairs_to_keys(mfsgd_handle* h, const Bad& bad, const int32_t* u, const int32_t* i, int64_t n, unsigned long long* keys) {
-    DevBuf cu, ci;
+    DevArray<int32_t> cu, ci;
     const int64_t chunk = std::min(n, kExclChunk);
     int rc;
-    if ((rc = dev_alloc(h, cu, sizeof(int32_t) * (size_t)chunk))) return rc;
-    if ((rc = dev_alloc(h, ci, sizeof(int32_t) * (size_t)chunk))) return rc;
+    if ((rc = dev_alloc(h, cu, (size_t)chunk)) || (rc = dev_alloc(h, ci, (size_t)chunk))) return rc;
     for (int64_t x0 = 0; x0 < n; x0 += chunk) {
         const int64_t c = std::min(chunk, n - x0);
-        HIPCHK_OR(bad, hipMemcpyAsync(cu.get(), u + x0, sizeof(int32_t) * (size_t)c, hipMemcpyHostToDevice, h->stream));
-        HIPCHK_OR(bad, hipMemcpyAsync(ci.get(), i + x0, sizeof(int32_t) * (size_t)c, hipMemcpyHostToDevice, h->stream));
-        HIPCHK_OR(bad, seen_pair_keys(cu.as<const int32_t>(), ci.as<const int32_t>(), c, keys + x0, h->stream));
+        HIPCHK_OR(bad, copy_up(cu, u + x0, (size_t)c, h->stream));
+        HIPCHK_OR(bad, copy_up(ci, i + x0, (size_t)c, h->stream));
+        HIPCHK_OR(bad, seen_pair_keys(cu.data(), ci.data(), c, keys + x0, h->stream));
         HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // (pageable memory: the copies have read the caller's arrays)
     }
     return MFSGD_OK;
@@ -55,26 +47,27 @@ static int seen_build(mfsgd_handle* h, const std::string& call, const int32_t* u
     const int32_t cap = h->user_capacity();
     Seen made;
     {
-        DevBuf keys, keys_tmp, count, temp;
-        if ((rc = dev_alloc(h, keys, 8 * (size_t)n))) return rc;
-        if ((rc = dev_alloc(h, keys_tmp, 8 * (size_t)n))) return rc;
-        if ((rc = dev_alloc(h, count, 16))) return rc;
-        if ((rc = dev_alloc(h, made.off, sizeof(long long) * ((size_t)cap + 1)))) return rc;
-        if ((rc = dev_alloc(h, made.slot, sizeof(int32_t) * (size_t)cap))) return rc;
-        if ((rc = pairs_to_keys(h, bad, u, i, n, keys.as<unsigned long long>()))) return rc;
+        DevArray<unsigned long long> keys;
+        DevBuf keys_tmp;  // read under two types: the sort's second key buffer, then the int32 items of the lists at its start
+        DevArray<unsigned> count;
+        DevBuf temp;  // the rocPRIM scratch, bytes of no type
+        if ((rc = dev_alloc(h, keys, (size_t)n))) return rc;
+        if ((rc = dev_alloc(h, keys_tmp, sizeof(unsigned long long) * (size_t)n))) return rc;
+        if ((rc = dev_alloc(h, count, 4))) return rc;
+        if ((rc = dev_alloc(h, made.off, (size_t)cap + 1)) || (rc = dev_alloc(h, made.slot, (size_t)cap))) return rc;
+        if ((rc = pairs_to_keys(h, bad, u, i, n, keys.data()))) return rc;
         // the slots are the users up to the capacity: off[x] of a user without pairs, and of those above the count, is
         // where the next user's keys start.  The items land in keys_tmp, which the sort is done with by then.
-        HIPCHK_OR(bad, recommend_excl_lists(keys.as<unsigned long long>(), keys_tmp.as<unsigned long long>(), n, cap,
-                                            count.as<unsigned>(), made.off.as<long long>(), keys_tmp.as<int32_t>(), temp,
-                                            h->stream));
+        HIPCHK_OR(bad, recommend_excl_lists(keys.data(), keys_tmp.as<unsigned long long>(), n, cap, count.data(), made.off.data(),
+                                            keys_tmp.as<int32_t>(), temp, h->stream));
         unsigned distinct = 0;
-        HIPCHK_OR(bad, hipMemcpyAsync(&distinct, count.get(), sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK_OR(bad, copy_down(&distinct, count, 1, h->stream));
         HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
         made.n = (int64_t)distinct;
-        if ((rc = dev_alloc(h, made.items, sizeof(int32_t) * (size_t)made.n))) return rc;
-        HIPCHK_OR(bad, hipMemcpyAsync(made.items.get(), keys_tmp.get(), sizeof(int32_t) * (size_t)made.n, hipMemcpyDeviceToDevice,
+        if ((rc = dev_alloc(h, made.items, (size_t)made.n))) return rc;
+        HIPCHK_OR(bad, hipMemcpyAsync(made.items.data(), keys_tmp.get(), sizeof(int32_t) * (size_t)made.n, hipMemcpyDeviceToDevice,
                                       h->stream));
-        HIPCHK_OR(bad, seen_tables(nullptr, 0, 0, cap, nullptr, made.slot.as<int32_t>(), h->stream));
+        HIPCHK_OR(bad, seen_tables(nullptr, 0, 0, cap, nullptr, made.slot.data(), h->stream));
         HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
     }
     made.present = true;
@@ -89,26 +82,27 @@ static int seen_merge_batch(mfsgd_handle* h, const std::string& call, const int3
     if (rc) return rc;
     auto bad = [h, &call](hipError_t e) { return serve_fail(h, call.c_str(), e); };
     Seen& old = h->seen;
-    DevBuf keys, keys_tmp, flags, count, temp, off2, items2;
-    if ((rc = dev_alloc(h, keys, 8 * (size_t)n))) return rc;
-    if ((rc = dev_alloc(h, keys_tmp, 8 * (size_t)n))) return rc;
+    DevArray<unsigned long long> keys, keys_tmp;
+    DevArray<unsigned char> flags;
+    DevArray<unsigned> count;
+    DevArray<long long> off2;
+    DevArray<int32_t> items2;
+    DevBuf temp;  // the rocPRIM scratch, bytes of no type
+    if ((rc = dev_alloc(h, keys, (size_t)n)) || (rc = dev_alloc(h, keys_tmp, (size_t)n))) return rc;
     if ((rc = dev_alloc(h, flags, (size_t)n))) return rc;
-    if ((rc = dev_alloc(h, count, 16))) return rc;  // [0] distinct keys of the batch, [1] those the index does not hold
-    if ((rc = pairs_to_keys(h, bad, u, i, n, keys.as<unsigned long long>()))) return rc;
-    HIPCHK_OR(bad, seen_batch_fresh(keys.as<unsigned long long>(), keys_tmp.as<unsigned long long>(), n, h->cfg.n_users,
-                                    old.off.as<const long long>(), old.items.as<const int32_t>(), flags.as<unsigned char>(),
-                                    count.as<unsigned>(), temp, h->stream));
+    if ((rc = dev_alloc(h, count, 4))) return rc;  // [0] distinct keys of the batch, [1] those the index does not hold
+    if ((rc = pairs_to_keys(h, bad, u, i, n, keys.data()))) return rc;
+    HIPCHK_OR(bad, seen_batch_fresh(keys.data(), keys_tmp.data(), n, h->cfg.n_users, old.off.data(), old.items.data(), flags.data(),
+                                    count.data(), temp, h->stream));
     unsigned counts[2] = {0, 0};
-    HIPCHK_OR(bad, hipMemcpyAsync(counts, count.get(), sizeof(counts), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK_OR(bad, copy_down(counts, count, 2, h->stream));
     HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
     const int64_t fresh = (int64_t)counts[1];
     if (fresh == 0) return MFSGD_OK;
     if (old.n + fresh > (int64_t)UINT32_MAX) return fail(h, MFSGD_ERR_INVALID_ARG, call + "more than 2^32 - 1 pairs");
-    if ((rc = dev_alloc(h, off2, sizeof(long long) * ((size_t)old.capacity + 1)))) return rc;
-    if ((rc = dev_alloc(h, items2, sizeof(int32_t) * (size_t)(old.n + fresh)))) return rc;
-    HIPCHK_OR(bad, seen_merge(old.off.as<const long long>(), old.items.as<const int32_t>(), old.n, old.capacity,
-                              keys_tmp.as<const unsigned long long>(), fresh, off2.as<long long>(), items2.as<int32_t>(),
-                              h->stream));
+    if ((rc = dev_alloc(h, off2, (size_t)old.capacity + 1)) || (rc = dev_alloc(h, items2, (size_t)(old.n + fresh)))) return rc;
+    HIPCHK_OR(bad, seen_merge(old.off.data(), old.items.data(), old.n, old.capacity, keys_tmp.data(), fresh, off2.data(),
+                              items2.data(), h->stream));
     HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
     old.off = std::move(off2);
     old.items = std::move(items2);
@@ -129,20 +123,18 @@ int seen_update(mfsgd_handle* h, const char* name, bool merge, const int32_t* u,
     return seen_build(h, call, u, i, n);
 }
 
-int seen_grown_tables(mfsgd_handle* h, const char* prefix, int32_t new_cap, DevBuf& off2, DevBuf& slot2) {
+int seen_grown_tables(mfsgd_handle* h, const char* prefix, int32_t new_cap, DevArray<long long>& off2, DevArray<int32_t>& slot2) {
     const Seen& s = h->seen;
     if (s.n == 0 || new_cap <= s.capacity) return MFSGD_OK;
     int rc = ensure_device(h);
     if (rc) return rc;
-    if ((rc = dev_alloc(h, off2, sizeof(long long) * ((size_t)new_cap + 1)))) return rc;
-    if ((rc = dev_alloc(h, slot2, sizeof(int32_t) * (size_t)new_cap))) return rc;
-    const hipError_t e = seen_tables(s.off.as<const long long>(), s.capacity, s.n, new_cap, off2.as<long long>(),
-                                     slot2.as<int32_t>(), h->stream);
+    if ((rc = dev_alloc(h, off2, (size_t)new_cap + 1)) || (rc = dev_alloc(h, slot2, (size_t)new_cap))) return rc;
+    const hipError_t e = seen_tables(s.off.data(), s.capacity, s.n, new_cap, off2.data(), slot2.data(), h->stream);
     if (e != hipSuccess) return serve_fail(h, prefix, e);
     return MFSGD_OK;
 }
 
-void seen_adopt_tables(mfsgd_handle* h, int32_t new_cap, DevBuf& off2, DevBuf& slot2) {
+void seen_adopt_tables(mfsgd_handle* h, int32_t new_cap, DevArray<long long>& off2, DevArray<int32_t>& slot2) {
     if (!off2) return;
     h->seen.off = std::move(off2);
     h->seen.slot = std::move(slot2);
@@ -157,23 +149,20 @@ int seen_get(mfsgd_handle* h, const int32_t* users, int32_t n_users, int64_t* ro
     if (items && items_capacity < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "get_seen: items_capacity is negative");
     if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "get_seen: single-partition handles only");
     if (!h->seen.present) return fail(h, MFSGD_ERR_STATE, "get_seen: no seen set");
-    for (int32_t j = 0; j < n_users; ++j)
-        if (users[j] < 0 || users[j] >= h->cfg.n_users)
-            return fail(h, MFSGD_ERR_INVALID_ARG, "get_seen: user " + std::to_string(j) + " out of range");
+    const int64_t j_bad = first_outside(users, n_users, h->cfg.n_users);
+    if (j_bad >= 0) return fail(h, MFSGD_ERR_INVALID_ARG, "get_seen: user " + std::to_string(j_bad) + " out of range");
     std::fill(row_ptr, row_ptr + (size_t)n_users + 1, (int64_t)0);
     const Seen& s = h->seen;
     if (n_users == 0 || s.n == 0) return MFSGD_OK;
     int rc = ensure_device(h);
     if (rc) return rc;
     auto bad = [h](hipError_t e) { return serve_fail(h, "get_seen: ", e); };
-    DevBuf d_users, d_ptr, d_out;
-    if ((rc = dev_alloc(h, d_users, sizeof(int32_t) * (size_t)n_users))) return rc;
-    if ((rc = dev_alloc(h, d_ptr, sizeof(long long) * ((size_t)n_users + 1)))) return rc;
-    HIPCHK_OR(bad, hipMemcpyAsync(d_users.get(), users, sizeof(int32_t) * (size_t)n_users, hipMemcpyHostToDevice, h->stream));
-    HIPCHK_OR(bad, seen_lengths(s.off.as<const long long>(), d_users.as<const int32_t>(), n_users, d_ptr.as<long long>() + 1,
-                                h->stream));
-    HIPCHK_OR(bad, hipMemcpyAsync(row_ptr + 1, d_ptr.as<long long>() + 1, sizeof(int64_t) * (size_t)n_users,
-                                  hipMemcpyDeviceToHost, h->stream));
+    DevArray<int32_t> d_users, d_out;
+    DevArray<long long> d_ptr;
+    if ((rc = dev_alloc(h, d_users, (size_t)n_users)) || (rc = dev_alloc(h, d_ptr, (size_t)n_users + 1))) return rc;
+    HIPCHK_OR(bad, copy_up(d_users, users, (size_t)n_users, h->stream));
+    HIPCHK_OR(bad, seen_lengths(s.off.data(), d_users.data(), n_users, d_ptr.data() + 1, h->stream));
+    HIPCHK_OR(bad, copy_down(row_ptr + 1, d_ptr, (size_t)n_users, h->stream, 1));
     HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
     int64_t longest = 0;
     for (int32_t j = 0; j < n_users; ++j) {  // lengths to offsets
@@ -186,11 +175,10 @@ int seen_get(mfsgd_handle* h, const int32_t* users, int32_t n_users, int64_t* ro
         return fail(h, MFSGD_ERR_INVALID_ARG,
                     "get_seen: items_capacity is " + std::to_string(items_capacity) + ", the lists hold " + std::to_string(total));
     if (total == 0) return MFSGD_OK;
-    if ((rc = dev_alloc(h, d_out, sizeof(int32_t) * (size_t)total))) return rc;
-    HIPCHK_OR(bad, hipMemcpyAsync(d_ptr.get(), row_ptr, sizeof(int64_t) * ((size_t)n_users + 1), hipMemcpyHostToDevice, h->stream));
-    HIPCHK_OR(bad, seen_gather(s.off.as<const long long>(), s.items.as<const int32_t>(), d_users.as<const int32_t>(), n_users,
-                               d_ptr.as<const long long>(), longest, d_out.as<int32_t>(), h->stream));
-    HIPCHK_OR(bad, hipMemcpyAsync(items, d_out.get(), sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, h->stream));
+    if ((rc = dev_alloc(h, d_out, (size_t)total))) return rc;
+    HIPCHK_OR(bad, copy_up(d_ptr, row_ptr, (size_t)n_users + 1, h->stream));
+    HIPCHK_OR(bad, seen_gather(s.off.data(), s.items.data(), d_users.data(), n_users, d_ptr.data(), longest, d_out.data(), h->stream));
+    HIPCHK_OR(bad, copy_down(items, d_out, (size_t)total, h->stream));
     HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
     return MFSGD_OK;
 }
@@ -209,31 +197,21 @@ int seen_sample(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int
     if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "sample_unseen: single-partition handles only");
     if (!h->seen.present) return fail(h, MFSGD_ERR_STATE, "sample_unseen: no seen set");
     if (total == 0) return MFSGD_OK;
-    const uint32_t U = (uint32_t)h->cfg.n_users;
-    for (int64_t x0 = 0; x0 < n; x0 += 4096) {  // (in blocks without a branch, as check_pairs)
-        const int64_t x1 = std::min(n, x0 + 4096);
-        uint32_t outside = 0;
-        for (int64_t x = x0; x < x1; ++x) outside |= (uint32_t)((uint32_t)users[x] >= U);
-        for (int64_t x = x0; outside && x < x1; ++x)
-            if ((uint32_t)users[x] >= U)
-                return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen: user " + std::to_string(x) + " out of range");
-    }
+    const int64_t x_bad = first_outside(users, n, h->cfg.n_users);
+    if (x_bad >= 0) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen: user " + std::to_string(x_bad) + " out of range");
     int rc = ensure_device(h);
     if (rc) return rc;
     auto bad = [h](hipError_t e) { return serve_fail(h, "sample_unseen: ", e); };
     const Seen& s = h->seen;
     const int64_t rows = std::min(n, std::max<int64_t>(1, kSampleChunk / m));
-    DevBuf d_users, d_out;
-    if ((rc = dev_alloc(h, d_users, sizeof(int32_t) * (size_t)rows))) return rc;
-    if ((rc = dev_alloc(h, d_out, sizeof(int32_t) * (size_t)(rows * m)))) return rc;
+    DevArray<int32_t> d_users, d_out;
+    if ((rc = dev_alloc(h, d_users, (size_t)rows)) || (rc = dev_alloc(h, d_out, (size_t)(rows * m)))) return rc;
     for (int64_t x0 = 0; x0 < n; x0 += rows) {
         const int64_t c = std::min(rows, n - x0), draws = c * m;
-        HIPCHK_OR(bad, hipMemcpyAsync(d_users.get(), users + x0, sizeof(int32_t) * (size_t)c, hipMemcpyHostToDevice, h->stream));
-        HIPCHK_OR(bad, sample_unseen_draws(s.n > 0 ? s.off.as<const long long>() : nullptr, s.items.as<const int32_t>(),
-                                           d_users.as<const int32_t>(), draws, m, h->cfg.n_items, seed,
-                                           (uint64_t)first + (uint64_t)(x0 * m), d_out.as<int32_t>(), h->stream));
-        HIPCHK_OR(bad, hipMemcpyAsync(out_items + x0 * m, d_out.get(), sizeof(int32_t) * (size_t)draws, hipMemcpyDeviceToHost,
-                                      h->stream));
+        HIPCHK_OR(bad, copy_up(d_users, users + x0, (size_t)c, h->stream));
+        HIPCHK_OR(bad, sample_unseen_draws(s.n > 0 ? s.off.data() : nullptr, s.items.data(), d_users.data(), draws, m, h->cfg.n_items,
+                                           seed, (uint64_t)first + (uint64_t)(x0 * m), d_out.data(), h->stream));
+        HIPCHK_OR(bad, copy_down(out_items + x0 * m, d_out, (size_t)draws, h->stream));
         HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // (pageable memory: the staging is free for the next piece)
     }
     return MFSGD_OK;

@@ -1,7 +1,7 @@
 // train.cpp -- epochs: the launch paths (one launch per round, the persistent kernel, the captured graph), the
 // persistent kernel's recovery protocol, the training calls, lr / lambda on a live handle, the held-out set with its
-// RMSE and early stopping on it, online updates of the live factors (their dependency levels and launches), the DSGD
-// partition calls and the diagnostics of the epoch kernel.
+// RMSE and early stopping on it, the DSGD partition calls and the diagnostics of the epoch kernel.  (Online updates of
+// the live factors: online_update.cpp.)
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -10,17 +10,18 @@
 #include <thread>
 
 #include "handle.hpp"
+#include "serve_util.hpp"
 
 namespace mfsgd {
 
 static CellLaunch make_launch(const mfsgd_handle* h, const Part& p, float* Q) {
     CellLaunch a{};
-    a.P = p.swapped ? Q : h->dP.as<float>();
-    a.Q = p.swapped ? h->dP.as<float>() : Q;
-    a.cells = p.d_cells.as<const CellDesc>();
-    a.rows = p.d_rows.as<const uint32_t>();
-    a.subs = p.d_subs.as<const SubDesc>();
-    a.entries = p.d_entries.as<const Entry>();
+    a.P = p.swapped ? Q : h->dP.data();
+    a.Q = p.swapped ? h->dP.data() : Q;
+    a.cells = p.d_cells.data();
+    a.rows = p.d_rows.data();
+    a.subs = p.d_subs.data();
+    a.entries = p.d_entries.data();
     a.B = p.sched.B;
     a.rd = 0;
     a.grid = p.sched.B;
@@ -68,7 +69,7 @@ static int launch_epoch_body(mfsgd_handle* h, Part& p, float* Q, hipStream_t st)
         // flags are counted within the launch: zero them (and the abort word) every time
         // no memset: the kernel resets its own hand-off flags behind a device-side barrier (epoch.hip,
         // run_ring) -- a memset node in a replayed graph is not reliably ordered before the kernel node
-        HIPCHK(h, launch_epoch_persistent(h->geo.L, p.sched.W, a, p.sched.B, p.d_sync.as<unsigned>(), abort_word(p), st));
+        HIPCHK(h, launch_epoch_persistent(h->geo.L, p.sched.W, a, p.sched.B, p.d_sync.data(), abort_word(p), st));
         return MFSGD_OK;
     }
     return launch_epoch_eager(h, p, Q, st);
@@ -80,7 +81,7 @@ static int launch_epoch(mfsgd_handle* h, Part& p, float* Q, hipStream_t st) {
     int rc = probe_persistent(h, p);
     if (rc) return rc;
     if (h->cfg.flags & MFSGD_FLAG_NO_GRAPH) return launch_epoch_body(h, p, Q, st);
-    const auto key = std::make_pair((const void*)h->dP.get(), (const void*)Q);
+    const auto key = std::make_pair((const void*)h->dP.data(), (const void*)Q);
     auto it = p.graphs.find(key);
     if (it == p.graphs.end()) {
         // capture the launch(es) of one epoch once; replayed every epoch
@@ -168,7 +169,7 @@ static int launch_sse(mfsgd_handle* h, Part& p, const float* Q, hipStream_t st) 
         a.grid = std::min(n_cells, per_cu * std::max(1, h->n_cu));
         HIPCHK(h, launch_sse_persistent(h->geo.L, p.sched.W, a, n_cells, st));
     }
-    HIPCHK(h, launch_reduce_sse(a.sse_partial, (int64_t)a.grid, p.d_sse_out.as<double>(), st));
+    HIPCHK(h, launch_reduce_sse(a.sse_partial, (int64_t)a.grid, p.d_sse_out.data(), st));
     return MFSGD_OK;
 }
 
@@ -179,7 +180,7 @@ static int part_sse_sync(mfsgd_handle* h, Part& p, const float* Q, hipStream_t s
     }
     int rc = launch_sse(h, p, Q, st);
     if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(sse, p.d_sse_out.get(), sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, copy_down(sse, p.d_sse_out, 1, st));
     HIPCHK(h, hipStreamSynchronize(st));
     return check_abort_strict(h, p);
 }
@@ -244,22 +245,24 @@ static int apply_hyper(mfsgd_handle* h, float lr, float lambda) {
             HIPCHK(h, h->n_parts > 1 ? hipDeviceSynchronize() : hipStreamSynchronize(h->stream));
         }
         const float c = 1.0f - lr * lambda;
-        std::vector<DevBuf> temps;  // descriptors of a part that is not on the device yet; freed before this returns
+        // descriptors of a part that is not on the device yet; freed before this returns
+        std::vector<DevArray<CellDesc>> temp_cells;
+        std::vector<DevArray<SubDesc>> temp_subs;
         bool launched = false;
         for (Part& p : h->parts) {
             Schedule& s = p.sched;
-            Entry* d_entries = p.on_device ? p.d_entries.as<Entry>() : s.dev.entries.as<Entry>();
+            Entry* d_entries = p.on_device ? p.d_entries.data() : s.dev.entries.data();
             if (!d_entries || s.n_entry_recs == 0 || s.cells.empty()) continue;
-            const CellDesc* d_cells = p.d_cells.as<const CellDesc>();
-            const SubDesc* d_subs = p.on_device ? p.d_subs.as<const SubDesc>() : s.dev.subs.as<const SubDesc>();
+            const CellDesc* d_cells = p.d_cells.data();
+            const SubDesc* d_subs = p.on_device ? p.d_subs.data() : s.dev.subs.data();
             if (!p.on_device) {  // the device packer's buffers, not adopted yet: the descriptors are still on the host only
-                temps.emplace_back();
-                if (const int rc = upload(h, temps.back(), s.cells)) return broken(rc, "the chunk descriptors did not reach the device: " + h->err);
-                d_cells = temps.back().as<const CellDesc>();
+                temp_cells.emplace_back();
+                if (const int rc = upload(h, temp_cells.back(), s.cells)) return broken(rc, "the chunk descriptors did not reach the device: " + h->err);
+                d_cells = temp_cells.back().data();
                 if (!d_subs) {
-                    temps.emplace_back();
-                    if (const int rc = upload(h, temps.back(), s.subs)) return broken(rc, "the sub-cell tables did not reach the device: " + h->err);
-                    d_subs = temps.back().as<const SubDesc>();
+                    temp_subs.emplace_back();
+                    if (const int rc = upload(h, temp_subs.back(), s.subs)) return broken(rc, "the sub-cell tables did not reach the device: " + h->err);
+                    d_subs = temp_subs.back().data();
                 }
             }
             const hipError_t e = launch_rehyper(d_cells, d_subs, d_entries, (int64_t)s.cells.size(), s.n_entry_recs, s.W,
@@ -298,7 +301,7 @@ static bool is_nan(float x) { return !(x == x); }
 static int run_epochs(mfsgd_handle* h, int epochs, const float* lr, const float* lambda, double* rmse_per_epoch) {
     int rc = prepare_compute(h);
     if (rc) return rc;
-    float* Q = h->dQ.as<float>();
+    float* Q = h->dQ.data();
     int pending = 0;  // epochs launched and not settled yet: all at the handle's current values
     for (int e = 0; e < epochs; ++e) {
         const float lr_e = lr ? lr[e] : h->cfg.lr, lam = lambda ? lambda[e] : h->cfg.lambda;
@@ -330,32 +333,20 @@ constexpr int64_t kPairsPiece = (int64_t)1 << 20;
 static int check_pairs(const mfsgd_handle* h, const char* call, const int32_t* u, const int32_t* i, const float* r, int64_t n) {
     if (n < 0) return fail(h, MFSGD_ERR_INVALID_ARG, std::string(call) + ": n is negative");
     if (n > 0 && (!u || !i || !r)) return fail(h, MFSGD_ERR_INVALID_ARG, std::string(call) + ": u, i or r is null");
-    for (int64_t j = 0; j < n; ++j)
-        if (u[j] < 0 || u[j] >= h->cfg.n_users || i[j] < 0 || i[j] >= h->cfg.n_items)
-            return fail(h, MFSGD_ERR_INVALID_ARG, std::string(call) + ": pair " + std::to_string(j) + " out of range");
+    const int64_t j = first_outside(u, h->cfg.n_users, i, h->cfg.n_items, n);
+    if (j >= 0) return fail(h, MFSGD_ERR_INVALID_ARG, std::string(call) + ": pair " + std::to_string(j) + " out of range");
     return MFSGD_OK;
 }
 
-// What every call that reads the factors asks before it asks for a device.
-static int check_reads_factors(const mfsgd_handle* h, const char* call) {
-    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, std::string(call) + ": single-partition handles only");
-    if (h->where == mfsgd_handle::Where::None) return fail(h, MFSGD_ERR_STATE, std::string(call) + ": factors not initialised");
-    return check_has_q(h, call);
-}
-
-// The scratch of launch_pairs_sse: its partials, then the sum.
-static int alloc_pairs_scratch(mfsgd_handle* h, DevBuf& b) { return dev_alloc(h, b, sizeof(double) * ((size_t)kPairsSlots + 1)); }
-
 // SSE of n >= 1 pairs that are on the device, under the handle's factors (P is always the users' matrix, whichever
 // side of the kernels the schedule gave it: as mfsgd_predict reads it), on the handle's stream; waits for it.
-static int pairs_sse_sync(mfsgd_handle* h, const char* call, const DevBuf& du, const DevBuf& di, const DevBuf& dr, int64_t n,
-                          const DevBuf& scratch, double* sse) {
+static int pairs_sse_sync(mfsgd_handle* h, const char* call, const Validation& v, int64_t n, double* sse) {
     const std::string prefix = std::string(call) + ": ";
     auto bad = [h, &prefix](hipError_t e) { return serve_fail(h, prefix.c_str(), e); };
-    double* partial = scratch.as<double>();
-    HIPCHK_OR(bad, launch_pairs_sse(h->geo.L, h->dP.as<const float>(), h->dQ.as<const float>(), du.as<const int32_t>(),
-                                    di.as<const int32_t>(), dr.as<const float>(), n, partial, partial + kPairsSlots, h->stream));
-    HIPCHK_OR(bad, hipMemcpyAsync(sse, partial + kPairsSlots, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    double* partial = v.d_sse.data();
+    HIPCHK_OR(bad, launch_pairs_sse(h->geo.L, h->dP.data(), h->dQ.data(), v.du.data(), v.di.data(), v.dr.data(), n, partial,
+                                    partial + kPairsSlots, h->stream));
+    HIPCHK_OR(bad, copy_down(sse, v.d_sse, 1, h->stream, kPairsSlots));
     HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
     return MFSGD_OK;
 }
@@ -366,7 +357,7 @@ static int validation_to_device(mfsgd_handle* h) {
     if (v.on_device || v.n == 0) return MFSGD_OK;
     int rc;
     if ((rc = upload(h, v.du, v.hu)) || (rc = upload(h, v.di, v.hi)) || (rc = upload(h, v.dr, v.hr)) ||
-        (rc = alloc_pairs_scratch(h, v.d_sse))) {
+        (rc = dev_alloc(h, v.d_sse, (size_t)kPairsSlots + 1))) {
         v.du.reset(), v.di.reset(), v.dr.reset(), v.d_sse.reset();
         return rc;
     }
@@ -381,96 +372,7 @@ static int validation_to_device(mfsgd_handle* h) {
 static int validation_sse(mfsgd_handle* h, const char* call, double* sse) {
     int rc = factors_to_device(h);
     if (rc || (rc = validation_to_device(h))) return rc;
-    const Validation& v = h->val;
-    return pairs_sse_sync(h, call, v.du, v.di, v.dr, v.n, v.d_sse, sse);
-}
-
-// Online updates ("Online updates") ----------------------------------------------
-// Ratings of one piece: the pieces of a list are consecutive and applied one after the other, so the levels are those of
-// a piece, and the device buffers of a call are sized by one.  (include/mfsgd.h states the size.)
-constexpr int64_t kOnlinePiece = (int64_t)1 << 20;
-// Consecutive narrow levels one workgroup walks in one launch: bounds the time a single launch runs.
-constexpr int32_t kOnlineRun = 1 << 16;
-
-static int check_online_pairs(const mfsgd_handle* h, const char* call, const int32_t* u, const int32_t* i, int64_t n) {
-    if (n < 0) return fail(h, MFSGD_ERR_INVALID_ARG, std::string(call) + ": n is negative");
-    if (n > 0 && (!u || !i)) return fail(h, MFSGD_ERR_INVALID_ARG, std::string(call) + ": u or i is null");
-    for (int64_t j = 0; j < n; ++j)
-        if (u[j] < 0 || u[j] >= h->cfg.n_users || i[j] < 0 || i[j] >= h->cfg.n_items)
-            return fail(h, MFSGD_ERR_INVALID_ARG, std::string(call) + ": rating " + std::to_string(j) + " out of range");
-    return MFSGD_OK;
-}
-
-// level[j] of the n ratings of one piece (every index in range), and how many levels there are: one pass, and a second
-// one that puts the handle's two "last level" arrays back to zero -- O(n), whatever n_users and n_items are.
-static int32_t online_levels_of(mfsgd_handle* h, const int32_t* u, const int32_t* i, int64_t n, int32_t* level) {
-    if (h->online_last_u.empty()) h->online_last_u.assign((size_t)h->cfg.n_users, 0);
-    if (h->online_last_i.empty()) h->online_last_i.assign((size_t)h->cfg.n_items, 0);
-    int32_t* lu = h->online_last_u.data();
-    int32_t* li = h->online_last_i.data();
-    int32_t n_levels = 0;
-    for (int64_t j = 0; j < n; ++j) {
-        const int32_t l = std::max(lu[u[j]], li[i[j]]);
-        level[j] = l;
-        lu[u[j]] = li[i[j]] = l + 1;
-        n_levels = std::max(n_levels, l + 1);
-    }
-    for (int64_t j = 0; j < n; ++j) lu[u[j]] = li[i[j]] = 0;
-    return n_levels;
-}
-
-// One piece ready for the device: its ratings in a stable counting sort by level.
-struct OnlinePiece {
-    std::vector<int32_t> level, level_ptr, u, i, orig;
-    std::vector<float> r;
-    int32_t n_levels = 0;
-};
-
-static void online_sort_piece(mfsgd_handle* h, const int32_t* u, const int32_t* i, const float* r, int64_t n, OnlinePiece& pc) {
-    pc.level.resize((size_t)n);
-    pc.u.resize((size_t)n), pc.i.resize((size_t)n), pc.orig.resize((size_t)n), pc.r.resize((size_t)n);
-    pc.n_levels = online_levels_of(h, u, i, n, pc.level.data());
-    pc.level_ptr.assign((size_t)pc.n_levels + 1, 0);
-    for (int64_t j = 0; j < n; ++j) ++pc.level_ptr[(size_t)pc.level[(size_t)j] + 1];
-    for (int32_t l = 0; l < pc.n_levels; ++l) pc.level_ptr[(size_t)l + 1] += pc.level_ptr[(size_t)l];
-    std::vector<int32_t> next(pc.level_ptr.begin(), pc.level_ptr.end() - 1);
-    for (int64_t j = 0; j < n; ++j) {
-        const int32_t at = next[(size_t)pc.level[(size_t)j]]++;
-        pc.u[(size_t)at] = u[j];
-        pc.i[(size_t)at] = i[j];
-        pc.r[(size_t)at] = canon_nan(r[j]);  // (records.hpp: a payload must not reach P and Q)
-        pc.orig[(size_t)at] = (int32_t)j;
-    }
-}
-
-static void online_count(mfsgd_online_info* info, const int32_t* level_ptr, int32_t n_levels) {
-    info->pieces += 1;
-    info->levels += n_levels;
-    for (int32_t l = 0; l < n_levels; ++l) info->max_width = std::max<int64_t>(info->max_width, level_ptr[l + 1] - level_ptr[l]);
-}
-
-// The launches of one piece that is on the device.  A wide level (more ratings than one pass of one workgroup holds) is a
-// launch of its own, of as many workgroups as it has passes: stream order is the barrier before and behind it.  A run of
-// consecutive narrow levels is ONE launch of ONE workgroup, which walks them (online.hip).  (Narrow is one pass, not a few:
-// calling levels of up to 4, 8 or 16 passes narrow saved launches and no time on the bench workload, 32 passes cost four
-// times the time -- DESIGN.md, "Online updates".)
-template <class Launch>
-static hipError_t online_launches(const std::vector<int32_t>& level_ptr, int32_t n_levels, int L, int64_t* launches, Launch&& launch) {
-    const int32_t gpb = 256 / L;
-    for (int32_t l = 0; l < n_levels;) {
-        const int32_t width = level_ptr[(size_t)l + 1] - level_ptr[(size_t)l];
-        int32_t l1 = l + 1, wgs = 1;
-        if (width > gpb) {
-            wgs = (width + gpb - 1) / gpb;
-        } else {
-            while (l1 < n_levels && l1 - l < kOnlineRun && level_ptr[(size_t)l1 + 1] - level_ptr[(size_t)l1] <= gpb) ++l1;
-        }
-        const hipError_t e = launch(l, l1, wgs);
-        if (e != hipSuccess) return e;
-        ++*launches;
-        l = l1;
-    }
-    return hipSuccess;
+    return pairs_sse_sync(h, call, h->val, h->val.n, sse);
 }
 
 }  // namespace mfsgd
@@ -495,7 +397,7 @@ int mfsgd_train_timed(mfsgd_handle* h, int32_t epochs, double* elapsed_ms, int64
         int rc = check_has_q(h, "train_timed");
         if (rc || (rc = prepare_compute(h))) return rc;
         Part& p = h->parts[0];
-        float* Q = h->dQ.as<float>();
+        float* Q = h->dQ.data();
         HIPCHK(h, hipStreamSynchronize(h->stream));
         HIPCHK(h, hipEventRecord(h->ev0, h->stream));
         for (int e = 0; e < epochs; ++e)
@@ -548,7 +450,7 @@ int mfsgd_train_bold_driver(mfsgd_handle* h, int32_t epochs, float up, float dow
         if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "bold_driver: handle has n_parts > 1, drive it with mfsgd_part_train");
         int rc = check_has_q(h, "bold_driver");
         if (rc || (rc = prepare_compute(h))) return rc;
-        float* Q = h->dQ.as<float>();
+        float* Q = h->dQ.data();
         double prev = 0.0;
         if ((rc = rmse_of(h, h->parts[0], Q, &prev))) return rc;
         for (int e = 0; e < epochs; ++e) {
@@ -572,7 +474,7 @@ int mfsgd_rmse(mfsgd_handle* h, double* out) {
         if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "rmse: handle has n_parts > 1, use mfsgd_part_sse");
         int rc = check_has_q(h, "rmse");
         if (rc || (rc = prepare_compute(h))) return rc;
-        return rmse_of(h, h->parts[0], h->dQ.as<const float>(), out);
+        return rmse_of(h, h->parts[0], h->dQ.data(), out);
     });
 }
 
@@ -630,19 +532,17 @@ int mfsgd_rmse_pairs(mfsgd_handle* h, const int32_t* u, const int32_t* i, const 
         if (rc || (rc = factors_to_device(h))) return rc;
         auto bad = [h](hipError_t e) { return serve_fail(h, "rmse_pairs: ", e); };
         const int64_t piece = std::min(n, kPairsPiece);
-        DevBuf du, di, dr, scratch;
-        if ((rc = dev_alloc(h, du, sizeof(int32_t) * (size_t)piece))) return rc;
-        if ((rc = dev_alloc(h, di, sizeof(int32_t) * (size_t)piece))) return rc;
-        if ((rc = dev_alloc(h, dr, sizeof(float) * (size_t)piece))) return rc;
-        if ((rc = alloc_pairs_scratch(h, scratch))) return rc;
+        Validation st;  // the staging of one piece, and the scratch: the device arrays of a held-out set, for this call
+        if ((rc = dev_alloc(h, st.du, (size_t)piece)) || (rc = dev_alloc(h, st.di, (size_t)piece))) return rc;
+        if ((rc = dev_alloc(h, st.dr, (size_t)piece)) || (rc = dev_alloc(h, st.d_sse, (size_t)kPairsSlots + 1))) return rc;
         double total = 0.0;
         for (int64_t j0 = 0; j0 < n; j0 += piece) {
             const int64_t c = std::min(piece, n - j0);
             double s = 0.0;
-            HIPCHK_OR(bad, hipMemcpyAsync(du.get(), u + j0, sizeof(int32_t) * (size_t)c, hipMemcpyHostToDevice, h->stream));
-            HIPCHK_OR(bad, hipMemcpyAsync(di.get(), i + j0, sizeof(int32_t) * (size_t)c, hipMemcpyHostToDevice, h->stream));
-            HIPCHK_OR(bad, hipMemcpyAsync(dr.get(), r + j0, sizeof(float) * (size_t)c, hipMemcpyHostToDevice, h->stream));
-            if ((rc = pairs_sse_sync(h, "rmse_pairs", du, di, dr, c, scratch, &s))) return rc;  // (the staging buffers are reused)
+            HIPCHK_OR(bad, copy_up(st.du, u + j0, (size_t)c, h->stream));
+            HIPCHK_OR(bad, copy_up(st.di, i + j0, (size_t)c, h->stream));
+            HIPCHK_OR(bad, copy_up(st.dr, r + j0, (size_t)c, h->stream));
+            if ((rc = pairs_sse_sync(h, "rmse_pairs", st, c, &s))) return rc;  // (the staging buffers are reused)
             total = j0 == 0 ? s : total + s;
         }
         *rmse = std::sqrt(total / (double)n);
@@ -696,88 +596,18 @@ int mfsgd_train_early_stop(mfsgd_handle* h, int32_t max_epochs, int32_t patience
                 *best_epoch = e;
                 bad_epochs = 0;
                 if (restore_best) {
-                    HIPCHK_OR(bad, hipMemcpyAsync(snap_p.get(), h->dP.get(), h->p_bytes(), hipMemcpyDeviceToDevice, h->stream));
-                    HIPCHK_OR(bad, hipMemcpyAsync(snap_q.get(), h->dQ.get(), h->q_bytes(), hipMemcpyDeviceToDevice, h->stream));
+                    HIPCHK_OR(bad, hipMemcpyAsync(snap_p.get(), h->dP.data(), h->p_bytes(), hipMemcpyDeviceToDevice, h->stream));
+                    HIPCHK_OR(bad, hipMemcpyAsync(snap_q.get(), h->dQ.data(), h->q_bytes(), hipMemcpyDeviceToDevice, h->stream));
                 }
             } else if (++bad_epochs >= patience) {
                 break;
             }
         }
         if (restore_best && *best_epoch >= 0 && *best_epoch != *epochs_run - 1) {
-            HIPCHK_OR(bad, hipMemcpyAsync(h->dP.get(), snap_p.get(), h->p_bytes(), hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK_OR(bad, hipMemcpyAsync(h->dQ.get(), snap_q.get(), h->q_bytes(), hipMemcpyDeviceToDevice, h->stream));
+            HIPCHK_OR(bad, hipMemcpyAsync(h->dP.data(), snap_p.get(), h->p_bytes(), hipMemcpyDeviceToDevice, h->stream));
+            HIPCHK_OR(bad, hipMemcpyAsync(h->dQ.data(), snap_q.get(), h->q_bytes(), hipMemcpyDeviceToDevice, h->stream));
         }
         HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // the snapshot is freed behind this
-        return MFSGD_OK;
-    });
-}
-
-int mfsgd_online_levels(mfsgd_handle* h, const int32_t* u, const int32_t* i, int64_t n, int32_t* level, mfsgd_online_info* info) {
-    return guarded(h, "online_levels", [&]() -> int {
-        if (const int rc = check_online_pairs(h, "online_levels", u, i, n)) return rc;
-        mfsgd_online_info got{};
-        got.n = n;
-        std::vector<int32_t> own, count;
-        if (!level && n > 0) own.resize((size_t)std::min(n, kOnlinePiece));
-        for (int64_t j0 = 0; j0 < n; j0 += kOnlinePiece) {
-            const int64_t c = std::min(kOnlinePiece, n - j0);
-            int32_t* lv = level ? level + j0 : own.data();
-            const int32_t n_levels = online_levels_of(h, u + j0, i + j0, c, lv);
-            count.assign((size_t)n_levels + 1, 0);  // (as a level_ptr: entry l + 1 counts level l)
-            for (int64_t j = 0; j < c; ++j) ++count[(size_t)lv[j] + 1];
-            for (int32_t l = 0; l < n_levels; ++l) count[(size_t)l + 1] += count[(size_t)l];
-            online_count(&got, count.data(), n_levels);
-        }
-        if (info) *info = got;
-        return MFSGD_OK;
-    });
-}
-
-int mfsgd_apply_ratings(mfsgd_handle* h, const int32_t* u, const int32_t* i, const float* r, int64_t n, float* err,
-                        mfsgd_online_info* info) {
-    return guarded(h, "apply_ratings", [&]() -> int {
-        int rc = check_online_pairs(h, "apply_ratings", u, i, n);
-        if (rc) return rc;
-        if (n > 0 && !r) return fail(h, MFSGD_ERR_INVALID_ARG, "apply_ratings: r is null");
-        if ((rc = check_reads_factors(h, "apply_ratings"))) return rc;
-        mfsgd_online_info got{};
-        got.n = n;
-        if (n == 0) {
-            if (info) *info = got;
-            return MFSGD_OK;
-        }
-        if ((rc = factors_to_device(h))) return rc;
-        auto bad = [h](hipError_t e) { return serve_fail(h, "apply_ratings: ", e); };
-        const size_t piece = (size_t)std::min(n, kOnlinePiece);
-        DevBuf du, di, dr, dorig, dptr, derr;  // sized by the largest piece; gone when this returns, whichever way
-        if ((rc = dev_alloc(h, du, sizeof(int32_t) * piece))) return rc;
-        if ((rc = dev_alloc(h, di, sizeof(int32_t) * piece))) return rc;
-        if ((rc = dev_alloc(h, dr, sizeof(float) * piece))) return rc;
-        if ((rc = dev_alloc(h, dorig, sizeof(int32_t) * piece))) return rc;
-        if ((rc = dev_alloc(h, dptr, sizeof(int32_t) * (piece + 1)))) return rc;
-        if (err && (rc = dev_alloc(h, derr, sizeof(float) * piece))) return rc;
-        const float lr = h->cfg.lr, c1 = 1.0f - h->cfg.lr * h->cfg.lambda;
-        OnlinePiece pc;
-        for (int64_t j0 = 0; j0 < n; j0 += kOnlinePiece) {
-            const int64_t c = std::min(kOnlinePiece, n - j0);
-            online_sort_piece(h, u + j0, i + j0, r + j0, c, pc);
-            online_count(&got, pc.level_ptr.data(), pc.n_levels);
-            HIPCHK_OR(bad, hipMemcpyAsync(du.get(), pc.u.data(), sizeof(int32_t) * (size_t)c, hipMemcpyHostToDevice, h->stream));
-            HIPCHK_OR(bad, hipMemcpyAsync(di.get(), pc.i.data(), sizeof(int32_t) * (size_t)c, hipMemcpyHostToDevice, h->stream));
-            HIPCHK_OR(bad, hipMemcpyAsync(dr.get(), pc.r.data(), sizeof(float) * (size_t)c, hipMemcpyHostToDevice, h->stream));
-            HIPCHK_OR(bad, hipMemcpyAsync(dorig.get(), pc.orig.data(), sizeof(int32_t) * (size_t)c, hipMemcpyHostToDevice, h->stream));
-            HIPCHK_OR(bad, hipMemcpyAsync(dptr.get(), pc.level_ptr.data(), sizeof(int32_t) * ((size_t)pc.n_levels + 1),
-                                          hipMemcpyHostToDevice, h->stream));
-            HIPCHK_OR(bad, online_launches(pc.level_ptr, pc.n_levels, h->geo.L, &got.launches, [&](int32_t l0, int32_t l1, int32_t wgs) {
-                return launch_apply_levels(h->geo.L, h->dP.as<float>(), h->dQ.as<float>(), du.as<const int32_t>(),
-                                           di.as<const int32_t>(), dr.as<const float>(), dorig.as<const int32_t>(),
-                                           dptr.as<const int32_t>(), l0, l1, wgs, h->cfg.k, lr, c1, err ? derr.as<float>() : nullptr,
-                                           h->stream);
-            }));
-            if (err) HIPCHK_OR(bad, hipMemcpyAsync(err + j0, derr.get(), sizeof(float) * (size_t)c, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // the staging buffers, the host's and the device's, are reused
-        }
-        if (info) *info = got;
         return MFSGD_OK;
     });
 }
@@ -843,12 +673,12 @@ int mfsgd_debug_epoch_profile(mfsgd_handle* h, uint64_t* out, int32_t* n_workgro
         if (p.persistent_np <= 0) return fail(h, MFSGD_ERR_STATE, "debug_epoch_profile: persistent kernel not in use");
         const size_t words = (size_t)p.persistent_np * 16;
         if ((rc = dev_alloc(h, p.d_sse_partial, std::max(words * sizeof(uint64_t), sizeof(double) * p.sched.cells.size())))) return rc;
-        CellLaunch a = make_launch(h, p, h->dQ.as<float>());
+        CellLaunch a = make_launch(h, p, h->dQ.data());
         a.grid = p.persistent_np;
         a.diag = true;
         a.sse_partial = p.d_sse_partial.as<double>();
         HIPCHK(h, hipMemsetAsync(p.d_sse_partial.get(), 0, words * sizeof(uint64_t), h->stream));
-        HIPCHK(h, launch_epoch_persistent(h->geo.L, p.sched.W, a, p.sched.B, p.d_sync.as<unsigned>(), abort_word(p), h->stream));
+        HIPCHK(h, launch_epoch_persistent(h->geo.L, p.sched.W, a, p.sched.B, p.d_sync.data(), abort_word(p), h->stream));
         HIPCHK(h, hipMemcpyAsync(out, p.d_sse_partial.get(), words * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         *n_workgroups = p.persistent_np;
@@ -908,7 +738,7 @@ int mfsgd_debug_round_stamps(mfsgd_handle* h, int32_t part, int32_t round, uint6
             int rc2 = dev_alloc(h, p.d_sse_partial, words * sizeof(uint64_t));
             if (rc2) return rc2;
         }
-        CellLaunch a = make_launch(h, p, h->dQ.as<float>());
+        CellLaunch a = make_launch(h, p, h->dQ.data());
         a.rd = round;
         a.diag = true;
         HIPCHK(h, hipMemsetAsync(p.d_sse_partial.get(), 0, words * sizeof(uint64_t), h->stream));
