@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver; + mfsgd_set_validation, mfsgd_validation_size, mfsgd_validation_rmse, mfsgd_rmse_pairs, mfsgd_train_early_stop; + mfsgd_row_inv_norms, mfsgd_similar_items, mfsgd_similar_users, mfsgd_similar_rows; + mfsgd_online_levels, mfsgd_apply_ratings; + mfsgd_fold_in_items, mfsgd_append_users, mfsgd_append_items, mfsgd_reserve_rows, mfsgd_get_capacity; + mfsgd_recommend_among, mfsgd_recommend_rows_among, mfsgd_debug_serve_seconds; + mfsgd_set_seen, mfsgd_mark_seen, mfsgd_clear_seen, mfsgd_seen_size, mfsgd_get_seen, mfsgd_recommend_unseen, mfsgd_recommend_unseen_among, mfsgd_rank_items_unseen, mfsgd_evaluate_ranking_unseen; + mfsgd_sample_unseen (additions: no existing call changed) */
+#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver; + mfsgd_set_validation, mfsgd_validation_size, mfsgd_validation_rmse, mfsgd_rmse_pairs, mfsgd_train_early_stop; + mfsgd_row_inv_norms, mfsgd_similar_items, mfsgd_similar_users, mfsgd_similar_rows; + mfsgd_online_levels, mfsgd_apply_ratings; + mfsgd_fold_in_items, mfsgd_append_users, mfsgd_append_items, mfsgd_reserve_rows, mfsgd_get_capacity; + mfsgd_recommend_among, mfsgd_recommend_rows_among, mfsgd_debug_serve_seconds; + mfsgd_set_seen, mfsgd_mark_seen, mfsgd_clear_seen, mfsgd_seen_size, mfsgd_get_seen, mfsgd_recommend_unseen, mfsgd_recommend_unseen_among, mfsgd_rank_items_unseen, mfsgd_evaluate_ranking_unseen; + mfsgd_sample_unseen; + mfsgd_triple_levels, mfsgd_apply_triples, mfsgd_bpr_weights (additions: no existing call changed) */
 
 typedef enum mfsgd_status {
     MFSGD_OK = 0,
@@ -108,7 +108,7 @@ int mfsgd_create(const mfsgd_config* cfg, mfsgd_handle** out);
 /* Java: close(). NULL is allowed. */
 void mfsgd_destroy(mfsgd_handle* h);
 /* Message of the last failure on this handle (h == NULL: of the last failed
- * mfsgd_create or mfsgd_ranking_metrics_from_ranks on this thread).  Never NULL;
+ * mfsgd_create, mfsgd_ranking_metrics_from_ranks or mfsgd_bpr_weights on this thread).  Never NULL;
  * valid until the next call. */
 const char* mfsgd_last_error(const mfsgd_handle* h);
 
@@ -553,6 +553,56 @@ int mfsgd_online_levels(mfsgd_handle* h, const int32_t* u, const int32_t* i, int
                         int32_t* level /* nullable */, mfsgd_online_info* info /* nullable */);
 int mfsgd_apply_ratings(mfsgd_handle* h, const int32_t* u, const int32_t* i, const float* r, int64_t n,
                         float* err /* nullable */, mfsgd_online_info* info /* nullable */);
+
+/* ---- pairwise ranking (BPR): (user, positive item, negative item) triples applied in the order given ------------------
+ * mfsgd_apply_triples applies (u[x], i[x], j[x]), x = 0 .. n - 1, to the live P and Q on the device, each with one step
+ * of Bayesian personalised ranking at the handle's current lr and lambda.  Everything is fp32,
+ * round to nearest even, subnormals kept, nothing contracted except the fmas written here; dot is the canonical dot, the
+ * bits mfsgd_predict returns.  With p = P[u[x]], qi = Q[i[x]], qj = Q[j[x]], all three read before anything is written:
+ *     x  = dot(p, qi) - dot(p, qj)                    the margin before the update
+ *     g  = lsig(x)                                    = 1 / (1 + e^x) = sigma(-x)
+ *     s  = lr * g;   c = 1 - lr * lambda
+ *     P[u][f] = fma( s, qi[f] - qj[f], c * p[f])
+ *     Q[i][f] = fma( s, p[f],          c * qi[f])
+ *     Q[j][f] = fma(-s, p[f],          c * qj[f])
+ * lsig is a pure function of the bits of x:
+ *     x is NaN:  g = 0x7FC00000
+ *     t  = x > 80 ? 80 : (x < -80 ? -80 : x)
+ *     n  = rintf(t * 0x3FB8AA3B)                      1.44269502f, ties to even
+ *     r  = fma(n, -0.693359375f, t);  r = fma(n, 2.12194440e-4f, r)
+ *     q  = 1.9875691500e-4f
+ *     q  = fma(q, r, 1.3981999507e-3f); q = fma(q, r, 8.3334519073e-3f); q = fma(q, r, 4.1665795894e-2f)
+ *     q  = fma(q, r, 1.6666665459e-1f); q = fma(q, r, 5.0000001201e-1f)
+ *     e  = fma(q, r * r, r) + 1.0f
+ *     y  = e * (the float whose bits are (int(n) + 127) << 23)      exact: |n| <= 116
+ *     g  = 1.0f / (1.0f + y)                          addition and division each correctly rounded
+ * (within 2.48 ulp of 1 / (1 + exp(t)) and never increasing in x: DESIGN.md.)  mfsgd_bpr_weights computes g[a] =
+ * lsig(x[a]) on the host with the function the kernel compiles: it has no handle and needs no GPU (messages through
+ * mfsgd_last_error(NULL), "bpr_weights: ...": a negative n, a null array with n > 0).
+ * Afterwards P and Q are bit for bit the sequential loop above over the list, and margin (nullable, n floats) holds x of
+ * every triple: its margin under the rows as they were just before it.  Duplicate triples are allowed and give two steps.
+ * A NaN or Inf in a factor propagates as the arithmetic says.
+ * How it runs in parallel is mfsgd_apply_ratings' way with three rows per step: pieces of at most 2^20 consecutive
+ * triples, one after the other; within a piece level[x] = 0 if no earlier triple of the piece has user u[x], or has i[x]
+ * or j[x] in EITHER item position, else 1 + the largest level among the latest earlier triple with that user, the latest
+ * with i[x] as either item and the latest with j[x] as either item.  mfsgd_triple_levels returns those levels (host
+ * only: no GPU, no ratings, no factors; `level` nullable, n entries, each relative to its triple's piece).  Launches are
+ * counted as for ratings: one per level wider than a workgroup pass, one per run of narrower ones.  Per piece 16 bytes
+ * per triple and 4 per level go up (at most 20 per triple), and 4 per triple come down if margins are asked for.
+ * Checks, all before any device work, in this order.  MFSGD_ERR_INVALID_ARG ("apply_triples: ..." / "triple_levels:
+ * ..."): a negative n; a null array with n > 0; a user or item out of range under the current counts (the message names
+ * the triple); i[x] == j[x] (the message names the triple).  Then, mfsgd_apply_triples whatever n is, MFSGD_ERR_STATE as
+ * mfsgd_apply_ratings reports it: n_parts != 1, factors never initialised, no Q.  n == 0 is MFSGD_OK and touches
+ * nothing.  MFSGD_ERR_NO_DEVICE: a valid call with n > 0 and no usable GPU; there is never a CPU result.  A failed
+ * check leaves the factors untouched.
+ * The device buffers are sized by the largest piece and freed before the call returns, on every path.  The call leaves
+ * as they were: the stored ratings and their identity, every schedule and cached training graph, the held-out set and
+ * the seen-item index.  Should a HIP call fail between two pieces, the pieces before it stay applied.                  */
+int mfsgd_triple_levels(mfsgd_handle* h, const int32_t* u, const int32_t* i, const int32_t* j, int64_t n,
+                        int32_t* level /* nullable */, mfsgd_online_info* info /* nullable */);
+int mfsgd_apply_triples(mfsgd_handle* h, const int32_t* u, const int32_t* i, const int32_t* j, int64_t n,
+                        float* margin /* nullable */, mfsgd_online_info* info /* nullable */);
+int mfsgd_bpr_weights(const float* x, float* g, int64_t n);
 
 /* ---- growing a live model: rows appended to P and Q in place -----------------------------------------------------------
  * mfsgd_append_users / mfsgd_append_items give the model n_new more users / items: the new rows take the indices

@@ -159,6 +159,9 @@ SIGNATURES = {
                                          _i32p, _i32p]),
     "mfsgd_online_levels": (C.c_int, [_H, _i32p, _i32p, C.c_int64, _i32p, C.POINTER(OnlineInfo)]),
     "mfsgd_apply_ratings": (C.c_int, [_H, _i32p, _i32p, _f32p, C.c_int64, _f32p, C.POINTER(OnlineInfo)]),
+    "mfsgd_triple_levels": (C.c_int, [_H, _i32p, _i32p, _i32p, C.c_int64, _i32p, C.POINTER(OnlineInfo)]),
+    "mfsgd_apply_triples": (C.c_int, [_H, _i32p, _i32p, _i32p, C.c_int64, _f32p, C.POINTER(OnlineInfo)]),
+    "mfsgd_bpr_weights": (C.c_int, [_f32p, _f32p, C.c_int64]),
     "mfsgd_append_users": (C.c_int, [_H, C.c_int32, _f32p, C.c_int64, _i32p]),
     "mfsgd_append_items": (C.c_int, [_H, C.c_int32, _f32p, C.c_int64, _i32p]),
     "mfsgd_reserve_rows": (C.c_int, [_H, C.c_int32, C.c_int32]),

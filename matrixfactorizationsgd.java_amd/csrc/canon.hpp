@@ -2,14 +2,43 @@
 // the training / RMSE / predict kernels (epoch.hip, cells.hip, kernels.hip) and the top-N scorer (recommend.hip), so that
 // predict(), recommend() and the oracle agree bit for bit by construction.
 // Build every translation unit that includes this with -ffp-contract=off.
+// lsig, the logistic weight of the pairwise update, is the one function here that the host compiles too
+// (online_update.cpp, mfsgd_bpr_weights): everything behind it is device code.
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "records.hpp"
 
 #pragma clang fp contract(off)
 
 namespace mfsgd {
 namespace {
+
+// lsig(x) = 1 / (1 + e^x) = sigma(-x), a pure function of the bits of x ("Pairwise ranking"): x
+// clamped to [-80, 80] by compares and selects, e^t by Cody-Waite reduction (n = rint(t * log2 e), ln 2 in two parts)
+// and a degree-6 polynomial, scaled by 2^n exactly (|n| <= 116), then one correctly rounded addition and one
+// correctly rounded division.  No exp, no reciprocal approximation: host and device round every step alike.
+MFSGD_HOST_DEVICE inline float lsig(const float x) {
+    if (x != x) return __builtin_bit_cast(float, kQuietNaN);
+    const float t = x > 80.0f ? 80.0f : (x < -80.0f ? -80.0f : x);
+    const float n = __builtin_rintf(t * 1.44269502f);  // 0x3FB8AA3B; ties to even
+    float r = __builtin_fmaf(n, -0.693359375f, t);
+    r = __builtin_fmaf(n, 2.12194440e-4f, r);
+    float q = 1.9875691500e-4f;
+    q = __builtin_fmaf(q, r, 1.3981999507e-3f);
+    q = __builtin_fmaf(q, r, 8.3334519073e-3f);
+    q = __builtin_fmaf(q, r, 4.1665795894e-2f);
+    q = __builtin_fmaf(q, r, 1.6666665459e-1f);
+    q = __builtin_fmaf(q, r, 5.0000001201e-1f);
+    const float e = __builtin_fmaf(q, r * r, r) + 1.0f;
+    const float y = e * __builtin_bit_cast(float, (uint32_t)((int32_t)n + 127) << 23);
+    return 1.0f / (1.0f + y);
+}
+
+#if defined(__HIP__) || defined(__HIPCC__)
 
 template <int CTRL>
 __device__ __forceinline__ float dpp_move(float v) {
@@ -76,6 +105,8 @@ __device__ __forceinline__ float4 axpy_row(const float s, const float4 x, const 
     o.w = __builtin_fmaf(s, x.w, c * y.w);
     return o;
 }
+
+#endif  // device code
 
 }  // namespace
 }  // namespace mfsgd

@@ -1,5 +1,5 @@
 // kernels.hpp -- host-callable launchers of every kernel unit: epoch.hip, cells.hip, kernels.hip, foldin.hip,
-// online.hip, rehyper.hip, recommend.hip, rank.hip, seen.hip, sample.hip, similar.hip, validate.hip and grow.hip.
+// online.hip, pairwise.hip, rehyper.hip, recommend.hip, rank.hip, seen.hip, sample.hip, similar.hip, validate.hip and grow.hip.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -65,6 +65,14 @@ hipError_t launch_fold_in(int L, const float* F, float* rows, int k, const long 
 hipError_t launch_apply_levels(int L, float* P, float* Q, const int32_t* u, const int32_t* i, const float* r,
                                const int32_t* orig, const int32_t* level_ptr, int l0, int l1, int workgroups, int k,
                                float lr, float c, float* err, hipStream_t st);
+
+// pairwise.hip.  The same for the triples (u, i, jn) of a pairwise update ("Pairwise ranking (BPR)"): the
+// triples of a level share no row of P and no row of Q in either item position, and i[t] != jn[t]; each gets the
+// three-row update of section 3, and margin[orig[t]] (margin nullable) the margin x before it.  Levels, workgroups,
+// what the caller checks and the stream are launch_apply_levels'.
+hipError_t launch_apply_triple_levels(int L, float* P, float* Q, const int32_t* u, const int32_t* i, const int32_t* jn,
+                                      const int32_t* orig, const int32_t* level_ptr, int l0, int l1, int workgroups, int k,
+                                      float lr, float c, float* margin, hipStream_t st);
 
 // rehyper.hip.  Re-bakes lr and c = 1 - lr*lambda into the entries of a schedule on the device, in place: afterwards
 // they are byte for byte what the packers write for those values (schedule.cpp, rehyper_schedule, is the host's form).

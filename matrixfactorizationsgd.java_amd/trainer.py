@@ -116,6 +116,18 @@ def ranking_metrics(users, ranks, topn):
     return out.as_dict()
 
 
+def bpr_weights(x):
+    """mfsgd_bpr_weights (host only, needs no model and no GPU): float32 g = lsig(x) = 1 / (1 + e^x) for every margin in
+    x, by the function the pairwise kernel compiles (include/mfsgd.h, "pairwise ranking"): the weight of a BPR step."""
+    xx = _f32(x)
+    g = np.empty(xx.shape, np.float32)
+    lib = _lib.load_library()
+    rc = lib.mfsgd_bpr_weights(_p(xx, C.c_float), _p(g, C.c_float), xx.size)
+    if rc != 0:
+        raise MfsgdError(rc, lib.mfsgd_last_error(None).decode())
+    return g
+
+
 def _pairs(a, b, what):
     """Two int32 1-d arrays of one length (None: no pairs)."""
     aa, bb = (np.empty(0, np.int32),) * 2 if a is None else (_i32(a), _i32(b))
@@ -371,6 +383,77 @@ class MatrixFactorizationSGD:
         self._check(self._lib.mfsgd_online_levels(self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32), uu.size,
                                                   _p(levels, C.c_int32), C.byref(out)))
         return levels, out.as_dict()
+
+    # -- pairwise ranking, BPR (include/mfsgd.h, "pairwise ranking") ----------------
+    @staticmethod
+    def _index_triples(u, i, j):
+        uu, ii, jj = _i32(np.atleast_1d(u)), _i32(np.atleast_1d(i)), _i32(np.atleast_1d(j))
+        if uu.ndim != 1 or uu.shape != ii.shape or uu.shape != jj.shape:
+            raise ValueError("u, i and j must be three 1-d arrays of the same length")
+        return uu, ii, jj
+
+    def triple_levels(self, u, i, j):
+        """(levels int32[n], dict(n, pieces, levels, max_width, launches = 0)): the dependency level of every triple
+        inside its piece of 2^20, as partial_fit_pairwise would run the list (mfsgd_triple_levels).  Host only: needs no
+        GPU, no ratings and no factors."""
+        uu, ii, jj = self._index_triples(u, i, j)
+        levels = np.empty(uu.size, np.int32)
+        out = _lib.OnlineInfo()
+        self._check(self._lib.mfsgd_triple_levels(self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32), _p(jj, C.c_int32),
+                                                  uu.size, _p(levels, C.c_int32), C.byref(out)))
+        return levels, out.as_dict()
+
+    def partial_fit_pairwise(self, u, i, j, *, margins=False, info=False):
+        """Applies the triples (u[x], i[x], j[x]) -- user, an item the user prefers, an item the user does not -- to the
+        live model in the order given, one BPR step each (mfsgd_apply_triples): bit for bit the sequential loop, at the
+        current lr and lambda.  i[x] == j[x] is refused.  The stored ratings, their schedules, the held-out set and the
+        seen-item index are not touched.  margins=True returns float32[n], each triple's margin dot(p, qi) - dot(p, qj)
+        just before its own update; info=True returns dict(n, pieces, levels, max_width, launches); both: (margins,
+        info); neither: None."""
+        uu, ii, jj = self._index_triples(u, i, j)
+        x = np.empty(uu.size, np.float32) if margins else None
+        out = _lib.OnlineInfo()
+        self._check(self._lib.mfsgd_apply_triples(self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32), _p(jj, C.c_int32),
+                                                  uu.size, None if x is None else _p(x, C.c_float), C.byref(out)))
+        res = tuple(a for a, on in ((x, margins), (out.as_dict(), info)) if on)
+        return None if not res else res[0] if len(res) == 1 else res
+
+    def fit_bpr(self, u, i, epochs, *, seed=0, first_epoch=0, stats=True):
+        """Trains on one-class data with Bayesian personalised ranking: (u[x], i[x]) are the positives, duplicates
+        allowed, and every epoch pairs each of them with one freshly drawn item its user has not seen and takes one
+        pairwise step per positive, in the order given -- pass the positives shuffled: the order is the caller's, and a
+        list sorted by user or item makes long dependency chains and a poor SGD order alike.
+        Unseen means unseen by the seen-item index, not by (u, i).  A handle without an index gets set_seen(u, i), and
+        keeps it; an index the handle already has is used as it is, so held-out positives put there first are never
+        drawn.  Factors that were never initialised are seeded, as in train().
+        Epoch e, counted from first_epoch: J = sample_unseen(u, 1, seed, first=e * n); the rows whose draw is -1 (users
+        who have seen everything) are dropped for that epoch; partial_fit_pairwise(u, i, J) of the rest.  Seed and epoch
+        number alone decide the draws: epochs=a followed by epochs=b, first_epoch=a is epochs=a + b bit for bit.  The
+        stored rating set is not touched.
+        Returns, with stats, dict(loss, auc), float64[epochs] each, from the margins x every triple had just before its
+        own step: the mean of log1p(exp(-x)), and the share of triples with x > 0.  Without stats: None."""
+        uu, ii = _pairs(np.atleast_1d(u), np.atleast_1d(i), "u and i")
+        epochs, n = int(epochs), uu.size
+        if epochs < 0:
+            raise ValueError("epochs must not be negative")
+        if self.seen_size() < 0:
+            self.set_seen(uu, ii)
+        if not self._initialised:
+            self.init_factors()
+        loss, auc = np.zeros(epochs, np.float64), np.zeros(epochs, np.float64)
+        jj = np.empty((n, 1), np.int32)
+        for e in range(epochs):
+            self._sample_unseen_into(uu, 1, seed, (int(first_epoch) + e) * n, jj)
+            J = jj[:, 0]
+            if n and J.min() < 0:  # users who have seen everything have no negatives
+                keep = J >= 0
+                x = self.partial_fit_pairwise(uu[keep], ii[keep], J[keep], margins=stats)
+            else:
+                x = self.partial_fit_pairwise(uu, ii, J, margins=stats)
+            if stats and x.size:
+                x = x.astype(np.float64)
+                loss[e], auc[e] = np.logaddexp(0.0, -x).mean(), (x > 0).mean()
+        return dict(loss=loss, auc=auc) if stats else None
 
     def train_timed(self, epochs):
         """(elapsed device milliseconds, kernel launches) for `epochs` passes."""
