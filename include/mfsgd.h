@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver; + mfsgd_set_validation, mfsgd_validation_size, mfsgd_validation_rmse, mfsgd_rmse_pairs, mfsgd_train_early_stop; + mfsgd_row_inv_norms, mfsgd_similar_items, mfsgd_similar_users, mfsgd_similar_rows; + mfsgd_online_levels, mfsgd_apply_ratings; + mfsgd_fold_in_items, mfsgd_append_users, mfsgd_append_items, mfsgd_reserve_rows, mfsgd_get_capacity; + mfsgd_recommend_among, mfsgd_recommend_rows_among, mfsgd_debug_serve_seconds; + mfsgd_set_seen, mfsgd_mark_seen, mfsgd_clear_seen, mfsgd_seen_size, mfsgd_get_seen, mfsgd_recommend_unseen, mfsgd_recommend_unseen_among, mfsgd_rank_items_unseen, mfsgd_evaluate_ranking_unseen; + mfsgd_sample_unseen; + mfsgd_triple_levels, mfsgd_apply_triples, mfsgd_bpr_weights (additions: no existing call changed) */
+#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver; + mfsgd_set_validation, mfsgd_validation_size, mfsgd_validation_rmse, mfsgd_rmse_pairs, mfsgd_train_early_stop; + mfsgd_row_inv_norms, mfsgd_similar_items, mfsgd_similar_users, mfsgd_similar_rows; + mfsgd_online_levels, mfsgd_apply_ratings; + mfsgd_fold_in_items, mfsgd_append_users, mfsgd_append_items, mfsgd_reserve_rows, mfsgd_get_capacity; + mfsgd_recommend_among, mfsgd_recommend_rows_among, mfsgd_debug_serve_seconds; + mfsgd_set_seen, mfsgd_mark_seen, mfsgd_clear_seen, mfsgd_seen_size, mfsgd_get_seen, mfsgd_recommend_unseen, mfsgd_recommend_unseen_among, mfsgd_rank_items_unseen, mfsgd_evaluate_ranking_unseen; + mfsgd_sample_unseen; + mfsgd_triple_levels, mfsgd_apply_triples, mfsgd_bpr_weights; + mfsgd_sample_unseen_hard (additions: no existing call changed) */
 
 typedef enum mfsgd_status {
     MFSGD_OK = 0,
@@ -368,6 +368,32 @@ int mfsgd_get_seen(mfsgd_handle* h, const int32_t* users, int32_t n_users, int64
  * all of it freed before the call returns, on every path -- mfsgd_debug_device_bytes is the same before and after.     */
 int mfsgd_sample_unseen(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first,
                         int32_t* out_items /* n x m, row-major */);
+/* mfsgd_sample_unseen_hard: hard negatives for pairwise ranking (dynamic negative sampling).  For each row x, the m
+ * candidates mfsgd_sample_unseen would draw for users[x] are drawn, scored under the factors as they are now, and the one
+ * the model likes best is returned: the negative a BPR step learns most from.  The candidates never exist in memory: 4
+ * bytes per row go up and 4 to 12 come down, whatever m is.
+ * Candidates.  The candidates of row x are exactly row x of mfsgd_sample_unseen(users, n, m, seed, first): candidate d has
+ * the counter first + x * m + d, the same mix and the same search, off the index where it lies.
+ * Score.  score(d) = dot(P[users[x]], Q[candidate d]), the canonical dot: the bits mfsgd_predict returns.
+ * Pick.  The candidate with the largest non-NaN score.  Scores that compare equal as floats (-0.0 == +0.0) go to the
+ * smaller d; a NaN score loses to every non-NaN score; if all m scores are NaN the pick is d = 0.  The rule does not
+ * depend on the order in which candidates are examined.
+ * Outputs.  out_items[x] is the picked item, out_scores[x] (nullable) its score bits, out_draw[x] (nullable) its d.  A
+ * user who has seen everything gives item -1, score 0x7FC00000 and draw -1.  With m = 1 the items are
+ * mfsgd_sample_unseen's column and the scores mfsgd_predict's; rows [a, b) of a call are the call on users + a with
+ * first + a * m.
+ * Checks, all before any device work, in this order ("sample_unseen_hard: ..."): MFSGD_ERR_INVALID_ARG for a negative n;
+ * for m < 1; for a negative first, or first + n * m above 2^63 - 1; for null users or out_items with n > 0.  Then
+ * MFSGD_ERR_STATE, whatever n is, for n_parts != 1, for a handle without an index ("no seen set"), and for factors that
+ * were never initialised, set or loaded, or no Q after mfsgd_init_p_offset.  Then n == 0 is MFSGD_OK and touches nothing.
+ * Then MFSGD_ERR_INVALID_ARG for a user outside [0, n_users); the message names the row, and the outputs are untouched.
+ * A valid call with n > 0 and no usable GPU is MFSGD_ERR_NO_DEVICE, an empty index included: there is never a CPU result.
+ * Modifies neither the model nor the index, nor any schedule or cached graph (factors still staged on the host move to
+ * the device first, as for any call that reads them).  The users go up and the picks come down in pieces of whole rows of
+ * at most 2^22 candidates (a row with more is a piece of its own), all staging freed before the call returns, on every
+ * path -- mfsgd_debug_device_bytes is the same before and after.                                                       */
+int mfsgd_sample_unseen_hard(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first,
+                             int32_t* out_items /* n */, float* out_scores /* nullable, n */, int32_t* out_draw /* nullable, n */);
 /* The serving calls against the index.  Each is the call it is named after -- mfsgd_recommend_excluding,
  * mfsgd_recommend_among, mfsgd_rank_items, mfsgd_evaluate_ranking -- given the index's pairs as its exclusion pairs:
  * order, ties, score bits, padding with -1 / NaN, the rule that a ranked pair's own item counts as eligible even if

@@ -138,6 +138,7 @@ SIGNATURES = {
     "mfsgd_seen_size": (C.c_int, [_H, _i64p]),
     "mfsgd_get_seen": (C.c_int, [_H, _i32p, C.c_int32, _i64p, _i32p, C.c_int64]),
     "mfsgd_sample_unseen": (C.c_int, [_H, _i32p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, _i32p]),
+    "mfsgd_sample_unseen_hard": (C.c_int, [_H, _i32p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, _i32p, _f32p, _i32p]),
     "mfsgd_recommend_unseen": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i32p, _f32p]),
     "mfsgd_recommend_unseen_among": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i64p, _i32p, C.c_int64, _i32p, _f32p]),
     "mfsgd_rank_items_unseen": (C.c_int, [_H, _i32p, _i32p, C.c_int64, _i32p]),

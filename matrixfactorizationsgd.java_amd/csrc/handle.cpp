@@ -537,6 +537,13 @@ int mfsgd_sample_unseen(mfsgd_handle* h, const int32_t* users, int64_t n, int32_
     return guarded(h, "sample_unseen", [&]() -> int { return seen_sample(h, users, n, m, seed, first, out_items); });
 }
 
+int mfsgd_sample_unseen_hard(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first,
+                             int32_t* out_items, float* out_scores, int32_t* out_draw) {
+    return guarded(h, "sample_unseen_hard", [&]() -> int {
+        return seen_sample_hard(h, users, n, m, seed, first, out_items, out_scores, out_draw);
+    });
+}
+
 int mfsgd_debug_device_bytes(int64_t* live) {
     if (!live) return MFSGD_ERR_INVALID_ARG;
     *live = g_dev_live_bytes.load();

@@ -85,7 +85,8 @@ struct Seen {
 // Pairs (exclusions, candidates, seen pairs) per upload of a call that reads a caller's list: 32 MB of staging
 constexpr int64_t kExclChunk = (int64_t)1 << 22;
 // Draws per piece of mfsgd_sample_unseen, whose rows go up and whose draws come down in pieces of whole rows: 16 MB of
-// draws and at most as much of rows (one row that asks for more draws is a piece of its own)
+// draws and at most as much of rows (one row that asks for more draws is a piece of its own).  Candidates per piece of
+// mfsgd_sample_unseen_hard too, which stages its rows and picks alone
 constexpr int64_t kSampleChunk = (int64_t)1 << 22;
 
 // d_sync: done[B] words (kDoneStride apart), then {arrivals, generation, -, -} of the kernel's start-of-launch
@@ -223,6 +224,9 @@ int seen_update(mfsgd_handle* h, const char* name, bool merge, const int32_t* u,
 int seen_get(mfsgd_handle* h, const int32_t* users, int32_t n_users, int64_t* row_ptr, int32_t* items, int64_t items_capacity);
 // ... and of mfsgd_sample_unseen (the kernel is sample.hip's)
 int seen_sample(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first, int32_t* out_items);
+// ... and of mfsgd_sample_unseen_hard (the kernel is hardneg.hip's)
+int seen_sample_hard(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first, int32_t* out_items,
+                     float* out_scores, int32_t* out_draw);
 // ratings.cpp
 void default_item_map(mfsgd_handle* h);
 int prepare_compute(mfsgd_handle* h);  // ratings present; factors and every partition's schedule on the device

@@ -1,5 +1,6 @@
 // kernels.hpp -- host-callable launchers of every kernel unit: epoch.hip, cells.hip, kernels.hip, foldin.hip,
-// online.hip, pairwise.hip, rehyper.hip, recommend.hip, rank.hip, seen.hip, sample.hip, similar.hip, validate.hip and grow.hip.
+// online.hip, pairwise.hip, rehyper.hip, recommend.hip, rank.hip, seen.hip, sample.hip, hardneg.hip, similar.hip, validate.hip
+// and grow.hip.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -196,6 +197,16 @@ hipError_t seen_gather(const long long* off, const int32_t* items, const int32_t
 // without pairs) with the counter first + x, among n_items items; -1 where the user has seen them all.  n_draws < 2^31.
 hipError_t sample_unseen_draws(const long long* off, const int32_t* items, const int32_t* users, int64_t n_draws, int32_t m,
                                int32_t n_items, int64_t seed, uint64_t first, int32_t* out, hipStream_t st);
+
+// hardneg.hip.  Hard negatives (include/mfsgd.h, mfsgd_sample_unseen_hard): for each of the n rows of `users` (every one a
+// user of the index {off, items} and a row of P; off == nullptr: an index without pairs) the best-scoring of the m >= 1
+// candidates sample_unseen_draws gives that row for the same (m, n_items, seed, first), the score being dot(P[user],
+// Q[candidate]) (kp-padded rows; the bits launch_predict returns) and the pick the header's rule: out_items[x] the item,
+// out_scores[x] its score and out_draw[x] its d (either nullable); -1, 0x7FC00000 and -1 where the user has seen every
+// item.  n <= 2^22 (a piece).  Asynchronous on st.
+hipError_t launch_hard_negatives(int L, const float* P, const float* Q, const long long* off, const int32_t* items,
+                                 const int32_t* users, int64_t n, int32_t m, int32_t n_items, int64_t seed, uint64_t first,
+                                 int32_t* out_items, float* out_scores, int32_t* out_draw, hipStream_t st);
 
 // similar.hip.  out[x] = rn(row x) = 1 / sqrt(dot(row, row)), or 0 where that dot is 0, for the
 // n_rows kp-padded rows of M.  Asynchronous on st.

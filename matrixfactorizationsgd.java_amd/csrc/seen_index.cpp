@@ -217,4 +217,46 @@ int seen_sample(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int
     return MFSGD_OK;
 }
 
+// Body of mfsgd_sample_unseen_hard (handle.cpp): row x receives the best-scoring of the m draws seen_sample would give it,
+// scored under the factors as they are.  The rows go up and the picks come down in the pieces of seen_sample: whole rows,
+// at most kSampleChunk candidates each (a row with more is a piece of its own); nothing per candidate is ever stored.
+int seen_sample_hard(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first, int32_t* out_items,
+                     float* out_scores, int32_t* out_draw) {
+    if (n < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_hard: n is negative");
+    if (m < 1) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_hard: m is below 1");
+    if (first < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_hard: first is negative");
+    if (n > INT64_MAX / m || first > INT64_MAX - n * m)
+        return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_hard: first + n * m exceeds 2^63 - 1");
+    if (n > 0 && (!users || !out_items)) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_hard: users or out_items is null");
+    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "sample_unseen_hard: single-partition handles only");
+    if (!h->seen.present) return fail(h, MFSGD_ERR_STATE, "sample_unseen_hard: no seen set");
+    int rc = check_reads_factors(h, "sample_unseen_hard");
+    if (rc) return rc;
+    if (n == 0) return MFSGD_OK;
+    const int64_t x_bad = first_outside(users, n, h->cfg.n_users);
+    if (x_bad >= 0) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_hard: user " + std::to_string(x_bad) + " out of range");
+    if ((rc = factors_to_device(h))) return rc;
+    auto bad = [h](hipError_t e) { return serve_fail(h, "sample_unseen_hard: ", e); };
+    const Seen& s = h->seen;
+    const int64_t rows = std::min(n, std::max<int64_t>(1, kSampleChunk / m));
+    DevArray<int32_t> d_users, d_items, d_draw;
+    DevArray<float> d_scores;
+    if ((rc = dev_alloc(h, d_users, (size_t)rows)) || (rc = dev_alloc(h, d_items, (size_t)rows))) return rc;
+    if (out_scores && (rc = dev_alloc(h, d_scores, (size_t)rows))) return rc;
+    if (out_draw && (rc = dev_alloc(h, d_draw, (size_t)rows))) return rc;
+    for (int64_t x0 = 0; x0 < n; x0 += rows) {
+        const int64_t c = std::min(rows, n - x0);
+        HIPCHK_OR(bad, copy_up(d_users, users + x0, (size_t)c, h->stream));
+        HIPCHK_OR(bad, launch_hard_negatives(h->geo.L, h->dP.data(), h->dQ.data(), s.n > 0 ? s.off.data() : nullptr, s.items.data(),
+                                             d_users.data(), c, m, h->cfg.n_items, seed, (uint64_t)first + (uint64_t)(x0 * m),
+                                             d_items.data(), out_scores ? d_scores.data() : nullptr,
+                                             out_draw ? d_draw.data() : nullptr, h->stream));
+        HIPCHK_OR(bad, copy_down(out_items + x0, d_items, (size_t)c, h->stream));
+        if (out_scores) HIPCHK_OR(bad, copy_down(out_scores + x0, d_scores, (size_t)c, h->stream));
+        if (out_draw) HIPCHK_OR(bad, copy_down(out_draw + x0, d_draw, (size_t)c, h->stream));
+        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // (pageable memory: the staging is free for the next piece)
+    }
+    return MFSGD_OK;
+}
+
 }  // namespace mfsgd

@@ -418,7 +418,7 @@ class MatrixFactorizationSGD:
         res = tuple(a for a, on in ((x, margins), (out.as_dict(), info)) if on)
         return None if not res else res[0] if len(res) == 1 else res
 
-    def fit_bpr(self, u, i, epochs, *, seed=0, first_epoch=0, stats=True):
+    def fit_bpr(self, u, i, epochs, *, seed=0, first_epoch=0, stats=True, candidates=1, refresh=None):
         """Trains on one-class data with Bayesian personalised ranking: (u[x], i[x]) are the positives, duplicates
         allowed, and every epoch pairs each of them with one freshly drawn item its user has not seen and takes one
         pairwise step per positive, in the order given -- pass the positives shuffled: the order is the caller's, and a
@@ -430,17 +430,42 @@ class MatrixFactorizationSGD:
         who have seen everything) are dropped for that epoch; partial_fit_pairwise(u, i, J) of the rest.  Seed and epoch
         number alone decide the draws: epochs=a followed by epochs=b, first_epoch=a is epochs=a + b bit for bit.  The
         stored rating set is not touched.
+        candidates=m > 1 trains against hard negatives instead (dynamic negative sampling): each positive's negative is
+        the best-scoring of m unseen draws under the current factors (sample_unseen_hard), which keeps the steps from
+        dying out once most uniform negatives already rank below their positive.  Epoch e walks the positives in blocks
+        of `refresh` rows (None: n, one block per epoch); for each block [a, b): J = sample_unseen_hard(u[a:b], m, seed,
+        first=e * n * m + a * m) under the factors as the blocks before it left them, rows with -1 dropped,
+        partial_fit_pairwise of the rest.  The candidates do not depend on refresh, the picks do; a smaller refresh
+        picks against fresher factors and costs a call per block.  Splitting the epochs with first_epoch gives the same
+        bits here too.  candidates=1 is the uniform draw above and does not read the factors to draw.
         Returns, with stats, dict(loss, auc), float64[epochs] each, from the margins x every triple had just before its
         own step: the mean of log1p(exp(-x)), and the share of triples with x > 0.  Without stats: None."""
         uu, ii = _pairs(np.atleast_1d(u), np.atleast_1d(i), "u and i")
-        epochs, n = int(epochs), uu.size
+        epochs, n, m = int(epochs), uu.size, int(candidates)
         if epochs < 0:
             raise ValueError("epochs must not be negative")
+        if m < 1 or (refresh is not None and int(refresh) < 1):
+            raise ValueError("candidates and refresh must be at least 1")
         if self.seen_size() < 0:
             self.set_seen(uu, ii)
         if not self._initialised:
             self.init_factors()
         loss, auc = np.zeros(epochs, np.float64), np.zeros(epochs, np.float64)
+        if m > 1:
+            step = max(n, 1) if refresh is None else int(refresh)
+            for e in range(epochs):
+                xs = []
+                for a in range(0, n, step):
+                    bu, bi = uu[a:a + step], ii[a:a + step]
+                    J = self.sample_unseen_hard(bu, m, seed, ((int(first_epoch) + e) * n + a) * m)
+                    if J.min() < 0:  # users who have seen everything have no negatives
+                        keep = J >= 0
+                        bu, bi, J = bu[keep], bi[keep], J[keep]
+                    xs.append(self.partial_fit_pairwise(bu, bi, J, margins=stats))
+                x = np.concatenate(xs).astype(np.float64) if stats and xs else np.empty(0)
+                if x.size:
+                    loss[e], auc[e] = np.logaddexp(0.0, -x).mean(), (x > 0).mean()
+            return dict(loss=loss, auc=auc) if stats else None
         jj = np.empty((n, 1), np.int32)
         for e in range(epochs):
             self._sample_unseen_into(uu, 1, seed, (int(first_epoch) + e) * n, jj)
@@ -564,6 +589,25 @@ class MatrixFactorizationSGD:
         """sample_unseen(uu, ...) into `out`, a C-contiguous int32 array of uu.size * m entries."""
         self._check(self._lib.mfsgd_sample_unseen(self._handle(), _p(uu, C.c_int32), uu.size, int(m), int(seed), int(first),
                                                   _p(out, C.c_int32)))
+
+    def sample_unseen_hard(self, users, m, seed=0, first=0, *, scores=False, draws=False):
+        """int32 [len(users)]: for each row, the best-scoring of the m items sample_unseen(users, m, seed, first) draws for
+        it, under the factors as they are now (mfsgd_sample_unseen_hard: drawn, scored and picked on the device, nothing
+        per candidate comes down).  The score is predict's; equal scores go to the earlier draw, a NaN score loses to
+        every number; -1 for a user who has seen every item.  scores=True adds float32 [len(users)], each pick's score
+        (NaN with -1); draws=True adds int32 [len(users)], each pick's position d in its row of draws (-1 with -1); with
+        either the result is a tuple (items, scores, draws) without what was not asked for."""
+        uu = _i32(np.atleast_1d(users))
+        if uu.ndim != 1:
+            raise ValueError("users must be a 1-d array")
+        items = np.empty(uu.size, np.int32)
+        sc = np.empty(uu.size, np.float32) if scores else None
+        dr = np.empty(uu.size, np.int32) if draws else None
+        self._check(self._lib.mfsgd_sample_unseen_hard(self._handle(), _p(uu, C.c_int32), uu.size, int(m), int(seed), int(first),
+                                                       _p(items, C.c_int32), None if sc is None else _p(sc, C.c_float),
+                                                       None if dr is None else _p(dr, C.c_int32)))
+        res = tuple(a for a, on in ((items, True), (sc, scores), (dr, draws)) if on)
+        return res[0] if len(res) == 1 else res
 
     def fit_implicit(self, u, i, epochs, negatives=4, *, seed=0, pos=1.0, neg=0.0, first_epoch=0, rmse=True):
         """Trains on one-class data (clicks, plays, purchases): (u[x], i[x]) are the positives, duplicates allowed, and
