@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver; + mfsgd_set_validation, mfsgd_validation_size, mfsgd_validation_rmse, mfsgd_rmse_pairs, mfsgd_train_early_stop; + mfsgd_row_inv_norms, mfsgd_similar_items, mfsgd_similar_users, mfsgd_similar_rows; + mfsgd_online_levels, mfsgd_apply_ratings; + mfsgd_fold_in_items, mfsgd_append_users, mfsgd_append_items, mfsgd_reserve_rows, mfsgd_get_capacity; + mfsgd_recommend_among, mfsgd_recommend_rows_among, mfsgd_debug_serve_seconds; + mfsgd_set_seen, mfsgd_mark_seen, mfsgd_clear_seen, mfsgd_seen_size, mfsgd_get_seen, mfsgd_recommend_unseen, mfsgd_recommend_unseen_among, mfsgd_rank_items_unseen, mfsgd_evaluate_ranking_unseen; + mfsgd_sample_unseen; + mfsgd_triple_levels, mfsgd_apply_triples, mfsgd_bpr_weights; + mfsgd_sample_unseen_hard (additions: no existing call changed) */
+#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver; + mfsgd_set_validation, mfsgd_validation_size, mfsgd_validation_rmse, mfsgd_rmse_pairs, mfsgd_train_early_stop; + mfsgd_row_inv_norms, mfsgd_similar_items, mfsgd_similar_users, mfsgd_similar_rows; + mfsgd_online_levels, mfsgd_apply_ratings; + mfsgd_fold_in_items, mfsgd_append_users, mfsgd_append_items, mfsgd_reserve_rows, mfsgd_get_capacity; + mfsgd_recommend_among, mfsgd_recommend_rows_among, mfsgd_debug_serve_seconds; + mfsgd_set_seen, mfsgd_mark_seen, mfsgd_clear_seen, mfsgd_seen_size, mfsgd_get_seen, mfsgd_recommend_unseen, mfsgd_recommend_unseen_among, mfsgd_rank_items_unseen, mfsgd_evaluate_ranking_unseen; + mfsgd_sample_unseen; + mfsgd_triple_levels, mfsgd_apply_triples, mfsgd_bpr_weights; + mfsgd_sample_unseen_hard; + mfsgd_sample_unseen_violating, mfsgd_apply_triples_weighted, mfsgd_warp_weights (additions: no existing call changed) */
 
 typedef enum mfsgd_status {
     MFSGD_OK = 0,
@@ -108,7 +108,7 @@ int mfsgd_create(const mfsgd_config* cfg, mfsgd_handle** out);
 /* Java: close(). NULL is allowed. */
 void mfsgd_destroy(mfsgd_handle* h);
 /* Message of the last failure on this handle (h == NULL: of the last failed
- * mfsgd_create, mfsgd_ranking_metrics_from_ranks or mfsgd_bpr_weights on this thread).  Never NULL;
+ * mfsgd_create, mfsgd_ranking_metrics_from_ranks, mfsgd_bpr_weights or mfsgd_warp_weights on this thread).  Never NULL;
  * valid until the next call. */
 const char* mfsgd_last_error(const mfsgd_handle* h);
 
@@ -134,7 +134,9 @@ int mfsgd_set_ratings(mfsgd_handle* h, const int32_t* u, const int32_t* i, const
  * NaN that enters the library -- a factor given to mfsgd_set_factors,
  * mfsgd_load_factors, mfsgd_append_users, mfsgd_append_items or
  * mfsgd_dsgd_set_q, a rating given to mfsgd_set_ratings
- * (in the schedules) or mfsgd_apply_ratings -- is replaced by the quiet NaN
+ * (in the schedules) or mfsgd_apply_ratings, a weight given to
+ * mfsgd_apply_triples_weighted (lr * w is the step size of three factor rows)
+ * -- is replaced by the quiet NaN
  * 0x7FC00000: the training kernels use the word 0xFFFFFFFF, itself a NaN, as
  * "not posted yet" between two of their waves, and arithmetic hands a NaN
  * operand's payload on.  mfsgd_get_factors before any training therefore
@@ -394,6 +396,42 @@ int mfsgd_sample_unseen(mfsgd_handle* h, const int32_t* users, int64_t n, int32_
  * path -- mfsgd_debug_device_bytes is the same before and after.                                                       */
 int mfsgd_sample_unseen_hard(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first,
                              int32_t* out_items /* n */, float* out_scores /* nullable, n */, int32_t* out_draw /* nullable, n */);
+/* mfsgd_sample_unseen_violating: the negative of a WARP step (Weston's weighted approximate-rank pairwise loss).  For each
+ * row x, the m candidates mfsgd_sample_unseen would draw for users[x] are walked until one violates the margin against
+ * the row's positive pos_items[x] under the factors as they are now; that candidate is returned with the number of draws
+ * it took, from which the positive's rank is estimated.  The candidates never exist in memory: 8 bytes per row go up and
+ * 4 to 16 come down, whatever m is.
+ * The rule.  A pure function of seed and the row's counter range, the user's list, n_items and the factor bits.  For row
+ * x with u = users[x], i = pos_items[x], S the user's list of length s and cnt = n_items - s:
+ *     cand[d] = draw d of row x of mfsgd_sample_unseen(users, n, m, seed, first)    counter first + x * m + d, d = 0 .. m - 1
+ *     sp      = dot(P[u], Q[i])                  the canonical dot: mfsgd_predict's bits
+ *     x[d]    = sp - dot(P[u], Q[cand[d]])       one fp32 subtraction: the bits mfsgd_apply_triples reports as the margin
+ *                                                of (u, i, cand[d]) under these factors
+ *     viol(d) = cand[d] != i  and  x[d] < margin float compare: a NaN x never violates; -0.0 == +0.0; x == margin does not
+ *     pick    = the smallest d with viol(d)
+ *     out     = item cand[pick], draw pick, margin x[pick], rank max(1, cnt / (pick + 1))          (integer division)
+ *     no d violates:           item -1, draw m,  margin 0x7FC00000, rank 0
+ *     u has seen everything:   item -1, draw -1, margin 0x7FC00000, rank 0
+ * cand[d] != i is part of the rule: mfsgd_apply_triples refuses i == j, and the positive need not be in the index.  rank
+ * estimates how many of the cnt unseen items violate the margin: a violator at the first draw says nearly all, one at
+ * draw d + 1 about one in d + 1.  The rule names a d without fixing the order in which candidates are examined: the
+ * kernel skips the draws and the rows of Q past the pick, and no part of the result depends on what it skipped.  Rows
+ * [a, b) of a call are the call on users + a, pos_items + a with first + a * m.
+ * Checks, all before any device work, in this order ("sample_unseen_violating: ..."): MFSGD_ERR_INVALID_ARG for a negative
+ * n; for m < 1; for a NaN margin (+Inf and -Inf are valid: everything but x = +Inf or NaN violates, nothing does); for a
+ * negative first, or first + n * m above 2^63 - 1; for null users, pos_items or out_items with n > 0.  Then
+ * MFSGD_ERR_STATE, whatever n is, for n_parts != 1, for a handle without an index ("no seen set"), and for factors that
+ * were never initialised, set or loaded, or no Q after mfsgd_init_p_offset.  Then n == 0 is MFSGD_OK and touches nothing.
+ * Then MFSGD_ERR_INVALID_ARG for a user outside [0, n_users) or a positive outside [0, n_items); the message names the
+ * row, and the outputs are untouched.  A valid call with n > 0 and no usable GPU is MFSGD_ERR_NO_DEVICE, an empty index
+ * included: there is never a CPU result.  Modifies neither the model nor the index, nor any schedule or cached graph
+ * (factors still staged on the host move to the device first, as for any call that reads them).  The rows go up and the
+ * picks come down in pieces of whole rows of at most 2^22 candidates (a row with more is a piece of its own), all
+ * staging freed before the call returns, on every path -- mfsgd_debug_device_bytes is the same before and after.         */
+int mfsgd_sample_unseen_violating(mfsgd_handle* h, const int32_t* users, const int32_t* pos_items, int64_t n, int32_t m,
+                                  float margin, int64_t seed, int64_t first, int32_t* out_items /* n */,
+                                  int32_t* out_draw /* nullable, n */, float* out_margin /* nullable, n */,
+                                  int32_t* out_rank /* nullable, n */);
 /* The serving calls against the index.  Each is the call it is named after -- mfsgd_recommend_excluding,
  * mfsgd_recommend_among, mfsgd_rank_items, mfsgd_evaluate_ranking -- given the index's pairs as its exclusion pairs:
  * order, ties, score bits, padding with -1 / NaN, the rule that a ranked pair's own item counts as eligible even if
@@ -629,6 +667,24 @@ int mfsgd_triple_levels(mfsgd_handle* h, const int32_t* u, const int32_t* i, con
 int mfsgd_apply_triples(mfsgd_handle* h, const int32_t* u, const int32_t* i, const int32_t* j, int64_t n,
                         float* margin /* nullable */, mfsgd_online_info* info /* nullable */);
 int mfsgd_bpr_weights(const float* x, float* g, int64_t n);
+/* mfsgd_apply_triples_weighted is mfsgd_apply_triples with one line of the step replaced: the step size of triple x is
+ *     s = lr * w[x]                                   one fp32 multiply, at the handle's current lr
+ * and lsig is not evaluated; c, the three fmas, the pad columns (+0.0), the margin x = dot(p, qi) - dot(p, qj) returned in
+ * `margin`, the pieces of 2^20, the levels (exactly mfsgd_triple_levels: weights do not enter), the launches, `info`,
+ * what the call leaves untouched and the state and device errors are mfsgd_apply_triples' own code.  w[x] =
+ * mfsgd_bpr_weights of the margins reproduces mfsgd_apply_triples on triples that share no row; importance weights,
+ * LambdaRank-style weights, hinge losses and WARP (below) are host policy on top of it.  Zero, negative and infinite
+ * weights are plain arithmetic; a NaN weight becomes 0x7FC00000 at the door (see "factors" above) and makes the k
+ * columns of its three rows NaN.  At most 4 more bytes per triple go up.  Checks: mfsgd_apply_triples' in its order
+ * ("apply_triples_weighted: ..."), w being one of the arrays that must not be null when n > 0.
+ * mfsgd_warp_weights is the weight of a WARP step for the rank mfsgd_sample_unseen_violating estimated: w[a] = L(rank[a]),
+ * L(0) = 0 and L(r) = (float)(1.0/1 + 1.0/2 + ... + 1.0/r) for r > 0, the sum in fp64, added in ascending order and
+ * rounded to fp32 once (Weston's harmonic weight).  Host only: no handle, no GPU; one prefix table up to the largest rank
+ * of the call, not O(rank) per element.  MFSGD_ERR_INVALID_ARG (message through mfsgd_last_error(NULL), "warp_weights:
+ * ..."): a negative n, a null array with n > 0, a negative rank (the message names the entry; w is untouched).          */
+int mfsgd_apply_triples_weighted(mfsgd_handle* h, const int32_t* u, const int32_t* i, const int32_t* j, const float* w,
+                                 int64_t n, float* margin /* nullable */, mfsgd_online_info* info /* nullable */);
+int mfsgd_warp_weights(const int32_t* rank, float* w, int64_t n);
 
 /* ---- growing a live model: rows appended to P and Q in place -----------------------------------------------------------
  * mfsgd_append_users / mfsgd_append_items give the model n_new more users / items: the new rows take the indices

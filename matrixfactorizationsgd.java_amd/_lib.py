@@ -139,6 +139,8 @@ SIGNATURES = {
     "mfsgd_get_seen": (C.c_int, [_H, _i32p, C.c_int32, _i64p, _i32p, C.c_int64]),
     "mfsgd_sample_unseen": (C.c_int, [_H, _i32p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, _i32p]),
     "mfsgd_sample_unseen_hard": (C.c_int, [_H, _i32p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, _i32p, _f32p, _i32p]),
+    "mfsgd_sample_unseen_violating": (C.c_int, [_H, _i32p, _i32p, C.c_int64, C.c_int32, C.c_float, C.c_int64, C.c_int64, _i32p,
+                                                _i32p, _f32p, _i32p]),
     "mfsgd_recommend_unseen": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i32p, _f32p]),
     "mfsgd_recommend_unseen_among": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i64p, _i32p, C.c_int64, _i32p, _f32p]),
     "mfsgd_rank_items_unseen": (C.c_int, [_H, _i32p, _i32p, C.c_int64, _i32p]),
@@ -163,6 +165,8 @@ SIGNATURES = {
     "mfsgd_triple_levels": (C.c_int, [_H, _i32p, _i32p, _i32p, C.c_int64, _i32p, C.POINTER(OnlineInfo)]),
     "mfsgd_apply_triples": (C.c_int, [_H, _i32p, _i32p, _i32p, C.c_int64, _f32p, C.POINTER(OnlineInfo)]),
     "mfsgd_bpr_weights": (C.c_int, [_f32p, _f32p, C.c_int64]),
+    "mfsgd_apply_triples_weighted": (C.c_int, [_H, _i32p, _i32p, _i32p, _f32p, C.c_int64, _f32p, C.POINTER(OnlineInfo)]),
+    "mfsgd_warp_weights": (C.c_int, [_i32p, _f32p, C.c_int64]),
     "mfsgd_append_users": (C.c_int, [_H, C.c_int32, _f32p, C.c_int64, _i32p]),
     "mfsgd_append_items": (C.c_int, [_H, C.c_int32, _f32p, C.c_int64, _i32p]),
     "mfsgd_reserve_rows": (C.c_int, [_H, C.c_int32, C.c_int32]),

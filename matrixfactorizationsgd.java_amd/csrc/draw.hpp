@@ -1,6 +1,7 @@
 // draw.hpp -- the draw of mfsgd_sample_unseen (include/mfsgd.h) as device functions, integers only: ONE definition,
-// shared by sample.hip (every draw goes to memory) and hardneg.hip (the draws are scored and only the best leaves the
-// kernel), so that the candidates of mfsgd_sample_unseen_hard are mfsgd_sample_unseen's by construction.
+// shared by sample.hip (every draw goes to memory), hardneg.hip (the draws are scored and only the best leaves the
+// kernel) and warp.hip (the draws are walked to the first that violates a margin), so that the candidates of
+// mfsgd_sample_unseen_hard and mfsgd_sample_unseen_violating are mfsgd_sample_unseen's by construction.
 // A draw is a pure function of (seed, its counter c), the user's sorted, distinct list S (length s) and the item count:
 //     r   = draw_mix32(seed, c): the upper 32 bits of splitmix64's output for the state seed + golden * (c + 1)
 //     t   = (r * cnt) >> 32 with cnt = n_items - s: the rank of the draw among the unseen items, in [0, cnt)

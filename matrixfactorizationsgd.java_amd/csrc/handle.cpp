@@ -544,6 +544,14 @@ int mfsgd_sample_unseen_hard(mfsgd_handle* h, const int32_t* users, int64_t n, i
     });
 }
 
+int mfsgd_sample_unseen_violating(mfsgd_handle* h, const int32_t* users, const int32_t* pos_items, int64_t n, int32_t m,
+                                  float margin, int64_t seed, int64_t first, int32_t* out_items, int32_t* out_draw,
+                                  float* out_margin, int32_t* out_rank) {
+    return guarded(h, "sample_unseen_violating", [&]() -> int {
+        return seen_sample_violating(h, users, pos_items, n, m, margin, seed, first, out_items, out_draw, out_margin, out_rank);
+    });
+}
+
 int mfsgd_debug_device_bytes(int64_t* live) {
     if (!live) return MFSGD_ERR_INVALID_ARG;
     *live = g_dev_live_bytes.load();

@@ -86,7 +86,7 @@ struct Seen {
 constexpr int64_t kExclChunk = (int64_t)1 << 22;
 // Draws per piece of mfsgd_sample_unseen, whose rows go up and whose draws come down in pieces of whole rows: 16 MB of
 // draws and at most as much of rows (one row that asks for more draws is a piece of its own).  Candidates per piece of
-// mfsgd_sample_unseen_hard too, which stages its rows and picks alone
+// mfsgd_sample_unseen_hard and mfsgd_sample_unseen_violating too, which stage their rows and picks alone
 constexpr int64_t kSampleChunk = (int64_t)1 << 22;
 
 // d_sync: done[B] words (kDoneStride apart), then {arrivals, generation, -, -} of the kernel's start-of-launch
@@ -227,6 +227,9 @@ int seen_sample(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int
 // ... and of mfsgd_sample_unseen_hard (the kernel is hardneg.hip's)
 int seen_sample_hard(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first, int32_t* out_items,
                      float* out_scores, int32_t* out_draw);
+// ... and of mfsgd_sample_unseen_violating (the kernel is warp.hip's)
+int seen_sample_violating(mfsgd_handle* h, const int32_t* users, const int32_t* pos_items, int64_t n, int32_t m, float margin,
+                          int64_t seed, int64_t first, int32_t* out_items, int32_t* out_draw, float* out_margin, int32_t* out_rank);
 // ratings.cpp
 void default_item_map(mfsgd_handle* h);
 int prepare_compute(mfsgd_handle* h);  // ratings present; factors and every partition's schedule on the device

@@ -1,5 +1,5 @@
 // kernels.hpp -- host-callable launchers of every kernel unit: epoch.hip, cells.hip, kernels.hip, foldin.hip,
-// online.hip, pairwise.hip, rehyper.hip, recommend.hip, rank.hip, seen.hip, sample.hip, hardneg.hip, similar.hip, validate.hip
+// online.hip, pairwise.hip, rehyper.hip, recommend.hip, rank.hip, seen.hip, sample.hip, hardneg.hip, warp.hip, similar.hip, validate.hip
 // and grow.hip.
 #pragma once
 
@@ -70,10 +70,11 @@ hipError_t launch_apply_levels(int L, float* P, float* Q, const int32_t* u, cons
 // pairwise.hip.  The same for the triples (u, i, jn) of a pairwise update ("Pairwise ranking (BPR)"): the
 // triples of a level share no row of P and no row of Q in either item position, and i[t] != jn[t]; each gets the
 // three-row update of section 3, and margin[orig[t]] (margin nullable) the margin x before it.  Levels, workgroups,
-// what the caller checks and the stream are launch_apply_levels'.
+// what the caller checks and the stream are launch_apply_levels'.  w (nullable; one weight per triple, in the order of
+// u, and no NaN but 0x7FC00000): the step size of triple t is lr * w[t] in place of lr * lsig(x), the rest alike.
 hipError_t launch_apply_triple_levels(int L, float* P, float* Q, const int32_t* u, const int32_t* i, const int32_t* jn,
-                                      const int32_t* orig, const int32_t* level_ptr, int l0, int l1, int workgroups, int k,
-                                      float lr, float c, float* margin, hipStream_t st);
+                                      const float* w, const int32_t* orig, const int32_t* level_ptr, int l0, int l1,
+                                      int workgroups, int k, float lr, float c, float* margin, hipStream_t st);
 
 // rehyper.hip.  Re-bakes lr and c = 1 - lr*lambda into the entries of a schedule on the device, in place: afterwards
 // they are byte for byte what the packers write for those values (schedule.cpp, rehyper_schedule, is the host's form).
@@ -207,6 +208,17 @@ hipError_t sample_unseen_draws(const long long* off, const int32_t* items, const
 hipError_t launch_hard_negatives(int L, const float* P, const float* Q, const long long* off, const int32_t* items,
                                  const int32_t* users, int64_t n, int32_t m, int32_t n_items, int64_t seed, uint64_t first,
                                  int32_t* out_items, float* out_scores, int32_t* out_draw, hipStream_t st);
+
+// warp.hip.  The negative of a WARP step (include/mfsgd.h, mfsgd_sample_unseen_violating): rows, index, candidates and
+// dots as for launch_hard_negatives, pos[x] (a row of Q) the row's positive.  Of the row's m >= 1 candidates the first in
+// d with candidate != pos[x] and dot(P[user], Q[pos]) - dot(P[user], Q[candidate]) < margin: out_items[x] the item,
+// out_draw[x] its d, out_margin[x] that difference and out_rank[x] = max(1, unseen items / (d + 1)) (the last three
+// nullable); -1, m, 0x7FC00000 and 0 where no candidate does, -1, -1, 0x7FC00000 and 0 where the user has seen every
+// item.  n <= 2^22 (a piece).  Asynchronous on st.
+hipError_t launch_first_violating(int L, const float* P, const float* Q, const long long* off, const int32_t* items,
+                                  const int32_t* users, const int32_t* pos, int64_t n, int32_t m, float margin, int32_t n_items,
+                                  int64_t seed, uint64_t first, int32_t* out_items, int32_t* out_draw, float* out_margin,
+                                  int32_t* out_rank, hipStream_t st);
 
 // similar.hip.  out[x] = rn(row x) = 1 / sqrt(dot(row, row)), or 0 where that dot is 0, for the
 // n_rows kp-padded rows of M.  Asynchronous on st.

@@ -2,7 +2,8 @@
 // of fresh ratings, the launch policy over them, and the two calls, mfsgd_online_levels and mfsgd_apply_ratings.  The
 // kernel is online.hip's.  The pairwise (BPR) update of a list of triples ("Pairwise ranking (BPR)") is the
 // same code with a third row per step: mfsgd_triple_levels, mfsgd_apply_triples (kernel: pairwise.hip) and the host's
-// view of its logistic weight, mfsgd_bpr_weights.
+// view of its logistic weight, mfsgd_bpr_weights.  mfsgd_apply_triples_weighted is mfsgd_apply_triples with the step size
+// of every triple given by the caller, and mfsgd_warp_weights the host's table of the WARP weight ("WARP").
 #include <algorithm>
 
 #include "canon.hpp"
@@ -26,10 +27,12 @@ static int check_online_pairs(const mfsgd_handle* h, const char* call, const int
 }
 
 // The same for triples (u, i, i2), i2 being the negative item; i[x] == i2[x] is refused on top (the message names the triple).
+// With weights (mfsgd_apply_triples_weighted), w is one of the arrays that must be there.
 static int check_online_triples(const mfsgd_handle* h, const char* call, const int32_t* u, const int32_t* i, const int32_t* i2,
-                                int64_t n) {
+                                int64_t n, bool weighted = false, const float* w = nullptr) {
     if (n < 0) return fail(h, MFSGD_ERR_INVALID_ARG, std::string(call) + ": n is negative");
-    if (n > 0 && (!u || !i || !i2)) return fail(h, MFSGD_ERR_INVALID_ARG, std::string(call) + ": u, i or j is null");
+    if (n > 0 && (!u || !i || !i2 || (weighted && !w)))
+        return fail(h, MFSGD_ERR_INVALID_ARG, std::string(call) + (weighted ? ": u, i, j or w is null" : ": u, i or j is null"));
     const uint32_t U = (uint32_t)h->cfg.n_users, I = (uint32_t)h->cfg.n_items;
     int64_t x = first_where(n, [=](int64_t t) {
         return (uint32_t)((uint32_t)u[t] >= U) | (uint32_t)((uint32_t)i[t] >= I) | (uint32_t)((uint32_t)i2[t] >= I);
@@ -66,20 +69,21 @@ static int32_t online_levels_of(mfsgd_handle* h, const int32_t* u, const int32_t
 }
 
 // One piece ready for the device: its ratings in a stable counting sort by level.  A piece of triples has i2, the
-// negative items, in the place of r.
+// negative items, in the place of r, and with them w, the weights of a weighted call (else empty).
 struct OnlinePiece {
     std::vector<int32_t> level, level_ptr, u, i, i2, orig;
-    std::vector<float> r;
+    std::vector<float> r, w;
     int32_t n_levels = 0;
 };
 
-// Exactly one of r and i2 is given.
-static void online_sort_piece(mfsgd_handle* h, const int32_t* u, const int32_t* i, const float* r, const int32_t* i2, int64_t n,
-                              OnlinePiece& pc) {
+// Exactly one of r and i2 is given; w (nullable) only with i2.
+static void online_sort_piece(mfsgd_handle* h, const int32_t* u, const int32_t* i, const float* r, const int32_t* i2, const float* w,
+                              int64_t n, OnlinePiece& pc) {
     pc.level.resize((size_t)n);
     pc.u.resize((size_t)n), pc.i.resize((size_t)n), pc.orig.resize((size_t)n);
     if (r) pc.r.resize((size_t)n);
     else pc.i2.resize((size_t)n);
+    pc.w.resize(w ? (size_t)n : 0);
     pc.n_levels = online_levels_of(h, u, i, n, pc.level.data(), i2);
     pc.level_ptr.assign((size_t)pc.n_levels + 1, 0);
     for (int64_t j = 0; j < n; ++j) ++pc.level_ptr[(size_t)pc.level[(size_t)j] + 1];
@@ -91,6 +95,7 @@ static void online_sort_piece(mfsgd_handle* h, const int32_t* u, const int32_t* 
         pc.i[(size_t)at] = i[j];
         if (r) pc.r[(size_t)at] = canon_nan(r[j]);  // (records.hpp: a payload must not reach P and Q)
         else pc.i2[(size_t)at] = i2[j];
+        if (w) pc.w[(size_t)at] = canon_nan(w[j]);  // (the same: lr * w is the step size of three rows)
         pc.orig[(size_t)at] = (int32_t)j;
     }
 }
@@ -144,11 +149,11 @@ static void levels_of_list(mfsgd_handle* h, const int32_t* u, const int32_t* i, 
     if (info) *info = got;
 }
 
-// Body of mfsgd_apply_ratings (r given) and mfsgd_apply_triples (i2 given) behind their argument checks: piece by piece,
-// the sort, the uploads, the launches of online.hip's or pairwise.hip's kernel, and out (nullable, n floats: the errors
-// or the margins) coming down.
+// Body of mfsgd_apply_ratings (r given), mfsgd_apply_triples (i2 given) and mfsgd_apply_triples_weighted (i2 and w given)
+// behind their argument checks: piece by piece, the sort, the uploads, the launches of online.hip's or pairwise.hip's
+// kernel, and out (nullable, n floats: the errors or the margins) coming down.
 static int apply_list(mfsgd_handle* h, const char* call, const int32_t* u, const int32_t* i, const float* r, const int32_t* i2,
-                      int64_t n, float* out, mfsgd_online_info* info) {
+                      const float* w, int64_t n, float* out, mfsgd_online_info* info) {
     int rc = check_reads_factors(h, call);
     if (rc) return rc;
     mfsgd_online_info got{};
@@ -162,28 +167,30 @@ static int apply_list(mfsgd_handle* h, const char* call, const int32_t* u, const
     auto bad = [&](hipError_t e) { return serve_fail(h, prefix.c_str(), e); };
     const size_t piece = (size_t)std::min(n, kOnlinePiece);
     DevArray<int32_t> du, di, di2, dorig, dptr;  // sized by the largest piece; gone when this returns, whichever way
-    DevArray<float> dr, dout;
+    DevArray<float> dr, dw, dout;
     if ((rc = dev_alloc(h, du, piece)) || (rc = dev_alloc(h, di, piece))) return rc;
     if ((rc = r ? dev_alloc(h, dr, piece) : dev_alloc(h, di2, piece)) || (rc = dev_alloc(h, dorig, piece))) return rc;
     if ((rc = dev_alloc(h, dptr, piece + 1))) return rc;
+    if (w && (rc = dev_alloc(h, dw, piece))) return rc;
     if (out && (rc = dev_alloc(h, dout, piece))) return rc;
     const float lr = h->cfg.lr, c1 = 1.0f - h->cfg.lr * h->cfg.lambda;
     OnlinePiece pc;
     for (int64_t j0 = 0; j0 < n; j0 += kOnlinePiece) {
         const size_t c = (size_t)std::min(kOnlinePiece, n - j0);
-        online_sort_piece(h, u + j0, i + j0, r ? r + j0 : nullptr, i2 ? i2 + j0 : nullptr, (int64_t)c, pc);
+        online_sort_piece(h, u + j0, i + j0, r ? r + j0 : nullptr, i2 ? i2 + j0 : nullptr, w ? w + j0 : nullptr, (int64_t)c, pc);
         online_count(&got, pc.level_ptr.data(), pc.n_levels);
         HIPCHK_OR(bad, copy_up(du, pc.u.data(), c, h->stream));
         HIPCHK_OR(bad, copy_up(di, pc.i.data(), c, h->stream));
         HIPCHK_OR(bad, r ? copy_up(dr, pc.r.data(), c, h->stream) : copy_up(di2, pc.i2.data(), c, h->stream));
+        if (w) HIPCHK_OR(bad, copy_up(dw, pc.w.data(), c, h->stream));
         HIPCHK_OR(bad, copy_up(dorig, pc.orig.data(), c, h->stream));
         HIPCHK_OR(bad, copy_up(dptr, pc.level_ptr.data(), (size_t)pc.n_levels + 1, h->stream));
         HIPCHK_OR(bad, online_launches(pc.level_ptr, pc.n_levels, h->geo.L, &got.launches, [&](int32_t l0, int32_t l1, int32_t wgs) {
             if (r)
                 return launch_apply_levels(h->geo.L, h->dP.data(), h->dQ.data(), du.data(), di.data(), dr.data(), dorig.data(),
                                            dptr.data(), l0, l1, wgs, h->cfg.k, lr, c1, dout.data(), h->stream);
-            return launch_apply_triple_levels(h->geo.L, h->dP.data(), h->dQ.data(), du.data(), di.data(), di2.data(), dorig.data(),
-                                              dptr.data(), l0, l1, wgs, h->cfg.k, lr, c1, dout.data(), h->stream);
+            return launch_apply_triple_levels(h->geo.L, h->dP.data(), h->dQ.data(), du.data(), di.data(), di2.data(), dw.data(),
+                                              dorig.data(), dptr.data(), l0, l1, wgs, h->cfg.k, lr, c1, dout.data(), h->stream);
         }));
         if (out) HIPCHK_OR(bad, copy_down(out + j0, dout, c, h->stream));
         HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // the staging buffers, the host's and the device's, are reused
@@ -220,7 +227,7 @@ int mfsgd_apply_ratings(mfsgd_handle* h, const int32_t* u, const int32_t* i, con
     return guarded(h, "apply_ratings", [&]() -> int {
         if (const int rc = check_online_pairs(h, "apply_ratings", u, i, n)) return rc;
         if (n > 0 && !r) return fail(h, MFSGD_ERR_INVALID_ARG, "apply_ratings: r is null");
-        return apply_list(h, "apply_ratings", u, i, r, nullptr, n, err, info);
+        return apply_list(h, "apply_ratings", u, i, r, nullptr, nullptr, n, err, info);
     });
 }
 
@@ -228,7 +235,15 @@ int mfsgd_apply_triples(mfsgd_handle* h, const int32_t* u, const int32_t* i, con
                         mfsgd_online_info* info) {
     return guarded(h, "apply_triples", [&]() -> int {
         if (const int rc = check_online_triples(h, "apply_triples", u, i, j, n)) return rc;
-        return apply_list(h, "apply_triples", u, i, nullptr, j, n, margin, info);
+        return apply_list(h, "apply_triples", u, i, nullptr, j, nullptr, n, margin, info);
+    });
+}
+
+int mfsgd_apply_triples_weighted(mfsgd_handle* h, const int32_t* u, const int32_t* i, const int32_t* j, const float* w, int64_t n,
+                                 float* margin, mfsgd_online_info* info) {
+    return guarded(h, "apply_triples_weighted", [&]() -> int {
+        if (const int rc = check_online_triples(h, "apply_triples_weighted", u, i, j, n, true, w)) return rc;
+        return apply_list(h, "apply_triples_weighted", u, i, nullptr, j, w, n, margin, info);
     });
 }
 
@@ -239,6 +254,33 @@ int mfsgd_bpr_weights(const float* x, float* g, int64_t n) {
             return MFSGD_ERR_INVALID_ARG;
         }
         for (int64_t a = 0; a < n; ++a) g[a] = lsig(x[a]);
+        return MFSGD_OK;
+    });
+}
+
+int mfsgd_warp_weights(const int32_t* rank, float* w, int64_t n) {
+    return guarded_free("warp_weights", [&]() -> int {
+        if (n < 0 || (n > 0 && (!rank || !w))) {
+            g_create_error = n < 0 ? "warp_weights: n is negative" : "warp_weights: rank or w is null";
+            return MFSGD_ERR_INVALID_ARG;
+        }
+        int32_t top = 0;
+        for (int64_t a = 0; a < n; ++a) {
+            if (rank[a] < 0) {
+                g_create_error = "warp_weights: rank " + std::to_string(a) + " is negative";
+                return MFSGD_ERR_INVALID_ARG;
+            }
+            top = std::max(top, rank[a]);
+        }
+        // L(r) for r = 0 .. top, once: the fp64 sum 1/1 + 1/2 + ... + 1/r in ascending order, rounded to fp32 once
+        std::vector<float> table((size_t)top + 1);
+        double sum = 0.0;
+        table[0] = 0.0f;
+        for (int64_t r = 1; r <= top; ++r) {
+            sum += 1.0 / (double)r;
+            table[(size_t)r] = (float)sum;
+        }
+        for (int64_t a = 0; a < n; ++a) w[a] = table[(size_t)rank[a]];
         return MFSGD_OK;
     });
 }

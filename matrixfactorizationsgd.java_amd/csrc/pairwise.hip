@@ -21,10 +21,12 @@ namespace {
 // orig[t] is the place of triple t in the caller's list, where its margin goes (margin == nullptr: nobody asked).
 // Launch shape, the barrier between the levels of a one-workgroup launch and the rule that every lane runs every pass
 // are online.hip's (apply_levels_kernel), for the reasons it states.
-template <int L>
+// WEIGHTED: the step size of triple t is lr * w[t], a weight the caller gives (mfsgd_apply_triples_weighted), in place of
+// lr * lsig(x); without it w is not read and the kernel is the one it was.
+template <int L, bool WEIGHTED>
 __global__ void __launch_bounds__(256) apply_triple_levels_kernel(float* P, float* Q, const int32_t* __restrict__ u,
                                                                   const int32_t* __restrict__ i, const int32_t* __restrict__ jn,
-                                                                  const int32_t* __restrict__ orig,
+                                                                  const float* __restrict__ w, const int32_t* __restrict__ orig,
                                                                   const int32_t* __restrict__ level_ptr, const int l0, const int l1,
                                                                   const int k, const float lr, const float c,
                                                                   float* __restrict__ margin) {
@@ -49,14 +51,16 @@ __global__ void __launch_bounds__(256) apply_triple_levels_kernel(float* P, floa
             const float di = group_allreduce<L>(ci);
             const float dj = group_allreduce<L>(cj);
             const float x = di - dj;  // the margin before the update
-            const float s = lr * lsig(x);
+            float s;
+            if constexpr (WEIGHTED) s = lr * w[t];
+            else s = lr * lsig(x);
             float4 d;
             d.x = qi.x - qj.x, d.y = qi.y - qj.y, d.z = qi.z - qj.z, d.w = qi.w - qj.w;
             float4 np = axpy_row(s, d, c, p);
             float4 ni = axpy_row(s, p, c, qi);
             float4 nj = axpy_row(-s, p, c, qj);
-            // the pad columns (k .. KP - 1) stay +0.0, as in online.hip: fma(s, 0, c * 0) is NaN for a NaN s (a NaN margin),
-            // and a NaN pad column would make every later dot of the row NaN
+            // the pad columns (k .. KP - 1) stay +0.0, as in online.hip: fma(s, 0, c * 0) is NaN for a NaN s (a NaN margin,
+            // or a NaN weight), and a NaN pad column would make every later dot of the row NaN
             const int pad_from = k - lig * 4;  // elements of this lane's chunk that are columns of the row
             if (pad_from < 4) {
                 if (pad_from < 1) np.x = ni.x = nj.x = 0.0f;
@@ -82,14 +86,18 @@ __global__ void __launch_bounds__(256) apply_triple_levels_kernel(float* P, floa
 }  // namespace
 
 hipError_t launch_apply_triple_levels(int L, float* P, float* Q, const int32_t* u, const int32_t* i, const int32_t* jn,
-                                      const int32_t* orig, const int32_t* level_ptr, int l0, int l1, int workgroups, int k,
-                                      float lr, float c, float* margin, hipStream_t st) {
+                                      const float* w, const int32_t* orig, const int32_t* level_ptr, int l0, int l1,
+                                      int workgroups, int k, float lr, float c, float* margin, hipStream_t st) {
     if (l1 <= l0) return hipSuccess;
     if (workgroups < 1 || (l1 - l0 > 1 && workgroups != 1)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)workgroups), block(256);
     return with_L(L, [&](auto l) {
-        hipLaunchKernelGGL((apply_triple_levels_kernel<l()>), grid, block, 0, st, P, Q, u, i, jn, orig, level_ptr, l0, l1, k, lr, c,
-                           margin);
+        if (w)
+            hipLaunchKernelGGL((apply_triple_levels_kernel<l(), true>), grid, block, 0, st, P, Q, u, i, jn, w, orig, level_ptr, l0,
+                               l1, k, lr, c, margin);
+        else
+            hipLaunchKernelGGL((apply_triple_levels_kernel<l(), false>), grid, block, 0, st, P, Q, u, i, jn, w, orig, level_ptr,
+                               l0, l1, k, lr, c, margin);
         return hipGetLastError();
     });
 }

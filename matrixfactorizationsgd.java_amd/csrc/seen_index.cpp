@@ -259,4 +259,54 @@ int seen_sample_hard(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m
     return MFSGD_OK;
 }
 
+// Body of mfsgd_sample_unseen_violating (handle.cpp): row x receives the first of the m draws seen_sample would give it
+// that violates the margin against the row's positive, under the factors as they are.  Users and positives go up and the
+// picks come down in the pieces of seen_sample_hard; nothing per candidate is ever stored.
+int seen_sample_violating(mfsgd_handle* h, const int32_t* users, const int32_t* pos_items, int64_t n, int32_t m, float margin,
+                          int64_t seed, int64_t first, int32_t* out_items, int32_t* out_draw, float* out_margin, int32_t* out_rank) {
+    if (n < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_violating: n is negative");
+    if (m < 1) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_violating: m is below 1");
+    if (margin != margin) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_violating: margin is NaN");
+    if (first < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_violating: first is negative");
+    if (n > INT64_MAX / m || first > INT64_MAX - n * m)
+        return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_violating: first + n * m exceeds 2^63 - 1");
+    if (n > 0 && (!users || !pos_items || !out_items))
+        return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_violating: users, pos_items or out_items is null");
+    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "sample_unseen_violating: single-partition handles only");
+    if (!h->seen.present) return fail(h, MFSGD_ERR_STATE, "sample_unseen_violating: no seen set");
+    int rc = check_reads_factors(h, "sample_unseen_violating");
+    if (rc) return rc;
+    if (n == 0) return MFSGD_OK;
+    const int64_t x_bad = first_outside(users, h->cfg.n_users, pos_items, h->cfg.n_items, n);
+    if (x_bad >= 0)
+        return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_violating: row " + std::to_string(x_bad) + " out of range");
+    if ((rc = factors_to_device(h))) return rc;
+    auto bad = [h](hipError_t e) { return serve_fail(h, "sample_unseen_violating: ", e); };
+    const Seen& s = h->seen;
+    const int64_t rows = std::min(n, std::max<int64_t>(1, kSampleChunk / m));
+    DevArray<int32_t> d_users, d_pos, d_items, d_draw, d_rank;
+    DevArray<float> d_margin;
+    if ((rc = dev_alloc(h, d_users, (size_t)rows)) || (rc = dev_alloc(h, d_pos, (size_t)rows))) return rc;
+    if ((rc = dev_alloc(h, d_items, (size_t)rows))) return rc;
+    if (out_draw && (rc = dev_alloc(h, d_draw, (size_t)rows))) return rc;
+    if (out_margin && (rc = dev_alloc(h, d_margin, (size_t)rows))) return rc;
+    if (out_rank && (rc = dev_alloc(h, d_rank, (size_t)rows))) return rc;
+    for (int64_t x0 = 0; x0 < n; x0 += rows) {
+        const int64_t c = std::min(rows, n - x0);
+        HIPCHK_OR(bad, copy_up(d_users, users + x0, (size_t)c, h->stream));
+        HIPCHK_OR(bad, copy_up(d_pos, pos_items + x0, (size_t)c, h->stream));
+        HIPCHK_OR(bad, launch_first_violating(h->geo.L, h->dP.data(), h->dQ.data(), s.n > 0 ? s.off.data() : nullptr, s.items.data(),
+                                              d_users.data(), d_pos.data(), c, m, margin, h->cfg.n_items, seed,
+                                              (uint64_t)first + (uint64_t)(x0 * m), d_items.data(),
+                                              out_draw ? d_draw.data() : nullptr, out_margin ? d_margin.data() : nullptr,
+                                              out_rank ? d_rank.data() : nullptr, h->stream));
+        HIPCHK_OR(bad, copy_down(out_items + x0, d_items, (size_t)c, h->stream));
+        if (out_draw) HIPCHK_OR(bad, copy_down(out_draw + x0, d_draw, (size_t)c, h->stream));
+        if (out_margin) HIPCHK_OR(bad, copy_down(out_margin + x0, d_margin, (size_t)c, h->stream));
+        if (out_rank) HIPCHK_OR(bad, copy_down(out_rank + x0, d_rank, (size_t)c, h->stream));
+        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // (pageable memory: the staging is free for the next piece)
+    }
+    return MFSGD_OK;
+}
+
 }  // namespace mfsgd

@@ -128,6 +128,19 @@ def bpr_weights(x):
     return g
 
 
+def warp_weights(rank):
+    """mfsgd_warp_weights (host only, needs no model and no GPU): float32 w = L(rank), L(0) = 0 and L(r) = 1/1 + 1/2 + ...
+    + 1/r summed in float64 in ascending order and rounded once, for every rank sample_unseen_violating estimated
+    (include/mfsgd.h): the weight of a WARP step.  A negative rank is refused."""
+    rr = _i32(rank)
+    w = np.empty(rr.shape, np.float32)
+    lib = _lib.load_library()
+    rc = lib.mfsgd_warp_weights(_p(rr, C.c_int32), _p(w, C.c_float), rr.size)
+    if rc != 0:
+        raise MfsgdError(rc, lib.mfsgd_last_error(None).decode())
+    return w
+
+
 def _pairs(a, b, what):
     """Two int32 1-d arrays of one length (None: no pairs)."""
     aa, bb = (np.empty(0, np.int32),) * 2 if a is None else (_i32(a), _i32(b))
@@ -403,18 +416,29 @@ class MatrixFactorizationSGD:
                                                   uu.size, _p(levels, C.c_int32), C.byref(out)))
         return levels, out.as_dict()
 
-    def partial_fit_pairwise(self, u, i, j, *, margins=False, info=False):
+    def partial_fit_pairwise(self, u, i, j, *, weights=None, margins=False, info=False):
         """Applies the triples (u[x], i[x], j[x]) -- user, an item the user prefers, an item the user does not -- to the
         live model in the order given, one BPR step each (mfsgd_apply_triples): bit for bit the sequential loop, at the
         current lr and lambda.  i[x] == j[x] is refused.  The stored ratings, their schedules, the held-out set and the
         seen-item index are not touched.  margins=True returns float32[n], each triple's margin dot(p, qi) - dot(p, qj)
         just before its own update; info=True returns dict(n, pieces, levels, max_width, launches); both: (margins,
-        info); neither: None."""
+        info); neither: None.
+        weights (float32[n]) gives every step its size instead: s = lr * weights[x] in place of lr * lsig(margin), the
+        rest of the step alike (mfsgd_apply_triples_weighted) -- hinge, importance and WARP weights (warp_weights) are the
+        caller's policy.  A NaN weight makes its three rows NaN."""
         uu, ii, jj = self._index_triples(u, i, j)
         x = np.empty(uu.size, np.float32) if margins else None
         out = _lib.OnlineInfo()
-        self._check(self._lib.mfsgd_apply_triples(self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32), _p(jj, C.c_int32),
-                                                  uu.size, None if x is None else _p(x, C.c_float), C.byref(out)))
+        if weights is None:
+            self._check(self._lib.mfsgd_apply_triples(self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32), _p(jj, C.c_int32),
+                                                      uu.size, None if x is None else _p(x, C.c_float), C.byref(out)))
+        else:
+            ww = _f32(np.atleast_1d(weights))
+            if ww.shape != uu.shape:
+                raise ValueError("weights must be a 1-d array as long as u")
+            self._check(self._lib.mfsgd_apply_triples_weighted(self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32),
+                                                               _p(jj, C.c_int32), _p(ww, C.c_float), uu.size,
+                                                               None if x is None else _p(x, C.c_float), C.byref(out)))
         res = tuple(a for a, on in ((x, margins), (out.as_dict(), info)) if on)
         return None if not res else res[0] if len(res) == 1 else res
 
@@ -479,6 +503,52 @@ class MatrixFactorizationSGD:
                 x = x.astype(np.float64)
                 loss[e], auc[e] = np.logaddexp(0.0, -x).mean(), (x > 0).mean()
         return dict(loss=loss, auc=auc) if stats else None
+
+    def fit_warp(self, u, i, epochs, *, candidates=10, margin=1.0, refresh=None, seed=0, first_epoch=0, stats=True):
+        """Trains on one-class data with WARP, Weston's weighted approximate-rank pairwise loss: (u[x], i[x]) are the
+        positives, in the order given (pass them shuffled, as for fit_bpr).  Each positive's negative is the first of
+        m = candidates unseen draws that violates the margin, dot(p, qi) - dot(p, qj) < margin, under the current
+        factors (sample_unseen_violating); the number of draws that took estimates the positive's rank, and the step is
+        a hinge step of size lr * warp_weights(rank): large where a violator turns up at once, small where it takes
+        many draws, none where none of the m violates.  The index and the factors are handled as in fit_bpr: a handle
+        without an index gets set_seen(u, i), factors that were never initialised are seeded.
+        Epoch e, counted from first_epoch, walks the positives in blocks of `refresh` rows (None: n, one block per
+        epoch); for each block [a, b): J, d, rk = sample_unseen_violating(u[a:b], i[a:b], m, margin, seed,
+        first=((first_epoch + e) * n + a) * m, draws=True, ranks=True) under the factors as the blocks before it left
+        them; the rows with J < 0 (no violator, or nothing unseen) are dropped;
+        partial_fit_pairwise(..., weights=warp_weights(rk)) of the rest.  Splitting the epochs with first_epoch gives
+        the same bits as one run.  The stored rating set is not touched.
+        Returns, with stats, dict(violating, trials), float64[epochs] each: the share of positives that had a violator,
+        and the mean of d + 1 over those positives (0 where there were none).  Without stats: None."""
+        uu, ii = _pairs(np.atleast_1d(u), np.atleast_1d(i), "u and i")
+        epochs, n, m = int(epochs), uu.size, int(candidates)
+        if epochs < 0:
+            raise ValueError("epochs must not be negative")
+        if m < 1 or (refresh is not None and int(refresh) < 1):
+            raise ValueError("candidates and refresh must be at least 1")
+        if np.isnan(margin):
+            raise ValueError("margin must not be NaN")
+        if self.seen_size() < 0:
+            self.set_seen(uu, ii)
+        if not self._initialised:
+            self.init_factors()
+        violating, trials = np.zeros(epochs, np.float64), np.zeros(epochs, np.float64)
+        step = max(n, 1) if refresh is None else int(refresh)
+        for e in range(epochs):
+            hits = draws = 0
+            for a in range(0, n, step):
+                bu, bi = uu[a:a + step], ii[a:a + step]
+                J, d, rk = self.sample_unseen_violating(bu, bi, m, margin, seed, ((int(first_epoch) + e) * n + a) * m,
+                                                        draws=True, ranks=True)
+                keep = J >= 0
+                self.partial_fit_pairwise(bu[keep], bi[keep], J[keep], weights=warp_weights(rk[keep]))
+                hits += int(keep.sum())
+                draws += int(d[keep].astype(np.int64).sum()) + int(keep.sum())
+            if n:
+                violating[e] = hits / n
+            if hits:
+                trials[e] = draws / hits
+        return dict(violating=violating, trials=trials) if stats else None
 
     def train_timed(self, epochs):
         """(elapsed device milliseconds, kernel launches) for `epochs` passes."""
@@ -607,6 +677,29 @@ class MatrixFactorizationSGD:
                                                        _p(items, C.c_int32), None if sc is None else _p(sc, C.c_float),
                                                        None if dr is None else _p(dr, C.c_int32)))
         res = tuple(a for a, on in ((items, True), (sc, scores), (dr, draws)) if on)
+        return res[0] if len(res) == 1 else res
+
+    def sample_unseen_violating(self, users, items, m, margin=1.0, seed=0, first=0, *, draws=False, margins=False, ranks=False):
+        """int32 [len(users)]: for each row, the first of the m items sample_unseen(users, m, seed, first) draws for it
+        that is not the row's positive items[x] and violates the margin against it, dot(p, q_pos) - dot(p, q_cand) <
+        margin, under the factors as they are now (mfsgd_sample_unseen_violating: drawn, scored and picked on the device,
+        the draws past the pick skipped); -1 where none of the m does, or the user has seen every item.  A NaN
+        difference never violates, one equal to the margin does not.  draws=True adds int32 [len(users)], each pick's
+        position d (m where no candidate violates, -1 where nothing is unseen); margins=True adds float32, the pick's
+        difference (NaN with -1): what partial_fit_pairwise reports as its margin; ranks=True adds int32, the estimate
+        max(1, unseen items // (d + 1)) of how many unseen items violate (0 with -1): what warp_weights takes.  With
+        any of them the result is a tuple (items, draws, margins, ranks) without what was not asked for."""
+        uu, ii = _pairs(np.atleast_1d(users), np.atleast_1d(items), "users and items")
+        out = np.empty(uu.size, np.int32)
+        dr = np.empty(uu.size, np.int32) if draws else None
+        mg = np.empty(uu.size, np.float32) if margins else None
+        rk = np.empty(uu.size, np.int32) if ranks else None
+        self._check(self._lib.mfsgd_sample_unseen_violating(self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32), uu.size, int(m),
+                                                            float(margin), int(seed), int(first), _p(out, C.c_int32),
+                                                            None if dr is None else _p(dr, C.c_int32),
+                                                            None if mg is None else _p(mg, C.c_float),
+                                                            None if rk is None else _p(rk, C.c_int32)))
+        res = tuple(a for a, on in ((out, True), (dr, draws), (mg, margins), (rk, ranks)) if on)
         return res[0] if len(res) == 1 else res
 
     def fit_implicit(self, u, i, epochs, negatives=4, *, seed=0, pos=1.0, neg=0.0, first_epoch=0, rmse=True):
