@@ -304,7 +304,8 @@ int mfsgd_evaluate_ranking(mfsgd_handle* h, const int32_t* users, const int32_t*
  * into larger ones, new before old (MFSGD_ERR_OOM leaves everything as it was; every list is kept).
  * Memory: with D distinct pairs, 4 D + 12 user_capacity + 8 bytes of device memory (4 per pair; per user of capacity 8
  * of offset and 4 of the table through which the kernels reach a list by user id), all of it counted by
- * mfsgd_debug_device_bytes; an empty index and a handle without one hold nothing.
+ * mfsgd_debug_device_bytes; an empty index and a handle without one hold nothing.  (A handle with item weights holds
+ * 8 D bytes more beside the index: "weighted negatives" below.)
  *
  * mfsgd_set_seen: the index becomes the distinct pairs of (u[x], i[x]), x < n; duplicates count once.  Needs neither
  * factors nor ratings.  Every pair must satisfy 0 <= u < n_users and 0 <= i < n_items under the handle's CURRENT counts
@@ -370,6 +371,69 @@ int mfsgd_get_seen(mfsgd_handle* h, const int32_t* users, int32_t n_users, int64
  * all of it freed before the call returns, on every path -- mfsgd_debug_device_bytes is the same before and after.     */
 int mfsgd_sample_unseen(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first,
                         int32_t* out_items /* n x m, row-major */);
+/* Weighted negatives: mfsgd_sample_unseen_weighted draws unseen items in proportion to a weight per item -- a power of
+ * the item's popularity, usually (word2vec's count^0.75) -- where mfsgd_sample_unseen draws them uniformly.  With a
+ * long-tailed catalogue nearly every uniform negative is an obscure item the model ranks low already.
+ * Weights.  Integers, 0 <= w[i] < 2^32, one per item: integers keep the draw exact and the same on every device (no pow
+ * decides a bit of it).  An item of weight 0 is never drawn; all weights zero is valid, and every draw is then -1.  The
+ * handle keeps C, the exclusive prefix of w (C[0] = 0, C[n_items] = W < 2^63 by construction), uint64 on the device.
+ * Weights belong to the items, not to the index: they survive mfsgd_set_seen, mfsgd_mark_seen and mfsgd_clear_seen, and
+ * need no index to be set.  mfsgd_append_items leaves them as they are, so that they no longer cover the model:
+ * mfsgd_sample_unseen_weighted is then MFSGD_ERR_STATE ("item weights cover X items, the model has Y") until they are set
+ * again.  Single-partition handles only (MFSGD_ERR_STATE), like the index.
+ * The unseen-mass table.  On a handle that has both weights and an index with pairs, g[q], for every pair of the index,
+ * is the weight of the UNSEEN items below S[q] in that user's list: uint64, 8 bytes per pair, beside the index's items,
+ * never decreasing along a list.  It is built eagerly by whichever call completes that state or changes either side --
+ * mfsgd_set_item_weights, and mfsgd_set_seen / mfsgd_mark_seen on a handle that has weights -- on the device: the
+ * pairs' weights are gathered, one device-wide exclusive scan (rocPRIM) sums them, and g[q] = C[S[q]] less the scanned
+ * weight before q in its own list.  It follows the index's rule: the new table is complete before the old one is
+ * released, and a failure leaves index, weights and table as they were.  A mark_seen that adds nothing builds nothing.
+ * mfsgd_append_users and mfsgd_reserve_rows do not move pairs and do not touch it; mfsgd_clear_seen and an empty index
+ * drop it; mfsgd_clear_item_weights drops it and C.  (Under weights that mfsgd_append_items left behind, the items
+ * appended since weigh nothing in a table built meanwhile; setting the weights again rebuilds it.)
+ * Memory on top of the index: 8 D + 8 (n_items + 1) bytes, all of it counted by mfsgd_debug_device_bytes; without pairs
+ * 8 (n_items + 1).  Transient peak of a build, on top of what the call has otherwise: 8 D bytes of scanned weights and
+ * the scan's scratch, freed before the call returns.  A handle that never sets weights allocates and runs nothing of this.
+ *
+ * mfsgd_set_item_weights: the weights become w[0 .. n).  MFSGD_ERR_INVALID_ARG ("set_item_weights: ..."): a negative n;
+ * a null w; (then MFSGD_ERR_STATE for n_parts != 1;) n other than the current n_items.  Then a device is needed
+ * (MFSGD_ERR_NO_DEVICE otherwise): the prefix is summed on the host and goes up whole.
+ * mfsgd_get_item_weights: *n = the item count the weights were set for, or -1 when the handle has none; with w != NULL
+ * and weights, w[i] = C[i + 1] - C[i] for those *n items.  A null n is MFSGD_ERR_INVALID_ARG.
+ * mfsgd_clear_item_weights: the handle has no weights afterwards, and C and g are freed.
+ * mfsgd_seen_item_counts: counts[i], i < n_items, = the number of users whose list holds item i -- the popularity the
+ * weights are usually made of.  A histogram over the index's items on the device, with integer atomics: the result
+ * does not depend on the order of arrival.  An empty index gives zeros, on the host alone.  MFSGD_ERR_INVALID_ARG for a
+ * null counts, then MFSGD_ERR_STATE for n_parts != 1 and for a handle without an index ("no seen set").
+ * mfsgd_sample_unseen_weighted: mfsgd_sample_unseen with the weighted draw -- the same rows, counters, pieces and
+ * staging.  Draw d of row x has the counter c = first + x * m + d and is a pure function of (seed, c), the user's list S
+ * (length s), the weights and n_items; unsigned 64-bit arithmetic but for the one 128-bit product:
+ *     z    = mfsgd_sample_unseen's z, all 64 bits of it (no >> 32)
+ *     cnt  = W                              if s == 0
+ *          = g[s-1] + W - C[S[s-1] + 1]     otherwise               the user's unseen mass
+ *     cnt == 0: out = -1                    (everything of positive weight is seen)
+ *     t    = (z * cnt) >> 64                the upper half of the 128-bit product; in [0, cnt)
+ *     p    = the number of q in [0, s) with g[q] <= t               one binary search, one 8-byte load per step
+ *     base = C[S[p]] - g[p] if p < s, W - cnt otherwise             the seen mass below the gap the draw falls in
+ *     out  = (the number of x in [0, n_items] with C[x] <= t + base) - 1          one binary search over C
+ * out is unseen and has positive weight (zero-weight ties in C resolve to the item x with C[x + 1] > t + base); item x
+ * comes out for exactly w[x] values of t, in ascending order, so its probability is w[x] / cnt within cnt / 2^64.  With
+ * unit weights out = t + p, mfsgd_sample_unseen's rule on the 64-bit t.  An empty index gives p = 0 and base = 0.
+ * out_mass[x] (nullable) receives the row's cnt: a host can weight or skip rows by it.  It is written for the rows of a
+ * call that draws (n * m > 0).
+ * Checks, all before any device work, in this order ("sample_unseen_weighted: ..."): mfsgd_sample_unseen's argument
+ * checks; MFSGD_ERR_STATE for n_parts != 1, for a handle without an index ("no seen set"), for one without weights ("no
+ * item weights"), for weights that no longer cover the model; n * m == 0 is then MFSGD_OK and touches nothing; then
+ * MFSGD_ERR_INVALID_ARG for a user outside [0, n_users), named by its row, the outputs untouched.  A valid call with
+ * work to do and no usable GPU is MFSGD_ERR_NO_DEVICE.  Modifies neither the model nor the index nor the weights; because
+ * g is built eagerly a draw allocates staging only (as mfsgd_sample_unseen, plus 8 bytes per row of a piece with
+ * out_mass), all of it freed before the call returns -- mfsgd_debug_device_bytes is the same before and after.         */
+int mfsgd_set_item_weights(mfsgd_handle* h, const uint32_t* w, int32_t n /* the current n_items */);
+int mfsgd_get_item_weights(mfsgd_handle* h, uint32_t* w /* nullable */, int32_t* n /* -1: none */);
+int mfsgd_clear_item_weights(mfsgd_handle* h);
+int mfsgd_seen_item_counts(mfsgd_handle* h, int64_t* counts /* n_items */);
+int mfsgd_sample_unseen_weighted(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first,
+                                 int32_t* out_items /* n x m, row-major */, int64_t* out_mass /* nullable, n */);
 /* mfsgd_sample_unseen_hard: hard negatives for pairwise ranking (dynamic negative sampling).  For each row x, the m
  * candidates mfsgd_sample_unseen would draw for users[x] are drawn, scored under the factors as they are now, and the one
  * the model likes best is returned: the negative a BPR step learns most from.  The candidates never exist in memory: 4

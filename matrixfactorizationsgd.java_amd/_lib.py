@@ -99,6 +99,7 @@ FLAG_HOST_PACK = 32
 
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
+_u32p = C.POINTER(C.c_uint32)
 _f32p = C.POINTER(C.c_float)
 _f64p = C.POINTER(C.c_double)
 _H = C.c_void_p
@@ -138,6 +139,11 @@ SIGNATURES = {
     "mfsgd_seen_size": (C.c_int, [_H, _i64p]),
     "mfsgd_get_seen": (C.c_int, [_H, _i32p, C.c_int32, _i64p, _i32p, C.c_int64]),
     "mfsgd_sample_unseen": (C.c_int, [_H, _i32p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, _i32p]),
+    "mfsgd_set_item_weights": (C.c_int, [_H, _u32p, C.c_int32]),
+    "mfsgd_get_item_weights": (C.c_int, [_H, _u32p, _i32p]),
+    "mfsgd_clear_item_weights": (C.c_int, [_H]),
+    "mfsgd_seen_item_counts": (C.c_int, [_H, _i64p]),
+    "mfsgd_sample_unseen_weighted": (C.c_int, [_H, _i32p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, _i32p, _i64p]),
     "mfsgd_sample_unseen_hard": (C.c_int, [_H, _i32p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, _i32p, _f32p, _i32p]),
     "mfsgd_sample_unseen_violating": (C.c_int, [_H, _i32p, _i32p, C.c_int64, C.c_int32, C.c_float, C.c_int64, C.c_int64, _i32p,
                                                 _i32p, _f32p, _i32p]),

@@ -346,6 +346,7 @@ void mfsgd_destroy(mfsgd_handle* h) {
     h->dQ.reset();
     h->val = Validation{};
     h->seen = Seen{};
+    h->weights = ItemWeights{};
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->side_stream) {
@@ -535,6 +536,30 @@ int mfsgd_get_seen(mfsgd_handle* h, const int32_t* users, int32_t n_users, int64
 int mfsgd_sample_unseen(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first,
                         int32_t* out_items) {
     return guarded(h, "sample_unseen", [&]() -> int { return seen_sample(h, users, n, m, seed, first, out_items); });
+}
+
+// ---- item weights and the weighted draw (seen_index.cpp) ----
+int mfsgd_set_item_weights(mfsgd_handle* h, const uint32_t* w, int32_t n) {
+    return guarded(h, "set_item_weights", [&]() -> int { return weights_set(h, w, n); });
+}
+
+int mfsgd_get_item_weights(mfsgd_handle* h, uint32_t* w, int32_t* n) {
+    return guarded(h, "get_item_weights", [&]() -> int { return weights_get(h, w, n); });
+}
+
+int mfsgd_clear_item_weights(mfsgd_handle* h) {
+    return guarded(h, "clear_item_weights", [&]() -> int { return weights_clear(h); });
+}
+
+int mfsgd_seen_item_counts(mfsgd_handle* h, int64_t* counts) {
+    return guarded(h, "seen_item_counts", [&]() -> int { return seen_item_histogram(h, counts); });
+}
+
+int mfsgd_sample_unseen_weighted(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first,
+                                 int32_t* out_items, int64_t* out_mass) {
+    return guarded(h, "sample_unseen_weighted", [&]() -> int {
+        return seen_sample_weighted(h, users, n, m, seed, first, out_items, out_mass);
+    });
 }
 
 int mfsgd_sample_unseen_hard(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first,

@@ -72,14 +72,26 @@ struct Validation {
 //          the user count on holds n, so users appended inside the capacity have empty lists and need no work
 //   slot   capacity x int32, slot[u] = u: {slot, off, items} is a RecommendExcl whose slots are the user ids, so the
 //          EXCL kernels of recommend.hip read the index as they read the lists of one call
-// 4 n + 12 capacity + 8 bytes in all.
+// 4 n + 12 capacity + 8 bytes in all.  On a handle that has item weights (ItemWeights below) and n > 0, beside them
+//   mass   n x uint64, parallel to items: mass[q] = the weight of the items below items[q] that q's user has NOT seen;
+//          never decreasing along a list.  What the weighted draw searches (draw.hpp).  8 n bytes more.  It is made by
+//          whichever call completes or changes that state (seen_index.cpp, seen_mass_build) and leaves with the index.
 struct Seen {
     bool present = false;
     int64_t n = 0;
     int32_t capacity = 0;
     DevArray<long long> off;
     DevArray<int32_t> items, slot;
+    DevArray<unsigned long long> mass;
     RecommendExcl excl() const { return n > 0 ? RecommendExcl{slot.data(), off.data(), items.data()} : RecommendExcl{}; }
+};
+
+// The item weights of a handle (mfsgd_set_item_weights): C, their exclusive prefix on the device, n + 1 x uint64 with
+// C[0] = 0 and C[n] = W < 2^63; n is the item count they were set for, which mfsgd_append_items leaves behind.
+struct ItemWeights {
+    bool present = false;
+    int32_t n = 0;
+    DevArray<unsigned long long> C;
 };
 
 // Pairs (exclusions, candidates, seen pairs) per upload of a call that reads a caller's list: 32 MB of staging
@@ -152,6 +164,8 @@ struct mfsgd_handle {
     mutable std::string err;
     // what each user has already seen (mfsgd_set_seen, mfsgd_mark_seen): read by the _unseen serving calls
     mfsgd::Seen seen;
+    // what the weighted draw draws in proportion to (mfsgd_set_item_weights): the items', not the index's
+    mfsgd::ItemWeights weights;
 };
 
 namespace mfsgd {
@@ -224,6 +238,13 @@ int seen_update(mfsgd_handle* h, const char* name, bool merge, const int32_t* u,
 int seen_get(mfsgd_handle* h, const int32_t* users, int32_t n_users, int64_t* row_ptr, int32_t* items, int64_t items_capacity);
 // ... and of mfsgd_sample_unseen (the kernel is sample.hip's)
 int seen_sample(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first, int32_t* out_items);
+// ... and of the item-weight calls, mfsgd_seen_item_counts and mfsgd_sample_unseen_weighted (seen.hip, sample.hip)
+int weights_set(mfsgd_handle* h, const uint32_t* w, int32_t n);
+int weights_get(mfsgd_handle* h, uint32_t* w, int32_t* n);
+int weights_clear(mfsgd_handle* h);
+int seen_item_histogram(mfsgd_handle* h, int64_t* counts);
+int seen_sample_weighted(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first,
+                         int32_t* out_items, int64_t* out_mass);
 // ... and of mfsgd_sample_unseen_hard (the kernel is hardneg.hip's)
 int seen_sample_hard(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first, int32_t* out_items,
                      float* out_scores, int32_t* out_draw);

@@ -193,11 +193,26 @@ hipError_t seen_lengths(const long long* off, const int32_t* users, int32_t n, l
 hipError_t seen_gather(const long long* off, const int32_t* items, const int32_t* users, int32_t n, const long long* row_ptr,
                        int64_t longest, int32_t* out, hipStream_t st);
 
+// The unseen-mass table of the index {off, items} (`total` > 0 pairs, cap + 1 offsets) under item weights given by their
+// exclusive prefix C (n_w + 1 entries; items from n_w on weigh nothing): mass[x] = the weight of the items below items[x]
+// that the list of x's user does not hold.  G: `total` entries of scratch (the scan of the pairs' weights).
+hipError_t seen_unseen_mass(const long long* off, const int32_t* items, int64_t total, int32_t cap, const unsigned long long* C,
+                            int32_t n_w, unsigned long long* G, unsigned long long* mass, DevBuf& temp, hipStream_t st);
+// counts[i] += the number of lists that hold item i (counts: one zeroed entry per item of the model).
+hipError_t seen_item_counts(const int32_t* items, int64_t total, unsigned long long* counts, hipStream_t st);
+
 // sample.hip.  Uniform draws among the items a user has not seen (include/mfsgd.h, mfsgd_sample_unseen): out[x], x <
 // n_draws, is draw x % m of row x / m of `users` (every one a user of the index {off, items}; off == nullptr: an index
 // without pairs) with the counter first + x, among n_items items; -1 where the user has seen them all.  n_draws < 2^31.
 hipError_t sample_unseen_draws(const long long* off, const int32_t* items, const int32_t* users, int64_t n_draws, int32_t m,
                                int32_t n_items, int64_t seed, uint64_t first, int32_t* out, hipStream_t st);
+
+// The same in proportion to the items' weights (mfsgd_sample_unseen_weighted): mass is the index's unseen-mass table
+// (seen_unseen_mass), C the prefix of exactly n_items weights; -1 where every item of positive weight is seen.
+// row_mass[x / m] (nullable) receives the unseen weight of the row's user.
+hipError_t sample_weighted_draws(const long long* off, const int32_t* items, const unsigned long long* mass,
+                                 const unsigned long long* C, const int32_t* users, int64_t n_draws, int32_t m, int32_t n_items,
+                                 int64_t seed, uint64_t first, int32_t* out, long long* row_mass, hipStream_t st);
 
 // hardneg.hip.  Hard negatives (include/mfsgd.h, mfsgd_sample_unseen_hard): for each of the n rows of `users` (every one a
 // user of the index {off, items} and a row of P; off == nullptr: an index without pairs) the best-scoring of the m >= 1

@@ -1,7 +1,8 @@
-// sample.hip -- uniform draws among the items a user has NOT seen (mfsgd_sample_unseen), read off the seen-item index
-// where it lies (handle.hpp, Seen; seen.hip).  Integers only.  The draw itself is draw.hpp's, which states it: the mix
-// of (seed, counter), the rank t among the unseen items, and the search for the t-th of them.
-// One thread per draw, one store per draw.
+// sample.hip -- draws among the items a user has NOT seen, uniform (mfsgd_sample_unseen) or in proportion to the items'
+// weights (mfsgd_sample_unseen_weighted), read off the seen-item index where it lies (handle.hpp, Seen; seen.hip).
+// Integers only.  The draws themselves are draw.hpp's, which states them: the mix of (seed, counter), the rank t among
+// the unseen items or their weight, and the search for what holds that rank.
+// One thread per draw, one store per draw (the first draw of a row also stores the row's unseen weight, when asked).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -41,6 +42,31 @@ __global__ void __launch_bounds__(kSampleThreads) sample_unseen_kernel(const lon
     out[x] = item;
 }
 
+// The same with weights: mass parallels items, C is the prefix of the n_items weights; row_mass[x / m] (nullable)
+// receives the unseen weight of the row's user.
+__global__ void __launch_bounds__(kSampleThreads) sample_weighted_kernel(
+    const long long* __restrict__ off, const int32_t* __restrict__ items, const unsigned long long* __restrict__ mass,
+    const unsigned long long* __restrict__ C, const int32_t* __restrict__ users, const long long n_draws, const int m,
+    const int n_items, const unsigned long long seed, const unsigned long long first, int32_t* __restrict__ out,
+    long long* __restrict__ row_mass) {
+    const long long x = (long long)blockIdx.x * kSampleThreads + threadIdx.x;
+    if (x >= n_draws) return;
+    long long from = 0, s = 0;
+    if (off) {
+        const int u = users[x / m];
+        from = off[u];
+        s = off[u + 1] - from;
+    }
+    const unsigned long long cnt = draw_unseen_mass(items + from, mass + from, s, C, n_items);
+    int32_t item = -1;  // everything of positive weight is seen
+    if (cnt > 0) {
+        const unsigned long long t = __umul64hi(draw_mix64(seed, first + (unsigned long long)x), cnt);
+        item = draw_weighted_at(items + from, mass + from, s, C, n_items, cnt, t);
+    }
+    out[x] = item;
+    if (row_mass && x % m == 0) row_mass[x / m] = (long long)cnt;
+}
+
 }  // namespace
 
 hipError_t sample_unseen_draws(const long long* off, const int32_t* items, const int32_t* users, int64_t n_draws, int32_t m,
@@ -49,6 +75,16 @@ hipError_t sample_unseen_draws(const long long* off, const int32_t* items, const
     const unsigned blocks = (unsigned)((n_draws + kSampleThreads - 1) / kSampleThreads);  // (a piece: below 2^31 draws)
     hipLaunchKernelGGL(sample_unseen_kernel, dim3(blocks), dim3(kSampleThreads), 0, st, off, items, users, (long long)n_draws,
                        (int)m, (int)n_items, (unsigned long long)seed, (unsigned long long)first, out);
+    return hipGetLastError();
+}
+
+hipError_t sample_weighted_draws(const long long* off, const int32_t* items, const unsigned long long* mass,
+                                 const unsigned long long* C, const int32_t* users, int64_t n_draws, int32_t m, int32_t n_items,
+                                 int64_t seed, uint64_t first, int32_t* out, long long* row_mass, hipStream_t st) {
+    if (n_draws <= 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((n_draws + kSampleThreads - 1) / kSampleThreads);  // (a piece: below 2^31 draws)
+    hipLaunchKernelGGL(sample_weighted_kernel, dim3(blocks), dim3(kSampleThreads), 0, st, off, items, mass, C, users,
+                       (long long)n_draws, (int)m, (int)n_items, (unsigned long long)seed, (unsigned long long)first, out, row_mass);
     return hipGetLastError();
 }
 

@@ -4,13 +4,17 @@
 // of recommend.hip reach a list by user id.  Integers only.
 // Building it from pairs is recommend.hip's (recommend_excl_lists); what lives here is the first step of that (a pair
 // to its key user << 32 | item), the merge of a sorted distinct batch into an index that is not sorted again, the
-// tables of a larger capacity, and the gather of requested lists.
+// tables of a larger capacity, the gather of requested lists, the histogram of the items over the lists
+// (mfsgd_seen_item_counts), and the unseen-mass table of the weighted draw (Seen::mass): the pairs' weights, one
+// device-wide exclusive scan of them (rocPRIM), and per pair the weight below its item less the seen weight before it in
+// its list.
 // The merge: every output element is placed on its own.  A batch key is new when a binary search of its user's old list
 // misses it; off' = off + the new keys of the users before; an old element lands at off'[u] + its old position + the
 // user's new keys below it, a new key at off'[u] + its position among the user's new keys + the old items below it.
 // No loop runs over a user's list, so a user with 10^5 items costs what 10^5 users with one do.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
 
 #include <algorithm>
@@ -144,6 +148,48 @@ __global__ void __launch_bounds__(kSeenThreads) gather_kernel(const long long* _
     }
 }
 
+// C[min(x, n_w)]: the prefix of n_w item weights read for an item count that may have grown past them (items appended
+// since weigh nothing)
+__device__ __forceinline__ unsigned long long prefix_at(const unsigned long long* __restrict__ C, const int n_w, const long long x) {
+    return C[x < n_w ? x : n_w];
+}
+
+// w[x] = the weight of items[x]
+__global__ void __launch_bounds__(kSeenThreads) pair_weights_kernel(const int32_t* __restrict__ items, const long long total,
+                                                                    const unsigned long long* __restrict__ C, const int n_w,
+                                                                    unsigned long long* __restrict__ w) {
+    const long long stride = (long long)gridDim.x * kSeenThreads;
+    for (long long x = (long long)blockIdx.x * kSeenThreads + threadIdx.x; x < total; x += stride)
+        w[x] = prefix_at(C, n_w, (long long)items[x] + 1) - prefix_at(C, n_w, items[x]);
+}
+
+// mass[x] = C[items[x]] - (G[x] - G[off[u]]), u the user of position x (found as merge_old_kernel finds it) and G the
+// exclusive scan of the pairs' weights over the whole index, which wraps: only differences inside one list are used
+__global__ void __launch_bounds__(kSeenThreads) unseen_mass_kernel(const long long* __restrict__ off,
+                                                                   const int32_t* __restrict__ items, const long long total,
+                                                                   const int cap, const unsigned long long* __restrict__ C,
+                                                                   const int n_w, const unsigned long long* __restrict__ G,
+                                                                   unsigned long long* __restrict__ mass) {
+    const long long stride = (long long)gridDim.x * kSeenThreads;
+    for (long long x = (long long)blockIdx.x * kSeenThreads + threadIdx.x; x < total; x += stride) {
+        long long lo = 0, hi = cap;  // the first u in 0 .. cap with off[u] > x
+        while (lo < hi) {
+            const long long mid = (lo + hi) >> 1;
+            if (off[mid] <= x) lo = mid + 1;
+            else hi = mid;
+        }
+        mass[x] = prefix_at(C, n_w, items[x]) - (G[x] - G[off[lo - 1]]);
+    }
+}
+
+// counts[items[x]] += 1: integer atomics, so the sums do not depend on the order of arrival
+__global__ void __launch_bounds__(kSeenThreads) item_counts_kernel(const int32_t* __restrict__ items, const long long total,
+                                                                   unsigned long long* __restrict__ counts) {
+    const long long stride = (long long)gridDim.x * kSeenThreads;
+    for (long long x = (long long)blockIdx.x * kSeenThreads + threadIdx.x; x < total; x += stride)
+        atomicAdd(&counts[items[x]], 1ull);
+}
+
 // bits of a key user << 32 | item that a sort has to look at, users being below n_users
 inline unsigned key_bits(int32_t n_users) {
     unsigned end_bit = 33;
@@ -197,6 +243,29 @@ hipError_t seen_merge(const long long* off, const int32_t* items, int64_t total,
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(merge_new_kernel, dim3(seen_blocks(n_fresh)), dim3(kSeenThreads), 0, st, fresh, (long long)n_fresh, off, items,
                        off2, items2);
+    return hipGetLastError();
+}
+
+hipError_t seen_unseen_mass(const long long* off, const int32_t* items, int64_t total, int32_t cap, const unsigned long long* C,
+                            int32_t n_w, unsigned long long* G, unsigned long long* mass, DevBuf& temp, hipStream_t st) {
+    if (total <= 0) return hipSuccess;
+    size_t need = 0;
+    hipError_t e = rocprim::exclusive_scan(nullptr, need, mass, G, 0ull, (size_t)total, rocprim::plus<unsigned long long>(), st);
+    if (e == hipSuccess) e = temp.alloc(need);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(pair_weights_kernel, dim3(seen_blocks(total)), dim3(kSeenThreads), 0, st, items, (long long)total, C, (int)n_w,
+                       mass);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    e = rocprim::exclusive_scan(temp.get(), need, mass, G, 0ull, (size_t)total, rocprim::plus<unsigned long long>(), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(unseen_mass_kernel, dim3(seen_blocks(total)), dim3(kSeenThreads), 0, st, off, items, (long long)total, (int)cap,
+                       C, (int)n_w, G, mass);
+    return hipGetLastError();
+}
+
+hipError_t seen_item_counts(const int32_t* items, int64_t total, unsigned long long* counts, hipStream_t st) {
+    if (total <= 0) return hipSuccess;
+    hipLaunchKernelGGL(item_counts_kernel, dim3(seen_blocks(total)), dim3(kSeenThreads), 0, st, items, (long long)total, counts);
     return hipGetLastError();
 }
 

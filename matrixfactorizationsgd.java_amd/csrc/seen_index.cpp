@@ -39,6 +39,22 @@ static int pairs_to_keys(mfsgd_handle* h, const Bad& bad, const int32_t* u, cons
     return MFSGD_OK;
 }
 
+// The unseen-mass table (handle.hpp, Seen::mass) of an index {off, items} of n > 0 pairs under the weights w: complete,
+// with the device idle, when this returns; its scratch (8 n bytes of scanned weights, and rocPRIM's) is gone by then.
+// Weights set for fewer items than the model has now count the items appended since as weightless, so the table of a
+// handle whose weights are stale is still well defined (the draw refuses until they are set again).
+static int seen_mass_build(mfsgd_handle* h, const std::string& call, const ItemWeights& w, const long long* off, const int32_t* items,
+                           int64_t n, int32_t cap, DevArray<unsigned long long>& mass) {
+    auto bad = [h, &call](hipError_t e) { return serve_fail(h, call.c_str(), e); };
+    DevArray<unsigned long long> scanned;
+    DevBuf temp;  // the rocPRIM scratch, bytes of no type
+    int rc;
+    if ((rc = dev_alloc(h, mass, (size_t)n)) || (rc = dev_alloc(h, scanned, (size_t)n))) return rc;
+    HIPCHK_OR(bad, seen_unseen_mass(off, items, n, cap, w.C.data(), w.n, scanned.data(), mass.data(), temp, h->stream));
+    HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
+    return MFSGD_OK;
+}
+
 // A whole index from n > 0 checked pairs, complete before it takes the place of the one the handle has.
 static int seen_build(mfsgd_handle* h, const std::string& call, const int32_t* u, const int32_t* i, int64_t n) {
     int rc = ensure_device(h);
@@ -70,6 +86,9 @@ static int seen_build(mfsgd_handle* h, const std::string& call, const int32_t* u
         HIPCHK_OR(bad, seen_tables(nullptr, 0, 0, cap, nullptr, made.slot.data(), h->stream));
         HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
     }
+    if (h->weights.present &&
+        (rc = seen_mass_build(h, call, h->weights, made.off.data(), made.items.data(), made.n, cap, made.mass)))
+        return rc;
     made.present = true;
     made.capacity = cap;
     h->seen = std::move(made);
@@ -104,6 +123,11 @@ static int seen_merge_batch(mfsgd_handle* h, const std::string& call, const int3
     HIPCHK_OR(bad, seen_merge(old.off.data(), old.items.data(), old.n, old.capacity, keys_tmp.data(), fresh, off2.data(),
                               items2.data(), h->stream));
     HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
+    if (h->weights.present) {  // the merged index's unseen-mass table, before anything of the old index is released
+        DevArray<unsigned long long> mass2;
+        if ((rc = seen_mass_build(h, call, h->weights, off2.data(), items2.data(), old.n + fresh, old.capacity, mass2))) return rc;
+        old.mass = std::move(mass2);
+    }
     old.off = std::move(off2);
     old.items = std::move(items2);
     old.n += fresh;
@@ -212,6 +236,131 @@ int seen_sample(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int
         HIPCHK_OR(bad, sample_unseen_draws(s.n > 0 ? s.off.data() : nullptr, s.items.data(), d_users.data(), draws, m, h->cfg.n_items,
                                            seed, (uint64_t)first + (uint64_t)(x0 * m), d_out.data(), h->stream));
         HIPCHK_OR(bad, copy_down(out_items + x0 * m, d_out, (size_t)draws, h->stream));
+        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // (pageable memory: the staging is free for the next piece)
+    }
+    return MFSGD_OK;
+}
+
+// Body of mfsgd_set_item_weights (handle.cpp).  The prefix is summed on the host (8 (n + 1) bytes, once per call) and goes
+// up whole; with an index that has pairs the unseen-mass table follows.  Both are complete before either takes the place
+// of what the handle has.
+int weights_set(mfsgd_handle* h, const uint32_t* w, int32_t n) {
+    const std::string call = "set_item_weights: ";
+    if (n < 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "n is negative");
+    if (!w) return fail(h, MFSGD_ERR_INVALID_ARG, call + "w is null");
+    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, call + "single-partition handles only");
+    if (n != h->cfg.n_items)
+        return fail(h, MFSGD_ERR_INVALID_ARG, call + "n is " + std::to_string(n) + ", the model has " + std::to_string(h->cfg.n_items) + " items");
+    int rc = ensure_device(h);
+    if (rc) return rc;
+    auto bad = [h, &call](hipError_t e) { return serve_fail(h, call.c_str(), e); };
+    std::vector<unsigned long long> prefix((size_t)n + 1);
+    prefix[0] = 0;
+    for (int32_t x = 0; x < n; ++x) prefix[(size_t)x + 1] = prefix[x] + w[x];  // (below 2^31 * 2^32: no wrap)
+    ItemWeights made;
+    DevArray<unsigned long long> mass;
+    if ((rc = dev_alloc(h, made.C, prefix.size()))) return rc;
+    HIPCHK_OR(bad, copy_up(made.C, prefix.data(), prefix.size(), h->stream));
+    HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
+    made.present = true;
+    made.n = n;
+    const Seen& s = h->seen;
+    if (s.n > 0 && (rc = seen_mass_build(h, call, made, s.off.data(), s.items.data(), s.n, s.capacity, mass))) return rc;
+    h->weights = std::move(made);
+    if (mass) h->seen.mass = std::move(mass);
+    return MFSGD_OK;
+}
+
+// Body of mfsgd_get_item_weights (handle.cpp): the differences of the prefix, for the item count it was set for.
+int weights_get(mfsgd_handle* h, uint32_t* w, int32_t* n) {
+    if (!n) return fail(h, MFSGD_ERR_INVALID_ARG, "get_item_weights: n is null");
+    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "get_item_weights: single-partition handles only");
+    const ItemWeights& iw = h->weights;
+    *n = iw.present ? iw.n : -1;
+    if (!iw.present || !w) return MFSGD_OK;
+    int rc = ensure_device(h);
+    if (rc) return rc;
+    auto bad = [h](hipError_t e) { return serve_fail(h, "get_item_weights: ", e); };
+    std::vector<unsigned long long> prefix((size_t)iw.n + 1);
+    HIPCHK_OR(bad, copy_down(prefix.data(), iw.C, prefix.size(), h->stream));
+    HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
+    for (int32_t x = 0; x < iw.n; ++x) w[x] = (uint32_t)(prefix[(size_t)x + 1] - prefix[x]);
+    return MFSGD_OK;
+}
+
+// Body of mfsgd_clear_item_weights (handle.cpp).
+int weights_clear(mfsgd_handle* h) {
+    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "clear_item_weights: single-partition handles only");
+    if (h->device_ready) {
+        (void)hipSetDevice(h->cfg.device);
+        (void)hipStreamSynchronize(h->stream);
+    }
+    h->weights = ItemWeights{};
+    h->seen.mass.reset();
+    return MFSGD_OK;
+}
+
+// Body of mfsgd_seen_item_counts (handle.cpp).
+int seen_item_histogram(mfsgd_handle* h, int64_t* counts) {
+    if (!counts) return fail(h, MFSGD_ERR_INVALID_ARG, "seen_item_counts: counts is null");
+    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "seen_item_counts: single-partition handles only");
+    if (!h->seen.present) return fail(h, MFSGD_ERR_STATE, "seen_item_counts: no seen set");
+    const size_t n_items = (size_t)h->cfg.n_items;
+    std::fill(counts, counts + n_items, (int64_t)0);
+    const Seen& s = h->seen;
+    if (s.n == 0) return MFSGD_OK;  // host only: an empty index holds nothing on the device
+    int rc = ensure_device(h);
+    if (rc) return rc;
+    auto bad = [h](hipError_t e) { return serve_fail(h, "seen_item_counts: ", e); };
+    DevArray<long long> d_counts;  // (summed as unsigned: no count reaches 2^63)
+    if ((rc = dev_alloc(h, d_counts, n_items))) return rc;
+    HIPCHK_OR(bad, hipMemsetAsync(d_counts.data(), 0, sizeof(long long) * n_items, h->stream));
+    HIPCHK_OR(bad, seen_item_counts(s.items.data(), s.n, reinterpret_cast<unsigned long long*>(d_counts.data()), h->stream));
+    HIPCHK_OR(bad, copy_down(counts, d_counts, n_items, h->stream));
+    HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
+    return MFSGD_OK;
+}
+
+// Body of mfsgd_sample_unseen_weighted (handle.cpp): seen_sample with the weighted draw -- the same pieces, the same
+// counters, and a row's unseen weight beside its draws when asked.
+int seen_sample_weighted(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first,
+                         int32_t* out_items, int64_t* out_mass) {
+    const std::string call = "sample_unseen_weighted: ";
+    if (n < 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "n is negative");
+    if (m < 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "m is negative");
+    if (first < 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "first is negative");
+    if ((m > 0 && n > INT64_MAX / m) || first > INT64_MAX - n * m)
+        return fail(h, MFSGD_ERR_INVALID_ARG, call + "first + n * m exceeds 2^63 - 1");
+    const int64_t total = n * m;
+    if (total > 0 && (!users || !out_items)) return fail(h, MFSGD_ERR_INVALID_ARG, call + "users or out_items is null");
+    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, call + "single-partition handles only");
+    if (!h->seen.present) return fail(h, MFSGD_ERR_STATE, call + "no seen set");
+    const ItemWeights& iw = h->weights;
+    if (!iw.present) return fail(h, MFSGD_ERR_STATE, call + "no item weights");
+    if (iw.n != h->cfg.n_items)
+        return fail(h, MFSGD_ERR_STATE,
+                    call + "item weights cover " + std::to_string(iw.n) + " items, the model has " + std::to_string(h->cfg.n_items));
+    if (total == 0) return MFSGD_OK;
+    const int64_t x_bad = first_outside(users, n, h->cfg.n_users);
+    if (x_bad >= 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "user " + std::to_string(x_bad) + " out of range");
+    const Seen& s = h->seen;
+    if (s.n > 0 && !s.mass) return fail(h, MFSGD_ERR_STATE, call + "the index has no unseen-mass table");  // (never: it is eager)
+    int rc = ensure_device(h);
+    if (rc) return rc;
+    auto bad = [h, &call](hipError_t e) { return serve_fail(h, call.c_str(), e); };
+    const int64_t rows = std::min(n, std::max<int64_t>(1, kSampleChunk / m));
+    DevArray<int32_t> d_users, d_out;
+    DevArray<long long> d_mass;
+    if ((rc = dev_alloc(h, d_users, (size_t)rows)) || (rc = dev_alloc(h, d_out, (size_t)(rows * m)))) return rc;
+    if (out_mass && (rc = dev_alloc(h, d_mass, (size_t)rows))) return rc;
+    for (int64_t x0 = 0; x0 < n; x0 += rows) {
+        const int64_t c = std::min(rows, n - x0), draws = c * m;
+        HIPCHK_OR(bad, copy_up(d_users, users + x0, (size_t)c, h->stream));
+        HIPCHK_OR(bad, sample_weighted_draws(s.n > 0 ? s.off.data() : nullptr, s.items.data(), s.mass.data(), iw.C.data(),
+                                             d_users.data(), draws, m, h->cfg.n_items, seed, (uint64_t)first + (uint64_t)(x0 * m),
+                                             d_out.data(), out_mass ? d_mass.data() : nullptr, h->stream));
+        HIPCHK_OR(bad, copy_down(out_items + x0 * m, d_out, (size_t)draws, h->stream));
+        if (out_mass) HIPCHK_OR(bad, copy_down(out_mass + x0, d_mass, (size_t)c, h->stream));
         HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // (pageable memory: the staging is free for the next piece)
     }
     return MFSGD_OK;

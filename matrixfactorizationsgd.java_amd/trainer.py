@@ -141,6 +141,30 @@ def warp_weights(rank):
     return w
 
 
+def popularity_weights(counts, alpha=0.75, resolution=16, least=1):
+    """uint32 item weights for set_item_weights from popularity counts (seen_item_counts):
+    max(least, rint(resolution * counts ** alpha)), computed in float64.  alpha=0.75 is word2vec's exponent, alpha=0 the
+    uniform draw, alpha=1 popularity itself; `resolution` is how finely the integer weights resolve small counts.
+    least=1 keeps items nobody has seen drawable, least=0 never draws them (word2vec's behaviour).  Python only: the
+    C-ABI takes the integers, so no pow decides a bit of a draw.  ValueError for a negative count, a non-finite alpha or
+    a weight above 2^32 - 1."""
+    cc = np.asarray(counts)
+    if cc.ndim != 1:
+        raise ValueError("counts must be a 1-d array")
+    cc = cc.astype(np.float64)
+    if not np.isfinite(alpha):
+        raise ValueError("alpha must be finite")
+    if cc.size and not (cc >= 0).all():
+        raise ValueError("counts must not be negative")
+    if int(least) < 0 or not float(resolution) >= 0:
+        raise ValueError("least and resolution must not be negative")
+    with np.errstate(divide="ignore"):  # (0 ** a negative alpha is inf, and refused below)
+        w = np.maximum(float(int(least)), np.rint(float(resolution) * cc ** float(alpha)))
+    if int(least) > 0xFFFFFFFF or (w.size and not (w <= 0xFFFFFFFF).all()):
+        raise ValueError("a weight exceeds 2^32 - 1")
+    return w.astype(np.uint32)
+
+
 def _pairs(a, b, what):
     """Two int32 1-d arrays of one length (None: no pairs)."""
     aa, bb = (np.empty(0, np.int32),) * 2 if a is None else (_i32(a), _i32(b))
@@ -442,7 +466,7 @@ class MatrixFactorizationSGD:
         res = tuple(a for a, on in ((x, margins), (out.as_dict(), info)) if on)
         return None if not res else res[0] if len(res) == 1 else res
 
-    def fit_bpr(self, u, i, epochs, *, seed=0, first_epoch=0, stats=True, candidates=1, refresh=None):
+    def fit_bpr(self, u, i, epochs, *, seed=0, first_epoch=0, stats=True, candidates=1, refresh=None, sampling="uniform"):
         """Trains on one-class data with Bayesian personalised ranking: (u[x], i[x]) are the positives, duplicates
         allowed, and every epoch pairs each of them with one freshly drawn item its user has not seen and takes one
         pairwise step per positive, in the order given -- pass the positives shuffled: the order is the caller's, and a
@@ -462,6 +486,9 @@ class MatrixFactorizationSGD:
         partial_fit_pairwise of the rest.  The candidates do not depend on refresh, the picks do; a smaller refresh
         picks against fresher factors and costs a call per block.  Splitting the epochs with first_epoch gives the same
         bits here too.  candidates=1 is the uniform draw above and does not read the factors to draw.
+        sampling="weighted" draws every epoch's J with sample_unseen_weighted instead, same counters, in proportion to
+        the item weights the handle has (set_item_weights, set_popularity_weights); everything else is as above.  With
+        candidates > 1 it is a ValueError: hard negatives among weighted candidates are not built.
         Returns, with stats, dict(loss, auc), float64[epochs] each, from the margins x every triple had just before its
         own step: the mean of log1p(exp(-x)), and the share of triples with x > 0.  Without stats: None."""
         uu, ii = _pairs(np.atleast_1d(u), np.atleast_1d(i), "u and i")
@@ -470,6 +497,10 @@ class MatrixFactorizationSGD:
             raise ValueError("epochs must not be negative")
         if m < 1 or (refresh is not None and int(refresh) < 1):
             raise ValueError("candidates and refresh must be at least 1")
+        weighted = self._sampling(sampling)
+        if weighted and m > 1:
+            raise ValueError('sampling="weighted" needs candidates=1')
+        draw_into = self._sample_weighted_into if weighted else self._sample_unseen_into
         if self.seen_size() < 0:
             self.set_seen(uu, ii)
         if not self._initialised:
@@ -492,7 +523,7 @@ class MatrixFactorizationSGD:
             return dict(loss=loss, auc=auc) if stats else None
         jj = np.empty((n, 1), np.int32)
         for e in range(epochs):
-            self._sample_unseen_into(uu, 1, seed, (int(first_epoch) + e) * n, jj)
+            draw_into(uu, 1, seed, (int(first_epoch) + e) * n, jj)
             J = jj[:, 0]
             if n and J.min() < 0:  # users who have seen everything have no negatives
                 keep = J >= 0
@@ -660,6 +691,69 @@ class MatrixFactorizationSGD:
         self._check(self._lib.mfsgd_sample_unseen(self._handle(), _p(uu, C.c_int32), uu.size, int(m), int(seed), int(first),
                                                   _p(out, C.c_int32)))
 
+    # -- weighted negatives (include/mfsgd.h, "weighted negatives") ------------------
+    def set_item_weights(self, w):
+        """The item weights of sample_unseen_weighted become w, one integer in [0, 2^32) per item of the model
+        (mfsgd_set_item_weights): an item of weight 0 is never drawn.  They belong to the items and outlive set_seen,
+        mark_seen and clear_seen; after add_items they must be set again before the next weighted draw."""
+        ww = np.atleast_1d(np.asarray(w))
+        if ww.ndim != 1 or (ww.size and ww.dtype.kind not in "iu"):
+            raise ValueError("w must be a 1-d integer array")
+        if ww.size and (int(ww.min()) < 0 or int(ww.max()) > 0xFFFFFFFF):
+            raise ValueError("weights must lie in [0, 2^32)")
+        ww = np.ascontiguousarray(ww, dtype=np.uint32)
+        self._check(self._lib.mfsgd_set_item_weights(self._handle(), _p(ww, C.c_uint32), ww.size))
+
+    def item_weights(self):
+        """uint32 weights as set (for the item count they were set for), or None when the handle has none."""
+        n = C.c_int32(-2)
+        self._check(self._lib.mfsgd_get_item_weights(self._handle(), None, C.byref(n)))
+        if n.value < 0:
+            return None
+        w = np.empty(n.value, np.uint32)
+        self._check(self._lib.mfsgd_get_item_weights(self._handle(), _p(w, C.c_uint32), C.byref(n)))
+        return w
+
+    def clear_item_weights(self):
+        """Drops the item weights and what the index keeps for them; the handle has none afterwards."""
+        self._check(self._lib.mfsgd_clear_item_weights(self._handle()))
+
+    def seen_item_counts(self):
+        """int64 [items]: the number of users whose seen list holds each item (mfsgd_seen_item_counts: a histogram on the
+        device) -- the popularity that popularity_weights turns into weights."""
+        counts = np.empty(self.items, np.int64)
+        self._check(self._lib.mfsgd_seen_item_counts(self._handle(), _p(counts, C.c_int64)))
+        return counts
+
+    def set_popularity_weights(self, alpha=0.75, resolution=16, least=1):
+        """set_item_weights(popularity_weights(seen_item_counts(), alpha, resolution, least))."""
+        self.set_item_weights(popularity_weights(self.seen_item_counts(), alpha, resolution, least))
+
+    def sample_unseen_weighted(self, users, m=1, seed=0, first=0, *, mass=False):
+        """sample_unseen with every unseen item drawn in proportion to its weight (mfsgd_sample_unseen_weighted: exact,
+        integers only, no rejection): int32 [len(users), m], -1 throughout a row whose user has seen every item of
+        positive weight.  Draw d of row x is a pure function of seed, the counter first + x * m + d, the user's list, the
+        weights and the item count.  mass=True adds int64 [len(users)], each row's unseen weight (written where m > 0)."""
+        uu = _i32(np.atleast_1d(users))
+        if uu.ndim != 1:
+            raise ValueError("users must be a 1-d array")
+        out = np.empty((uu.size, max(int(m), 0)), np.int32)
+        ms = np.zeros(uu.size, np.int64) if mass else None
+        self._sample_weighted_into(uu, m, seed, first, out, ms)
+        return (out, ms) if mass else out
+
+    def _sample_weighted_into(self, uu, m, seed, first, out, mass=None):
+        """sample_unseen_weighted(uu, ...) into `out`, a C-contiguous int32 array of uu.size * m entries."""
+        self._check(self._lib.mfsgd_sample_unseen_weighted(self._handle(), _p(uu, C.c_int32), uu.size, int(m), int(seed),
+                                                           int(first), _p(out, C.c_int32),
+                                                           None if mass is None else _p(mass, C.c_int64)))
+
+    @staticmethod
+    def _sampling(sampling):
+        if sampling not in ("uniform", "weighted"):
+            raise ValueError('sampling must be "uniform" or "weighted"')
+        return sampling == "weighted"
+
     def sample_unseen_hard(self, users, m, seed=0, first=0, *, scores=False, draws=False):
         """int32 [len(users)]: for each row, the best-scoring of the m items sample_unseen(users, m, seed, first) draws for
         it, under the factors as they are now (mfsgd_sample_unseen_hard: drawn, scored and picked on the device, nothing
@@ -702,7 +796,7 @@ class MatrixFactorizationSGD:
         res = tuple(a for a, on in ((out, True), (dr, draws), (mg, margins), (rk, ranks)) if on)
         return res[0] if len(res) == 1 else res
 
-    def fit_implicit(self, u, i, epochs, negatives=4, *, seed=0, pos=1.0, neg=0.0, first_epoch=0, rmse=True):
+    def fit_implicit(self, u, i, epochs, negatives=4, *, seed=0, pos=1.0, neg=0.0, first_epoch=0, rmse=True, sampling="uniform"):
         """Trains on one-class data (clicks, plays, purchases): (u[x], i[x]) are the positives, duplicates allowed, and
         every epoch pairs each of them with `negatives` freshly drawn items its user has not seen, trained towards `neg`.
         Unseen means unseen by the seen-item index, not by (u, i).  A handle without an index gets set_seen(u, i), and
@@ -714,11 +808,14 @@ class MatrixFactorizationSGD:
         users who have seen everything; set_ratings of that set, fit(1).  Seed and epoch number alone decide the draws:
         epochs=a followed by epochs=b, first_epoch=a is epochs=a + b bit for bit.  negatives=0: one set_ratings of the
         positives and fit(epochs).  Returns the RMSE of each epoch over that epoch's own set (None with rmse=False);
-        the last epoch's set stays the handle's rating set."""
+        the last epoch's set stays the handle's rating set.
+        sampling="weighted" draws every epoch's J with sample_unseen_weighted instead, same counters, in proportion to
+        the item weights the handle has (set_item_weights, set_popularity_weights); everything else is as above."""
         uu, ii = _pairs(np.atleast_1d(u), np.atleast_1d(i), "u and i")
         epochs, negatives, n = int(epochs), int(negatives), uu.size
         if epochs < 0 or negatives < 0:
             raise ValueError("epochs and negatives must not be negative")
+        draw_into = self._sample_weighted_into if self._sampling(sampling) else self._sample_unseen_into
         if self.seen_size() < 0:
             self.set_seen(uu, ii)
         if not self._initialised:
@@ -732,7 +829,7 @@ class MatrixFactorizationSGD:
         set_r = np.concatenate([rr, np.full(n * negatives, neg, np.float32)])
         out = np.zeros(epochs, np.float64)
         for x in range(epochs):
-            self._sample_unseen_into(uu, negatives, seed, (int(first_epoch) + x) * n * negatives, set_i[n:])
+            draw_into(uu, negatives, seed, (int(first_epoch) + x) * n * negatives, set_i[n:])
             if n and set_i[n:].min() < 0:  # users who have seen everything have no negatives
                 keep = np.concatenate([np.ones(n, bool), set_i[n:] >= 0])
                 self.set_ratings(set_u[keep], set_i[keep], set_r[keep])
