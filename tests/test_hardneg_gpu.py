@@ -50,7 +50,7 @@ def _normal_factors(rng, U, I, k):
 
 
 # ---- 1. lane groups and candidate counts -----------------------------------------------------------------------------------------
-@pytest.mark.parametrize("k", (1, 6, 16, 64, 256))  # L = 1, 2, 4, 16, 64
+@pytest.mark.parametrize("k", (1, 6, 16, 20, 64, 100, 256))  # L = 1, 2, 4, 8, 16, 32 (the permlane level of the dot), 64
 def test_lane_groups_and_candidate_counts(mf, oracle, k):
     U, I, full, seed, first = 48, 130, 11, 5, (1 << 40) + 7
     L = _group_lanes(k)

@@ -46,7 +46,9 @@ def _check(mf, oracle, U, I, k, u, i, j, after=None):
 
 
 # ---- 1. every lane-group shape ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("k", (1, 6, 16, 64, 256))  # L = 1; pad columns; L = 4 without; L = 16; one group per wave
+# L = 1; pad columns at L = 2; L = 4 without; L = 8 with a lane of padding only; L = 16; L = 32 (the permlane level of the
+# dot) with pad columns and without; one group per wave
+@pytest.mark.parametrize("k", (1, 6, 16, 20, 64, 100, 128, 256))
 def test_lane_group_sizes(mf, oracle, k):
     U, I, u, i, j = pc.random_batch()
 
@@ -61,7 +63,7 @@ def test_lane_group_sizes(mf, oracle, k):
         gP, gQ = m.get_factors()
         _same(gP, P, "P after fit(1)"), _same(gQ, Q, "Q after fit(1)")
 
-    info = _check(mf, oracle, U, I, k, u, i, j, after=then_train if k == 6 else None)
+    info = _check(mf, oracle, U, I, k, u, i, j, after=then_train if k in (6, 20, 100) else None)
     assert 1 <= info["launches"] <= info["levels"]
 
 
@@ -117,7 +119,7 @@ def _special_factors(k, rng):
 SPECIAL = (np.array([0, 1, 2, 3], np.int32), np.array([0, 1, 3, 4], np.int32), np.array([1, 2, 4, 5], np.int32))
 
 
-@pytest.mark.parametrize("k", (6, 64))
+@pytest.mark.parametrize("k", (6, 9, 64, 65))  # 9 and 65: the last lane of a group (L = 4), the last 15 (L = 32) hold padding only
 def test_saturated_and_infinite_margins(mf, k):
     rng = np.random.default_rng(k)
     P0, Q0 = _special_factors(k, rng)
@@ -142,25 +144,55 @@ def test_saturated_and_infinite_margins(mf, k):
         assert np.array_equal(g.view(np.uint32)[~np.isnan(w)], w.view(np.uint32)[~np.isnan(w)]), what
 
 
-@pytest.mark.parametrize("k", (6, 64))
-def test_a_nan_factor(mf, oracle, k):
+def _nan_alike(got, want, what):
     """NaN payloads and signs are not part of the contract: which entries are NaN is, and every other bit."""
+    assert got.dtype == want.dtype and got.shape == want.shape, what
+    assert np.array_equal(np.isnan(got), np.isnan(want)), what
+    assert np.array_equal(got.view(np.uint32)[~np.isnan(want)], want.view(np.uint32)[~np.isnan(want)]), what
+
+
+@pytest.mark.parametrize("k", (6, 9, 64, 65))  # 9 and 65: lanes that hold padding only (L = 4, L = 32)
+def test_a_nan_factor(mf, oracle, k):
+    """NaN payloads and signs are not part of the contract: which entries are NaN is, and every other bit.  After the
+    batch with the NaN steps a second one goes over the three rows of a NaN step and over rows still finite, and every
+    pair is predicted, against the sequential loop: the state after a NaN step goes on working.  (A NaN step makes every
+    real column of its rows NaN, so this cannot tell whether a pad column took the NaN too; the infinite steps of
+    tests/test_warp_gpu.py can.)"""
     U, I, u, i, j = pc.random_batch(n=80)
     P0, Q0 = oracle.init_factors(U, I, k, SEED)
     P0[5, k // 2], Q0[7, 0] = np.nan, np.nan
     P, Q, x = pc.c_pass(P0, Q0, u, i, j, LR, LAM)
     assert np.isnan(x).any() and not np.isnan(x).all() and not np.isnan(P).all()
+    # The second batch, in this order:
+    #   three finite steps: users still finite, all on the two items still finite (the batch left no more than a few);
+    #   the triple t of a NaN step once more: its three rows are NaN already;
+    #   `again`: those of the batch's first 20 triples that name neither finite item, so more NaN steps, which leave the
+    #   two finite items finite and the last predict with numbers to compare.
+    t = int(np.flatnonzero(np.isnan(x))[0])
+    assert np.isnan(P[u[t]]).all() and np.isnan(Q[i[t]]).all() and np.isnan(Q[j[t]]).all()
+    fu, fi = np.flatnonzero(~np.isnan(P).any(axis=1)), np.flatnonzero(~np.isnan(Q).any(axis=1))
+    assert fu.size >= 3 and fi.size >= 2
+    again = np.flatnonzero(~np.isin(i[:20], fi) & ~np.isin(j[:20], fi))
+    assert again.size >= 10
+    u2 = np.concatenate([fu[:3], [u[t]], u[again]]).astype(np.int32)
+    i2 = np.concatenate([np.full(3, fi[0]), [i[t]], i[again]]).astype(np.int32)
+    j2 = np.concatenate([np.full(3, fi[1]), [j[t]], j[again]]).astype(np.int32)
+    P2, Q2, x2 = pc.c_pass(P, Q, u2, i2, j2, LR, LAM)
+    assert np.isnan(x2[3]) and not np.isnan(x2[:3]).any()
     with mf.MatrixFactorizationSGD(U, I, k, LR, LAM, SEED) as m:
         m.set_factors(P0, Q0)
         got = m.partial_fit_pairwise(u, i, j, margins=True)
         gP, gQ = m.get_factors()
         pu, pi = np.repeat(np.arange(U, dtype=np.int32), I), np.tile(np.arange(I, dtype=np.int32), U)
         pred = m.predict(pu, pi)  # the pad columns stayed +0.0: a row without a NaN column has finite dots
-    for g, w, what in ((got, x, "margins"), (gP, P, "P"), (gQ, Q, "Q")):
-        assert np.array_equal(np.isnan(g), np.isnan(w)), what
-        assert np.array_equal(g.view(np.uint32)[~np.isnan(w)], w.view(np.uint32)[~np.isnan(w)]), what
-    want = oracle.predict(P, Q, pu, pi)
-    assert np.array_equal(np.isnan(pred), np.isnan(want)) and np.array_equal(pred[~np.isnan(want)], want[~np.isnan(want)])
+        got2 = m.partial_fit_pairwise(u2, i2, j2, margins=True)
+        gP2, gQ2 = m.get_factors()
+        pred2 = m.predict(pu, pi)
+    for g, w, what in ((got, x, "margins"), (gP, P, "P"), (gQ, Q, "Q"), (pred, oracle.predict(P, Q, pu, pi), "predict"),
+                       (got2, x2, "margins of the second batch"), (gP2, P2, "P after it"), (gQ2, Q2, "Q after it"),
+                       (pred2, oracle.predict(P2, Q2, pu, pi), "predict after it")):
+        _nan_alike(g, w, what)
+    assert not np.isnan(pred2).all() and np.isnan(pred2).any()
 
 
 # ---- 4. a live handle stays whole -----------------------------------------------------------------------------------------------

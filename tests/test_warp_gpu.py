@@ -68,7 +68,19 @@ def _ranked_factors(rng, k):
 
 
 # ---- 1. lane groups, candidate counts and margins -----------------------------------------------------------------------------
-@pytest.mark.parametrize("k", (5, 64, 128, 256))  # pad columns and L = 2; L = 16; the permlane level; one group per wave
+def _mixed_waves(items, draws, m, rows):
+    """How many waves -- `rows` consecutive rows, from a multiple of `rows` on -- hold both a row whose first draw is its
+    pick and a live row that walks all m draws without one (draws == m: not a user who has seen everything, whose group
+    never enters the rounds): the groups of such a wave leave the rounds at different trips, by the ballot."""
+    n = items.size // rows * rows
+    first = ((items >= 0) & (draws == 0))[:n].reshape(-1, rows).any(axis=1)
+    never = ((items < 0) & (draws == m))[:n].reshape(-1, rows).any(axis=1)
+    return int((first & never).sum())
+
+
+# L = 1, 4 and 8 (64, 16 and 8 rows to a wave: each finds its pick in a round of its own); pad columns and L = 2; L = 16;
+# the permlane level; one group per wave
+@pytest.mark.parametrize("k", (3, 5, 12, 20, 64, 128, 256))
 def test_lane_groups_candidate_counts_and_margins(mf, oracle, k):
     seed, first, n = 5, (1 << 40) + 7, 700
     L = _group_lanes(k)
@@ -112,6 +124,9 @@ def test_lane_groups_candidate_counts_and_margins(mf, oracle, k):
                     assert (draws[hit] >= L).any(), what
                 if margin != np.inf:
                     assert (draws[~full] == m).any(), what
+                if L <= 8 and margin != np.inf:  # (the outputs are the reference's by now) many rows to a wave, and in some
+                    # waves a pick at the first draw beside a row without any: the ballot exit with mixed groups
+                    assert _mixed_waves(items, draws, m, 64) > 0 and _mixed_waves(items, draws, m, 64 // L) > 0, what
                 if m > 1 and margin == 1.0:  # (its own difference is 0: below the margin, were it not passed over)
                     upto = np.where(hit, draws, m)[out]
                     assert any((cand[r, :d] == pos[r]).any() for r, d in zip(out, upto)), what
@@ -271,7 +286,7 @@ def _hot_batch(rng, n=400):
     return UU, II, u, i, j
 
 
-@pytest.mark.parametrize("k", (5, 64, 256))
+@pytest.mark.parametrize("k", (1, 5, 16, 20, 64, 100, 256))  # L = 1, 2, 4, 8, 16, 32, 64
 def test_the_weighted_step_is_the_sequential_loop(mf, oracle, k):
     rng = np.random.default_rng(k)
     UU, II, u, i, j = _hot_batch(rng)
@@ -301,14 +316,18 @@ def test_the_weighted_step_is_the_sequential_loop(mf, oracle, k):
         _nan_alike((x,) + h.get_factors(), (want_x, P, Q), f"k {k}: infinite weights")
 
 
-@pytest.mark.parametrize("k", (5, 64))
-def test_a_nan_weight_is_canonical_at_the_door(mf, k):
+@pytest.mark.parametrize("k", (5, 9, 64, 65))  # 9 and 65: lanes that hold padding only (L = 4, L = 32)
+def test_a_nan_weight_is_canonical_at_the_door(mf, oracle, k):
     """A weight of 0xFFFFFFFF would hand the word the training kernels read as "not posted yet" to three factor rows.  The
-    factors are read, not trained on."""
+    factors are read, not trained on.  A second batch with finite weights then goes over the rows of the NaN steps and over
+    rows still finite, and every pair is predicted, against the sequential loop: the state after a NaN step goes on
+    working.  (A NaN step makes every real column of its rows NaN, so this cannot tell whether a pad column took the NaN
+    too: test_an_infinite_step_leaves_the_pad_columns_zero can.)"""
     rng = np.random.default_rng(k)
     UU, II, u, i, j = _hot_batch(rng, 60)
     w = rng.standard_normal(u.size).astype(np.float32)
     w.view(np.uint32)[[2, 31]] = 0xFFFFFFFF
+    pu, pi = np.repeat(np.arange(UU, dtype=np.int32), II), np.tile(np.arange(II, dtype=np.int32), UU)
     with mf.MatrixFactorizationSGD(UU, II, k, LR, LAM, SEED) as h:
         h.init_factors()
         P0, Q0 = h.get_factors()
@@ -322,6 +341,52 @@ def test_a_nan_weight_is_canonical_at_the_door(mf, k):
             assert bits.size and ((bits & 0x3FFFFF) != 0x3FFFFF).all()
         finite = ~np.isnan(h.predict(u, i))  # the pad columns stayed +0.0: rows the NaN never reached have finite dots
         assert finite.any()
+        _nan_alike((h.predict(pu, pi),), (oracle.predict(wP, wQ, pu, pi),), f"k {k}: predict")
+        # the second batch: four triples over rows that are still finite, the two NaN steps' triples, 20 of the batch again
+        fu, fi = np.flatnonzero(~np.isnan(wP).any(axis=1)), np.flatnonzero(~np.isnan(wQ).any(axis=1))
+        assert fu.size >= 4 and fi.size >= 2
+        pick = np.r_[2, 31, 0:20]
+        u2 = np.concatenate([fu[:4], u[pick]]).astype(np.int32)
+        i2 = np.concatenate([np.full(4, fi[0]), i[pick]]).astype(np.int32)
+        j2 = np.concatenate([np.full(4, fi[1]), j[pick]]).astype(np.int32)
+        w2 = rng.standard_normal(u2.size).astype(np.float32)
+        x2 = h.partial_fit_pairwise(u2, i2, j2, weights=w2, margins=True)
+        wP2, wQ2, wx2 = WC.c_pass(wP, wQ, u2, i2, j2, w2, LR, LAM)
+        assert np.isnan(wx2[4:6]).all() and not np.isnan(wx2[:4]).any() and not np.isnan(wP2).all()
+        pred = h.predict(pu, pi)
+        _nan_alike((x2,) + h.get_factors() + (pred,), (wx2, wP2, wQ2, oracle.predict(wP2, wQ2, pu, pi)), f"k {k}: a finite batch after")
+        assert np.isnan(pred).any() and not np.isnan(pred).all()
+
+
+@pytest.mark.parametrize("k", (1, 5, 9, 20, 65, 100))  # pad columns beside real ones in a lane, and lanes of padding only
+def test_an_infinite_step_leaves_the_pad_columns_zero(mf, oracle, k):
+    """Where a pad column left non-zero can be seen.  A step of weight +Inf makes every real column of its three rows
+    +Inf or -Inf (none NaN: no column of q_i - q_j or p is 0 here), while fma(Inf, 0, c * 0) in a pad column is NaN.  A
+    row chosen to agree in sign with such a row, column by column, then has the dot +Inf in the sequential loop, which has
+    no pad columns -- and NaN on the device if one of its pad columns took the step."""
+    UU, II = 6, 8
+    rng = np.random.default_rng(k)
+    P0 = rng.uniform(0.5, 1.5, (UU, k)).astype(np.float32) * rng.choice([-1.0, 1.0], (UU, k)).astype(np.float32)
+    Q0 = rng.uniform(0.5, 1.5, (II, k)).astype(np.float32) * rng.choice([-1.0, 1.0], (II, k)).astype(np.float32)
+    Q0[1] = -Q0[0] * np.float32(0.5)  # the triple (0, 0, 1): q_i - q_j has the signs of q_i
+    Q0[2] = Q0[0]  # agrees with the new P[0]
+    P0[1] = P0[0]  # agrees with the new Q[0], disagrees with the new Q[1]
+    u, i, j, w = np.array([0], np.int32), np.array([0], np.int32), np.array([1], np.int32), np.array([np.inf], np.float32)
+    wP, wQ, wx = WC.c_pass(P0, Q0, u, i, j, w, LR, LAM)
+    assert np.isinf(wP[0]).all() and np.isinf(wQ[0]).all() and np.isinf(wQ[1]).all() and np.isfinite(wx).all()
+    pu, pi = np.array([0, 1, 1], np.int32), np.array([2, 0, 1], np.int32)
+    want = oracle.predict(wP, wQ, pu, pi)
+    assert list(want) == [np.inf, np.inf, -np.inf]
+    with mf.MatrixFactorizationSGD(UU, II, k, LR, LAM, SEED) as h:
+        h.set_factors(P0, Q0)
+        x = h.partial_fit_pairwise(u, i, j, weights=w, margins=True)
+        P, Q = h.get_factors()
+        assert x.tobytes() == wx.tobytes() and P.tobytes() == wP.tobytes() and Q.tobytes() == wQ.tobytes()
+        assert h.predict(pu, pi).tobytes() == want.tobytes()
+        # a finite step over the same three rows: Inf - Inf in the margin, and NaN from there on, as in the loop
+        x2 = h.partial_fit_pairwise(u, i, j, weights=np.ones(1, np.float32), margins=True)
+        wP2, wQ2, wx2 = WC.c_pass(wP, wQ, u, i, j, np.ones(1, np.float32), LR, LAM)
+        _nan_alike((x2,) + h.get_factors(), (wx2, wP2, wQ2), f"k {k}: a finite step after")
 
 
 @pytest.mark.parametrize("k", (5, 64))
