@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver; + mfsgd_set_validation, mfsgd_validation_size, mfsgd_validation_rmse, mfsgd_rmse_pairs, mfsgd_train_early_stop; + mfsgd_row_inv_norms, mfsgd_similar_items, mfsgd_similar_users, mfsgd_similar_rows; + mfsgd_online_levels, mfsgd_apply_ratings; + mfsgd_fold_in_items, mfsgd_append_users, mfsgd_append_items, mfsgd_reserve_rows, mfsgd_get_capacity; + mfsgd_recommend_among, mfsgd_recommend_rows_among, mfsgd_debug_serve_seconds; + mfsgd_set_seen, mfsgd_mark_seen, mfsgd_clear_seen, mfsgd_seen_size, mfsgd_get_seen, mfsgd_recommend_unseen, mfsgd_recommend_unseen_among, mfsgd_rank_items_unseen, mfsgd_evaluate_ranking_unseen; + mfsgd_sample_unseen; + mfsgd_triple_levels, mfsgd_apply_triples, mfsgd_bpr_weights; + mfsgd_sample_unseen_hard; + mfsgd_sample_unseen_violating, mfsgd_apply_triples_weighted, mfsgd_warp_weights (additions: no existing call changed) */
+#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver; + mfsgd_set_validation, mfsgd_validation_size, mfsgd_validation_rmse, mfsgd_rmse_pairs, mfsgd_train_early_stop; + mfsgd_row_inv_norms, mfsgd_similar_items, mfsgd_similar_users, mfsgd_similar_rows; + mfsgd_online_levels, mfsgd_apply_ratings; + mfsgd_fold_in_items, mfsgd_append_users, mfsgd_append_items, mfsgd_reserve_rows, mfsgd_get_capacity; + mfsgd_recommend_among, mfsgd_recommend_rows_among, mfsgd_debug_serve_seconds; + mfsgd_set_seen, mfsgd_mark_seen, mfsgd_clear_seen, mfsgd_seen_size, mfsgd_get_seen, mfsgd_recommend_unseen, mfsgd_recommend_unseen_among, mfsgd_rank_items_unseen, mfsgd_evaluate_ranking_unseen; + mfsgd_sample_unseen; + mfsgd_triple_levels, mfsgd_apply_triples, mfsgd_bpr_weights; + mfsgd_sample_unseen_hard; + mfsgd_sample_unseen_violating, mfsgd_apply_triples_weighted, mfsgd_warp_weights; + mfsgd_fold_in_users_pairwise (additions: no existing call changed) */
 
 typedef enum mfsgd_status {
     MFSGD_OK = 0,
@@ -206,6 +206,47 @@ int mfsgd_fold_in_users(mfsgd_handle* h, int32_t n_new, const int64_t* row_ptr, 
  * "fold_in_items: " and name the user of a rating where those name its item.  The model is not modified.             */
 int mfsgd_fold_in_items(mfsgd_handle* h, int32_t n_new, const int64_t* row_ptr, const int32_t* users, const float* ratings,
                         int32_t epochs, const float* init_rows, int64_t seed, float* out_rows);
+/* Pairwise fold-in: rows for n_new users that are not in the model, from their positives alone, for a model that only
+ * orders items (mfsgd_apply_triples: fit_bpr, fit_warp).  Each new user runs a BPR chain of its own against the model's
+ * item factors Q, which stay fixed, and draws its own negatives among the items it has not named.  New user x owns the
+ * positives A = items[row_ptr[x] .. row_ptr[x + 1]) (CSR, row_ptr[0] == 0), of length len, in the order given; an item
+ * twice in one list gives two steps per epoch.  T = row_ptr[n_new].  The start rows are mfsgd_fold_in_users': init_rows
+ * (n_new x k, dense) or, with init_rows == NULL, the rows seeded by `seed`.
+ * The rule.  A pure function of the start row, A, Q's bits, n_items, lr, lambda, epochs, m, draw_seed and the row's
+ * counter range.  S is A sorted and made distinct, of length s; cnt = n_items - s.  For e = 0 .. epochs - 1, then
+ * a = 0 .. len - 1, the step tau = e * len + a:
+ *     c_d     = first + ((row_ptr[x] * epochs + tau) * m + d),  d = 0 .. m - 1      unsigned 64-bit, as mfsgd_sample_unseen
+ *     cand[d] = mfsgd_sample_unseen's draw for (draw_seed, c_d, S, n_items): with r its 32-bit mix, t = (r * cnt) >> 32,
+ *               cand[d] = t + p, p = the number of q in [0, s) with S[q] - q <= t
+ *     pick    = 0 if m == 1, otherwise mfsgd_sample_unseen_hard's pick over score(d) = dot(row, Q[cand[d]]) with the row
+ *               as it is NOW: the largest non-NaN score, scores equal as floats to the smaller d, all NaN to d = 0
+ *     i = A[a];  j = cand[pick]
+ *     xm = dot(row, Q[i]) - dot(row, Q[j]);  g = lsig(xm);  sz = lr * g;  c = 1 - lr * lambda
+ *     row[f] = fma(sz, Q[i][f] - Q[j][f], c * row[f])                the p line of mfsgd_apply_triples, nothing else
+ *     out_margin[row_ptr[x] * epochs + tau] = xm;  out_neg[row_ptr[x] * epochs + tau] = j         (either nullable)
+ * dot is the canonical dot and lsig the logistic weight of DESIGN.md section 3; everything is fp32, nothing is
+ * contracted.  With cnt == 0 (the list names every item) no step is taken: the start row comes back, the user's margins
+ * are 0x7FC00000 and their negatives -1.  A user without positives and epochs == 0 are valid (the start row comes back).
+ * Counters.  User x owns the counters first + row_ptr[x] * epochs * m .. first + row_ptr[x + 1] * epochs * m, so a call
+ * can be split and reordered: users [a, b) of a call are the call on row_ptr rebased to a (row_ptr[a .. b] - row_ptr[a],
+ * items + row_ptr[a], init_rows + a * k) with first + row_ptr[a] * epochs * m.  With seeded start rows the split call
+ * must be given its rows through init_rows, the seeded rows being numbered from 0 in every call.
+ * Checks, all before any device work, in this order ("fold_in_pairwise: ..."): MFSGD_ERR_INVALID_ARG for a negative n_new
+ * or epochs; for m < 1; for a negative first, or first + T * epochs * m above 2^63 - 1; for a null array that is needed
+ * (row_ptr and out_rows with n_new > 0, items with T > 0), row_ptr[0] != 0, a decreasing row_ptr or more than 2^32 - 1
+ * positives of one user; for an item outside [0, n_items), the message naming its position in items.  Then
+ * MFSGD_ERR_STATE as mfsgd_fold_in_users reports it: n_parts != 1, factors never initialised, set or loaded, or no Q.
+ * Then n_new == 0 is MFSGD_OK and touches nothing.  A valid call with n_new > 0 and no usable GPU is MFSGD_ERR_NO_DEVICE.
+ * The call needs no seen-item index and no stored ratings, and modifies neither the model nor any schedule, cached
+ * graph, index, item weights or held-out set.  Positives go to the device in batches of whole users of at most 2^22
+ * positives (a user with more is a batch of its own); each batch's lists S are built there, and 4 bytes per step come
+ * down for each of out_margin and out_neg that is asked for.  All staging is freed before the call returns, on every
+ * path -- mfsgd_debug_device_bytes is the same before and after.  A user's chain is sequential, as in
+ * mfsgd_fold_in_users.  Not done here: WARP-style picks, weighted draws, new items, a lambda of its own for negatives. */
+int mfsgd_fold_in_users_pairwise(mfsgd_handle* h, int32_t n_new, const int64_t* row_ptr, const int32_t* items,
+                                 int32_t epochs, int32_t m, const float* init_rows, int64_t seed, int64_t draw_seed,
+                                 int64_t first, float* out_rows, float* out_margin /* nullable, T * epochs */,
+                                 int32_t* out_neg /* nullable, T * epochs */);
 /* Top-N as mfsgd_recommend_excluding, where "user j" is rows[j] (n_rows x k, dense: for instance what
  * mfsgd_fold_in_users returned) instead of a row of P: every row is answered, in order, and excl_row[x] indexes rows.
  * Same ordering, padding, scores and argument checks, with n_rows in the place of n_users.                           */

@@ -122,6 +122,8 @@ SIGNATURES = {
     "mfsgd_recommend_excluding": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i32p, _i32p, C.c_int64, _i32p, _f32p]),
     "mfsgd_fold_in_users": (C.c_int, [_H, C.c_int32, _i64p, _i32p, _f32p, C.c_int32, _f32p, C.c_int64, _f32p]),
     "mfsgd_fold_in_items": (C.c_int, [_H, C.c_int32, _i64p, _i32p, _f32p, C.c_int32, _f32p, C.c_int64, _f32p]),
+    "mfsgd_fold_in_users_pairwise": (C.c_int, [_H, C.c_int32, _i64p, _i32p, C.c_int32, C.c_int32, _f32p, C.c_int64, C.c_int64,
+                                              C.c_int64, _f32p, _f32p, _i32p]),
     "mfsgd_recommend_rows": (C.c_int, [_H, _f32p, C.c_int32, C.c_int32, _i32p, _i32p, C.c_int64, _i32p, _f32p]),
     "mfsgd_recommend_among": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i64p, _i32p, C.c_int64, _i32p, _i32p, C.c_int64,
                                         _i32p, _f32p]),

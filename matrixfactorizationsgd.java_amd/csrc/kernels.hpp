@@ -1,5 +1,5 @@
 // kernels.hpp -- host-callable launchers of every kernel unit: epoch.hip, cells.hip, kernels.hip, foldin.hip,
-// online.hip, pairwise.hip, rehyper.hip, recommend.hip, rank.hip, seen.hip, sample.hip, hardneg.hip, warp.hip, similar.hip, validate.hip
+// foldin_pairwise.hip, online.hip, pairwise.hip, rehyper.hip, recommend.hip, rank.hip, seen.hip, sample.hip, hardneg.hip, warp.hip, similar.hip, validate.hip
 // and grow.hip.
 #pragma once
 
@@ -56,6 +56,35 @@ hipError_t launch_predict(int L, const float* P, const float* Q, const int32_t* 
 hipError_t launch_fold_in(int L, const float* F, float* rows, int k, const long long* row_ptr, long long base,
                           const int32_t* perm, int nb, const int32_t* ids, const float* ratings, int epochs, float lr,
                           float c, hipStream_t st);
+
+// foldin_pairwise.hip.  Pairwise fold-in of the nb new users of one batch against Q (include/mfsgd.h,
+// mfsgd_fold_in_users_pairwise): group g takes new user x = perm[g], whose positives are entries ptr[x] .. ptr[x + 1] of
+// ids (ptr: nb + 1 words counting from the batch's first positive, which is positive `base` of the call) and whose
+// sorted distinct list is s_items[s_off[x] .. s_off[x + 1]) (recommend_excl_lists' output for the keys x << 32 | id),
+// and runs `epochs` passes of the rule over them: step tau of the user draws its m candidates at the counters
+// first + ((base + ptr[x]) * epochs + tau) * m + d.  rows: nb x k dense, the start rows on entry and the folded rows on
+// return.  out_margin / out_neg (either nullable): entry ptr[x] * epochs + tau receives step tau's margin and negative;
+// 0x7FC00000 and -1 throughout for a user whose list names every item.  perm is best sorted by length, longest first;
+// the result does not depend on it.  The batch holds at least one positive, every id is a row of Q and m >= 1: the
+// caller checks.  Asynchronous on st.
+struct PairwiseFold {
+    const float* Q;
+    float* rows;
+    int k;
+    const long long* ptr;
+    long long base;
+    const int32_t* perm;
+    int nb;
+    const int32_t* ids;
+    const long long* s_off;
+    const int32_t* s_items;
+    int n_items, epochs, m;
+    float lr, c;  // c = 1 - lr * lambda
+    unsigned long long seed, first;
+    float* out_margin;
+    int32_t* out_neg;
+};
+hipError_t launch_fold_in_pairwise(int L, const PairwiseFold& a, hipStream_t st);
 
 // online.hip.  Levels l0 .. l1 - 1 of one piece of an online update against the live P and Q (kp-padded rows): level l is
 // the ratings level_ptr[l] .. level_ptr[l + 1] - 1 of u / i / r, which share no user and no item; each gets the whole

@@ -551,6 +551,112 @@ static int fold_in_core(mfsgd_handle* h, const FoldName& what, const DevArray<fl
     return MFSGD_OK;
 }
 
+// A pairwise fold-in call as the caller gave it: n_new lists of positives in CSR form, and where the results go.
+struct PairwiseFoldRequest {
+    int32_t n_new;
+    const int64_t* row_ptr;
+    const int32_t* items;
+    int32_t epochs, m;
+    const float* init_rows;
+    int64_t seed, draw_seed, first;
+    float* out_rows;
+    float* out_margin;
+    int32_t* out_neg;
+};
+
+// Body of mfsgd_fold_in_users_pairwise: fold_in_core's batches, perm and staging; per batch the sorted distinct lists S
+// are made on the device out of the positives that were just uploaded, the way candidates_to_device makes its per-row
+// lists (keys user << 32 | item, sorted and made distinct, one CSR offset array), and the chain kernel runs off them.
+static int fold_in_pairwise_core(mfsgd_handle* h, const PairwiseFoldRequest& req) {
+    const std::string call = "fold_in_pairwise: ";
+    const int32_t n_new = req.n_new, epochs = req.epochs, m = req.m;
+    const int64_t* row_ptr = req.row_ptr;
+    if (n_new < 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "n_new is negative");
+    if (epochs < 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "epochs is negative");
+    if (m < 1) return fail(h, MFSGD_ERR_INVALID_ARG, call + "m is below 1");
+    if (req.first < 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "first is negative");
+    // (the counters of T positives; a T that the checks below refuse is not multiplied)
+    const int64_t claimed = n_new > 0 && row_ptr ? row_ptr[n_new] : 0;
+    if (claimed > 0 && (__int128)req.first + (__int128)claimed * epochs * m > (__int128)INT64_MAX)
+        return fail(h, MFSGD_ERR_INVALID_ARG, call + "first + T * epochs * m exceeds 2^63 - 1");
+    if (n_new > 0 && (!row_ptr || !req.out_rows)) return fail(h, MFSGD_ERR_INVALID_ARG, call + "row_ptr or out_rows is null");
+    if (n_new > 0 && row_ptr[0] != 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "row_ptr[0] is not 0");
+    for (int32_t x = 0; x < n_new; ++x) {
+        if (row_ptr[x + 1] < row_ptr[x])
+            return fail(h, MFSGD_ERR_INVALID_ARG, call + "row_ptr decreases at user " + std::to_string(x));
+        if (row_ptr[x + 1] - row_ptr[x] > (int64_t)UINT32_MAX)  // (a batch is whole users, and its keys are counted in 32 bits)
+            return fail(h, MFSGD_ERR_INVALID_ARG, call + "more than 2^32 - 1 positives of user " + std::to_string(x));
+    }
+    const int64_t total = n_new > 0 ? row_ptr[n_new] : 0;
+    if (total > 0 && !req.items) return fail(h, MFSGD_ERR_INVALID_ARG, call + "items is null");
+    const int64_t j = first_outside(req.items, total, h->cfg.n_items);
+    if (j >= 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "item of positive " + std::to_string(j) + " out of range");
+    if (const int rc = check_reads_factors(h, "fold_in_pairwise")) return rc;
+    if (n_new == 0) return MFSGD_OK;
+    int rc = factors_to_device(h);
+    if (rc) return rc;
+    const int k = h->cfg.k;
+    // batches of whole lists, in the caller's order, so that each batch is one contiguous piece of items
+    const Batches bt = cut_batches(n_new, [row_ptr](int32_t x) { return row_ptr[x + 1] - row_ptr[x]; }, kFoldChunk, kFoldRows);
+    auto bad = [h, &call](hipError_t e) { return serve_fail(h, call.c_str(), e); };
+    const bool work = epochs > 0 && total > 0;
+    const size_t stage = (size_t)bt.max_weight, steps = stage * (size_t)epochs;
+    DevArray<float> d_rows, d_margin;
+    DevArray<long long> d_ptr, s_off;
+    DevArray<int32_t> d_perm, d_ids, s_items, d_neg;
+    DevArray<unsigned long long> keys, keys_tmp;
+    DevArray<unsigned> count;
+    DevBuf temp;  // the rocPRIM scratch, bytes of no type
+    const size_t row_floats = (size_t)n_new * (size_t)k;
+    if ((rc = dev_alloc(h, d_rows, row_floats))) return rc;
+    if (work) {
+        if ((rc = dev_alloc(h, d_ptr, (size_t)bt.max_rows + 1)) || (rc = dev_alloc(h, d_perm, (size_t)bt.max_rows))) return rc;
+        if ((rc = dev_alloc(h, d_ids, stage))) return rc;
+        if ((rc = dev_alloc(h, keys, stage)) || (rc = dev_alloc(h, keys_tmp, stage)) || (rc = dev_alloc(h, count, 4))) return rc;
+        if ((rc = dev_alloc(h, s_off, (size_t)bt.max_rows + 1)) || (rc = dev_alloc(h, s_items, stage))) return rc;
+        if (req.out_margin && (rc = dev_alloc(h, d_margin, steps))) return rc;
+        if (req.out_neg && (rc = dev_alloc(h, d_neg, steps))) return rc;
+    }
+    // the start rows, dense: the kernel pads them to kp in its registers
+    if (req.init_rows)
+        HIPCHK_OR(bad, copy_up(d_rows, req.init_rows, row_floats, h->stream));
+    else
+        HIPCHK_OR(bad, launch_init_rows(d_rows.data(), n_new, k, k, req.seed, 0, (float)(1.0 / std::sqrt((double)k)), h->stream));
+    std::vector<int32_t> perm;
+    std::vector<long long> ptr;
+    for (size_t b = 0; b < bt.count() && work; ++b) {
+        const int32_t x0 = bt.cut[b], nb = bt.cut[b + 1] - x0;
+        const int64_t base = row_ptr[x0], nr = row_ptr[x0 + nb] - base;
+        if (nr == 0) continue;
+        // longest first: a wave runs as long as its longest list
+        perm.resize((size_t)nb);
+        std::iota(perm.begin(), perm.end(), 0);
+        const int64_t* rp = row_ptr + x0;
+        std::stable_sort(perm.begin(), perm.end(), [rp](int32_t a, int32_t b2) { return rp[a + 1] - rp[a] > rp[b2 + 1] - rp[b2]; });
+        // the offsets count from the batch's first positive: what the key kernel and the chain kernel index the batch by
+        ptr.resize((size_t)nb + 1);
+        for (int32_t x = 0; x <= nb; ++x) ptr[(size_t)x] = rp[x] - base;
+        HIPCHK_OR(bad, copy_up(d_ptr, ptr.data(), (size_t)nb + 1, h->stream));
+        HIPCHK_OR(bad, copy_up(d_perm, perm.data(), (size_t)nb, h->stream));
+        HIPCHK_OR(bad, copy_up(d_ids, req.items + base, (size_t)nr, h->stream));
+        HIPCHK_OR(bad, recommend_cand_keys(d_ptr.data(), nb, d_ids.data(), 0, nr, keys.data(), h->stream));
+        HIPCHK_OR(bad, recommend_excl_lists(keys.data(), keys_tmp.data(), nr, nb, count.data(), s_off.data(), s_items.data(), temp,
+                                            h->stream));
+        const PairwiseFold job{h->dQ.data(), d_rows.data() + (size_t)x0 * k, k, d_ptr.data(), base, d_perm.data(), nb,
+                               d_ids.data(), s_off.data(), s_items.data(), h->cfg.n_items, epochs, m, h->cfg.lr,
+                               1.0f - h->cfg.lr * h->cfg.lambda, (unsigned long long)req.draw_seed, (unsigned long long)req.first,
+                               d_margin.data(), d_neg.data()};
+        HIPCHK_OR(bad, launch_fold_in_pairwise(h->geo.L, job, h->stream));
+        const size_t at = (size_t)base * (size_t)epochs, n_steps = (size_t)nr * (size_t)epochs;
+        if (req.out_margin) HIPCHK_OR(bad, copy_down(req.out_margin + at, d_margin, n_steps, h->stream));
+        if (req.out_neg) HIPCHK_OR(bad, copy_down(req.out_neg + at, d_neg, n_steps, h->stream));
+        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // perm, ptr and the staging buffers are reused
+    }
+    HIPCHK_OR(bad, copy_down(req.out_rows, d_rows, row_floats, h->stream));
+    HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
+    return MFSGD_OK;
+}
+
 }  // namespace mfsgd
 
 using namespace mfsgd;
@@ -813,6 +919,15 @@ int mfsgd_fold_in_users(mfsgd_handle* h, int32_t n_new, const int64_t* row_ptr, 
     return guarded(h, "fold_in", [&]() -> int {
         return fold_in_core(h, kFoldInUsers, &mfsgd_handle::dQ, h->cfg.n_items,
                             {n_new, row_ptr, items, ratings, epochs, init_rows, seed, out_rows});
+    });
+}
+
+int mfsgd_fold_in_users_pairwise(mfsgd_handle* h, int32_t n_new, const int64_t* row_ptr, const int32_t* items, int32_t epochs,
+                                 int32_t m, const float* init_rows, int64_t seed, int64_t draw_seed, int64_t first,
+                                 float* out_rows, float* out_margin, int32_t* out_neg) {
+    return guarded(h, "fold_in_pairwise", [&]() -> int {
+        return fold_in_pairwise_core(h, {n_new, row_ptr, items, epochs, m, init_rows, seed, draw_seed, first, out_rows,
+                                         out_margin, out_neg});
     });
 }
 

@@ -879,6 +879,43 @@ class MatrixFactorizationSGD:
         seeded start rows are fold_in()'s.  The model is not modified; add_items(rows) puts the rows into it."""
         return self._fold_in(self._lib.mfsgd_fold_in_items, row_ptr, users, ratings, epochs, init, seed, "users")
 
+    def fold_in_pairwise(self, row_ptr, items, epochs, *, candidates=1, init=None, seed=None, draw_seed=0, first=0,
+                         margins=False, negatives=False):
+        """Rows [n_new, k] for users that are not in a model trained by fit_bpr or fit_warp, from their positives alone
+        (mfsgd_fold_in_users_pairwise): new user x owns the positives items[row_ptr[x] .. row_ptr[x + 1]) (CSR), and
+        `epochs` passes of the BPR step run over them against the model's item factors, which stay fixed.  Every step
+        draws `candidates` items the user has not named -- sample_unseen's draws for draw_seed and the counters from
+        first + row_ptr[x] * epochs * candidates on -- and takes the one the row scores highest (sample_unseen_hard's
+        pick; candidates=1: the draw).  init and seed: the start rows, as in fold_in().  margins=True adds float32
+        [row_ptr[-1] * epochs], each step's margin before it; negatives=True adds int32 of that shape, each step's
+        negative; with either the result is a tuple (rows, margins, negatives) without what was not asked for.  A user
+        who names every item takes no step (NaN and -1).  The model is not modified; the rows feed recommend_rows,
+        rank_items_rows and add_users."""
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        ii = _i32(items)
+        if rp.ndim != 1 or rp.size < 1:
+            raise ValueError("row_ptr must be a 1-d array of n_new + 1 offsets")
+        n_new = rp.size - 1
+        if ii.ndim != 1 or ii.size != rp[-1]:
+            raise ValueError("items must be a 1-d array of row_ptr[-1] entries")
+        ip = None
+        if init is not None:
+            init = _f32(init)
+            if init.shape != (n_new, self.k):
+                raise ValueError("init must be n_new x k")
+            ip = _p(init, C.c_float)
+        steps = int(rp[-1]) * max(int(epochs), 0)
+        rows = np.empty((n_new, self.k), np.float32)
+        mg = np.empty(steps, np.float32) if margins else None
+        ng = np.empty(steps, np.int32) if negatives else None
+        self._check(self._lib.mfsgd_fold_in_users_pairwise(self._handle(), n_new, _p(rp, C.c_int64), _p(ii, C.c_int32), int(epochs),
+                                                           int(candidates), ip, self.seed if seed is None else int(seed),
+                                                           int(draw_seed), int(first), _p(rows, C.c_float),
+                                                           None if mg is None else _p(mg, C.c_float),
+                                                           None if ng is None else _p(ng, C.c_int32)))
+        res = tuple(a for a, on in ((rows, True), (mg, margins), (ng, negatives)) if on)
+        return res[0] if len(res) == 1 else res
+
     # -- growing a live model (include/mfsgd.h, "growing a live model") -------------
     def _dims(self):
         u, i = C.c_int32(), C.c_int32()
