@@ -1,8 +1,8 @@
 // draw.hpp -- the draws of mfsgd_sample_unseen and mfsgd_sample_unseen_weighted (include/mfsgd.h) as device functions,
-// integers only: ONE definition each.  The uniform one is shared by sample.hip (every draw goes to memory), hardneg.hip
-// (the draws are scored and only the best leaves the kernel) and warp.hip (the draws are walked to the first that
-// violates a margin), so that the candidates of mfsgd_sample_unseen_hard and mfsgd_sample_unseen_violating are
-// mfsgd_sample_unseen's by construction; the weighted one is sample.hip's for now and lies here for the same reason.
+// integers only: ONE definition each.  The uniform one is shared by sample.hip (every draw goes to memory), pick.hip
+// (the draws are scored and only the best leaves the kernel, or walked to the first that violates a margin) and
+// foldin_pairwise.hip (a chain draws its own negatives), so that the candidates of mfsgd_sample_unseen_hard and
+// mfsgd_sample_unseen_violating are mfsgd_sample_unseen's by construction; the weighted one lies here for the same reason.
 // A uniform draw is a pure function of (seed, its counter c), the user's sorted, distinct list S (length s) and the item
 // count:
 //     r   = draw_mix32(seed, c): the upper 32 bits of splitmix64's output for the state seed + golden * (c + 1)
@@ -78,6 +78,48 @@ __device__ __forceinline__ int32_t draw_weighted_at(const int32_t* __restrict__ 
         else b = mid;
     }
     return (int32_t)(a - 1);
+}
+
+// What a draw knows of a user: the sorted, distinct list of the items the user HAS seen (list[0 .. s), which starts at
+// items[from] of the index) and cnt = n_items - s, the number of those the user has not.  off == nullptr: an index
+// without pairs, every list is empty.
+struct Unseen {
+    long long s = 0, from = 0, cnt = 0;
+    const int32_t* list = nullptr;
+    Unseen() = default;
+    __device__ __forceinline__ Unseen(const long long* off, const int32_t* items, const int u, const int n_items)
+        : Unseen(off, items, [u] { return u; }, n_items) {}
+    // user() is asked for the user only where there are lists (sample.hip divides for the row of a draw only then).
+    template <class User>
+    __device__ __forceinline__ Unseen(const long long* off, const int32_t* items, User&& user, const int n_items) {
+        if (off) {
+            const int u = user();
+            from = off[u];
+            s = off[u + 1] - from;
+        }
+        list = items + from;
+        cnt = (long long)n_items - s;
+    }
+};
+
+// The uniform draw of counter c among the items that are not in the set's list: the mix, the rank, the search.  cnt > 0.
+__device__ __forceinline__ int32_t draw_uniform(const Unseen& set, const unsigned long long seed, const unsigned long long c) {
+    const unsigned long long r = draw_mix32(seed, c);
+    return draw_unseen_at(set.list, set.s, (long long)((r * (unsigned long long)set.cnt) >> 32));
+}
+
+// The weighted draw of counter c: the unseen weight, the rank within it, the two searches.  mass is the index's table
+// (parallel to its items), C the prefix of the n_items weights; cnt receives the unseen weight of the set's user, and
+// the draw is -1 when that is 0: everything of positive weight is seen.
+__device__ __forceinline__ int32_t draw_weighted(const Unseen& set, const unsigned long long* __restrict__ mass,
+                                                 const unsigned long long* __restrict__ C, const int n_items,
+                                                 const unsigned long long seed, const unsigned long long c,
+                                                 unsigned long long& cnt) {
+    const unsigned long long* g = mass + set.from;
+    cnt = draw_unseen_mass(set.list, g, set.s, C, n_items);
+    int32_t item = -1;
+    if (cnt > 0) item = draw_weighted_at(set.list, g, set.s, C, n_items, cnt, __umul64hi(draw_mix64(seed, c), cnt));
+    return item;
 }
 
 }  // namespace

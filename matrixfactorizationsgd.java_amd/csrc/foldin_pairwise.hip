@@ -5,7 +5,8 @@
 // select.  What a step adds to foldin.hip's: a negative, the pick among m unseen draws.
 //
 // The draw is draw.hpp's (mfsgd_sample_unseen's by construction), the score the canonical dot of canon.hpp, the pick the
-// rule of hardneg.hip, the update the P line of pairwise.hip's step with canon.hpp's lsig: nothing is restated here.
+// rule of pick.hip's hard negatives, the update the P line of pairwise.hip's step with canon.hpp's lsig: nothing is
+// restated here but that rule's one line (through a shared function these kernels compile to other code).
 // A draw is a function of its counter and the user's list S, never of the row, so the draws, their binary searches and
 // the Q gathers of the positive and of the candidates run ahead of the chain; on the chain are the m scores, the pick,
 // lsig and the update.  A draw is made by ONE lane of the group and handed round (a lane permute, no LDS memory): the L
@@ -29,7 +30,7 @@ namespace {
 // the gathers (foldin.hip, kFoldDepth, is the idiom).  6, not kFoldDepth's 8: two rows a step are twice the registers, and
 // at 8 the kernel has room for two waves a SIMD where it has room for three at 6 ("Pairwise fold-in": measured).
 constexpr int kPairDepth = 6;
-// m > 1.  Candidates of one group whose Q rows are in flight together (hardneg.hip, kHardDepth); the next chunk is
+// m > 1.  Candidates of one group whose Q rows are in flight together (pick.hip, kPickDepth); the next chunk is
 // gathered while the chunk in hand is scored, across the end of a step too.
 constexpr int kPairChunk = 4;
 
@@ -41,8 +42,8 @@ struct Group {
     static constexpr int GPB = 256 / L;  // groups per block
     int lig, x;
     bool live, draws;
-    long long p0, len, at, s, cnt, steps, trip;
-    const int32_t* list;
+    long long p0, len, at, steps, trip;
+    Unseen set;  // of the batch's own lists; filled below by selects (Unseen's constructor branches: other code)
     float4 row;
 
     __device__ __forceinline__ Group(const PairwiseFold& a) {
@@ -52,10 +53,10 @@ struct Group {
         x = live ? a.perm[g] : 0;
         p0 = live ? a.ptr[x] : 0;
         len = live ? a.ptr[x + 1] - p0 : 0;
-        const long long from = live ? a.s_off[x] : 0;
-        s = live ? a.s_off[x + 1] - from : 0;
-        list = a.s_items + from;
-        cnt = (long long)a.n_items - s;
+        set.from = live ? a.s_off[x] : 0;
+        set.s = live ? a.s_off[x + 1] - set.from : 0;
+        set.list = a.s_items + set.from;
+        const long long cnt = set.cnt = (long long)a.n_items - set.s;
         draws = live && cnt > 0;  // a group without draws gathers row 0 of Q in their place
         // a group without positives reads entry 0 of the batch (the launcher sends no batch without positives)
         at = len > 0 ? p0 : 0;
@@ -77,8 +78,7 @@ struct Group {
 
     // The item of the user's draw number n (counter c0 + n); 0 for a group without draws.
     __device__ __forceinline__ int32_t draw(const PairwiseFold& a, const unsigned long long c0, const long long n) const {
-        const unsigned long long r = draw_mix32(a.seed, c0 + (unsigned long long)n);
-        return draw_unseen_at(list, s, (long long)((r * (unsigned long long)cnt) >> 32));
+        return draw_uniform(set, a.seed, c0 + (unsigned long long)n);
     }
 
     // One step of the chain on the row: the margin before it, the P line of the pairwise step, kept when `on`.
@@ -102,7 +102,7 @@ struct Group {
 
     __device__ __forceinline__ void finish(const PairwiseFold& a) const {
         if (!live) return;
-        if (cnt <= 0)  // no step was taken: the user's margins and negatives say so
+        if (set.cnt <= 0)  // no step was taken: the user's margins and negatives say so
             for (long long e = lig; e < len * a.epochs; e += L) {
                 if (a.out_margin) a.out_margin[p0 * a.epochs + e] = __builtin_bit_cast(float, kQuietNaN);
                 if (a.out_neg) a.out_neg[p0 * a.epochs + e] = -1;

@@ -1,4 +1,4 @@
-// handle.hpp -- what the units of the C-ABI that see inside the handle share (handle.cpp, seen_index.cpp, ratings.cpp,
+// handle.hpp -- what the units of the C-ABI that see inside the handle share (handle.cpp, seen_index.cpp, sampling.cpp, ratings.cpp,
 // train.cpp, online_update.cpp, serve.cpp): the handle, its partitions, the error channel, the guard with that channel, and the helpers that cross
 // units.  Internal: installed nowhere.  dsgd.cpp and io.cpp see the handle through include/mfsgd.h only, and take the
 // guard from guard.hpp.
@@ -236,19 +236,18 @@ void seen_adopt_tables(mfsgd_handle* h, int32_t new_cap, DevArray<long long>& of
 // ... and the bodies of mfsgd_set_seen (merge == false) / mfsgd_mark_seen, `name` being the call's, and of mfsgd_get_seen
 int seen_update(mfsgd_handle* h, const char* name, bool merge, const int32_t* u, const int32_t* i, int64_t n);
 int seen_get(mfsgd_handle* h, const int32_t* users, int32_t n_users, int64_t* row_ptr, int32_t* items, int64_t items_capacity);
-// ... and of mfsgd_sample_unseen (the kernel is sample.hip's)
-int seen_sample(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first, int32_t* out_items);
-// ... and of the item-weight calls, mfsgd_seen_item_counts and mfsgd_sample_unseen_weighted (seen.hip, sample.hip)
+// ... and of the item-weight calls and mfsgd_seen_item_counts (seen.hip)
 int weights_set(mfsgd_handle* h, const uint32_t* w, int32_t n);
 int weights_get(mfsgd_handle* h, uint32_t* w, int32_t* n);
 int weights_clear(mfsgd_handle* h);
 int seen_item_histogram(mfsgd_handle* h, int64_t* counts);
+// sampling.cpp.  The bodies of mfsgd_sample_unseen and mfsgd_sample_unseen_weighted (the kernels are sample.hip's), of
+// mfsgd_sample_unseen_hard and of mfsgd_sample_unseen_violating (pick.hip's)
+int seen_sample(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first, int32_t* out_items);
 int seen_sample_weighted(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first,
                          int32_t* out_items, int64_t* out_mass);
-// ... and of mfsgd_sample_unseen_hard (the kernel is hardneg.hip's)
 int seen_sample_hard(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first, int32_t* out_items,
                      float* out_scores, int32_t* out_draw);
-// ... and of mfsgd_sample_unseen_violating (the kernel is warp.hip's)
 int seen_sample_violating(mfsgd_handle* h, const int32_t* users, const int32_t* pos_items, int64_t n, int32_t m, float margin,
                           int64_t seed, int64_t first, int32_t* out_items, int32_t* out_draw, float* out_margin, int32_t* out_rank);
 // ratings.cpp

@@ -1,5 +1,5 @@
 // kernels.hpp -- host-callable launchers of every kernel unit: epoch.hip, cells.hip, kernels.hip, foldin.hip,
-// foldin_pairwise.hip, online.hip, pairwise.hip, rehyper.hip, recommend.hip, rank.hip, seen.hip, sample.hip, hardneg.hip, warp.hip, similar.hip, validate.hip
+// foldin_pairwise.hip, online.hip, pairwise.hip, rehyper.hip, recommend.hip, rank.hip, seen.hip, sample.hip, pick.hip, similar.hip, validate.hip
 // and grow.hip.
 #pragma once
 
@@ -243,7 +243,7 @@ hipError_t sample_weighted_draws(const long long* off, const int32_t* items, con
                                  const unsigned long long* C, const int32_t* users, int64_t n_draws, int32_t m, int32_t n_items,
                                  int64_t seed, uint64_t first, int32_t* out, long long* row_mass, hipStream_t st);
 
-// hardneg.hip.  Hard negatives (include/mfsgd.h, mfsgd_sample_unseen_hard): for each of the n rows of `users` (every one a
+// pick.hip.  Hard negatives (include/mfsgd.h, mfsgd_sample_unseen_hard): for each of the n rows of `users` (every one a
 // user of the index {off, items} and a row of P; off == nullptr: an index without pairs) the best-scoring of the m >= 1
 // candidates sample_unseen_draws gives that row for the same (m, n_items, seed, first), the score being dot(P[user],
 // Q[candidate]) (kp-padded rows; the bits launch_predict returns) and the pick the header's rule: out_items[x] the item,
@@ -253,7 +253,7 @@ hipError_t launch_hard_negatives(int L, const float* P, const float* Q, const lo
                                  const int32_t* users, int64_t n, int32_t m, int32_t n_items, int64_t seed, uint64_t first,
                                  int32_t* out_items, float* out_scores, int32_t* out_draw, hipStream_t st);
 
-// warp.hip.  The negative of a WARP step (include/mfsgd.h, mfsgd_sample_unseen_violating): rows, index, candidates and
+// pick.hip.  The negative of a WARP step (include/mfsgd.h, mfsgd_sample_unseen_violating): rows, index, candidates and
 // dots as for launch_hard_negatives, pos[x] (a row of Q) the row's positive.  Of the row's m >= 1 candidates the first in
 // d with candidate != pos[x] and dot(P[user], Q[pos]) - dot(P[user], Q[candidate]) < margin: out_items[x] the item,
 // out_draw[x] its d, out_margin[x] that difference and out_rank[x] = max(1, unseen items / (d + 1)) (the last three

@@ -27,18 +27,9 @@ __global__ void __launch_bounds__(kSampleThreads) sample_unseen_kernel(const lon
                                                                        int32_t* __restrict__ out) {
     const long long x = (long long)blockIdx.x * kSampleThreads + threadIdx.x;
     if (x >= n_draws) return;
-    long long from = 0, s = 0;
-    if (off) {
-        const int u = users[x / m];
-        from = off[u];
-        s = off[u + 1] - from;
-    }
-    const long long cnt = (long long)n_items - s;
+    const Unseen set(off, items, [&] { return users[x / m]; }, n_items);
     int32_t item = -1;  // the user has seen everything
-    if (cnt > 0) {
-        const unsigned long long r = draw_mix32(seed, first + (unsigned long long)x);
-        item = draw_unseen_at(items + from, s, (long long)((r * (unsigned long long)cnt) >> 32));
-    }
+    if (set.cnt > 0) item = draw_uniform(set, seed, first + (unsigned long long)x);
     out[x] = item;
 }
 
@@ -51,19 +42,9 @@ __global__ void __launch_bounds__(kSampleThreads) sample_weighted_kernel(
     long long* __restrict__ row_mass) {
     const long long x = (long long)blockIdx.x * kSampleThreads + threadIdx.x;
     if (x >= n_draws) return;
-    long long from = 0, s = 0;
-    if (off) {
-        const int u = users[x / m];
-        from = off[u];
-        s = off[u + 1] - from;
-    }
-    const unsigned long long cnt = draw_unseen_mass(items + from, mass + from, s, C, n_items);
-    int32_t item = -1;  // everything of positive weight is seen
-    if (cnt > 0) {
-        const unsigned long long t = __umul64hi(draw_mix64(seed, first + (unsigned long long)x), cnt);
-        item = draw_weighted_at(items + from, mass + from, s, C, n_items, cnt, t);
-    }
-    out[x] = item;
+    const Unseen set(off, items, [&] { return users[x / m]; }, n_items);
+    unsigned long long cnt;
+    out[x] = draw_weighted(set, mass, C, n_items, seed, first + (unsigned long long)x, cnt);
     if (row_mass && x % m == 0) row_mass[x / m] = (long long)cnt;
 }
 

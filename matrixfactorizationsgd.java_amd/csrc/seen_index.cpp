@@ -1,7 +1,8 @@
 // seen_index.cpp -- the seen-item index of a handle, behind the entry points of handle.cpp: mfsgd_set_seen builds it from
 // (user, item) pairs, mfsgd_mark_seen merges a batch into it without sorting it again, mfsgd_get_seen reads lists back,
-// and the growth calls extend its per-user tables here.  The index itself is described in handle.hpp (Seen), its device code
-// is seen.hip, and the serving calls that read it are serve.cpp's (_unseen).
+// and the growth calls extend its per-user tables here; so are the item weights (mfsgd_set_item_weights and its kin).  The
+// index itself is described in handle.hpp (Seen), its device code is seen.hip, and the calls that read it are serve.cpp's
+// (_unseen) and sampling.cpp's (mfsgd_sample_unseen and its kin).
 #include <algorithm>
 #include <cstring>
 
@@ -207,40 +208,6 @@ int seen_get(mfsgd_handle* h, const int32_t* users, int32_t n_users, int64_t* ro
     return MFSGD_OK;
 }
 
-// Body of mfsgd_sample_unseen (handle.cpp): row x of out_items receives m draws among the items users[x] has not seen.
-// The rows go up and the draws come down in pieces of whole rows, at most kSampleChunk draws each (a row with more is a
-// piece of its own); draw d of row x has the counter first + x * m + d wherever the pieces are cut.
-int seen_sample(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first, int32_t* out_items) {
-    if (n < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen: n is negative");
-    if (m < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen: m is negative");
-    if (first < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen: first is negative");
-    if ((m > 0 && n > INT64_MAX / m) || first > INT64_MAX - n * m)
-        return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen: first + n * m exceeds 2^63 - 1");
-    const int64_t total = n * m;
-    if (total > 0 && (!users || !out_items)) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen: users or out_items is null");
-    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "sample_unseen: single-partition handles only");
-    if (!h->seen.present) return fail(h, MFSGD_ERR_STATE, "sample_unseen: no seen set");
-    if (total == 0) return MFSGD_OK;
-    const int64_t x_bad = first_outside(users, n, h->cfg.n_users);
-    if (x_bad >= 0) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen: user " + std::to_string(x_bad) + " out of range");
-    int rc = ensure_device(h);
-    if (rc) return rc;
-    auto bad = [h](hipError_t e) { return serve_fail(h, "sample_unseen: ", e); };
-    const Seen& s = h->seen;
-    const int64_t rows = std::min(n, std::max<int64_t>(1, kSampleChunk / m));
-    DevArray<int32_t> d_users, d_out;
-    if ((rc = dev_alloc(h, d_users, (size_t)rows)) || (rc = dev_alloc(h, d_out, (size_t)(rows * m)))) return rc;
-    for (int64_t x0 = 0; x0 < n; x0 += rows) {
-        const int64_t c = std::min(rows, n - x0), draws = c * m;
-        HIPCHK_OR(bad, copy_up(d_users, users + x0, (size_t)c, h->stream));
-        HIPCHK_OR(bad, sample_unseen_draws(s.n > 0 ? s.off.data() : nullptr, s.items.data(), d_users.data(), draws, m, h->cfg.n_items,
-                                           seed, (uint64_t)first + (uint64_t)(x0 * m), d_out.data(), h->stream));
-        HIPCHK_OR(bad, copy_down(out_items + x0 * m, d_out, (size_t)draws, h->stream));
-        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // (pageable memory: the staging is free for the next piece)
-    }
-    return MFSGD_OK;
-}
-
 // Body of mfsgd_set_item_weights (handle.cpp).  The prefix is summed on the host (8 (n + 1) bytes, once per call) and goes
 // up whole; with an index that has pairs the unseen-mass table follows.  Both are complete before either takes the place
 // of what the handle has.
@@ -318,143 +285,6 @@ int seen_item_histogram(mfsgd_handle* h, int64_t* counts) {
     HIPCHK_OR(bad, seen_item_counts(s.items.data(), s.n, reinterpret_cast<unsigned long long*>(d_counts.data()), h->stream));
     HIPCHK_OR(bad, copy_down(counts, d_counts, n_items, h->stream));
     HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
-    return MFSGD_OK;
-}
-
-// Body of mfsgd_sample_unseen_weighted (handle.cpp): seen_sample with the weighted draw -- the same pieces, the same
-// counters, and a row's unseen weight beside its draws when asked.
-int seen_sample_weighted(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first,
-                         int32_t* out_items, int64_t* out_mass) {
-    const std::string call = "sample_unseen_weighted: ";
-    if (n < 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "n is negative");
-    if (m < 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "m is negative");
-    if (first < 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "first is negative");
-    if ((m > 0 && n > INT64_MAX / m) || first > INT64_MAX - n * m)
-        return fail(h, MFSGD_ERR_INVALID_ARG, call + "first + n * m exceeds 2^63 - 1");
-    const int64_t total = n * m;
-    if (total > 0 && (!users || !out_items)) return fail(h, MFSGD_ERR_INVALID_ARG, call + "users or out_items is null");
-    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, call + "single-partition handles only");
-    if (!h->seen.present) return fail(h, MFSGD_ERR_STATE, call + "no seen set");
-    const ItemWeights& iw = h->weights;
-    if (!iw.present) return fail(h, MFSGD_ERR_STATE, call + "no item weights");
-    if (iw.n != h->cfg.n_items)
-        return fail(h, MFSGD_ERR_STATE,
-                    call + "item weights cover " + std::to_string(iw.n) + " items, the model has " + std::to_string(h->cfg.n_items));
-    if (total == 0) return MFSGD_OK;
-    const int64_t x_bad = first_outside(users, n, h->cfg.n_users);
-    if (x_bad >= 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "user " + std::to_string(x_bad) + " out of range");
-    const Seen& s = h->seen;
-    if (s.n > 0 && !s.mass) return fail(h, MFSGD_ERR_STATE, call + "the index has no unseen-mass table");  // (never: it is eager)
-    int rc = ensure_device(h);
-    if (rc) return rc;
-    auto bad = [h, &call](hipError_t e) { return serve_fail(h, call.c_str(), e); };
-    const int64_t rows = std::min(n, std::max<int64_t>(1, kSampleChunk / m));
-    DevArray<int32_t> d_users, d_out;
-    DevArray<long long> d_mass;
-    if ((rc = dev_alloc(h, d_users, (size_t)rows)) || (rc = dev_alloc(h, d_out, (size_t)(rows * m)))) return rc;
-    if (out_mass && (rc = dev_alloc(h, d_mass, (size_t)rows))) return rc;
-    for (int64_t x0 = 0; x0 < n; x0 += rows) {
-        const int64_t c = std::min(rows, n - x0), draws = c * m;
-        HIPCHK_OR(bad, copy_up(d_users, users + x0, (size_t)c, h->stream));
-        HIPCHK_OR(bad, sample_weighted_draws(s.n > 0 ? s.off.data() : nullptr, s.items.data(), s.mass.data(), iw.C.data(),
-                                             d_users.data(), draws, m, h->cfg.n_items, seed, (uint64_t)first + (uint64_t)(x0 * m),
-                                             d_out.data(), out_mass ? d_mass.data() : nullptr, h->stream));
-        HIPCHK_OR(bad, copy_down(out_items + x0 * m, d_out, (size_t)draws, h->stream));
-        if (out_mass) HIPCHK_OR(bad, copy_down(out_mass + x0, d_mass, (size_t)c, h->stream));
-        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // (pageable memory: the staging is free for the next piece)
-    }
-    return MFSGD_OK;
-}
-
-// Body of mfsgd_sample_unseen_hard (handle.cpp): row x receives the best-scoring of the m draws seen_sample would give it,
-// scored under the factors as they are.  The rows go up and the picks come down in the pieces of seen_sample: whole rows,
-// at most kSampleChunk candidates each (a row with more is a piece of its own); nothing per candidate is ever stored.
-int seen_sample_hard(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first, int32_t* out_items,
-                     float* out_scores, int32_t* out_draw) {
-    if (n < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_hard: n is negative");
-    if (m < 1) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_hard: m is below 1");
-    if (first < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_hard: first is negative");
-    if (n > INT64_MAX / m || first > INT64_MAX - n * m)
-        return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_hard: first + n * m exceeds 2^63 - 1");
-    if (n > 0 && (!users || !out_items)) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_hard: users or out_items is null");
-    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "sample_unseen_hard: single-partition handles only");
-    if (!h->seen.present) return fail(h, MFSGD_ERR_STATE, "sample_unseen_hard: no seen set");
-    int rc = check_reads_factors(h, "sample_unseen_hard");
-    if (rc) return rc;
-    if (n == 0) return MFSGD_OK;
-    const int64_t x_bad = first_outside(users, n, h->cfg.n_users);
-    if (x_bad >= 0) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_hard: user " + std::to_string(x_bad) + " out of range");
-    if ((rc = factors_to_device(h))) return rc;
-    auto bad = [h](hipError_t e) { return serve_fail(h, "sample_unseen_hard: ", e); };
-    const Seen& s = h->seen;
-    const int64_t rows = std::min(n, std::max<int64_t>(1, kSampleChunk / m));
-    DevArray<int32_t> d_users, d_items, d_draw;
-    DevArray<float> d_scores;
-    if ((rc = dev_alloc(h, d_users, (size_t)rows)) || (rc = dev_alloc(h, d_items, (size_t)rows))) return rc;
-    if (out_scores && (rc = dev_alloc(h, d_scores, (size_t)rows))) return rc;
-    if (out_draw && (rc = dev_alloc(h, d_draw, (size_t)rows))) return rc;
-    for (int64_t x0 = 0; x0 < n; x0 += rows) {
-        const int64_t c = std::min(rows, n - x0);
-        HIPCHK_OR(bad, copy_up(d_users, users + x0, (size_t)c, h->stream));
-        HIPCHK_OR(bad, launch_hard_negatives(h->geo.L, h->dP.data(), h->dQ.data(), s.n > 0 ? s.off.data() : nullptr, s.items.data(),
-                                             d_users.data(), c, m, h->cfg.n_items, seed, (uint64_t)first + (uint64_t)(x0 * m),
-                                             d_items.data(), out_scores ? d_scores.data() : nullptr,
-                                             out_draw ? d_draw.data() : nullptr, h->stream));
-        HIPCHK_OR(bad, copy_down(out_items + x0, d_items, (size_t)c, h->stream));
-        if (out_scores) HIPCHK_OR(bad, copy_down(out_scores + x0, d_scores, (size_t)c, h->stream));
-        if (out_draw) HIPCHK_OR(bad, copy_down(out_draw + x0, d_draw, (size_t)c, h->stream));
-        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // (pageable memory: the staging is free for the next piece)
-    }
-    return MFSGD_OK;
-}
-
-// Body of mfsgd_sample_unseen_violating (handle.cpp): row x receives the first of the m draws seen_sample would give it
-// that violates the margin against the row's positive, under the factors as they are.  Users and positives go up and the
-// picks come down in the pieces of seen_sample_hard; nothing per candidate is ever stored.
-int seen_sample_violating(mfsgd_handle* h, const int32_t* users, const int32_t* pos_items, int64_t n, int32_t m, float margin,
-                          int64_t seed, int64_t first, int32_t* out_items, int32_t* out_draw, float* out_margin, int32_t* out_rank) {
-    if (n < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_violating: n is negative");
-    if (m < 1) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_violating: m is below 1");
-    if (margin != margin) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_violating: margin is NaN");
-    if (first < 0) return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_violating: first is negative");
-    if (n > INT64_MAX / m || first > INT64_MAX - n * m)
-        return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_violating: first + n * m exceeds 2^63 - 1");
-    if (n > 0 && (!users || !pos_items || !out_items))
-        return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_violating: users, pos_items or out_items is null");
-    if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, "sample_unseen_violating: single-partition handles only");
-    if (!h->seen.present) return fail(h, MFSGD_ERR_STATE, "sample_unseen_violating: no seen set");
-    int rc = check_reads_factors(h, "sample_unseen_violating");
-    if (rc) return rc;
-    if (n == 0) return MFSGD_OK;
-    const int64_t x_bad = first_outside(users, h->cfg.n_users, pos_items, h->cfg.n_items, n);
-    if (x_bad >= 0)
-        return fail(h, MFSGD_ERR_INVALID_ARG, "sample_unseen_violating: row " + std::to_string(x_bad) + " out of range");
-    if ((rc = factors_to_device(h))) return rc;
-    auto bad = [h](hipError_t e) { return serve_fail(h, "sample_unseen_violating: ", e); };
-    const Seen& s = h->seen;
-    const int64_t rows = std::min(n, std::max<int64_t>(1, kSampleChunk / m));
-    DevArray<int32_t> d_users, d_pos, d_items, d_draw, d_rank;
-    DevArray<float> d_margin;
-    if ((rc = dev_alloc(h, d_users, (size_t)rows)) || (rc = dev_alloc(h, d_pos, (size_t)rows))) return rc;
-    if ((rc = dev_alloc(h, d_items, (size_t)rows))) return rc;
-    if (out_draw && (rc = dev_alloc(h, d_draw, (size_t)rows))) return rc;
-    if (out_margin && (rc = dev_alloc(h, d_margin, (size_t)rows))) return rc;
-    if (out_rank && (rc = dev_alloc(h, d_rank, (size_t)rows))) return rc;
-    for (int64_t x0 = 0; x0 < n; x0 += rows) {
-        const int64_t c = std::min(rows, n - x0);
-        HIPCHK_OR(bad, copy_up(d_users, users + x0, (size_t)c, h->stream));
-        HIPCHK_OR(bad, copy_up(d_pos, pos_items + x0, (size_t)c, h->stream));
-        HIPCHK_OR(bad, launch_first_violating(h->geo.L, h->dP.data(), h->dQ.data(), s.n > 0 ? s.off.data() : nullptr, s.items.data(),
-                                              d_users.data(), d_pos.data(), c, m, margin, h->cfg.n_items, seed,
-                                              (uint64_t)first + (uint64_t)(x0 * m), d_items.data(),
-                                              out_draw ? d_draw.data() : nullptr, out_margin ? d_margin.data() : nullptr,
-                                              out_rank ? d_rank.data() : nullptr, h->stream));
-        HIPCHK_OR(bad, copy_down(out_items + x0, d_items, (size_t)c, h->stream));
-        if (out_draw) HIPCHK_OR(bad, copy_down(out_draw + x0, d_draw, (size_t)c, h->stream));
-        if (out_margin) HIPCHK_OR(bad, copy_down(out_margin + x0, d_margin, (size_t)c, h->stream));
-        if (out_rank) HIPCHK_OR(bad, copy_down(out_rank + x0, d_rank, (size_t)c, h->stream));
-        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // (pageable memory: the staging is free for the next piece)
-    }
     return MFSGD_OK;
 }
 

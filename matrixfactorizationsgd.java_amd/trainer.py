@@ -173,6 +173,20 @@ def _pairs(a, b, what):
     return aa, bb
 
 
+def _users(users):
+    """The `users` argument of the calls that take one user per row: a 1-d int32 array, or ValueError."""
+    uu = _i32(np.atleast_1d(users))
+    if uu.ndim != 1:
+        raise ValueError("users must be a 1-d array")
+    return uu
+
+
+def _asked(*outputs):
+    """(array, asked for) pairs -> the arrays that were asked for: None, the one, or a tuple of them."""
+    res = tuple(a for a, on in outputs if on)
+    return None if not res else res[0] if len(res) == 1 else res
+
+
 def _exclusions(exclude):
     """The `exclude` argument of the serving calls: (seen, u, i).  None: no pairs; (u, i): those pairs; the string "seen":
     what the handle's seen-item index holds (the _unseen calls of the C-ABI), and then u and i are empty."""
@@ -463,8 +477,15 @@ class MatrixFactorizationSGD:
             self._check(self._lib.mfsgd_apply_triples_weighted(self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32),
                                                                _p(jj, C.c_int32), _p(ww, C.c_float), uu.size,
                                                                None if x is None else _p(x, C.c_float), C.byref(out)))
-        res = tuple(a for a, on in ((x, margins), (out.as_dict(), info)) if on)
-        return None if not res else res[0] if len(res) == 1 else res
+        return _asked((x, margins), (out.as_dict(), info))
+
+    def _index_and_factors(self, uu, ii):
+        """What fit_implicit, fit_bpr and fit_warp start from: a handle without a seen-item index gets set_seen(uu, ii),
+        and factors that were never initialised are seeded."""
+        if self.seen_size() < 0:
+            self.set_seen(uu, ii)
+        if not self._initialised:
+            self.init_factors()
 
     def fit_bpr(self, u, i, epochs, *, seed=0, first_epoch=0, stats=True, candidates=1, refresh=None, sampling="uniform"):
         """Trains on one-class data with Bayesian personalised ranking: (u[x], i[x]) are the positives, duplicates
@@ -501,10 +522,7 @@ class MatrixFactorizationSGD:
         if weighted and m > 1:
             raise ValueError('sampling="weighted" needs candidates=1')
         draw_into = self._sample_weighted_into if weighted else self._sample_unseen_into
-        if self.seen_size() < 0:
-            self.set_seen(uu, ii)
-        if not self._initialised:
-            self.init_factors()
+        self._index_and_factors(uu, ii)
         loss, auc = np.zeros(epochs, np.float64), np.zeros(epochs, np.float64)
         if m > 1:
             step = max(n, 1) if refresh is None else int(refresh)
@@ -559,10 +577,7 @@ class MatrixFactorizationSGD:
             raise ValueError("candidates and refresh must be at least 1")
         if np.isnan(margin):
             raise ValueError("margin must not be NaN")
-        if self.seen_size() < 0:
-            self.set_seen(uu, ii)
-        if not self._initialised:
-            self.init_factors()
+        self._index_and_factors(uu, ii)
         violating, trials = np.zeros(epochs, np.float64), np.zeros(epochs, np.float64)
         step = max(n, 1) if refresh is None else int(refresh)
         for e in range(epochs):
@@ -661,9 +676,7 @@ class MatrixFactorizationSGD:
     def seen(self, users):
         """(row_ptr int64[len(users) + 1], items int32[row_ptr[-1]]): the seen items of the requested users, ascending
         within a user, CSR over `users` as given (mfsgd_get_seen: gathered on the device)."""
-        uu = _i32(np.atleast_1d(users))
-        if uu.ndim != 1:
-            raise ValueError("users must be a 1-d array")
+        uu = _users(users)
         ptr = np.zeros(uu.size + 1, np.int64)
         self._check(self._lib.mfsgd_get_seen(self._handle(), _p(uu, C.c_int32), uu.size, _p(ptr, C.c_int64), None, 0))
         items = np.empty(int(ptr[-1]), np.int32)
@@ -679,9 +692,7 @@ class MatrixFactorizationSGD:
         -1 throughout a row whose user has seen every item.  Draw d of row x is a pure function of seed, the counter
         first + x * m + d, the user's list and the item count: rows [a:b] of a call are the call on users[a:b] with
         first + a * m."""
-        uu = _i32(np.atleast_1d(users))
-        if uu.ndim != 1:
-            raise ValueError("users must be a 1-d array")
+        uu = _users(users)
         out = np.empty((uu.size, max(int(m), 0)), np.int32)
         self._sample_unseen_into(uu, m, seed, first, out)
         return out
@@ -734,9 +745,7 @@ class MatrixFactorizationSGD:
         integers only, no rejection): int32 [len(users), m], -1 throughout a row whose user has seen every item of
         positive weight.  Draw d of row x is a pure function of seed, the counter first + x * m + d, the user's list, the
         weights and the item count.  mass=True adds int64 [len(users)], each row's unseen weight (written where m > 0)."""
-        uu = _i32(np.atleast_1d(users))
-        if uu.ndim != 1:
-            raise ValueError("users must be a 1-d array")
+        uu = _users(users)
         out = np.empty((uu.size, max(int(m), 0)), np.int32)
         ms = np.zeros(uu.size, np.int64) if mass else None
         self._sample_weighted_into(uu, m, seed, first, out, ms)
@@ -761,17 +770,14 @@ class MatrixFactorizationSGD:
         every number; -1 for a user who has seen every item.  scores=True adds float32 [len(users)], each pick's score
         (NaN with -1); draws=True adds int32 [len(users)], each pick's position d in its row of draws (-1 with -1); with
         either the result is a tuple (items, scores, draws) without what was not asked for."""
-        uu = _i32(np.atleast_1d(users))
-        if uu.ndim != 1:
-            raise ValueError("users must be a 1-d array")
+        uu = _users(users)
         items = np.empty(uu.size, np.int32)
         sc = np.empty(uu.size, np.float32) if scores else None
         dr = np.empty(uu.size, np.int32) if draws else None
         self._check(self._lib.mfsgd_sample_unseen_hard(self._handle(), _p(uu, C.c_int32), uu.size, int(m), int(seed), int(first),
                                                        _p(items, C.c_int32), None if sc is None else _p(sc, C.c_float),
                                                        None if dr is None else _p(dr, C.c_int32)))
-        res = tuple(a for a, on in ((items, True), (sc, scores), (dr, draws)) if on)
-        return res[0] if len(res) == 1 else res
+        return _asked((items, True), (sc, scores), (dr, draws))
 
     def sample_unseen_violating(self, users, items, m, margin=1.0, seed=0, first=0, *, draws=False, margins=False, ranks=False):
         """int32 [len(users)]: for each row, the first of the m items sample_unseen(users, m, seed, first) draws for it
@@ -793,8 +799,7 @@ class MatrixFactorizationSGD:
                                                             None if dr is None else _p(dr, C.c_int32),
                                                             None if mg is None else _p(mg, C.c_float),
                                                             None if rk is None else _p(rk, C.c_int32)))
-        res = tuple(a for a, on in ((out, True), (dr, draws), (mg, margins), (rk, ranks)) if on)
-        return res[0] if len(res) == 1 else res
+        return _asked((out, True), (dr, draws), (mg, margins), (rk, ranks))
 
     def fit_implicit(self, u, i, epochs, negatives=4, *, seed=0, pos=1.0, neg=0.0, first_epoch=0, rmse=True, sampling="uniform"):
         """Trains on one-class data (clicks, plays, purchases): (u[x], i[x]) are the positives, duplicates allowed, and
@@ -816,10 +821,7 @@ class MatrixFactorizationSGD:
         if epochs < 0 or negatives < 0:
             raise ValueError("epochs and negatives must not be negative")
         draw_into = self._sample_weighted_into if self._sampling(sampling) else self._sample_unseen_into
-        if self.seen_size() < 0:
-            self.set_seen(uu, ii)
-        if not self._initialised:
-            self.init_factors()
+        self._index_and_factors(uu, ii)
         rr = np.full(n, pos, np.float32)
         if negatives == 0:
             self.set_ratings(uu, ii, rr)
@@ -913,8 +915,7 @@ class MatrixFactorizationSGD:
                                                            int(draw_seed), int(first), _p(rows, C.c_float),
                                                            None if mg is None else _p(mg, C.c_float),
                                                            None if ng is None else _p(ng, C.c_int32)))
-        res = tuple(a for a, on in ((rows, True), (mg, margins), (ng, negatives)) if on)
-        return res[0] if len(res) == 1 else res
+        return _asked((rows, True), (mg, margins), (ng, negatives))
 
     # -- growing a live model (include/mfsgd.h, "growing a live model") -------------
     def _dims(self):

@@ -3,19 +3,14 @@ of mfsgd_fold_in_users_pairwise (include/mfsgd.h) restated.  The draws are tests
 tests/hardneg_common.pick, and the arithmetic of a step is a small C restatement written from the header's text -- the
 canonical dot is the oracle's mfo_dot, lsig is the text tests/pairwise_common.py compiles -- built the way that module
 builds its own: the host compiler at -O2 -ffp-contract=off, linked to the oracle."""
-import atexit
 import ctypes as C
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
 from tests import hardneg_common as HC
 from tests import implicit_common as IC
 from tests import pairwise_common as PC
-from tests.conftest import ROOT
+from tests.restatement import build
 
 NAN_BITS = HC.NAN_BITS  # the margin of a step that was not taken
 
@@ -62,37 +57,14 @@ void fp_chain(float* row, const float* Q, int32_t k, const int32_t* pos, const i
 
 _f = C.POINTER(C.c_float)
 _i = C.POINTER(C.c_int32)
-_lib = None
 
 
 def restatement():
-    """The compiled restatement (built once per process, in a directory of its own that goes when the process does)."""
-    global _lib
-    if _lib is None:
-        from tests.oracle_bind import Oracle
-
-        Oracle()  # builds oracle/libmfsgd_oracle.so when it is not there
-        cc = shutil.which("gcc") or shutil.which("cc")
-        assert cc, "no C compiler"
-        tmp = tempfile.mkdtemp(prefix="mfsgd_fold_in_pairwise_")
-        atexit.register(shutil.rmtree, tmp, ignore_errors=True)
-        src, so = os.path.join(tmp, "fold_in_pairwise_restatement.c"), os.path.join(tmp, "libfold_in_pairwise_restatement.so")
-        with open(src, "w") as f:
-            f.write(C_SOURCE)
-        oracle_dir = os.path.join(ROOT, "oracle")
-        p = subprocess.run([cc, "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-Wall", "-Wextra", "-o", so, src,
-                            "-L" + oracle_dir, "-Wl,-rpath," + oracle_dir, "-l:libmfsgd_oracle.so", "-lm"],
-                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert p.returncode == 0, p.stdout
-        lib = C.CDLL(so)
-        lib.fp_scores.argtypes = [_f, _f, C.c_int32, _i, C.c_int32, _f]
-        lib.fp_scores.restype = None
-        lib.fp_step.argtypes = [_f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float]
-        lib.fp_step.restype = C.c_float
-        lib.fp_chain.argtypes = [_f, _f, C.c_int32, _i, _i, C.c_int64, C.c_float, C.c_float, _f]
-        lib.fp_chain.restype = None
-        _lib = lib
-    return _lib
+    """The compiled restatement (tests/restatement.py builds it, once per process)."""
+    return build("fold_in_pairwise", C_SOURCE, {
+        "fp_scores": (None, [_f, _f, C.c_int32, _i, C.c_int32, _f]),
+        "fp_step": (C.c_float, [_f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float]),
+        "fp_chain": (None, [_f, _f, C.c_int32, _i, _i, C.c_int64, C.c_float, C.c_float, _f])})
 
 
 def chain(row, Q, pos, neg, lr, lam):

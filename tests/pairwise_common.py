@@ -2,17 +2,12 @@
 levels restated in Python, the batches that reach each shape of a level list, and a small C restatement of the arithmetic
 of DESIGN.md section 3 ("Pairwise ranking") -- lsig and the sequential triple loop over dense rows -- written from that
 text, compiled here with the host compiler at -O2 -ffp-contract=off and linked to the oracle for its canonical dot."""
-import atexit
 import ctypes as C
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
 from tests import online_common as oc
-from tests.conftest import ROOT
+from tests.restatement import build
 
 PIECE = oc.PIECE  # triples per piece (include/mfsgd.h, "pairwise ranking")
 
@@ -164,35 +159,12 @@ void pw_pass(float* P, float* Q, int32_t k, const int32_t* u, const int32_t* i, 
 
 _f = C.POINTER(C.c_float)
 _i = C.POINTER(C.c_int32)
-_lib = None
 
 
 def restatement():
-    """The compiled restatement (built once per process, in a directory of its own that goes when the process does)."""
-    global _lib
-    if _lib is None:
-        from tests.oracle_bind import Oracle
-
-        Oracle()  # builds oracle/libmfsgd_oracle.so when it is not there
-        cc = shutil.which("gcc") or shutil.which("cc")
-        assert cc, "no C compiler"
-        tmp = tempfile.mkdtemp(prefix="mfsgd_pairwise_")
-        atexit.register(shutil.rmtree, tmp, ignore_errors=True)
-        src, so = os.path.join(tmp, "pairwise_restatement.c"), os.path.join(tmp, "libpairwise_restatement.so")
-        with open(src, "w") as f:
-            f.write(C_SOURCE)
-        oracle_dir = os.path.join(ROOT, "oracle")
-        p = subprocess.run([cc, "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-Wall", "-Wextra", "-o", so, src,
-                            "-L" + oracle_dir, "-Wl,-rpath," + oracle_dir, "-l:libmfsgd_oracle.so", "-lm"],
-                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert p.returncode == 0, p.stdout
-        lib = C.CDLL(so)
-        lib.pw_lsig.argtypes = [_f, _f, C.c_int64]
-        lib.pw_lsig.restype = None
-        lib.pw_pass.argtypes = [_f, _f, C.c_int32, _i, _i, _i, C.c_int64, C.c_float, C.c_float, _f]
-        lib.pw_pass.restype = None
-        _lib = lib
-    return _lib
+    """The compiled restatement (tests/restatement.py builds it, once per process)."""
+    return build("pairwise", C_SOURCE, {"pw_lsig": (None, [_f, _f, C.c_int64]),
+                                          "pw_pass": (None, [_f, _f, C.c_int32, _i, _i, _i, C.c_int64, C.c_float, C.c_float, _f])})
 
 
 def c_lsig(x):

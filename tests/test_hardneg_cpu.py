@@ -141,6 +141,7 @@ def test_the_checks_come_in_the_stated_order(mf, bare):
     assert _hard(m, None, 2, 0, first=-1)[1] == PRE + "m is below 1"
     assert _hard(m, None, 2, 3, first=-1)[1] == PRE + "first is negative"
     assert _hard(m, None, 2, 3, first=I64_MAX)[1] == PRE + "first + n * m exceeds 2^63 - 1"
+    assert _hard(m, None, 1 << 62, 4, first=-1)[1] == PRE + "first is negative"  # (before the overflow)
     assert _hard(m, None, 2, 3)[:2] == (INVALID_ARG, PRE + "users or out_items is null")
     assert _hard(m, None, 0, 3)[:2] == (STATE, PRE + "no seen set")  # (n == 0: null arrays are fine)
     # 5. the state, whatever n is and before the users: the index, then the factors
@@ -167,6 +168,8 @@ def test_the_checks_come_in_the_stated_order(mf, bare):
         for n in (2, 0):
             assert _hard(p, [0, U], n, 3)[:2] == (STATE, PRE + "single-partition handles only")
         assert _hard(p, None, 2, 3)[:2] == (INVALID_ARG, PRE + "users or out_items is null")
+        assert _hard(p, None, 2, 0)[1] == PRE + "m is below 1"
+        assert _hard(p, [0, U], 2, 3, first=I64_MAX)[1] == PRE + "first + n * m exceeds 2^63 - 1"
     out = np.zeros(1, np.int32)
     assert mf.load_library().mfsgd_sample_unseen_hard(None, _i32(out), 1, 1, 0, 0, _i32(out), None, None) == INVALID_ARG
 

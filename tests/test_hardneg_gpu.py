@@ -1,4 +1,4 @@
-"""Hard negatives on the device (csrc/hardneg.hip, mfsgd_sample_unseen_hard): items, scores and draws against the numpy
+"""Hard negatives on the device (csrc/pick.hip, mfsgd_sample_unseen_hard): items, scores and draws against the numpy
 restatement of the pick (tests/hardneg_common.py), byte for byte, for every lane-group size and the candidate counts around
 it; the shapes of the seen-item index; ties, NaN and infinite scores; the pieces a call is staged in; that a live handle
 stays whole; fit_bpr(candidates=m) against the sequence of calls it is documented as; and the planted one-class problem."""

@@ -102,10 +102,15 @@ def test_the_checks_come_in_the_stated_order(mf, bare):
     assert _sample(m, None, 2, -1, first=-1)[1] == "sample_unseen: m is negative"
     assert _sample(m, None, 2, 3, first=-1)[1] == "sample_unseen: first is negative"
     assert _sample(m, None, 2, 3, first=I64_MAX)[1] == "sample_unseen: first + n * m exceeds 2^63 - 1"
+    assert _sample(m, None, 1 << 62, 4, first=-1)[1] == "sample_unseen: first is negative"  # (before the overflow)
     assert _sample(m, None, 2, 3)[:2] == (INVALID_ARG, "sample_unseen: users or out_items is null")
     # 3. then the missing index, before the users
     assert _sample(m, [0, U], 2, 3)[:2] == (STATE, "sample_unseen: no seen set")
+    for n, per_row in ((0, 3), (2, 0)):  # ... and whatever n * m is, where null arrays are fine
+        assert _sample(m, [0, U], n, per_row)[:2] == (STATE, "sample_unseen: no seen set")
+        assert _sample(m, None, n, per_row, out=False)[:2] == (STATE, "sample_unseen: no seen set")
     m.set_seen([], [])
+    assert _sample(m, [0, U], 0, 3)[0] == OK  # nothing to do comes before the users
     # 4. then the users, named by row
     for users, row in (([0, U], 1), ([-1, 0], 0), ([0, 1, 2, 1 << 30], 3)):
         rc, msg, out = _sample(m, users, len(users), 3)
@@ -125,6 +130,8 @@ def test_the_checks_come_in_the_stated_order(mf, bare):
     with mf.MatrixFactorizationSGD(U, I, K, 0.01, 0.05, 1, n_parts=2) as p:
         assert _sample(p, [0, U], 2, 3)[:2] == (STATE, "sample_unseen: single-partition handles only")
         assert _sample(p, None, 2, 3)[:2] == (INVALID_ARG, "sample_unseen: users or out_items is null")
+        assert _sample(p, [0, U], 0, 3)[:2] == (STATE, "sample_unseen: single-partition handles only")
+        assert _sample(p, [0, U], 2, 3, first=I64_MAX)[1] == "sample_unseen: first + n * m exceeds 2^63 - 1"
     assert mf.load_library().mfsgd_sample_unseen(None, _i32(users), 1, 1, 0, 0, _i32(out)) == INVALID_ARG
 
 

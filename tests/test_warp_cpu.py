@@ -213,6 +213,7 @@ def test_the_checks_come_in_the_stated_order(mf, bare):
     assert _viol(m, None, None, 2, 3, margin=nan, first=-1)[1] == PRE + "margin is NaN"
     assert _viol(m, None, None, 2, 3, first=-1)[1] == PRE + "first is negative"
     assert _viol(m, None, None, 2, 3, first=I64_MAX)[1] == PRE + "first + n * m exceeds 2^63 - 1"
+    assert _viol(m, None, None, 1 << 62, 4, first=-1)[1] == PRE + "first is negative"  # (before the overflow)
     assert _viol(m, None, None, 2, 3)[:2] == (INVALID_ARG, PRE + "users, pos_items or out_items is null")
     assert _viol(m, None, None, 0, 3)[:2] == (STATE, PRE + "no seen set")  # (n == 0: null arrays are fine)
     # 2. the state, whatever n is and before the rows: the index, then the factors
@@ -240,6 +241,8 @@ def test_the_checks_come_in_the_stated_order(mf, bare):
         for n in (2, 0):
             assert _viol(p, [0, U], [0, I], n, 3)[:2] == (STATE, PRE + "single-partition handles only")
         assert _viol(p, None, None, 2, 3)[:2] == (INVALID_ARG, PRE + "users, pos_items or out_items is null")
+        assert _viol(p, None, None, 2, 3, margin=nan)[1] == PRE + "margin is NaN"
+        assert _viol(p, [0, U], [0, I], 2, 3, first=I64_MAX)[1] == PRE + "first + n * m exceeds 2^63 - 1"
     out = np.zeros(1, np.int32)
     assert mf.load_library().mfsgd_sample_unseen_violating(None, _i32(out), _i32(out), 1, 1, 1.0, 0, 0, _i32(out), None, None,
                                                            None) == INVALID_ARG

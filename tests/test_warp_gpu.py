@@ -1,4 +1,4 @@
-"""WARP on the device: mfsgd_sample_unseen_violating (csrc/warp.hip) against the numpy restatement of its rule
+"""WARP on the device: mfsgd_sample_unseen_violating (csrc/pick.hip) against the numpy restatement of its rule
 (tests/warp_common.py) -- items, draws, margins and ranks, byte for byte -- for the lane-group sizes, the candidate counts
 around a round and the margins that are special; the shapes of the seen-item index; that a call may be cut and leaves a
 live handle whole; mfsgd_apply_triples_weighted against the sequential loop restated in C; and fit_warp against the loop it

@@ -221,6 +221,7 @@ def test_the_weighted_draw_checks_in_the_stated_order(mf, bare):
     assert _sample(m, None, 2, -1, first=-1)[1] == call + "m is negative"
     assert _sample(m, None, 2, 3, first=-1)[1] == call + "first is negative"
     assert _sample(m, None, 2, 3, first=I64_MAX)[1] == call + "first + n * m exceeds 2^63 - 1"
+    assert _sample(m, None, 1 << 62, 4, first=-1)[1] == call + "first is negative"  # (before the overflow)
     assert _sample(m, None, 2, 3)[:2] == (INVALID_ARG, call + "users or out_items is null")
     # 2. no index, then no weights: both before the users, and whatever n * m is
     assert _sample(m, [0, U], 2, 3)[:2] == (STATE, call + "no seen set")
@@ -239,6 +240,8 @@ def test_the_weighted_draw_checks_in_the_stated_order(mf, bare):
     with mf.MatrixFactorizationSGD(U, I, K, 0.01, 0.05, 1, n_parts=2) as p:
         assert _sample(p, [0, U], 2, 3)[:2] == (STATE, call + "single-partition handles only")
         assert _sample(p, None, 2, 3)[:2] == (INVALID_ARG, call + "users or out_items is null")
+        assert _sample(p, [0, U], 0, 3)[:2] == (STATE, call + "single-partition handles only")
+        assert _sample(p, [0, U], 2, 3, first=I64_MAX)[1] == call + "first + n * m exceeds 2^63 - 1"
     out = np.zeros(4, np.int32)
     assert mf.load_library().mfsgd_sample_unseen_weighted(None, _ptr(out, C.c_int32), 1, 1, 0, 0, _ptr(out, C.c_int32), None) == INVALID_ARG
     if not have_gpu():
@@ -249,6 +252,7 @@ def test_the_weighted_draw_checks_in_the_stated_order(mf, bare):
         rc, msg, out, ms = _sample(m, [0, 1], n, per_row, mass=True)
         assert rc == OK and (out == UNTOUCHED).all() and (ms == UNTOUCHED).all(), msg
         assert _sample(m, None, n, per_row, out=False)[0] == OK
+        assert _sample(m, [0, U], n, per_row)[0] == OK  # nothing to do comes before the users
     for users, row in (([0, U], 1), ([-1, 0], 0), ([0, 1, 2, 1 << 30], 3)):
         rc, msg, out, ms = _sample(m, users, len(users), 3, mass=True)
         assert (rc, msg) == (INVALID_ARG, call + f"user {row} out of range")

@@ -3,17 +3,12 @@ mfsgd_sample_unseen_violating in numpy, on top of tests/implicit_common.sample f
 passed in; the harmonic weight of mfsgd_warp_weights; the sequential loop of mfsgd_apply_triples_weighted in C over the
 oracle's canonical dot (compiled as tests/pairwise_common.py compiles its own); and fit_warp as the loop it is documented
 as.  Everything the device is compared with is compared byte for byte."""
-import atexit
 import ctypes as C
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
 from tests import implicit_common as IC
-from tests.conftest import ROOT
+from tests.restatement import build
 
 NAN_BITS = 0x7FC00000  # the margin of a row without a pick
 
@@ -108,33 +103,11 @@ void ww_pass(float* P, float* Q, int32_t k, const int32_t* u, const int32_t* i, 
 
 _f = C.POINTER(C.c_float)
 _i = C.POINTER(C.c_int32)
-_lib = None
 
 
 def restatement():
-    """The compiled restatement (built once per process, in a directory of its own that goes when the process does)."""
-    global _lib
-    if _lib is None:
-        from tests.oracle_bind import Oracle
-
-        Oracle()  # builds oracle/libmfsgd_oracle.so when it is not there
-        cc = shutil.which("gcc") or shutil.which("cc")
-        assert cc, "no C compiler"
-        tmp = tempfile.mkdtemp(prefix="mfsgd_warp_")
-        atexit.register(shutil.rmtree, tmp, ignore_errors=True)
-        src, so = os.path.join(tmp, "warp_restatement.c"), os.path.join(tmp, "libwarp_restatement.so")
-        with open(src, "w") as f:
-            f.write(C_SOURCE)
-        oracle_dir = os.path.join(ROOT, "oracle")
-        p = subprocess.run([cc, "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-Wall", "-Wextra", "-o", so, src,
-                            "-L" + oracle_dir, "-Wl,-rpath," + oracle_dir, "-l:libmfsgd_oracle.so", "-lm"],
-                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert p.returncode == 0, p.stdout
-        lib = C.CDLL(so)
-        lib.ww_pass.argtypes = [_f, _f, C.c_int32, _i, _i, _i, _f, C.c_int64, C.c_float, C.c_float, _f]
-        lib.ww_pass.restype = None
-        _lib = lib
-    return _lib
+    """The compiled restatement (tests/restatement.py builds it, once per process)."""
+    return build("warp", C_SOURCE, {"ww_pass": (None, [_f, _f, C.c_int32, _i, _i, _i, _f, C.c_int64, C.c_float, C.c_float, _f])})
 
 
 def canon_weights(w):

@@ -3,8 +3,8 @@
 
     tools/kernel_identity.py PARENT_TREE BRANCH_TREE [-j JOBS]
 
-For each tree, every unit of the Makefile's KERNEL_OBJS is compiled with the Makefile's own flags plus
---cuda-device-only, the gfx950 object is unbundled and disassembled.  The comparison is per kernel symbol and ACROSS
+For each tree, every unit of the Makefile's KERNEL_OBJS and PREP_OBJS is compiled with the flags of the Makefile's rule
+for its list (PREP_OBJS: without -ffp-contract=off) plus --cuda-device-only, the gfx950 object is unbundled and disassembled.  The comparison is per kernel symbol and ACROSS
 files (a kernel may have moved to another unit): the two symbol sets, and for each symbol the sequence of instruction
 encodings and the resources of its kernel descriptor (VGPRs, SGPRs, LDS, scratch).  Needs no GPU.  Exit status 0 iff
 the sets are equal and every kernel is identical; a kernel that differs is shown side by side, instruction by
@@ -72,21 +72,26 @@ def disassemble(csrc, unit, flags, hipcc, work):
 
 def tree_kernels(tree, jobs, work):
     csrc = os.path.join(tree, CSRC)
-    units = [o[:-2] for o in make_var(csrc, "KERNEL_OBJS")]
-    flags = make_var(csrc, "CXXFLAGS") + make_var(csrc, "HIPFLAGS")
+    cxx = make_var(csrc, "CXXFLAGS")
+    # the Makefile's two lists of device units and what its rule for each adds to CXXFLAGS
+    lists = (("KERNEL_OBJS", make_var(csrc, "HIPFLAGS")), ("PREP_OBJS", ["--offload-arch=" + make_var(csrc, "ARCH")[0]]))
+    units = [(o[:-2], cxx + extra) for name, extra in lists for o in make_var(csrc, name)]
     hipcc = make_var(csrc, "HIPCC")[0]
     os.makedirs(work, exist_ok=True)
     with concurrent.futures.ThreadPoolExecutor(jobs) as ex:
-        return list(ex.map(lambda u: disassemble(csrc, u, flags, hipcc, work), units))
+        return list(ex.map(lambda uf: disassemble(csrc, uf[0], uf[1], hipcc, work), units))
 
 
 def merge(units):
     code, res, where = {}, {}, {}
     for unit, k, r in units:
-        for s in k:
+        for sym in k:
+            # a library's kernel template (rocPRIM's) that several units instantiate is compared per unit: each unit
+            # compiles its own copy, under its own flags
+            s = f"{sym} [{unit}.hip]" if "rocprim" in sym else sym
             if s in code:
                 sys.exit(f"kernel {s} is in two units: {where[s]}.hip and {unit}.hip")
-            code[s], res[s], where[s] = k[s], r[s], unit
+            code[s], res[s], where[s] = k[sym], r[sym], unit
     return code, res, where
 
 
