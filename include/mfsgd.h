@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver; + mfsgd_set_validation, mfsgd_validation_size, mfsgd_validation_rmse, mfsgd_rmse_pairs, mfsgd_train_early_stop; + mfsgd_row_inv_norms, mfsgd_similar_items, mfsgd_similar_users, mfsgd_similar_rows; + mfsgd_online_levels, mfsgd_apply_ratings; + mfsgd_fold_in_items, mfsgd_append_users, mfsgd_append_items, mfsgd_reserve_rows, mfsgd_get_capacity; + mfsgd_recommend_among, mfsgd_recommend_rows_among, mfsgd_debug_serve_seconds; + mfsgd_set_seen, mfsgd_mark_seen, mfsgd_clear_seen, mfsgd_seen_size, mfsgd_get_seen, mfsgd_recommend_unseen, mfsgd_recommend_unseen_among, mfsgd_rank_items_unseen, mfsgd_evaluate_ranking_unseen; + mfsgd_sample_unseen; + mfsgd_triple_levels, mfsgd_apply_triples, mfsgd_bpr_weights; + mfsgd_sample_unseen_hard; + mfsgd_sample_unseen_violating, mfsgd_apply_triples_weighted, mfsgd_warp_weights; + mfsgd_fold_in_users_pairwise (additions: no existing call changed) */
+#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver; + mfsgd_set_validation, mfsgd_validation_size, mfsgd_validation_rmse, mfsgd_rmse_pairs, mfsgd_train_early_stop; + mfsgd_row_inv_norms, mfsgd_similar_items, mfsgd_similar_users, mfsgd_similar_rows; + mfsgd_online_levels, mfsgd_apply_ratings; + mfsgd_fold_in_items, mfsgd_append_users, mfsgd_append_items, mfsgd_reserve_rows, mfsgd_get_capacity; + mfsgd_recommend_among, mfsgd_recommend_rows_among, mfsgd_debug_serve_seconds; + mfsgd_set_seen, mfsgd_mark_seen, mfsgd_clear_seen, mfsgd_seen_size, mfsgd_get_seen, mfsgd_recommend_unseen, mfsgd_recommend_unseen_among, mfsgd_rank_items_unseen, mfsgd_evaluate_ranking_unseen; + mfsgd_sample_unseen; + mfsgd_triple_levels, mfsgd_apply_triples, mfsgd_bpr_weights; + mfsgd_sample_unseen_hard; + mfsgd_sample_unseen_violating, mfsgd_apply_triples_weighted, mfsgd_warp_weights; + mfsgd_fold_in_users_pairwise; + mfsgd_sample_unseen_hard_weighted, mfsgd_sample_unseen_violating_weighted, mfsgd_fold_in_users_pairwise_weighted (additions: no existing call changed) */
 
 typedef enum mfsgd_status {
     MFSGD_OK = 0,
@@ -242,11 +242,35 @@ int mfsgd_fold_in_items(mfsgd_handle* h, int32_t n_new, const int64_t* row_ptr, 
  * positives (a user with more is a batch of its own); each batch's lists S are built there, and 4 bytes per step come
  * down for each of out_margin and out_neg that is asked for.  All staging is freed before the call returns, on every
  * path -- mfsgd_debug_device_bytes is the same before and after.  A user's chain is sequential, as in
- * mfsgd_fold_in_users.  Not done here: WARP-style picks, weighted draws, new items, a lambda of its own for negatives. */
+ * mfsgd_fold_in_users.  Not done here: WARP-style picks, new items, a lambda of its own for negatives (weighted draws:
+ * mfsgd_fold_in_users_pairwise_weighted below). */
 int mfsgd_fold_in_users_pairwise(mfsgd_handle* h, int32_t n_new, const int64_t* row_ptr, const int32_t* items,
                                  int32_t epochs, int32_t m, const float* init_rows, int64_t seed, int64_t draw_seed,
                                  int64_t first, float* out_rows, float* out_margin /* nullable, T * epochs */,
                                  int32_t* out_neg /* nullable, T * epochs */);
+/* mfsgd_fold_in_users_pairwise_weighted: mfsgd_fold_in_users_pairwise for a model trained against weighted negatives (item
+ * weights: mfsgd_set_item_weights, further down).  It is that call's rule with one line replaced:
+ *     cand[d] = mfsgd_sample_unseen_weighted's draw for (draw_seed, c_d, S, the handle's weights, n_items): with z its
+ *               64-bit mix, cnt the unseen WEIGHT of S and g the unseen-mass table of S, t = (z * cnt) >> 64 and the
+ *               two searches of that call
+ * The counters c_d, the pick, the step, the outputs and the way a call can be split are unchanged.  "cnt == 0" reads
+ * "the user's unseen weight is 0" -- the list names every item of positive weight, or all weights are zero --: no step
+ * is taken, the start row comes back, the user's margins are 0x7FC00000 and their negatives -1.  An item of weight 0 is
+ * never a negative.  Unit weights do NOT reproduce mfsgd_fold_in_users_pairwise: that call's draw uses the 32-bit r.
+ * Checks, all before any device work, in this order ("fold_in_pairwise_weighted: ..."): the argument checks of
+ * mfsgd_fold_in_users_pairwise; its state checks (n_parts != 1, factors never initialised, set or loaded, no Q); then
+ * MFSGD_ERR_STATE for a handle without weights ("no item weights") and for weights that no longer cover the model ("item
+ * weights cover X items, the model has Y", after mfsgd_append_items).  Then n_new == 0 is MFSGD_OK and touches nothing.  A
+ * valid call with n_new > 0 and no usable GPU is MFSGD_ERR_NO_DEVICE.
+ * The call needs no seen-item index and no stored ratings, and modifies nothing in the handle: not the model, the
+ * weights, the index or its mass table, a schedule or a cached graph.  Per batch, after the lists S are built, their
+ * unseen-mass table is built the way the index's is (the pairs' weights, one device-wide exclusive scan, g): staging of
+ * 16 bytes per distinct positive of the batch plus the scan's scratch, on top of mfsgd_fold_in_users_pairwise's, all of
+ * it freed before the call returns, on every path -- mfsgd_debug_device_bytes is the same before and after.             */
+int mfsgd_fold_in_users_pairwise_weighted(mfsgd_handle* h, int32_t n_new, const int64_t* row_ptr, const int32_t* items,
+                                          int32_t epochs, int32_t m, const float* init_rows, int64_t seed, int64_t draw_seed,
+                                          int64_t first, float* out_rows, float* out_margin /* nullable, T * epochs */,
+                                          int32_t* out_neg /* nullable, T * epochs */);
 /* Top-N as mfsgd_recommend_excluding, where "user j" is rows[j] (n_rows x k, dense: for instance what
  * mfsgd_fold_in_users returned) instead of a row of P: every row is answered, in order, and excl_row[x] indexes rows.
  * Same ordering, padding, scores and argument checks, with n_rows in the place of n_users.                           */
@@ -537,6 +561,48 @@ int mfsgd_sample_unseen_violating(mfsgd_handle* h, const int32_t* users, const i
                                   float margin, int64_t seed, int64_t first, int32_t* out_items /* n */,
                                   int32_t* out_draw /* nullable, n */, float* out_margin /* nullable, n */,
                                   int32_t* out_rank /* nullable, n */);
+/* Weighted picks: mfsgd_sample_unseen_hard_weighted and mfsgd_sample_unseen_violating_weighted are the two calls above
+ * over the candidates of mfsgd_sample_unseen_weighted, for hard negatives and WARP on a long-tailed catalogue, where
+ * nearly every uniform candidate is an obscure item the model ranks low already.  The kernels are the same: the draw is
+ * their only difference.
+ * Candidates, both calls.  The candidates of row x are exactly row x of mfsgd_sample_unseen_weighted(users, n, m, seed,
+ * first): candidate d has the counter first + x * m + d, the 64-bit z, cnt_w = the unseen weight of users[x],
+ * t = (z * cnt_w) >> 64 and the two searches, over the index's mass table g and over C.  Rows [a, b) of a call are the
+ * call on users + a (pos_items + a) with first + a * m.  out_mass[x] (nullable) receives the row's cnt_w, as
+ * mfsgd_sample_unseen_weighted's does; it is written for every row of a call with n > 0.  Unit weights do NOT reproduce
+ * the uniform calls: the uniform draw takes its rank from the 32-bit r, (r * cnt) >> 32, the weighted one from all 64
+ * bits of z.  An item of weight 0 is never a candidate.
+ * mfsgd_sample_unseen_hard_weighted.  mfsgd_sample_unseen_hard's score and pick over those candidates: the largest
+ * non-NaN score, equal scores to the smaller d, d = 0 when all m scores are NaN.  A row with cnt_w == 0 -- the user has
+ * seen everything of positive weight, or all weights are zero -- gives item -1, score 0x7FC00000 and draw -1.  With m = 1
+ * the items are mfsgd_sample_unseen_weighted's column and the scores mfsgd_predict's.
+ * mfsgd_sample_unseen_violating_weighted.  mfsgd_sample_unseen_violating's rule over those candidates, cand[d] != i, the
+ * NaN margins that never violate and the margins of +-Inf included:
+ *     out     = item cand[pick], draw pick, margin x[pick], rank max(1, N / (pick + 1))   with N = n_items - s
+ *     no d violates:  item -1, draw m,  margin 0x7FC00000, rank 0
+ *     cnt_w == 0:     item -1, draw -1, margin 0x7FC00000, rank 0       (N may be above 0: unseen items that weigh nothing)
+ * N is the unseen item COUNT, the N of the uniform call, not cnt_w.  Under a weighted proposal the number of draws
+ * estimates the violators' share of the unseen WEIGHT -- a violator at draw d + 1 says about one part in d + 1 of it --
+ * and N scales that share to a number of items; it is the uniform call's estimate where popular and obscure items
+ * violate alike, and counts a popular violator for more than one item otherwise.  mfsgd_warp_weights takes the result
+ * unchanged.
+ * Checks, all before any device work, in this order, the messages starting with the new call's name: the argument checks
+ * of the uniform call (n, m, the margin, first, the null arrays); then MFSGD_ERR_STATE, whatever n is, for n_parts != 1,
+ * for a handle without an index ("no seen set"), for one without weights ("no item weights"), for weights that no longer
+ * cover the model ("item weights cover X items, the model has Y"), and for the factor state of the uniform call.  Then
+ * n == 0 is MFSGD_OK and touches nothing.  Then MFSGD_ERR_INVALID_ARG for a user (or positive) out of range, named by its
+ * row, the outputs untouched.  A valid call with n > 0 and no usable GPU is MFSGD_ERR_NO_DEVICE.  Model, index, weights,
+ * mass table, schedules and cached graphs are not modified.  The pieces are the uniform calls': whole rows of at most 2^22
+ * candidates (a row with more is a piece of its own), 8 more bytes per row of a piece with out_mass, all staging freed
+ * before the call returns, on every path -- mfsgd_debug_device_bytes is the same before and after.
+ * Cost on top of the uniform call: the second search, log2(n_items) dependent 8-byte loads per candidate.               */
+int mfsgd_sample_unseen_hard_weighted(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first,
+                                      int32_t* out_items /* n */, float* out_scores /* nullable, n */,
+                                      int32_t* out_draw /* nullable, n */, int64_t* out_mass /* nullable, n */);
+int mfsgd_sample_unseen_violating_weighted(mfsgd_handle* h, const int32_t* users, const int32_t* pos_items, int64_t n, int32_t m,
+                                           float margin, int64_t seed, int64_t first, int32_t* out_items /* n */,
+                                           int32_t* out_draw /* nullable, n */, float* out_margin /* nullable, n */,
+                                           int32_t* out_rank /* nullable, n */, int64_t* out_mass /* nullable, n */);
 /* The serving calls against the index.  Each is the call it is named after -- mfsgd_recommend_excluding,
  * mfsgd_recommend_among, mfsgd_rank_items, mfsgd_evaluate_ranking -- given the index's pairs as its exclusion pairs:
  * order, ties, score bits, padding with -1 / NaN, the rule that a ranked pair's own item counts as eligible even if

@@ -124,6 +124,8 @@ SIGNATURES = {
     "mfsgd_fold_in_items": (C.c_int, [_H, C.c_int32, _i64p, _i32p, _f32p, C.c_int32, _f32p, C.c_int64, _f32p]),
     "mfsgd_fold_in_users_pairwise": (C.c_int, [_H, C.c_int32, _i64p, _i32p, C.c_int32, C.c_int32, _f32p, C.c_int64, C.c_int64,
                                               C.c_int64, _f32p, _f32p, _i32p]),
+    "mfsgd_fold_in_users_pairwise_weighted": (C.c_int, [_H, C.c_int32, _i64p, _i32p, C.c_int32, C.c_int32, _f32p, C.c_int64,
+                                                       C.c_int64, C.c_int64, _f32p, _f32p, _i32p]),
     "mfsgd_recommend_rows": (C.c_int, [_H, _f32p, C.c_int32, C.c_int32, _i32p, _i32p, C.c_int64, _i32p, _f32p]),
     "mfsgd_recommend_among": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i64p, _i32p, C.c_int64, _i32p, _i32p, C.c_int64,
                                         _i32p, _f32p]),
@@ -149,6 +151,10 @@ SIGNATURES = {
     "mfsgd_sample_unseen_hard": (C.c_int, [_H, _i32p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, _i32p, _f32p, _i32p]),
     "mfsgd_sample_unseen_violating": (C.c_int, [_H, _i32p, _i32p, C.c_int64, C.c_int32, C.c_float, C.c_int64, C.c_int64, _i32p,
                                                 _i32p, _f32p, _i32p]),
+    "mfsgd_sample_unseen_hard_weighted": (C.c_int, [_H, _i32p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, _i32p, _f32p, _i32p,
+                                                    _i64p]),
+    "mfsgd_sample_unseen_violating_weighted": (C.c_int, [_H, _i32p, _i32p, C.c_int64, C.c_int32, C.c_float, C.c_int64, C.c_int64,
+                                                         _i32p, _i32p, _f32p, _i32p, _i64p]),
     "mfsgd_recommend_unseen": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i32p, _f32p]),
     "mfsgd_recommend_unseen_among": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i64p, _i32p, C.c_int64, _i32p, _f32p]),
     "mfsgd_rank_items_unseen": (C.c_int, [_H, _i32p, _i32p, C.c_int64, _i32p]),

@@ -2,7 +2,9 @@
 // integers only: ONE definition each.  The uniform one is shared by sample.hip (every draw goes to memory), pick.hip
 // (the draws are scored and only the best leaves the kernel, or walked to the first that violates a margin) and
 // foldin_pairwise.hip (a chain draws its own negatives), so that the candidates of mfsgd_sample_unseen_hard and
-// mfsgd_sample_unseen_violating are mfsgd_sample_unseen's by construction; the weighted one lies here for the same reason.
+// mfsgd_sample_unseen_violating are mfsgd_sample_unseen's by construction; the weighted one is shared the same way, so
+// that those of the _weighted calls are mfsgd_sample_unseen_weighted's.  The kernels that score their draws take either
+// as a policy (UniformDraw, WeightedDraw, at the end of this file).
 // A uniform draw is a pure function of (seed, its counter c), the user's sorted, distinct list S (length s) and the item
 // count:
 //     r   = draw_mix32(seed, c): the upper 32 bits of splitmix64's output for the state seed + golden * (c + 1)
@@ -108,19 +110,57 @@ __device__ __forceinline__ int32_t draw_uniform(const Unseen& set, const unsigne
     return draw_unseen_at(set.list, set.s, (long long)((r * (unsigned long long)set.cnt) >> 32));
 }
 
-// The weighted draw of counter c: the unseen weight, the rank within it, the two searches.  mass is the index's table
-// (parallel to its items), C the prefix of the n_items weights; cnt receives the unseen weight of the set's user, and
-// the draw is -1 when that is 0: everything of positive weight is seen.
+// The weighted draw of counter c for a user whose unseen weight cnt > 0 is known: the mix, the rank within cnt, the two
+// searches.  mass is the index's table (parallel to its items), C the prefix of the n_items weights.
+__device__ __forceinline__ int32_t draw_weighted_of(const Unseen& set, const unsigned long long* __restrict__ mass,
+                                                    const unsigned long long* __restrict__ C, const int n_items,
+                                                    const unsigned long long cnt, const unsigned long long seed,
+                                                    const unsigned long long c) {
+    return draw_weighted_at(set.list, mass + set.from, set.s, C, n_items, cnt, __umul64hi(draw_mix64(seed, c), cnt));
+}
+
+// The same for a caller that does not know it: cnt receives the unseen weight of the set's user, and the draw is -1 when
+// that is 0: everything of positive weight is seen.
 __device__ __forceinline__ int32_t draw_weighted(const Unseen& set, const unsigned long long* __restrict__ mass,
                                                  const unsigned long long* __restrict__ C, const int n_items,
                                                  const unsigned long long seed, const unsigned long long c,
                                                  unsigned long long& cnt) {
-    const unsigned long long* g = mass + set.from;
-    cnt = draw_unseen_mass(set.list, g, set.s, C, n_items);
+    cnt = draw_unseen_mass(set.list, mass + set.from, set.s, C, n_items);
     int32_t item = -1;
-    if (cnt > 0) item = draw_weighted_at(set.list, g, set.s, C, n_items, cnt, __umul64hi(draw_mix64(seed, c), cnt));
+    if (cnt > 0) item = draw_weighted_of(set, mass, C, n_items, cnt, seed, c);
     return item;
 }
+
+// The draw as a policy of the kernels that score their draws (pick.hip, foldin_pairwise.hip), so that each of them is
+// ONE definition for both draws.  A policy says what a user has to draw from -- mass(): the number of unseen items, or
+// their weight; nothing is drawn for a user whose mass is 0 -- makes the draw of a counter for a user whose mass is
+// known and above 0, and carries what the draw reads beside the lists.  Both are passed to kernels by value.
+struct UniformDraw {
+    __device__ __forceinline__ unsigned long long mass(const Unseen& set, const int) const { return (unsigned long long)set.cnt; }
+    __device__ __forceinline__ int32_t draw(const Unseen& set, const int, const unsigned long long,
+                                            const unsigned long long seed, const unsigned long long c) const {
+        return draw_uniform(set, seed, c);
+    }
+    __device__ __forceinline__ void report(const long long, const unsigned long long) const {}
+};
+
+// g: the unseen-mass table of the lists the kernel draws from (parallel to their items; never read where every list is
+// empty), C: the prefix of the n_items weights, row_mass (nullable): where report() puts the mass of row x.
+struct WeightedDraw {
+    const unsigned long long* g;
+    const unsigned long long* C;
+    long long* row_mass;
+    __device__ __forceinline__ unsigned long long mass(const Unseen& set, const int n_items) const {
+        return draw_unseen_mass(set.list, g + set.from, set.s, C, n_items);
+    }
+    __device__ __forceinline__ int32_t draw(const Unseen& set, const int n_items, const unsigned long long cnt,
+                                            const unsigned long long seed, const unsigned long long c) const {
+        return draw_weighted_of(set, g, C, n_items, cnt, seed, c);
+    }
+    __device__ __forceinline__ void report(const long long x, const unsigned long long cnt) const {
+        if (row_mass) row_mass[x] = (long long)cnt;
+    }
+};
 
 }  // namespace
 }  // namespace mfsgd

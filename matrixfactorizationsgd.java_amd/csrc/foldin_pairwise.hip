@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "canon.hpp"
 #include "dispatch.hpp"
@@ -30,6 +31,9 @@ namespace {
 // the gathers (foldin.hip, kFoldDepth, is the idiom).  6, not kFoldDepth's 8: two rows a step are twice the registers, and
 // at 8 the kernel has room for two waves a SIMD where it has room for three at 6 ("Pairwise fold-in": measured).
 constexpr int kPairDepth = 6;
+// The same with the weighted draw, which holds a second search's state per draw and the user's unseen weight: at 6 it
+// needs 170 to 174 registers for L = 1, 4, 8, 16 (two waves a SIMD), at 5 it stays within the 168 of three.
+constexpr int kPairDepthWeighted = 5;
 // m > 1.  Candidates of one group whose Q rows are in flight together (pick.hip, kPickDepth); the next chunk is
 // gathered while the chunk in hand is scored, across the end of a step too.
 constexpr int kPairChunk = 4;
@@ -37,16 +41,21 @@ constexpr int kPairChunk = 4;
 // What both kernels know of their group.  Group g of the launch folds in new user x = perm[g] of the batch: positives
 // ptr[x] .. ptr[x + 1] of ids (ptr counts from the batch's first positive), the sorted distinct list
 // s_items[s_off[x] .. s_off[x + 1]), row `rows + x * k` (dense; read once at the start, written once at the end).
-template <int L>
+// The draw is a policy (draw.hpp: UniformDraw, or WeightedDraw over the batch's own mass table for
+// mfsgd_fold_in_users_pairwise_weighted): `mass` is what the user has to draw from, the number of unseen items or their
+// weight, and a user whose mass is 0 takes no step.
+template <int L, class Draw>
 struct Group {
     static constexpr int GPB = 256 / L;  // groups per block
+    const Draw& dr;
     int lig, x;
     bool live, draws;
     long long p0, len, at, steps, trip;
     Unseen set;  // of the batch's own lists; filled below by selects (Unseen's constructor branches: other code)
+    unsigned long long mass;
     float4 row;
 
-    __device__ __forceinline__ Group(const PairwiseFold& a) {
+    __device__ __forceinline__ Group(const PairwiseFold& a, const Draw& draw_) : dr(draw_) {
         lig = threadIdx.x % L;
         const long long g = (long long)blockIdx.x * GPB + threadIdx.x / L;
         live = g < a.nb;
@@ -56,11 +65,12 @@ struct Group {
         set.from = live ? a.s_off[x] : 0;
         set.s = live ? a.s_off[x + 1] - set.from : 0;
         set.list = a.s_items + set.from;
-        const long long cnt = set.cnt = (long long)a.n_items - set.s;
-        draws = live && cnt > 0;  // a group without draws gathers row 0 of Q in their place
+        set.cnt = (long long)a.n_items - set.s;
+        mass = dr.mass(set, a.n_items);  // (a group that is not live has an empty list: nothing of it is read)
+        draws = live && mass > 0;        // a group without draws gathers row 0 of Q in their place
         // a group without positives reads entry 0 of the batch (the launcher sends no batch without positives)
         at = len > 0 ? p0 : 0;
-        steps = cnt > 0 ? len * a.epochs : 0;  // the list names every item: no step is taken
+        steps = mass > 0 ? len * a.epochs : 0;  // the list names every item (of positive weight): no step is taken
         // trip count of the wave: the longest chain among its groups
         trip = steps;
         for (int w = L; w < 64; w <<= 1) {
@@ -78,7 +88,7 @@ struct Group {
 
     // The item of the user's draw number n (counter c0 + n); 0 for a group without draws.
     __device__ __forceinline__ int32_t draw(const PairwiseFold& a, const unsigned long long c0, const long long n) const {
-        return draw_uniform(set, a.seed, c0 + (unsigned long long)n);
+        return dr.draw(set, a.n_items, mass, a.seed, c0 + (unsigned long long)n);
     }
 
     // One step of the chain on the row: the margin before it, the P line of the pairwise step, kept when `on`.
@@ -102,7 +112,7 @@ struct Group {
 
     __device__ __forceinline__ void finish(const PairwiseFold& a) const {
         if (!live) return;
-        if (set.cnt <= 0)  // no step was taken: the user's margins and negatives say so
+        if (mass == 0)  // no step was taken: the user's margins and negatives say so
             for (long long e = lig; e < len * a.epochs; e += L) {
                 if (a.out_margin) a.out_margin[p0 * a.epochs + e] = __builtin_bit_cast(float, kQuietNaN);
                 if (a.out_neg) a.out_neg[p0 * a.epochs + e] = -1;
@@ -119,11 +129,11 @@ struct Group {
 // m == 1: the negative of step tau is the user's draw number tau.  Every D steps the group makes the D draws that the
 // id stream takes up next, lane `lig` those of the steps e = lig, lig + L, ... < D of the block, so the binary searches
 // of a block run side by side; the ids are handed round when their step's entry is fetched.
-template <int L, int D>
-__global__ void __launch_bounds__(256) fold_in_pairwise_kernel(const PairwiseFold a) {
+template <int L, int D, class Draw>
+__global__ void __launch_bounds__(256) fold_in_pairwise_kernel(const PairwiseFold a, const Draw dr) {
     constexpr int KP = 4 * L;
     constexpr int DR = (D + L - 1) / L;  // draws of one lane per block of D steps
-    Group<L> G(a);
+    Group<L, Draw> G(a, dr);
     if (G.trip > 0) {  // wave-uniform
         const unsigned long long c0 = a.first + (unsigned long long)(a.base + G.p0) * (unsigned long long)a.epochs;
         const long long wrap = G.len > 0 ? G.len : 1;
@@ -185,11 +195,11 @@ __global__ void __launch_bounds__(256) fold_in_pairwise_kernel(const PairwiseFol
 // two batches are held (w0: batch wb, w1: batch wb + 1), which is enough for a chunk of DC <= L consecutive draws.
 // m is the same for every user, so every lane of the launch walks the same chunks.  A place past the step's last
 // candidate repeats the chunk's first and is dropped by a select.
-template <int L, int D>
-__global__ void __launch_bounds__(256) fold_in_pairwise_hard_kernel(const PairwiseFold a) {
+template <int L, int D, class Draw>
+__global__ void __launch_bounds__(256) fold_in_pairwise_hard_kernel(const PairwiseFold a, const Draw dr) {
     constexpr int KP = 4 * L;
     constexpr int DC = D < L ? D : L;
-    Group<L> G(a);
+    Group<L, Draw> G(a, dr);
     if (G.trip > 0) {  // wave-uniform
         const int m = a.m;
         const unsigned long long c0 =
@@ -279,10 +289,15 @@ hipError_t launch_fold_in_pairwise(int L, const PairwiseFold& a, hipStream_t st)
     const int gpb = 256 / L;
     const dim3 grid((unsigned)((a.nb + gpb - 1) / gpb)), block(256);
     return with_L(L, [&](auto l) {
-        if (a.m == 1)
-            hipLaunchKernelGGL((fold_in_pairwise_kernel<l(), kPairDepth>), grid, block, 0, st, a);
-        else
-            hipLaunchKernelGGL((fold_in_pairwise_hard_kernel<l(), kPairChunk>), grid, block, 0, st, a);
+        auto go = [&](auto dr) {
+            constexpr int depth = std::is_same_v<decltype(dr), WeightedDraw> ? kPairDepthWeighted : kPairDepth;
+            if (a.m == 1)
+                hipLaunchKernelGGL((fold_in_pairwise_kernel<l(), depth, decltype(dr)>), grid, block, 0, st, a, dr);
+            else
+                hipLaunchKernelGGL((fold_in_pairwise_hard_kernel<l(), kPairChunk, decltype(dr)>), grid, block, 0, st, a, dr);
+        };
+        if (a.C) go(WeightedDraw{a.s_mass, a.C, nullptr});  // (the batch's own table: the lists are the batch's)
+        else go(UniformDraw{});
         return hipGetLastError();
     });
 }

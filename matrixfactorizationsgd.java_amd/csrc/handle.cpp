@@ -577,6 +577,22 @@ int mfsgd_sample_unseen_violating(mfsgd_handle* h, const int32_t* users, const i
     });
 }
 
+int mfsgd_sample_unseen_hard_weighted(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first,
+                                      int32_t* out_items, float* out_scores, int32_t* out_draw, int64_t* out_mass) {
+    return guarded(h, "sample_unseen_hard_weighted", [&]() -> int {
+        return seen_sample_hard_weighted(h, users, n, m, seed, first, out_items, out_scores, out_draw, out_mass);
+    });
+}
+
+int mfsgd_sample_unseen_violating_weighted(mfsgd_handle* h, const int32_t* users, const int32_t* pos_items, int64_t n, int32_t m,
+                                           float margin, int64_t seed, int64_t first, int32_t* out_items, int32_t* out_draw,
+                                           float* out_margin, int32_t* out_rank, int64_t* out_mass) {
+    return guarded(h, "sample_unseen_violating_weighted", [&]() -> int {
+        return seen_sample_violating_weighted(h, users, pos_items, n, m, margin, seed, first, out_items, out_draw, out_margin,
+                                              out_rank, out_mass);
+    });
+}
+
 int mfsgd_debug_device_bytes(int64_t* live) {
     if (!live) return MFSGD_ERR_INVALID_ARG;
     *live = g_dev_live_bytes.load();

@@ -250,6 +250,13 @@ int seen_sample_hard(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m
                      float* out_scores, int32_t* out_draw);
 int seen_sample_violating(mfsgd_handle* h, const int32_t* users, const int32_t* pos_items, int64_t n, int32_t m, float margin,
                           int64_t seed, int64_t first, int32_t* out_items, int32_t* out_draw, float* out_margin, int32_t* out_rank);
+// ... and of mfsgd_sample_unseen_hard_weighted and mfsgd_sample_unseen_violating_weighted: the same kernels under the
+// weighted draw
+int seen_sample_hard_weighted(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first,
+                              int32_t* out_items, float* out_scores, int32_t* out_draw, int64_t* out_mass);
+int seen_sample_violating_weighted(mfsgd_handle* h, const int32_t* users, const int32_t* pos_items, int64_t n, int32_t m,
+                                   float margin, int64_t seed, int64_t first, int32_t* out_items, int32_t* out_draw,
+                                   float* out_margin, int32_t* out_rank, int64_t* out_mass);
 // ratings.cpp
 void default_item_map(mfsgd_handle* h);
 int prepare_compute(mfsgd_handle* h);  // ratings present; factors and every partition's schedule on the device

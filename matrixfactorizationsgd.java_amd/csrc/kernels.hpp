@@ -83,6 +83,12 @@ struct PairwiseFold {
     unsigned long long seed, first;
     float* out_margin;
     int32_t* out_neg;
+    // mfsgd_fold_in_users_pairwise_weighted: the draws are sample_weighted_draws' for the lists {s_off, s_items}, s_mass
+    // their unseen-mass table (seen_unseen_mass over the batch's distinct pairs) and C the prefix of exactly n_items
+    // weights; a user whose unseen weight is 0 takes no step (0x7FC00000 and -1), the rest is as above.  C == nullptr:
+    // the uniform draw.
+    const unsigned long long* s_mass = nullptr;
+    const unsigned long long* C = nullptr;
 };
 hipError_t launch_fold_in_pairwise(int L, const PairwiseFold& a, hipStream_t st);
 
@@ -243,6 +249,18 @@ hipError_t sample_weighted_draws(const long long* off, const int32_t* items, con
                                  const unsigned long long* C, const int32_t* users, int64_t n_draws, int32_t m, int32_t n_items,
                                  int64_t seed, uint64_t first, int32_t* out, long long* row_mass, hipStream_t st);
 
+// pick.hip.  The weighted draw of a pick launch (mfsgd_sample_unseen_hard_weighted, mfsgd_sample_unseen_violating_weighted):
+// mass is the index's unseen-mass table (seen_unseen_mass; not read where off == nullptr), C the prefix of exactly
+// n_items weights, out_mass (nullable) receives each row's unseen weight.  C == nullptr: the uniform draw, the launch
+// as it is described below.  With weights the candidates are those sample_weighted_draws gives the row, a row has
+// nothing to draw where its user's unseen WEIGHT is 0, and everything else -- scores, rules, outputs, the unseen item
+// count in the rank -- is unchanged.
+struct PickWeights {
+    const unsigned long long* mass = nullptr;
+    const unsigned long long* C = nullptr;
+    long long* out_mass = nullptr;
+};
+
 // pick.hip.  Hard negatives (include/mfsgd.h, mfsgd_sample_unseen_hard): for each of the n rows of `users` (every one a
 // user of the index {off, items} and a row of P; off == nullptr: an index without pairs) the best-scoring of the m >= 1
 // candidates sample_unseen_draws gives that row for the same (m, n_items, seed, first), the score being dot(P[user],
@@ -251,7 +269,8 @@ hipError_t sample_weighted_draws(const long long* off, const int32_t* items, con
 // item.  n <= 2^22 (a piece).  Asynchronous on st.
 hipError_t launch_hard_negatives(int L, const float* P, const float* Q, const long long* off, const int32_t* items,
                                  const int32_t* users, int64_t n, int32_t m, int32_t n_items, int64_t seed, uint64_t first,
-                                 int32_t* out_items, float* out_scores, int32_t* out_draw, hipStream_t st);
+                                 int32_t* out_items, float* out_scores, int32_t* out_draw, hipStream_t st,
+                                 const PickWeights& w = {});
 
 // pick.hip.  The negative of a WARP step (include/mfsgd.h, mfsgd_sample_unseen_violating): rows, index, candidates and
 // dots as for launch_hard_negatives, pos[x] (a row of Q) the row's positive.  Of the row's m >= 1 candidates the first in
@@ -262,7 +281,7 @@ hipError_t launch_hard_negatives(int L, const float* P, const float* Q, const lo
 hipError_t launch_first_violating(int L, const float* P, const float* Q, const long long* off, const int32_t* items,
                                   const int32_t* users, const int32_t* pos, int64_t n, int32_t m, float margin, int32_t n_items,
                                   int64_t seed, uint64_t first, int32_t* out_items, int32_t* out_draw, float* out_margin,
-                                  int32_t* out_rank, hipStream_t st);
+                                  int32_t* out_rank, hipStream_t st, const PickWeights& w = {});
 
 // similar.hip.  out[x] = rn(row x) = 1 / sqrt(dot(row, row)), or 0 where that dot is 0, for the
 // n_rows kp-padded rows of M.  Asynchronous on st.

@@ -5,6 +5,9 @@
 // candidates never exist in memory.  The draw is draw.hpp's (sample.hip's, by construction); the dots are the canonical
 // dot of canon.hpp, the bits predict_kernel returns.  What the kernels share -- a row's prologue, a round's draws, a
 // chunk's gather, the launch -- is stated once; the loops and the rules are each kernel's own.
+// The draw is a policy of the kernels (draw.hpp: UniformDraw, WeightedDraw), not a second copy of them: with
+// WeightedDraw the candidates are mfsgd_sample_unseen_weighted's (mfsgd_sample_unseen_hard_weighted,
+// mfsgd_sample_unseen_violating_weighted; DESIGN.md, "Weighted picks"), everything else alike.
 // Build with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 
@@ -25,31 +28,36 @@ namespace {
 constexpr int kPickDepth = 4;
 
 // What both kernels know of their group: one lane group of L lanes per row x < n of the piece; the P row of users[x] is
-// loaded once.  The groups behind row n - 1, and a row whose user has seen everything, are not `live`: they compute on
-// zeros and issue no loads.  Draw d of the row has the counter c0 + d.
+// loaded once.  The groups behind row n - 1, and a row whose user has nothing to draw from (mass == 0: every item is
+// seen, or with weights every item of positive weight), are not `live`: they compute on zeros and issue no loads.  Draw
+// d of the row has the counter c0 + d.
 // off == nullptr: an index without pairs, every list is empty.
-template <int L>
+template <int L, class Draw>
 struct PickRow {
     static constexpr int KP = 4 * L;
     static constexpr int GPB = 256 / L;  // groups per block
     const int lig = threadIdx.x % L;
     const long long x = (long long)blockIdx.x * GPB + threadIdx.x / L;
     const bool row;
+    const Draw& dr;
+    const int n_items;
     int u = 0;
-    Unseen set;  // (empty, with nothing unseen, behind row n - 1)
-    bool live;   // the same in every lane of a group
+    Unseen set;                   // (empty, with nothing unseen, behind row n - 1)
+    unsigned long long mass = 0;  // what the row's user has to draw from: the policy's measure of the unseen items
+    bool live;                    // the same in every lane of a group
     const unsigned long long c0;
     float4 p = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 
-    __device__ __forceinline__ PickRow(const float* __restrict__ P, const long long* __restrict__ off,
+    __device__ __forceinline__ PickRow(const Draw& draw_, const float* __restrict__ P, const long long* __restrict__ off,
                                        const int32_t* __restrict__ items, const int32_t* __restrict__ users, const long long n,
-                                       const int m, const int n_items, const unsigned long long first)
-        : row(x < n), c0(first + (unsigned long long)x * (unsigned long long)m) {
+                                       const int m, const int n_items_, const unsigned long long first)
+        : row(x < n), dr(draw_), n_items(n_items_), c0(first + (unsigned long long)x * (unsigned long long)m) {
         if (row) {
             u = users[x];
             set = Unseen(off, items, u, n_items);
+            mass = dr.mass(set, n_items);
         }
-        live = row && set.cnt > 0;
+        live = row && mass > 0;
         if (live) p = q_row(P, u);
     }
 
@@ -59,11 +67,12 @@ struct PickRow {
     }
 
     // The candidates are taken in rounds of L: in the round that starts at candidate d0, lane `lig` of the group draws
-    // d = d0 + lig (counter c0 + d), so the binary searches of a round run side by side.  This lane's draw of a round of
+    // d = d0 + lig (counter c0 + d), so the binary searches of a round run side by side (with weights, two a lane: one
+    // over the mass table, one over the weights' prefix).  This lane's draw of a round of
     // `steps` candidates (1 .. L); 0 past them and for a group that is not `on` (a branch the whole group takes alike).
     __device__ __forceinline__ int32_t draw(const unsigned long long seed, const long long d0, const int steps, const bool on) const {
         int32_t mine = 0;
-        if (on && lig < steps) mine = draw_uniform(set, seed, c0 + (unsigned long long)(d0 + lig));
+        if (on && lig < steps) mine = dr.draw(set, n_items, mass, seed, c0 + (unsigned long long)(d0 + lig));
         return mine;
     }
 
@@ -90,15 +99,16 @@ struct PickRow {
 // d, and the running best (score, d, item) is the same in every lane of the group.
 // m is the same for every row, so every lane of the launch runs the same trip counts (the DPP levels of
 // group_allreduce need their partner lanes live).
-template <int L, int D>
+template <int L, int D, class Draw>
 __global__ void __launch_bounds__(256) hard_negative_kernel(const float* __restrict__ P, const float* __restrict__ Q,
                                                             const long long* __restrict__ off,
                                                             const int32_t* __restrict__ items,
                                                             const int32_t* __restrict__ users, const long long n,
                                                             const int m, const int n_items, const unsigned long long seed,
                                                             const unsigned long long first, int32_t* __restrict__ out_items,
-                                                            float* __restrict__ out_scores, int32_t* __restrict__ out_draw) {
-    const PickRow<L> R(P, off, items, users, n, m, n_items, first);
+                                                            float* __restrict__ out_scores, int32_t* __restrict__ out_draw,
+                                                            const Draw dr) {
+    const PickRow<L, Draw> R(dr, P, off, items, users, n, m, n_items, first);
     float best_s = __builtin_bit_cast(float, kQuietNaN);
     int32_t best_d = -1, best_item = -1;
     for (long long d0 = 0; d0 < m; d0 += L) {
@@ -121,7 +131,8 @@ __global__ void __launch_bounds__(256) hard_negative_kernel(const float* __restr
         }
     }
     if (R.row && R.lig == 0) {
-        const bool none = R.set.cnt <= 0;  // the user has seen everything
+        const bool none = R.mass == 0;  // the user has nothing to draw from
+        dr.report(R.x, R.mass);
         out_items[R.x] = none ? -1 : best_item;
         if (out_scores) out_scores[R.x] = none ? __builtin_bit_cast(float, kQuietNaN) : best_s;
         if (out_draw) out_draw[R.x] = none ? -1 : best_d;
@@ -137,13 +148,13 @@ __global__ void __launch_bounds__(256) hard_negative_kernel(const float* __restr
 // group_allreduce, like the permutes of the gather, are never inside a branch.  The loops are left only when no group of
 // the WAVE needs anything more: a ballot, so every lane of the wave leaves at the same trip, and a wave shares nothing
 // with the other waves of its workgroup (no LDS, no barrier).
-template <int L, int D>
+template <int L, int D, class Draw>
 __global__ void __launch_bounds__(256) first_violating_kernel(
     const float* __restrict__ P, const float* __restrict__ Q, const long long* __restrict__ off, const int32_t* __restrict__ items,
     const int32_t* __restrict__ users, const int32_t* __restrict__ pos, const long long n, const int m, const float margin,
     const int n_items, const unsigned long long seed, const unsigned long long first, int32_t* __restrict__ out_items,
-    int32_t* __restrict__ out_draw, float* __restrict__ out_margin, int32_t* __restrict__ out_rank) {
-    const PickRow<L> R(P, off, items, users, n, m, n_items, first);
+    int32_t* __restrict__ out_draw, float* __restrict__ out_margin, int32_t* __restrict__ out_rank, const Draw dr) {
+    const PickRow<L, Draw> R(dr, P, off, items, users, n, m, n_items, first);
     const int ip = R.row ? pos[R.x] : 0;
     float4 qp = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (R.live) qp = R.q_row(Q, ip);
@@ -175,13 +186,14 @@ __global__ void __launch_bounds__(256) first_violating_kernel(
         }
     }
     if (R.row && R.lig == 0) {
-        const bool none = R.set.cnt <= 0;  // the user has seen everything
+        const bool none = R.mass == 0;  // the user has nothing to draw from
         const bool hit = pick_d >= 0;
+        dr.report(R.x, R.mass);
         out_items[R.x] = pick_item;
         if (out_draw) out_draw[R.x] = none ? -1 : hit ? pick_d : m;
         if (out_margin) out_margin[R.x] = pick_x;
         if (out_rank) {
-            const long long rk = hit ? R.set.cnt / ((long long)pick_d + 1) : 0;
+            const long long rk = hit ? R.set.cnt / ((long long)pick_d + 1) : 0;  // (the unseen COUNT under either draw)
             out_rank[R.x] = hit ? (int32_t)(rk < 1 ? 1 : rk) : 0;
         }
     }
@@ -200,26 +212,37 @@ hipError_t launch_pick(const int L, const int64_t n, const int32_t m, Launch&& l
     });
 }
 
+// The weighted policy of a launch: no weights (C == nullptr) is the uniform draw.
+WeightedDraw weighted(const PickWeights& w) { return WeightedDraw{w.mass, w.C, w.out_mass}; }
+
 }  // namespace
 
 hipError_t launch_hard_negatives(int L, const float* P, const float* Q, const long long* off, const int32_t* items,
                                  const int32_t* users, int64_t n, int32_t m, int32_t n_items, int64_t seed, uint64_t first,
-                                 int32_t* out_items, float* out_scores, int32_t* out_draw, hipStream_t st) {
+                                 int32_t* out_items, float* out_scores, int32_t* out_draw, hipStream_t st, const PickWeights& w) {
     return launch_pick(L, n, m, [&](auto l, const dim3 grid, const dim3 block) {
-        hipLaunchKernelGGL((hard_negative_kernel<l(), kPickDepth>), grid, block, 0, st, P, Q, off, items, users, (long long)n,
-                           (int)m, (int)n_items, (unsigned long long)seed, (unsigned long long)first, out_items, out_scores,
-                           out_draw);
+        auto go = [&](auto dr) {
+            hipLaunchKernelGGL((hard_negative_kernel<l(), kPickDepth, decltype(dr)>), grid, block, 0, st, P, Q, off, items, users,
+                               (long long)n, (int)m, (int)n_items, (unsigned long long)seed, (unsigned long long)first, out_items,
+                               out_scores, out_draw, dr);
+        };
+        if (w.C) go(weighted(w));
+        else go(UniformDraw{});
     });
 }
 
 hipError_t launch_first_violating(int L, const float* P, const float* Q, const long long* off, const int32_t* items,
                                   const int32_t* users, const int32_t* pos, int64_t n, int32_t m, float margin, int32_t n_items,
                                   int64_t seed, uint64_t first, int32_t* out_items, int32_t* out_draw, float* out_margin,
-                                  int32_t* out_rank, hipStream_t st) {
+                                  int32_t* out_rank, hipStream_t st, const PickWeights& w) {
     return launch_pick(L, n, m, [&](auto l, const dim3 grid, const dim3 block) {
-        hipLaunchKernelGGL((first_violating_kernel<l(), kPickDepth>), grid, block, 0, st, P, Q, off, items, users, pos, (long long)n,
-                           (int)m, margin, (int)n_items, (unsigned long long)seed, (unsigned long long)first, out_items, out_draw,
-                           out_margin, out_rank);
+        auto go = [&](auto dr) {
+            hipLaunchKernelGGL((first_violating_kernel<l(), kPickDepth, decltype(dr)>), grid, block, 0, st, P, Q, off, items, users,
+                               pos, (long long)n, (int)m, margin, (int)n_items, (unsigned long long)seed, (unsigned long long)first,
+                               out_items, out_draw, out_margin, out_rank, dr);
+        };
+        if (w.C) go(weighted(w));
+        else go(UniformDraw{});
     });
 }
 

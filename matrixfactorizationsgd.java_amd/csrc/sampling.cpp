@@ -1,6 +1,7 @@
 // sampling.cpp -- the calls that sample among the items a user has NOT seen, behind the entry points of handle.cpp:
 // mfsgd_sample_unseen (uniform draws), mfsgd_sample_unseen_weighted (draws by item weight), mfsgd_sample_unseen_hard (the
-// best-scoring of a row's draws) and mfsgd_sample_unseen_violating (the first of them that violates a margin).  They read
+// best-scoring of a row's draws) and mfsgd_sample_unseen_violating (the first of them that violates a margin), and the
+// last two over weighted draws (mfsgd_sample_unseen_hard_weighted, mfsgd_sample_unseen_violating_weighted).  They read
 // the seen-item index (handle.hpp, Seen; seen_index.cpp builds it) and share their checks, their pieces and their
 // staging, which are stated once, here; the kernels are sample.hip's and pick.hip's.
 #include <algorithm>
@@ -11,7 +12,7 @@
 namespace mfsgd {
 namespace {
 
-// What tells the four calls apart in the checks they share.
+// What tells the calls apart in the checks they share.
 struct Family {
     const char* name;
     int32_t m_min;          // the smallest m: 0 ("m is negative" below it) or 1 ("m is below 1")
@@ -170,6 +171,58 @@ int seen_sample_violating(mfsgd_handle* h, const int32_t* users, const int32_t* 
                                       d_pos.data(), c, m, margin, h->cfg.n_items, seed, c_first, items.data(), draw.data(),
                                       margins.data(), rank.data(), h->stream);
     }, items, draw, margins, rank);
+}
+
+// The weighted draw of a pick call on a checked handle: the index's mass table, the weights' prefix, the column of the
+// rows' unseen weights.
+static PickWeights pick_weights(const mfsgd_handle* h, const Column<long long, int64_t>& mass) {
+    return PickWeights{h->seen.mass.data(), h->weights.C.data(), mass.data()};
+}
+
+// Body of mfsgd_sample_unseen_hard_weighted (handle.cpp): seen_sample_hard over the candidates seen_sample_weighted would
+// give the row -- the same pieces and counters, and a row's unseen weight beside its pick when asked.
+int seen_sample_hard_weighted(mfsgd_handle* h, const int32_t* users, int64_t n, int32_t m, int64_t seed, int64_t first,
+                              int32_t* out_items, float* out_scores, int32_t* out_draw, int64_t* out_mass) {
+    static const Family k{"sample_unseen_hard_weighted", 1, true, "user", false, true};
+    int rc = check_sample(h, k, users, nullptr, n, m, 0.0f, first, out_items);
+    if (rc || n == 0) return rc;
+    const Seen& s = h->seen;
+    if (s.n > 0 && !s.mass)  // (never: it is eager)
+        return fail(h, MFSGD_ERR_STATE, "sample_unseen_hard_weighted: the index has no unseen-mass table");
+    if ((rc = factors_to_device(h))) return rc;
+    Column<int32_t> items(h, out_items), draw(h, out_draw);
+    Column<float> scores(h, out_scores);
+    Column<long long, int64_t> mass(h, out_mass);
+    return sample_pieces(h, k, users, n, m, first, [&](const int32_t* d_users, int64_t, int64_t c, uint64_t c_first) {
+        return launch_hard_negatives(h->geo.L, h->dP.data(), h->dQ.data(), seen_off(s), s.items.data(), d_users, c, m,
+                                     h->cfg.n_items, seed, c_first, items.data(), scores.data(), draw.data(), h->stream,
+                                     pick_weights(h, mass));
+    }, items, scores, draw, mass);
+}
+
+// Body of mfsgd_sample_unseen_violating_weighted (handle.cpp): seen_sample_violating over those candidates.
+int seen_sample_violating_weighted(mfsgd_handle* h, const int32_t* users, const int32_t* pos_items, int64_t n, int32_t m,
+                                   float margin, int64_t seed, int64_t first, int32_t* out_items, int32_t* out_draw,
+                                   float* out_margin, int32_t* out_rank, int64_t* out_mass) {
+    static const Family k{"sample_unseen_violating_weighted", 1, true, "row", true, true};
+    int rc = check_sample(h, k, users, pos_items, n, m, margin, first, out_items);
+    if (rc || n == 0) return rc;
+    const Seen& s = h->seen;
+    if (s.n > 0 && !s.mass)  // (never: it is eager)
+        return fail(h, MFSGD_ERR_STATE, "sample_unseen_violating_weighted: the index has no unseen-mass table");
+    if ((rc = factors_to_device(h))) return rc;
+    DevArray<int32_t> d_pos;
+    if ((rc = dev_alloc(h, d_pos, (size_t)piece_rows(n, m)))) return rc;
+    Column<int32_t> items(h, out_items), draw(h, out_draw), rank(h, out_rank);
+    Column<float> margins(h, out_margin);
+    Column<long long, int64_t> mass(h, out_mass);
+    return sample_pieces(h, k, users, n, m, first, [&](const int32_t* d_users, int64_t x0, int64_t c, uint64_t c_first) {
+        const hipError_t e = copy_up(d_pos, pos_items + x0, (size_t)c, h->stream);
+        if (e != hipSuccess) return e;
+        return launch_first_violating(h->geo.L, h->dP.data(), h->dQ.data(), seen_off(s), s.items.data(), d_users,
+                                      d_pos.data(), c, m, margin, h->cfg.n_items, seed, c_first, items.data(), draw.data(),
+                                      margins.data(), rank.data(), h->stream, pick_weights(h, mass));
+    }, items, draw, margins, rank, mass);
 }
 
 }  // namespace mfsgd

@@ -562,13 +562,17 @@ struct PairwiseFoldRequest {
     float* out_rows;
     float* out_margin;
     int32_t* out_neg;
+    bool weighted = false;  // mfsgd_fold_in_users_pairwise_weighted: the draws go by the handle's item weights
 };
 
 // Body of mfsgd_fold_in_users_pairwise: fold_in_core's batches, perm and staging; per batch the sorted distinct lists S
 // are made on the device out of the positives that were just uploaded, the way candidates_to_device makes its per-row
 // lists (keys user << 32 | item, sorted and made distinct, one CSR offset array), and the chain kernel runs off them.
+// And of mfsgd_fold_in_users_pairwise_weighted: the same, and per batch the unseen-mass table of those lists under the
+// handle's weights (seen_unseen_mass, as for the index), which the chain's weighted draws search.
 static int fold_in_pairwise_core(mfsgd_handle* h, const PairwiseFoldRequest& req) {
-    const std::string call = "fold_in_pairwise: ";
+    const char* name = req.weighted ? "fold_in_pairwise_weighted" : "fold_in_pairwise";
+    const std::string call = std::string(name) + ": ";
     const int32_t n_new = req.n_new, epochs = req.epochs, m = req.m;
     const int64_t* row_ptr = req.row_ptr;
     if (n_new < 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "n_new is negative");
@@ -591,7 +595,12 @@ static int fold_in_pairwise_core(mfsgd_handle* h, const PairwiseFoldRequest& req
     if (total > 0 && !req.items) return fail(h, MFSGD_ERR_INVALID_ARG, call + "items is null");
     const int64_t j = first_outside(req.items, total, h->cfg.n_items);
     if (j >= 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "item of positive " + std::to_string(j) + " out of range");
-    if (const int rc = check_reads_factors(h, "fold_in_pairwise")) return rc;
+    if (const int rc = check_reads_factors(h, name)) return rc;
+    const ItemWeights& iw = h->weights;
+    if (req.weighted && !iw.present) return fail(h, MFSGD_ERR_STATE, call + "no item weights");
+    if (req.weighted && iw.n != h->cfg.n_items)
+        return fail(h, MFSGD_ERR_STATE,
+                    call + "item weights cover " + std::to_string(iw.n) + " items, the model has " + std::to_string(h->cfg.n_items));
     if (n_new == 0) return MFSGD_OK;
     int rc = factors_to_device(h);
     if (rc) return rc;
@@ -604,12 +613,13 @@ static int fold_in_pairwise_core(mfsgd_handle* h, const PairwiseFoldRequest& req
     DevArray<float> d_rows, d_margin;
     DevArray<long long> d_ptr, s_off;
     DevArray<int32_t> d_perm, d_ids, s_items, d_neg;
-    DevArray<unsigned long long> keys, keys_tmp;
+    DevArray<unsigned long long> keys, keys_tmp, s_mass, scanned;  // (the last two: 16 bytes per distinct positive, weighted)
     DevArray<unsigned> count;
     DevBuf temp;  // the rocPRIM scratch, bytes of no type
     const size_t row_floats = (size_t)n_new * (size_t)k;
     if ((rc = dev_alloc(h, d_rows, row_floats))) return rc;
     if (work) {
+        if (req.weighted && ((rc = dev_alloc(h, s_mass, stage)) || (rc = dev_alloc(h, scanned, stage)))) return rc;
         if ((rc = dev_alloc(h, d_ptr, (size_t)bt.max_rows + 1)) || (rc = dev_alloc(h, d_perm, (size_t)bt.max_rows))) return rc;
         if ((rc = dev_alloc(h, d_ids, stage))) return rc;
         if ((rc = dev_alloc(h, keys, stage)) || (rc = dev_alloc(h, keys_tmp, stage)) || (rc = dev_alloc(h, count, 4))) return rc;
@@ -642,10 +652,20 @@ static int fold_in_pairwise_core(mfsgd_handle* h, const PairwiseFoldRequest& req
         HIPCHK_OR(bad, recommend_cand_keys(d_ptr.data(), nb, d_ids.data(), 0, nr, keys.data(), h->stream));
         HIPCHK_OR(bad, recommend_excl_lists(keys.data(), keys_tmp.data(), nr, nb, count.data(), s_off.data(), s_items.data(), temp,
                                             h->stream));
-        const PairwiseFold job{h->dQ.data(), d_rows.data() + (size_t)x0 * k, k, d_ptr.data(), base, d_perm.data(), nb,
-                               d_ids.data(), s_off.data(), s_items.data(), h->cfg.n_items, epochs, m, h->cfg.lr,
-                               1.0f - h->cfg.lr * h->cfg.lambda, (unsigned long long)req.draw_seed, (unsigned long long)req.first,
-                               d_margin.data(), d_neg.data()};
+        PairwiseFold job{h->dQ.data(), d_rows.data() + (size_t)x0 * k, k, d_ptr.data(), base, d_perm.data(), nb,
+                         d_ids.data(), s_off.data(), s_items.data(), h->cfg.n_items, epochs, m, h->cfg.lr,
+                         1.0f - h->cfg.lr * h->cfg.lambda, (unsigned long long)req.draw_seed, (unsigned long long)req.first,
+                         d_margin.data(), d_neg.data()};
+        if (req.weighted) {
+            // the batch's mass table, over its distinct pairs: their number comes down first
+            unsigned distinct = 0;
+            HIPCHK_OR(bad, copy_down(&distinct, count, 1, h->stream));
+            HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
+            HIPCHK_OR(bad, seen_unseen_mass(s_off.data(), s_items.data(), (int64_t)distinct, nb, iw.C.data(), iw.n, scanned.data(),
+                                            s_mass.data(), temp, h->stream));
+            job.s_mass = s_mass.data();
+            job.C = iw.C.data();
+        }
         HIPCHK_OR(bad, launch_fold_in_pairwise(h->geo.L, job, h->stream));
         const size_t at = (size_t)base * (size_t)epochs, n_steps = (size_t)nr * (size_t)epochs;
         if (req.out_margin) HIPCHK_OR(bad, copy_down(req.out_margin + at, d_margin, n_steps, h->stream));
@@ -919,6 +939,15 @@ int mfsgd_fold_in_users(mfsgd_handle* h, int32_t n_new, const int64_t* row_ptr, 
     return guarded(h, "fold_in", [&]() -> int {
         return fold_in_core(h, kFoldInUsers, &mfsgd_handle::dQ, h->cfg.n_items,
                             {n_new, row_ptr, items, ratings, epochs, init_rows, seed, out_rows});
+    });
+}
+
+int mfsgd_fold_in_users_pairwise_weighted(mfsgd_handle* h, int32_t n_new, const int64_t* row_ptr, const int32_t* items,
+                                          int32_t epochs, int32_t m, const float* init_rows, int64_t seed, int64_t draw_seed,
+                                          int64_t first, float* out_rows, float* out_margin, int32_t* out_neg) {
+    return guarded(h, "fold_in_pairwise_weighted", [&]() -> int {
+        return fold_in_pairwise_core(h, {n_new, row_ptr, items, epochs, m, init_rows, seed, draw_seed, first, out_rows,
+                                         out_margin, out_neg, true});
     });
 }
 

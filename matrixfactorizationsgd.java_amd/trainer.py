@@ -487,7 +487,8 @@ class MatrixFactorizationSGD:
         if not self._initialised:
             self.init_factors()
 
-    def fit_bpr(self, u, i, epochs, *, seed=0, first_epoch=0, stats=True, candidates=1, refresh=None, sampling="uniform"):
+    def fit_bpr(self, u, i, epochs, *, seed=0, first_epoch=0, stats=True, candidates=1, refresh=None, sampling="uniform",
+                candidate_sampling="uniform"):
         """Trains on one-class data with Bayesian personalised ranking: (u[x], i[x]) are the positives, duplicates
         allowed, and every epoch pairs each of them with one freshly drawn item its user has not seen and takes one
         pairwise step per positive, in the order given -- pass the positives shuffled: the order is the caller's, and a
@@ -508,8 +509,14 @@ class MatrixFactorizationSGD:
         picks against fresher factors and costs a call per block.  Splitting the epochs with first_epoch gives the same
         bits here too.  candidates=1 is the uniform draw above and does not read the factors to draw.
         sampling="weighted" draws every epoch's J with sample_unseen_weighted instead, same counters, in proportion to
-        the item weights the handle has (set_item_weights, set_popularity_weights); everything else is as above.  With
-        candidates > 1 it is a ValueError: hard negatives among weighted candidates are not built.
+        the item weights the handle has (set_item_weights, set_popularity_weights); everything else is as above.  It is
+        the spelling for candidates=1 only: with candidates > 1 it is a ValueError.
+        candidate_sampling="weighted", with candidates > 1, draws each block's picks with
+        sample_unseen_hard(..., sampling="weighted") instead: hard negatives among candidates drawn in proportion to the
+        item weights, same counters, rows with -1 (users whose unseen items all weigh nothing) dropped; everything else
+        is as above.  It is the spelling for candidates > 1 only: with candidates=1 anything but "uniform" is a
+        ValueError, sampling="weighted" being the weighted draw there.  A handle without weights for the items it has
+        now is a ValueError too, before the index or the factors are touched.
         Returns, with stats, dict(loss, auc), float64[epochs] each, from the margins x every triple had just before its
         own step: the mean of log1p(exp(-x)), and the share of triples with x > 0.  Without stats: None."""
         uu, ii = _pairs(np.atleast_1d(u), np.atleast_1d(i), "u and i")
@@ -521,6 +528,10 @@ class MatrixFactorizationSGD:
         weighted = self._sampling(sampling)
         if weighted and m > 1:
             raise ValueError('sampling="weighted" needs candidates=1')
+        if self._sampling(candidate_sampling, "candidate_sampling"):
+            if m == 1:
+                raise ValueError('candidate_sampling="weighted" needs candidates > 1: with candidates=1 it is sampling="weighted"')
+            self._need_item_weights("candidate_sampling")
         draw_into = self._sample_weighted_into if weighted else self._sample_unseen_into
         self._index_and_factors(uu, ii)
         loss, auc = np.zeros(epochs, np.float64), np.zeros(epochs, np.float64)
@@ -530,7 +541,7 @@ class MatrixFactorizationSGD:
                 xs = []
                 for a in range(0, n, step):
                     bu, bi = uu[a:a + step], ii[a:a + step]
-                    J = self.sample_unseen_hard(bu, m, seed, ((int(first_epoch) + e) * n + a) * m)
+                    J = self.sample_unseen_hard(bu, m, seed, ((int(first_epoch) + e) * n + a) * m, sampling=candidate_sampling)
                     if J.min() < 0:  # users who have seen everything have no negatives
                         keep = J >= 0
                         bu, bi, J = bu[keep], bi[keep], J[keep]
@@ -553,7 +564,8 @@ class MatrixFactorizationSGD:
                 loss[e], auc[e] = np.logaddexp(0.0, -x).mean(), (x > 0).mean()
         return dict(loss=loss, auc=auc) if stats else None
 
-    def fit_warp(self, u, i, epochs, *, candidates=10, margin=1.0, refresh=None, seed=0, first_epoch=0, stats=True):
+    def fit_warp(self, u, i, epochs, *, candidates=10, margin=1.0, refresh=None, seed=0, first_epoch=0, stats=True,
+                 sampling="uniform"):
         """Trains on one-class data with WARP, Weston's weighted approximate-rank pairwise loss: (u[x], i[x]) are the
         positives, in the order given (pass them shuffled, as for fit_bpr).  Each positive's negative is the first of
         m = candidates unseen draws that violates the margin, dot(p, qi) - dot(p, qj) < margin, under the current
@@ -567,6 +579,10 @@ class MatrixFactorizationSGD:
         them; the rows with J < 0 (no violator, or nothing unseen) are dropped;
         partial_fit_pairwise(..., weights=warp_weights(rk)) of the rest.  Splitting the epochs with first_epoch gives
         the same bits as one run.  The stored rating set is not touched.
+        sampling="weighted" draws every block with sample_unseen_violating(..., sampling="weighted") instead: the
+        candidates come in proportion to the item weights the handle has (set_item_weights, set_popularity_weights),
+        same counters; everything else is as above.  A handle without weights for the items it has now is a
+        ValueError, before the index or the factors are touched.
         Returns, with stats, dict(violating, trials), float64[epochs] each: the share of positives that had a violator,
         and the mean of d + 1 over those positives (0 where there were none).  Without stats: None."""
         uu, ii = _pairs(np.atleast_1d(u), np.atleast_1d(i), "u and i")
@@ -577,6 +593,8 @@ class MatrixFactorizationSGD:
             raise ValueError("candidates and refresh must be at least 1")
         if np.isnan(margin):
             raise ValueError("margin must not be NaN")
+        if self._sampling(sampling):
+            self._need_item_weights("sampling")
         self._index_and_factors(uu, ii)
         violating, trials = np.zeros(epochs, np.float64), np.zeros(epochs, np.float64)
         step = max(n, 1) if refresh is None else int(refresh)
@@ -585,7 +603,7 @@ class MatrixFactorizationSGD:
             for a in range(0, n, step):
                 bu, bi = uu[a:a + step], ii[a:a + step]
                 J, d, rk = self.sample_unseen_violating(bu, bi, m, margin, seed, ((int(first_epoch) + e) * n + a) * m,
-                                                        draws=True, ranks=True)
+                                                        draws=True, ranks=True, sampling=sampling)
                 keep = J >= 0
                 self.partial_fit_pairwise(bu[keep], bi[keep], J[keep], weights=warp_weights(rk[keep]))
                 hits += int(keep.sum())
@@ -758,28 +776,57 @@ class MatrixFactorizationSGD:
                                                            None if mass is None else _p(mass, C.c_int64)))
 
     @staticmethod
-    def _sampling(sampling):
+    def _sampling(sampling, keyword="sampling"):
         if sampling not in ("uniform", "weighted"):
-            raise ValueError('sampling must be "uniform" or "weighted"')
+            raise ValueError(keyword + ' must be "uniform" or "weighted"')
         return sampling == "weighted"
 
-    def sample_unseen_hard(self, users, m, seed=0, first=0, *, scores=False, draws=False):
+    def _need_item_weights(self, keyword):
+        """What fit_bpr and fit_warp ask before they touch anything for a weighted keyword: weights, set for the items
+        the model has now (the draw itself would refuse only after the index and the factors were made)."""
+        n = C.c_int32(-2)
+        self._check(self._lib.mfsgd_get_item_weights(self._handle(), None, C.byref(n)))
+        if n.value < 0:
+            raise ValueError(keyword + '="weighted" needs item weights: set_item_weights or set_popularity_weights first')
+        self._dims()
+        if n.value != self.items:
+            raise ValueError(keyword + f'="weighted": the item weights cover {n.value} items, the model has {self.items}')
+
+    @classmethod
+    def _sampling_mass(cls, sampling, mass):
+        """The weighted flag of a pick call, whose mass=True is the weighted call's alone."""
+        weighted = cls._sampling(sampling)
+        if mass and not weighted:
+            raise ValueError('mass=True needs sampling="weighted"')
+        return weighted
+
+    def sample_unseen_hard(self, users, m, seed=0, first=0, *, scores=False, draws=False, sampling="uniform", mass=False):
         """int32 [len(users)]: for each row, the best-scoring of the m items sample_unseen(users, m, seed, first) draws for
         it, under the factors as they are now (mfsgd_sample_unseen_hard: drawn, scored and picked on the device, nothing
         per candidate comes down).  The score is predict's; equal scores go to the earlier draw, a NaN score loses to
         every number; -1 for a user who has seen every item.  scores=True adds float32 [len(users)], each pick's score
         (NaN with -1); draws=True adds int32 [len(users)], each pick's position d in its row of draws (-1 with -1); with
-        either the result is a tuple (items, scores, draws) without what was not asked for."""
+        either the result is a tuple (items, scores, draws) without what was not asked for.
+        sampling="weighted": the candidates are sample_unseen_weighted(users, m, seed, first)'s instead, drawn in
+        proportion to the item weights the handle has (mfsgd_sample_unseen_hard_weighted); -1 for a user whose unseen
+        items all weigh nothing.  mass=True (weighted only: a ValueError otherwise) adds int64 [len(users)], each row's
+        unseen weight, at the end of the tuple."""
+        weighted = self._sampling_mass(sampling, mass)
         uu = _users(users)
         items = np.empty(uu.size, np.int32)
         sc = np.empty(uu.size, np.float32) if scores else None
         dr = np.empty(uu.size, np.int32) if draws else None
-        self._check(self._lib.mfsgd_sample_unseen_hard(self._handle(), _p(uu, C.c_int32), uu.size, int(m), int(seed), int(first),
-                                                       _p(items, C.c_int32), None if sc is None else _p(sc, C.c_float),
-                                                       None if dr is None else _p(dr, C.c_int32)))
-        return _asked((items, True), (sc, scores), (dr, draws))
+        ms = np.zeros(uu.size, np.int64) if mass else None
+        args = (self._handle(), _p(uu, C.c_int32), uu.size, int(m), int(seed), int(first), _p(items, C.c_int32),
+                None if sc is None else _p(sc, C.c_float), None if dr is None else _p(dr, C.c_int32))
+        if weighted:
+            self._check(self._lib.mfsgd_sample_unseen_hard_weighted(*args, None if ms is None else _p(ms, C.c_int64)))
+        else:
+            self._check(self._lib.mfsgd_sample_unseen_hard(*args))
+        return _asked((items, True), (sc, scores), (dr, draws), (ms, mass))
 
-    def sample_unseen_violating(self, users, items, m, margin=1.0, seed=0, first=0, *, draws=False, margins=False, ranks=False):
+    def sample_unseen_violating(self, users, items, m, margin=1.0, seed=0, first=0, *, draws=False, margins=False, ranks=False,
+                                sampling="uniform", mass=False):
         """int32 [len(users)]: for each row, the first of the m items sample_unseen(users, m, seed, first) draws for it
         that is not the row's positive items[x] and violates the margin against it, dot(p, q_pos) - dot(p, q_cand) <
         margin, under the factors as they are now (mfsgd_sample_unseen_violating: drawn, scored and picked on the device,
@@ -788,18 +835,26 @@ class MatrixFactorizationSGD:
         position d (m where no candidate violates, -1 where nothing is unseen); margins=True adds float32, the pick's
         difference (NaN with -1): what partial_fit_pairwise reports as its margin; ranks=True adds int32, the estimate
         max(1, unseen items // (d + 1)) of how many unseen items violate (0 with -1): what warp_weights takes.  With
-        any of them the result is a tuple (items, draws, margins, ranks) without what was not asked for."""
+        any of them the result is a tuple (items, draws, margins, ranks) without what was not asked for.
+        sampling="weighted": the candidates are sample_unseen_weighted(users, m, seed, first)'s instead
+        (mfsgd_sample_unseen_violating_weighted); -1, and a draw of -1, for a user whose unseen items all weigh nothing;
+        the rank still scales by the number of unseen items.  mass=True (weighted only: a ValueError otherwise) adds
+        int64 [len(users)], each row's unseen weight, at the end of the tuple."""
+        weighted = self._sampling_mass(sampling, mass)
         uu, ii = _pairs(np.atleast_1d(users), np.atleast_1d(items), "users and items")
         out = np.empty(uu.size, np.int32)
         dr = np.empty(uu.size, np.int32) if draws else None
         mg = np.empty(uu.size, np.float32) if margins else None
         rk = np.empty(uu.size, np.int32) if ranks else None
-        self._check(self._lib.mfsgd_sample_unseen_violating(self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32), uu.size, int(m),
-                                                            float(margin), int(seed), int(first), _p(out, C.c_int32),
-                                                            None if dr is None else _p(dr, C.c_int32),
-                                                            None if mg is None else _p(mg, C.c_float),
-                                                            None if rk is None else _p(rk, C.c_int32)))
-        return _asked((out, True), (dr, draws), (mg, margins), (rk, ranks))
+        ms = np.zeros(uu.size, np.int64) if mass else None
+        args = (self._handle(), _p(uu, C.c_int32), _p(ii, C.c_int32), uu.size, int(m), float(margin), int(seed), int(first),
+                _p(out, C.c_int32), None if dr is None else _p(dr, C.c_int32), None if mg is None else _p(mg, C.c_float),
+                None if rk is None else _p(rk, C.c_int32))
+        if weighted:
+            self._check(self._lib.mfsgd_sample_unseen_violating_weighted(*args, None if ms is None else _p(ms, C.c_int64)))
+        else:
+            self._check(self._lib.mfsgd_sample_unseen_violating(*args))
+        return _asked((out, True), (dr, draws), (mg, margins), (rk, ranks), (ms, mass))
 
     def fit_implicit(self, u, i, epochs, negatives=4, *, seed=0, pos=1.0, neg=0.0, first_epoch=0, rmse=True, sampling="uniform"):
         """Trains on one-class data (clicks, plays, purchases): (u[x], i[x]) are the positives, duplicates allowed, and
@@ -882,7 +937,7 @@ class MatrixFactorizationSGD:
         return self._fold_in(self._lib.mfsgd_fold_in_items, row_ptr, users, ratings, epochs, init, seed, "users")
 
     def fold_in_pairwise(self, row_ptr, items, epochs, *, candidates=1, init=None, seed=None, draw_seed=0, first=0,
-                         margins=False, negatives=False):
+                         margins=False, negatives=False, sampling="uniform"):
         """Rows [n_new, k] for users that are not in a model trained by fit_bpr or fit_warp, from their positives alone
         (mfsgd_fold_in_users_pairwise): new user x owns the positives items[row_ptr[x] .. row_ptr[x + 1]) (CSR), and
         `epochs` passes of the BPR step run over them against the model's item factors, which stay fixed.  Every step
@@ -892,7 +947,12 @@ class MatrixFactorizationSGD:
         [row_ptr[-1] * epochs], each step's margin before it; negatives=True adds int32 of that shape, each step's
         negative; with either the result is a tuple (rows, margins, negatives) without what was not asked for.  A user
         who names every item takes no step (NaN and -1).  The model is not modified; the rows feed recommend_rows,
-        rank_items_rows and add_users."""
+        rank_items_rows and add_users.
+        sampling="weighted": the draws are sample_unseen_weighted's instead, in proportion to the item weights the
+        handle has (mfsgd_fold_in_users_pairwise_weighted) -- the objective of a model trained with weighted negatives;
+        a user who names every item of positive weight takes no step."""
+        call = (self._lib.mfsgd_fold_in_users_pairwise_weighted if self._sampling(sampling)
+                else self._lib.mfsgd_fold_in_users_pairwise)
         rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
         ii = _i32(items)
         if rp.ndim != 1 or rp.size < 1:
@@ -910,11 +970,9 @@ class MatrixFactorizationSGD:
         rows = np.empty((n_new, self.k), np.float32)
         mg = np.empty(steps, np.float32) if margins else None
         ng = np.empty(steps, np.int32) if negatives else None
-        self._check(self._lib.mfsgd_fold_in_users_pairwise(self._handle(), n_new, _p(rp, C.c_int64), _p(ii, C.c_int32), int(epochs),
-                                                           int(candidates), ip, self.seed if seed is None else int(seed),
-                                                           int(draw_seed), int(first), _p(rows, C.c_float),
-                                                           None if mg is None else _p(mg, C.c_float),
-                                                           None if ng is None else _p(ng, C.c_int32)))
+        self._check(call(self._handle(), n_new, _p(rp, C.c_int64), _p(ii, C.c_int32), int(epochs), int(candidates), ip,
+                         self.seed if seed is None else int(seed), int(draw_seed), int(first), _p(rows, C.c_float),
+                         None if mg is None else _p(mg, C.c_float), None if ng is None else _p(ng, C.c_int32)))
         return _asked((rows, True), (mg, margins), (ng, negatives))
 
     # -- growing a live model (include/mfsgd.h, "growing a live model") -------------
