@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver; + mfsgd_set_validation, mfsgd_validation_size, mfsgd_validation_rmse, mfsgd_rmse_pairs, mfsgd_train_early_stop; + mfsgd_row_inv_norms, mfsgd_similar_items, mfsgd_similar_users, mfsgd_similar_rows; + mfsgd_online_levels, mfsgd_apply_ratings; + mfsgd_fold_in_items, mfsgd_append_users, mfsgd_append_items, mfsgd_reserve_rows, mfsgd_get_capacity; + mfsgd_recommend_among, mfsgd_recommend_rows_among, mfsgd_debug_serve_seconds; + mfsgd_set_seen, mfsgd_mark_seen, mfsgd_clear_seen, mfsgd_seen_size, mfsgd_get_seen, mfsgd_recommend_unseen, mfsgd_recommend_unseen_among, mfsgd_rank_items_unseen, mfsgd_evaluate_ranking_unseen; + mfsgd_sample_unseen; + mfsgd_triple_levels, mfsgd_apply_triples, mfsgd_bpr_weights; + mfsgd_sample_unseen_hard; + mfsgd_sample_unseen_violating, mfsgd_apply_triples_weighted, mfsgd_warp_weights; + mfsgd_fold_in_users_pairwise; + mfsgd_sample_unseen_hard_weighted, mfsgd_sample_unseen_violating_weighted, mfsgd_fold_in_users_pairwise_weighted (additions: no existing call changed) */
+#define MFSGD_ABI_VERSION 3 /* 3 (round 3): + mfsgd_part_settle, mfsgd_dsgd_plan_ex, mfsgd_dsgd_stats; solo-record word order in the debug arrays; + mfsgd_recommend_excluding, mfsgd_fold_in_users, mfsgd_recommend_rows; + mfsgd_rank_items, mfsgd_rank_items_rows, mfsgd_ranking_metrics_from_ranks, mfsgd_evaluate_ranking; + mfsgd_set_hyper, mfsgd_get_hyper, mfsgd_train_schedule, mfsgd_train_bold_driver; + mfsgd_set_validation, mfsgd_validation_size, mfsgd_validation_rmse, mfsgd_rmse_pairs, mfsgd_train_early_stop; + mfsgd_row_inv_norms, mfsgd_similar_items, mfsgd_similar_users, mfsgd_similar_rows; + mfsgd_online_levels, mfsgd_apply_ratings; + mfsgd_fold_in_items, mfsgd_append_users, mfsgd_append_items, mfsgd_reserve_rows, mfsgd_get_capacity; + mfsgd_recommend_among, mfsgd_recommend_rows_among, mfsgd_debug_serve_seconds; + mfsgd_set_seen, mfsgd_mark_seen, mfsgd_clear_seen, mfsgd_seen_size, mfsgd_get_seen, mfsgd_recommend_unseen, mfsgd_recommend_unseen_among, mfsgd_rank_items_unseen, mfsgd_evaluate_ranking_unseen; + mfsgd_sample_unseen; + mfsgd_triple_levels, mfsgd_apply_triples, mfsgd_bpr_weights; + mfsgd_sample_unseen_hard; + mfsgd_sample_unseen_violating, mfsgd_apply_triples_weighted, mfsgd_warp_weights; + mfsgd_fold_in_users_pairwise; + mfsgd_sample_unseen_hard_weighted, mfsgd_sample_unseen_violating_weighted, mfsgd_fold_in_users_pairwise_weighted; + mfsgd_recommend_users, mfsgd_recommend_users_among, mfsgd_recommend_users_unseen, mfsgd_recommend_users_unseen_among, mfsgd_recommend_users_rows, mfsgd_recommend_users_rows_among (additions: no existing call changed) */
 
 typedef enum mfsgd_status {
     MFSGD_OK = 0,
@@ -623,6 +623,67 @@ int mfsgd_recommend_unseen_among(mfsgd_handle* h, const int32_t* users, int32_t 
 int mfsgd_rank_items_unseen(mfsgd_handle* h, const int32_t* users, const int32_t* items, int64_t n, int32_t* out_rank);
 int mfsgd_evaluate_ranking_unseen(mfsgd_handle* h, const int32_t* users, const int32_t* items, int64_t n, int32_t topn,
                                   mfsgd_ranking_metrics* out, int32_t* out_rank /* nullable */);
+
+/* ---- item-side serving: the best users for an item ----------------------------------------------------------------
+ * "Which users are the best audience for this item": the mfsgd_recommend family with the two sides exchanged.  Row b of
+ * the output holds the topn users with the largest dot(P[u], Q[items[b]]) -- the canonical dot is bitwise symmetric in
+ * its two rows, so these are the bits mfsgd_predict(u, items[b]) returns -- best first; scores that compare equal as
+ * floats (-0.0 == +0.0) go to the smaller USER index; NaN scores are handled exactly as mfsgd_recommend_excluding
+ * handles them; a row with fewer than topn eligible users is padded with user -1 and score NaN.  out_users /
+ * out_scores: n x topn, row-major.  items may repeat and come in any order.
+ * Exclusion pairs keep the orientation they have everywhere else in the library, (user, item): a caller passes the
+ * same excl_u / excl_i arrays it passes to mfsgd_recommend_excluding, and user excl_u[x] is never returned in a row
+ * whose item is excl_i[x].  Pairs of items nobody asked about are ignored; duplicates are allowed; n_excl == 0 (the
+ * pointers may then be NULL) excludes nothing.  Every pair is range-checked under the current counts (0 <= excl_u <
+ * n_users, 0 <= excl_i < n_items) before any device work.
+ * The _unseen calls exclude user u from item j's row when the handle's seen-item index holds (u, j): the output is
+ * byte for byte that of the pair call given the index's pairs.  A handle without an index is MFSGD_ERR_STATE ("no seen
+ * set"); an empty index excludes nothing and builds nothing.  The index is CSR by user and nothing by item is kept in
+ * the handle (mfsgd_set_seen, mfsgd_mark_seen, mfsgd_append_users and mfsgd_reserve_rows are what they were), so each
+ * such call reads the whole index on the device (csrc/audience.hip): with D pairs in the index, two passes of 4 D
+ * bytes each (one counts the pairs of requested items, one writes them), a search of log2(n_users) steps through the
+ * offsets per kept pair to find its user, and 20 bytes of staging per kept pair, which are then sorted into one user
+ * list per distinct requested item exactly as a caller's pairs are.  More than 2^32 - 1 kept pairs are refused, as for
+ * a caller's list, here after that count.
+ * Candidates ("the best 100 of this segment"): cand_users follows mfsgd_recommend_among's rules -- cand_ptr == NULL,
+ * one list shared by every request row; otherwise CSR over the request rows (cand_ptr[0] == 0, non-decreasing,
+ * cand_ptr[n] == n_cand).  Lists may be unsorted, repeat users and be empty; a list that names every user gives the
+ * unrestricted call's row bit for bit; n_cand == 0 gives rows of padding without device work.  Users appended with
+ * mfsgd_append_users are valid candidates; indices between count and capacity are not.
+ * The _rows calls: "item b" is rows[b] (n_rows x k, dense: for instance what mfsgd_fold_in_items returned -- "who
+ * should be shown this new item"); every row is answered, in order, and excl_row / cand_ptr index the rows.
+ * Checks, all before any device work, in mfsgd_recommend_excluding's / mfsgd_recommend_among's order, the messages
+ * starting with the call's own name ("recommend_users: ", "recommend_users_among: ", "recommend_users_unseen: ",
+ * "recommend_users_unseen_among: ", "recommend_users_rows: ", "recommend_users_rows_among: "): MFSGD_ERR_INVALID_ARG for
+ * a negative n or n_excl, topn < 1 or a null array that is needed ("bad argument"); then MFSGD_ERR_STATE for
+ * n_parts != 1 and for "no seen set"; then MFSGD_ERR_INVALID_ARG for topn > n_users ("topn exceeds the number of
+ * users"), "item X out of range" for a requested item, the candidate checks ("n_cand is negative", "cand_users is
+ * null", the three cand_ptr rules, "candidate X out of range" against n_users, more than 2^32 - 1 candidates), "excluded
+ * pair X out of range", more than 2^32 - 1 pairs of requested items.  Then n == 0 is MFSGD_OK.  Then MFSGD_ERR_STATE for
+ * factors never initialised, set or loaded, or no Q; MFSGD_ERR_NO_DEVICE for a valid call with work to do and no usable
+ * GPU.
+ * Nothing in the handle is modified: not the factors, the index, its mass table, the item weights, a schedule or a
+ * cached graph.  Every list and all staging is freed before return, on every path -- mfsgd_debug_device_bytes is the
+ * same before and after.  mfsgd_debug_serve_seconds reports the two halves as for mfsgd_recommend; the lists half
+ * covers the candidate lists, the exclusion lists and the read of the index.  Selection is mfsgd_recommend's, kernels
+ * and all (csrc/recommend.hip), with P in the place of Q.
+ * Not done here: ranks of users (a rank_users), a by-item index kept in the handle, multi-partition handles.          */
+int mfsgd_recommend_users(mfsgd_handle* h, const int32_t* items, int32_t n, int32_t topn, const int32_t* excl_u,
+                          const int32_t* excl_i, int64_t n_excl, int32_t* out_users, float* out_scores);
+int mfsgd_recommend_users_among(mfsgd_handle* h, const int32_t* items, int32_t n, int32_t topn, const int64_t* cand_ptr,
+                                const int32_t* cand_users, int64_t n_cand, const int32_t* excl_u, const int32_t* excl_i,
+                                int64_t n_excl, int32_t* out_users, float* out_scores);
+int mfsgd_recommend_users_unseen(mfsgd_handle* h, const int32_t* items, int32_t n, int32_t topn, int32_t* out_users,
+                                 float* out_scores);
+int mfsgd_recommend_users_unseen_among(mfsgd_handle* h, const int32_t* items, int32_t n, int32_t topn,
+                                       const int64_t* cand_ptr, const int32_t* cand_users, int64_t n_cand,
+                                       int32_t* out_users, float* out_scores);
+int mfsgd_recommend_users_rows(mfsgd_handle* h, const float* rows, int32_t n_rows, int32_t topn, const int32_t* excl_row,
+                               const int32_t* excl_user, int64_t n_excl, int32_t* out_users, float* out_scores);
+int mfsgd_recommend_users_rows_among(mfsgd_handle* h, const float* rows, int32_t n_rows, int32_t topn,
+                                     const int64_t* cand_ptr, const int32_t* cand_users, int64_t n_cand,
+                                     const int32_t* excl_row, const int32_t* excl_user, int64_t n_excl, int32_t* out_users,
+                                     float* out_scores);
 
 /* ---- similar items and users: cosine nearest neighbours among the rows of Q, or of P --------------------------------
  * The arithmetic, all fp32, round to nearest even, subnormals kept, nothing contracted; dot is

@@ -157,6 +157,14 @@ SIGNATURES = {
                                                          _i32p, _i32p, _f32p, _i32p, _i64p]),
     "mfsgd_recommend_unseen": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i32p, _f32p]),
     "mfsgd_recommend_unseen_among": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i64p, _i32p, C.c_int64, _i32p, _f32p]),
+    "mfsgd_recommend_users": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i32p, _i32p, C.c_int64, _i32p, _f32p]),
+    "mfsgd_recommend_users_among": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i64p, _i32p, C.c_int64, _i32p, _i32p, C.c_int64,
+                                              _i32p, _f32p]),
+    "mfsgd_recommend_users_unseen": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i32p, _f32p]),
+    "mfsgd_recommend_users_unseen_among": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i64p, _i32p, C.c_int64, _i32p, _f32p]),
+    "mfsgd_recommend_users_rows": (C.c_int, [_H, _f32p, C.c_int32, C.c_int32, _i32p, _i32p, C.c_int64, _i32p, _f32p]),
+    "mfsgd_recommend_users_rows_among": (C.c_int, [_H, _f32p, C.c_int32, C.c_int32, _i64p, _i32p, C.c_int64, _i32p, _i32p,
+                                                   C.c_int64, _i32p, _f32p]),
     "mfsgd_rank_items_unseen": (C.c_int, [_H, _i32p, _i32p, C.c_int64, _i32p]),
     "mfsgd_evaluate_ranking_unseen": (C.c_int, [_H, _i32p, _i32p, C.c_int64, C.c_int32, C.POINTER(RankingMetrics), _i32p]),
     "mfsgd_row_inv_norms": (C.c_int, [_H, C.c_int32, _f32p]),

@@ -1,6 +1,6 @@
 // kernels.hpp -- host-callable launchers of every kernel unit: epoch.hip, cells.hip, kernels.hip, foldin.hip,
-// foldin_pairwise.hip, online.hip, pairwise.hip, rehyper.hip, recommend.hip, rank.hip, seen.hip, sample.hip, pick.hip, similar.hip, validate.hip
-// and grow.hip.
+// foldin_pairwise.hip, online.hip, pairwise.hip, rehyper.hip, recommend.hip, rank.hip, seen.hip, audience.hip, sample.hip, pick.hip,
+// similar.hip, validate.hip and grow.hip.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -235,6 +235,14 @@ hipError_t seen_unseen_mass(const long long* off, const int32_t* items, int64_t 
                             int32_t n_w, unsigned long long* G, unsigned long long* mass, DevBuf& temp, hipStream_t st);
 // counts[i] += the number of lists that hold item i (counts: one zeroed entry per item of the model).
 hipError_t seen_item_counts(const int32_t* items, int64_t total, unsigned long long* counts, hipStream_t st);
+
+// audience.hip.  The index {off, items} (`total` pairs; off[0 .. n_users] is read) by item: for every pair whose item has
+// a slot (slot_of_item[n_items], -1 for the rest) the key slot << 32 | user is appended to keys[*count ...], in no
+// particular order (count starts at 0; at most cap are written).  keys == nullptr: *count receives their number alone.
+// recommend_excl_lists then makes the lists of them, one ascending user list per slot.
+hipError_t seen_audience_keys(const int32_t* slot_of_item, int32_t n_items, const long long* off, const int32_t* items,
+                              int32_t n_users, int64_t total, unsigned long long* keys, unsigned long long* count, int64_t cap,
+                              hipStream_t st);
 
 // sample.hip.  Uniform draws among the items a user has not seen (include/mfsgd.h, mfsgd_sample_unseen): out[x], x <
 // n_draws, is draw x % m of row x / m of `users` (every one a user of the index {off, items}; off == nullptr: an index

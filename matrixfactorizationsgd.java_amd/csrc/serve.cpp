@@ -12,10 +12,13 @@
 
 namespace mfsgd {
 
-// How a serving call speaks of itself and of the users it was given, in the messages the two cores share.
+// How a serving call speaks of itself and of the users it was given, in the messages the two cores share; and (the
+// top-N calls) of one request row and of the side that is scanned, which are the other way round for recommend_users.
 struct ServeName {
     const char* call;
     const char* whose;
+    const char* row = "user";
+    const char* scanned = "items";
 };
 constexpr ServeName kRecommend{"recommend", "the requested users"}, kRank{"rank_items", "the users asked about"};
 constexpr ServeName kAmong{"recommend_among", "the requested users"}, kRowsAmong{"recommend_rows_among", "the rows"};
@@ -23,9 +26,19 @@ constexpr ServeName kAmong{"recommend_among", "the requested users"}, kRowsAmong
 constexpr ServeName kUnseen{"recommend_unseen", "the requested users"}, kUnseenAmong{"recommend_unseen_among", "the requested users"};
 constexpr ServeName kRankUnseen{"rank_items_unseen", "the users asked about"};
 constexpr ServeName kEvaluateUnseen{"evaluate_ranking_unseen", "the users asked about"};
+// ... and the item-side calls: the request rows are items (or item rows of the caller's), the users are scanned
+constexpr ServeName kUsers{"recommend_users", "the requested items", "item", "users"};
+constexpr ServeName kUsersAmong{"recommend_users_among", "the requested items", "item", "users"};
+constexpr ServeName kUsersUnseen{"recommend_users_unseen", "the requested items", "item", "users"};
+constexpr ServeName kUsersUnseenAmong{"recommend_users_unseen_among", "the requested items", "item", "users"};
+constexpr ServeName kUsersRows{"recommend_users_rows", "the rows", "item", "users"};
+constexpr ServeName kUsersRowsAmong{"recommend_users_rows_among", "the rows", "item", "users"};
 
 // What a serving call leaves out: nothing, the pairs (u[x], i[x]) of a list of the caller's, or (the _unseen calls) what
 // the handle's seen-item index holds, which is read where it lies -- nothing is built, uploaded or looped over for it.
+// In the cores u[x] is a row of the request side and i[x] one of the scanned side: an item-side call hands its
+// (user, item) arrays over exchanged, and from there on a pair list is a pair list.  The index, CSR by user, cannot
+// be read where it lies for an item: the lists of the requested items are made of it per call (audience.hip).
 struct Exclusions {
     enum { kNone, kPairs, kSeen } from = kNone;
     const int32_t *u = nullptr, *i = nullptr;
@@ -42,6 +55,17 @@ struct Candidates {
     int64_t n;
 };
 
+// The two sides of a top-N call (recommend_core): `own` is the model's matrix the request rows index where the caller
+// brings no rows, `scanned` the one whose rows are scored and returned, all cfg.*n_scanned of them.
+struct TopnSides {
+    const DevArray<float> mfsgd_handle::*own;
+    const DevArray<float> mfsgd_handle::*scanned;
+    int32_t mfsgd_config::*n_scanned;
+};
+// P's users against Q's items; and the item-side calls (recommend_users): Q's items against P's users
+constexpr TopnSides kItemsOfUsers{&mfsgd_handle::dP, &mfsgd_handle::dQ, &mfsgd_config::n_items};
+constexpr TopnSides kUsersOfItems{&mfsgd_handle::dQ, &mfsgd_handle::dP, &mfsgd_config::n_users};
+
 // A top-N call: "user j" is row j of a matrix of n_rows rows -- the model's P (host_rows == nullptr), or host_rows
 // (n_rows x k, dense) -- and `users` names the n_users rows asked for.  cand != nullptr: among the candidates only.
 struct TopnRequest {
@@ -53,6 +77,8 @@ struct TopnRequest {
     Exclusions excl;
     int32_t* out_items = nullptr;
     float* out_scores = nullptr;
+    TopnSides sides = kItemsOfUsers;  // (recommend_core; kUsersOfItems: everything above reads with the two words exchanged)
+    bool for_items() const { return sides.scanned == &mfsgd_handle::dP; }
 };
 
 // A rank call over the same kind of row matrix: the n pairs (users[x], items[x]), and where their ranks go.
@@ -72,10 +98,11 @@ static std::vector<int32_t> all_rows(int32_t n) {
     return all;
 }
 
-// The row matrix of a serving call on the device: the model's P, or host_rows (n_rows x k, dense), which goes up into
-// a kp-padded temporary (`buf`) for the length of the call.
-static int upload_rows(mfsgd_handle* h, const float* host_rows, int32_t n_rows, DevArray<float>& buf, const float** rows) {
-    *rows = h->dP.data();
+// The row matrix of a serving call on the device: the model's P (`own`: or its Q, for an item-side call), or host_rows
+// (n_rows x k, dense), which goes up into a kp-padded temporary (`buf`) for the length of the call.
+static int upload_rows(mfsgd_handle* h, const float* host_rows, int32_t n_rows, DevArray<float>& buf, const float** rows,
+                       const DevArray<float> mfsgd_handle::*own = &mfsgd_handle::dP) {
+    *rows = (h->*own).data();
     if (!host_rows) return MFSGD_OK;
     const int k = h->cfg.k, kp = h->geo.kp;
     std::vector<float> padded((size_t)n_rows * kp, 0.0f);
@@ -85,12 +112,13 @@ static int upload_rows(mfsgd_handle* h, const float* host_rows, int32_t n_rows, 
     return rc;
 }
 
-// Range check of the exclusion pairs, and *kept = how many of them belong to a user that has a slot.
+// Range check of the exclusion pairs (n_scanned: the rows of the scanned side, the model's items unless the call is an
+// item-side one), and *kept = how many of them belong to a user that has a slot.
 static int count_exclusions(const mfsgd_handle* h, const ServeName& what, const std::vector<int32_t>& slot_of_user, int32_t n_rows,
-                            const Exclusions& excl, int64_t* kept) {
+                            int32_t n_scanned, const Exclusions& excl, int64_t* kept) {
     *kept = 0;
     for (int64_t x0 = 0; x0 < excl.n; x0 += 4096) {  // (block by block: the pairs are read from memory once)
-        const int64_t x1 = std::min(excl.n, x0 + 4096), x = first_outside(excl.u + x0, n_rows, excl.i + x0, h->cfg.n_items, x1 - x0);
+        const int64_t x1 = std::min(excl.n, x0 + 4096), x = first_outside(excl.u + x0, n_rows, excl.i + x0, n_scanned, x1 - x0);
         if (x >= 0)
             return fail(h, MFSGD_ERR_INVALID_ARG, std::string(what.call) + ": excluded pair " + std::to_string(x0 + x) + " out of range");
         for (int64_t y = x0; y < x1; ++y) *kept += slot_of_user[(size_t)excl.u[y]] >= 0 ? 1 : 0;
@@ -106,6 +134,38 @@ struct ExclLists {
     DevArray<long long> off;
 };
 
+// The keys of one call's exclusion lists on their way there: slot << 32 | id of the scanned side, appended in no
+// particular order, then sorted through keys_tmp.  count: [0] appended keys (u64), then the distinct ones (u32).
+struct ExclKeys {
+    DevArray<unsigned long long> keys, keys_tmp, count;
+};
+
+// The slot table on the device and the counter (the caller zeroes it before each pass that appends or counts keys).
+static int excl_keys_begin(mfsgd_handle* h, const Slots& slots, ExclLists& lists, ExclKeys& k) {
+    const int rc = upload(h, lists.slot, slots.slot_of_row);
+    return rc ? rc : dev_alloc(h, k.count, 2);
+}
+
+// Room for `kept` keys and for the lists they become: 20 bytes per kept pair (two key buffers and the lists' ids), and
+// an offset per slot.
+static int excl_keys_alloc(mfsgd_handle* h, const Slots& slots, int64_t kept, ExclLists& lists, ExclKeys& k) {
+    int rc;
+    if ((rc = dev_alloc(h, k.keys, (size_t)kept)) || (rc = dev_alloc(h, k.keys_tmp, (size_t)kept))) return rc;
+    if ((rc = dev_alloc(h, lists.off, (size_t)slots.n() + 1)) || (rc = dev_alloc(h, lists.items, (size_t)kept))) return rc;
+    return MFSGD_OK;
+}
+
+// The `kept` appended keys sorted and made distinct into one list per slot (recommend.hip), and `ex` pointing into
+// `lists`, which is the caller's.  Ends in a synchronise.
+static hipError_t excl_keys_to_lists(mfsgd_handle* h, const Slots& slots, int64_t kept, ExclKeys& k, ExclLists& lists, DevBuf& temp,
+                                     RecommendExcl& ex) {
+    hipError_t e = recommend_excl_lists(k.keys.data(), k.keys_tmp.data(), kept, slots.n(), reinterpret_cast<unsigned*>(k.count.data() + 1),
+                                        lists.off.data(), lists.items.data(), temp, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) ex = RecommendExcl{lists.slot.data(), lists.off.data(), lists.items.data()};
+    return e;
+}
+
 // Exclusion lists of one recommend call on the device: the pairs go up in chunks of bounded size, those of requested
 // users are kept (slot << 32 | item), then sorted and made distinct into one list per slot (recommend.hip).
 // Scratch lives as long as this function; `ex` points into `lists`, which is the caller's.
@@ -116,25 +176,51 @@ static int exclusions_to_device(mfsgd_handle* h, const ServeName& what, const Sl
     const std::string prefix = std::string(what.call) + ": exclusion lists: ";
     auto bad = [h, &prefix](hipError_t e) { return serve_fail(h, prefix.c_str(), e); };
     DevArray<int32_t> cu, ci;
-    DevArray<unsigned long long> keys, keys_tmp, count;
+    ExclKeys k;
     const int64_t chunk = std::min(excl.n, kExclChunk);
     int rc;
-    if ((rc = upload(h, lists.slot, slots.slot_of_row))) return rc;
+    if ((rc = excl_keys_begin(h, slots, lists, k)) || (rc = excl_keys_alloc(h, slots, kept, lists, k))) return rc;
     if ((rc = dev_alloc(h, cu, (size_t)chunk)) || (rc = dev_alloc(h, ci, (size_t)chunk))) return rc;
-    if ((rc = dev_alloc(h, keys, (size_t)kept)) || (rc = dev_alloc(h, keys_tmp, (size_t)kept))) return rc;
-    if ((rc = dev_alloc(h, count, 2))) return rc;  // [0] appended pairs (u64), then distinct ones (u32)
-    if ((rc = dev_alloc(h, lists.off, (size_t)slots.n() + 1)) || (rc = dev_alloc(h, lists.items, (size_t)kept))) return rc;
-    HIPCHK_OR(bad, hipMemsetAsync(count.data(), 0, 16, h->stream));
+    HIPCHK_OR(bad, hipMemsetAsync(k.count.data(), 0, 16, h->stream));
     for (int64_t x0 = 0; x0 < excl.n; x0 += chunk) {
         const int64_t c = std::min(chunk, excl.n - x0);
         HIPCHK_OR(bad, copy_up(cu, excl.u + x0, (size_t)c, h->stream));
         HIPCHK_OR(bad, copy_up(ci, excl.i + x0, (size_t)c, h->stream));
-        HIPCHK_OR(bad, recommend_excl_filter(lists.slot.data(), cu.data(), ci.data(), c, keys.data(), count.data(), kept, h->stream));
+        HIPCHK_OR(bad, recommend_excl_filter(lists.slot.data(), cu.data(), ci.data(), c, k.keys.data(), k.count.data(), kept, h->stream));
     }
-    HIPCHK_OR(bad, recommend_excl_lists(keys.data(), keys_tmp.data(), kept, slots.n(), reinterpret_cast<unsigned*>(count.data() + 1),
-                                        lists.off.data(), lists.items.data(), temp, h->stream));
+    HIPCHK_OR(bad, excl_keys_to_lists(h, slots, kept, k, lists, temp, ex));
+    return MFSGD_OK;
+}
+
+// The same lists for an item-side _unseen call (slots: of the requested items), made of the seen-item index, which is
+// CSR by user and cannot be read where it lies for an item: one pass over its pairs counts those of requested items
+// -- how many are kept is not known before -- and a second writes them as slot << 32 | user (audience.hip); from there
+// they are a caller's pairs.  No pair kept: nothing is built and ex stays empty.  The index's lists are read up to the
+// user count (the offsets above it hold the total).  mfsgd_mark_seen keeps an index below 2^32 pairs, so the cap of a
+// pair list cannot be met here; it is asked all the same, the lists' counters being 32 bits wide.
+static int audience_to_device(mfsgd_handle* h, const ServeName& what, const Slots& slots, const Seen& seen, ExclLists& lists,
+                              DevBuf& temp, RecommendExcl& ex) {
+    const std::string prefix = std::string(what.call) + ": exclusion lists: ";
+    auto bad = [h, &prefix](hipError_t e) { return serve_fail(h, prefix.c_str(), e); };
+    ExclKeys k;
+    auto pass = [&](unsigned long long* to, int64_t cap) {
+        return seen_audience_keys(lists.slot.data(), (int32_t)slots.slot_of_row.size(), seen.off.data(), seen.items.data(),
+                                  std::min(h->cfg.n_users, seen.capacity), seen.n, to, k.count.data(), cap, h->stream);
+    };
+    unsigned long long kept = 0;
+    int rc;
+    if ((rc = excl_keys_begin(h, slots, lists, k))) return rc;
+    HIPCHK_OR(bad, hipMemsetAsync(k.count.data(), 0, 16, h->stream));
+    HIPCHK_OR(bad, pass(nullptr, 0));
+    HIPCHK_OR(bad, copy_down(&kept, k.count, 1, h->stream));
     HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
-    ex = RecommendExcl{lists.slot.data(), lists.off.data(), lists.items.data()};
+    if (kept > (unsigned long long)UINT32_MAX)
+        return fail(h, MFSGD_ERR_INVALID_ARG, std::string(what.call) + ": more than 2^32 - 1 excluded pairs of " + what.whose);
+    if (kept == 0) return MFSGD_OK;
+    if ((rc = excl_keys_alloc(h, slots, (int64_t)kept, lists, k))) return rc;
+    HIPCHK_OR(bad, hipMemsetAsync(k.count.data(), 0, 16, h->stream));  // (the counter counts again)
+    HIPCHK_OR(bad, pass(k.keys.data(), (int64_t)kept));
+    HIPCHK_OR(bad, excl_keys_to_lists(h, slots, (int64_t)kept, k, lists, temp, ex));
     return MFSGD_OK;
 }
 
@@ -247,6 +333,8 @@ static int topn_batches(mfsgd_handle* h, const char* prefix, TopnJob job, const 
 // Body of the recommend calls.  `what` is how the messages of the argument checks name the call (both recommend calls
 // say "recommend"), `own` the call's own name, which its state errors carry.  The candidates (the among calls) are
 // checked after the users and before the exclusion pairs.
+// The same body serves the item-side calls (recommend_users): req names the two matrices and `what` the words, so
+// "users" below are the request rows of either side and "items" the rows that are scanned.
 static int recommend_core(mfsgd_handle* h, const ServeName& what, const char* own, const TopnRequest& req) {
     const std::string call = std::string(what.call) + ": ";
     const Exclusions& excl = req.excl;
@@ -257,12 +345,13 @@ static int recommend_core(mfsgd_handle* h, const ServeName& what, const char* ow
         return fail(h, MFSGD_ERR_INVALID_ARG, call + "bad argument");
     if (h->n_parts != 1) return fail(h, MFSGD_ERR_STATE, call + "single-partition handles only");
     if (excl.from == Exclusions::kSeen && !h->seen.present) return fail(h, MFSGD_ERR_STATE, call + "no seen set");
-    if (topn > h->cfg.n_items) return fail(h, MFSGD_ERR_INVALID_ARG, call + "topn exceeds the number of items");
+    const int32_t n_scanned = h->cfg.*req.sides.n_scanned;
+    if (topn > n_scanned) return fail(h, MFSGD_ERR_INVALID_ARG, call + "topn exceeds the number of " + what.scanned);
     int64_t x = first_outside(req.users, n_users, req.n_rows);
-    if (x >= 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "user " + std::to_string(x) + " out of range");
+    if (x >= 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + what.row + " " + std::to_string(x) + " out of range");
     if (cand) {
         if (cand->n < 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "n_cand is negative");
-        if (cand->n > 0 && !cand->items) return fail(h, MFSGD_ERR_INVALID_ARG, call + "cand_items is null");
+        if (cand->n > 0 && !cand->items) return fail(h, MFSGD_ERR_INVALID_ARG, call + "cand_" + what.scanned + " is null");
         if (cand->ptr) {
             if (cand->ptr[0] != 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "cand_ptr[0] is not 0");
             for (int32_t b = 0; b < n_users; ++b)
@@ -271,7 +360,7 @@ static int recommend_core(mfsgd_handle* h, const ServeName& what, const char* ow
             if (cand->ptr[n_users] != cand->n)
                 return fail(h, MFSGD_ERR_INVALID_ARG, call + "cand_ptr ends at " + std::to_string(cand->ptr[n_users]) + ", not at n_cand");
         }
-        if ((x = first_outside(cand->items, cand->n, h->cfg.n_items)) >= 0)
+        if ((x = first_outside(cand->items, cand->n, n_scanned)) >= 0)
             return fail(h, MFSGD_ERR_INVALID_ARG, call + "candidate " + std::to_string(x) + " out of range");
         if (cand->n > (int64_t)UINT32_MAX) return fail(h, MFSGD_ERR_INVALID_ARG, call + "more than 2^32 - 1 candidates");
     }
@@ -281,7 +370,7 @@ static int recommend_core(mfsgd_handle* h, const ServeName& what, const char* ow
     int rc;
     if (excl.n > 0) {
         slots = slots_of(req.users, n_users, req.n_rows);
-        if ((rc = count_exclusions(h, what, slots.slot_of_row, req.n_rows, excl, &kept))) return rc;
+        if ((rc = count_exclusions(h, what, slots.slot_of_row, req.n_rows, n_scanned, excl, &kept))) return rc;
     }
     if (n_users == 0) return MFSGD_OK;
     if (req.host_rows && h->where == mfsgd_handle::Where::None)  // (asked here: factors_to_device wants a device first)
@@ -296,15 +385,20 @@ static int recommend_core(mfsgd_handle* h, const ServeName& what, const char* ow
     ExclLists lists;
     DevBuf temp;  // the rocPRIM scratch, bytes of no type: one for the lists and every batch, grown when one needs more
     TopnJob job;
-    if ((rc = upload_rows(h, req.host_rows, req.n_rows, d_rows, &job.P))) return rc;
-    job.Q = h->dQ.data();
-    job.n_items = h->cfg.n_items;
+    if ((rc = upload_rows(h, req.host_rows, req.n_rows, d_rows, &job.P, req.sides.own))) return rc;
+    job.Q = (h->*req.sides.scanned).data();
+    job.n_items = n_scanned;
     job.topn = topn;
     const auto t0 = std::chrono::steady_clock::now();
     CandLists cl;  // built once for all batches
     if (cand && (rc = candidates_to_device(h, what, *cand, n_users, temp, cl))) return rc;
     // the exclusion lists: built once for all batches; none when no pair belongs to a requested user, or the index is empty
-    if (excl.from == Exclusions::kSeen) job.ex = h->seen.excl();
+    // (an item-side call cannot read the index where it lies: the lists of its items are made of it, like a caller's)
+    const bool unseen = excl.from == Exclusions::kSeen;
+    const Seen* by_item = unseen && req.for_items() && h->seen.n > 0 ? &h->seen : nullptr;
+    if (unseen && !req.for_items()) job.ex = h->seen.excl();
+    if (by_item) slots = slots_of(req.users, n_users, req.n_rows);
+    if (by_item && (rc = audience_to_device(h, what, slots, *by_item, lists, temp, job.ex))) return rc;
     if (kept > 0 && (rc = exclusions_to_device(h, what, slots, excl, kept, lists, temp, job.ex))) return rc;
     const auto t1 = std::chrono::steady_clock::now();
     rc = topn_batches(h, call.c_str(), job, req, cand ? &cl : nullptr, temp);
@@ -410,7 +504,7 @@ static int rank_core(mfsgd_handle* h, const ServeName& what, const RankRequest& 
         slots.row_of_slot.swap(rows_sorted);
     }
     int64_t kept = 0;
-    int rc = count_exclusions(h, what, slots.slot_of_row, req.n_rows, excl, &kept);
+    int rc = count_exclusions(h, what, slots.slot_of_row, req.n_rows, I, excl, &kept);
     if (rc) return rc;
     if (n == 0) return MFSGD_OK;
     // (one partition is known by now, and asked about again)
@@ -918,6 +1012,65 @@ int mfsgd_recommend_unseen_among(mfsgd_handle* h, const int32_t* users, int32_t 
         const Candidates cand{cand_ptr, cand_items, n_cand};
         return recommend_core(h, kUnseenAmong, kUnseenAmong.call, {nullptr, h->cfg.n_users, users, n_users, topn, &cand,
                               Exclusions::seen(), out_items, out_scores});
+    });
+}
+
+// The item-side family: Q's rows (or item rows of the caller's) against P.  The exclusion pairs keep the library's
+// (user, item) orientation at the surface and reach the core exchanged, request side first.
+int mfsgd_recommend_users(mfsgd_handle* h, const int32_t* items, int32_t n, int32_t topn, const int32_t* excl_u,
+                          const int32_t* excl_i, int64_t n_excl, int32_t* out_users, float* out_scores) {
+    return guarded(h, kUsers.call, [&]() -> int {
+        return recommend_core(h, kUsers, kUsers.call, {nullptr, h->cfg.n_items, items, n, topn, nullptr,
+                              Exclusions::pairs(excl_i, excl_u, n_excl), out_users, out_scores, kUsersOfItems});
+    });
+}
+
+int mfsgd_recommend_users_among(mfsgd_handle* h, const int32_t* items, int32_t n, int32_t topn, const int64_t* cand_ptr,
+                                const int32_t* cand_users, int64_t n_cand, const int32_t* excl_u, const int32_t* excl_i,
+                                int64_t n_excl, int32_t* out_users, float* out_scores) {
+    return guarded(h, kUsersAmong.call, [&]() -> int {
+        const Candidates cand{cand_ptr, cand_users, n_cand};
+        return recommend_core(h, kUsersAmong, kUsersAmong.call, {nullptr, h->cfg.n_items, items, n, topn, &cand,
+                              Exclusions::pairs(excl_i, excl_u, n_excl), out_users, out_scores, kUsersOfItems});
+    });
+}
+
+int mfsgd_recommend_users_unseen(mfsgd_handle* h, const int32_t* items, int32_t n, int32_t topn, int32_t* out_users,
+                                 float* out_scores) {
+    return guarded(h, kUsersUnseen.call, [&]() -> int {
+        return recommend_core(h, kUsersUnseen, kUsersUnseen.call, {nullptr, h->cfg.n_items, items, n, topn, nullptr,
+                              Exclusions::seen(), out_users, out_scores, kUsersOfItems});
+    });
+}
+
+int mfsgd_recommend_users_unseen_among(mfsgd_handle* h, const int32_t* items, int32_t n, int32_t topn, const int64_t* cand_ptr,
+                                       const int32_t* cand_users, int64_t n_cand, int32_t* out_users, float* out_scores) {
+    return guarded(h, kUsersUnseenAmong.call, [&]() -> int {
+        const Candidates cand{cand_ptr, cand_users, n_cand};
+        return recommend_core(h, kUsersUnseenAmong, kUsersUnseenAmong.call, {nullptr, h->cfg.n_items, items, n, topn, &cand,
+                              Exclusions::seen(), out_users, out_scores, kUsersOfItems});
+    });
+}
+
+int mfsgd_recommend_users_rows(mfsgd_handle* h, const float* rows, int32_t n_rows, int32_t topn, const int32_t* excl_row,
+                               const int32_t* excl_user, int64_t n_excl, int32_t* out_users, float* out_scores) {
+    return guarded(h, kUsersRows.call, [&]() -> int {
+        if (n_rows < 0 || (n_rows > 0 && !rows)) return fail(h, MFSGD_ERR_INVALID_ARG, "recommend_users_rows: bad argument");
+        const std::vector<int32_t> all = all_rows(n_rows);
+        return recommend_core(h, kUsersRows, kUsersRows.call, {rows, n_rows, all.data(), n_rows, topn, nullptr,
+                              Exclusions::pairs(excl_row, excl_user, n_excl), out_users, out_scores, kUsersOfItems});
+    });
+}
+
+int mfsgd_recommend_users_rows_among(mfsgd_handle* h, const float* rows, int32_t n_rows, int32_t topn, const int64_t* cand_ptr,
+                                     const int32_t* cand_users, int64_t n_cand, const int32_t* excl_row,
+                                     const int32_t* excl_user, int64_t n_excl, int32_t* out_users, float* out_scores) {
+    return guarded(h, kUsersRowsAmong.call, [&]() -> int {
+        if (n_rows < 0 || (n_rows > 0 && !rows)) return fail(h, MFSGD_ERR_INVALID_ARG, "recommend_users_rows_among: bad argument");
+        const std::vector<int32_t> all = all_rows(n_rows);
+        const Candidates cand{cand_ptr, cand_users, n_cand};
+        return recommend_core(h, kUsersRowsAmong, kUsersRowsAmong.call, {rows, n_rows, all.data(), n_rows, topn, &cand,
+                              Exclusions::pairs(excl_row, excl_user, n_excl), out_users, out_scores, kUsersOfItems});
     });
 }
 

@@ -667,6 +667,39 @@ class MatrixFactorizationSGD:
                                                         _p(items, C.c_int32), _p(scores, C.c_float)))
         return items, scores
 
+    def recommend_users(self, items, topn, exclude=None, candidates=None):
+        """(users, scores), each [len(items), topn]: the best audience of each item, best first -- recommend() with the
+        two sides exchanged (mfsgd_recommend_users); the scores are the bits predict(user, item) returns, equal scores go
+        to the smaller user.  exclude = (u, i): the same (user, item) pairs recommend() takes; user u[x] is never
+        returned for item i[x], and a row with fewer than topn eligible users is padded with user -1 and score NaN.
+        exclude = "seen": the pairs of the seen-item index -- the same rows, without the list; the index is by user, so
+        each call reads all of it once on the device to find the requested items' users.
+        candidates: the users a row may return at all ("the best 100 of this segment", mfsgd_recommend_users_among), in
+        the three forms recommend() takes, the per-row forms indexing `items`.  None: every user."""
+        ii = _i32(np.atleast_1d(items))
+        seen, eu, ei = _exclusions(exclude)
+        cp, cu = (None, None) if candidates is None else _candidates(candidates, ii.size)
+        users = np.empty((ii.size, int(topn)), np.int32)
+        scores = np.empty((ii.size, int(topn)), np.float32)
+        if seen and candidates is None:
+            self._check(self._lib.mfsgd_recommend_users_unseen(self._handle(), _p(ii, C.c_int32), ii.size, int(topn),
+                                                               _p(users, C.c_int32), _p(scores, C.c_float)))
+        elif seen:
+            self._check(self._lib.mfsgd_recommend_users_unseen_among(self._handle(), _p(ii, C.c_int32), ii.size, int(topn),
+                                                                     None if cp is None else _p(cp, C.c_int64),
+                                                                     _p(cu, C.c_int32), cu.size, _p(users, C.c_int32),
+                                                                     _p(scores, C.c_float)))
+        elif candidates is None:
+            self._check(self._lib.mfsgd_recommend_users(self._handle(), _p(ii, C.c_int32), ii.size, int(topn),
+                                                        _p(eu, C.c_int32), _p(ei, C.c_int32), eu.size,
+                                                        _p(users, C.c_int32), _p(scores, C.c_float)))
+        else:
+            self._check(self._lib.mfsgd_recommend_users_among(self._handle(), _p(ii, C.c_int32), ii.size, int(topn),
+                                                              None if cp is None else _p(cp, C.c_int64), _p(cu, C.c_int32),
+                                                              cu.size, _p(eu, C.c_int32), _p(ei, C.c_int32), eu.size,
+                                                              _p(users, C.c_int32), _p(scores, C.c_float)))
+        return users, scores
+
     # -- the seen-item index (include/mfsgd.h, "the seen-item index") ---------------
     def set_seen(self, u, i):
         """The seen-item index becomes the distinct pairs (u[x], i[x]) (mfsgd_set_seen): built once on the device and kept
@@ -1045,6 +1078,33 @@ class MatrixFactorizationSGD:
                                                              ci.size, _p(er, C.c_int32), _p(ei, C.c_int32), er.size,
                                                              _p(items, C.c_int32), _p(scores, C.c_float)))
         return items, scores
+
+    def recommend_users_rows(self, rows, topn, exclude=None, candidates=None):
+        """recommend_users() for items that are not in the model (for instance what fold_in_items returned: "who should be
+        shown this new item"): (users, scores), each [len(rows), topn].  exclude = (row, user): pairs never returned, row
+        indexing `rows`.  candidates: as in recommend_users(), the per-row forms indexing `rows`
+        (mfsgd_recommend_users_rows_among)."""
+        rows = _f32(rows)
+        if rows.ndim != 2 or rows.shape[1] != self.k:
+            raise ValueError("rows must be n_rows x k")
+        er, eu = (np.empty(0, np.int32),) * 2 if exclude is None else (_i32(exclude[0]), _i32(exclude[1]))
+        if er.shape != eu.shape or er.ndim != 1:
+            raise ValueError("exclude must be two 1-d arrays of the same length")
+        n = rows.shape[0]
+        cp, cu = (None, None) if candidates is None else _candidates(candidates, n)
+        users = np.empty((n, int(topn)), np.int32)
+        scores = np.empty((n, int(topn)), np.float32)
+        if candidates is None:
+            self._check(self._lib.mfsgd_recommend_users_rows(self._handle(), _p(rows, C.c_float), n, int(topn),
+                                                             _p(er, C.c_int32), _p(eu, C.c_int32), er.size,
+                                                             _p(users, C.c_int32), _p(scores, C.c_float)))
+        else:
+            self._check(self._lib.mfsgd_recommend_users_rows_among(self._handle(), _p(rows, C.c_float), n, int(topn),
+                                                                   None if cp is None else _p(cp, C.c_int64),
+                                                                   _p(cu, C.c_int32), cu.size, _p(er, C.c_int32),
+                                                                   _p(eu, C.c_int32), er.size, _p(users, C.c_int32),
+                                                                   _p(scores, C.c_float)))
+        return users, scores
 
     def rank_items(self, u, i, exclude=None):
         """int32[n]: for each held-out pair (u[x], i[x]) the number of items that come before i[x] in u[x]'s
