@@ -5,7 +5,7 @@
 // one ascending user list per slot).  Integers only.
 // Cost per call: two passes (one that counts, one that writes) of 4 D bytes of items read each, a search of
 // log2(n_users) steps through the offsets for each pair that is kept, and one 8-byte key written per kept pair; the
-// host stages 20 bytes per kept pair for them (two key buffers for the sort and the lists' 4-byte users, serve.cpp).
+// host stages 20 bytes per kept pair for them (two key buffers for the sort and the lists' 4-byte users, serve_lists.cpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

@@ -1,5 +1,5 @@
 // handle.hpp -- what the units of the C-ABI that see inside the handle share (handle.cpp, seen_index.cpp, sampling.cpp, ratings.cpp,
-// train.cpp, online_update.cpp, serve.cpp): the handle, its partitions, the error channel, the guard with that channel, and the helpers that cross
+// train.cpp, online_update.cpp, serve_lists.cpp, serve_topn.cpp, serve_rank.cpp, serve_fold.cpp): the handle, its partitions, the error channel, the guard with that channel, and the helpers that cross
 // units.  Internal: installed nowhere.  dsgd.cpp and io.cpp see the handle through include/mfsgd.h only, and take the
 // guard from guard.hpp.
 #pragma once
@@ -193,7 +193,7 @@ int hip_fail(const mfsgd_handle* h, const std::string& what, hipError_t e);
 // ... and most of them leave no error behind in the runtime
 int serve_fail(const mfsgd_handle* h, const char* prefix, hipError_t e);
 
-// The guard (guard.hpp) with this error channel: every `int` entry point of the four units runs its body in guarded()
+// The guard (guard.hpp) with this error channel: every `int` entry point of these units runs its body in guarded()
 // or, without a handle, in guarded_free().
 // A null handle is MFSGD_ERR_INVALID_ARG.  std::bad_alloc becomes MFSGD_ERR_OOM, "<name>: out of host memory"; any other
 // std::exception becomes `other`, "<name>: <what()>".

@@ -1,7 +1,7 @@
 // seen_index.cpp -- the seen-item index of a handle, behind the entry points of handle.cpp: mfsgd_set_seen builds it from
 // (user, item) pairs, mfsgd_mark_seen merges a batch into it without sorting it again, mfsgd_get_seen reads lists back,
 // and the growth calls extend its per-user tables here; so are the item weights (mfsgd_set_item_weights and its kin).  The
-// index itself is described in handle.hpp (Seen), its device code is seen.hip, and the calls that read it are serve.cpp's
+// index itself is described in handle.hpp (Seen), its device code is seen.hip, and the calls that read it are serve_topn.cpp's and serve_rank.cpp's
 // (_unseen) and sampling.cpp's (mfsgd_sample_unseen and its kin).
 #include <algorithm>
 #include <cstring>

@@ -644,28 +644,28 @@ class MatrixFactorizationSGD:
         candidates: the items a row may return at all (mfsgd_recommend_among) -- a 1-d integer array, one list for every
         row; a tuple (ptr, items), CSR over the rows of `users` (row b is the position in users, not the user); or a
         sequence of one 1-d array per row.  Lists may be unsorted, repeat items and be empty.  None: every item."""
-        uu = _i32(np.atleast_1d(users))
-        seen, eu, ei = _exclusions(exclude)
-        cp, ci = (None, None) if candidates is None else _candidates(candidates, uu.size)
-        items = np.empty((uu.size, int(topn)), np.int32)
-        scores = np.empty((uu.size, int(topn)), np.float32)
-        if seen and candidates is None:
-            self._check(self._lib.mfsgd_recommend_unseen(self._handle(), _p(uu, C.c_int32), uu.size, int(topn),
-                                                         _p(items, C.c_int32), _p(scores, C.c_float)))
-        elif seen:
-            self._check(self._lib.mfsgd_recommend_unseen_among(self._handle(), _p(uu, C.c_int32), uu.size, int(topn),
-                                                               None if cp is None else _p(cp, C.c_int64), _p(ci, C.c_int32),
-                                                               ci.size, _p(items, C.c_int32), _p(scores, C.c_float)))
-        elif candidates is None:
-            self._check(self._lib.mfsgd_recommend_excluding(self._handle(), _p(uu, C.c_int32), uu.size, int(topn),
-                                                            _p(eu, C.c_int32), _p(ei, C.c_int32), eu.size,
-                                                            _p(items, C.c_int32), _p(scores, C.c_float)))
-        else:
-            self._check(self._lib.mfsgd_recommend_among(self._handle(), _p(uu, C.c_int32), uu.size, int(topn),
-                                                        None if cp is None else _p(cp, C.c_int64), _p(ci, C.c_int32), ci.size,
-                                                        _p(eu, C.c_int32), _p(ei, C.c_int32), eu.size,
-                                                        _p(items, C.c_int32), _p(scores, C.c_float)))
-        return items, scores
+        lib = self._lib
+        return self._top_n((lib.mfsgd_recommend_excluding, lib.mfsgd_recommend_among, lib.mfsgd_recommend_unseen,
+                            lib.mfsgd_recommend_unseen_among), _i32(np.atleast_1d(users)), _exclusions(exclude), candidates, topn)
+
+    def _top_n(self, family, request, exclusions, candidates, topn):
+        """The one call behind recommend, recommend_users and their _rows forms: (ids, scores), each [n, topn].  family: the
+        C functions (plain, among, unseen, unseen among) -- the _rows families have no unseen forms; request: the ids asked
+        for (int32; n is their number) or dense rows (float32, n x k); exclusions: (seen, a, b) as _exclusions returns it,
+        the pairs in the order the family takes them; candidates: the caller's, in any of the three forms, or None."""
+        rows = request.dtype == np.float32
+        n = request.shape[0] if rows else request.size
+        seen, ea, eb = exclusions
+        cp, cc = (None, None) if candidates is None else _candidates(candidates, n)
+        ids = np.empty((n, int(topn)), np.int32)
+        scores = np.empty((n, int(topn)), np.float32)
+        args = [self._handle(), _p(request, C.c_float if rows else C.c_int32), n, int(topn)]
+        if candidates is not None:
+            args += [None if cp is None else _p(cp, C.c_int64), _p(cc, C.c_int32), cc.size]
+        if not seen:
+            args += [_p(ea, C.c_int32), _p(eb, C.c_int32), ea.size]
+        self._check(family[2 * seen + (candidates is not None)](*args, _p(ids, C.c_int32), _p(scores, C.c_float)))
+        return ids, scores
 
     def recommend_users(self, items, topn, exclude=None, candidates=None):
         """(users, scores), each [len(items), topn]: the best audience of each item, best first -- recommend() with the
@@ -676,29 +676,10 @@ class MatrixFactorizationSGD:
         each call reads all of it once on the device to find the requested items' users.
         candidates: the users a row may return at all ("the best 100 of this segment", mfsgd_recommend_users_among), in
         the three forms recommend() takes, the per-row forms indexing `items`.  None: every user."""
-        ii = _i32(np.atleast_1d(items))
-        seen, eu, ei = _exclusions(exclude)
-        cp, cu = (None, None) if candidates is None else _candidates(candidates, ii.size)
-        users = np.empty((ii.size, int(topn)), np.int32)
-        scores = np.empty((ii.size, int(topn)), np.float32)
-        if seen and candidates is None:
-            self._check(self._lib.mfsgd_recommend_users_unseen(self._handle(), _p(ii, C.c_int32), ii.size, int(topn),
-                                                               _p(users, C.c_int32), _p(scores, C.c_float)))
-        elif seen:
-            self._check(self._lib.mfsgd_recommend_users_unseen_among(self._handle(), _p(ii, C.c_int32), ii.size, int(topn),
-                                                                     None if cp is None else _p(cp, C.c_int64),
-                                                                     _p(cu, C.c_int32), cu.size, _p(users, C.c_int32),
-                                                                     _p(scores, C.c_float)))
-        elif candidates is None:
-            self._check(self._lib.mfsgd_recommend_users(self._handle(), _p(ii, C.c_int32), ii.size, int(topn),
-                                                        _p(eu, C.c_int32), _p(ei, C.c_int32), eu.size,
-                                                        _p(users, C.c_int32), _p(scores, C.c_float)))
-        else:
-            self._check(self._lib.mfsgd_recommend_users_among(self._handle(), _p(ii, C.c_int32), ii.size, int(topn),
-                                                              None if cp is None else _p(cp, C.c_int64), _p(cu, C.c_int32),
-                                                              cu.size, _p(eu, C.c_int32), _p(ei, C.c_int32), eu.size,
-                                                              _p(users, C.c_int32), _p(scores, C.c_float)))
-        return users, scores
+        lib = self._lib
+        return self._top_n((lib.mfsgd_recommend_users, lib.mfsgd_recommend_users_among, lib.mfsgd_recommend_users_unseen,
+                            lib.mfsgd_recommend_users_unseen_among), _i32(np.atleast_1d(items)), _exclusions(exclude), candidates,
+                           topn)
 
     # -- the seen-item index (include/mfsgd.h, "the seen-item index") ---------------
     def set_seen(self, u, i):
@@ -1058,53 +1039,24 @@ class MatrixFactorizationSGD:
         """recommend() for rows that are not in the model (for instance what fold_in returned): (items, scores), each
         [len(rows), topn].  exclude = (row, item): pairs never returned, row indexing `rows`.  candidates: as in
         recommend(), the per-row forms indexing `rows` (mfsgd_recommend_rows_among)."""
+        return self._top_n_rows((self._lib.mfsgd_recommend_rows, self._lib.mfsgd_recommend_rows_among), rows, exclude, candidates,
+                                topn)
+
+    def _top_n_rows(self, family, rows, exclude, candidates, topn):
+        """_top_n for the _rows calls: family is (plain, among), and exclude None or the two arrays of its pairs."""
         rows = _f32(rows)
         if rows.ndim != 2 or rows.shape[1] != self.k:
             raise ValueError("rows must be n_rows x k")
-        er, ei = (np.empty(0, np.int32),) * 2 if exclude is None else (_i32(exclude[0]), _i32(exclude[1]))
-        if er.shape != ei.shape or er.ndim != 1:
-            raise ValueError("exclude must be two 1-d arrays of the same length")
-        n = rows.shape[0]
-        cp, ci = (None, None) if candidates is None else _candidates(candidates, n)
-        items = np.empty((n, int(topn)), np.int32)
-        scores = np.empty((n, int(topn)), np.float32)
-        if candidates is None:
-            self._check(self._lib.mfsgd_recommend_rows(self._handle(), _p(rows, C.c_float), n, int(topn), _p(er, C.c_int32),
-                                                       _p(ei, C.c_int32), er.size, _p(items, C.c_int32),
-                                                       _p(scores, C.c_float)))
-        else:
-            self._check(self._lib.mfsgd_recommend_rows_among(self._handle(), _p(rows, C.c_float), n, int(topn),
-                                                             None if cp is None else _p(cp, C.c_int64), _p(ci, C.c_int32),
-                                                             ci.size, _p(er, C.c_int32), _p(ei, C.c_int32), er.size,
-                                                             _p(items, C.c_int32), _p(scores, C.c_float)))
-        return items, scores
+        pairs = _pairs(None, None, "exclude") if exclude is None else _pairs(exclude[0], exclude[1], "exclude")
+        return self._top_n(family, rows, (False,) + pairs, candidates, topn)
 
     def recommend_users_rows(self, rows, topn, exclude=None, candidates=None):
         """recommend_users() for items that are not in the model (for instance what fold_in_items returned: "who should be
         shown this new item"): (users, scores), each [len(rows), topn].  exclude = (row, user): pairs never returned, row
         indexing `rows`.  candidates: as in recommend_users(), the per-row forms indexing `rows`
         (mfsgd_recommend_users_rows_among)."""
-        rows = _f32(rows)
-        if rows.ndim != 2 or rows.shape[1] != self.k:
-            raise ValueError("rows must be n_rows x k")
-        er, eu = (np.empty(0, np.int32),) * 2 if exclude is None else (_i32(exclude[0]), _i32(exclude[1]))
-        if er.shape != eu.shape or er.ndim != 1:
-            raise ValueError("exclude must be two 1-d arrays of the same length")
-        n = rows.shape[0]
-        cp, cu = (None, None) if candidates is None else _candidates(candidates, n)
-        users = np.empty((n, int(topn)), np.int32)
-        scores = np.empty((n, int(topn)), np.float32)
-        if candidates is None:
-            self._check(self._lib.mfsgd_recommend_users_rows(self._handle(), _p(rows, C.c_float), n, int(topn),
-                                                             _p(er, C.c_int32), _p(eu, C.c_int32), er.size,
-                                                             _p(users, C.c_int32), _p(scores, C.c_float)))
-        else:
-            self._check(self._lib.mfsgd_recommend_users_rows_among(self._handle(), _p(rows, C.c_float), n, int(topn),
-                                                                   None if cp is None else _p(cp, C.c_int64),
-                                                                   _p(cu, C.c_int32), cu.size, _p(er, C.c_int32),
-                                                                   _p(eu, C.c_int32), er.size, _p(users, C.c_int32),
-                                                                   _p(scores, C.c_float)))
-        return users, scores
+        return self._top_n_rows((self._lib.mfsgd_recommend_users_rows, self._lib.mfsgd_recommend_users_rows_among), rows, exclude,
+                                candidates, topn)
 
     def rank_items(self, u, i, exclude=None):
         """int32[n]: for each held-out pair (u[x], i[x]) the number of items that come before i[x] in u[x]'s

@@ -1,7 +1,7 @@
 """include/mfsgd.h promises that no C++ exception crosses the boundary.  A host allocation that fails inside a serving
 call comes back as MFSGD_ERR_OOM and leaves the handle usable (it used to end the process), and every `int` entry point
-of the boundary units (csrc/handle.cpp, ratings.cpp, train.cpp, online_update.cpp, serve.cpp, dsgd.cpp, io.cpp) runs its body inside the
-guard of csrc/guard.hpp, through the wrapper of its unit."""
+of the boundary units (csrc/handle.cpp, ratings.cpp, train.cpp, online_update.cpp, serve_topn.cpp, serve_rank.cpp, serve_fold.cpp, dsgd.cpp,
+io.cpp) runs its body inside the guard of csrc/guard.hpp, through the wrapper of its unit."""
 import os
 import re
 import subprocess
@@ -11,7 +11,8 @@ from tests.conftest import ROOT
 
 CSRC = os.path.join(ROOT, "matrixfactorizationsgd.java_amd", "csrc")
 RING, REHEARSAL_ONLY = "dsgd.cpp", ("shm_transport.cpp",)  # the rest goes into libmfsgd.so
-UNITS = ("handle.cpp", "ratings.cpp", "train.cpp", "online_update.cpp", "serve.cpp", RING, "io.cpp", "rccl_transport.cpp") + REHEARSAL_ONLY
+UNITS = ("handle.cpp", "ratings.cpp", "train.cpp", "online_update.cpp", "serve_lists.cpp", "serve_topn.cpp", "serve_rank.cpp", "serve_fold.cpp",
+         RING, "io.cpp", "rccl_transport.cpp") + REHEARSAL_ONLY
 # calls that allocate nothing and throw nothing: a cap, not a target
 UNGUARDED = {"mfsgd_abi_version", "mfsgd_get_dims", "mfsgd_get_parts", "mfsgd_get_hyper", "mfsgd_debug_device_bytes",
              "mfsgd_dsgd_stats", "mfsgd_ratings_file_info", "mfsgd_ratings_file_read"}

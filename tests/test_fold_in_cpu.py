@@ -60,6 +60,60 @@ def test_bad_fold_in_arguments_are_invalid(model, kw, names):
     assert msg.startswith("fold_in:") and names in msg
 
 
+def _fold_raw(m, fn, n_new, row_ptr, ids, ratings, epochs=1, out=True):
+    """(status, message) of one raw call of mfsgd_fold_in_users or mfsgd_fold_in_items."""
+    rows = np.zeros((max(1, n_new), K), np.float32) if out else None
+    rc = getattr(m._lib, fn)(m._handle(), n_new, _ptr(row_ptr, np.int64, C.c_int64), _ptr(ids, np.int32, C.c_int32),
+                             _ptr(ratings, np.float32, C.c_float), epochs, None, 3, _ptr(rows, np.float32, C.c_float))
+    return rc, _err(m)
+
+
+# (the C function, how it names itself, a new row, an id and the ids, and how many rows the fixed side has)
+@pytest.mark.parametrize("fn,call,row,id_,ids,n_fixed", [
+    ("mfsgd_fold_in_users", "fold_in", "user", "item", "items", I),
+    ("mfsgd_fold_in_items", "fold_in_items", "item", "user", "users", U),
+])
+def test_the_fold_in_checks_come_in_their_order(mf, fn, call, row, id_, ids, n_fixed):
+    """Two faults in one call, one case for each neighbouring pair of the order: n_new, epochs, the null row_ptr / out_rows,
+    the state of the factors (before row_ptr is read, and before n_new == 0 is answered), row_ptr[0], a decreasing
+    row_ptr, the null ids / ratings, an id out of range.  The earlier fault is the one reported."""
+    pre = call + ": "
+    two, bad = dict(ids=[0, 1], ratings=[1, 2]), [0, n_fixed, 1]
+
+    def go(m, n_new, row_ptr, ids, ratings, **kw):
+        return _fold_raw(m, fn, n_new, row_ptr, ids, ratings, **kw)
+
+    with mf.MatrixFactorizationSGD(U, I, K, 0.01, 0.05, 1) as m:  # factors never set: what passes here is asked before the state
+        assert go(m, -1, [0], [], [], epochs=-1) == (INVALID_ARG, pre + "n_new is negative")
+        assert go(m, 2, None, epochs=-1, **two) == (INVALID_ARG, pre + "epochs is negative")
+        assert go(m, 2, [0, 1, 2], epochs=-1, out=False, **two) == (INVALID_ARG, pre + "epochs is negative")
+        assert go(m, 2, None, **two) == (INVALID_ARG, pre + "row_ptr or out_rows is null")
+        assert go(m, 2, [0, 1, 2], out=False, **two) == (INVALID_ARG, pre + "row_ptr or out_rows is null")
+        # the state before anything of row_ptr is read, and whatever n_new is
+        assert go(m, 2, [1, 1, 2], **two) == (STATE, pre + "factors not initialised")
+        assert go(m, 0, [0], None, None) == (STATE, pre + "factors not initialised")
+        m.init_p_offset(1, 0)  # P alone
+        for args in ((2, [1, 1, 2], [0, 1], [1, 2]), (0, [0], None, None)):
+            rc, msg = go(m, *args)
+            assert rc == STATE and msg.startswith(pre + "Q is not initialised")
+        assert go(m, 2, None, **two) == (INVALID_ARG, pre + "row_ptr or out_rows is null")
+    with mf.MatrixFactorizationSGD(U, I, K, 0.01, 0.05, 1, n_parts=2) as m:
+        assert go(m, 2, [1, 1, 2], **two) == (STATE, pre + "single-partition handles only")
+        assert go(m, 0, [0], None, None) == (STATE, pre + "single-partition handles only")
+        assert go(m, 2, [0, 1, 2], out=False, **two) == (INVALID_ARG, pre + "row_ptr or out_rows is null")
+    with mf.MatrixFactorizationSGD(U, I, K, 0.01, 0.05, 1) as m:
+        m.init_factors()
+        assert go(m, 2, [1, 3, 2], bad, None) == (INVALID_ARG, pre + "row_ptr[0] is not 0")
+        assert go(m, 3, [0, 2, 1, 3], None, [1, 2, 3]) == (INVALID_ARG, pre + f"row_ptr decreases at {row} 1")
+        assert go(m, 3, [0, 2, 1, 3], bad, None) == (INVALID_ARG, pre + f"row_ptr decreases at {row} 1")
+        assert go(m, 3, [0, 2, 1, 3], bad, [1, 2, 3]) == (INVALID_ARG, pre + f"row_ptr decreases at {row} 1")
+        assert go(m, 2, [0, 1, 3], bad, None) == (INVALID_ARG, pre + f"{ids} or ratings is null")
+        assert go(m, 2, [0, 1, 3], None, [1, 2, 3]) == (INVALID_ARG, pre + f"{ids} or ratings is null")
+        assert go(m, 2, [0, 1, 3], bad, [1, 2, 3]) == (INVALID_ARG, pre + f"{id_} of rating 1 out of range")
+        assert go(m, 2, [0, 1, 3], [0, 1, -1], [1, 2, 3]) == (INVALID_ARG, pre + f"{id_} of rating 2 out of range")
+        assert go(m, 0, [1], bad, None)[0] == OK  # nobody to fold in: row_ptr is not read
+
+
 def test_fold_in_null_handle(model):
     rp = np.zeros(1, np.int64)
     assert model._lib.mfsgd_fold_in_users(None, 0, _ptr(rp, np.int64, C.c_int64), None, None, 1, None, 0,

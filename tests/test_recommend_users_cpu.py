@@ -167,6 +167,31 @@ def test_checks_run_in_recommend_cores_order(model, mf):
             STATE, "recommend_users_unseen: single-partition handles only")
 
 
+def test_the_remaining_neighbours_of_recommend_cores_order(model, mf):
+    """Two faults in one call, for the neighbouring pairs the test above leaves out: bad argument / partitions / no seen set /
+    topn, the item before the first candidate check, and the candidate checks among themselves."""
+    bad_item, bad_pair = [0, I], ([0, U], [1, 1], 2)
+    name = "recommend_users_among"
+    with mf.MatrixFactorizationSGD(U, I, K, 0.01, 0.05, 1, n_parts=2) as m:
+        assert _call(m, name, bad_item, 2, 0, SHARED, bad_pair)[:2] == (INVALID_ARG, name + ": bad argument")
+        assert _call(m, name, bad_item, 2, U + 1, SHARED, bad_pair)[:2] == (STATE, name + ": single-partition handles only")
+        assert _call(m, "recommend_users_unseen_among", bad_item, 2, U + 1, SHARED)[:2] == (
+            STATE, "recommend_users_unseen_among: single-partition handles only")
+    with mf.MatrixFactorizationSGD(U, I, K, 0.01, 0.05, 1) as m:  # no index
+        unseen = "recommend_users_unseen_among"
+        assert _call(m, unseen, bad_item, 2, U + 1, (None, [0, U], -1))[:2] == (STATE, unseen + ": no seen set")
+        assert _call(m, unseen, bad_item, -1, U + 1, SHARED)[:2] == (INVALID_ARG, unseen + ": bad argument")
+    # the item before the first of the candidate checks
+    assert _call(model, name, bad_item, 2, 2, (None, None, -1), bad_pair)[1] == name + ": item 1 out of range"
+    # the candidate checks: n_cand, the null array, cand_ptr[0], a decreasing cand_ptr, its end, the range
+    assert _call(model, name, [0, 1], 2, 2, (None, None, -1), bad_pair)[1] == name + ": n_cand is negative"
+    assert _call(model, name, [0, 1], 2, 2, ([1, 2, 3], None, 3), bad_pair)[1] == name + ": cand_users is null"
+    assert _call(model, name, [0, 1], 2, 2, ([1, 3, 2], [0, 1, U], 3), bad_pair)[1] == name + ": cand_ptr[0] is not 0"
+    assert _call(model, name, [0, 1], 2, 2, ([0, 2, 1], [0, 1, U], 3), bad_pair)[1] == name + ": cand_ptr decreases at row 1"
+    assert _call(model, name, [0, 1], 2, 2, ([0, 1, 2], [0, 1, U], 3), bad_pair)[1] == name + ": cand_ptr ends at 2, not at n_cand"
+    assert _call(model, name, [0, 1], 2, 2, ([0, 1, 3], [0, 1, U], 3), bad_pair)[1] == name + ": candidate 2 out of range"
+
+
 def test_nothing_asked_is_ok(model, mf):
     assert _call(model, "recommend_users", [], 0, 3)[0] == OK
     assert _call(model, "recommend_users", None, 0, 3, outs=False)[0] == OK

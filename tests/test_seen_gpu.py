@@ -16,8 +16,8 @@ pytestmark = pytest.mark.gpu
 LR, LAM = 0.01, 0.05
 TILE = 14336      # csrc/recommend.hip: kTopnTile, positions per tile of the fused kernel
 CHUNK = 1 << 22   # csrc/handle.hpp: kExclChunk, pairs per upload of set_seen / mark_seen
-LAUNCH_ROWS = 65535     # csrc/serve.cpp, topn_batches: kLaunchRows, request rows per launch
-SORT_CELLS = 64 << 20   # csrc/serve.cpp: kSortCells, scores one batch of the sort path materialises
+LAUNCH_ROWS = 65535     # csrc/serve_topn.cpp, topn_batches: kLaunchRows, request rows per launch
+SORT_CELLS = 64 << 20   # csrc/serve_topn.cpp: kSortCells, scores one batch of the sort path materialises
 GATHER_ROWS = 4096      # csrc/seen.hip, seen_gather: grid.x, the rows a pass of the gather takes
 GATHER_SPAN = 64 * 256  # ... grid.y parts of kSeenThreads positions: what a pass takes of one list
 INVALID_ARG = -1

@@ -121,7 +121,7 @@ def test_the_switch_between_the_fused_and_the_sort_path(mf, oracle, I):
 
 # ---- C4: more users than one launch, or one staging batch, takes ----------------------------------------------------------------
 def test_fused_path_more_users_than_one_launch(mf, oracle):
-    U, I, k, topn = 70000, 5, 4, 5  # a launch takes 65 535 users (csrc/serve.cpp, kLaunchRows): the second one has 4 465
+    U, I, k, topn = 70000, 5, 4, 5  # a launch takes 65 535 users (csrc/serve_topn.cpp, kLaunchRows): the second one has 4 465
     rng = np.random.default_rng(70000)
     P = rng.standard_normal((U, k)).astype(np.float32)
     Q = rng.standard_normal((I, k)).astype(np.float32)
@@ -140,7 +140,7 @@ def test_fused_path_more_users_than_one_launch(mf, oracle):
 
 
 def test_sort_path_more_users_than_one_staging_batch(mf, oracle):
-    """csrc/serve.cpp, topn_batches: the sort path stages kSortCells / I = ((int64_t)64 << 20) / I scores' worth of users per batch;
+    """csrc/serve_topn.cpp, topn_batches: the sort path stages kSortCells / I = ((int64_t)64 << 20) / I scores' worth of users per batch;
     at I = 229 377 that is 292 users, so 300 users are a batch of 292 and one of 8."""
     I, k, topn, n_users = 16 * TILE + 1, 4, 129, 300
     assert (64 << 20) // I == 292

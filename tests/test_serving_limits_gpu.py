@@ -1,4 +1,4 @@
-"""The serving calls across the limits of their host-side staging (csrc/serve.cpp): more ranked pairs than one launch of
+"""The serving calls across the limits of their host-side staging (csrc/serve_topn.cpp, serve_rank.cpp, serve_fold.cpp): more ranked pairs than one launch of
 rank_items takes, one user whose own pairs exceed a launch, more exclusion pairs and more candidates than one upload, each
 with the pointer or offset that the second piece re-bases.  Every expectation is the oracle's canonical scores and a plain
 numpy selection, never another call of the library; where a test also runs exclude="seen" it is compared with the same
@@ -21,7 +21,7 @@ LR, LAM = 0.01, 0.05
 TILE = 14336           # csrc/recommend.hip: kTopnTile, positions per tile of the fused kernel
 CAND = 2048            # csrc/recommend.hip: kTopnCand; fused while tiles * topn <= CAND and topn <= 128
 CHUNK = 1 << 22        # csrc/handle.hpp: kExclChunk, exclusion pairs / candidates per upload
-RANK_CHUNK = 1 << 22   # csrc/serve.cpp: kRankChunk, pairs of one rank launch (whole users)
+RANK_CHUNK = 1 << 22   # csrc/serve_rank.cpp: kRankChunk, pairs of one rank launch (whole users)
 RANK_CAP = 512         # csrc/rank.hip: kRankCap, thresholds per user and round
 NONE = np.empty(0, np.int32)
 
@@ -79,7 +79,7 @@ def topn_ref(S, X, topn):
 
 
 def rank_launches(u):
-    """The users of each launch of rank_core (csrc/serve.cpp) for the pairs' users u as given: a slot per distinct user in
+    """The users of each launch of rank_core (csrc/serve_rank.cpp) for the pairs' users u as given: a slot per distinct user in
     the order of first appearance, the slots stably sorted by pair count (most first), launches of whole users of at most
     RANK_CHUNK pairs -- a single user with more is a launch of its own."""
     counts = np.bincount(u)
