@@ -724,6 +724,52 @@ int mfsgd_similar_users(mfsgd_handle* h, const int32_t* users, int32_t n, int32_
 int mfsgd_similar_rows(mfsgd_handle* h, int32_t side, const float* rows, int32_t n_rows, int32_t topn,
                        int32_t* out_index, float* out_scores);
 
+/* ---- least-squares fold-in: exact rows for new users or items, implicit feedback too, and ALS ------------------------
+ * With the other side fixed, the row that minimises the model's objective solves a k x k positive-definite system
+ *     (sum_j a_j f_j f_j^T + alpha * F^T F + delta * I) x = sum_j b_j f_j
+ * so it needs no learning rate, no epochs and no start row.  alpha = 0, a = 1, b = r, delta = lambda * len is the fixed
+ * point of mfsgd_fold_in_users' chain; alpha > 0 is implicit-feedback fold-in (a = c - alpha, b = c, delta = lambda); run
+ * over all users and then all items it is ALS.  The rule, bit for bit: everything fp32, round to
+ * nearest even, subnormals kept, nothing contracted except the fmas written here, sqrtf and / correctly rounded.
+ * F is the fixed side (n rows; Q for MFSGD_SIDE_USERS, P for MFSGD_SIDE_ITEMS), f_j = F[ids[j]], pad columns never enter;
+ * j runs over row_ptr[x] .. row_ptr[x + 1] in the order given, an id that appears twice contributes two terms.
+ * G = gram(F), lower triangle p >= q: tiles of T = 256 * ceil(n / 65536) rows, tile t owning rows [tT, min(n, (t+1)T));
+ *     g_t[p][q] = +0.0f;  for r in the tile, ascending: g_t[p][q] = fmaf(F[r][p], F[r][q], g_t[p][q])
+ *     G[p][q] = g_0[p][q];  then G[p][q] = G[p][q] + g_t[p][q] for t = 1, 2, ...;  the upper triangle a copy of the lower
+ * The system of a row, lower triangle p >= q:
+ *     A[p][q] = +0.0f;  rhs[p] = +0.0f
+ *     for j in list order:  t = (a given ? a[j] * f_j[p] : f_j[p])        (one rounding, on the ROW index p)
+ *                           A[p][q] = fmaf(t, f_j[q], A[p][q]);   rhs[p] = fmaf(b[j], f_j[p], rhs[p])
+ *     if alpha != 0:        A[p][q] = fmaf(alpha, G[p][q], A[p][q])       (G is not computed when alpha == 0)
+ *     dg = fmaf(ridge_per_entry, (float)len, ridge);   A[p][p] = A[p][p] + dg
+ * The solve, Cholesky by columns, every inner sum a chain in ascending index:
+ *     for j = 0 .. k-1:  s = A[j][j];  for t = 0 .. j-1: s = fmaf(-L[j][t], L[j][t], s)
+ *                        if !(s > 0.0f): status = j + 1, the row's k floats are 0x7FC00000, stop
+ *                        d = sqrtf(s);  inv[j] = 1.0f / d
+ *                        for i = j+1 .. k-1:  v = A[i][j];  for t = 0 .. j-1: v = fmaf(-L[i][t], L[j][t], v);  L[i][j] = v * inv[j]
+ *     forward:   for i = 0 .. k-1:  s = rhs[i];  for t = 0 .. i-1:         s = fmaf(-L[i][t], y[t], s);  y[i] = s * inv[i]
+ *     backward:  for i = k-1 .. 0:  s = y[i];    for t = k-1 down to i+1:  s = fmaf(-L[t][i], x[t], s);  x[i] = s * inv[i]
+ * A row with an empty list is +0.0f in all k columns with status 0, and no solve is run.  NaN and Inf propagate as the
+ * arithmetic says; a NaN pivot fails the s > 0 test, so such a row is reported and never silently wrong.  A row that
+ * fails its pivot is not an error of the call: the call returns MFSGD_OK and out_status (nullable, n_new) says which
+ * rows failed (0, or the 1-based pivot).  The chain over a list is sequential: a very long row costs len / 4 dependent
+ * matrix instructions (four rank-1 updates each) and is not split across workgroups -- orders of magnitude fewer
+ * dependent steps than the SGD chain's len x epochs all the same.
+ * Checked before any device work, in this order.  MFSGD_ERR_INVALID_ARG ("fold_in_solve: ..." / "gram: ..."): a side
+ * other than MFSGD_SIDE_USERS / MFSGD_SIDE_ITEMS, a negative n_new, a null array that is needed (row_ptr and out_rows
+ * with n_new > 0, ids and b with entries; out of mfsgd_gram), row_ptr[0] != 0, a decreasing row_ptr, an id outside the
+ * fixed side under the current counts (the message names the entry), a non-finite alpha, ridge or ridge_per_entry.
+ * MFSGD_ERR_STATE as mfsgd_fold_in_users reports it.  n_new == 0 is MFSGD_OK and touches nothing.
+ * MFSGD_ERR_NO_DEVICE: a valid call with work to do and no usable GPU.  Nothing is written to the outputs of a call
+ * that is refused.  The handle is not modified, nothing is cached between calls (G is computed per call when
+ * alpha != 0) and all staging is freed on every path.  Lists go up in batches of whole rows, as in mfsgd_fold_in_users. */
+/* gram(F) of P (side 0) or Q (side 1): k x k floats, row-major, symmetric. */
+int mfsgd_gram(mfsgd_handle* h, int32_t side, float* out);
+/* side: the side the NEW rows belong to (MFSGD_SIDE_USERS: new users, against Q).  a nullable: all 1.  out_rows n_new x k. */
+int mfsgd_fold_in_solve(mfsgd_handle* h, int32_t side, int32_t n_new, const int64_t* row_ptr, const int32_t* ids,
+                        const float* a, const float* b, float alpha, float ridge, float ridge_per_entry,
+                        float* out_rows, int32_t* out_status);
+
 /* ---- lr and lambda on a live model; learning-rate schedules --------------------------------------------------------
  * mfsgd_set_hyper gives the handle another lr and lambda without rebuilding anything: the two numbers sit in the
  * schedules' step entries (lr * r and the decay factor 1 - lr * lambda) and nowhere else in them, so the entries are

@@ -171,6 +171,9 @@ SIGNATURES = {
     "mfsgd_similar_items": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i32p, _f32p]),
     "mfsgd_similar_users": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i32p, _f32p]),
     "mfsgd_similar_rows": (C.c_int, [_H, C.c_int32, _f32p, C.c_int32, C.c_int32, _i32p, _f32p]),
+    "mfsgd_gram": (C.c_int, [_H, C.c_int32, _f32p]),
+    "mfsgd_fold_in_solve": (C.c_int, [_H, C.c_int32, C.c_int32, _i64p, _i32p, _f32p, _f32p, C.c_float, C.c_float, C.c_float,
+                                      _f32p, _i32p]),
     "mfsgd_train_timed": (C.c_int, [_H, C.c_int32, _f64p, _i64p]),
     "mfsgd_set_hyper": (C.c_int, [_H, C.c_float, C.c_float]),
     "mfsgd_get_hyper": (C.c_int, [_H, _f32p, _f32p]),

@@ -1,6 +1,6 @@
 // kernels.hpp -- host-callable launchers of every kernel unit: epoch.hip, cells.hip, kernels.hip, foldin.hip,
 // foldin_pairwise.hip, online.hip, pairwise.hip, rehyper.hip, recommend.hip, rank.hip, seen.hip, audience.hip, sample.hip, pick.hip,
-// similar.hip, validate.hip and grow.hip.
+// similar.hip, solve.hip, validate.hip and grow.hip.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -294,6 +294,34 @@ hipError_t launch_first_violating(int L, const float* P, const float* Q, const l
 // similar.hip.  out[x] = rn(row x) = 1 / sqrt(dot(row, row)), or 0 where that dot is 0, for the
 // n_rows kp-padded rows of M.  Asynchronous on st.
 hipError_t launch_row_inv_norms(int L, const float* M, int64_t n_rows, float* out, hipStream_t st);
+
+// solve.hip.  The Gram matrix of the n >= 1 kp-padded rows of F (include/mfsgd.h, "least-squares fold-in"): tile t of
+// gram_tile_rows(n) rows is one chain into partial[t] (room for gram_tiles(n) x k x k floats), and G (k x k, symmetric)
+// is the partials added in tile order.  Asynchronous on st.
+int64_t gram_tile_rows(int64_t n);
+int64_t gram_tiles(int64_t n);
+hipError_t launch_gram(int L, const float* F, int64_t n, int k, float* partial, float* G, hipStream_t st);
+// The nb new rows of one batch by least squares against the fixed side F: workgroup g takes new row x = perm[g], whose
+// list is entries ptr[x] - base .. ptr[x + 1] - base of ids / a / b (a nullable: all 1), builds the system of the
+// rule -- alpha * G on top where alpha != 0 (G is not read otherwise), ridge_per_entry * len + ridge on the diagonal --
+// and solves it by Cholesky.  rows (nb x k dense) gets the solution, zeros for an empty list, 0x7FC00000 where a pivot
+// is not positive; status[x] (nullable) 0 or the 1-based pivot.  A list is one chain: it is not split across
+// workgroups.  Every id is a row of F: the caller checks.  Asynchronous on st.
+struct SolveRows {
+    const float* F;
+    float* rows;
+    int k;
+    const long long* ptr;
+    long long base;
+    const int32_t* perm;
+    int nb;
+    const int32_t* ids;
+    const float *a, *b;
+    const float* G;
+    float alpha, ridge, ridge_per_entry;
+    int32_t* status;
+};
+hipError_t launch_solve_rows(int L, const SolveRows& a, hipStream_t st);
 
 // validate.hip.  Sum over the n >= 1 pairs of (double)e * (double)e with e = r[j] - dot(P[u[j]], Q[i[j]]) in fp32 (the
 // bits launch_predict returns), into *out.  Pair j is added to partial j mod kPairsSlots, each partial in ascending j,

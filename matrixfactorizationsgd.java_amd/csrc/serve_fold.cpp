@@ -1,6 +1,7 @@
 // serve_fold.cpp -- the fold-in side of what a trained model answers: rows for new users or new items against the fixed
-// factors of the other side, from their ratings (fold_in_core) or, for users, from their positives alone
-// (fold_in_pairwise_core).  Both run on one frame: the check of the CSR offsets, and the batches with their staging.
+// factors of the other side, from their ratings by an SGD chain (fold_in_core) or by least squares (fold_in_solve_core,
+// with the Gram matrix of a side beside it) or, for users, from their positives alone (fold_in_pairwise_core).  All run
+// on one frame: the check of the CSR offsets, and the batches with their staging.
 #include <algorithm>
 #include <cmath>
 #include <numeric>
@@ -29,7 +30,8 @@ static int check_fold_lists(const mfsgd_handle* h, const std::string& call, cons
 }
 
 // A fold-in call as the caller gave it: n_new lists in CSR form (row_ptr over ids and, the rated calls, ratings), the
-// start rows (init_rows, or seeded from `seed`) and where the rows go.
+// start rows (init_rows, or seeded from `seed`) and where the rows go.  The least-squares call has no start rows
+// (start_rows = false: a row starts, and without entries stays, +0.0f) and no epochs: its one pass is epochs = 1.
 struct FoldRequest {
     int32_t n_new;
     const int64_t* row_ptr;
@@ -39,12 +41,13 @@ struct FoldRequest {
     const float* init_rows;
     int64_t seed;
     float* out_rows;
+    bool start_rows = true;
 };
 
-// One batch on the device: nb new rows (rows: theirs, dense), whose nr ids start at `base` of the call's; ptr[nb + 1],
-// perm[nb] (the batch's rows, longest list first) and ids[nr] are the frame's staging.
+// One batch on the device: nb new rows from row x0 of the call on (rows: theirs, dense), whose nr ids start at `base` of
+// the call's; ptr[nb + 1], perm[nb] (the batch's rows, longest list first) and ids[nr] are the frame's staging.
 struct FoldBatch {
-    int32_t nb;
+    int32_t x0, nb;
     int64_t base, nr;
     float* rows;
     const long long* ptr;
@@ -52,8 +55,8 @@ struct FoldBatch {
 };
 
 // The frame of a checked fold-in call with n_new > 0: the factors on the device, batches of whole lists in the caller's
-// order (each one contiguous piece of ids), the start rows, per batch with ids its offsets, perm and ids up, `run(batch)`
-// and a synchronise, and the rows down at the end.  rebased: the offsets go up counted from the batch's first id (the
+// order (each one contiguous piece of ids), the start rows (zeros where the call has none), per batch with ids its
+// offsets, perm and ids up, `run(batch)` and a synchronise, and the rows down at the end.  rebased: the offsets go up counted from the batch's first id (the
 // pairwise kernels index the batch by them); otherwise as they are, and the kernel gets the batch's `base` beside them.
 // `extra(bt)` allocates what the core stages beside that, sized by the largest batch; neither it nor a batch is run
 // where epochs == 0 or there are no ids: the start rows are the result.  `call` starts the message of a HIP failure.
@@ -75,8 +78,10 @@ static int fold_batches(mfsgd_handle* h, const std::string& call, const FoldRequ
         if ((rc = dev_alloc(h, d_ptr, (size_t)bt.max_rows + 1)) || (rc = dev_alloc(h, d_perm, (size_t)bt.max_rows))) return rc;
         if ((rc = dev_alloc(h, d_ids, (size_t)bt.max_weight)) || (rc = extra(bt))) return rc;
     }
-    // the start rows, dense: the kernel pads them to kp in its registers
-    if (f.init_rows)
+    // the start rows, dense: the kernel pads them to kp in its registers (no start rows: what a list without ids keeps)
+    if (!f.start_rows)
+        HIPCHK_OR(bad, hipMemsetAsync(d_rows.data(), 0, row_floats * sizeof(float), h->stream));
+    else if (f.init_rows)
         HIPCHK_OR(bad, copy_up(d_rows, f.init_rows, row_floats, h->stream));
     else
         HIPCHK_OR(bad, launch_init_rows(d_rows.data(), n_new, k, k, f.seed, 0, (float)(1.0 / std::sqrt((double)k)), h->stream));
@@ -100,7 +105,7 @@ static int fold_batches(mfsgd_handle* h, const std::string& call, const FoldRequ
         }
         HIPCHK_OR(bad, copy_up(d_perm, perm.data(), (size_t)nb, h->stream));
         HIPCHK_OR(bad, copy_up(d_ids, f.ids + base, (size_t)nr, h->stream));
-        if ((rc = run(FoldBatch{nb, base, nr, d_rows.data() + (size_t)x0 * k, d_ptr.data(), d_perm.data(), d_ids.data()}))) return rc;
+        if ((rc = run(FoldBatch{x0, nb, base, nr, d_rows.data() + (size_t)x0 * k, d_ptr.data(), d_perm.data(), d_ids.data()}))) return rc;
         HIPCHK_OR(bad, hipStreamSynchronize(h->stream));  // perm, ptr and the staging buffers are reused
     }
     HIPCHK_OR(bad, copy_down(f.out_rows, d_rows, row_floats, h->stream));
@@ -233,6 +238,82 @@ static int fold_in_pairwise_core(mfsgd_handle* h, const PairwiseFoldRequest& req
         });
 }
 
+// G = gram(F) of the n rows of one side on the device, k x k; the tile partials live as long as this function.
+static int gram_to_device(mfsgd_handle* h, const std::string& call, const float* F, int32_t n, DevArray<float>& d_G) {
+    auto bad = [h, &call](hipError_t e) { return serve_fail(h, call.c_str(), e); };
+    const size_t kk = (size_t)h->cfg.k * (size_t)h->cfg.k;
+    DevArray<float> partial;
+    int rc = dev_alloc(h, d_G, kk);
+    if (rc || (rc = dev_alloc(h, partial, (size_t)gram_tiles(n) * kk))) return rc;
+    HIPCHK_OR(bad, launch_gram(h->geo.L, F, n, h->cfg.k, partial.data(), d_G.data(), h->stream));
+    HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
+    return MFSGD_OK;
+}
+
+static bool is_side(int32_t side) { return side == MFSGD_SIDE_USERS || side == MFSGD_SIDE_ITEMS; }
+
+// A least-squares fold-in call as the caller gave it: the lists (ratings: b), the weights a (nullable) and the three
+// numbers of the system, and where the status of each row goes (nullable).
+struct SolveFoldRequest {
+    FoldRequest lists;
+    const float* a;
+    float alpha, ridge, ridge_per_entry;
+    int32_t* out_status;
+};
+
+// Body of mfsgd_fold_in_solve: n_new rows of `side` against the fixed factors of the other side, each the solution of
+// its own k x k system (solve.hip).  G of the fixed side is made once per call, and only where alpha != 0.
+static int fold_in_solve_core(mfsgd_handle* h, int32_t side, const SolveFoldRequest& req) {
+    const std::string call = "fold_in_solve: ";
+    const FoldRequest& lists = req.lists;
+    const int32_t n_new = lists.n_new;
+    const int64_t* row_ptr = lists.row_ptr;
+    if (!is_side(side)) return fail(h, MFSGD_ERR_INVALID_ARG, call + "side is neither MFSGD_SIDE_USERS nor MFSGD_SIDE_ITEMS");
+    if (n_new < 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "n_new is negative");
+    if (n_new > 0 && (!row_ptr || !lists.out_rows)) return fail(h, MFSGD_ERR_INVALID_ARG, call + "row_ptr or out_rows is null");
+    int rc = check_fold_lists(h, call, row_ptr, n_new, "row", false);
+    if (rc) return rc;
+    const bool users = side == MFSGD_SIDE_USERS;  // new users: against Q
+    const int32_t n_fixed = users ? h->cfg.n_items : h->cfg.n_users;
+    const int64_t total = n_new > 0 ? row_ptr[n_new] : 0;
+    if (total > 0 && (!lists.ids || !lists.ratings)) return fail(h, MFSGD_ERR_INVALID_ARG, call + "ids or b is null");
+    const int64_t j = first_outside(lists.ids, total, n_fixed);
+    if (j >= 0) return fail(h, MFSGD_ERR_INVALID_ARG, call + "id of entry " + std::to_string(j) + " out of range");
+    if (!std::isfinite(req.alpha) || !std::isfinite(req.ridge) || !std::isfinite(req.ridge_per_entry))
+        return fail(h, MFSGD_ERR_INVALID_ARG, call + "alpha, ridge or ridge_per_entry is not finite");
+    if ((rc = check_reads_factors(h, "fold_in_solve"))) return rc;
+    if (n_new == 0) return MFSGD_OK;
+    if ((rc = factors_to_device(h))) return rc;
+    auto bad = [h, &call](hipError_t e) { return serve_fail(h, call.c_str(), e); };
+    const float* F = users ? h->dQ.data() : h->dP.data();
+    DevArray<float> d_a, d_b, d_G;
+    DevArray<int32_t> d_status;  // of the whole call: a list without entries never reaches the kernel, and is status 0
+    if (req.out_status) {
+        if ((rc = dev_alloc(h, d_status, (size_t)n_new))) return rc;
+        HIPCHK_OR(bad, hipMemsetAsync(d_status.data(), 0, (size_t)n_new * sizeof(int32_t), h->stream));
+    }
+    rc = fold_batches(
+        h, call, lists, false,
+        [&](const Batches& bt) -> int {
+            int rc2 = dev_alloc(h, d_b, (size_t)bt.max_weight);
+            if (rc2 || (req.a && (rc2 = dev_alloc(h, d_a, (size_t)bt.max_weight)))) return rc2;
+            return req.alpha != 0.0f ? gram_to_device(h, call, F, n_fixed, d_G) : MFSGD_OK;
+        },
+        [&](const FoldBatch& b) -> int {
+            HIPCHK_OR(bad, copy_up(d_b, lists.ratings + b.base, (size_t)b.nr, h->stream));
+            if (req.a) HIPCHK_OR(bad, copy_up(d_a, req.a + b.base, (size_t)b.nr, h->stream));
+            const SolveRows job{F, b.rows, h->cfg.k, b.ptr, b.base, b.perm, b.nb, b.ids, req.a ? d_a.data() : nullptr, d_b.data(),
+                                d_G.data(), req.alpha, req.ridge, req.ridge_per_entry,
+                                req.out_status ? d_status.data() + b.x0 : nullptr};
+            HIPCHK_OR(bad, launch_solve_rows(h->geo.L, job, h->stream));
+            return MFSGD_OK;
+        });
+    if (rc || !req.out_status) return rc;
+    HIPCHK_OR(bad, copy_down(req.out_status, d_status, (size_t)n_new, h->stream));
+    HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
+    return MFSGD_OK;
+}
+
 }  // namespace mfsgd
 
 using namespace mfsgd;
@@ -270,6 +351,31 @@ int mfsgd_fold_in_items(mfsgd_handle* h, int32_t n_new, const int64_t* row_ptr, 
     return guarded(h, "fold_in_items", [&]() -> int {
         return fold_in_core(h, kFoldInItems, &mfsgd_handle::dP, h->cfg.n_users,
                             {n_new, row_ptr, users, ratings, epochs, init_rows, seed, out_rows});
+    });
+}
+
+int mfsgd_gram(mfsgd_handle* h, int32_t side, float* out) {
+    return guarded(h, "gram", [&]() -> int {
+        if (!is_side(side)) return fail(h, MFSGD_ERR_INVALID_ARG, "gram: side is neither MFSGD_SIDE_USERS nor MFSGD_SIDE_ITEMS");
+        if (!out) return fail(h, MFSGD_ERR_INVALID_ARG, "gram: out is null");
+        const bool of_items = side == MFSGD_SIDE_ITEMS;  // (the users' side reads P alone)
+        int rc = check_reads_factors(h, "gram", of_items);
+        if (rc || (rc = factors_to_device(h))) return rc;
+        auto bad = [h](hipError_t e) { return serve_fail(h, "gram: ", e); };
+        DevArray<float> d_G;
+        if ((rc = gram_to_device(h, "gram: ", of_items ? h->dQ.data() : h->dP.data(), of_items ? h->cfg.n_items : h->cfg.n_users, d_G)))
+            return rc;
+        HIPCHK_OR(bad, copy_down(out, d_G, d_G.size(), h->stream));
+        HIPCHK_OR(bad, hipStreamSynchronize(h->stream));
+        return MFSGD_OK;
+    });
+}
+
+int mfsgd_fold_in_solve(mfsgd_handle* h, int32_t side, int32_t n_new, const int64_t* row_ptr, const int32_t* ids, const float* a,
+                        const float* b, float alpha, float ridge, float ridge_per_entry, float* out_rows, int32_t* out_status) {
+    return guarded(h, "fold_in_solve", [&]() -> int {
+        return fold_in_solve_core(h, side, {{n_new, row_ptr, ids, b, 1, nullptr, 0, out_rows, false}, a, alpha, ridge,
+                                            ridge_per_entry, out_status});
     });
 }
 

@@ -950,6 +950,139 @@ class MatrixFactorizationSGD:
         seeded start rows are fold_in()'s.  The model is not modified; add_items(rows) puts the rows into it."""
         return self._fold_in(self._lib.mfsgd_fold_in_items, row_ptr, users, ratings, epochs, init, seed, "users")
 
+    # -- least-squares fold-in and ALS (include/mfsgd.h, "least-squares fold-in") -------
+    def gram(self, side):
+        """float32[k, k]: the Gram matrix P^T P (side "users") or Q^T Q ("items") by the rule of mfsgd_gram -- the
+        alpha term of the implicit fold-in's system."""
+        code, _ = self._side(side)
+        out = np.empty((self.k, self.k), np.float32)
+        self._check(self._lib.mfsgd_gram(self._handle(), code, _p(out, C.c_float)))
+        return out
+
+    def _fold_in_solve(self, side, row_ptr, ids, a, b, alpha, ridge, ridge_per_entry, status, what):
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        ii, bb = _i32(ids), _f32(b)
+        if rp.ndim != 1 or rp.size < 1:
+            raise ValueError("row_ptr must be a 1-d array of n_new + 1 offsets")
+        n_new = rp.size - 1
+        if ii.ndim != 1 or ii.shape != bb.shape or ii.size != rp[-1]:
+            raise ValueError(f"{what} must be 1-d arrays of row_ptr[-1] entries")
+        ap = None
+        if a is not None:
+            a = _f32(a)
+            if a.shape != ii.shape:
+                raise ValueError(f"{what} must be 1-d arrays of row_ptr[-1] entries")
+            ap = _p(a, C.c_float)
+        rows = np.empty((n_new, self.k), np.float32)
+        st = np.zeros(n_new, np.int32)
+        self._check(self._lib.mfsgd_fold_in_solve(self._handle(), side, n_new, _p(rp, C.c_int64), _p(ii, C.c_int32), ap,
+                                                  _p(bb, C.c_float), float(alpha), float(ridge), float(ridge_per_entry),
+                                                  _p(rows, C.c_float), _p(st, C.c_int32)))
+        return (rows, st) if status else rows
+
+    def _fold_in_exact(self, side, row_ptr, ids, ratings, lam, weights, status, what):
+        rr = _f32(ratings)
+        a = None
+        if weights is not None:
+            a = _f32(weights)
+            if a.shape != rr.shape:
+                raise ValueError(f"{what} must be 1-d arrays of row_ptr[-1] entries")
+            rr = a * rr  # one fp32 multiply
+        return self._fold_in_solve(side, row_ptr, ids, a, rr, 0.0, 0.0, self.lam if lam is None else lam, status, what)
+
+    def fold_in_exact(self, row_ptr, items, ratings, lam=None, weights=None, status=False):
+        """fold_in() without a learning rate, epochs or start rows: row x is the minimiser of
+        sum_j w_j (r_j - x . q_j)^2 + lam * len * |x|^2 over the user's list -- the fixed point fold_in()'s chain
+        converges to -- found by solving its k x k system on the device (mfsgd_fold_in_solve, bit for bit the rule
+        in include/mfsgd.h).  lam None: the handle's lambda; weights None: all 1.  A user without ratings gets zeros.
+        status=True: (rows, status), status[x] 0 or the 1-based pivot at which the system of row x turned out not
+        positive definite (its row is NaN then).  The model is not modified."""
+        return self._fold_in_exact(0, row_ptr, items, ratings, lam, weights, status, "items, ratings and weights")
+
+    def fold_in_items_exact(self, row_ptr, users, ratings, lam=None, weights=None, status=False):
+        """fold_in_exact() for items that are not in the model, against the model's user factors."""
+        return self._fold_in_exact(1, row_ptr, users, ratings, lam, weights, status, "users, ratings and weights")
+
+    def _fold_in_implicit(self, side, row_ptr, ids, confidence, lam, unobserved, status, what):
+        c = _f32(confidence)
+        return self._fold_in_solve(side, row_ptr, ids, c - np.float32(unobserved), c, unobserved, lam, 0.0, status, what)
+
+    def fold_in_implicit(self, row_ptr, items, confidence, lam, unobserved=1.0, status=False):
+        """Rows for new users of a one-class model (fit_implicit with pos=1, neg=0; fit_ials): the minimiser of
+        sum_observed c_j (1 - x . q_j)^2 + unobserved * sum_rest (x . q)^2 + lam * |x|^2, the implicit-feedback
+        fold-in of Hu, Koren and Volinsky ("recalculate_user" elsewhere).  confidence: c_j of each named item.  The
+        sum over everything unobserved costs one Gram matrix of Q per call.  status as in fold_in_exact()."""
+        return self._fold_in_implicit(0, row_ptr, items, confidence, lam, unobserved, status, "items and confidence")
+
+    def fold_in_items_implicit(self, row_ptr, users, confidence, lam, unobserved=1.0, status=False):
+        """fold_in_implicit() for items that are not in the model, against the model's user factors."""
+        return self._fold_in_implicit(1, row_ptr, users, confidence, lam, unobserved, status, "users and confidence")
+
+    def _als(self, u, i, weights, sweeps, fold_users, fold_items, objective):
+        """The alternation fit_als and fit_ials share: CSR by user and by item in the order given (a stable sort), then
+        per sweep P from every user's list against Q, Q from every item's list against the new P."""
+        uu, ii = _pairs(u, i, "u and i")
+        if not self._initialised:
+            self.init_factors()
+        by_u, by_i = np.argsort(uu, kind="stable"), np.argsort(ii, kind="stable")
+        ptr_u = np.concatenate([[0], np.cumsum(np.bincount(uu, minlength=self.users))]).astype(np.int64)
+        ptr_i = np.concatenate([[0], np.cumsum(np.bincount(ii, minlength=self.items))]).astype(np.int64)
+        P, Q = self.get_factors()
+        out = np.zeros(2 * int(sweeps), np.float64)
+        for s in range(int(sweeps)):
+            for half, (fold, ptr, order, ids) in enumerate(((fold_users, ptr_u, by_u, ii), (fold_items, ptr_i, by_i, uu))):
+                rows, st = fold(ptr, ids[order], weights[order])
+                if st.any():
+                    x = int(np.flatnonzero(st)[0])
+                    raise MfsgdError(-1, f"the system of {'item' if half else 'user'} {x} is not positive definite "
+                                         f"(pivot {int(st[x])}): raise lam")
+                P, Q = (P, rows) if half else (rows, Q)
+                self.set_factors(P, Q)
+                out[2 * s + half] = objective(P, Q)
+        return out
+
+    def fit_als(self, u, i, r, sweeps, lam=None):
+        """Alternating least squares on ratings (ALS-WR): each sweep replaces every row of P by fold_in_exact() of that
+        user's ratings against Q, then every row of Q by fold_in_items_exact() of that item's ratings against the new
+        P.  Inside a list the ratings keep the order given.  Factors that were never initialised are seeded, as in
+        train().  Returns float64[2 * sweeps]: after each half-sweep the objective
+        sum (r - p . q)^2 + lam * sum_u n_u |p_u|^2 + lam * sum_i n_i |q_i|^2, in fp64 on the host.  A user or item
+        without ratings gets a zero row.  MfsgdError when a system is not positive definite."""
+        lam = self.lam if lam is None else float(lam)
+        uu, ii = _pairs(u, i, "u and i")
+        rr = _f32(r)
+        if rr.shape != uu.shape:
+            raise ValueError("u, i and r must be 1-d arrays of the same length")
+        nu, ni = np.bincount(uu, minlength=self.users), np.bincount(ii, minlength=self.items)
+
+        def objective(P, Q):
+            P, Q = P.astype(np.float64), Q.astype(np.float64)
+            e = rr.astype(np.float64) - np.einsum("ij,ij->i", P[uu], Q[ii])
+            return float(e @ e) + lam * float(nu @ (P * P).sum(1)) + lam * float(ni @ (Q * Q).sum(1))
+
+        return self._als(uu, ii, rr, sweeps, lambda ptr, ids, w: self.fold_in_exact(ptr, ids, w, lam, status=True),
+                         lambda ptr, ids, w: self.fold_in_items_exact(ptr, ids, w, lam, status=True), objective)
+
+    def fit_ials(self, u, i, sweeps, confidence=41.0, lam=None, unobserved=1.0):
+        """Alternating least squares on one-class data (iALS, Hu, Koren and Volinsky): fit_als() with fold_in_implicit()
+        and fold_in_items_implicit().  confidence: c of every positive, one number or one per pair.  Returns
+        float64[2 * sweeps]: after each half-sweep
+        sum_j c_j (1 - s_j)^2 + unobserved * (|P Q^T|_F^2 - sum_j s_j^2) + lam * (|P|_F^2 + |Q|_F^2), s_j = p . q of
+        pair j, in fp64 on the host -- what both half-sweeps minimise."""
+        lam = self.lam if lam is None else float(lam)
+        uu, ii = _pairs(u, i, "u and i")
+        cc = np.ascontiguousarray(np.broadcast_to(_f32(confidence), uu.shape))
+        un = float(unobserved)
+
+        def objective(P, Q):
+            P, Q = P.astype(np.float64), Q.astype(np.float64)
+            s = np.einsum("ij,ij->i", P[uu], Q[ii])
+            rest = float(((P.T @ P) * (Q.T @ Q)).sum()) - float(s @ s)
+            return float(cc.astype(np.float64) @ ((1.0 - s) ** 2)) + un * rest + lam * (float((P * P).sum()) + float((Q * Q).sum()))
+
+        return self._als(uu, ii, cc, sweeps, lambda ptr, ids, c: self.fold_in_implicit(ptr, ids, c, lam, un, status=True),
+                         lambda ptr, ids, c: self.fold_in_items_implicit(ptr, ids, c, lam, un, status=True), objective)
+
     def fold_in_pairwise(self, row_ptr, items, epochs, *, candidates=1, init=None, seed=None, draw_seed=0, first=0,
                          margins=False, negatives=False, sampling="uniform"):
         """Rows [n_new, k] for users that are not in a model trained by fit_bpr or fit_warp, from their positives alone
